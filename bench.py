@@ -263,6 +263,31 @@ def load_pmc(B, L, F):
         return {}, f"unavailable: {type(e).__name__}"
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write {name: array} as out_dir/<name>.npy (float32 stays float32, everything else becomes float64).  If the arrays hold more
+    than `budget` bytes, each array above an equal share of it is replaced by a fixed, seeded sample of its flattened entries (the
+    same indices on every run), so two builds can be compared output for output.  Returns {name: what was written}."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float32 if v.dtype == np.float32 else np.float64, copy=False) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    share = budget // max(1, len(arrays))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, v in arrays.items():
+        entry = {"shape": list(v.shape), "dtype": str(v.dtype)}
+        if total > budget and v.nbytes > share:
+            n = share // v.itemsize
+            idx = np.sort(np.random.default_rng(SEED).choice(v.size, size=n, replace=False))
+            v = v.reshape(-1)[idx]
+            entry["sampled"] = {"entries": int(n), "of": int(arrays[name].size), "seed": SEED}
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        written[name] = entry
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -286,13 +311,18 @@ def main():
     ap.add_argument("--extras", default="auto", choices=["auto", "on", "off"],
                     help="SURVEY 8(d)'s further measurements in the same JSON line: the padded variant, the metric path (DeviceEvaluator vs the "
                          "port's CPU loop) and a short window of BASELINE configs 1 / 3 / 4 / 5 (auto: headline workload on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its loss, the loss accumulated over the timed "
+                         "steps, the scorer's parameters and buffers after it) as DIR/<name>.npy; inputs are seeded, so runs with the same "
+                         "arguments compare output for output")
     ap.add_argument("--force-collectives", action="store_true",
                     help="N = 1 only: initialise a one-rank RCCL process group and run the data-parallel step through it (backward -> "
                          "all-reduce -> optimiser step instead of the fused single-device step); what a 1-GPU box can execute of the RCCL path")
     args = ap.parse_args()
 
-    # `python bench.py --gpus N` without a launcher: become the launcher.  One rank per GPU over RCCL, exactly the command line the
-    # module docstring gives; rank 0 of the child job prints the one JSON line.
+    # `python bench.py --gpus N` without a launcher: run the launcher as a child process and pass on its exit status (this process has
+    # already asked HIP for the device count, so it is not replaced).  One rank per GPU over RCCL, exactly the command line the module
+    # docstring gives; rank 0 of the child job prints the one JSON line.
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         if torch.cuda.device_count() < args.gpus:
             raise SystemExit(f"bench.py --gpus {args.gpus}: this node exposes {torch.cuda.device_count()} GPU(s); one rank per GPU is required")
@@ -303,7 +333,8 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        import subprocess
+        raise SystemExit(subprocess.call(cmd))
     # stdout carries exactly ONE line, the JSON: RCCL prints a version banner to stdout when a process group is torn down, so from here on
     # file descriptor 1 of every rank points at stderr and the JSON goes to a private duplicate of the original stdout
     json_out = os.fdopen(os.dup(1), "w")
@@ -383,6 +414,7 @@ def main():
             hooks = (entry-point timings, all-reduce timings): HIP-event brackets around every C-ABI call of every EVENT_EVERY-th
             step (two events per call are not free: at 64 queries per step they would be a fifth of the step)."""
             acc = torch.zeros((), device=device)
+            loss = None
             for i in range(n):
                 X, Y, ln = batches[i % len(batches)]
                 on = hooks is not None and i % EVENT_EVERY == 0
@@ -395,6 +427,7 @@ def main():
                 if on:
                     _lib.TIMING, dp.TIMING = None, None
                 acc += loss.detach()
+            measure.last_loss = loss          # what train_op handed back on the last step (for --dump-outputs)
             return acc
 
         # Untimed pre-warm with EXACTLY the code of the timed region (event hooks included): the first launch of every kernel
@@ -425,6 +458,14 @@ def main():
 
     ranker = build_ranker()
     elapsed, timing, ar_timing, final_loss = measure(ranker, B, args.steps, args.warmup, 5)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the contract window's outputs, before any further window trains the same ranker on
+        parts = ranker.list_sf if ranker.sf_id == "listsf" else {"": ranker.point_sf}      # listsf: a dict of modules (host.ini_listsf)
+        arrays = {"loss": measure.last_loss.detach().cpu().numpy(), "epoch_loss": np.float64(final_loss)}
+        for part, mod in parts.items():
+            arrays.update({".".join(x for x in ("scorer", part, k) if x): v.detach().cpu().numpy() for k, v in mod.state_dict().items()})
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, arrays)}
     single_call = bool(getattr(ranker, "single_call_step", False)) and "desc" in next(iter(ranker.__dict__.get("_direct_buffers", {"": {}}).values()))
     # The contract's window is the one above (`steps`, `ms_per_step`, `value`).  It is tens of ms long, so its spread is reported too:
     # args.windows - 1 further windows of the same K steps, each bracketed the same way
@@ -719,6 +760,8 @@ def main():
             "pmc_traffic_source": pmc_source,
             "parallel": parallel_facts,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if "1024" in by_batch:     # SURVEY 8(d)'s headline batch, next to `value` (measured at --batch queries per GPU)
             out["value_at_1024"] = by_batch["1024"]["queries_per_s_per_gpu"]
             out["ms_per_step_at_1024"] = by_batch["1024"]["ms_per_step"]

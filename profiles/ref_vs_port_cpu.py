@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The reference ITSELF (wildltr/ptranking imported read-only from /root/reference) timed beside the oracle's torch-CPU port of its
+"""The reference ITSELF (wildltr/ptranking imported read-only from $PTRANKING_REF, default /root/reference) timed beside the oracle's torch-CPU port of its
 train step, same process, same synthetic MSLR-shaped batches, same thread count — run in the BUILD container (the reference cannot
 travel to the GPU box).  Shows that bench.py's `cpu_baseline` (kind "port") is timing-faithful to the reference's train_op
 (ptranking/base/ranker.py:589-603 followed by loss.item(), :579-584).  Writes profiles/r06_reference_vs_port_cpu.json.
@@ -15,7 +15,7 @@ os.environ.setdefault("PYTHONDONTWRITEBYTECODE", "1")
 sys.dont_write_bytecode = True
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, "/root/reference")
+sys.path.insert(0, os.environ.get("PTRANKING_REF") or "/root/reference")          # a wildltr/ptranking checkout
 
 import numpy as np
 import torch
@@ -75,7 +75,7 @@ def main():
         rows[f"B{B}"] = {"reference_queries_per_s": r_q, "reference_steps": r_it, "port_queries_per_s": p_q, "port_steps": p_it,
                          "port_over_reference": p_q / r_q}
         print(B, rows[f"B{B}"], flush=True)
-    doc = {"note": "wildltr/ptranking's own LambdaRank.train_op + loss.item() (imported from /root/reference) vs oracle/torch_ref.cpu_train_step "
+    doc = {"note": "wildltr/ptranking's own LambdaRank.train_op + loss.item() (imported from a reference checkout) vs oracle/torch_ref.cpu_train_step "
                    "(the `cpu_baseline` port of bench.py), same batches (MSLR-shaped synthetic, 128 docs x 136 feats), same process, build container",
            "host": {"threads": threads, "nproc": os.cpu_count(), "torch": torch.__version__},
            "rows": rows}

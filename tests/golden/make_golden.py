@@ -5,7 +5,7 @@ Run here (the build container), never on the GPU box:
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
 
-It imports wildltr/ptranking read-only from /root/reference, feeds seeded synthetic
+It imports wildltr/ptranking read-only from $PTRANKING_REF, default /root/reference, feeds seeded synthetic
 batches through the reference's own loss classes / metric functions on CPU and stores
 inputs + outputs as small .npz files.  The reference cannot travel to the GPU box, the
 fixtures do: every parity test (oracle vs golden on CPU, HIP vs golden on the GPU)
@@ -33,9 +33,9 @@ import sys
 
 os.environ.setdefault("PYTHONDONTWRITEBYTECODE", "1")
 sys.dont_write_bytecode = True
-REF = "/root/reference"
+REF = os.environ.get("PTRANKING_REF") or "/root/reference"         # a wildltr/ptranking checkout
 if not os.path.isdir(REF):
-    raise SystemExit("the reference tree is only mounted in the build container")
+    raise SystemExit(f"no wildltr/ptranking checkout at {REF} (set PTRANKING_REF)")
 sys.path.insert(0, REF)
 
 import numpy as np

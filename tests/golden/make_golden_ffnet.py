@@ -17,9 +17,9 @@ import sys
 
 os.environ.setdefault("PYTHONDONTWRITEBYTECODE", "1")
 sys.dont_write_bytecode = True
-REF = "/root/reference"
+REF = os.environ.get("PTRANKING_REF") or "/root/reference"         # a wildltr/ptranking checkout
 if not os.path.isdir(REF):
-    raise SystemExit("the reference tree is only mounted in the build container")
+    raise SystemExit(f"no wildltr/ptranking checkout at {REF} (set PTRANKING_REF)")
 sys.path.insert(0, REF)
 
 import numpy as np  # noqa: E402

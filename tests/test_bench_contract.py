@@ -23,12 +23,33 @@ def test_bench_cli_and_cpu_baseline_helpers():
     assert cb["kind"] == "port" and cb["unit"] == "queries/s" and cb["value"] > 0 and cb["cores"] >= 1 and "sample" in cb
 
 
+def test_dump_outputs_writes_float_arrays_and_samples_over_budget(tmp_path):
+    """CPU: bench.dump_outputs keeps float32 as float32, widens the rest to float64, and above its byte budget stores the same seeded
+    sample of a large array on every call."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    big = np.arange(4096, dtype=np.float32)
+    arrays = {"loss": np.float32(1.5), "epoch_loss": 3.25, "count": np.int64(7), "w": big}
+    w1 = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert set(w1) == set(arrays) and not any("sampled" in e for e in w1.values())
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float32 and np.load(tmp_path / "a" / "count.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "a" / "w.npy"), big)
+    w2 = bench.dump_outputs(str(tmp_path / "b"), arrays, budget=4096)
+    w3 = bench.dump_outputs(str(tmp_path / "c"), arrays, budget=4096)
+    assert w2 == w3 and w2["w"]["sampled"]["of"] == 4096 and "sampled" not in w2["loss"]
+    sb, sc = np.load(tmp_path / "b" / "w.npy"), np.load(tmp_path / "c" / "w.npy")
+    assert np.array_equal(sb, sc) and sb.size == w2["w"]["sampled"]["entries"] and sum(
+        np.load(f).nbytes for f in (tmp_path / "b").glob("*.npy")) <= 4096
+    assert np.all(np.diff(sb) > 0) and set(sb.tolist()) <= set(big.tolist())
+
+
 @pytest.mark.gpu
-def test_bench_prints_one_contract_json_line():
+def test_bench_prints_one_contract_json_line(tmp_path):
     env = dict(os.environ)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "256",
-                          "--sweep", "64", "--sweep-steps", "6", "--cpu-seconds", "0.5", "--extras", "on"], capture_output=True, text=True, timeout=900,
-                         env=env, cwd=ROOT)
+                          "--sweep", "64", "--sweep-steps", "6", "--cpu-seconds", "0.5", "--extras", "on", "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -68,6 +89,14 @@ def test_bench_prints_one_contract_json_line():
                 else:
                     yield from fracs(v)
     assert all(0.0 <= f <= 1.0 for f in fracs(d)), list(fracs(d))
+    # --dump-outputs: the last timed step's loss, the timed steps' accumulated loss and the scorer's state after them
+    import numpy as np
+    dumped = d["dump_outputs"]["arrays"]
+    assert {"loss", "epoch_loss", "scorer.ff_2.weight"} <= set(dumped)
+    for name in dumped:
+        a = np.load(tmp_path / "out" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+    assert abs(float(np.load(tmp_path / "out" / "epoch_loss.npy")) - d["final_epoch_loss"]) <= 1e-9 * abs(d["final_epoch_loss"])
 
 
 def test_one_set_of_issue_constants():

@@ -1,6 +1,6 @@
 """CPU: the pointsf modules this package builds (host.build_pointsf: the reference's module names, LTRBatchNorm / LTRBatchNorm2
 mirrors) reproduce the REFERENCE's own get_stacked_FFNet — outputs and autograd gradients recorded by
-tests/golden/make_golden_ffnet.py from /root/reference (ptranking/base/utils.py:288-356).  This pins the torch-module side that
+tests/golden/make_golden_ffnet.py from the reference (ptranking/base/utils.py:288-356).  This pins the torch-module side that
 tests/test_stack_gpu.py and tests/test_scorer_gpu.py compare the HIP kernels against."""
 import os
 
