@@ -69,9 +69,7 @@ __device__ __forceinline__ float af_bwd(int af, float y) {
     }
 }
 
-#ifndef PTR_BN_BWD_ROWS
-#define PTR_BN_BWD_ROWS 2
-#endif
+constexpr int kBnBwdRows = 2;      // independent rows in flight per thread of colsum2_kernel's backward sums (r6, reasons there)
 
 struct BnActArgs {
     int group;                   // rows per statistics group: 0 = one group (LTRBatchNorm, the whole batch), L = per query (LTRBatchNorm2)
@@ -179,7 +177,7 @@ colsum2_kernel(const float *__restrict__ z, const float *__restrict__ da, const 
             // independent rows in flight: four for the statistics; TWO for the backward sums (r6) — with four, AF'(y) and the dropout hash of four float4 pairs need
             // 130 registers = three waves per SIMD, and a wave issues one instruction per ~5 cycles whatever its instruction-level parallelism (scratch/valu_rate):
             // 66 registers = seven waves per SIMD hide the loads AND issue faster
-            constexpr int UR = MODE == 1 ? PTR_BN_BWD_ROWS : 4;
+            constexpr int UR = MODE == 1 ? kBnBwdRows : 4;
             for (; r + (UR - 1) * rsub < r_end; r += UR * rsub) {
                 vec zv[UR], dv[UR];
 #pragma unroll

@@ -588,10 +588,7 @@ extern "C" int ptr_linear_backward_weight(const float *X, int ldx, const float *
     bw_tiling(K, N, MTO, NTW);
     const int nnb = (N + 16 * MTO - 1) / (16 * MTO), nkb = (K + 64 * NTW - 1) / (64 * NTW);
     const int chunks = bw_chunks(R, K, N);
-#ifndef LIN_BW_RB
-#define LIN_BW_RB 16
-#endif
-    constexpr int RB = LIN_BW_RB;
+    constexpr int RB = 16;                       // rows per double-buffered LDS block
     auto go = [&](auto kern, int mto, int ntw) -> int {
         const size_t lds = (size_t)(2 * RB * (16 * mto + 16) + 2 * RB * (64 * ntw + 16)) * sizeof(float);
         if (int e = allow_lds(kern, lds)) return e;

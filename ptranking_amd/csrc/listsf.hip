@@ -30,12 +30,8 @@ constexpr int kRC = 32;                // rows per LDS chunk (dK / dV)
 constexpr int kDsPadLd = 20;           // row stride (floats) of the dS transpose pad: 16-byte aligned rows, 80 B = 20 banks apart
 // workgroups per CU the attention kernels are compiled for (register budget): the backward kernels gain 4 % from a third wave per
 // SIMD (<= 168 VGPRs), the forward loses 10 % (measured at 1024 x 256 x 136, 2 heads: scratch/exp_attn.py)
-#ifndef PTR_ATTN_MINBLK_FWD
-#define PTR_ATTN_MINBLK_FWD 2
-#endif
-#ifndef PTR_ATTN_MINBLK_BWD
-#define PTR_ATTN_MINBLK_BWD (DT <= 5 ? 3 : 2)      // head dimensions above 80 would spill 80-170 registers at 168
-#endif
+constexpr int kAttnMinBlkFwd = 2;
+constexpr int attn_minblk_bwd(int DT) { return DT <= 5 ? 3 : 2; }     // head dimensions above 80 would spill 80-170 registers at 168
 
 struct AttnArgs {
     int B, L, H, dh, F;
@@ -186,7 +182,7 @@ __device__ __forceinline__ float xor_sum(float v) {
 
 // ============================================================================================ forward
 template <int DT, int RT, int NW>
-__global__ void __launch_bounds__(NW * 64, PTR_ATTN_MINBLK_FWD)
+__global__ void __launch_bounds__(NW * 64, kAttnMinBlkFwd)
 mhsa_fwd_kernel(const float *__restrict__ Q, const float *__restrict__ K, const float *__restrict__ V,
                 const int32_t *__restrict__ lens, AttnArgs a, float *__restrict__ O, float *__restrict__ LSE) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -325,7 +321,7 @@ attn_rowdot_kernel(const float *__restrict__ O, const float *__restrict__ dO, At
 
 // ============================================================================================ backward: dQ
 template <int DT, int NW>
-__global__ void __launch_bounds__(NW * 64, PTR_ATTN_MINBLK_BWD)
+__global__ void __launch_bounds__(NW * 64, attn_minblk_bwd(DT))
 mhsa_bwd_dq_kernel(const float *__restrict__ Q, const float *__restrict__ K, const float *__restrict__ V,
                    const float *__restrict__ dO, const float *__restrict__ LSE, const float *__restrict__ Dv,
                    const int32_t *__restrict__ lens, AttnArgs a, float *__restrict__ dQ) {
@@ -422,7 +418,7 @@ mhsa_bwd_dq_kernel(const float *__restrict__ Q, const float *__restrict__ K, con
 // dS[row][kc + 16 kt + 4 g ..] — the B operand layout directly.  Keys >= n (padding; columns a non-live key block never wrote) are
 // SELECTED to zero, not multiplied.
 template <int DT, int NW>
-__global__ void __launch_bounds__(NW * 64, PTR_ATTN_MINBLK_BWD)
+__global__ void __launch_bounds__(NW * 64, attn_minblk_bwd(DT))
 mhsa_bwd_dq_ds_kernel(const float *__restrict__ K, const float *__restrict__ dS_ws, const int32_t *__restrict__ lens, AttnArgs a,
                       float *__restrict__ dQ) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -496,7 +492,7 @@ mhsa_bwd_dq_ds_kernel(const float *__restrict__ K, const float *__restrict__ dS_
 // STORE_DS: the variant that also hands the scaled dS to mhsa_bwd_dq_ds_kernel; compiled for two workgroups per CU (the transpose of the
 // dS tiles does not fit the 168 registers of three: 49 spills, +280 us per launch at config 5)
 template <int DT, int NW, bool STORE_DS>
-__global__ void __launch_bounds__(NW * 64, STORE_DS ? 2 : PTR_ATTN_MINBLK_BWD)
+__global__ void __launch_bounds__(NW * 64, STORE_DS ? 2 : attn_minblk_bwd(DT))
 mhsa_bwd_dkv_kernel(const float *__restrict__ Q, const float *__restrict__ K, const float *__restrict__ V,
                     const float *__restrict__ dO, const float *__restrict__ LSE, const float *__restrict__ Dv,
                     const int32_t *__restrict__ lens, AttnArgs a, float *__restrict__ dK, float *__restrict__ dV,

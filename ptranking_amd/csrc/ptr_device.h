@@ -425,11 +425,8 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
-#ifndef PTR_RING_DPP
-#define PTR_RING_DPP 0x134
-#endif
 __device__ __forceinline__ float dpp_rol1(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), PTR_RING_DPP /* wave_rol:1 */, 0xF, 0xF, false));
+    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x134 /* wave_rol:1 */, 0xF, 0xF, false));
 }
 
 

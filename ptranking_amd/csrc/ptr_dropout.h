@@ -16,20 +16,15 @@ constexpr uint32_t kDropRowMul = 0x9E3779B1u, kDropFgMul = 0x85EBCA77u, kDropSit
 // the key in a register and add a scalar per feature group — scorer_x6.hip — enter here)
 __device__ __forceinline__ void drop_bits_key(uint32_t ks, uint32_t seed_hi, uint32_t &w0, uint32_t &w1) {
     w0 = lowbias32(ks);
-#ifdef PTR_DROP_FULL_HASH
-    w1 = lowbias32(w0 ^ seed_hi ^ 0x68E31DA4u);
-#else
     uint32_t t = w0 ^ seed_hi ^ 0x68E31DA4u;
     t ^= t >> 15; t *= 0x2C1B3C6Du; t ^= t >> 13;
     w1 = t;
-#endif
 }
 // 64 random bits for features [4*fg, 4*fg+3] of `row` at dropout site `site` (site l = the Dropout in front of hidden layer l)
 __device__ __forceinline__ void drop_bits(uint32_t seed_lo, uint32_t seed_hi, int site, int row, int fg, uint32_t &w0, uint32_t &w1) {
     // A VALU instruction takes its cycles away from the matrix pipe of its SIMD (no MFMA / VALU overlap: scratch/clock), and 32-bit
     // integer multiplies are quarter rate on CDNA: the row term is loop invariant for a lane (hoisted by the compiler), the
     // first word gets the full two-multiply finaliser, the second word one more multiply-xorshift round on top of it
-    // (PTR_DROP_FULL_HASH restores the round-1 generator: a second full finaliser)
     // seed_lo enters ADDITIVELY: a replica that owns rows [row0, row0 + n) of a global batch passes seed_lo + row0 * 0x9E3779B1 and draws
     // exactly the masks the single-device run draws for those rows (ptranking_amd/dp.py fold_row_offset) — data-parallel replicas never
     // share masks, and N ranks x B/N queries reproduce one rank x B

@@ -17,7 +17,7 @@ constexpr int kAL = 112;         // floats per row of the stored activations / l
 // r5: the stored activations are TILE-MAJOR: [layer][row tile of 16][feature tile of 16 (7 of them)][row in tile][feature in tile] — every
 // (16 rows x 16 features) block is ONE contiguous KB, the unit a forward store instruction writes (lane (j, g) = row j, features 4g..4g+3 of
 // the tile: 64 lanes x 16 B back to back) and an LDS-DMA piece of the backward reads.  Row-major rows (448 B) made every store instruction
-// touch sixteen 64-byte pieces in sixteen different rows (bf16x6 training forward 375 -> 349 us at 524 288 x 136, scratch/r5_call1.sh).
+// touch sixteen 64-byte pieces in sixteen different rows (bf16x6 training forward 375 -> 349 us at 524 288 x 136, scratch/r5_call1.sh, in git history).
 // A layer holds ceil(R / 16) whole row tiles: rows past R of the last tile are written (finite values) and never contribute (their
 // dLoss/dscore is 0).  The dZ scratch of the layer-wise backward stays row-major [R][112].
 constexpr int kActTile = 16 * kAL;                                   // floats of one row tile (7 KB)

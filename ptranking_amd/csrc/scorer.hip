@@ -25,9 +25,6 @@
 
 namespace ptr {
 
-#ifndef DW_U
-#define DW_U 4
-#endif
 __host__ __device__ inline int ld_w1(int F) { return (F + 3) / 4 * 4 + 4; }   // LDS leading dimension of W1 (bank spread)
 
 
@@ -179,11 +176,7 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
         }
     };
     f32x4 xpre[RT];
-#ifndef PTR_FWD_STATIC_TILES
     constexpr bool kQueue = W1G != 2;
-#else
-    constexpr bool kQueue = false;
-#endif
     // dynamic tile queue per workgroup: the two waves of a SIMD do not progress at the same rate (the older one wins the issue
     // arbitration: 90 K vs 145 K cycles per tile measured) — with a static split the faster half idles at the end.
     // Slab mode (W1G == 2): the waves of a workgroup share the W1 slabs and walk their tiles in LOCKSTEP (one barrier per slab), so a
@@ -253,11 +246,7 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
             rok[rt] = row[rt] < R;
-#ifdef PTR_FWD_XL2      // experiment: the same loads from an L2-resident part of X
-            xrow[rt] = X + (size_t)((rok[rt] ? row[rt] : R - 1) & 4095) * F;
-#else
             xrow[rt] = X + (size_t)(rok[rt] ? row[rt] : R - 1) * F;
-#endif
         }
         // load_raw only issues the loads; finish_x (zero padding + input dropout) runs AFTER the MFMAs of the super-step the
         // loads are prefetched under — anything consuming the loaded value earlier would pull the s_waitcnt in front of them.
@@ -334,20 +323,14 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
         // One super-step of a layer: acc[mt] += A fragment wa[mt] (k-steps c < nc) x B fragment b.  Tiles go in groups of two / three with the
         // k-step outermost inside a group: consecutive MFMAs write DIFFERENT accumulators (a dependent v_mfma_f32_16x16x4_f32 issues after 40
         // cycles, an independent one after 32; the 4x4 form of tile 6 needs an s_nop between dependent k-steps) while a group's fragments
-        // die with it (k-step outermost over all seven tiles keeps 28 fragment registers live and spills in the 16-wave form).
+        // die with it (k-step outermost over all seven tiles keeps 28 fragment registers live and spills in the 16-wave form).  Against the
+        // round-2 order (tile outermost): 352 -> 340 us, DESIGN.md §3.2 "r3: MFMA order inside a super-step".
         auto mma_tiles = [&](const f32x4 (&wa)[kMT], const f32x4 (&b)[RT], int nc) {
             auto one = [&]<int MT>(std::integral_constant<int, MT> mt_, int c) {
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) acc[MT][rt] = mma(mt_, wa[MT][c], b[rt][c], acc[MT][rt]);
             };
             using std::integral_constant;
-#ifdef PTR_FWD_MT_OUTER     // experiment builds: the round-2 order (tile outermost, its four k-steps back to back)
-            static_for<kMT>([&](auto mt_) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) if (c < nc) one(mt_, c);
-            });
-            return;
-#endif
 #pragma unroll
             for (int c = 0; c < 4; ++c) if (c < nc) { one(integral_constant<int, 0>{}, c); one(integral_constant<int, 1>{}, c); }
 #pragma unroll
@@ -470,7 +453,6 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
 #pragma unroll
                     for (int c = 0; c < 4; ++c) h[c] = fmaxf(h[c], 0.0f);
                     if constexpr (TRAIN) {
-#ifndef PTR_FWD_NOHASH
                         if (mt < kMT - 1) {
                             uint32_t w0, w1;
                             drop_bits(a.seed_lo, a.seed_hi, l, row[rt], 4 * mt + g, w0, w1);
@@ -478,7 +460,6 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
                         } else {                                 // tile 6: element 0 is feature 96 + g
                             h[0] *= drop_keep1(a.seed_lo, a.seed_hi, l, row[rt], 96 + g, thr) ? scale : 0.0f;
                         }
-#endif
                     }
                     hin[mt][rt] = h;
                 }
@@ -505,16 +486,8 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt) {
                         if (row[rt] < R16) {            // whole row tiles (tile-major `acts`, ptr_mlp.h): rows past R hold finite values nobody uses
-#if defined(PTR_FWD_L2STORE)     // experiment: same store instructions, L2-resident target
-                            float *arow = acts + (size_t)(l - 1) * act_layer_floats(R) + act_off(row[rt] & 4095, 0);
-#else
                             float *arow = acts + (size_t)(l - 1) * act_layer_floats(R) + act_off(row[rt], 0);
-#endif
-#if !defined(PTR_FWD_NOSTORE)
                             *reinterpret_cast<f32x4 *>(arow + 256 * S + 4 * g) = S < kLast ? hin[S][rt] : tail_store(hin[S][rt][0], 1.0f);
-#else
-                            if (hin[S][rt][0] == 123.456f) acts[0] = 1.0f;
-#endif
                         }
                     }
                     if constexpr (RT > 1) __builtin_amdgcn_sched_barrier(0);
@@ -539,16 +512,8 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
                 for (int c = 0; c < (mt == kMT - 1 ? 1 : 4); ++c) { h[c] = fmaxf(h[c], 0.0f); sc[rt] = fmaf(h[c], w4[c], sc[rt]); }
                 if constexpr (TRAIN) {
                     if (row[rt] < R16) {
-#if defined(PTR_FWD_L2STORE)
-                        float *arow = acts + (size_t)(NL - 1) * act_layer_floats(R) + act_off(row[rt] & 4095, 0);
-#else
                         float *arow = acts + (size_t)(NL - 1) * act_layer_floats(R) + act_off(row[rt], 0);
-#endif
-#if defined(PTR_FWD_NOSTORE)
-                        if (h[0] == 123.456f) acts[1] = 1.0f;
-#else
                         *reinterpret_cast<f32x4 *>(arow + 256 * mt + 4 * g) = mt < kMT - 1 ? h : tail_store(h[0], 0.0f);
-#endif
                     }
                 }
             }
@@ -735,7 +700,8 @@ mlp_bwd_dw_kernel(const float *__restrict__ A, int lda, const float *__restrict_
                   float *__restrict__ ws, size_t np_stride, size_t w_off, size_t b_off) {
     const int R = a.R;
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, wave = tid >> 6;
-    const int chunk = ((R + gridDim.x - 1) / gridDim.x + 4 * DW_U - 1) / (4 * DW_U) * (4 * DW_U);
+    constexpr int U = 4;                                   // k-steps (of 4 rows) per iteration (prefetch depth)
+    const int chunk = ((R + gridDim.x - 1) / gridDim.x + 4 * U - 1) / (4 * U) * (4 * U);
     const int r_begin = blockIdx.x * chunk, r_end = min(R, r_begin + chunk);
     const uint32_t thr = drop_thr(a.p_drop);
     const float scale = (SITE0 && a.p_drop > 0.0f) ? 1.0f / (1.0f - a.p_drop) : 1.0f;
@@ -751,7 +717,6 @@ mlp_bwd_dw_kernel(const float *__restrict__ A, int lda, const float *__restrict_
 #pragma unroll
     for (int mt = 0; mt < kMT; ++mt) dbv[mt] = 0.0f;
 
-    constexpr int U = DW_U;                                // k-steps (of 4 rows) per iteration (prefetch depth)
     // Per-lane column offsets / validity are loop invariant; loads are branch-free (clamped column, select-to-zero).
     int fa[kMT], kb[NTW];
     bool fa_ok[kMT], kb_ok[NTW];

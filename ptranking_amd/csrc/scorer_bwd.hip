@@ -34,30 +34,16 @@
 namespace ptr {
 
 constexpr int kSR = 32;            // rows per slab
-#ifndef BWD_WAVES
-#define BWD_WAVES 8
-#endif
-// waves per workgroup: 8 (2 per SIMD, <= 256 VGPRs; the kernel uses 245).  -DBWD_WAVES=12 builds the three-waves-per-SIMD form (waves 8..11
-// multiply dW tiles only, <= 168 VGPRs) — measured r3: the chain waves (50 W^T fragment registers + chain operands + accumulators) do not
-// fit, 140 registers spill; an experiment switch, not a product path.
-constexpr int kBW = BWD_WAVES;
+// waves per workgroup: 8 (2 per SIMD, <= 256 VGPRs; the kernel uses 245).  A three-waves-per-SIMD form (12 waves, waves 8..11 multiplying
+// dW tiles only, <= 168 VGPRs) was measured in r3: the chain waves (50 W^T fragment registers + chain operands + accumulators) do not fit,
+// 140 registers spill.
+constexpr int kBW = 8;
 constexpr int kBT = kBW * 64;
 constexpr int kSlabF = kSR * kAL;  // floats of one activation / dZ image
 // The short VALU / LDS / VMEM bursts that prepare the next slab run at raised wave priority: beside a partner wave that streams
 // MFMAs they otherwise only get the issue slots the stream leaves over (measured 4x slower than alone).
-#ifndef BWD_PREP_PRIO
-#define BWD_PREP_PRIO 1
-#endif
-#if BWD_PREP_PRIO
 #define PREP_BEGIN() __builtin_amdgcn_s_setprio(2)
 #define PREP_END() __builtin_amdgcn_s_setprio(0)
-#else
-#define PREP_BEGIN() do { } while (0)
-#define PREP_END() do { } while (0)
-#endif
-#ifndef BWD_KS_UNROLL
-#define BWD_KS_UNROLL 2            // unroll of the dW k-step loop (register pressure vs load batching)
-#endif
 
 __host__ __device__ constexpr int ldx_of(int NT1) { return (NT1 & 1) ? 16 * NT1 : 16 * NT1 + 16; }   // = 16 (mod 32)
 __host__ __device__ constexpr size_t bwd_fused_lds_floats(int NL, int NT1) {
@@ -322,11 +308,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ X, const floa
             int xr, xc;
             const bool in = x_slot(tid_o, u, xr, xc);
             uint32_t w0, w1;
-#ifdef BWD_NO_HASH                                                       // timing experiment only (wrong masks)
-            w0 = w1 = 0xFFFFFFFFu;
-#else
             drop_bits(a.seed_lo, a.seed_hi, 0, min(row0 + xr, R - 1), xc, w0, w1);
-#endif
             f32x4 v = drop4(xraw[u], w0, w1, thr_e, inv_keep);
             const float okf = 4 * xc < F ? 1.0f : 0.0f;
 #pragma unroll
@@ -653,15 +635,7 @@ mlp_bwd_fused_kernel(const float *__restrict__ X, const float *__restrict__ P, c
         case 4: bwd_body<NL, NT1, 4>(X, P, acts, dpreds, a, ws, np_stride, smem, dz0); break;
         case 5: bwd_body<NL, NT1, 5>(X, P, acts, dpreds, a, ws, np_stride, smem, dz0); break;
         case 6: bwd_body<NL, NT1, 6>(X, P, acts, dpreds, a, ws, np_stride, smem, dz0); break;
-#if BWD_WAVES == 12
-        case 7: bwd_body<NL, NT1, 7>(X, P, acts, dpreds, a, ws, np_stride, smem, dz0); break;
-        case 8: bwd_body<NL, NT1, 8>(X, P, acts, dpreds, a, ws, np_stride, smem, dz0); break;
-        case 9: bwd_body<NL, NT1, 9>(X, P, acts, dpreds, a, ws, np_stride, smem, dz0); break;
-        case 10: bwd_body<NL, NT1, 10>(X, P, acts, dpreds, a, ws, np_stride, smem, dz0); break;
-        default: bwd_body<NL, NT1, 11>(X, P, acts, dpreds, a, ws, np_stride, smem, dz0); break;
-#else
         default: bwd_body<NL, NT1, 7>(X, P, acts, dpreds, a, ws, np_stride, smem, dz0); break;
-#endif
     }
 }
 

@@ -75,12 +75,8 @@ __device__ __forceinline__ void b6_bdma16(b6_srd srd, uint32_t voff, uint32_t so
 // four consecutive features of one document -> the three planes of an image (8 bytes each)
 __device__ __forceinline__ void b6_write4(uint32_t addr, int plane_bytes, const f32x4 v) {
     uint32_t a[3], b[3];
-#ifdef PTR_B6_ABL_NOVALU     // timing-only ablation (wrong results): no splitting
-    a[0] = a[1] = a[2] = __float_as_uint(v[0]); b[0] = b[1] = b[2] = __float_as_uint(v[2]);
-#else
     b6_split2(v[0], v[1], a[0], a[1], a[2]);
     b6_split2(v[2], v[3], b[0], b[1], b[2]);
-#endif
 #pragma unroll
     for (int p = 0; p < 3; ++p) *reinterpret_cast<lds_u32x2_b *>((uintptr_t)(addr + (uint32_t)(p * plane_bytes))) = u32x2{a[p], b[p]};
 }
@@ -89,51 +85,8 @@ __device__ __forceinline__ void b6_barrier() { asm volatile("s_waitcnt lgkmcnt(0
 // A scalar the compiler cannot fold: image bases go through this INSIDE the slab loop, or hipcc precomputes one address register per (image,
 // plane, tile) combination — the images lie past the 64 KB ds offset range — hoists the dozens of them out of the loop and spills them
 __device__ __forceinline__ uint32_t b6_opaque(uint32_t x) { asm volatile("" : "+s"(x)); return x; }
-#ifndef PTR_B6_DMA_CHAIN_ONLY
-#define PTR_B6_DMA_CHAIN_ONLY 1
-#endif
-#ifndef PTR_B6_PREFETCH_LATE
-#define PTR_B6_PREFETCH_LATE 1        /* 1: the next-next slab's DMA is issued at the end of the chain-3 phase instead of right behind B4 */
-#endif
-#ifndef PTR_B6_PIPE_W7
-#define PTR_B6_PIPE_W7 1
-#endif
-#ifndef PTR_B6_PIPE_C2
-#define PTR_B6_PIPE_C2 0
-#endif
-#ifndef PTR_B6_PRIO
-#define PTR_B6_PRIO 0
-#endif
-#ifndef PTR_B6_X_PHASE
-#define PTR_B6_X_PHASE 1              /* chain phase (0 / 1) in which X is loaded and turned into its plane image */
-#endif
-#ifndef PTR_B6_SWZ
-#define PTR_B6_SWZ 1
-#endif
-#ifndef PTR_B6_STAGE_ORDER
-#define PTR_B6_STAGE_ORDER 0
-#endif
-#ifndef PTR_B6_TAILPRE
-#define PTR_B6_TAILPRE 1              /* r6: the chain's 16-deep tail operands are read beside the last full slice's MFMAs (in the registers the B-fragment prefetch no longer needs) */
-#endif
-#ifndef PTR_B6_CHAIN_ORDER
-#define PTR_B6_CHAIN_ORDER 0
-#endif
-#ifndef PTR_B6_EPI_MIX
-#define PTR_B6_EPI_MIX 0              /* r6 experiment: the chain's epilogue (gating, split, image stores) issued BETWEEN the dW row's MFMAs (2-3 VALU per MFMA) instead of in front of them */
-#endif
-#ifndef PTR_B6_EPI_K
-#define PTR_B6_EPI_K 3
-#endif
-#ifndef PTR_B6_W7_ILV
-#define PTR_B6_W7_ILV 0               /* experiment: wave 7's two tiles of a row as one interleaved stream (no back-to-back MFMAs on one accumulator) */
-#endif
-#ifndef PTR_B6_W7_DEPTH
-#define PTR_B6_W7_DEPTH 2             /* experiment: dZ tiles in flight for wave 7 (2 = one row ahead, 3 = two rows ahead) */
-#endif
-#ifndef PTR_B6_W7HOLD
-#define PTR_B6_W7HOLD 1               /* r6: wave 7 keeps the in-tile fragments its rows share in registers for the phase and streams only the dZ tiles */
-#endif
+// r6 measured and did not keep: wave 7's two accumulators interleaved, the complementary chain / dW order of the two waves of a SIMD, the
+// chain's epilogue between the dW MFMAs and both document tiles' staging reads up front ("Candidates measured this round")
 #define B6_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16((A).v, (B).v, (C), 0, 0, 0)
 
 template <int NT1>
@@ -223,20 +176,12 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     // store (ds_write_b64: 16 consecutive lanes = the 16 rows of one chunk column, 224-byte stride = 4 distinct bank pairs) is 2-way instead of 4-way
     // conflicted (SQ counters, r5: 45 % of this kernel's LDS cycles were conflict cycles), and every reader follows with a per-lane constant: the chain's
     // ds_read_b128 takes the other 16-byte half on the swizzled rows (still conflict-free), a transpose read permutes its four chunks per lane group.
-#if PTR_B6_SWZ
     const uint32_t swz = (uint32_t)((j >> 2) & 1);
     const uint32_t wr_z = (uint32_t)(j * kB6ZRS) + 8u * ((uint32_t)g ^ (2u * swz));        // + 16 dt rows, + 32 tile bytes: this lane's 8 bytes of a 112-column image row
     const uint32_t wr_x = (uint32_t)(j * kB6XRS) + 8u * ((uint32_t)g ^ (2u * swz));
     const uint32_t rd_b = (uint32_t)(j * kB6ZRS + 32 * (g >> 1)) + 16u * (((uint32_t)g & 1u) ^ swz);       // chain B fragment: document j, 8 features from 32 s + 8 g
     const uint32_t tr_z = (uint32_t)((4 * g + (j >> 2)) * kB6ZRS) + 8u * (((uint32_t)j & 3u) ^ (2u * ((uint32_t)g & 1u)));     // transpose-read chunk of a 112-column image (row 4 g + (j >> 2): its swizzle bit is g & 1)
     const uint32_t tr_x = (uint32_t)((4 * g + (j >> 2)) * kB6XRS) + 8u * (((uint32_t)j & 3u) ^ (2u * ((uint32_t)g & 1u)));
-#else
-    const uint32_t wr_z = (uint32_t)(j * kB6ZRS + 8 * g);            // + 16 dt rows, + 32 tile bytes: this lane's 8 bytes of a 112-column image row
-    const uint32_t wr_x = (uint32_t)(j * kB6XRS + 8 * g);
-    const uint32_t rd_b = (uint32_t)(j * kB6ZRS + 16 * g);           // chain B fragment: document j, 8 features from 32 s + 8 g
-    const uint32_t tr_z = (uint32_t)((4 * g + (j >> 2)) * kB6ZRS + 8 * (j & 3));     // transpose-read chunk of a 112-column image
-    const uint32_t tr_x = (uint32_t)((4 * g + (j >> 2)) * kB6XRS + 8 * (j & 3));
-#endif
 
     // the slab's fragment of tile t (16 features x 32 documents) of an image, k slot (G, e): e < 4 document 4 G + e, e >= 4 document 16 + 4 G + e - 4
     auto read_tr = [&](BFrag (&f)[3], uint32_t img_lane, int plane_bytes, int row_bytes, int t) __attribute__((always_inline)) {
@@ -248,21 +193,11 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
             f[p].u[0] = l2[0]; f[p].u[1] = l2[1]; f[p].u[2] = h2[0]; f[p].u[3] = h2[1];
         }
     };
-#ifdef PTR_B6_ABL_NOLDS      // timing-only ablation (wrong results): every LDS-sourced MFMA operand is ONE fragment read at kernel start — the operand reads are dead code
-    BFrag ablf[3];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) { ablf[p].q = *reinterpret_cast<lds_u32x4_b *>((uintptr_t)(lds0 + (uint32_t)(lane * 16 + p * 1024))); asm volatile("" : "+v"(ablf[p].q)); }
-#define B6_LDSOP(x) ablf
-#else
-#define B6_LDSOP(x) x
-#endif
-    auto mma6 = [&](f32x4 &c, const BFrag (&af_)[3], const BFrag (&bf_)[3]) __attribute__((always_inline)) {
-        const BFrag (&af)[3] = B6_LDSOP(af_); const BFrag (&bf)[3] = B6_LDSOP(bf_);
+    auto mma6 = [&](f32x4 &c, const BFrag (&af)[3], const BFrag (&bf)[3]) __attribute__((always_inline)) {
         c = B6_MFMA(af[0], bf[2], c); c = B6_MFMA(af[1], bf[1], c); c = B6_MFMA(af[2], bf[0], c);
         c = B6_MFMA(af[0], bf[1], c); c = B6_MFMA(af[1], bf[0], c); c = B6_MFMA(af[0], bf[0], c);
     };
-    auto mma6w = [&](f32x4 &c, int w0, const BFrag (&bf_)[3]) __attribute__((always_inline)) {       // A = the W^T fragment kept in st[w0 .. w0 + 2]
-        const BFrag (&bf)[3] = B6_LDSOP(bf_);
+    auto mma6w = [&](f32x4 &c, int w0, const BFrag (&bf)[3]) __attribute__((always_inline)) {       // A = the W^T fragment kept in st[w0 .. w0 + 2]
         const bf16x8 a0 = __builtin_bit_cast(bf16x8, st[w0]), a1 = __builtin_bit_cast(bf16x8, st[w0 + 1]), a2 = __builtin_bit_cast(bf16x8, st[w0 + 2]);
         c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bf[2].v, c, 0, 0, 0); c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, bf[1].v, c, 0, 0, 0);
         c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, bf[0].v, c, 0, 0, 0); c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bf[1].v, c, 0, 0, 0);
@@ -358,11 +293,7 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
         // end of a layer reads the next layer's first tile / zeros: those documents carry dLoss/dscore = 0)
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
-#if PTR_B6_DMA_CHAIN_ONLY
             const int k = chain ? W + 7 * q : 3 * 14;                // scalar; wave 7 (the longest MFMA stream of the chain phases) issues none
-#else
-            const int k = W + 8 * q;                                 // scalar
-#endif
             if (k < 3 * 14) {
                 const int layer = k / 14, ch = k - 14 * layer;
                 b6_bdma16(asrd, l16, (uint32_t)layer * (uint32_t)(act_layer_floats(R) * 4) + (uint32_t)row0 * (kAL * 4) + (uint32_t)ch * 1024,
@@ -379,65 +310,31 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     // w + 4 share a SIMD: waves 0..3 stage first and multiply second, waves 4..7 the other way round, so a SIMD's matrix pipe and vector
     // ALU are busy at the same time.  Three barriers per slab (was four, with an all-VALU staging phase of 3.8 K cycles of 21.4 K).
     uint32_t m2 = 0u, m1 = 0u;                         // gate bits (activation > 0) of this lane's 2 x 4 elements of layers 2 / 1, per slab
-    auto staging = [&](uint32_t zdst, int dt0 = 0, int dt1 = 2) __attribute__((always_inline)) {        // zdst: LDS offset (from lds0) of the dZ buffer that receives dZ3; document tiles dt0 .. dt1 - 1
-        if (dt0 == 0) { m2 = 0u; m1 = 0u; }
-#if defined(PTR_B6_ABL_NOSTAGE) || defined(PTR_B6_ABL_ST_NOMASK)     // (opaque gate bits: with a known 0 the compiler deletes the chain behind them)
-        m2 = 0xa5u; m1 = 0x5au;
-        asm volatile("" : "+v"(m2), "+v"(m1));
-#endif
-#ifdef PTR_B6_ABL_NOSTAGE    // timing-only ablation (wrong results): no staging pass at all
-        if (false) {
-#else
+    auto staging = [&](uint32_t zdst) __attribute__((always_inline)) {        // zdst: LDS offset (from lds0) of the dZ buffer that receives dZ3
+        m2 = 0u; m1 = 0u;
         if (chain) {
-#endif
             const f32x4 wo4 = *reinterpret_cast<lds_f32x4_b *>((uintptr_t)(b6_opaque(lds0 + (uint32_t)(kB6_WO + 64 * W)) + (uint32_t)(16 * g)));
-#ifndef PTR_B6_STAGE_PRELOAD
-#define PTR_B6_STAGE_PRELOAD 0        /* experiment: both document tiles' staging-area reads issued up front (r5 / default: tile by tile — the second tile's reads wait behind the first tile's stores) */
-#endif
-#if PTR_B6_STAGE_PRELOAD
-            f32x4 pre[2][3];
-            {
-                const uint32_t so0 = b6_opaque(lds0 + (uint32_t)(kB6_ST + 1024 * W)) + (uint32_t)(j * 64 + 16 * g);
 #pragma unroll
-                for (int dt = dt0; dt < dt1; ++dt)
-#pragma unroll
-                    for (int l = 0; l < 3; ++l) pre[dt][l] = *reinterpret_cast<lds_f32x4_b *>((uintptr_t)(so0 + (uint32_t)(dt * kActTile * 4 + l * kB6STG)));
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#endif
-#pragma unroll
-            for (int dt = dt0; dt < dt1; ++dt) {
+            for (int dt = 0; dt < 2; ++dt) {
                 // the staging area is a straight copy of two tile-major row tiles (ptr_mlp.h): feature tile W of row tile dt at dt * 7168 + W * 1024, lane (j, g) at j * 64 + 16 g
                 const uint32_t so = b6_opaque(lds0 + (uint32_t)(kB6_ST + 1024 * W)) + (uint32_t)(j * 64 + 16 * g) + (uint32_t)(dt * kActTile * 4);
-#ifdef PTR_B6_ABL_ST_NOREAD     // timing-only ablations of the staging pass (wrong results): no staging-area reads / no mask bits / no A1, A2 image stores
-                f32x4 a1 = wo4, a2 = wo4, a3 = wo4;
-                asm volatile("" : "+v"(a1), "+v"(a2), "+v"(a3));
-#elif PTR_B6_STAGE_PRELOAD
-                const f32x4 a1 = pre[dt][0], a2 = pre[dt][1], a3 = pre[dt][2];
-                (void)so;
-#else
                 const f32x4 a1 = *reinterpret_cast<lds_f32x4_b *>((uintptr_t)so);
                 const f32x4 a2 = *reinterpret_cast<lds_f32x4_b *>((uintptr_t)(so + kB6STG));
                 const f32x4 a3 = *reinterpret_cast<lds_f32x4_b *>((uintptr_t)(so + 2 * kB6STG));
-#endif
                 const float ds = dsv[dt];
                 f32x4 z3;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     z3[r] = a3[r] > 0.0f ? ds * wo4[r] : 0.0f;
                     awo[r] = fmaf(ds, a3[r], awo[r]);
-#ifndef PTR_B6_ABL_ST_NOMASK
                     m2 |= (a2[r] > 0.0f ? 1u : 0u) << (4 * dt + r);
                     m1 |= (a1[r] > 0.0f ? 1u : 0u) << (4 * dt + r);
-#endif
                 }
                 if (W == 0 && g == 0) abo += ds;
                 const uint32_t wo = wr_z + b6_opaque(lds0 + (uint32_t)(32 * W)) + (uint32_t)(16 * dt * kB6ZRS);
                 b6_write4(wo + b6_opaque(zdst), kB6ZPL, z3);
-#ifndef PTR_B6_ABL_ST_NOWRITE
                 b6_write4(wo + kB6_A2, kB6ZPL, a2);
                 b6_write4(wo + kB6_A1, kB6ZPL, a1);
-#endif
             }
         }
     };
@@ -459,9 +356,6 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
 #else
 #define B6_STAMP2() do { } while (0)
 #endif
-#if PTR_B6_PRIO
-    if (W >= 4) __builtin_amdgcn_s_setprio(1);      // waves w and w + 4 share a SIMD and the older one wins every arbitration: static priority for the younger half
-#endif
     uint32_t zi = kB6_ZA, zo = kB6_ZB;
     staging(zi);                                                     // slab 0
     b6_barrier();                                                    // images complete, staging area consumed
@@ -474,10 +368,11 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
         // ---- chain 3 (dZ3 -> dZ2) + dW_3, chain 2 (dZ2 -> dZ1) + dW_2
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-            if constexpr (!TAIL) { if (c == PTR_B6_X_PHASE) load_x(slab); }      // live through this phase only (registers), staged in front of its barrier
+            if constexpr (!TAIL) { if (c == 1) load_x(slab); }     // live through this phase only (registers), staged in front of its barrier
             const uint32_t zin = b6_opaque(lds0 + (c == 0 ? zi : zo)), zout = b6_opaque(lds0 + (c == 0 ? zo : zi) + (uint32_t)(32 * W));
             const uint32_t aim = b6_opaque(lds0 + (c == 0 ? kB6_A2 : kB6_A1));
             if (chain) {
+              // (two lambdas called in sequence: written out inline, the same statements get a different register allocation)
               auto chain_part = [&]() __attribute__((always_inline)) {
                 f32x4 cc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
                 auto read_b = [&](BFrag (&b)[3], int u) __attribute__((always_inline)) {       // u = 2 s + dt
@@ -493,13 +388,14 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
                         for (int p = 0; p < 3; ++p)
                             bt[dt][p] = *reinterpret_cast<lds_u32x2_b *>((uintptr_t)(zin + wr_z + (uint32_t)(192 + p * kB6ZPL + 16 * dt * kB6ZRS)));
                 };
-                if (c != PTR_B6_X_PHASE || PTR_B6_PIPE_C2) {      // the chain phase without X in flight has the registers for a fragment in flight beside the one being multiplied
+                // r6: the tail operands are read beside the last full slice's MFMAs (± 0, kept)
+                if (c == 0) {                                     // the chain phase without X in flight has the registers for a fragment in flight beside the one being multiplied
                     BFrag b[2][3];
                     read_b(b[0], 0);
 #pragma unroll
                     for (int u = 0; u < 6; ++u) {
                         if (u + 1 < 6) read_b(b[(u + 1) & 1], u + 1);
-                        else if (PTR_B6_TAILPRE) read_bt();      // the last step has no fragment to prefetch: its 12 registers take the tail operands
+                        else read_bt();                           // the last step has no fragment to prefetch: its 12 registers take the tail operands
                         __builtin_amdgcn_sched_barrier(0);
                         mma6w(cc[u & 1], 18 + 3 * (3 * c + (u >> 1)), b[u & 1]);
                         __builtin_amdgcn_sched_barrier(0);
@@ -509,12 +405,11 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
                     for (int u = 0; u < 6; ++u) {
                         BFrag b[3];
                         read_b(b, u);
-                        if (PTR_B6_TAILPRE && u == 5) read_bt();
+                        if (u == 5) read_bt();
                         mma6w(cc[u & 1], 18 + 3 * (3 * c + (u >> 1)), b);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-                if (!PTR_B6_TAILPRE) read_bt();
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
                     mma6t(cc[dt], c, bt[dt]);
@@ -522,41 +417,6 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
                 }
                 B6_STAMP2();                                      // chain MFMAs issued
                 const uint32_t m = c == 0 ? m2 : m1;
-#if PTR_B6_EPI_MIX
-                if (!(TAIL && c == 1)) {
-                    // the epilogue rides between the MFMAs of the dW row: tile n's six MFMAs carry chunk n — gating of document tile 0 | its split + image
-                    // stores | gating of tile 1 | its split + stores | (nothing)
-                    BFrag za[3], ab[2][3];
-                    f32x4 dz = f32x4{0.f, 0.f, 0.f, 0.f};
-                    const bool pipe = c != PTR_B6_X_PHASE;          // (compile-time after unrolling) the phase with X in flight has no registers for a fragment ahead
-                    read_tr(za, zin + tr_z + (uint32_t)(32 * W), kB6ZPL, kB6ZRS, 0);
-                    if (pipe) read_tr(ab[0], aim + tr_z, kB6ZPL, kB6ZRS, 0);
-#pragma unroll
-                    for (int n = 0; n < 5; ++n) {
-                        if (pipe) { if (n + 1 < 5) read_tr(ab[(n + 1) & 1], aim + tr_z, kB6ZPL, kB6ZRS, n + 1); }
-                        else read_tr(ab[0], aim + tr_z, kB6ZPL, kB6ZRS, n);
-                        __builtin_amdgcn_sched_barrier(0);
-                        mma6(st[5 * c + n], za, ab[pipe ? (n & 1) : 0]);
-                        if (n < 4) {
-                            const int dt = n >> 1;
-                            if ((n & 1) == 0) {
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) dz[r] = (m >> (4 * dt + r)) & 1u ? cc[dt][r] * scale : 0.0f;
-                            } else {
-                                b6_write4(zout + wr_z + (uint32_t)(16 * dt * kB6ZRS), kB6ZPL, dz);
-                            }
-#pragma unroll
-                            for (int i_ = 0; i_ < 6; ++i_) {
-                                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                                __builtin_amdgcn_sched_group_barrier(0x002, PTR_B6_EPI_K, 0);
-                            }
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    B6_STAMP2();
-                    return;
-                }
-#endif
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
                     f32x4 dz;
@@ -571,156 +431,72 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
                 }
                 B6_STAMP2();                                      // epilogue done (gating, split, image stores issued)
               };
-              // dW of the layer whose dZ is the chain's INPUT: row w, in-tiles 0..4 of the activations below it
               auto dw_part = [&]() __attribute__((always_inline)) {
-#if PTR_B6_EPI_MIX
-                if (!(TAIL && c == 1)) return;                   // (done inside chain_part, interleaved with the epilogue)
-#endif
-                if (c == 0) dw_row(std::integral_constant<int, 5>{}, std::bool_constant<PTR_B6_X_PHASE != 0 || PTR_B6_PIPE_C2 != 0>{}, 0, zin, W, aim + tr_z, kB6ZPL, kB6ZRS, 0);
-                else dw_row(std::integral_constant<int, 5>{}, std::bool_constant<PTR_B6_X_PHASE != 1 || PTR_B6_PIPE_C2 != 0>{}, 5, zin, W, aim + tr_z, kB6ZPL, kB6ZRS, 0);
+                // dW of the layer whose dZ is the chain's INPUT: row w, in-tiles 0..4 of the activations below it
+                if (c == 0) dw_row(std::integral_constant<int, 5>{}, std::true_type{}, 0, zin, W, aim + tr_z, kB6ZPL, kB6ZRS, 0);
+                else dw_row(std::integral_constant<int, 5>{}, std::false_type{}, 5, zin, W, aim + tr_z, kB6ZPL, kB6ZRS, 0);
               };
-#if PTR_B6_CHAIN_ORDER
-              // r6 experiment: the two waves of a SIMD (w, w + 4) run the phase's two independent halves in OPPOSITE order, so that one wave's epilogue
-              // (vector ALU + LDS stores) runs beside the other's matrix instructions instead of beside its epilogue.  One copy of each body: a two-trip loop
-              const bool chain_first = W < 4;
-#pragma unroll 1
-              for (int h = 0; h < 2; ++h) {
-                  if ((h == 0) == chain_first) chain_part(); else dw_part();
-                  __builtin_amdgcn_sched_barrier(0);
-              }
-#else
               chain_part();
               dw_part();
-#endif
             } else {
                 B6_STAMP2(); B6_STAMP2();
-#if PTR_B6_W7HOLD
                 // wave 7: in-tiles 5, 6 of every row.  r6: the two activation fragments are the SAME for all seven rows — read once per phase
-                // (r5: seven times: 126 transpose reads per phase, now 54), only the dZ tile of the row streams, one row ahead of its MFMAs
-                constexpr int ZD = PTR_B6_W7_DEPTH;
+                // (r5: seven times: 126 transpose reads per phase, now 54), only the dZ tile of the row streams, ZD - 1 rows ahead of its MFMAs
+                constexpr int ZD = 2;                             // dZ tiles in flight (two rows ahead measured no faster)
                 BFrag ab5[3], ab6[3], zr[ZD][3];
                 read_tr(zr[0], zin + tr_z, kB6ZPL, kB6ZRS, 0);
                 read_tr(ab5, aim + tr_z, kB6ZPL, kB6ZRS, 5);
                 read_tr(ab6, aim + tr_z, kB6ZPL, kB6ZRS, 6);
-                if (ZD == 3) read_tr(zr[1], zin + tr_z + 32u, kB6ZPL, kB6ZRS, 0);
+#pragma unroll
+                for (int d = 1; d < ZD - 1; ++d) read_tr(zr[d], zin + tr_z + (uint32_t)(32 * d), kB6ZPL, kB6ZRS, 0);
 #pragma unroll
                 for (int mo = 0; mo < 7; ++mo) {
                     if (mo + ZD - 1 < 7) read_tr(zr[(mo + ZD - 1) % ZD], zin + tr_z + (uint32_t)(32 * (mo + ZD - 1)), kB6ZPL, kB6ZRS, 0);
                     __builtin_amdgcn_sched_barrier(0);
-#if PTR_B6_W7_ILV
-                    {
-                        f32x4 &c0 = st[14 * c + 2 * mo], &c1 = st[14 * c + 2 * mo + 1];
-                        const BFrag (&af)[3] = zr[mo % ZD];
-                        c0 = B6_MFMA(af[0], ab5[2], c0); c1 = B6_MFMA(af[0], ab6[2], c1); c0 = B6_MFMA(af[1], ab5[1], c0); c1 = B6_MFMA(af[1], ab6[1], c1);
-                        c0 = B6_MFMA(af[2], ab5[0], c0); c1 = B6_MFMA(af[2], ab6[0], c1); c0 = B6_MFMA(af[0], ab5[1], c0); c1 = B6_MFMA(af[0], ab6[1], c1);
-                        c0 = B6_MFMA(af[1], ab5[0], c0); c1 = B6_MFMA(af[1], ab6[0], c1); c0 = B6_MFMA(af[0], ab5[0], c0); c1 = B6_MFMA(af[0], ab6[0], c1);
-                    }
-#else
                     mma6(st[14 * c + 2 * mo], zr[mo % ZD], ab5);
                     mma6(st[14 * c + 2 * mo + 1], zr[mo % ZD], ab6);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
-#else
-#pragma unroll
-                for (int mo = 0; mo < 7; ++mo)       // wave 7: in-tiles 5, 6 of every row
-                    dw_row(std::integral_constant<int, 2>{}, std::bool_constant<PTR_B6_PIPE_W7 != 0>{}, 14 * c + 2 * mo, zin, mo, aim + tr_z, kB6ZPL, kB6ZRS, 5);
-#endif
             }
-            if constexpr (!TAIL) { if (c == PTR_B6_X_PHASE) stage_x(slab); }     // the XI image (read by dW_1 only: free since the last B4)
+            if constexpr (!TAIL) { if (c == 1) stage_x(slab); }    // the XI image (read by dW_1 only: free since the last B4)
             // (the DMA goes BEHIND the X staging: hipcc's waitcnt for the X registers does not count the asm DMA, a wait placed behind it would
             // wait for the whole prefetch)
-#if PTR_B6_PREFETCH_LATE
             if (c == 0 && slab != slab0) {                           // the staging area was consumed before the last B4: the NEXT slab's activations
                 const int nxt = slab + (int)gridDim.x;               // (the prologue issued slab0's successor itself)
                 prefetch(nxt < nslabs ? nxt : nslabs - 1);
             }
-#endif
             if (c == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the NEXT slab's staging area has landed (issued a phase ago)
             B6_STAMP();
             b6_barrier();                                            // B2 / B3
             B6_STAMP();
         }
         // ---- dW_1: dZ1 (in `zi`) x the X image  ||  the staging pass of the next slab (-> `zo`, A2, A1: nobody reads them in this phase)
-        {
-            const bool more = slab + (int)gridDim.x < nslabs;       // wave-uniform
-            if constexpr (TAIL) {
-                if (more) staging(zo);
-            } else {
+        const bool more = slab + (int)gridDim.x < nslabs;           // wave-uniform
+        if constexpr (TAIL) {
+            if (more) staging(zo);
+        } else {
             const uint32_t za = b6_opaque(lds0 + zi), xi = b6_opaque(lds0 + kB6_XI) + tr_x;
-            auto dw1 = [&]() __attribute__((always_inline)) {
-                if (chain) {
-                    dw_row(std::integral_constant<int, 8>{}, std::true_type{}, 10, za, W, xi, kB6XPL, kB6XRS, 0);
-                } else {
-#if PTR_B6_W7HOLD
-                    BFrag xb[3], zr[2][3];                        // wave 7: in-tile 8 of X for every row — one fragment for the phase, the dZ tiles stream
-                    read_tr(zr[0], za + tr_z, kB6ZPL, kB6ZRS, 0);
-                    read_tr(xb, xi, kB6XPL, kB6XRS, 8);
-#pragma unroll
-                    for (int mo = 0; mo < 7; ++mo) {
-                        if (mo + 1 < 7) read_tr(zr[(mo + 1) & 1], za + tr_z + (uint32_t)(32 * (mo + 1)), kB6ZPL, kB6ZRS, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                        mma6(st[28 + mo], zr[mo & 1], xb);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-#else
-#pragma unroll
-                    for (int mo = 0; mo < 7; ++mo) dw_row(std::integral_constant<int, 1>{}, std::false_type{}, 28 + mo, za, mo, xi, kB6XPL, kB6XRS, 8);
-#endif
-                }
-            };
-#if PTR_B6_STAGE_ORDER == 4
-            // complementary halves of a SIMD without a second copy of either body (two copies under a wave-id branch spilled 115 registers):
-            // a two-trip loop that runs the staging pass in the first trip for waves 0..3 and in the second for waves 4..7 — waves w and
-            // w + 4 share a SIMD, so its vector ALU splits one wave's next slab while its matrix pipe multiplies the other's dW_1
-            const bool stage_first = W < 4;
-#pragma unroll 1
-            for (int h = 0; h < 2; ++h) {
-                if ((h == 0) == stage_first) { if (more) staging(zo); }
-                else dw1();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#elif PTR_B6_STAGE_ORDER == 3
-            // the two halves of the staging pass between the two halves of the dW_1 row: the MFMAs of four tiles drain while the vector ALU splits
+            if (more) staging(zo);
+            __builtin_amdgcn_sched_barrier(0);
+            B6_STAMP2();                                              // staging pass done
             if (chain) {
-                if (more) staging(zo, 0, 1);
-                __builtin_amdgcn_sched_barrier(0);
-                dw_row(std::integral_constant<int, 4>{}, std::true_type{}, 10, za, W, xi, kB6XPL, kB6XRS, 0);
-                if (more) staging(zo, 1, 2);
-                __builtin_amdgcn_sched_barrier(0);
-                dw_row(std::integral_constant<int, 4>{}, std::true_type{}, 14, za, W, xi, kB6XPL, kB6XRS, 4);
-            } else dw1();
-#elif PTR_B6_STAGE_ORDER == 0
-            if (more) staging(zo);
-            __builtin_amdgcn_sched_barrier(0);
-            B6_STAMP2();                                          // staging pass done
-            dw1();
-#elif PTR_B6_STAGE_ORDER == 1
-            dw1();
-            __builtin_amdgcn_sched_barrier(0);
-            if (more) staging(zo);
-#else
-            if (W < 4) {
-                if (more) staging(zo);
-                __builtin_amdgcn_sched_barrier(0);
-                dw1();
+                dw_row(std::integral_constant<int, 8>{}, std::true_type{}, 10, za, W, xi, kB6XPL, kB6XRS, 0);
             } else {
-                dw1();
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) staging(zo);
+                BFrag xb[3], zr[2][3];                            // wave 7: in-tile 8 of X for every row — one fragment for the phase, the dZ tiles stream
+                read_tr(zr[0], za + tr_z, kB6ZPL, kB6ZRS, 0);
+                read_tr(xb, xi, kB6XPL, kB6XRS, 8);
+#pragma unroll
+                for (int mo = 0; mo < 7; ++mo) {
+                    if (mo + 1 < 7) read_tr(zr[(mo + 1) & 1], za + tr_z + (uint32_t)(32 * (mo + 1)), kB6ZPL, kB6ZRS, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    mma6(st[28 + mo], zr[mo & 1], xb);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
-#endif
         }
-            }
         B6_STAMP();
         b6_barrier();                                                // B4: dZ1 / X consumed, next slab's images complete, staging area free
         B6_STAMP();
-#if !PTR_B6_PREFETCH_LATE
-        {
-            const int nxt = slab + 2 * (int)gridDim.x;
-            prefetch(nxt < nslabs ? nxt : nslabs - 1);
-        }
-#endif
         const uint32_t tz = zi; zi = zo; zo = tz;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // the run-ahead DMA must not outlive the workgroup's LDS allocation

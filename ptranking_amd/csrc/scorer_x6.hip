@@ -103,10 +103,7 @@ __device__ __forceinline__ void x6_glds16(const void *gsrc, uint32_t lds_dst) {
 using x6_rsrc = __amdgpu_buffer_rsrc_t;
 __device__ __forceinline__ x6_rsrc x6_srd(void *p, uint32_t bytes) { return __builtin_amdgcn_make_buffer_rsrc(p, 0, (int)bytes, 0x00020000); }
 __device__ __forceinline__ void x6_store16(x6_rsrc srd, uint32_t off, f32x4 v) {
-#ifndef PTR_X6_STORE_AUX
-#define PTR_X6_STORE_AUX 0
-#endif
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), srd, (int)off, 0, PTR_X6_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), srd, (int)off, 0, 0);
 }
 __device__ __forceinline__ f32x4 x6_load16(x6_rsrc srd, uint32_t voff, uint32_t soff) {      // out of range: zeros
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd, (int)voff, (int)soff, 0));
@@ -116,9 +113,6 @@ constexpr uint32_t kX6Oob = 0xFFFFC000u;       // an offset no buffer of ours re
                                                // (6 x 1 KB feature tiles of a row tile: 0xFFFFF000 + 4096 wrapped to offset 0 and wrote row 0, r5)
 constexpr uint64_t kX6BufLimit = 0xFFFFC000ull;
 
-#ifndef PTR_X6_KTAIL
-#define PTR_X6_KTAIL 1            /* r6: the last slice of a hidden layer as a 16-deep slice (0: the r4/r5 32-deep form, A/B measurements) */
-#endif
 #define X6_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16((A).v, (B).v, (C), 0, 0, 0)
 
 // =================================================================================================== forward
@@ -221,19 +215,13 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     // steps of a workgroup get the same margin from six extra DMA pieces issued behind the prologue's (into the slot slice 5 overwrites).
     auto slice_sync = [&]() __attribute__((always_inline)) -> uint32_t {
         X6_STAMP();
-#ifdef PTR_X6_NOBAR          // ablation builds (wrong results, timing only)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
         // DT = 4: 18 pieces behind slice i + 1, and in any four steps 28 stores (one epilogue) or 32 X loads; the prologue's 24 X loads
         // give the first steps the same margin
         if constexpr (DT == 4) { if constexpr (STORE) asm volatile("s_waitcnt vmcnt(46)\n\ts_barrier" ::: "memory"); else asm volatile("s_waitcnt vmcnt(18)\n\ts_barrier" ::: "memory"); }
         else if constexpr (STORE) asm volatile("s_waitcnt vmcnt(23)\n\ts_barrier" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(9)\n\ts_barrier" ::: "memory");
-#endif
         X6_STAMP();
-#ifndef PTR_X6_NODMA
         dma_issue();
-#endif
         cur_slot = cur_slot + 1 == kX6Ring ? 0 : cur_slot + 1;
         return lane_a + (uint32_t)cur_slot * kX6SliceBytes;
     };
@@ -317,13 +305,10 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
         });
         return nb;
     };
-#ifndef PTR_X6_LATE
-#define PTR_X6_LATE 2
-#endif
     using Early = std::false_type;
     using Full = std::false_type;
-    using Tail16 = std::bool_constant<PTR_X6_KTAIL != 0>;
-    using LateE = std::bool_constant<TRAIN && PTR_X6_LATE != 0>;      // steps whose work is an epilogue
+    using Tail16 = std::true_type;                 // r6: the last slice of a hidden layer is 16 deep (the r4/r5 form: 32 deep, zero-padded)
+    using LateE = std::bool_constant<TRAIN>;       // steps whose work is an epilogue (r5: no spills that way)
     using KNone = X6K<0, 0, 0, 0, 0, 0, 0>;
     auto nowork = [](auto) __attribute__((always_inline)) {};
 
@@ -337,20 +322,13 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     //   jX / l16  byte offset of the lane's 32 bytes inside row j of X / of its 16 bytes inside a (16 rows x 16 features) block of `acts`
     //             (row j at 64 j, its features 4 g .. + 3 at + 16 g: the block is one contiguous KB per store instruction either way)
     //   jH / jK   dropout key parts  j * kDropRowMul + g * kDropFgMul + seed_lo (hidden sites, fg = 4 mt + g) / with 2 g (X site, fg = 8 s + 2 g + h)
-#ifdef PTR_X6_LANE_LINEAR   // timing experiment (wrong block layout): lane l at byte 16 l of its (16 rows x 16 features) block
-    uint32_t jX = (uint32_t)j * (uint32_t)(F * 4) + (uint32_t)g * 32, l16 = (uint32_t)lane * 16;
-#else
     uint32_t jX = (uint32_t)j * (uint32_t)(F * 4) + (uint32_t)g * 32, l16 = (uint32_t)(j * 64 + g * 16);   // row j, features 4 g .. + 3 of the block
-#endif
     uint32_t jH = (uint32_t)j * kDropRowMul + (uint32_t)g * kDropFgMul + a.seed_lo, jK = jH + (uint32_t)g * kDropFgMul;
     asm volatile("" : "+v"(jX), "+v"(l16), "+v"(jH), "+v"(jK));
     // quarter q = (dt, h) of slice s of the 32 documents from row t32 on: the float4 a lane contributes to the B fragment.  X is read through
     // a buffer resource: rows past R and columns past F get an out-of-range offset (zeros)
     auto load_xq = [&](f32x4 (&rw)[DT][2], int t32, int s, int q) __attribute__((always_inline)) {
         const int dt = q >> 1, h = q & 1;
-#ifdef PTR_X6_NOX
-        const uint32_t vo = jX, so = (uint32_t)((t32 + 16 * dt) & 1023) * (uint32_t)(F * 4);
-#else
         // columns past F (the last slice when F % 32 != 0) are out of range like the rows past R: they read zeros, NOT the next row's first
         // features — a NaN / Inf there would reach this row's products as 0 * Inf
         // (the column test on the SCALAR unit: lane groups g < ng hold columns below F — a 64-bit lane mask ANDed with the row test's,
@@ -361,7 +339,6 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
         const uint64_t m = __builtin_amdgcn_ballot_w64(j < R - t32 - 16 * dt) & cmask;
         const uint32_t vo = __builtin_amdgcn_inverse_ballot_w64(m) ? jX : kX6Oob;
         const uint32_t so = (uint32_t)(t32 + 16 * dt) * (uint32_t)(F * 4);
-#endif
         rw[dt][h] = x6_load16(xsrd, vo, so + (uint32_t)(128 * s + 16 * h));
     };
     // quarter q of the X fragment of slice s: input dropout (site 0, fg = 8 s + 2 g + h) + split
@@ -395,13 +372,7 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     uint32_t abase = lane_a;
     read_a(af[0], abase, 0);
     // VALU per MFMA of the hints: an X-fragment quarter is ~22 (eval) / ~50 (training) instructions, a tile's epilogue ~52 / ~110
-#ifndef PTR_X6_KE_TRAIN
-#define PTR_X6_KE_TRAIN 9
-#endif
-#ifndef PTR_X6_KX_TRAIN
-#define PTR_X6_KX_TRAIN 4
-#endif
-    constexpr int KX = TRAIN ? PTR_X6_KX_TRAIN : 2, KE = TRAIN ? PTR_X6_KE_TRAIN : 5;
+    constexpr int KX = TRAIN ? 4 : 2, KE = TRAIN ? 9 : 5;
 
 #pragma unroll 1
     for (int it = 0; it < npass; ++it) {
@@ -411,11 +382,7 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
             // tile-major: this wave's 16-row tile is 7 contiguous KB, a store instruction = lane * 16 + 1024 * feature tile.  Whole tiles are
             // written (rows past R of the last tile hold finite values nobody uses); tiles past the last one get an out-of-range offset
             const uint32_t rt = (uint32_t)(t32 + 16 * dt) >> 4;
-#ifdef PTR_X6_L2STORE      // ablation: the same store instructions, aimed at an L2-resident part of the buffer
-            uint32_t o = rt < nrt ? l16 + ((rt & 127u) * (uint32_t)(kActTile * 4)) : kX6Oob;
-#else
             uint32_t o = rt < nrt ? l16 + (rt * (uint32_t)(kActTile * 4) + (uint32_t)layer * layer_bytes) : kX6Oob;
-#endif
             asm volatile("" : "+v"(o));
             return o;
         };
@@ -435,19 +402,10 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
                 if constexpr (STORE) {
                     f32x4 o = h;
                     if (mt == kMT - 1 && g == 1) o[0] = 1.0f;              // the ones column (100) of the fused backward
-#ifndef PTR_X6_NOSTORE
                     x6_store16(asrd, store_off(site - 1, dt) + X6_TSTRIDE * mt, o);
-#endif
                 }
                 split_pack4(h, bp[mt >> 1][dt], 2 * (mt & 1));
-#ifdef PTR_X6_EPI_SB
-                if constexpr (TRAIN) X6_SB();
-#endif
-                if (mt == kMT - 1) {
-#if !PTR_X6_KTAIL       /* (the 16-deep tail slice never reads the second half of these fragments) */
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) { bp[3][dt][p].u[2] = 0u; bp[3][dt][p].u[3] = 0u; }
-#endif
+                if (mt == kMT - 1) {            // (the second half of bp[3] stays as split: the 16-deep tail slice never reads it)
                     // feature 100 (lane group 1, element 0; its activation is exactly 0) = 1.0: the slot the weight image keeps the bias in
                     bp[3][dt][0].u[0] |= g == 1 ? 0x3F80u : 0u;
                 }
@@ -468,11 +426,7 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
                 acc[mt][dt] = bn;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) { h[c] = relu1(h[c]); sc[dt] = fmaf(h[c], w4[c], sc[dt]); }
-                if constexpr (STORE) {
-#ifndef PTR_X6_NOSTORE
-                    x6_store16(asrd, store_off(NL - 1, dt) + X6_TSTRIDE * mt, h);
-#endif
-                }
+                if constexpr (STORE) x6_store16(asrd, store_off(NL - 1, dt) + X6_TSTRIDE * mt, h);
             }
         };
 
@@ -517,38 +471,23 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
             constexpr bool LAST = decltype(lastlayer_)::value;
             abase = slice_step(I0{}, abase, bp[0], nowork, KNone{}, Early{}, Full{});
             abase = slice_step(I1{}, abase, bp[1], nowork, KNone{}, Early{}, Full{});
-#ifndef PTR_X6_XLOAD_POS
-#define PTR_X6_XLOAD_POS 0          /* where the next tile's first X loads are issued: 0 behind the layer's second slice step (r4/r5), 1 behind its third, 2 inside its third (behind the SYNC) */
-#endif
-#ifndef PTR_X6_XQ_R0
-#define PTR_X6_XQ_R0 0              /* first tile region of the last step that converts a quarter of the next tile's slice 0 */
-#endif
-            auto xloads = [&]() __attribute__((always_inline)) {
+            // the next tile's first two X slices, in front of this layer's store burst (issued one or two steps later, the loads still wait for
+            // the burst to drain: DESIGN.md §0, Forward)
+            if constexpr (LAST) {
 #pragma unroll
                 for (int q = 0; q < 2 * DT; ++q) { load_xq(raw[0], t32n, 0, q); load_xq(raw[1], t32n, n1 > 1 ? 1 : 0, q); }      // (past the end: zeros, never used)
-            };
-            if constexpr (LAST && PTR_X6_XLOAD_POS == 0) {       // the next tile's first two X slices, in front of this layer's store burst
-                xloads();
                 X6_SB();
             }
-            if constexpr (LAST && PTR_X6_XLOAD_POS == 2) {
-                abase = slice_step(I0{}, abase, bp[2], [&](auto r_) __attribute__((always_inline)) { if constexpr (decltype(r_)::value == 4) xloads(); }, KNone{}, Early{}, Full{});
-            } else {
-                abase = slice_step(I0{}, abase, bp[2], nowork, KNone{}, Early{}, Full{});
-            }
-            if constexpr (LAST && PTR_X6_XLOAD_POS == 1) {
-                xloads();
-                X6_SB();
-            }
+            abase = slice_step(I0{}, abase, bp[2], nowork, KNone{}, Early{}, Full{});
             if constexpr (LAST) {
                 abase = slice_step(I1{}, abase, bp[3], [&](auto r_) __attribute__((always_inline)) {
                     constexpr int r = decltype(r_)::value;
                     // the third slice right behind the quarter it replaces: in front of all but the first few stores of the burst
                     auto quarter = [&](int q) __attribute__((always_inline)) { make_bq(raw[0], t32n, 0, bfx[0], q); load_xq(raw[0], t32n, n1 > 2 ? 2 : 0, q); };
-                    if constexpr (DT == 2) { if constexpr (r >= PTR_X6_XQ_R0 && r < PTR_X6_XQ_R0 + 4) quarter(r - PTR_X6_XQ_R0); }
+                    if constexpr (DT == 2) { if constexpr (r < 4) quarter(r); }
                     else if constexpr (r < 4) { quarter(2 * r); quarter(2 * r + 1); }
                     if constexpr (r > 0) epilogue_out(std::integral_constant<int, r - 1>{});
-                }, X6K<KX, KX + 1, KX + 1, KX + 1, 1, 1, 1>{}, std::bool_constant<TRAIN && PTR_X6_LATE == 2>{}, Tail16{});
+                }, X6K<KX, KX + 1, KX + 1, KX + 1, 1, 1, 1>{}, LateE{}, Tail16{});
                 epilogue_out(std::integral_constant<int, kMT - 1>{});
             } else {
                 abase = slice_step(I1{}, abase, bp[3], [&](auto r_) __attribute__((always_inline)) {

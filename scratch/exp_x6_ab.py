@@ -1,4 +1,4 @@
-"""time of the bf16x6 forward for the library named by PTR_LIB (ablation builds: scratch/ab_x6.sh): F = 136, 524288 rows"""
+"""time of the bf16x6 forward for the library named by PTR_LIB (e.g. a `python -m ptranking_amd.build --variant` build): F = 136, 524288 rows"""
 import ctypes as C, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ptranking_amd import _lib
