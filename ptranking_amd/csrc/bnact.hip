@@ -249,7 +249,8 @@ colsum2_reduce_kernel(const float *__restrict__ partial, int nblk, int N, int R,
         Rf = fmaxf(cnt_red[0], 1.0f);
         if (total_out && blockIdx.x == 0 && threadIdx.x == 0) total_out[0] = Rf;
     }
-    auto rows_of = [&](int b) { return counts ? counts[b] : (float)(min(R, (b + 1) * chunk) - b * chunk); };
+    // chunk b's rows: 0 for the chunks past R (above 131 072 rows the 512 chunks of ceil(R / 512) rows can end before the grid does)
+    auto rows_of = [&](int b) { return counts ? counts[b] : (float)max(0, min(R, (b + 1) * chunk) - b * chunk); };
     auto p0 = [&](int b) { return b < nblk ? partial[((size_t)b * 2 + 0) * N + c] : 0.0f; };
     auto p1 = [&](int b) { return b < nblk ? partial[((size_t)b * 2 + 1) * N + c] : 0.0f; };
     float s1 = 0.0f, s2 = 0.0f;

@@ -15,12 +15,28 @@ def close(a, b, tol=2e-5, what=""):
     assert err <= tol * scale, f"{what}: max|diff|={err:.3e} > {tol * scale:.3e}"
 
 
-@pytest.mark.parametrize("R,K,N", [(1000, 136, 128), (777, 128, 256), (515, 256, 512), (300, 512, 136), (2049, 136, 408), (640, 136, 136),
-                                   (333, 512, 1), (100, 10, 100), (65, 100, 1), (4096, 46, 100), (50, 7, 5), (1, 136, 128),
-                                   # several trips per wave round the tile loop (256 CUs x 16 waves x 16 rows = 65 536 rows per trip), ragged tail
-                                   (140001, 136, 136), (70003, 100, 100), (66000, 34, 200)])
+LINEAR_SHAPES = [(1000, 136, 128), (777, 128, 256), (515, 256, 512), (300, 512, 136), (2049, 136, 408), (640, 136, 136),
+                 (333, 512, 1), (100, 10, 100), (65, 100, 1), (4096, 46, 100), (50, 7, 5), (1, 136, 128),
+                 # several trips per wave round the fp32 kernel's tile loop (256 CUs x 16 waves x 16 rows = 65 536 rows per trip), ragged tail
+                 (140001, 136, 136), (70003, 100, 100), (66000, 34, 200)]
+
+
+@pytest.mark.parametrize("R,K,N", LINEAR_SHAPES)
 @pytest.mark.parametrize("bias", [True, False])
 def test_linear_forward_backward_match_torch_cpu(R, K, N, bias):
+    _linear_forward_backward_vs_torch_cpu(R, K, N, bias)
+
+
+@pytest.mark.parametrize("R,K,N", LINEAR_SHAPES)
+@pytest.mark.parametrize("bias", [True, False])
+def test_linear_forward_backward_match_torch_cpu_on_the_fp32_kernel(R, K, N, bias, monkeypatch):
+    """PTR_LIN_X6=0: the fp32-MFMA forward / backward-input kernel on every shape — the default serves K <= 256 from 1024 rows on with the
+    bf16x6 kernels, so without the switch the multi-trip shapes above never reach the fp32 kernel's tile loop."""
+    monkeypatch.setenv("PTR_LIN_X6", "0")
+    _linear_forward_backward_vs_torch_cpu(R, K, N, bias)
+
+
+def _linear_forward_backward_vs_torch_cpu(R, K, N, bias):
     from ptranking_amd.linear import linear
     torch.manual_seed(R + K + N)
     x = torch.randn(R, K)
@@ -44,8 +60,8 @@ def test_linear_forward_backward_match_torch_cpu(R, K, N, bias):
 
 @pytest.mark.parametrize("wide", ["0", "1"])
 def test_linear_tile_forms_agree_with_torch(wide, monkeypatch):
-    """16 waves x 16-row tiles (default) and 8 waves x 32-row tiles (PTR_LIN_WIDE=0) of the forward / backward-input kernel: the switch is
-    read once per process, so each form runs in its own interpreter."""
+    """16 waves x 16-row tiles (default) and 8 waves x 32-row tiles (PTR_LIN_WIDE=0) of the fp32-MFMA forward / backward-input kernel: the switch is
+    read once per process, so each form runs in its own interpreter (PTR_LIN_X6=0 there: the bf16x6 kernels would otherwise serve 3000 and 70 001 rows)."""
     import os, subprocess, sys
     code = (
         "import torch\n"
@@ -61,7 +77,7 @@ def test_linear_tile_forms_agree_with_torch(wide, monkeypatch):
         "        d = (a_.detach().cpu().double() - b_.detach().double()).abs().max().item()\n"
         "        assert d <= 2e-5 * max(1.0, b_.abs().max().item()), (R, K, N, d)\n"
         "print('forms ok')\n")
-    env = dict(os.environ, PTR_LIN_WIDE=wide)
+    env = dict(os.environ, PTR_LIN_WIDE=wide, PTR_LIN_X6="0")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600,
                          cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert out.returncode == 0 and "forms ok" in out.stdout, out.stderr[-2000:]
