@@ -375,11 +375,6 @@ approxndcg_ring_kernel(const float *__restrict__ preds, const float *__restrict_
     }
 }
 
-static int approx_ring_enabled() {                   // PTR_APPROX_RING=0 selects the LDS kernel (A/B measurements, tests); read per call
-    const char *e = getenv("PTR_APPROX_RING");
-    return !(e && e[0] == '0');
-}
-
 // One workgroup: S = sum 1/IDCG, loss, the factor kernel 3 applies.  out_scale[0] = applied factor, out_scale[1] = local S.
 __global__ void __launch_bounds__(kBlock)
 approx_finish_kernel(const float *__restrict__ dcg_q, const float *__restrict__ inv_q, int B, int couple_batch,
@@ -414,7 +409,7 @@ extern "C" int ptr_approxndcg_fwd_bwd(const float *preds, const float *labels, c
     if (!loss_out || !scale_out || (B > 0 && (!dcg_q || !inv_idcg_q || !grad))) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
     if (!(alpha > 0.0f)) { set_error("%s: alpha must be > 0 (got %g)", who, (double)alpha); return PTR_ERR_INVALID_ARG; }
     hipStream_t st = as_stream(stream);
-    if (B > 0 && L <= 512 && approx_ring_enabled()) {
+    if (B > 0 && L <= 512 && env_int("PTR_APPROX_RING", 1)) {           // PTR_APPROX_RING=0 selects the LDS kernel (tests)
         auto go = [&](auto kern, int dpt) -> int {
             constexpr int QPB = kBlock / kWave;
             const size_t lds = (size_t)QPB * 64 * approx_ring_sort_width(dpt) * sizeof(float);

@@ -405,17 +405,12 @@ static int bn_blocks(int R) {
     int b = (R + 255) / 256;
     return b < 1 ? 1 : (b > 512 ? 512 : b);
 }
-// chunks of the BACKWARD sums (colsum2_kernel<1>; PTR_BN_BWD_BLOCKS overrides the cap for measurements).  r6 measured 512 / 2048 chunks with two / four rows in flight
-// at 131 072 x 100: 1.267 / 1.277 / 1.272 / 1.324 ms per default-pointsf step — more chunks cost the fixed-order reduction more than they give the sums
-static int bn_blocks_bwd_cap() {
-    static int cap = 0;
-    if (!cap) { const char *e = getenv("PTR_BN_BWD_BLOCKS"); cap = e ? atoi(e) : 0; if (cap < 1 || cap > 4096) cap = 512; }
-    return cap;
-}
+// chunks of the BACKWARD sums (colsum2_kernel<1>).  r6 measured 512 / 2048 chunks with two / four rows in flight at 131 072 x 100:
+// 1.267 / 1.277 / 1.272 / 1.324 ms per default-pointsf step — more chunks cost the fixed-order reduction more than they give the sums
+constexpr int kBnBwdBlocks = 512;
 static int bn_blocks_bwd(int R) {
     int b = (R + 63) / 64;
-    const int cap = bn_blocks_bwd_cap();
-    return b < 1 ? 1 : (b > cap ? cap : b);
+    return b < 1 ? 1 : (b > kBnBwdBlocks ? kBnBwdBlocks : b);
 }
 
 static int check_bnact(const char *who, int R, int N, int ld, int af, float p) {

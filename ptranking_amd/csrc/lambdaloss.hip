@@ -444,8 +444,7 @@ extern "C" int ptr_lambdaloss_fwd_bwd(const float *preds, const float *labels, c
         return PTR_ERR_INVALID_ARG;
     }
     hipStream_t st = as_stream(stream);
-    static const bool topk_off = [] { const char *e = getenv("PTR_LAMBDALOSS_TOPK"); return e && atoi(e) == 0; }();
-    const bool topk = !topk_off && presort && k <= 11 && loss_type != PTR_LAMBDALOSS_NDCG_LOSS1 && L % 4 == 0 && L <= 1024 &&
+    const bool topk = presort && k <= 11 && loss_type != PTR_LAMBDALOSS_NDCG_LOSS1 && L % 4 == 0 && L <= 1024 &&
                       ((reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(grad)) & 15) == 0;
     if (B > 0 && topk) {
         // small cut-off on presorted labels: wavefront arg-max selection instead of a sort, one pair per lane (lambdaloss_topk_kernel)

@@ -37,7 +37,7 @@ __host__ __device__ inline int lin_ldk(int K) { return (K + 3) / 4 * 4 + 4; }
 //   * the MT weight fragments of a super-step as ONE batch of LDS reads, MFMAs in groups of two tiles with the k-step outermost
 //     (consecutive MFMAs write different accumulators);
 //   * zero-padding selects only on a padded last super-step / the tail tile;
-//   * 16 waves x 16-row tiles (4 waves per SIMD) by default, 8 waves x 32-row tiles for A/B (PTR_LIN_WIDE=0).
+//   * launched as 16 waves x 16-row tiles (4 waves per SIMD); the round-2 form, 8 waves x 32-row tiles, is in git history.
 template <int MT, int RT, bool TRANS, bool VECX, int NW>
 __global__ void __launch_bounds__(NW * 64)
 linear_fwd_kernel(const float *__restrict__ X, const float *__restrict__ W, const float *__restrict__ bias,
@@ -446,23 +446,12 @@ relu_gate_kernel(const float *__restrict__ dy, const float *__restrict__ y, size
     if (i < n) out[i] = y[i] > 0.0f ? dy[i] : 0.0f;
 }
 
-static int lin_num_cus() {
-    static int n = 0;
-    if (!n) {
-        hipDeviceProp_t prop;
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
-// output tiles (of 16) per workgroup: as many as fit 150 KB of LDS next to K inputs, at most `cap` (10 for the 16-row form — 11 and 12 spill at 128 VGPRs —: N = 136 in ONE
-// block — X is read once instead of twice, 9 tiles instead of 2 x 5; 8 for the 32-row form's registers), padding minimised
-static void lin_tiling(int K, int N, int cap, int &MT, int &nblocks) {
+// output tiles (of 16) per workgroup: as many as fit 150 KB of LDS next to K inputs, at most 10 (11 and 12 spill at 128 VGPRs): N = 136 in ONE
+// block — X is read once instead of twice, 9 tiles instead of 2 x 5 —, padding minimised
+static void lin_tiling(int K, int N, int &MT, int &nblocks) {
     const int n16 = (N + 15) / 16;
     int mt_max = (int)((150 * 1024) / ((size_t)16 * lin_ldk(K) * sizeof(float) + 64));
-    if (mt_max > cap) mt_max = cap;
+    if (mt_max > 10) mt_max = 10;
     if (mt_max < 1) mt_max = 1;
     nblocks = (n16 + mt_max - 1) / mt_max;
     MT = (n16 + nblocks - 1) / nblocks;
@@ -477,19 +466,18 @@ static int launch_linear(const float *X, int ldx, const float *W, const float *b
     if (R == 0) return 0;
     {   // r6: the bf16x6 form of the same product (linear_x6.hip) where it serves the shape
         const LinArgs ax{R, K, N, ldx, ldy, ldg, act, p_drop, (uint32_t)seed, (uint32_t)(seed >> 32), site};
-        const int rc = launch_linear_x6(TRANS, X, W, bias, gate, ax, Y, lin_num_cus(), st, who);
+        const int rc = launch_linear_x6(TRANS, X, W, bias, gate, ax, Y, st, who);
         if (rc >= 0) return rc;
     }
-    // 16 waves x 16-row tiles (4 waves per SIMD; <= 128 VGPRs) or, PTR_LIN_WIDE=0, the round-2 form 8 waves x 32-row tiles
-    static const int wide = [] { const char *e = getenv("PTR_LIN_WIDE"); return e ? atoi(e) != 0 : 1; }();
+    // 16 waves x 16-row tiles (4 waves per SIMD; <= 128 VGPRs)
     int MT, nby;
-    lin_tiling(K, N, wide ? 10 : 8, MT, nby);
+    lin_tiling(K, N, MT, nby);
     const size_t lds = ((size_t)16 * MT * lin_ldk(K) + 16 * MT) * sizeof(float);
     if (lds > 160 * 1024) { set_error("%s: K=%d does not fit the LDS weight tile", who, K); return PTR_ERR_UNSUPPORTED; }
     LinArgs a{R, K, N, ldx, ldy, ldg, act, p_drop, (uint32_t)seed, (uint32_t)(seed >> 32), site};
-    const int nw = wide ? 16 : 8, rpt = wide ? 16 : 32;
-    const int ntiles = (R + rpt - 1) / rpt;
-    int gx = lin_num_cus() / nby;
+    constexpr int nw = 16;
+    const int ntiles = (R + 15) / 16;
+    int gx = num_cus() / nby;
     if (gx < 1) gx = 1;
     gx = ntiles < gx * nw ? (ntiles + nw - 1) / nw : gx;
     const bool vecx = ((ldx & 3) == 0) && ((K & 3) == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
@@ -498,16 +486,10 @@ static int launch_linear(const float *X, int ldx, const float *W, const float *b
         hipLaunchKernelGGL(kern, dim3(gx, nby), dim3(nw * 64), lds, st, X, W, bias, gate, a, Y);
         return check_hip(hipGetLastError(), who);
     };
-#define LIN_CASE(M)                                                                                                     \
-    case M:                                                                                                             \
-        if (wide) return vecx ? go(linear_fwd_kernel<M, 1, TRANS, true, 16>) : go(linear_fwd_kernel<M, 1, TRANS, false, 16>);   \
-        return vecx ? go(linear_fwd_kernel<M, 2, TRANS, true, 8>) : go(linear_fwd_kernel<M, 2, TRANS, false, 8>);
-#define LIN_CASE_W(M) case M: return vecx ? go(linear_fwd_kernel<M, 1, TRANS, true, 16>) : go(linear_fwd_kernel<M, 1, TRANS, false, 16>);
+#define LIN_CASE(M) case M: return vecx ? go(linear_fwd_kernel<M, 1, TRANS, true, 16>) : go(linear_fwd_kernel<M, 1, TRANS, false, 16>);
     switch (MT) {
-        LIN_CASE(1) LIN_CASE(2) LIN_CASE(3) LIN_CASE(4) LIN_CASE(5) LIN_CASE(6) LIN_CASE(7) LIN_CASE(8)
-        LIN_CASE_W(9) LIN_CASE_W(10)
+        LIN_CASE(1) LIN_CASE(2) LIN_CASE(3) LIN_CASE(4) LIN_CASE(5) LIN_CASE(6) LIN_CASE(7) LIN_CASE(8) LIN_CASE(9) LIN_CASE(10)
     }
-#undef LIN_CASE_W
 #undef LIN_CASE
     set_error("%s: internal tiling error", who);
     return PTR_ERR_UNSUPPORTED;
@@ -534,7 +516,7 @@ static int bw_chunks(int R, int K, int N) {
     int MTO, NTW;
     bw_tiling(K, N, MTO, NTW);
     const int blocks_y = ((N + 16 * MTO - 1) / (16 * MTO)) * ((K + 64 * NTW - 1) / (64 * NTW));
-    int chunks = (2 * lin_num_cus() + blocks_y - 1) / blocks_y;
+    int chunks = (2 * num_cus() + blocks_y - 1) / blocks_y;
     const int max_chunks = (R + 255) / 256;        // at least 256 rows per chunk
     if (chunks > max_chunks) chunks = max_chunks;
     return chunks < 1 ? 1 : chunks;

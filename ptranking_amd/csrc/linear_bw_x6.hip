@@ -7,8 +7,8 @@
 //
 // Same machine as scorer_dw_x6.hip (fp32 products from six v_mfma_f32_16x16x32_bf16 on exactly split operands, [row][column] bf16 plane images
 // in LDS, both MFMA operands through ds_read_b64_tr_b16, slabs of 32 rows prefetched one slab ahead): the NARROW operand (<= 16 MT columns,
-// MT = 7 or 9) is held whole, the WIDE operand streams in passes of 384 columns; a wave owns 3 wide tiles x MT narrow tiles.  Either side of
-// the product can be the narrow one:
+// MT = 7 or 9) is held whole, the WIDE operand streams in passes of at most 256 columns (see the kernel for how the waves share the tiles).
+// Either side of the product can be the narrow one:
 //   narrow = dY (N <= 144): tile rows are out-features, lanes in-features: partial[n * K + k]; db from per-thread column sums of the dY slab;
 //   narrow = X  (K <= 140): tile rows are in-features: partial[n * K + k] written with lanes along n; the X image carries a column of ONES
 //                           behind its last feature, so row K of the product IS db (the fused scorer backward's trick).
@@ -28,12 +28,13 @@ using lds_u32x2_l = __attribute__((address_space(3))) u32x2;
 using lds_i16x4_l = __attribute__((address_space(3))) i16x4;
 
 constexpr int kL6S = 32;                         // rows per slab
-constexpr int kL6CT = 24;                        // wide tiles per pass (384 columns); r6: CT = 8 (128 columns) for the products whose wide side is that small
-// wide image: 768 B per row padded to 800, 512 to 544, or 256 to 288 (all = 32 mod 256: conflict-free transpose reads)
-__host__ __device__ constexpr int l6_wrs(int CT) { return CT == 24 ? 800 : CT == 16 ? 544 : 288; }      // 768 / 512 / 256 B of tiles + 32
+// wide tiles per pass CT = 16 (256 columns), or 8 (128 columns) for the products whose wide side is that small.  The r4 / r5 form (8 waves,
+// CT = 24) lost to the 16-wave one and is in git history.
+// wide image: 512 B per row padded to 544, or 256 to 288 (both = 32 mod 256: conflict-free transpose reads)
+__host__ __device__ constexpr int l6_wrs(int CT) { return CT == 16 ? 544 : 288; }      // 512 / 256 B of tiles + 32
 __host__ __device__ constexpr int l6_nrs(int MT) { return MT == 9 ? 288 : 224; }             // narrow image row stride (bytes): 144 / 112 bf16, both = +-32 mod 256
-// CT = 8: the column-sum scratch of the epilogue lies over the wide image (dead by then) — 49 / 55 KB per workgroup, two workgroups per CU
-__host__ __device__ constexpr int l6_lds(int MT, int CT) { return 3 * kL6S * l6_wrs(CT) + 3 * kL6S * l6_nrs(MT) + (CT == 24 ? kL6S * 16 * MT * 4 : 0); }
+// the column-sum scratch of the epilogue lies over the wide image (dead by then); CT = 8: 49 / 55 KB per workgroup, two workgroups per CU
+__host__ __device__ constexpr int l6_lds(int MT, int CT) { return 3 * kL6S * l6_wrs(CT) + 3 * kL6S * l6_nrs(MT); }
 
 __device__ __forceinline__ uint32_t l6_cvt_pk(float x0, float x1) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x0, x1}, bf16x2)); }
 __device__ __forceinline__ void l6_split2(float x0, float x1, uint32_t &p1, uint32_t &p2, uint32_t &p3) {      // round-to-nearest split, scorer_x6.hip
@@ -53,7 +54,7 @@ __device__ __forceinline__ void l6_write4(uint32_t addr, int plane_bytes, const 
 }
 
 // Zn: the narrow operand [R][ldn], NN columns (+ a column of ones at index NN when `ones`); Aw: the wide operand [R][ldw], KW columns, this launch
-// covers its tiles tile0 .. tile0 + 23.  Element (o, k) of the product -> part[o * s_n + k * s_w] for o < NN, the ones row -> part[bias_off + k];
+// covers its tiles tile0 .. tile0 + ntp - 1.  Element (o, k) of the product -> part[o * s_n + k * s_w] for o < NN, the ones row -> part[bias_off + k];
 // colsum != 0 (narrow = dY, first pass): the column sums of the narrow slab -> part[bias_off + o].
 // r6, CT = 8: ONE wide tile per wave, <= 128 registers, two workgroups per CU.  The slab loop is stage (VALU split) -> barrier -> MFMAs -> barrier with the next
 // slab's loads in flight behind the first barrier; with one wide tile per wave the MFMA phase is 42-54 instructions and a slab took 3.2 us of which the matrix
@@ -67,17 +68,17 @@ linear_bw_x6_kernel(const float *__restrict__ Zn, int ldn, int NN, int ones, con
     extern __shared__ __attribute__((aligned(16))) uint8_t smem_l6[];
     constexpr int NRS = l6_nrs(MT), NPL = kL6S * NRS;
     constexpr int kL6WRS = l6_wrs(CT), kL6WPL = kL6S * kL6WRS, NWT = CT / 8;      // NWT: wide tiles per wave (W, W + 8, ..)
-    constexpr int WW4 = CT * 4;                            // float4 per wide-slice row (96 / 32)
+    constexpr int WW4 = CT * 4;                            // float4 per wide-slice row (64 / 32)
     constexpr int NT = NW * 64, HALVES = NW / 8, MTL = (MT + HALVES - 1) / HALVES;      // HALVES: groups of 8 waves sharing the wide tiles, each with every HALVES-th narrow tile
-    constexpr int SW = (kL6S * WW4 + NT - 1) / NT;         // wide load slots per thread (6 / 2)
+    constexpr int SW = (kL6S * WW4 + NT - 1) / NT;         // wide load slots per thread (2)
     constexpr int ZW4 = 4 * MT;                            // float4 per narrow row (28 / 36)
     constexpr int SZ = (kL6S * ZW4 + NT - 1) / NT;         // narrow load slots per thread (2 / 3)
-    constexpr int kW_ = 0, kZ_ = 3 * kL6WPL, kB_ = CT == 24 ? kZ_ + 3 * NPL : 0;      // CT = 8 / 16: the column-sum scratch lies over the (dead) wide image
+    constexpr int kW_ = 0, kZ_ = 3 * kL6WPL, kB_ = 0;      // the column-sum scratch lies over the (dead) wide image
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, Wall = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int W = Wall & 7, half = Wall >> 3;               // wide tiles W, W + 8, ..; narrow tiles half, half + HALVES, ..
     const int chunk = ((R + gridDim.x - 1) / gridDim.x + kL6S - 1) / kL6S * kL6S;
     const int r_begin = blockIdx.x * chunk, r_end = min(R, r_begin + chunk);
-    const int col0 = 16 * tile0, colE = min(KW, col0 + 16 * ntp);        // this pass: wide columns [col0, colE), ntp <= 24 tiles
+    const int col0 = 16 * tile0, colE = min(KW, col0 + 16 * ntp);        // this pass: wide columns [col0, colE), ntp <= CT tiles
     const uint32_t lds0 = l6_lds_addr(smem_l6);
 
     // slot geometry recomputed at each use from an opaque thread index (hoisted it costs the registers the accumulators need)
@@ -227,8 +228,7 @@ linear_bw_x6_kernel(const float *__restrict__ Zn, int ldn, int NN, int ones, con
 // PTR_LIN_BW_X6: "0" never, "1" (default) from 32768 rows on, "2" always (tests).  Applicable when one side has at most 144 columns (140 for
 // X, which needs a free column for the ones), every leading dimension and column count is a multiple of 4 and the pointers are 16-byte aligned.
 int lin_bw_x6_plan(int R, int K, int N, int ldx, int ldy, const void *X, const void *dY) {       // 0 = not served, 1 = narrow dY, 2 = narrow X
-    const char *e = getenv("PTR_LIN_BW_X6");
-    const int mode = e ? atoi(e) : 1;
+    const int mode = env_int("PTR_LIN_BW_X6", 1);
     if (mode <= 0 || (mode == 1 && R < 32768)) return 0;
     if ((K | N | ldx | ldy) & 3) return 0;
     if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(dY)) & 15) return 0;
@@ -236,7 +236,7 @@ int lin_bw_x6_plan(int R, int K, int N, int ldx, int ldy, const void *X, const v
     if (!a_ok && !b_ok) return 0;
     if (a_ok && b_ok) {
         // both narrow: r6 — the orientation whose WIDE side fits 128 columns runs the one-tile-per-wave form (two workgroups per CU); otherwise hold
-        // the SMALLER one's companion as the wide stream (one pass either way up to 384 columns)
+        // the SMALLER one's companion as the wide stream (one pass either way up to 256 columns)
         if (K <= 128 && N <= K) return 1;
         if (N <= 128 && K < N) return 2;
         if (K <= 128) return 1;
@@ -245,20 +245,12 @@ int lin_bw_x6_plan(int R, int K, int N, int ldx, int ldy, const void *X, const v
     }
     return a_ok ? 1 : 2;
 }
-static int l6_num_cus() {
-    static const int ncu = [] {                          // queried once: hipGetDeviceProperties is not a per-call cost
-        int dev = 0;
-        hipDeviceProp_t pr;
-        return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-    }();
-    return ncu;
-}
 // the one-tile-per-wave form serves a product whose wide side (plan 1: X, plan 2: dY) has at most 128 columns
 static bool l6_small(int plan, int K, int N) { return (plan == 1 ? K : N) <= 128; }
 // row chunks (= partials): one per CU, two for the one-tile-per-wave form (two workgroups per CU); at least 256 rows each.  plan 0: the largest count any plan uses
 int lin_bw_x6_chunks(int R, int K, int N, int plan) {
     const int per_cu = (plan == 0 || l6_small(plan, K, N)) ? 2 : 1;
-    const int maxc = (R + 255) / 256, want = per_cu * l6_num_cus();
+    const int maxc = (R + 255) / 256, want = per_cu * num_cus();
     return maxc < want ? (maxc < 1 ? 1 : maxc) : want;
 }
 
@@ -279,13 +271,11 @@ int launch_lin_bw_x6(int plan, const float *X, int ldx, const float *dY, int ldy
         };
         return mt == 7 ? go8(linear_bw_x6_kernel<7, 8, 8>, 7) : go8(linear_bw_x6_kernel<9, 8, 8>, 9);
     }
-    // 9+ wide tiles: passes of <= 16 tiles on the 16-wave form (PTR_LIN_BW_FORM=24: the 8-wave / 24-tile form, A/B measurements)
-    const char *fe = getenv("PTR_LIN_BW_FORM");
-    const int ct = (fe && atoi(fe) == 24) ? 24 : 16;
+    // 9+ wide tiles: passes of <= 16 tiles on the 16-wave form
     auto go = [&](auto kern, int MT, int CT, int threads) -> int {
         const size_t lds = (size_t)l6_lds(MT, CT);
         if (int e = allow_lds(kern, lds)) return e;
-        // balanced passes: ceil(T / CT) of them, each ceil(T / passes) tiles wide (26 tiles: 13 + 13, not 24 + 2)
+        // balanced passes: ceil(T / CT) of them, each ceil(T / passes) tiles wide (20 tiles: 10 + 10, not 16 + 4)
         const int passes = (T + CT - 1) / CT, tpp = (T + passes - 1) / passes;
         for (int t0 = 0; t0 < T; t0 += tpp) {
             hipLaunchKernelGGL(kern, dim3(chunks), dim3(threads), lds, st, Zn, ldn, NN, ones, Aw, ldw, KW, t0, T - t0 < tpp ? T - t0 : tpp, R, ws, n, s_n, s_w,
@@ -294,8 +284,7 @@ int launch_lin_bw_x6(int plan, const float *X, int ldx, const float *dY, int ldy
         }
         return 0;
     };
-    if (ct == 16) return mt == 7 ? go(linear_bw_x6_kernel<7, 16, 16>, 7, 16, 1024) : go(linear_bw_x6_kernel<9, 16, 16>, 9, 16, 1024);
-    return mt == 7 ? go(linear_bw_x6_kernel<7, kL6CT, 8>, 7, kL6CT, 512) : go(linear_bw_x6_kernel<9, kL6CT, 8>, 9, kL6CT, 512);
+    return mt == 7 ? go(linear_bw_x6_kernel<7, 16, 16>, 7, 16, 1024) : go(linear_bw_x6_kernel<9, 16, 16>, 9, 16, 1024);
 }
 
 }  // namespace ptr

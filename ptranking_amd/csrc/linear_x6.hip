@@ -516,10 +516,9 @@ linear_fwd_x6c_kernel(const float *__restrict__ X, const float *__restrict__ W, 
 
 }  // namespace
 
-int launch_linear_x6(bool trans, const float *X, const float *W, const float *bias, const float *gate, const LinArgs &a, float *Y, int num_cus,
-                     hipStream_t st, const char *who) {
-    const char *sw = getenv("PTR_LIN_X6");                     // 0: fp32-MFMA kernel; 2: general form only (A/B measurements, tests; read per call)
-    const int on = sw ? atoi(sw) : 1;
+int launch_linear_x6(bool trans, const float *X, const float *W, const float *bias, const float *gate, const LinArgs &a, float *Y, hipStream_t st,
+                     const char *who) {
+    const int on = env_int("PTR_LIN_X6", 1);                  // 0: fp32-MFMA kernel; 2: general form only (tests)
     if (!on) return -1;
     const int K = a.K, N = a.N, R = a.R;
     // served: K <= 256 in 16-byte rows (the fp32 X fragments are 16-byte loads), weights readable as 16-byte rows in the forward orientation
@@ -550,7 +549,7 @@ int launch_linear_x6(bool trans, const float *X, const float *W, const float *bi
     if (MT < 4) return -1;
     const size_t lds = (size_t)MT * per_tile + (size_t)64 * MT;
     const int ntiles = (R + 16 * kLxRT - 1) / (16 * kLxRT);
-    int gx = num_cus / nby;
+    int gx = num_cus() / nby;
     if (gx < 1) gx = 1;
     if (ntiles < gx * kLxNW) gx = (ntiles + kLxNW - 1) / kLxNW;
     auto go = [&](auto kern) -> int {

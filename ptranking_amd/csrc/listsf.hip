@@ -786,13 +786,9 @@ static int attn_args(const char *who, int B, int L, int F, int H, int ld, float 
 
 }  // namespace ptr
 
-// Waves per workgroup: 4 (default) lets two independent workgroups share a CU, so one group's barrier / staging phases are
-// covered by the other's MFMA work; 8 halves the K/V re-staging traffic.  PTR_ATTN_WAVES=8 selects the latter.
-static int attn_waves() {
-    static int nw = [] { const char *e = getenv("PTR_ATTN_WAVES"); return (e && atoi(e) == 8) ? 8 : 4; }();
-    return nw;
-}
-
+// Waves per workgroup: 4 lets two independent workgroups share a CU, so one group's barrier / staging phases are covered by the
+// other's MFMA work; 8 would halve the K/V re-staging traffic.  Only the dK / dV kernel of the widest heads runs 8 waves (its 4-wave
+// form spills more); the 8-wave forms of the other kernels were a measurement switch and are in git history.
 extern "C" int ptr_mhsa_forward(const float *Q, const float *K, const float *V, int ld_qkv, const int32_t *lens, int B, int L, int F,
                                 int n_heads, float p_drop, uint64_t seed, int site, float *O, float *lse, void *stream) {
     using namespace ptr;
@@ -814,11 +810,10 @@ extern "C" int ptr_mhsa_forward(const float *Q, const float *K, const float *V, 
             return check_hip(hipGetLastError(), who);
         };
         // two row tiles per wave (every K / V operand read feeds two MFMAs) when the rows exist and the registers allow it
-        static const int rt1 = [] { const char *e = getenv("PTR_ATTN_RT1"); return e ? atoi(e) : 0; }();    // measurements
         if constexpr (D <= 5) {
-            if (L > 64 && !rt1) return attn_waves() == 8 && L > 128 ? launch.template operator()<2, 8>() : launch.template operator()<2, 4>();
+            if (L > 64) return launch.template operator()<2, 4>();
         }
-        return attn_waves() == 8 && L > 64 ? launch.template operator()<1, 8>() : launch.template operator()<1, 4>();
+        return launch.template operator()<1, 4>();
     });
 }
 
@@ -867,15 +862,18 @@ extern "C" int ptr_mhsa_backward(const float *Q, const float *K, const float *V,
             hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)B * n_heads * nrb)), dim3(NW * 64), lds, st, K, ds_ws, lens, a, dQ);
             return check_hip(hipGetLastError(), who);
         };
-        const bool w8 = attn_waves() == 8 && L > 64 && D <= 6;     // the 8-wave variants of the widest heads would spill
-        const bool kv8 = L > 64 && (D >= 7 || attn_waves() == 8);   // 4-wave dK/dV variants of the widest heads spill more
+        auto dkv = [&]() -> int {                                   // 4-wave dK/dV variants of the widest heads spill more
+            if constexpr (D >= 7) {
+                if (L > 64) return launch_dkv.template operator()<8>();
+            }
+            return launch_dkv.template operator()<4>();
+        };
         if (ds_ws) {   // dK / dV first (it writes dS), then dQ as ONE GEMM unit from the stored dS
-            if (int rc = kv8 ? launch_dkv.template operator()<8>() : launch_dkv.template operator()<4>()) return rc;
-            return w8 ? launch_dq_ds.template operator()<8>() : launch_dq_ds.template operator()<4>();
+            if (int rc = dkv()) return rc;
+            return launch_dq_ds.template operator()<4>();
         }
-        int rc = w8 ? launch_dq.template operator()<8>() : launch_dq.template operator()<4>();
-        if (rc) return rc;
-        return kv8 ? launch_dkv.template operator()<8>() : launch_dkv.template operator()<4>();
+        if (int rc = launch_dq.template operator()<4>()) return rc;
+        return dkv();
     });
 }
 

@@ -161,8 +161,7 @@ listnet_vec_kernel(const float *__restrict__ preds, const float *__restrict__ la
 static int launch_listnet_vec(const float *preds, const float *labels, const int32_t *lens, int B, int L, float *loss_q, float *grad,
                               hipStream_t st, bool *served) {
     *served = false;
-    static const bool off = [] { const char *e = getenv("PTR_LISTNET_VEC"); return e && atoi(e) == 0; }();
-    if (off || L % 4 != 0 || L > 1024) return 0;
+    if (L % 4 != 0 || L > 1024) return 0;
     if ((reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(grad)) & 15) return 0;
     *served = true;
     auto go = [&]<int G, int V>() -> int {
@@ -342,8 +341,7 @@ listmle_vec_kernel(const float *__restrict__ preds, const int64_t *__restrict__ 
 static int launch_listmle_vec(const float *preds, const int64_t *perm, const int32_t *lens, int B, int L, float *loss_q, float *grad,
                               hipStream_t st, bool *served) {
     *served = false;
-    static const bool off = [] { const char *e = getenv("PTR_LISTMLE_VEC"); return e && atoi(e) == 0; }();
-    if (off || L % 4 != 0 || L > 1024) return 0;
+    if (L % 4 != 0 || L > 1024) return 0;
     if ((reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(perm) | reinterpret_cast<uintptr_t>(grad)) & 15) return 0;
     *served = true;
     auto go = [&]<int V>() -> int {

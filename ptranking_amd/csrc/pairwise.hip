@@ -218,21 +218,6 @@ pairwise_bce_kernel(const float *__restrict__ preds, const float *__restrict__ l
 }
 
 
-static int ring_waves() {                         // PTR_RING_WAVES=1/2/4/8/16 pins the waves per workgroup (measurements)
-    const char *e = getenv("PTR_RING_WAVES");
-    const int v = e ? atoi(e) : 0;
-    return v == 1 || v == 2 || v == 4 || v == 8 || v == 16 ? v : 0;
-}
-static int ring_num_cus() {
-    static int n = 0;
-    if (!n) { int dev = 0; hipDeviceProp_t pr; n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256; }
-    return n;
-}
-static int ring_enabled() {                       // PTR_LAMBDARANK_RING=0 selects the LDS kernel (A/B measurements, tests)
-    const char *e = getenv("PTR_LAMBDARANK_RING");
-    return e ? (atoi(e) != 0) : 1;
-}
-
 template <bool WEIGHTED>
 static int launch_pairwise(const float *preds, const float *labels, const int32_t *lens, int B, int L, float sigma,
                            float *loss_out, float *loss_q, float *grad, void *stream, const char *who) {
@@ -240,10 +225,10 @@ static int launch_pairwise(const float *preds, const float *labels, const int32_
     if (B > 0 && (!loss_q || !grad)) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
     if (WEIGHTED && !(sigma >= 0.0f)) { set_error("%s: sigma must be >= 0 (got %g)", who, (double)sigma); return PTR_ERR_INVALID_ARG; }
     hipStream_t st = as_stream(stream);
-    if (WEIGHTED && B > 0 && L <= 512 && sigma > 0.0f && ring_enabled()) {
+    if (WEIGHTED && B > 0 && L <= 512 && sigma > 0.0f && env_int("PTR_LAMBDARANK_RING", 1)) {     // 0: the LDS kernel (tests)
         const int dpt = L <= 64 ? 1 : L <= 128 ? 2 : L <= 256 ? 4 : 8;
-        int QPB = ring_waves();
-        if (!QPB) { QPB = kRingBlock / kWave; while (QPB > 1 && B < QPB * ring_num_cus()) QPB >>= 1; }
+        int QPB = kRingBlock / kWave;             // waves per workgroup: fewer when the batch does not fill the CUs
+        while (QPB > 1 && B < QPB * num_cus()) QPB >>= 1;
         if (dpt >= 4 && QPB > kRing4Waves) QPB = kRing4Waves;
         if (dpt >= 8 && QPB > 4) QPB = 4;
         if (dpt < 8) {                            // pairwise_ring.hip

@@ -7,6 +7,7 @@
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/ptranking_amd.h"
 
@@ -21,6 +22,24 @@ int check_hip(hipError_t e, const char *what);
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+
+// The one reader of the PTR_* run-time switches: unset or empty gives `dflt`, anything else its atoi value.  Read per
+// call, so a test can flip a switch inside one process.
+inline int env_int(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e && e[0] ? atoi(e) : dflt;
+}
+
+// Compute units of the device, queried once per process (thread-safe static); 256 when the query fails.
+inline int num_cus() {
+    static const int n = [] {
+        int dev = 0;
+        hipDeviceProp_t pr;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess || pr.multiProcessorCount <= 0) return 256;
+        return pr.multiProcessorCount;
+    }();
+    return n;
+}
 
 // Shapes: L in (0, PTR_MAX_LIST_LEN]; B >= 0.  Returns 0 or an error code (message set).
 int check_batch(const void *preds, const void *second, int B, int L, const char *who);
@@ -84,17 +103,12 @@ template <class K> inline int persistent_grid(K kernel, int block, size_t lds, i
         if (e.kernel == kp && e.dev == dev && e.block == block && e.lds == lds && e.resident > 0) { resident = e.resident; break; }
     if (resident <= 0) {
         int per_cu = 0;
-        hipDeviceProp_t pr;
-        int cus = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, block, lds) != hipSuccess || per_cu <= 0) per_cu = 4;
-        resident = cus * per_cu;
+        resident = num_cus() * per_cu;
         cache[next_slot] = Entry{kp, dev, block, lds, resident};
         next_slot = (next_slot + 1) % 8;
     }
-    static const int mult = [] { const char *e = getenv("PTR_PERSIST_MULT"); return e ? atoi(e) : 1; }();   // 0: one block per unit of work (measurements)
-    if (mult <= 0) return want > 0 ? want : 1;
-    const long cap = (long)resident * mult;
-    return want < cap ? (want > 0 ? want : 1) : (int)cap;
+    return want < resident ? (want > 0 ? want : 1) : resident;
 }
 
 // Raises the dynamic-LDS cap of `kernel` when a launch needs more than the 64 KiB default.

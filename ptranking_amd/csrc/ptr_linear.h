@@ -15,7 +15,7 @@ struct LinArgs {
 
 // linear_x6.hip: Y = epi(X Wm^T + bias) with every fp32 product as six bf16 products (fp32 results).  Returns < 0 when the shape is not served
 // (the caller then runs the fp32-MFMA kernel), 0 on success, a PTR_ERR_* code otherwise.  trans: Wm = W^T with W [K][N] (backward-input).
-int launch_linear_x6(bool trans, const float *X, const float *W, const float *bias, const float *gate, const LinArgs &a, float *Y, int num_cus,
-                     hipStream_t st, const char *who);
+int launch_linear_x6(bool trans, const float *X, const float *W, const float *bias, const float *gate, const LinArgs &a, float *Y, hipStream_t st,
+                     const char *who);
 
 }  // namespace ptr

@@ -39,8 +39,6 @@ struct MlpArgs {
     uint32_t seed_lo, seed_hi;
 };
 
-int mlp_num_cus();
-
 // ---- the bf16x6 forward's pre-split weight image (scorer_x6.hip): one slice = [3 planes][7 tiles][lane group g][16 out-features][8 k-slots] bf16
 constexpr int kX6Rows = kHP;                       // 112 A rows per slice
 constexpr int kX6PlaneBytes = kX6Rows * 32 * 2;    // 7168

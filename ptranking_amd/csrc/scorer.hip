@@ -120,9 +120,7 @@ __host__ __device__ inline int fwd_w1_mode(int F, int NL) {
 #define FWD_STAMP(i) do { } while (0)
 #endif
 
-// TQ: K tail of layer 1 (see load_raw): 0 = zero-padded last super-step; 1 / 2 = F mod 16 of 4 / 8 features (VEC, W1 in LDS) taken in
-// 1 / 2 MFMAs per output tile
-template <int RT, int NTHR, bool TRAIN, bool VEC, int W1G, int TQ>
+template <int RT, int NTHR, bool TRAIN, bool VEC, int W1G>
 __global__ void __launch_bounds__(NTHR)
 mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs a, float *__restrict__ preds,
                float *__restrict__ acts) {
@@ -150,10 +148,6 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
     const uint32_t thr = drop_thr(a.p_drop);
     const float scale = TRAIN ? 1.0f / (1.0f - a.p_drop) : 1.0f;
     const int nS1 = (F + 15) >> 4;
-    // K tail of layer 1 (see load_raw): rem = F mod 16 of 4 or 8 features with W1 in LDS and float4 X loads; other shapes keep the
-    // zero-padded last super-step
-    const int nSf = F >> 4;
-    constexpr int tq = TQ;
 
     int ntile_done = 0;
     (void)ntile_done;
@@ -162,7 +156,7 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
     // in order), and their HBM latency is off the tile's critical path.  Past the end: a valid address, never consumed.
     auto prefetch_first = [&](int t, f32x4 (&xb)[RT]) {
         const int tt = t < ntiles ? t : ntiles - 1;
-        const int k0 = (tq > 0 && nSf == 0) ? (tq == 2 ? 4 * (g >> 1) : 0) : 4 * g;      // F < 16: the first super-step is the K tail
+        const int k0 = 4 * g;
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
             const int r = tt * rows_per_tile + 16 * rt + j;
@@ -250,13 +244,10 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
         }
         // load_raw only issues the loads; finish_x (zero padding + input dropout) runs AFTER the MFMAs of the super-step the
         // loads are prefetched under — anything consuming the loaded value earlier would pull the s_waitcnt in front of them.
-        // K TAIL (tq > 0): the contraction dimension is NOT padded to a multiple of 16.  The last super-step holds rem = F - 16 * nSf
-        // features; with rem = 4 * tq (tq = 1, 2) lane group g takes features k = 16 nSf + tq g + c, c < tq, so tq MFMAs per output tile
-        // cover them instead of four half-empty ones: the lanes load the aligned float4 that holds their features (tq = 2: groups 0/1 the
-        // first, 2/3 the second; tq = 1: all the same one) and finish_x picks them out.
+        // The contraction dimension is zero-padded to a multiple of 16: a K-tail form for F mod 16 = 4 / 8 (one or two MFMAs per tile instead
+        // of a half-empty super-step) was measured slower, ptr_mlp_forward below.
         auto load_raw = [&](int S, f32x4 (&xb)[RT]) {
-            int k0 = 16 * S + 4 * g;
-            if (tq > 0 && S == nSf) k0 = 16 * S + (tq == 2 ? 4 * (g >> 1) : 0);
+            const int k0 = 16 * S + 4 * g;
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 if constexpr (VEC) {
@@ -268,13 +259,11 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
             }
         };
         auto finish_x = [&](int S, f32x4 (&xb)[RT]) {
-            const bool tail = tq > 0 && S == nSf;                  // uniform
-            int k0 = 16 * S + 4 * g;
-            if (tail) k0 = 16 * S + (tq == 2 ? 4 * (g >> 1) : 0);
+            const int k0 = 16 * S + 4 * g;
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 f32x4 v = xb[rt];
-                if ((!tail && 16 * S + 16 > F) || !tile_full) {   // uniform: only a padded last super-step and the tail tile need the zero padding
+                if (16 * S + 16 > F || !tile_full) {              // uniform: only a padded last super-step and the tail tile need the zero padding
 #pragma unroll
                     for (int c = 0; c < 4; ++c) v[c] *= ((k0 + c < F) && rok[rt]) ? 1.0f : 0.0f;
                 }
@@ -282,10 +271,6 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
                     uint32_t w0, w1;
                     drop_bits(a.seed_lo, a.seed_hi, 0, row[rt], k0 >> 2, w0, w1);
                     v = drop4(v, w0, w1, thr, scale);
-                }
-                if (tail) {                                        // this lane group's tq features to the front
-                    if (tq == 2) { const bool hi = g & 1; v[0] = hi ? v[2] : v[0]; v[1] = hi ? v[3] : v[1]; }
-                    else v[0] = g == 0 ? v[0] : (g == 1 ? v[1] : (g == 2 ? v[2] : v[3]));
                 }
                 xb[rt] = v;
             }
@@ -393,51 +378,26 @@ mlp_fwd_kernel(const float *__restrict__ X, const float *__restrict__ P, MlpArgs
                 slab_buf ^= 1;
             }
         };
-        // the K tail: tq MFMAs per output tile; A operand = W1[row][16 nSf + tq g + c] straight from the [out][in] layout (W1 in LDS only)
-        auto l1_tail = [&](f32x4 (&cur)[RT]) {
-            if constexpr (W1G == 0) {
-                float wt[kMT][2];
-#pragma unroll
-                for (int mt = 0; mt < kMT; ++mt) {
-                    const float *wp = W1s + (size_t)(16 * mt + j) * ld1 + 16 * nSf + tq * g;
-                    wt[mt][0] = wp[0];
-                    wt[mt][1] = wp[tq - 1];                    // tq == 1: the same element again (unused)
-                }
-                static_for<kMT>([&](auto mt_) {
-                    constexpr int mt = mt_;
-#pragma unroll
-                    for (int rt = 0; rt < RT; ++rt) {
-                        acc[mt][rt] = mma(mt_, wt[mt][0], cur[rt][0], acc[mt][rt]);
-                        if (tq == 2) acc[mt][rt] = mma(mt_, wt[mt][1], cur[rt][1], acc[mt][rt]);
-                    }
-                });
-            }
-        };
         load_raw(nS1 > 1 ? 1 : 0, xb);
-        // super-steps 0 .. nSm-1 by the rotating l1_step; with a K tail the last super-step (nSf) is the tail step
-        const int nSm = tq > 0 ? nSf : nS1;
         int S1 = 0;
-        for (; S1 + 3 <= nSm; S1 += 3) {                      // branch-free body: the compiler counts the loads in flight exactly
+        for (; S1 + 3 <= nS1; S1 += 3) {                      // branch-free body: the compiler counts the loads in flight exactly
             slab_enter(S1);
             l1_step(S1, 0, xa, xb, xc);
             l1_step(S1 + 1, 1, xb, xc, xa);
             l1_step(S1 + 2, 2, xc, xa, xb);
             slab_leave(S1);
         }
-        const int left = nSm - S1;                            // 0, 1 or 2 leftover super-steps; then the tail reads the next buffer in turn
+        const int left = nS1 - S1;                            // 0, 1 or 2 leftover super-steps (the empty branch keeps the measured code layout)
         if (left == 0) {
-            if (tq > 0) l1_tail(xa);
         } else if (left == 1) {
             slab_enter(S1);
             l1_step(S1, 0, xa, xb, xc);
             slab_leave(S1);
-            if (tq > 0) l1_tail(xb);
         } else {
             slab_enter(S1);
             l1_step(S1, 0, xa, xb, xc);
             l1_step(S1 + 1, 1, xb, xc, xa);
             slab_leave(S1);
-            if (tq > 0) l1_tail(xc);
         }
         tile6_finish();
 
@@ -1066,33 +1026,10 @@ static int check_mlp(const char *who, int R, int F, int NL, float p) {
     return 0;
 }
 
-static int dw_blocks_per_cu() {
-    static int v = 0;
-    if (!v) { const char *e = getenv("PTR_DW_BLOCKS_PER_CU"); v = e ? atoi(e) : 2; if (v < 1 || v > 8) v = 2; }
-    return v;
-}
-
-// Tile-shape knobs (measured on MI355X, B*L = 524288 rows, F = 136): forward 16 waves x 16-row tiles 432 us vs 8 waves x
-// 32-row tiles 461 us; dZ 8 waves 400 us vs 16 waves (spills at the 128-VGPR cap) 415 us.
-static int env_flag(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return e ? (atoi(e) != 0) : dflt;
-}
-static int fwd_wide() { static int v = -2; if (v == -2) v = env_flag("PTR_FWD_WIDE", -1); return v; }   // -1: by configuration
-static int dw_staged() { static int v = -1; if (v < 0) v = env_flag("PTR_DW_STAGED", 1); return v; }
-static int dw_rb() { static int v = -1; if (v < 0) { const char *e = getenv("PTR_DW_RB"); v = (e && atoi(e) == 32) ? 32 : 16; } return v; }   // 16 measured best (32: 1.09 vs 1.05 ms backward)
-static int dz_wide() { static int v = -1; if (v < 0) v = env_flag("PTR_DZ_WIDE", 0); return v; }
-
-int mlp_num_cus() {
-    static int n = 0;
-    if (!n) {
-        hipDeviceProp_t prop;
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
+// Layer-wise backward shapes (measured on MI355X, B*L = 524288 rows, F = 136; the other forms are in git history): dZ 8 waves 400 us
+// vs 16 waves (spills at the 128-VGPR cap) 415 us; dW 16 rows per LDS block (32: 1.09 vs 1.05 ms backward); two dW blocks per CU.
+constexpr int kDwBlocksPerCu = 2;
+constexpr int kDwRB = 16;
 
 }  // namespace ptr
 
@@ -1100,7 +1037,7 @@ extern "C" size_t ptr_mlp_num_params(int F, int NL) { return ptr::n_params(NL, F
 
 // floats of workspace ptr_mlp_backward needs
 extern "C" size_t ptr_mlp_backward_ws_floats(int F, int NL) {
-    return (size_t)ptr::dw_blocks_per_cu() * ptr::mlp_num_cus() * ptr::n_params(NL, F);
+    return (size_t)ptr::kDwBlocksPerCu * ptr::num_cus() * ptr::n_params(NL, F);
 }
 
 // floats of dZ scratch ptr_mlp_backward needs for (R, F, NL): 0 when the single-pass fused backward serves the configuration
@@ -1124,11 +1061,12 @@ extern "C" int ptr_mlp_forward(const float *X, const float *params, int R, int F
     // 16 waves x 16-row tiles (4 waves/SIMD) or 8 waves x 32-row tiles (half the weight-fragment LDS reads per MFMA).  Measured
     // inside the train step (rocprofv3, F=136): the 16-row form is 7-9 % faster from 1024 to 4096 queries of 128 documents and
     // 20-30 % faster below 256 (twice the waves on few tiles); in eval mode and with first-layer weights streamed from L2
-    // (F=700) the 32-row form wins.  PTR_FWD_WIDE=0/1 pins the choice.
-    const bool wide = fwd_wide() < 0 ? (train && !w1g) : fwd_wide() != 0;
+    // (F=700) the 32-row form wins.  (B*L = 524288 rows, F = 136: 432 us vs 461 us.)  So the 16-row form runs exactly when training
+    // with W1 in LDS; the other two pairings are in git history.
+    const bool wide = train && !w1g;
     const int rows_per_tile = wide ? 16 : 32, wpb = wide ? 16 : 8;
     const int ntiles = (R + rows_per_tile - 1) / rows_per_tile;
-    const int grid = ntiles < mlp_num_cus() ? ntiles : mlp_num_cus();      // few tiles: one per CU (the SIMD to itself) before two per CU
+    const int grid = ntiles < num_cus() ? ntiles : num_cus();      // few tiles: one per CU (the SIMD to itself) before two per CU
     auto launch = [&](auto kern) -> int {
         if (int e = allow_lds(kern, lds)) return e;
         hipLaunchKernelGGL(kern, dim3(grid > 0 ? grid : 1), dim3(wpb * 64), lds, as_stream(stream), X, params, a, preds, acts);
@@ -1136,31 +1074,15 @@ extern "C" int ptr_mlp_forward(const float *X, const float *params, int R, int F
     };
     if (w1g) {   // large F (e.g. Yahoo's 700): W1 streamed from L2, F % 4 == 0 guaranteed by check_mlp
         if (!vec) { set_error("%s: X must be 16-byte aligned for F=%d", who, F); return PTR_ERR_INVALID_ARG; }
-        const int force_stream = env_flag("PTR_FWD_W1_STREAM", 0);             // tests / experiments: the per-wave streaming form (read per call)
-        if (w1g == 2 && !force_stream) {
-            if (wide) return train ? launch(mlp_fwd_kernel<1, 1024, true, true, 2, 0>) : launch(mlp_fwd_kernel<1, 1024, false, true, 2, 0>);
-            return train ? launch(mlp_fwd_kernel<2, 512, true, true, 2, 0>) : launch(mlp_fwd_kernel<2, 512, false, true, 2, 0>);
-        }
-        if (wide) return train ? launch(mlp_fwd_kernel<1, 1024, true, true, 1, 0>) : launch(mlp_fwd_kernel<1, 1024, false, true, 1, 0>);
-        return train ? launch(mlp_fwd_kernel<2, 512, true, true, 1, 0>) : launch(mlp_fwd_kernel<2, 512, false, true, 1, 0>);
+        if (w1g == 2 && !env_int("PTR_FWD_W1_STREAM", 0))                     // tests: PTR_FWD_W1_STREAM=1 pins the per-wave streaming form
+            return train ? launch(mlp_fwd_kernel<2, 512, true, true, 2>) : launch(mlp_fwd_kernel<2, 512, false, true, 2>);
+        return train ? launch(mlp_fwd_kernel<2, 512, true, true, 1>) : launch(mlp_fwd_kernel<2, 512, false, true, 1>);
     }
-    // K tail of layer 1 (F mod 16 of 4 or 8 with float4 X loads): no zero-padded k-steps — 136 features: 34 k-steps instead of 36.
+    // K tail of layer 1 (F mod 16 of 4 or 8 with float4 X loads) without zero-padded k-steps — 136 features: 34 k-steps instead of 36.
     // Measured (B = 4096 x 128 x 136, r3): the hidden-layer K tails alone 383 -> 370 us; with the layer-1 tail on top 373 us — its selects
-    // and tail operands push the 16-wave form past 128 VGPRs (18 spills vs 6).  It is therefore opt-in (PTR_FWD_TQ=1; tests run both).
-    int tq = 0;
-    if (const char *e = getenv("PTR_FWD_TQ")) { if (atoi(e) != 0 && vec) tq = (F & 15) == 8 ? 2 : ((F & 15) == 4 ? 1 : 0); }
-    auto pick = [&](auto rt_, auto nthr_, auto train_) -> int {
-        constexpr int RT_ = decltype(rt_)::value, NT_ = decltype(nthr_)::value;
-        constexpr bool TR_ = decltype(train_)::value;
-        if (!vec) return launch(mlp_fwd_kernel<RT_, NT_, TR_, false, 0, 0>);
-        if (tq == 2) return launch(mlp_fwd_kernel<RT_, NT_, TR_, true, 0, 2>);
-        if (tq == 1) return launch(mlp_fwd_kernel<RT_, NT_, TR_, true, 0, 1>);
-        return launch(mlp_fwd_kernel<RT_, NT_, TR_, true, 0, 0>);
-    };
-    using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-    using N1024 = std::integral_constant<int, 1024>; using N512 = std::integral_constant<int, 512>;
-    if (wide) return train ? pick(I1{}, N1024{}, std::true_type{}) : pick(I1{}, N1024{}, std::false_type{});
-    return train ? pick(I2{}, N512{}, std::true_type{}) : pick(I2{}, N512{}, std::false_type{});
+    // and tail operands push the 16-wave form past 128 VGPRs (18 spills vs 6).  Not kept (git history); layer 1 is zero-padded.
+    if (wide) return vec ? launch(mlp_fwd_kernel<1, 1024, true, true, 0>) : launch(mlp_fwd_kernel<1, 1024, true, false, 0>);
+    return vec ? launch(mlp_fwd_kernel<2, 512, false, true, 0>) : launch(mlp_fwd_kernel<2, 512, false, false, 0>);
 }
 
 namespace ptr {
@@ -1250,11 +1172,10 @@ int ptr::mlp_backward_impl(const char *who, const float *X, const float *params,
     }
     if (!dz) { set_error("%s: dz scratch is required for this configuration (ptr_mlp_backward_dz_floats)", who); return PTR_ERR_INVALID_ARG; }
     // 1. dZ chain (+ partial d w_out / d b_out)
-    const int ncu = mlp_num_cus();
-    const int nblk = dw_blocks_per_cu() * ncu;
+    const int ncu = num_cus();
+    const int nblk = kDwBlocksPerCu * ncu;
     const size_t NP = n_params(NL, F);
-    const bool wide = dz_wide() != 0;
-    const int wpb = wide ? 16 : 8;
+    constexpr int wpb = 8;
     const int ntiles = (R + 15) / 16;
     int grid_dz = ntiles < wpb * ncu ? (ntiles + wpb - 1) / wpb : ncu;
     if (grid_dz < 1) grid_dz = 1;
@@ -1274,7 +1195,7 @@ int ptr::mlp_backward_impl(const char *who, const float *X, const float *params,
             hipLaunchKernelGGL(kern, dim3(grid_dz), dim3(wpb * 64), lds, st, params, acts, dpreds, a, dz, ws, NP, off_wout(NL, F));
             return check_hip(hipGetLastError(), who);
         };
-        if (int e = wide ? go(mlp_bwd_dz_kernel<1, 1024>) : go(mlp_bwd_dz_kernel<1, 512>)) return e;
+        if (int e = go(mlp_bwd_dz_kernel<1, 512>)) return e;
     }
     // 2. dW per layer (row contraction), every block writes its partial into ws[block][flat parameter layout]
     for (int l = 0; l < (tail ? 1 : NL); ++l) {
@@ -1287,27 +1208,27 @@ int ptr::mlp_backward_impl(const char *who, const float *X, const float *params,
             hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), 0, st, A, lda, dZ, K, nt_base, a, ws, NP, off_W(l, F), off_b(l, F));
             return check_hip(hipGetLastError(), who);
         };
-        auto go_lds = [&](auto kern, int ntw, int rb, int nt_base) -> int {
-            if (int e0 = allow_lds(kern, dw_lds_bytes(ntw, rb))) return e0;
-            hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), dw_lds_bytes(ntw, rb), st, A, lda, dZ, K, nt_base, a, ws, NP, off_W(l, F),
+        auto go_lds = [&](auto kern, int ntw, int nt_base) -> int {
+            if (int e0 = allow_lds(kern, dw_lds_bytes(ntw, kDwRB))) return e0;
+            hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), dw_lds_bytes(ntw, kDwRB), st, A, lda, dZ, K, nt_base, a, ws, NP, off_W(l, F),
                                off_b(l, F));
             return check_hip(hipGetLastError(), who);
         };
-        const bool aligned = (lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0) && dw_staged();
+        const bool aligned = (lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);      // staged through LDS; unaligned: unstaged
         int e = 0;
         if (l == 0) {   // in-feature tiles per wave and pass: 3 (192 columns) or 6 (384 columns)
             if (aligned) {
-                if (ntk <= 12) e = dw_rb() == 32 ? go_lds(mlp_bwd_dw_lds_kernel<3, true, 32>, 3, 32, 0) : go_lds(mlp_bwd_dw_lds_kernel<3, true, 16>, 3, 16, 0);
+                if (ntk <= 12) e = go_lds(mlp_bwd_dw_lds_kernel<3, true, kDwRB>, 3, 0);
                 else if (dw_x6_supported(R, K, lda, A))   // wide inputs: the bf16x6 row contraction (scorer_dw_x6.hip), same partial layout
                     e = launch_dw_x6(A, lda, dZ, K, ntk, a, ws, NP, off_W(l, F), off_b(l, F), nblk, st, who);
-                else for (int base = 0; base < ntk && !e; base += 24) e = go_lds(mlp_bwd_dw_lds_kernel<6, true, 16>, 6, 16, base);
+                else for (int base = 0; base < ntk && !e; base += 24) e = go_lds(mlp_bwd_dw_lds_kernel<6, true, kDwRB>, 6, base);
             } else if (ntk <= 12) e = go(mlp_bwd_dw_kernel<3, true, 4>, 0);
             else if (ntk <= 24) e = go(mlp_bwd_dw_kernel<6, true, 4>, 0);
             else if (ntk <= 48) { e = go(mlp_bwd_dw_kernel<6, true, 4>, 0); if (!e) e = go(mlp_bwd_dw_kernel<6, true, 4>, 24); }
             else { set_error("%s: F=%d not supported by the dW kernel", who, F); return PTR_ERR_UNSUPPORTED; }
         } else {
             if (!aligned) e = go(mlp_bwd_dw_kernel<2, false, 4>, 0);
-            else e = dw_rb() == 32 ? go_lds(mlp_bwd_dw_lds_kernel<2, false, 32>, 2, 32, 0) : go_lds(mlp_bwd_dw_lds_kernel<2, false, 16>, 2, 16, 0);
+            else e = go_lds(mlp_bwd_dw_lds_kernel<2, false, kDwRB>, 2, 0);
         }
         if (e) return e;
     }

@@ -639,14 +639,9 @@ mlp_bwd_fused_kernel(const float *__restrict__ X, const float *__restrict__ P, c
     }
 }
 
-// PTR_BWD_FUSED=0 selects the layer-wise kernels (A/B measurements, tests); read on every call so a test can flip it
-static int bwd_fused_enabled() {
-    const char *e = getenv("PTR_BWD_FUSED");
-    return e ? (atoi(e) != 0) : 1;
-}
-
+// PTR_BWD_FUSED=0 selects the layer-wise kernels (tests)
 bool bwd_fused_supported(int F, int NL, const void *X, const void *acts) {
-    if (!bwd_fused_enabled()) return false;
+    if (!env_int("PTR_BWD_FUSED", 1)) return false;
     const int NT1 = (F + 15) / 16;
     // F < 16 * NT1: the X image needs a free column F for the ones column that makes column F of dW_0 the bias gradient
     // (F = 144 fills all nine tiles: it takes the layer-wise kernels)
@@ -655,7 +650,7 @@ bool bwd_fused_supported(int F, int NL, const void *X, const void *acts) {
 
 int bwd_fused_grid(int R) {
     const int nslabs = (R + kSR - 1) / kSR;
-    return nslabs < mlp_num_cus() ? nslabs : mlp_num_cus();
+    return nslabs < num_cus() ? nslabs : num_cus();
 }
 
 int launch_bwd_fused(const float *X, const float *params, const float *acts, const float *dpreds, const MlpArgs &a, float *ws,
@@ -672,10 +667,9 @@ int launch_bwd_fused(const float *X, const float *params, const float *acts, con
 }
 
 // The TAIL form (NT1 = 0): chain + every hidden-layer gradient + d w_out / d b_out in one pass over the stored activations, dZ of the first
-// layer written to dz0 [R][112] for the wide-input dW kernel.  PTR_BWD_TAIL=0 keeps the layer-wise dZ / dW kernels (A/B measurements, tests).
+// layer written to dz0 [R][112] for the wide-input dW kernel.  PTR_BWD_TAIL=0 keeps the layer-wise dZ / dW kernels (tests).
 bool bwd_tail_supported(int NL, const void *acts) {
-    const char *e = getenv("PTR_BWD_TAIL");
-    if (e && atoi(e) == 0) return false;
+    if (!env_int("PTR_BWD_TAIL", 1)) return false;
     return (NL == 2 || NL == 3) && (reinterpret_cast<uintptr_t>(acts) & 15) == 0;
 }
 

@@ -554,12 +554,8 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
 // PTR_BWD_X6 (read per call): "0" selects the fp32-MFMA fused backward (scorer_bwd.hip) instead.  r5: this kernel is the DEFAULT wherever it
 // serves the shape — software-pipelined (the next slab's staging pass inside the dW_1 phase, DMA issued by the chain waves at the end of the
 // chain-3 phase) it takes 462 us at 524 288 x 136 against 587-603 us (r4: 610 vs 600, opt-in).
-static int bwd_x6_mode() {
-    const char *e = getenv("PTR_BWD_X6");
-    return e ? atoi(e) : 1;
-}
 bool bwd_x6_supported(int R, int F, int NL, const void *X, const void *acts) {
-    if (bwd_x6_mode() == 0) return false;
+    if (!env_int("PTR_BWD_X6", 1)) return false;
     const int NT1 = (F + 15) / 16;
     if ((uint64_t)NL * (uint64_t)act_layer_floats(R) * 4 >= 0xFFFFF000ull || (uint64_t)R * (uint64_t)F * 4 >= 0xFFFFF000ull) return false;     // buffer resources: < 4 GB
     return NL == 3 && NT1 == 9 && F % 4 == 0 && F < 16 * NT1 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (reinterpret_cast<uintptr_t>(acts) & 15) == 0;
@@ -578,7 +574,7 @@ int launch_bwd_x6(const float *X, const float *params, const float *acts, const 
 // activations on the bf16 instructions, dZ of the first layer written to dz0 [R][112] for the first-layer dW kernel.  Same grid and partial layout as
 // the fp32-MFMA tail kernel (launch_bwd_tail, scorer_bwd.hip), which PTR_BWD_X6=0 keeps.
 bool bwd_x6_tail_supported(int R, int NL, const void *acts) {
-    if (bwd_x6_mode() == 0) return false;
+    if (!env_int("PTR_BWD_X6", 1)) return false;
     if ((uint64_t)NL * (uint64_t)act_layer_floats(R) * 4 >= 0xFFFFF000ull || (uint64_t)R * (kAL * 4) >= 0xFFFFF000ull) return false;      // buffer resources: < 4 GB
     return NL == 3 && (reinterpret_cast<uintptr_t>(acts) & 15) == 0;
 }

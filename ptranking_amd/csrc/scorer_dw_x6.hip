@@ -232,8 +232,7 @@ mlp_bwd_dw_x6_kernel(const float *__restrict__ A, int lda, const float *__restri
 // re-splits dZ): F = 700 = 44 tiles is 2 passes of 24 against 3 of 16 — config 4 measured 1.858 ms against 1.881 with the extra pass.  PTR_DW_X6_FORM=16 / 24 forces a form.
 int launch_dw_x6(const float *A, int lda, const float *dZ, int K, int ntk, const MlpArgs &a, float *ws, size_t np_stride, size_t w_off, size_t b_off,
                  int nblk, hipStream_t st, const char *who) {
-    const char *fe = getenv("PTR_DW_X6_FORM");
-    const int forced = fe ? atoi(fe) : 0;
+    const int forced = env_int("PTR_DW_X6_FORM", 0);
     const bool f24 = forced == 24 || (forced != 16 && (ntk + 15) / 16 > (ntk + 23) / 24);
     auto go = [&](auto kern, int ct, int threads) -> int {
         if (int e = allow_lds(kern, d6_lds(ct))) return e;
@@ -248,8 +247,7 @@ int launch_dw_x6(const float *A, int lda, const float *dZ, int K, int ntk, const
 
 // PTR_DW_X6: "0" never, "1" (default) the first layer's dW of wide inputs (more than 12 column tiles, i.e. F > 192) from 32768 rows on, "2" always
 bool dw_x6_supported(int R, int K, int lda, const void *A) {
-    const char *e = getenv("PTR_DW_X6");                   // read per call: tests and A/B runs switch it inside one process
-    const int mode = e ? atoi(e) : 1;
+    const int mode = env_int("PTR_DW_X6", 1);
     if (mode <= 0) return false;
     if (K % 4 != 0 || lda % 4 != 0 || (reinterpret_cast<uintptr_t>(A) & 15) != 0) return false;
     if ((K + 15) / 16 <= 12) return false;

@@ -554,7 +554,7 @@ int ptr::mlp_forward_x6_impl(const float *X, const float *params, int R, int F, 
     const size_t lds = x6_lds_bytes(NL);
     constexpr int dt = 2, nw = 16 / dt, rpt = 16 * dt;
     const int ntiles = (R + rpt - 1) / rpt, nblk = (ntiles + nw - 1) / nw;
-    const int grid = nblk < mlp_num_cus() ? nblk : mlp_num_cus();
+    const int grid = nblk < num_cus() ? nblk : num_cus();
     auto launch = [&](auto kern) -> int {
         if (int e = allow_lds(kern, lds)) return e;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(nw * 64), lds, st, X, params, reinterpret_cast<const uint8_t *>(wimg), a, preds, acts);

@@ -1,5 +1,5 @@
 #!/bin/bash
-# step time + forward/backward kernel time at the by_batch sizes (env passes through, e.g. PTR_FWD_WIDE=1)
+# step time + forward/backward kernel time at the by_batch sizes (env passes through, e.g. PTR_LIB=<variant>.so)
 for b in "$@"; do
   python bench.py --batch $b --steps 50 --warmup 10 --no-cpu-baseline --sweep= 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels']

@@ -1,4 +1,4 @@
-"""Attention core forward / forward+backward time at config 5's shape (1024 x 256 x 136, 2 heads, dropout 0.1); env: PTR_ATTN_RT1, PTR_ATTN_WAVES, PTR_LIB."""
+"""Attention core forward / forward+backward time at config 5's shape (1024 x 256 x 136, 2 heads, dropout 0.1); env: PTR_LIB."""
 import os, sys, torch
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 from ptranking_amd import listsf as LS
@@ -18,4 +18,4 @@ f = lambda: LS.mhsa_core(qd, kd, vd, H, p_drop=0.1, seed=7, site=0)
 def fb():
     f().backward(g)
 tf, tfb = timeit(f), timeit(fb)
-print(f"{os.environ.get('PTR_LIB', 'default')[-10:]} RT1={os.environ.get('PTR_ATTN_RT1', '0')} W={os.environ.get('PTR_ATTN_WAVES', '4')}: fwd {tf*1e3:.0f} us  fwd+bwd {tfb*1e3:.0f} us  bwd {1e3*(tfb-tf):.0f} us")
+print(f"{os.environ.get('PTR_LIB', 'default')[-10:]}: fwd {tf*1e3:.0f} us  fwd+bwd {tfb*1e3:.0f} us  bwd {1e3*(tfb-tf):.0f} us")

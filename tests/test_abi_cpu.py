@@ -164,3 +164,34 @@ def test_missing_library_is_a_loud_error(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))
     with pytest.raises(_lib.NativeLibraryError, match="no CPU / eager fallback"):
         _lib.load()
+
+
+def _documented_switches():
+    """The PTR_* variables of INTEGRATION.md §6 (first column of its table), without the ones only the tests read."""
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec = doc.split("## 6. Run-time switches", 1)[1].split("\n## ", 1)[0]
+    rows = [line.split("|")[1] for line in sec.splitlines() if line.startswith("| `")]
+    names = {n for col in rows if "(tests)" not in col for n in re.findall(r"`(PTR_[A-Z0-9_]+)`", col)}
+    assert names, "INTEGRATION.md §6 lists no switches"
+    return names
+
+
+def test_runtime_switches_are_read_in_one_place_and_documented():
+    """Every PTR_* variable the library reads goes through ptr::env_int (ptr_device.h) or os.environ in the package, and INTEGRATION.md §6
+    lists exactly those; getenv itself appears only in ptr_device.h."""
+    pkg = os.path.join(ROOT, "ptranking_amd")
+    csrc = os.path.join(pkg, "csrc")
+    read = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h", ".cpp")):
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        if f != "ptr_device.h":
+            assert "getenv(" not in src, f"{f} reads the environment itself; use ptr::env_int"
+        read |= set(re.findall(r'env_int\("(PTR_[A-Z0-9_]+)"', src))
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith(".py"):
+            for line in open(os.path.join(pkg, f)):
+                if "os.environ" in line:
+                    read |= set(re.findall(r'"(PTR_[A-Z0-9_]+)"', line))
+    assert read == _documented_switches(), (sorted(read - _documented_switches()), sorted(_documented_switches() - read))

@@ -58,29 +58,21 @@ def _linear_forward_backward_vs_torch_cpu(R, K, N, bias):
         close(bg.grad, br.grad, tol=5e-5, what="db")
 
 
-@pytest.mark.parametrize("wide", ["0", "1"])
-def test_linear_tile_forms_agree_with_torch(wide, monkeypatch):
-    """16 waves x 16-row tiles (default) and 8 waves x 32-row tiles (PTR_LIN_WIDE=0) of the fp32-MFMA forward / backward-input kernel: the switch is
-    read once per process, so each form runs in its own interpreter (PTR_LIN_X6=0 there: the bf16x6 kernels would otherwise serve 3000 and 70 001 rows)."""
-    import os, subprocess, sys
-    code = (
-        "import torch\n"
-        "from ptranking_amd.linear import linear\n"
-        "torch.manual_seed(5)\n"
-        "for R, K, N in ((3000, 136, 136), (70001, 100, 100), (515, 256, 512), (50, 7, 5)):\n"
-        "    x = torch.randn(R, K); w = torch.randn(N, K) / K ** 0.5; b = torch.randn(N); g = torch.randn(R, N)\n"
-        "    xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)\n"
-        "    yr = torch.nn.functional.linear(xr, wr, b); yr.backward(g)\n"
-        "    xg, wg = x.cuda().requires_grad_(True), w.cuda().requires_grad_(True)\n"
-        "    y = linear(xg, wg, b.cuda()); y.backward(g.cuda())\n"
-        "    for a_, b_ in ((y, yr), (xg.grad, xr.grad)):\n"
-        "        d = (a_.detach().cpu().double() - b_.detach().double()).abs().max().item()\n"
-        "        assert d <= 2e-5 * max(1.0, b_.abs().max().item()), (R, K, N, d)\n"
-        "print('forms ok')\n")
-    env = dict(os.environ, PTR_LIN_WIDE=wide, PTR_LIN_X6="0")
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600,
-                         cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    assert out.returncode == 0 and "forms ok" in out.stdout, out.stderr[-2000:]
+def test_linear_tile_forms_agree_with_torch(monkeypatch):
+    """The fp32-MFMA forward / backward-input kernel (16 waves x 16-row tiles) at every tile count it picks (PTR_LIN_X6=0: the bf16x6 kernels
+    would otherwise serve 3000 and 70 001 rows)."""
+    from ptranking_amd.linear import linear
+    monkeypatch.setenv("PTR_LIN_X6", "0")
+    torch.manual_seed(5)
+    for R, K, N in ((3000, 136, 136), (70001, 100, 100), (515, 256, 512), (50, 7, 5)):
+        x = torch.randn(R, K); w = torch.randn(N, K) / K ** 0.5; b = torch.randn(N); g = torch.randn(R, N)
+        xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+        yr = torch.nn.functional.linear(xr, wr, b); yr.backward(g)
+        xg, wg = x.cuda().requires_grad_(True), w.cuda().requires_grad_(True)
+        y = linear(xg, wg, b.cuda()); y.backward(g.cuda())
+        for a_, b_ in ((y, yr), (xg.grad, xr.grad)):
+            d = (a_.detach().cpu().double() - b_.detach().double()).abs().max().item()
+            assert d <= 2e-5 * max(1.0, b_.abs().max().item()), (R, K, N, d)
 
 
 def test_linear_reads_strided_rows_in_place_and_is_bit_stable():

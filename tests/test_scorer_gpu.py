@@ -90,9 +90,8 @@ def test_train_forward_backward_match_torch_with_same_masks(F, NL, R, monkeypatc
 
 @pytest.mark.parametrize("F,R", [(136, 2048 + 37), (8, 333), (132, 900), (24, 100), (4, 77)])
 def test_layer1_k_tail_form_matches_torch(F, R, monkeypatch):
-    """PTR_FWD_TQ=1: the first layer's contraction tail (F mod 16 = 4 or 8) in 1 / 2 MFMAs per output tile instead of a zero-padded
-    super-step (opt-in: it costs registers in the 16-wave form).  Training and eval forward against the CPU modules."""
-    monkeypatch.setenv("PTR_FWD_TQ", "1")
+    """The first layer's contraction tail at F mod 16 = 4 or 8 (and F < 16): the zero-padded last super-step of the default forward.
+    Training and eval forward against the CPU modules."""
     p = 0.1
     fused, ref = make_pair(F, 3, dropout=p)
     fused.train()
