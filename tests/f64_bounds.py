@@ -45,6 +45,45 @@ Batch norm + activation (the arithmetic of csrc/bnact.hip):
     (E_f' likewise: erf_fast's 0.5 * 6.8e-8 in GELU', and y pdf(y) (1 + y^2) u for the exp2 of -y^2/2 on a rounded argument.)
   The mean offset |mu| enters the statistics bound only: given mu, (z - mu) is one rounding of |z - mu|.  A kernel that computes
   z * rstd - mu * rstd instead rounds |z| rstd and |mu| rstd — far above E_xh on a column whose mean is many standard deviations.
+
+Multi-head attention core (the arithmetic of csrc/listsf.hip), per (query, head), s = 1/sqrt(dh), keys >= lens excluded (P = 0 there,
+so the dK / dV rows of padded keys are exactly 0: E = 0 demands equality), keep' = keep / (1 - p) from the kernel's exported mask:
+  forward (`mhsa_fwd`):
+        S = s q.k                   E_S = c u s |q|.|k|
+        P = exp(S - m) / l          E_P = P (e_j + sum_k P_k e_k),   e_j = E_S_j + c u (1 + |S_j - m|)
+    (|S - m| u: the rounding of the exponent's argument, relative to the argument; the online softmax's rescaling factors
+    exp(m_old - m_new) of a key add up to at most |S_j - m| more of it; sum_k P_k e_k is the error of the normaliser l)
+        O = (P keep') V             E_O = c u |P'| |V| + E_P' |V|
+        LSE = m + log l             E_LSE = sum P e + c u (|LSE| + 1)
+  backward (`mhsa_bwd`), given the kernel's own O and LSE (inputs of ptr_mhsa_backward: exact in float64, as bnact_fwd takes the
+  kernel's mean / rstd — the forward's error stays out of the backward's gate):
+        P = exp(S - lse)            E_P = P (E_S + c u (1 + |S - lse|))
+        D = sum O dO                E_D = c u sum |O| |dO|
+        dP = dO V^T                 E_dP = c u |dO| |V|^T
+        dS = P (dP keep' - D) s     E_dS = s (P (E_dP keep' + E_D + c u (|dP keep'| + |D|)) + E_P |dP keep' - D|)
+    (the roundings of dP keep' and of the difference are relative to |dP keep'| + |D|, not to |dS|: they matter where dP keep' ~ D)
+        dQ = dS K                   E_dQ = c u |dS| |K| + E_dS |K|
+        dK = dS^T Q                 E_dK = c u |dS|^T |Q| + E_dS^T |Q|
+        dV = P'^T dO                E_dV = c u |P'|^T |dO| + E_P'^T |dO|
+
+LayerNorm (list_ranker.py:152-174; csrc/listsf.hip layernorm_*_kernel): two-pass mean / UNBIASED variance over the F features of a
+row, eps added to the standard deviation:
+  forward (`layernorm_fwd`):
+        mean = sum x / F            E_mean = c u mean |x|
+        c_i = x_i - mean            E_c = E_mean + u |c|
+        var = sum c^2 / (F - 1)     E_var = (c u sum c^2 + F E_mean^2 + 2 u E_mean sum |c|) / (F - 1)
+    (sum_i (c_i + d)^2 = sum c^2 + F d^2: a shared error d of the mean enters the two-pass variance at second order only.  A one-pass
+    E[x^2] - mean^2 rounds mean^2, and fails this bound on rows whose mean is a few standard deviations)
+        sd = sqrt(var)              E_sd = min(E_var / (2 sd), sqrt(E_var)) + c u sd        (sqrt(E_var): the bound at sd = 0)
+        rinv = 1 / (sd + eps)       E_rinv = rinv^2 (E_sd + c u (sd + eps)) + c u rinv
+        y = a c rinv + b            E_y = |a| (E_c rinv + |c| E_rinv) + c u (|a c rinv| + |y|)
+    A near-constant row (sd ~ u |mean|) gets a bound of the order of |a| c u |mean| / (sd + eps): the kernel's own c_i there are all
+    rounding, and so is y.  (sqrt and the reciprocal count c u, not u: the device's are 1-ulp approximations.)
+  backward (`layernorm_bwd`), given the kernel's stats {mean, rinv, sd}; g = dy a, c = x - mean:
+        dx = rinv (g - mean g) - c k2,   k2 = rinv^2 sum(g c) / (sd (F - 1)),   k2 = 0 on a row with sd = 0 (the kernel's rule: the
+    derivative of 1/(std + eps) is undefined there; autograd gives NaN)
+        E_dx = rinv c u sum|g| / F + |c| rinv^2 c u sum|g c| / (sd (F - 1)) + c u (rinv (|g| + |mean g|) + |c k2|)
+        da = sum_rows dy c rinv     E_da = c u sum |dy c rinv|;      db = sum_rows dy    E_db = c u sum |dy|
 """
 import math
 
@@ -62,6 +101,10 @@ C_X6 = 32.0       # bf16x6 GEMMs (linear_x6.hip, linear_bw_x6.hip, scorer_x6.hip
                   # Scorer chains, either forward: worst 4.4.  A dropped bf16 plane product of the linear forward needs 69.
 C_BNACT = 16.0    # batch-norm statistics / bnact forward / backward (bnact.hip): worst 10.5 (rstd of per-query groups of 128 rows: the one-pass
                   # M2 = sum d^2 - sum d * mean_d cancels against the pivot's offset); everything else <= 2.3; 1.5x headroom
+C_ATTN = 8.0      # attention core forward / backward (listsf.hip mhsa_*_kernel, tests/test_listsf_bounds_gpu.py): worst 4.94 (dK, 3 x 128 keys,
+                  # dh 17, stored dS); dV at 513 and 1031 keys 4.4; O and LSE <= 3.3; 1.6x headroom.  fp32 torch on the CPU: 3.4
+C_LN = 6.0        # LayerNorm forward / backward (listsf.hip layernorm_*_kernel): worst 3.35 (row mean, 32773 x 700); y, dx 3.2 up to
+                  # 262144 x 136; 1.8x headroom.  fp32 torch on the CPU: 3.2
 
 MAX_AMBIGUOUS = 0.01     # at most this fraction of ReLU units (elements) may lie within their bound of the kink (else the bound says little)
 ERF_FAST_ABS = 6.8e-8    # erf_fast's stated maximum absolute error (csrc/bnact.hip)
@@ -407,3 +450,171 @@ def bnact_bwd(z, da, mean, rstd, gamma, beta, af, c, group=0, keep=None, p=0.0, 
             + c * U * gr * (dy.abs() + s1.abs() / n_ + xh.abs() * s2.abs() / n_)) * real
     return dict(dz=dz, E_dz=E_dz, dgamma=sdyx.sum(0), E_dgamma=E_sdyx.sum(0) + c * U * sdyx.abs().sum(0),
                 dbeta=sdy.sum(0), E_dbeta=E_sdy.sum(0) + c * U * sdy.abs().sum(0), amb=amb)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- attention
+def attn_inputs(B, L, F, H, seed=0):
+    """fp32 Q, K, V, dO [B, L, F] shaped to make the attention bounds bite: per-head scales of Q, K and V spread over ~2^10; every
+    other head (head 0 of a one-head call with an even seed) peaked, |S| up to ~60; dO columns scaled 2^-10..1 and ~10 % zero rows.
+    Returns (Q, K, V, dO, lens) with lens [B] int32 = L, 1, then random (B >= 2), or all L (B == 1)."""
+    g = torch.Generator().manual_seed(seed)
+    dh = F // H
+    r = lambda: torch.randn(B, L, H, dh, generator=g, dtype=torch.float64)
+    e = lambda lo, hi: torch.pow(2.0, torch.randint(lo, hi + 1, (1, 1, H, 1), generator=g).double())
+    peaked = ((torch.arange(H) + seed) % 2 == 0).double().reshape(1, 1, H, 1)
+    sq, sk = e(-5, 3), e(-5, 3)
+    sq = peaked * 6.0 + (1 - peaked) * sq                      # S = q.k / sqrt(dh) ~ N(0, sq sk): 6 x 2.5 -> |S| up to ~60
+    sk = peaked * 2.5 + (1 - peaked) * sk
+    Q, K, V = r() * sq, r() * sk, r() * e(-5, 5)
+    dO = torch.randn(B, L, F, generator=g, dtype=torch.float64) * torch.pow(2.0, torch.randint(-10, 1, (1, 1, F), generator=g).double())
+    dO[torch.rand(B, L, generator=g) < 0.1] = 0.0
+    lens = torch.randint(1, L + 1, (B,), generator=g, dtype=torch.int32)
+    lens[0] = L
+    if B >= 2:
+        lens[1] = 1
+    f = lambda t: t.reshape(B, L, F).float().contiguous()
+    return f(Q), f(K), f(V), dO.float().contiguous(), lens
+
+
+def _heads(T, H):
+    """[B, L, F] -> float64 [B, H, L, dh] (heads are column blocks)."""
+    B, L, F = T.shape
+    return d64(T).reshape(B, L, H, F // H).permute(0, 2, 1, 3)
+
+
+def _merge(T):
+    """float64 [B, H, L, dh] -> [B, L, H * dh]."""
+    B, H, L, dh = T.shape
+    return T.permute(0, 2, 1, 3).reshape(B, L, H * dh)
+
+
+def _attn_setup(Q, K, H, lens, keep, p, c):
+    q, k = _heads(Q, H), _heads(K, H)
+    B, _, L, dh = q.shape
+    s = 1.0 / math.sqrt(dh)
+    S = s * (q @ k.transpose(-1, -2))
+    E_S = c * U * s * (q.abs() @ k.abs().transpose(-1, -2))
+    n = d64(lens).long() if lens is not None else torch.full((B,), L, dtype=torch.long)
+    ok = (torch.arange(L)[None, :] < n[:, None]).reshape(B, 1, 1, L)
+    kp = d64(keep) / (1.0 - p) if keep is not None else torch.ones(1, dtype=torch.float64)
+    return q, k, s, S, E_S, ok, kp
+
+
+def mhsa_fwd(Q, K, V, H, keep, p, lens, c):
+    """O = softmax(s Q_h K_h^T, keys < lens) keep' V_h and LSE [B, H, L] with their bounds (module docstring).  keep: the kernel's
+    [B, H, L, L] 1/0 keep mask (ptr_mhsa_dropout_mask) or None.  A query with no key (lens 0) has O = 0, LSE = 0 exactly.
+    Returns (O, E_O, LSE, E_LSE)."""
+    q, k, s, S, E_S, ok, kp = _attn_setup(Q, K, H, lens, keep, p, c)
+    v = _heads(V, H)
+    has = ok.any(-1, keepdim=True)
+    Sm = S.masked_fill(~ok, -math.inf)
+    m = torch.where(has, Sm.amax(-1, keepdim=True), torch.zeros(1, dtype=torch.float64))
+    lse = torch.where(has, torch.logsumexp(Sm, -1, keepdim=True), torch.zeros(1, dtype=torch.float64))
+    P = torch.exp(Sm - torch.where(has, lse, torch.zeros(1, dtype=torch.float64)))
+    e = torch.where(ok, E_S + c * U * (1.0 + (S - m).abs()), torch.zeros(1, dtype=torch.float64))
+    Pe = (P * e).sum(-1, keepdim=True)
+    E_P = P * (e + Pe) + FLT_MIN * ok
+    Pd, E_Pd = P * kp, E_P * kp
+    O = Pd @ v
+    E_O = c * U * (Pd.abs() @ v.abs()) + E_Pd @ v.abs()
+    E_lse = torch.where(has, Pe + c * U * (lse.abs() + 1.0), torch.zeros(1, dtype=torch.float64))
+    return _merge(O), _merge(E_O), lse[..., 0], E_lse[..., 0]
+
+
+def mhsa_bwd(Q, K, V, O_k, dO, lse_k, H, keep, p, lens, c):
+    """dQ, dK, dV of the attention core for output gradient dO, given the kernel's own O and LSE ([B, L, F] and B*H*L), with their
+    bounds (module docstring).  Returns dict(dQ, E_dQ, dK, E_dK, dV, E_dV) as [B, L, F]."""
+    q, k, s, S, E_S, ok, kp = _attn_setup(Q, K, H, lens, keep, p, c)
+    v, o, g = _heads(V, H), _heads(O_k, H), _heads(dO, H)
+    B, _, L, _ = q.shape
+    lse = d64(lse_k).reshape(B, H, L, 1)
+    P = torch.where(ok, torch.exp(S - lse), torch.zeros(1, dtype=torch.float64))
+    E_P = P * (E_S + c * U * (1.0 + (S - lse).abs())) + FLT_MIN * ok
+    D = (o * g).sum(-1, keepdim=True)
+    E_D = c * U * (o.abs() * g.abs()).sum(-1, keepdim=True)
+    dP = g @ v.transpose(-1, -2)
+    E_dP = c * U * (g.abs() @ v.abs().transpose(-1, -2))
+    dPk = dP * kp
+    t = dPk - D
+    dS = P * t * s
+    E_dS = s * (P * (E_dP * kp + E_D + c * U * (dPk.abs() + D.abs())) + E_P * t.abs())
+    Pd, E_Pd = P * kp, E_P * kp
+    aS, tS = dS.abs(), lambda x: x.transpose(-1, -2)
+    res = dict(dQ=dS @ k, E_dQ=c * U * (aS @ k.abs()) + E_dS @ k.abs(),
+               dK=tS(dS) @ q, E_dK=c * U * (tS(aS) @ q.abs()) + tS(E_dS) @ q.abs(),
+               dV=tS(Pd) @ g, E_dV=c * U * (tS(Pd.abs()) @ g.abs()) + tS(E_Pd) @ g.abs())
+    return {key: _merge(val) for key, val in res.items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- LayerNorm
+def layernorm_fwd(x, a2, b2, eps, c):
+    """y = a2 (x - mean) / (sd + eps) + b2 per row (sd unbiased) with its bound, and the statistics the kernel exports.  Returns
+    (y, E_y, stats) with stats = dict(mean, rinv, sd, E_mean, E_rinv, E_sd), each [R]."""
+    x = d64(x)
+    F = x.shape[1]
+    a, b = d64(a2).reshape(1, F), d64(b2).reshape(1, F)
+    mean = x.mean(1, keepdim=True)
+    cc = x - mean
+    var = (cc * cc).sum(1, keepdim=True) / (F - 1)
+    sd = var.sqrt()
+    rinv = 1.0 / (sd + eps)
+    y = a * cc * rinv + b
+    E_mean = c * U * x.abs().mean(1, keepdim=True)
+    E_c = E_mean + U * cc.abs()
+    E_var = (c * U * (cc * cc).sum(1, keepdim=True) + F * E_mean ** 2 + 2 * U * E_mean * cc.abs().sum(1, keepdim=True)) / (F - 1)
+    E_sd = torch.where(sd > 0, torch.minimum(E_var / (2 * sd), E_var.sqrt()), E_var.sqrt()) + c * U * sd
+    E_rinv = rinv ** 2 * (E_sd + c * U * (sd + eps)) + c * U * rinv
+    E_y = a.abs() * (E_c * rinv + cc.abs() * E_rinv) + c * U * ((a * cc * rinv).abs() + y.abs())
+    st = dict(mean=mean[:, 0], rinv=rinv[:, 0], sd=sd[:, 0], E_mean=E_mean[:, 0], E_rinv=E_rinv[:, 0], E_sd=E_sd[:, 0])
+    return y, E_y, st
+
+
+def layernorm_bwd(x, a2, dy, stats_k, c):
+    """dx, da2, db2 of the LayerNorm for output gradient dy, given the kernel's stats [R, 3] = {mean, rinv, sd} (exact inputs), with
+    their bounds.  Rows with sd = 0 drop the second term, as the kernel does.  Returns dict(dx, E_dx, da, E_da, db, E_db)."""
+    x, dy, st = d64(x), d64(dy), d64(stats_k).reshape(-1, 3)
+    F = x.shape[1]
+    a = d64(a2).reshape(1, F)
+    mean, rinv, sd = st[:, 0:1], st[:, 1:2], st[:, 2:3]
+    cc = x - mean
+    gg = dy * a
+    gbar = gg.sum(1, keepdim=True) / F
+    pos = sd > 0
+    den = torch.where(pos, sd * (F - 1), torch.ones(1, dtype=torch.float64))
+    k2 = torch.where(pos, rinv ** 2 * (gg * cc).sum(1, keepdim=True) / den, torch.zeros(1, dtype=torch.float64))
+    E_k2 = torch.where(pos, rinv ** 2 * c * U * (gg * cc).abs().sum(1, keepdim=True) / den, torch.zeros(1, dtype=torch.float64))
+    dx = rinv * (gg - gbar) - cc * k2
+    E_dx = (rinv * c * U * gg.abs().sum(1, keepdim=True) / F + cc.abs() * E_k2
+            + c * U * (rinv * (gg.abs() + gbar.abs()) + (cc * k2).abs()))
+    t = dy * cc * rinv
+    return dict(dx=dx, E_dx=E_dx, da=t.sum(0), E_da=c * U * t.abs().sum(0), db=dy.sum(0), E_db=c * U * dy.abs().sum(0))
+
+
+def ln_inputs(R, F, seed=0):
+    """fp32 [R, F] LayerNorm inputs, a2, b2 and dy: rows of scale 2^-8..2^8, a quarter of them offset by 100..1000x their spread,
+    near-constant rows (spread 2^-20 of the value), exactly constant rows (1.5 x 2^k: sums exact in fp32; and 0.1: not), ~5 % all-zero
+    rows (padded documents); dy rows scaled 2^-12..1 with columns scaled 2^-6..1.  Returns (x, a2, b2, dy, kinds) with kinds [R]:
+    0 plain, 1 offset, 2 near-constant, 3 constant exact, 4 constant inexact, 5 zero."""
+    g = torch.Generator().manual_seed(seed)
+    sc = torch.pow(2.0, torch.randint(-8, 9, (R, 1), generator=g).double())
+    x = torch.randn(R, F, generator=g, dtype=torch.float64) * sc
+    u = torch.rand(R, generator=g)
+    kinds = torch.zeros(R, dtype=torch.long)
+    kinds[u < 0.25] = 1
+    kinds[(u >= 0.25) & (u < 0.3)] = 2
+    kinds[(u >= 0.3) & (u < 0.33)] = 3
+    kinds[(u >= 0.33) & (u < 0.36)] = 4
+    kinds[u >= 0.95] = 5
+    if R >= 6:
+        kinds[:6] = torch.arange(6)                      # every kind at least once
+    off = sc * (100.0 + 900.0 * torch.rand(R, 1, generator=g, dtype=torch.float64))
+    x = torch.where((kinds == 1)[:, None], x + off, x)
+    x = torch.where((kinds == 2)[:, None], off * (1.0 + 2.0 ** -20 * torch.randn(R, F, generator=g, dtype=torch.float64)), x)
+    x = torch.where((kinds == 3)[:, None], 1.5 * sc, x)
+    x = torch.where((kinds == 4)[:, None], 0.1 * torch.ones_like(x), x)
+    x = torch.where((kinds == 5)[:, None], torch.zeros_like(x), x)
+    a2 = 1.0 + 0.5 * torch.randn(F, generator=g, dtype=torch.float64)
+    b2 = 0.1 * torch.randn(F, generator=g, dtype=torch.float64)
+    dy = (torch.randn(R, F, generator=g, dtype=torch.float64) * torch.pow(2.0, torch.randint(-12, 1, (R, 1), generator=g).double())
+          * torch.pow(2.0, torch.randint(-6, 1, (1, F), generator=g).double()))
+    return x.float().contiguous(), a2.float(), b2.float(), dy.float().contiguous(), kinds

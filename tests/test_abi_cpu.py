@@ -195,3 +195,58 @@ def test_runtime_switches_are_read_in_one_place_and_documented():
                 if "os.environ" in line:
                     read |= set(re.findall(r'"(PTR_[A-Z0-9_]+)"', line))
     assert read == _documented_switches(), (sorted(read - _documented_switches()), sorted(_documented_switches() - read))
+
+
+def _listsf_dispatch():
+    """The dispatch rules of csrc/listsf.hip, restated: attention D = ceil(dh / 16) (dispatch_dt), two row tiles per forward wave iff
+    D <= 5 and L > 64, the 8-wave dK / dV kernel iff D >= 7 and L > 64, STORE_DS iff a dS scratch is passed, vector loads iff dh and the
+    row stride are multiples of 4 floats; LayerNorm NI = ceil(F / 64) (1..4, else the generic 0), forward grid <= 8192 blocks of 4 rows,
+    backward <= 1024 (kLnBlocks).  Each rule's constant must still be in the source."""
+    src = open(os.path.join(ROOT, "ptranking_amd", "csrc", "listsf.hip")).read()
+    for needle in ("const int DT = (a.dh + 15) / 16;", "if constexpr (D <= 5) {\n            if (L > 64) return launch.template operator()<2, 4>();",
+                   "if constexpr (D >= 7) {\n                if (L > 64) return launch_dkv.template operator()<8>();",
+                   "return ds_ws ? go(mhsa_bwd_dkv_kernel<D, NW, true>) : go(mhsa_bwd_dkv_kernel<D, NW, false>);",
+                   "const bool vec = ((dh & 3) == 0)", "default: return f.template operator()<8>();",
+                   "const int ni = (F + 63) / 64;", "if (ni == 1) launch.template operator()<1>(); else if (ni == 2) launch.template operator()<2>();",
+                   "else if (ni == 3) launch.template operator()<3>(); else if (ni == 4) launch.template operator()<4>();",
+                   "(R + 3) / 4 < 8192 ? (R + 3) / 4 : 8192", "constexpr int kLnBlocks = 1024;", "(R + 3) / 4 < kLnBlocks ? (R + 3) / 4 : kLnBlocks",
+                   "r += (size_t)gridDim.x * 4"):
+        assert needle in src, f"csrc/listsf.hip no longer contains {needle!r}: restate the dispatch rules here"
+
+    def attn(Bn, L, F, H, mode, ds, packed):
+        dh = F // H
+        D = -(-dh // 16)
+        ld = 3 * F if packed else F
+        return dict(fwd=(D, 2 if D <= 5 and L > 64 else 1), dkv=(D, 8 if D >= 7 and L > 64 else 4, ds),
+                    vec=(dh % 4 == 0 and ld % 4 == 0), L=L, dh=dh, mode=mode, packed=packed)
+
+    def ln(R, F):
+        ni = -(-F // 64)
+        return dict(ni=ni if ni <= 4 else 0, fwd_trips=-(-R // (4 * min(-(-R // 4), 8192))), bwd_trips=-(-R // (4 * min(-(-R // 4), 1024))))
+    return attn, ln
+
+
+def test_listsf_bound_cases_hit_every_dispatch_form():
+    """tests/test_listsf_bounds_gpu.py's case lists launch every attention and LayerNorm kernel form at least once."""
+    import importlib
+    G = importlib.import_module("test_listsf_bounds_gpu")
+    attn, ln = _listsf_dispatch()
+    forms = [attn(*c) for c in G.ATTN_CASES]
+    want_fwd = {(D, rt) for D in range(1, 9) for rt in ((1, 2) if D <= 5 else (1,))}
+    # the product passes the dS scratch from 128 keys on (listsf.py _ds_scratch), where D >= 7 takes the 8-wave dK / dV kernel
+    want_dkv = {(D, nw, ds) for D in range(1, 9) for nw in ((4, 8) if D >= 7 else (4,)) for ds in (False, True) if not (D >= 7 and nw == 4 and ds)}
+    assert want_fwd - {f["fwd"] for f in forms} == set()
+    assert want_dkv - {f["dkv"] for f in forms} == set()
+    assert {f["vec"] for f in forms} == {True, False}
+    assert {f["packed"] for f in forms if f["vec"]} == {True, False} and True in {f["packed"] for f in forms if not f["vec"]}
+    assert all(f["L"] >= 128 for f in forms if f["dkv"][2])
+    assert {f["mode"] for f in forms} == {"eval", "dropout", "lens", "dropout+lens"}
+    assert {7, 32, 33, 64, 65, 128, 129, 256, 257, 513, 1031} <= {f["L"] for f in forms}
+    assert {4, 16, 17, 40, 64, 68, 90, 100, 112, 128} <= {f["dh"] for f in forms}
+    lns = [(ln(R, F), R, F) for R, F in G.LN_CASES]
+    assert {f["ni"] for f, _, _ in lns} == {0, 1, 2, 3, 4}
+    for ni in range(5):
+        assert max(f["fwd_trips"] for f, _, _ in lns if f["ni"] == ni) >= 2, f"NI={ni}: no forward row loop with a second trip"
+        assert max(f["bwd_trips"] for f, _, _ in lns if f["ni"] == ni) >= 8, f"NI={ni}: backward row loop takes few trips"
+    assert {F for _, _, F in lns} == {2, 24, 64, 65, 128, 136, 200, 256, 257, 700}
+    assert (262144, 136) in G.LN_CASES and 1 in {R for _, R, _ in lns}

@@ -1,10 +1,13 @@
 """CPU self-test of tests/f64_bounds.py: fp32 restatements of each dense primitive pass the element-wise float64 gate, and planted faults
 — the kind a bf16x6 or a chunked-reduction kernel can make — fail it while the max-norm `close` the dense-layer GPU tests used before
 passes them (the gap the element-wise gate closes)."""
+import math
+
 import pytest
 import torch
 
 import f64_bounds as B
+import golden_util as G
 
 
 def _bf16_planes(x):
@@ -243,3 +246,263 @@ def test_relu_chain_bounds_pass_an_fp32_mlp_with_dropout():
     for l in range(NL + 1):
         B.gate(Wp[l].grad, ref["dW"][l], ref["E_dW"][l], f"cpu fp32 mlp dW{l}", B.C_FP32)
         B.gate(bp[l].grad, ref["db"][l], ref["E_db"][l], f"cpu fp32 mlp db{l}", B.C_FP32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- attention
+def _fp32_mhsa_fwd(Q, K, V, H, keep, p, lens, KC=32, lens_off=0):
+    """mhsa_fwd_kernel restated in fp32 torch ops: online softmax over KC-key chunks (running max, rescaled sum and accumulator),
+    O = acc (1 / (1-p)) / l, LSE = m + log l.  lens_off: the key mask reaches lens + lens_off keys (planted fault).  Returns (O, LSE)."""
+    Bn, L, F = Q.shape
+    dh = F // H
+    s = torch.tensor(1.0 / math.sqrt(dh), dtype=torch.float32)
+    hv = lambda T: T.reshape(Bn, L, H, dh).permute(0, 2, 1, 3)
+    q, k, v = hv(Q), hv(K), hv(V)
+    kinv = torch.tensor(1.0 / (1.0 - p), dtype=torch.float32) if keep is not None else torch.tensor(1.0)
+    O, LSE = torch.zeros(Bn, H, L, dh), torch.zeros(Bn, H, L)
+    for b in range(Bn):
+        n = min(L, int(lens[b]) + lens_off) if lens is not None else L
+        m, l, acc = torch.full((H, L, 1), -math.inf), torch.zeros(H, L, 1), torch.zeros(H, L, dh)
+        for kc in range(0, n, KC):
+            ke = min(n, kc + KC)
+            S = (q[b] @ k[b, :, kc:ke].transpose(-1, -2)) * s
+            m_new = torch.maximum(m, S.amax(-1, keepdim=True))
+            corr = torch.exp(m - m_new)
+            e = torch.exp(S - m_new)
+            rs = e.sum(-1, keepdim=True)
+            if keep is not None:
+                e = e * keep[b, :, :, kc:ke]
+            l, m = l * corr + rs, m_new
+            acc = acc * corr + e @ v[b, :, kc:ke]
+        if n > 0:
+            O[b] = acc * (kinv / l)
+            LSE[b] = (m + torch.log(l))[..., 0]
+    return O.permute(0, 2, 1, 3).reshape(Bn, L, F), LSE
+
+
+def _fp32_mhsa_bwd(Q, K, V, O, dO, lse, H, keep, p, lens, lens_off=0, ds_twice_tail=False, d_bf16=False):
+    """The backward kernels restated in fp32: P = exp(S - lse), D = rowsum(O dO), dS = P (dP keep' - D) s, dQ = dS K, dK = dS^T Q,
+    dV = P'^T dO.  Planted faults: lens_off (key mask off by lens_off keys), ds_twice_tail (the last head's dS scaled by s twice),
+    d_bf16 (D from a bf16-rounded O).  Returns (dQ, dK, dV)."""
+    Bn, L, F = Q.shape
+    dh = F // H
+    s = torch.tensor(1.0 / math.sqrt(dh), dtype=torch.float32)
+    hv = lambda T: T.reshape(Bn, L, H, dh).permute(0, 2, 1, 3)
+    mg = lambda T: T.permute(0, 2, 1, 3).reshape(Bn, L, F)
+    q, k, v, o, g = hv(Q), hv(K), hv(V), hv(O.bfloat16().float() if d_bf16 else O), hv(dO)
+    n = (lens.long() + lens_off).clamp(max=L) if lens is not None else torch.full((Bn,), L)
+    ok = (torch.arange(L)[None, :] < n[:, None]).reshape(Bn, 1, 1, L)
+    S = (q @ k.transpose(-1, -2)) * s
+    P = torch.where(ok, torch.exp(S - lse.reshape(Bn, H, L, 1)), torch.zeros(1))
+    D = (o * g).sum(-1, keepdim=True)
+    dP = g @ v.transpose(-1, -2)
+    kp = keep * torch.tensor(1.0 / (1.0 - p), dtype=torch.float32) if keep is not None else torch.ones(1)
+    dS = P * (dP * kp - D) * s
+    if ds_twice_tail:
+        dS[:, H - 1] = dS[:, H - 1] * s
+    return mg(dS @ k), mg(dS.transpose(-1, -2) @ q), mg((P * kp).transpose(-1, -2) @ g)
+
+
+def _keep_mask(Bn, H, L, p, seed):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.rand(Bn, H, L, L, generator=g) >= p).float()
+
+
+def _attn_gate(Q, K, V, dO, H, keep, p, lens, what, **faults):
+    """fp32 forward + backward (with faults) through the f64 gates of mhsa_fwd and mhsa_bwd (given the fp32 O and LSE)."""
+    fwd_faults = {k: v for k, v in faults.items() if k == "lens_off"}
+    O, LSE = _fp32_mhsa_fwd(Q, K, V, H, keep, p, lens, **fwd_faults)
+    rO, EO, rL, EL = B.mhsa_fwd(Q, K, V, H, keep, p, lens, B.C_ATTN)
+    B.gate(O, rO, EO, f"{what} O", B.C_ATTN)
+    B.gate(LSE, rL, EL, f"{what} LSE", B.C_ATTN)
+    dQ, dK, dV = _fp32_mhsa_bwd(Q, K, V, O, dO, LSE, H, keep, p, lens, **faults)
+    ref = B.mhsa_bwd(Q, K, V, O, dO, LSE, H, keep, p, lens, B.C_ATTN)
+    B.gate(dV, ref["dV"], ref["E_dV"], f"{what} dV", B.C_ATTN)
+    B.gate(dK, ref["dK"], ref["E_dK"], f"{what} dK", B.C_ATTN)
+    B.gate(dQ, ref["dQ"], ref["E_dQ"], f"{what} dQ", B.C_ATTN)
+    return O, dQ, dK, dV
+
+
+@pytest.mark.parametrize("Bn,L,F,H,mode", [(3, 200, 136, 2, "lens"), (2, 97, 200, 2, "dropout"), (3, 70, 17, 1, "dropout+lens"),
+                                           (1, 33, 64, 4, "eval")])
+def test_fp32_attention_passes_the_gate(Bn, L, F, H, mode):
+    Q, K, V, dO, lens = B.attn_inputs(Bn, L, F, H, seed=L)
+    p = 0.1 if "dropout" in mode else 0.0
+    keep = _keep_mask(Bn, H, L, p, L) if p else None
+    _attn_gate(Q, K, V, dO, H, keep, p, lens if "lens" in mode else None, f"cpu fp32 attention {mode}")
+
+
+def _torch_ref_attention(Q, K, V, dO, H, lens):
+    """The fp32 reference the existing oracle tests compare with (oracle/torch_ref.py, autograd)."""
+    from oracle import torch_ref as T
+    qc, kc, vc = (t.clone().requires_grad_(True) for t in (Q, K, V))
+    out = T.mhsa_core_ref(qc, kc, vc, H, lens=lens)
+    (out * dO).sum().backward()
+    return out.detach(), qc.grad, kc.grad, vc.grad
+
+
+def test_attention_lens_off_by_one_fails_the_gate_and_passes_close():
+    """The key mask admits key lens[b] too, a key with small K and V: in a peaked head (|S| up to ~50) its probability is ~e^-20 or
+    less, so O and the gradients of the real keys move far below 1e-5; but the padded key's dK / dV rows are no longer exactly 0."""
+    Bn, L, F, H = 3, 100, 40, 1
+    Q, K, V, dO, _ = B.attn_inputs(Bn, L, F, H, seed=4)
+    Q *= 0.8
+    lens = torch.tensor([L, L, 60], dtype=torch.int32)
+    K[2, 60] *= 1e-3
+    V[2, 60] *= 1e-3
+    ref = _torch_ref_attention(Q, K, V, dO, H, lens)
+    with pytest.raises(AssertionError, match="element-wise f64 bound failed"):
+        _attn_gate(Q, K, V, dO, H, None, 0.0, lens, "planted: lens off by one", lens_off=1)
+    O, LSE = _fp32_mhsa_fwd(Q, K, V, H, None, 0.0, lens, lens_off=1)
+    dQ, dK, dV = _fp32_mhsa_bwd(Q, K, V, O, dO, LSE, H, None, 0.0, lens, lens_off=1)
+    assert float(dV[2, 60].abs().max()) > 0
+    for name, a, r in zip(("O", "dQ", "dK", "dV"), (O, dQ, dK, dV), ref):
+        G.assert_close(a.numpy(), r.numpy(), f"planted: lens off by one {name}")
+
+
+def test_attention_ds_scaled_twice_on_a_tail_head_fails_the_gate_and_passes_close():
+    """dS of the last head multiplied by 1/sqrt(dh) once more: the tail head's dQ / dK are 10x too small, but its V is 2^-18 of the
+    other head's, so they sit under the old gate's floor of 1e-6 x max."""
+    Bn, L, F, H = 2, 130, 200, 2
+    Q, K, V, dO, lens = B.attn_inputs(Bn, L, F, H, seed=3)
+    V[..., 100:] *= 2.0 ** -18
+    ref = _torch_ref_attention(Q, K, V, dO, H, None)
+    with pytest.raises(AssertionError, match="element-wise f64 bound failed"):
+        _attn_gate(Q, K, V, dO, H, None, 0.0, None, "planted: dS scaled twice", ds_twice_tail=True)
+    O, LSE = _fp32_mhsa_fwd(Q, K, V, H, None, 0.0, None)
+    dQ, dK, dV = _fp32_mhsa_bwd(Q, K, V, O, dO, LSE, H, None, 0.0, None, ds_twice_tail=True)
+    for name, a, r in zip(("O", "dQ", "dK", "dV"), (O, dQ, dK, dV), ref):
+        G.assert_close(a.numpy(), r.numpy(), f"planted: dS scaled twice {name}")
+
+
+def test_attention_d_from_bf16_output_fails_the_gate():
+    Bn, L, F, H = 2, 130, 136, 2
+    Q, K, V, dO, lens = B.attn_inputs(Bn, L, F, H, seed=4)
+    with pytest.raises(AssertionError, match="element-wise f64 bound failed"):
+        _attn_gate(Q, K, V, dO, H, None, 0.0, lens, "planted: D from bf16 O", d_bf16=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- LayerNorm
+def _fp32_ln_fwd(x, a2, b2, eps=1e-6, one_pass=False):
+    """layernorm_fwd_kernel restated in fp32: two-pass mean and unbiased variance (one_pass: (sum x^2 - mean sum x) / (F - 1), planted),
+    eps added to sd.  Returns (y, stats [R, 3] = {mean, 1 / (sd + eps), sd})."""
+    F = x.shape[1]
+    mean = x.sum(1, keepdim=True) / F
+    if one_pass:
+        var = ((x * x).sum(1, keepdim=True) - mean * x.sum(1, keepdim=True)).clamp(min=0) / (F - 1)
+    else:
+        c = x - mean
+        var = (c * c).sum(1, keepdim=True) / (F - 1)
+    sd = torch.sqrt(var)
+    rinv = 1.0 / (sd + eps)
+    return a2 * (x - mean) * rinv + b2, torch.cat([mean, rinv, sd], 1)
+
+
+def _ln_reduce(part):
+    """layernorm_reduce_kernel's order: lane sl (16 of them) adds partials sl, sl + 16, sl + 32, sl + 48 per trip of 64; then the 16
+    lane sums in lane order."""
+    nblk = part.shape[0]
+    at = lambda k: part[k] if k < nblk else torch.zeros(part.shape[1])
+    t = torch.zeros(part.shape[1])
+    for sl in range(16):
+        s = torch.zeros(part.shape[1])
+        for k in range(sl, nblk, 64):
+            s = s + ((at(k) + at(k + 16)) + (at(k + 32) + at(k + 48)))
+        t = t + s
+    return t
+
+
+def _fp32_ln_bwd(x, a2, dy, stats, drop_part=None):
+    """layernorm_bwd_kernel + layernorm_reduce_kernel restated in fp32 (per-block partials of da / db over rows r with
+    (r / 4) % blocks == block, blocks = min(ceil(R / 4), 1024)).  drop_part: that block's partial goes missing (planted).
+    Returns (dx, da, db)."""
+    R, F = x.shape
+    mean, rinv, sd = stats[:, 0:1], stats[:, 1:2], stats[:, 2:3]
+    c = x - mean
+    gg = dy * a2
+    gbar = gg.sum(1, keepdim=True) / F
+    k2 = torch.where(sd > 0, rinv * rinv * (gg * c).sum(1, keepdim=True) / (sd * (F - 1)), torch.zeros(1))
+    dx = rinv * (gg - gbar) - c * k2
+    nblk = min(-(-R // 4), 1024)
+    blk = (torch.arange(R) // 4) % nblk
+    pa = torch.zeros(nblk, F).index_add_(0, blk, dy * c * rinv)
+    pb = torch.zeros(nblk, F).index_add_(0, blk, dy)
+    if drop_part is not None:
+        pa[drop_part] = 0.0
+        pb[drop_part] = 0.0
+    return dx, _ln_reduce(pa), _ln_reduce(pb)
+
+
+def _ln_gate(x, a2, b2, dy, what, eps=1e-6, **faults):
+    y, st = _fp32_ln_fwd(x, a2, b2, eps, one_pass=faults.get("one_pass", False))
+    ry, Ey, rst = B.layernorm_fwd(x, a2, b2, eps, B.C_LN)
+    B.gate(st[:, 0], rst["mean"], rst["E_mean"], f"{what} mean", B.C_LN)
+    B.gate(st[:, 2], rst["sd"], rst["E_sd"], f"{what} sd", B.C_LN)
+    B.gate(st[:, 1], rst["rinv"], rst["E_rinv"], f"{what} rinv", B.C_LN)
+    B.gate(y, ry, Ey, f"{what} y", B.C_LN)
+    dx, da, db = _fp32_ln_bwd(x, a2, dy, st, drop_part=faults.get("drop_part"))
+    ref = B.layernorm_bwd(x, a2, dy, st, B.C_LN)
+    B.gate(dx, ref["dx"], ref["E_dx"], f"{what} dx", B.C_LN)
+    B.gate(da, ref["da"], ref["E_da"], f"{what} da", B.C_LN)
+    B.gate(db, ref["db"], ref["E_db"], f"{what} db", B.C_LN)
+    return y, dx, da, db
+
+
+def test_layernorm_inputs_have_the_stated_rows():
+    x, a2, b2, dy, kinds = B.ln_inputs(5000, 136, seed=1)
+    xd = x.double()
+    sd, mean = xd.std(1), xd.mean(1)
+    assert bool((mean[kinds == 1].abs() > 50 * sd[kinds == 1]).all())
+    assert bool((sd[kinds == 2] < 1e-5 * mean[kinds == 2].abs()).all())
+    assert bool((sd[kinds >= 3] == 0).all()) and bool((x[kinds == 5] == 0).all())
+    assert all(int((kinds == k).sum()) > 10 for k in range(6))
+
+
+@pytest.mark.parametrize("R,F", [(3000, 136), (700, 24), (300, 700), (64, 2), (4101, 65)])
+def test_fp32_layernorm_passes_the_gate(R, F):
+    x, a2, b2, dy, _ = B.ln_inputs(R, F, seed=R + F)
+    _ln_gate(x, a2, b2, dy, f"cpu fp32 layernorm R={R} F={F}")
+
+
+def _torch_ref_layernorm(x, a2, b2, dy):
+    from oracle import torch_ref as T
+    xc, ac, bc = (t.clone().requires_grad_(True) for t in (x, a2, b2))
+    y = T.layer_norm_ref(xc, ac, bc)
+    (y * dy).sum().backward()
+    return y.detach(), xc.grad, ac.grad, bc.grad
+
+
+def test_one_pass_layernorm_variance_fails_the_gate_and_passes_close():
+    """var = (sum x^2 - mean sum x) / (F - 1) on rows whose mean is 5 standard deviations: the roundings of sum x^2 ~ 26 F var move
+    the variance by a few 1e-6 relative — under the 1e-5 of the fp32 comparison, over the two-pass bound."""
+    g = torch.Generator().manual_seed(21)
+    R, F = 2000, 136
+    x = 5.0 + torch.randn(R, F, generator=g)
+    a2, b2, dy = torch.randn(F, generator=g), torch.randn(F, generator=g), torch.randn(R, F, generator=g)
+    _ln_gate(x, a2, b2, dy, "cpu fp32 layernorm offset 5 sd")
+    y, st = _fp32_ln_fwd(x, a2, b2, one_pass=True)
+    dx, da, db = _fp32_ln_bwd(x, a2, dy, st)
+    for name, got, r in zip(("y", "dx", "da", "db"), (y, dx, da, db), _torch_ref_layernorm(x, a2, b2, dy)):
+        G.assert_close(got.numpy(), r.numpy(), f"planted: one-pass variance {name}")
+    with pytest.raises(AssertionError, match="element-wise f64 bound failed"):
+        _ln_gate(x, a2, b2, dy, "planted: one-pass variance", one_pass=True)
+
+
+def test_dropped_layernorm_partial_fails_the_gate_and_passes_close():
+    """32 768 rows in 1024 partials of 32 rows, dy columns scaled 2^-20..1: one partial whose rows carry only the columns below 2^-17 goes
+    missing from da / db."""
+    g = torch.Generator().manual_seed(22)
+    R, F, drop = 32768, 100, 500
+    x = torch.randn(R, F, generator=g)
+    a2, b2 = torch.randn(F, generator=g), torch.randn(F, generator=g)
+    e = torch.randint(-20, 1, (F,), generator=g)
+    e[0], e[1] = 0, -20
+    dy = torch.randn(R, F, generator=g) * torch.pow(2.0, e.float())
+    rows = ((torch.arange(R) // 4) % 1024) == drop
+    dy[rows.nonzero()[:, 0][:, None], (e > -18).nonzero()[:, 0][None, :]] = 0.0
+    _ln_gate(x, a2, b2, dy, "cpu fp32 layernorm 1024 partials")
+    y, st = _fp32_ln_fwd(x, a2, b2)
+    dx, da, db = _fp32_ln_bwd(x, a2, dy, st, drop_part=drop)
+    for name, got, r in zip(("y", "dx", "da", "db"), (y, dx, da, db), _torch_ref_layernorm(x, a2, b2, dy)):
+        G.assert_close(got.numpy(), r.numpy(), f"planted: dropped partial {name}")
+    with pytest.raises(AssertionError, match="element-wise f64 bound failed"):
+        _ln_gate(x, a2, b2, dy, "planted: dropped partial", drop_part=drop)
