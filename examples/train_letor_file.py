@@ -48,8 +48,12 @@ def main():
                           bn_affine=False)}
     cls = getattr(pa, args.model)
     paras = pa.DEFAULT_PARAS[args.model]
-    ranker = cls(sf_para_dict=sf, gpu=True, device=dev) if args.model in ("ListNet", "RankCosine", "RankMSE") else \
-        cls(sf_para_dict=sf, model_para_dict=dict(paras), gpu=True, device=dev)
+    if args.model in ("ListNet", "RankCosine", "RankMSE"):
+        ranker = cls(sf_para_dict=sf, gpu=True, device=dev)
+    elif args.model == "WassRank":              # the reference's own calling convention (ltr.py:173-174)
+        ranker = cls(sf_para_dict=sf, wass_para_dict=dict(paras), gpu=True, device=dev)
+    else:
+        ranker = cls(sf_para_dict=sf, model_para_dict=dict(paras), gpu=True, device=dev)
     ranker.init()
     ks = [1, 3, 5, 10]
     for epoch in range(1, args.epochs + 1):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PTR_ABI_VERSION 5
+#define PTR_ABI_VERSION 6
 #define PTR_MAX_LIST_LEN 4096
 #define PTR_MAX_CUTOFFS 32
 #define PTR_MLP_ACT_LD 112
@@ -115,6 +115,30 @@ int ptr_listmle_fwd_bwd(const float *preds, const int64_t *perm, const int32_t *
  * top_k <= 0: the whole list (top_k=None).  The reference only accepts batch size 1; here every query is independent. */
 int ptr_mdprank_fwd_bwd(const float *preds, const float *labels, const int64_t *perm, const int32_t *lens, int B, int L, int top_k,
                         float gamma, float *loss_out, float *loss_q, float *grad, void *stream);
+
+#define PTR_WASS_COST_P1 0   /* 'p1':  |i - j| (positions)                  wasserstein_cost_mat.py:47-60,121-122 */
+#define PTR_WASS_COST_P2 1   /* 'p2':  |i - j|^2                            :124-125 */
+#define PTR_WASS_COST_EG 2   /* 'eg':  explicit grouping of label gains     :84-111,127-129 */
+#define PTR_WASS_COST_DG 3   /* 'dg':  delta gain |(2^y_i-1) - (2^y_j-1)|   :63-81,131-132 */
+#define PTR_WASS_COST_DDG 4  /* 'ddg': dg * |1/log2(i+2) - 1/log2(j+2)|     :63-81,134-135 */
+
+/* WassRank — replaces ptranking/ltr_adhoc/listwise/wassrank/wassRank.py:43-88 in mode 'SinkhornOT' with smooth_type 'ST' and
+ * norm_type 'BothST': get_explicit_cost_mat (wasserstein_cost_mat.py:113-139), get_normalized_histograms (:181-208) and OldSinkhornOT
+ * (pytorch_wasserstein.py:323-393), forward and backward in one launch.  Per query with n real documents in the given order:
+ *   C_ij from labels and positions (cost_type = PTR_WASS_COST_*): eg: g = gain_base^y - 1, g < 1 -> -non_rele_gap, c = |g_i - g_j|,
+ *   c < 1 -> var_penalty (any pair closer than 1), diagonal 0; dg ignores gain_base (base 2); positions are 0-based;
+ *   b = softmax(labels), a = softmax(m * preds), m = the query's maximum label if scale_by_max_label != 0, else 1;
+ *   log u = log v = -log n, then sh_itr times: log v = log b - LSE_i(log u_i - C_ij/lam), log u = log a - LSE_j(log v_j - C_ij/lam);
+ *   loss_q = sum_ij C_ij exp(log u_i - C_ij/lam + log v_j); loss_out = mean over the B queries (the reference's .mean(0).sum());
+ *   grad = m a_i (G_i - sum_j a_j G_j), G = lam log u centred / B (the reference's grad, then autograd through F.softmax); padded
+ *   documents get 0.
+ * Every log-sum-exp is taken with its own row's maximum: the same mathematics as the reference's log(K @ exp(v - max v)) + max v with
+ * one shift per query, which underflows to log(0) and NaN in fp32; this form is finite whenever the inputs are.  The reference only
+ * runs at batch size 1 (it squeezes the [B,L,L] cost to 2-D); here every query is independent and B = 1 reproduces it.
+ * Errors: PTR_ERR_INVALID_ARG for a NULL pointer, a bad cost_type, lam <= 0 or sh_itr < 0; PTR_ERR_UNSUPPORTED for L > PTR_MAX_LIST_LEN. */
+int ptr_wassrank_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, int cost_type,
+                         float gain_base, float non_rele_gap, float var_penalty, float lam, int sh_itr,
+                         int scale_by_max_label, float *loss_out, float *loss_q, float *grad, void *stream);
 
 /* Device tie-shuffled label-descending order (the role of arg_shuffle_ties, sampling_utils.py:13-28) from a
  * counter-based RNG: same distribution, NOT the torch.randperm stream (not parity-checked, statistically tested). */

@@ -11,7 +11,7 @@ import torch  # noqa: F401  — must be imported first so that OUR .so binds to 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PTR_LIB") or os.path.join(_PKG, "libptranking_amd.so")   # PTR_LIB: an experiment build (build.py --variant)
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 MAX_LIST_LEN = 4096
 MAX_CUTOFFS = 32
 
@@ -32,6 +32,7 @@ SIGNATURES = {
     "ptr_stlistnet_fwd_bwd": [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp],
     "ptr_rankmse_fwd_bwd": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
     "ptr_rankcosine_fwd_bwd": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
+    "ptr_wassrank_fwd_bwd": [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp],
     "ptr_shuffle_ties_order": [_vp, _vp, _i, _i, _u64, _vp, _vp],
     "ptr_sort_desc": [_vp, _vp, _i, _i, _vp, _vp, _vp],
     "ptr_metrics_at_ks": [_vp, _vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -7,6 +7,7 @@ tensors — there is no CPU path (the reference's CPU op sequences are what `ora
 Shapes: preds / labels `[B, L]` (padded, row-major), optional `lens` int32 `[B]`.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -14,9 +15,10 @@ from . import _lib
 
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
-           "softrank_loss", "mdprank_loss", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
+           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
 
 LAMBDALOSS_TYPES = {"NDCG_Loss1": 0, "NDCG_Loss2": 1, "NDCG_Loss2++": 2}   # ptranking/ltr_adhoc/listwise/lambdaloss.py:27
+WASS_COST_TYPES = {"p1": 0, "p2": 1, "eg": 2, "dg": 3, "ddg": 4}   # PTR_WASS_COST_*; wassrank/wasserstein_cost_mat.py:113-139
 
 
 def _check(name, t, dtype=torch.float32, shape=None):
@@ -127,6 +129,34 @@ def rankmse_loss(preds, labels, lens=None):
         out = torch.empty(1, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             _lib.call("ptr_rankmse_fwd_bwd", _lib.ptr(p), _lib.ptr(labels), _lib.ptr(lens), B, L, _lib.ptr(out), _lib.ptr(loss_q),
+                      _lib.ptr(grad), _lib.current_stream(dev))
+        return out.reshape(()), grad
+
+    if preds.requires_grad:
+        return _FusedLoss.apply(preds if preds.is_contiguous() else preds.contiguous(), lambda p: launch(p.detach()))
+    return launch(preds_c)[0]
+
+
+def wassrank_loss(preds, labels, cost_type="eg", lam=0.1, sh_itr=20, gain_base=4.0, non_rele_gap=100.0, var_penalty=math.e,
+                  scale_by_max_label=False, lens=None):
+    """WassRank, ptranking/ltr_adhoc/listwise/wassrank/wassRank.py:43-88 (mode 'SinkhornOT', smooth_type 'ST', norm_type 'BothST'):
+    mean over queries of the entropic Wasserstein distance between softmax(m * preds) and softmax(labels) under the cost `cost_type`
+    ('p1', 'p2', 'eg', 'dg', 'ddg'), sh_itr log-domain Sinkhorn iterations with regulariser lam.  m is the query's maximum label when
+    scale_by_max_label, else 1.  The reference runs at batch size 1 only; here every query is independent (B = 1 reproduces it), and
+    every log-sum-exp takes its own row's maximum, so the loss stays finite where the reference's fp32 evaluation turns NaN."""
+    if cost_type not in WASS_COST_TYPES:
+        raise NotImplementedError(f"WassRank cost_type {cost_type!r} (supported: {sorted(WASS_COST_TYPES)})")
+    preds_c, labels, lens, B, L = _batch(preds.detach(), labels, lens)
+    dev = preds_c.device
+    params = (WASS_COST_TYPES[cost_type], C.c_float(float(gain_base)), C.c_float(float(non_rele_gap)), C.c_float(float(var_penalty)),
+              C.c_float(float(lam)), int(sh_itr), int(bool(scale_by_max_label)))
+
+    def launch(p):
+        loss_q = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
+        grad = torch.empty((B, L), device=dev, dtype=torch.float32)
+        out = torch.empty(1, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.call("ptr_wassrank_fwd_bwd", _lib.ptr(p), _lib.ptr(labels), _lib.ptr(lens), B, L, *params, _lib.ptr(out), _lib.ptr(loss_q),
                       _lib.ptr(grad), _lib.current_stream(dev))
         return out.reshape(()), grad
 

@@ -1,15 +1,18 @@
 """Drop the fused rankers into an installed wildltr/ptranking so that its unchanged pipeline driver picks them up.
 
 `LTREvaluator.load_ranker` instantiates rankers through `globals()[model_id]` of the module
-ptranking/ltr_adhoc/eval/ltr.py (:156-178), so rebinding the six names in that module is all a drop-in needs:
+ptranking/ltr_adhoc/eval/ltr.py (:156-178), so rebinding the names of RANKER_NAMES in that module is all a drop-in needs:
 
     import ptranking_amd
-    ptranking_amd.install()          # RankNet, LambdaRank, LambdaLoss, ApproxNDCG, ListNet, ListMLE -> fused HIP versions
+    ptranking_amd.install()          # RankNet, LambdaRank, LambdaLoss, ApproxNDCG, ListNet, ListMLE, STListNet, RankCosine, RankMSE,
+                                     # SoftRank, WassRank -> fused HIP versions
     LTREvaluator(cuda=0).run(model_id='LambdaRank', ...)   # the reference's own driver, data layer, config, tapes
 
 The installed classes derive from the reference's own AdhocNeuralRanker (ptranking/base/adhoc_ranker.py:7), i.e. the
 scorers (pointsf AND listsf), optimiser config, save/load stay the reference's code; only `custom_loss_function`,
 the train loop's host syncs and the Evaluator metric methods are replaced.  `<Model>Parameter` classes are left alone.
+WassRank is built by load_ranker with its own calling convention (ltr.py:173-174), which the installed class keeps; a WassRank
+configuration with mode='EntropicOT' (or smooth_type='NG') now raises NotImplementedError instead of running the reference's torch code.
 """
 import importlib
 

@@ -10,6 +10,7 @@ ptranking.base.adhoc_ranker.AdhocNeuralRanker when `ptranking_amd.install()` dro
 ptranking.ltr_adhoc.eval.ltr.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -22,7 +23,8 @@ from .listsf import FusedListScorerMixin
 from .scorer import (FlatAdagrad, FlatAdam, FlatRMSprop, FusedPointScorer, FusedScorerMixin, alloc_acts, mlp_forward, x6_wimg_for, x6_image_tag,
                      x6_set_image_tag)
 
-RANKER_NAMES = ("RankNet", "LambdaRank", "LambdaLoss", "ApproxNDCG", "ListNet", "ListMLE", "STListNet", "RankCosine", "RankMSE", "SoftRank")
+RANKER_NAMES = ("RankNet", "LambdaRank", "LambdaLoss", "ApproxNDCG", "ListNet", "ListMLE", "STListNet", "RankCosine", "RankMSE", "SoftRank",
+                "WassRank")
 # SURVEY.md 2 marks these OUT OF SCOPE (the reference's driver cannot reach them): kept as classes for whoever asks for them by name
 # (install(extras=True), pa.DASALC / pa.MDPRank), not part of the default drop-in surface
 EXTRA_RANKER_NAMES = ("DASALC", "MDPRank")
@@ -41,6 +43,8 @@ DEFAULT_PARAS = {
     "SoftRank": dict(model_id="SoftRank", delta=2.0, metric='nDCG', top_k=None),       # listwise/softrank.py:97
     "DASALC": dict(model_id="DASALC"),
     "MDPRank": dict(model_id="MDPRank", temperature=1.0, gamma=1.0, top_k=10, distribution='PL'),   # listwise/mdprank.py:95-96
+    "WassRank": dict(model_id="WassRank", mode='SinkhornOT', sh_itr=20, lam=0.1, smooth_type='ST', norm_type='BothST',   # listwise/wassrank/
+                     cost_type='eg', non_rele_gap=100, var_penalty=math.e, gain_base=4),                                 # wassRank.py:97-104
 }
 
 
@@ -257,6 +261,24 @@ class FusedStepMixin:
         dp.end_step()                            # a query slice recorded by dp.shard_queries() described this step's batch only
         return loss
 
+    def _batch_mean_step(self, loss, b_local):
+        """The step of a loss that is a MEAN over the batch.  Under data parallelism the local gradient (scaled 1/B_local) is turned back
+        into a sum, shipped with B_local in the same bucket, and divided by the global batch size after the single all-reduce."""
+        if not (self.data_parallel and dp.is_distributed()):
+            return self._fused_step(loss)
+        b_local = float(b_local)
+        bucket = self._bucket(extra=2)
+        bucket.zero()
+        loss.backward()
+        bucket.flat[:bucket.numel].mul_(b_local)
+        bucket.extras[0] = b_local
+        bucket.extras[1] = loss.detach() * b_local
+        bucket.all_reduce()
+        b_global = bucket.extras[0].clone()
+        bucket.flat[:bucket.numel].div_(b_global)
+        self.optimizer.step()
+        return bucket.extras[1] / b_global
+
 
 class RankNetLoss(FusedStepMixin):
     _direct_entry = ("ptr_ranknet_fwd_bwd", lambda self, kw: [C.c_float(float(self.sigma))])
@@ -402,24 +424,28 @@ class RankCosineLoss(FusedStepMixin):
 
 class RankMSELoss(FusedStepMixin):
     def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
-        """ptranking/ltr_adhoc/pointwise/rank_mse.py:29-40.  The loss is a MEAN over the batch (the one in-scope loss that is not
-        a sum over queries): under data parallelism the local gradient (scaled 1/B_local) is turned back into a sum, shipped with
-        B_local in the same bucket, and divided by the global batch size after the single all-reduce."""
+        """ptranking/ltr_adhoc/pointwise/rank_mse.py:29-40.  The loss is a MEAN over the batch (not a sum over queries): under data
+        parallelism it takes FusedStepMixin._batch_mean_step's route."""
         loss = F_.rankmse_loss(batch_preds, batch_std_labels, lens=kwargs.get('lens'))
-        if not (self.data_parallel and dp.is_distributed()):
-            return self._fused_step(loss)
-        b_local = float(batch_preds.size(0))
-        bucket = self._bucket(extra=2)
-        bucket.zero()
-        loss.backward()
-        bucket.flat[:bucket.numel].mul_(b_local)
-        bucket.extras[0] = b_local
-        bucket.extras[1] = loss.detach() * b_local
-        bucket.all_reduce()
-        b_global = bucket.extras[0].clone()
-        bucket.flat[:bucket.numel].div_(b_global)
-        self.optimizer.step()
-        return bucket.extras[1] / b_global
+        return self._batch_mean_step(loss, batch_preds.size(0))
+
+
+class WassRankLoss(FusedStepMixin):
+    def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
+        """ptranking/ltr_adhoc/listwise/wassrank/wassRank.py:43-88, mode 'SinkhornOT' (smooth_type 'ST', norm_type 'BothST').  batch_ids,
+        lens and label_type are accepted, none is required, and nothing is printed (the reference prints batch_preds on every call).
+        The reference squeezes the [B,L,L] cost to 2-D and so only runs at batch size 1; here every query is independent, and the loss
+        is the MEAN over the batch, as the reference's .mean(0).sum() — under data parallelism the RankMSE route (_batch_mean_step).
+
+        The predictions are scaled by the query's maximum label when self.TL_AF (= get_tl_af(), read at construction as the reference
+        does) is 'S' or 'ST'.  On the reference's own base, AdhocNeuralRanker.get_tl_af() returns None (adhoc_ranker.py:83-87 has no
+        `return`), so an installed WassRank never scales, exactly as the reference's driver does not; the stand-alone base returns TL_AF
+        from sf_para_dict and does scale for TL_AF 'S'."""
+        wd = self.wass_para_dict
+        loss = F_.wassrank_loss(batch_preds, batch_std_labels, cost_type=wd['cost_type'], lam=wd['lam'], sh_itr=wd['sh_itr'],
+                                gain_base=wd['gain_base'], non_rele_gap=wd['non_rele_gap'], var_penalty=wd['var_penalty'],
+                                scale_by_max_label=self.TL_AF in ('S', 'ST'), lens=kwargs.get('lens'))
+        return self._batch_mean_step(loss, batch_preds.size(0))
 
 
 class ListMLELoss(FusedStepMixin):
@@ -529,8 +555,32 @@ def make_ranker_classes(base=PointScorerRanker):
             self.distribution = model_para_dict['distribution']  # 'PL', 'STPL'
             self.pg_checking = False
 
+    class WassRank(WassRankLoss, FusedScorerMixin, FusedListScorerMixin, DeviceTrainLoop, DeviceEvaluator, base):
+        """ptranking/ltr_adhoc/listwise/wassrank/wassRank.py:22-41 with the reference's constructor (and the driver's calling convention,
+        ltr.py:173-174).  dict_cost_mats / dict_std_dists are kept but never consulted: the ST target histogram is a pure function of the
+        labels and the cost is recomputed inside the kernel, so the reference's per-qid caches change no value."""
+
+        def __init__(self, sf_para_dict, wass_para_dict=None, dict_cost_mats=None, dict_std_dists=None, gpu=False, device=None):
+            base.__init__(self, id='WassRank', sf_para_dict=sf_para_dict, gpu=gpu, device=device)
+            self.TL_AF = self.get_tl_af()
+            self.wass_para_dict = dict(DEFAULT_PARAS['WassRank']) if wass_para_dict is None else wass_para_dict
+            if dict_cost_mats is not None:
+                self.dict_cost_mats = dict_cost_mats
+            if dict_std_dists is not None:
+                self.dict_std_dists = dict_std_dists
+            wd = self.wass_para_dict
+            if wd['mode'] != 'SinkhornOT':     # EntropicOT: autograd through every iteration + a batch-global early stop (host sync per iteration)
+                raise NotImplementedError(f"WassRank mode {wd['mode']!r}: only mode='SinkhornOT' is served")
+            if wd['smooth_type'] != 'ST':      # NG: zero mass on label-0 documents, log(0) — NaN in the reference at any precision
+                raise NotImplementedError(f"WassRank smooth_type {wd['smooth_type']!r}: only smooth_type='ST' is served")
+            if wd.get('norm_type', 'BothST') != 'BothST':
+                raise NotImplementedError(f"WassRank norm_type {wd['norm_type']!r}: only norm_type='BothST' is served")
+            if wd['cost_type'] not in F_.WASS_COST_TYPES:
+                raise NotImplementedError(f"WassRank cost_type {wd['cost_type']!r} (supported: {sorted(F_.WASS_COST_TYPES)})")
+
     out = dict(RankNet=RankNet, LambdaRank=LambdaRank, LambdaLoss=LambdaLoss, ApproxNDCG=ApproxNDCG, ListNet=ListNet,
-               ListMLE=ListMLE, STListNet=STListNet, RankCosine=RankCosine, RankMSE=RankMSE, SoftRank=SoftRank, DASALC=DASALC, MDPRank=MDPRank)
+               ListMLE=ListMLE, STListNet=STListNet, RankCosine=RankCosine, RankMSE=RankMSE, SoftRank=SoftRank, WassRank=WassRank,
+               DASALC=DASALC, MDPRank=MDPRank)
     for name, cls in out.items():
         cls.__name__ = cls.__qualname__ = name
         cls.__module__ = __name__
@@ -542,3 +592,4 @@ RankNet, LambdaRank, LambdaLoss = _standalone["RankNet"], _standalone["LambdaRan
 ApproxNDCG, ListNet, ListMLE = _standalone["ApproxNDCG"], _standalone["ListNet"], _standalone["ListMLE"]
 STListNet, RankCosine, RankMSE = _standalone["STListNet"], _standalone["RankCosine"], _standalone["RankMSE"]
 SoftRank, DASALC, MDPRank = _standalone["SoftRank"], _standalone["DASALC"], _standalone["MDPRank"]
+WassRank = _standalone["WassRank"]
