@@ -228,7 +228,10 @@ lambdarank_ring_kernel(const float *__restrict__ preds, const float *__restrict_
         part = fmaf(Gi[m], inv_log2_pos(i), part);
         Di[m] = inv_log2_pos(in ? rk[m] : i);              // padding keeps positions n..RS-1
     }
-    const float ridcg = 1.0f / wave_sum_dpp(part);
+    // a query of fewer than two documents has no pair: loss and gradients 0, whatever its labels.  Its 1 / IDCG is taken as 0 so that
+    // no NaN (0 * inf for a single irrelevant document) or inf - inf (degenerate() below, for an empty query) reaches them.
+    const float idcg = wave_sum_dpp(part);
+    const float ridcg = n > 1 ? 1.0f / idcg : 0.0f;
 #pragma unroll
     for (int m = 0; m < DPT; ++m) {
         const bool in = lane + 64 * m < n;

@@ -250,3 +250,116 @@ def test_listsf_bound_cases_hit_every_dispatch_form():
         assert max(f["bwd_trips"] for f, _, _ in lns if f["ni"] == ni) >= 8, f"NI={ni}: backward row loop takes few trips"
     assert {F for _, _, F in lns} == {2, 24, 64, 65, 128, 136, 200, 256, 257, 700}
     assert (262144, 136) in G.LN_CASES and 1 in {R for _, R, _ in lns}
+
+
+def _loss_dispatch():
+    """The dispatch rules of the ranking-loss entry points (pairwise.hip launch_pairwise, approxndcg.hip ptr_approxndcg_fwd_bwd,
+    listwise.hip launch_listnet_vec / launch_listmle_vec, ptr_device.h pick_tiling), restated.  The constants are checked against the source."""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ptranking_amd", "csrc")
+    src = {f: open(os.path.join(csrc, f)).read() for f in ("pairwise.hip", "approxndcg.hip", "listwise.hip", "ptr_device.h", "ptr_ring.h")}
+    for f, needle in [("pairwise.hip", "L <= 512 && sigma > 0.0f && env_int(\"PTR_LAMBDARANK_RING\", 1)"),
+                      ("pairwise.hip", "const int dpt = L <= 64 ? 1 : L <= 128 ? 2 : L <= 256 ? 4 : 8;"),
+                      ("pairwise.hip", "while (QPB > 1 && B < QPB * num_cus()) QPB >>= 1;"),
+                      ("pairwise.hip", "if (dpt >= 4 && QPB > kRing4Waves) QPB = kRing4Waves;"),
+                      ("pairwise.hip", "if (dpt >= 8 && QPB > 4) QPB = 4;"), ("ptr_ring.h", "constexpr int kRing4Waves = 8;"),
+                      ("ptr_ring.h", "const bool ok = open && (empty || (pure && (!have || first == zlab)));"),
+                      ("ptr_ring.h", "constexpr int kRingBlock = 1024;"), ("pairwise.hip", "!WEIGHTED && B > 0 && L <= 32"),
+                      ("approxndcg.hip", "L <= 512 && env_int(\"PTR_APPROX_RING\", 1)"),
+                      ("approxndcg.hip", "L <= 64 ? go(approxndcg_ring_kernel<1>, 1) : L <= 128 ? go(approxndcg_ring_kernel<2>, 2)"),
+                      ("approxndcg.hip", ": L <= 192 ? go(approxndcg_ring_kernel<3>, 3) : L <= 256 ? go(approxndcg_ring_kernel<4>, 4)"),
+                      ("approxndcg.hip", ": L <= 384 ? go(approxndcg_ring_kernel<6>, 6) : go(approxndcg_ring_kernel<8>, 8);"),
+                      ("listwise.hip", "if (L % 4 != 0 || L > 1024) return 0;"),
+                      ("ptr_device.h", "if (L <= 64) return {64, 1};"), ("ptr_device.h", "if (L <= 2048) return {256, 8};")]:
+        assert needle in src[f], f"{f} no longer holds `{needle}`: restate the dispatch rules here"
+
+    def tiling(L):
+        return (64, 1) if L <= 64 else (64, 2) if L <= 128 else (256, 1) if L <= 256 else (256, 2) if L <= 512 else \
+            (256, 4) if L <= 1024 else (256, 8) if L <= 2048 else (256, 16)
+
+    def lambdarank(B, L, sigma, ring):
+        if L <= 512 and sigma > 0 and ring:
+            dpt = 1 if L <= 64 else 2 if L <= 128 else 4 if L <= 256 else 8
+            qpb = 16
+            while qpb > 1 and B < qpb * 256:
+                qpb >>= 1
+            qpb = min(qpb, 8) if dpt >= 4 else qpb
+            qpb = min(qpb, 4) if dpt >= 8 else qpb
+            cap = 16 if dpt < 4 else 8 if dpt < 8 else 4
+            return ("ring", dpt, "full" if qpb == cap else "shrunk")
+        return ("lds",) + tiling(L)
+
+    def ranknet(L):
+        return ("half-wave",) if L <= 32 else ("lds",) + tiling(L)
+
+    def approx(L, ring):
+        if L <= 512 and ring:
+            return ("ring", 1 if L <= 64 else 2 if L <= 128 else 3 if L <= 192 else 4 if L <= 256 else 6 if L <= 384 else 8)
+        return ("lds",) + tiling(L)
+
+    def listwise(L, unaligned):
+        if L % 4 or L > 1024 or unaligned:
+            return ("lds",)
+        return ("vec", 1 if L <= 256 else 2 if L <= 512 else 4, 16 if L <= 64 else 32 if L <= 128 else 64)
+
+    return lambdarank, ranknet, approx, listwise
+
+
+def _ring_z(labels, n, dpt):
+    """Z of the LambdaRank ring kernel (ptr_ring.h): trailing slots (documents 64k..64k+63) whose real documents all carry one label,
+    the same one from slot to slot; empty slots count."""
+    z, zlab, have = 0, None, False
+    for k in range(dpt - 1, -1, -1):
+        real = labels[64 * k:min(64 * (k + 1), n)]
+        empty = 64 * k >= n
+        pure = empty or bool((real == real[0]).all())
+        if not (empty or (pure and (not have or real[0] == zlab))):
+            break
+        if not empty:
+            zlab, have = real[0], True
+        z += 1
+    return z
+
+
+def test_loss_bound_cases_hit_every_dispatch_form():
+    """tests/test_loss_bounds_gpu.py's case lists launch every form of the LambdaRank, RankNet, ApproxNDCG, ListNet and ListMLE kernels."""
+    import importlib
+    G = importlib.import_module("test_loss_bounds_gpu")
+    lambdarank, ranknet, approx, listwise = _loss_dispatch()
+    tilings = {(64, 1), (64, 2), (256, 1), (256, 2), (256, 4), (256, 8), (256, 16)}
+    lr = {lambdarank(B, L, s, r) for B, L, s, _, _, _, r, _ in G.LAMBDARANK_CASES}
+    # every ring form, its workgroup shrunk (B < waves x CUs) and full
+    assert {("ring", d, w) for d in (1, 2, 4, 8) for w in ("full", "shrunk")} <= lr
+    assert {("lds",) + t for t in tilings} <= lr
+    assert any(c[2] == 0 for c in G.LAMBDARANK_CASES) and any(c[6] == 0 for c in G.LAMBDARANK_CASES)
+    assert any(L > 512 for _, L, *_ in G.LAMBDARANK_CASES)
+    # the ring kernel's equal-label skip, computed from the generated inputs: for DPT 2, 4 and 8, queries with no skipped slot (Z = 0),
+    # with trailing slots of real documents of one grade (label-sorted lists), and with empty trailing slots only
+    zs = {}
+    for c in G.LAMBDARANK_CASES:
+        B, L, s, _, _, _, r, _ = c
+        f = lambdarank(B, L, s, r)
+        if f[0] != "ring" or f[1] == 1:
+            continue
+        p, y, n, _ = G.lambdarank_inputs(c)
+        for q in range(B):
+            z = _ring_z(y[q], int(n[q]), f[1])
+            real = 0 < z < f[1] and n[q] - 64 * (f[1] - z) >= 32    # a skipped run of >= 32 real documents (z = DPT: degenerate())
+            zs.setdefault(f[1], set()).add("none" if z == 0 else "all" if z == f[1] else "real" if real else "empty")
+    assert all(zs.get(d, set()) >= {"none", "real", "empty"} for d in (2, 4, 8)), zs
+    assert any(B >= 4096 and L == 128 for B, L, *_ in G.LAMBDARANK_CASES)
+    rn = {ranknet(L) for _, L, *_ in G.RANKNET_CASES}
+    assert {("half-wave",)} | {("lds",) + t for t in tilings} <= rn
+    ap = {approx(L, r) for _, L, _, _, _, r, _ in G.APPROX_CASES}
+    assert {("ring", d) for d in (1, 2, 3, 4, 6, 8)} | {("lds",) + t for t in tilings} <= ap
+    assert {(c, o == 1.0) for _, _, _, c, o, _, _ in G.APPROX_CASES} >= {(1, False), (1, True), (0, False)}
+    assert {pre for _, _, pre, *_ in G.APPROX_CASES} == {0, 1}
+    lw = {listwise(L, u) for _, L, _, u in G.LISTWISE_CASES}
+    assert {("vec", 1, 16), ("vec", 1, 32), ("vec", 1, 64), ("vec", 2, 64), ("vec", 4, 64), ("lds",)} <= lw
+    lds = [(L, u) for _, L, _, u in G.LISTWISE_CASES if listwise(L, u) == ("lds",)]
+    assert any(L % 4 for L, _ in lds) and any(L > 1024 for L, _ in lds) and any(u for _, u in lds)
+    import f64_loss_bounds as FL                     # ListMLE's two routes: per wavefront, max - min of the scores below 24 or not
+    for B, L, off, _ in G.LISTWISE_CASES:
+        p, _, n = FL.listwise_inputs(B, L, seed=L + B, offset=1000.0 if off else 0.0)
+        spread = [float(p[q, :n[q]].max() - p[q, :n[q]].min()) for q in range(B) if n[q] > 1]
+        assert min(spread) < 24.0 < max(spread), (B, L)
+    assert any(B % 4 for B, *_ in G.APPROX_CASES) and any(B % 16 for B, *_ in G.LAMBDARANK_CASES)      # B not a multiple of a workgroup

@@ -506,3 +506,170 @@ def test_dropped_layernorm_partial_fails_the_gate_and_passes_close():
         G.assert_close(got.numpy(), r.numpy(), f"planted: dropped partial {name}")
     with pytest.raises(AssertionError, match="element-wise f64 bound failed"):
         _ln_gate(x, a2, b2, dy, "planted: dropped partial", drop_part=drop)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- losses
+# tests/f64_loss_bounds.py: the C oracle (the reference's arithmetic in fp32, oracle/ltr_oracle.c) passes every loss gate on the
+# generated inputs; planted faults pass the rule the loss tests use (golden_util.assert_close on the batch total and the gradient,
+# tests/test_parity_gpu.py loss_and_grad) and fail the new gates.
+import numpy as np  # noqa: E402
+
+import f64_loss_bounds as FL  # noqa: E402
+
+
+def _oracle():
+    from oracle import c_oracle
+    return c_oracle
+
+
+def _old_rule_passes(total, total_ref, grad, grad_ref):
+    try:
+        G.assert_close(np.array(total), np.array(total_ref), "loss")
+        G.assert_close(grad, grad_ref, "grad")
+        return True
+    except AssertionError:
+        return False
+
+
+@pytest.mark.parametrize("L,kw", [(16, {}), (100, dict(quantise=True, offset=1000.0)), (40, dict(mix="yahoo", lens="full"))],
+                         ids=["L16", "L100-quant-offset", "L40-yahoo-full"])
+def test_oracle_pair_losses_pass_the_gate(L, kw):
+    O = _oracle()
+    p, y, n, screened = FL.pair_inputs(48, L, seed=L, **kw)
+    assert screened <= FL.MAX_SCREENED
+    for name, fn, ref in (("ranknet", O.ranknet, FL.ranknet), ("lambdarank", O.lambdarank, FL.lambdarank)):
+        lq, g = fn(p, y, 1.0, n)
+        r = ref(p, y, n, 1.0, FL.C_PAIR)
+        FL.gate_losses(lq, g, r, f"oracle {name} L{L}", FL.C_PAIR, float(lq.astype(np.float64).sum()), FL.batch_total(r, FL.C_PAIR))
+    assert np.isnan(FL.lambdarank(p, y, n, 1.0)["loss_q"][2])              # query 2 has no relevant document
+
+
+@pytest.mark.parametrize("presort,couple", [(1, 1), (0, 1), (1, 0), (0, 0)])
+def test_oracle_approxndcg_passes_the_gate(presort, couple):
+    O = _oracle()
+    p, y, n, _ = FL.pair_inputs(40, 60, sigma=10.0, seed=5, quantise=bool(presort), offset=1000.0 * presort, every_relevant=bool(couple))
+    if not couple:              # a one-document query without a relevant one: the oracle gives 0 * 1 / 0 = 0 there, the kernel NaN
+        n[5:] = np.maximum(n[5:], 2)
+    lo, dcg, inv, g = O.approxndcg(p, y, 10.0, bool(presort), bool(couple), n)
+    r = FL.approxndcg(p, y, n, 10.0, bool(presort), bool(couple), 0.0, FL.C_APPROX)
+    c = FL.C_APPROX
+    FL.gate_nan(dcg, r["dcg_q"], r["E_dcg_q"], "oracle approxndcg dcg_q", c)
+    FL.gate_nan(inv, r["inv_idcg_q"], r["E_inv_idcg_q"], "oracle approxndcg inv_idcg_q", c)
+    FL.gate_nan(g, r["grad"], r["E_grad"], "oracle approxndcg grad", c)
+    FL.gate_nan([lo], [r["loss"]], [r["E_loss"]], "oracle approxndcg loss", c)
+
+
+@pytest.mark.parametrize("L,offset", [(20, 0.0), (64, 1000.0), (130, 0.0)])
+def test_oracle_listwise_losses_pass_the_gate(L, offset):
+    O = _oracle()
+    p, y, n = FL.listwise_inputs(40, L, seed=L, offset=offset)
+    perm = FL.listmle_perm(y, n)
+    c = FL.C_LIST
+    for name, got, ref in (("listnet", O.listnet(p, y, n), FL.listnet(p, y, n, c)),
+                           ("listmle", O.listmle(p, perm, n), FL.listmle(p, perm, n, c)),
+                           ("rankmse", O.rankmse(p, y, n), FL.rankmse(p, y, n, c)),
+                           ("rankcosine", O.rankcosine(p, y, n), FL.rankcosine(p, y, n, c))):
+        FL.gate_losses(got[0], got[1], ref, f"oracle {name} L{L}", c)
+    assert FL.rankcosine(p, y, n, c)["loss_q"][4] == 2.0                    # zero-length query: (1 - 0) / 0.5
+
+
+def test_lambdarank_loss_with_a_slightly_wrong_ln2_fails_the_gate_and_passes_the_old_rule():
+    """The ring kernel scales its log2-domain loss by ln2 / sigma once per query: a ln2 3e-6 off is a relative bias below the old 1e-5."""
+    O = _oracle()
+    p, y, n, _ = FL.pair_inputs(64, 128, seed=3, specials=False)
+    lq, g = O.lambdarank(p, y, 1.0, n)
+    bad = (lq.astype(np.float64) * (1.0 + 3e-6)).astype(np.float32)
+    assert _old_rule_passes(bad.astype(np.float64).sum(), lq.astype(np.float64).sum(), g, g)
+    r = FL.lambdarank(p, y, n, 1.0, FL.C_PAIR)
+    FL.gate_losses(lq, g, r, "lambdarank oracle", FL.C_PAIR)
+    with pytest.raises(AssertionError, match="loss_q"):
+        FL.gate_losses(bad, g, r, "lambdarank ln2 off", FL.C_PAIR)
+
+
+def test_one_wrong_query_loss_in_a_bench_sized_batch_fails_the_gate_and_passes_the_old_rule():
+    """RankNet, B = 4096: one query's loss_q 2 % off (the first query of a slot past a workgroup boundary) moves the batch total by ~5e-6."""
+    O = _oracle()
+    p, y, n, _ = FL.pair_inputs(4096, 8, seed=12, specials=False)
+    lq, g = O.ranknet(p, y, 1.0, n)
+    bad = lq.copy()
+    bad[17 * 16] *= np.float32(1.02)
+    assert _old_rule_passes(bad.astype(np.float64).sum(), lq.astype(np.float64).sum(), g, g)
+    r = FL.ranknet(p, y, n, 1.0, FL.C_PAIR)
+    FL.gate_losses(lq, g, r, "ranknet oracle", FL.C_PAIR)
+    with pytest.raises(AssertionError, match="loss_q"):
+        FL.gate_losses(bad, g, r, "ranknet one query off", FL.C_PAIR)
+
+
+def test_approxndcg_inv_idcg_in_the_neighbours_slot_fails_the_gate():
+    """inv_idcg_q of a workgroup's last query (4 per workgroup) written to its neighbour's slot: no test read these slots before, so the
+    loss and the gradients — all the old rule saw — are the oracle's own."""
+    O = _oracle()
+    p, y, n, _ = FL.pair_inputs(24, 40, sigma=10.0, seed=13, every_relevant=True)
+    lo, dcg, inv, g = O.approxndcg(p, y, 10.0, True, True, n)
+    bad = inv.copy()
+    bad[8] = inv[7]                 # no test read inv_idcg_q before: the loss and the gradients, all the old rule saw, are untouched
+    r = FL.approxndcg(p, y, n, 10.0, True, True, 0.0, FL.C_APPROX)
+    FL.gate_nan(inv, r["inv_idcg_q"], r["E_inv_idcg_q"], "inv_idcg_q oracle", FL.C_APPROX)
+    with pytest.raises(AssertionError):
+        FL.gate_nan(bad, r["inv_idcg_q"], r["E_inv_idcg_q"], "inv_idcg_q in the neighbour's slot", FL.C_APPROX)
+
+
+def test_listnet_normaliser_with_a_low_precision_log_fails_the_gate_and_passes_the_old_rule():
+    """ListNet with log Z carrying 2^-16 relative error (a short log approximation): every query's loss moves by ~1.5e-5 absolute."""
+    O = _oracle()
+    p, y, n = FL.listwise_inputs(64, 64, seed=14)
+    lq, g = O.listnet(p, y, n)
+    zs = np.array([np.exp(p[q, :n[q]].astype(np.float64) - p[q, :n[q]].max()).sum() if n[q] else 1.0 for q in range(len(n))])
+    bad = (lq + np.where(n > 0, np.log(zs) * 2.0 ** -16, 0.0)).astype(np.float32)
+    assert _old_rule_passes(bad.astype(np.float64).sum(), lq.astype(np.float64).sum(), g, g)
+    r = FL.listnet(p, y, n, FL.C_LIST)
+    FL.gate_losses(lq, g, r, "listnet oracle", FL.C_LIST)
+    with pytest.raises(AssertionError, match="loss_q"):
+        FL.gate_losses(bad, g, r, "listnet low-precision log", FL.C_LIST)
+
+
+def _fixture_cases():
+    """(name, family, case) of the reference's own fp32 outputs that the loss gates cover (losses_knife.npz, the threshold band, is not
+    among them)."""
+    out = []
+    for f in ("losses.npz", "losses_big.npz", "losses_long.npz", "siblings.npz"):
+        for fam, cases in G._load(f).items():
+            if fam in ("ranknet", "lambdarank", "approxndcg", "listnet", "listmle", "rankmse", "rankcosine"):
+                out += [(f"{f[:-4]}/{fam}/{k}", fam, cases[k]) for k in sorted(cases) if _in_model(fam, cases[k])]
+    return out
+
+
+def _in_model(fam, case):
+    """Pair-loss cases whose sigma |ds| reaches the screened band or beyond (losses/ranknet/wide: p underflows to 0 in fp32 past
+    x ~ -87, a branch the restatement does not take) stay with their own fp32 tests, as losses_knife.npz does."""
+    if fam not in ("ranknet", "lambdarank"):
+        return True
+    p = np.asarray(case["preds"], np.float64)
+    x = float(case["sigma"]) * np.abs(p[:, :, None] - p[:, None, :]).max()
+    return x < FL.SCREEN_BANDS[0][0]
+
+
+@pytest.mark.parametrize("name,fam,case", _fixture_cases(), ids=[c[0] for c in _fixture_cases()])
+def test_reference_fp32_outputs_pass_the_gate(name, fam, case):
+    """The reference's own fp32 runs (its batch loss total and gradient) against the float64 gates: the total against the summed bound."""
+    p, y, g = case["preds"], case["labels"], case["grad"]
+    if fam in ("ranknet", "lambdarank"):
+        c = FL.C_PAIR
+        r = (FL.ranknet if fam == "ranknet" else FL.lambdarank)(p, y, None, float(case["sigma"]), c)
+        tot, E = FL.batch_total(r, c)
+    elif fam == "approxndcg":
+        c = FL.C_APPROX
+        presort = bool(int(case["presort"])) if "presort" in case else True          # as tests/test_oracle_golden.py runs it
+        r = FL.approxndcg(p, y, None, float(case["alpha"]), presort, True, 0.0, c)
+        tot, E = r["loss"], r["E_loss"]
+    else:
+        c = FL.C_LIST
+        if fam == "listmle":
+            r = FL.listmle(p, case["perm"], None, c)
+        else:
+            r = {"listnet": FL.listnet, "rankmse": FL.rankmse, "rankcosine": FL.rankcosine}[fam](p, y, None, c)
+        tot, E = FL.batch_total(r, c, 1.0 / p.shape[0] if fam == "rankmse" else 1.0)
+    FL.gate_nan([float(case["loss"])], [tot], [E], f"{name} loss", c)
+    if fam == "listmle":        # the reference's autograd gradient through its log-cumsum-exp needs c 4.2 on two cases (c1, c4)
+        return
+    FL.gate_nan(g, r["grad"], r["E_grad"], f"{name} grad", c)
