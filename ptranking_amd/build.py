@@ -4,6 +4,7 @@
 but travels with the tree to the GPU box.  One translation unit per kernel family, linked into one shared library
 whose only runtime dependency is the HIP runtime (libamdhip64) — no torch types anywhere in the ABI.
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -16,7 +17,8 @@ OBJ_DIR = os.path.join(PKG_DIR, "csrc", "build")
 LIB_PATH = os.path.join(PKG_DIR, "libptranking_amd.so")
 ARCH = "gfx950"
 SOURCES = ["abi.hip", "pairwise.hip", "pairwise_ring.hip", "lambdaloss.hip", "approxndcg.hip", "listwise.hip", "wassrank.hip", "metrics.hip", "scorer.hip", "scorer_bwd.hip", "scorer_x6.hip", "scorer_bwd_x6.hip", "scorer_dw_x6.hip", "linear.hip", "linear_x6.hip", "linear_bw_x6.hip", "bnact.hip", "listsf.hip", "train_step.hip", "letor.cpp"]
-HEADERS = ["ptr_device.h", "ptr_dropout.h", "ptr_mlp.h", "ptr_ring.h", "ptr_linear.h", os.path.join("..", "..", "include", "ptranking_amd.h")]
+# every header of csrc/ (globbed: one that is forgotten in a hand-kept list leaves a stale .so behind an incremental build) + the public header
+HEADERS = sorted(os.path.basename(h) for h in glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join("..", "..", "include", "ptranking_amd.h")]
 CXXFLAGS = ["-O3", "-std=c++20", "-fPIC", "-fno-gpu-rdc", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
             "-ffp-contract=off"]
 

@@ -5,7 +5,7 @@
 // Reference: the autograd backward of torch.nn.Linear inside ptranking/base/utils.py:288-356 (`get_stacked_FFNet`) and
 // ptranking/base/list_ranker.py:176-254 (the encoder's projections).
 //
-// Same machine as scorer_dw_x6.hip (fp32 products from six v_mfma_f32_16x16x32_bf16 on exactly split operands, [row][column] bf16 plane images
+// Same machine as scorer_dw_x6.hip (fp32 products from six v_mfma_f32_16x16x32_bf16 on exactly split operands — ptr_x6.h —, [row][column] bf16 plane images
 // in LDS, both MFMA operands through ds_read_b64_tr_b16, slabs of 32 rows prefetched one slab ahead): the NARROW operand (<= 16 MT columns,
 // MT = 7 or 9) is held whole, the WIDE operand streams in passes of at most 256 columns (see the kernel for how the waves share the tiles).
 // Either side of the product can be the narrow one:
@@ -13,19 +13,9 @@
 //   narrow = X  (K <= 140): tile rows are in-features: partial[n * K + k] written with lanes along n; the X image carries a column of ONES
 //                           behind its last feature, so row K of the product IS db (the fused scorer backward's trick).
 // Partials: ws[chunk][N * K + N], the layout of linear_bwd_w_kernel — reduce_chunks_kernel is unchanged.
-#include "ptr_device.h"
+#include "ptr_x6.h"
 
 namespace ptr {
-
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-using i16x4 = __attribute__((ext_vector_type(4))) short;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-union LFrag { bf16x8 v; u32x4 q; uint32_t u[4]; };
-using lds_u32x2_l = __attribute__((address_space(3))) u32x2;
-using lds_i16x4_l = __attribute__((address_space(3))) i16x4;
 
 constexpr int kL6S = 32;                         // rows per slab
 // wide tiles per pass CT = 16 (256 columns), or 8 (128 columns) for the products whose wide side is that small.  The r4 / r5 form (8 waves,
@@ -35,23 +25,6 @@ __host__ __device__ constexpr int l6_wrs(int CT) { return CT == 16 ? 544 : 288; 
 __host__ __device__ constexpr int l6_nrs(int MT) { return MT == 9 ? 288 : 224; }             // narrow image row stride (bytes): 144 / 112 bf16, both = +-32 mod 256
 // the column-sum scratch of the epilogue lies over the wide image (dead by then); CT = 8: 49 / 55 KB per workgroup, two workgroups per CU
 __host__ __device__ constexpr int l6_lds(int MT, int CT) { return 3 * kL6S * l6_wrs(CT) + 3 * kL6S * l6_nrs(MT); }
-
-__device__ __forceinline__ uint32_t l6_cvt_pk(float x0, float x1) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x0, x1}, bf16x2)); }
-__device__ __forceinline__ void l6_split2(float x0, float x1, uint32_t &p1, uint32_t &p2, uint32_t &p3) {      // round-to-nearest split, scorer_x6.hip
-    p1 = l6_cvt_pk(x0, x1);
-    const float r0 = x0 - __uint_as_float(p1 << 16), r1 = x1 - __uint_as_float(p1 & 0xffff0000u);
-    p2 = l6_cvt_pk(r0, r1);
-    const float s0 = r0 - __uint_as_float(p2 << 16), s1 = r1 - __uint_as_float(p2 & 0xffff0000u);
-    p3 = l6_cvt_pk(s0, s1);
-}
-__device__ __forceinline__ uint32_t l6_lds_addr(const void *p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)p; }
-__device__ __forceinline__ void l6_write4(uint32_t addr, int plane_bytes, const f32x4 v) {
-    uint32_t a[3], b[3];
-    l6_split2(v[0], v[1], a[0], a[1], a[2]);
-    l6_split2(v[2], v[3], b[0], b[1], b[2]);
-#pragma unroll
-    for (int p = 0; p < 3; ++p) *reinterpret_cast<lds_u32x2_l *>((uintptr_t)(addr + (uint32_t)(p * plane_bytes))) = u32x2{a[p], b[p]};
-}
 
 // Zn: the narrow operand [R][ldn], NN columns (+ a column of ones at index NN when `ones`); Aw: the wide operand [R][ldw], KW columns, this launch
 // covers its tiles tile0 .. tile0 + ntp - 1.  Element (o, k) of the product -> part[o * s_n + k * s_w] for o < NN, the ones row -> part[bias_off + k];
@@ -79,7 +52,7 @@ linear_bw_x6_kernel(const float *__restrict__ Zn, int ldn, int NN, int ones, con
     const int chunk = ((R + gridDim.x - 1) / gridDim.x + kL6S - 1) / kL6S * kL6S;
     const int r_begin = blockIdx.x * chunk, r_end = min(R, r_begin + chunk);
     const int col0 = 16 * tile0, colE = min(KW, col0 + 16 * ntp);        // this pass: wide columns [col0, colE), ntp <= CT tiles
-    const uint32_t lds0 = l6_lds_addr(smem_l6);
+    const uint32_t lds0 = lds_byte_addr(smem_l6);
 
     // slot geometry recomputed at each use from an opaque thread index (hoisted it costs the registers the accumulators need)
     auto wgeo = [&](int s, int t_, int &row, int &col, bool &ok) __attribute__((always_inline)) {
@@ -125,7 +98,7 @@ linear_bw_x6_kernel(const float *__restrict__ Zn, int ldn, int NN, int ones, con
                 f32x4 v = rw[s];
 #pragma unroll
                 for (int c = 0; c < 4; ++c) v[c] *= okf;
-                l6_write4(lds0 + (uint32_t)(kW_ + row * kL6WRS + 2 * (col - col0)), kL6WPL, v);
+                split_write4(lds0 + (uint32_t)(kW_ + row * kL6WRS + 2 * (col - col0)), kL6WPL, v);
             }
         }
 #pragma unroll
@@ -139,17 +112,8 @@ linear_bw_x6_kernel(const float *__restrict__ Zn, int ldn, int NN, int ones, con
 #pragma unroll
                 for (int c = 0; c < 4; ++c) { v[c] *= okf; zsum[s][c] += v[c]; }
                 if (ones && col == NN && rok) v[0] = 1.0f;            // NN % 4 == 0: the ones column opens a float4 of its own
-                l6_write4(lds0 + (uint32_t)(kZ_ + row * NRS + 2 * col), NPL, v);
+                split_write4(lds0 + (uint32_t)(kZ_ + row * NRS + 2 * col), NPL, v);
             }
-        }
-    };
-    auto read_tr = [&](LFrag (&f)[3], uint32_t img_lane, int plane_bytes, int row_bytes, int t) __attribute__((always_inline)) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_i16x4_l *>((uintptr_t)(img_lane + (uint32_t)(p * plane_bytes + 32 * t))));
-            const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_i16x4_l *>((uintptr_t)(img_lane + (uint32_t)(p * plane_bytes + 32 * t + 16 * row_bytes))));
-            const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-            f[p].u[0] = l2[0]; f[p].u[1] = l2[1]; f[p].u[2] = h2[0]; f[p].u[3] = h2[1];
         }
     };
     const uint32_t tr_w = lds0 + (uint32_t)(kW_ + (4 * g + (j >> 2)) * kL6WRS + 8 * (j & 3));
@@ -166,7 +130,7 @@ linear_bw_x6_kernel(const float *__restrict__ Zn, int ldn, int NN, int ones, con
         stage(r0);
         __syncthreads();
         if (r0 + kL6S < r_end) gload(r0 + kL6S);
-        LFrag xb[NWT][3];
+        Frag xb[NWT][3];
 #pragma unroll
         for (int n = 0; n < NWT; ++n)
             if (W + 8 * n < ntp) read_tr(xb[n], tr_w, kL6WPL, kL6WRS, W + 8 * n);        // wave-uniform: a wave multiplies only the tiles the pass holds
@@ -174,19 +138,12 @@ linear_bw_x6_kernel(const float *__restrict__ Zn, int ldn, int NN, int ones, con
         for (int ml = 0; ml < MTL; ++ml) {
             const int mt = ml * HALVES + half;
             if (W >= ntp || mt >= MT) break;
-            LFrag za[3];
+            Frag za[3];
             read_tr(za, tr_z, NPL, NRS, mt);
 #pragma unroll
             for (int n = 0; n < NWT; ++n) {
                 if (W + 8 * n >= ntp) continue;
-                f32x4 c = acc[n][ml];
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(za[0].v, xb[n][2].v, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(za[1].v, xb[n][1].v, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(za[2].v, xb[n][0].v, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(za[0].v, xb[n][1].v, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(za[1].v, xb[n][0].v, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(za[0].v, xb[n][0].v, c, 0, 0, 0);
-                acc[n][ml] = c;
+                mma6(acc[n][ml], za, xb[n]);
             }
         }
         __syncthreads();

@@ -1,5 +1,5 @@
 // bf16x6 forward / backward-input of the tall-skinny linear layers (r6): Y[R][N] = epi(X[R][K] Wm^T + bias) with every fp32 product as six
-// v_mfma_f32_16x16x32_bf16 products on exactly split operands (fp32 accumulation, fp32 results — the arithmetic of scorer_x6.hip) instead of
+// v_mfma_f32_16x16x32_bf16 products on exactly split operands (fp32 accumulation, fp32 results — the arithmetic of ptr_x6.h) instead of
 // v_mfma_f32_16x16x4_f32: the matrix time of a layer drops by 2.6x and the 136 / 100 / 128-wide layers of the listsf encoder and of the
 // layer-wise pointsf stack become bound by their X and Y streams.  Serves 16-byte aligned rows of any K (whole-K weight image in LDS up to 256 inputs, K in
 // chunks of 128 beyond); narrow outputs and small batches stay on linear.hip's fp32-MFMA kernel (launch_linear_x6 returns < 0).
@@ -19,53 +19,19 @@
 #include "ptr_device.h"
 #include "ptr_dropout.h"
 #include "ptr_linear.h"
+#include "ptr_x6.h"
 
 namespace ptr {
 namespace {
 
-using lx_bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using lx_bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using lx_u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using lx_u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-using lx_i16x4 = __attribute__((ext_vector_type(4))) short;
-using lx_f32x2 = __attribute__((ext_vector_type(2))) float;
-union LxFrag { lx_bf16x8 v; lx_u32x4 q; uint32_t u[4]; };
-using lx_lds_u32x4 = __attribute__((address_space(3))) lx_u32x4;
-using lx_lds_u32x2 = __attribute__((address_space(3))) lx_u32x2;
-__device__ __forceinline__ uint32_t lx_lds_addr(const void *p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)p; }
-__device__ __forceinline__ lx_u32x4 lx_lds16(uint32_t addr) { return *reinterpret_cast<const lx_lds_u32x4 *>((uintptr_t)addr); }
-__device__ __forceinline__ lx_u32x2 lx_lds8(uint32_t addr) { return *reinterpret_cast<const lx_lds_u32x2 *>((uintptr_t)addr); }
+__device__ __forceinline__ u32x4 lx_lds16(uint32_t addr) { return *reinterpret_cast<const lds_u32x4 *>((uintptr_t)addr); }
+__device__ __forceinline__ u32x2 lx_lds8(uint32_t addr) { return *reinterpret_cast<const lds_u32x2 *>((uintptr_t)addr); }
 
 constexpr int kLxNW = 8;          // waves per workgroup (two per SIMD: 256 registers each)
 constexpr int kLxRT = 2;          // 16-document tiles per wave
 constexpr int kLxNT = kLxNW * 64;
 
 __host__ __device__ constexpr int lx_steps(int K) { return (((K + 15) & ~15) + 31) / 32; }      // k-steps incl. a 16-deep tail
-
-__device__ __forceinline__ uint32_t lx_cvt_pk(float x0, float x1) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(lx_f32x2{x0, x1}, lx_bf16x2)); }
-// round-to-nearest split of two fp32 values into one dword of each plane (scorer_x6.hip split_pack2: x = p1 + p2 + p3 exactly)
-__device__ __forceinline__ void lx_split2(float x0, float x1, uint32_t &p1, uint32_t &p2, uint32_t &p3) {
-    p1 = lx_cvt_pk(x0, x1);
-    const float r0 = x0 - __uint_as_float(p1 << 16), r1 = x1 - __uint_as_float(p1 & 0xffff0000u);
-    p2 = lx_cvt_pk(r0, r1);
-    const float s0 = r0 - __uint_as_float(p2 << 16), s1 = r1 - __uint_as_float(p2 & 0xffff0000u);
-    p3 = lx_cvt_pk(s0, s1);
-}
-__device__ __forceinline__ void lx_split4(const f32x4 v, LxFrag (&f)[3], int d) {
-    lx_split2(v[0], v[1], f[0].u[d], f[1].u[d], f[2].u[d]);
-    lx_split2(v[2], v[3], f[0].u[d + 1], f[1].u[d + 1], f[2].u[d + 1]);
-}
-// four consecutive weights of one row -> 8 bytes of each plane image
-__device__ __forceinline__ void lx_put4(uint8_t *dst, int plane, const f32x4 v) {
-    uint32_t a[3], b[3];
-    lx_split2(v[0], v[1], a[0], a[1], a[2]);
-    lx_split2(v[2], v[3], b[0], b[1], b[2]);
-#pragma unroll
-    for (int p = 0; p < 3; ++p) *reinterpret_cast<lx_u32x2 *>(dst + (size_t)p * plane) = lx_u32x2{a[p], b[p]};
-}
-
-// the six products of one fp32 product, small terms first (scorer_x6.hip mma_tile)
-constexpr int kLxA[6] = {0, 1, 2, 0, 1, 0}, kLxB[6] = {2, 1, 0, 1, 0, 0};
 
 // ---- the weight block [n0, n0 + 16 MT) x K as three bf16 plane images in LDS, zero padded (rows past N, k >= K), followed by the bias; batches of four
 // independent loads per thread.  k slots of a 32-deep k-step: lane (j, g) owns k = 4 g .. 4 g + 3 (fragment bytes 0..7) and 16 + 4 g .. 16 + 4 g + 3 (bytes
@@ -102,8 +68,8 @@ __device__ __forceinline__ void lx_stage(const float *__restrict__ W, int K, int
             if (base + u * kLxNT >= n4) continue;
             const int s_ = c[u] >> 3, cc = c[u] & 7;                                     // k-step, four-k group inside it
             const int tl = r[u] >> 4, rj = r[u] & 15;
-            if (s_ < nfull) lx_put4(smem + (size_t)s_ * SL + tl * 1024 + (cc & 3) * 256 + rj * 16 + (cc >> 2) * 8, PL, v[u]);
-            else if (cc < 4) lx_put4(smem + (size_t)s_ * SL + tl * 1024 + cc * 128 + rj * 8, PL, v[u]);
+            if (s_ < nfull) split_put4(smem + (size_t)s_ * SL + tl * 1024 + (cc & 3) * 256 + rj * 16 + (cc >> 2) * 8, PL, v[u]);
+            else if (cc < 4) split_put4(smem + (size_t)s_ * SL + tl * 1024 + cc * 128 + rj * 8, PL, v[u]);
         }
     }
 }
@@ -120,10 +86,10 @@ __device__ __forceinline__ void lx_kstep(uint32_t ab, const f32x4 (&x)[kLxRT][2]
     constexpr int PL = MT * 1024, RT = kLxRT;
     asm volatile("" : "+v"(ab));                  // ab: an LDS byte address.  One base register per k-step, every fragment at an immediate offset (<= 27 KB) from it: left to the compiler, the
                                                   // bases of all k-steps plus the > 64 KB offsets that do not fit the immediate field are hoisted into ~45 registers
-    LxFrag bf[RT][3];
+    Frag bf[RT][3];
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) { lx_split4(x[rt][0], bf[rt], 0); lx_split4(x[rt][1], bf[rt], 2); }
-    LxFrag af[2][3];
+    for (int rt = 0; rt < RT; ++rt) { split_pack4(x[rt][0], bf[rt], 0); split_pack4(x[rt][1], bf[rt], 2); }
+    Frag af[2][3];
 #pragma unroll
     for (int p = 0; p < 3; ++p) af[0][p].q = lx_lds16(ab + p * PL);
 #pragma unroll
@@ -137,7 +103,7 @@ __device__ __forceinline__ void lx_kstep(uint32_t ab, const f32x4 (&x)[kLxRT][2]
         for (int q = 0; q < 6; ++q)
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt)
-                acc[mt][rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt & 1][kLxA[q]].v, bf[rt][kLxB[q]].v, acc[mt][rt], 0, 0, 0);
+                acc[mt][rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt & 1][kSixA[q]].v, bf[rt][kSixB[q]].v, acc[mt][rt], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -146,20 +112,20 @@ template <int MT>
 __device__ __forceinline__ void lx_ktail(uint32_t ab, const f32x4 (&x)[kLxRT][2], f32x4 (&acc)[MT][kLxRT]) {
     constexpr int PL = MT * 1024, RT = kLxRT;
     asm volatile("" : "+v"(ab));
-    LxFrag bf[RT][3];
+    Frag bf[RT][3];
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) lx_split4(x[rt][0], bf[rt], 0);
+    for (int rt = 0; rt < RT; ++rt) split_pack4(x[rt][0], bf[rt], 0);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-        lx_u32x2 af[3];
+        u32x2 af[3];
 #pragma unroll
         for (int p = 0; p < 3; ++p) af[p] = lx_lds8(ab + p * PL + mt * 1024);
 #pragma unroll
         for (int q = 0; q < 6; ++q)
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt)
-                acc[mt][rt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(lx_i16x4, af[kLxA[q]]),
-                                                                         __builtin_bit_cast(lx_i16x4, lx_u32x2{bf[rt][kLxB[q]].u[0], bf[rt][kLxB[q]].u[1]}),
+                acc[mt][rt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(i16x4, af[kSixA[q]]),
+                                                                         __builtin_bit_cast(i16x4, u32x2{bf[rt][kSixB[q]].u[0], bf[rt][kSixB[q]].u[1]}),
                                                                          acc[mt][rt], 0, 0, 0);
     }
 }
@@ -206,7 +172,7 @@ __device__ __forceinline__ void lx_store(const LxEpi &e, const f32x4 (&acc)[MT][
                 for (int c = 0; c < 4; ++c) h[c] = fmaxf(h[c], 0.0f);
             }
             const uint32_t yoff = ok ? (uint32_t)(row[rt] * e.ldy + nb) * 4u : kLxOob;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(lx_u32x4, h), e.Y, (int)yoff, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, h), e.Y, (int)yoff, 0, 0);
         }
 }
 __device__ __forceinline__ LxEpi lx_epi(const LinArgs &a, const float *gate, float *Y, int n0) {
@@ -241,8 +207,8 @@ linear_fwd_x6t_kernel(const float *__restrict__ X, const float *__restrict__ W, 
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, wave = tid >> 6;
     const int ntiles = (R + 16 * RT - 1) / (16 * RT);
     const LxEpi epi = lx_epi(a, gate, Y, n0);
-    const uint32_t afrag = lx_lds_addr(smem_lx) + g * 256 + j * 16;
-    const uint32_t afrag_t = lx_lds_addr(smem_lx) + NFULL * SL + g * 128 + j * 8;
+    const uint32_t afrag = lds_byte_addr(smem_lx) + g * 256 + j * 16;
+    const uint32_t afrag_t = lds_byte_addr(smem_lx) + NFULL * SL + g * 128 + j * 8;
     const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
     // column offsets (floats) of the lane's two 16-byte pieces of every k-step, clamped to column 0 past K (selected away later)
     int ka[NS], kb[NS];
@@ -338,8 +304,8 @@ linear_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ W, c
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, wave = tid >> 6;
     const int ntiles = (R + 16 * RT - 1) / (16 * RT);
     const LxEpi epi = lx_epi(a, gate, Y, n0);
-    const uint32_t afrag = lx_lds_addr(smem_lx) + g * 256 + j * 16;                 // + S SL + p PL + mt 1024: ds_read_b128
-    const uint32_t afrag_t = lx_lds_addr(smem_lx) + nfull * SL + g * 128 + j * 8;   // the tail's 8-byte fragments
+    const uint32_t afrag = lds_byte_addr(smem_lx) + g * 256 + j * 16;                 // + S SL + p PL + mt 1024: ds_read_b128
+    const uint32_t afrag_t = lds_byte_addr(smem_lx) + nfull * SL + g * 128 + j * 8;   // the tail's 8-byte fragments
     const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
 
     // (row, rok, xrow) describe the tile whose X fragments are being loaded / multiplied; the tile loop hands them over one tile early (below)
@@ -450,8 +416,8 @@ linear_fwd_x6c_kernel(const float *__restrict__ X, const float *__restrict__ W, 
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, wave = tid >> 6;
     const int ntiles = (R + 16 * RT - 1) / (16 * RT);
     const LxEpi epi = lx_epi(a, gate, Y, n0);
-    const uint32_t afrag = lx_lds_addr(smem_lx) + g * 256 + j * 16;
-    const uint32_t afrag_t = lx_lds_addr(smem_lx) + g * 128 + j * 8;               // + (local step) SL
+    const uint32_t afrag = lds_byte_addr(smem_lx) + g * 256 + j * 16;
+    const uint32_t afrag_t = lds_byte_addr(smem_lx) + g * 128 + j * 8;               // + (local step) SL
     const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
     const int tiles_per_round = gridDim.x * kLxNW;
     const int nrounds = (ntiles + tiles_per_round - 1) / tiles_per_round;          // every wave walks every round: the chunk loop holds workgroup barriers

@@ -746,5 +746,21 @@ __device__ __forceinline__ void stage_ideal_order(float *S_id, float *Y_id, int 
     __syncthreads();
 }
 
+// ---- wave-level LDS primitives of the kernels that stream through LDS by DMA (scorer_bwd.hip, the bf16x6 kernels)
+// LDS byte address of a pointer into shared memory: what `ds` instructions at hand-made offsets and the DMA's m0 take
+__device__ __forceinline__ uint32_t lds_byte_addr(const void *p) {
+    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)p;
+}
+// 64 lanes x 16 bytes, global (per-lane address) -> LDS (wave-uniform base + lane*16).  Invisible to hipcc's waitcnt bookkeeping:
+// completion is waited for explicitly (s_waitcnt vmcnt before the publishing barrier).
+__device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+// LDS writes of this wave complete (lgkmcnt) -> workgroup barrier.  No fence semantics on purpose: a __syncthreads() would also
+// drain the LDS-DMA and prefetch loads that are meant to stay in flight across the barrier.
+__device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 #endif  // __HIPCC__
 }  // namespace ptr

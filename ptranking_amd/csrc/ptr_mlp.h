@@ -6,6 +6,7 @@
 
 #include "ptr_device.h"
 #include "ptr_dropout.h"
+#include "ptr_x6.h"
 
 namespace ptr {
 
@@ -47,12 +48,10 @@ __host__ __device__ inline int x6_n1(int F) { return (F + 31) / 32; }
 __host__ __device__ inline int x6_nslices(int F, int NL) { return x6_n1(F) + 4 * (NL - 1); }
 #if defined(__HIPCC__)
 // r6: ONE parameter's three bf16 planes written into the image at the place x6_prep_kernel puts them — the optimiser step of the fused train step
-// (reduce_partials_kernel) refreshes the image element by element, so the next step's forward needs no prep launch.  Same split as scorer_x6.hip
-// split_pack2 (round to nearest, v_cvt_pk_bf16_f32), element for element: the image is bit-identical to a fresh x6_prep_kernel run.
+// (reduce_partials_kernel) refreshes the image element by element, so the next step's forward needs no prep launch.  The split is ptr_x6.h's
+// (split_pack1 = one half of the split_pack2 x6_prep_kernel uses): the image is bit-identical to a fresh x6_prep_kernel run.
 // i = index into the flat parameter vector; b_1, w_out and b_out are not part of the image (they live in LDS / registers of the forward).
 __device__ __forceinline__ void x6_img_put(uint8_t *__restrict__ img, int F, int NL, size_t i, float x) {
-    using bf2 = __attribute__((ext_vector_type(2))) __bf16;
-    using f2 = __attribute__((ext_vector_type(2))) float;
     const size_t w1 = (size_t)kH * F;
     int sl, row, g, e;
     if (i < w1) {                                                    // W1[row][k]: slice k / 32, slot (g, e) <-> feature 32 s + 8 g + e
@@ -71,11 +70,8 @@ __device__ __forceinline__ void x6_img_put(uint8_t *__restrict__ img, int F, int
         sl = x6_n1(F) + 4 * (l - 1) + (k >> 5);
         g = (kk & 15) >> 2; e = 4 * (kk >> 4) + (kk & 3);           // hidden layers: slot (g, e) <-> feature 32 s + 16 (e >> 2) + 4 g + (e & 3)
     }
-    const uint16_t p1 = (uint16_t)(__builtin_bit_cast(uint32_t, __builtin_convertvector(f2{x, 0.0f}, bf2)) & 0xffffu);
-    const float r = x - __uint_as_float((uint32_t)p1 << 16);
-    const uint16_t p2 = (uint16_t)(__builtin_bit_cast(uint32_t, __builtin_convertvector(f2{r, 0.0f}, bf2)) & 0xffffu);
-    const float t = r - __uint_as_float((uint32_t)p2 << 16);
-    const uint16_t p3 = (uint16_t)(__builtin_bit_cast(uint32_t, __builtin_convertvector(f2{t, 0.0f}, bf2)) & 0xffffu);
+    uint16_t p1, p2, p3;
+    split_pack1(x, p1, p2, p3);
     uint8_t *at = img + (size_t)sl * kX6SliceBytes + (size_t)(row >> 4) * 1024 + g * 256 + (row & 15) * 16 + e * 2;
     *reinterpret_cast<uint16_t *>(at) = p1;
     *reinterpret_cast<uint16_t *>(at + kX6PlaneBytes) = p2;

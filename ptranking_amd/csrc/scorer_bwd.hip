@@ -163,19 +163,7 @@ template <int NL, int NT1> struct TileMap {
 template <int NL, int NT1> inline constexpr TileMap<NL, NT1> kTM{};
 
 using lds_f = __attribute__((address_space(3))) float;
-__device__ __forceinline__ uint32_t lds_byte_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)p;
-}
-// 64 lanes x 16 bytes, global (per-lane address) -> LDS (wave-uniform base + lane*16).  Invisible to hipcc's waitcnt bookkeeping:
-// completion is waited for explicitly (s_waitcnt vmcnt(0) before the publishing barrier).
-__device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-// LDS writes of this wave complete (lgkmcnt) -> workgroup barrier.  No fence semantics on purpose: a __syncthreads() would also
-// drain the LDS-DMA and prefetch loads that are meant to stay in flight across the barrier.
-__device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (lds_byte_addr, glds16 — the LDS-DMA, waited for with s_waitcnt vmcnt(0) before the publishing barrier — and wg_barrier: ptr_device.h)
 
 // Experiment builds only (-DPTR_BWD_TRACE): shader-clock stamps of workgroup 0's first slabs, one row of 16 stamps per (slab, wave),
 // written behind the partial gradients in `ws` (which is sized for 2 partials per CU; the fused kernel uses one).

@@ -1,4 +1,4 @@
-// Single-pass fused backward of the pointsf scorer on bf16 matrix instructions with fp32 results ("bf16 x 6", see scorer_x6.hip for the
+// Single-pass fused backward of the pointsf scorer on bf16 matrix instructions with fp32 results ("bf16 x 6", see ptr_x6.h for the
 // arithmetic): dZ chain + every weight gradient in ONE kernel that reads X and the stored activations once and never materialises dZ in HBM.
 //
 // Reference: the autograd backward of ptranking/base/point_ranker.py:45-55 + ptranking/base/utils.py:288-356
@@ -27,14 +27,6 @@
 
 namespace ptr {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-using i16x4 = __attribute__((ext_vector_type(4))) short;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-union BFrag { bf16x8 v; u32x4 q; uint32_t u[4]; };
-
 constexpr int kB6S = 32;                        // documents per slab
 constexpr int kB6ZRS = 224, kB6ZPL = kB6S * kB6ZRS, kB6ZIMG = 3 * kB6ZPL;        // 112-column images: row stride, plane, image (21504 B)
 constexpr int kB6XRS = 288, kB6XPL = kB6S * kB6XRS, kB6XIMG = 3 * kB6XPL;        // the X image: 144 columns (27648 B)
@@ -44,20 +36,6 @@ constexpr int kB6_WO = kB6_ST + 3 * kB6STG;                                     
 constexpr int kB6Lds = kB6_WO + 512;
 static_assert(kB6Lds <= 160 * 1024, "LDS budget");
 
-__device__ __forceinline__ uint32_t b6_cvt_pk(float x0, float x1) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x0, x1}, bf16x2)); }
-// two fp32 values -> one dword of each plane (round-to-nearest split, see scorer_x6.hip split_pack2)
-__device__ __forceinline__ void b6_split2(float x0, float x1, uint32_t &p1, uint32_t &p2, uint32_t &p3) {
-    p1 = b6_cvt_pk(x0, x1);
-    const float r0 = x0 - __uint_as_float(p1 << 16), r1 = x1 - __uint_as_float(p1 & 0xffff0000u);
-    p2 = b6_cvt_pk(r0, r1);
-    const float s0 = r0 - __uint_as_float(p2 << 16), s1 = r1 - __uint_as_float(p2 & 0xffff0000u);
-    p3 = b6_cvt_pk(s0, s1);
-}
-using lds_u32x4_b = __attribute__((address_space(3))) u32x4;
-using lds_u32x2_b = __attribute__((address_space(3))) u32x2;
-using lds_f32x4_b = __attribute__((address_space(3))) f32x4;
-using lds_i16x4_b = __attribute__((address_space(3))) i16x4;
-__device__ __forceinline__ uint32_t b6_lds_addr(const void *p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)p; }
 // Global memory is read through buffer resources (32-bit lane offset + scalar offset; out-of-range lanes read zeros): 64-bit per-lane
 // pointers cost two registers per (piece, tile) once hipcc hoists their loop-invariant parts.
 using b6_srd = __attribute__((ext_vector_type(4))) int;
@@ -72,22 +50,11 @@ __device__ __forceinline__ void b6_bdma16(b6_srd srd, uint32_t voff, uint32_t so
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(srd), "s"(soff), "s"(lds_dst) : "memory");
 }
-// four consecutive features of one document -> the three planes of an image (8 bytes each)
-__device__ __forceinline__ void b6_write4(uint32_t addr, int plane_bytes, const f32x4 v) {
-    uint32_t a[3], b[3];
-    b6_split2(v[0], v[1], a[0], a[1], a[2]);
-    b6_split2(v[2], v[3], b[0], b[1], b[2]);
-#pragma unroll
-    for (int p = 0; p < 3; ++p) *reinterpret_cast<lds_u32x2_b *>((uintptr_t)(addr + (uint32_t)(p * plane_bytes))) = u32x2{a[p], b[p]};
-}
-// LDS writes of this wave complete (lgkmcnt) -> workgroup barrier; NOT __syncthreads(): its fence would also drain the DMA / prefetch loads
-__device__ __forceinline__ void b6_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // A scalar the compiler cannot fold: image bases go through this INSIDE the slab loop, or hipcc precomputes one address register per (image,
 // plane, tile) combination — the images lie past the 64 KB ds offset range — hoists the dozens of them out of the loop and spills them
 __device__ __forceinline__ uint32_t b6_opaque(uint32_t x) { asm volatile("" : "+s"(x)); return x; }
 // r6 measured and did not keep: wave 7's two accumulators interleaved, the complementary chain / dW order of the two waves of a SIMD, the
 // chain's epilogue between the dW MFMAs and both document tiles' staging reads up front ("Candidates measured this round")
-#define B6_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16((A).v, (B).v, (C), 0, 0, 0)
 
 template <int NT1>
 __global__ void __launch_bounds__(512, 2)
@@ -102,7 +69,7 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     constexpr int NL = 3;
     const int F = a.F, R = a.R;
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, W = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t lds0 = b6_lds_addr(smem_b6);
+    const uint32_t lds0 = lds_byte_addr(smem_b6);
 #ifdef PTR_B6_TRACE_EDGE      // experiment builds: shader-clock stamps of the kernel's prologue / epilogue (workgroup 0, every wave), behind the phase stamps' area
     unsigned long long *etrace = reinterpret_cast<unsigned long long *>(ws + (size_t)gridDim.x * np_stride) + 8 * 256 + W * 16;
     int nedge = 0;
@@ -145,9 +112,9 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
                     const int k = 32 * s + 8 * g + e;               // out-feature = contraction index (< 96)
                     v[e] = ri < kH ? Wl[(size_t)k * kH + ri] : 0.0f;
                 }
-                BFrag pl[3];
+                Frag pl[3];
 #pragma unroll
-                for (int d = 0; d < 4; ++d) b6_split2(v[2 * d], v[2 * d + 1], pl[0].u[d], pl[1].u[d], pl[2].u[d]);
+                for (int d = 0; d < 4; ++d) split_pack2(v[2 * d], v[2 * d + 1], pl[0].u[d], pl[1].u[d], pl[2].u[d]);
 #pragma unroll
                 for (int p = 0; p < 3; ++p) st[18 + 3 * (3 * c + s) + p] = __builtin_bit_cast(f32x4, pl[p].q);
             }
@@ -156,8 +123,8 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { const int k = 96 + 4 * g + e; v[e] = (ri < kH && k < kH) ? Wl[(size_t)k * kH + ri] : 0.0f; }
                 uint32_t t0[3], t1[3];
-                b6_split2(v[0], v[1], t0[0], t0[1], t0[2]);
-                b6_split2(v[2], v[3], t1[0], t1[1], t1[2]);
+                split_pack2(v[0], v[1], t0[0], t0[1], t0[2]);
+                split_pack2(v[2], v[3], t1[0], t1[1], t1[2]);
 #pragma unroll
                 for (int p = 0; p < 3; ++p) {
                     const int d = 2 * (3 * c + p);                  // dword index among the 12 tail dwords (st[36..38])
@@ -183,25 +150,12 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     const uint32_t tr_z = (uint32_t)((4 * g + (j >> 2)) * kB6ZRS) + 8u * (((uint32_t)j & 3u) ^ (2u * ((uint32_t)g & 1u)));     // transpose-read chunk of a 112-column image (row 4 g + (j >> 2): its swizzle bit is g & 1)
     const uint32_t tr_x = (uint32_t)((4 * g + (j >> 2)) * kB6XRS) + 8u * (((uint32_t)j & 3u) ^ (2u * ((uint32_t)g & 1u)));
 
-    // the slab's fragment of tile t (16 features x 32 documents) of an image, k slot (G, e): e < 4 document 4 G + e, e >= 4 document 16 + 4 G + e - 4
-    auto read_tr = [&](BFrag (&f)[3], uint32_t img_lane, int plane_bytes, int row_bytes, int t) __attribute__((always_inline)) {
+    // (read_tr, ptr_x6.h: the slab's fragment of tile t — 16 features x 32 documents — of an image, from tr_z / tr_x)
+    auto mma6w = [&](f32x4 &c, int w0, const Frag (&bf)[3]) __attribute__((always_inline)) {       // A = the W^T fragment kept in st[w0 .. w0 + 2]
+        Frag af[3];
 #pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_i16x4_b *>((uintptr_t)(img_lane + (uint32_t)(p * plane_bytes + 32 * t))));
-            const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_i16x4_b *>((uintptr_t)(img_lane + (uint32_t)(p * plane_bytes + 32 * t + 16 * row_bytes))));
-            const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-            f[p].u[0] = l2[0]; f[p].u[1] = l2[1]; f[p].u[2] = h2[0]; f[p].u[3] = h2[1];
-        }
-    };
-    auto mma6 = [&](f32x4 &c, const BFrag (&af)[3], const BFrag (&bf)[3]) __attribute__((always_inline)) {
-        c = B6_MFMA(af[0], bf[2], c); c = B6_MFMA(af[1], bf[1], c); c = B6_MFMA(af[2], bf[0], c);
-        c = B6_MFMA(af[0], bf[1], c); c = B6_MFMA(af[1], bf[0], c); c = B6_MFMA(af[0], bf[0], c);
-    };
-    auto mma6w = [&](f32x4 &c, int w0, const BFrag (&bf)[3]) __attribute__((always_inline)) {       // A = the W^T fragment kept in st[w0 .. w0 + 2]
-        const bf16x8 a0 = __builtin_bit_cast(bf16x8, st[w0]), a1 = __builtin_bit_cast(bf16x8, st[w0 + 1]), a2 = __builtin_bit_cast(bf16x8, st[w0 + 2]);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bf[2].v, c, 0, 0, 0); c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, bf[1].v, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, bf[0].v, c, 0, 0, 0); c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bf[1].v, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, bf[0].v, c, 0, 0, 0); c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bf[0].v, c, 0, 0, 0);
+        for (int p = 0; p < 3; ++p) af[p].q = __builtin_bit_cast(u32x4, st[w0 + p]);
+        mma6(c, af, bf);
     };
     // the 16-deep tail of chain layer cl: A = its two dwords per plane out of st[36..38], B = 8 bytes per plane (features 96 + 4 g .. + 3)
     auto mma6t = [&](f32x4 &c, int cl, const u32x2 (&bt)[3]) __attribute__((always_inline)) {       // cl: constant after unrolling
@@ -212,19 +166,18 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
             at[p] = __builtin_bit_cast(i16x4, u32x2{__float_as_uint(st[36 + d / 4][d % 4]), __float_as_uint(st[36 + d / 4][d % 4 + 1])});
             bb[p] = __builtin_bit_cast(i16x4, bt[p]);
         }
-        c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(at[0], bb[2], c, 0, 0, 0); c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(at[1], bb[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(at[2], bb[0], c, 0, 0, 0); c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(at[0], bb[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(at[1], bb[0], c, 0, 0, 0); c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(at[0], bb[0], c, 0, 0, 0);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(at[kSixA[q]], bb[kSixB[q]], c, 0, 0, 0);
     };
     // one dW row: A fragment = dZ tile `mo` of image zimg, B fragments = in-tiles n0 .. n0 + NN - 1 of image aimg.  PIPE: the next B fragment is
     // read while the current one is multiplied (12 registers more: only where the phase has them — not in chain 2, where X is in flight)
     auto dw_row = [&](auto nn_, auto pipe_, int acc0, uint32_t zimg, int mo, uint32_t aimg_lane, int a_plane, int a_row, int n0) __attribute__((always_inline)) {
         constexpr int NN = decltype(nn_)::value;
         constexpr bool PIPE = decltype(pipe_)::value;
-        BFrag za[3];
+        Frag za[3];
         read_tr(za, zimg + tr_z + (uint32_t)(32 * mo), kB6ZPL, kB6ZRS, 0);
         if constexpr (PIPE && NN > 1) {
-            BFrag ab[2][3];
+            Frag ab[2][3];
             read_tr(ab[0], aimg_lane, a_plane, a_row, n0);
 #pragma unroll
             for (int n = 0; n < NN; ++n) {
@@ -236,7 +189,7 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
         } else {
 #pragma unroll
             for (int n = 0; n < NN; ++n) {
-                BFrag ab[3];
+                Frag ab[3];
                 read_tr(ab, aimg_lane, a_plane, a_row, n0 + n);
                 mma6(st[acc0 + n], za, ab);
                 __builtin_amdgcn_sched_barrier(0);        // one fragment in flight: the scheduler otherwise issues every read of the row up front and spills
@@ -279,7 +232,7 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
             f32x4 v = drop4(x2[dt], w0, w1, thr, scale);
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = col + r < F ? v[r] : (col + r == F ? 1.0f : 0.0f);      // the ones column: column F of dW_1 is db_1
-            b6_write4(b6_opaque(lds0 + kB6_XI + (uint32_t)(32 * t)) + wr_x + (uint32_t)(16 * dt * kB6XRS), kB6XPL, v);
+            split_write4(b6_opaque(lds0 + kB6_XI + (uint32_t)(32 * t)) + wr_x + (uint32_t)(16 * dt * kB6XRS), kB6XPL, v);
         }
     };
     auto stage_x = [&](int slab) __attribute__((always_inline)) {
@@ -313,14 +266,14 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     auto staging = [&](uint32_t zdst) __attribute__((always_inline)) {        // zdst: LDS offset (from lds0) of the dZ buffer that receives dZ3
         m2 = 0u; m1 = 0u;
         if (chain) {
-            const f32x4 wo4 = *reinterpret_cast<lds_f32x4_b *>((uintptr_t)(b6_opaque(lds0 + (uint32_t)(kB6_WO + 64 * W)) + (uint32_t)(16 * g)));
+            const f32x4 wo4 = *reinterpret_cast<lds_f32x4 *>((uintptr_t)(b6_opaque(lds0 + (uint32_t)(kB6_WO + 64 * W)) + (uint32_t)(16 * g)));
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
                 // the staging area is a straight copy of two tile-major row tiles (ptr_mlp.h): feature tile W of row tile dt at dt * 7168 + W * 1024, lane (j, g) at j * 64 + 16 g
                 const uint32_t so = b6_opaque(lds0 + (uint32_t)(kB6_ST + 1024 * W)) + (uint32_t)(j * 64 + 16 * g) + (uint32_t)(dt * kActTile * 4);
-                const f32x4 a1 = *reinterpret_cast<lds_f32x4_b *>((uintptr_t)so);
-                const f32x4 a2 = *reinterpret_cast<lds_f32x4_b *>((uintptr_t)(so + kB6STG));
-                const f32x4 a3 = *reinterpret_cast<lds_f32x4_b *>((uintptr_t)(so + 2 * kB6STG));
+                const f32x4 a1 = *reinterpret_cast<lds_f32x4 *>((uintptr_t)so);
+                const f32x4 a2 = *reinterpret_cast<lds_f32x4 *>((uintptr_t)(so + kB6STG));
+                const f32x4 a3 = *reinterpret_cast<lds_f32x4 *>((uintptr_t)(so + 2 * kB6STG));
                 const float ds = dsv[dt];
                 f32x4 z3;
 #pragma unroll
@@ -332,9 +285,9 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
                 }
                 if (W == 0 && g == 0) abo += ds;
                 const uint32_t wo = wr_z + b6_opaque(lds0 + (uint32_t)(32 * W)) + (uint32_t)(16 * dt * kB6ZRS);
-                b6_write4(wo + b6_opaque(zdst), kB6ZPL, z3);
-                b6_write4(wo + kB6_A2, kB6ZPL, a2);
-                b6_write4(wo + kB6_A1, kB6ZPL, a1);
+                split_write4(wo + b6_opaque(zdst), kB6ZPL, z3);
+                split_write4(wo + kB6_A2, kB6ZPL, a2);
+                split_write4(wo + kB6_A1, kB6ZPL, a1);
             }
         }
     };
@@ -358,7 +311,7 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
 #endif
     uint32_t zi = kB6_ZA, zo = kB6_ZB;
     staging(zi);                                                     // slab 0
-    b6_barrier();                                                    // images complete, staging area consumed
+    wg_barrier();                                                    // images complete, staging area consumed
     {
         const int nxt = slab0 + (int)gridDim.x;
         prefetch(nxt < nslabs ? nxt : nslabs - 1);                  // (past the last slab: a redundant copy nobody stages — its dLoss/dscore is never used)
@@ -375,10 +328,10 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
               // (two lambdas called in sequence: written out inline, the same statements get a different register allocation)
               auto chain_part = [&]() __attribute__((always_inline)) {
                 f32x4 cc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-                auto read_b = [&](BFrag (&b)[3], int u) __attribute__((always_inline)) {       // u = 2 s + dt
+                auto read_b = [&](Frag (&b)[3], int u) __attribute__((always_inline)) {       // u = 2 s + dt
 #pragma unroll
                     for (int p = 0; p < 3; ++p)
-                        b[p].q = *reinterpret_cast<lds_u32x4_b *>((uintptr_t)(zin + rd_b + (uint32_t)(p * kB6ZPL + 16 * (u & 1) * kB6ZRS + 64 * (u >> 1))));
+                        b[p].q = *reinterpret_cast<lds_u32x4 *>((uintptr_t)(zin + rd_b + (uint32_t)(p * kB6ZPL + 16 * (u & 1) * kB6ZRS + 64 * (u >> 1))));
                 };
                 u32x2 bt[2][3];                                   // the 16-deep tail's B operands (features 96 + 4 g .. + 3 of both document tiles)
                 auto read_bt = [&]() __attribute__((always_inline)) {
@@ -386,11 +339,11 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
                     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
                         for (int p = 0; p < 3; ++p)
-                            bt[dt][p] = *reinterpret_cast<lds_u32x2_b *>((uintptr_t)(zin + wr_z + (uint32_t)(192 + p * kB6ZPL + 16 * dt * kB6ZRS)));
+                            bt[dt][p] = *reinterpret_cast<lds_u32x2 *>((uintptr_t)(zin + wr_z + (uint32_t)(192 + p * kB6ZPL + 16 * dt * kB6ZRS)));
                 };
                 // r6: the tail operands are read beside the last full slice's MFMAs (± 0, kept)
                 if (c == 0) {                                     // the chain phase without X in flight has the registers for a fragment in flight beside the one being multiplied
-                    BFrag b[2][3];
+                    Frag b[2][3];
                     read_b(b[0], 0);
 #pragma unroll
                     for (int u = 0; u < 6; ++u) {
@@ -403,7 +356,7 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
                 } else {
 #pragma unroll
                     for (int u = 0; u < 6; ++u) {
-                        BFrag b[3];
+                        Frag b[3];
                         read_b(b, u);
                         if (u == 5) read_bt();
                         mma6w(cc[u & 1], 18 + 3 * (3 * c + (u >> 1)), b);
@@ -426,7 +379,7 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
                         const uint32_t row = (uint32_t)(slab * kB6S + 16 * dt + j);
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, dz), zsrd, (int)(row < (uint32_t)R ? row * (kAL * 4) + (uint32_t)(64 * W + 16 * g) : 0xFFFFF000u), 0, 0);
                     } else {
-                        b6_write4(zout + wr_z + (uint32_t)(16 * dt * kB6ZRS), kB6ZPL, dz);
+                        split_write4(zout + wr_z + (uint32_t)(16 * dt * kB6ZRS), kB6ZPL, dz);
                     }
                 }
                 B6_STAMP2();                                      // epilogue done (gating, split, image stores issued)
@@ -443,7 +396,7 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
                 // wave 7: in-tiles 5, 6 of every row.  r6: the two activation fragments are the SAME for all seven rows — read once per phase
                 // (r5: seven times: 126 transpose reads per phase, now 54), only the dZ tile of the row streams, ZD - 1 rows ahead of its MFMAs
                 constexpr int ZD = 2;                             // dZ tiles in flight (two rows ahead measured no faster)
-                BFrag ab5[3], ab6[3], zr[ZD][3];
+                Frag ab5[3], ab6[3], zr[ZD][3];
                 read_tr(zr[0], zin + tr_z, kB6ZPL, kB6ZRS, 0);
                 read_tr(ab5, aim + tr_z, kB6ZPL, kB6ZRS, 5);
                 read_tr(ab6, aim + tr_z, kB6ZPL, kB6ZRS, 6);
@@ -467,7 +420,7 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
             }
             if (c == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the NEXT slab's staging area has landed (issued a phase ago)
             B6_STAMP();
-            b6_barrier();                                            // B2 / B3
+            wg_barrier();                                            // B2 / B3
             B6_STAMP();
         }
         // ---- dW_1: dZ1 (in `zi`) x the X image  ||  the staging pass of the next slab (-> `zo`, A2, A1: nobody reads them in this phase)
@@ -482,7 +435,7 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
             if (chain) {
                 dw_row(std::integral_constant<int, 8>{}, std::true_type{}, 10, za, W, xi, kB6XPL, kB6XRS, 0);
             } else {
-                BFrag xb[3], zr[2][3];                            // wave 7: in-tile 8 of X for every row — one fragment for the phase, the dZ tiles stream
+                Frag xb[3], zr[2][3];                            // wave 7: in-tile 8 of X for every row — one fragment for the phase, the dZ tiles stream
                 read_tr(zr[0], za + tr_z, kB6ZPL, kB6ZRS, 0);
                 read_tr(xb, xi, kB6XPL, kB6XRS, 8);
 #pragma unroll
@@ -495,7 +448,7 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
             }
         }
         B6_STAMP();
-        b6_barrier();                                                // B4: dZ1 / X consumed, next slab's images complete, staging area free
+        wg_barrier();                                                // B4: dZ1 / X consumed, next slab's images complete, staging area free
         B6_STAMP();
         const uint32_t tz = zi; zi = zo; zo = tz;
     }

@@ -5,7 +5,7 @@
 // layer); dropout site 0 recomputed from the key (ptr_dropout.h), as in the kernel this one replaces.
 //
 // Arithmetic: each fp32 operand is split into three bf16 planes (round to nearest) and a product is six v_mfma_f32_16x16x32_bf16 with fp32
-// accumulation (scorer_x6.hip has the error analysis: not above the fp32-MFMA path's).  One workgroup of 8 waves walks its row chunk in slabs of
+// accumulation (ptr_x6.h has the error analysis: not above the fp32-MFMA path's).  One workgroup of 8 waves walks its row chunk in slabs of
 // 32 rows = one MFMA contraction step:
 //   * the X slab [32 x 384 columns of this pass] and the dZ slab [32 x 112] are loaded ONE SLAB AHEAD into registers (16-byte loads, in flight
 //     under the MFMAs of the current slab), then split and written as [row][feature] bf16 plane images in LDS (row strides 800 / 224 B: = 32 mod 256,
@@ -25,15 +25,6 @@
 
 namespace ptr {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-using i16x4 = __attribute__((ext_vector_type(4))) short;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-union DFrag { bf16x8 v; u32x4 q; uint32_t u[4]; };
-using lds_u32x2_d = __attribute__((address_space(3))) u32x2;
-using lds_i16x4_d = __attribute__((address_space(3))) i16x4;
-
 constexpr int kD6S = 32;                         // rows per slab
 // column tiles per pass: 24 (384 columns, eight waves x three tiles: r4 / r5) or — r6, where it costs no extra pass — 16 (sixteen waves: waves 0-7 / 8-15 share the column tiles
 // W, W + 8 and split the seven dZ tiles even / odd; 2 x 4 accumulators per wave, <= 128 registers, four waves per SIMD: the staging pass is issued by twice the
@@ -42,23 +33,6 @@ __host__ __device__ constexpr int d6_xrs(int CT) { return CT == 24 ? 800 : 544; 
 constexpr int kD6ZRS = 224, kD6ZPL = kD6S * kD6ZRS;      // dZ image: 112 bf16 per row
 __host__ __device__ constexpr int d6_lds(int CT) { return 3 * kD6S * d6_xrs(CT) + 3 * kD6ZPL + kD6S * kAL * 4; }      // + bias scratch: 32 x 112 floats
 static_assert(d6_lds(24) <= 160 * 1024 && d6_lds(16) <= 160 * 1024, "LDS budget");
-
-__device__ __forceinline__ uint32_t d6_cvt_pk(float x0, float x1) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x0, x1}, bf16x2)); }
-__device__ __forceinline__ void d6_split2(float x0, float x1, uint32_t &p1, uint32_t &p2, uint32_t &p3) {
-    p1 = d6_cvt_pk(x0, x1);
-    const float r0 = x0 - __uint_as_float(p1 << 16), r1 = x1 - __uint_as_float(p1 & 0xffff0000u);
-    p2 = d6_cvt_pk(r0, r1);
-    const float s0 = r0 - __uint_as_float(p2 << 16), s1 = r1 - __uint_as_float(p2 & 0xffff0000u);
-    p3 = d6_cvt_pk(s0, s1);
-}
-__device__ __forceinline__ uint32_t d6_lds_addr(const void *p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)p; }
-__device__ __forceinline__ void d6_write4(uint32_t addr, int plane_bytes, const f32x4 v) {
-    uint32_t a[3], b[3];
-    d6_split2(v[0], v[1], a[0], a[1], a[2]);
-    d6_split2(v[2], v[3], b[0], b[1], b[2]);
-#pragma unroll
-    for (int p = 0; p < 3; ++p) *reinterpret_cast<lds_u32x2_d *>((uintptr_t)(addr + (uint32_t)(p * plane_bytes))) = u32x2{a[p], b[p]};
-}
 
 template <bool SITE0, int CT, int NW>
 __global__ void __launch_bounds__(NW * 64, 1)
@@ -80,7 +54,7 @@ mlp_bwd_dw_x6_kernel(const float *__restrict__ A, int lda, const float *__restri
     const uint32_t thr = drop_thr(a.p_drop);
     const float scale = (SITE0 && a.p_drop > 0.0f) ? 1.0f / (1.0f - a.p_drop) : 1.0f;
     const int col0 = 16 * nt_base;
-    const uint32_t lds0 = d6_lds_addr(smem_d6);
+    const uint32_t lds0 = lds_byte_addr(smem_d6);
 
     // slot geometry is RECOMPUTED at each use from an opaque copy of the thread index: hoisted out of the slab loop it costs ~24 registers this
     // kernel does not have (21 accumulator tiles + 9 + 3 fragments + 8 prefetch registers)
@@ -134,7 +108,7 @@ mlp_bwd_dw_x6_kernel(const float *__restrict__ A, int lda, const float *__restri
             const float okf = (rok & ok) ? 1.0f : 0.0f;
 #pragma unroll
             for (int c = 0; c < 4; ++c) v[c] *= okf;
-            d6_write4(lds0 + (uint32_t)(kD6_X + row * kD6XRS + 2 * (col - col0)), kD6XPL, v);
+            split_write4(lds0 + (uint32_t)(kD6_X + row * kD6XRS + 2 * (col - col0)), kD6XPL, v);
         }
 #pragma unroll
         for (int s = 0; s < SZ; ++s) {
@@ -145,20 +119,11 @@ mlp_bwd_dw_x6_kernel(const float *__restrict__ A, int lda, const float *__restri
                 f32x4 v = rz[s];
 #pragma unroll
                 for (int c = 0; c < 4; ++c) { v[c] *= okf; zsum[s][c] += v[c]; }
-                d6_write4(lds0 + (uint32_t)(kD6_Z + row * kD6ZRS + 2 * col), kD6ZPL, v);
+                split_write4(lds0 + (uint32_t)(kD6_Z + row * kD6ZRS + 2 * col), kD6ZPL, v);
             }
         }
     };
-    // the fragment of tile t (16 features x 32 rows) of an image: lane (j, g) -> feature 16 t + j, contraction slots = rows {4g..4g+3, 16+4g..16+4g+3}
-    auto read_tr = [&](DFrag (&f)[3], uint32_t img_lane, int plane_bytes, int row_bytes, int t) __attribute__((always_inline)) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_i16x4_d *>((uintptr_t)(img_lane + (uint32_t)(p * plane_bytes + 32 * t))));
-            const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_i16x4_d *>((uintptr_t)(img_lane + (uint32_t)(p * plane_bytes + 32 * t + 16 * row_bytes))));
-            const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-            f[p].u[0] = l2[0]; f[p].u[1] = l2[1]; f[p].u[2] = h2[0]; f[p].u[3] = h2[1];
-        }
-    };
+    // this lane's chunk of the images for read_tr (ptr_x6.h): lane (j, g) -> feature 16 t + j, contraction slots = rows {4g..4g+3, 16+4g..16+4g+3}
     const uint32_t tr_x = lds0 + (uint32_t)(kD6_X + (4 * g + (j >> 2)) * kD6XRS + 8 * (j & 3));
     const uint32_t tr_z = lds0 + (uint32_t)(kD6_Z + (4 * g + (j >> 2)) * kD6ZRS + 8 * (j & 3));
 
@@ -173,26 +138,17 @@ mlp_bwd_dw_x6_kernel(const float *__restrict__ A, int lda, const float *__restri
         stage(r0);
         __syncthreads();
         if (r0 + kD6S < r_end) gload(r0 + kD6S);           // next slab in flight under this slab's MFMAs
-        DFrag xb[NWT][3];
+        Frag xb[NWT][3];
 #pragma unroll
         for (int n = 0; n < NWT; ++n) read_tr(xb[n], tr_x, kD6XPL, kD6XRS, W + 8 * n);
 #pragma unroll
         for (int ml = 0; ml < MTL; ++ml) {
             const int mt = ml * HALVES + half;
             if (mt >= kMT) break;                          // wave-uniform
-            DFrag za[3];
+            Frag za[3];
             read_tr(za, tr_z, kD6ZPL, kD6ZRS, mt);
 #pragma unroll
-            for (int n = 0; n < NWT; ++n) {
-                f32x4 c = acc[n][ml];
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(za[0].v, xb[n][2].v, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(za[1].v, xb[n][1].v, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(za[2].v, xb[n][0].v, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(za[0].v, xb[n][1].v, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(za[1].v, xb[n][0].v, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(za[0].v, xb[n][0].v, c, 0, 0, 0);
-                acc[n][ml] = c;
-            }
+            for (int n = 0; n < NWT; ++n) mma6(acc[n][ml], za, xb[n]);
         }
         __syncthreads();
     }

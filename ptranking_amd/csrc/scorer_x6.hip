@@ -2,11 +2,8 @@
 //
 // Reference: ptranking/base/point_ranker.py:30-55, ptranking/base/utils.py:288-356 ((Dropout -> Linear -> ReLU) x NL -> Linear).
 //
-// Arithmetic.  An fp32 number is EXACTLY the sum of three bf16 pieces (8 + 8 + 8 mantissa bits; split by rounding to nearest, see
-// split_pack2), so  a * b = a1 b1 + (a1 b2 + a2 b1) + (a1 b3 + a2 b2 + a3 b1) + terms below 2^-24 |a b|:  six v_mfma_f32_16x16x32_bf16
-// (fp32 accumulation inside the instruction) do the work of eight v_mfma_f32_16x16x4_f32 at 6 x 16 instead of 8 x 32 issue cycles, with
-// an error against float64 equal to or below the fp32 MFMA's (scratch/bf16x6, tests/test_x6_gpu.py).  The bf16 matrix pipe also runs
-// BESIDE the vector ALU (the fp32 MFMA shares its issue stream), so the dropout generator and the splitting ride in the MFMA gaps.
+// Arithmetic: ptr_x6.h (the exact three-plane split, the six products, their error).  The bf16 matrix pipe also runs BESIDE the vector ALU
+// (the fp32 MFMA shares its issue stream), so the dropout generator and the splitting ride in the MFMA gaps.
 //
 // Data flow ("transposed world", as scorer.hip):  Z^T[feature][doc] = W[feature][k] * A^T[k][doc].  A wave owns 32 documents (two
 // 16-document B tiles) through all layers; an output tile leaves lane (j = l & 15, g = l >> 4) holding document j's features
@@ -23,38 +20,11 @@
 
 namespace ptr {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-union Frag { bf16x8 v; u32x4 q; uint32_t u[4]; };
-
 // (kX6Rows / kX6PlaneBytes / kX6SliceBytes / x6_n1 / x6_nslices: ptr_mlp.h — the optimiser step of the fused train step writes the image too)
 constexpr int kX6Pieces = kX6SliceBytes / 1024;
 constexpr int kX6Ring = 6;                         // slices resident in LDS
 
 __host__ __device__ inline size_t x6_lds_bytes(int NL) { return (size_t)kX6Ring * kX6SliceBytes + ((size_t)NL * kHP + kHP + 16) * sizeof(float); }
-
-// Split by ROUNDING (v_cvt_pk_bf16_f32, round to nearest even): a = p1 + p2 + p3 exactly (|p2| <= 2^-9 |a|, |p3| <= 2^-18 |a|), and the
-// pieces below the first carry either sign — the dropped products a2 b3 + a3 b2 + a3 b3 (<= 2^-26 |a b|) average out.  A split by
-// truncation (two AND / SUB pairs, r3 probe) has all pieces of one sign: on all-positive data every dropped product pulls the same way
-// and the median relative error was 1.6e-7 against 5e-8 for the fp32 MFMA (tests/test_x6_gpu.py all_positive); same instruction count.
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float x0, float x1) {                // {bf16(x0), bf16(x1)} in one dword, element 0 in the low half
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
-}
-// two fp32 values -> one dword of each of the three planes
-__device__ __forceinline__ void split_pack2(float x0, float x1, uint32_t &p1, uint32_t &p2, uint32_t &p3) {
-    p1 = cvt_pk_bf16(x0, x1);
-    const float r0 = x0 - __uint_as_float(p1 << 16), r1 = x1 - __uint_as_float(p1 & 0xffff0000u);
-    p2 = cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - __uint_as_float(p2 << 16), s1 = r1 - __uint_as_float(p2 & 0xffff0000u);
-    p3 = cvt_pk_bf16(s0, s1);
-}
-// four consecutive fp32 values -> dwords d, d+1 of the three plane fragments
-__device__ __forceinline__ void split_pack4(const f32x4 v, Frag (&f)[3], int d) {
-    split_pack2(v[0], v[1], f[0].u[d], f[1].u[d], f[2].u[d]);
-    split_pack2(v[2], v[3], f[0].u[d + 1], f[1].u[d + 1], f[2].u[d + 1]);
-}
 
 // ReLU as ONE instruction: v_med3_f32(x, 0, 3e38) (with +inf the compiler folds it back to fmaxf, which adds a canonicalising
 // v_max_f32 x, x in front under IEEE mode).  NOT inline asm: the hazard recogniser does not look into asm blocks, and a VALU read of an MFMA
@@ -87,15 +57,6 @@ __global__ void __launch_bounds__(256) x6_prep_kernel(const float *__restrict__ 
 #pragma unroll
     for (int p = 0; p < 3; ++p)
         *reinterpret_cast<u32x4 *>(img + (size_t)sl * kX6SliceBytes + (size_t)p * kX6PlaneBytes + (size_t)(row >> 4) * 1024 + g * 256 + (row & 15) * 16) = f[p].q;
-}
-
-using lds_u32x4 = __attribute__((address_space(3))) u32x4;
-__device__ __forceinline__ uint32_t x6_lds_addr(const void *p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)p; }
-// 64 lanes x 16 bytes, global (per-lane address) -> LDS (wave-uniform base + lane * 16); invisible to hipcc's waitcnt bookkeeping
-__device__ __forceinline__ void x6_glds16(const void *gsrc, uint32_t lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
 // Raw buffer resource over [p, p + bytes): stores through it take a 32-bit byte offset and are DROPPED by the hardware when the offset
@@ -166,7 +127,7 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     const uint32_t thr = drop_thr(a.p_drop);
     const float scale = TRAIN ? 1.0f / (1.0f - a.p_drop) : 1.0f;
     const int n1 = x6_n1(F), ns = n1 + 4 * (NL - 1);
-    const uint32_t ring = x6_lds_addr(smem_x6);
+    const uint32_t ring = lds_byte_addr(smem_x6);
     // this lane's 16 bytes of an A fragment (slice / plane / tile by offset): a tile is stored lane-linear — lane l = 16 g + j at byte 16 l —
     // which is what makes a ds_read_b128 conflict free (its 16-lane groups are {0-3, 12-15, 20-27}, ...: row-major [j][g] collides 2-way)
     const uint32_t lane_a = ring + (uint32_t)(lane * 16);
@@ -181,7 +142,7 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
         for (int i = 0; i < PW; ++i) {
             int q = wave * PW + i;
             q = q < kX6Pieces ? q : kX6Pieces - 1;
-            x6_glds16(src + q * 1024, __builtin_amdgcn_readfirstlane(dst + (uint32_t)q * 1024));
+            glds16(src + q * 1024, __builtin_amdgcn_readfirstlane(dst + (uint32_t)q * 1024));
         }
         dma_slice = dma_slice + 1 == ns ? 0 : dma_slice + 1;
         dma_slot = dma_slot + 1 == kX6Ring ? 0 : dma_slot + 1;
@@ -192,7 +153,7 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     if constexpr (STORE && DT == 2) {    // six more operations behind slices 1..4 (see slice_sync): slice 0 once more, into the free slot
 #pragma unroll
         for (int i = 0; i < 6; ++i)
-            x6_glds16(img + (size_t)i * 1024 + lane * 16, __builtin_amdgcn_readfirstlane(ring + (uint32_t)(kX6Ring - 1) * kX6SliceBytes + (uint32_t)i * 1024));
+            glds16(img + (size_t)i * 1024 + lane * 16, __builtin_amdgcn_readfirstlane(ring + (uint32_t)(kX6Ring - 1) * kX6SliceBytes + (uint32_t)i * 1024));
     }
     // slice 0: this wave's pieces have landed when at most the pieces of slices 1..4 (+ the extra six) are outstanding (vmcnt counts in order)
     if constexpr (DT == 4) asm volatile("s_waitcnt vmcnt(24)\n\ts_barrier" ::: "memory");
@@ -228,8 +189,7 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
 
     // bias / w_out rows: ONE opaque base register each + immediate offsets (past the 64 KB `ds` offset range hipcc otherwise keeps a
     // loop-invariant address register per (tile) and spills them)
-    using lds_f32x4 = __attribute__((address_space(3))) f32x4;
-    uint32_t bs_base = x6_lds_addr(Bs) + (uint32_t)g * 16;
+    uint32_t bs_base = lds_byte_addr(Bs) + (uint32_t)g * 16;
     asm volatile("" : "+v"(bs_base));
     uint32_t wo_delta = (uint32_t)NL * (kHP * 4);                // Wo = Bs + NL * 112 floats: a scalar added at the (seven) uses instead of a second register
     asm volatile("" : "+s"(wo_delta));
@@ -249,29 +209,25 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
 #pragma unroll
         for (int p = 0; p < 3; ++p) buf[p].q = *reinterpret_cast<lds_u32x4 *>((uintptr_t)(abase + (uint32_t)(p * kX6PlaneBytes + mt * 1024)));
     };
-    // acc[mt][dt] += the six plane products of a slice, small terms first
+    // acc[mt][dt] += the six plane products of a slice (order: ptr_x6.h), the document tiles interleaved
     auto mma_tile = [&](const Frag (&buf)[3], auto mt_, const Frag (&bf)[DT][3]) __attribute__((always_inline)) {
         constexpr int mt = decltype(mt_)::value;
-        constexpr int kA[6] = {0, 1, 2, 0, 1, 0}, kB[6] = {2, 1, 0, 1, 0, 0};
 #pragma unroll
         for (int q = 0; q < 6; ++q)
 #pragma unroll
-            for (int dt = 0; dt < DT; ++dt) acc[mt][dt] = X6_MFMA(buf[kA[q]], bf[dt][kB[q]], acc[mt][dt]);
+            for (int dt = 0; dt < DT; ++dt) acc[mt][dt] = X6_MFMA(buf[kSixA[q]], bf[dt][kSixB[q]], acc[mt][dt]);
     };
     // r6: the LAST slice of a hidden layer holds only features 96..111 (100 real + the ones feature): its k slots (g, e >= 4) <-> features 112.. are zeros
     // in both operands, so the slice is 16 deep — one v_mfma_f32_16x16x16_bf16 on the first 8 bytes of each fragment (k slot (g, e < 4) <-> feature
     // 96 + 4 g + e) at HALF the matrix-pipe time of the 32-deep instruction that multiplied 16 zeros per lane.  Hidden layers: 3.5 instead of 4 slices.
     auto mma_tile_tail = [&](const Frag (&buf)[3], auto mt_, const Frag (&bf)[DT][3]) __attribute__((always_inline)) {
         constexpr int mt = decltype(mt_)::value;
-        constexpr int kA[6] = {0, 1, 2, 0, 1, 0}, kB[6] = {2, 1, 0, 1, 0, 0};
-        using i16x4 = __attribute__((ext_vector_type(4))) short;
-        using u32x2_ = __attribute__((ext_vector_type(2))) uint32_t;
 #pragma unroll
         for (int q = 0; q < 6; ++q)
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt)
-                acc[mt][dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(i16x4, u32x2_{buf[kA[q]].u[0], buf[kA[q]].u[1]}),
-                                                                         __builtin_bit_cast(i16x4, u32x2_{bf[dt][kB[q]].u[0], bf[dt][kB[q]].u[1]}), acc[mt][dt], 0, 0, 0);
+                acc[mt][dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(i16x4, u32x2{buf[kSixA[q]].u[0], buf[kSixA[q]].u[1]}),
+                                                                         __builtin_bit_cast(i16x4, u32x2{bf[dt][kSixB[q]].u[0], bf[dt][kSixB[q]].u[1]}), acc[mt][dt], 0, 0, 0);
     };
     // one slice step (see the schedule above).  In: af[AP] = tile 0 of this slice; out: af[AP ^ 1] = tile 0 of the next slice (its base
     // returned).  work(r): the VALU work beside the MFMAs of tile r; Ks: VALU instructions per MFMA of the interleave hint (0 = none)

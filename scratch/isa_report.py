@@ -4,9 +4,11 @@
                                                            v_mfma_f32_16x16x4_f32 issues after 40 cycles, an independent one after 32)
     python scratch/isa_report.py blocks file.hip KERNEL    per basic block with >= 20 MFMAs: MFMA / VALU / LDS / VMEM / SALU counts and the VALU mix
     python scratch/isa_report.py regs   [file.hip ...]     VGPRs, spills and scratch bytes per kernel
+    python scratch/isa_report.py digest [file.hip ...]     name, instruction count and a hash of the instruction lines per kernel (default: every .hip
+                                                           file): `diff` the output of two trees to show that a refactor left the device code alone
 
 What found the forward's dependent chains (r3: 352 -> 340 us) and the layer-wise dZ kernel's (147 of 196 MFMAs)."""
-import os, re, subprocess, sys, tempfile
+import glob, hashlib, os, re, subprocess, sys, tempfile
 from collections import Counter
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,6 +102,12 @@ def regs(files):
             print(f"{os.path.basename(f):16s} {demangle(n)[:90]:90s} VGPRs {v.get('VGPRs'):>4s} spill {v.get('VGPRs Spill'):>4s} scratch {v.get('ScratchSize [bytes/lane]'):>4s}")
 
 
+def digest(files):
+    for f in files:
+        for name, k in sorted(kernels(asm(f)).items()):
+            print(f"{os.path.basename(f):20s} {demangle(name)[:100]:100s} instr {len(k):6d}  {hashlib.sha256(chr(10).join(k).encode()).hexdigest()[:16]}")
+
+
 if __name__ == "__main__":
     cmd = sys.argv[1] if len(sys.argv) > 1 else "deps"
     files = [a if os.path.exists(a) else os.path.join(CSRC, a) for a in sys.argv[2:] if a.endswith(".hip")]
@@ -108,6 +116,8 @@ if __name__ == "__main__":
         deps(files or allf)
     elif cmd == "regs":
         regs(files or allf)
+    elif cmd == "digest":
+        digest(files or sorted(glob.glob(os.path.join(CSRC, "*.hip"))))
     elif cmd == "blocks":
         blocks(files[0], sys.argv[3])
     else:

@@ -197,6 +197,29 @@ def test_runtime_switches_are_read_in_one_place_and_documented():
     assert read == _documented_switches(), (sorted(read - _documented_switches()), sorted(_documented_switches() - read))
 
 
+def test_bf16x6_split_and_wave_primitives_have_one_home():
+    """The bf16x6 numeric contract is written once: the packed fp32 -> bf16 conversion under the three-plane split and the transpose-read
+    that feeds the six products live in ptr_x6.h, the global -> LDS DMA in ptr_device.h, and no other file of csrc/ spells them out again
+    (comments stripped: several file headers name the instructions in prose).  A private copy compiles, passes its own kernel's tolerance
+    gate and breaks the bit-identity between kernels only in combination."""
+    csrc = os.path.join(ROOT, "ptranking_amd", "csrc")
+    owners = {r"__builtin_convertvector\s*\([^;]*bf\w*\s*\)": "ptr_x6.h",
+              r"__builtin_amdgcn_ds_read_tr16_b64": "ptr_x6.h",
+              r"global_load_lds_dwordx4": "ptr_device.h"}
+    found = {pat: set() for pat in owners}
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h", ".cpp")):
+            continue
+        code = open(os.path.join(csrc, f)).read()
+        code = re.sub(r"/\*.*?\*/", "", code, flags=re.S)
+        code = re.sub(r"//[^\n]*", "", code)
+        for pat in owners:
+            if re.search(pat, code):
+                found[pat].add(f)
+    for pat, owner in owners.items():
+        assert found[pat] == {owner}, f"{pat} belongs in csrc/{owner} alone, found in {sorted(found[pat])}"
+
+
 def _listsf_dispatch():
     """The dispatch rules of csrc/listsf.hip, restated: attention D = ceil(dh / 16) (dispatch_dt), two row tiles per forward wave iff
     D <= 5 and L > 64, the 8-wave dK / dV kernel iff D >= 7 and L > 64, STORE_DS iff a dS scratch is passed, vector loads iff dh and the
