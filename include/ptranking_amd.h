@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PTR_ABI_VERSION 6
+#define PTR_ABI_VERSION 7
 #define PTR_MAX_LIST_LEN 4096
 #define PTR_MAX_CUTOFFS 32
 #define PTR_MLP_ACT_LD 112
@@ -345,6 +345,42 @@ int ptr_bnact_forward(const float *z, int ld, int R, int N, int group_rows, cons
 int ptr_bnact_backward(const float *z, const float *da, int ld, int R, int N, int group_rows, const int32_t *lens, int rows_per_query,
                        const float *mean, const float *rstd, const float *gamma, const float *beta, int af, float p_drop, uint64_t seed,
                        int site, float *ws, float *dz, float *dgamma, float *dbeta, void *stream);
+
+/* ---- synchronised 'BN' statistics across data-parallel ranks (ABI v7) ---------------------------------------------------------------
+ * The whole-batch statistics of ptr_bn_stats and the backward of ptr_bnact_backward, cut where the ranks must talk.  W ranks hold R_w
+ * rows each; between the calls the host gathers one fixed-size record per rank (dp.gather_slots), so every rank runs the second half
+ * on identical bytes and gets identical statistics whatever the collective backend's reduction order.  group_rows must be 0 in all
+ * four (per-query 'BN2' statistics couple no ranks: PTR_ERR_INVALID_ARG); lens / rows_per_query as above; an empty shard (R == 0) is an
+ * error, a shard whose rows are all padding is not.
+ *   forward   ptr_bn_stats_partial -> gather slots -> ptr_bn_stats_combine -> ptr_bnact_forward(mean, rstd)
+ *   backward  ptr_bnact_backward_sums -> gather sums -> ptr_bnact_backward_apply
+ * slot  = ptr_bn_slot_floats(N) = 2 N + 4 floats: [ mean[N] | M2[N] | count | 3 unused ] — the mean and the sum of squared deviations
+ *         from it of this rank's real rows, and how many they are (0: mean and M2 are 0).  Counts travel as floats: exact while the
+ *         ranks hold fewer than 2^24 = 16 777 216 real rows IN TOTAL.
+ * combine: mean = sum n_w mean_w / n, var = sum (M2_w + n_w (mean_w - mean)^2) / n (biased), rstd = 1 / sqrt(var + eps), n = sum n_w;
+ *         slots taken in rank order 0 .. W-1 (up to 32 ranks: one addition per rank in that order; beyond, ranks w, w + 32, ... are
+ *         pre-added — a fixed order either way, no atomics); a slot with count 0 has weight 0 and contributes exactly nothing.
+ *         total_count[0] = max(n, 1) stays on the device for ptr_bnact_backward_apply.
+ * sums  = 2 N floats: [ sum dy [N] | sum dy xhat [N] ] over this rank's real rows, xhat from the GLOBAL mean / rstd — these are this
+ *         rank's dbeta | dgamma (the gradient all-reduce adds them across ranks like every other parameter gradient).
+ * apply:  sums[W][2 N] (the gathered records) are added in the same fixed rank order into ws[2 N], then
+ *         dz = gamma rstd (dy - sum_dy / n - xhat sum_dyx / n) with n read from total_count; a padded row's dz is 0. */
+size_t ptr_bn_slot_floats(int N);
+/* ws: ptr_bn_ws_floats(R, N, 0) floats */
+int ptr_bn_stats_partial(const float *z, int ld, int R, int N, int group_rows, const int32_t *lens, int rows_per_query, float *ws,
+                         float *slot, void *stream);
+/* slots: W records, slot_stride (>= 2 N + 1) floats apart */
+int ptr_bn_stats_combine(const float *slots, int W, int slot_stride, int N, float eps, float *mean, float *rstd, float *total_count,
+                         void *stream);
+/* ws: ptr_bn_ws_floats(R, N, 0) floats */
+int ptr_bnact_backward_sums(const float *z, const float *da, int ld, int R, int N, int group_rows, const int32_t *lens, int rows_per_query,
+                            const float *mean, const float *rstd, const float *gamma, const float *beta, int af, float p_drop,
+                            uint64_t seed, int site, float *ws, float *sums, void *stream);
+/* ws: 2 N floats (the global sums) */
+int ptr_bnact_backward_apply(const float *z, const float *da, int ld, int R, int N, int group_rows, const int32_t *lens, int rows_per_query,
+                             const float *mean, const float *rstd, const float *gamma, const float *beta, int af, float p_drop,
+                             uint64_t seed, int site, const float *sums, int W, const float *total_count, float *ws, float *dz,
+                             void *stream);
 
 /* ---- listsf: the permutation-equivariant scorer's fused pieces (fp32 MFMA attention core, the reference's LayerNorm) ----
  * ptr_mhsa_forward replaces ptranking/base/list_ranker.py:216-240 (Q K^T / sqrt(d_h) -> softmax -> Dropout -> . V, heads = column

@@ -11,7 +11,7 @@ import torch  # noqa: F401  — must be imported first so that OUR .so binds to 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PTR_LIB") or os.path.join(_PKG, "libptranking_amd.so")   # PTR_LIB: an experiment build (build.py --variant)
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 MAX_LIST_LEN = 4096
 MAX_CUTOFFS = 32
 
@@ -60,6 +60,11 @@ SIGNATURES = {
     "ptr_bn_stats": [_vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp],
     "ptr_bnact_forward": [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _u64, _i, _vp, _vp],
     "ptr_bnact_backward": [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _u64, _i, _vp, _vp, _vp, _vp, _vp],
+    "ptr_bn_slot_floats": [_i],
+    "ptr_bn_stats_partial": [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp],
+    "ptr_bn_stats_combine": [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "ptr_bnact_backward_sums": [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _u64, _i, _vp, _vp, _vp],
+    "ptr_bnact_backward_apply": [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _u64, _i, _vp, _i, _vp, _vp, _vp, _vp],
     "ptr_dropout_apply": [_vp, _i, _i, _i, _f, _u64, _i, _vp, _i, _vp],
     "ptr_relu_gate": [_vp, _vp, C.c_int64, _vp, _vp],
     "ptr_mhsa_forward": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _u64, _i, _vp, _vp, _vp],
@@ -73,6 +78,7 @@ SIGNATURES = {
 }
 _RESTYPES = {"ptr_last_error": C.c_char_p, "ptr_mlp_num_params": C.c_size_t, "ptr_mlp_backward_ws_floats": C.c_size_t,
              "ptr_mlp_backward_dz_floats": C.c_size_t, "ptr_mlp_acts_floats": C.c_size_t, "ptr_mlp_x6_ws_bytes": C.c_size_t, "ptr_linear_backward_weight_ws_floats": C.c_size_t, "ptr_bn_ws_floats": C.c_size_t,
+             "ptr_bn_slot_floats": C.c_size_t,
              "ptr_layernorm_backward_ws_floats": C.c_size_t}
 OPTIONAL = set()
 

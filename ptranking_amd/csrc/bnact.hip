@@ -225,11 +225,15 @@ colsum2_kernel(const float *__restrict__ z, const float *__restrict__ da, const 
 //   FINISH 0: out1 = sum partial[.][0], out2 = sum partial[.][1]
 //   FINISH 1: partials are (chunk mean, chunk M2) over `chunk` rows each (the last one shorter): out1 = mean, out2 = 1 / sqrt(var + eps),
 //             var = (sum M2_b + n_b (mean_b - mean)^2) / R   (biased, as BatchNorm normalises)
-// counts != NULL (padded batches): chunk b holds counts[b] real rows; their total replaces R and is also written to total_out[0]
+//   FINISH 2: FINISH 1 stopped before the division: out1 = mean, out2 = M2 = sum M2_b + n_b (mean_b - mean)^2 of these rows, and
+//             total_out[0] = their real-row count UNCLAMPED (0 for rows that are all padding: mean 0, M2 0) — one rank's slot of the
+//             synchronised statistics, which FINISH 1 then combines across ranks with the same formula
+// counts != NULL (padded batches): chunk b holds counts[b * cstride] real rows; their total replaces R and is also written to total_out[0]
+// partial b starts at partial + b * pstride: [N] first | [N] second values (2 * N for the chunk partials, the slot length for rank slots)
 template <int FINISH>
 __global__ void __launch_bounds__(256)
 colsum2_reduce_kernel(const float *__restrict__ partial, int nblk, int N, int R, int chunk, float eps, float *__restrict__ out1,
-                      float *__restrict__ out2, const float *__restrict__ counts, float *__restrict__ total_out) {
+                      float *__restrict__ out2, const float *__restrict__ counts, float *__restrict__ total_out, size_t pstride, size_t cstride) {
     constexpr int CL = 8, BL = 32;
     __shared__ float red[2][BL][CL + 1];
     __shared__ float cnt_red[256];
@@ -239,7 +243,7 @@ colsum2_reduce_kernel(const float *__restrict__ partial, int nblk, int N, int R,
     float Rf = (float)R;
     if (counts) {                                            // fixed-order total of the chunk counts (integers: exact in fp32 up to 2^24)
         float t = 0.0f;
-        for (int b = threadIdx.x; b < nblk; b += 256) t += counts[b];
+        for (int b = threadIdx.x; b < nblk; b += 256) t += counts[b * cstride];
         cnt_red[threadIdx.x] = t;
         __syncthreads();
         for (int s_ = 128; s_ > 0; s_ >>= 1) {
@@ -247,12 +251,12 @@ colsum2_reduce_kernel(const float *__restrict__ partial, int nblk, int N, int R,
             __syncthreads();
         }
         Rf = fmaxf(cnt_red[0], 1.0f);
-        if (total_out && blockIdx.x == 0 && threadIdx.x == 0) total_out[0] = Rf;
+        if (total_out && blockIdx.x == 0 && threadIdx.x == 0) total_out[0] = FINISH == 2 ? cnt_red[0] : Rf;
     }
     // chunk b's rows: 0 for the chunks past R (above 131 072 rows the 512 chunks of ceil(R / 512) rows can end before the grid does)
-    auto rows_of = [&](int b) { return counts ? counts[b] : (float)max(0, min(R, (b + 1) * chunk) - b * chunk); };
-    auto p0 = [&](int b) { return b < nblk ? partial[((size_t)b * 2 + 0) * N + c] : 0.0f; };
-    auto p1 = [&](int b) { return b < nblk ? partial[((size_t)b * 2 + 1) * N + c] : 0.0f; };
+    auto rows_of = [&](int b) { return counts ? counts[b * cstride] : (float)max(0, min(R, (b + 1) * chunk) - b * chunk); };
+    auto p0 = [&](int b) { return b < nblk ? partial[(size_t)b * pstride + c] : 0.0f; };
+    auto p1 = [&](int b) { return b < nblk ? partial[(size_t)b * pstride + N + c] : 0.0f; };
     float s1 = 0.0f, s2 = 0.0f;
     if (on)
         for (int b = bl; b < nblk; b += 4 * BL) {
@@ -295,7 +299,7 @@ colsum2_reduce_kernel(const float *__restrict__ partial, int nblk, int N, int R,
         float v = 0.0f;
         for (int k = 0; k < BL; ++k) v += red[0][k][cl];
         out1[c] = mean_tot;
-        out2[c] = 1.0f / sqrtf(v / Rf + eps);
+        out2[c] = FINISH == 2 ? v : 1.0f / sqrtf(v / Rf + eps);
     }
 }
 
@@ -378,7 +382,10 @@ bnact_bwd_kernel(const float *__restrict__ z, const float *__restrict__ da, cons
         if (gamma) ga = ldv(gamma + c);
         if (beta) be = ldv(beta + c);
         float cnt = (float)(a.group > 0 ? a.group : a.R);
-        if (a.lens) cnt = a.group > 0 ? (float)max(min(max(a.lens[r / a.group], 0), a.L), 1) : total_real[0];
+        // whole-batch statistics take their row count from device memory when one is given: the real rows of a padded batch, or the
+        // documents of ALL ranks under synchronised statistics (ptr_bnact_backward_apply) — no host synchronisation either way
+        if (a.group == 0 && total_real) cnt = total_real[0];
+        else if (a.lens && a.group > 0) cnt = (float)max(min(max(a.lens[r / a.group], 0), a.L), 1);
         const float invR = 1.0f / cnt;
         const float real = row_is_real(a, r) ? 1.0f : 0.0f;      // a padded row takes no part in the statistics: its dz is 0
         for (int e = 0; e < W; ++e) {
@@ -462,7 +469,7 @@ extern "C" int ptr_bn_stats(const float *z, int ld, int R, int N, int group_rows
         hipLaunchKernelGGL(group_finish_kernel, dim3(fin), dim3(256), 0, st, ws, (size_t)nb, N, group_rows, eps, mean, rstd, lens);
     } else {
         hipLaunchKernelGGL(colsum2_reduce_kernel<1>, dim3((N + 7) / 8), dim3(256), 0, st, ws, nb, N, R, (R + nb - 1) / nb, eps, mean, rstd, counts,
-                           (float *)nullptr);
+                           (float *)nullptr, (size_t)2 * N, (size_t)1);
     }
     return check_hip(hipGetLastError(), who);
 }
@@ -516,7 +523,8 @@ extern "C" int ptr_bnact_backward(const float *z, const float *da, int ld, int R
         if (v4) hipLaunchKernelGGL((colsum2_kernel<1, 4>), dim3(nb), dim3(256), 0, st, z, da, mean, rstd, gamma, beta, a, ws, counts);
         else hipLaunchKernelGGL((colsum2_kernel<1, 1>), dim3(nb), dim3(256), 0, st, z, da, mean, rstd, gamma, beta, a, ws, counts);
         if (a.group == 0 || dbeta || dgamma)
-            hipLaunchKernelGGL(colsum2_reduce_kernel<0>, dim3((N + 7) / 8), dim3(256), 0, st, ws, nb, N, R, 0, 0.0f, tot_dy, tot_dyx, counts, total_real);
+            hipLaunchKernelGGL(colsum2_reduce_kernel<0>, dim3((N + 7) / 8), dim3(256), 0, st, ws, nb, N, R, 0, 0.0f, tot_dy, tot_dyx, counts, total_real,
+                               (size_t)2 * N, (size_t)1);
         sum_dy = a.group > 0 ? ws : tot_dy;                 // grouped: the per-group partials themselves
         sum_dyx = a.group > 0 ? ws + N : tot_dyx;
     }
@@ -528,6 +536,98 @@ extern "C" int ptr_bnact_backward(const float *z, const float *da, int ld, int R
         const size_t n = (size_t)R * N;
         hipLaunchKernelGGL(bnact_bwd_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, z, da, mean, rstd, gamma, beta, sum_dy, sum_dyx, a, dz,
                            total_real);
+    }
+    return check_hip(hipGetLastError(), who);
+}
+
+// ---- synchronised statistics: the 'BN' layers of a data-parallel replica normalise over the documents of ALL ranks ------------------
+// The host exchanges one slot per rank between ptr_bn_stats_partial and ptr_bn_stats_combine, and one [2][N] pair of column sums per
+// rank between ptr_bnact_backward_sums and ptr_bnact_backward_apply (dp.gather_slots: a bit-exact gather).  The kernels are the ones
+// above — colsum2_kernel, colsum2_reduce_kernel, bnact_bwd_kernel — launched in other combinations; whole-batch statistics only.
+extern "C" size_t ptr_bn_slot_floats(int N) { return N > 0 ? 2 * (size_t)N + 4 : 0; }
+
+namespace ptr {
+static int check_sync(const char *who, int R, int group_rows) {
+    if (R == 0) { set_error("%s: empty batch", who); return PTR_ERR_INVALID_ARG; }
+    if (group_rows != 0) { set_error("%s: per-query statistics (group_rows=%d) couple no ranks: nothing to synchronise", who, group_rows); return PTR_ERR_INVALID_ARG; }
+    return 0;
+}
+}  // namespace ptr
+
+// slot = [mean[N] | M2[N] | count | 3 unused] of this rank's real rows (count 0: mean 0, M2 0).  ws: ptr_bn_ws_floats(R, N, 0) floats.
+extern "C" int ptr_bn_stats_partial(const float *z, int ld, int R, int N, int group_rows, const int32_t *lens, int rows_per_query, float *ws,
+                                    float *slot, void *stream) {
+    using namespace ptr;
+    const char *who = "ptr_bn_stats_partial";
+    if (int rc = check_bnact(who, R, N, ld, 0, 0.0f)) return rc;
+    if (int rc = check_sync(who, R, group_rows)) return rc;
+    if (!z || !ws || !slot) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_lens(who, lens, rows_per_query, R, 0)) return rc;
+    hipStream_t st = as_stream(stream);
+    BnActArgs a{0, R, N, ld, 0, 0, 0.0f, 0, 0, 0, lens, lens ? rows_per_query : 0};
+    const int nb = bn_blocks(R);
+    float *counts = ws + (size_t)nb * 2 * N + 2 * (size_t)N;      // always counted here: the slot carries this rank's real rows
+    if (vec4_ok(N, ld, z, ws)) hipLaunchKernelGGL((colsum2_kernel<0, 4>), dim3(nb), dim3(256), 0, st, z, nullptr, nullptr, nullptr, nullptr, nullptr, a, ws, counts);
+    else hipLaunchKernelGGL((colsum2_kernel<0, 1>), dim3(nb), dim3(256), 0, st, z, nullptr, nullptr, nullptr, nullptr, nullptr, a, ws, counts);
+    hipLaunchKernelGGL(colsum2_reduce_kernel<2>, dim3((N + 7) / 8), dim3(256), 0, st, ws, nb, N, R, (R + nb - 1) / nb, 0.0f, slot, slot + N, counts,
+                       slot + 2 * (size_t)N, (size_t)2 * N, (size_t)1);
+    return check_hip(hipGetLastError(), who);
+}
+
+// slots[W][slot_stride] -> mean[N], rstd[N], total_count[0] = max(documents of all ranks, 1)
+extern "C" int ptr_bn_stats_combine(const float *slots, int W, int slot_stride, int N, float eps, float *mean, float *rstd, float *total_count,
+                                    void *stream) {
+    using namespace ptr;
+    const char *who = "ptr_bn_stats_combine";
+    if (W <= 0 || N <= 0 || slot_stride < 2 * (long long)N + 1) { set_error("%s: bad shape W=%d N=%d slot_stride=%d", who, W, N, slot_stride); return PTR_ERR_INVALID_ARG; }
+    if (!slots || !mean || !rstd || !total_count) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(colsum2_reduce_kernel<1>, dim3((N + 7) / 8), dim3(256), 0, as_stream(stream), slots, W, N, 0, 0, eps, mean, rstd,
+                       slots + 2 * (size_t)N, total_count, (size_t)slot_stride, (size_t)slot_stride);
+    return check_hip(hipGetLastError(), who);
+}
+
+// sums = [sum dy [N] | sum dy * xhat [N]] over this rank's real rows, xhat from the GLOBAL mean / rstd: this rank's dbeta | dgamma
+extern "C" int ptr_bnact_backward_sums(const float *z, const float *da, int ld, int R, int N, int group_rows, const int32_t *lens, int rows_per_query,
+                                       const float *mean, const float *rstd, const float *gamma, const float *beta, int af, float p_drop,
+                                       uint64_t seed, int site, float *ws, float *sums, void *stream) {
+    using namespace ptr;
+    const char *who = "ptr_bnact_backward_sums";
+    if (int rc = check_bnact(who, R, N, ld, af, p_drop)) return rc;
+    if (int rc = check_sync(who, R, group_rows)) return rc;
+    if (!z || !da || !mean || !rstd || !ws || !sums) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_lens(who, lens, rows_per_query, R, 0)) return rc;
+    hipStream_t st = as_stream(stream);
+    BnActArgs a{0, R, N, ld, af, 1, p_drop, (uint32_t)seed, (uint32_t)(seed >> 32), site, lens, lens ? rows_per_query : 0};
+    const int nb = bn_blocks_bwd(R);
+    if (vec4_ok(N, ld, z, da, ws, mean, rstd, gamma, beta)) hipLaunchKernelGGL((colsum2_kernel<1, 4>), dim3(nb), dim3(256), 0, st, z, da, mean, rstd, gamma, beta, a, ws, (float *)nullptr);
+    else hipLaunchKernelGGL((colsum2_kernel<1, 1>), dim3(nb), dim3(256), 0, st, z, da, mean, rstd, gamma, beta, a, ws, (float *)nullptr);
+    hipLaunchKernelGGL(colsum2_reduce_kernel<0>, dim3((N + 7) / 8), dim3(256), 0, st, ws, nb, N, R, 0, 0.0f, sums, sums + N, (const float *)nullptr,
+                       (float *)nullptr, (size_t)2 * N, (size_t)1);
+    return check_hip(hipGetLastError(), who);
+}
+
+// dz of this rank's rows from every rank's sums[W][2 * N] (added in rank order into ws[2 * N]) and the global count on the device
+extern "C" int ptr_bnact_backward_apply(const float *z, const float *da, int ld, int R, int N, int group_rows, const int32_t *lens, int rows_per_query,
+                                        const float *mean, const float *rstd, const float *gamma, const float *beta, int af, float p_drop,
+                                        uint64_t seed, int site, const float *sums, int W, const float *total_count, float *ws, float *dz,
+                                        void *stream) {
+    using namespace ptr;
+    const char *who = "ptr_bnact_backward_apply";
+    if (int rc = check_bnact(who, R, N, ld, af, p_drop)) return rc;
+    if (int rc = check_sync(who, R, group_rows)) return rc;
+    if (W <= 0) { set_error("%s: W=%d ranks", who, W); return PTR_ERR_INVALID_ARG; }
+    if (!z || !da || !mean || !rstd || !sums || !total_count || !ws || !dz) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_lens(who, lens, rows_per_query, R, 0)) return rc;
+    hipStream_t st = as_stream(stream);
+    BnActArgs a{0, R, N, ld, af, 1, p_drop, (uint32_t)seed, (uint32_t)(seed >> 32), site, lens, lens ? rows_per_query : 0};
+    hipLaunchKernelGGL(colsum2_reduce_kernel<0>, dim3((N + 7) / 8), dim3(256), 0, st, sums, W, N, R, 0, 0.0f, ws, ws + N, (const float *)nullptr,
+                       (float *)nullptr, (size_t)2 * N, (size_t)1);
+    if (vec4_ok(N, ld, z, da, dz, ws, mean, rstd, gamma, beta)) {
+        const size_t n = (size_t)R * (N / 4);
+        hipLaunchKernelGGL(bnact_bwd_kernel<4>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, z, da, mean, rstd, gamma, beta, ws, ws + N, a, dz, total_count);
+    } else {
+        const size_t n = (size_t)R * N;
+        hipLaunchKernelGGL(bnact_bwd_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, z, da, mean, rstd, gamma, beta, ws, ws + N, a, dz, total_count);
     }
     return check_hip(hipGetLastError(), who);
 }

@@ -73,6 +73,54 @@ def init_from_env(backend=None):
     return rk, ws, local
 
 
+# ---- synchronised batch-norm statistics ('BN' scorers: statistics over all documents of the batch) --------------------------------
+# Off (the default): every rank normalises with the statistics of its own shard, as torch DDP does without SyncBatchNorm — N ranks x B/N
+# queries then do NOT reproduce one rank x B, and the trained model depends on how many GPUs took part.  On (`sync_batch_norm(ranker)`):
+# the 'BN' layers of every linear.FusedStack of the ranker take mean / variance over the documents of ALL ranks in training mode and run
+# the matching backward, at the price of one small collective per 'BN' layer in the forward and one in the backward (12 per step for the
+# default pointsf).  They are counted here, apart from TIMING: the step still has ONE gradient all-reduce.
+# Every rank must make the same sequence of scorer calls per step (a rank whose shard is all padding joins with count 0).  Evaluation
+# (eval_mode, torch.no_grad() scoring) keeps rank-local statistics whatever the switch says: a distributed evaluation does not
+# guarantee the same number of forward calls on every rank, and a collective there could deadlock.
+BN_COLLECTIVES = 0
+
+
+def new_slots(floats, device):
+    """A zero-filled [world size][floats] fp32 buffer for gather_slots and the row this rank writes."""
+    buf = torch.zeros((world_size(), floats), device=device, dtype=torch.float32)
+    return buf, buf[rank()]
+
+
+def gather_slots(buf):
+    """All-gather of one fixed-size record per rank as ONE in-place all_reduce(SUM): `buf` is [world size][floats], zero everywhere but
+    in this rank's own row (new_slots).  Adding zeros is exact, so every rank ends with every rank's record bit for bit (up to the sign
+    of a zero) under ANY reduction order of RCCL or gloo — and gloo has no all_gather for GPU tensors, which the
+    two-ranks-on-one-GPU tests would need.  What is summed ACROSS records afterwards is summed by our own fixed-order kernels, not by
+    the backend, so replicas stay bit-identical."""
+    global BN_COLLECTIVES
+    if buf.dim() != 2 or buf.shape[0] != world_size() or not buf.is_contiguous():
+        raise ValueError(f"gather_slots: expected a contiguous [{world_size()}][floats] buffer, got {tuple(buf.shape)}")
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+        BN_COLLECTIVES += 1
+    return buf
+
+
+def sync_batch_norm(ranker, on=True):
+    """Switch the synchronised 'BN' statistics of every fused stack of `ranker` (point_sf, or the listsf head / tail stacks) on or off.
+    Returns the number of stacks switched.  It takes effect under data parallelism in training mode only (see above); a stack that
+    cannot honour it there (module-by-module route) raises NotImplementedError instead of normalising with local statistics."""
+    from .host import _scorer_modules
+    from .linear import FusedStack
+    n = 0
+    for top in _scorer_modules(ranker):
+        for m in top.modules():
+            if isinstance(m, FusedStack):
+                m.sync_batch_norm = bool(on)
+                n += 1
+    return n
+
+
 ROW_KEY = 0x9E3779B1        # the per-row multiplier of the counter-based dropout generator (csrc/ptr_dropout.h drop_bits)
 ROW_OFFSET = None           # explicit global index of this rank's first row; None: derived from QUERY_SHARD, else rank * local rows
 QUERY_SHARD = None          # (first global query, number of local queries) of this rank's slice, recorded by shard_queries()

@@ -227,10 +227,56 @@ def _bnact_bwd(z, da, group, mean, rstd, gamma, beta, af, p, seed, site, dg_out=
     return dz, dg, db
 
 
-def _stack_forward(x, p, seed, spec, params, fixed_stats=None, sink=None, lens=None, L=0):
+def _bn_stats_sync(z, lens=None, L=0):
+    """Whole-batch statistics over the documents of ALL data-parallel ranks: this rank's (mean, M2, count) slot -> gathered slots of every
+    rank (one collective, dp.gather_slots) -> the rank-order combination, run by every rank on identical bytes.  Returns mean, rstd and the
+    global document count [1], which stays on the device for the backward."""
+    R, N = z.shape
+    dev = z.device
+    S = _lib.query("ptr_bn_slot_floats", N)
+    slots, own = dp.new_slots(S, dev)
+    ws = torch.empty(_lib.query("ptr_bn_ws_floats", R, N, 0), device=dev, dtype=torch.float32)
+    mean = torch.empty(N, device=dev, dtype=torch.float32)
+    rstd = torch.empty(N, device=dev, dtype=torch.float32)
+    cnt = torch.empty(1, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_bn_stats_partial", _lib.ptr(z), N, R, N, 0, _lib.ptr(lens), L, _lib.ptr(ws), _lib.ptr(own), _lib.current_stream(dev))
+        dp.gather_slots(slots)
+        _lib.call("ptr_bn_stats_combine", _lib.ptr(slots), slots.shape[0], S, N, C.c_float(BN_EPS), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(cnt),
+                  _lib.current_stream(dev))
+    return mean, rstd, cnt
+
+
+def _bnact_bwd_sync(z, da, mean, rstd, cnt, gamma, beta, af, p, seed, site, dg_out=None, db_out=None, lens=None, L=0):
+    """The backward of a layer normalised with synchronised statistics: local column sums (with the global mean / rstd) -> gathered sums
+    of every rank (one collective) -> their fixed-order total and dz.  dgamma / dbeta are the LOCAL sums: the gradient all-reduce adds
+    them across ranks like every other parameter gradient (the global sums would be counted once per rank)."""
+    R, N = z.shape
+    dev = z.device
+    sums, own = dp.new_slots(2 * N, dev)
+    ws = torch.empty(_lib.query("ptr_bn_ws_floats", R, N, 0), device=dev, dtype=torch.float32)
+    dz = torch.empty_like(z)
+    with torch.cuda.device(dev):
+        st = _lib.current_stream(dev)
+        _lib.call("ptr_bnact_backward_sums", _lib.ptr(z), _lib.ptr(da), N, R, N, 0, _lib.ptr(lens), L, _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gamma),
+                  _lib.ptr(beta), af, C.c_float(p), C.c_uint64(seed), site, _lib.ptr(ws), _lib.ptr(own), st)
+        db = dg = None
+        if beta is not None:
+            db = own[:N].clone() if db_out is None else db_out.copy_(own[:N].view_as(db_out))
+        if gamma is not None:
+            dg = own[N:].clone() if dg_out is None else dg_out.copy_(own[N:].view_as(dg_out))
+        dp.gather_slots(sums)
+        _lib.call("ptr_bnact_backward_apply", _lib.ptr(z), _lib.ptr(da), N, R, N, 0, _lib.ptr(lens), L, _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gamma),
+                  _lib.ptr(beta), af, C.c_float(p), C.c_uint64(seed), site, _lib.ptr(sums), sums.shape[0], _lib.ptr(cnt), _lib.ptr(ws), _lib.ptr(dz), st)
+    return dz, dg, db
+
+
+def _stack_forward(x, p, seed, spec, params, fixed_stats=None, sink=None, lens=None, L=0, sync=False):
     """Forward of the general stack.  spec = (n_linear, hidden af codes, tail af or 0, has_bn, group): group = 0 — statistics over the
     whole batch ('BN'), L — per query ('BN2').  fixed_stats: per-layer (mean, rstd) to use instead of the batch statistics (BN2 under
-    torch.no_grad(): its moving statistics).  sink: list receiving (layer, mean, rstd) of the statistics computed here."""
+    torch.no_grad(): its moving statistics).  sink: list receiving (layer, mean, rstd) of the statistics computed here.  sync ('BN' under data parallelism,
+    FusedStack.sync_batch_norm): the statistics of every layer are those of the documents of ALL ranks; the 6th result then holds each
+    layer's global document count (a device scalar the backward divides by), else None."""
     n, afs, tail_af, has_bn, group = spec
     per = 4 if has_bn else 2
     x2, ldx = _rows(x)
@@ -245,7 +291,7 @@ def _stack_forward(x, p, seed, spec, params, fixed_stats=None, sink=None, lens=N
         ins, lda = [a], K0
     else:
         ins, lda = [x2], ldx
-    zs, stats = [], []
+    zs, stats, cnts = [], [], []
     out = None
     for i in range(n):
         W, b = params[per * i], params[per * i + 1]
@@ -255,11 +301,14 @@ def _stack_forward(x, p, seed, spec, params, fixed_stats=None, sink=None, lens=N
         af = afs[i] if hidden else tail_af
         if not hidden and af == 0:
             out = z
-            zs.append(None); stats.append((None, None))
+            zs.append(None); stats.append((None, None)); cnts.append(None)
             break
         gi = group
+        cnt = None
         if not has_bn:
             mean, rstd = None, None
+        elif sync:
+            mean, rstd, cnt = _bn_stats_sync(z, lens, L)
         elif fixed_stats is not None:
             (mean, rstd), gi = fixed_stats[i], 0
         else:
@@ -268,12 +317,12 @@ def _stack_forward(x, p, seed, spec, params, fixed_stats=None, sink=None, lens=N
                 sink.append((i, mean, rstd))
         pd = p if (hidden and i < n - 2) else 0.0          # the dropout in front of the NEXT hidden Linear
         a = _bnact_fwd(z, gi, mean, rstd, gamma, beta, af, pd, seed, i + 1, lens, L)
-        zs.append(z); stats.append((mean, rstd))
+        zs.append(z); stats.append((mean, rstd)); cnts.append(cnt)
         if hidden:
             ins.append(a)
         else:
             out = a
-    return out, ins, zs, stats, lda
+    return out, ins, zs, stats, lda, (cnts if sync else None)
 
 
 class _StackFn(torch.autograd.Function):
@@ -282,9 +331,9 @@ class _StackFn(torch.autograd.Function):
     and the layer inputs are kept for backward."""
 
     @staticmethod
-    def forward(ctx, x, p, seed, spec, sink, gsinks, lens, *params):
+    def forward(ctx, x, p, seed, spec, sink, gsinks, lens, sync, *params):
         L = x.shape[-2] if (lens is not None and x.dim() == 3) else 0
-        out, ins, zs, stats, lda = _stack_forward(x, p, seed, spec, params, sink=sink, lens=lens, L=L)
+        out, ins, zs, stats, lda, ctx.sync_counts = _stack_forward(x, p, seed, spec, params, sink=sink, lens=lens, L=L, sync=sync)
         flat_stats = [t for ms in stats for t in ms]
         ctx.save_for_backward(*ins, *zs, *flat_stats, *params)
         ctx.meta = (spec[0], p, seed, spec, lda)
@@ -313,8 +362,12 @@ class _StackFn(torch.autograd.Function):
             af = afs[i] if hidden else tail_af
             if hidden or af != 0:
                 pd = p if (hidden and i < n - 2) else 0.0
-                d, dg, dbt = _bnact_bwd(zs[i], d, group, fs[2 * i], fs[2 * i + 1], gamma, beta, af, pd, seed, i + 1,
-                                        gs[per * i + 2] if has_bn else None, gs[per * i + 3] if has_bn else None, ctx.lens, ctx.L)
+                if ctx.sync_counts is not None:    # synchronised statistics: one collective per layer here too, on every rank alike
+                    d, dg, dbt = _bnact_bwd_sync(zs[i], d, fs[2 * i], fs[2 * i + 1], ctx.sync_counts[i], gamma, beta, af, pd, seed, i + 1,
+                                                 gs[per * i + 2], gs[per * i + 3], ctx.lens, ctx.L)
+                else:
+                    d, dg, dbt = _bnact_bwd(zs[i], d, group, fs[2 * i], fs[2 * i + 1], gamma, beta, af, pd, seed, i + 1,
+                                            gs[per * i + 2] if has_bn else None, gs[per * i + 3] if has_bn else None, ctx.lens, ctx.L)
                 if has_bn:
                     grads[per * i + 2], grads[per * i + 3] = ret(dg, per * i + 2), ret(dbt, per * i + 3)
             a_in = ins[i]
@@ -330,8 +383,8 @@ class _StackFn(torch.autograd.Function):
                         _lib.call("ptr_dropout_apply", _lib.ptr(dx), dx.shape[1], dx.shape[0], dx.shape[1], C.c_float(p), C.c_uint64(seed), 0,
                                   _lib.ptr(dxd), dx.shape[1], _lib.current_stream(dev))
                     dx = dxd
-                return (dx.view(*dout.shape[:-1], W.shape[1]), None, None, None, None, None, None, *grads)
-        return (None, None, None, None, None, None, None, *grads)
+                return (dx.view(*dout.shape[:-1], W.shape[1]), None, None, None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, None, None, *grads)
 
 
 class FusedStack(nn.Sequential):
@@ -348,6 +401,18 @@ class FusedStack(nn.Sequential):
     _flat = None             # (flat parameter buffer, flat gradient buffer) once flatten_parameters() has re-homed the parameters
     _grads_fresh = False     # set by the owning optimiser's zero_grad(): the next backward may WRITE the gradients (no accumulation)
     batch_lens = None        # padded query batch: int32 [B] real list lengths, set by the ranker around forward (host.scorer_lens)
+    sync_batch_norm = False  # 'BN' statistics over the documents of ALL data-parallel ranks in training (dp.sync_batch_norm switches it)
+
+    def _sync_wanted(self):
+        """Synchronised statistics apply: switched on, training mode with gradients (evaluation and torch.no_grad() scoring keep
+        rank-local statistics — ranks need not make the same number of forward calls there), under data parallelism."""
+        return self.sync_batch_norm and self.training and torch.is_grad_enabled() and dp.is_distributed()
+
+    def _refuse_unsynced(self, reason):
+        """The module-by-module route would normalise a 'BN' layer with this rank's own statistics: an error while the switch is on."""
+        if self._sync_wanted() and any(type(c).__name__ in ("_BatchNormOverDocs", "LTRBatchNorm") for c in self.children()):
+            raise NotImplementedError(f"sync_batch_norm is on under data parallelism, but this batch-norm stack runs module by module ({reason}): "
+                                      f"its 'BN' layers would use rank-local statistics")
 
     def handles_padding(self, x):
         """True when a padded batch (batch_lens) is scored exactly like the unpadded lists on this input: the fused GPU path masks the
@@ -472,11 +537,13 @@ class FusedStack(nn.Sequential):
 
     def forward(self, x):
         if not x.is_cuda:
+            self._refuse_unsynced(f"tensor on {x.device}")
             return super().forward(x)
         if self._plan is None:
             self._plan = self._make_plan() or False
         plan = self._plan
         if plan is False or (plan["kind"] == "bn2" and x.dim() != 3):
+            self._refuse_unsynced("a structure the fused stack does not recognise")
             return super().forward(x)
         lins = plan["lins"]
         p = plan["p"] if self.training else 0.0
@@ -486,6 +553,7 @@ class FusedStack(nn.Sequential):
             if getattr(self, "batch_lens", None) is not None and plan["kind"] is not None:
                 raise NotImplementedError("a padded batch (batch_lens) reached a batch-norm stack on its module-by-module path: the padded "
                                           "rows would enter the BN statistics (host.scorer_lens should have refused this configuration)")
+            self._refuse_unsynced(f"input width {x.shape[-1]} is not a multiple of 4 and the stack has dropout")
             return super().forward(x)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0.0 else 0      # CPU generator: no device sync
         if p > 0.0:
@@ -533,7 +601,8 @@ class FusedStack(nn.Sequential):
         lens = self.batch_lens if (has_bn and x.dim() == 3) else None       # padded batch: real rows only in the statistics
         if lens is not None and not (lens.is_cuda and lens.dtype == torch.int32 and lens.is_contiguous() and lens.shape == (x.shape[0],)):
             raise ValueError("batch_lens must be a contiguous CUDA int32 tensor [B]")
-        out = _StackFn.apply(x, float(p), seed, spec, sink, self._claim_sinks(params), lens, *params)
+        sync = kind == "bn" and self._sync_wanted()
+        out = _StackFn.apply(x, float(p), seed, spec, sink, self._claim_sinks(params), lens, sync, *params)
         if sink:                                   # moving statistics, averaged over the queries of the batch (utils.py:242-245)
             with torch.no_grad():
                 for i, mean, rstd in sink:
