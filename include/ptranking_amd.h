@@ -29,9 +29,10 @@
 extern "C" {
 #endif
 
-#define PTR_ABI_VERSION 7
+#define PTR_ABI_VERSION 8
 #define PTR_MAX_LIST_LEN 4096
 #define PTR_MAX_CUTOFFS 32
+#define PTR_MAX_SUBTOPICS 32
 #define PTR_MLP_ACT_LD 112
 
 #define PTR_ERR_INVALID_ARG 1001   /* NULL pointer, negative size, bad enum value               */
@@ -139,6 +140,38 @@ int ptr_mdprank_fwd_bwd(const float *preds, const float *labels, const int64_t *
 int ptr_wassrank_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, int cost_type,
                          float gain_base, float non_rele_gap, float var_penalty, float lam, int sh_itr,
                          int scale_by_max_label, float *loss_out, float *loss_q, float *grad, void *stream);
+
+/* ---- search-result diversification (ABI v8, csrc/diversity.hip): the reference's ltr_diversification frame -------------------------------
+ * Data model: preds [B,L]; rele [B,T,L] = per query the reference's q_doc_rele_mat (subtopic-by-document relevance, document axis
+ * contiguous, values >= 0, graded values allowed); lens int32[B] (nullable: L) real documents, ntopics int32[B] (nullable: T) real
+ * subtopics per query.  Padded documents and padded subtopics are never read, contribute nothing, get gradient 0 and count in no
+ * denominator.  The reference runs ONE query per call (ptranking/base/ranker.py:636-669); a batch here is B independent reference calls.
+ *
+ * ptr_alphadcg_fwd_bwd — DALETOR's loss, replaces ptranking/ltr_diversification/score_and_sort/daletor.py:9-38 (get_approx_ranks,
+ * alphaDCG_as_a_loss; Robust_Sigmoid ptranking/base/utils.py:57-95) and its autograd backward in one launch; nothing of size L x L or
+ * T x L x L is written.  Per query:  ind[i][j] = rs(rt (s_j - s_i)), pi[i] = 0.5 + sum_j ind[i][j], cover[t][i] = sum_j ind[i][j] R[t][j]
+ * - R[t][i] / 2, loss_q = - sum over the kept (t, i) of R[t][i] (1 - alpha)^cover[t][i] / log2(1 + pi[i]).
+ *   top_k <= 0: every term is kept (top_k=None).  top_k_axis = PTR_ADCG_TOPK_SUBTOPICS reproduces the reference, whose `[0:top_k]` slices the
+ *   SUBTOPIC rows (daletor.py:30-35: the sum over dim=1 runs over documents first): kept <=> t < top_k.  PTR_ADCG_TOPK_DOCUMENTS is the
+ *   alpha-DCG@k its docstring describes: kept <=> i < top_k, documents in the given (presorted ideal) order.
+ *   loss_q [B], grad [B,L], loss_out [1] = sum of loss_q (nullable).  rt > 0 and 0 < alpha < 1, else PTR_ERR_INVALID_ARG;
+ *   PTR_ERR_UNSUPPORTED for L > PTR_MAX_LIST_LEN, T > PTR_MAX_SUBTOPICS, or a query tile beyond the LDS of a compute unit:
+ *   8 * round_up(L, 4) * (1 + Tp) + 16 bytes <= 160 KiB, Tp = T rounded up to 4, 8, 16 or 32 (T <= 4: L <= 4092; T <= 8: L <= 2272;
+ *   T <= 16: L <= 1204; T <= 32: L <= 620). */
+#define PTR_ADCG_TOPK_SUBTOPICS 0
+#define PTR_ADCG_TOPK_DOCUMENTS 1
+int ptr_alphadcg_fwd_bwd(const float *preds, const float *rele, const int32_t *lens, const int32_t *ntopics, int B, int T, int L, float rt,
+                         float alpha, int top_k, int top_k_axis, float *loss_out, float *loss_q, float *grad, void *stream);
+/* ptr_div_metrics_at_ks — alpha-nDCG@ks, ERR-IA@ks, nERR-IA@ks: replaces the Evaluator prologue of ptranking/base/ranker.py:269-475 (predict
+ * -> .cpu() -> torch.sort -> gather) and ptranking/metric/srd/diversity_metric.py:43-82, :189-245, :265-291.  The scores are ranked like
+ * ptr_sort_desc (value descending, original index ascending); the ideal ranking is the INPUT order (ranker.py:296, "under the assumption of
+ * presort").  ks: HOST int32[nk]; outputs [B,nk], each nullable; a cut-off k > lens[q] yields 0 (the reference's padding); an ideal value
+ * <= 0 yields 0; ERR-IA divides by ntopics[q] (empty subtopics count); max_label (2^max_label normalises the satisfaction
+ * probability) must be >= 0 when err_ia or nerr_ia is requested.  valid [B] (nullable) = 0 for a query whose relevance sums to less than 1
+ * — the evaluator skips it (ranker.py:282, :319) — else 1; the metric rows of such a query are 0. */
+int ptr_div_metrics_at_ks(const float *preds, const float *rele, const int32_t *lens, const int32_t *ntopics, int B, int T, int L,
+                          const int32_t *ks, int nk, float alpha, float max_label, float *andcg, float *err_ia, float *nerr_ia,
+                          int32_t *valid, void *stream);
 
 /* Device tie-shuffled label-descending order (the role of arg_shuffle_ties, sampling_utils.py:13-28) from a
  * counter-based RNG: same distribution, NOT the torch.randperm stream (not parity-checked, statistically tested). */

@@ -11,9 +11,10 @@ import torch  # noqa: F401  — must be imported first so that OUR .so binds to 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PTR_LIB") or os.path.join(_PKG, "libptranking_amd.so")   # PTR_LIB: an experiment build (build.py --variant)
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 MAX_LIST_LEN = 4096
 MAX_CUTOFFS = 32
+MAX_SUBTOPICS = 32
 
 _vp, _i, _f, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_uint64
 
@@ -33,6 +34,8 @@ SIGNATURES = {
     "ptr_rankmse_fwd_bwd": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
     "ptr_rankcosine_fwd_bwd": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
     "ptr_wassrank_fwd_bwd": [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp],
+    "ptr_alphadcg_fwd_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp],
+    "ptr_div_metrics_at_ks": [_vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(C.c_int32), _i, _f, _f, _vp, _vp, _vp, _vp, _vp],
     "ptr_shuffle_ties_order": [_vp, _vp, _i, _i, _u64, _vp, _vp],
     "ptr_sort_desc": [_vp, _vp, _i, _i, _vp, _vp, _vp],
     "ptr_metrics_at_ks": [_vp, _vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -15,25 +15,14 @@
 //   Outputs per query: DCG_b, 1/IDCG_b and the gradient for scale 1 (or already times 1/IDCG_b when un-coupled).
 // Kernel 2 (one workgroup): S = sum 1/IDCG, loss, scale.   Kernel 3: grad *= S (coupled mode only).
 #include "ptr_device.h"
+#include "ptr_rsig.h"
 
 namespace ptr {
 
 // LDS per group (floats): S_id[Lp] | Y_id[Lp] | acc[NW][Lp] | red[4]
 __host__ __device__ constexpr size_t approx_group_floats(int Lp, int NW) { return (size_t)Lp * (2 + NW) + 4; }
 
-// Both Robust_Sigmoid values of an unordered pair from one exponential.
-// delta = s_b - s_a.  ya = rs(alpha*delta) (contribution of b to pi_hat_a), yb = rs(-alpha*delta).
-__device__ __forceinline__ void robust_pair(float delta, float alpha, float &ya, float &yb) {
-    const float x = alpha * fabsf(delta);
-    const float e = __expf(-x);
-    const float dd = 1.0f + e;
-    float r = __builtin_amdgcn_rcpf(dd);
-    r = fmaf(r, fmaf(-dd, r, 1.0f), r);          // 1/(1+e)      (base/utils.py:71)
-    const float sm = e * r;                       // e/(1+e)      (base/utils.py:73-74)
-    const bool pos = delta > 0.0f, neg = delta < 0.0f;
-    ya = pos ? r : (neg ? sm : 0.5f);
-    yb = pos ? sm : (neg ? r : 0.5f);
-}
+// robust_pair(): both Robust_Sigmoid values of an unordered pair from one exponential (ptr_rsig.h, shared with diversity.hip)
 
 // SoftRank (ptranking/ltr_adhoc/listwise/softrank.py:47-69) is the same two-pass scheme with a Gaussian rank indicator:
 //   E[rank_i] = 1 + sum_{j != i} 0.5*erfc((s_i - s_j)/den),  den = sqrt(2*(2*delta^2))               (:50-56)

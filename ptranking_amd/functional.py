@@ -15,9 +15,10 @@ from . import _lib
 
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
-           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
+           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
 
 LAMBDALOSS_TYPES = {"NDCG_Loss1": 0, "NDCG_Loss2": 1, "NDCG_Loss2++": 2}   # ptranking/ltr_adhoc/listwise/lambdaloss.py:27
+ADCG_TOPK_AXES = {"reference": 0, "subtopics": 0, 0: 0, "documents": 1, 1: 1}   # PTR_ADCG_TOPK_*
 WASS_COST_TYPES = {"p1": 0, "p2": 1, "eg": 2, "dg": 3, "ddg": 4}   # PTR_WASS_COST_*; wassrank/wasserstein_cost_mat.py:113-139
 
 
@@ -257,6 +258,79 @@ def approxndcg_loss(preds, labels, alpha=10.0, presort=True, couple_batch=True, 
     else:
         loss = launch(preds_c)[0]
     return (loss, parts) if return_parts else loss
+
+
+def _div_batch(preds, rele, lens, ntopics):
+    """preds [B, L], rele [B, T, L], lens / ntopics int32 [B] or None — checked, contiguous."""
+    preds = _check("preds", preds)
+    if preds.dim() != 2:
+        raise ValueError(f"preds must be [batch, ranking_size], got {tuple(preds.shape)}")
+    B, L = preds.shape
+    if L > _lib.MAX_LIST_LEN:
+        raise ValueError(f"ranking_size {L} exceeds the supported maximum {_lib.MAX_LIST_LEN}")
+    rele = _check("rele", rele)
+    if rele.dim() != 3 or rele.shape[0] != B or rele.shape[2] != L:
+        raise ValueError(f"rele must be [batch, num_subtopics, ranking_size] = [{B}, T, {L}], got {tuple(rele.shape)}")
+    T = rele.shape[1]
+    if T < 1 or T > _lib.MAX_SUBTOPICS:
+        raise ValueError(f"{T} subtopics: between 1 and {_lib.MAX_SUBTOPICS} are supported")
+    if rele.device != preds.device:
+        raise RuntimeError("preds and rele live on different devices")
+    if lens is not None:
+        lens = _check("lens", lens, torch.int32, (B,))
+    if ntopics is not None:
+        ntopics = _check("ntopics", ntopics, torch.int32, (B,))
+    return preds, rele, lens, ntopics, B, T, L
+
+
+def alphadcg_loss(preds, rele, rt=10.0, alpha=0.5, top_k=10, top_k_axis="reference", lens=None, ntopics=None, return_loss_q=False):
+    """DALETOR's alpha-DCG loss, ptranking/ltr_diversification/score_and_sort/daletor.py:9-38, for a padded batch: preds [B, L], rele [B, T, L]
+    (per query the reference's q_doc_rele_mat), the sum over queries of the reference's one-query loss.  top_k_axis="reference" keeps the
+    first top_k SUBTOPIC rows as the reference's slice does; "documents" keeps the first top_k documents of the presorted ideal order (the
+    alpha-DCG@k its docstring describes); top_k=None: no cut-off.  With return_loss_q also returns the per-query losses [B]."""
+    if top_k_axis not in ADCG_TOPK_AXES:
+        raise ValueError(f"top_k_axis {top_k_axis!r} (supported: 'reference', 'documents')")
+    preds_c, rele, lens, ntopics, B, T, L = _div_batch(preds.detach(), rele, lens, ntopics)
+    dev = preds_c.device
+    parts = {}
+
+    def launch(p):
+        loss_q = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
+        grad = torch.empty((B, L), device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.call("ptr_alphadcg_fwd_bwd", _lib.ptr(p), _lib.ptr(rele), _lib.ptr(lens), _lib.ptr(ntopics), B, T, L, C.c_float(float(rt)),
+                      C.c_float(float(alpha)), int(top_k) if top_k else 0, ADCG_TOPK_AXES[top_k_axis], None, _lib.ptr(loss_q), _lib.ptr(grad),
+                      _lib.current_stream(dev))
+            parts["loss_q"] = loss_q[:B]
+            return _reduce(loss_q, B, dev), grad
+
+    if preds.requires_grad:
+        loss = _FusedLoss.apply(preds if preds.is_contiguous() else preds.contiguous(), lambda p: launch(p.detach()))
+    else:
+        loss = launch(preds_c)[0]
+    return (loss, parts["loss_q"]) if return_loss_q else loss
+
+
+def div_metrics_at_ks(preds, rele, ks, alpha=0.5, max_label=None, lens=None, ntopics=None):
+    """alpha-nDCG@ks, ERR-IA@ks, nERR-IA@ks and the evaluator's `valid` flag for a padded batch -> (andcg [B, nk], err_ia, nerr_ia, valid int32
+    [B]) on the device.  Replaces ptranking/base/ranker.py:269-475 (sort, gather) + ptranking/metric/srd/diversity_metric.py.  The ideal
+    ranking is the input order (presort).  max_label=None: the two ERR-IA outputs are not computed and come back as None (the reference
+    asserts on it, diversity_metric.py:190) — a maximum is never guessed from the batch."""
+    preds, rele, lens, ntopics, B, T, L = _div_batch(preds.detach(), rele, lens, ntopics)
+    ks = [int(k) for k in ks]
+    if len(ks) > _lib.MAX_CUTOFFS:
+        raise ValueError(f"at most {_lib.MAX_CUTOFFS} cut-offs")
+    dev = preds.device
+    new = lambda: torch.empty((B, len(ks)), device=dev, dtype=torch.float32)
+    andcg = new()
+    err, nerr = (None, None) if max_label is None else (new(), new())
+    valid = torch.empty(B, device=dev, dtype=torch.int32)
+    ks_arr = (C.c_int32 * max(len(ks), 1))(*ks)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_div_metrics_at_ks", _lib.ptr(preds), _lib.ptr(rele), _lib.ptr(lens), _lib.ptr(ntopics), B, T, L, ks_arr, len(ks),
+                  C.c_float(float(alpha)), C.c_float(0.0 if max_label is None else float(max_label)), _lib.ptr(andcg), _lib.ptr(err),
+                  _lib.ptr(nerr), _lib.ptr(valid), _lib.current_stream(dev))
+    return andcg, err, nerr, valid
 
 
 def shuffle_ties_order(labels, seed, lens=None):

@@ -39,8 +39,30 @@ def install(names=RANKER_NAMES, ltr_module="ptranking.ltr_adhoc.eval.ltr", extra
     return done
 
 
-def uninstall(ltr_module="ptranking.ltr_adhoc.eval.ltr"):
-    """Restore the reference's own classes."""
+def install_diversification(names=None, ltr_module="ptranking.ltr_diversification.eval.ltr_diversification"):
+    """Rebind DIV_RANKER_NAMES (DALETOR) inside the reference's diversification driver module, which looks its rankers up by name the same
+    way (ltr_diversification.py:387-389); returns {name: installed class}.  The installed DALETOR is the stand-alone class of
+    ptranking_amd.diversity (pointsf scorer on the fused kernels; sf_id='listsf' raises NotImplementedError).  uninstall() restores."""
+    from .diversity import DALETOR, DIV_RANKER_NAMES
+    classes = {"DALETOR": DALETOR}
+    mod = importlib.import_module(ltr_module)
+    done = {}
+    for n in (DIV_RANKER_NAMES if names is None else names):
+        if n not in classes:
+            raise KeyError(f"{n} is not one of {DIV_RANKER_NAMES}")
+        _saved.setdefault((ltr_module, n), getattr(mod, n, None))
+        setattr(mod, n, classes[n])
+        done[n] = classes[n]
+    return done
+
+
+def uninstall(ltr_module=None):
+    """Restore the reference's own classes: in `ltr_module`, or (default) in every module install() / install_diversification() touched."""
+    for m in sorted({m for m, _ in _saved} if ltr_module is None else {ltr_module}):
+        _uninstall_module(m)
+
+
+def _uninstall_module(ltr_module):
     mod = importlib.import_module(ltr_module)
     for (m, n), cls in list(_saved.items()):
         if m != ltr_module:
