@@ -173,6 +173,50 @@ int ptr_div_metrics_at_ks(const float *preds, const float *rele, const int32_t *
                           const int32_t *ks, int nk, float alpha, float max_label, float *andcg, float *err_ia, float *nerr_ia,
                           int32_t *valid, void *stream);
 
+/* ---- DivProbRanker's objectives (csrc/divprob.hip).  The two symbols below are ADDITIVE to ABI v8: nothing declared before them changed, so
+ * PTR_ABI_VERSION stays 8; a v8 library built before them simply lacks the two names.
+ * Data model as above, with two score tensors: mus [B,L] and vars [B,L], the mean and the variance the scorer predicts per document.  With
+ * x[i][j] = (mu_i - mu_j) / sqrt(2 (var_i + var_j)), Phi[i][j] = erfc(x[i][j]) / 2 for j != i and the expected rank R[i] = 1 + sum_j Phi[i][j]
+ * (ptranking/ltr_diversification/util/prob_utils.py:5-26, :62-80).  A variance <= 0 among the first lens[q] documents is the caller's
+ * error: the pair argument divides by zero and the query's outputs are NaN (nothing is checked on the device).  A query with
+ * ntopics[q] = 0 contributes exactly 0.
+ *
+ * ptr_divprob_fwd_bwd — one launch for the loss and both gradients of one of the four objectives (opt_ideal: documents in the given, presorted
+ * order), replacing the op sequences of ptranking/ltr_diversification/score_and_sort/div_prob_ranker.py and their autograd backward:
+ *   PTR_DIVPROB_ANDCG          alpha_dcg_as_a_loss, div_prob_ranker.py:29-79: c[t][i] = sum_j Phi[i][j] r[t][j], loss_q = - sum over the kept
+ *                              (t, i) of r[t][i] (1 - beta)^c[t][i] / log2(1 + R[i]); top_k / top_k_axis exactly as ptr_alphadcg_fwd_bwd
+ *                              (PTR_ADCG_TOPK_SUBTOPICS reproduces the reference's slice of SUBTOPIC rows, :70-75).
+ *   PTR_DIVPROB_ERRIA          err_ia_as_a_loss, :81-165: s = (2^r - 1) / 2^max_label, loss_q = - sum_t sum_i s[t][i] prod_{k<i} (1 - s[t][k])
+ *                              / R[i] over the first top_k documents (top_k <= 0 or >= lens: all; top_k_axis is not used).
+ *   PTR_DIVPROB_PAIRCLS        prob_lambda_loss('PairCLS'), :167-181 + util/div_lambda_utils.py:26-43: over pairs i < j,
+ *                              - [ tb log P + (1 - tb) log Q ], Q = Phi[i][j], P = 1 - Q, tb = mean over the query's subtopics of
+ *                              (1 + clamp(r[t][i] - r[t][j], -1, 1)) / 2; each logarithm is clamped at -100 as F.binary_cross_entropy does.
+ *   PTR_DIVPROB_LAMBDAPAIRCLS  prob_lambda_loss('LambdaPairCLS', opt_ideal), :182-202: the same term times get_delta_alpha_dcg of the input order
+ *                              (ptranking/metric/srd/diversity_metric.py:143-183), | sum_t (g_ti - g_tj)(d_i f_ti - d_j f_tj) | with g = 2^r - 1,
+ *                              d_i = 1 / log2(i + 2), f_ti = (1 - beta)^(sum_{k<i} r[t][k]); norm != 0 divides by the input order's alpha-DCG
+ *                              (:13-30); an ideal value <= 0 gives weight 0 where the reference divides by zero.
+ *   log Q and log P are computed from the scaled complementary error function, never through 1 - Q, so they stay exact where the reference's
+ *   fp32 `1 - erfc(x) / 2` has rounded to 1 (|x| >= 3.8); a logarithm at the -100 clamp passes no gradient, elsewhere the gradient
+ *   is the exact ratio exp(-x^2) / (sqrt(pi) Q).  top_k, max_label and norm are ignored by the objectives that do not name them.
+ *   loss_q [B], grad_mu [B,L], grad_var [B,L], loss_out [1] = sum of loss_q (nullable).  PTR_ERR_INVALID_ARG: a NULL pointer, objective or
+ *   top_k_axis out of range, beta outside (0, 1), max_label < 0 for PTR_DIVPROB_ERRIA.  PTR_ERR_UNSUPPORTED: L > PTR_MAX_LIST_LEN,
+ *   T > PTR_MAX_SUBTOPICS, or a query tile beyond the LDS of a compute unit: 4 * round_up(L, 4) * (3 + K * Tp) + 16 bytes <= 160 KiB, Tp = T
+ *   rounded up to 4, 8, 16 or 32, K = the relevance-sized tiles the objective keeps: 1 for ERRIA and PAIRCLS (T <= 4: L <= 4096; T <= 8:
+ *   L <= 3720; T <= 16: L <= 2152; T <= 32: L <= 1168), 2 for ANDCG (T <= 4: L <= 3720; T <= 8: L <= 2152; T <= 16: L <= 1168; T <= 32:
+ *   L <= 608), 3 for LAMBDAPAIRCLS (T <= 4: L <= 2728; T <= 8: L <= 1516; T <= 16: L <= 800; T <= 32: L <= 412). */
+#define PTR_DIVPROB_ANDCG 0
+#define PTR_DIVPROB_ERRIA 1
+#define PTR_DIVPROB_PAIRCLS 2
+#define PTR_DIVPROB_LAMBDAPAIRCLS 3
+int ptr_divprob_fwd_bwd(const float *mus, const float *vars, const float *rele, const int32_t *lens, const int32_t *ntopics, int B, int T, int L,
+                        int objective, float beta, int top_k, int top_k_axis, float max_label, int norm, float *loss_out, float *loss_q,
+                        float *grad_mu, float *grad_var, void *stream);
+/* ptr_divprob_expected_ranks — ranks [B,L] = R[i] (get_expected_rank, prob_utils.py:62-80; the 'RERAR' sort key of
+ * ptranking/ltr_diversification/base/div_mdn_ranker.py:314-320 is its reciprocal): the first pass of the kernel above, forward only.
+ * Padded documents get 0.  LDS: 12 * round_up(L, 4) bytes per query (48 KiB at L = PTR_MAX_LIST_LEN = 4096; 6 KiB per workgroup of four
+ * queries at L = 128): every supported L fits. */
+int ptr_divprob_expected_ranks(const float *mus, const float *vars, const int32_t *lens, int B, int L, float *ranks, void *stream);
+
 /* Device tie-shuffled label-descending order (the role of arg_shuffle_ties, sampling_utils.py:13-28) from a
  * counter-based RNG: same distribution, NOT the torch.randperm stream (not parity-checked, statistically tested). */
 int ptr_shuffle_ties_order(const float *labels, const int32_t *lens, int B, int L, uint64_t seed, int64_t *perm,

@@ -5,7 +5,8 @@
     host        LABEL_TYPE, DeviceEvaluator, DeviceTrainLoop, the stand-alone pointsf base ranker
     scorer      the pointsf MLP scorer on fused fp32-MFMA kernels (FusedPointScorer) + FlatAdam
     batching    PaddedQueryBatches: device-resident padded query batches (+ lens) replacing the reference's loader stack
-    diversity   the diversification frame: DALETOR (alpha-DCG loss kernel), alpha-nDCG / ERR-IA / nERR-IA on the device, DivQueryBatches
+    diversity   the diversification frame: DALETOR (alpha-DCG loss kernel), DivProbRanker (Gaussian pairwise-rank loss kernel),
+                alpha-nDCG / ERR-IA / nERR-IA on the device, DivQueryBatches
     dp          data-parallel gradient exchange (one RCCL all-reduce per step)
     install()   rebinds the ranker names of RANKER_NAMES (RankNet, LambdaRank, LambdaLoss, ApproxNDCG, ListNet, ListMLE, STListNet,
                 RankCosine, RankMSE, SoftRank, WassRank) inside an installed ptranking so LTREvaluator uses them unchanged; a WassRank
@@ -20,7 +21,7 @@ from .batching import PaddedQueryBatches            # noqa: F401
 from . import letor                                   # noqa: F401
 from .host import LABEL_TYPE, DeviceEvaluator       # noqa: F401
 from .install import install, install_diversification, uninstall   # noqa: F401
-from .diversity import DALETOR, DIV_RANKER_NAMES, DivQueryBatches     # noqa: F401
+from .diversity import DALETOR, DIV_RANKER_NAMES, EXTRA_DIV_RANKER_NAMES, DivProbRanker, DivQueryBatches     # noqa: F401
 from .rankers import (ApproxNDCG, LambdaLoss, LambdaRank, ListMLE, ListNet, RankNet, STListNet, RankCosine, RankMSE, SoftRank, WassRank, DASALC, MDPRank,  # noqa: F401
                       DEFAULT_PARAS, EXTRA_RANKER_NAMES, RANKER_NAMES, make_ranker_classes)
 

@@ -4,11 +4,14 @@
                     evaluation call (ptranking/base/ranker.py:636-669, :269-475) and moves every prediction to the CPU to sort it
   DALETOR           ptranking/ltr_diversification/score_and_sort/daletor.py:41-68 with the method names of
                     ptranking/ltr_diversification/base/diversity_ranker.py and ptranking/base/ranker.py:269-475, :636-695
+  DivProbRanker     ptranking/ltr_diversification/score_and_sort/div_prob_ranker.py:234-359 on base/div_mdn_ranker.py:19-337: a mean and a
+                    variance per document, four objectives built from the Gaussian pairwise comparison (ptr_divprob_fwd_bwd)
 
-Called with the reference's one-query arguments the ranker behaves like the reference (B = 1); called with a DivQueryBatches it trains and
-evaluates in padded batches: one fused loss launch (ptr_alphadcg_fwd_bwd) per batch, one metric launch (ptr_div_metrics_at_ks) per batch,
-no `.cpu()` inside the loops.  Scorer: sf_id 'pointsf' (the point scorer on [q_repr | q_repr * doc | doc], div_point_ranker.py:14-24).
-The listwise scorer of div_list_ranker.py is out of scope and refused.
+Called with the reference's one-query arguments a ranker behaves like the reference (B = 1); called with a DivQueryBatches it trains and
+evaluates in padded batches: one fused loss launch (ptr_alphadcg_fwd_bwd / ptr_divprob_fwd_bwd) per batch, one metric launch
+(ptr_div_metrics_at_ks) per batch, no `.cpu()` inside the loops.  Scorer: sf_id 'pointsf' (the point scorer on
+[q_repr | q_repr * doc | doc], div_point_ranker.py:14-24).  The listwise scorers of div_list_ranker.py / div_mdn_ranker.py are out of scope
+and refused.  Both rankers share one epoch loop and one set of evaluation methods (_DivRanker).
 """
 import copy
 import math
@@ -22,7 +25,12 @@ from .rankers import FusedStepMixin
 from .scorer import FusedScorerMixin
 
 DIV_RANKER_NAMES = ("DALETOR",)
-DEFAULT_DIV_PARAS = {"DALETOR": dict(model_id="DALETOR", rt=10.0, top_k=10)}     # daletor.py:90
+EXTRA_DIV_RANKER_NAMES = ("DivProbRanker",)      # bound by install_diversification(extras=True) only
+DEFAULT_DIV_PARAS = {"DALETOR": dict(model_id="DALETOR", rt=10.0, top_k=10),     # daletor.py:90
+                     "DivProbRanker": dict(model_id="DivProbRanker", K=1, cluster=False, sort_id="ExpRele", top_k=None, opt_id="SuperSoft",
+                                           limit_delta=0.01, metric="nERR-IA", opt_ideal=True, norm=True)}     # div_prob_ranker.py:387-389
+SORT_ID = ("ExpRele", "RERAR", "RiskAware")      # div_mdn_ranker.py:17
+SRD_METRIC = ("aNDCG", "nERR-IA")                # diversity_metric.py:8
 
 
 def _np(a, dtype=np.float32):
@@ -97,34 +105,14 @@ class DivQueryBatches:
             yield self._batches[i]
 
 
-class DALETOR(FusedStepMixin, FusedScorerMixin, PointScorerRanker):
-    """Le Yan, Zhen Qin, Rama Kumar Pasumarthi, Xuanhui Wang, Mike Bendersky: Diversification-Aware Learning to Rank using Distributed
-    Representation, WWW 2021 — the reference's class (daletor.py:41-68) on the fused alpha-DCG loss kernel.
-
-    top_k_axis: "reference" (default) keeps the reference's behaviour, whose top_k slices SUBTOPIC rows; "documents" is the alpha-DCG@k over
-    the first top_k documents that its docstring describes.  alpha is 0.5, the value the reference hard-wires in the loss and in every metric."""
-
-    alpha = 0.5
-    top_k_axis = "reference"
-
-    def __init__(self, sf_para_dict=None, model_para_dict=None, gpu=False, device=None):
-        if sf_para_dict['sf_id'] == 'listsf':
-            raise NotImplementedError("DALETOR with sf_id='listsf' (div_list_ranker.py: an encoder on 3F features and a second concatenation to "
-                                      "6F) is out of scope; use sf_id='pointsf'")
-        sf_para_dict = copy.deepcopy(sf_para_dict)      # the reference triples the caller's own dict in place (diversity_ranker.py:22)
-        sf_para_dict['pointsf']['num_features'] *= 3    # q_repr + latent cross + doc_repr
-        PointScorerRanker.__init__(self, id='DALETOR', sf_para_dict=sf_para_dict, gpu=gpu, device=device)
-        self.rt = model_para_dict['rt']
-        self.top_k = model_para_dict['top_k']
-
-    # ---- scoring (div_point_ranker.py:14-24)
-    def div_forward(self, q_repr, doc_reprs):
-        num_docs = doc_reprs.size(0)
-        cat_reprs = torch.cat((q_repr.expand(num_docs, -1), q_repr * doc_reprs, doc_reprs), 1)
-        return self.point_sf(cat_reprs.unsqueeze(0)).view(-1, num_docs)      # [1, num_docs]
-
-    def div_predict(self, q_repr, doc_reprs):
-        return self.div_forward(q_repr, doc_reprs)
+class _DivRanker(FusedStepMixin, FusedScorerMixin, PointScorerRanker):
+    """What the rankers of the diversification frame share: the point scorer on [q_repr | q_repr * doc | doc], the epoch loop
+    (ranker.py:636-669) and the evaluation methods (ranker.py:269-475), per query as the reference runs them or over a DivQueryBatches.
+    A subclass provides
+      _batch_outputs(X, lens)        the scorer's outputs for a padded batch, as the tuple div_custom_loss_function takes before the relevance;
+                                     the first one is what the stop check of ranker.py:666-667 looks at
+      _batch_sort_scores(X, lens)    the scores [B, L] a padded batch is ranked by
+    and the reference's div_forward / div_predict / div_train_op / div_custom_loss_function."""
 
     def _to_dev(self, t):
         return t.to(self.device, non_blocking=True) if torch.is_tensor(t) and t.device != torch.device(self.device) else t
@@ -133,21 +121,7 @@ class DALETOR(FusedStepMixin, FusedScorerMixin, PointScorerRanker):
         with scorer_lens(self, lens, X):
             return self.forward(X)
 
-    # ---- training (ranker.py:636-669, daletor.py:53-68)
-    def div_custom_loss_function(self, batch_preds, q_doc_rele_mat, **kwargs):
-        assert 'presort' in kwargs and kwargs['presort'] is True     # aiming for directly optimising alpha-nDCG over top-k documents
-        rele = q_doc_rele_mat if q_doc_rele_mat.dim() == 3 else q_doc_rele_mat.unsqueeze(0)
-        loss = F_.alphadcg_loss(batch_preds, rele.float(), rt=self.rt, alpha=self.alpha, top_k=self.top_k, top_k_axis=self.top_k_axis,
-                                lens=kwargs.get('lens'), ntopics=kwargs.get('ntopics'))
-        return self._fused_step(loss)
-
-    def div_train_op(self, q_repr, doc_reprs, q_doc_rele_mat, **kwargs):
-        stop_training = False
-        batch_pred = self.div_forward(q_repr, doc_reprs)
-        if 'epoch_k' in kwargs and kwargs['epoch_k'] % self.stop_check_freq == 0:
-            stop_training = self.stop_training(batch_pred)
-        return self.div_custom_loss_function(batch_pred, q_doc_rele_mat, **kwargs), stop_training
-
+    # ---- training (ranker.py:636-669)
     def div_train(self, train_data, epoch_k=None):
         """One epoch.  A DivQueryBatches trains in padded batches (a query without a relevant document adds exactly 0 to the loss and to the
         gradient); anything else is iterated query by query as the reference does, minus its per-query `.item()`."""
@@ -160,11 +134,11 @@ class DALETOR(FusedStepMixin, FusedScorerMixin, PointScorerRanker):
             check = epoch_k is not None and epoch_k % self.stop_check_freq == 0
             bad = torch.zeros((), dtype=torch.bool, device=self.device)
             for ids, X, rele, lens, ntopics in train_data:
-                batch_pred = self._score_batch(X, lens)
+                outs = self._batch_outputs(X, lens)
                 if check:
-                    p = batch_pred.detach()
+                    p = outs[0].detach()
                     bad |= ~(p != 0).any() | torch.isnan(p).any()
-                epoch_loss += self.div_custom_loss_function(batch_pred, rele, presort=True, lens=lens, ntopics=ntopics).detach().reshape(-1)[:1]
+                epoch_loss += self.div_custom_loss_function(*outs, rele, presort=True, lens=lens, ntopics=ntopics).detach().reshape(-1)[:1]
             if check and bool(bad):
                 print('All zero or NaN error.\n')
                 stop_training = True
@@ -205,7 +179,7 @@ class DALETOR(FusedStepMixin, FusedScorerMixin, PointScorerRanker):
         with torch.no_grad():
             if isinstance(test_data, DivQueryBatches):
                 for ids, X, rele, lens, ntopics in test_data:
-                    add(self._score_batch(X, lens), rele, lens, ntopics)
+                    add(self._batch_sort_scores(X, lens), rele, lens, ntopics)
             else:
                 assert test_data.presort is True
                 for item in test_data:
@@ -246,3 +220,160 @@ class DALETOR(FusedStepMixin, FusedScorerMixin, PointScorerRanker):
         if need_per_q_andcg:
             return andcg, err_ia, nerr_ia, [row.view(1, -1) for a, keep in per_q for row in a[keep].cpu()]
         return andcg, err_ia, nerr_ia
+
+
+class DALETOR(_DivRanker):
+    """Le Yan, Zhen Qin, Rama Kumar Pasumarthi, Xuanhui Wang, Mike Bendersky: Diversification-Aware Learning to Rank using Distributed
+    Representation, WWW 2021 — the reference's class (daletor.py:41-68) on the fused alpha-DCG loss kernel.
+
+    top_k_axis: "reference" (default) keeps the reference's behaviour, whose top_k slices SUBTOPIC rows; "documents" is the alpha-DCG@k over
+    the first top_k documents that its docstring describes.  alpha is 0.5, the value the reference hard-wires in the loss and in every metric."""
+
+    alpha = 0.5
+    top_k_axis = "reference"
+
+    def __init__(self, sf_para_dict=None, model_para_dict=None, gpu=False, device=None):
+        if sf_para_dict['sf_id'] == 'listsf':
+            raise NotImplementedError("DALETOR with sf_id='listsf' (div_list_ranker.py: an encoder on 3F features and a second concatenation to "
+                                      "6F) is out of scope; use sf_id='pointsf'")
+        sf_para_dict = copy.deepcopy(sf_para_dict)      # the reference triples the caller's own dict in place (diversity_ranker.py:22)
+        sf_para_dict['pointsf']['num_features'] *= 3    # q_repr + latent cross + doc_repr
+        PointScorerRanker.__init__(self, id='DALETOR', sf_para_dict=sf_para_dict, gpu=gpu, device=device)
+        self.rt = model_para_dict['rt']
+        self.top_k = model_para_dict['top_k']
+
+    # ---- scoring (div_point_ranker.py:14-24)
+    def div_forward(self, q_repr, doc_reprs):
+        num_docs = doc_reprs.size(0)
+        cat_reprs = torch.cat((q_repr.expand(num_docs, -1), q_repr * doc_reprs, doc_reprs), 1)
+        return self.point_sf(cat_reprs.unsqueeze(0)).view(-1, num_docs)      # [1, num_docs]
+
+    def div_predict(self, q_repr, doc_reprs):
+        return self.div_forward(q_repr, doc_reprs)
+
+    def _batch_outputs(self, X, lens):
+        return (self._score_batch(X, lens),)
+
+    def _batch_sort_scores(self, X, lens):
+        return self._score_batch(X, lens)
+
+    # ---- training (ranker.py:636-669, daletor.py:53-68)
+    def div_custom_loss_function(self, batch_preds, q_doc_rele_mat, **kwargs):
+        assert 'presort' in kwargs and kwargs['presort'] is True     # aiming for directly optimising alpha-nDCG over top-k documents
+        rele = q_doc_rele_mat if q_doc_rele_mat.dim() == 3 else q_doc_rele_mat.unsqueeze(0)
+        loss = F_.alphadcg_loss(batch_preds, rele.float(), rt=self.rt, alpha=self.alpha, top_k=self.top_k, top_k_axis=self.top_k_axis,
+                                lens=kwargs.get('lens'), ntopics=kwargs.get('ntopics'))
+        return self._fused_step(loss)
+
+    def div_train_op(self, q_repr, doc_reprs, q_doc_rele_mat, **kwargs):
+        stop_training = False
+        batch_pred = self.div_forward(q_repr, doc_reprs)
+        if 'epoch_k' in kwargs and kwargs['epoch_k'] % self.stop_check_freq == 0:
+            stop_training = self.stop_training(batch_pred)
+        return self.div_custom_loss_function(batch_pred, q_doc_rele_mat, **kwargs), stop_training
+
+
+class DivProbRanker(_DivRanker):
+    """The reference's DivProbRanker (ptranking/ltr_diversification/score_and_sort/div_prob_ranker.py:234-359 on
+    ptranking/ltr_diversification/base/div_mdn_ranker.py:19-337): the scorer predicts a mean and a variance per document (for K > 1 a softmax
+    mixture of K components), and the loss is one of four objectives built from the Gaussian pairwise comparison, all on ONE fused kernel
+    (ptr_divprob_fwd_bwd): opt_id 'SuperSoft' with metric 'aNDCG' or 'nERR-IA', 'PairCLS', 'LambdaPairCLS'.
+
+    Scorer: the point scorer with out_dim = 2 (K = 1) or 3 K on [q_repr | q_repr * doc | doc] — the column order of DivQueryBatches and
+    DALETOR; the reference's own order is [q_repr | doc | q_repr * doc] (div_mdn_ranker.py:213-214), a fixed permutation of the input
+    columns of a freshly initialised network.  sort_id: 'ExpRele' (the means), 'RiskAware' (mean - 0.1 variance), 'RERAR' (reciprocal
+    expected ranks, ptr_divprob_expected_ranks).  Out of scope and refused: the listwise scorers (sf_id 'listsf...', with or without
+    batch_cocos), cluster=True, opt_ideal=False, opt_id='Portfolio', generate_div_run.
+
+    top_k_axis: as DALETOR's — "reference" keeps the reference's alpha_dcg_as_a_loss, whose top_k slices SUBTOPIC rows.  The pairwise
+    objectives are the exact cross entropy, not the reference's `1 - erfc(x) / 2` arithmetic."""
+
+    top_k_axis = "reference"
+
+    def __init__(self, sf_para_dict=None, model_para_dict=None, gpu=False, device=None):
+        sf_id = sf_para_dict['sf_id']
+        if sf_id.startswith('listsf'):
+            raise NotImplementedError(f"DivProbRanker with sf_id={sf_id!r} (the listwise MDN scorer of div_mdn_ranker.py:103-154, with or without "
+                                      "batch_cocos) is out of scope; use sf_id='pointsf'")
+        K, cluster = model_para_dict['K'], model_para_dict['cluster']
+        assert K >= 1                                                            # div_mdn_ranker.py:39
+        if cluster:
+            raise NotImplementedError("DivProbRanker with cluster=True (a group of independent scorers, div_mdn_ranker.py:48-51) is out of scope")
+        assert model_para_dict['sort_id'] in SORT_ID                             # :43
+        self.opt_id = model_para_dict['opt_id']
+        assert self.opt_id in ['PairCLS', 'LambdaPairCLS', 'SuperSoft', 'Portfolio']     # div_prob_ranker.py:248
+        if self.opt_id == 'Portfolio':
+            raise NotImplementedError("DivProbRanker with opt_id='Portfolio' (a cvxpy layer, div_prob_ranker.py:264-286) is out of scope")
+        sf_para_dict = copy.deepcopy(sf_para_dict)      # the reference rewrites the caller's own dict in place (div_mdn_ranker.py:35, :53-56)
+        sf_para_dict[sf_id]['num_features'] *= 3        # q_repr + latent cross + doc_repr
+        sf_para_dict[sf_id]['out_dim'] = 2 if K == 1 else 3 * K      # mu and sigma / mixing coefficient, mu, sigma per component
+        PointScorerRanker.__init__(self, id='DivProbRanker', sf_para_dict=sf_para_dict, gpu=gpu, device=device)
+        self.K, self.cluster, self.sort_id, self.limit_delta = K, cluster, model_para_dict['sort_id'], model_para_dict['limit_delta']
+        self.b = 0.1                                    # :46
+        self.beta = 0.5                                 # i.e., alpha in alpha-nDCG (div_prob_ranker.py:250)
+        self.norm, self.top_k, self.metric, self.opt_ideal = False, None, None, True
+        if 'LambdaPairCLS' == self.opt_id:
+            self.opt_ideal, self.norm = model_para_dict['opt_ideal'], model_para_dict['norm']
+        elif 'SuperSoft' == self.opt_id:
+            self.opt_ideal, self.top_k, self.metric = model_para_dict['opt_ideal'], model_para_dict['top_k'], model_para_dict['metric']
+            assert self.metric in SRD_METRIC
+        if not self.opt_ideal:
+            raise NotImplementedError("DivProbRanker with opt_ideal=False (a re-sort by expected rank, div_prob_ranker.py:55-61, :203-231) is "
+                                      "out of scope")
+
+    def uniform_eval_setting(self, **kwargs):
+        eval_dict = kwargs['eval_dict']
+        if 'SuperSoft' == self.opt_id and eval_dict["do_validation"] and not eval_dict['vali_metric'] == self.metric:
+            eval_dict['vali_metric'] = self.metric
+
+    # ---- scoring (div_mdn_ranker.py:248-326)
+    def _head(self, batch_components):
+        """[B, L, 2] or [B, L, 3 K] scorer outputs -> (means [B, L], variances [B, L]), div_mdn_ranker.py:276-294."""
+        to_var = torch.exp if self.limit_delta is None else (lambda s: torch.sigmoid(s) * self.limit_delta)     # representing sigma^2
+        if 1 == self.K:
+            return batch_components[:, :, 0], to_var(batch_components[:, :, 1])
+        batch_weights, batch_mu_i, batch_std_var_i = torch.split(batch_components, split_size_or_sections=self.K, dim=2)
+        batch_coefficients = torch.softmax(batch_weights, dim=2)
+        return torch.sum(batch_coefficients * batch_mu_i, dim=2), torch.sum(batch_coefficients * to_var(batch_std_var_i), dim=2)
+
+    def _sort_scores(self, batch_mus, batch_vars, lens=None):
+        if 'RERAR' == self.sort_id:       # reciprocal_expected_rank_as_relevance
+            ranks = F_.expected_ranks(batch_mus.contiguous(), batch_vars.contiguous(), lens=lens)
+            return torch.where(ranks > 0, 1.0 / ranks, torch.zeros_like(ranks))     # padded documents: 0
+        elif 'ExpRele' == self.sort_id:
+            return batch_mus
+        elif 'RiskAware' == self.sort_id:
+            return batch_mus - self.b * batch_vars
+        raise NotImplementedError
+
+    def div_forward(self, q_repr, doc_reprs):
+        num_docs = doc_reprs.size(0)
+        cat_reprs = torch.cat((q_repr.expand(num_docs, -1), q_repr * doc_reprs, doc_reprs), 1)
+        return self._head(self.point_sf(cat_reprs.unsqueeze(0)).view(1, num_docs, -1))      # ([1, num_docs], [1, num_docs])
+
+    def div_predict(self, q_repr, doc_reprs):
+        batch_mus, batch_vars = self.div_forward(q_repr, doc_reprs)
+        return self._sort_scores(batch_mus, batch_vars)
+
+    def _batch_outputs(self, X, lens):
+        with scorer_lens(self, lens, X):
+            return self._head(self.point_sf(X).view(X.size(0), X.size(1), -1))       # host.py's forward views ONE output per document
+
+    def _batch_sort_scores(self, X, lens):
+        return self._sort_scores(*self._batch_outputs(X, lens), lens=lens)
+
+    # ---- training (div_prob_ranker.py:295-359, div_mdn_ranker.py:329-337)
+    def div_custom_loss_function(self, batch_mus, batch_vars, q_doc_rele_mat, **kwargs):
+        assert 'presort' in kwargs and kwargs['presort'] is True     # aiming for directly optimising alpha-nDCG over top-k documents
+        if kwargs.get('batch_cocos') is not None:
+            raise NotImplementedError("batch_cocos (the correlation coefficients of the listwise scorer) is out of scope")
+        rele = q_doc_rele_mat if q_doc_rele_mat.dim() == 3 else q_doc_rele_mat.unsqueeze(0)
+        objective = self.metric if 'SuperSoft' == self.opt_id else self.opt_id
+        loss = F_.divprob_loss(batch_mus, batch_vars, rele.float(), objective, beta=self.beta, top_k=self.top_k, top_k_axis=self.top_k_axis,
+                               max_label=1.0, norm=self.norm, lens=kwargs.get('lens'), ntopics=kwargs.get('ntopics'))
+        return self._fused_step(loss)
+
+    def div_train_op(self, q_repr, doc_reprs, q_doc_rele_mat, **kwargs):
+        stop_training = False
+        batch_mus, batch_sigma_sqs = self.div_forward(q_repr, doc_reprs)
+        return self.div_custom_loss_function(batch_mus, batch_sigma_sqs, q_doc_rele_mat, **kwargs), stop_training

@@ -15,10 +15,11 @@ from . import _lib
 
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
-           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
+           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES","shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
 
 LAMBDALOSS_TYPES = {"NDCG_Loss1": 0, "NDCG_Loss2": 1, "NDCG_Loss2++": 2}   # ptranking/ltr_adhoc/listwise/lambdaloss.py:27
 ADCG_TOPK_AXES = {"reference": 0, "subtopics": 0, 0: 0, "documents": 1, 1: 1}   # PTR_ADCG_TOPK_*
+DIVPROB_OBJECTIVES = {"aNDCG": 0, "nERR-IA": 1, "PairCLS": 2, "LambdaPairCLS": 3, 0: 0, 1: 1, 2: 2, 3: 3}   # PTR_DIVPROB_*
 WASS_COST_TYPES = {"p1": 0, "p2": 1, "eg": 2, "dg": 3, "ddg": 4}   # PTR_WASS_COST_*; wassrank/wasserstein_cost_mat.py:113-139
 
 
@@ -331,6 +332,85 @@ def div_metrics_at_ks(preds, rele, ks, alpha=0.5, max_label=None, lens=None, nto
                   C.c_float(float(alpha)), C.c_float(0.0 if max_label is None else float(max_label)), _lib.ptr(andcg), _lib.ptr(err),
                   _lib.ptr(nerr), _lib.ptr(valid), _lib.current_stream(dev))
     return andcg, err, nerr, valid
+
+
+class _FusedLoss2(torch.autograd.Function):
+    """forward(mus, vars, launch) where launch(mus, vars) -> (loss 0-d tensor, grad_mu [B,L], grad_var [B,L]); backward scales both."""
+
+    @staticmethod
+    def forward(ctx, mus, vars, launch):
+        loss, grad_mu, grad_var = launch(mus, vars)
+        ctx.save_for_backward(grad_mu, grad_var)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad_mu, grad_var = ctx.saved_tensors
+        return grad_mu * grad_out, grad_var * grad_out, None
+
+
+def _divprob_scores(mus, vars, lens):
+    mus = _check("mus", mus)
+    if mus.dim() != 2:
+        raise ValueError(f"mus must be [batch, ranking_size], got {tuple(mus.shape)}")
+    B, L = mus.shape
+    vars = _check("vars", vars, shape=(B, L))
+    if vars.device != mus.device:
+        raise RuntimeError("mus and vars live on different devices")
+    if L > _lib.MAX_LIST_LEN:
+        raise ValueError(f"ranking_size {L} exceeds the supported maximum {_lib.MAX_LIST_LEN}")
+    if lens is not None:
+        lens = _check("lens", lens, torch.int32, (B,))
+    return mus, vars, lens, B, L
+
+
+def divprob_loss(mus, vars, rele, objective, beta=0.5, top_k=None, top_k_axis="reference", max_label=1.0, norm=True, lens=None, ntopics=None,
+                 return_loss_q=False):
+    """DivProbRanker's objectives, ptranking/ltr_diversification/score_and_sort/div_prob_ranker.py:29-202 (opt_ideal), for a padded batch:
+    mus / vars [B, L] (the predicted mean and variance per document), rele [B, T, L]; the sum over queries of the reference's one-query loss,
+    differentiable in mus and vars (one launch, both gradients).  objective: 'aNDCG' (alpha_dcg_as_a_loss; top_k / top_k_axis as
+    alphadcg_loss), 'nERR-IA' (err_ia_as_a_loss; top_k cuts documents, max_label), 'PairCLS', 'LambdaPairCLS' (prob_lambda_loss; norm).
+    The pairwise terms are the exact -[t log P + (1 - t) log Q] with each logarithm clamped at -100, not the reference's
+    `1 - erfc(x) / 2`, which rounds to 1 from |x| = 3.8 on.  With return_loss_q also returns the per-query losses [B]."""
+    if objective not in DIVPROB_OBJECTIVES:
+        raise ValueError(f"objective {objective!r} (supported: 'aNDCG', 'nERR-IA', 'PairCLS', 'LambdaPairCLS')")
+    if top_k_axis not in ADCG_TOPK_AXES:
+        raise ValueError(f"top_k_axis {top_k_axis!r} (supported: 'reference', 'documents')")
+    mus_c, rele, lens, ntopics, B, T, L = _div_batch(mus.detach(), rele, lens, ntopics)
+    vars_c = _check("vars", vars.detach(), shape=(B, L))
+    if vars_c.device != mus_c.device:
+        raise RuntimeError("mus and vars live on different devices")
+    dev = mus_c.device
+    parts = {}
+
+    def launch(m, v):
+        loss_q = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
+        grad_mu = torch.empty((B, L), device=dev, dtype=torch.float32)
+        grad_var = torch.empty((B, L), device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.call("ptr_divprob_fwd_bwd", _lib.ptr(m), _lib.ptr(v), _lib.ptr(rele), _lib.ptr(lens), _lib.ptr(ntopics), B, T, L,
+                      DIVPROB_OBJECTIVES[objective], C.c_float(float(beta)), int(top_k) if top_k else 0, ADCG_TOPK_AXES[top_k_axis],
+                      C.c_float(float(max_label)), int(bool(norm)), None, _lib.ptr(loss_q), _lib.ptr(grad_mu), _lib.ptr(grad_var),
+                      _lib.current_stream(dev))
+            parts["loss_q"] = loss_q[:B]
+            return _reduce(loss_q, B, dev), grad_mu, grad_var
+
+    if mus.requires_grad or vars.requires_grad:
+        loss = _FusedLoss2.apply(mus.contiguous(), vars.contiguous(), lambda m, v: launch(m.detach(), v.detach()))
+    else:
+        loss = launch(mus_c, vars_c)[0]
+    return (loss, parts["loss_q"]) if return_loss_q else loss
+
+
+def expected_ranks(mus, vars, lens=None):
+    """Expected ranks [B, L] of documents with independent normal scores: 1 + sum_{j != i} erfc((mu_i - mu_j) / sqrt(2 (var_i + var_j))) / 2,
+    ptranking/ltr_diversification/util/prob_utils.py:62-80; padded documents get 0.  Not differentiable (DivProbRanker's 'RERAR' sort key)."""
+    mus, vars, lens, B, L = _divprob_scores(mus.detach(), vars.detach(), lens)
+    ranks = torch.empty((B, L), device=mus.device, dtype=torch.float32)
+    with torch.cuda.device(mus.device):
+        _lib.call("ptr_divprob_expected_ranks", _lib.ptr(mus), _lib.ptr(vars), _lib.ptr(lens), B, L, _lib.ptr(ranks),
+                  _lib.current_stream(mus.device))
+    return ranks
 
 
 def shuffle_ties_order(labels, seed, lens=None):

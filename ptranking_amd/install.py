@@ -39,17 +39,24 @@ def install(names=RANKER_NAMES, ltr_module="ptranking.ltr_adhoc.eval.ltr", extra
     return done
 
 
-def install_diversification(names=None, ltr_module="ptranking.ltr_diversification.eval.ltr_diversification"):
+def install_diversification(names=None, ltr_module="ptranking.ltr_diversification.eval.ltr_diversification", extras=False):
     """Rebind DIV_RANKER_NAMES (DALETOR) inside the reference's diversification driver module, which looks its rankers up by name the same
     way (ltr_diversification.py:387-389); returns {name: installed class}.  The installed DALETOR is the stand-alone class of
-    ptranking_amd.diversity (pointsf scorer on the fused kernels; sf_id='listsf' raises NotImplementedError).  uninstall() restores."""
-    from .diversity import DALETOR, DIV_RANKER_NAMES
+    ptranking_amd.diversity (pointsf scorer on the fused kernels; sf_id='listsf' raises NotImplementedError).  extras=True adds
+    EXTRA_DIV_RANKER_NAMES (DivProbRanker: pointsf, opt_ideal, no cluster / Portfolio; its pairwise objectives are the exact cross entropy,
+    not the reference's fp32 arithmetic), which the default drop-in and an explicit `names` leave alone, as install(extras=True) does for
+    the ad-hoc rankers.  uninstall() restores."""
+    from .diversity import DALETOR, DIV_RANKER_NAMES, EXTRA_DIV_RANKER_NAMES, DivProbRanker
     classes = {"DALETOR": DALETOR}
+    names = DIV_RANKER_NAMES if names is None else tuple(names)
+    if extras:
+        classes["DivProbRanker"] = DivProbRanker
+        names = names + tuple(n for n in EXTRA_DIV_RANKER_NAMES if n not in names)
     mod = importlib.import_module(ltr_module)
     done = {}
-    for n in (DIV_RANKER_NAMES if names is None else names):
+    for n in names:
         if n not in classes:
-            raise KeyError(f"{n} is not one of {DIV_RANKER_NAMES}")
+            raise KeyError(f"{n} is not one of {DIV_RANKER_NAMES + (EXTRA_DIV_RANKER_NAMES if extras else ())}")
         _saved.setdefault((ltr_module, n), getattr(mod, n, None))
         setattr(mod, n, classes[n])
         done[n] = classes[n]
