@@ -89,7 +89,30 @@ OPTIONAL = set()
 
 _lib = None
 
-LOSS_KINDS = {"ptr_ranknet_fwd_bwd": 1, "ptr_lambdarank_fwd_bwd": 2, "ptr_lambdaloss_fwd_bwd": 3, "ptr_listnet_fwd_bwd": 4}   # PTR_LOSS_*
+
+class Loss:
+    """A loss that ptr_train_step also serves: the entry point (preds, labels, lens, B, L, <params>, loss_out, loss_q, grad, stream), its
+    PTR_LOSS_* kind, and <params> in ABI order as (name, ctypes type).  ptr_train_step reads the same values from its descriptor as
+    loss_i[] = the integer parameters and loss_f[] = the float parameters, each in ABI order (csrc/train_step.hip)."""
+
+    def __init__(self, entry, kind, params=()):
+        self.entry, self.kind, self.params = entry, kind, tuple(params)
+
+    def c_args(self, **values):
+        """<params> as the entry point takes them."""
+        return [C.c_float(float(values[n])) if t is _f else int(values[n]) for n, t in self.params]
+
+    def desc_arrays(self, **values):
+        """(loss_i, loss_f) as `ptr_train_step_desc` carries them."""
+        return (tuple(int(values[n]) for n, t in self.params if t is _i), tuple(C.c_float(float(values[n])).value for n, t in self.params if t is _f))
+
+
+LOSSES = {
+    "ranknet": Loss("ptr_ranknet_fwd_bwd", 1, [("sigma", _f)]),                                                                  # PTR_LOSS_RANKNET
+    "lambdarank": Loss("ptr_lambdarank_fwd_bwd", 2, [("sigma", _f)]),                                                            # PTR_LOSS_LAMBDARANK
+    "lambdaloss": Loss("ptr_lambdaloss_fwd_bwd", 3, [("k", _i), ("sigma", _f), ("mu", _f), ("loss_type", _i), ("presort", _i)]),   # PTR_LOSS_LAMBDALOSS
+    "listnet": Loss("ptr_listnet_fwd_bwd", 4),                                                                                   # PTR_LOSS_LISTNET
+}
 
 
 class TrainStepDesc(C.Structure):

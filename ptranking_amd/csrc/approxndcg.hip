@@ -402,9 +402,7 @@ extern "C" int ptr_approxndcg_fwd_bwd(const float *preds, const float *labels, c
         auto go = [&](auto kern, int dpt) -> int {
             constexpr int QPB = kBlock / kWave;
             const size_t lds = (size_t)QPB * 64 * approx_ring_sort_width(dpt) * sizeof(float);
-            hipLaunchKernelGGL(kern, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, st, preds, labels, lens, B, L, alpha, presort, couple_batch,
-                               dcg_q, inv_idcg_q, grad);
-            return check_hip(hipGetLastError(), who);
+            return launch_queries(kern, B, QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, alpha, presort, couple_batch, dcg_q, inv_idcg_q, grad);
         };
         const int rc = L <= 64 ? go(approxndcg_ring_kernel<1>, 1) : L <= 128 ? go(approxndcg_ring_kernel<2>, 2)
                      : L <= 192 ? go(approxndcg_ring_kernel<3>, 3) : L <= 256 ? go(approxndcg_ring_kernel<4>, 4)
@@ -414,12 +412,9 @@ extern "C" int ptr_approxndcg_fwd_bwd(const float *preds, const float *labels, c
         const int Lp = round_up(L, 4);
         int rc = dispatch_tiling(L, [&]<int G, int DPT>() -> int {
             constexpr int QPB = kBlock / G, NW = G / kWave;
-            auto kern = approxndcg_kernel<G, DPT, false>;
             const size_t lds = QPB * approx_group_floats(Lp, NW) * sizeof(float);
-            if (int e = allow_lds(kern, lds)) return e;
-            hipLaunchKernelGGL(kern, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, st, preds, labels, lens, B, L, Lp, alpha, presort,
-                               couple_batch, PTR_MAX_LIST_LEN, dcg_q, inv_idcg_q, grad);
-            return check_hip(hipGetLastError(), who);
+            return launch_queries(approxndcg_kernel<G, DPT, false>, B, QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, Lp, alpha, presort,
+                                  couple_batch, PTR_MAX_LIST_LEN, dcg_q, inv_idcg_q, grad);
         });
         if (rc) return rc;
     }
@@ -440,24 +435,19 @@ extern "C" int ptr_softrank_fwd_bwd(const float *preds, const float *labels, con
                                     int top_k, float *loss_out, float *loss_q, float *grad, void *stream) {
     using namespace ptr;
     const char *who = "ptr_softrank_fwd_bwd";
-    if (int rc = check_batch(preds, labels, B, L, who)) return rc;
-    if (B > 0 && (!loss_q || !grad)) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_loss_args(preds, labels, B, L, loss_q && grad, who)) return rc;
     if (!(delta > 0.0f)) { set_error("%s: delta must be > 0 (got %g)", who, (double)delta); return PTR_ERR_INVALID_ARG; }
-    hipStream_t st = as_stream(stream);
     if (B > 0) {
         const float var = 2.0f * (delta * delta);             // softrank.py:52, in fp32 like the reference's tensor arithmetic
         const float inv_den = 1.0f / sqrtf(2.0f * var);       // :54
         const int Lp = round_up(L, 4);
         int rc = dispatch_tiling(L, [&]<int G, int DPT>() -> int {
             constexpr int QPB = kBlock / G, NW = G / kWave;
-            auto kern = approxndcg_kernel<G, DPT, true>;
             const size_t lds = QPB * approx_group_floats(Lp, NW) * sizeof(float);
-            if (int e = allow_lds(kern, lds)) return e;
-            hipLaunchKernelGGL(kern, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, st, preds, labels, lens, B, L, Lp, inv_den, 1, 0,
-                               top_k > 0 ? top_k : PTR_MAX_LIST_LEN, loss_q, (float *)nullptr, grad);
-            return check_hip(hipGetLastError(), who);
+            return launch_queries(approxndcg_kernel<G, DPT, true>, B, QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, Lp, inv_den, 1, 0,
+                                  top_k > 0 ? top_k : PTR_MAX_LIST_LEN, loss_q, (float *)nullptr, grad);
         });
         if (rc) return rc;
     }
-    return loss_out ? ptr_sum_f32(loss_q, B, 1.0f, loss_out, stream) : 0;
+    return finish_loss(loss_q, B, 1.0f, loss_out, stream);
 }

@@ -17,21 +17,12 @@
 // R[:, j] broadcast from LDS; A and Bc go to LDS; pass 2 walks the partners once more and, because d is symmetric, takes both
 // directions of a pair from the same exponential.  No atomics, nothing of size L x L anywhere, fixed summation order.
 // LDS per query: S[Lp] | A[Lp] | R[Lp][TP] | Bc[Lp][TP] (TP = T rounded up to 4, 8, 16 or 32: float4 broadcast reads of a column).
-#include "ptr_device.h"
+#include "ptr_div.h"
 #include "ptr_rsig.h"
 
 namespace ptr {
 
 __host__ __device__ constexpr size_t adcg_group_floats(int Lp, int TP) { return (size_t)Lp * (2 + 2 * TP) + 4; }
-constexpr size_t kLdsPerWorkgroup = 160 * 1024;       // gfx950: 160 KiB per CU, all of it available to one workgroup
-
-template <int TP> __device__ __forceinline__ void lds_row(const float *row, float (&v)[TP]) {
-#pragma unroll
-    for (int u = 0; u < TP; u += 4) {
-        const float4 x = *reinterpret_cast<const float4 *>(row + u);
-        v[u] = x.x; v[u + 1] = x.y; v[u + 2] = x.z; v[u + 3] = x.w;
-    }
-}
 
 template <int G, int TP>
 __global__ void __launch_bounds__(kBlock)
@@ -214,16 +205,6 @@ div_metrics_kernel(const float *__restrict__ preds, const float *__restrict__ re
     }
 }
 
-static int tp_of(int T) { return T <= 4 ? 4 : T <= 8 ? 8 : T <= 16 ? 16 : 32; }
-
-static int check_div(const void *preds, const void *rele, int B, int T, int L, float alpha, const char *who) {
-    if (int rc = check_batch(preds, rele, B, L, who)) return rc;
-    if (T <= 0) { set_error("%s: bad number of subtopics T=%d", who, T); return PTR_ERR_INVALID_ARG; }
-    if (!(alpha > 0.0f && alpha < 1.0f)) { set_error("%s: alpha must be in (0, 1) (got %g)", who, (double)alpha); return PTR_ERR_INVALID_ARG; }
-    if (T > PTR_MAX_SUBTOPICS) { set_error("%s: %d subtopics exceed PTR_MAX_SUBTOPICS=%d", who, T, PTR_MAX_SUBTOPICS); return PTR_ERR_UNSUPPORTED; }
-    return 0;
-}
-
 }  // namespace ptr
 
 extern "C" int ptr_alphadcg_fwd_bwd(const float *preds, const float *rele, const int32_t *lens, const int32_t *ntopics, int B, int T,
@@ -233,8 +214,8 @@ extern "C" int ptr_alphadcg_fwd_bwd(const float *preds, const float *rele, const
     const char *who = "ptr_alphadcg_fwd_bwd";
     if (int rc = check_div(preds, rele, B, T, L, alpha, who)) return rc;
     if (!(rt > 0.0f)) { set_error("%s: rt must be > 0 (got %g)", who, (double)rt); return PTR_ERR_INVALID_ARG; }
-    if (top_k_axis != 0 && top_k_axis != 1) { set_error("%s: top_k_axis must be 0 (subtopics) or 1 (documents), got %d", who, top_k_axis); return PTR_ERR_INVALID_ARG; }
-    if (B > 0 && (!loss_q || !grad)) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_top_k_axis(top_k_axis, who)) return rc;
+    if (int rc = check_pointers(B, loss_q && grad, who)) return rc;
     const int Lp = round_up(L, 4), TP = tp_of(T);
     const int QPB = L <= 128 ? kBlock / kWave : 1;
     const size_t lds = (size_t)QPB * adcg_group_floats(Lp, TP) * sizeof(float);
@@ -246,17 +227,12 @@ extern "C" int ptr_alphadcg_fwd_bwd(const float *preds, const float *rele, const
     if (B > 0) {
         const double c = 1.0 - (double)alpha;
         auto go = [&](auto kern) -> int {
-            if (int e = allow_lds(kern, lds)) return e;
-            hipLaunchKernelGGL(kern, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, as_stream(stream), preds, rele, lens, ntopics, B, T, L, Lp, rt,
-                               (float)log2(c), (float)log(c), top_k, top_k_axis, loss_q, grad);
-            return check_hip(hipGetLastError(), who);
+            return launch_queries(kern, B, QPB, kBlock, lds, stream, who, preds, rele, lens, ntopics, B, T, L, Lp, rt, (float)log2(c), (float)log(c), top_k,
+                                  top_k_axis, loss_q, grad);
         };
-        int rc;
-        if (QPB > 1) rc = TP == 4 ? go(alphadcg_kernel<64, 4>) : TP == 8 ? go(alphadcg_kernel<64, 8>) : TP == 16 ? go(alphadcg_kernel<64, 16>) : go(alphadcg_kernel<64, 32>);
-        else rc = TP == 4 ? go(alphadcg_kernel<256, 4>) : TP == 8 ? go(alphadcg_kernel<256, 8>) : TP == 16 ? go(alphadcg_kernel<256, 16>) : go(alphadcg_kernel<256, 32>);
-        if (rc) return rc;
+        if (int rc = dispatch_tp(T, [&]<int TP_>() { return QPB > 1 ? go(alphadcg_kernel<64, TP_>) : go(alphadcg_kernel<256, TP_>); })) return rc;
     }
-    return loss_out ? ptr_sum_f32(loss_q, B, 1.0f, loss_out, stream) : 0;
+    return finish_loss(loss_q, B, 1.0f, loss_out, stream);
 }
 
 extern "C" int ptr_div_metrics_at_ks(const float *preds, const float *rele, const int32_t *lens, const int32_t *ntopics, int B, int T,
@@ -282,11 +258,8 @@ extern "C" int ptr_div_metrics_at_ks(const float *preds, const float *rele, cons
     return dispatch_tiling(L, [&]<int G, int DPT>() -> int {
         constexpr int QPB = kBlock / G;
         const int Lp = round_up(L, 4);
-        auto kern = div_metrics_kernel<G, DPT>;
         const size_t lds = (size_t)QPB * (2 * (size_t)Lp + 4) * sizeof(float);
-        if (int e = allow_lds(kern, lds)) return e;
-        hipLaunchKernelGGL(kern, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, as_stream(stream), preds, rele, lens, ntopics, B, T, L, Lp, ck,
-                           (float)log2(1.0 - (double)alpha), inv_2ml, andcg, err_ia, nerr_ia, valid);
-        return check_hip(hipGetLastError(), who);
+        return launch_queries(div_metrics_kernel<G, DPT>, B, QPB, kBlock, lds, stream, who, preds, rele, lens, ntopics, B, T, L, Lp, ck,
+                              (float)log2(1.0 - (double)alpha), inv_2ml, andcg, err_ia, nerr_ia, valid);
     });
 }

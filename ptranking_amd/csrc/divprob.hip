@@ -29,28 +29,14 @@
 // side is read as an LDS broadcast; forward and backward in one launch, no atomics, nothing of size L x L anywhere, fixed summation order.
 // LDS per query: M[Lp] | V[Lp] | A[Lp] | K tiles [Lp][TP] | red[4]; K = 1 (ERRIA: s; PAIRCLS: r), 2 (ANDCG: r, dLoss/dcov),
 // 3 (LAMBDAPAIRCLS: r, d f, g); TP = T rounded up to 4, 8, 16 or 32.
-#include "ptr_device.h"
+#include "ptr_div.h"
 
 namespace ptr {
-
-constexpr size_t kLdsPerWorkgroup = 160 * 1024;       // gfx950: 160 KiB per CU, all of it available to one workgroup
 
 __host__ __device__ constexpr int divprob_tiles(int obj) {
     return obj == PTR_DIVPROB_ANDCG ? 2 : obj == PTR_DIVPROB_LAMBDAPAIRCLS ? 3 : 1;
 }
 __host__ __device__ constexpr size_t divprob_group_floats(int Lp, int TP, int K) { return (size_t)Lp * (3 + K * TP) + 4; }
-
-template <int TP> __device__ __forceinline__ void lds_row(const float *row, float (&v)[TP]) {
-#pragma unroll
-    for (int u = 0; u < TP; u += 4) {
-        const float4 x = *reinterpret_cast<const float4 *>(row + u);
-        v[u] = x.x; v[u + 1] = x.y; v[u + 2] = x.z; v[u + 3] = x.w;
-    }
-}
-template <int TP> __device__ __forceinline__ void lds_put(float *row, const float (&v)[TP]) {
-#pragma unroll
-    for (int u = 0; u < TP; u += 4) *reinterpret_cast<float4 *>(row + u) = float4{v[u], v[u + 1], v[u + 2], v[u + 3]};
-}
 
 // 1 / sqrt(z): v_rsq_f32 and one Newton step (the pair argument x carries its error into erfc at relative weight ~ 2 x^2)
 __device__ __forceinline__ float inv_sqrt(float z) {
@@ -350,17 +336,11 @@ divprob_ranks_kernel(const float *__restrict__ mus, const float *__restrict__ va
         for (int i = t; i < L; i += G) ranks[(size_t)q * L + i] = i < n ? out[i] : 0.0f;     // thread t reads what it wrote
 }
 
-static int tp_of(int T) { return T <= 4 ? 4 : T <= 8 ? 8 : T <= 16 ? 16 : 32; }
-
 template <int G, int TP> static auto divprob_kernel_of(int objective) {
     return objective == PTR_DIVPROB_ANDCG ? divprob_kernel<G, TP, PTR_DIVPROB_ANDCG>
          : objective == PTR_DIVPROB_ERRIA ? divprob_kernel<G, TP, PTR_DIVPROB_ERRIA>
          : objective == PTR_DIVPROB_PAIRCLS ? divprob_kernel<G, TP, PTR_DIVPROB_PAIRCLS>
                                             : divprob_kernel<G, TP, PTR_DIVPROB_LAMBDAPAIRCLS>;
-}
-template <int G> static auto divprob_kernel_of(int TP, int objective) {
-    return TP == 4 ? divprob_kernel_of<G, 4>(objective) : TP == 8 ? divprob_kernel_of<G, 8>(objective)
-         : TP == 16 ? divprob_kernel_of<G, 16>(objective) : divprob_kernel_of<G, 32>(objective);
 }
 
 }  // namespace ptr
@@ -371,20 +351,20 @@ extern "C" int ptr_divprob_fwd_bwd(const float *mus, const float *vars, const fl
     using namespace ptr;
     const char *who = "ptr_divprob_fwd_bwd";
     if (int rc = check_batch(mus, vars, B, L, who)) return rc;
-    if (B > 0 && !rele) { set_error("%s: NULL input pointer (rele)", who); return PTR_ERR_INVALID_ARG; }
-    if (T <= 0) { set_error("%s: bad number of subtopics T=%d", who, T); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_pointers(B, rele != nullptr, who, "NULL input pointer (rele)")) return rc;
+    if (int rc = check_subtopics_given(T, who)) return rc;
     if (objective < PTR_DIVPROB_ANDCG || objective > PTR_DIVPROB_LAMBDAPAIRCLS) {
         set_error("%s: objective must be one of PTR_DIVPROB_* (0 .. 3), got %d", who, objective);
         return PTR_ERR_INVALID_ARG;
     }
     if (!(beta > 0.0f && beta < 1.0f)) { set_error("%s: beta must be in (0, 1) (got %g)", who, (double)beta); return PTR_ERR_INVALID_ARG; }
-    if (top_k_axis != 0 && top_k_axis != 1) { set_error("%s: top_k_axis must be 0 (subtopics) or 1 (documents), got %d", who, top_k_axis); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_top_k_axis(top_k_axis, who)) return rc;
     if (objective == PTR_DIVPROB_ERRIA && !(max_label >= 0.0f)) {
         set_error("%s: ERR-IA needs max_label >= 0 (got %g)", who, (double)max_label);
         return PTR_ERR_INVALID_ARG;
     }
-    if (T > PTR_MAX_SUBTOPICS) { set_error("%s: %d subtopics exceed PTR_MAX_SUBTOPICS=%d", who, T, PTR_MAX_SUBTOPICS); return PTR_ERR_UNSUPPORTED; }
-    if (B > 0 && (!loss_q || !grad_mu || !grad_var)) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_subtopics_fit(T, who)) return rc;
+    if (int rc = check_pointers(B, loss_q && grad_mu && grad_var, who)) return rc;
     const int Lp = round_up(L, 4), TP = tp_of(T), K = divprob_tiles(objective);
     const size_t per_query = divprob_group_floats(Lp, TP, K) * sizeof(float);
     if (per_query > kLdsPerWorkgroup) {
@@ -398,27 +378,24 @@ extern "C" int ptr_divprob_fwd_bwd(const float *mus, const float *vars, const fl
     if (B > 0) {
         const double c = 1.0 - (double)beta;
         auto go = [&](auto kern) -> int {
-            if (int e = allow_lds(kern, lds)) return e;
-            hipLaunchKernelGGL(kern, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, as_stream(stream), mus, vars, rele, lens, ntopics, B, T, L, Lp,
-                               (float)log2(c), (float)log(c), top_k, top_k_axis, objective == PTR_DIVPROB_ERRIA ? exp2f(-max_label) : 0.0f,
-                               norm, loss_q, grad_mu, grad_var);
-            return check_hip(hipGetLastError(), who);
+            return launch_queries(kern, B, QPB, kBlock, lds, stream, who, mus, vars, rele, lens, ntopics, B, T, L, Lp, (float)log2(c), (float)log(c), top_k,
+                                  top_k_axis, objective == PTR_DIVPROB_ERRIA ? exp2f(-max_label) : 0.0f, norm, loss_q, grad_mu, grad_var);
         };
-        if (int rc = QPB > 1 ? go(divprob_kernel_of<64>(TP, objective)) : go(divprob_kernel_of<256>(TP, objective))) return rc;
+        if (int rc = dispatch_tp(T, [&]<int TP_>() {
+                return QPB > 1 ? go(divprob_kernel_of<64, TP_>(objective)) : go(divprob_kernel_of<256, TP_>(objective));
+            })) return rc;
     }
-    return loss_out ? ptr_sum_f32(loss_q, B, 1.0f, loss_out, stream) : 0;
+    return finish_loss(loss_q, B, 1.0f, loss_out, stream);
 }
 
 extern "C" int ptr_divprob_expected_ranks(const float *mus, const float *vars, const int32_t *lens, int B, int L, float *ranks, void *stream) {
     using namespace ptr;
     const char *who = "ptr_divprob_expected_ranks";
-    if (int rc = check_batch(mus, vars, B, L, who)) return rc;
-    if (B > 0 && !ranks) { set_error("%s: NULL output pointer (ranks)", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_loss_args(mus, vars, B, L, ranks != nullptr, who, "NULL output pointer (ranks)")) return rc;
     if (B == 0) return 0;
     const int Lp = round_up(L, 4);
     const int QPB = L <= 128 ? kBlock / kWave : 1;
     const size_t lds = (size_t)QPB * 3 * Lp * sizeof(float);          // <= 48 KiB at L = PTR_MAX_LIST_LEN
-    if (QPB > 1) hipLaunchKernelGGL(divprob_ranks_kernel<64>, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, as_stream(stream), mus, vars, lens, B, L, Lp, ranks);
-    else hipLaunchKernelGGL(divprob_ranks_kernel<256>, dim3(B), dim3(kBlock), lds, as_stream(stream), mus, vars, lens, B, L, Lp, ranks);
-    return check_hip(hipGetLastError(), who);
+    return QPB > 1 ? launch_queries(divprob_ranks_kernel<64>, B, QPB, kBlock, lds, stream, who, mus, vars, lens, B, L, Lp, ranks)
+                   : launch_queries(divprob_ranks_kernel<256>, B, 1, kBlock, lds, stream, who, mus, vars, lens, B, L, Lp, ranks);
 }

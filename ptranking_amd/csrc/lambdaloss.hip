@@ -437,8 +437,7 @@ extern "C" int ptr_lambdaloss_fwd_bwd(const float *preds, const float *labels, c
                                       float *grad, void *stream) {
     using namespace ptr;
     const char *who = "ptr_lambdaloss_fwd_bwd";
-    if (int rc = check_batch(preds, labels, B, L, who)) return rc;
-    if (B > 0 && (!loss_q || !grad)) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_loss_args(preds, labels, B, L, loss_q && grad, who)) return rc;
     if (loss_type != PTR_LAMBDALOSS_NDCG_LOSS1 && loss_type != PTR_LAMBDALOSS_NDCG_LOSS2 && loss_type != PTR_LAMBDALOSS_NDCG_LOSS2PP) {
         set_error("%s: loss_type %d not supported (0 = NDCG_Loss1, 1 = NDCG_Loss2, 2 = NDCG_Loss2++)", who, loss_type);
         return PTR_ERR_INVALID_ARG;
@@ -459,14 +458,11 @@ extern "C" int ptr_lambdaloss_fwd_bwd(const float *preds, const float *labels, c
         int rc = dispatch_wave256_tiling(L, [&]<int G, int DPT>() -> int {
             constexpr int QPB = kBlock / G, NW = G / kWave;
             const int Lp = G == kWave ? kWave * DPT : round_up(L, 4);
-            auto kern = lambdaloss_kernel<G, DPT>;
             const size_t lds = QPB * lambdaloss_group_floats(Lp, NW) * sizeof(float);
-            if (int e = allow_lds(kern, lds)) return e;
-            hipLaunchKernelGGL(kern, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, st, preds, labels, lens, B, L, Lp, k, sigma, mu,
-                               loss_type, presort, loss_q, grad);
-            return check_hip(hipGetLastError(), who);
+            return launch_queries(lambdaloss_kernel<G, DPT>, B, QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, Lp, k, sigma, mu, loss_type,
+                                  presort, loss_q, grad);
         });
         if (rc) return rc;
     }
-    return loss_out ? ptr_sum_f32(loss_q, B, 1.0f, loss_out, stream) : 0;
+    return finish_loss(loss_q, B, 1.0f, loss_out, stream);
 }

@@ -166,8 +166,7 @@ static int launch_listnet_vec(const float *preds, const float *labels, const int
     *served = true;
     auto go = [&]<int G, int V>() -> int {
         constexpr int QPB = (kBlock / kWave) * (kWave / G);
-        hipLaunchKernelGGL((listnet_vec_kernel<G, V>), dim3((B + QPB - 1) / QPB), dim3(kBlock), 0, st, preds, labels, lens, B, L, loss_q, grad);
-        return check_hip(hipGetLastError(), "ptr_listnet_fwd_bwd");
+        return launch_queries(listnet_vec_kernel<G, V>, B, QPB, kBlock, 0, st, "ptr_listnet_fwd_bwd", preds, labels, lens, B, L, loss_q, grad);
     };
     if (L <= 64) return go.template operator()<16, 1>();
     if (L <= 128) return go.template operator()<32, 1>();
@@ -345,8 +344,7 @@ static int launch_listmle_vec(const float *preds, const int64_t *perm, const int
     if ((reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(perm) | reinterpret_cast<uintptr_t>(grad)) & 15) return 0;
     *served = true;
     auto go = [&]<int V>() -> int {
-        hipLaunchKernelGGL((listmle_vec_kernel<V>), dim3((B + 3) / 4), dim3(kBlock), 0, st, preds, perm, lens, B, L, loss_q, grad);
-        return check_hip(hipGetLastError(), "ptr_listmle_fwd_bwd");
+        return launch_queries(listmle_vec_kernel<V>, B, 4, kBlock, 0, st, "ptr_listmle_fwd_bwd", preds, perm, lens, B, L, loss_q, grad);
     };
     if (L <= 256) return go.template operator()<1>();
     if (L <= 512) return go.template operator()<2>();
@@ -680,8 +678,7 @@ extern "C" int ptr_listnet_fwd_bwd(const float *preds, const float *labels, cons
                                    float *loss_q, float *grad, void *stream) {
     using namespace ptr;
     const char *who = "ptr_listnet_fwd_bwd";
-    if (int rc = check_batch(preds, labels, B, L, who)) return rc;
-    if (B > 0 && (!loss_q || !grad)) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_loss_args(preds, labels, B, L, loss_q && grad, who)) return rc;
     if (B > 0) {
         bool served = false;
         if (int rc = launch_listnet_vec(preds, labels, lens, B, L, loss_q, grad, as_stream(stream), &served)) return rc;
@@ -689,67 +686,56 @@ extern "C" int ptr_listnet_fwd_bwd(const float *preds, const float *labels, cons
             const int Lp = round_up(L, 4);
             const size_t per_q = 2 * (size_t)Lp * sizeof(float);
             const int wpb = waves_per_block(per_q);
-            if (int e = allow_lds(listnet_kernel, wpb * per_q)) return e;
-            hipLaunchKernelGGL(listnet_kernel, dim3((B + wpb - 1) / wpb), dim3(wpb * kWave), wpb * per_q, as_stream(stream), preds, labels,
-                               (const float *)nullptr, lens, B, L, Lp, 1.0f, loss_q, grad);
-            if (int rc = check_hip(hipGetLastError(), who)) return rc;
+            if (int rc = launch_queries(listnet_kernel, B, wpb, wpb * kWave, wpb * per_q, stream, who, preds, labels, (const float *)nullptr, lens, B, L,
+                                        Lp, 1.0f, loss_q, grad)) return rc;
         }
     }
-    return loss_out ? ptr_sum_f32(loss_q, B, 1.0f, loss_out, stream) : 0;
+    return finish_loss(loss_q, B, 1.0f, loss_out, stream);
 }
 
 extern "C" int ptr_stlistnet_fwd_bwd(const float *preds, const float *labels, const float *unif, const int32_t *lens, int B, int L,
                                      float temperature, float *loss_out, float *loss_q, float *grad, void *stream) {
     using namespace ptr;
     const char *who = "ptr_stlistnet_fwd_bwd";
-    if (int rc = check_batch(preds, labels, B, L, who)) return rc;
-    if (B > 0 && (!loss_q || !grad || !unif)) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_loss_args(preds, labels, B, L, loss_q && grad && unif, who, "NULL pointer")) return rc;
     if (!(temperature > 0.0f)) { set_error("%s: temperature must be > 0 (got %g)", who, (double)temperature); return PTR_ERR_INVALID_ARG; }
     if (B > 0) {
         const int Lp = round_up(L, 4);
         const size_t per_q = 2 * (size_t)Lp * sizeof(float);
         const int wpb = waves_per_block(per_q);
-        if (int e = allow_lds(listnet_kernel, wpb * per_q)) return e;
-        hipLaunchKernelGGL(listnet_kernel, dim3((B + wpb - 1) / wpb), dim3(wpb * kWave), wpb * per_q, as_stream(stream), preds, labels,
-                           unif, lens, B, L, Lp, 1.0f / temperature, loss_q, grad);
-        if (int rc = check_hip(hipGetLastError(), who)) return rc;
+        if (int rc = launch_queries(listnet_kernel, B, wpb, wpb * kWave, wpb * per_q, stream, who, preds, labels, unif, lens, B, L, Lp,
+                                    1.0f / temperature, loss_q, grad)) return rc;
     }
-    return loss_out ? ptr_sum_f32(loss_q, B, 1.0f, loss_out, stream) : 0;
+    return finish_loss(loss_q, B, 1.0f, loss_out, stream);
 }
 
 extern "C" int ptr_rankmse_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, float *loss_out,
                                    float *loss_q, float *grad, void *stream) {
     using namespace ptr;
     const char *who = "ptr_rankmse_fwd_bwd";
-    if (int rc = check_batch(preds, labels, B, L, who)) return rc;
-    if (B > 0 && (!loss_q || !grad)) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_loss_args(preds, labels, B, L, loss_q && grad, who)) return rc;
     if (B > 0) {
-        hipLaunchKernelGGL(rankmse_kernel, dim3((B + 3) / 4), dim3(kBlock), 0, as_stream(stream), preds, labels, lens, B, L, 1.0f / (float)B,
-                           loss_q, grad);
-        if (int rc = check_hip(hipGetLastError(), who)) return rc;
+        if (int rc = launch_queries(rankmse_kernel, B, 4, kBlock, 0, stream, who, preds, labels, lens, B, L, 1.0f / (float)B, loss_q, grad)) return rc;
     }
-    return loss_out ? ptr_sum_f32(loss_q, B, B > 0 ? 1.0f / (float)B : 0.0f, loss_out, stream) : 0;
+    return finish_loss(loss_q, B, B > 0 ? 1.0f / (float)B : 0.0f, loss_out, stream);
 }
 
 extern "C" int ptr_rankcosine_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, float *loss_out,
                                       float *loss_q, float *grad, void *stream) {
     using namespace ptr;
     const char *who = "ptr_rankcosine_fwd_bwd";
-    if (int rc = check_batch(preds, labels, B, L, who)) return rc;
-    if (B > 0 && (!loss_q || !grad)) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_loss_args(preds, labels, B, L, loss_q && grad, who)) return rc;
     if (B > 0) {
-        hipLaunchKernelGGL(rankcosine_kernel, dim3((B + 3) / 4), dim3(kBlock), 0, as_stream(stream), preds, labels, lens, B, L, loss_q, grad);
-        if (int rc = check_hip(hipGetLastError(), who)) return rc;
+        if (int rc = launch_queries(rankcosine_kernel, B, 4, kBlock, 0, stream, who, preds, labels, lens, B, L, loss_q, grad)) return rc;
     }
-    return loss_out ? ptr_sum_f32(loss_q, B, 1.0f, loss_out, stream) : 0;
+    return finish_loss(loss_q, B, 1.0f, loss_out, stream);
 }
 
 extern "C" int ptr_listmle_fwd_bwd(const float *preds, const int64_t *perm, const int32_t *lens, int B, int L, float *loss_out,
                                    float *loss_q, float *grad, void *stream) {
     using namespace ptr;
     const char *who = "ptr_listmle_fwd_bwd";
-    if (int rc = check_batch(preds, perm, B, L, who)) return rc;
-    if (B > 0 && (!loss_q || !grad)) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_loss_args(preds, perm, B, L, loss_q && grad, who)) return rc;
     if (B > 0) {
         bool served = false;
         if (int rc = launch_listmle_vec(preds, perm, lens, B, L, loss_q, grad, as_stream(stream), &served)) return rc;
@@ -757,32 +743,26 @@ extern "C" int ptr_listmle_fwd_bwd(const float *preds, const int64_t *perm, cons
             const int Lp = round_up(L, 4);
             const size_t per_q = 4 * (size_t)Lp * sizeof(float);
             const int wpb = waves_per_block(per_q);
-            if (int e = allow_lds(listmle_kernel, wpb * per_q)) return e;
-            hipLaunchKernelGGL(listmle_kernel, dim3((B + wpb - 1) / wpb), dim3(wpb * kWave), wpb * per_q, as_stream(stream), preds, perm,
-                               lens, B, L, Lp, loss_q, grad);
-            if (int rc = check_hip(hipGetLastError(), who)) return rc;
+            if (int rc = launch_queries(listmle_kernel, B, wpb, wpb * kWave, wpb * per_q, stream, who, preds, perm, lens, B, L, Lp, loss_q, grad)) return rc;
         }
     }
-    return loss_out ? ptr_sum_f32(loss_q, B, 1.0f, loss_out, stream) : 0;
+    return finish_loss(loss_q, B, 1.0f, loss_out, stream);
 }
 
 extern "C" int ptr_mdprank_fwd_bwd(const float *preds, const float *labels, const int64_t *perm, const int32_t *lens, int B, int L,
                                    int top_k, float gamma, float *loss_out, float *loss_q, float *grad, void *stream) {
     using namespace ptr;
     const char *who = "ptr_mdprank_fwd_bwd";
-    if (int rc = check_batch(preds, perm, B, L, who)) return rc;
-    if (B > 0 && (!labels || !loss_q || !grad)) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_loss_args(preds, perm, B, L, labels && loss_q && grad, who, "NULL pointer")) return rc;
     if (!(gamma > 0.0f)) { set_error("%s: gamma must be > 0 (got %g)", who, (double)gamma); return PTR_ERR_INVALID_ARG; }
     if (B > 0) {
         const int Lp = round_up(L, 4);
         const size_t per_q = 5 * (size_t)Lp * sizeof(float);
         const int wpb = waves_per_block(per_q);
-        if (int e = allow_lds(mdprank_kernel, wpb * per_q)) return e;
-        hipLaunchKernelGGL(mdprank_kernel, dim3((B + wpb - 1) / wpb), dim3(wpb * kWave), wpb * per_q, as_stream(stream), preds, labels,
-                           perm, lens, B, L, Lp, top_k, gamma, loss_q, grad);
-        if (int rc = check_hip(hipGetLastError(), who)) return rc;
+        if (int rc = launch_queries(mdprank_kernel, B, wpb, wpb * kWave, wpb * per_q, stream, who, preds, labels, perm, lens, B, L, Lp, top_k, gamma,
+                                    loss_q, grad)) return rc;
     }
-    return loss_out ? ptr_sum_f32(loss_q, B, 1.0f, loss_out, stream) : 0;
+    return finish_loss(loss_q, B, 1.0f, loss_out, stream);
 }
 
 extern "C" int ptr_shuffle_ties_order(const float *labels, const int32_t *lens, int B, int L, uint64_t seed, int64_t *perm,
@@ -794,11 +774,8 @@ extern "C" int ptr_shuffle_ties_order(const float *labels, const int32_t *lens, 
     return dispatch_wave_tiling(L, [&]<int G, int DPT>() -> int {
         constexpr int QPB = kBlock / G;
         const int Lp = G == kWave ? kWave * DPT : round_up(L, 4);      // one wavefront per query: 64*DPT padded keys through the register sort
-        auto kern = shuffle_ties_kernel<G, DPT>;
         const size_t lds = ((size_t)QPB * 3 * Lp + 4) * sizeof(float);
-        if (int e = allow_lds(kern, lds)) return e;
-        hipLaunchKernelGGL(kern, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, as_stream(stream), labels, lens, B, L, Lp, seed, perm,
-                           (int)(((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(perm)) & 15) == 0));
-        return check_hip(hipGetLastError(), who);
+        return launch_queries(shuffle_ties_kernel<G, DPT>, B, QPB, kBlock, lds, stream, who, labels, lens, B, L, Lp, seed, perm,
+                              (int)(((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(perm)) & 15) == 0));
     });
 }

@@ -367,18 +367,14 @@ metrics_kernel(const float *__restrict__ preds, const float *__restrict__ labels
 extern "C" int ptr_sort_desc(const float *preds, const int32_t *lens, int B, int L, float *vals, int64_t *idx, void *stream) {
     using namespace ptr;
     const char *who = "ptr_sort_desc";
-    if (int rc = check_batch(preds, vals, B, L, who)) return rc;
-    if (B > 0 && !idx) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_loss_args(preds, vals, B, L, idx != nullptr, who)) return rc;
     if (B == 0) return 0;
     return dispatch_wave_tiling(L, [&]<int G, int DPT>() -> int {
         constexpr int QPB = kBlock / G;
         const int Lp = G == kWave ? kWave * DPT : round_up(L, 4);      // one wavefront per query sorts 64*DPT padded keys
-        auto kern = sort_desc_kernel<G, DPT>;
         const size_t lds = (size_t)QPB * 3 * Lp * sizeof(float);
-        if (int e = allow_lds(kern, lds)) return e;
-        hipLaunchKernelGGL(kern, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, as_stream(stream), preds, lens, B, L, Lp, vals, idx,
-                           (int)(((reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(vals) | reinterpret_cast<uintptr_t>(idx)) & 15) == 0));
-        return check_hip(hipGetLastError(), who);
+        return launch_queries(sort_desc_kernel<G, DPT>, B, QPB, kBlock, lds, stream, who, preds, lens, B, L, Lp, vals, idx,
+                              (int)(((reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(vals) | reinterpret_cast<uintptr_t>(idx)) & 15) == 0));
     });
 }
 
@@ -425,10 +421,8 @@ extern "C" int ptr_metrics_at_ks(const float *preds, const float *labels, const 
         const int Lp = G == kWave ? kWave * DPT : round_up(L, 4);
         auto go = [&](auto kern) -> int {
             const size_t lds = (size_t)QPB * 3 * Lp * sizeof(float);
-            if (int e = allow_lds(kern, lds)) return e;
-            hipLaunchKernelGGL(kern, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, st, preds, labels, lens, B, L, Lp, ck, presort, label_type == PTR_LABEL_PERMUTATION ? 1 : 0, max_label,
-                               ml_dev, ndcg, nerr, ap, prec, (int)(((reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(labels)) & 15) == 0));
-            return check_hip(hipGetLastError(), who);
+            return launch_queries(kern, B, QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, Lp, ck, presort, label_type == PTR_LABEL_PERMUTATION ? 1 : 0,
+                                  max_label, ml_dev, ndcg, nerr, ap, prec, (int)(((reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(labels)) & 15) == 0));
         };
         // the Evaluator's calls: one metric (ndcg_at_k(s), nerr_at_k, ap_at_k, p_at_k) or all four (adhoc_performance_at_ks)
         switch (which) {

@@ -221,8 +221,7 @@ pairwise_bce_kernel(const float *__restrict__ preds, const float *__restrict__ l
 template <bool WEIGHTED>
 static int launch_pairwise(const float *preds, const float *labels, const int32_t *lens, int B, int L, float sigma,
                            float *loss_out, float *loss_q, float *grad, void *stream, const char *who) {
-    if (int rc = check_batch(preds, labels, B, L, who)) return rc;
-    if (B > 0 && (!loss_q || !grad)) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_loss_args(preds, labels, B, L, loss_q && grad, who)) return rc;
     if (WEIGHTED && !(sigma >= 0.0f)) { set_error("%s: sigma must be >= 0 (got %g)", who, (double)sigma); return PTR_ERR_INVALID_ARG; }
     hipStream_t st = as_stream(stream);
     if (WEIGHTED && B > 0 && L <= 512 && sigma > 0.0f && env_int("PTR_LAMBDARANK_RING", 1)) {     // 0: the LDS kernel (tests)
@@ -235,32 +234,25 @@ static int launch_pairwise(const float *preds, const float *labels, const int32_
             if (int e = launch_lambdarank_ring_small(dpt, QPB, preds, labels, lens, B, L, sigma, loss_q, grad, st)) return check_hip((hipError_t)e, who);
         } else {
             const size_t lds = (size_t)QPB * 2 * 64 * dpt * sizeof(float);
-            hipLaunchKernelGGL(lambdarank_ring_kernel<8>, dim3((B + QPB - 1) / QPB), dim3(QPB * kWave), lds, st, preds, labels, lens, B, L, sigma, loss_q, grad);
-            if (int rc = check_hip(hipGetLastError(), who)) return rc;
+            if (int rc = launch_queries(lambdarank_ring_kernel<8>, B, QPB, QPB * kWave, lds, stream, who, preds, labels, lens, B, L, sigma, loss_q, grad)) return rc;
         }
     } else if (!WEIGHTED && B > 0 && L <= 32) {
         if constexpr (!WEIGHTED) {               // RankNet on short lists: two queries per wavefront
             const int Lp = round_up(L, 4);
             constexpr int QPB = kBlock / 32;
-            auto kern = pairwise_bce_kernel<32, 1, false>;
             const size_t lds = QPB * pairwise_group_floats(Lp, 1) * sizeof(float);
-            hipLaunchKernelGGL(kern, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, st, preds, labels, lens, B, L, Lp, sigma, loss_q, grad);
-            if (int rc = check_hip(hipGetLastError(), who)) return rc;
+            if (int rc = launch_queries(pairwise_bce_kernel<32, 1, false>, B, QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, Lp, sigma, loss_q, grad)) return rc;
         }
     } else if (B > 0) {
         const int Lp = round_up(L, 4);
         int rc = dispatch_tiling(L, [&]<int G, int DPT>() -> int {
             constexpr int QPB = kBlock / G, NW = G / kWave;
-            auto kern = pairwise_bce_kernel<G, DPT, WEIGHTED>;
             const size_t lds = QPB * pairwise_group_floats(Lp, NW) * sizeof(float);
-            if (int e = allow_lds(kern, lds)) return e;
-            hipLaunchKernelGGL(kern, dim3((B + QPB - 1) / QPB), dim3(kBlock), lds, st, preds, labels, lens, B, L, Lp, sigma,
-                               loss_q, grad);
-            return check_hip(hipGetLastError(), who);
+            return launch_queries(pairwise_bce_kernel<G, DPT, WEIGHTED>, B, QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, Lp, sigma, loss_q, grad);
         });
         if (rc) return rc;
     }
-    return loss_out ? ptr_sum_f32(loss_q, B, 1.0f, loss_out, stream) : 0;
+    return finish_loss(loss_q, B, 1.0f, loss_out, stream);
 }
 
 }  // namespace ptr

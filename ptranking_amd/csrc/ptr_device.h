@@ -118,6 +118,33 @@ template <class K> inline int allow_lds(K kernel, size_t bytes) {
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes), "hipFuncSetAttribute");
 }
 
+// ---- the three steps every ptr_*_fwd_bwd entry point shares
+// Pointers that a launch reads or writes are only required when there is a query to launch for.
+inline int check_pointers(int B, bool all_given, const char *who, const char *what = "NULL output pointer") {
+    if (B > 0 && !all_given) { set_error("%s: %s", who, what); return PTR_ERR_INVALID_ARG; }
+    return 0;
+}
+
+// Argument prologue: the batch shape (check_batch), then the outputs.
+inline int check_loss_args(const void *preds, const void *second, int B, int L, bool outputs_given, const char *who,
+                           const char *what = "NULL output pointer") {
+    if (int rc = check_batch(preds, second, B, L, who)) return rc;
+    return check_pointers(B, outputs_given, who, what);
+}
+
+// One launch over the batch, `QPB` queries per workgroup of `block` threads with `lds` bytes of dynamic LDS (the cap is raised when needed).
+template <class K, class... Args>
+inline int launch_queries(K kernel, int B, int QPB, int block, size_t lds, void *stream, const char *who, Args... args) {
+    if (int e = allow_lds(kernel, lds)) return e;
+    hipLaunchKernelGGL(kernel, dim3((B + QPB - 1) / QPB), dim3(block), lds, as_stream(stream), args...);
+    return check_hip(hipGetLastError(), who);
+}
+
+// Epilogue: loss_out = scale * sum of the per-query loss slots, when the caller asks for it.
+inline int finish_loss(const float *loss_q, int B, float scale, float *loss_out, void *stream) {
+    return loss_out ? ptr_sum_f32(loss_q, B, scale, loss_out, stream) : 0;
+}
+
 // ---------------------------------------------------------------- device side
 #if defined(__HIPCC__)
 

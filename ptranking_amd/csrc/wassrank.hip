@@ -237,8 +237,7 @@ extern "C" int ptr_wassrank_fwd_bwd(const float *preds, const float *labels, con
                                     int scale_by_max_label, float *loss_out, float *loss_q, float *grad, void *stream) {
     using namespace ptr;
     const char *who = "ptr_wassrank_fwd_bwd";
-    if (int rc = check_batch(preds, labels, B, L, who)) return rc;
-    if (B > 0 && (!loss_q || !grad)) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_loss_args(preds, labels, B, L, loss_q && grad, who)) return rc;
     if (cost_type < PTR_WASS_COST_P1 || cost_type > PTR_WASS_COST_DDG) {
         set_error("%s: unknown cost_type %d (PTR_WASS_COST_*)", who, cost_type);
         return PTR_ERR_INVALID_ARG;
@@ -250,10 +249,8 @@ extern "C" int ptr_wassrank_fwd_bwd(const float *preds, const float *labels, con
         const size_t lds = (6 * (size_t)Lp + 8) * sizeof(float);
         const float inv_b = 1.0f / (float)B;
         auto launch = [&]<int G>(auto kern) -> int {
-            if (int e = allow_lds(kern, lds)) return e;
-            hipLaunchKernelGGL(kern, dim3(B), dim3(G), lds, as_stream(stream), preds, labels, lens, L, Lp, gain_base, non_rele_gap,
-                               var_penalty, lam, sh_itr, scale_by_max_label, inv_b, loss_q, grad);
-            return check_hip(hipGetLastError(), who);
+            return launch_queries(kern, B, 1, G, lds, stream, who, preds, labels, lens, L, Lp, gain_base, non_rele_gap, var_penalty, lam, sh_itr,
+                                  scale_by_max_label, inv_b, loss_q, grad);
         };
         int rc;
         if (L <= 64) rc = dispatch_cost<64, 1>(cost_type, [&](auto k) { return launch.template operator()<64>(k); });
@@ -262,5 +259,5 @@ extern "C" int ptr_wassrank_fwd_bwd(const float *preds, const float *labels, con
         else rc = dispatch_cost<256, 2>(cost_type, [&](auto k) { return launch.template operator()<256>(k); });
         if (rc) return rc;
     }
-    return loss_out ? ptr_sum_f32(loss_q, B, B > 0 ? 1.0f / (float)B : 0.0f, loss_out, stream) : 0;
+    return finish_loss(loss_q, B, B > 0 ? 1.0f / (float)B : 0.0f, loss_out, stream);
 }

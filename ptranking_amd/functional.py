@@ -35,34 +35,45 @@ def _check(name, t, dtype=torch.float32, shape=None):
     return t.contiguous()
 
 
-def _batch(preds, second, lens, second_dtype=torch.float32, second_name="labels"):
-    preds = _check("preds", preds)
-    if preds.dim() != 2:
-        raise ValueError(f"preds must be [batch, ranking_size], got {tuple(preds.shape)}")
-    B, L = preds.shape
+def _matrix(name, t):
+    """The [B, L] check the batch checkers share: a float32 CUDA matrix -> (contiguous tensor, B, L)."""
+    t = _check(name, t)
+    if t.dim() != 2:
+        raise ValueError(f"{name} must be [batch, ranking_size], got {tuple(t.shape)}")
+    return (t, *t.shape)
+
+
+def _list_len(L):
     if L > _lib.MAX_LIST_LEN:
         raise ValueError(f"ranking_size {L} exceeds the supported maximum {_lib.MAX_LIST_LEN}")
+
+
+def _counts(name, t, B):
+    """An optional int32 [B] tensor (lens, ntopics)."""
+    return None if t is None else _check(name, t, torch.int32, (B,))
+
+
+def _batch(preds, second, lens, second_dtype=torch.float32, second_name="labels"):
+    preds, B, L = _matrix("preds", preds)
+    _list_len(L)
     second = _check(second_name, second, second_dtype, (B, L))
     if second.device != preds.device:
         raise RuntimeError("preds and labels live on different devices")
-    if lens is not None:
-        lens = _check("lens", lens, torch.int32, (B,))
-    return preds, second, lens, B, L
+    return preds, second, _counts("lens", lens, B), B, L
 
 
 class _FusedLoss(torch.autograd.Function):
-    """forward(preds, launch) where launch(preds) -> (loss 0-d tensor, grad [B,L]); backward scales grad."""
+    """forward(launch, *inputs) where launch(*inputs) -> (loss 0-d tensor, one grad [B,L] per input); backward scales the grads."""
 
     @staticmethod
-    def forward(ctx, preds, launch):
-        loss, grad = launch(preds)
-        ctx.save_for_backward(grad)
+    def forward(ctx, launch, *inputs):
+        loss, *grads = launch(*(x.detach() for x in inputs))
+        ctx.save_for_backward(*grads)
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
-        (grad,) = ctx.saved_tensors
-        return grad * grad_out, None
+        return (None, *(g * grad_out for g in ctx.saved_tensors))
 
 
 def _reduce(loss_q, B, dev):
@@ -71,33 +82,53 @@ def _reduce(loss_q, B, dev):
     return out.reshape(())
 
 
-def _simple(entry, preds, labels, lens, *params):
-    """Shared driver of the (preds, labels, lens, B, L, <params>, loss_out, loss_q, grad, stream) entry points: one launch
-    of the fused loss+gradient kernel, then the deterministic reduction of the per-query loss slots."""
-    preds_c, labels, lens, B, L = _batch(preds.detach(), labels, lens)
-    dev = preds_c.device
+def _fused(entry, inputs, checked, args, own_loss=False, slots=(("loss_q", None),)):
+    """The one launch path of the fused losses -> (loss, {slot name: tensor}).  The entry point takes (*inputs, *args, loss_out, *slots,
+    one gradient per input, stream): `inputs` are the differentiable [B, L] tensors as the caller passed them and `checked` their detached,
+    validated, contiguous forms; `args` the remaining pointer (tensor or None) and scalar arguments in ABI order; `slots` the per-query
+    outputs as (name, size), size None meaning [B].  own_loss: the entry point writes loss_out itself; otherwise loss_out is NULL and the
+    first slot is summed by the deterministic reduction."""
+    B, L = checked[0].shape
+    dev = checked[0].device
+    parts = {}
 
-    def launch(p):
-        loss_q = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
-        grad = torch.empty((B, L), device=dev, dtype=torch.float32)
+    def launch(*xs):
+        new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+        outs = [new(max(B, 1) if n is None else n) for _, n in slots]
+        grads = [new(B, L) for _ in xs]
+        out = new(1) if own_loss else None
         with torch.cuda.device(dev):
-            _lib.call(entry, _lib.ptr(p), _lib.ptr(labels), _lib.ptr(lens), B, L, *params, None, _lib.ptr(loss_q),
-                      _lib.ptr(grad), _lib.current_stream(dev))
-            return _reduce(loss_q, B, dev), grad
+            _lib.call(entry, *map(_lib.ptr, xs), *(_lib.ptr(a) if isinstance(a, torch.Tensor) else a for a in args), _lib.ptr(out),
+                      *map(_lib.ptr, outs), *map(_lib.ptr, grads), _lib.current_stream(dev))
+            loss = out.reshape(()) if own_loss else _reduce(outs[0], B, dev)
+        parts.update((name, t[:B] if n is None else t) for (name, n), t in zip(slots, outs))
+        return (loss, *grads)
 
-    if preds.requires_grad:
-        return _FusedLoss.apply(preds if preds.is_contiguous() else preds.contiguous(), lambda p: launch(p.detach()))
-    return launch(preds_c)[0]
+    if any(x.requires_grad for x in inputs):
+        return _FusedLoss.apply(launch, *(x.contiguous() for x in inputs)), parts
+    return launch(*checked)[0], parts
+
+
+def _simple(entry, preds, labels, lens, *params, own_loss=False):
+    """The (preds, labels, lens, B, L, <params>, loss_out, loss_q, grad, stream) entry points."""
+    preds_c, labels, lens, B, L = _batch(preds.detach(), labels, lens)
+    return _fused(entry, [preds], [preds_c], [labels, lens, B, L, *params], own_loss)[0]
+
+
+def _table_loss(name, preds, labels, lens, **values):
+    """A loss of _lib.LOSSES (the ones ptr_train_step also serves): its C arguments come from the table."""
+    loss = _lib.LOSSES[name]
+    return _simple(loss.entry, preds, labels, lens, *loss.c_args(**values))
 
 
 def ranknet_loss(preds, labels, sigma=1.0, lens=None):
     """RankNet, ptranking/ltr_adhoc/pairwise/ranknet.py:32-36."""
-    return _simple("ptr_ranknet_fwd_bwd", preds, labels, lens, C.c_float(float(sigma)))
+    return _table_loss("ranknet", preds, labels, lens, sigma=sigma)
 
 
 def lambdarank_loss(preds, labels, sigma=1.0, lens=None):
     """LambdaRank, ptranking/ltr_adhoc/listwise/lambdarank.py:39-56.  `labels` in ideal (descending) order per query."""
-    return _simple("ptr_lambdarank_fwd_bwd", preds, labels, lens, C.c_float(float(sigma)))
+    return _table_loss("lambdarank", preds, labels, lens, sigma=sigma)
 
 
 def lambdaloss_loss(preds, labels, k=5, sigma=1.0, mu=5.0, loss_type="NDCG_Loss2", presort=True, lens=None):
@@ -106,8 +137,7 @@ def lambdaloss_loss(preds, labels, k=5, sigma=1.0, mu=5.0, loss_type="NDCG_Loss2
     of a batch uses its own weights (identical to the reference at B = 1)."""
     if loss_type not in LAMBDALOSS_TYPES:
         raise NotImplementedError(f"LambdaLoss type {loss_type!r} (supported: {sorted(LAMBDALOSS_TYPES)})")
-    return _simple("ptr_lambdaloss_fwd_bwd", preds, labels, lens, int(k), C.c_float(float(sigma)), C.c_float(float(mu)),
-                   LAMBDALOSS_TYPES[loss_type], int(bool(presort)))
+    return _table_loss("lambdaloss", preds, labels, lens, k=k, sigma=sigma, mu=mu, loss_type=LAMBDALOSS_TYPES[loss_type], presort=bool(presort))
 
 
 def softrank_loss(preds, labels, delta=2.0, top_k=None, lens=None):
@@ -117,26 +147,12 @@ def softrank_loss(preds, labels, delta=2.0, top_k=None, lens=None):
 
 def listnet_loss(preds, labels, lens=None):
     """ListNet, ptranking/ltr_adhoc/listwise/listnet.py:39."""
-    return _simple("ptr_listnet_fwd_bwd", preds, labels, lens)
+    return _table_loss("listnet", preds, labels, lens)
 
 
 def rankmse_loss(preds, labels, lens=None):
     """RankMSE, ptranking/ltr_adhoc/pointwise/rank_mse.py:13-22 (mean over queries of the per-query squared error sums)."""
-    preds_c, labels, lens, B, L = _batch(preds.detach(), labels, lens)
-    dev = preds_c.device
-
-    def launch(p):
-        loss_q = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
-        grad = torch.empty((B, L), device=dev, dtype=torch.float32)
-        out = torch.empty(1, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.call("ptr_rankmse_fwd_bwd", _lib.ptr(p), _lib.ptr(labels), _lib.ptr(lens), B, L, _lib.ptr(out), _lib.ptr(loss_q),
-                      _lib.ptr(grad), _lib.current_stream(dev))
-        return out.reshape(()), grad
-
-    if preds.requires_grad:
-        return _FusedLoss.apply(preds if preds.is_contiguous() else preds.contiguous(), lambda p: launch(p.detach()))
-    return launch(preds_c)[0]
+    return _simple("ptr_rankmse_fwd_bwd", preds, labels, lens, own_loss=True)
 
 
 def wassrank_loss(preds, labels, cost_type="eg", lam=0.1, sh_itr=20, gain_base=4.0, non_rele_gap=100.0, var_penalty=math.e,
@@ -148,23 +164,9 @@ def wassrank_loss(preds, labels, cost_type="eg", lam=0.1, sh_itr=20, gain_base=4
     every log-sum-exp takes its own row's maximum, so the loss stays finite where the reference's fp32 evaluation turns NaN."""
     if cost_type not in WASS_COST_TYPES:
         raise NotImplementedError(f"WassRank cost_type {cost_type!r} (supported: {sorted(WASS_COST_TYPES)})")
-    preds_c, labels, lens, B, L = _batch(preds.detach(), labels, lens)
-    dev = preds_c.device
-    params = (WASS_COST_TYPES[cost_type], C.c_float(float(gain_base)), C.c_float(float(non_rele_gap)), C.c_float(float(var_penalty)),
-              C.c_float(float(lam)), int(sh_itr), int(bool(scale_by_max_label)))
-
-    def launch(p):
-        loss_q = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
-        grad = torch.empty((B, L), device=dev, dtype=torch.float32)
-        out = torch.empty(1, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.call("ptr_wassrank_fwd_bwd", _lib.ptr(p), _lib.ptr(labels), _lib.ptr(lens), B, L, *params, _lib.ptr(out), _lib.ptr(loss_q),
-                      _lib.ptr(grad), _lib.current_stream(dev))
-        return out.reshape(()), grad
-
-    if preds.requires_grad:
-        return _FusedLoss.apply(preds if preds.is_contiguous() else preds.contiguous(), lambda p: launch(p.detach()))
-    return launch(preds_c)[0]
+    return _simple("ptr_wassrank_fwd_bwd", preds, labels, lens, WASS_COST_TYPES[cost_type], C.c_float(float(gain_base)),
+                   C.c_float(float(non_rele_gap)), C.c_float(float(var_penalty)), C.c_float(float(lam)), int(sh_itr),
+                   int(bool(scale_by_max_label)), own_loss=True)
 
 
 def rankcosine_loss(preds, labels, lens=None):
@@ -176,61 +178,24 @@ def stlistnet_loss(preds, labels, temperature=1.0, unif=None, lens=None):
     """STListNet, ptranking/ltr_adhoc/listwise/st_listnet.py:41-49.  `unif` = the uniform draws the Gumbel noise is made of
     (default: torch.rand on the device, as the reference does)."""
     preds_c, labels, lens, B, L = _batch(preds.detach(), labels, lens)
-    dev = preds_c.device
     if unif is None:
-        unif = torch.rand((B, L), device=dev)
+        unif = torch.rand((B, L), device=preds_c.device)
     unif = _check("unif", unif, torch.float32, (B, L))
-
-    def launch(p):
-        loss_q = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
-        grad = torch.empty((B, L), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.call("ptr_stlistnet_fwd_bwd", _lib.ptr(p), _lib.ptr(labels), _lib.ptr(unif), _lib.ptr(lens), B, L,
-                      C.c_float(float(temperature)), None, _lib.ptr(loss_q), _lib.ptr(grad), _lib.current_stream(dev))
-            return _reduce(loss_q, B, dev), grad
-
-    if preds.requires_grad:
-        return _FusedLoss.apply(preds if preds.is_contiguous() else preds.contiguous(), lambda p: launch(p.detach()))
-    return launch(preds_c)[0]
+    return _fused("ptr_stlistnet_fwd_bwd", [preds], [preds_c], [labels, unif, lens, B, L, C.c_float(float(temperature))])[0]
 
 
 def listmle_loss(preds, perm, lens=None):
     """ListMLE, ptranking/ltr_adhoc/listwise/listmle.py:82,92-97; `perm` int64 [B,L] from arg_shuffle_ties / shuffle_ties_order."""
     preds_c, perm, lens, B, L = _batch(preds.detach(), perm, lens, torch.int64, "perm")
-    dev = preds_c.device
-
-    def launch(p):
-        loss_q = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
-        grad = torch.empty((B, L), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.call("ptr_listmle_fwd_bwd", _lib.ptr(p), _lib.ptr(perm), _lib.ptr(lens), B, L, None, _lib.ptr(loss_q),
-                      _lib.ptr(grad), _lib.current_stream(dev))
-            return _reduce(loss_q, B, dev), grad
-
-    if preds.requires_grad:
-        return _FusedLoss.apply(preds if preds.is_contiguous() else preds.contiguous(), lambda p: launch(p.detach()))
-    return launch(preds_c)[0]
+    return _fused("ptr_listmle_fwd_bwd", [preds], [preds_c], [perm, lens, B, L])[0]
 
 
 def mdprank_loss(preds, labels, perm, top_k=10, gamma=1.0, lens=None):
     """MDPRank, ptranking/ltr_adhoc/listwise/mdprank.py:46-75: return-weighted ListMLE on the sampled ranking `perm` (int64 [B,L]).
     `preds` are the action scores by ORIGINAL document index (for 'STPL' the caller passes (preds + gumbel) / temperature)."""
     preds_c, perm, lens, B, L = _batch(preds.detach(), perm, lens, torch.int64, "perm")
-    labels = _check("labels", labels, shape=(B, L)).contiguous()
-    dev = preds_c.device
-
-    def launch(p):
-        loss_q = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
-        grad = torch.empty((B, L), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.call("ptr_mdprank_fwd_bwd", _lib.ptr(p), _lib.ptr(labels), _lib.ptr(perm), _lib.ptr(lens), B, L,
-                      int(top_k) if top_k else 0, C.c_float(float(gamma)), None, _lib.ptr(loss_q), _lib.ptr(grad),
-                      _lib.current_stream(dev))
-            return _reduce(loss_q, B, dev), grad
-
-    if preds.requires_grad:
-        return _FusedLoss.apply(preds if preds.is_contiguous() else preds.contiguous(), lambda p: launch(p.detach()))
-    return launch(preds_c)[0]
+    labels = _check("labels", labels, shape=(B, L))
+    return _fused("ptr_mdprank_fwd_bwd", [preds], [preds_c], [labels, perm, lens, B, L, int(top_k) if top_k else 0, C.c_float(float(gamma))])[0]
 
 
 def approxndcg_loss(preds, labels, alpha=10.0, presort=True, couple_batch=True, lens=None, grad_scale_override=0.0,
@@ -238,37 +203,16 @@ def approxndcg_loss(preds, labels, alpha=10.0, presort=True, couple_batch=True, 
     """ApproxNDCG, ptranking/ltr_adhoc/listwise/approxNDCG.py:45-62.  couple_batch=True reproduces the reference's batch
     coupling (loss = -(sum DCG_b)(sum 1/IDCG_a)).  With return_parts also returns (dcg_q [B], inv_idcg_q [B], scale [2])."""
     preds_c, labels, lens, B, L = _batch(preds.detach(), labels, lens)
-    dev = preds_c.device
-    parts = {}
-
-    def launch(p):
-        out = torch.empty(1, device=dev, dtype=torch.float32)
-        dcg = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
-        inv = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
-        scale = torch.empty(2, device=dev, dtype=torch.float32)
-        grad = torch.empty((B, L), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.call("ptr_approxndcg_fwd_bwd", _lib.ptr(p), _lib.ptr(labels), _lib.ptr(lens), B, L, C.c_float(float(alpha)),
-                      int(bool(presort)), int(bool(couple_batch)), C.c_float(float(grad_scale_override)), _lib.ptr(out),
-                      _lib.ptr(dcg), _lib.ptr(inv), _lib.ptr(scale), _lib.ptr(grad), _lib.current_stream(dev))
-        parts.update(dcg_q=dcg[:B], inv_idcg_q=inv[:B], scale=scale)
-        return out.reshape(()), grad
-
-    if preds.requires_grad:
-        loss = _FusedLoss.apply(preds if preds.is_contiguous() else preds.contiguous(), lambda p: launch(p.detach()))
-    else:
-        loss = launch(preds_c)[0]
+    loss, parts = _fused("ptr_approxndcg_fwd_bwd", [preds], [preds_c],
+                         [labels, lens, B, L, C.c_float(float(alpha)), int(bool(presort)), int(bool(couple_batch)), C.c_float(float(grad_scale_override))],
+                         own_loss=True, slots=(("dcg_q", None), ("inv_idcg_q", None), ("scale", 2)))
     return (loss, parts) if return_parts else loss
 
 
 def _div_batch(preds, rele, lens, ntopics):
     """preds [B, L], rele [B, T, L], lens / ntopics int32 [B] or None — checked, contiguous."""
-    preds = _check("preds", preds)
-    if preds.dim() != 2:
-        raise ValueError(f"preds must be [batch, ranking_size], got {tuple(preds.shape)}")
-    B, L = preds.shape
-    if L > _lib.MAX_LIST_LEN:
-        raise ValueError(f"ranking_size {L} exceeds the supported maximum {_lib.MAX_LIST_LEN}")
+    preds, B, L = _matrix("preds", preds)
+    _list_len(L)
     rele = _check("rele", rele)
     if rele.dim() != 3 or rele.shape[0] != B or rele.shape[2] != L:
         raise ValueError(f"rele must be [batch, num_subtopics, ranking_size] = [{B}, T, {L}], got {tuple(rele.shape)}")
@@ -277,11 +221,7 @@ def _div_batch(preds, rele, lens, ntopics):
         raise ValueError(f"{T} subtopics: between 1 and {_lib.MAX_SUBTOPICS} are supported")
     if rele.device != preds.device:
         raise RuntimeError("preds and rele live on different devices")
-    if lens is not None:
-        lens = _check("lens", lens, torch.int32, (B,))
-    if ntopics is not None:
-        ntopics = _check("ntopics", ntopics, torch.int32, (B,))
-    return preds, rele, lens, ntopics, B, T, L
+    return preds, rele, _counts("lens", lens, B), _counts("ntopics", ntopics, B), B, T, L
 
 
 def alphadcg_loss(preds, rele, rt=10.0, alpha=0.5, top_k=10, top_k_axis="reference", lens=None, ntopics=None, return_loss_q=False):
@@ -292,23 +232,8 @@ def alphadcg_loss(preds, rele, rt=10.0, alpha=0.5, top_k=10, top_k_axis="referen
     if top_k_axis not in ADCG_TOPK_AXES:
         raise ValueError(f"top_k_axis {top_k_axis!r} (supported: 'reference', 'documents')")
     preds_c, rele, lens, ntopics, B, T, L = _div_batch(preds.detach(), rele, lens, ntopics)
-    dev = preds_c.device
-    parts = {}
-
-    def launch(p):
-        loss_q = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
-        grad = torch.empty((B, L), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.call("ptr_alphadcg_fwd_bwd", _lib.ptr(p), _lib.ptr(rele), _lib.ptr(lens), _lib.ptr(ntopics), B, T, L, C.c_float(float(rt)),
-                      C.c_float(float(alpha)), int(top_k) if top_k else 0, ADCG_TOPK_AXES[top_k_axis], None, _lib.ptr(loss_q), _lib.ptr(grad),
-                      _lib.current_stream(dev))
-            parts["loss_q"] = loss_q[:B]
-            return _reduce(loss_q, B, dev), grad
-
-    if preds.requires_grad:
-        loss = _FusedLoss.apply(preds if preds.is_contiguous() else preds.contiguous(), lambda p: launch(p.detach()))
-    else:
-        loss = launch(preds_c)[0]
+    loss, parts = _fused("ptr_alphadcg_fwd_bwd", [preds], [preds_c], [rele, lens, ntopics, B, T, L, C.c_float(float(rt)), C.c_float(float(alpha)),
+                                                                     int(top_k) if top_k else 0, ADCG_TOPK_AXES[top_k_axis]])
     return (loss, parts["loss_q"]) if return_loss_q else loss
 
 
@@ -334,34 +259,13 @@ def div_metrics_at_ks(preds, rele, ks, alpha=0.5, max_label=None, lens=None, nto
     return andcg, err, nerr, valid
 
 
-class _FusedLoss2(torch.autograd.Function):
-    """forward(mus, vars, launch) where launch(mus, vars) -> (loss 0-d tensor, grad_mu [B,L], grad_var [B,L]); backward scales both."""
-
-    @staticmethod
-    def forward(ctx, mus, vars, launch):
-        loss, grad_mu, grad_var = launch(mus, vars)
-        ctx.save_for_backward(grad_mu, grad_var)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        grad_mu, grad_var = ctx.saved_tensors
-        return grad_mu * grad_out, grad_var * grad_out, None
-
-
 def _divprob_scores(mus, vars, lens):
-    mus = _check("mus", mus)
-    if mus.dim() != 2:
-        raise ValueError(f"mus must be [batch, ranking_size], got {tuple(mus.shape)}")
-    B, L = mus.shape
+    mus, B, L = _matrix("mus", mus)
     vars = _check("vars", vars, shape=(B, L))
     if vars.device != mus.device:
         raise RuntimeError("mus and vars live on different devices")
-    if L > _lib.MAX_LIST_LEN:
-        raise ValueError(f"ranking_size {L} exceeds the supported maximum {_lib.MAX_LIST_LEN}")
-    if lens is not None:
-        lens = _check("lens", lens, torch.int32, (B,))
-    return mus, vars, lens, B, L
+    _list_len(L)
+    return mus, vars, _counts("lens", lens, B), B, L
 
 
 def divprob_loss(mus, vars, rele, objective, beta=0.5, top_k=None, top_k_axis="reference", max_label=1.0, norm=True, lens=None, ntopics=None,
@@ -380,25 +284,9 @@ def divprob_loss(mus, vars, rele, objective, beta=0.5, top_k=None, top_k_axis="r
     vars_c = _check("vars", vars.detach(), shape=(B, L))
     if vars_c.device != mus_c.device:
         raise RuntimeError("mus and vars live on different devices")
-    dev = mus_c.device
-    parts = {}
-
-    def launch(m, v):
-        loss_q = torch.empty(max(B, 1), device=dev, dtype=torch.float32)
-        grad_mu = torch.empty((B, L), device=dev, dtype=torch.float32)
-        grad_var = torch.empty((B, L), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.call("ptr_divprob_fwd_bwd", _lib.ptr(m), _lib.ptr(v), _lib.ptr(rele), _lib.ptr(lens), _lib.ptr(ntopics), B, T, L,
-                      DIVPROB_OBJECTIVES[objective], C.c_float(float(beta)), int(top_k) if top_k else 0, ADCG_TOPK_AXES[top_k_axis],
-                      C.c_float(float(max_label)), int(bool(norm)), None, _lib.ptr(loss_q), _lib.ptr(grad_mu), _lib.ptr(grad_var),
-                      _lib.current_stream(dev))
-            parts["loss_q"] = loss_q[:B]
-            return _reduce(loss_q, B, dev), grad_mu, grad_var
-
-    if mus.requires_grad or vars.requires_grad:
-        loss = _FusedLoss2.apply(mus.contiguous(), vars.contiguous(), lambda m, v: launch(m.detach(), v.detach()))
-    else:
-        loss = launch(mus_c, vars_c)[0]
+    loss, parts = _fused("ptr_divprob_fwd_bwd", [mus, vars], [mus_c, vars_c],
+                         [rele, lens, ntopics, B, T, L, DIVPROB_OBJECTIVES[objective], C.c_float(float(beta)), int(top_k) if top_k else 0,
+                          ADCG_TOPK_AXES[top_k_axis], C.c_float(float(max_label)), int(bool(norm))])
     return (loss, parts["loss_q"]) if return_loss_q else loss
 
 

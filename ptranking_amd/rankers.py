@@ -66,14 +66,18 @@ class FusedStepMixin:
     fuse_optimizer_step = True    # direct step on one device: optimiser step + loss-slot sum inside ptr_mlp_backward_step
     single_call_step = True       # r6: ... and the whole step as ONE C-ABI call (ptr_train_step: the same three entry points chained in C)
     reuse_weight_image = True     # r6: ... whose optimiser launch refreshes the bf16x6 forward's weight image, so the next step skips the prep launch
-    _direct_entry = None          # (C-ABI entry point, lambda self, kwargs: [loss parameters]) — set by the loss mixins that qualify
+    _direct_loss = None           # the _lib.LOSSES entry of the loss — set by the loss mixins that qualify
     _direct_owner = None          # the class whose custom_loss_function the entry point implements
 
     def _direct_check(self, kwargs):
         """The reference's asserts of the loss (run on the direct path too)."""
 
+    def _loss_values(self, kwargs):
+        """The parameters of _direct_loss by name, as plain Python values."""
+        return {}
+
     def _direct_train_op(self, X, Y, kwargs):
-        spec = self._direct_entry
+        spec = self._direct_loss
         sf = getattr(self, "point_sf", None)
         if (spec is None or not self.use_direct_step or not isinstance(sf, FusedPointScorer) or not isinstance(self.optimizer, FlatAdam)
                 or type(self).custom_loss_function is not self._direct_owner.custom_loss_function or not sf.training
@@ -111,7 +115,7 @@ class FusedStepMixin:
             seed = dp.local_dropout_seed(seed, R, local_queries=B)
         dp.end_step()                            # the recorded query slice described this batch only — with or without dropout (as _fused_step does)
         loss = torch.empty(1, device=dev)
-        entry, params = spec
+        values = self._loss_values(kwargs)
         distributed = self.data_parallel and dp.is_distributed()
         # single device: the optimiser step and the loss-slot sum ride in the backward's partial reduction (three launches fewer per step,
         # bit-identical results); under data parallelism the all-reduce sits between the gradient and the step
@@ -119,7 +123,7 @@ class FusedStepMixin:
         if fuse_step and self.single_call_step:
             # r6: forward -> loss -> backward + step enqueued by ONE foreign call (ptr_train_step chains the very entry points used below:
             # bit-identical parameters); bench.py's per-stage timings (_lib.TIMING) come from events the call records between its stages
-            return self._single_call_step(X, Y, lens, buf, flat, B, L, Fd, NL, R, p, seed, spec, kwargs, loss, dev)
+            return self._single_call_step(X, Y, lens, buf, flat, B, L, Fd, NL, R, p, seed, spec, values, kwargs, loss, dev)
         with torch.cuda.device(dev):
             st = _lib.current_stream(dev)
             mlp_forward(X, flat, R, Fd, NL, 1, p, seed, buf["preds"], buf["acts"], dev)
@@ -129,7 +133,7 @@ class FusedStepMixin:
             # data parallel with a flat optimiser: backward -> flat gradient -> all-reduce -> ONE launch (optimiser step + loss-slot sum,
             # ptr_opt_step_loss): the single-device launch sequence + one kernel + one collective, nothing returns to autograd in between
             dp_fused = distributed and self.fuse_optimizer_step and type(self.optimizer) in (FlatAdam, FlatAdagrad, FlatRMSprop)
-            _lib.call(entry, _lib.ptr(buf["preds"]), _lib.ptr(Y), _lib.ptr(lens), B, L, *params(self, kwargs),
+            _lib.call(spec.entry, _lib.ptr(buf["preds"]), _lib.ptr(Y), _lib.ptr(lens), B, L, *spec.c_args(**values),
                       None if (fuse_step or dp_fused) else _lib.ptr(loss), _lib.ptr(buf["loss_q"]), _lib.ptr(buf["dpreds"]), st)
             if fuse_step:
                 kind, lr, h1, h2, eps, wd, step, s1, s2 = self.optimizer.fused_step_args(flat)
@@ -156,22 +160,17 @@ class FusedStepMixin:
                     self.optimizer.step_flat(flat)
         return loss.reshape(()), stop_training
 
-    def _single_call_step(self, X, Y, lens, buf, flat, B, L, Fd, NL, R, p, seed, spec, kwargs, loss, dev):
-        entry, params = spec
+    def _single_call_step(self, X, Y, lens, buf, flat, B, L, Fd, NL, R, p, seed, spec, values, kwargs, loss, dev):
         d = buf.get("desc")
         if d is None:
             d = buf["desc"] = _lib.TrainStepDesc()
             d.struct_bytes = C.sizeof(_lib.TrainStepDesc)
-            d.loss_kind = _lib.LOSS_KINDS[entry]
+            d.loss_kind = spec.kind
             d.B, d.L, d.F, d.NL = B, L, Fd, NL
             for k in ("preds", "acts", "loss_q", "dpreds", "dz", "ws"):
                 setattr(d, k, None if buf[k] is None else buf[k].data_ptr())
-        pl = params(self, kwargs)                      # the loss parameters, as the separate entry point takes them
-        if d.loss_kind == 3:                           # LambdaLoss: k, sigma, mu, loss_type, presort
-            d.loss_i[0], d.loss_i[1], d.loss_i[2] = pl[0], pl[3], pl[4]
-            d.loss_f[0], d.loss_f[1] = pl[1].value, pl[2].value
-        elif pl:
-            d.loss_f[0] = pl[0].value                  # RankNet / LambdaRank: sigma
+        li, lf = spec.desc_arrays(**values)            # the loss parameters, as the separate entry point takes them
+        d.loss_i[:len(li)], d.loss_f[:len(lf)] = li, lf
         wimg = x6_wimg_for(X, R, Fd, NL, True, dev)    # the forward mlp_forward would choose for this call
         d.wimg = None if wimg is None else wimg.data_ptr()
         d.X, d.labels, d.lens = X.data_ptr(), Y.data_ptr(), (None if lens is None else lens.data_ptr())
@@ -211,7 +210,7 @@ class FusedStepMixin:
             x6_set_image_tag(dev, Fd, NL, (flat.data_ptr(), flat._version, step, wimg.data_ptr()))
         if evs is not None:
             timing.setdefault("ptr_mlp_forward_x6" if wimg is not None else "ptr_mlp_forward", []).append((evs[0], evs[1]))
-            timing.setdefault(entry, []).append((evs[1], evs[2]))
+            timing.setdefault(spec.entry, []).append((evs[1], evs[2]))
             timing.setdefault("ptr_mlp_backward_step", []).append((evs[2], evs[3]))
         stop_training = False
         if 'epoch_k' in kwargs and kwargs['epoch_k'] % self.stop_check_freq == 0:
@@ -281,7 +280,10 @@ class FusedStepMixin:
 
 
 class RankNetLoss(FusedStepMixin):
-    _direct_entry = ("ptr_ranknet_fwd_bwd", lambda self, kw: [C.c_float(float(self.sigma))])
+    _direct_loss = _lib.LOSSES["ranknet"]
+
+    def _loss_values(self, kwargs):
+        return dict(sigma=self.sigma)
 
     def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
         """ptranking/ltr_adhoc/pairwise/ranknet.py:25-42"""
@@ -289,7 +291,10 @@ class RankNetLoss(FusedStepMixin):
 
 
 class LambdaRankLoss(FusedStepMixin):
-    _direct_entry = ("ptr_lambdarank_fwd_bwd", lambda self, kw: [C.c_float(float(self.sigma))])
+    _direct_loss = _lib.LOSSES["lambdarank"]
+
+    def _loss_values(self, kwargs):
+        return dict(sigma=self.sigma)
 
     def _direct_check(self, kwargs):
         assert 'label_type' in kwargs and is_multilabel(kwargs['label_type'])
@@ -297,15 +302,16 @@ class LambdaRankLoss(FusedStepMixin):
 
     def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
         """ptranking/ltr_adhoc/listwise/lambdarank.py:27-62"""
-        assert 'label_type' in kwargs and is_multilabel(kwargs['label_type'])
-        assert 'presort' in kwargs and kwargs['presort'] is True  # aiming for direct usage of ideal ranking
+        self._direct_check(kwargs)
         return self._fused_step(F_.lambdarank_loss(batch_preds, batch_std_labels, sigma=self.sigma, lens=kwargs.get('lens')))
 
 
 class LambdaLossLoss(FusedStepMixin):
-    _direct_entry = ("ptr_lambdaloss_fwd_bwd",
-                     lambda self, kw: [int(self.k), C.c_float(float(self.sigma)), C.c_float(float(getattr(self, 'mu', 5.0))),
-                                       F_.LAMBDALOSS_TYPES[self.loss_type], int(bool('presort' in kw and kw['presort']))])
+    _direct_loss = _lib.LOSSES["lambdaloss"]
+
+    def _loss_values(self, kwargs):
+        return dict(k=self.k, sigma=self.sigma, mu=getattr(self, 'mu', 5.0), loss_type=F_.LAMBDALOSS_TYPES[self.loss_type],
+                    presort=bool('presort' in kwargs and kwargs['presort']))
 
     def _direct_check(self, kwargs):
         assert is_multilabel(kwargs['label_type'])
@@ -314,7 +320,7 @@ class LambdaLossLoss(FusedStepMixin):
 
     def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
         """ptranking/ltr_adhoc/listwise/lambdaloss.py:73-138"""
-        assert is_multilabel(kwargs['label_type'])
+        self._direct_check(kwargs)
         presort = bool('presort' in kwargs and kwargs['presort'])
         loss = F_.lambdaloss_loss(batch_preds, batch_std_labels, k=self.k, sigma=self.sigma, mu=getattr(self, 'mu', 5.0),
                                   loss_type=self.loss_type, presort=presort, lens=kwargs.get('lens'))
@@ -401,7 +407,7 @@ class MDPRankLoss(FusedStepMixin):
 
 
 class ListNetLoss(FusedStepMixin):
-    _direct_entry = ("ptr_listnet_fwd_bwd", lambda self, kw: [])
+    _direct_loss = _lib.LOSSES["listnet"]
 
     def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
         """ptranking/ltr_adhoc/listwise/listnet.py:22-45"""
