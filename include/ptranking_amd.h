@@ -470,8 +470,12 @@ int ptr_bnact_backward_apply(const float *z, const float *da, int ld, int R, int
  * seed, site must be the forward call's.  Head dimension F / n_heads <= PTR_MHSA_MAX_HEAD_DIM.
  * ld_qkv = row stride in floats of Q, K, V (and dQ, dK, dV): F for three separate tensors, 3F when they are the column blocks
  * of ONE packed [B][L][3F] projection (pass base, base + F, base + 2F) — one GEMM then produces all three and dQ|dK|dV is
- * directly the gradient of that projection.  O, dO are always [B][L][F]. */
-#define PTR_MHSA_MAX_HEAD_DIM 128
+ * directly the gradient of that projection.  O, dO are always [B][L][F].
+ * Heads up to 128 wide run the kernels that keep the whole head in registers (csrc/listsf.hip); heads of 129 .. PTR_MHSA_MAX_HEAD_DIM
+ * (352 = 22 column tiles of 16: the reference's 2-head default on the 700 Yahoo! features is 350) run the wide forms
+ * (csrc/listsf_wide.hip: one workgroup per CU, one operand of head width per wave in registers).  Same contract, same dropout masks; wider heads are refused
+ * with PTR_ERR_UNSUPPORTED. */
+#define PTR_MHSA_MAX_HEAD_DIM 352
 int ptr_mhsa_forward(const float *Q, const float *K, const float *V, int ld_qkv, const int32_t *lens, int B, int L, int F,
                      int n_heads, float p_drop, uint64_t seed, int site, float *O, float *lse, void *stream);
 /* ds_ws (ABI v2, nullable): B * n_heads * L * L floats of scratch.  When given, the dK / dV kernel stores the scaled dS it forms and the dQ

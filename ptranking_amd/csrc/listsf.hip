@@ -21,38 +21,17 @@
 //   LDS as one ds_read_b128 per 4 k-steps (k-slot (c, g) <-> d = 16*blk + 4*g + c), shared by all row tiles.
 #include <stdlib.h>
 
+#include "ptr_attn.h"
 #include "ptr_device.h"
 #include "ptr_dropout.h"
 
 namespace ptr {
 
 constexpr int kRC = 32;                // rows per LDS chunk (dK / dV)
-constexpr int kDsPadLd = 20;           // row stride (floats) of the dS transpose pad: 16-byte aligned rows, 80 B = 20 banks apart
 // workgroups per CU the attention kernels are compiled for (register budget): the backward kernels gain 4 % from a third wave per
 // SIMD (<= 168 VGPRs), the forward loses 10 % (measured at 1024 x 256 x 136, 2 heads: scratch/exp_attn.py)
 constexpr int kAttnMinBlkFwd = 2;
 constexpr int attn_minblk_bwd(int DT) { return DT <= 5 ? 3 : 2; }     // head dimensions above 80 would spill 80-170 registers at 168
-
-struct AttnArgs {
-    int B, L, H, dh, F;
-    int ld;                            // row stride (floats) of Q / K / V and dQ / dK / dV: F, or 3F for a packed [B][L][3F] projection
-    float inv_scale;                   // 1 / sqrt(dh)
-    float p_drop;
-    uint32_t seed_lo, seed_hi;
-    int site;
-};
-
-// LDS leading dimension for a [rows][dh] tile: covers the 16*DT columns the d-tiles touch, ld/4 odd (conflict-free b128)
-__host__ __device__ constexpr int attn_ld(int DT) { return ((16 * DT / 4) & 1) ? 16 * DT : 16 * DT + 4; }
-
-// Workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  The row (key) blocks of one (query, head) re-read the
-// same K / V (Q / dO) rows, so consecutive LOGICAL block ids are placed on the same XCD: logical = xcd * (n / 8) + slot.
-__device__ __forceinline__ int xcd_major_block_id() {
-    const int n = gridDim.x, b = blockIdx.x;
-    return (n & 7) == 0 ? (b & 7) * (n >> 3) + (b >> 3) : b;
-}
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // Software-pipelined staging of rows [row0, row0 + NROWS) of a head's column block into an LDS tile dst[NROWS][LD] (rows >=
 // row_lim and columns >= dh zero): load() issues the global loads of the NEXT chunk into registers before the
@@ -169,15 +148,6 @@ __device__ __forceinline__ void multi_dot(const float *As, int a_row0, int ld, i
             }
         }
     }
-}
-
-__device__ __forceinline__ float xor_max(float v) {
-    v = fmaxf(v, __shfl_xor(v, 16));
-    return fmaxf(v, __shfl_xor(v, 32));
-}
-__device__ __forceinline__ float xor_sum(float v) {
-    v += __shfl_xor(v, 16);
-    return v + __shfl_xor(v, 32);
 }
 
 // ============================================================================================ forward
@@ -798,6 +768,7 @@ extern "C" int ptr_mhsa_forward(const float *Q, const float *K, const float *V, 
     if (B == 0) return 0;
     if (!Q || !K || !V || !O || !lse) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
     hipStream_t st = as_stream(stream);
+    if (a.dh > kAttnNarrowMaxHeadDim) return mhsa_wide_forward(Q, K, V, lens, a, O, lse, st, who);      // listsf_wide.hip
     const int DT = (a.dh + 15) / 16;
     return dispatch_dt(DT, [&]<int D>() -> int {
         auto launch = [&]<int RT, int NW>() -> int {
@@ -831,6 +802,7 @@ extern "C" int ptr_mhsa_backward(const float *Q, const float *K, const float *V,
     const int rblocks = (int)((nrows + 15) / 16 < 4096 ? (nrows + 15) / 16 : 4096);
     hipLaunchKernelGGL(attn_rowdot_kernel, dim3(rblocks), dim3(256), 0, st, O, dO, a, dvec);
     if (int rc = check_hip(hipGetLastError(), who)) return rc;
+    if (a.dh > kAttnNarrowMaxHeadDim) return mhsa_wide_backward(Q, K, V, dO, lse, dvec, lens, a, dQ, dK, dV, ds_ws, st, who);
     const int DT = (a.dh + 15) / 16;
     return dispatch_dt(DT, [&]<int D>() -> int {
         auto launch_dq = [&]<int NW>() -> int {

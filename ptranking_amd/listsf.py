@@ -27,7 +27,7 @@ from . import dp
 from .host import SplitKLinear, build_stacked_ffnet
 from .linear import linear
 
-MAX_HEAD_DIM = 128        # PTR_MHSA_MAX_HEAD_DIM
+MAX_HEAD_DIM = 352        # PTR_MHSA_MAX_HEAD_DIM: heads to 128 on the narrow kernels (csrc/listsf.hip), 129..352 on the wide ones (csrc/listsf_wide.hip)
 Encoder_Type = ['DASALC', 'AllRank', 'AttnDIN']   # list_ranker.py:13
 
 
