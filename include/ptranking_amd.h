@@ -62,14 +62,19 @@ int ptr_lambdarank_fwd_bwd(const float *preds, const float *labels, const int32_
 
 /* LambdaLoss — replaces ptranking/ltr_adhoc/listwise/lambdaloss.py:83-132 and its backward.
  * loss_type: PTR_LAMBDALOSS_*; k = truncation (pairs with both ranks < k); mu only used by NDCG_Loss2++;
- * presort != 0 => labels already in ideal order (lambdaloss.py:83-84), else they are sorted first (:86-87). */
+ * presort != 0 => labels already in ideal order (lambdaloss.py:83-84), else they are sorted first (:86-87).
+ * A list with documents but no relevant one (IDCG = 0): NDCG_Loss1 gives a NaN loss and a NaN gradient on every document,
+ * as the reference; NDCG_Loss2 / Loss2++ give loss 0 and gradient 0.  A zero-length list gives 0.  A list that holds a NaN score
+ * or label gives a NaN loss and a NaN gradient on every document (the reference ranks a NaN score first and stays finite). */
 int ptr_lambdaloss_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, int k,
                            float sigma, float mu, int loss_type, int presort, float *loss_out, float *loss_q,
                            float *grad, void *stream);
 
 /* SoftRank — replaces ptranking/ltr_adhoc/listwise/softrank.py:47-69 and its backward: expected ranks from
  * 0.5*erfc((s_i-s_j)/sqrt(4*delta^2)), loss = -sum_q sum_{i<top_k} (2^l_i-1)/(log2(E[rank_i]+1)*IDCG_q).  Labels must be
- * in ideal order (the reference asserts presort).  top_k <= 0: no truncation (top_k=None).  delta > 0. */
+ * in ideal order (the reference asserts presort).  top_k <= 0: no truncation (top_k=None).  delta > 0.
+ * A zero-length list has loss 0 and a zero gradient; a list without a relevant document is NaN, as the reference
+ * (its gradient too, except a one-document list's, which has no pair and is 0). */
 int ptr_softrank_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, float delta, int top_k,
                          float *loss_out, float *loss_q, float *grad, void *stream);
 

@@ -215,6 +215,21 @@ int orc_lambdaloss(const float *preds, const float *labels, const int32_t *lens,
             }
         for (int r = 0; r < n; ++r) g[il[ip[r]]] = gs[r];
         loss_q[q] = (float)loss;
+        if (loss_type == 0 && n > 0 && idcg == 0.0f) {
+            /* NDCG_Loss1 without a relevant document: gains 0 / 0, every power weight NaN.  The reference's clamp(min) keeps NaN: the
+             * loss is NaN and so is the gradient of every document of the list.  (Loss2 / Loss2++ select no entry: loss 0, and the
+             * gradient stays the derivative of that constant, 0, where the reference's autograd returns 0 * NaN.) */
+            for (int r = 0; r < n; ++r) g[r] = NAN;
+            if (kk > 0) loss_q[q] = NAN;
+        }
+        int unranked = idcg != idcg;
+        for (int r = 0; r < n; ++r) unranked |= s[r] != s[r];
+        if (unranked) {
+            /* a NaN score or label: no ranking.  The loss and the gradient of every document of the list are NaN (the reference ranks a
+             * NaN score first and stays finite: tests/golden/losses_nanscore.npz) */
+            for (int r = 0; r < n; ++r) g[r] = NAN;
+            loss_q[q] = NAN;
+        }
     }
     free(tmp); free(il); free(ip); free(buf);
     return ORC_OK;

@@ -188,7 +188,9 @@ approxndcg_kernel(const float *__restrict__ preds, const float *__restrict__ lab
             float tot = ga[m];
 #pragma unroll
             for (int w = 0; w < NW; ++w) tot += acc[(size_t)w * Lp + a];
-            S_id[a] = tot * scale;                            // own index only
+            // own index only.  SoftRank, one document: no pair, so the reference's gradient is exactly 0 even where 1 / IDCG is inf
+            // (tests/golden/losses_norel.npz, softrank/no_relevant_one_doc)
+            S_id[a] = (SOFT && n == 1) ? 0.0f : tot * scale;
         }
     }
     __syncthreads();
@@ -199,7 +201,8 @@ approxndcg_kernel(const float *__restrict__ preds, const float *__restrict__ lab
             if (i < L) grad[(size_t)q * L + i] = i < n ? S_id[ipos[m]] : 0.0f;
         }
         if (t == 0) {
-            if constexpr (SOFT) { dcg_q[q] = -(dcg * inv_idcg); }         // per-query loss
+            // per-query loss; a zero-length query is an empty sum: 0, not 0 * (1 / 0)
+            if constexpr (SOFT) { dcg_q[q] = n > 0 ? -(dcg * inv_idcg) : 0.0f; }
             else { dcg_q[q] = dcg; inv_idcg_q[q] = inv_idcg; }
         }
     }

@@ -8,6 +8,13 @@
 //   * the mask is `label_i > label_j` AND both predicted ranks < k (a full-matrix mask: every unordered pair with
 //     different grades contributes exactly one term, seen from its winner);
 //   * clamp(min=1e-8) before and after the power, log2 (not ln), score differences clamped to +-1e8, NaN -> 0.
+//   * a list with documents but no relevant one has IDCG = 0 and normalised gains 0 / 0, so every power weight is NaN.  NDCG_Loss1
+//     follows the reference to NaN: clamp(min) keeps NaN, the loss is NaN and so is the gradient of EVERY document of the list, whatever
+//     k is.  NDCG_Loss2 / Loss2++ select no entry there (all labels are equal): the loss is 0, as the reference's, and the gradient is
+//     the derivative of that constant, 0 — NOT the reference's NaN, which is autograd's 0 * NaN through the entries the mask left out.
+// NOT reproduced: a NaN score.  The reference's torch.sort ranks it FIRST, its differences count as 0 and carry no gradient, and the loss
+// stays finite (tests/golden/losses_nanscore.npz).  Here a list that holds a NaN score (or label) has no ranking: its loss is NaN and so
+// is the gradient of every document of the list, in both kernels (the NaN travels in the IDCG sum, so the check costs no reduction).
 #include <utility>
 #include "ptr_device.h"
 #include "ptr_dropout.h"          // f32x4
@@ -60,7 +67,8 @@ lambdaloss_kernel(const float *__restrict__ preds, const float *__restrict__ lab
         const int p = t + m * G;
         sp[m] = p < Lp ? S_id[p] : -INFINITY;
         yp[m] = p < Lp ? Y_id[p] : 0.0f;
-        if (p < n) part += gain_of(yp[m]) / log2f((float)p + 2.0f);     // adhoc_metric.py:205-217 on the ideal ranking
+        if (p < n) part += sp[m] != sp[m] ? __builtin_nanf("") : gain_of(yp[m]) / log2f((float)p + 2.0f);   // adhoc_metric.py:205-217 on the
+        // ideal ranking; a NaN score makes the sum NaN (header)
     }
     // lambdaloss.py:89 (pk, filled below, is the scratch of either form: 4*Lp floats >= the 64*DPT sorted keys of the one-wave form)
     if constexpr (G == kWave) count_ranks_wave<DPT>(S_id, reinterpret_cast<float *>(pk), n, Lp, t, sp, rk);
@@ -201,13 +209,15 @@ lambdaloss_kernel(const float *__restrict__ preds, const float *__restrict__ lab
     }
     __syncthreads();
     const float loss = group_sum<G>(lacc, red, t);
+    const bool unranked = idcg != idcg;                                                    // a NaN score or label (header)
+    const bool norel = (loss_type == PTR_LAMBDALOSS_NDCG_LOSS1 && n > 0 && idcg == 0.0f) || unranked;   // gains 0 / 0: the reference's NaN (header)
     if (valid) {
 #pragma unroll
         for (int m = 0; m < DPT; ++m) {
             const int i = t + m * G;
-            if (i < L) grad[(size_t)q * L + i] = i < n ? Y_id[ipos[m]] : 0.0f;
+            if (i < L) grad[(size_t)q * L + i] = i < n ? (norel ? __builtin_nanf("") : Y_id[ipos[m]]) : 0.0f;
         }
-        if (t == 0) loss_q[q] = loss;
+        if (t == 0) loss_q[q] = (norel && kk > 0) || unranked ? __builtin_nanf("") : loss;
     }
 }
 
@@ -261,8 +271,9 @@ lambdaloss_topk_kernel(const float *__restrict__ preds, const float *__restrict_
                 const bool in = full || i < n;                                             // full lists (n == L == 256 V): no masks
                 s[4 * m + e] = in ? a4[e] : -INFINITY;
                 y[4 * m + e] = in ? b4[e] : 0.0f;
-                part += in ? (__builtin_amdgcn_exp2f(b4[e]) - 1.0f) * disc[4 * m + e] : 0.0f;   // IDCG of the (presorted = ideal) label order,
-                // adhoc_metric.py:205-217 (2^l - 1 on v_exp_f32: exact for the integer grades, 1 ulp otherwise)
+                part += in ? (a4[e] != a4[e] ? __builtin_nanf("") : (__builtin_amdgcn_exp2f(b4[e]) - 1.0f) * disc[4 * m + e]) : 0.0f;
+                // IDCG of the (presorted = ideal) label order, adhoc_metric.py:205-217 (2^l - 1 on v_exp_f32: exact for the integer grades,
+                // 1 ulp otherwise); a NaN score makes it NaN: the list's loss and gradients are NaN (header of this file)
             }
         }
         const float idcg = wave_sum_dpp(part);
@@ -291,8 +302,8 @@ lambdaloss_topk_kernel(const float *__restrict__ preds, const float *__restrict_
         float rs = 0.0f, ry = 0.0f;
         int ri = -1;
         if constexpr (V == 1) {
-            // a lane's four documents stay where they are; a document that cannot win any more (padding, a NaN score — the reference sorts
-            // those last —, taken in an earlier round) is a quiet NaN, which v_max ignores and no comparison matches
+            // a lane's four documents stay where they are; a document that cannot win any more (padding, taken in an earlier round, a NaN
+            // score: such a list's outputs are NaN, see below) is a quiet NaN, which v_max ignores and no comparison matches
             float hs[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) hs[e] = (full || 4 * lane + e < n) ? __builtin_canonicalizef(s[e]) : __builtin_nanf("");
@@ -420,13 +431,20 @@ lambdaloss_topk_kernel(const float *__restrict__ preds, const float *__restrict_
                 for (int e = 0; e < 4; ++e)
                     if ((idx >> 8) == m && (idx & 3) == e) o4[m][e] = mine ? gq : o4[m][e];   // scalar condition: one select per record
         }
+        const bool unranked = idcg != idcg;                                                // uniform: a NaN score or label (header of this file)
+        if (unranked) {
+#pragma unroll
+            for (int m = 0; m < V; ++m)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o4[m][e] = 4 * (lane + 64 * m) + e < n ? __builtin_nanf("") : 0.0f;
+        }
         f32x4 *go = reinterpret_cast<f32x4 *>(grad + (size_t)q * L);
 #pragma unroll
         for (int m = 0; m < V; ++m) {
             const int c = lane + 64 * m;
             if (c < L4) go[c] = o4[m];
         }
-        if (lane == 0) loss_q[q] = loss;
+        if (lane == 0) loss_q[q] = unranked ? __builtin_nanf("") : loss;
     }
 }
 

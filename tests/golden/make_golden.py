@@ -498,6 +498,64 @@ def gen_long():
     print(f"losses_long.npz: {len(store)} arrays")
 
 
+def gen_norel():
+    """A query with documents but no relevant one (every label 0, so IDCG = 0 and the normalised gains are 0 / 0): what the reference
+    itself returns for LambdaLoss NDCG_Loss1 / NDCG_Loss2 / NDCG_Loss2++ and SoftRank.  One list per case (NDCG_Loss1 only runs at batch
+    size 1).  A file of its own: the older files stay byte-identical."""
+    from ptranking.ltr_adhoc.listwise.softrank import SoftRank
+    store = {}
+    preds = np.array([[0.5, -1.25, 2.0, 0.0, -0.75, 1.5]], np.float32)
+    labels = np.zeros((1, 6), np.float32)
+    for lt, code in (("NDCG_Loss1", 0), ("NDCG_Loss2", 1), ("NDCG_Loss2++", 2)):
+        for k in (3, 6):
+            mpd = dict(k=k, sigma=1.0, loss_type=lt, mu=5.0)
+            loss, grad = run_loss(LambdaLoss(sf_para_dict=SF, model_para_dict=mpd, device="cpu"), preds, labels)
+            add(store, f"lambdaloss/no_relevant_t{code}_k{k}", preds=preds, labels=labels, sigma=np.float32(1.0), k=np.int32(k),
+                mu=np.float32(5.0), loss_type=np.int32(code), loss=loss, grad=grad)
+    for top_k in (None, 3):
+        mpd = dict(delta=2.0, top_k=top_k, metric="nDCG")
+        loss, grad = run_loss(SoftRank(sf_para_dict=SF, model_para_dict=mpd, device="cpu"), preds, labels)
+        add(store, f"softrank/no_relevant_k{top_k or 0}", preds=preds, labels=labels, delta=np.float32(2.0), top_k=np.int32(top_k or 0),
+            loss=loss, grad=grad)
+    # one document, not relevant: no pair, so the loss is NaN (0 / 0) but the gradient exactly 0
+    mpd = dict(delta=2.0, top_k=None, metric="nDCG")
+    loss, grad = run_loss(SoftRank(sf_para_dict=SF, model_para_dict=mpd, device="cpu"), preds[:, :1].copy(), labels[:, :1].copy())
+    add(store, "softrank/no_relevant_one_doc", preds=preds[:, :1].copy(), labels=labels[:, :1].copy(), delta=np.float32(2.0), top_k=np.int32(0),
+        loss=loss, grad=grad)
+    np.savez_compressed(os.path.join(HERE, "losses_norel.npz"), **store)
+    print(f"losses_norel.npz: {len(store)} arrays")
+    for k_ in sorted(store):
+        if k_.endswith("/loss") or k_.endswith("/grad"):
+            print(" ", k_, store[k_])
+
+
+def gen_nanscore():
+    """Lists with NaN scores, so that fewer than k documents have a rank by score: what the reference itself returns for LambdaLoss
+    NDCG_Loss2 / NDCG_Loss2++ (torch.sort ranks NaN first, the differences count as 0 and carry no gradient: finite outputs).  An
+    8-document list with 3 real scores and a 512-document list with 4, k = 5 and k = L.  A file of its own."""
+    store = {}
+    nan = np.nan
+    p8 = np.array([[0.5, nan, 2.0, nan, nan, 1.5, nan, nan]], np.float32)
+    y8 = np.array([[3, 2, 2, 1, 1, 0, 0, 0]], np.float32)
+    rng = np.random.default_rng(SEED + 31)
+    p512, y512 = synth(rng, 1, 512)
+    keep = [0, 7, 130, 300]
+    rest = np.setdiff1d(np.arange(512), keep)
+    p512[0, rest] = nan
+    for tag, preds, labels in (("L8", p8, y8), ("L512", p512, y512)):
+        for lt, code in (("NDCG_Loss2", 1), ("NDCG_Loss2++", 2)):
+            for k in (5, preds.shape[1]):
+                mpd = dict(k=k, sigma=1.0, loss_type=lt, mu=5.0)
+                loss, grad = run_loss(LambdaLoss(sf_para_dict=SF, model_para_dict=mpd, device="cpu"), preds, labels)
+                add(store, f"lambdaloss/nan_scores_{tag}_t{code}_k{k}", preds=preds, labels=labels, sigma=np.float32(1.0), k=np.int32(k),
+                    mu=np.float32(5.0), loss_type=np.int32(code), loss=loss, grad=grad)
+    np.savez_compressed(os.path.join(HERE, "losses_nanscore.npz"), **store)
+    print(f"losses_nanscore.npz: {len(store)} arrays")
+    for k_ in sorted(store):
+        if k_.endswith("/loss"):
+            print(" ", k_, store[k_])
+
+
 if __name__ == "__main__":
     if "--only-long" in sys.argv:
         gen_long()
@@ -507,6 +565,10 @@ if __name__ == "__main__":
         gen_knife()
     elif "--only-siblings" in sys.argv:
         gen_siblings()
+    elif "--only-norel" in sys.argv:
+        gen_norel()
+    elif "--only-nanscore" in sys.argv:
+        gen_nanscore()
     else:
         gen_losses()
         gen_metrics()
@@ -514,4 +576,6 @@ if __name__ == "__main__":
         gen_big()
         gen_knife()
         gen_long()
+        gen_norel()
+        gen_nanscore()
     print("torch", torch.__version__, "numpy", np.__version__)

@@ -4,6 +4,7 @@ import ctypes
 import os
 import re
 
+import numpy as np
 import pytest
 import torch
 
@@ -344,7 +345,8 @@ def _ring_z(labels, n, dpt):
 
 
 def test_loss_bound_cases_hit_every_dispatch_form():
-    """tests/test_loss_bounds_gpu.py's case lists launch every form of the LambdaRank, RankNet, ApproxNDCG, ListNet and ListMLE kernels."""
+    """tests/test_loss_bounds_gpu.py's case lists launch every form of the LambdaRank, RankNet, ApproxNDCG, ListNet, ListMLE, LambdaLoss
+    and SoftRank kernels."""
     import importlib
     G = importlib.import_module("test_loss_bounds_gpu")
     lambdarank, ranknet, approx, listwise = _loss_dispatch()
@@ -386,3 +388,85 @@ def test_loss_bound_cases_hit_every_dispatch_form():
         spread = [float(p[q, :n[q]].max() - p[q, :n[q]].min()) for q in range(B) if n[q] > 1]
         assert min(spread) < 24.0 < max(spread), (B, L)
     assert any(B % 4 for B, *_ in G.APPROX_CASES) and any(B % 16 for B, *_ in G.LAMBDARANK_CASES)      # B not a multiple of a workgroup
+    _check_lambdaloss_softrank_stlistnet_cases()
+
+
+def _lambdaloss_route(L, k, loss_type, presort, unaligned):
+    """ptr_lambdaloss_fwd_bwd (csrc/lambdaloss.hip): the top-k kernel for a small cut-off on presorted, 16-byte aligned rows of a
+    multiple of four documents, lambdaloss_kernel on dispatch_wave256_tiling otherwise."""
+    if presort and k <= 11 and loss_type != 0 and L % 4 == 0 and L <= 1024 and not unaligned:
+        return ("topk", 1 if L <= 256 else 2 if L <= 512 else 4)
+    if L <= 256:
+        return ("generic", 64, 1 if L <= 64 else 2 if L <= 128 else 4)
+    return ("generic", 256, 2 if L <= 512 else 4 if L <= 1024 else 8 if L <= 2048 else 16)
+
+
+def _topk_libm_queries(case, p, y, n):
+    """Queries of a top-k case that leave the fast route: an active pair among the kk best with |sigma ds| > 80."""
+    _, L, k, _, _, sigma, _ = case
+    out = []
+    for q in range(p.shape[0]):
+        nq = int(n[q])
+        s, lab = p[q, :nq].astype(np.float64), y[q, :nq]
+        if np.isnan(s).any():                        # a NaN score: the list's outputs are NaN by either route
+            out.append(False)
+            continue
+        o = np.lexsort((np.arange(nq), -s))[:min(k, nq)]
+        x = sigma * np.abs(s[o][:, None] - s[o][None, :])
+        out.append(bool(((lab[o][:, None] != lab[o][None, :]) & ~(x <= 80.0)).any()))
+    return out
+
+
+def _check_lambdaloss_softrank_stlistnet_cases():
+    """tests/test_loss_bounds_gpu.py's LambdaLoss cases launch all ten forms of ptr_lambdaloss_fwd_bwd, every route that sends a top-k
+    eligible call to the generic kernel, both arithmetic routes of the top-k kernel, a batch whose wavefronts must walk; the SoftRank
+    cases every dispatch_tiling form."""
+    import importlib
+    G = importlib.import_module("test_loss_bounds_gpu")
+    route = lambda c: _lambdaloss_route(c[1], c[2], c[3], c[4], "u" in c[6])
+    gen = {route(c) for c in G.LAMBDALOSS_GENERIC_CASES}
+    assert gen == {("generic", 64, 1), ("generic", 64, 2), ("generic", 64, 4), ("generic", 256, 2), ("generic", 256, 4), ("generic", 256, 8),
+                   ("generic", 256, 16)}
+    assert {route(c) for c in G.LAMBDALOSS_TOPK_CASES} == {("topk", 1), ("topk", 2), ("topk", 4)}
+    assert route(G.LAMBDALOSS_PERSISTENT) == ("topk", 1)
+    # each reason that keeps a small cut-off off the top-k kernel, alone
+    elig = lambda c, **kw: _lambdaloss_route(**{**dict(L=c[1], k=c[2], loss_type=c[3], presort=c[4], unaligned="u" in c[6]), **kw})[0] == "topk"
+    why = set()
+    for c in G.LAMBDALOSS_GENERIC_CASES:
+        why |= {r for r, kw in (("k", dict(k=11)), ("L%4", dict(L=64)), ("unaligned", dict(unaligned=False)), ("loss1", dict(loss_type=1)),
+                                ("presort", dict(presort=1))) if elig(c, **kw)}
+    assert why == {"k", "L%4", "unaligned", "loss1", "presort"}, why
+    assert {c[3] for c in G.LAMBDALOSS_GENERIC_CASES} == {0, 1, 2} and {c[4] for c in G.LAMBDALOSS_GENERIC_CASES} == {0, 1}
+    assert all(c[0] % 4 for c in G.LAMBDALOSS_GENERIC_CASES) and all(c[0] <= 96 for c in G.LAMBDALOSS_GENERIC_CASES + G.LAMBDALOSS_TOPK_CASES)
+    ks = {("1" if c[2] == 1 else "2" if c[2] == 2 else "5" if c[2] == 5 else "L" if c[2] == c[1] else "2L" if c[2] == 2 * c[1] else
+           "odd" if c[2] % 2 else "even") for c in G.LAMBDALOSS_GENERIC_CASES}
+    assert ks >= {"1", "2", "5", "odd", "even", "L", "2L"}
+    assert {c[2] for c in G.LAMBDALOSS_TOPK_CASES} >= {1, 2, 5, 11} and all(c[3] in (1, 2) and c[4] == 1 for c in G.LAMBDALOSS_TOPK_CASES)
+    # the top-k kernel's two arithmetic routes, full lists (the mask-free path), lists shorter than k, ties inside a lane's four documents
+    for c in G.LAMBDALOSS_TOPK_CASES:
+        p, y, n, _, n_small, _ = G.lambdaloss_inputs(c)
+        libm = _topk_libm_queries(c, p, y, n)
+        assert any(libm) and not all(libm) if "x" in c[6] else not any(libm), c
+        assert "x" not in c[6] or n_small > 0, c     # the libm-route case also holds entries with p < eps
+    full = {1 if L <= 256 else 2 for c in G.LAMBDALOSS_TOPK_CASES for L in [c[1]]
+            if L in (256, 512) and (G.lambdaloss_inputs(c)[2] == L).any()}
+    assert full == {1, 2}
+    c = G.LAMBDALOSS_TOPK_CASES[0]
+    assert (G.lambdaloss_inputs(c)[2] < c[2]).any()
+    tied = False
+    for c in G.LAMBDALOSS_TOPK_CASES:
+        if "q" in c[6] and c[1] <= 256:
+            p, _, n, *_ = G.lambdaloss_inputs(c)
+            tied |= any(len(set(p[q, 4 * j:4 * j + 4].tolist())) < 4 for q in range(c[0]) for j in range(int(n[q]) // 4))
+    assert tied
+    # 8192 wavefronts (256 CUs x 4 SIMDs x 8) is all the device holds: every one walks at least three queries, kk changing on the way
+    Bp = G.LAMBDALOSS_PERSISTENT[0]
+    assert Bp >= 3 * 256 * 4 * 8 and Bp % 4
+    _, _, n, order = G.lambdaloss_persistent_inputs()
+    assert set(n.tolist()) == set(range(9)) and len(set(order.tolist())) == 256 and (np.diff(np.minimum(n, 5)) != 0).mean() > 0.5
+    lambdarank, ranknet, approx, listwise = _loss_dispatch()
+    tilings = {(64, 1), (64, 2), (256, 1), (256, 2), (256, 4), (256, 8), (256, 16)}
+    assert {approx(L, 0)[1:] for _, L, *_ in G.SOFTRANK_CASES} == tilings
+    assert {d for _, _, d, _, _ in G.SOFTRANK_CASES} == {2.0, 0.3} and any(o for *_, o in G.SOFTRANK_CASES)
+    assert {("none" if k == 0 else "> n" if k > L else "cut") for _, L, _, k, _ in G.SOFTRANK_CASES} == {"none", "> n", "cut"}
+    assert {L for _, L, *_ in G.STLISTNET_CASES} == {64, 63, 128, 1500} and {T for _, _, T, _, _ in G.STLISTNET_CASES} == {1.0, 2.0, 0.5}

@@ -673,3 +673,524 @@ def test_reference_fp32_outputs_pass_the_gate(name, fam, case):
     if fam == "listmle":        # the reference's autograd gradient through its log-cumsum-exp needs c 4.2 on two cases (c1, c4)
         return
     FL.gate_nan(g, r["grad"], r["E_grad"], f"{name} grad", c)
+
+
+# ------------------------------------------------------------------------------------------------------ LambdaLoss, SoftRank, STListNet
+# The oracle and the reference's fp32 fixtures pass the new gates, the restated gradients are the derivative of the restated losses,
+# float64 emulations of the kernels' own expressions agree with the restatements, planted faults fail.
+LL_MU = 5.0
+
+
+@pytest.mark.parametrize("L,k,kw", [(16, 5, {}), (100, 100, dict(quantise=True, offset=1000.0, need_clamps=True)), (40, 11, dict(mix="yahoo", lens="full"))],
+                         ids=["L16-k5", "L100-kL-quant-offset", "L40-k11-yahoo-full"])
+def test_oracle_lambdaloss_passes_the_gate(L, k, kw):
+    """The oracle rounds p ** w near 1 in fp32, as the reference does: log_floor.  Prints the constant each loss type needs."""
+    O = _oracle()
+    c = FL.C_LLOSS
+    for lt in (0, 1, 2):
+        for presort in (True, False):
+            p, y, n, *_ = FL.lambdaloss_inputs(48, L, k, mu=LL_MU, loss_type=lt, presort=presort, seed=L + lt, **kw)
+            lq, g = O.lambdaloss(p, y, k=k, sigma=1.0, mu=LL_MU, loss_type=lt, presort=presort, lens=n)
+            r = FL.lambdaloss(p, y, n, k, 1.0, LL_MU, lt, presort, c, log_floor=True)
+            FL.gate_losses(lq, g, r, f"oracle lambdaloss t{lt} pre{int(presort)} L{L}", c, float(lq.astype(np.float64).sum()), FL.batch_total(r, c))
+            assert r["loss_q"][4] == 0                                          # length 0
+            assert np.isnan(r["loss_q"][2]) == (lt == 0) and np.isnan(r["grad"][2, 0]) == (lt == 0)      # no relevant document
+            assert lt == 0 or (r["loss_q"][2] == 0 and (r["grad"][2] == 0).all())
+
+
+@pytest.mark.parametrize("L,delta,top_k", [(16, 2.0, None), (100, 0.3, 10), (40, 1.0, 50)])
+def test_oracle_softrank_passes_the_gate(L, delta, top_k):
+    O = _oracle()
+    c = FL.C_APPROX
+    p, y, n, _ = FL.pair_inputs(40, L, sigma=FL.softrank_inv_den(delta), seed=L, sort_labels=True, span=8.0, offset=1000.0 if L == 100 else 0.0)
+    lq, g = O.softrank(p, y, delta, top_k, n)
+    r = FL.softrank(p, y, n, delta, top_k, c)
+    FL.gate_losses(lq, g, r, f"oracle softrank L{L}", c)
+    assert r["loss_q"][4] == 0 and np.isnan(r["loss_q"][2]) and r["grad"][5, 0] == 0 and r["loss_q"][3] == -1.0
+
+
+@pytest.mark.parametrize("L,T,offset", [(20, 1.0, 0.0), (64, 2.0, 1000.0), (130, 0.5, 0.0)])
+def test_oracle_stlistnet_passes_the_gate(L, T, offset):
+    O = _oracle()
+    c = FL.C_LIST
+    p, y, u, n = FL.stlistnet_inputs(40, L, seed=L, offset=offset)
+    lq, g = O.stlistnet(p, y, u, T, n)
+    FL.gate_losses(lq, g, FL.stlistnet(p, y, u, n, T, c), f"oracle stlistnet L{L}", c)
+
+
+def _new_fixture_cases():
+    out = []
+    for f in ("losses.npz", "losses_big.npz", "losses_knife.npz", "siblings.npz", "losses_norel.npz"):
+        for fam, cases in G._load(f).items():
+            if fam in ("lambdaloss", "lambdaloss1", "softrank", "stlistnet"):
+                out += [(f"{f[:-4]}/{fam}/{k}", fam, cases[k]) for k in sorted(cases) if not fam.startswith("lambdaloss") or _ll_in_model(fam, cases[k])]
+    return out
+
+
+def _ll_args(fam, case):
+    lt = 0 if fam == "lambdaloss1" else int(case["loss_type"])
+    return (int(case["k"]), float(case["sigma"]), float(case["mu"]) if "mu" in case else LL_MU, lt,
+            bool(int(case["presort"])) if "presort" in case else True)
+
+
+def _ll_in_model(fam, case):
+    """Queries with an entry inside the screened distance of a clamp (most of losses_knife.npz) stay with their own fp32 tests."""
+    p, y = np.asarray(case["preds"]), np.asarray(case["labels"])
+    return not any(FL.lambdaloss_query(p[q], y[q], *_ll_args(fam, case), 1.0, detail=True)[4].any() for q in range(p.shape[0]))
+
+
+@pytest.mark.parametrize("name,fam,case", _new_fixture_cases(), ids=[c[0] for c in _new_fixture_cases()])
+def test_reference_fp32_lambdaloss_softrank_stlistnet_pass_the_gate(name, fam, case):
+    """The reference's own fp32 batch total and gradient; where it is NaN (losses_norel.npz) the restatement is NaN."""
+    p, y, g = case["preds"], case["labels"], case["grad"]
+    if fam in ("lambdaloss", "lambdaloss1"):
+        c = FL.C_LLOSS
+        r = FL.lambdaloss(p, y, None, *_ll_args(fam, case), c, log_floor=True)
+    elif fam == "softrank":
+        c = FL.C_APPROX
+        r = FL.softrank(p, y, None, float(case["delta"]), int(case["top_k"]), c)
+    else:
+        c = FL.C_LIST
+        r = FL.stlistnet(p, y, case["unif"], None, float(case["temperature"]), c)
+    tot, E = FL.batch_total(r, c)
+    FL.gate_nan([float(case["loss"])], [tot], [E], f"{name} loss", c)
+    if "no_relevant" in name and fam == "lambdaloss" and int(case["loss_type"]) != 0:
+        # Loss2 / Loss2++ select no entry: loss 0.  The reference's gradient is autograd's 0 * NaN; the product's is the constant's, 0
+        assert np.isnan(g).all() and (r["grad"] == 0).all()
+        return
+    FL.gate_nan(g, r["grad"], r["E_grad"], f"{name} grad", c)
+
+
+def _central(fn, s, h=1e-5):
+    g = np.empty(s.size)
+    for i in range(s.size):
+        a, b = s.copy(), s.copy()
+        a[i] += h
+        b[i] -= h
+        g[i] = (fn(a) - fn(b)) / (2 * h)
+    return g
+
+
+def test_restated_gradients_are_the_derivatives_of_the_restated_losses():
+    """Central differences in float64, at points away from the clamps (N(0, 1) scores: no entry near either)."""
+    g_ = np.random.default_rng(5)
+    n = 12
+    s = g_.standard_normal(n) + 0.01 * np.arange(n)
+    y = -np.sort(-g_.choice(5, size=n).astype(np.float64))
+    y[0] = max(y[0], 1.0)
+    for lt in (0, 1, 2):
+        for presort, k in ((True, 7), (False, 12)):
+            yy = y if presort else g_.permutation(y)
+            f = lambda v: FL.lambdaloss_query(v, yy, k, 1.3, LL_MU, lt, presort, 1.0)[0]
+            *_, near, a, b = FL.lambdaloss_query(s, yy, k, 1.3, LL_MU, lt, presort, 1.0, detail=True)
+            assert not near.any() and a == 0 and b == 0
+            np.testing.assert_allclose(FL.lambdaloss_query(s, yy, k, 1.3, LL_MU, lt, presort, 1.0)[2], _central(f, s), rtol=1e-7, atol=1e-9)
+    for top_k in (None, 5):
+        f = lambda v: FL.softrank_query(v, y, 0.4, top_k, 1.0)[0]
+        np.testing.assert_allclose(FL.softrank_query(s, y, 0.4, top_k, 1.0)[2], _central(f, s), rtol=1e-7, atol=1e-9)
+    u = g_.random(n).astype(np.float32)
+    f = lambda v: FL.stlistnet_query(v, y, u, 0.5, 1.0)[0]
+    np.testing.assert_allclose(FL.stlistnet_query(s, y, u, 0.5, 1.0)[2], _central(f, s), rtol=1e-7, atol=1e-9)
+
+
+# ---- float64 emulations of the kernels' own expressions (csrc/lambdaloss.hip, approxndcg.hip, listwise.hip)
+def _emu_lambdaloss_generic(s, y, k, sigma, mu, lt, presort):
+    """lambdaloss_kernel: ideal staging, ranks, the circulant walk over (a, a + d mod kk) with forward / wrapped rank distances, Loss1's
+    two ordered entries per unordered pair plus the diagonal."""
+    s, y = np.asarray(s, np.float64), np.asarray(y, np.float64)
+    n = s.size
+    idx = np.arange(n)
+    il = idx if presort else np.lexsort((idx, -y))
+    S, Y = s[il], y[il]
+    rk = np.empty(n, int)
+    rk[np.lexsort((idx, -S))] = idx
+    idcg = sum((2.0 ** Y[p] - 1.0) / math.log2(p + 2.0) for p in range(n))
+    pk = np.zeros((n, 4))
+    for p in range(n):
+        pk[rk[p], 0], pk[rk[p], 1], pk[rk[p], 3] = S[p], (2.0 ** Y[p] - 1.0) / idcg, Y[p]
+        pk[p, 2] = 1.0 / (1.0 / math.log2(p + 2.0))
+    kk = min(max(k, 0), n)
+    ln2, l2e = math.log(2.0), FL.LL_LOG2_EPS
+    loss, gr = 0.0, np.zeros(n)
+    lg = lambda x: -math.log1p(math.exp(-x)) / ln2 if x > -700 else x / ln2
+
+    def pair(a, d, dfw, dwr):
+        nonlocal loss
+        b, fwd = a + d, a + d < kk
+        if not fwd:
+            b -= kk
+        me, o = pk[a], pk[b]
+        if lt == 0:
+            x = sigma * (me[0] - o[0])
+            wb, wa = o[1] * o[2], me[1] * me[2]
+            pab, pba = 1.0 / (1.0 + math.exp(-x)), 1.0 / (1.0 + math.exp(x))
+            lab = lg(x) if pab >= FL.LL_EPS else l2e
+            lba = lg(-x) if pba >= FL.LL_EPS else l2e
+            zab, zba = wb * lab, wa * lba
+            loss -= (zab if zab >= l2e else l2e) + (zba if zba >= l2e else l2e)
+            g = 0.0
+            if pab >= FL.LL_EPS and zab >= l2e:
+                g -= wb * sigma * (1.0 - pab) / ln2
+            if pba >= FL.LL_EPS and zba >= l2e:
+                g += wa * sigma * (1.0 - pba) / ln2
+            gr[a] += g
+            gr[b] -= g
+            return
+        if me[3] == o[3]:
+            return
+        a_wins = me[3] > o[3]
+        delta = dfw if fwd else dwr
+        absG = abs(me[1] - o[1])
+        w = delta * absG if lt == 1 else (abs(me[2] - o[2]) + mu * delta) * absG
+        x = sigma * ((me[0] - o[0]) if a_wins else (o[0] - me[0]))
+        p0 = 1.0 / (1.0 + math.exp(-x))
+        lp = lg(x) if p0 >= FL.LL_EPS else l2e
+        z = w * lp
+        ok = z >= l2e
+        loss -= z if ok else l2e
+        g = -(w * sigma * (1.0 - p0)) / ln2 if (p0 >= FL.LL_EPS and ok) else 0.0
+        g = g if a_wins else -g
+        gr[a] += g
+        gr[b] -= g
+
+    if lt == 0:
+        loss += sum(min(pk[a, 1] * pk[a, 2], -l2e) for a in range(kk))
+    for d in range(1, ((kk - 1) >> 1) + 1):
+        dfw, dw = abs(pk[d - 1, 2] - pk[d, 2]), kk - d
+        dwr = abs(pk[dw - 1, 2] - pk[dw, 2])
+        for a in range(kk):
+            pair(a, d, dfw, dwr)
+    if kk > 0 and kk % 2 == 0:
+        d = kk >> 1
+        dfw = abs(pk[d - 1, 2] - pk[d, 2])
+        for a in range(d):
+            pair(a, d, dfw, dfw)
+    out = np.empty(n)
+    out[il] = gr[rk]
+    return loss, out
+
+
+def _emu_lambdaloss_topk(s, y, k, sigma, mu, lt, fast=True):
+    """lambdaloss_topk_kernel: kk arg-max rounds (score descending, index ascending), the pair of each lane from the triangular lane
+    index, the fast route's e = exp(-|x|), p = 1 / (1 + e) or e / (1 + e), log2 p = min(x, 0) log2(e) - log2(1 + e), and the gather of
+    record r's pairs from lane a (kk - 1) - a (a - 1) / 2 + b - a - 1."""
+    s, y = np.asarray(s, np.float64), np.asarray(y, np.float64)
+    n = s.size
+    idcg = sum((2.0 ** y[i] - 1.0) / math.log2(i + 2.0) for i in range(n))
+    kk = min(max(k, 0), n)
+    live, rec = np.ones(n, bool), []
+    for _ in range(kk):
+        m = s[live].max()
+        i = int(np.nonzero(live & (s == m))[0][0])
+        rec.append(i)
+        live[i] = False
+    rinv = [1.0 / (1.0 / math.log2(r + 2.0)) for r in range(64)]
+    npairs = kk * (kk - 1) // 2
+    ln2, l2e = math.log(2.0), FL.LL_LOG2_EPS
+    ga, loss = np.zeros(64), 0.0
+    for lane in range(npairs):
+        a, rem = 0, lane
+        for _ in range(11):
+            row = kk - 1 - a
+            if rem >= row and row > 0:
+                rem -= row
+                a += 1
+        b = a + 1 + rem
+        delta, dpos = abs(rinv[b - a - 1] - rinv[b - a]), abs(rinv[a] - rinv[b])
+        ya, yb = y[rec[a]], y[rec[b]]
+        if ya == yb:
+            continue
+        Ga, Gb = (2.0 ** ya - 1.0) / idcg, (2.0 ** yb - 1.0) / idcg
+        w = delta * abs(Ga - Gb) if lt == 1 else (dpos + mu * delta) * abs(Ga - Gb)
+        x = sigma * ((s[rec[a]] - s[rec[b]]) if ya > yb else (s[rec[b]] - s[rec[a]]))
+        if fast:
+            e = math.exp(-abs(x))
+            pb = 1.0 / (1.0 + e)
+            p0 = pb if x >= 0 else e * pb
+            lp = min(x, 0.0) / ln2 - math.log2(1.0 + e) if p0 >= FL.LL_EPS else l2e
+        else:
+            p0 = 1.0 / (1.0 + math.exp(-x)) if x > -700 else 0.0
+            lp = -math.log1p(math.exp(-x)) / ln2 if p0 >= FL.LL_EPS else l2e
+        z = w * lp
+        ok = z >= l2e
+        loss -= z if ok else l2e
+        g = -(w * sigma * (1.0 - p0)) / ln2 if (p0 >= FL.LL_EPS and ok) else 0.0
+        ga[lane] = g if ya > yb else -g
+    out = np.zeros(n)
+    for r in range(kk):
+        for o in range(kk):
+            if o != r:
+                a_, b_ = min(r, o), max(r, o)
+                gv = ga[a_ * (kk - 1) - ((a_ * (a_ - 1)) >> 1) + (b_ - a_ - 1)]
+                out[rec[r]] += gv if r < o else -gv
+    return loss, out
+
+
+def _emu_softrank(s, y, inv_den, top_k):
+    """approxndcg_kernel<SOFT>: both indicators of a pair from one erfc of |x| (the complement by subtraction), the circulant half
+    matrix, the symmetric flow cb phi - ca phi, the 1 / IDCG scale."""
+    s, y = np.asarray(s, np.float64), np.asarray(y, np.float64)
+    n = s.size
+    gn = 2.0 ** y - 1.0
+    idcg = sum(gn[a] / math.log2(a + 2.0) for a in range(n))
+    top = top_k if top_k and top_k > 0 else 1 << 30
+    pi = np.zeros(n)
+
+    def pairs():
+        for d in range(1, ((n - 1) >> 1) + 1):
+            for a in range(n):
+                yield a, (a + d) % n
+        if n > 0 and n % 2 == 0:
+            for a in range(n >> 1):
+                yield a, a + (n >> 1)
+
+    for a, b in pairs():
+        d = s[b] - s[a]
+        sm = 0.5 * math.erfc(abs(d) * inv_den)
+        lg = 1.0 - sm
+        pi[a] += lg if d > 0 else sm
+        pi[b] += sm if d > 0 else lg
+    ca, dcg = np.zeros(n), 0.0
+    for a in range(n):
+        if a < top:
+            v = pi[a] + 1.0
+            l2 = math.log2(v + 1.0)
+            dcg += gn[a] / l2
+            ca[a] = gn[a] / (math.log(2.0) * (1.0 + v) * l2 * l2)
+    g = np.zeros(n)
+    for a, b in pairs():
+        x = (s[b] - s[a]) * inv_den
+        phi = 0.5641895835477563 * inv_den * math.exp(-x * x)
+        flow = ca[b] * phi - ca[a] * phi
+        g[a] += flow
+        g[b] -= flow
+    return -(dcg / idcg), g / idcg
+
+
+def _emu_stlistnet(s, y, u, inv_t):
+    """listnet_kernel with unif: a = (s + -log(-log(u + 1e-20) + 1e-20)) / T, log-softmax by max shift, grad (softmax sum_py - py) / T."""
+    uu = (np.asarray(u, np.float32) + np.float32(1e-20)).astype(np.float64)
+    a = (np.asarray(s, np.float64) + -np.log(-np.log(uu) + 1e-20)) * inv_t
+    y = np.asarray(y, np.float64)
+    ea, eb = np.exp(a - a.max()), np.exp(y - y.max())
+    py = eb / eb.sum()
+    lsm = (a - a.max()) - math.log(ea.sum())
+    return -(py * lsm).sum(), (np.exp(lsm) * py.sum() - py) * inv_t
+
+
+def test_float64_emulations_of_the_kernels_agree_with_the_restatements():
+    tol = dict(rtol=1e-12, atol=1e-12)
+    for lt in (0, 1, 2):
+        for L, k, presort, kw in ((24, 24, True, dict(need_clamps=True)), (24, 7, False, {}), (24, 8, True, dict(quantise=True)), (9, 50, True, {})):
+            p, y, n, *_ = FL.lambdaloss_inputs(12, L, k, sigma=1.5, mu=LL_MU, loss_type=lt, presort=presort, seed=L + k, **kw)
+            for q in range(12):
+                sq, yq = p[q, :n[q]], y[q, :n[q]]
+                if n[q] == 0 or not (yq > 0).any():
+                    continue
+                r = FL.lambdaloss_query(sq, yq, k, 1.5, LL_MU, lt, presort, 1.0)
+                lo, gr = _emu_lambdaloss_generic(sq, yq, k, 1.5, LL_MU, lt, presort)
+                np.testing.assert_allclose(lo, r[0], **tol)
+                np.testing.assert_allclose(gr, r[2], **tol)
+                if lt and presort and k <= 11:
+                    for fast in (True, False):
+                        lo, gr = _emu_lambdaloss_topk(sq, yq, k, 1.5, LL_MU, lt, fast)
+                        np.testing.assert_allclose(lo, r[0], **tol)
+                        np.testing.assert_allclose(gr, r[2], **tol)
+    p, y, n, _ = FL.pair_inputs(12, 21, sigma=0.5, seed=3, sort_labels=True, span=8.0, every_relevant=True, quantise=True)
+    u = np.random.default_rng(4).random(p.shape).astype(np.float32)
+    u[0, :2] = (0.0, 2.0 ** -24)
+    for q in range(12):
+        sq, yq = p[q, :n[q]], y[q, :n[q]]
+        for top_k in (None, 4):
+            r = FL.softrank_query(sq, yq, 0.5, top_k, 1.0)
+            lo, gr = _emu_softrank(sq, yq, 0.5, top_k)
+            np.testing.assert_allclose(lo, r[0], **tol)
+            np.testing.assert_allclose(gr, r[2], **tol)
+        r = FL.stlistnet_query(sq, yq, u[q, :n[q]], 0.5, 1.0)
+        lo, gr = _emu_stlistnet(sq, yq, u[q, :n[q]], 0.5)
+        np.testing.assert_allclose(lo, r[0], **tol)
+        np.testing.assert_allclose(gr, r[2], **tol)
+
+
+# ---- planted faults
+def test_lambdaloss_log2_of_the_fp32_probability_fails_without_the_floor_and_passes_the_old_rule():
+    """log2 p from the fp32-rounded p (what a hardware log of p gives near 1, and what the generic kernel's comment rules out) at
+    k = L = 256.  One query of the batch is a converged one — grades 21 / sigma apart, so every winner's p rounds to 1 in fp32 and its
+    log2 to 0, where the true term is e^-x / ln2 —: its ~2e4 pair losses are all lost, all with one sign.  (Rounding p merely NEAR 1 is
+    unbiased noise, and Loss2's weights already carry ~1e-4 relative from the adjacent discounts they subtract; only the bias shows.)
+    The batch total, all the old rule saw, moves by 1e-10; the query's loss_q leaves the relative bound, and is inside it again once
+    the floor is added that the top-k kernel (at most 55 pairs) is allowed."""
+    O = _oracle()
+    p, y, n, *_ = FL.lambdaloss_inputs(8, 256, 256, loss_type=1, presort=True, seed=21, lens="full", specials=False)
+    p[0] = (21.0 * y[0] + np.random.default_rng(1).uniform(-0.5, 0.5, 256)).astype(np.float32)
+    *_, near, _, _ = FL.lambdaloss_query(p[0], y[0], 256, 1.0, LL_MU, 1, True, 1.0, detail=True)
+    assert not near.any()
+    lq, g = O.lambdaloss(p, y, k=256, sigma=1.0, mu=LL_MU, loss_type=1, presort=True, lens=n)
+    c = FL.C_LLOSS
+    r = FL.lambdaloss(p, y, n, 256, 1.0, LL_MU, 1, True, c)
+    bad = r["loss_q"].copy()
+    for q in range(8):
+        s_, y_ = p[q].astype(np.float64), y[q].astype(np.float64)
+        o = np.lexsort((np.arange(256), -s_))
+        ss, ys = s_[o], y_[o]
+        G_ = FL._gain(ys) / (FL._gain(y_) * FL._disc(256)).sum()
+        inv = np.log2(np.arange(256) + 2.0)
+        d = np.abs(np.arange(256)[:, None] - np.arange(256)[None, :])
+        w = np.where(d > 0, np.abs(inv[np.maximum(d - 1, 0)] - inv[d]), 0.0) * np.abs(G_[:, None] - G_[None, :])
+        act = ys[:, None] > ys[None, :]
+        x = ss[:, None] - ss[None, :]
+        pr = FL._sig(x)
+        ok = act & (pr >= 1e-7)
+        lp = -(np.maximum(-x, 0.0) + np.log1p(np.exp(-np.abs(x)))) / FL.LN2
+        lp32 = np.log2(pr.astype(np.float32).astype(np.float64), where=ok, out=np.zeros_like(pr))
+        bad[q] += (w * (lp - lp32))[ok].sum()
+    assert _old_rule_passes(bad.sum(), r["loss_q"].sum(), g, g)
+    FL.gate_losses(lq, g, FL.lambdaloss(p, y, n, 256, 1.0, LL_MU, 1, True, c, log_floor=True), "lambdaloss oracle", c)
+    with pytest.raises(AssertionError, match="loss_q"):
+        FL.gate_nan(bad, r["loss_q"], r["E_loss_q"], "lambdaloss fp32 log2 p loss_q", c)
+    rf = FL.lambdaloss(p, y, n, 256, 1.0, LL_MU, 1, True, c, log_floor=True)
+    FL.gate_nan(bad, rf["loss_q"], rf["E_loss_q"], "lambdaloss fp32 log2 p with the floor", c)
+
+
+def _erfc_as(x):
+    """Abramowitz & Stegun 7.1.26: erfc to 1.5e-7 absolute."""
+    t = 1.0 / (1.0 + 0.3275911 * x)
+    return t * (0.254829592 + t * (-0.284496736 + t * (1.421413741 + t * (-1.453152027 + t * 1.061405429)))) * np.exp(-x * x)
+
+
+def test_softrank_with_a_low_precision_erfc_fails_the_gate_and_passes_the_old_rule():
+    """erfc by Abramowitz & Stegun 7.1.26 (1.5e-7 absolute).  Near x = 0 that is inside the noise of a c u-relative erfc; from x ~ 1.3 on
+    it is 2 to 300 times the bound of the small indicator.  Query 0 has its best document 1.9 .. 2.6 den above 63 others (there the
+    approximation errs by +3e-8 .. +7e-8, all one way), and top_k = 1 makes its loss that document's expected rank alone."""
+    O = _oracle()
+    delta = 2.0
+    inv_den = FL.softrank_inv_den(delta)
+    p, y, n, _ = FL.pair_inputs(32, 64, sigma=inv_den, seed=17, sort_labels=True, span=8.0, every_relevant=True, lens="full", specials=False)
+    p[0, 0], y[0, 0] = 0.0, 3.0
+    p[0, 1:] = (-(1.9 + 0.7 * np.arange(63) / 62.0) / inv_den).astype(np.float32)
+    lq, g = O.softrank(p, y, delta, 1, n)
+    bad = np.empty(32)
+    for q in range(32):
+        s_, y_ = p[q].astype(np.float64), y[q].astype(np.float64)
+        x = (s_[:, None] - s_[None, :]) * inv_den
+        sm = 0.5 * _erfc_as(np.abs(x))
+        yv = np.where(x > 0, sm, 1.0 - sm)
+        np.fill_diagonal(yv, 0.0)
+        pi = 1.0 + yv.sum(1)
+        bad[q] = -((FL._gain(y_[0]) / np.log2(pi[0] + 1.0)) / (FL._gain(y_) * FL._disc(64)).sum())
+    c = FL.C_APPROX
+    r = FL.softrank(p, y, n, delta, 1, c)
+    FL.gate_losses(lq, g, r, "softrank oracle", c)
+    assert _old_rule_passes(bad.sum(), r["loss_q"].sum(), g, g)
+    with pytest.raises(AssertionError, match="loss_q"):
+        FL.gate_losses(bad, g, r, "softrank low-precision erfc", c)
+
+
+def test_stlistnet_gumbel_noise_through_a_low_precision_log_fails_the_gate_and_passes_the_old_rule():
+    """The inner log of the Gumbel draw with 2^-17.5 (5e-6) relative error, of either sign: every noise value moves by 5e-6 absolute.
+    The old rule lets a gradient element move by 1e-5 of itself plus 1e-6 of the largest; the gate's bound on the same elements is
+    about half of what they move."""
+    O = _oracle()
+    p, y, u, n = FL.stlistnet_inputs(48, 64, seed=19)
+    lq, g = O.stlistnet(p, y, u, 1.0, n)
+    rng = np.random.default_rng(2)
+    uu = (u + np.float32(1e-20)).astype(np.float64)
+    gum = -(np.log(-(np.log(uu) * (1.0 + 2.0 ** -17.5 * rng.choice([-1.0, 1.0], size=u.shape))) + 1e-20))
+    bad_l, bad_g = np.zeros(48), np.zeros((48, 64))
+    for q in range(48):
+        if n[q]:
+            bad_l[q], _, bad_g[q, :n[q]], _ = FL.listnet_query(p[q, :n[q]].astype(np.float64) + gum[q, :n[q]], y[q, :n[q]], 1.0)
+    c = FL.C_LIST
+    r = FL.stlistnet(p, y, u, n, 1.0, c)
+    FL.gate_losses(lq, g, r, "stlistnet oracle", c)
+    assert _old_rule_passes(bad_l.sum(), r["loss_q"].sum(), bad_g, r["grad"])
+    with pytest.raises(AssertionError):
+        FL.gate_losses(bad_l, bad_g, r, "stlistnet low-precision log", c)
+
+
+def test_planted_exact_and_nan_faults_fail_the_new_gates():
+    O = _oracle()
+    c = FL.C_LLOSS
+    p, y, n, *_ = FL.lambdaloss_inputs(24, 32, 5, loss_type=1, presort=True, seed=23)
+    lq, g = O.lambdaloss(p, y, k=5, sigma=1.0, mu=LL_MU, loss_type=1, presort=True, lens=n)
+    r = FL.lambdaloss(p, y, n, 5, 1.0, LL_MU, 1, True, c, log_floor=True)
+    FL.gate_losses(lq, g, r, "lambdaloss oracle", c)
+    q = 10
+    beyond = int(np.argsort(-p[q, :n[q]].astype(np.float64), kind="stable")[7])        # ranked eighth: beyond k = 5
+    assert r["grad"][q, beyond] == 0 and r["E_grad"][q, beyond] == 0
+    bad = g.copy()
+    bad[q, beyond] = 1e-9
+    with pytest.raises(AssertionError, match="grad"):
+        FL.gate_losses(lq, bad, r, "a 1e-9 gradient beyond k", c)
+    # NDCG_Loss1 with a finite loss on the query without a relevant document (what the kernel returned before this gate)
+    lq1, g1 = O.lambdaloss(p, y, k=5, sigma=1.0, mu=LL_MU, loss_type=0, presort=True, lens=n)
+    r1 = FL.lambdaloss(p, y, n, 5, 1.0, LL_MU, 0, True, c, log_floor=True)
+    FL.gate_losses(lq1, g1, r1, "lambdaloss1 oracle", c)
+    assert np.isnan(r1["loss_q"][2])
+    bad = lq1.copy()
+    bad[2] = 25 * 26.575424
+    with pytest.raises(AssertionError, match="loss_q"):
+        FL.gate_losses(bad, g1, r1, "Loss1 finite where the reference is NaN", c)
+    # SoftRank: NaN on the zero-length query
+    ps, ys, ns, _ = FL.pair_inputs(24, 32, sigma=0.25, seed=29, sort_labels=True, span=8.0)
+    ls, gs = O.softrank(ps, ys, 2.0, None, ns)
+    rs = FL.softrank(ps, ys, ns, 2.0, None, FL.C_APPROX)
+    FL.gate_losses(ls, gs, rs, "softrank oracle", FL.C_APPROX)
+    bad = ls.copy()
+    assert ns[4] == 0 and bad[4] == 0
+    bad[4] = np.nan
+    with pytest.raises(AssertionError, match="loss_q"):
+        FL.gate_losses(bad, gs, rs, "softrank NaN on a zero-length query", FL.C_APPROX)
+
+
+def test_oracle_follows_the_reference_on_a_query_without_a_relevant_document():
+    """tests/golden/losses_norel.npz, the reference's own outputs: NDCG_Loss1 is NaN, loss and every gradient; NDCG_Loss2 / Loss2++ are 0
+    — with a NaN gradient in the reference (autograd's 0 * NaN through the unselected entries), where the oracle and the kernels keep
+    the derivative of the constant, 0 —; SoftRank is NaN throughout."""
+    O = _oracle()
+    fams = G._load("losses_norel.npz")
+    for name, case in sorted(fams["lambdaloss"].items()):
+        lt = int(case["loss_type"])
+        assert np.isnan(case["grad"]).all() and np.isnan(case["loss"]) == (lt == 0) and (lt == 0 or float(case["loss"]) == 0), name
+        lq, g = O.lambdaloss(case["preds"], case["labels"], k=int(case["k"]), sigma=1.0, mu=float(case["mu"]), loss_type=lt, presort=True)
+        assert (np.isnan(g).all() and np.isnan(lq[0])) if lt == 0 else ((g == 0).all() and lq[0] == 0), name
+    for name, case in sorted(fams["softrank"].items()):
+        one = case["preds"].shape[1] == 1                      # one document: no pair, the gradient is exactly 0
+        assert "one_doc" in name if one else "one_doc" not in name
+        assert ((case["grad"] == 0).all() if one else np.isnan(case["grad"]).all()) and np.isnan(case["loss"]), name
+        lq, g = O.softrank(case["preds"], case["labels"], float(case["delta"]), int(case["top_k"]) or None)
+        assert ((g == 0).all() if one else np.isnan(g).all()) and np.isnan(lq[0]), name
+        r = FL.softrank(case["preds"], case["labels"], None, float(case["delta"]), int(case["top_k"]), FL.C_APPROX)
+        assert ((r["grad"] == 0).all() if one else np.isnan(r["grad"]).all()) and np.isnan(r["loss_q"][0]), name
+    assert any("one_doc" in name for name in fams["softrank"])
+
+
+def test_a_nan_score_gives_a_nan_list_where_the_reference_ranks_it_first():
+    """tests/golden/losses_nanscore.npz, the reference's own outputs on lists with fewer than k real scores: torch.sort ranks a NaN score
+    first, its differences count as 0 and carry no gradient, and every output is finite.  The product deviates, on purpose (header of
+    csrc/lambdaloss.hip): such a list has no ranking, so its loss and the gradient of every document are NaN — in the oracle and in the
+    restatement that the kernels are gated against."""
+    O = _oracle()
+    cases = G._load("losses_nanscore.npz")["lambdaloss"]
+    assert len(cases) == 8
+    for name, case in sorted(cases.items()):
+        p, y, k, lt = case["preds"], case["labels"], int(case["k"]), int(case["loss_type"])
+        real = int((~np.isnan(p)).sum())
+        assert 0 < real < 5 and np.isfinite(case["loss"]) and np.isfinite(case["grad"]).all() and (case["grad"][np.isnan(p)] == 0).all(), name
+        first = torch.sort(torch.from_numpy(p), dim=1, descending=True)[1][0, :p.shape[1] - real].numpy()
+        assert np.isnan(p[0, first]).all(), name                 # the reference's order: every NaN before the best real score
+        lq, g = O.lambdaloss(p, y, k=k, sigma=1.0, mu=float(case["mu"]), loss_type=lt, presort=True)
+        r = FL.lambdaloss(p, y, None, k, 1.0, float(case["mu"]), lt, True, FL.C_LLOSS)
+        assert np.isnan(lq[0]) and np.isnan(g).all() and np.isnan(r["loss_q"][0]) and np.isnan(r["grad"]).all() and (r["E_grad"] == 0).all(), name
+        FL.gate_losses(lq, g, r, name, FL.C_LLOSS)
+    # a NaN score in one list leaves its neighbours alone; padding stays 0
+    p, y, n, *_ = FL.lambdaloss_inputs(12, 16, 5, loss_type=2, presort=True, seed=3)
+    clean = FL.lambdaloss(p, y, n, 5, 1.0, LL_MU, 2, True, FL.C_LLOSS)
+    q = int(np.argmax(n >= 2))
+    p[q, 1] = np.nan
+    lq, g = O.lambdaloss(p, y, k=5, sigma=1.0, mu=LL_MU, loss_type=2, presort=True, lens=n)
+    r = FL.lambdaloss(p, y, n, 5, 1.0, LL_MU, 2, True, FL.C_LLOSS, log_floor=True)
+    FL.gate_losses(lq, g, r, "one NaN score", FL.C_LLOSS)
+    others = np.arange(12) != q
+    assert np.array_equal(r["grad"][others], clean["grad"][others], equal_nan=True) and np.isnan(r["grad"][q, :n[q]]).all()
+    assert (g[q, n[q]:] == 0).all() and np.isnan(lq[q])

@@ -1,5 +1,5 @@
-"""GPU: the ranking-loss kernels (csrc/pairwise.hip + ptr_ring.h, csrc/approxndcg.hip, csrc/listwise.hip) against float64 with
-ELEMENT-WISE error bounds (tests/f64_loss_bounds.py) on structured inputs.  The C ABI is called directly, so that every output is gated:
+"""GPU: the ranking-loss kernels (csrc/pairwise.hip + ptr_ring.h, csrc/approxndcg.hip, csrc/listwise.hip, csrc/lambdaloss.hip) against
+float64 with ELEMENT-WISE error bounds (tests/f64_loss_bounds.py) on structured inputs.  The C ABI is called directly, so that every output is gated:
 each query's loss_q, the batch total loss_out, every gradient element (padded slots exactly 0), and ApproxNDCG's dcg_q, inv_idcg_q and
 scale_out.  Outputs start as NaN, so a slot the kernel never writes fails.
 
@@ -273,3 +273,190 @@ def test_listwise_against_float64(case):
         FL.gate_losses(got["loss_q"], got["grad"], ref, f"rankmse {_list_id(case)}", c)
         tot, E = FL.batch_total(ref, c, 1.0 / Bn)
         FL.gate_nan([got["loss_out"]], [tot], [E], f"rankmse {_list_id(case)} loss_out", c)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- LambdaLoss
+# (B, L, k, loss type 0 Loss1 / 1 Loss2 / 2 Loss2++, presort, sigma, flags): q quantised + 1e3 offset, u unaligned rows, c both clamps
+# populated (k >= L), x scores x 30 (the top-k kernel's libm route), n NaN scores in three lists (fewer than k documents with a rank by
+# score: such a list's outputs are NaN).  tests/test_abi_cpu.py restates ptr_lambdaloss_fwd_bwd's route.
+LAMBDALOSS_GENERIC_CASES = [
+    (37, 20, 1, 0, 1, 1.0, ""),          # (64, 1): Loss1, k = 1 (the diagonal alone)
+    (38, 64, 64, 1, 0, 1.0, "c"),        # (64, 1): k = L, even circulant walk, labels sorted by the kernel
+    (33, 128, 2, 2, 0, 2.0, ""),         # (64, 2): k = 2
+    (30, 128, 128, 2, 1, 1.0, "c"),      # (64, 2): k = L, Loss2++ with both clamps
+    (21, 256, 37, 0, 1, 1.0, "q"),       # (64, 4): Loss1, odd k, ties + offset
+    (13, 300, 600, 1, 1, 2.0, ""),       # (256, 2): k = 2 L > n
+    (10, 512, 512, 0, 0, 1.0, "c"),      # (256, 2): Loss1 at k = L with both clamps
+    (7, 700, 40, 2, 1, 1.0, ""),         # (256, 4): even k
+    (9, 1500, 5, 0, 1, 1.0, ""),         # (256, 8): Loss1, k = 5
+    (7, 2100, 101, 1, 0, 1.0, ""),       # (256, 16): odd k
+    (18, 64, 12, 1, 1, 1.0, ""),         # top-k eligible but k = 12
+    (19, 63, 5, 2, 1, 1.0, ""),          # ... but L % 4 != 0
+    (17, 128, 5, 1, 1, 1.0, "u"),        # ... but unaligned rows
+    (22, 64, 5, 0, 1, 1.0, ""),          # ... but Loss1
+    (23, 256, 5, 2, 0, 1.0, ""),         # ... but presort = 0
+    (19, 64, 20, 1, 1, 1.0, "n"),        # NaN scores, one wavefront per list
+    (13, 300, 7, 2, 0, 1.0, "n"),        # NaN scores, four wavefronts per list, labels sorted by the kernel
+]
+LAMBDALOSS_TOPK_CASES = [
+    (37, 8, 5, 2, 1, 1.0, ""),           # V 1: lists shorter than k (the pair table rebuilt)
+    (29, 64, 1, 1, 1, 1.0, ""),          # k = 1: no pair
+    (41, 64, 11, 1, 1, 1.0, "q"),        # k = 11 (55 pairs), ties across lanes and inside a lane's four documents
+    (26, 256, 2, 2, 1, 2.0, ""),         # full lists (lens == 256: the mask-free path) among ragged ones
+    (27, 64, 5, 2, 1, 2.5, "x"),         # |sigma ds| > 80: the libm route and p < eps
+    (14, 512, 5, 1, 1, 1.0, ""),         # V 2, with full lists
+    (11, 1024, 11, 2, 1, 1.0, "q"),      # V 4
+    (21, 8, 5, 1, 1, 1.0, "n"),          # V 1: lists with 2, 0 and n - 1 real scores (the selection ends early)
+    (13, 512, 5, 2, 1, 1.0, "n"),        # V 2: the same
+]
+LAMBDALOSS_PERSISTENT = (3 * 8192 + 17, 8, 5, 2, 1, 1.0, "")      # every wavefront walks >= 3 queries: 8192 is all the device can hold
+MU = 5.0
+
+
+def _ll_id(c):
+    return f"{c[0]}x{c[1]}-k{c[2]}-t{c[3]}-pre{c[4]}-s{c[5]:g}" + (f"-{c[6]}" if c[6] else "")
+
+
+def lambdaloss_inputs(case):
+    """The inputs of a LAMBDALOSS_*_CASES entry (tests/test_abi_cpu.py computes the top-k kernel's route from them)."""
+    Bn, L, k, lt, pre, sigma, fl = case
+    out = FL.lambdaloss_inputs(Bn, L, k, sigma=sigma, mu=MU, loss_type=lt, presort=bool(pre), need_clamps="c" in fl,
+                               scale=30.0 if "x" in fl else 1.0, seed=L + 3 * Bn + lt, quantise="q" in fl,
+                               offset=1000.0 if "q" in fl else 0.0, mix="yahoo" if (Bn + L) % 2 else "mslr")
+    if "n" in fl:
+        # three lists beyond the specials with at least four documents: two real scores left (fewer than k), none, all but one
+        p, n = out[0], out[2]
+        qa, qb, qc = [q for q in range(8, Bn) if n[q] >= 4][:3]
+        p[qa, 1:n[qa] - 1] = np.nan
+        p[qb, :n[qb]] = np.nan
+        p[qc, 1] = np.nan
+        assert min(k, int(n[qa])) > 2
+    return out
+
+
+def _run_lambdaloss(case, p, y, n):
+    _, _, k, lt, pre, sigma, fl = case
+    return run("ptr_lambdaloss_fwd_bwd", p, y, n, k, C.c_float(sigma), C.c_float(MU), lt, pre, unaligned="u" in fl)
+
+
+@pytest.mark.parametrize("case", LAMBDALOSS_GENERIC_CASES, ids=_ll_id)
+def test_lambdaloss_generic_against_float64(case):
+    Bn, L, k, lt, pre, sigma, fl = case
+    p, y, n, *_ = lambdaloss_inputs(case)
+    got = _run_lambdaloss(case, p, y, n)
+    ref = FL.lambdaloss(p, y, n, k, sigma, MU, lt, bool(pre), FL.C_LLOSS)
+    assert "n" not in fl or np.isnan(ref["loss_q"]).sum() == 3 + (lt == 0)
+    _check(got, ref, f"lambdaloss generic {_ll_id(case)}", FL.C_LLOSS, True)
+
+
+@pytest.mark.parametrize("case", LAMBDALOSS_TOPK_CASES, ids=_ll_id)
+def test_lambdaloss_topk_against_float64(case):
+    Bn, L, k, lt, pre, sigma, fl = case
+    p, y, n, *_ = lambdaloss_inputs(case)
+    got = _run_lambdaloss(case, p, y, n)
+    ref = FL.lambdaloss(p, y, n, k, sigma, MU, lt, True, FL.C_LLOSS, log_floor=True)
+    assert "n" not in fl or np.isnan(ref["loss_q"]).sum() == 3
+    _check(got, ref, f"lambdaloss topk {_ll_id(case)}", FL.C_LLOSS, True)
+
+
+def lambdaloss_persistent_inputs():
+    """256 distinct ragged queries (lengths 0..8, so kk changes between a wavefront's consecutive queries) tiled in a shuffled order.
+    Returns (preds, labels, lens, order [B]: the distinct query behind each row)."""
+    Bn, L, k, lt, pre, sigma, _ = LAMBDALOSS_PERSISTENT
+    p, y, n, *_ = FL.lambdaloss_inputs(256, L, k, sigma=sigma, mu=MU, loss_type=lt, presort=True, seed=11)
+    g = np.random.default_rng(12)
+    n = (np.arange(256) % 9).astype(np.int32)
+    g.shuffle(n)
+    for q in range(256):                                 # the screen saw other lengths: no entry of the lists as they now are nears a clamp
+        assert not FL.lambdaloss_query(p[q, :n[q]], y[q, :n[q]], k, sigma, MU, lt, True, 1.0, detail=True)[4].any(), q
+    order = g.permutation(Bn) % 256
+    return p[order], y[order], n[order], order
+
+
+def test_lambdaloss_topk_persistent_walk_against_float64():
+    Bn, L, k, lt, pre, sigma, _ = LAMBDALOSS_PERSISTENT
+    p, y, n, order = lambdaloss_persistent_inputs()
+    got = _run_lambdaloss(LAMBDALOSS_PERSISTENT, p, y, n)
+    _, first = np.unique(order, return_index=True)
+    assert len(first) == 256
+    ref = FL.lambdaloss(p, y, n, k, sigma, MU, lt, True, FL.C_LLOSS, first, log_floor=True)
+    _check(got, ref, "lambdaloss topk persistent", FL.C_LLOSS, False)
+    src = first[order]                                   # every copy is bit-identical to the first copy of its query
+    assert np.array_equal(got["loss_q"], got["loss_q"][src], equal_nan=True)
+    assert np.array_equal(got["grad"], got["grad"][src], equal_nan=True)
+    assert (got["grad"][np.arange(L)[None, :] >= n[:, None]] == 0).all()
+    # the whole batch's total (ptr_sum_f32 at this B): every row's float64 loss and bound are those of the first copy of its query
+    lq, E = ref["loss_q"][order], ref["E_loss_q"][order]
+    assert np.isfinite(lq).all()
+    FL.gate_nan(np.array([got["loss_out"]]), np.array([lq.sum()]), np.array([E.sum() + FL.C_LLOSS * FL.U * np.abs(lq).sum()]),
+                "lambdaloss topk persistent loss_out", FL.C_LLOSS)
+
+
+@pytest.mark.parametrize("L,k,lt", [(64, 5, 2), (64, 64, 0), (300, 40, 1)])
+def test_lambdaloss_loss_out_against_float64(L, k, lt):
+    """The batch total as a value: every query has a relevant document (one without makes Loss1's total NaN), one has length 0."""
+    p, y, n, _ = FL.pair_inputs(23, L, seed=L + 2, every_relevant=True, sort_labels=True)
+    n[4] = 0
+    got = run("ptr_lambdaloss_fwd_bwd", p, y, n, k, C.c_float(1.0), C.c_float(MU), lt, 1)
+    ref = FL.lambdaloss(p, y, n, k, 1.0, MU, lt, True, FL.C_LLOSS, log_floor=k <= 11)
+    assert np.isfinite(ref["loss_q"]).all() and ref["loss_q"][4] == 0
+    _check(got, ref, f"lambdaloss loss_out {L}-k{k}-t{lt}", FL.C_LLOSS, True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- SoftRank
+# (B, L, delta, top_k (0: none), 1e3 offset): one case per dispatch_tiling form
+SOFTRANK_CASES = [
+    (37, 50, 2.0, 0, False),          # (64, 1)
+    (33, 128, 0.3, 10, False),        # (64, 2)
+    (21, 256, 2.0, 300, False),       # (256, 1), top_k > n
+    (13, 512, 0.3, 0, True),          # (256, 2), offset
+    (7, 700, 2.0, 10, False),         # (256, 4)
+    (6, 1500, 0.3, 0, False),         # (256, 8)
+    (5, 2100, 2.0, 10, False),        # (256, 16)
+]
+
+
+def _soft_id(c):
+    return f"{c[0]}x{c[1]}-d{c[2]:g}-k{c[3]}" + ("-offset" if c[4] else "")
+
+
+def softrank_inputs(Bn, L, delta, off, **kw):
+    """Label-sorted lists whose (s_i - s_j) / den spans the indicator's whole range, with the specials of pair_inputs."""
+    p, y, n, _ = FL.pair_inputs(Bn, L, sigma=FL.softrank_inv_den(delta), seed=L + 5 * Bn, offset=1000.0 if off else 0.0, sort_labels=True,
+                                span=8.0, **kw)
+    return p, y, n
+
+
+@pytest.mark.parametrize("case", SOFTRANK_CASES, ids=_soft_id)
+def test_softrank_against_float64(case):
+    Bn, L, delta, top_k, off = case
+    p, y, n = softrank_inputs(Bn, L, delta, off)
+    got = run("ptr_softrank_fwd_bwd", p, y, n, C.c_float(delta), top_k)
+    ref = FL.softrank(p, y, n, delta, top_k, FL.C_APPROX)
+    assert ref["loss_q"][4] == 0 and (Bn < 6 or np.isnan(ref["loss_q"][2]))
+    _check(got, ref, f"softrank {_soft_id(case)}", FL.C_APPROX, True)
+
+
+def test_softrank_loss_out_with_a_zero_length_query_against_float64():
+    """The batch total as a value: every query has a relevant document, one has length 0 (loss 0, not 0 * inf)."""
+    p, y, n = softrank_inputs(23, 70, 2.0, False, every_relevant=True)
+    n[4] = 0
+    got = run("ptr_softrank_fwd_bwd", p, y, n, C.c_float(2.0), 0)
+    ref = FL.softrank(p, y, n, 2.0, 0, FL.C_APPROX)
+    assert np.isfinite(ref["loss_q"]).all() and ref["loss_q"][4] == 0
+    _check(got, ref, "softrank loss_out", FL.C_APPROX, True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- STListNet
+# (B, L, temperature, 1e3 offset, unaligned rows); one kernel form (listnet_kernel with the Gumbel prologue)
+STLISTNET_CASES = [(37, 64, 1.0, False, False), (11, 63, 2.0, True, False), (9, 128, 0.5, False, True), (6, 1500, 1.0, False, False)]
+
+
+@pytest.mark.parametrize("case", STLISTNET_CASES, ids=lambda c: f"{c[0]}x{c[1]}-T{c[2]:g}" + ("-offset" if c[3] else "") + ("-unaligned" if c[4] else ""))
+def test_stlistnet_against_float64(case):
+    Bn, L, T, off, unal = case
+    p, y, u, n = FL.stlistnet_inputs(Bn, L, seed=L + Bn, offset=1000.0 if off else 0.0)
+    assert n[3] == 1 and n[4] == 0
+    got = run("ptr_stlistnet_fwd_bwd", p, y, n, C.c_float(T), unif=u, unaligned=unal)
+    ref = FL.stlistnet(p, y, u, n, T, FL.C_LIST)
+    _check(got, ref, f"stlistnet {Bn}x{L}-T{T:g}", FL.C_LIST, True)
