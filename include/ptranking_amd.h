@@ -222,6 +222,67 @@ int ptr_divprob_fwd_bwd(const float *mus, const float *vars, const float *rele, 
  * queries at L = 128): every supported L fits. */
 int ptr_divprob_expected_ranks(const float *mus, const float *vars, const int32_t *lens, int B, int L, float *ranks, void *stream);
 
+/* ---- The tree frame's custom objectives (csrc/tree.hip).  The two symbols below are ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
+ * They compute what a LightGBM custom objective returns every boosting round — a gradient and a Hessian per document — and nothing else of
+ * the tree frame: the boosting stays in LightGBM.
+ * Data model: RAGGED, LightGBM's layout.  preds and labels are flat fp32 arrays over all documents, offsets int64 [B + 1] (device) the
+ * running sum of the group sizes: query q owns [offsets[q], offsets[q + 1]).  grad and hess are flat fp32 arrays of the same length.  There
+ * is no padding.  queries (int32 [nq], device, nullable) lists the queries to evaluate; NULL means all B of them, and then nq must equal B.
+ * max_len is the longest list among the launched queries (the host knows it): it sizes the LDS rows and selects the form — 16 queries per
+ * workgroup up to 16 documents, one wavefront per query up to 128, one workgroup per query up to PTR_MAX_LIST_LEN — so a caller with mixed
+ * lengths buckets its queries by length once and launches each class through `queries`.  Results do not depend on the form, on the other
+ * queries of the launch or on the run: every sum has a fixed order that depends on the query alone.  A launched query longer than max_len is
+ * the caller's error and gets NaN; a query of 0 documents writes nothing; documents of queries that are not launched are not written.
+ *
+ * ptr_tree_pair_grad_hess replaces per_query_gradient_hessian_lambda (ptranking/ltr_tree/util/lightgbm_util.py:120-183, a Python loop over
+ * document pairs) with triu_indice (:17-60), get_delta_ndcg / get_delta_gains / ideal_dcg (:82-118), and the loop over `group` of the four
+ * RankNet / LambdaRank wrappers (:185-302).  Per document i, over the partners j != i of its query that pass the pair mask, d = s_i - s_j:
+ *     grad_i = sum_j w_ij epsilon (sigmoid(epsilon d) - (1 + clip(y_i - y_j, -1, 1)) / 2)
+ *     h_ij   = max(epsilon^2 sigmoid(d) (1 - sigmoid(d)), 1e-16) w_ij
+ *   pair_type  PTR_TREE_PAIRS_ALL / _NOTIES (labels differ) / _NO00 (not both 0) / _00 (both 0): the four masks of triu_indice.
+ *   weighting  PTR_TREE_W_NONE: w = 1.  _DELTA_NDCG: |G_i - G_j| |D_i - D_j|, G = (2^y - 1) / IDCG, D = 1 / log2(rank + 2), rank 0-based in
+ *              predicted order.  _DELTA_GAIN: |g_i - g_j|, g = 2^y - 1.
+ *              Finding 1: the reference's lambdarank wrappers (:244-302) pass weighting=True, and `True in ['DeltaNDCG', 'DeltaGain']` is
+ *              false (:149): its "lambdarank" objective is UNWEIGHTED RankNet over NoTies pairs.  That is PTR_TREE_W_NONE here; the weights
+ *              are what the per-query function computes when it is called with weighting='DeltaNDCG' / 'DeltaGain'.
+ *   hessian    PTR_TREE_HESS_REFERENCE: hess_i = sum_j h_ij over the partners ranked below i minus the sum over those ranked above it.
+ *              Finding 2: the reference adds +h to the higher-ranked document of a pair and -h to the lower one (:175-178), so its
+ *              Hessian is negative for low-ranked documents.  _SUM: hess_i = sum_j h_ij, what LightGBM and XGBoost do; never negative.
+ *              _CONSTANT: the reference's FIRST_ORDER: hess is filled with 1.0 and no pair Hessian is evaluated.
+ *              Finding 3: the Hessian's sigmoid is taken at epsilon 1 whatever epsilon is (:171), and the 1e-16 floor applies before the weight.
+ *   Finding 4 (group.astype(np.int), which numpy >= 1.24 refuses) concerns the Python wrappers only: offsets are int64 here.
+ *   Finding 5: np.flip(np.argsort(preds)) (:130) breaks ties in an implementation-defined way.  Here a higher score ranks first and equal
+ *              scores rank by original index (the rule of ptr_lambdarank_fwd_bwd): it decides D and the Hessian's sign, e.g. on the
+ *              all-equal scores of the first boosting round.
+ *   Edge rules, as the reference: one document: grad = hess = 0.  No pair passes the mask (all-equal labels under NOTIES): 0 under every
+ *   weighting.  No relevant document with pairs under _DELTA_NDCG: NaN (the normalised gains are 0 / 0).  A NaN score or label: NaN grad and
+ *   hess on every document of that list and of no other (hess stays 1.0 under _CONSTANT).
+ *
+ * ptr_tree_listnet_grad_hess replaces per_query_gradient_hessian_listnet (:308-330) and the loop of its two wrappers (:333-389):
+ *     grad = softmax(s) - softmax(gain), hess = p (1 - p), p = softmax(s); gain = 2^y - 1 (PTR_TREE_GAIN_POWER) or y (PTR_TREE_GAIN_LABEL).
+ *   hessian: _REFERENCE and _SUM coincide; _CONSTANT fills 1.0.  One document: grad 0, hess 0 (p = 1).  Findings 4 and 5 do not reach it
+ *   (nothing is sorted), nor do 1 to 3.
+ *
+ * PTR_ERR_INVALID_ARG (before any launch): a NULL pointer while nq > 0, a negative size, queries == NULL with nq != B, epsilon < 0 or NaN, an
+ * enum value out of range.  PTR_ERR_UNSUPPORTED: max_len > PTR_MAX_LIST_LEN.  LDS per query: 4 round_up(max_len, 4) bytes times 2 (no weights),
+ * 3 (_DELTA_GAIN, ListNet) or 4 (_DELTA_NDCG): 64 KiB at 4096 documents. */
+#define PTR_TREE_PAIRS_ALL 0
+#define PTR_TREE_PAIRS_NOTIES 1
+#define PTR_TREE_PAIRS_NO00 2
+#define PTR_TREE_PAIRS_00 3
+#define PTR_TREE_W_NONE 0
+#define PTR_TREE_W_DELTA_NDCG 1
+#define PTR_TREE_W_DELTA_GAIN 2
+#define PTR_TREE_HESS_REFERENCE 0
+#define PTR_TREE_HESS_SUM 1
+#define PTR_TREE_HESS_CONSTANT 2
+#define PTR_TREE_GAIN_POWER 0
+#define PTR_TREE_GAIN_LABEL 1
+int ptr_tree_pair_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries, int nq, int max_len,
+                            int pair_type, int weighting, float epsilon, int hessian, float *grad, float *hess, void *stream);
+int ptr_tree_listnet_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries, int nq, int max_len,
+                               int gain_type, int hessian, float *grad, float *hess, void *stream);
+
 /* Device tie-shuffled label-descending order (the role of arg_shuffle_ties, sampling_utils.py:13-28) from a
  * counter-based RNG: same distribution, NOT the torch.randperm stream (not parity-checked, statistically tested). */
 int ptr_shuffle_ties_order(const float *labels, const int32_t *lens, int B, int L, uint64_t seed, int64_t *perm,

@@ -7,6 +7,8 @@
     batching    PaddedQueryBatches: device-resident padded query batches (+ lens) replacing the reference's loader stack
     diversity   the diversification frame: DALETOR (alpha-DCG loss kernel), DivProbRanker (Gaussian pairwise-rank loss kernel),
                 alpha-nDCG / ERR-IA / nERR-IA on the device, DivQueryBatches
+    tree        the tree frame's custom LightGBM objectives (RankNet / LambdaRank / ListNet gradient + Hessian over ragged groups):
+                TreeObjective, the six drop-in functions, install_tree(); the boosting itself stays in LightGBM
     dp          data-parallel gradient exchange (one RCCL all-reduce per step)
     install()   rebinds the ranker names of RANKER_NAMES (RankNet, LambdaRank, LambdaLoss, ApproxNDCG, ListNet, ListMLE, STListNet,
                 RankCosine, RankMSE, SoftRank, WassRank) inside an installed ptranking so LTREvaluator uses them unchanged; a WassRank
@@ -16,11 +18,12 @@
 The only compute implementation is the HIP library ptranking_amd/libptranking_amd.so (C ABI: include/ptranking_amd.h);
 there is no CPU fallback.  Build it with `python -m ptranking_amd.build`.
 """
-from . import _lib, batching, diversity, dp, functional, host, rankers, scorer   # noqa: F401
+from . import _lib, batching, diversity, dp, functional, host, rankers, scorer, tree   # noqa: F401
 from .batching import PaddedQueryBatches            # noqa: F401
 from . import letor                                   # noqa: F401
 from .host import LABEL_TYPE, DeviceEvaluator       # noqa: F401
-from .install import install, install_diversification, uninstall   # noqa: F401
+from .install import install, install_diversification, install_tree, uninstall   # noqa: F401
+from .tree import TreeObjective                     # noqa: F401
 from .diversity import DALETOR, DIV_RANKER_NAMES, EXTRA_DIV_RANKER_NAMES, DivProbRanker, DivQueryBatches     # noqa: F401
 from .rankers import (ApproxNDCG, LambdaLoss, LambdaRank, ListMLE, ListNet, RankNet, STListNet, RankCosine, RankMSE, SoftRank, WassRank, DASALC, MDPRank,  # noqa: F401
                       DEFAULT_PARAS, EXTRA_RANKER_NAMES, RANKER_NAMES, make_ranker_classes)

@@ -1,0 +1,320 @@
+// The tree frame's custom objectives (the reference's ltr_tree frame): the gradient AND the Hessian per document that LightGBM asks a custom
+// objective for every boosting round, over LightGBM's ragged layout (flat arrays + group sizes).  The boosting itself stays in LightGBM.
+//
+// Reference: ptranking/ltr_tree/util/lightgbm_util.py:120-183 (per_query_gradient_hessian_lambda: a Python loop over document pairs),
+//            :17-60 (triu_indice: the four pair masks), :82-118 (ideal_dcg, get_delta_gains, get_delta_ndcg), :308-330
+//            (per_query_gradient_hessian_listnet), :185-389 (the six wrappers that walk `group`).
+//
+// What reading the reference turned up (include/ptranking_amd.h states which entry point each concerns; DESIGN.md has the whole list):
+//   1. the lambdarank wrappers pass weighting=True, which the per-query function never recognises ('True in [DeltaNDCG, DeltaGain]' is
+//      false): the weights are a separate argument here (PTR_TREE_W_*), and the drop-in passes PTR_TREE_W_NONE;
+//   2. the Hessian is signed by rank order: for a pair at sorted positions r < c, hess[r] += h and hess[c] -= h (PTR_TREE_HESS_REFERENCE);
+//      PTR_TREE_HESS_SUM adds h to both, as LightGBM and XGBoost do;
+//   3. the Hessian's sigmoid ignores epsilon: epsilon^2 s(d)(1 - s(d)) with s at epsilon 1, floored at 1e-16 BEFORE the weight;
+//   5. the reference's sort is not stable; here a higher score ranks first and equal scores rank by original index, the rule
+//      ptr_lambdarank_fwd_bwd documents.
+//
+// Closed form per document i, over the partners j != i of its query that pass the pair mask (d = s_i - s_j, s() the logistic function):
+//   grad_i = sum_j w_ij epsilon (s(epsilon d) - (1 + clip(y_i - y_j, -1, 1)) / 2)
+//   h_ij   = max(epsilon^2 s(d) (1 - s(d)), 1e-16) w_ij
+//   hess_i = sum_j h_ij [j ranks below i] - sum_j h_ij [j ranks above i]     (REFERENCE)         hess_i = sum_j h_ij     (SUM)
+//   w_ij   = 1 | |G_i - G_j| |D_i - D_j| (G = (2^y - 1) / IDCG, D = 1 / log2(rank + 2), rank 0-based in predicted order) | |g_i - g_j| (g = 2^y - 1)
+// Both sums are symmetric in (i, j), so ONE thread owns document i (strided where the list is longer than the group), walks all its partners
+// in index order and writes its own two results: no atomics, nothing of size n x n, and the order of every floating-point addition depends
+// on the query alone — not on the form that runs it, the batch around it or the launch.  The group-wide sums (IDCG, the softmax
+// normalisers) are a halving tree over LDS whose shape depends on n alone, for the same reason.
+//
+// Forms (G threads per query, 256 / G queries per workgroup), chosen by the longest list of the launch:
+//   G = 16   n <= 16      sixteen short queries per workgroup
+//   G = 64   n <= 128     one wavefront per query, four per workgroup
+//   G = 256  n <= 4096    one workgroup per query (PTR_MAX_LIST_LEN)
+// The host buckets its queries by length class once and launches each class through the `queries` index list (ptranking_amd/tree.py).
+// LDS per query: K rows of round_up(max_len, 4) floats — scores | labels | (normalised) gains | discounts; K = 2 (no weights), 3 (DeltaGain),
+// 4 (DeltaNDCG): at most 16 round_up(n, 4) bytes.  ListNet: scores | gains | the tree's row.
+#include "ptr_device.h"
+
+namespace ptr {
+
+__host__ __device__ constexpr int tree_rows(int W) { return W == PTR_TREE_W_DELTA_NDCG ? 4 : W == PTR_TREE_W_DELTA_GAIN ? 3 : 2; }
+
+// Barrier over the G threads of one group.  G < 256: the group lies inside one wavefront, whose LDS operations execute in order.
+template <int G> __device__ __forceinline__ void group_sync() {
+    if constexpr (G == kBlock) __syncthreads();
+    else wave_lds_sync();
+}
+// Does any thread of the group hold `pred`?  (G == 256: a workgroup barrier as well: every thread of the block must call it.)
+template <int G> __device__ __forceinline__ bool group_any(bool pred, int tid) {
+    if constexpr (G == kBlock) return __syncthreads_or(pred) != 0;
+    else if constexpr (G == kWave) return __any(pred) != 0;
+    else return ((__ballot(pred) >> ((tid & (kWave - 1)) & ~(G - 1))) & ((1ull << G) - 1)) != 0;
+}
+// x[0] = op over x[0 .. n), in place: halves of ceil(m / 2) folded onto each other.  The tree's shape depends on n alone, so the result does
+// not depend on G.  Within a level the entries written ([0, m - h)) and read ([h, m)) do not overlap.  Starts and ends with a group barrier;
+// the caller reads x[0] and passes another barrier before it reuses the row.
+template <int G, class Op> __device__ __forceinline__ void group_tree(float *x, int n, int t, Op op) {
+    group_sync<G>();
+    for (int m = n; m > 1;) {
+        const int h = (m + 1) >> 1;
+        for (int i = t; i + h < m; i += G) x[i] = op(x[i], x[i + h]);
+        m = h;
+        group_sync<G>();
+    }
+}
+
+// The query of this group: its first document and its length.  A query longer than the launch's max_len (the caller's error: the LDS rows
+// are sized by max_len) is not evaluated: its documents receive NaN.
+struct TreeQuery { int64_t base; int n; };
+template <int G>
+__device__ __forceinline__ TreeQuery tree_query(const int64_t *__restrict__ offsets, int B, const int32_t *__restrict__ queries, int nq, int max_len, int t,
+                                                float *__restrict__ grad, float *__restrict__ hess) {
+    constexpr int QPB = kBlock / G;
+    const int gq = blockIdx.x * QPB + (int)threadIdx.x / G;
+    TreeQuery r{0, 0};
+    if (gq >= nq) return r;
+    const int q = queries ? queries[gq] : gq;
+    if (q < 0 || q >= B) return r;
+    r.base = offsets[q];
+    const int64_t len = offsets[q + 1] - r.base;
+    if (len > (int64_t)max_len) {
+        for (int64_t i = t; i < len; i += G) { grad[r.base + i] = NAN; hess[r.base + i] = NAN; }
+        return r;
+    }
+    r.n = len < 0 ? 0 : (int)len;
+    return r;
+}
+
+// 1 / (1 + e) from v_rcp_f32 and one Newton step (the LambdaRank kernels' form, pairwise.hip)
+__device__ __forceinline__ float rcp1p(float e) {
+    const float dd = 1.0f + e;
+    const float r = __builtin_amdgcn_rcpf(dd);
+    return fmaf(r, fmaf(-dd, r, 1.0f), r);
+}
+
+// pmask: bit (2 [y_i == y_j] + [y_i == y_j == 0]) set where the pair type keeps the pair (triu_indice, lightgbm_util.py:17-60)
+template <int G, int W, int H>
+__global__ void __launch_bounds__(kBlock)
+tree_pair_kernel(const float *__restrict__ preds, const float *__restrict__ labels, const int64_t *__restrict__ offsets, int B,
+                 const int32_t *__restrict__ queries, int nq, int Lp, int max_len, int pmask, float eps, float *__restrict__ grad,
+                 float *__restrict__ hess) {
+    constexpr int K = tree_rows(W);
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, grp = tid / G, t = tid % G;
+    const TreeQuery qu = tree_query<G>(offsets, B, queries, nq, max_len, t, grad, hess);
+    const int64_t base = qu.base;
+    const int n = G >= kWave ? __builtin_amdgcn_readfirstlane(qu.n) : qu.n;
+
+    float *S = smem + (size_t)grp * K * Lp, *Y = S + Lp;
+    float *A = S + (size_t)Lp * (K > 2 ? 2 : 0), *D = S + (size_t)Lp * (K > 3 ? 3 : 0);
+
+    // ---- stage the scores and the labels; both rows are padded with -inf up to a multiple of 4 (count_ranks reads float4)
+    bool bad = false;
+    const int np = (n + 3) & ~3;
+    for (int i = t; i < np; i += G) {
+        const float s = i < n ? preds[base + i] : -INFINITY, y = i < n ? labels[base + i] : -INFINITY;
+        S[i] = s; Y[i] = y;
+        bad |= s != s || y != y;
+    }
+    // a NaN score or label gives the list no ranking: NaN on every document of this list, and of no other (COVERAGE a9)
+    const bool nanq = group_any<G>(bad, tid);
+    group_sync<G>();
+
+    if constexpr (W == PTR_TREE_W_DELTA_NDCG) {
+        // IDCG from the exact label ranks (ideal_dcg, lightgbm_util.py:82-94), summed by the tree
+        for (int i = t; i < n; i += G) {
+            const float own[1] = {Y[i]};
+            int rk[1];
+            count_ranks<G, 1>(Y, n, i, own, rk);
+            D[i] = gain_of(own[0]) * inv_log2_pos(rk[0]);
+        }
+        group_tree<G>(D, n, t, [](float a, float b) { return a + b; });
+        const float idcg = n > 0 ? D[0] : 1.0f;
+        group_sync<G>();
+        for (int i = t; i < n; i += G) {
+            const float own[1] = {S[i]};
+            int rk[1];
+            count_ranks<G, 1>(S, n, i, own, rk);
+            A[i] = gain_of(Y[i]) / idcg;                       // 0 / 0 without a relevant document: NaN wherever a pair reads it, as the reference
+            D[i] = inv_log2_pos(rk[0]);                        // get_delta_ndcg, :103-118
+        }
+        group_sync<G>();
+    } else if constexpr (W == PTR_TREE_W_DELTA_GAIN) {
+        for (int i = t; i < n; i += G) A[i] = gain_of(Y[i]);   // get_delta_gains, :96-101
+        group_sync<G>();
+    }
+
+    const bool eps_one = eps == 1.0f;
+    const float eps2 = eps * eps;
+    for (int i = t; i < n; i += G) {
+        const float si = S[i], yi = Y[i];
+        const float ai = K > 2 ? A[i] : 0.0f, di = K > 3 ? D[i] : 0.0f;
+        const bool yi0 = yi == 0.0f;
+        float g = 0.0f, h = 0.0f;
+#pragma unroll 4
+        for (int j = 0; j < n; ++j) {
+            const float sj = S[j], yj = Y[j];
+            const float ds = si - sj;                          // the difference first, epsilon after: rounds relative to |ds|, not to |s|
+            const bool tie = yi == yj;
+            const bool pass = ((pmask >> ((tie ? 2 : 0) + (tie && yi0 ? 1 : 0))) & 1) != 0 && j != i;
+            // e / (1 + e)^2 = s(d)(1 - s(d)) without the cancellation of 1 - s; at epsilon 1 the gradient's sigmoid shares e and r
+            const float e1 = __expf(-fabsf(ds));
+            const float r1 = rcp1p(e1);
+            float p;
+            if (eps_one) {
+                p = ds >= 0.0f ? r1 : e1 * r1;
+            } else {
+                const float x = eps * ds;
+                const float e = __expf(-fabsf(x));
+                const float r = rcp1p(e);
+                p = x >= 0.0f ? r : e * r;
+            }
+            const float tt = 0.5f * (1.0f + __builtin_amdgcn_fmed3f(yi - yj, -1.0f, 1.0f));
+            float w = 1.0f;
+            if constexpr (W == PTR_TREE_W_DELTA_NDCG) w = fabsf(ai - A[j]) * fabsf(di - D[j]);
+            if constexpr (W == PTR_TREE_W_DELTA_GAIN) w = fabsf(ai - A[j]);
+            const float lam = w * (eps * (p - tt));            // :162-163
+            g += pass ? lam : 0.0f;
+            if constexpr (H != PTR_TREE_HESS_CONSTANT) {
+                float hv = fmaxf(eps2 * (e1 * r1 * r1), 1e-16f) * w;                  // :171-173
+                if constexpr (H == PTR_TREE_HESS_REFERENCE) {
+                    const bool below = ds > 0.0f || (ds == 0.0f && j > i);            // j ranks below i: +h to i (:177-178)
+                    hv = below ? hv : -hv;
+                }
+                h += pass ? hv : 0.0f;
+            }
+        }
+        grad[base + i] = nanq ? NAN : g;
+        hess[base + i] = H == PTR_TREE_HESS_CONSTANT ? 1.0f : (nanq ? NAN : h);
+    }
+}
+
+// ListNet: grad = softmax(s) - softmax(gain), hess = p (1 - p) (per_query_gradient_hessian_listnet, lightgbm_util.py:308-330).
+// LDS per query: scores | gains | the tree's row.
+template <int G>
+__global__ void __launch_bounds__(kBlock)
+tree_listnet_kernel(const float *__restrict__ preds, const float *__restrict__ labels, const int64_t *__restrict__ offsets, int B,
+                    const int32_t *__restrict__ queries, int nq, int Lp, int max_len, int power_gain, int const_hess, float *__restrict__ grad,
+                    float *__restrict__ hess) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, grp = tid / G, t = tid % G;
+    const TreeQuery qu = tree_query<G>(offsets, B, queries, nq, max_len, t, grad, hess);
+    const int64_t base = qu.base;
+    const int n = G >= kWave ? __builtin_amdgcn_readfirstlane(qu.n) : qu.n;
+    float *S = smem + (size_t)grp * 3 * Lp, *Y = S + Lp, *T = Y + Lp;
+
+    bool bad = false;
+    for (int i = t; i < n; i += G) {
+        const float s = preds[base + i], y = labels[base + i];
+        S[i] = s; Y[i] = power_gain ? gain_of(y) : y;
+        bad |= s != s || y != y;
+    }
+    const bool nanq = group_any<G>(bad, tid);
+
+    // max and normaliser of one row (_softmax, :5-11), both by the tree; every thread of the group gets the same two values
+    auto softmax_parts = [&](const float *row, float &mx, float &z) {
+        group_sync<G>();
+        for (int i = t; i < n; i += G) T[i] = row[i];
+        group_tree<G>(T, n, t, [](float a, float b) { return fmaxf(a, b); });
+        mx = n > 0 ? T[0] : 0.0f;
+        group_sync<G>();
+        for (int i = t; i < n; i += G) T[i] = expf(row[i] - mx);
+        group_tree<G>(T, n, t, [](float a, float b) { return a + b; });
+        z = n > 0 ? T[0] : 1.0f;
+    };
+    float ms, zs, my, zy;
+    softmax_parts(S, ms, zs);
+    softmax_parts(Y, my, zy);
+    for (int i = t; i < n; i += G) {
+        const float pp = expf(S[i] - ms) / zs, pt = expf(Y[i] - my) / zy;
+        grad[base + i] = nanq ? NAN : pp - pt;
+        hess[base + i] = const_hess ? 1.0f : (nanq ? NAN : pp * (1.0f - pp));
+    }
+}
+
+// ---- host side
+static int tree_check(const void *preds, const void *labels, const void *offsets, int B, const void *queries, int nq, int max_len, int hessian,
+                      const void *grad, const void *hess, const char *who) {
+    if (B < 0 || nq < 0 || max_len < 0) {
+        set_error("%s: negative size (B=%d, nq=%d, max_len=%d)", who, B, nq, max_len);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (!queries && nq != B) { set_error("%s: queries is NULL (all queries), so nq must equal B (nq=%d, B=%d)", who, nq, B); return PTR_ERR_INVALID_ARG; }
+    if (hessian < PTR_TREE_HESS_REFERENCE || hessian > PTR_TREE_HESS_CONSTANT) {
+        set_error("%s: hessian must be one of PTR_TREE_HESS_* (0 .. 2), got %d", who, hessian);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (int rc = check_pointers(nq, preds && labels && offsets, who, "NULL input pointer (preds, labels or offsets)")) return rc;
+    return check_pointers(nq, grad && hess, who, "NULL output pointer (grad or hess)");
+}
+
+static int tree_check_len(int max_len, const char *who) {
+    if (max_len > PTR_MAX_LIST_LEN) {
+        set_error("%s: max_len=%d exceeds PTR_MAX_LIST_LEN=%d", who, max_len, PTR_MAX_LIST_LEN);
+        return PTR_ERR_UNSUPPORTED;
+    }
+    return 0;
+}
+
+// Calls f.template operator()<G>() for the form of max_len.
+template <class F> static int dispatch_tree_form(int max_len, F &&f) {
+    if (max_len <= 16) return f.template operator()<16>();
+    if (max_len <= 128) return f.template operator()<64>();
+    return f.template operator()<256>();
+}
+template <int G, int W> static auto tree_pair_kernel_of(int hessian) {
+    return hessian == PTR_TREE_HESS_REFERENCE ? tree_pair_kernel<G, W, PTR_TREE_HESS_REFERENCE>
+         : hessian == PTR_TREE_HESS_SUM ? tree_pair_kernel<G, W, PTR_TREE_HESS_SUM>
+                                        : tree_pair_kernel<G, W, PTR_TREE_HESS_CONSTANT>;
+}
+
+}  // namespace ptr
+
+extern "C" int ptr_tree_pair_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries, int nq,
+                                       int max_len, int pair_type, int weighting, float epsilon, int hessian, float *grad, float *hess,
+                                       void *stream) {
+    using namespace ptr;
+    const char *who = "ptr_tree_pair_grad_hess";
+    if (int rc = tree_check(preds, labels, offsets, B, queries, nq, max_len, hessian, grad, hess, who)) return rc;
+    if (pair_type < PTR_TREE_PAIRS_ALL || pair_type > PTR_TREE_PAIRS_00) {
+        set_error("%s: pair_type must be one of PTR_TREE_PAIRS_* (0 .. 3), got %d", who, pair_type);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (weighting < PTR_TREE_W_NONE || weighting > PTR_TREE_W_DELTA_GAIN) {
+        set_error("%s: weighting must be one of PTR_TREE_W_* (0 .. 2), got %d", who, weighting);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (!(epsilon >= 0.0f)) { set_error("%s: epsilon must be >= 0 (got %g)", who, (double)epsilon); return PTR_ERR_INVALID_ARG; }
+    if (int rc = tree_check_len(max_len, who)) return rc;
+    if (nq == 0 || max_len == 0) return 0;
+    // bit 0: labels differ; bit 2: equal labels, not both 0; bit 3: both 0
+    const int pmask = pair_type == PTR_TREE_PAIRS_ALL ? 0xD : pair_type == PTR_TREE_PAIRS_NOTIES ? 0x1 : pair_type == PTR_TREE_PAIRS_NO00 ? 0x5 : 0x8;
+    const int Lp = round_up(max_len, 4);
+    return dispatch_tree_form(max_len, [&]<int G>() {
+        auto go = [&](auto kern, int K) -> int {
+            const size_t lds = (size_t)(kBlock / G) * K * Lp * sizeof(float);
+            return launch_queries(kern, nq, kBlock / G, kBlock, lds, stream, who, preds, labels, offsets, B, queries, nq, Lp, max_len, pmask, epsilon,
+                                  grad, hess);
+        };
+        return weighting == PTR_TREE_W_NONE ? go(tree_pair_kernel_of<G, PTR_TREE_W_NONE>(hessian), tree_rows(PTR_TREE_W_NONE))
+             : weighting == PTR_TREE_W_DELTA_NDCG ? go(tree_pair_kernel_of<G, PTR_TREE_W_DELTA_NDCG>(hessian), tree_rows(PTR_TREE_W_DELTA_NDCG))
+                                                  : go(tree_pair_kernel_of<G, PTR_TREE_W_DELTA_GAIN>(hessian), tree_rows(PTR_TREE_W_DELTA_GAIN));
+    });
+}
+
+extern "C" int ptr_tree_listnet_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries, int nq,
+                                          int max_len, int gain_type, int hessian, float *grad, float *hess, void *stream) {
+    using namespace ptr;
+    const char *who = "ptr_tree_listnet_grad_hess";
+    if (int rc = tree_check(preds, labels, offsets, B, queries, nq, max_len, hessian, grad, hess, who)) return rc;
+    if (gain_type < PTR_TREE_GAIN_POWER || gain_type > PTR_TREE_GAIN_LABEL) {
+        set_error("%s: gain_type must be one of PTR_TREE_GAIN_* (0 .. 1), got %d", who, gain_type);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (int rc = tree_check_len(max_len, who)) return rc;
+    if (nq == 0 || max_len == 0) return 0;
+    const int Lp = round_up(max_len, 4);
+    return dispatch_tree_form(max_len, [&]<int G>() {
+        const size_t lds = (size_t)(kBlock / G) * 3 * Lp * sizeof(float);
+        return launch_queries(tree_listnet_kernel<G>, nq, kBlock / G, kBlock, lds, stream, who, preds, labels, offsets, B, queries, nq, Lp, max_len,
+                              gain_type == PTR_TREE_GAIN_POWER ? 1 : 0, hessian == PTR_TREE_HESS_CONSTANT ? 1 : 0, grad, hess);
+    });
+}

@@ -15,11 +15,16 @@ from . import _lib
 
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
-           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES","shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
+           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
+           "TREE_GAIN_TYPES", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
 
 LAMBDALOSS_TYPES = {"NDCG_Loss1": 0, "NDCG_Loss2": 1, "NDCG_Loss2++": 2}   # ptranking/ltr_adhoc/listwise/lambdaloss.py:27
 ADCG_TOPK_AXES = {"reference": 0, "subtopics": 0, 0: 0, "documents": 1, 1: 1}   # PTR_ADCG_TOPK_*
 DIVPROB_OBJECTIVES = {"aNDCG": 0, "nERR-IA": 1, "PairCLS": 2, "LambdaPairCLS": 3, 0: 0, 1: 1, 2: 2, 3: 3}   # PTR_DIVPROB_*
+TREE_PAIR_TYPES = {"All": 0, "NoTies": 1, "No00": 2, "00": 3}              # PTR_TREE_PAIRS_*; ptranking/ltr_tree/util/lightgbm_util.py:17-60
+TREE_WEIGHTINGS = {None: 0, False: 0, "DeltaNDCG": 1, "DeltaGain": 2}       # PTR_TREE_W_*; lightgbm_util.py:80
+TREE_HESSIANS = {"reference": 0, "sum": 1, "constant": 2}                   # PTR_TREE_HESS_*
+TREE_GAIN_TYPES = {"Power": 0, "Label": 1}                                  # PTR_TREE_GAIN_*; lightgbm_util.py:306
 WASS_COST_TYPES = {"p1": 0, "p2": 1, "eg": 2, "dg": 3, "ddg": 4}   # PTR_WASS_COST_*; wassrank/wasserstein_cost_mat.py:113-139
 
 
@@ -299,6 +304,69 @@ def expected_ranks(mus, vars, lens=None):
         _lib.call("ptr_divprob_expected_ranks", _lib.ptr(mus), _lib.ptr(vars), _lib.ptr(lens), B, L, _lib.ptr(ranks),
                   _lib.current_stream(mus.device))
     return ranks
+
+
+def _enum(name, value, table):
+    if value not in table:
+        raise ValueError(f"{name} {value!r} (supported: {', '.join(repr(k) for k in table if k is not False)})")
+    return table[value]
+
+
+def _ragged(entry, preds, labels, offsets, queries, max_len, out, *params):
+    """The one launch path of the ragged (LightGBM-layout) entry points: (preds, labels, offsets, B, queries, nq, max_len, <params>, grad,
+    hess, stream) -> (grad, hess).  preds / labels: flat float32 [N]; offsets: int64 [B + 1], the running sum of the group sizes; queries:
+    int32 [nq] or None (all); max_len: the longest launched list (None: read back from `offsets`, which costs a host sync)."""
+    preds = _check("preds", preds)
+    if preds.dim() != 1:
+        raise ValueError(f"preds must be flat [documents], got {tuple(preds.shape)}")
+    dev = preds.device
+    labels = _check("labels", labels, shape=preds.shape)
+    offsets = _check("offsets", offsets, torch.int64)
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError(f"offsets must be [queries + 1], got {tuple(offsets.shape)}")
+    B = offsets.numel() - 1
+    nq = B
+    if queries is not None:
+        queries = _check("queries", queries, torch.int32)
+        if queries.dim() != 1:
+            raise ValueError(f"queries must be [launched queries], got {tuple(queries.shape)}")
+        nq = queries.numel()
+    if any(t is not None and t.device != dev for t in (labels, offsets, queries)):
+        raise RuntimeError("preds, labels, offsets and queries live on different devices")
+    if max_len is None:
+        max_len = int((offsets[1:] - offsets[:-1]).max()) if B > 0 else 0
+    if int(max_len) > _lib.MAX_LIST_LEN:
+        raise ValueError(f"a list of {int(max_len)} documents exceeds the supported maximum {_lib.MAX_LIST_LEN}")
+    if out is None:
+        # documents of queries that are not launched are not written: they read 0
+        new = torch.empty_like if queries is None else torch.zeros_like
+        out = (new(preds), new(preds))
+    grad, hess = (_check(n, t, shape=preds.shape) for n, t in zip(("grad", "hess"), out))
+    with torch.cuda.device(dev):
+        _lib.call(entry, _lib.ptr(preds), _lib.ptr(labels), _lib.ptr(offsets), B, _lib.ptr(queries), nq, int(max_len), *params, _lib.ptr(grad),
+                  _lib.ptr(hess), _lib.current_stream(dev))
+    return grad, hess
+
+
+def tree_pair_grad_hess(preds, labels, offsets, pair_type="NoTies", weighting=None, epsilon=1.0, hessian="reference", queries=None, max_len=None,
+                        out=None):
+    """Gradient and Hessian per document of the tree frame's pairwise objectives over LightGBM's ragged layout — what
+    per_query_gradient_hessian_lambda (ptranking/ltr_tree/util/lightgbm_util.py:120-183) returns for every query of `group`, in one launch.
+    preds / labels flat float32 [N], offsets int64 [B + 1]; returns two float32 [N] tensors.  Not differentiable.
+    pair_type 'All' / 'NoTies' / 'No00' / '00'; weighting None / 'DeltaNDCG' / 'DeltaGain' (the reference's lambdarank WRAPPERS never
+    apply a weight: None reproduces them, 'DeltaNDCG' is real LambdaMART); hessian 'reference' (signed by rank order, negative for
+    low-ranked documents), 'sum' (LightGBM's and XGBoost's: never negative) or 'constant' (1.0, the reference's FIRST_ORDER).
+    Equal scores rank by original index.  queries (int32 [nq]) / max_len launch a subset, e.g. one length class; `out` = (grad, hess) to
+    write into."""
+    return _ragged("ptr_tree_pair_grad_hess", preds, labels, offsets, queries, max_len, out, _enum("pair_type", pair_type, TREE_PAIR_TYPES),
+                   _enum("weighting", weighting, TREE_WEIGHTINGS), C.c_float(float(epsilon)), _enum("hessian", hessian, TREE_HESSIANS))
+
+
+def tree_listnet_grad_hess(preds, labels, offsets, gain_type="Power", hessian="reference", queries=None, max_len=None, out=None):
+    """ListNet as a tree objective (per_query_gradient_hessian_listnet, lightgbm_util.py:308-330): grad = softmax(preds) - softmax(gain),
+    hess = p (1 - p) per query of the ragged batch; gain 2^label - 1 ('Power') or the label ('Label').  Arguments as tree_pair_grad_hess."""
+    return _ragged("ptr_tree_listnet_grad_hess", preds, labels, offsets, queries, max_len, out, _enum("gain_type", gain_type, TREE_GAIN_TYPES),
+                   _enum("hessian", hessian, TREE_HESSIANS))
 
 
 def shuffle_ties_order(labels, seed, lens=None):

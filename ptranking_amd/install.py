@@ -15,6 +15,7 @@ WassRank is built by load_ranker with its own calling convention (ltr.py:173-174
 configuration with mode='EntropicOT' (or smooth_type='NG') now raises NotImplementedError instead of running the reference's torch code.
 """
 import importlib
+import sys
 
 from .rankers import EXTRA_RANKER_NAMES, RANKER_NAMES, make_ranker_classes
 
@@ -63,8 +64,28 @@ def install_diversification(names=None, ltr_module="ptranking.ltr_diversificatio
     return done
 
 
+def install_tree(util_module="ptranking.ltr_tree.util.lightgbm_util", user_modules=("ptranking.ltr_tree.lambdamart.lightgbm_lambdaMART",)):
+    """Rebind the six custom LightGBM objectives (ptranking_amd.tree.DROP_IN_NAMES: lightgbm_custom_obj_{ranknet,lambdarank,listnet} and
+    their *_fobj forms) inside the reference's lightgbm_util module, and inside each of `user_modules` that is ALREADY imported: the
+    reference's LightGBMLambdaMART imports the six names by value (lightgbm_lambdaMART.py:14-16), so a binding made there before
+    install_tree() would keep the Python loops; a module imported afterwards picks the new names up from lightgbm_util itself.  The
+    installed functions return what the reference's return (unweighted 'lambdarank', the rank-signed Hessian; ptranking_amd/tree.py), from
+    one fused kernel.  Returns {name: installed function}; uninstall() restores."""
+    from . import tree
+    done = {n: getattr(tree, n) for n in tree.DROP_IN_NAMES}
+    mods = [importlib.import_module(util_module)] + [sys.modules[m] for m in user_modules if m in sys.modules]
+    for mod in mods:
+        for n, fn in done.items():
+            if mod.__name__ != util_module and not hasattr(mod, n):
+                continue
+            _saved.setdefault((mod.__name__, n), getattr(mod, n, None))
+            setattr(mod, n, fn)
+    return done
+
+
 def uninstall(ltr_module=None):
-    """Restore the reference's own classes: in `ltr_module`, or (default) in every module install() / install_diversification() touched."""
+    """Restore the reference's own classes and functions: in `ltr_module`, or (default) in every module install(), install_diversification()
+    or install_tree() touched."""
     for m in sorted({m for m, _ in _saved} if ltr_module is None else {ltr_module}):
         _uninstall_module(m)
 
