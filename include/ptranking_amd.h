@@ -283,6 +283,47 @@ int ptr_tree_pair_grad_hess(const float *preds, const float *labels, const int64
 int ptr_tree_listnet_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries, int nq, int max_len,
                                int gain_type, int hessian, float *grad, float *hess, void *stream);
 
+/* ---- Smooth-rank metric objectives (csrc/smoothmetric.hip).  The symbol below is ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
+ * ptr_smoothmetric_fwd_bwd — loss and dLoss/dpreds of precision_ / AP_ / nERR_ / nDCG_as_opt_objective
+ * (ptranking/metric/smooth_metric/metric_as_opt_objective.py:12-257) on the smooth ranks of get_approx_ranks
+ * (ptranking/ltr_adhoc/listwise/approxNDCG.py:19-27), with their autograd backward, in one launch.  The reference knows no padding: the
+ * contract is "the reference on the unpadded list, one query at a time", loss_out = the sum over the queries.
+ *   labels     in ideal (descending) order per query: the reference asserts presort for nERR, nDCG and every opt_ideal form; there is no
+ *              unsorted mode.  Graded (MultiLabel) labels.
+ *   top_k      <= 0 means None.  K = n (None) or min(top_k, n); Kdiv = n (None) or top_k (P divides by top_k even on a shorter list).  The
+ *              reference's nERR raises for top_k > n; here K is clamped for every metric.
+ *   max_label  nERR only (2^max_label normalises the satisfaction probability); < 0 => the batch maximum over the valid documents (the
+ *              reference's torch.max(batch_std_labels)) is computed on the device into max_label_ws[1], with no host sync — the convention
+ *              of ptr_metrics_at_ks.  max_label_ws may be NULL otherwise.
+ *   Per query, n = lens[q]:   r_i = 1 + sum_{j != i} rs(alpha (s_j - s_i));   loss_q = - sum_i W_i phi(r_i), phi(r) = 1 / r (P, AP, nERR) or
+ *   1 / log2(1 + r) (nDCG).  pos_i = the input index under opt_ideal, else the 0-based rank by (score descending, index ascending) — the
+ *   order of the reference's torch.sort of the smooth ranks whenever those are distinct.  b = clamp(y, 0, 1); yp, bp = labels by position:
+ *     P      W_i = [pos_i < K] (pos_i + 1) b_i / Kdiv
+ *     AP     W_i = [pos_i < K] (pos_i + 1) (sum_{pos_i <= p < K} bp_p / (p + 1)) / sum_{p < K} bp_p;  opt_ideal == 0 with top_k <= 0 takes the
+ *            reference's other formula (:118-123): W_i = b_i #{relevant at positions <= pos_i} / sum b
+ *     nERR   sat = (2^yp - 1) / 2^max_label;  W_i = [pos_i < K] sat_{pos_i} prod_{p < pos_i} (1 - sat_p) / idealERR@K, the ideal value the same
+ *            expression over the input order with 1 / (p + 1) for 1 / r
+ *     nDCG   W_i = [pos_i < K] (2^y_i - 1) / IDCG, the IDCG over the WHOLE list even under top_k (the reference slices a [B, 1] tensor)
+ *   Filter (opt_ideal == 0 and top_k > 0, the reference's pos_inds): a query whose top-K positions hold no relevant document (sum of bp for P
+ *   and AP, of the labels for nERR, of the gains for nDCG equal to 0) contributes loss 0 and gradient 0, and valid_q = 0.  In every other form
+ *   a list without a relevant document gives what the reference gives: 0 for P, 0 / 0 = NaN for AP, nERR and nDCG, confined to that query's
+ *   loss_q and gradient row (and loss_out).  n = 0: loss 0, gradient 0, valid 0.  n = 1: no pair, the gradient is exactly 0 — or NaN
+ *   where the loss is (the reference's backward passes +c and -c through the diagonal of its difference matrix).
+ *   Outputs: loss_q [B], grad [B,L] (padded slots exactly 0), loss_out [1] = sum of loss_q (nullable: the caller sums loss_q with
+ *   ptr_sum_f32), valid_q [B] (nullable; 1.0 where the query contributed), ranks [B,L] (nullable; the smooth ranks, 0 on padding).
+ *   Lists of up to 512 documents: one wavefront per query out of registers; up to PTR_MAX_LIST_LEN: one workgroup per query (24 KiB of LDS up
+ *   to L = 1024, 48 KiB up to 2048, 96 KiB beyond, + 16 bytes).  No atomics.  A query's outputs depend on (its documents, L) alone: the same bits
+ *   alone, in any batch of the same padded width L and on every run; another L selects another form and another order of the sums.
+ *   PTR_ERR_INVALID_ARG (before any launch): a NULL required pointer, metric outside 0..3, alpha <= 0 or NaN, L <= 0 or L > PTR_MAX_LIST_LEN,
+ *   nERR with max_label < 0 and no max_label_ws. */
+#define PTR_SMOOTH_P 0
+#define PTR_SMOOTH_AP 1
+#define PTR_SMOOTH_NERR 2
+#define PTR_SMOOTH_NDCG 3
+int ptr_smoothmetric_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, int metric, int opt_ideal, int top_k,
+                             float alpha, float max_label, float *loss_out, float *loss_q, float *valid_q, float *ranks, float *max_label_ws,
+                             float *grad, void *stream);
+
 /* Device tie-shuffled label-descending order (the role of arg_shuffle_ties, sampling_utils.py:13-28) from a
  * counter-based RNG: same distribution, NOT the torch.randperm stream (not parity-checked, statistically tested). */
 int ptr_shuffle_ties_order(const float *labels, const int32_t *lens, int B, int L, uint64_t seed, int64_t *perm,

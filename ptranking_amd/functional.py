@@ -16,7 +16,7 @@ from . import _lib
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
            "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
-           "TREE_GAIN_TYPES", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
+           "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
 
 LAMBDALOSS_TYPES = {"NDCG_Loss1": 0, "NDCG_Loss2": 1, "NDCG_Loss2++": 2}   # ptranking/ltr_adhoc/listwise/lambdaloss.py:27
 ADCG_TOPK_AXES = {"reference": 0, "subtopics": 0, 0: 0, "documents": 1, 1: 1}   # PTR_ADCG_TOPK_*
@@ -25,6 +25,7 @@ TREE_PAIR_TYPES = {"All": 0, "NoTies": 1, "No00": 2, "00": 3}              # PTR
 TREE_WEIGHTINGS = {None: 0, False: 0, "DeltaNDCG": 1, "DeltaGain": 2}       # PTR_TREE_W_*; lightgbm_util.py:80
 TREE_HESSIANS = {"reference": 0, "sum": 1, "constant": 2}                   # PTR_TREE_HESS_*
 TREE_GAIN_TYPES = {"Power": 0, "Label": 1}                                  # PTR_TREE_GAIN_*; lightgbm_util.py:306
+SMOOTH_METRICS = {"P": 0, "AP": 1, "nERR": 2, "nDCG": 3, 0: 0, 1: 1, 2: 2, 3: 3}   # PTR_SMOOTH_*; metric/smooth_metric/metric_as_opt_objective.py
 WASS_COST_TYPES = {"p1": 0, "p2": 1, "eg": 2, "dg": 3, "ddg": 4}   # PTR_WASS_COST_*; wassrank/wasserstein_cost_mat.py:113-139
 
 
@@ -212,6 +213,28 @@ def approxndcg_loss(preds, labels, alpha=10.0, presort=True, couple_batch=True, 
                          [labels, lens, B, L, C.c_float(float(alpha)), int(bool(presort)), int(bool(couple_batch)), C.c_float(float(grad_scale_override))],
                          own_loss=True, slots=(("dcg_q", None), ("inv_idcg_q", None), ("scale", 2)))
     return (loss, parts) if return_parts else loss
+
+
+def smooth_metric_objective(preds, labels, metric, alpha=10.0, top_k=None, opt_ideal=True, max_label=None, lens=None, return_parts=False):
+    """A ranking metric as the optimisation objective, on smooth ranks: precision_ / AP_ / nERR_ / nDCG_as_opt_objective of
+    ptranking/metric/smooth_metric/metric_as_opt_objective.py:12-257 fed with get_approx_ranks(preds, alpha) (approxNDCG.py:19-27), the sum
+    over the queries of the reference's one-query loss (minus the smooth metric).  metric 'P' / 'AP' / 'nERR' / 'nDCG'; `labels` in ideal
+    (descending) order per query, as the reference asserts; top_k None = the whole list; opt_ideal=True weighs the documents by their input
+    (ideal) position, False by their current rank (score descending, index on ties), where a query without a relevant document among its
+    top_k contributes nothing, as the reference filters it.  max_label (nERR): None = the batch maximum, found on the device.
+    metric='nDCG', opt_ideal=True, top_k=None is ApproxNDCG's per-query form.  With return_parts also returns
+    dict(loss_q [B], valid_q [B] (1.0 where the query contributed), ranks [B, L] (the smooth ranks, 0 on padding), max_label_ws [1])."""
+    if metric not in SMOOTH_METRICS:
+        raise ValueError(f"metric {metric!r} (supported: 'P', 'AP', 'nERR', 'nDCG')")
+    preds_c, labels, lens, B, L = _batch(preds.detach(), labels, lens)
+    loss, parts = _fused("ptr_smoothmetric_fwd_bwd", [preds], [preds_c],
+                         [labels, lens, B, L, SMOOTH_METRICS[metric], int(bool(opt_ideal)), int(top_k) if top_k else 0, C.c_float(float(alpha)),
+                          C.c_float(-1.0 if max_label is None else float(max_label))],
+                         slots=(("loss_q", None), ("valid_q", None), ("ranks", max(B, 1) * L), ("max_label_ws", 1)))
+    if return_parts:
+        parts["ranks"] = parts["ranks"][:B * L].view(B, L)
+        return loss, parts
+    return loss
 
 
 def _div_batch(preds, rele, lens, ntopics):

@@ -28,6 +28,9 @@ RANKER_NAMES = ("RankNet", "LambdaRank", "LambdaLoss", "ApproxNDCG", "ListNet", 
 # SURVEY.md 2 marks these OUT OF SCOPE (the reference's driver cannot reach them): kept as classes for whoever asks for them by name
 # (install(extras=True), pa.DASALC / pa.MDPRank), not part of the default drop-in surface
 EXTRA_RANKER_NAMES = ("DASALC", "MDPRank")
+# the smooth-rank metric objectives (ptranking/metric/smooth_metric/metric_as_opt_objective.py): the reference has no ranker class around
+# them, so this one is opt-in by name (install(names=RANKER_NAMES + METRIC_RANKER_NAMES), pa.SmoothMetric)
+METRIC_RANKER_NAMES = ("SmoothMetric",)
 
 # default hyper-parameters = the reference's `default_para_dict()`s
 DEFAULT_PARAS = {
@@ -45,6 +48,7 @@ DEFAULT_PARAS = {
     "MDPRank": dict(model_id="MDPRank", temperature=1.0, gamma=1.0, top_k=10, distribution='PL'),   # listwise/mdprank.py:95-96
     "WassRank": dict(model_id="WassRank", mode='SinkhornOT', sh_itr=20, lam=0.1, smooth_type='ST', norm_type='BothST',   # listwise/wassrank/
                      cost_type='eg', non_rele_gap=100, var_penalty=math.e, gain_base=4),                                 # wassRank.py:97-104
+    "SmoothMetric": dict(model_id="SmoothMetric", metric='nDCG', alpha=10, top_k=None, opt_ideal=True),   # alpha: listwise/approxNDCG.py:131
 }
 
 
@@ -371,6 +375,27 @@ class SoftRankLoss(FusedStepMixin):
                                                  lens=kwargs.get('lens')))
 
 
+class SmoothMetricLoss(FusedStepMixin):
+    max_label = None
+
+    def uniform_eval_setting(self, **kwargs):
+        """Validate on the metric that is optimised (the pattern of approxNDCG.py:78-81)."""
+        eval_dict = kwargs['eval_dict']
+        if eval_dict["do_validation"] and not eval_dict['vali_metric'] == self.metric:
+            eval_dict['vali_metric'] = self.metric
+
+    def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
+        """ptranking/metric/smooth_metric/metric_as_opt_objective.py on get_approx_ranks (approxNDCG.py:19-27).  The reference's callers skip
+        the step of a batch whose every query the top-k filter drops (zero_metric_value); here such a batch still steps, with a zero
+        gradient: finding that out would cost a host sync per batch."""
+        assert 'presort' in kwargs and kwargs['presort'] is True  # aiming for direct usage of ideal ranking
+        assert 'label_type' in kwargs and is_multilabel(kwargs['label_type'])
+        if self.metric == 'nERR' and self.max_label is None and self.data_parallel and dp.is_distributed():
+            raise ValueError("SmoothMetric nERR under data parallelism needs model_para_dict['max_label']: the batch maximum is rank-local")
+        return self._fused_step(F_.smooth_metric_objective(batch_preds, batch_std_labels, self.metric, alpha=self.alpha, top_k=self.top_k,
+                                                           opt_ideal=self.opt_ideal, max_label=self.max_label, lens=kwargs.get('lens')))
+
+
 class MDPRankLoss(FusedStepMixin):
     def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
         """ptranking/ltr_adhoc/listwise/mdprank.py:24-78.  The reference asserts batch size 1 ("aiming for meaningful
@@ -584,9 +609,22 @@ def make_ranker_classes(base=PointScorerRanker):
             if wd['cost_type'] not in F_.WASS_COST_TYPES:
                 raise NotImplementedError(f"WassRank cost_type {wd['cost_type']!r} (supported: {sorted(F_.WASS_COST_TYPES)})")
 
+    class SmoothMetric(SmoothMetricLoss, FusedScorerMixin, FusedListScorerMixin, DeviceTrainLoop, DeviceEvaluator, base):
+        """P / AP / nERR / nDCG on smooth ranks as the training objective; model_para_dict: metric, alpha, top_k, opt_ideal, optional max_label."""
+
+        def __init__(self, sf_para_dict=None, model_para_dict=None, gpu=False, device=None):
+            base.__init__(self, id='SmoothMetric', sf_para_dict=sf_para_dict, gpu=gpu, device=device)
+            self.metric = model_para_dict['metric']
+            if self.metric not in ('P', 'AP', 'nERR', 'nDCG'):
+                raise NotImplementedError(f"metric {self.metric!r} (supported: 'P', 'AP', 'nERR', 'nDCG')")
+            self.alpha = model_para_dict['alpha']
+            self.top_k = model_para_dict['top_k']
+            self.opt_ideal = bool(model_para_dict['opt_ideal'])
+            self.max_label = model_para_dict.get('max_label')
+
     out = dict(RankNet=RankNet, LambdaRank=LambdaRank, LambdaLoss=LambdaLoss, ApproxNDCG=ApproxNDCG, ListNet=ListNet,
                ListMLE=ListMLE, STListNet=STListNet, RankCosine=RankCosine, RankMSE=RankMSE, SoftRank=SoftRank, WassRank=WassRank,
-               DASALC=DASALC, MDPRank=MDPRank)
+               DASALC=DASALC, MDPRank=MDPRank, SmoothMetric=SmoothMetric)
     for name, cls in out.items():
         cls.__name__ = cls.__qualname__ = name
         cls.__module__ = __name__
@@ -599,3 +637,4 @@ ApproxNDCG, ListNet, ListMLE = _standalone["ApproxNDCG"], _standalone["ListNet"]
 STListNet, RankCosine, RankMSE = _standalone["STListNet"], _standalone["RankCosine"], _standalone["RankMSE"]
 SoftRank, DASALC, MDPRank = _standalone["SoftRank"], _standalone["DASALC"], _standalone["MDPRank"]
 WassRank = _standalone["WassRank"]
+SmoothMetric = _standalone["SmoothMetric"]
