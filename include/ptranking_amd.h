@@ -324,6 +324,43 @@ int ptr_smoothmetric_fwd_bwd(const float *preds, const float *labels, const int3
                              float alpha, float max_label, float *loss_out, float *loss_q, float *valid_q, float *ranks, float *max_label_ws,
                              float *grad, void *stream);
 
+/* ---- Device Plackett-Luce sampling and the fused multi-sample MDPRank loss (csrc/plsample.hip).  The three symbols below are ADDITIVE to
+ * ABI v8 as well: PTR_ABI_VERSION stays 8.
+ * A ranking from the Plackett-Luce model with weights exp(s_i / T) is the descending order of s_i / T + g_i, g_i i.i.d. standard Gumbel.
+ *   u(seed, q0 + q, s, i)  a multiple of 2^-24 in [0, 1) from a counter hash (32-bit arithmetic); q0 = the GLOBAL index of the batch's first
+ *                          query, so a shard of a batch draws what the whole batch would.  g = -log(-log(u + 1e-20) + 1e-20) in fp32
+ *                          (ptranking/ltr_adhoc/util/sampling_utils.py:68), so g lies in [-3.83, 16.6].
+ *   unif                   nullable [B,S,L] by document: replaces the hash (the parity route: the reference's torch.rand draws).
+ *   PTR_PL_DIST_PL         key s_i / T + g_i (s_i at T == 1, sampling_utils.py:41-44) — the law of sample_ranking_PL's torch.multinomial
+ *                          without replacement (:49), with no weight that can underflow; action = the raw scores in sampled order (:56).
+ *   PTR_PL_DIST_STPL       key s_i + g_i; action = (s_i + g_i) / T in sampled order, no division at T == 1 (sampling_utils.py:60-81,
+ *                          ptranking/ltr_adversarial/util/list_sampling.py:38-67 with S = num_sample_ranking).  T does not enter the
+ *                          ranking's law there, as in the reference.
+ *   Order (key descending, index ascending), as ptr_sort_desc.  Padded documents never enter the sort: perm[q,s,p] = p for p >= lens[q] and
+ *   action is 0 there; n = 0 gives the identity; a list with a NaN score gets the identity and NaN action on its real positions.
+ * ptr_pl_uniforms writes the uniforms [B,S,L] the two entry points below draw.
+ * ptr_pl_sample writes perm int64 [B,S,L] and, when action != NULL, action [B,S,L].
+ * ptr_mdprank_sample_fwd_bwd draws the S rankings of every query and evaluates ptranking/ltr_adhoc/listwise/mdprank.py:45-71 on each, in one
+ * launch (the maths of ptr_mdprank_fwd_bwd): loss_q[q] = (1/S) sum_s loss(q,s), grad[q,i] = (1/S) sum_s d loss(q,s) / d s_i, loss_out = sum_q
+ * loss_q (nullable), perm_out nullable [B,S,L].  Under 'PL' the loss sees the raw scores (no 1/T in the gradient: T only shapes the draw,
+ * mdprank.py:37); under 'STPL' it sees (s + g) / T and the gradient carries 1/T (:40-41).  S = 1 is the reference's episode.  n = 0: loss 0,
+ * gradient 0.  A NaN score makes the loss and every gradient entry of that list NaN.  top_k <= 0: the whole list.
+ * An episode whose action values spread over more than 80 units is evaluated in the log domain: where the reference's log(cumsum(exp)) is
+ * -inf the loss and the gradient stay finite.
+ *   One wavefront per query up to 1024 documents (register sort), one workgroup per query up to PTR_MAX_LIST_LEN; LDS per query 16 or 24
+ *   bytes (sampler / loss) x 64 ceil(L / 64) up to 1024 documents, 12 or 20 bytes x round_up(L, 4) + 16 beyond.  No atomics: a query's bits
+ *   depend on (its data, L, S, seed, q0 + q) alone.
+ *   PTR_ERR_INVALID_ARG (before any HIP call): B < 0, L <= 0, L > PTR_MAX_LIST_LEN, S < 1, temperature <= 0 or NaN, a distribution other
+ *   than the two, gamma <= 0 or NaN, and with B > 0 a NULL preds / labels / perm / loss_q / grad / unif (ptr_pl_uniforms). */
+#define PTR_PL_DIST_PL 0
+#define PTR_PL_DIST_STPL 1
+int ptr_pl_uniforms(int B, int L, int S, uint64_t seed, int64_t q0, float *unif, void *stream);
+int ptr_pl_sample(const float *preds, const int32_t *lens, int B, int L, int S, float temperature, int distribution, uint64_t seed, int64_t q0,
+                  const float *unif, int64_t *perm, float *action, void *stream);
+int ptr_mdprank_sample_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, int S, int top_k, float gamma,
+                               float temperature, int distribution, uint64_t seed, int64_t q0, const float *unif, float *loss_out,
+                               float *loss_q, float *grad, int64_t *perm_out, void *stream);
+
 /* Device tie-shuffled label-descending order (the role of arg_shuffle_ties, sampling_utils.py:13-28) from a
  * counter-based RNG: same distribution, NOT the torch.randperm stream (not parity-checked, statistically tested). */
 int ptr_shuffle_ties_order(const float *labels, const int32_t *lens, int B, int L, uint64_t seed, int64_t *perm,

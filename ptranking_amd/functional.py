@@ -16,8 +16,10 @@ from . import _lib
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
            "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
-           "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
+           "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
 
+# (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
+# launch table, and it draws its own)
 LAMBDALOSS_TYPES = {"NDCG_Loss1": 0, "NDCG_Loss2": 1, "NDCG_Loss2++": 2}   # ptranking/ltr_adhoc/listwise/lambdaloss.py:27
 ADCG_TOPK_AXES = {"reference": 0, "subtopics": 0, 0: 0, "documents": 1, 1: 1}   # PTR_ADCG_TOPK_*
 DIVPROB_OBJECTIVES = {"aNDCG": 0, "nERR-IA": 1, "PairCLS": 2, "LambdaPairCLS": 3, 0: 0, 1: 1, 2: 2, 3: 3}   # PTR_DIVPROB_*
@@ -26,6 +28,7 @@ TREE_WEIGHTINGS = {None: 0, False: 0, "DeltaNDCG": 1, "DeltaGain": 2}       # PT
 TREE_HESSIANS = {"reference": 0, "sum": 1, "constant": 2}                   # PTR_TREE_HESS_*
 TREE_GAIN_TYPES = {"Power": 0, "Label": 1}                                  # PTR_TREE_GAIN_*; lightgbm_util.py:306
 SMOOTH_METRICS = {"P": 0, "AP": 1, "nERR": 2, "nDCG": 3, 0: 0, 1: 1, 2: 2, 3: 3}   # PTR_SMOOTH_*; metric/smooth_metric/metric_as_opt_objective.py
+PL_DISTRIBUTIONS = {"PL": 0, "STPL": 1, 0: 0, 1: 1}   # PTR_PL_DIST_*; ptranking/ltr_adhoc/listwise/mdprank.py:19
 WASS_COST_TYPES = {"p1": 0, "p2": 1, "eg": 2, "dg": 3, "ddg": 4}   # PTR_WASS_COST_*; wassrank/wasserstein_cost_mat.py:113-139
 
 
@@ -88,9 +91,9 @@ def _reduce(loss_q, B, dev):
     return out.reshape(())
 
 
-def _fused(entry, inputs, checked, args, own_loss=False, slots=(("loss_q", None),)):
+def _fused(entry, inputs, checked, args, own_loss=False, slots=(("loss_q", None),), tail=()):
     """The one launch path of the fused losses -> (loss, {slot name: tensor}).  The entry point takes (*inputs, *args, loss_out, *slots,
-    one gradient per input, stream): `inputs` are the differentiable [B, L] tensors as the caller passed them and `checked` their detached,
+    one gradient per input, *tail, stream): `tail` are further output pointers (tensor or None) behind the gradients; `inputs` are the differentiable [B, L] tensors as the caller passed them and `checked` their detached,
     validated, contiguous forms; `args` the remaining pointer (tensor or None) and scalar arguments in ABI order; `slots` the per-query
     outputs as (name, size), size None meaning [B].  own_loss: the entry point writes loss_out itself; otherwise loss_out is NULL and the
     first slot is summed by the deterministic reduction."""
@@ -105,7 +108,7 @@ def _fused(entry, inputs, checked, args, own_loss=False, slots=(("loss_q", None)
         out = new(1) if own_loss else None
         with torch.cuda.device(dev):
             _lib.call(entry, *map(_lib.ptr, xs), *(_lib.ptr(a) if isinstance(a, torch.Tensor) else a for a in args), _lib.ptr(out),
-                      *map(_lib.ptr, outs), *map(_lib.ptr, grads), _lib.current_stream(dev))
+                      *map(_lib.ptr, outs), *map(_lib.ptr, grads), *map(_lib.ptr, tail), _lib.current_stream(dev))
             loss = out.reshape(()) if own_loss else _reduce(outs[0], B, dev)
         parts.update((name, t[:B] if n is None else t) for (name, n), t in zip(slots, outs))
         return (loss, *grads)
@@ -333,6 +336,78 @@ def _enum(name, value, table):
     if value not in table:
         raise ValueError(f"{name} {value!r} (supported: {', '.join(repr(k) for k in table if k is not False)})")
     return table[value]
+
+
+def _seed64(seed):
+    return C.c_uint64(int(seed) & (2 ** 64 - 1))
+
+
+def _pl_unif(unif, B, S, L, dev):
+    if unif is None:
+        return None
+    unif = _check("unif", unif, torch.float32, (B, S, L))
+    if unif.device != dev:
+        raise RuntimeError("preds and unif live on different devices")
+    return unif
+
+
+def _pl_samples(samples):
+    if int(samples) < 1:
+        raise ValueError(f"samples must be >= 1, got {samples}")
+    return int(samples)
+
+
+def pl_uniforms(B, L, samples=1, seed=0, q0=0, device=None):
+    """The uniforms sample_rankings_pl / mdprank_sampled_loss draw for (seed, q0): float32 [B, samples, L], multiples of 2^-24 in [0, 1),
+    u(seed, q0 + q, s, i) from a counter hash.  q0 = the global index of the batch's first query."""
+    _list_len(L)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"device {dev}: ptranking_amd runs on the MI355X HIP path only (no CPU fallback)")
+    S = _pl_samples(samples)
+    unif = torch.empty((int(B), S, int(L)), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_pl_uniforms", int(B), int(L), S, _seed64(seed), C.c_int64(int(q0)), _lib.ptr(unif), _lib.current_stream(dev))
+    return unif
+
+
+def sample_rankings_pl(preds, samples=1, temperature=1.0, distribution='PL', seed=0, q0=0, lens=None, unif=None, return_action=False):
+    """Rankings sampled on the device from the Plackett-Luce model -> int64 [B, samples, L]: the descending order of preds / T + gumbel
+    ('PL': the law of sample_ranking_PL's torch.multinomial without replacement, ptranking/ltr_adhoc/util/sampling_utils.py:31-57, with
+    no weight that can underflow) or of preds + gumbel ('STPL': sample_ranking_PL_gumbel_softmax, :60-81, and
+    ptranking/ltr_adversarial/util/list_sampling.py:38-67 with samples = num_sample_ranking), ties by index.  Counter-based: the same
+    (seed, q0 + q) draws the same rankings in any batch; `unif` float32 [B, samples, L] replaces the generator (e.g. the reference's
+    torch.rand draws).  Padded positions (lens) hold their own index.  return_action: also the scores ('PL') or (preds + gumbel) / T
+    ('STPL') in sampled order, float32 [B, samples, L].  Not differentiable."""
+    preds, B, L = _matrix("preds", preds.detach())
+    _list_len(L)
+    S = _pl_samples(samples)
+    dist = _enum("distribution", distribution, PL_DISTRIBUTIONS)
+    lens = _counts("lens", lens, B)
+    unif = _pl_unif(unif, B, S, L, preds.device)
+    perm = torch.empty((B, S, L), device=preds.device, dtype=torch.int64)
+    action = torch.empty((B, S, L), device=preds.device, dtype=torch.float32) if return_action else None
+    with torch.cuda.device(preds.device):
+        _lib.call("ptr_pl_sample", _lib.ptr(preds), _lib.ptr(lens), B, L, S, C.c_float(float(temperature)), dist, _seed64(seed),
+                  C.c_int64(int(q0)), _lib.ptr(unif), _lib.ptr(perm), _lib.ptr(action), _lib.current_stream(preds.device))
+    return (perm, action) if return_action else perm
+
+
+def mdprank_sampled_loss(preds, labels, top_k=10, gamma=1.0, temperature=1.0, distribution='PL', samples=1, seed=0, q0=0, lens=None, unif=None,
+                         return_perm=False):
+    """MDPRank with the sampling inside the kernel (ptranking/ltr_adhoc/listwise/mdprank.py:36-71): one launch draws `samples` rankings per
+    query as sample_rankings_pl does and evaluates the return-weighted ListMLE of each; the loss is the sum over queries of the mean over
+    the samples, differentiable in preds.  'PL': the loss sees the raw scores (no 1 / T in the gradient); 'STPL': (preds + gumbel) / T.
+    samples=1 is the reference's episode.  return_perm: also the sampled rankings, int64 [B, samples, L]."""
+    preds_c, labels, lens, B, L = _batch(preds.detach(), labels, lens)
+    S = _pl_samples(samples)
+    dist = _enum("distribution", distribution, PL_DISTRIBUTIONS)
+    unif = _pl_unif(unif, B, S, L, preds_c.device)
+    perm = torch.empty((B, S, L), device=preds_c.device, dtype=torch.int64) if return_perm else None
+    loss = _fused("ptr_mdprank_sample_fwd_bwd", [preds], [preds_c],
+                  [labels, lens, B, L, S, int(top_k) if top_k else 0, C.c_float(float(gamma)), C.c_float(float(temperature)), dist, _seed64(seed),
+                   C.c_int64(int(q0)), unif], own_loss=True, tail=(perm,))[0]
+    return (loss, perm) if return_perm else loss
 
 
 def _ragged(entry, preds, labels, offsets, queries, max_len, out, *params):

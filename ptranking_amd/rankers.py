@@ -397,11 +397,42 @@ class SmoothMetricLoss(FusedStepMixin):
 
 
 class MDPRankLoss(FusedStepMixin):
+    # "torch" (default): the ranking is drawn with torch.multinomial / torch.rand + torch.sort as below; "device": sampling and loss in
+    # one launch (functional.mdprank_sampled_loss), samples_per_query rankings per query, from a counter-based generator keyed by a per-call
+    # seed and the query's global index.  Both read from model_para_dict ('sampler', 'samples_per_query').
+    sampler = "torch"
+    samples_per_query = 1
+    _pl_seed = 137            # ptranking/ltr_global.py:7
+    _pl_calls = 0
+
+    def _query_offset(self, B, kwargs):
+        """Global index of this batch's first query: kwargs['q0'] when the caller knows it; under data parallelism the rank's recorded
+        slice (dp.shard_queries), else rank * local batch size, so that ranks draw disjoint streams."""
+        if kwargs.get('q0') is not None:
+            return int(kwargs['q0'])
+        if not (self.data_parallel and dp.is_distributed()) or dp.world_size() == 1:
+            return 0
+        if dp.QUERY_SHARD is not None and dp.QUERY_SHARD[1] == B:
+            return int(dp.QUERY_SHARD[0])
+        return dp.rank() * B
+
+    def _device_sampled_step(self, batch_preds, batch_std_labels, lens, kwargs):
+        if self.distribution not in F_.PL_DISTRIBUTIONS:
+            raise NotImplementedError
+        self._pl_calls += 1
+        loss = F_.mdprank_sampled_loss(batch_preds, batch_std_labels, top_k=self.top_k, gamma=self.gamma, temperature=self.temperature,
+                                       distribution=self.distribution, samples=self.samples_per_query,
+                                       seed=self._pl_seed * 0x9E3779B1 + self._pl_calls, q0=self._query_offset(batch_preds.size(0), kwargs),
+                                       lens=lens)
+        return self._fused_step(loss)
+
     def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
         """ptranking/ltr_adhoc/listwise/mdprank.py:24-78.  The reference asserts batch size 1 ("aiming for meaningful
         batch-normalization"); every query is an independent episode here, so any batch size works and B = 1 reproduces it."""
         assert 'presort' in kwargs and kwargs['presort'] is True  # aiming for direct usage of ideal ranking
         lens = kwargs.get('lens')
+        if self.sampler == 'device':
+            return self._device_sampled_step(batch_preds, batch_std_labels, lens, kwargs)
         with torch.no_grad():
             det = batch_preds.detach()
             if lens is not None:      # padded documents must be sampled last: they get (numerically) zero probability mass
@@ -584,6 +615,12 @@ def make_ranker_classes(base=PointScorerRanker):
             self.top_k = model_para_dict['top_k']
             self.temperature = model_para_dict['temperature']
             self.distribution = model_para_dict['distribution']  # 'PL', 'STPL'
+            self.sampler = model_para_dict.get('sampler', 'torch')                    # 'torch' (the reference's construction) or 'device'
+            self.samples_per_query = int(model_para_dict.get('samples_per_query', 1))
+            if self.sampler not in ('torch', 'device'):
+                raise ValueError(f"MDPRank sampler {self.sampler!r} (supported: 'torch', 'device')")
+            if self.samples_per_query < 1 or (self.sampler == 'torch' and self.samples_per_query != 1):
+                raise ValueError("MDPRank samples_per_query must be >= 1, and 1 with sampler='torch'")
             self.pg_checking = False
 
     class WassRank(WassRankLoss, FusedScorerMixin, FusedListScorerMixin, DeviceTrainLoop, DeviceEvaluator, base):
