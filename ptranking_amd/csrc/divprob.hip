@@ -44,10 +44,7 @@ __device__ __forceinline__ float inv_sqrt(float z) {
     return fmaf(0.5f * r, fmaf(-z * r, r, 1.0f), r);
 }
 // a / b from v_rcp_f32 and one Newton step
-__device__ __forceinline__ float quot(float a, float b) {
-    const float r = __builtin_amdgcn_rcpf(b);
-    return a * fmaf(r, fmaf(-b, r, 1.0f), r);
-}
+__device__ __forceinline__ float quot(float a, float b) { return a * rcp_nr(b); }
 
 // The pair (i, j) seen from document i.  x is clamped to +-1e18 so that x^2 stays finite (beyond |x| ~ 13 every quantity below is at
 // its limit anyway).  sq_hi + sq_lo = x^2 exactly; e2 = exp(-x^2) with the rounding of x^2 taken out.

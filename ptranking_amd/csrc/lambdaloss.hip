@@ -392,8 +392,7 @@ lambdaloss_topk_kernel(const float *__restrict__ preds, const float *__restrict_
             // log2(1 + e) with one v_log_f32 (1 ulp: 1e-7 absolute near p = 1)
             const float e = __expf(-fabsf(x));
             const float dd = 1.0f + e;
-            float pb = __builtin_amdgcn_rcpf(dd);
-            pb = fmaf(pb, fmaf(-dd, pb, 1.0f), pb);
+            const float pb = rcp_nr(dd);
             p0 = x >= 0.0f ? pb : e * pb;
             lp = p0 >= eps ? fminf(x, 0.0f) * inv_ln2 - __builtin_amdgcn_logf(dd) : log2_eps;
         }

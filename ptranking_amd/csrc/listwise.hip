@@ -270,7 +270,7 @@ __device__ __forceinline__ void listmle_vec_body(const f32x4 (&a)[V], const int 
         const float lg = EXACT ? logf(T[i]) : fast_ln(T[i]);
         loss += in ? (lg + m) - u[i] : 0.0f;
         if constexpr (EXACT) inv[i] = in ? 1.0f / T[i] : 0.0f;
-        else { const float r = __builtin_amdgcn_rcpf(T[i]); inv[i] = in ? fmaf(r, fmaf(-T[i], r, 1.0f), r) : 0.0f; }
+        else inv[i] = in ? rcp_nr(T[i]) : 0.0f;
     }
     loss_out = wave_sum_dpp(loss);
     run = 0.0f;

@@ -124,8 +124,7 @@ pairwise_bce_kernel(const float *__restrict__ preds, const float *__restrict__ l
             const float x = sigma * ds;                         // >= 0 in predicted order
             const float e = __expf(-x);
             const float dd = 1.0f + e;
-            float p = __builtin_amdgcn_rcpf(dd);
-            p = fmaf(p, fmaf(-dd, p, 1.0f), p);                 // one Newton step: correctly-rounded-class 1/(1+e)
+            const float p = rcp_nr(dd);                         // one Newton step: correctly-rounded-class 1/(1+e)
             const float qv = 1.0f - p;
             const bool t1 = dy > 0.0f;                          // target 1 (lo has the higher grade) or 0; ties: w == 0
             const float lg = fmaxf(fast_ln(t1 ? p : qv), -100.0f);  // argument is 0 or a normal float <= 1
@@ -152,8 +151,7 @@ pairwise_bce_kernel(const float *__restrict__ preds, const float *__restrict__ l
                 // |x| > 27.6 on) becomes a factor instead of a division
                 const float e = __expf(-fabsf(x));
                 const float dd = 1.0f + e;
-                float pb = __builtin_amdgcn_rcpf(dd);
-                pb = fmaf(pb, fmaf(-dd, pb, 1.0f), pb);
+                const float pb = rcp_nr(dd);
                 p = x >= 0.0f ? pb : e * pb;
                 qv = 1.0f - p;
                 l1 = fmaxf(fast_ln(p), -100.0f); l0 = fmaxf(fast_ln(qv), -100.0f);

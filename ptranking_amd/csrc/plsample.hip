@@ -49,83 +49,6 @@ __device__ __forceinline__ float pl_key(float s, float u, float temperature, int
     return (dist == PTR_PL_DIST_PL && temperature != 1.0f ? s / temperature : s) + g;
 }
 
-// ---- exclusive scans over the G threads of a group (thread order), fixed order.  G == 256: workgroup barriers inside, `red` = 4 floats.
-template <int G> __device__ __forceinline__ float grp_excl_suffix(float v, float *red, int t) {
-    const float incl = wave_incl_suffix_sum(v, t & 63);
-    const float ex = dpp_wave_shl1(incl);
-    if constexpr (G == kWave) {
-        return ex;
-    } else {
-        __syncthreads();
-        if ((t & 63) == 0) red[t >> 6] = incl;
-        __syncthreads();
-        float add = 0.0f;
-        for (int w = G / kWave - 1; w > (t >> 6); --w) add += red[w];
-        return ex + add;
-    }
-}
-template <int G> __device__ __forceinline__ float grp_excl_prefix(float v, float *red, int t) {
-    const float incl = wave_incl_sum(v, t & 63);
-    const float ex = dpp_wave_shr1(incl);
-    if constexpr (G == kWave) {
-        return ex;
-    } else {
-        __syncthreads();
-        if ((t & 63) == 63) red[t >> 6] = incl;
-        __syncthreads();
-        float add = 0.0f;
-        for (int w = 0; w < (t >> 6); ++w) add += red[w];
-        return ex + add;
-    }
-}
-
-// log(e^x + e^y); -inf is the empty sum
-__device__ __forceinline__ float lse2(float x, float y) {
-    const float hi = fmaxf(x, y), lo = fminf(x, y);
-    return hi == -INFINITY ? -INFINITY : hi + log1pf(expf(lo - hi));
-}
-// the two exclusive scans above in the log domain (v = log of a sum), for the episodes whose exp(a - m) would underflow
-template <int G> __device__ __forceinline__ float grp_excl_suffix_lse(float v, float *red, int t) {
-    const int lane = t & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float o = __shfl_down(v, d, 64);
-        if (lane + d < 64) v = lse2(v, o);
-    }
-    const float nx = __shfl_down(v, 1, 64);
-    const float ex = lane < 63 ? nx : -INFINITY;
-    if constexpr (G == kWave) {
-        return ex;
-    } else {
-        __syncthreads();
-        if (lane == 0) red[t >> 6] = v;
-        __syncthreads();
-        float add = -INFINITY;
-        for (int w = G / kWave - 1; w > (t >> 6); --w) add = lse2(add, red[w]);
-        return lse2(ex, add);
-    }
-}
-template <int G> __device__ __forceinline__ float grp_excl_prefix_lse(float v, float *red, int t) {
-    const int lane = t & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float o = __shfl_up(v, d, 64);
-        if (lane >= d) v = lse2(v, o);
-    }
-    const float pv = __shfl_up(v, 1, 64);
-    const float ex = lane > 0 ? pv : -INFINITY;
-    if constexpr (G == kWave) {
-        return ex;
-    } else {
-        __syncthreads();
-        if (lane == 63) red[t >> 6] = v;
-        __syncthreads();
-        float add = -INFINITY;
-        for (int w = 0; w < (t >> 6); ++w) add = lse2(add, red[w]);
-        return lse2(ex, add);
-    }
-}
-
 // mdprank.py:45-71 on ONE sampled ranking held by position (thread t: positions t*DPT ..): a = action value, id = document.  Adds
 // gscale * d loss / d a to GA[document] and returns the episode's loss (every thread).  GN = 2^label - 1 by document.
 template <int G, int DPT>

@@ -283,9 +283,102 @@ __device__ __forceinline__ float wave_incl_suffix_sum(float v, int lane) {
     }
     return v;
 }
+__device__ __forceinline__ float dpp_wave_shl1(float v) {      // lane t <- lane t + 1, lane 63 <- 0
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130 /* wave_shl:1 */, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float dpp_wave_shr1(float v) {      // lane t <- lane t - 1, lane 0 <- 0
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138 /* wave_shr:1 */, 0xF, 0xF, true));
+}
+__device__ __forceinline__ int dpp_wave_shl1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xF, 0xF, true); }
+__device__ __forceinline__ int dpp_wave_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, true); }
 
-// ln(x) = log2(x)*ln2 on the transcendental pipe (v_log_f32); for x == 0 or normal x only (no denormal scaling).
-__device__ __forceinline__ float fast_ln(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
+// ---- exclusive scans over the G threads of a group (thread order), fixed order.  G == 256: workgroup barriers inside, `red` = 4 floats.
+template <int G> __device__ __forceinline__ float grp_excl_suffix(float v, float *red, int t) {
+    const float incl = wave_incl_suffix_sum(v, t & 63);
+    const float ex = dpp_wave_shl1(incl);
+    if constexpr (G == kWave) {
+        return ex;
+    } else {
+        __syncthreads();
+        if ((t & 63) == 0) red[t >> 6] = incl;
+        __syncthreads();
+        float add = 0.0f;
+        for (int w = G / kWave - 1; w > (t >> 6); --w) add += red[w];
+        return ex + add;
+    }
+}
+template <int G> __device__ __forceinline__ float grp_excl_prefix(float v, float *red, int t) {
+    const float incl = wave_incl_sum(v, t & 63);
+    const float ex = dpp_wave_shr1(incl);
+    if constexpr (G == kWave) {
+        return ex;
+    } else {
+        __syncthreads();
+        if ((t & 63) == 63) red[t >> 6] = incl;
+        __syncthreads();
+        float add = 0.0f;
+        for (int w = 0; w < (t >> 6); ++w) add += red[w];
+        return ex + add;
+    }
+}
+
+// log(e^x + e^y); -inf is the empty sum
+__device__ __forceinline__ float lse2(float x, float y) {
+    const float hi = fmaxf(x, y), lo = fminf(x, y);
+    return hi == -INFINITY ? -INFINITY : hi + log1pf(expf(lo - hi));
+}
+// the two exclusive scans above in the log domain (v = log of a sum), for sums whose exp(a - m) would underflow
+template <int G> __device__ __forceinline__ float grp_excl_suffix_lse(float v, float *red, int t) {
+    const int lane = t & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const float o = __shfl_down(v, d, 64);
+        if (lane + d < 64) v = lse2(v, o);
+    }
+    const float nx = __shfl_down(v, 1, 64);
+    const float ex = lane < 63 ? nx : -INFINITY;
+    if constexpr (G == kWave) {
+        return ex;
+    } else {
+        __syncthreads();
+        if (lane == 0) red[t >> 6] = v;
+        __syncthreads();
+        float add = -INFINITY;
+        for (int w = G / kWave - 1; w > (t >> 6); --w) add = lse2(add, red[w]);
+        return lse2(ex, add);
+    }
+}
+template <int G> __device__ __forceinline__ float grp_excl_prefix_lse(float v, float *red, int t) {
+    const int lane = t & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const float o = __shfl_up(v, d, 64);
+        if (lane >= d) v = lse2(v, o);
+    }
+    const float pv = __shfl_up(v, 1, 64);
+    const float ex = lane > 0 ? pv : -INFINITY;
+    if constexpr (G == kWave) {
+        return ex;
+    } else {
+        __syncthreads();
+        if (lane == 63) red[t >> 6] = v;
+        __syncthreads();
+        float add = -INFINITY;
+        for (int w = 0; w < (t >> 6); ++w) add = lse2(add, red[w]);
+        return lse2(ex, add);
+    }
+}
+
+// 2^x and log2(x) on the transcendental pipe (v_exp_f32, v_log_f32); for x == 0 or normal x only (no denormal scaling).
+__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+__device__ __forceinline__ float fast_log2(float x) { return __builtin_amdgcn_logf(x); }
+// ln(x) = log2(x)*ln2
+__device__ __forceinline__ float fast_ln(float x) { return fast_log2(x) * 0.6931471805599453f; }
+// 1 / d from v_rcp_f32 and one Newton step
+__device__ __forceinline__ float rcp_nr(float d) {
+    const float r = __builtin_amdgcn_rcpf(d);
+    return fmaf(r, fmaf(-d, r, 1.0f), r);
+}
 
 // 2^l - 1 (ptranking/metric/adhoc/adhoc_metric.py:208-209); exact for the integer grades 0..4 stored as floats.
 __device__ __forceinline__ float gain_of(float label) { return exp2f(label) - 1.0f; }
@@ -456,15 +549,18 @@ __device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
 }
 // 1 / log2(pos + 2)
 __device__ __forceinline__ float inv_log2_pos(int pos) {
-    const float d = __builtin_amdgcn_logf((float)(pos + 2));
-    const float r = __builtin_amdgcn_rcpf(d);
-    return fmaf(r, fmaf(-d, r, 1.0f), r);
+    return rcp_nr(fast_log2((float)(pos + 2)));
 }
 // LDS hand-over between the lanes of ONE wavefront (its own LDS region): LDS operations of a wave execute in order, only the
 // compiler has to be kept from reordering them — no workgroup barrier, the four waves of a block stay independent
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+}
+// Barrier over the G threads of one group.  G < 256: the group lies inside one wavefront, whose LDS operations execute in order.
+template <int G> __device__ __forceinline__ void group_sync() {
+    if constexpr (G == kBlock) __syncthreads();
+    else wave_lds_sync();
 }
 __device__ __forceinline__ float dpp_rol1(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x134 /* wave_rol:1 */, 0xF, 0xF, false));
@@ -626,14 +722,6 @@ __device__ __forceinline__ void rank_blocked_wave(float *sorted, float *scratch,
     }
     wave_lds_sync();
 }
-__device__ __forceinline__ float dpp_wave_shl1(float v) {      // lane t <- lane t + 1, lane 63 <- 0
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130 /* wave_shl:1 */, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_wave_shr1(float v) {      // lane t <- lane t - 1, lane 0 <- 0
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138 /* wave_shr:1 */, 0xF, 0xF, true));
-}
-__device__ __forceinline__ int dpp_wave_shl1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xF, 0xF, true); }
-__device__ __forceinline__ int dpp_wave_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, true); }
 
 // r5: the (score descending, index ascending) order of 65 .. 1024 documents from ONE register sort, without a rank search.
 // Key = order-preserving integer image of the score with its low IB bits replaced by (N - 1 - index) (N = 64 DPT, IB = log2 N), sorted

@@ -253,8 +253,7 @@ lambdarank_ring_kernel(const float *__restrict__ preds, const float *__restrict_
             Ts = dpp_rol1(Ts); Tg = dpp_rol1(Tg); Td = dpp_rol1(Td); Tacc[0] = dpp_rol1(Tacc[0]);
             const float e = __builtin_amdgcn_exp2f(-fabsf((so - Ts) * c2));
             const float dd = 1.0f + e;
-            float p = __builtin_amdgcn_rcpf(dd);
-            p = fmaf(p, fmaf(-dd, p, 1.0f), p);
+            const float p = rcp_nr(dd);
             const float qv = 1.0f - p;
             const float dDn = Td - Do;
             float un = ((go - Tg) * dDn) * sigma;

@@ -18,8 +18,8 @@
 //   O(n)     labels scattered to their positions in LDS, one scan by ONE wavefront (suffix sum for AP, prefix count for the full-list re-sorted
 //            AP, exclusive prefix product for nERR), W_i, the loss and c_i;
 //   pass 2   the gradient from the pair derivatives.
-// Lists of up to 512 documents: one wavefront per query, both passes out of registers (smooth_ring: the ring scheme of approxndcg_ring_kernel,
-// restated here because approxndcg.hip keeps it private).  Up to PTR_MAX_LIST_LEN: one workgroup per query, scores in LDS, the partner's share
+// Lists of up to 512 documents: one wavefront per query, both passes out of registers (approx_ring, ptr_rsig.h: the ring of
+// approxndcg_ring_kernel; padding records carry s = -1e30, c = 0).  Up to PTR_MAX_LIST_LEN: one workgroup per query, scores in LDS, the partner's share
 // of a pair accumulated in one LDS row per wavefront, the rank indicators in fixed point (exact integer additions: see pass 1 there).  Nothing
 // of size n x n exists and there are no atomics; every sum has a fixed order given (n, L): a query's outputs do not depend on the rest of the
 // batch or on the run.
@@ -27,10 +27,6 @@
 #include "ptr_rsig.h"
 
 namespace ptr {
-
-template <int G> __device__ __forceinline__ void group_sync() {
-    if constexpr (G == kWave) wave_lds_sync(); else __syncthreads();
-}
 
 enum { kScanPrefixSum = 0, kScanSuffixSum = 1, kScanPrefixProdExcl = 2 };
 
@@ -156,84 +152,6 @@ __device__ __forceinline__ void smooth_phi(int metric, float W, float r, float &
     }
 }
 
-// =====================================================================================================================
-// A COPY of approx_ring (approxndcg.hip keeps it private to its translation unit): a fix to either must be made in both.
-// The register ring of approxndcg_ring_kernel (approxndcg.hip approx_ring, same instruction stream): lane a owns documents a, a + 64, ...; every
-// slot has two travelling copies (the records 1..16 and 17..32 lanes ahead) rotated one lane per step.  PASS 1: out = sum_{j != i} y_ij;
-// PASS 2: out = the gradient from the coefficients c.  Padding records carry s = -1e30, c = 0 and contribute exactly 0 to real documents.
-template <int DPT, int PASS>
-__device__ __forceinline__ void smooth_ring(const float (&s)[DPT], const float (&c)[DPT], float c2, float alpha, int lane, float (&out)[DPT]) {
-    f32x2 so2[DPT], co2[DPT], acc2[DPT];
-    f32x2 Ts[DPT], Tc[DPT], Ta[DPT];
-    const int ahead16 = (lane + 16) & 63;
-#pragma unroll
-    for (int k = 0; k < DPT; ++k) {
-        so2[k] = f32x2{s[k], s[k]};
-        Ts[k] = f32x2{s[k], __shfl(s[k], ahead16, 64)};
-        acc2[k] = f32x2{0.f, 0.f}; Ta[k] = f32x2{0.f, 0.f};
-        if constexpr (PASS == 2) { co2[k] = f32x2{c[k], c[k]}; Tc[k] = f32x2{c[k], __shfl(c[k], ahead16, 64)}; }
-    }
-    const f32x2 c22 = {c2, c2}, one2 = {1.0f, 1.0f}, al2 = {alpha, alpha};
-    auto pair2 = [&](int k, int t, f32x2 mask, bool use_mask) __attribute__((always_inline)) {
-        const f32x2 dl = pk_sub(Ts[t], so2[k]);                   // delta = s_b - s_a
-        const f32x2 x = dl * c22;                                 // alpha*log2(e) folded
-        const f32x2 e = {__builtin_amdgcn_exp2f(-fabsf(x.x)), __builtin_amdgcn_exp2f(-fabsf(x.y))};
-        const f32x2 dd = one2 + e;
-        f32x2 r = {__builtin_amdgcn_rcpf(dd.x), __builtin_amdgcn_rcpf(dd.y)};
-        r = __builtin_elementwise_fma(r, __builtin_elementwise_fma(-dd, r, one2), r);
-        const f32x2 sm = e * r;
-        f32x2 ya, yb;                                             // delta == 0: e = 1, r = sm = 0.5 on its own
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const bool pos = dl[h] > 0.0f;
-            ya[h] = pos ? r[h] : sm[h];
-            yb[h] = pos ? sm[h] : r[h];
-        }
-        if constexpr (PASS == 1) {
-            if (use_mask) { ya = ya * mask; yb = yb * mask; }
-            acc2[k] = pk_add(acc2[k], ya);
-            Ta[t] = pk_add(Ta[t], yb);
-        } else {
-            const f32x2 dab = (ya * al2) * pk_sub(one2, ya), dba = (yb * al2) * pk_sub(one2, yb);      // base/utils.py:78
-            f32x2 flow = __builtin_elementwise_fma(-co2[k], dab, Tc[t] * dba);
-            if (use_mask) flow = flow * mask;
-            acc2[k] = pk_add(acc2[k], flow);
-            Ta[t] = pk_sub(Ta[t], flow);
-        }
-    };
-    auto rotate = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int t = 0; t < DPT; ++t)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                Ts[t][h] = dpp_rol1(Ts[t][h]); Ta[t][h] = dpp_rol1(Ta[t][h]);
-                if constexpr (PASS == 2) Tc[t][h] = dpp_rol1(Tc[t][h]);
-            }
-    };
-#pragma unroll
-    for (int k = 0; k < DPT; ++k)
-#pragma unroll
-        for (int t = k + 1; t < DPT; ++t) pair2(k, t, f32x2{1.0f, 0.0f}, true);
-    for (int r = 1; r < 16; ++r) {
-        rotate();
-#pragma unroll
-        for (int k = 0; k < DPT; ++k)
-#pragma unroll
-            for (int t = 0; t < DPT; ++t) pair2(k, t, one2, false);
-    }
-    {
-        rotate();
-        const float lm = lane < 32 ? 1.0f : 0.0f;
-#pragma unroll
-        for (int k = 0; k < DPT; ++k)
-#pragma unroll
-            for (int t = 0; t < DPT; ++t) pair2(k, t, f32x2{1.0f, lm}, true);
-    }
-    const int behind16 = (lane - 16) & 63;
-#pragma unroll
-    for (int k = 0; k < DPT; ++k) out[k] = (acc2[k].x + acc2[k].y) + (__shfl(Ta[k].x, behind16, 64) + __shfl(Ta[k].y, lane ^ 32, 64));
-}
-
 __device__ __forceinline__ float smooth_pow_max(float max_label, const float *max_label_dev) {
     return exp2f(max_label_dev ? max_label_dev[0] : max_label);
 }
@@ -275,7 +193,7 @@ smooth_ring_kernel(const float *__restrict__ preds, const float *__restrict__ la
 
     const float c2 = alpha * 1.4426950408889634f;
     float pia[DPT], W[DPT], ca[DPT], tot[DPT];
-    smooth_ring<DPT, 1>(si, si, c2, alpha, lane, pia);
+    approx_ring<DPT, 1>(si, si, c2, alpha, lane, pia);
     const bool keep = smooth_weights<kWave, DPT>(row, nullptr, n, lane, metric, opt_ideal != 0, top_k,
                                                  metric == PTR_SMOOTH_NERR ? smooth_pow_max(max_label, max_label_dev) : 1.0f, yi, pos, W);
     float part = 0.0f;
@@ -290,7 +208,7 @@ smooth_ring_kernel(const float *__restrict__ preds, const float *__restrict__ la
         tot[m] = 0.0f;
     }
     const float loss = 0.0f - wave_sum_dpp(part);
-    if (keep && n > 1) smooth_ring<DPT, 2>(si, ca, c2, alpha, lane, tot);
+    if (keep && n > 1) approx_ring<DPT, 2>(si, ca, c2, alpha, lane, tot);
     // n == 1: no pair.  The reference's backward still passes +c and -c through the diagonal of its difference matrix: exactly 0 for a finite
     // c, NaN where the only document is irrelevant and W = 0 / 0 (tests/golden/smooth_metric.npz, edge/n1_norel)
     if (n == 1) tot[0] = ca[0] - ca[0];

@@ -37,11 +37,6 @@ namespace ptr {
 
 __host__ __device__ constexpr int tree_rows(int W) { return W == PTR_TREE_W_DELTA_NDCG ? 4 : W == PTR_TREE_W_DELTA_GAIN ? 3 : 2; }
 
-// Barrier over the G threads of one group.  G < 256: the group lies inside one wavefront, whose LDS operations execute in order.
-template <int G> __device__ __forceinline__ void group_sync() {
-    if constexpr (G == kBlock) __syncthreads();
-    else wave_lds_sync();
-}
 // Does any thread of the group hold `pred`?  (G == 256: a workgroup barrier as well: every thread of the block must call it.)
 template <int G> __device__ __forceinline__ bool group_any(bool pred, int tid) {
     if constexpr (G == kBlock) return __syncthreads_or(pred) != 0;
@@ -83,12 +78,8 @@ __device__ __forceinline__ TreeQuery tree_query(const int64_t *__restrict__ offs
     return r;
 }
 
-// 1 / (1 + e) from v_rcp_f32 and one Newton step (the LambdaRank kernels' form, pairwise.hip)
-__device__ __forceinline__ float rcp1p(float e) {
-    const float dd = 1.0f + e;
-    const float r = __builtin_amdgcn_rcpf(dd);
-    return fmaf(r, fmaf(-dd, r, 1.0f), r);
-}
+// 1 / (1 + e) (the LambdaRank kernels' form, pairwise.hip)
+__device__ __forceinline__ float rcp1p(float e) { return rcp_nr(1.0f + e); }
 
 // pmask: bit (2 [y_i == y_j] + [y_i == y_j == 0]) set where the pair type keeps the pair (triu_indice, lightgbm_util.py:17-60)
 template <int G, int W, int H>

@@ -44,9 +44,6 @@ __device__ __forceinline__ float wass_cost(float ki, float kj, float di, float d
     }
 }
 
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float fast_log2(float x) { return __builtin_amdgcn_logf(x); }
-
 // out[j] = base[j] - LSE2_i(in[i] - s * C_ij) for every real document j (< n).  `in` is padded with -inf up to n4 = round_up(n, 4), K and D
 // with 0, so the padded terms are exp2(-inf) = 0.  Thread t owns the columns j = j0 + d*G + t of each tile of G*DPT columns.
 template <int COST, int G, int DPT>
