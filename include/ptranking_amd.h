@@ -367,7 +367,9 @@ int ptr_shuffle_ties_order(const float *labels, const int32_t *lens, int B, int 
                            void *stream);
 
 /* torch.sort(preds, dim=1, descending=True) as ptranking/base/ranker.py:50 and lambdarank.py:39 call it:
- * vals[B,L] fp32, idx[B,L] int64; order = (value descending, original index ascending); padded tail: 0 / identity. */
+ * vals[B,L] fp32, idx[B,L] int64; order = (value descending, original index ascending); padded tail: 0 / identity.
+ * NaN scores sort FIRST (ahead of +inf), among themselves by original index — torch.sort(descending=True, stable=True); -0.0 and +0.0
+ * compare equal.  idx is a permutation of [0, lens[q]) on every input. */
 int ptr_sort_desc(const float *preds, const int32_t *lens, int B, int L, float *vals, int64_t *idx, void *stream);
 
 /* Evaluator prologue + metrics — replaces ptranking/base/ranker.py:46-60,220-243 (sort, gather, ideal sort) and
@@ -376,7 +378,9 @@ int ptr_sort_desc(const float *preds, const int32_t *lens, int B, int L, float *
  *   max_label: nERR's 2^max_label normaliser; < 0 => the batch maximum is computed on device into max_label_ws[1];
  *   label_type: PTR_LABEL_* (nDCG's gain, adhoc_metric.py:207-212; nERR exists for MultiLabel only, as in the reference);
  *   ndcg/nerr/ap/prec: [B,nk] outputs, each nullable.  Cut-offs larger than the list are zero-filled at the END
- *   of the row exactly like the reference's padded_*_at_ks. */
+ *   of the row exactly like the reference's padded_*_at_ks.
+ *   The predicted ranking is ptr_sort_desc's: a NaN score ranks first (index ascending among NaNs), as torch.sort has it.  A list
+ *   without a relevant document gives nDCG = nERR = AP = NaN (0 / 0, as the reference) and P = 0 at every fitting cut-off. */
 #define PTR_LABEL_MULTILABEL 0    /* LABEL_TYPE.MultiLabel: graded labels, DCG gain 2^l - 1 (data_utils.py:120-126)          */
 #define PTR_LABEL_PERMUTATION 1   /* LABEL_TYPE.Permutation: labels = n - rank position, DCG gain = the label itself        */
 int ptr_metrics_at_ks(const float *preds, const float *labels, const int32_t *lens, int B, int L, const int32_t *ks,

@@ -37,10 +37,14 @@ static inline int qlen(const int32_t *lens, int q, int L) {
     return n < 0 ? 0 : (n > L ? L : n);
 }
 
-/* ---- stable descending argsort: (value desc, index asc) -------------------------------------- */
+/* ---- stable descending argsort: (NaN first, value desc, index asc) — a total order, so qsort is defined on a row that
+ * holds NaNs, and the order torch.sort(descending=True, stable=True) returns ------------------------------------------ */
 typedef struct { float v; int32_t i; } kv_t;
 static int kv_cmp_desc(const void *a, const void *b) {
     const kv_t *x = (const kv_t *)a, *y = (const kv_t *)b;
+    const int xn = x->v != x->v, yn = y->v != y->v;
+    if (xn != yn) return yn - xn;
+    if (xn) return (x->i > y->i) - (x->i < y->i);
     if (x->v > y->v) return -1;
     if (x->v < y->v) return 1;
     return (x->i > y->i) - (x->i < y->i);

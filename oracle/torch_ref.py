@@ -243,8 +243,9 @@ def loss_and_grad(fn, preds, *args, **kw):
 
 # --------------------------------------------------------------------------- metrics
 def sort_desc(preds):
-    """torch.sort(descending=True) as ptranking/base/ranker.py:50 calls it (values, int64 indices)."""
-    return torch.sort(preds, dim=1, descending=True)
+    """torch.sort(descending=True) as ptranking/base/ranker.py:50 calls it (values, int64 indices); stable, so that equal scores and
+    NaN scores (which sort first) keep their original order at every list length."""
+    return torch.sort(preds, dim=1, descending=True, stable=True)
 
 
 def _pad_ks(vals_at, ks, L, B):

@@ -383,12 +383,52 @@ __device__ __forceinline__ float rcp_nr(float d) {
 // 2^l - 1 (ptranking/metric/adhoc/adhoc_metric.py:208-209); exact for the integer grades 0..4 stored as floats.
 __device__ __forceinline__ float gain_of(float label) { return exp2f(label) - 1.0f; }
 
+// Order-preserving integer image of a float key with every NaN above +inf (and -0.0 keyed as +0.0): comparing the images is torch.sort's
+// descending order on a row that holds NaNs.  Used by count_ranks<.., NANFIRST> below.
+__device__ __forceinline__ uint32_t rank_key_nan_first(float x) {
+    const int b = __builtin_bit_cast(int, x);
+    const uint32_t o = b == (int)0x80000000 ? 0x80000000u : (uint32_t)b ^ ((uint32_t)(b >> 31) | 0x80000000u);   // -0.0 keys as +0.0
+    return x != x ? 0xFFFFFFFFu : o;
+}
+
 // Descending rank of each owned key among keys[0..n): rank = #{j : k_j > k_i  or (k_j == k_i and j < i)}, i.e. the
 // position torch.sort(descending=True) gives on tie-free input, with ties broken by original index.
 // keys[] is in LDS, padded with -inf up to a multiple of 4 (float4 broadcast reads).  own[m] / index t + m*G.
 // BLK: own[m] is document t*DPT + m (the blocked layout of the one-wavefront paths) instead of t + m*G.
-template <int G, int DPT, bool BLK = false>
+// NANFIRST: the keys are compared through rank_key_nan_first() — torch.sort's order for a row that holds NaNs (every NaN ahead of +inf,
+// the NaNs among themselves by original index).  The evaluation kernels (metrics.hip) take this form, and only once a NaN has been seen;
+// the float compares of the plain form give a NaN rank 0 beside the true maximum, which the loss kernels answer by poisoning the list.
+template <int G, int DPT, bool BLK = false, bool NANFIRST = false>
 __device__ __forceinline__ void count_ranks(const float *keys, int n, int t, const float (&own)[DPT], int (&rk)[DPT]) {
+    if constexpr (NANFIRST) {
+        // the same two counts and the same tie pass on the order-preserving integer image of the keys (a total order)
+        int ge[DPT];
+        uint32_t so[DPT];
+#pragma unroll
+        for (int m = 0; m < DPT; ++m) { rk[m] = 0; ge[m] = 0; so[m] = rank_key_nan_first(own[m]); }
+        const float4 *k4 = reinterpret_cast<const float4 *>(keys);
+        const int n4 = (n + 3) >> 2;
+        for (int j4 = 0; j4 < n4; ++j4) {
+            const float4 v = k4[j4];
+            const uint32_t a = rank_key_nan_first(v.x), b = rank_key_nan_first(v.y), c = rank_key_nan_first(v.z), d = rank_key_nan_first(v.w);
+#pragma unroll
+            for (int m = 0; m < DPT; ++m) {
+                const uint32_t s = so[m];
+                rk[m] += (a > s) + (b > s) + (c > s) + (d > s);
+                ge[m] += (a >= s) + (b >= s) + (c >= s) + (d >= s);
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < DPT; ++m) {
+            const int i = BLK ? t * DPT + m : t + m * G;
+            if (i < n && ge[m] - rk[m] != 1) {
+                int extra = 0;
+                for (int j = 0; j < i; ++j) extra += rank_key_nan_first(keys[j]) == so[m] ? 1 : 0;
+                rk[m] += extra;
+            }
+        }
+        return;
+    }
     // Fast path (tie-free lists, the common case): rank = #{j : k_j > k_i} — one compare + one add-with-carry per pair.
     // #{j : k_j >= k_i} is counted alongside; a lane whose two counts differ by more than its own element has a tie, and
     // only then the wave takes the slow pass that adds #{j < i : k_j == k_i} (original index breaks ties).
@@ -438,7 +478,8 @@ __device__ __forceinline__ f32x2 pk_fma_clamp(f32x2 a, f32x2 b, f32x2 c) {
 // original index order).  Both are detected (integrality + a scatter / gather permutation check through `mark`, n ints of LDS), and
 // the whole group recounts with count_ranks().  keys[] as for count_ranks (padded with -inf to a multiple of 4).  Contains group-wide
 // barriers: every thread of the group (G == 256: of the block) must call it.
-template <int G, int DPT>
+// NANFIRST: a recount that meets a NaN key orders it first (count_ranks<.., NANFIRST>); every other recount, and the fast count, are unchanged.
+template <int G, int DPT, bool NANFIRST = false>
 __device__ __forceinline__ void count_ranks_fast(const float *keys, int *mark, int n, int t, const float (&own)[DPT], int (&rk)[DPT]) {
     const float big = 0x1p100f;
     const f32x2 big2 = {big, big};
@@ -488,7 +529,18 @@ __device__ __forceinline__ void count_ranks_fast(const float *keys, int *mark, i
     bool any;
     if constexpr (G == kWave) any = __any(redo);
     else any = __syncthreads_or(redo);
-    if (any) count_ranks<G, DPT>(keys, n, t, own, rk);
+    if (any) {
+        if constexpr (NANFIRST) {
+            bool isnan = false;
+#pragma unroll
+            for (int m = 0; m < DPT; ++m) isnan |= own[m] != own[m];
+            bool anynan;
+            if constexpr (G == kWave) anynan = __any(isnan);
+            else anynan = __syncthreads_or(isnan);
+            if (anynan) { count_ranks<G, DPT, false, true>(keys, n, t, own, rk); return; }
+        }
+        count_ranks<G, DPT>(keys, n, t, own, rk);
+    }
 }
 
 // ---- helpers of the register "ring" pair loops (pairwise.hip lambdarank_ring_kernel, approxndcg.hip approxndcg_ring_kernel)
@@ -693,7 +745,7 @@ template <int DPT> __device__ __forceinline__ void lds_store_blocked(float *row,
         for (int r = 0; r < DPT; ++r) row[t * DPT + r] = v[r];
     }
 }
-template <int DPT>
+template <int DPT, bool NANFIRST = false>
 __device__ __forceinline__ void rank_blocked_wave(float *sorted, float *scratch, int n, int t, const float (&own)[DPT], int (&rk)[DPT],
                                                   float (&v)[DPT]) {
     constexpr int N = kWave * DPT;
@@ -708,6 +760,16 @@ __device__ __forceinline__ void rank_blocked_wave(float *sorted, float *scratch,
     if (__any(bad)) {
         lds_store_blocked<DPT>(scratch, t, own);
         wave_lds_sync();
+        if constexpr (NANFIRST) {
+            bool isnan = false;
+#pragma unroll
+            for (int r = 0; r < DPT; ++r) isnan |= own[r] != own[r];
+            if (__any(isnan)) {                                              // torch.sort's order: NaN first
+                count_ranks<kWave, DPT, true, true>(scratch, n, t, own, rk);
+                wave_lds_sync();
+                return;
+            }
+        }
         count_ranks<kWave, DPT, true>(scratch, n, t, own, rk);
         wave_lds_sync();
         return;
