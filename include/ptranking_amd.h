@@ -324,6 +324,38 @@ int ptr_smoothmetric_fwd_bwd(const float *preds, const float *labels, const int3
                              float alpha, float max_label, float *loss_out, float *loss_q, float *valid_q, float *ranks, float *max_label_ws,
                              float *grad, void *stream);
 
+/* ---- Gaussian expected-rank metric objectives (csrc/gaussmetric.hip).  The symbol below is ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
+ * ptr_gaussmetric_fwd_bwd — loss, dLoss/dmus and dLoss/dvars of precision_ / AP_ / nERR_ / nDCG_as_opt_objective
+ * (ptranking/metric/smooth_metric/metric_as_opt_objective.py:12-257) on the expected ranks of documents whose scores are independent normal
+ * variables, get_expected_rank / get_expected_rank_const (ptranking/ltr_diversification/util/prob_utils.py:62-101), with their autograd
+ * backward, in one launch.  The contract is that of ptr_smoothmetric_fwd_bwd with the rank source exchanged: metric, labels, top_k (K,
+ * Kdiv), max_label / max_label_ws, the weights W_i per form, the filter with valid_q, n = 0, "the reference on the unpadded list, one query
+ * at a time" and padded slots exactly 0 are as documented there.
+ *   Per query, n = lens[q]:   x_ij = (mu_i - mu_j) / sqrt(2 (v_i + v_j));   r_i = 1 + sum_{j != i} erfc(x_ij) / 2;
+ *   loss_q = - sum_i W_i phi(r_i).  With u_i = -W_i phi'(r_i), g = exp(-x^2) / sqrt(pi) and a = 1 / sqrt(2 (v_i + v_j)):
+ *   dloss/dmu_i = sum_j g a (u_j - u_i),   dloss/dv_i = sum_j g a (x a) (u_i - u_j).
+ *   pos_i = the input index under opt_ideal, else the 0-based rank of the kernel's OWN fp32 r_i ascending with ties by index ascending (the
+ *   reference's torch.sort of the ranks).  Expected ranks are not monotone in the mean, so the order is counted from the computed ranks.
+ *   vars       [B,L], or NULL: every document then has the variance const_std^2 (rounded once from the double product), const_std > 0 the
+ *              reference's `const_var`, which is a standard deviation (prob_utils.py:87); grad_var may then be NULL, and the results are
+ *              bit-identical to a call with vars filled with that value.  A variance <= 0 is the caller's error: NaN for that query, as in
+ *              ptr_divprob_fwd_bwd.
+ *   A list without a relevant document gives what the reference gives (0 for P; NaN for AP, nERR and nDCG in the unfiltered forms, in that
+ *   query's loss_q and gradient rows).  n = 1: no pair, both gradients are exactly 0 even where the loss is NaN (the reference masks the
+ *   diagonal out of its sum).
+ *   Outputs: loss_q [B], grad_mu [B,L], grad_var [B,L] (nullable with vars == NULL), loss_out [1] (nullable), valid_q [B] (nullable),
+ *   ranks [B,L] (nullable; r, 0 on padding), pos [B,L] int32 (nullable; the hard positions, -1 on padding).
+ *   Lists of up to 512 documents: one wavefront per query out of registers, four queries per workgroup — a ring over the lanes that
+ *   evaluates every unordered pair once (8 bytes of LDS per document slot, 1, 2, 3, 4, 6 or 8 x 64 slots, for the rank count and the weight
+ *   step); up to PTR_MAX_LIST_LEN: one workgroup per query, every document walks all its partners (16 bytes per slot, 4, 8 or 16 x 256 slots:
+ *   64 KiB at L = 4096, + 16 bytes).  No atomics, nothing of size n x n; the sums over the partners are compensated.  A query's outputs
+ *   depend on (its documents, L) alone.
+ *   PTR_ERR_INVALID_ARG (before any launch): a NULL required pointer, vars == NULL with const_std <= 0 or NaN, vars != NULL with
+ *   grad_var == NULL, metric outside 0..3, L <= 0 or L > PTR_MAX_LIST_LEN, nERR with max_label < 0 and no max_label_ws. */
+int ptr_gaussmetric_fwd_bwd(const float *mus, const float *vars, const float *labels, const int32_t *lens, int B, int L, int metric,
+                            int opt_ideal, int top_k, float const_std, float max_label, float *loss_out, float *loss_q, float *valid_q,
+                            float *ranks, int32_t *pos, float *max_label_ws, float *grad_mu, float *grad_var, void *stream);
+
 /* ---- Device Plackett-Luce sampling and the fused multi-sample MDPRank loss (csrc/plsample.hip).  The three symbols below are ADDITIVE to
  * ABI v8 as well: PTR_ABI_VERSION stays 8.
  * A ranking from the Plackett-Luce model with weights exp(s_i / T) is the descending order of s_i / T + g_i, g_i i.i.d. standard Gumbel.

@@ -14,7 +14,8 @@
                 RankCosine, RankMSE, SoftRank, WassRank) inside an installed ptranking so LTREvaluator uses them unchanged; a WassRank
                 configured with mode='EntropicOT' (or smooth_type='NG') now raises NotImplementedError instead of running the reference's
                 torch code; install(names=RANKER_NAMES + METRIC_RANKER_NAMES) adds SmoothMetric (P / AP / nERR / nDCG on smooth ranks as the
-                training objective), which the reference has no class for
+                training objective), which the reference has no class for; install(names=RANKER_NAMES + PROB_RANKER_NAMES) adds
+                ProbSmoothMetric (the same four objectives on Gaussian expected ranks, a mean and a variance per document)
 
 The only compute implementation is the HIP library ptranking_amd/libptranking_amd.so (C ABI: include/ptranking_amd.h);
 there is no CPU fallback.  Build it with `python -m ptranking_amd.build`.
@@ -27,6 +28,7 @@ from .install import install, install_diversification, install_tree, uninstall  
 from .tree import TreeObjective                     # noqa: F401
 from .diversity import DALETOR, DIV_RANKER_NAMES, EXTRA_DIV_RANKER_NAMES, DivProbRanker, DivQueryBatches     # noqa: F401
 from .rankers import (ApproxNDCG, LambdaLoss, LambdaRank, ListMLE, ListNet, RankNet, STListNet, RankCosine, RankMSE, SoftRank, WassRank, DASALC, MDPRank,  # noqa: F401
-                      SmoothMetric, DEFAULT_PARAS, EXTRA_RANKER_NAMES, METRIC_RANKER_NAMES, RANKER_NAMES, make_ranker_classes)
+                      SmoothMetric, ProbSmoothMetric, DEFAULT_PARAS, EXTRA_RANKER_NAMES, METRIC_RANKER_NAMES, PROB_RANKER_NAMES, RANKER_NAMES,
+                      make_ranker_classes)
 
 __version__ = "0.1.0"

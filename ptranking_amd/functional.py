@@ -16,7 +16,7 @@ from . import _lib
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
            "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
-           "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
+           "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "gaussian_metric_objective", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
 # launch table, and it draws its own)
@@ -236,6 +236,46 @@ def smooth_metric_objective(preds, labels, metric, alpha=10.0, top_k=None, opt_i
                          slots=(("loss_q", None), ("valid_q", None), ("ranks", max(B, 1) * L), ("max_label_ws", 1)))
     if return_parts:
         parts["ranks"] = parts["ranks"][:B * L].view(B, L)
+        return loss, parts
+    return loss
+
+
+def gaussian_metric_objective(mus, vars, labels, metric, top_k=None, opt_ideal=True, max_label=None, lens=None, const_std=None, return_parts=False):
+    """A ranking metric as the optimisation objective, on Gaussian expected ranks: precision_ / AP_ / nERR_ / nDCG_as_opt_objective of
+    ptranking/metric/smooth_metric/metric_as_opt_objective.py:12-257 fed with get_expected_rank(mus, vars)
+    (ptranking/ltr_diversification/util/prob_utils.py:62-80) — every document's score a normal variable with mean mus and variance vars,
+    its rank 1 + sum_{j != i} erfc((mu_i - mu_j) / sqrt(2 (v_i + v_j))) / 2 — the sum over the queries of the reference's one-query loss,
+    differentiable in mus and vars (one launch, both gradients).  vars=None with const_std > 0: every document has the standard deviation
+    const_std (get_expected_rank_const, SoftRank's rank model).  metric, labels, top_k, max_label and lens as smooth_metric_objective;
+    opt_ideal=False weighs the documents by their current position in the order of the expected ranks (ascending, index on ties).  With
+    return_parts also returns dict(loss_q [B], valid_q [B], ranks [B, L] (0 on padding), pos int32 [B, L] (the positions the weights were
+    taken at, -1 on padding), max_label_ws [1])."""
+    if metric not in SMOOTH_METRICS:
+        raise ValueError(f"metric {metric!r} (supported: 'P', 'AP', 'nERR', 'nDCG')")
+    if vars is None:
+        if const_std is None or not float(const_std) > 0.0:
+            raise ValueError(f"without vars, const_std must be > 0 (got {const_std!r})")
+        mus_c, B, L = _matrix("mus", mus.detach() if isinstance(mus, torch.Tensor) else mus)
+        _list_len(L)
+        lens = _counts("lens", lens, B)
+        inputs, checked, head, tail = [mus], [mus_c], [None], (None,)
+    else:
+        if const_std is not None:
+            raise ValueError("give vars or const_std, not both")
+        mus_c, vars_c, lens, B, L = _divprob_scores(mus.detach() if isinstance(mus, torch.Tensor) else mus,
+                                                    vars.detach() if isinstance(vars, torch.Tensor) else vars, lens)
+        inputs, checked, head, tail = [mus, vars], [mus_c, vars_c], [], ()
+    labels = _check("labels", labels, shape=(B, L))
+    if labels.device != mus_c.device:
+        raise RuntimeError("mus and labels live on different devices")
+    n = max(B, 1) * L
+    loss, parts = _fused("ptr_gaussmetric_fwd_bwd", inputs, checked,
+                         [*head, labels, lens, B, L, SMOOTH_METRICS[metric], int(bool(opt_ideal)), int(top_k) if top_k else 0,
+                          C.c_float(0.0 if const_std is None else float(const_std)), C.c_float(-1.0 if max_label is None else float(max_label))],
+                         slots=(("loss_q", None), ("valid_q", None), ("ranks", n), ("pos", n), ("max_label_ws", 1)), tail=tail)
+    if return_parts:
+        parts["ranks"] = parts["ranks"][:B * L].view(B, L)
+        parts["pos"] = parts["pos"][:B * L].view(torch.int32).view(B, L)
         return loss, parts
     return loss
 

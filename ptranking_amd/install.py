@@ -17,7 +17,7 @@ configuration with mode='EntropicOT' (or smooth_type='NG') now raises NotImpleme
 import importlib
 import sys
 
-from .rankers import EXTRA_RANKER_NAMES, METRIC_RANKER_NAMES, RANKER_NAMES, make_ranker_classes
+from .rankers import EXTRA_RANKER_NAMES, METRIC_RANKER_NAMES, PROB_RANKER_NAMES, RANKER_NAMES, make_ranker_classes
 
 _saved = {}
 
@@ -25,7 +25,8 @@ _saved = {}
 def install(names=RANKER_NAMES, ltr_module="ptranking.ltr_adhoc.eval.ltr", extras=False):
     """Rebind `names` inside the reference's ltr module; returns {name: installed class}.  extras=True adds the rankers SURVEY.md 2 marks
     out of scope (EXTRA_RANKER_NAMES: DASALC, MDPRank), which the default drop-in leaves alone.  SmoothMetric (METRIC_RANKER_NAMES) has no
-    reference class to replace: it is bound only when named, install(names=RANKER_NAMES + METRIC_RANKER_NAMES), and uninstall() removes it."""
+    reference class to replace: it is bound only when named, install(names=RANKER_NAMES + METRIC_RANKER_NAMES), and uninstall() removes it; so is
+    ProbSmoothMetric (PROB_RANKER_NAMES), install(names=RANKER_NAMES + PROB_RANKER_NAMES)."""
     if extras:
         names = tuple(names) + tuple(n for n in EXTRA_RANKER_NAMES if n not in names)
     mod = importlib.import_module(ltr_module)
@@ -34,7 +35,7 @@ def install(names=RANKER_NAMES, ltr_module="ptranking.ltr_adhoc.eval.ltr", extra
     done = {}
     for n in names:
         if n not in classes:
-            raise KeyError(f"{n} is not one of {RANKER_NAMES + EXTRA_RANKER_NAMES + METRIC_RANKER_NAMES}")
+            raise KeyError(f"{n} is not one of {RANKER_NAMES + EXTRA_RANKER_NAMES + METRIC_RANKER_NAMES + PROB_RANKER_NAMES}")
         _saved.setdefault((ltr_module, n), getattr(mod, n, None))
         setattr(mod, n, classes[n])
         done[n] = classes[n]

@@ -9,6 +9,7 @@ interface: ptranking_amd.host.PointScorerRanker stand-alone, or the reference's 
 ptranking.base.adhoc_ranker.AdhocNeuralRanker when `ptranking_amd.install()` drops them into
 ptranking.ltr_adhoc.eval.ltr.
 """
+import copy
 import ctypes as C
 import math
 import os
@@ -31,6 +32,10 @@ EXTRA_RANKER_NAMES = ("DASALC", "MDPRank")
 # the smooth-rank metric objectives (ptranking/metric/smooth_metric/metric_as_opt_objective.py): the reference has no ranker class around
 # them, so this one is opt-in by name (install(names=RANKER_NAMES + METRIC_RANKER_NAMES), pa.SmoothMetric)
 METRIC_RANKER_NAMES = ("SmoothMetric",)
+# the same objectives on Gaussian expected ranks (prob_utils.get_expected_rank): the scorer predicts a mean and a variance per document.  No
+# reference class either: bound only by install(names=RANKER_NAMES + PROB_RANKER_NAMES), pa.ProbSmoothMetric
+PROB_RANKER_NAMES = ("ProbSmoothMetric",)
+PROB_SORT_IDS = ('ExpRele', 'RiskAware', 'RERAR')       # ptranking/ltr_diversification/base/div_mdn_ranker.py:43
 
 # default hyper-parameters = the reference's `default_para_dict()`s
 DEFAULT_PARAS = {
@@ -49,6 +54,8 @@ DEFAULT_PARAS = {
     "WassRank": dict(model_id="WassRank", mode='SinkhornOT', sh_itr=20, lam=0.1, smooth_type='ST', norm_type='BothST',   # listwise/wassrank/
                      cost_type='eg', non_rele_gap=100, var_penalty=math.e, gain_base=4),                                 # wassRank.py:97-104
     "SmoothMetric": dict(model_id="SmoothMetric", metric='nDCG', alpha=10, top_k=None, opt_ideal=True),   # alpha: listwise/approxNDCG.py:131
+    "ProbSmoothMetric": dict(model_id="ProbSmoothMetric", metric='nDCG', top_k=None, opt_ideal=True, limit_delta=0.01, const_std=None,
+                             sort_id='ExpRele'),        # limit_delta, sort_id: ltr_diversification/score_and_sort/div_prob_ranker.py:387-389
 }
 
 
@@ -396,6 +403,61 @@ class SmoothMetricLoss(FusedStepMixin):
                                                            opt_ideal=self.opt_ideal, max_label=self.max_label, lens=kwargs.get('lens')))
 
 
+class ProbSmoothMetricLoss(FusedStepMixin):
+    """P / AP / nERR / nDCG on Gaussian expected ranks.  The scorer's outputs are [B, L, 2] (mean, raw variance) or, with const_std, [B, L]."""
+    max_label = None
+    const_std = None
+    limit_delta = 0.01
+    sort_id = 'ExpRele'
+    risk_b = 0.1                                        # div_mdn_ranker.py:46
+
+    def uniform_eval_setting(self, **kwargs):
+        eval_dict = kwargs['eval_dict']
+        if eval_dict["do_validation"] and not eval_dict['vali_metric'] == self.metric:
+            eval_dict['vali_metric'] = self.metric
+
+    def _head(self, batch_components):
+        """Scorer outputs -> (means [B, L], variances [B, L] or None), the K = 1 head of div_mdn_ranker.py:276-294."""
+        if self.const_std is not None:
+            return batch_components, None
+        to_var = torch.exp if self.limit_delta is None else (lambda s: torch.sigmoid(s) * self.limit_delta)     # representing sigma^2
+        return batch_components[:, :, 0], to_var(batch_components[:, :, 1])
+
+    def _sort_scores(self, batch_mus, batch_vars, lens=None):
+        """The scores a list is ranked by, as diversity.DivProbRanker._sort_scores."""
+        if 'ExpRele' == self.sort_id:
+            return batch_mus
+        if batch_vars is None:
+            batch_vars = torch.full_like(batch_mus, float(self.const_std) ** 2)
+        if 'RiskAware' == self.sort_id:
+            return batch_mus - self.risk_b * batch_vars
+        ranks = F_.expected_ranks(batch_mus.contiguous(), batch_vars.contiguous(), lens=lens)     # 'RERAR'
+        return torch.where(ranks > 0, 1.0 / ranks, torch.zeros_like(ranks))     # padded documents: 0
+
+    def forward(self, batch_q_doc_vectors):
+        B, L = batch_q_doc_vectors.size(0), batch_q_doc_vectors.size(1)
+        out = self.point_sf(batch_q_doc_vectors)
+        return out.view(B, L) if self.const_std is not None else out.view(B, L, 2)
+
+    def predict(self, batch_q_doc_vectors, lens=None):
+        """The scores of sort_id; lens int32 [B]: the list lengths of a padded batch ('RERAR' ranks the valid documents only)."""
+        if lens is None:
+            lens = getattr(self, '_batch_lens', None)             # set by the evaluation loop around a padded batch
+        return self._sort_scores(*self._head(self.forward(batch_q_doc_vectors)), lens=lens)
+
+    def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
+        """metric_as_opt_objective.py on get_expected_rank / get_expected_rank_const (prob_utils.py:62-101); batch_preds are the scorer's
+        outputs as forward() returns them.  A batch whose every query the top-k filter drops still steps, as SmoothMetric's does."""
+        assert 'presort' in kwargs and kwargs['presort'] is True  # aiming for direct usage of ideal ranking
+        assert 'label_type' in kwargs and is_multilabel(kwargs['label_type'])
+        if self.metric == 'nERR' and self.max_label is None and self.data_parallel and dp.is_distributed():
+            raise ValueError("ProbSmoothMetric nERR under data parallelism needs model_para_dict['max_label']: the batch maximum is rank-local")
+        batch_mus, batch_vars = self._head(batch_preds)
+        return self._fused_step(F_.gaussian_metric_objective(batch_mus, batch_vars, batch_std_labels, self.metric, top_k=self.top_k,
+                                                             opt_ideal=self.opt_ideal, max_label=self.max_label, lens=kwargs.get('lens'),
+                                                             const_std=self.const_std))
+
+
 class MDPRankLoss(FusedStepMixin):
     # "torch" (default): the ranking is drawn with torch.multinomial / torch.rand + torch.sort as below; "device": sampling and loss in
     # one launch (functional.mdprank_sampled_loss), samples_per_query rankings per query, from a counter-based generator keyed by a per-call
@@ -659,9 +721,36 @@ def make_ranker_classes(base=PointScorerRanker):
             self.opt_ideal = bool(model_para_dict['opt_ideal'])
             self.max_label = model_para_dict.get('max_label')
 
+    class ProbSmoothMetric(ProbSmoothMetricLoss, FusedScorerMixin, DeviceTrainLoop, DeviceEvaluator, base):
+        """P / AP / nERR / nDCG on Gaussian expected ranks as the training objective: the point scorer predicts a mean and a variance per
+        document (out_dim = 2; heads exp, or sigmoid * limit_delta), or a mean alone with model_para_dict['const_std'] (out_dim = 1, every
+        document the same standard deviation: SoftRank's rank model).  model_para_dict: metric, top_k, opt_ideal, optional max_label,
+        limit_delta, const_std, sort_id ('ExpRele', 'RiskAware', 'RERAR': the scores predict() returns)."""
+
+        def __init__(self, sf_para_dict=None, model_para_dict=None, gpu=False, device=None):
+            sf_id = sf_para_dict['sf_id']
+            if sf_id != 'pointsf':
+                raise NotImplementedError(f"ProbSmoothMetric with sf_id={sf_id!r}: the point scorer (sf_id='pointsf') only")
+            self.metric = model_para_dict['metric']
+            if self.metric not in ('P', 'AP', 'nERR', 'nDCG'):
+                raise NotImplementedError(f"metric {self.metric!r} (supported: 'P', 'AP', 'nERR', 'nDCG')")
+            self.sort_id = model_para_dict.get('sort_id', 'ExpRele')
+            if self.sort_id not in PROB_SORT_IDS:
+                raise ValueError(f"sort_id {self.sort_id!r} (supported: {PROB_SORT_IDS})")
+            self.const_std = model_para_dict.get('const_std')
+            if self.const_std is not None and not float(self.const_std) > 0.0:
+                raise ValueError(f"const_std must be > 0 (got {self.const_std!r})")
+            sf_para_dict = copy.deepcopy(sf_para_dict)                       # the caller's dict keeps its out_dim
+            sf_para_dict[sf_id]['out_dim'] = 1 if self.const_std is not None else 2     # mean | mean and variance, div_mdn_ranker.py:53-56
+            base.__init__(self, id='ProbSmoothMetric', sf_para_dict=sf_para_dict, gpu=gpu, device=device)
+            self.top_k = model_para_dict['top_k']
+            self.opt_ideal = bool(model_para_dict['opt_ideal'])
+            self.max_label = model_para_dict.get('max_label')
+            self.limit_delta = model_para_dict.get('limit_delta', 0.01)
+
     out = dict(RankNet=RankNet, LambdaRank=LambdaRank, LambdaLoss=LambdaLoss, ApproxNDCG=ApproxNDCG, ListNet=ListNet,
                ListMLE=ListMLE, STListNet=STListNet, RankCosine=RankCosine, RankMSE=RankMSE, SoftRank=SoftRank, WassRank=WassRank,
-               DASALC=DASALC, MDPRank=MDPRank, SmoothMetric=SmoothMetric)
+               DASALC=DASALC, MDPRank=MDPRank, SmoothMetric=SmoothMetric, ProbSmoothMetric=ProbSmoothMetric)
     for name, cls in out.items():
         cls.__name__ = cls.__qualname__ = name
         cls.__module__ = __name__
@@ -675,3 +764,4 @@ STListNet, RankCosine, RankMSE = _standalone["STListNet"], _standalone["RankCosi
 SoftRank, DASALC, MDPRank = _standalone["SoftRank"], _standalone["DASALC"], _standalone["MDPRank"]
 WassRank = _standalone["WassRank"]
 SmoothMetric = _standalone["SmoothMetric"]
+ProbSmoothMetric = _standalone["ProbSmoothMetric"]
