@@ -914,8 +914,11 @@ mlp_bwd_dw_lds_kernel(const float *__restrict__ A, int lda, const float *__restr
 }
 __host__ __device__ constexpr size_t dw_lds_bytes(int NTW, int RB) { return (size_t)(2 * RB * kAL + 2 * RB * (64 * NTW + 16)) * sizeof(float); }
 
-// grad[i] = sum_b ws[b][i], fixed order.  A 1024-thread workgroup owns 64 consecutive i: wave w sums the partials
-// b = w, w+16, ... (4 independent accumulators keep 4 loads in flight), then one wave adds the 16 wave totals in order.
+// grad[i] = sum_b ws[b][i], fixed order.  A 1024-thread workgroup owns 128 consecutive i, every lane two of them (i and i + 64): wave w sums
+// the partials b = w, w+16, ... of both (4 independent accumulators each: 8 loads in flight), then waves 0 / 1 add the 16 wave totals of the
+// first / second 64 elements in order — per element the additions of the one-element-per-lane form this replaces, bit for bit.  Two elements per
+// lane halve the grid: (n + 127) / 128 (+ 1) workgroups — 267 at 34 001 parameters — are resident at once on 256 CUs x 2 workgroups, where
+// the 533 of the 64-element form ran a second, nearly empty round of the whole chain partials -> barrier -> optimiser state -> stores.
 // Entries i >= tail_begin (d w_out, d b_out: written by the dZ kernel's smaller grid) only have nblk_tail partials.
 // Optional epilogue of the partial reduction: the optimiser step on the element just reduced (single-device training: no all-reduce sits
 // between gradient and step) and the sum of the loss slots of the batch — three launches fewer per train step.
@@ -926,10 +929,12 @@ struct OptStep {
     const float *loss_q; int nq; float *loss_out;
     uint8_t *wimg; int F, NL;      // r6: the bf16x6 forward's weight image, refreshed element by element behind the step (NULL: none)
 };
+constexpr int kRedElems = 128;               // elements per workgroup of reduce_partials_kernel
+inline unsigned reduce_grid(size_t n, bool loss_block) { return (unsigned)((n + kRedElems - 1) / kRedElems) + (loss_block ? 1u : 0u); }
 __global__ void __launch_bounds__(1024)
 reduce_partials_kernel(const float *__restrict__ ws, int nblk, int nblk_tail, size_t tail_begin, size_t stride, size_t n,
                        float *__restrict__ grad, OptStep o) {
-    __shared__ float part[16][64];
+    __shared__ float part[16][kRedElems];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (o.loss_out && blockIdx.x == gridDim.x - 1) {
         // one extra block: the loss slots of the batch, summed by the function sum_f32_kernel calls (ptr_device.h block1024_sum): the fused
@@ -938,25 +943,49 @@ reduce_partials_kernel(const float *__restrict__ ws, int nblk, int nblk_tail, si
         if (threadIdx.x == 0) o.loss_out[0] = tot;
         return;
     }
-    const size_t i = (size_t)blockIdx.x * 64 + lane;
-    const bool ok = i < n;
-    const size_t ic = ok ? i : n - 1;
-    const int nb = ic >= tail_begin ? nblk_tail : nblk;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    // the two elements of this lane (clamped to n - 1 past the end: loaded, never stored)
+    const size_t ia = (size_t)blockIdx.x * kRedElems + lane, ib = ia + 64;
+    const size_t ica = ia < n ? ia : n - 1, icb = ib < n ? ib : n - 1;
+    const int nba = ica >= tail_begin ? nblk_tail : nblk, nbb = icb >= tail_begin ? nblk_tail : nblk;
+    const int nbc = nba < nbb ? nba : nbb;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
     int b = w;
-    for (; b + 48 < nb; b += 64) {
-        s0 += ws[(size_t)b * stride + ic];
-        s1 += ws[(size_t)(b + 16) * stride + ic];
-        s2 += ws[(size_t)(b + 32) * stride + ic];
-        s3 += ws[(size_t)(b + 48) * stride + ic];
+    for (; b + 48 < nbc; b += 64) {              // both elements: 8 independent loads
+        a0 += ws[(size_t)b * stride + ica];
+        a1 += ws[(size_t)(b + 16) * stride + ica];
+        a2 += ws[(size_t)(b + 32) * stride + ica];
+        a3 += ws[(size_t)(b + 48) * stride + ica];
+        b0 += ws[(size_t)b * stride + icb];
+        b1 += ws[(size_t)(b + 16) * stride + icb];
+        b2 += ws[(size_t)(b + 32) * stride + icb];
+        b3 += ws[(size_t)(b + 48) * stride + icb];
     }
-    for (; b < nb; b += 16) s0 += ws[(size_t)b * stride + ic];
-    part[w][lane] = (s0 + s1) + (s2 + s3);
+    // what is left of either element, in the same order.  The two 4-accumulator loops run no iteration unless the elements' counts differ: only
+    // in the ONE workgroup that straddles tail_begin, and only on the layer-wise path (every other caller passes tail_begin = n)
+    int ba = b, bb = b;
+    for (; ba + 48 < nba; ba += 64) {
+        a0 += ws[(size_t)ba * stride + ica];
+        a1 += ws[(size_t)(ba + 16) * stride + ica];
+        a2 += ws[(size_t)(ba + 32) * stride + ica];
+        a3 += ws[(size_t)(ba + 48) * stride + ica];
+    }
+    for (; bb + 48 < nbb; bb += 64) {
+        b0 += ws[(size_t)bb * stride + icb];
+        b1 += ws[(size_t)(bb + 16) * stride + icb];
+        b2 += ws[(size_t)(bb + 32) * stride + icb];
+        b3 += ws[(size_t)(bb + 48) * stride + icb];
+    }
+    for (; ba < nba; ba += 16) a0 += ws[(size_t)ba * stride + ica];
+    for (; bb < nbb; bb += 16) b0 += ws[(size_t)bb * stride + icb];
+    part[w][lane] = (a0 + a1) + (a2 + a3);
+    part[w][64 + lane] = (b0 + b1) + (b2 + b3);
     __syncthreads();
-    if (w == 0 && ok) {
-        float s = part[0][lane];
+    const int col = 64 * w + lane;                                  // waves 0 / 1: the first / second 64 elements
+    const size_t i = (size_t)blockIdx.x * kRedElems + col;
+    if (w < 2 && i < n) {
+        float s = part[0][col];
 #pragma unroll
-        for (int k = 1; k < 16; ++k) s += part[k][lane];
+        for (int k = 1; k < 16; ++k) s += part[k][col];
         if (grad) grad[i] = s;                          // (ptr_opt_step_loss: ws IS the gradient, one "partial" — nothing to write back)
         // fused optimiser step on the element just reduced: the arithmetic of adam_kernel / adagrad_kernel / rmsprop_kernel, bit for bit
         if (o.kind == PTR_OPT_ADAM) {
@@ -1147,7 +1176,7 @@ extern "C" int ptr_opt_step_loss(float *params, const float *grad, int64_t n, in
     else if (opt_kind == PTR_OPT_ADAGRAD) o.lr = lr / (1.0f + (float)(step - 1) * hyper1);
     else o.lr = lr;
     const size_t nn = (size_t)n;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((nn + 63) / 64) + (loss_out ? 1 : 0)), dim3(1024), 0, as_stream(stream), grad, 1, 1, nn,
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(nn, loss_out != nullptr)), dim3(1024), 0, as_stream(stream), grad, 1, 1, nn,
                        nn, nn, (float *)nullptr, o);
     return check_hip(hipGetLastError(), who);
 }
@@ -1166,7 +1195,7 @@ int ptr::mlp_backward_impl(const char *who, const float *X, const float *params,
                                                         : launch_bwd_fused(X, params, acts, dpreds, a, ws, st, who)) return e;
         const int nb = bwd_fused_grid(R);
         const size_t NPf = n_params(NL, F);
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((NPf + 63) / 64) + (opt.loss_out ? 1 : 0)), dim3(1024), 0, st, ws, nb, nb, NPf, NPf, NPf,
+        hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(NPf, opt.loss_out != nullptr)), dim3(1024), 0, st, ws, nb, nb, NPf, NPf, NPf,
                            grad, opt);
         return check_hip(hipGetLastError(), who);
     }
@@ -1233,7 +1262,7 @@ int ptr::mlp_backward_impl(const char *who, const float *X, const float *params,
         if (e) return e;
     }
     // 3. one deterministic reduction of all partials into the flat gradient
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((NP + 63) / 64) + (opt.loss_out ? 1 : 0)), dim3(1024), 0, st, ws, nblk,
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(NP, opt.loss_out != nullptr)), dim3(1024), 0, st, ws, nblk,
                        tail ? bwd_fused_grid(R) : grid_dz, tail ? off_W(1, F) : off_wout(NL, F), NP, NP, grad, opt);
     return check_hip(hipGetLastError(), who);
 }

@@ -82,10 +82,19 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     const uint32_t thr = a.p_drop > 0.0f ? drop_thr(a.p_drop) : 0u;
     const float scale = a.p_drop > 0.0f ? 1.0f / (1.0f - a.p_drop) : 1.0f;
     const bool chain = W < 7;
-    // every image starts as zeros (rows of documents past R in the last slab are read before anything was written there: 0 x NaN = NaN)
-    for (int i = tid; i < kB6Lds / 16; i += 512) reinterpret_cast<u32x4 *>(smem_b6)[i] = u32x4{0u, 0u, 0u, 0u};
-    __syncthreads();                       // before the first DMA lands in the staging area
-    B6_EDGE();                                                       // E1 LDS zeroed
+    // No zero fill of the LDS (it was 2.3 K cycles of every launch): every byte that is read has been written by this launch before.
+    //   staging area  42 DMA pieces of 1 KB = 3 x kB6STG per prefetch, all of it, whatever R is.  THE ONE HARDWARE ASSUMPTION: a piece past the end
+    //                 of `acts` (the last layer's second row tile of a last slab with <= 16 rows, e.g. rows 48..63 at R = 40) is an out-of-range
+    //                 buffer load to LDS, and it must WRITE zeros there as an out-of-range load to registers returns zeros — `awo` takes
+    //                 fmaf(0, a3, awo) of those rows, so a leftover Inf / NaN pattern would reach d w_out (the fill used to cover the first
+    //                 prefetch, the previous slab's finite values the later ones)
+    //   ZA / ZB, A2, A1  a staging pass writes all 32 rows x 112 columns of its three images (7 chain waves x 2 document tiles x 64 lanes x 4
+    //                 columns, no condition on R: rows past R carry dLoss/dscore = 0 from the out-of-range load and the finite activations the
+    //                 forward stores for the whole last row tile); the chain writes all of its output image the same way, in front of the
+    //                 barrier its readers wait at
+    //   XI            stage_x writes tiles 0..8 = all 144 columns of all 32 rows in front of B3 (rows past R: zeros from the out-of-range load)
+    //   w_out         112 floats written below, 112 read
+    B6_EDGE();                                                       // E1 (no LDS fill any more)
 
     // ---- persistent registers: ONE array of 42 x 4, used by role (a single instruction stream allocates the maximum over the waves anyway —
     // separate arrays for the chain fragments and the accumulators would add up: 296 spills in the first build):
@@ -294,7 +303,7 @@ mlp_bwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     const int slab0 = blockIdx.x;
     prefetch(slab0 < nslabs ? slab0 : nslabs - 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                       // zero fill + first staging visible to every wave
+    __syncthreads();                       // w_out + first staging area visible to every wave
     B6_EDGE();                                                       // E3 first slab's activations landed (r6: gathering W^T BEHIND the first DMA instead of in front of it was measured — 12.5 K against 11.7 K cycles to this point: not kept)
 
 #ifdef PTR_B6_TRACE       // experiment builds: shader-clock stamps of workgroup 0 behind its partial gradient (ws is sized for 2 partials per CU)

@@ -271,7 +271,13 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
     // tiles of 32 documents: workgroup b, wave w, pass it -> tile (it * gridDim.x + b) * 8 + w; every wave of a workgroup runs the same
     // number of passes (lockstep), a wave whose tile lies past the end runs masked (clamped loads, no stores)
     const int npass = (ntiles + NW * (int)gridDim.x - 1) / (NW * (int)gridDim.x);
-    auto tile_of = [&](int it) __attribute__((always_inline)) { return (it * (int)gridDim.x + (int)blockIdx.x) * NW + wave; };
+    // The TRAINING form walks the passes from the last to the first (rows are independent: preds and acts are the same bits either way): it
+    // ends on rows 0 onward, the rows the backward starts with, while their X and activations are the most recent lines of the 256 MiB
+    // Infinity Cache (measured: DESIGN.md §0, "The fixed per-step cost").  The tile BEHIND the last pass (it = npass: the run-ahead X loads of
+    // the last iteration) lies past the end in the forward order and is masked by load_xq's row test; in the reversed order the formula would
+    // go NEGATIVE and pass that signed test with a wrapped scalar offset, so the pass index is clamped at 0: the run-ahead then re-reads this
+    // wave's own tile of pass 0 — rows inside X or masked like any row past R — and nobody uses the values.
+    auto tile_of = [&](int it) __attribute__((always_inline)) { return ((TRAIN ? max(npass - 1 - it, 0) : it) * (int)gridDim.x + (int)blockIdx.x) * NW + wave; };
     // Per-lane constants, one register each; everything that depends on the tile is a SCALAR added per use (s_mul / s_add on the scalar
     // unit, one v_add or an soffset operand on the vector side) — per-tile VGPR copies of rows, offsets and keys cost a dozen registers
     // this kernel does not have:
@@ -431,7 +437,7 @@ mlp_fwd_x6_kernel(const float *__restrict__ X, const float *__restrict__ P, cons
             // the burst to drain: DESIGN.md §0, Forward)
             if constexpr (LAST) {
 #pragma unroll
-                for (int q = 0; q < 2 * DT; ++q) { load_xq(raw[0], t32n, 0, q); load_xq(raw[1], t32n, n1 > 1 ? 1 : 0, q); }      // (past the end: zeros, never used)
+                for (int q = 0; q < 2 * DT; ++q) { load_xq(raw[0], t32n, 0, q); load_xq(raw[1], t32n, n1 > 1 ? 1 : 0, q); }      // (behind the last pass: never used — forward order: past the end, masked to zeros; reversed: this wave's tile of pass 0 again, see tile_of)
                 X6_SB();
             }
             abase = slice_step(I0{}, abase, bp[2], nowork, KNone{}, Early{}, Full{});

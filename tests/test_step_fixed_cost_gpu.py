@@ -1,0 +1,269 @@
+"""GPU: the fixed per-step cost around the fused scorer kernels, bit for bit.
+
+* `reduce_partials_kernel` (csrc/scorer.hip) gives every lane two elements so that one resident round of workgroups covers every parameter.
+  The additions per element are the documented ones: wave w sums the partials b = w, w + 16, ... with four accumulators, (s0 + s1) + (s2 + s3),
+  then the 16 wave totals in order.  The test re-adds the partials the backward left in the caller's workspace on the CPU in fp32 in that order
+  and requires the returned gradient to be equal — on the single-pass backward (every entry has the same number of partials) and on the
+  layer-wise path (PTR_BWD_FUSED=0: entries from off_W(1) on have fewer partials, and that border lies inside a workgroup).
+* `ptr_opt_step_loss` (the same kernel over one partial) against the separate optimiser kernels and ptr_sum_f32.
+* `mlp_bwd_x6_kernel` (csrc/scorer_bwd_x6.hip) no longer zero-fills its LDS: a last partial slab (rows past R) must give the bits of the same
+  rows padded to a whole slab with dLoss/dscore = 0 on the padding.
+* The hand-over in the real training path (`ptr_train_step`: the two-element reduction with the fused optimiser AND the image refresh, the backward
+  without its zero fill on a partial slab): a ranker that reuses the weight image, one that rebuilds it every step and one on the three-call path.
+* The training form of `mlp_fwd_x6_kernel` (csrc/scorer_x6.hip) walks its passes from the last to the first: rows are independent, so more
+  than one pass must give the bits of the same rows run as two separate calls.
+"""
+import ctypes as C
+
+import pytest
+import torch
+
+from ptranking_amd import scorer as _scorer
+
+pytestmark = pytest.mark.gpu
+
+NL = 3
+KH = 100
+
+
+def _n_cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _off_w1(F):
+    return KH * F + KH
+
+
+def _forward_backward(F, R, p, seed, X, w, params, ws, dz=None):
+    from ptranking_amd import _lib
+    st = _lib.current_stream(X.device)
+    preds = torch.empty(R, device="cuda")
+    acts = _scorer.alloc_acts(R, NL, "cuda")
+    _lib.call("ptr_mlp_forward", _lib.ptr(X), _lib.ptr(params), R, F, NL, 1, C.c_float(p), C.c_uint64(seed), _lib.ptr(preds), _lib.ptr(acts), st)
+    g = torch.full_like(params, float("nan"))
+    _lib.call("ptr_mlp_backward", _lib.ptr(X), _lib.ptr(params), _lib.ptr(acts), _lib.ptr(w), R, F, NL, C.c_float(p), C.c_uint64(seed),
+              None if dz is None else _lib.ptr(dz), _lib.ptr(ws), _lib.ptr(g), st)
+    torch.cuda.synchronize()
+    return g
+
+
+def _readd(P, nb_of_entry):
+    """The documented order on the CPU in fp32.  P: [partials][n] float32 CPU; nb_of_entry: list of (begin, end, number of partials)."""
+    out = torch.empty(P.shape[1], dtype=torch.float32)
+    for lo, hi, nb in nb_of_entry:
+        Q = P[:, lo:hi]
+        tot = []
+        for w in range(16):
+            s = [torch.zeros(hi - lo, dtype=torch.float32) for _ in range(4)]
+            b = w
+            while b + 48 < nb:
+                for k in range(4):
+                    s[k] = s[k] + Q[b + 16 * k]
+                b += 64
+            while b < nb:
+                s[0] = s[0] + Q[b]
+                b += 16
+            tot.append((s[0] + s[1]) + (s[2] + s[3]))
+        acc = tot[0]
+        for k in range(1, 16):
+            acc = acc + tot[k]
+        out[lo:hi] = acc
+    return out
+
+
+# R = 96: 3 partials (the `b < nb` remainder loop alone); 32 * 300: one partial per CU, some workgroups hold two slabs; 32 * 64 + 5: tail rows
+@pytest.mark.parametrize("R", [96, 32 * 300, 32 * 64 + 5])
+def test_reduction_is_the_documented_order_on_the_single_pass_backward(R):
+    from ptranking_amd import _lib
+    from ptranking_amd.scorer import FusedPointScorer
+    F = 136
+    torch.manual_seed(R)
+    fused = FusedPointScorer(F, num_layers=NL, dropout=0.1).cuda()
+    params = fused.flat.data
+    n = params.numel()
+    X = torch.randn(R, F, device="cuda"); w = torch.randn(R, device="cuda")
+    ws = torch.full((_lib.query("ptr_mlp_backward_ws_floats", F, NL),), float("nan"), device="cuda")
+    g = _forward_backward(F, R, 0.1, 11 + R, X, w, params, ws)
+    nb = min((R + 31) // 32, _n_cus())
+    P = ws[:nb * n].reshape(nb, n).cpu()
+    assert torch.isfinite(P).all(), "every workgroup writes its whole partial"
+    want = _readd(P, [(0, n, nb)])
+    assert torch.equal(g.cpu(), want)
+
+
+def test_reduction_keeps_the_tail_rule_on_the_layer_wise_path(monkeypatch):
+    """PTR_BWD_FUSED=0: the first layer's entries [0, off_W(1)) have one partial per dW workgroup (two per CU), everything behind them one per
+    workgroup of the tail kernel — and off_W(1) = 13 700 is no multiple of the 128 elements of a reduction workgroup, nor of 64."""
+    from ptranking_amd import _lib
+    from ptranking_amd.scorer import FusedPointScorer
+    monkeypatch.setenv("PTR_BWD_FUSED", "0")
+    F, R = 136, 32 * 64 + 5
+    torch.manual_seed(3)
+    fused = FusedPointScorer(F, num_layers=NL, dropout=0.1).cuda()
+    params = fused.flat.data
+    n = params.numel()
+    X = torch.randn(R, F, device="cuda"); w = torch.randn(R, device="cuda")
+    ws = torch.full((_lib.query("ptr_mlp_backward_ws_floats", F, NL),), float("nan"), device="cuda")
+    dz = torch.empty(NL * R * 112, device="cuda")
+    g = _forward_backward(F, R, 0.1, 5, X, w, params, ws, dz)
+    nblk, ntail = 2 * _n_cus(), min((R + 31) // 32, _n_cus())
+    P = ws[:nblk * n].reshape(nblk, n).cpu()
+    t0 = _off_w1(F)
+    assert torch.isfinite(P[:, :t0]).all() and torch.isfinite(P[:ntail, t0:]).all()
+    assert torch.isnan(P[ntail:, t0:]).all(), "the entries behind the first layer have only the tail kernel's partials"
+    want = _readd(P, [(0, t0, nblk), (t0, n, ntail)])
+    assert torch.equal(g.cpu(), want)
+
+
+# 34 001 = the parameters of F = 136 (81 elements in the last workgroup: its second half is partly past the end); 33 961: 41 (wholly past the end);
+# 5: a single workgroup
+@pytest.mark.parametrize("n", [34001, 33961, 5])
+@pytest.mark.parametrize("kind", ["Adam", "Adagrad", "RMS"])
+def test_opt_step_loss_equals_the_separate_kernels(kind, n):
+    from ptranking_amd import _lib
+    from ptranking_amd.scorer import FLAT_OPTIMIZERS
+    torch.manual_seed(n)
+    nq = 777
+    p0 = torch.randn(n, device="cuda"); g = torch.randn(n, device="cuda"); lq = torch.rand(nq, device="cuda")
+    pa_, pb_ = torch.nn.Parameter(p0.clone()), torch.nn.Parameter(p0.clone())
+    kw = dict(lr=1e-2, weight_decay=1e-3)
+    oa, ob = FLAT_OPTIMIZERS[kind]([pa_], **kw), FLAT_OPTIMIZERS[kind]([pb_], **kw)
+    st = _lib.current_stream(p0.device)
+    want = torch.empty(1, device="cuda")
+    _lib.call("ptr_sum_f32", _lib.ptr(lq), nq, C.c_float(1.0), _lib.ptr(want), st)
+    for it in range(3):
+        pa_.grad = g * (it + 1); pb_.grad = g * (it + 1)
+        oa.step()
+        k, lr, h1, h2, eps, wd, step, s1, s2 = ob.fused_step_args(pb_)
+        got = torch.empty(1, device="cuda")
+        _lib.call("ptr_opt_step_loss", _lib.ptr(pb_), _lib.ptr(pb_.grad), C.c_int64(n), k, C.c_float(lr), C.c_float(h1), C.c_float(h2), C.c_float(eps),
+                  C.c_float(wd), step, _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(lq), nq, _lib.ptr(got), st)
+        assert torch.equal(pa_.detach(), pb_.detach()), (kind, it)
+        for key, sa in oa.state[pa_].items():                       # the moments / accumulators too
+            if torch.is_tensor(sa):
+                assert torch.equal(sa, ob.state[pb_][key]), (kind, it, key)
+        assert torch.equal(got, want)
+        assert torch.equal(pb_.grad, g * (it + 1))                  # the gradient is read, not rewritten
+
+
+# F = 136: the single-pass kernel (mlp_bwd_x6_kernel<9>); F = 200: its TAIL form <0> + the first layer's dW kernel.  R = 40: one whole and one
+# partial slab; 32 * 64 + 5: 65 slabs, the last one partial
+@pytest.mark.parametrize("F,R", [(136, 40), (136, 32 * 64 + 5), (200, 40), (200, 32 * 64 + 5)])
+def test_partial_last_slab_equals_the_zero_gradient_padding(F, R, monkeypatch):
+    """Rows past R of the last slab contribute nothing, whatever the LDS held at launch: the gradient equals, number for number, that of the
+    batch padded to whole slabs with arbitrary documents whose dLoss/dscore is 0 (their products are exact zeros; same slabs, same
+    workgroups, same order) — of every entry the slab kernel itself produces."""
+    from ptranking_amd import _lib
+    from ptranking_amd.scorer import FusedPointScorer
+    monkeypatch.delenv("PTR_BWD_X6", raising=False)
+    torch.manual_seed(F + R)
+    fused = FusedPointScorer(F, num_layers=NL, dropout=0.1).cuda()
+    params = fused.flat.data
+    Rp = (R + 31) // 32 * 32
+    Xp = torch.randn(Rp, F, device="cuda"); wp = torch.randn(Rp, device="cuda")
+    wp[R:] = 0.0
+    X = Xp[:R].contiguous(); w = wp[:R].contiguous()
+    ws = torch.empty(_lib.query("ptr_mlp_backward_ws_floats", F, NL), device="cuda")
+    dz = torch.empty(NL * Rp * 112, device="cuda") if F == 200 else None
+    g = _forward_backward(F, R, 0.1, 21, X, w, params, ws, dz)
+    gp = _forward_backward(F, Rp, 0.1, 21, Xp, wp, params, ws, dz)
+    assert torch.isfinite(g).all()
+    # F = 200: the first layer's entries come from the row-contraction dW kernel, whose split of the rows over its workgroups depends on R
+    lo = 0 if F == 136 else _off_w1(F)
+    assert torch.equal(g[lo:], gp[lo:])
+
+
+def test_training_forward_pass_order_leaves_every_row_alone():
+    """65 536 + 96 rows are 2051 tiles of 32 documents — more than the 2048 one pass of 256 workgroups x 8 waves takes.  The same rows as two calls
+    (the second one's dropout seed shifted by its row offset, csrc/ptr_dropout.h / dp.fold_row_offset): equal scores and stored activations."""
+    from ptranking_amd import _lib
+    from ptranking_amd.dp import fold_row_offset
+    from ptranking_amd.scorer import FusedPointScorer, x6_workspace
+    F, R, R0, seed = 136, 65536 + 96, 65536, 1234567
+    torch.manual_seed(9)
+    fused = FusedPointScorer(F, num_layers=NL, dropout=0.1).cuda()
+    X = torch.randn(R, F, device="cuda")
+    wimg = x6_workspace(X.device, F, NL)
+    assert wimg is not None
+    st = _lib.current_stream(X.device)
+
+    def fwd(Xs, sd):
+        n = Xs.shape[0]
+        preds = torch.full((n,), float("nan"), device="cuda")
+        acts = torch.full((_scorer.acts_floats(n, NL),), float("nan"), device="cuda")
+        _lib.call("ptr_mlp_forward_x6", _lib.ptr(Xs), _lib.ptr(fused.flat.data), n, F, NL, 1, C.c_float(0.1), C.c_uint64(sd), _lib.ptr(preds), _lib.ptr(acts),
+                  _lib.ptr(wimg), st)
+        torch.cuda.synchronize()
+        return preds, _scorer.acts_rowmajor(acts, n, NL)
+    p_all, a_all = fwd(X, seed)
+    p_lo, a_lo = fwd(X[:R0].contiguous(), seed)
+    p_hi, a_hi = fwd(X[R0:].contiguous(), fold_row_offset(seed, R0))
+    assert torch.isfinite(p_all).all()
+    assert torch.equal(p_all, torch.cat([p_lo, p_hi]))
+    assert torch.equal(a_all, torch.cat([a_lo, a_hi], dim=1))
+
+
+# 3 x 40 documents: 120 rows, the last slab partial (24 rows); 9 x 128: 36 whole slabs
+@pytest.mark.parametrize("B,L", [(3, 40), (9, 128)])
+def test_weight_image_hand_over_keeps_every_bit(B, L, monkeypatch):
+    """Three rankers on the same weights and batches under PTR_MLP_X6=2: `a` hands the weight image from the optimiser launch to the next forward,
+    `b` rebuilds it every step (reuse_weight_image = False), `c` takes the three-call path (separate forward / backward / optimiser kernels).  Four
+    steps with an evaluation forward and a torch in-place edit of the parameters in between: loss, parameters and optimiser state equal, bit for
+    bit; and the slices the optimiser launch left in the image equal, byte for byte, what a fresh x6_prep_kernel writes for the same parameters.
+    (The issue's clause on the backward's W^T fragments in the image is absent: that part of the image is not built.)"""
+    import copy
+    import numpy as np
+    import ptranking_amd as pa
+    from ptranking_amd import _lib
+    from ptranking_amd.scorer import x6_workspace
+    monkeypatch.setenv("PTR_MLP_X6", "2")
+    F = 136
+    sf = {"sf_id": "pointsf", "opt": "Adam", "lr": 1e-3,
+          "pointsf": dict(num_features=F, num_layers=NL, AF="R", TL_AF="S", apply_tl_af=False, BN=False, bn_type=None, bn_affine=False, dropout=0.1)}
+    rng = np.random.default_rng(B * L)
+    X = torch.from_numpy(rng.standard_normal((B, L, F)).astype(np.float32)).cuda()
+    Yn = rng.choice(5, size=(B, L), p=[0.5147, 0.3250, 0.1339, 0.0183, 0.0081]).astype(np.float32)
+    Yn[:, 0] = np.maximum(Yn[:, 0], 1)
+    Y = torch.from_numpy(-np.sort(-Yn, axis=1)).cuda()
+    kw = dict(epoch_k=1, presort=True, label_type=pa.LABEL_TYPE.MultiLabel)
+
+    def run(reuse, single):
+        """The whole sequence of one ranker, back to back (the rankers share ONE image buffer: interleaving them would never hand it over)."""
+        torch.manual_seed(12)
+        r = pa.LambdaRank(sf_para_dict=copy.deepcopy(sf), model_para_dict=dict(sigma=1.0), gpu=True, device="cuda:0")
+        r.init(); r.point_sf.dropout = 0.1; r.train_mode()
+        r.reuse_weight_image, r.single_call_step = reuse, single
+        trail, current = [], []
+        for i in range(4):
+            if i == 2:
+                r.eval_mode(); _ = r.predict(X); r.train_mode()       # rebuilds the image through the other entry point
+            if i == 3:
+                with torch.no_grad():
+                    r.point_sf.flat.mul_(0.999)                         # torch moves the parameters: the image is stale
+            torch.manual_seed(300 + i)
+            loss = r.train_op(X, Y, **kw)[0]
+            st = r.optimizer.state[r.point_sf.flat]
+            trail.append((loss.detach().clone(), r.point_sf.flat.detach().clone(), st["exp_avg"].clone(), st["exp_avg_sq"].clone(), int(st["step"])))
+            if single:
+                current.append(int(next(iter(r._direct_buffers.values()))["desc"].wimg_current))
+        return r, trail, current
+
+    a, ta, cur_a = run(True, True)
+    # the image as a's last optimiser launch left it, against a fresh prep of a's parameters (an evaluation forward through the public entry point)
+    wimg = x6_workspace(X.device, F, NL)
+    n_img = (5 + 4 * (NL - 1)) * 21504                                  # ceil(136 / 32) + 4 + 4 slices of 21 504 bytes
+    left = wimg[:n_img].clone()
+    preds = torch.empty(B * L, device="cuda")
+    _lib.call("ptr_mlp_forward_x6", _lib.ptr(X.reshape(B * L, F)), _lib.ptr(a.point_sf.flat.data), B * L, F, NL, 0, C.c_float(0.0), C.c_uint64(0),
+              _lib.ptr(preds), None, _lib.ptr(wimg), _lib.current_stream(X.device))
+    torch.cuda.synchronize()
+    assert torch.equal(left, wimg[:n_img]), "the optimiser launch keeps the image what x6_prep_kernel makes of the new parameters"
+    _, tb, cur_b = run(False, True)
+    _, tc, _ = run(True, False)
+    assert cur_a == [0, 1, 0, 0], cur_a                                 # handed over exactly when nothing touched parameters or image in between
+    assert cur_b == [0, 0, 0, 0], cur_b
+    for i in range(4):
+        for other in (tb, tc):
+            assert ta[i][4] == other[i][4]
+            for x, y in zip(ta[i][:4], other[i][:4]):
+                assert torch.equal(x, y), i
