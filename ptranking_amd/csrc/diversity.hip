@@ -126,7 +126,7 @@ alphadcg_kernel(const float *__restrict__ preds, const float *__restrict__ rele,
 // ---------------------------------------------------------------------------------------------------------------- metrics
 struct DivCutoffs { int nk; int kmax; int k[PTR_MAX_CUTOFFS]; };
 
-// One group per query ranks the scores exactly as ptr_sort_desc does (count_ranks: value descending, original index ascending) and
+// One group per query ranks the scores exactly as ptr_sort_desc does (count_ranks: value descending, NaN first, original index ascending) and
 // scatters the top documents into `order`; then ONE wavefront walks the ranks 0 .. min(max(ks), n) - 1 with lane = subtopic: the
 // system ranking and the ideal one (the input order, ranker.py:296) side by side, every running quantity per lane, a cross-lane sum
 // only at the cut-offs.  LDS per group: keys[Lp] | order[Lp] | red[4].
@@ -150,14 +150,26 @@ div_metrics_kernel(const float *__restrict__ preds, const float *__restrict__ re
 
     float own[DPT];
     int rk[DPT];
+    bool isnan = false;
 #pragma unroll
     for (int m = 0; m < DPT; ++m) {
         const int i = t + m * G;
         own[m] = i < n ? preds[(size_t)q * L + i] : -INFINITY;
+        isnan |= own[m] != own[m];
         if (i < Lp) { keys[i] = own[m]; order[i] = 0; }
     }
+    // A NaN score ranks first, as in ptr_sort_desc and torch.sort; the float compares of the plain count would give it rank 0 beside the
+    // true maximum (two documents in order[0], none in order[n - 1]).  The vote rides on the barrier the staging needs anyway: each
+    // wavefront leaves its own in red[] ahead of it (group_sum() below opens with a barrier before it reuses red).
+    static_assert(G == kWave || G == 4 * kWave, "red[] holds one vote per wavefront of a four-wave group");
+    bool anynan = __any(isnan);
+    if constexpr (G != kWave) {
+        if ((t & 63) == 0) red[t >> 6] = anynan ? 1.0f : 0.0f;
+    }
     __syncthreads();
-    count_ranks<G, DPT>(keys, n, t, own, rk);
+    if constexpr (G != kWave) anynan = (red[0] + red[1]) + (red[2] + red[3]) != 0.0f;
+    if (anynan) count_ranks<G, DPT, false, true>(keys, n, t, own, rk);
+    else count_ranks<G, DPT>(keys, n, t, own, rk);
 #pragma unroll
     for (int m = 0; m < DPT; ++m)
         if (t + m * G < n && rk[m] >= 0 && rk[m] < n) order[rk[m]] = t + m * G;

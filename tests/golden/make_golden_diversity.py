@@ -19,7 +19,13 @@ runs, ptranking/base/ranker.py:636-669).
                        order, ranker.py:296), andcg_k1 / err_ia_k1 / nerr_ia_k1 = the single-cut-off functions at k1 <= L, valid = the
                        evaluator's skip rule (ranker.py:282).
 
-The archive is written with fixed zip timestamps so that a rerun reproduces it bit for bit.
+tests/golden/diversity_edge.npz (a second archive, so that diversity.npz keeps its bytes) holds what the reference returns for NON-FINITE scores:
+
+  nonfinite/<case>/... preds fp32 [1, L] with one NaN, two +inf and one -inf score (and each kind alone), rele uint8 [T, L], rt, top_k;
+                       loss32 / grad32 and loss64 / grad64 as above.  Robust_Sigmoid's two torch.where take a NaN difference (a NaN score,
+                       inf - inf) as 0.5, so loss and gradient stay finite: asserted here.
+
+Both archives are written with fixed zip timestamps so that a rerun reproduces them bit for bit.
 """
 import io
 import os
@@ -160,7 +166,40 @@ def main():
             store[f"metrics/{name}/{k}"] = np.asarray(v)
         print(f"metrics {name:22s} andcg {np.round(a, 4)}", flush=True)
 
-    out = os.path.join(HERE, "diversity.npz")
+    out = write_archive("diversity.npz", store)
+    print(f"wrote {out}: {len(cases)} loss cases, {len(mcases)} metric cases, {os.path.getsize(out)} bytes")
+
+    # ---------------------------------------------------------------- non-finite scores (a generator of their own: diversity.npz keeps its bytes)
+    rng = np.random.default_rng(SEED + 1)
+    edge = {}
+    # (name, T, L, rt, top_k, {index: value})
+    ecases = [
+        ("mixed_T5_L40", 5, 40, 10.0, 10, {3: np.nan, 7: np.inf, 21: np.inf, 30: -np.inf}),
+        ("mixed_T7_L130_full", 7, 130, 10.0, None, {0: np.inf, 64: np.nan, 100: np.inf, 129: -np.inf}),
+        ("nan_T3_L20", 3, 20, 10.0, 10, {11: np.nan}),
+        ("two_nan_T3_L20", 3, 20, 10.0, 2, {0: np.nan, 19: np.nan}),
+        ("pinf_T4_L33", 4, 33, 100.0, None, {5: np.inf, 6: np.inf}),
+        ("ninf_T4_L33", 4, 33, 10.0, 3, {32: -np.inf}),
+    ]
+    for name, T, L, rt, top_k, planted in ecases:
+        preds = rng.standard_normal((1, L)).astype(np.float32)
+        for i, v in planted.items():
+            preds[0, i] = v
+        rele = presorted_rele(rng, T, L, 0.3, graded=True)
+        l32, g32 = ref_loss(preds, rele, rt, top_k, torch.float32)
+        l64, g64 = ref_loss(preds, rele, rt, top_k, torch.float64)
+        assert np.isfinite(l64) and np.all(np.isfinite(g64)) and np.isfinite(l32) and np.all(np.isfinite(g32)), name
+        fields = dict(preds=preds, rele=rele, rt=np.float32(rt), top_k=np.int32(top_k or 0), loss32=np.float32(l32), grad32=g32.astype(np.float32),
+                      loss64=np.float64(l64), grad64=g64.astype(np.float64))
+        for k, v in fields.items():
+            edge[f"nonfinite/{name}/{k}"] = np.asarray(v)
+        print(f"nonfinite {name:22s} loss64 {l64:+.6g}  max|grad64| {np.max(np.abs(g64)):.4g}", flush=True)
+    out = write_archive("diversity_edge.npz", edge)
+    print(f"wrote {out}: {len(ecases)} non-finite cases, {os.path.getsize(out)} bytes")
+
+
+def write_archive(fname, store):
+    out = os.path.join(HERE, fname)
     with zipfile.ZipFile(out, "w", compression=zipfile.ZIP_DEFLATED) as z:
         for k in sorted(store):
             buf = io.BytesIO()
@@ -169,7 +208,7 @@ def main():
             info.compress_type = zipfile.ZIP_DEFLATED
             info.external_attr = 0o644 << 16
             z.writestr(info, buf.getvalue())
-    print(f"wrote {out}: {len(cases)} loss cases, {len(mcases)} metric cases, {os.path.getsize(out)} bytes")
+    return out
 
 
 if __name__ == "__main__":
