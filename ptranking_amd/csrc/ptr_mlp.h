@@ -1,5 +1,5 @@
-// Shared definitions of the fused pointsf scorer kernels (scorer.hip: forward, layer-wise backward, Adam; scorer_bwd.hip: the
-// single-pass fused backward).  Reference: ptranking/base/point_ranker.py:30-55, ptranking/base/utils.py:288-356.
+// Shared definitions of the fused pointsf scorer kernels (scorer.hip: forward, layer-wise backward; scorer_bwd.hip: the
+// single-pass fused backward; optim.hip: the partial reduction + optimiser step).  Reference: ptranking/base/point_ranker.py:30-55, ptranking/base/utils.py:288-356.
 #pragma once
 #include <stdlib.h>
 #include <utility>
@@ -48,7 +48,7 @@ __host__ __device__ inline int x6_n1(int F) { return (F + 31) / 32; }
 __host__ __device__ inline int x6_nslices(int F, int NL) { return x6_n1(F) + 4 * (NL - 1); }
 #if defined(__HIPCC__)
 // r6: ONE parameter's three bf16 planes written into the image at the place x6_prep_kernel puts them — the optimiser step of the fused train step
-// (reduce_partials_kernel) refreshes the image element by element, so the next step's forward needs no prep launch.  The split is ptr_x6.h's
+// (reduce_partials_kernel, optim.hip) refreshes the image element by element, so the next step's forward needs no prep launch.  The split is ptr_x6.h's
 // (split_pack1 = one half of the split_pack2 x6_prep_kernel uses): the image is bit-identical to a fresh x6_prep_kernel run.
 // i = index into the flat parameter vector; b_1, w_out and b_out are not part of the image (they live in LDS / registers of the forward).
 __device__ __forceinline__ void x6_img_put(uint8_t *__restrict__ img, int F, int NL, size_t i, float x) {

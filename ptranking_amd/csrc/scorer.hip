@@ -1,4 +1,4 @@
-// Fused fp32-MFMA pointwise MLP scorer (the reference's `pointsf`): forward, backward and a flat Adam step.
+// Fused fp32-MFMA pointwise MLP scorer (the reference's `pointsf`): forward and layer-wise backward (the optimiser step: optim.hip).
 //
 // Reference: ptranking/base/point_ranker.py:30-55 (ff_dims = [F] + [100]*num_layers + [1], forward = Sequential(X).view(-1, L)),
 //            ptranking/base/utils.py:288-356 (get_stacked_FFNet with AF='R', BN=False, apply_tl_af=False:
@@ -22,6 +22,7 @@
 // HBM traffic per row (F = 136, 3 hidden layers, training): forward reads 4F, writes 3*400 + 4; dZ reads 3*400 + 4, writes
 // 3*400; dW reads 4F + 5*400.  MFMA work per row: 2*(100F + 2*100*100 + 100) flop forward, about twice that backward.
 #include "ptr_mlp.h"
+#include "ptr_optim.h"
 
 namespace ptr {
 
@@ -653,7 +654,7 @@ mlp_bwd_dz_kernel(const float *__restrict__ P, const float *__restrict__ acts, c
 // One launch per layer.  dW[out][in] = sum_rows dZ[row][out] * A[row][in];  db[out] = sum_rows dZ[row][out].
 // A = X with the input dropout recomputed (layer 0, SITE0) or the stored activation (other layers).  Each wave owns the
 // in-feature tiles nt = wave, wave + 4, ... and all 7 out-feature tiles; a block walks its contiguous chunk of rows 4 at a time.
-// ws[block][n_params]: per-block partial gradient in the flat parameter layout, reduced by reduce_partials_kernel.
+// ws[block][n_params]: per-block partial gradient in the flat parameter layout, reduced by reduce_partials_kernel (optim.hip).
 template <int NTW, bool SITE0, int NWV>
 __global__ void __launch_bounds__(NWV * 64)
 mlp_bwd_dw_kernel(const float *__restrict__ A, int lda, const float *__restrict__ dZ, int K, int nt_base, MlpArgs a,
@@ -914,126 +915,6 @@ mlp_bwd_dw_lds_kernel(const float *__restrict__ A, int lda, const float *__restr
 }
 __host__ __device__ constexpr size_t dw_lds_bytes(int NTW, int RB) { return (size_t)(2 * RB * kAL + 2 * RB * (64 * NTW + 16)) * sizeof(float); }
 
-// grad[i] = sum_b ws[b][i], fixed order.  A 1024-thread workgroup owns 128 consecutive i, every lane two of them (i and i + 64): wave w sums
-// the partials b = w, w+16, ... of both (4 independent accumulators each: 8 loads in flight), then waves 0 / 1 add the 16 wave totals of the
-// first / second 64 elements in order — per element the additions of the one-element-per-lane form this replaces, bit for bit.  Two elements per
-// lane halve the grid: (n + 127) / 128 (+ 1) workgroups — 267 at 34 001 parameters — are resident at once on 256 CUs x 2 workgroups, where
-// the 533 of the 64-element form ran a second, nearly empty round of the whole chain partials -> barrier -> optimiser state -> stores.
-// Entries i >= tail_begin (d w_out, d b_out: written by the dZ kernel's smaller grid) only have nblk_tail partials.
-// Optional epilogue of the partial reduction: the optimiser step on the element just reduced (single-device training: no all-reduce sits
-// between gradient and step) and the sum of the loss slots of the batch — three launches fewer per train step.
-struct OptStep {
-    int kind;                      // 0 = none, PTR_OPT_ADAM / _ADAGRAD / _RMSPROP
-    float lr, h1, h2, eps, wd, bc1, bc2_sqrt;
-    float *param, *s1, *s2;
-    const float *loss_q; int nq; float *loss_out;
-    uint8_t *wimg; int F, NL;      // r6: the bf16x6 forward's weight image, refreshed element by element behind the step (NULL: none)
-};
-constexpr int kRedElems = 128;               // elements per workgroup of reduce_partials_kernel
-inline unsigned reduce_grid(size_t n, bool loss_block) { return (unsigned)((n + kRedElems - 1) / kRedElems) + (loss_block ? 1u : 0u); }
-__global__ void __launch_bounds__(1024)
-reduce_partials_kernel(const float *__restrict__ ws, int nblk, int nblk_tail, size_t tail_begin, size_t stride, size_t n,
-                       float *__restrict__ grad, OptStep o) {
-    __shared__ float part[16][kRedElems];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (o.loss_out && blockIdx.x == gridDim.x - 1) {
-        // one extra block: the loss slots of the batch, summed by the function sum_f32_kernel calls (ptr_device.h block1024_sum): the fused
-        // step returns the same bits as the separate call
-        const float tot = block1024_sum(o.loss_q, o.nq, &part[0][0]);
-        if (threadIdx.x == 0) o.loss_out[0] = tot;
-        return;
-    }
-    // the two elements of this lane (clamped to n - 1 past the end: loaded, never stored)
-    const size_t ia = (size_t)blockIdx.x * kRedElems + lane, ib = ia + 64;
-    const size_t ica = ia < n ? ia : n - 1, icb = ib < n ? ib : n - 1;
-    const int nba = ica >= tail_begin ? nblk_tail : nblk, nbb = icb >= tail_begin ? nblk_tail : nblk;
-    const int nbc = nba < nbb ? nba : nbb;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
-    int b = w;
-    for (; b + 48 < nbc; b += 64) {              // both elements: 8 independent loads
-        a0 += ws[(size_t)b * stride + ica];
-        a1 += ws[(size_t)(b + 16) * stride + ica];
-        a2 += ws[(size_t)(b + 32) * stride + ica];
-        a3 += ws[(size_t)(b + 48) * stride + ica];
-        b0 += ws[(size_t)b * stride + icb];
-        b1 += ws[(size_t)(b + 16) * stride + icb];
-        b2 += ws[(size_t)(b + 32) * stride + icb];
-        b3 += ws[(size_t)(b + 48) * stride + icb];
-    }
-    // what is left of either element, in the same order.  The two 4-accumulator loops run no iteration unless the elements' counts differ: only
-    // in the ONE workgroup that straddles tail_begin, and only on the layer-wise path (every other caller passes tail_begin = n)
-    int ba = b, bb = b;
-    for (; ba + 48 < nba; ba += 64) {
-        a0 += ws[(size_t)ba * stride + ica];
-        a1 += ws[(size_t)(ba + 16) * stride + ica];
-        a2 += ws[(size_t)(ba + 32) * stride + ica];
-        a3 += ws[(size_t)(ba + 48) * stride + ica];
-    }
-    for (; bb + 48 < nbb; bb += 64) {
-        b0 += ws[(size_t)bb * stride + icb];
-        b1 += ws[(size_t)(bb + 16) * stride + icb];
-        b2 += ws[(size_t)(bb + 32) * stride + icb];
-        b3 += ws[(size_t)(bb + 48) * stride + icb];
-    }
-    for (; ba < nba; ba += 16) a0 += ws[(size_t)ba * stride + ica];
-    for (; bb < nbb; bb += 16) b0 += ws[(size_t)bb * stride + icb];
-    part[w][lane] = (a0 + a1) + (a2 + a3);
-    part[w][64 + lane] = (b0 + b1) + (b2 + b3);
-    __syncthreads();
-    const int col = 64 * w + lane;                                  // waves 0 / 1: the first / second 64 elements
-    const size_t i = (size_t)blockIdx.x * kRedElems + col;
-    if (w < 2 && i < n) {
-        float s = part[0][col];
-#pragma unroll
-        for (int k = 1; k < 16; ++k) s += part[k][col];
-        if (grad) grad[i] = s;                          // (ptr_opt_step_loss: ws IS the gradient, one "partial" — nothing to write back)
-        // fused optimiser step on the element just reduced: the arithmetic of adam_kernel / adagrad_kernel / rmsprop_kernel, bit for bit
-        if (o.kind == PTR_OPT_ADAM) {
-            const float pi = o.param[i];
-            const float gi = s + o.wd * pi;
-            const float mi = o.h1 * o.s1[i] + (1.0f - o.h1) * gi;
-            const float vi = o.h2 * o.s2[i] + (1.0f - o.h2) * gi * gi;
-            o.s1[i] = mi; o.s2[i] = vi;
-            const float denom = sqrtf(vi) / o.bc2_sqrt + o.eps;
-            const float pn = pi - (o.lr / o.bc1) * (mi / denom);
-            o.param[i] = pn;
-            if (o.wimg) x6_img_put(o.wimg, o.F, o.NL, i, pn);
-        } else if (o.kind == PTR_OPT_ADAGRAD) {
-            const float pi = o.param[i];
-            const float gi = s + o.wd * pi;
-            const float si = o.s1[i] + gi * gi;
-            o.s1[i] = si;
-            const float pn = pi - o.lr * (gi / (sqrtf(si) + o.eps));     // o.lr = the decayed clr
-            o.param[i] = pn;
-            if (o.wimg) x6_img_put(o.wimg, o.F, o.NL, i, pn);
-        } else if (o.kind == PTR_OPT_RMSPROP) {
-            const float pi = o.param[i];
-            const float gi = s + o.wd * pi;
-            const float si = o.h1 * o.s1[i] + (1.0f - o.h1) * gi * gi;
-            o.s1[i] = si;
-            const float pn = pi - o.lr * (gi / (sqrtf(si) + o.eps));
-            o.param[i] = pn;
-            if (o.wimg) x6_img_put(o.wimg, o.F, o.NL, i, pn);
-        }
-    }
-}
-
-// =================================================================================================== Adam (torch.optim.Adam semantics)
-// g = grad + wd*p; m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g*g; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
-__global__ void __launch_bounds__(256)
-adam_kernel(float *__restrict__ p, const float *__restrict__ grad, float *__restrict__ m, float *__restrict__ v, size_t n, float lr,
-            float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float pi = p[i];
-    const float gi = grad[i] + wd * pi;
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = pi - (lr / bc1) * (mi / denom);
-}
-
 // debug / test helper: the dropout keep-mask of one site as floats [R][n_feat]
 __global__ void __launch_bounds__(256)
 dropout_mask_kernel(MlpArgs a, int site, int n_feat, float *__restrict__ out) {
@@ -1136,49 +1017,10 @@ int ptr::mlp_backward_step_impl(const float *X, float *params, const float *acts
                                 float *state1, float *state2, const float *loss_q, int nq, float *loss_out, void *wimg, void *stream) {
     using namespace ptr;
     const char *who = "ptr_mlp_backward_step";
-    if (opt_kind < PTR_OPT_ADAM || opt_kind > PTR_OPT_RMSPROP) { set_error("%s: unknown optimiser %d", who, opt_kind); return PTR_ERR_INVALID_ARG; }
-    if (step < 1 || !state1 || (opt_kind == PTR_OPT_ADAM && !state2) || (loss_out && nq > 0 && !loss_q) || nq < 0) {
-        set_error("%s: bad optimiser / loss arguments", who);
-        return PTR_ERR_INVALID_ARG;
-    }
-    OptStep o{};
-    o.kind = opt_kind; o.h1 = hyper1; o.h2 = hyper2; o.eps = eps; o.wd = weight_decay;
-    o.param = params; o.s1 = state1; o.s2 = state2; o.loss_q = loss_q; o.nq = nq; o.loss_out = loss_out;
+    OptStep o;
+    if (int rc = make_opt_step(o, who, opt_kind, lr, hyper1, hyper2, eps, weight_decay, step, params, state1, state2, true, loss_q, nq, loss_out)) return rc;
     o.wimg = reinterpret_cast<uint8_t *>(wimg); o.F = F; o.NL = NL;
-    if (opt_kind == PTR_OPT_ADAM) {                                  // as ptr_adam_step
-        o.lr = lr; o.bc1 = 1.0f - powf(hyper1, (float)step); o.bc2_sqrt = sqrtf(1.0f - powf(hyper2, (float)step));
-    } else if (opt_kind == PTR_OPT_ADAGRAD) {                        // as ptr_adagrad_step: hyper1 = lr_decay
-        o.lr = lr / (1.0f + (float)(step - 1) * hyper1);
-    } else {
-        o.lr = lr;                                                   // hyper1 = alpha
-    }
     return mlp_backward_impl(who, X, params, acts, dpreds, R, F, NL, p_drop, seed, dz, ws, grad, stream, o);
-}
-
-// The optimiser step + the loss-slot sum as ONE launch on a gradient that is already reduced (data parallelism: backward -> flat gradient ->
-// RCCL all-reduce -> this): reduce_partials_kernel over ONE "partial" — the gradient itself — so the arithmetic is ptr_mlp_backward_step's,
-// bit for bit, and the data-parallel step is the single-device launch sequence + one kernel + one collective.
-extern "C" int ptr_opt_step_loss(float *params, const float *grad, int64_t n, int opt_kind, float lr, float hyper1, float hyper2, float eps,
-                                 float weight_decay, int step, float *state1, float *state2, const float *loss_q, int nq, float *loss_out,
-                                 void *stream) {
-    using namespace ptr;
-    const char *who = "ptr_opt_step_loss";
-    if (opt_kind < PTR_OPT_ADAM || opt_kind > PTR_OPT_RMSPROP) { set_error("%s: unknown optimiser %d", who, opt_kind); return PTR_ERR_INVALID_ARG; }
-    if (n < 0 || step < 1 || nq < 0 || (n > 0 && (!params || !grad || !state1 || (opt_kind == PTR_OPT_ADAM && !state2))) || (loss_out && nq > 0 && !loss_q)) {
-        set_error("%s: bad optimiser / loss arguments", who);
-        return PTR_ERR_INVALID_ARG;
-    }
-    if (n == 0 && !loss_out) return 0;
-    OptStep o{};
-    o.kind = opt_kind; o.h1 = hyper1; o.h2 = hyper2; o.eps = eps; o.wd = weight_decay;
-    o.param = params; o.s1 = state1; o.s2 = state2; o.loss_q = loss_q; o.nq = nq; o.loss_out = loss_out;
-    if (opt_kind == PTR_OPT_ADAM) { o.lr = lr; o.bc1 = 1.0f - powf(hyper1, (float)step); o.bc2_sqrt = sqrtf(1.0f - powf(hyper2, (float)step)); }
-    else if (opt_kind == PTR_OPT_ADAGRAD) o.lr = lr / (1.0f + (float)(step - 1) * hyper1);
-    else o.lr = lr;
-    const size_t nn = (size_t)n;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(nn, loss_out != nullptr)), dim3(1024), 0, as_stream(stream), grad, 1, 1, nn,
-                       nn, nn, (float *)nullptr, o);
-    return check_hip(hipGetLastError(), who);
 }
 
 int ptr::mlp_backward_impl(const char *who, const float *X, const float *params, const float *acts, const float *dpreds, int R, int F, int NL,
@@ -1195,9 +1037,7 @@ int ptr::mlp_backward_impl(const char *who, const float *X, const float *params,
                                                         : launch_bwd_fused(X, params, acts, dpreds, a, ws, st, who)) return e;
         const int nb = bwd_fused_grid(R);
         const size_t NPf = n_params(NL, F);
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(NPf, opt.loss_out != nullptr)), dim3(1024), 0, st, ws, nb, nb, NPf, NPf, NPf,
-                           grad, opt);
-        return check_hip(hipGetLastError(), who);
+        return launch_reduce_partials(ws, nb, nb, NPf, NPf, NPf, grad, opt, st, who);
     }
     if (!dz) { set_error("%s: dz scratch is required for this configuration (ptr_mlp_backward_dz_floats)", who); return PTR_ERR_INVALID_ARG; }
     // 1. dZ chain (+ partial d w_out / d b_out)
@@ -1262,66 +1102,7 @@ int ptr::mlp_backward_impl(const char *who, const float *X, const float *params,
         if (e) return e;
     }
     // 3. one deterministic reduction of all partials into the flat gradient
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(NP, opt.loss_out != nullptr)), dim3(1024), 0, st, ws, nblk,
-                       tail ? bwd_fused_grid(R) : grid_dz, tail ? off_W(1, F) : off_wout(NL, F), NP, NP, grad, opt);
-    return check_hip(hipGetLastError(), who);
-}
-
-namespace ptr {
-// torch.optim.Adagrad (lr_decay, eps; initial accumulator 0) and torch.optim.RMSprop (alpha, eps; no momentum, not centered) on flat
-// buffers — the other two optimisers the reference configures (ptranking/base/ranker.py:518-521), L2 weight decay added to the gradient
-__global__ void __launch_bounds__(256)
-adagrad_kernel(float *__restrict__ p, const float *__restrict__ grad, float *__restrict__ sum, size_t n, float clr, float eps, float wd) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float pi = p[i];
-    const float gi = grad[i] + wd * pi;
-    const float si = sum[i] + gi * gi;
-    sum[i] = si;
-    p[i] = pi - clr * (gi / (sqrtf(si) + eps));
-}
-__global__ void __launch_bounds__(256)
-rmsprop_kernel(float *__restrict__ p, const float *__restrict__ grad, float *__restrict__ sq, size_t n, float lr, float alpha, float eps, float wd) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float pi = p[i];
-    const float gi = grad[i] + wd * pi;
-    const float si = alpha * sq[i] + (1.0f - alpha) * gi * gi;
-    sq[i] = si;
-    p[i] = pi - lr * (gi / (sqrtf(si) + eps));
-}
-}  // namespace ptr
-
-extern "C" int ptr_adagrad_step(float *param, const float *grad, float *state_sum, int64_t n, float lr, float lr_decay, float eps,
-                                float weight_decay, int step, void *stream) {
-    using namespace ptr;
-    if (n < 0 || step < 1 || (n > 0 && (!param || !grad || !state_sum))) { set_error("ptr_adagrad_step: bad arguments"); return PTR_ERR_INVALID_ARG; }
-    if (n == 0) return 0;
-    const float clr = lr / (1.0f + (float)(step - 1) * lr_decay);
-    hipLaunchKernelGGL(adagrad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), param, grad, state_sum, (size_t)n, clr, eps,
-                       weight_decay);
-    return check_hip(hipGetLastError(), "ptr_adagrad_step");
-}
-
-extern "C" int ptr_rmsprop_step(float *param, const float *grad, float *square_avg, int64_t n, float lr, float alpha, float eps,
-                                float weight_decay, void *stream) {
-    using namespace ptr;
-    if (n < 0 || (n > 0 && (!param || !grad || !square_avg))) { set_error("ptr_rmsprop_step: bad arguments"); return PTR_ERR_INVALID_ARG; }
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(rmsprop_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), param, grad, square_avg, (size_t)n, lr, alpha,
-                       eps, weight_decay);
-    return check_hip(hipGetLastError(), "ptr_rmsprop_step");
-}
-
-extern "C" int ptr_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr, float beta1,
-                             float beta2, float eps, float weight_decay, int step, void *stream) {
-    using namespace ptr;
-    if (n < 0 || step < 1 || (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq))) { set_error("ptr_adam_step: bad arguments"); return PTR_ERR_INVALID_ARG; }
-    if (n == 0) return 0;
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq,
-                       (size_t)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt);
-    return check_hip(hipGetLastError(), "ptr_adam_step");
+    return launch_reduce_partials(ws, nblk, tail ? bwd_fused_grid(R) : grid_dz, tail ? off_W(1, F) : off_wout(NL, F), NP, NP, grad, opt, st, who);
 }
 
 extern "C" int ptr_mlp_dropout_mask(int R, int n_feat, int site, float p_drop, uint64_t seed, float *out, void *stream) {

@@ -21,8 +21,8 @@ from . import dp
 from . import functional as F_
 from .host import DeviceEvaluator, DeviceTrainLoop, PointScorerRanker, is_multilabel
 from .listsf import FusedListScorerMixin
-from .scorer import (FlatAdagrad, FlatAdam, FlatRMSprop, FusedPointScorer, FusedScorerMixin, alloc_acts, mlp_forward, x6_wimg_for, x6_image_tag,
-                     x6_set_image_tag)
+from .scorer import (FLAT_OPTIMIZERS, FlatOptimizer, FusedPointScorer, FusedScorerMixin, alloc_acts, mlp_forward, opt_step_c_values, x6_wimg_for,
+                     x6_image_tag, x6_set_image_tag)
 
 RANKER_NAMES = ("RankNet", "LambdaRank", "LambdaLoss", "ApproxNDCG", "ListNet", "ListMLE", "STListNet", "RankCosine", "RankMSE", "SoftRank",
                 "WassRank")
@@ -90,7 +90,7 @@ class FusedStepMixin:
     def _direct_train_op(self, X, Y, kwargs):
         spec = self._direct_loss
         sf = getattr(self, "point_sf", None)
-        if (spec is None or not self.use_direct_step or not isinstance(sf, FusedPointScorer) or not isinstance(self.optimizer, FlatAdam)
+        if (spec is None or not self.use_direct_step or not isinstance(sf, FusedPointScorer) or not isinstance(self.optimizer, FlatOptimizer)
                 or type(self).custom_loss_function is not self._direct_owner.custom_loss_function or not sf.training
                 or not torch.is_grad_enabled() or not (X.is_cuda and X.dim() == 3 and X.dtype == torch.float32 and X.is_contiguous())
                 or not (Y.is_cuda and Y.dtype == torch.float32 and Y.is_contiguous() and Y.shape == X.shape[:2])
@@ -130,7 +130,7 @@ class FusedStepMixin:
         distributed = self.data_parallel and dp.is_distributed()
         # single device: the optimiser step and the loss-slot sum ride in the backward's partial reduction (three launches fewer per step,
         # bit-identical results); under data parallelism the all-reduce sits between the gradient and the step
-        fuse_step = self.fuse_optimizer_step and not distributed and type(self.optimizer) in (FlatAdam, FlatAdagrad, FlatRMSprop)
+        fuse_step = self.fuse_optimizer_step and not distributed and type(self.optimizer) in FLAT_OPTIMIZERS.values()
         if fuse_step and self.single_call_step:
             # r6: forward -> loss -> backward + step enqueued by ONE foreign call (ptr_train_step chains the very entry points used below:
             # bit-identical parameters); bench.py's per-stage timings (_lib.TIMING) come from events the call records between its stages
@@ -143,15 +143,16 @@ class FusedStepMixin:
                 stop_training = self.stop_training(buf["preds"])
             # data parallel with a flat optimiser: backward -> flat gradient -> all-reduce -> ONE launch (optimiser step + loss-slot sum,
             # ptr_opt_step_loss): the single-device launch sequence + one kernel + one collective, nothing returns to autograd in between
-            dp_fused = distributed and self.fuse_optimizer_step and type(self.optimizer) in (FlatAdam, FlatAdagrad, FlatRMSprop)
+            dp_fused = distributed and self.fuse_optimizer_step and type(self.optimizer) in FLAT_OPTIMIZERS.values()
             _lib.call(spec.entry, _lib.ptr(buf["preds"]), _lib.ptr(Y), _lib.ptr(lens), B, L, *spec.c_args(**values),
                       None if (fuse_step or dp_fused) else _lib.ptr(loss), _lib.ptr(buf["loss_q"]), _lib.ptr(buf["dpreds"]), st)
             if fuse_step:
-                kind, lr, h1, h2, eps, wd, step, s1, s2 = self.optimizer.fused_step_args(flat)
+                opt = opt_step_c_values(self.optimizer.fused_step_args(flat)).values()
                 try:
-                    self._launch_backward_step(X, flat, buf, R, Fd, NL, p, seed, kind, lr, h1, h2, eps, wd, step, s1, s2, B, loss, st)
+                    _lib.call("ptr_mlp_backward_step", _lib.ptr(X), _lib.ptr(flat), _lib.ptr(buf["acts"]), _lib.ptr(buf["dpreds"]), R, Fd, NL, C.c_float(p),
+                              C.c_uint64(seed), _lib.ptr(buf["dz"]), _lib.ptr(buf["ws"]), _lib.ptr(flat.grad), *opt, _lib.ptr(buf["loss_q"]), B, _lib.ptr(loss), st)
                 except Exception:
-                    self.optimizer.state[flat]["step"] -= 1      # the launch failed: the bias-correction counter must not run ahead
+                    self.optimizer.undo_step(flat)
                     raise
             else:
                 _lib.call("ptr_mlp_backward", _lib.ptr(X), _lib.ptr(flat), _lib.ptr(buf["acts"]), _lib.ptr(buf["dpreds"]), R, Fd, NL, C.c_float(p),
@@ -159,13 +160,12 @@ class FusedStepMixin:
                 if distributed:
                     dp.all_reduce_sum(flat.grad)
                 if dp_fused:
-                    kind, lr, h1, h2, eps, wd, step, s1, s2 = self.optimizer.fused_step_args(flat)
+                    opt = opt_step_c_values(self.optimizer.fused_step_args(flat)).values()
                     try:
-                        _lib.call("ptr_opt_step_loss", _lib.ptr(flat), _lib.ptr(flat.grad), C.c_int64(flat.numel()), kind, C.c_float(lr), C.c_float(h1),
-                                  C.c_float(h2), C.c_float(eps), C.c_float(wd), step, _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(buf["loss_q"]), B,
+                        _lib.call("ptr_opt_step_loss", _lib.ptr(flat), _lib.ptr(flat.grad), C.c_int64(flat.numel()), *opt, _lib.ptr(buf["loss_q"]), B,
                                   _lib.ptr(loss), st)
                     except Exception:
-                        self.optimizer.state[flat]["step"] -= 1
+                        self.optimizer.undo_step(flat)
                         raise
                 else:
                     self.optimizer.step_flat(flat)
@@ -200,10 +200,12 @@ class FusedStepMixin:
         else:
             for k in range(4):
                 d.events[k] = None
-        kind, lr, h1, h2, eps, wd, step, s1, s2 = self.optimizer.fused_step_args(flat)
-        d.opt_kind, d.step, d.lr, d.hyper1, d.hyper2, d.eps, d.weight_decay = kind, step, lr, h1, h2, eps, wd
+        opt = opt_step_c_values(self.optimizer.fused_step_args(flat))
+        for name, v in opt.items():
+            setattr(d, name, v)
+        step = opt["step"]
         d.p_drop, d.seed = p, seed
-        d.params, d.grad, d.state1, d.state2 = flat.data_ptr(), flat.grad.data_ptr(), s1.data_ptr(), (None if s2 is None else s2.data_ptr())
+        d.params, d.grad = flat.data_ptr(), flat.grad.data_ptr()
         d.loss_out = loss.data_ptr()
         if wimg is not None:
             x6_set_image_tag(dev, Fd, NL, None)        # until the call has gone through, nobody may trust the image
@@ -215,7 +217,7 @@ class FusedStepMixin:
                 finally:
                     _lib.TIMING = timing
         except Exception:
-            self.optimizer.state[flat]["step"] -= 1      # the launch failed: the bias-correction counter must not run ahead
+            self.optimizer.undo_step(flat)
             raise
         if wimg is not None:                           # the optimiser launch rewrote the image for the parameters it has just produced
             x6_set_image_tag(dev, Fd, NL, (flat.data_ptr(), flat._version, step, wimg.data_ptr()))
@@ -227,11 +229,6 @@ class FusedStepMixin:
         if 'epoch_k' in kwargs and kwargs['epoch_k'] % self.stop_check_freq == 0:
             stop_training = self.stop_training(buf["preds"])      # the scores of THIS step's forward (the reference checks them before the loss; it steps either way)
         return loss.reshape(()), stop_training
-
-    def _launch_backward_step(self, X, flat, buf, R, Fd, NL, p, seed, kind, lr, h1, h2, eps, wd, step, s1, s2, B, loss, st):
-        _lib.call("ptr_mlp_backward_step", _lib.ptr(X), _lib.ptr(flat), _lib.ptr(buf["acts"]), _lib.ptr(buf["dpreds"]), R, Fd, NL, C.c_float(p),
-                  C.c_uint64(seed), _lib.ptr(buf["dz"]), _lib.ptr(buf["ws"]), _lib.ptr(flat.grad), kind, C.c_float(lr), C.c_float(h1),
-                  C.c_float(h2), C.c_float(eps), C.c_float(wd), step, _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(buf["loss_q"]), B, _lib.ptr(loss), st)
 
     def _bucket(self, extra=0):
         if self._grad_bucket is None or self._grad_bucket.extra != extra:

@@ -254,40 +254,49 @@ class FusedPointScorer(nn.Module):
         return out
 
 
-class FlatAdam(torch.optim.Optimizer):
-    """torch.optim.Adam semantics (L2 weight decay folded into the gradient, bias correction) as ONE kernel per flat
-    parameter tensor — the update the reference configures in ptranking/base/ranker.py:516-517."""
+class FlatOptimizer(torch.optim.Optimizer):
+    """torch.optim semantics (L2 weight decay folded into the gradient) as ONE kernel per flat parameter tensor: the state, the step counter
+    and the launches of the three optimisers the reference configures (ptranking/base/ranker.py:516-521).  A subclass states what differs:
+    KIND (PTR_OPT_*), STATE (torch's names of its buffers, in ABI order), ENTRY (its stand-alone entry point: param, grad, <STATE>, n, lr,
+    <hypers>, eps, weight_decay, [step,] stream), TAKES_STEP and hypers(group)."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    KIND, STATE, ENTRY, TAKES_STEP = 0, (), None, True
 
-    def _step_param(self, p, group):
-        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
-            raise RuntimeError("FlatAdam needs contiguous CUDA float32 parameters / gradients")
+    def hypers(self, group):
+        """The optimiser's own hyper-parameters (one or two) as the entry points take them."""
+        raise NotImplementedError
+
+    def _next_step(self, p):
+        """The state of `p` (created on first use) with its step counter advanced to THIS step."""
         st = self.state[p]
         if not st:
             st["step"] = 0
-            st["exp_avg"] = torch.zeros_like(p)
-            st["exp_avg_sq"] = torch.zeros_like(p)
+            for k in self.STATE:
+                st[k] = torch.zeros_like(p)
         st["step"] += 1
-        b1, b2 = group["betas"]
-        with torch.cuda.device(p.device):
-            _lib.call("ptr_adam_step", _lib.ptr(p), _lib.ptr(p.grad), _lib.ptr(st["exp_avg"]), _lib.ptr(st["exp_avg_sq"]),
-                      C.c_int64(p.numel()), C.c_float(group["lr"]), C.c_float(b1), C.c_float(b2), C.c_float(group["eps"]),
-                      C.c_float(group["weight_decay"]), int(st["step"]), _lib.current_stream(p.device))
+        return st
+
+    def undo_step(self, p):
+        """Takes back the count of a step whose launch failed: the bias-correction counter must not run ahead."""
+        self.state[p]["step"] -= 1
 
     def fused_step_args(self, p):
         """(opt_kind, lr, hyper1, hyper2, eps, weight_decay, step, state1, state2) of THIS step for ptr_mlp_backward_step — the state /
         step bookkeeping of _step_param without its kernel launch."""
-        group, st = self.param_groups[0], self.state[p]
-        if not st:
-            st["step"] = 0
-            st["exp_avg"] = torch.zeros_like(p)
-            st["exp_avg_sq"] = torch.zeros_like(p)
-        st["step"] += 1
-        b1, b2 = group["betas"]
+        group, st = self.param_groups[0], self._next_step(p)
+        h1, h2 = (tuple(self.hypers(group)) + (0.0,))[:2]
+        s1, s2 = (tuple(st[k] for k in self.STATE) + (None,))[:2]
         self._opt_called = True
-        return 1, group["lr"], b1, b2, group["eps"], group["weight_decay"], int(st["step"]), st["exp_avg"], st["exp_avg_sq"]
+        return self.KIND, group["lr"], h1, h2, group["eps"], group["weight_decay"], int(st["step"]), s1, s2
+
+    def _step_param(self, p, group):
+        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
+            raise RuntimeError(f"{type(self).__name__} needs contiguous CUDA float32 parameters / gradients")
+        st = self._next_step(p)
+        with torch.cuda.device(p.device):
+            _lib.call(self.ENTRY, _lib.ptr(p), _lib.ptr(p.grad), *(_lib.ptr(st[k]) for k in self.STATE), C.c_int64(p.numel()), C.c_float(group["lr"]),
+                      *(C.c_float(h) for h in self.hypers(group)), C.c_float(group["eps"]), C.c_float(group["weight_decay"]),
+                      *((int(st["step"]),) if self.TAKES_STEP else ()), _lib.current_stream(p.device))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -308,63 +317,45 @@ class FlatAdam(torch.optim.Optimizer):
         self._opt_called = True           # what torch.optim.lr_scheduler's wrapper of step() records
 
 
-class FlatAdagrad(FlatAdam):
-    """torch.optim.Adagrad (lr_decay 0, eps 1e-10, accumulator from 0) as one kernel per flat parameter tensor (ranker.py:520-521)."""
+def opt_step_c_values(args):
+    """fused_step_args()'s nine values as C values by ABI name: in this order the run of arguments ptr_mlp_backward_step and ptr_opt_step_loss
+    share, under these names the fields of ptr_train_step's descriptor."""
+    kind, lr, h1, h2, eps, wd, step, s1, s2 = args
+    return dict(opt_kind=kind, lr=C.c_float(lr), hyper1=C.c_float(h1), hyper2=C.c_float(h2), eps=C.c_float(eps), weight_decay=C.c_float(wd), step=step,
+                state1=_lib.ptr(s1), state2=_lib.ptr(s2))
+
+
+class FlatAdam(FlatOptimizer):
+    """torch.optim.Adam (bias correction) — the update the reference configures in ptranking/base/ranker.py:516-517."""
+    KIND, STATE, ENTRY = 1, ("exp_avg", "exp_avg_sq"), "ptr_adam_step"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def hypers(self, group):
+        return group["betas"]
+
+
+class FlatAdagrad(FlatOptimizer):
+    """torch.optim.Adagrad (lr_decay 0, eps 1e-10, accumulator from 0; ranker.py:520-521)."""
+    KIND, STATE, ENTRY = 2, ("sum",), "ptr_adagrad_step"
 
     def __init__(self, params, lr=1e-2, lr_decay=0.0, eps=1e-10, weight_decay=0.0):
-        torch.optim.Optimizer.__init__(self, params, dict(lr=lr, lr_decay=lr_decay, eps=eps, weight_decay=weight_decay))
+        super().__init__(params, dict(lr=lr, lr_decay=lr_decay, eps=eps, weight_decay=weight_decay))
 
-    def _step_param(self, p, group):
-        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
-            raise RuntimeError("FlatAdagrad needs contiguous CUDA float32 parameters / gradients")
-        st = self.state[p]
-        if not st:
-            st["step"] = 0
-            st["sum"] = torch.zeros_like(p)
-        st["step"] += 1
-        with torch.cuda.device(p.device):
-            _lib.call("ptr_adagrad_step", _lib.ptr(p), _lib.ptr(p.grad), _lib.ptr(st["sum"]), C.c_int64(p.numel()), C.c_float(group["lr"]),
-                      C.c_float(group["lr_decay"]), C.c_float(group["eps"]), C.c_float(group["weight_decay"]), int(st["step"]),
-                      _lib.current_stream(p.device))
+    def hypers(self, group):
+        return (group["lr_decay"],)
 
 
-    def fused_step_args(self, p):
-        group, st = self.param_groups[0], self.state[p]
-        if not st:
-            st["step"] = 0
-            st["sum"] = torch.zeros_like(p)
-        st["step"] += 1
-        self._opt_called = True
-        return 2, group["lr"], group["lr_decay"], 0.0, group["eps"], group["weight_decay"], int(st["step"]), st["sum"], None
-
-
-class FlatRMSprop(FlatAdam):
-    """torch.optim.RMSprop (alpha 0.99, eps 1e-8, no momentum, not centered) as one kernel per flat parameter tensor (ranker.py:518-519)."""
+class FlatRMSprop(FlatOptimizer):
+    """torch.optim.RMSprop (alpha 0.99, eps 1e-8, no momentum, not centered; ranker.py:518-519)."""
+    KIND, STATE, ENTRY, TAKES_STEP = 3, ("square_avg",), "ptr_rmsprop_step", False
 
     def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0):
-        torch.optim.Optimizer.__init__(self, params, dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay))
+        super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay))
 
-    def _step_param(self, p, group):
-        if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
-            raise RuntimeError("FlatRMSprop needs contiguous CUDA float32 parameters / gradients")
-        st = self.state[p]
-        if not st:
-            st["step"] = 0
-            st["square_avg"] = torch.zeros_like(p)
-        st["step"] += 1
-        with torch.cuda.device(p.device):
-            _lib.call("ptr_rmsprop_step", _lib.ptr(p), _lib.ptr(p.grad), _lib.ptr(st["square_avg"]), C.c_int64(p.numel()), C.c_float(group["lr"]),
-                      C.c_float(group["alpha"]), C.c_float(group["eps"]), C.c_float(group["weight_decay"]), _lib.current_stream(p.device))
-
-
-    def fused_step_args(self, p):
-        group, st = self.param_groups[0], self.state[p]
-        if not st:
-            st["step"] = 0
-            st["square_avg"] = torch.zeros_like(p)
-        st["step"] += 1
-        self._opt_called = True
-        return 3, group["lr"], group["alpha"], 0.0, group["eps"], group["weight_decay"], int(st["step"]), st["square_avg"], None
+    def hypers(self, group):
+        return (group["alpha"],)
 
 
 FLAT_OPTIMIZERS = {'Adam': FlatAdam, 'Adagrad': FlatAdagrad, 'RMS': FlatRMSprop}      # the `opt` strings of ranker.py:516-521

@@ -299,3 +299,37 @@ def test_strict_device_is_the_default_and_extras_are_opt_in(monkeypatch, stand_i
         assert set(installed) == set(pa.RANKER_NAMES) | set(pa.EXTRA_RANKER_NAMES)
     finally:
         pa.uninstall()
+
+
+@pytest.mark.parametrize("opt,kind,hyper,h12,keys", [
+    ("Adam", 1, dict(lr=2e-3, betas=(0.8, 0.99), eps=1e-6, weight_decay=1e-3), (0.8, 0.99), ("exp_avg", "exp_avg_sq")),
+    ("Adagrad", 2, dict(lr=2e-2, lr_decay=0.1, eps=1e-9, weight_decay=1e-3), (0.1, 0.0), ("sum",)),
+    ("RMS", 3, dict(lr=3e-2, alpha=0.9, eps=1e-7, weight_decay=1e-3), (0.9, 0.0), ("square_avg",)),
+])
+def test_flat_optimiser_bookkeeping_without_a_gpu(opt, kind, hyper, h12, keys):
+    """The bookkeeping the three flat optimisers share (scorer.FlatOptimizer) on a CPU parameter: `fused_step_args` returns PTR_OPT_* and the
+    group's values in ABI order, creates exactly torch's state keys, counts `step` up by one per call and `undo_step` takes it back by one;
+    state_dict() -> load_state_dict() round-trips."""
+    from ptranking_amd.scorer import FLAT_OPTIMIZERS, FLAT_VIEW_OPTIMIZERS, FlatOptimizer
+    cls = FLAT_OPTIMIZERS[opt]
+    assert issubclass(cls, FlatOptimizer) and issubclass(FLAT_VIEW_OPTIMIZERS[opt], cls)
+    assert [c for c in FLAT_OPTIMIZERS.values() if issubclass(cls, c)] == [cls]          # no flat optimiser is another one's subclass
+    p = torch.nn.Parameter(torch.arange(5, dtype=torch.float32))
+    o = cls([p], **hyper)
+    assert not o.state[p]
+    for t in (1, 2, 3):
+        k, lr, h1, h2, eps, wd, step, s1, s2 = o.fused_step_args(p)
+        assert (k, lr, h1, h2, eps, wd, step) == (kind, hyper["lr"], h12[0], h12[1], hyper["eps"], hyper["weight_decay"], t)
+        st = o.state[p]
+        assert set(st) == {"step", *keys} and st["step"] == t
+        assert s1 is st[keys[0]] and (s2 is st[keys[1]] if len(keys) == 2 else s2 is None)
+        assert all(st[key].shape == p.shape and st[key].dtype == torch.float32 and not st[key].any() for key in keys)
+    o.undo_step(p)
+    assert o.state[p]["step"] == 2 and o.fused_step_args(p)[6] == 3
+    o.state[p][keys[0]].copy_(torch.arange(5.0) + 1)
+    q = torch.nn.Parameter(torch.zeros(5))
+    o2 = cls([q], **{**hyper, "lr": 1.0})
+    o2.load_state_dict(o.state_dict())
+    assert set(o2.state[q]) == {"step", *keys} and o2.state[q]["step"] == 3 and o2.param_groups[0]["lr"] == hyper["lr"]
+    assert all(torch.equal(o2.state[q][key], o.state[p][key]) for key in keys)
+    assert o2.fused_step_args(q)[:7] == (kind, hyper["lr"], h12[0], h12[1], hyper["eps"], hyper["weight_decay"], 4)

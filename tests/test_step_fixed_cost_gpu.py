@@ -1,6 +1,6 @@
 """GPU: the fixed per-step cost around the fused scorer kernels, bit for bit.
 
-* `reduce_partials_kernel` (csrc/scorer.hip) gives every lane two elements so that one resident round of workgroups covers every parameter.
+* `reduce_partials_kernel` (csrc/optim.hip) gives every lane two elements so that one resident round of workgroups covers every parameter.
   The additions per element are the documented ones: wave w sums the partials b = w, w + 16, ... with four accumulators, (s0 + s1) + (s2 + s3),
   then the 16 wave totals in order.  The test re-adds the partials the backward left in the caller's workspace on the CPU in fp32 in that order
   and requires the returned gradient to be equal — on the single-pass backward (every entry has the same number of partials) and on the
