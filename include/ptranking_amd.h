@@ -222,6 +222,41 @@ int ptr_divprob_fwd_bwd(const float *mus, const float *vars, const float *rele, 
  * queries at L = 128): every supported L fits. */
 int ptr_divprob_expected_ranks(const float *mus, const float *vars, const int32_t *lens, int B, int L, float *ranks, void *stream);
 
+/* ---- TREC ndeval's diversity measures and its greedy ideal ranking (csrc/ndeval.hip).  The symbol below is ADDITIVE to ABI v8 as well:
+ * PTR_ABI_VERSION stays 8.
+ * ptr_ndeval_measures — what ptranking/metric/srd/ndeval.c (ndeval 4.4, the one native component of the reference, run by
+ * DivLTREvaluator.fold_evaluation_reproduce) prints per topic, in float64 and bit for bit: the same IEEE double operations in the same
+ * order.  Data model as above; judgments are binarised (rele > 0 is relevant, ndeval.c:908).  Per query:
+ *   pool     the first lens[q] documents (the qrels' document set); nrelSub[j] = the number of documents relevant to subtopic j;
+ *            S = actual_subtopics[q] = the number of subtopics with nrelSub > 0 (actualSubtopics, :336-345).
+ *   run      the pool ranked as ptr_sort_desc ranks it (value descending, NaN first, original index ascending); preds == NULL: the input
+ *            order.  depth_m > 0 keeps the first depth_m ranked documents (ndeval -M, :1000-1020); the ideal side always uses the whole
+ *            pool.  A document with an all-zero column is an unjudged document.
+ *   ideal    ideal_order [B,L] (nullable; entries beyond lens[q] = -1), idealResult :351-400: lens[q] greedy rounds; a candidate scores the
+ *            sum over its subtopics j, ascending, of gain[j]; gain[j] starts at 1 and is multiplied by (1 - alpha) whenever a chosen
+ *            document covers j; the largest score wins, ties go to the larger document index (ndeval's "larger docno" with zero-padded
+ *            docnos).  Scores are doubles compared for equality, so the tie decisions are ndeval's.
+ *   per_k    [B,6,nk] (nullable) at the HOST cut-offs ks[nk], each in 1..PTR_NDEVAL_DEPTH: ERR-IA (computeERR :597-643), nERR-IA, alpha-DCG
+ *            (computeDCG :651-698), alpha-nDCG (renormalize :1143-1156: run / ideal, 0 wherever the run's alpha-DCG is 0), P-IA
+ *            (computePrecision :736-759) and strec (computeSTRecall :704-730).  The cumulative arrays are divided by the cumulative "ideal
+ *            ideal" array (gain S, S (1 - alpha), ...) from index 1 on only: at k = 1 the two raw measures are NOT divided by S — ndeval's
+ *            behaviour, kept.  A run shorter than k: the counts freeze and P-IA still divides by k S.
+ *   per_q    [B,3] (nullable): NRBP (computeNRBP :531-562, over the whole run), nNRBP = NRBP / the ideal ranking's NRBP, MAP-IA (computeMAP
+ *            :484-525, denominators = the pool's nrelSub).
+ *   S == 0 (lens[q] == 0 included): every measure is 0 and nNRBP is NaN (0 / 0), as ndeval prints; callers filter on actual_subtopics
+ *   [B] (nullable).
+ * Padded documents and padded subtopics are never read.  log() is evaluated on the host only (the 20 discounts log 2 / log(i + 2)).
+ * One wavefront per query, four queries per workgroup, up to 128 documents; one workgroup per query beyond.  LDS per query:
+ * 32 * round_up(L, 4) + 1664 bytes (129.6 KiB at L = PTR_MAX_LIST_LEN = 4096): every supported L fits the 160 KiB of a compute unit, so the
+ * LDS limit coincides with PTR_MAX_LIST_LEN.
+ * Errors, before any launch: PTR_ERR_INVALID_ARG for a NULL rele, alpha outside (0, 1), beta outside [0, 1] (NaN included), depth_m < 0,
+ * a cut-off outside 1..PTR_NDEVAL_DEPTH; PTR_ERR_UNSUPPORTED for L > PTR_MAX_LIST_LEN, T > PTR_MAX_SUBTOPICS, nk > PTR_MAX_CUTOFFS or a
+ * query tile beyond the LDS of a compute unit.  B == 0 succeeds. */
+#define PTR_NDEVAL_DEPTH 20
+int ptr_ndeval_measures(const float *preds, const float *rele, const int32_t *lens, const int32_t *ntopics, int B, int T, int L,
+                        const int32_t *ks, int nk, double alpha, double beta, int depth_m, double *per_k, double *per_q,
+                        int32_t *actual_subtopics, int32_t *ideal_order, void *stream);
+
 /* ---- The tree frame's custom objectives (csrc/tree.hip).  The two symbols below are ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
  * They compute what a LightGBM custom objective returns every boosting round — a gradient and a Hessian per document — and nothing else of
  * the tree frame: the boosting stays in LightGBM.

@@ -221,6 +221,47 @@ class _DivRanker(FusedStepMixin, FusedScorerMixin, PointScorerRanker):
             return andcg, err_ia, nerr_ia, [row.view(1, -1) for a, keep in per_q for row in a[keep].cpu()]
         return andcg, err_ia, nerr_ia
 
+    def ndeval_performance_at_ks(self, test_data=None, ks=[5, 10, 20], alpha=0.5, beta=0.5, depth=None, need_per_q=False):
+        """The figures TREC's ndeval reports for this ranker's run (ptranking/metric/srd/ndeval.c, which
+        DivLTREvaluator.fold_evaluation_reproduce shells out to) without the run file: functional.ndeval_measures on the scores of every
+        query, summed on the device and read once -> dict of CPU float64 tensors keyed by functional.NDEVAL_MEASURES ([len(ks)] or
+        0-d).  The mean is ndeval's `amean`: over every query with at least one document, the nNRBP NaN of a query without a relevant
+        document included.  The documents need not be presorted — ndeval builds its own ideal ranking.  With need_per_q also returns the
+        per-query dicts (device tensors, "actual_subtopics" included), one per batch."""
+        self.eval_mode()
+        dev = torch.device(self.device)
+        sums = {m: torch.zeros(len(ks) if m in ("ERR-IA", "nERR-IA", "alpha-DCG", "alpha-nDCG", "P-IA", "strec") else (), device=dev,
+                               dtype=torch.float64) for m in F_.NDEVAL_MEASURES}
+        cnt = torch.zeros((), device=dev, dtype=torch.float64)
+        per_q = []
+
+        def add(preds, rele, lens, ntopics):
+            out = F_.ndeval_measures(preds.detach(), rele, ks, alpha=alpha, beta=beta, depth=depth, lens=lens, ntopics=ntopics)
+            keep = (lens > 0) if lens is not None else torch.ones(preds.size(0), dtype=torch.bool, device=dev)
+            for m in F_.NDEVAL_MEASURES:
+                x = out[m]
+                sums[m] += torch.where(keep if x.dim() == 1 else keep.unsqueeze(1), x, torch.zeros((), dtype=x.dtype, device=dev)).sum(dim=0)
+            cnt.add_(keep.sum())
+            if need_per_q:
+                per_q.append(out)
+
+        with torch.no_grad():
+            if isinstance(test_data, DivQueryBatches):
+                for ids, X, rele, lens, ntopics in test_data:
+                    add(self._batch_sort_scores(X, lens), rele, lens, ntopics)
+            else:
+                for item in test_data:
+                    _, q_repr, doc_reprs, rele = unpack_div_query(item)
+                    q_repr, doc_reprs, rele = self._to_dev(q_repr), self._to_dev(doc_reprs), self._to_dev(rele)
+                    add(self.div_predict(q_repr, doc_reprs), rele.float().unsqueeze(0).contiguous(), None, None)
+        stacked = torch.cat([(sums[m] / cnt).reshape(-1) for m in F_.NDEVAL_MEASURES]).cpu()      # the one host read
+        res, o = {}, 0
+        for m in F_.NDEVAL_MEASURES:
+            k = sums[m].numel()
+            res[m] = stacked[o:o + k].reshape(sums[m].shape)
+            o += k
+        return (res, per_q) if need_per_q else res
+
 
 class DALETOR(_DivRanker):
     """Le Yan, Zhen Qin, Rama Kumar Pasumarthi, Xuanhui Wang, Mike Bendersky: Diversification-Aware Learning to Rank using Distributed

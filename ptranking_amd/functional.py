@@ -15,13 +15,14 @@ from . import _lib
 
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
-           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
+           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "ndeval_measures", "div_ideal_order", "NDEVAL_MEASURES","divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
            "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "gaussian_metric_objective", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
 # launch table, and it draws its own)
 LAMBDALOSS_TYPES = {"NDCG_Loss1": 0, "NDCG_Loss2": 1, "NDCG_Loss2++": 2}   # ptranking/ltr_adhoc/listwise/lambdaloss.py:27
 ADCG_TOPK_AXES = {"reference": 0, "subtopics": 0, 0: 0, "documents": 1, 1: 1}   # PTR_ADCG_TOPK_*
+NDEVAL_MEASURES = ("ERR-IA", "nERR-IA", "alpha-DCG", "alpha-nDCG", "NRBP", "nNRBP", "MAP-IA", "P-IA", "strec")   # ndeval.c:1214-1222, its CSV columns
 DIVPROB_OBJECTIVES = {"aNDCG": 0, "nERR-IA": 1, "PairCLS": 2, "LambdaPairCLS": 3, 0: 0, 1: 1, 2: 2, 3: 3}   # PTR_DIVPROB_*
 TREE_PAIR_TYPES = {"All": 0, "NoTies": 1, "No00": 2, "00": 3}              # PTR_TREE_PAIRS_*; ptranking/ltr_tree/util/lightgbm_util.py:17-60
 TREE_WEIGHTINGS = {None: 0, False: 0, "DeltaNDCG": 1, "DeltaGain": 2}       # PTR_TREE_W_*; lightgbm_util.py:80
@@ -328,6 +329,62 @@ def div_metrics_at_ks(preds, rele, ks, alpha=0.5, max_label=None, lens=None, nto
                   C.c_float(float(alpha)), C.c_float(0.0 if max_label is None else float(max_label)), _lib.ptr(andcg), _lib.ptr(err),
                   _lib.ptr(nerr), _lib.ptr(valid), _lib.current_stream(dev))
     return andcg, err, nerr, valid
+
+
+def _ndeval_batch(preds, rele, lens, ntopics):
+    """rele [B, T, L] (and preds [B, L] unless None) for ptr_ndeval_measures — checked, contiguous."""
+    if preds is not None:
+        return _div_batch(preds.detach(), rele, lens, ntopics)
+    rele = _check("rele", rele)
+    if rele.dim() != 3:
+        raise ValueError(f"rele must be [batch, num_subtopics, ranking_size], got {tuple(rele.shape)}")
+    B, T, L = rele.shape
+    _list_len(L)
+    if T < 1 or T > _lib.MAX_SUBTOPICS:
+        raise ValueError(f"{T} subtopics: between 1 and {_lib.MAX_SUBTOPICS} are supported")
+    return None, rele, _counts("lens", lens, B), _counts("ntopics", ntopics, B), B, T, L
+
+
+def ndeval_measures(preds, rele, ks=(5, 10, 20), alpha=0.5, beta=0.5, depth=None, lens=None, ntopics=None, return_ideal_order=False):
+    """TREC ndeval's diversity measures (ptranking/metric/srd/ndeval.c, the program DivLTREvaluator.fold_evaluation_reproduce runs) for a
+    padded batch, in float64 and bit for bit what the program computes per topic -> dict keyed by NDEVAL_MEASURES: "ERR-IA", "nERR-IA",
+    "alpha-DCG", "alpha-nDCG", "P-IA" and "strec" [B, nk] at the cut-offs ks (each in 1..20), "NRBP", "nNRBP" and "MAP-IA" [B]; plus
+    "actual_subtopics" int32 [B] (the subtopics with a relevant document: 0 marks a query whose measures are all 0 and whose nNRBP is NaN)
+    and, with return_ideal_order, "ideal_order" int64 [B, L] (-1 beyond lens).  Judgments are binarised (rele > 0); the run is preds ranked
+    as sort_desc ranks it (preds=None: the input order), cut to `depth` documents when given (ndeval -M); the ideal ranking is ndeval's
+    greedy over the whole pool, not the input order — which is how these figures differ from div_metrics_at_ks."""
+    preds, rele, lens, ntopics, B, T, L = _ndeval_batch(preds, rele, lens, ntopics)
+    ks = [int(k) for k in ks]
+    if len(ks) > _lib.MAX_CUTOFFS:
+        raise ValueError(f"at most {_lib.MAX_CUTOFFS} cut-offs")
+    dev, nk = rele.device, len(ks)
+    per_k = torch.empty((B, 6, nk), device=dev, dtype=torch.float64)
+    per_q = torch.empty((B, 3), device=dev, dtype=torch.float64)
+    subtopics = torch.empty(B, device=dev, dtype=torch.int32)
+    ideal = torch.empty((B, L), device=dev, dtype=torch.int32) if return_ideal_order else None
+    with torch.cuda.device(dev):
+        _lib.call("ptr_ndeval_measures", _lib.ptr(preds), _lib.ptr(rele), _lib.ptr(lens), _lib.ptr(ntopics), B, T, L,
+                  (C.c_int32 * max(nk, 1))(*ks), nk, C.c_double(float(alpha)), C.c_double(float(beta)), int(depth) if depth else 0,
+                  _lib.ptr(per_k), _lib.ptr(per_q), _lib.ptr(subtopics), _lib.ptr(ideal), _lib.current_stream(dev))
+    out = {"ERR-IA": per_k[:, 0], "nERR-IA": per_k[:, 1], "alpha-DCG": per_k[:, 2], "alpha-nDCG": per_k[:, 3], "NRBP": per_q[:, 0],
+           "nNRBP": per_q[:, 1], "MAP-IA": per_q[:, 2], "P-IA": per_k[:, 4], "strec": per_k[:, 5], "actual_subtopics": subtopics}
+    if return_ideal_order:
+        out["ideal_order"] = ideal.long()
+    return out
+
+
+def div_ideal_order(rele, alpha=0.5, lens=None, ntopics=None):
+    """The ideal ranking the diversification frame presorts by -> int64 [B, L] document indices (-1 beyond lens): ndeval's greedy
+    (ndeval.c:351-400; ptranking/metric/srd/diversity_metric.py:113-141 is the same loop over a Python set) on the binarised judgments —
+    each round takes the document with the largest sum of (1 - alpha)^(times its subtopic is covered so far), ties to the larger index.
+    Gathering a query's documents, and the document axis of its rele, by this order gives what alphadcg_loss, divprob_loss,
+    div_metrics_at_ks and DivQueryBatches expect as the given order."""
+    _, rele, lens, ntopics, B, T, L = _ndeval_batch(None, rele, lens, ntopics)
+    ideal = torch.empty((B, L), device=rele.device, dtype=torch.int32)
+    with torch.cuda.device(rele.device):
+        _lib.call("ptr_ndeval_measures", None, _lib.ptr(rele), _lib.ptr(lens), _lib.ptr(ntopics), B, T, L, (C.c_int32 * 1)(1), 0,
+                  C.c_double(float(alpha)), C.c_double(0.5), 0, None, None, None, _lib.ptr(ideal), _lib.current_stream(rele.device))
+    return ideal.long()
 
 
 def _divprob_scores(mus, vars, lens):
