@@ -710,6 +710,29 @@ size_t ptr_layernorm_backward_ws_floats(int F);
 int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, const float *stats, int64_t R, int F, float *ws,
                            float *dX, float *da2, float *db2, void *stream);
 
+/* Test helper (no GPU, nothing launched): which kernel form the entry point named `entry` launches for a shape.  It calls the very function
+ * the entry point's launcher calls, so it reads the same PTR_* switches and the same device (compute units).  args [nargs] in, form [nform]
+ * out (nform may exceed the count below; the rest is left alone).  `aligned`: the call's arrays are 16-byte aligned.
+ *   entry                                        args                                     form
+ *   ptr_lambdarank_fwd_bwd                       B, L, sigma > 0                          kind, G, DPT, QPB      kind: 0 LDS kernel, 1 ring (QPB
+ *   ptr_ranknet_fwd_bwd                          B, L                                     kind, G, DPT, QPB        waves), 2 half-wave; QPB: queries
+ *                                                                                                                  per workgroup
+ *   ptr_approxndcg_fwd_bwd, ptr_softrank_fwd_bwd,
+ *   ptr_smoothmetric_fwd_bwd, ptr_gaussmetric_fwd_bwd   L                                 ring, G, DPT           ring: 1 ring form, 0 LDS / walk form
+ *   ptr_listnet_fwd_bwd, ptr_listmle_fwd_bwd     L, aligned                               vec, G, V              vec: 1 register kernel (V float4 per
+ *                                                                                                                  lane, G lanes per query), 0 LDS kernel
+ *   ptr_lambdaloss_fwd_bwd                       L, k, loss_type, presort, aligned        vec, G, V              vec: 1 top-k kernel; 0 generic, (G, DPT)
+ *   ptr_mhsa_forward, ptr_mhsa_backward          L, head dim, row stride, ds_ws given,    wide, D, forward row tiles, dK/dV waves, stored dS,
+ *                                                alignment of the arrays in bytes           floats per global access
+ *   ptr_layernorm_forward, ptr_layernorm_backward   R, F                                  NI, forward workgroups, backward workgroups
+ *   ptr_wassrank_fwd_bwd                         L                                        G, DPT
+ *   ptr_alphadcg_fwd_bwd                         T, L                                     G, TP
+ *   ptr_div_metrics_at_ks                        L                                        G, DPT
+ *   ptr_divprob_fwd_bwd                          objective, T, L                          G, TP
+ * G: threads per query, DPT: documents per thread, TP: subtopic tile.  PTR_ERR_INVALID_ARG for an entry without a form, another nargs, or
+ * nform below the count. */
+int ptr_launch_form(const char *entry, const int64_t *args, int nargs, int32_t *form, int nform);
+
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):
  *   "<label> qid:<id> <fid>:<val> ... [# comment]", feature ids one-indexed unless one_indexed == 0 (Yahoo! sets,

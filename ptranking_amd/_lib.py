@@ -86,6 +86,7 @@ SIGNATURES = {
     "ptr_layernorm_forward": [_vp, _vp, _vp, C.c_int64, _i, _f, _vp, _vp, _vp],
     "ptr_layernorm_backward_ws_floats": [_i],
     "ptr_layernorm_backward": [_vp, _vp, _vp, _vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp],
+    "ptr_launch_form": [C.c_char_p, C.POINTER(C.c_int64), _i, C.POINTER(C.c_int32), _i],
     "ptr_letor_scan": [C.c_char_p, _i, _vp, _vp, _vp],
     "ptr_letor_load": [C.c_char_p, _i, _f, C.c_int64, C.c_int32, C.c_int64, _vp, _i, _vp, _vp, _vp],
 }

@@ -1,8 +1,11 @@
 // C-ABI plumbing: thread-local error text, argument checks, the deterministic slot reduction.
 #include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
 
+#include "ptr_attn.h"
 #include "ptr_device.h"
+#include "ptr_div.h"
 
 namespace ptr {
 
@@ -39,7 +42,59 @@ __global__ void __launch_bounds__(1024) sum_f32_kernel(const float *__restrict__
     if (threadIdx.x == 0) out[0] = scale * tot;
 }
 
+// ptr_launch_form: each entry point's arguments -> the form function its launcher calls.  A form struct is ints only and goes out as it is.
+struct FormQuery { const char *entry; int nargs, nform; void (*ask)(const int64_t *a, int32_t *out); };
+template <class T> static void put(int32_t *out, const T &form) {
+    static_assert(sizeof(T) % sizeof(int32_t) == 0);
+    memcpy(out, &form, sizeof(T));
+}
+static void ask_attention(const int64_t *a, int32_t *out) {         // (L, dh, ld, store_ds, align_bytes)
+    const int dh = (int)a[1], stride = (int)a[2];
+    const uintptr_t address = (uintptr_t)a[4];
+    const AttnForm f = attn_form(dh, (int)a[0], a[3] != 0);
+    put(out, f);
+    out[5] = f.wide ? wide_access_width(dh, stride, address) : ATTN_FLOAT4_ROWS(dh, stride, address) ? 4 : 1;
+}
+static void ask_layernorm(const int64_t *a, int32_t *out) { put(out, layernorm_form(a[0], (int)a[1])); }
+static void ask_ring(const int64_t *a, int32_t *out) { put(out, ring_form((int)a[0])); }
+static void ask_listnet(const int64_t *a, int32_t *out) { put(out, listnet_form((int)a[0], a[1] != 0)); }
+static const FormQuery kFormQueries[] = {
+    {"ptr_lambdarank_fwd_bwd", 3, 4, [](const int64_t *a, int32_t *out) { put(out, pairwise_form(true, (int)a[0], (int)a[1], a[2] != 0)); }},
+    {"ptr_ranknet_fwd_bwd", 2, 4, [](const int64_t *a, int32_t *out) { put(out, pairwise_form(false, (int)a[0], (int)a[1], true)); }},
+    {"ptr_approxndcg_fwd_bwd", 1, 3, [](const int64_t *a, int32_t *out) { put(out, approxndcg_form((int)a[0])); }},
+    {"ptr_softrank_fwd_bwd", 1, 3, [](const int64_t *a, int32_t *out) { put(out, ring_form((int)a[0], false)); }},
+    {"ptr_smoothmetric_fwd_bwd", 1, 3, ask_ring},
+    {"ptr_gaussmetric_fwd_bwd", 1, 3, ask_ring},
+    {"ptr_listnet_fwd_bwd", 2, 3, ask_listnet},
+    {"ptr_listmle_fwd_bwd", 2, 3, [](const int64_t *a, int32_t *out) { put(out, listmle_form((int)a[0], a[1] != 0)); }},
+    {"ptr_lambdaloss_fwd_bwd", 5, 3,
+     [](const int64_t *a, int32_t *out) { put(out, lambdaloss_form((int)a[0], (int)a[1], (int)a[2], (int)a[3], a[4] != 0)); }},
+    {"ptr_mhsa_forward", 5, 6, ask_attention},
+    {"ptr_mhsa_backward", 5, 6, ask_attention},
+    {"ptr_layernorm_forward", 2, 3, ask_layernorm},
+    {"ptr_layernorm_backward", 2, 3, ask_layernorm},
+    {"ptr_wassrank_fwd_bwd", 1, 2, [](const int64_t *a, int32_t *out) { put(out, wassrank_form((int)a[0])); }},
+    {"ptr_alphadcg_fwd_bwd", 2, 2, [](const int64_t *a, int32_t *out) { put(out, div_form((int)a[0], (int)a[1])); }},
+    {"ptr_div_metrics_at_ks", 1, 2, [](const int64_t *a, int32_t *out) { put(out, pick_tiling((int)a[0])); }},
+    {"ptr_divprob_fwd_bwd", 3, 2, [](const int64_t *a, int32_t *out) { put(out, divprob_form((int)a[0], (int)a[1], (int)a[2])); }},
+};
+
 }  // namespace ptr
+
+extern "C" int ptr_launch_form(const char *entry, const int64_t *args, int nargs, int32_t *form, int nform) {
+    if (!entry || !args || !form) { ptr::set_error("ptr_launch_form: NULL pointer"); return PTR_ERR_INVALID_ARG; }
+    for (const ptr::FormQuery &q : ptr::kFormQueries) {
+        if (strcmp(entry, q.entry) != 0) continue;
+        if (nargs != q.nargs || nform < q.nform) {
+            ptr::set_error("ptr_launch_form: %s takes %d arguments and gives %d form values (got %d, room for %d)", entry, q.nargs, q.nform, nargs, nform);
+            return PTR_ERR_INVALID_ARG;
+        }
+        q.ask(args, form);
+        return 0;
+    }
+    ptr::set_error("ptr_launch_form: no form is defined for entry point '%s'", entry);
+    return PTR_ERR_INVALID_ARG;
+}
 
 extern "C" int ptr_abi_version(void) { return PTR_ABI_VERSION; }
 

@@ -307,6 +307,8 @@ __global__ void __launch_bounds__(kBlock) scale_inplace_kernel(float *__restrict
     for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) x[i] *= s;
 }
 
+RingForm approxndcg_form(int L) { return ring_form(L, env_int("PTR_APPROX_RING", 1)); }      // PTR_APPROX_RING=0 selects the LDS kernel (tests)
+
 }  // namespace ptr
 
 extern "C" int ptr_approxndcg_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, float alpha,
@@ -318,15 +320,14 @@ extern "C" int ptr_approxndcg_fwd_bwd(const float *preds, const float *labels, c
     if (!loss_out || !scale_out || (B > 0 && (!dcg_q || !inv_idcg_q || !grad))) { set_error("%s: NULL output pointer", who); return PTR_ERR_INVALID_ARG; }
     if (!(alpha > 0.0f)) { set_error("%s: alpha must be > 0 (got %g)", who, (double)alpha); return PTR_ERR_INVALID_ARG; }
     hipStream_t st = as_stream(stream);
-    if (B > 0 && L <= 512 && env_int("PTR_APPROX_RING", 1)) {           // PTR_APPROX_RING=0 selects the LDS kernel (tests)
-        auto go = [&](auto kern, int dpt) -> int {
+    const RingForm f = approxndcg_form(L);
+    if (B > 0 && f.ring) {
+        const int rc = dispatch_ring_dpt(f.DPT, [&]<int DPT>() -> int {
             constexpr int QPB = kBlock / kWave;
-            const size_t lds = (size_t)QPB * 64 * approx_ring_sort_width(dpt) * sizeof(float);
-            return launch_queries(kern, B, QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, alpha, presort, couple_batch, dcg_q, inv_idcg_q, grad);
-        };
-        const int rc = L <= 64 ? go(approxndcg_ring_kernel<1>, 1) : L <= 128 ? go(approxndcg_ring_kernel<2>, 2)
-                     : L <= 192 ? go(approxndcg_ring_kernel<3>, 3) : L <= 256 ? go(approxndcg_ring_kernel<4>, 4)
-                     : L <= 384 ? go(approxndcg_ring_kernel<6>, 6) : go(approxndcg_ring_kernel<8>, 8);
+            const size_t lds = (size_t)QPB * 64 * approx_ring_sort_width(DPT) * sizeof(float);
+            return launch_queries(approxndcg_ring_kernel<DPT>, B, QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, alpha, presort, couple_batch,
+                                  dcg_q, inv_idcg_q, grad);
+        });
         if (rc) return rc;
     } else if (B > 0) {
         const int Lp = round_up(L, 4);

@@ -228,8 +228,8 @@ extern "C" int ptr_alphadcg_fwd_bwd(const float *preds, const float *rele, const
     if (!(rt > 0.0f)) { set_error("%s: rt must be > 0 (got %g)", who, (double)rt); return PTR_ERR_INVALID_ARG; }
     if (int rc = check_top_k_axis(top_k_axis, who)) return rc;
     if (int rc = check_pointers(B, loss_q && grad, who)) return rc;
-    const int Lp = round_up(L, 4), TP = tp_of(T);
-    const int QPB = L <= 128 ? kBlock / kWave : 1;
+    const DivForm f = div_form(T, L);
+    const int Lp = round_up(L, 4), TP = f.TP, QPB = kBlock / f.G;
     const size_t lds = (size_t)QPB * adcg_group_floats(Lp, TP) * sizeof(float);
     if (lds > kLdsPerWorkgroup) {
         set_error("%s: T=%d, L=%d need %zu bytes of LDS per workgroup (limit %zu): 8 * round_up(L, 4) * (1 + %d) + 16 bytes per query", who, T, L,
@@ -242,7 +242,7 @@ extern "C" int ptr_alphadcg_fwd_bwd(const float *preds, const float *rele, const
             return launch_queries(kern, B, QPB, kBlock, lds, stream, who, preds, rele, lens, ntopics, B, T, L, Lp, rt, (float)log2(c), (float)log(c), top_k,
                                   top_k_axis, loss_q, grad);
         };
-        if (int rc = dispatch_tp(T, [&]<int TP_>() { return QPB > 1 ? go(alphadcg_kernel<64, TP_>) : go(alphadcg_kernel<256, TP_>); })) return rc;
+        if (int rc = dispatch_tp(TP, [&]<int TP_>() { return f.G == kWave ? go(alphadcg_kernel<64, TP_>) : go(alphadcg_kernel<256, TP_>); })) return rc;
     }
     return finish_loss(loss_q, B, 1.0f, loss_out, stream);
 }

@@ -313,6 +313,13 @@ template <int G, int TP> static auto divprob_kernel_of(int objective) {
                                             : divprob_kernel<G, TP, PTR_DIVPROB_LAMBDAPAIRCLS>;
 }
 
+static size_t divprob_query_bytes(int objective, int T, int L) {
+    return divprob_group_floats(round_up(L, 4), tp_of(T), divprob_tiles(objective)) * sizeof(float);
+}
+DivForm divprob_form(int objective, int T, int L) {
+    return div_form(T, L, (kBlock / kWave) * divprob_query_bytes(objective, T, L) <= kLdsPerWorkgroup);
+}
+
 }  // namespace ptr
 
 extern "C" int ptr_divprob_fwd_bwd(const float *mus, const float *vars, const float *rele, const int32_t *lens, const int32_t *ntopics, int B,
@@ -336,14 +343,14 @@ extern "C" int ptr_divprob_fwd_bwd(const float *mus, const float *vars, const fl
     if (int rc = check_subtopics_fit(T, who)) return rc;
     if (int rc = check_pointers(B, loss_q && grad_mu && grad_var, who)) return rc;
     const int Lp = round_up(L, 4), TP = tp_of(T), K = divprob_tiles(objective);
-    const size_t per_query = divprob_group_floats(Lp, TP, K) * sizeof(float);
+    const size_t per_query = divprob_query_bytes(objective, T, L);
     if (per_query > kLdsPerWorkgroup) {
         set_error("%s: T=%d, L=%d need %zu bytes of LDS per workgroup (limit %zu): 4 * round_up(L, 4) * (3 + %d * %d) + 16 bytes per query", who, T,
                   L, per_query, kLdsPerWorkgroup, K, TP);
         return PTR_ERR_UNSUPPORTED;
     }
-    // one wavefront per query and four queries per workgroup up to 128 documents, where four tiles fit; else the whole workgroup on one query
-    const int QPB = (L <= 128 && (kBlock / kWave) * per_query <= kLdsPerWorkgroup) ? kBlock / kWave : 1;
+    const DivForm f = divprob_form(objective, T, L);
+    const int QPB = kBlock / f.G;
     const size_t lds = (size_t)QPB * per_query;
     if (B > 0) {
         const double c = 1.0 - (double)beta;
@@ -351,8 +358,8 @@ extern "C" int ptr_divprob_fwd_bwd(const float *mus, const float *vars, const fl
             return launch_queries(kern, B, QPB, kBlock, lds, stream, who, mus, vars, rele, lens, ntopics, B, T, L, Lp, (float)log2(c), (float)log(c), top_k,
                                   top_k_axis, objective == PTR_DIVPROB_ERRIA ? exp2f(-max_label) : 0.0f, norm, loss_q, grad_mu, grad_var);
         };
-        if (int rc = dispatch_tp(T, [&]<int TP_>() {
-                return QPB > 1 ? go(divprob_kernel_of<64, TP_>(objective)) : go(divprob_kernel_of<256, TP_>(objective));
+        if (int rc = dispatch_tp(TP, [&]<int TP_>() {
+                return f.G == kWave ? go(divprob_kernel_of<64, TP_>(objective)) : go(divprob_kernel_of<256, TP_>(objective));
             })) return rc;
     }
     return finish_loss(loss_q, B, 1.0f, loss_out, stream);

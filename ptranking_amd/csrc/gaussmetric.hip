@@ -342,24 +342,16 @@ extern "C" int ptr_gaussmetric_fwd_bwd(const float *mus, const float *vars, cons
             ml_dev = max_label_ws;
         }
         const float const_var = vars ? 0.0f : (float)((double)const_std * (double)const_std);     // the variance every document gets
-        auto ring = [&](auto kern, int dpt) -> int {
-            constexpr int QPB = kBlock / kWave;
-            return launch_queries(kern, B, QPB, kBlock, (size_t)QPB * 128 * dpt * sizeof(float), stream, who, mus, vars, labels, lens, B, L, metric,
-                                  opt_ideal, top_k, const_var, max_label, ml_dev, loss_q, valid_q, ranks, pos, grad_mu, grad_var);
+        const RingForm f = ring_form(L);
+        auto go = [&](auto kern, int QPB, size_t lds_floats) -> int {
+            return launch_queries(kern, B, QPB, kBlock, lds_floats * sizeof(float), stream, who, mus, vars, labels, lens, B, L, metric, opt_ideal, top_k,
+                                  const_var, max_label, ml_dev, loss_q, valid_q, ranks, pos, grad_mu, grad_var);
         };
-        auto walk = [&](auto kern, int dpt) -> int {
-            return launch_queries(kern, B, 1, kBlock, gauss_group_floats(kBlock * dpt) * sizeof(float), stream, who, mus, vars, labels, lens, B, L,
-                                  metric, opt_ideal, top_k, const_var, max_label, ml_dev, loss_q, valid_q, ranks, pos, grad_mu, grad_var);
-        };
-        const int rc = L <= 64     ? ring(gauss_ring_kernel<1>, 1)
-                       : L <= 128  ? ring(gauss_ring_kernel<2>, 2)
-                       : L <= 192  ? ring(gauss_ring_kernel<3>, 3)
-                       : L <= 256  ? ring(gauss_ring_kernel<4>, 4)
-                       : L <= 384  ? ring(gauss_ring_kernel<6>, 6)
-                       : L <= 512  ? ring(gauss_ring_kernel<8>, 8)
-                       : L <= 1024 ? walk(gauss_metric_kernel<256, 4>, 4)
-                       : L <= 2048 ? walk(gauss_metric_kernel<256, 8>, 8)
-                                   : walk(gauss_metric_kernel<256, 16>, 16);
+        auto walk = [&]<int DPT>() { return go(gauss_metric_kernel<256, DPT>, 1, gauss_group_floats(kBlock * DPT)); };
+        const int rc = f.ring     ? dispatch_ring_dpt(f.DPT, [&]<int DPT>() { return go(gauss_ring_kernel<DPT>, kBlock / kWave, (size_t)kBlock / kWave * 128 * DPT); })
+                     : f.DPT == 4 ? walk.template operator()<4>()
+                     : f.DPT == 8 ? walk.template operator()<8>()
+                                  : walk.template operator()<16>();
         if (rc) return rc;
     }
     return finish_loss(loss_q, B, 1.0f, loss_out, stream);

@@ -447,6 +447,16 @@ lambdaloss_topk_kernel(const float *__restrict__ preds, const float *__restrict_
     }
 }
 
+// A small cut-off on presorted labels, on 16-byte aligned rows of a multiple of four documents: wavefront arg-max selection instead of a sort,
+// one pair per lane (lambdaloss_topk_kernel, V float4 per lane).  Otherwise lambdaloss_kernel: one wavefront per query up to 256 documents
+// (ranks from a register bitonic sort, one accumulator row), four beyond; its (G, DPT) comes back in (G, V).
+VecForm lambdaloss_form(int L, int k, int loss_type, int presort, bool aligned) {
+    if (presort && k <= 11 && loss_type != PTR_LAMBDALOSS_NDCG_LOSS1 && L % 4 == 0 && L <= 1024 && aligned)
+        return {1, kWave, vec_per_lane(L)};
+    const Tiling t = pick_wave256_tiling(L);
+    return {0, t.G, t.DPT};
+}
+
 }  // namespace ptr
 
 extern "C" int ptr_lambdaloss_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, int k,
@@ -460,18 +470,15 @@ extern "C" int ptr_lambdaloss_fwd_bwd(const float *preds, const float *labels, c
         return PTR_ERR_INVALID_ARG;
     }
     hipStream_t st = as_stream(stream);
-    const bool topk = presort && k <= 11 && loss_type != PTR_LAMBDALOSS_NDCG_LOSS1 && L % 4 == 0 && L <= 1024 &&
-                      ((reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(grad)) & 15) == 0;
-    if (B > 0 && topk) {
-        // small cut-off on presorted labels: wavefront arg-max selection instead of a sort, one pair per lane (lambdaloss_topk_kernel)
+    const VecForm f = lambdaloss_form(L, k, loss_type, presort, aligned16(preds, labels, grad));
+    if (B > 0 && f.vec) {
         auto go = [&](auto kern) -> int {
             const int blocks = persistent_grid(kern, kBlock, 0, (B + 3) / 4);   // persistent wavefronts: the resident set walks the queries
             hipLaunchKernelGGL(kern, dim3(blocks), dim3(kBlock), 0, st, preds, labels, lens, B, L, k, sigma, mu, loss_type, loss_q, grad);
             return check_hip(hipGetLastError(), who);
         };
-        if (int rc = L <= 256 ? go(lambdaloss_topk_kernel<1>) : (L <= 512 ? go(lambdaloss_topk_kernel<2>) : go(lambdaloss_topk_kernel<4>))) return rc;
+        if (int rc = f.V == 1 ? go(lambdaloss_topk_kernel<1>) : (f.V == 2 ? go(lambdaloss_topk_kernel<2>) : go(lambdaloss_topk_kernel<4>))) return rc;
     } else if (B > 0) {
-        // one wavefront per query up to 256 documents (ranks from a register bitonic sort, one accumulator row), four beyond
         int rc = dispatch_wave256_tiling(L, [&]<int G, int DPT>() -> int {
             constexpr int QPB = kBlock / G, NW = G / kWave;
             const int Lp = G == kWave ? kWave * DPT : round_up(L, 4);

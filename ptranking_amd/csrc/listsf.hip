@@ -43,7 +43,7 @@ struct RowStage {
     // Raw loads only (clamped, always-valid addresses): nothing here may consume the loaded values, or the s_waitcnt lands
     // in front of the compute phase the loads are supposed to hide behind.  store() applies the zero padding.
     __device__ __forceinline__ void load(const float *src, int F, int dh, int row0, int row_lim, int tid) {
-        const bool vec = ((dh & 3) == 0) && ((F & 3) == 0) && ((reinterpret_cast<uintptr_t>(src) & 15) == 0);
+        const bool vec = ATTN_FLOAT4_ROWS(dh, F, src);
         const int last = row_lim > 0 ? row_lim - 1 : 0;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
@@ -168,7 +168,7 @@ mhsa_fwd_kernel(const float *__restrict__ Q, const float *__restrict__ K, const 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, g = lane >> 4;
     const int row0 = rb * RPB;
     const int dh4 = (dh + 3) & ~3, nb = dh4 >> 4, rem = (dh4 & 15) >> 2;
-    const bool vecq = ((dh & 3) == 0) && ((ldi & 3) == 0) && ((reinterpret_cast<uintptr_t>(Q + base) & 15) == 0);
+    const bool vecq = ATTN_FLOAT4_ROWS(dh, ldi, Q + base);
 
     const uint32_t thr = drop_thr(a.p_drop);
     float m[RT], l[RT];
@@ -253,7 +253,7 @@ mhsa_fwd_kernel(const float *__restrict__ Q, const float *__restrict__ K, const 
         }
     }
     const float keep_inv = thr != 0 ? 1.0f / (1.0f - a.p_drop) : 1.0f;
-    const bool vec = ((dh & 3) == 0) && ((F & 3) == 0) && ((reinterpret_cast<uintptr_t>(O + obase) & 15) == 0);
+    const bool vec = ATTN_FLOAT4_ROWS(dh, F, O + obase);
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
         const int row = row0 + wrow + 16 * rt + j;
@@ -369,7 +369,7 @@ mhsa_bwd_dq_kernel(const float *__restrict__ Q, const float *__restrict__ K, con
         }
     }
     if (!rok) return;
-    const bool vec = ((dh & 3) == 0) && ((ldi & 3) == 0) && ((reinterpret_cast<uintptr_t>(dQ + base) & 15) == 0);
+    const bool vec = ATTN_FLOAT4_ROWS(dh, ldi, dQ + base);
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
         const int d = 16 * dt + 4 * g;
@@ -445,7 +445,7 @@ mhsa_bwd_dq_ds_kernel(const float *__restrict__ K, const float *__restrict__ dS_
         }
     }
     if (!rok) return;
-    const bool vec = ((dh & 3) == 0) && ((ldi & 3) == 0) && ((reinterpret_cast<uintptr_t>(dQ + base) & 15) == 0);
+    const bool vec = ATTN_FLOAT4_ROWS(dh, ldi, dQ + base);
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
         const int d = 16 * dt + 4 * g;
@@ -504,7 +504,7 @@ mhsa_bwd_dkv_kernel(const float *__restrict__ Q, const float *__restrict__ K, co
     if (live) prefetch(0);
     OperandRegs<DT> kr[1], vr[1];                          // this wave's 16 keys as B operands, for the whole kernel
     {
-        const bool vk = ((dh & 3) == 0) && ((ldi & 3) == 0) && ((reinterpret_cast<uintptr_t>(K + base) & 15) == 0) &&
+        const bool vk = ATTN_FLOAT4_ROWS(dh, ldi, K + base) &&
                         ((reinterpret_cast<uintptr_t>(V + base) & 15) == 0);
         const bool kok = key < n;
         const size_t ko = (size_t)(key < L ? key : L - 1) * ldi;
@@ -572,7 +572,7 @@ mhsa_bwd_dkv_kernel(const float *__restrict__ Q, const float *__restrict__ K, co
         }
     }
     if (key >= L) return;
-    const bool vec = ((dh & 3) == 0) && ((ldi & 3) == 0) && ((reinterpret_cast<uintptr_t>(dK + base) & 15) == 0) &&
+    const bool vec = ATTN_FLOAT4_ROWS(dh, ldi, dK + base) &&
                      ((reinterpret_cast<uintptr_t>(dV + base) & 15) == 0);
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
@@ -728,8 +728,6 @@ layernorm_reduce_kernel(const float *__restrict__ part, int nblk, int F, float *
     }
 }
 
-constexpr int kLnBlocks = 1024;
-
 template <class Fn> inline int dispatch_dt(int DT, Fn &&f) {
     switch (DT) {
         case 1: return f.template operator()<1>();
@@ -740,6 +738,16 @@ template <class Fn> inline int dispatch_dt(int DT, Fn &&f) {
         case 6: return f.template operator()<6>();
         case 7: return f.template operator()<7>();
         default: return f.template operator()<8>();
+    }
+}
+
+template <class Fn> inline int dispatch_ni(int NI, Fn &&f) {
+    switch (NI) {
+        case 1: return f.template operator()<1>();
+        case 2: return f.template operator()<2>();
+        case 3: return f.template operator()<3>();
+        case 4: return f.template operator()<4>();
+        default: return f.template operator()<0>();
     }
 }
 
@@ -756,9 +764,7 @@ static int attn_args(const char *who, int B, int L, int F, int H, int ld, float 
 
 }  // namespace ptr
 
-// Waves per workgroup: 4 lets two independent workgroups share a CU, so one group's barrier / staging phases are covered by the
-// other's MFMA work; 8 would halve the K/V re-staging traffic.  Only the dK / dV kernel of the widest heads runs 8 waves (its 4-wave
-// form spills more); the 8-wave forms of the other kernels were a measurement switch and are in git history.
+// The forms: attn_form (ptr_attn.h).  The 8-wave forms of the kernels other than dK / dV were a measurement switch and are in git history.
 extern "C" int ptr_mhsa_forward(const float *Q, const float *K, const float *V, int ld_qkv, const int32_t *lens, int B, int L, int F,
                                 int n_heads, float p_drop, uint64_t seed, int site, float *O, float *lse, void *stream) {
     using namespace ptr;
@@ -768,9 +774,9 @@ extern "C" int ptr_mhsa_forward(const float *Q, const float *K, const float *V, 
     if (B == 0) return 0;
     if (!Q || !K || !V || !O || !lse) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
     hipStream_t st = as_stream(stream);
-    if (a.dh > kAttnNarrowMaxHeadDim) return mhsa_wide_forward(Q, K, V, lens, a, O, lse, st, who);      // listsf_wide.hip
-    const int DT = (a.dh + 15) / 16;
-    return dispatch_dt(DT, [&]<int D>() -> int {
+    const AttnForm f = attn_form(a.dh, L, false);
+    if (f.wide) return mhsa_wide_forward(f.D, Q, K, V, lens, a, O, lse, st, who);      // listsf_wide.hip
+    return dispatch_dt(f.D, [&]<int D>() -> int {
         auto launch = [&]<int RT, int NW>() -> int {
             constexpr int RPB = 16 * RT * NW;
             auto kern = mhsa_fwd_kernel<D, RT, NW>;
@@ -780,9 +786,8 @@ extern "C" int ptr_mhsa_forward(const float *Q, const float *K, const float *V, 
             hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)B * n_heads * nrb)), dim3(NW * 64), lds, st, Q, K, V, lens, a, O, lse);
             return check_hip(hipGetLastError(), who);
         };
-        // two row tiles per wave (every K / V operand read feeds two MFMAs) when the rows exist and the registers allow it
-        if constexpr (D <= 5) {
-            if (L > 64) return launch.template operator()<2, 4>();
+        if constexpr (D <= 5) {                                     // the only D with a two-tile form
+            if (f.fwd_row_tiles == 2) return launch.template operator()<2, 4>();
         }
         return launch.template operator()<1, 4>();
     });
@@ -802,9 +807,9 @@ extern "C" int ptr_mhsa_backward(const float *Q, const float *K, const float *V,
     const int rblocks = (int)((nrows + 15) / 16 < 4096 ? (nrows + 15) / 16 : 4096);
     hipLaunchKernelGGL(attn_rowdot_kernel, dim3(rblocks), dim3(256), 0, st, O, dO, a, dvec);
     if (int rc = check_hip(hipGetLastError(), who)) return rc;
-    if (a.dh > kAttnNarrowMaxHeadDim) return mhsa_wide_backward(Q, K, V, dO, lse, dvec, lens, a, dQ, dK, dV, ds_ws, st, who);
-    const int DT = (a.dh + 15) / 16;
-    return dispatch_dt(DT, [&]<int D>() -> int {
+    const AttnForm f = attn_form(a.dh, L, ds_ws != nullptr);
+    if (f.wide) return mhsa_wide_backward(f.D, Q, K, V, dO, lse, dvec, lens, a, dQ, dK, dV, ds_ws, st, who);
+    return dispatch_dt(f.D, [&]<int D>() -> int {
         auto launch_dq = [&]<int NW>() -> int {
             constexpr int RPB = 16 * NW;
             auto kern = mhsa_bwd_dq_kernel<D, NW>;
@@ -823,7 +828,7 @@ extern "C" int ptr_mhsa_backward(const float *Q, const float *K, const float *V,
                 hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)B * n_heads * nkb)), dim3(NW * 64), lds, st, Q, K, V, dO, lse, dvec, lens, a, dK, dV, ds_ws);
                 return check_hip(hipGetLastError(), who);
             };
-            return ds_ws ? go(mhsa_bwd_dkv_kernel<D, NW, true>) : go(mhsa_bwd_dkv_kernel<D, NW, false>);
+            return f.store_ds ? go(mhsa_bwd_dkv_kernel<D, NW, true>) : go(mhsa_bwd_dkv_kernel<D, NW, false>);
         };
         auto launch_dq_ds = [&]<int NW>() -> int {
             constexpr int RPB = 16 * NW;
@@ -834,13 +839,13 @@ extern "C" int ptr_mhsa_backward(const float *Q, const float *K, const float *V,
             hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)B * n_heads * nrb)), dim3(NW * 64), lds, st, K, ds_ws, lens, a, dQ);
             return check_hip(hipGetLastError(), who);
         };
-        auto dkv = [&]() -> int {                                   // 4-wave dK/dV variants of the widest heads spill more
-            if constexpr (D >= 7) {
-                if (L > 64) return launch_dkv.template operator()<8>();
+        auto dkv = [&]() -> int {
+            if constexpr (D >= 7) {                                 // the only D with an 8-wave form
+                if (f.dkv_waves == 8) return launch_dkv.template operator()<8>();
             }
             return launch_dkv.template operator()<4>();
         };
-        if (ds_ws) {   // dK / dV first (it writes dS), then dQ as ONE GEMM unit from the stored dS
+        if (f.store_ds) {   // dK / dV first (it writes dS), then dQ as ONE GEMM unit from the stored dS
             if (int rc = dkv()) return rc;
             return launch_dq_ds.template operator()<4>();
         }
@@ -867,15 +872,11 @@ extern "C" int ptr_layernorm_forward(const float *X, const float *a2, const floa
     if (R < 0 || F < 2) { set_error("%s: bad shape R=%lld F=%d", who, (long long)R, F); return PTR_ERR_INVALID_ARG; }
     if (R == 0) return 0;
     if (!X || !a2 || !b2 || !Y || !stats) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
-    const int blocks = (int)((R + 3) / 4 < 8192 ? (R + 3) / 4 : 8192);
-    const int ni = (F + 63) / 64;
-    auto launch = [&]<int NI>() {
-        hipLaunchKernelGGL(layernorm_fwd_kernel<NI>, dim3(blocks), dim3(256), 0, as_stream(stream), X, a2, b2, (size_t)R, F, eps, Y, stats);
-    };
-    if (ni == 1) launch.template operator()<1>(); else if (ni == 2) launch.template operator()<2>();
-    else if (ni == 3) launch.template operator()<3>(); else if (ni == 4) launch.template operator()<4>();
-    else launch.template operator()<0>();
-    return check_hip(hipGetLastError(), who);
+    const LnForm f = layernorm_form(R, F);
+    return dispatch_ni(f.NI, [&]<int NI>() {
+        hipLaunchKernelGGL(layernorm_fwd_kernel<NI>, dim3(f.fwd_blocks), dim3(256), 0, as_stream(stream), X, a2, b2, (size_t)R, F, eps, Y, stats);
+        return check_hip(hipGetLastError(), who);
+    });
 }
 
 extern "C" size_t ptr_layernorm_backward_ws_floats(int F) { return (size_t)ptr::kLnBlocks * 2 * (size_t)(F > 0 ? F : 0); }
@@ -888,20 +889,14 @@ extern "C" int ptr_layernorm_backward(const float *X, const float *a2, const flo
     if (!a2 || !da2 || !db2 || !ws || (R > 0 && (!X || !dY || !stats || !dX))) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
     const size_t lds = (size_t)4 * 2 * F * sizeof(float);
     if (lds > 160 * 1024) { set_error("%s: F=%d too wide", who, F); return PTR_ERR_UNSUPPORTED; }
-    const int ni = (F + 63) / 64;
     hipStream_t st = as_stream(stream);
-    int blocks = (int)((R + 3) / 4 < kLnBlocks ? (R + 3) / 4 : kLnBlocks);
-    if (blocks < 1) blocks = 1;
-    auto launch = [&]<int NI>() -> int {
+    const LnForm f = layernorm_form(R, F);
+    const int rc0 = dispatch_ni(f.NI, [&]<int NI>() -> int {
         if (int e = allow_lds(layernorm_bwd_kernel<NI>, lds)) return e;
-        hipLaunchKernelGGL(layernorm_bwd_kernel<NI>, dim3(blocks), dim3(256), lds, st, X, a2, dY, stats, (size_t)R, F, dX, ws);
+        hipLaunchKernelGGL(layernorm_bwd_kernel<NI>, dim3(f.bwd_blocks), dim3(256), lds, st, X, a2, dY, stats, (size_t)R, F, dX, ws);
         return check_hip(hipGetLastError(), who);
-    };
-    int rc0;
-    if (ni == 1) rc0 = launch.template operator()<1>(); else if (ni == 2) rc0 = launch.template operator()<2>();
-    else if (ni == 3) rc0 = launch.template operator()<3>(); else if (ni == 4) rc0 = launch.template operator()<4>();
-    else rc0 = launch.template operator()<0>();
+    });
     if (rc0) return rc0;
-    hipLaunchKernelGGL(layernorm_reduce_kernel, dim3((2 * F + 15) / 16), dim3(256), 0, st, ws, blocks, F, da2, db2);
+    hipLaunchKernelGGL(layernorm_reduce_kernel, dim3((2 * F + 15) / 16), dim3(256), 0, st, ws, f.bwd_blocks, F, da2, db2);
     return check_hip(hipGetLastError(), who);
 }

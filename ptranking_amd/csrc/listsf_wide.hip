@@ -32,10 +32,7 @@ constexpr int kWideChunk = 16;                     // streamed rows per LDS chun
 // Yahoo! head of 350 starts 1400 bytes into its row), else 1.  Columns at and beyond dh are never touched: a group of `mode` columns is
 // inside or outside the head as a whole.
 __device__ __forceinline__ int wide_access_mode(int dh, int stride, const void *p) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    if (((dh | stride) & 3) == 0 && (a & 15) == 0) return 4;
-    if (((dh | stride) & 1) == 0 && (a & 7) == 0) return 2;
-    return 1;
+    return wide_access_width(dh, stride, reinterpret_cast<uintptr_t>(p));       // ptr_attn.h
 }
 using f32x2v = __attribute__((ext_vector_type(2))) float;
 // Columns c .. c + 3 of a row, raw: columns at and beyond dh read (a valid) column 0 instead and are zeroed by the caller.
@@ -457,15 +454,15 @@ mhsa_wide_bwd_dkv_kernel(const float *__restrict__ Q, const float *__restrict__ 
 constexpr int kWideMaxDT = 22;
 static_assert(PTR_MHSA_MAX_HEAD_DIM == 16 * kWideMaxDT, "the widest form is the public limit");
 
-// DT = column tiles rounded up to even: one form per 32 columns of head dimension, 129 .. 352.
-template <class Fn> inline int dispatch_wide_dt(int dh, Fn &&f) {
-    switch ((dh + 31) / 32) {
-        case 5: return f.template operator()<10>();
-        case 6: return f.template operator()<12>();
-        case 7: return f.template operator()<14>();
-        case 8: return f.template operator()<16>();
-        case 9: return f.template operator()<18>();
-        case 10: return f.template operator()<20>();
+// Calls f.template operator()<DT>() for the D of a wide attn_form (ptr_attn.h): head dimensions 129 .. 352.
+template <class Fn> inline int dispatch_wide_dt(int DT, Fn &&f) {
+    switch (DT) {
+        case 10: return f.template operator()<10>();
+        case 12: return f.template operator()<12>();
+        case 14: return f.template operator()<14>();
+        case 16: return f.template operator()<16>();
+        case 18: return f.template operator()<18>();
+        case 20: return f.template operator()<20>();
         default: return f.template operator()<kWideMaxDT>();
     }
 }
@@ -479,16 +476,16 @@ static int wide_launch(K kern, const AttnArgs &a, int lds_rows, int DT, size_t l
     return check_hip(hipGetLastError(), who);
 }
 
-int mhsa_wide_forward(const float *Q, const float *K, const float *V, const int32_t *lens, const AttnArgs &a, float *O, float *LSE,
+int mhsa_wide_forward(int DT, const float *Q, const float *K, const float *V, const int32_t *lens, const AttnArgs &a, float *O, float *LSE,
                       hipStream_t st, const char *who) {
-    return dispatch_wide_dt(a.dh, [&]<int D>() -> int {
+    return dispatch_wide_dt(DT, [&]<int D>() -> int {
         return wide_launch(mhsa_wide_fwd_kernel<D>, a, 2 * kWideChunk, D, 0, st, who, Q, K, V, lens, a, O, LSE);
     });
 }
 
-int mhsa_wide_backward(const float *Q, const float *K, const float *V, const float *dO, const float *LSE, const float *Dv,
+int mhsa_wide_backward(int DT, const float *Q, const float *K, const float *V, const float *dO, const float *LSE, const float *Dv,
                        const int32_t *lens, const AttnArgs &a, float *dQ, float *dK, float *dV, float *ds_ws, hipStream_t st, const char *who) {
-    return dispatch_wide_dt(a.dh, [&]<int D>() -> int {
+    return dispatch_wide_dt(DT, [&]<int D>() -> int {
         constexpr size_t extra = 2 * kWideChunk + kWideNW * 16 * kDsPadLd;                // lse_s, D_s, the dS transpose pads
         auto dkv = [&](auto kern) -> int {
             return wide_launch(kern, a, 2 * kWideChunk + kWideRows, D, extra, st, who, Q, K, V, dO, LSE, Dv, lens, a, dK, dV, ds_ws);

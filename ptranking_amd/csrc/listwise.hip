@@ -157,21 +157,28 @@ listnet_vec_kernel(const float *__restrict__ preds, const float *__restrict__ la
     if (valid && t == 0) loss_q[q] = n > 0 ? loss : 0.0f;
 }
 
-// true when the register kernel serves the batch; launches it
-static int launch_listnet_vec(const float *preds, const float *labels, const int32_t *lens, int B, int L, float *loss_q, float *grad,
-                              hipStream_t st, bool *served) {
-    *served = false;
-    if (L % 4 != 0 || L > 1024) return 0;
-    if ((reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(grad)) & 15) return 0;
-    *served = true;
+// The register kernels serve 16-byte aligned rows of a multiple of four documents, up to 1024: V float4 per lane, and for ListNet (whose
+// groups may be a part of a wavefront) G lanes per query.  Everything else takes the LDS kernels.
+VecForm listmle_form(int L, bool aligned) {
+    if (L % 4 != 0 || L > 1024 || !aligned) return {0, kWave, 0};
+    return {1, kWave, vec_per_lane(L)};
+}
+VecForm listnet_form(int L, bool aligned) {
+    VecForm f = listmle_form(L, aligned);
+    if (f.vec) f.G = L <= 64 ? 16 : L <= 128 ? 32 : 64;
+    return f;
+}
+
+static int launch_listnet_vec(VecForm f, const float *preds, const float *labels, const int32_t *lens, int B, int L, float *loss_q, float *grad,
+                              hipStream_t st) {
     auto go = [&]<int G, int V>() -> int {
         constexpr int QPB = (kBlock / kWave) * (kWave / G);
         return launch_queries(listnet_vec_kernel<G, V>, B, QPB, kBlock, 0, st, "ptr_listnet_fwd_bwd", preds, labels, lens, B, L, loss_q, grad);
     };
-    if (L <= 64) return go.template operator()<16, 1>();
-    if (L <= 128) return go.template operator()<32, 1>();
-    if (L <= 256) return go.template operator()<64, 1>();
-    if (L <= 512) return go.template operator()<64, 2>();
+    if (f.G == 16) return go.template operator()<16, 1>();
+    if (f.G == 32) return go.template operator()<32, 1>();
+    if (f.V == 1) return go.template operator()<64, 1>();
+    if (f.V == 2) return go.template operator()<64, 2>();
     return go.template operator()<64, 4>();
 }
 
@@ -337,17 +344,13 @@ listmle_vec_kernel(const float *__restrict__ preds, const int64_t *__restrict__ 
         if (p0 + 4 * mm < L) go[(p0 >> 2) + mm] = g[mm];
     if (lane == 0) loss_q[q] = loss;
 }
-static int launch_listmle_vec(const float *preds, const int64_t *perm, const int32_t *lens, int B, int L, float *loss_q, float *grad,
-                              hipStream_t st, bool *served) {
-    *served = false;
-    if (L % 4 != 0 || L > 1024) return 0;
-    if ((reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(perm) | reinterpret_cast<uintptr_t>(grad)) & 15) return 0;
-    *served = true;
+static int launch_listmle_vec(VecForm f, const float *preds, const int64_t *perm, const int32_t *lens, int B, int L, float *loss_q, float *grad,
+                              hipStream_t st) {
     auto go = [&]<int V>() -> int {
         return launch_queries(listmle_vec_kernel<V>, B, 4, kBlock, 0, st, "ptr_listmle_fwd_bwd", preds, perm, lens, B, L, loss_q, grad);
     };
-    if (L <= 256) return go.template operator()<1>();
-    if (L <= 512) return go.template operator()<2>();
+    if (f.V == 1) return go.template operator()<1>();
+    if (f.V == 2) return go.template operator()<2>();
     return go.template operator()<4>();
 }
 
@@ -680,9 +683,10 @@ extern "C" int ptr_listnet_fwd_bwd(const float *preds, const float *labels, cons
     const char *who = "ptr_listnet_fwd_bwd";
     if (int rc = check_loss_args(preds, labels, B, L, loss_q && grad, who)) return rc;
     if (B > 0) {
-        bool served = false;
-        if (int rc = launch_listnet_vec(preds, labels, lens, B, L, loss_q, grad, as_stream(stream), &served)) return rc;
-        if (!served) {                                        // unaligned rows, L % 4 != 0, L > 1024: the LDS kernel
+        const VecForm f = listnet_form(L, aligned16(preds, labels, grad));
+        if (f.vec) {
+            if (int rc = launch_listnet_vec(f, preds, labels, lens, B, L, loss_q, grad, as_stream(stream))) return rc;
+        } else {                                              // unaligned rows, L % 4 != 0, L > 1024: the LDS kernel
             const int Lp = round_up(L, 4);
             const size_t per_q = 2 * (size_t)Lp * sizeof(float);
             const int wpb = waves_per_block(per_q);
@@ -737,9 +741,10 @@ extern "C" int ptr_listmle_fwd_bwd(const float *preds, const int64_t *perm, cons
     const char *who = "ptr_listmle_fwd_bwd";
     if (int rc = check_loss_args(preds, perm, B, L, loss_q && grad, who)) return rc;
     if (B > 0) {
-        bool served = false;
-        if (int rc = launch_listmle_vec(preds, perm, lens, B, L, loss_q, grad, as_stream(stream), &served)) return rc;
-        if (!served) {                                        // unaligned rows, L % 4 != 0, L > 1024: the LDS kernel
+        const VecForm f = listmle_form(L, aligned16(preds, perm, grad));
+        if (f.vec) {
+            if (int rc = launch_listmle_vec(f, preds, perm, lens, B, L, loss_q, grad, as_stream(stream))) return rc;
+        } else {                                              // unaligned rows, L % 4 != 0, L > 1024: the LDS kernel
             const int Lp = round_up(L, 4);
             const size_t per_q = 4 * (size_t)Lp * sizeof(float);
             const int wpb = waves_per_block(per_q);

@@ -216,40 +216,51 @@ pairwise_bce_kernel(const float *__restrict__ preds, const float *__restrict__ l
 }
 
 
+// LambdaRank with sigma > 0 up to 512 documents: the ring kernel (ptr_ring.h), one wavefront per query, 1 / 2 / 4 / 8 documents per lane.
+// RankNet up to 32 documents: two queries per wavefront.  Everything else: pairwise_bce_kernel on pick_tiling.
+PairwiseForm pairwise_form(bool weighted, int B, int L, bool sigma_positive) {
+    if (weighted && L <= kRingMaxLen && sigma_positive && env_int("PTR_LAMBDARANK_RING", 1)) {     // 0: the LDS kernel (tests)
+        const int dpt = L <= 64 ? 1 : L <= 128 ? 2 : L <= 256 ? 4 : 8;
+        int QPB = kRingBlock / kWave;             // waves per workgroup: fewer when the batch does not fill the CUs
+        while (QPB > 1 && B < QPB * num_cus()) QPB >>= 1;
+        if (dpt >= 4 && QPB > kRing4Waves) QPB = kRing4Waves;
+        if (dpt >= 8 && QPB > 4) QPB = 4;
+        return {kPairwiseRing, kWave, dpt, QPB};
+    }
+    if (!weighted && L <= 32) return {kPairwiseHalfWave, 32, 1, kBlock / 32};
+    const Tiling t = pick_tiling(L);
+    return {kPairwiseLds, t.G, t.DPT, kBlock / t.G};
+}
+
 template <bool WEIGHTED>
 static int launch_pairwise(const float *preds, const float *labels, const int32_t *lens, int B, int L, float sigma,
                            float *loss_out, float *loss_q, float *grad, void *stream, const char *who) {
     if (int rc = check_loss_args(preds, labels, B, L, loss_q && grad, who)) return rc;
     if (WEIGHTED && !(sigma >= 0.0f)) { set_error("%s: sigma must be >= 0 (got %g)", who, (double)sigma); return PTR_ERR_INVALID_ARG; }
     hipStream_t st = as_stream(stream);
-    if (WEIGHTED && B > 0 && L <= 512 && sigma > 0.0f && env_int("PTR_LAMBDARANK_RING", 1)) {     // 0: the LDS kernel (tests)
-        const int dpt = L <= 64 ? 1 : L <= 128 ? 2 : L <= 256 ? 4 : 8;
-        int QPB = kRingBlock / kWave;             // waves per workgroup: fewer when the batch does not fill the CUs
-        while (QPB > 1 && B < QPB * num_cus()) QPB >>= 1;
-        if (dpt >= 4 && QPB > kRing4Waves) QPB = kRing4Waves;
-        if (dpt >= 8 && QPB > 4) QPB = 4;
-        if (dpt < 8) {                            // pairwise_ring.hip
-            if (int e = launch_lambdarank_ring_small(dpt, QPB, preds, labels, lens, B, L, sigma, loss_q, grad, st)) return check_hip((hipError_t)e, who);
-        } else {
-            const size_t lds = (size_t)QPB * 2 * 64 * dpt * sizeof(float);
-            if (int rc = launch_queries(lambdarank_ring_kernel<8>, B, QPB, QPB * kWave, lds, stream, who, preds, labels, lens, B, L, sigma, loss_q, grad)) return rc;
-        }
-    } else if (!WEIGHTED && B > 0 && L <= 32) {
-        if constexpr (!WEIGHTED) {               // RankNet on short lists: two queries per wavefront
-            const int Lp = round_up(L, 4);
-            constexpr int QPB = kBlock / 32;
-            const size_t lds = QPB * pairwise_group_floats(Lp, 1) * sizeof(float);
-            if (int rc = launch_queries(pairwise_bce_kernel<32, 1, false>, B, QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, Lp, sigma, loss_q, grad)) return rc;
-        }
-    } else if (B > 0) {
+    int rc = 0;
+    if (B > 0) {
+        const PairwiseForm f = pairwise_form(WEIGHTED, B, L, sigma > 0.0f);
         const int Lp = round_up(L, 4);
-        int rc = dispatch_tiling(L, [&]<int G, int DPT>() -> int {
-            constexpr int QPB = kBlock / G, NW = G / kWave;
-            const size_t lds = QPB * pairwise_group_floats(Lp, NW) * sizeof(float);
-            return launch_queries(pairwise_bce_kernel<G, DPT, WEIGHTED>, B, QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, Lp, sigma, loss_q, grad);
-        });
-        if (rc) return rc;
+        if (f.kind == kPairwiseRing && f.DPT < 8) {         // pairwise_ring.hip
+            rc = check_hip((hipError_t)launch_lambdarank_ring_small(f.DPT, f.QPB, preds, labels, lens, B, L, sigma, loss_q, grad, st), who);
+        } else if (f.kind == kPairwiseRing) {
+            const size_t lds = (size_t)f.QPB * 2 * 64 * f.DPT * sizeof(float);
+            rc = launch_queries(lambdarank_ring_kernel<8>, B, f.QPB, f.QPB * kWave, lds, stream, who, preds, labels, lens, B, L, sigma, loss_q, grad);
+        } else if (f.kind == kPairwiseHalfWave) {
+            if constexpr (!WEIGHTED) {               // RankNet on short lists: two queries per wavefront
+                const size_t lds = f.QPB * pairwise_group_floats(Lp, 1) * sizeof(float);
+                rc = launch_queries(pairwise_bce_kernel<32, 1, false>, B, f.QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, Lp, sigma, loss_q, grad);
+            }
+        } else {
+            rc = dispatch_tiling(L, [&]<int G, int DPT>() -> int {
+                constexpr int QPB = kBlock / G, NW = G / kWave;
+                const size_t lds = QPB * pairwise_group_floats(Lp, NW) * sizeof(float);
+                return launch_queries(pairwise_bce_kernel<G, DPT, WEIGHTED>, B, QPB, kBlock, lds, stream, who, preds, labels, lens, B, L, Lp, sigma, loss_q, grad);
+            });
+        }
     }
+    if (rc) return rc;
     return finish_loss(loss_q, B, 1.0f, loss_out, stream);
 }
 

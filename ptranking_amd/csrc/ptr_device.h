@@ -22,6 +22,9 @@ int check_hip(hipError_t e, const char *what);
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+inline bool aligned16(const void *a, const void *b, const void *c) {      // the float4 kernels' condition on their three arrays
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+}
 
 // The one reader of the PTR_* run-time switches: unset or empty gives `dflt`, anything else its atoi value.  Read per
 // call, so a test can flip a switch inside one process.
@@ -44,6 +47,9 @@ inline int num_cus() {
 // Shapes: L in (0, PTR_MAX_LIST_LEN]; B >= 0.  Returns 0 or an error code (message set).
 int check_batch(const void *preds, const void *second, int B, int L, const char *who);
 
+// ---- launch forms: which kernel form serves a shape.  Each family's launcher computes its form with a pure host function (no pointers: an
+// alignment comes in as a flag) and switches on it; ptr_launch_form (abi.hip) answers with the same functions.  A form is a struct of ints.
+
 // (G, DPT) tiling by list length: G*DPT >= round_up(L, 4) always holds.
 struct Tiling { int G; int DPT; };
 inline Tiling pick_tiling(int L) {
@@ -56,36 +62,84 @@ inline Tiling pick_tiling(int L) {
     return {256, 16};
 }
 
-// Calls f.template operator()<G, DPT>() for the tiling of L.
-template <class F> inline int dispatch_tiling(int L, F &&f) {
-    Tiling t = pick_tiling(L);
-    if (t.G == 64 && t.DPT == 1) return f.template operator()<64, 1>();
-    if (t.G == 64 && t.DPT == 2) return f.template operator()<64, 2>();
-    if (t.DPT == 1) return f.template operator()<256, 1>();
-    if (t.DPT == 2) return f.template operator()<256, 2>();
-    if (t.DPT == 4) return f.template operator()<256, 4>();
-    if (t.DPT == 8) return f.template operator()<256, 8>();
-    return f.template operator()<256, 16>();
-}
-
 // Tiling of the sort / metric kernels: ONE wavefront per query up to 1024 documents (the rank step is a register bitonic sort of
 // 64*DPT keys, ptr_device.h wave_sort_desc), the four-wave counting form beyond.
-template <class F> inline int dispatch_wave_tiling(int L, F &&f) {
-    if (L <= 64) return f.template operator()<64, 1>();
-    if (L <= 128) return f.template operator()<64, 2>();
-    if (L <= 256) return f.template operator()<64, 4>();
-    if (L <= 512) return f.template operator()<64, 8>();
-    if (L <= 1024) return f.template operator()<64, 16>();
-    if (L <= 2048) return f.template operator()<256, 8>();
-    return f.template operator()<256, 16>();
+inline Tiling pick_wave_tiling(int L) {
+    if (L <= 64) return {64, 1};
+    if (L <= 128) return {64, 2};
+    if (L <= 256) return {64, 4};
+    if (L <= 512) return {64, 8};
+    if (L <= 1024) return {64, 16};
+    if (L <= 2048) return {256, 8};
+    return {256, 16};
 }
 
+// One wavefront per query up to 256 documents, pick_tiling beyond.
+inline Tiling pick_wave256_tiling(int L) { return L <= 256 ? pick_wave_tiling(L) : pick_tiling(L); }
+
+// Call f.template operator()<G, DPT>() for a tiling; each names exactly the forms its pick_* function returns.
+template <class F> inline int dispatch_tiling(int L, F &&f) {
+    const Tiling t = pick_tiling(L);
+    if (t.G == 64) return t.DPT == 1 ? f.template operator()<64, 1>() : f.template operator()<64, 2>();
+    switch (t.DPT) {
+        case 1: return f.template operator()<256, 1>();
+        case 2: return f.template operator()<256, 2>();
+        case 4: return f.template operator()<256, 4>();
+        case 8: return f.template operator()<256, 8>();
+        default: return f.template operator()<256, 16>();
+    }
+}
+template <class F> inline int dispatch_wave_tiling(int L, F &&f) {
+    const Tiling t = pick_wave_tiling(L);
+    if (t.G == 64) switch (t.DPT) {
+        case 1: return f.template operator()<64, 1>();
+        case 2: return f.template operator()<64, 2>();
+        case 4: return f.template operator()<64, 4>();
+        case 8: return f.template operator()<64, 8>();
+        default: return f.template operator()<64, 16>();
+    }
+    return t.DPT == 8 ? f.template operator()<256, 8>() : f.template operator()<256, 16>();
+}
 template <class F> inline int dispatch_wave256_tiling(int L, F &&f) {
-    if (L <= 64) return f.template operator()<64, 1>();
-    if (L <= 128) return f.template operator()<64, 2>();
-    if (L <= 256) return f.template operator()<64, 4>();
+    const Tiling t = pick_wave256_tiling(L);
+    if (t.G == 64) return t.DPT == 1 ? f.template operator()<64, 1>() : t.DPT == 2 ? f.template operator()<64, 2>() : f.template operator()<64, 4>();
     return dispatch_tiling(L, f);
 }
+
+// The smooth-rank kernels (ApproxNDCG, the sigmoid and Gaussian metric objectives): up to 512 documents one wavefront per query holds the list
+// in registers, ring_dpt(L) documents per lane (the "ring" form); longer lists, or a caller that rules the ring out, take pick_tiling.
+constexpr int kRingMaxLen = 512;
+inline int ring_dpt(int L) { return L <= 64 ? 1 : L <= 128 ? 2 : L <= 192 ? 3 : L <= 256 ? 4 : L <= 384 ? 6 : 8; }
+struct RingForm { int ring; int G; int DPT; };           // ring: 1 = the ring form (G = 64), 0 = the LDS form on pick_tiling
+inline RingForm ring_form(int L, bool ring_allowed = true) {
+    if (L <= kRingMaxLen && ring_allowed) return {1, kWave, ring_dpt(L)};
+    const Tiling t = pick_tiling(L);
+    return {0, t.G, t.DPT};
+}
+// Calls f.template operator()<DPT>() for a ring_dpt value.
+template <class F> inline int dispatch_ring_dpt(int dpt, F &&f) {
+    switch (dpt) {
+        case 1: return f.template operator()<1>();
+        case 2: return f.template operator()<2>();
+        case 3: return f.template operator()<3>();
+        case 4: return f.template operator()<4>();
+        case 6: return f.template operator()<6>();
+        default: return f.template operator()<8>();
+    }
+}
+
+RingForm approxndcg_form(int L);                                                          // approxndcg.hip: ring_form under PTR_APPROX_RING
+
+// The forms of the other loss families, each defined beside its launcher.
+struct PairwiseForm { int kind; int G; int DPT; int QPB; };      // kind: 0 = LDS kernel on pick_tiling, 1 = ring (QPB waves per workgroup), 2 = half-wave
+enum { kPairwiseLds = 0, kPairwiseRing = 1, kPairwiseHalfWave = 2 };
+PairwiseForm pairwise_form(bool weighted, int B, int L, bool sigma_positive);             // pairwise.hip
+struct VecForm { int vec; int G; int V; };               // vec: 1 = the register kernel, G lanes per query and V float4 per lane; 0 = the other kernel
+inline int vec_per_lane(int L) { return L <= 256 ? 1 : L <= 512 ? 2 : 4; }                // float4 per lane: one wavefront holds L <= 1024 documents
+VecForm listnet_form(int L, bool aligned);                                               // listwise.hip
+VecForm listmle_form(int L, bool aligned);
+VecForm lambdaloss_form(int L, int k, int loss_type, int presort, bool aligned);          // lambdaloss.hip: vec = top-k; else (G, DPT) in (G, V)
+Tiling wassrank_form(int L);                                                              // wassrank.hip
 
 // Grid of a PERSISTENT kernel (its wavefronts walk the work with a grid stride): the blocks the device keeps resident at once — CUs x the
 // occupancy of `kernel` at `block` threads and `lds` bytes of dynamic LDS — capped by the blocks the work needs.  Cached per kernel.

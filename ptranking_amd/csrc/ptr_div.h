@@ -13,9 +13,14 @@ constexpr size_t kLdsPerWorkgroup = 160 * 1024;       // gfx950: 160 KiB per CU,
 // ---------------------------------------------------------------- host side
 inline int tp_of(int T) { return T <= 4 ? 4 : T <= 8 ? 8 : T <= 16 ? 16 : 32; }
 
-// Calls f.template operator()<TP>() for the subtopic tile of T.
-template <class F> inline int dispatch_tp(int T, F &&f) {
-    const int TP = tp_of(T);
+// The form of the loss kernels: G threads per query (one wavefront and four queries per workgroup up to 128 documents, when the four tiles
+// fit the LDS; else the whole workgroup on one query) and the subtopic tile TP.
+struct DivForm { int G; int TP; };
+inline DivForm div_form(int T, int L, bool four_tiles_fit = true) { return {L <= 128 && four_tiles_fit ? kWave : kBlock, tp_of(T)}; }
+DivForm divprob_form(int objective, int T, int L);                                        // divprob.hip: by its objective's LDS need
+
+// Calls f.template operator()<TP>() for a subtopic tile.
+template <class F> inline int dispatch_tp(int TP, F &&f) {
     if (TP == 4) return f.template operator()<4>();
     if (TP == 8) return f.template operator()<8>();
     if (TP == 16) return f.template operator()<16>();

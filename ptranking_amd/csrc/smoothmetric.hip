@@ -322,22 +322,16 @@ extern "C" int ptr_smoothmetric_fwd_bwd(const float *preds, const float *labels,
             if (int rc = smooth_max_label_launch(labels, lens, B, L, max_label_ws, stream, who)) return rc;
             ml_dev = max_label_ws;
         }
-        int rc;
-        if (L <= 512) {
-            auto go = [&](auto kern, int dpt) -> int {
-                constexpr int QPB = kBlock / kWave;
-                return launch_queries(kern, B, QPB, kBlock, (size_t)QPB * 128 * dpt * sizeof(float), stream, who, preds, labels, lens, B, L, metric,
-                                      opt_ideal, top_k, alpha, max_label, ml_dev, loss_q, valid_q, ranks, grad);
-            };
-            rc = L <= 64 ? go(smooth_ring_kernel<1>, 1) : L <= 128 ? go(smooth_ring_kernel<2>, 2) : L <= 192 ? go(smooth_ring_kernel<3>, 3)
-               : L <= 256 ? go(smooth_ring_kernel<4>, 4) : L <= 384 ? go(smooth_ring_kernel<6>, 6) : go(smooth_ring_kernel<8>, 8);
-        } else {
-            auto go = [&](auto kern, int dpt) -> int {
-                return launch_queries(kern, B, 1, kBlock, smooth_lds_floats(kBlock * dpt) * sizeof(float), stream, who, preds, labels, lens, B, L, metric,
-                                      opt_ideal, top_k, alpha, max_label, ml_dev, loss_q, valid_q, ranks, grad);
-            };
-            rc = L <= 1024 ? go(smooth_lds_kernel<4>, 4) : L <= 2048 ? go(smooth_lds_kernel<8>, 8) : go(smooth_lds_kernel<16>, 16);
-        }
+        const RingForm f = ring_form(L);
+        auto go = [&](auto kern, int QPB, size_t lds_floats) -> int {
+            return launch_queries(kern, B, QPB, kBlock, lds_floats * sizeof(float), stream, who, preds, labels, lens, B, L, metric, opt_ideal, top_k,
+                                  alpha, max_label, ml_dev, loss_q, valid_q, ranks, grad);
+        };
+        auto walk = [&]<int DPT>() { return go(smooth_lds_kernel<DPT>, 1, smooth_lds_floats(kBlock * DPT)); };
+        const int rc = f.ring     ? dispatch_ring_dpt(f.DPT, [&]<int DPT>() { return go(smooth_ring_kernel<DPT>, kBlock / kWave, (size_t)kBlock / kWave * 128 * DPT); })
+                     : f.DPT == 4 ? walk.template operator()<4>()
+                     : f.DPT == 8 ? walk.template operator()<8>()
+                                  : walk.template operator()<16>();
         if (rc) return rc;
     }
     return finish_loss(loss_q, B, 1.0f, loss_out, stream);

@@ -227,6 +227,14 @@ template <int G, int DPT, class F> int dispatch_cost(int cost_type, F &&f) {
 
 }  // namespace
 
+// One workgroup of G threads per query, each thread DPT columns of a column tile.
+Tiling wassrank_form(int L) {
+    if (L <= 64) return {64, 1};
+    if (L <= 128) return {64, 2};
+    if (L <= 256) return {128, 2};
+    return {256, 2};
+}
+
 }  // namespace ptr
 
 extern "C" int ptr_wassrank_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, int cost_type,
@@ -249,10 +257,11 @@ extern "C" int ptr_wassrank_fwd_bwd(const float *preds, const float *labels, con
             return launch_queries(kern, B, 1, G, lds, stream, who, preds, labels, lens, L, Lp, gain_base, non_rele_gap, var_penalty, lam, sh_itr,
                                   scale_by_max_label, inv_b, loss_q, grad);
         };
+        const Tiling f = wassrank_form(L);
         int rc;
-        if (L <= 64) rc = dispatch_cost<64, 1>(cost_type, [&](auto k) { return launch.template operator()<64>(k); });
-        else if (L <= 128) rc = dispatch_cost<64, 2>(cost_type, [&](auto k) { return launch.template operator()<64>(k); });
-        else if (L <= 256) rc = dispatch_cost<128, 2>(cost_type, [&](auto k) { return launch.template operator()<128>(k); });
+        if (f.DPT == 1) rc = dispatch_cost<64, 1>(cost_type, [&](auto k) { return launch.template operator()<64>(k); });
+        else if (f.G == 64) rc = dispatch_cost<64, 2>(cost_type, [&](auto k) { return launch.template operator()<64>(k); });
+        else if (f.G == 128) rc = dispatch_cost<128, 2>(cost_type, [&](auto k) { return launch.template operator()<128>(k); });
         else rc = dispatch_cost<256, 2>(cost_type, [&](auto k) { return launch.template operator()<256>(k); });
         if (rc) return rc;
     }

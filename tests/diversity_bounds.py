@@ -87,25 +87,9 @@ LN2 = math.log(2.0)
 TINY = 2.0 ** -126
 
 
-# ---------------------------------------------------------------------------------------------------------------------------- dispatch mirrors
-def tp_of(T):
-    """csrc/ptr_div.h tp_of."""
-    return 4 if T <= 4 else 8 if T <= 8 else 16 if T <= 16 else 32
-
-
-def loss_form(T, L):
-    """(G, TP) of alphadcg_kernel as ptr_alphadcg_fwd_bwd dispatches it."""
-    return (64 if L <= 128 else 256, tp_of(T))
-
-
-def metric_form(L):
-    """(G, DPT) of div_metrics_kernel: csrc/ptr_device.h pick_tiling."""
-    for top, form in ((64, (64, 1)), (128, (64, 2)), (256, (256, 1)), (512, (256, 2)), (1024, (256, 4)), (2048, (256, 8))):
-        if L <= top:
-            return form
-    return (256, 16)
-
-
+# ---------------------------------------------------------------------------------------------------------------------------- kernel forms
+# (G, TP) of alphadcg_kernel by (T, L) and (G, DPT) of div_metrics_kernel by L, as the case lists want them: tests/test_diversity_bounds_cpu.py
+# asks the library (tests/launch_form.py) whether its launchers agree
 LOSS_FORMS = {(3, 40): (64, 4), (7, 100): (64, 8), (12, 128): (64, 16), (30, 64): (64, 32), (4, 129): (256, 4), (8, 200): (256, 8),
               (16, 260): (256, 16), (32, 300): (256, 32)}
 LOSS_LIMIT_FORMS = {(8, 2272): (256, 8), (3, 4092): (256, 4)}              # on the documented LDS limits, B = 1

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from launch_form import launch_form, ring_or_tiling
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "ptranking_amd.h")
 
@@ -78,6 +80,17 @@ def test_argument_errors_need_no_gpu(lib_path):
     assert rc == 1002 and b"nERR" in lib.ptr_last_error()          # nERR is undefined for LABEL_TYPE.Permutation
     rc = lib.ptr_metrics_at_ks(one, one, None, 1, 8, ks, 3, 1, 7, ctypes.c_float(4.0), None, one, None, None, None, None)
     assert rc == 1001 and b"label_type" in lib.ptr_last_error()
+
+
+def test_launch_form_answers_without_a_gpu_and_refuses_what_it_does_not_know():
+    from ptranking_amd import _lib
+    lib = _lib.load()
+    assert launch_form("ptr_wassrank_fwd_bwd", 200)[:3] == (128, 2, 0)
+    args, out = (ctypes.c_int64 * 2)(200, 0), (ctypes.c_int32 * 8)()
+    assert lib.ptr_launch_form(b"ptr_sort_desc", args, 1, out, 8) == 1001 and b"ptr_sort_desc" in lib.ptr_last_error()
+    assert lib.ptr_launch_form(b"ptr_wassrank_fwd_bwd", args, 2, out, 8) == 1001 and b"takes 1" in lib.ptr_last_error()
+    assert lib.ptr_launch_form(b"ptr_wassrank_fwd_bwd", args, 1, out, 1) == 1001
+    assert lib.ptr_launch_form(None, args, 1, out, 8) == 1001 and lib.ptr_launch_form(b"ptr_wassrank_fwd_bwd", args, 1, None, 8) == 1001
 
 
 def test_x6_entry_point_validates_without_a_gpu():
@@ -221,40 +234,27 @@ def test_bf16x6_split_and_wave_primitives_have_one_home():
         assert found[pat] == {owner}, f"{pat} belongs in csrc/{owner} alone, found in {sorted(found[pat])}"
 
 
-def _listsf_dispatch():
-    """The dispatch rules of csrc/listsf.hip, restated: attention D = ceil(dh / 16) (dispatch_dt), two row tiles per forward wave iff
-    D <= 5 and L > 64, the 8-wave dK / dV kernel iff D >= 7 and L > 64, STORE_DS iff a dS scratch is passed, vector loads iff dh and the
-    row stride are multiples of 4 floats; LayerNorm NI = ceil(F / 64) (1..4, else the generic 0), forward grid <= 8192 blocks of 4 rows,
-    backward <= 1024 (kLnBlocks).  Each rule's constant must still be in the source."""
-    src = open(os.path.join(ROOT, "ptranking_amd", "csrc", "listsf.hip")).read()
-    for needle in ("const int DT = (a.dh + 15) / 16;", "if constexpr (D <= 5) {\n            if (L > 64) return launch.template operator()<2, 4>();",
-                   "if constexpr (D >= 7) {\n                if (L > 64) return launch_dkv.template operator()<8>();",
-                   "return ds_ws ? go(mhsa_bwd_dkv_kernel<D, NW, true>) : go(mhsa_bwd_dkv_kernel<D, NW, false>);",
-                   "const bool vec = ((dh & 3) == 0)", "default: return f.template operator()<8>();",
-                   "const int ni = (F + 63) / 64;", "if (ni == 1) launch.template operator()<1>(); else if (ni == 2) launch.template operator()<2>();",
-                   "else if (ni == 3) launch.template operator()<3>(); else if (ni == 4) launch.template operator()<4>();",
-                   "(R + 3) / 4 < 8192 ? (R + 3) / 4 : 8192", "constexpr int kLnBlocks = 1024;", "(R + 3) / 4 < kLnBlocks ? (R + 3) / 4 : kLnBlocks",
-                   "r += (size_t)gridDim.x * 4"):
-        assert needle in src, f"csrc/listsf.hip no longer contains {needle!r}: restate the dispatch rules here"
+def _attn_form(Bn, L, F, H, mode, ds, packed):
+    """The forms ptr_mhsa_forward / ptr_mhsa_backward launch for a case of 16-byte aligned arrays: D column tiles, row tiles per forward wave,
+    waves and stored dS of the dK / dV kernel, float4 accesses or scalar ones."""
+    dh = F // H
+    wide, D, row_tiles, dkv_waves, store_ds, access = launch_form("ptr_mhsa_backward", L, dh, 3 * F if packed else F, ds, 16)[:6]
+    assert not wide and launch_form("ptr_mhsa_forward", L, dh, 3 * F if packed else F, ds, 16)[:6] == (wide, D, row_tiles, dkv_waves, store_ds, access)
+    return dict(fwd=(D, row_tiles), dkv=(D, dkv_waves, bool(store_ds)), vec=access == 4, L=L, dh=dh, mode=mode, packed=packed)
 
-    def attn(Bn, L, F, H, mode, ds, packed):
-        dh = F // H
-        D = -(-dh // 16)
-        ld = 3 * F if packed else F
-        return dict(fwd=(D, 2 if D <= 5 and L > 64 else 1), dkv=(D, 8 if D >= 7 and L > 64 else 4, ds),
-                    vec=(dh % 4 == 0 and ld % 4 == 0), L=L, dh=dh, mode=mode, packed=packed)
 
-    def ln(R, F):
-        ni = -(-F // 64)
-        return dict(ni=ni if ni <= 4 else 0, fwd_trips=-(-R // (4 * min(-(-R // 4), 8192))), bwd_trips=-(-R // (4 * min(-(-R // 4), 1024))))
-    return attn, ln
+def _ln_form(R, F):
+    """NI of the LayerNorm kernels and the trips of their row loops: four rows per workgroup and trip, one per wave."""
+    ni, fwd_blocks, bwd_blocks = launch_form("ptr_layernorm_forward", R, F)[:3]
+    assert launch_form("ptr_layernorm_backward", R, F)[:3] == (ni, fwd_blocks, bwd_blocks)
+    return dict(ni=ni, fwd_trips=-(-R // (4 * fwd_blocks)), bwd_trips=-(-R // (4 * bwd_blocks)))
 
 
 def test_listsf_bound_cases_hit_every_dispatch_form():
     """tests/test_listsf_bounds_gpu.py's case lists launch every attention and LayerNorm kernel form at least once."""
     import importlib
     G = importlib.import_module("test_listsf_bounds_gpu")
-    attn, ln = _listsf_dispatch()
+    attn, ln = _attn_form, _ln_form
     forms = [attn(*c) for c in G.ATTN_CASES]
     want_fwd = {(D, rt) for D in range(1, 9) for rt in ((1, 2) if D <= 5 else (1,))}
     # the product passes the dS scratch from 128 keys on (listsf.py _ds_scratch), where D >= 7 takes the 8-wave dK / dV kernel
@@ -276,56 +276,31 @@ def test_listsf_bound_cases_hit_every_dispatch_form():
     assert (262144, 136) in G.LN_CASES and 1 in {R for _, R, _ in lns}
 
 
-def _loss_dispatch():
-    """The dispatch rules of the ranking-loss entry points (pairwise.hip launch_pairwise, approxndcg.hip ptr_approxndcg_fwd_bwd,
-    listwise.hip launch_listnet_vec / launch_listmle_vec, ptr_device.h pick_tiling), restated.  The constants are checked against the source."""
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ptranking_amd", "csrc")
-    src = {f: open(os.path.join(csrc, f)).read() for f in ("pairwise.hip", "approxndcg.hip", "listwise.hip", "ptr_device.h", "ptr_ring.h")}
-    for f, needle in [("pairwise.hip", "L <= 512 && sigma > 0.0f && env_int(\"PTR_LAMBDARANK_RING\", 1)"),
-                      ("pairwise.hip", "const int dpt = L <= 64 ? 1 : L <= 128 ? 2 : L <= 256 ? 4 : 8;"),
-                      ("pairwise.hip", "while (QPB > 1 && B < QPB * num_cus()) QPB >>= 1;"),
-                      ("pairwise.hip", "if (dpt >= 4 && QPB > kRing4Waves) QPB = kRing4Waves;"),
-                      ("pairwise.hip", "if (dpt >= 8 && QPB > 4) QPB = 4;"), ("ptr_ring.h", "constexpr int kRing4Waves = 8;"),
-                      ("ptr_ring.h", "const bool ok = open && (empty || (pure && (!have || first == zlab)));"),
-                      ("ptr_ring.h", "constexpr int kRingBlock = 1024;"), ("pairwise.hip", "!WEIGHTED && B > 0 && L <= 32"),
-                      ("approxndcg.hip", "L <= 512 && env_int(\"PTR_APPROX_RING\", 1)"),
-                      ("approxndcg.hip", "L <= 64 ? go(approxndcg_ring_kernel<1>, 1) : L <= 128 ? go(approxndcg_ring_kernel<2>, 2)"),
-                      ("approxndcg.hip", ": L <= 192 ? go(approxndcg_ring_kernel<3>, 3) : L <= 256 ? go(approxndcg_ring_kernel<4>, 4)"),
-                      ("approxndcg.hip", ": L <= 384 ? go(approxndcg_ring_kernel<6>, 6) : go(approxndcg_ring_kernel<8>, 8);"),
-                      ("listwise.hip", "if (L % 4 != 0 || L > 1024) return 0;"),
-                      ("ptr_device.h", "if (L <= 64) return {64, 1};"), ("ptr_device.h", "if (L <= 2048) return {256, 8};")]:
-        assert needle in src[f], f"{f} no longer holds `{needle}`: restate the dispatch rules here"
+def _lambdarank_form(B, L, sigma, ring, monkeypatch):
+    """("ring", DPT, "full" or "shrunk": its workgroup against the one a batch that fills the device gets) or ("lds", G, DPT)."""
+    monkeypatch.setenv("PTR_LAMBDARANK_RING", str(ring))
+    kind, G, DPT, QPB = launch_form("ptr_lambdarank_fwd_bwd", B, L, sigma > 0)[:4]
+    if kind != 1:
+        assert kind == 0
+        return ("lds", G, DPT)
+    return ("ring", DPT, "full" if QPB == launch_form("ptr_lambdarank_fwd_bwd", 2 ** 30, L, 1)[3] else "shrunk")
 
-    def tiling(L):
-        return (64, 1) if L <= 64 else (64, 2) if L <= 128 else (256, 1) if L <= 256 else (256, 2) if L <= 512 else \
-            (256, 4) if L <= 1024 else (256, 8) if L <= 2048 else (256, 16)
 
-    def lambdarank(B, L, sigma, ring):
-        if L <= 512 and sigma > 0 and ring:
-            dpt = 1 if L <= 64 else 2 if L <= 128 else 4 if L <= 256 else 8
-            qpb = 16
-            while qpb > 1 and B < qpb * 256:
-                qpb >>= 1
-            qpb = min(qpb, 8) if dpt >= 4 else qpb
-            qpb = min(qpb, 4) if dpt >= 8 else qpb
-            cap = 16 if dpt < 4 else 8 if dpt < 8 else 4
-            return ("ring", dpt, "full" if qpb == cap else "shrunk")
-        return ("lds",) + tiling(L)
+def _ranknet_form(L):
+    kind, G, DPT, _ = launch_form("ptr_ranknet_fwd_bwd", 1, L)[:4]
+    return ("half-wave",) if kind == 2 else ("lds", G, DPT)
 
-    def ranknet(L):
-        return ("half-wave",) if L <= 32 else ("lds",) + tiling(L)
 
-    def approx(L, ring):
-        if L <= 512 and ring:
-            return ("ring", 1 if L <= 64 else 2 if L <= 128 else 3 if L <= 192 else 4 if L <= 256 else 6 if L <= 384 else 8)
-        return ("lds",) + tiling(L)
+def _approx_form(L, ring, monkeypatch):
+    monkeypatch.setenv("PTR_APPROX_RING", str(ring))
+    return ring_or_tiling("ptr_approxndcg_fwd_bwd", L)
 
-    def listwise(L, unaligned):
-        if L % 4 or L > 1024 or unaligned:
-            return ("lds",)
-        return ("vec", 1 if L <= 256 else 2 if L <= 512 else 4, 16 if L <= 64 else 32 if L <= 128 else 64)
 
-    return lambdarank, ranknet, approx, listwise
+def _listwise_form(L, unaligned):
+    """("vec", V, G) of ListNet's register kernel or ("lds",); ListMLE takes its register kernel for the same calls, with the same V."""
+    vec, G, V = launch_form("ptr_listnet_fwd_bwd", L, not unaligned)[:3]
+    assert launch_form("ptr_listmle_fwd_bwd", L, not unaligned)[:3] == (vec, 64, V)
+    return ("vec", V, G) if vec else ("lds",)
 
 
 def _ring_z(labels, n, dpt):
@@ -344,12 +319,13 @@ def _ring_z(labels, n, dpt):
     return z
 
 
-def test_loss_bound_cases_hit_every_dispatch_form():
+def test_loss_bound_cases_hit_every_dispatch_form(monkeypatch):
     """tests/test_loss_bounds_gpu.py's case lists launch every form of the LambdaRank, RankNet, ApproxNDCG, ListNet, ListMLE, LambdaLoss
     and SoftRank kernels."""
     import importlib
     G = importlib.import_module("test_loss_bounds_gpu")
-    lambdarank, ranknet, approx, listwise = _loss_dispatch()
+    lambdarank = lambda B, L, s, r: _lambdarank_form(B, L, s, r, monkeypatch)
+    ranknet, approx, listwise = _ranknet_form, lambda L, r: _approx_form(L, r, monkeypatch), _listwise_form
     tilings = {(64, 1), (64, 2), (256, 1), (256, 2), (256, 4), (256, 8), (256, 16)}
     lr = {lambdarank(B, L, s, r) for B, L, s, _, _, _, r, _ in G.LAMBDARANK_CASES}
     # every ring form, its workgroup shrunk (B < waves x CUs) and full
@@ -392,13 +368,9 @@ def test_loss_bound_cases_hit_every_dispatch_form():
 
 
 def _lambdaloss_route(L, k, loss_type, presort, unaligned):
-    """ptr_lambdaloss_fwd_bwd (csrc/lambdaloss.hip): the top-k kernel for a small cut-off on presorted, 16-byte aligned rows of a
-    multiple of four documents, lambdaloss_kernel on dispatch_wave256_tiling otherwise."""
-    if presort and k <= 11 and loss_type != 0 and L % 4 == 0 and L <= 1024 and not unaligned:
-        return ("topk", 1 if L <= 256 else 2 if L <= 512 else 4)
-    if L <= 256:
-        return ("generic", 64, 1 if L <= 64 else 2 if L <= 128 else 4)
-    return ("generic", 256, 2 if L <= 512 else 4 if L <= 1024 else 8 if L <= 2048 else 16)
+    """("topk", V) or ("generic", G, DPT) of ptr_lambdaloss_fwd_bwd."""
+    topk, G, V = launch_form("ptr_lambdaloss_fwd_bwd", L, k, loss_type, presort, not unaligned)[:3]
+    return ("topk", V) if topk else ("generic", G, V)
 
 
 def _topk_libm_queries(case, p, y, n):
@@ -464,9 +436,8 @@ def _check_lambdaloss_softrank_stlistnet_cases():
     assert Bp >= 3 * 256 * 4 * 8 and Bp % 4
     _, _, n, order = G.lambdaloss_persistent_inputs()
     assert set(n.tolist()) == set(range(9)) and len(set(order.tolist())) == 256 and (np.diff(np.minimum(n, 5)) != 0).mean() > 0.5
-    lambdarank, ranknet, approx, listwise = _loss_dispatch()
     tilings = {(64, 1), (64, 2), (256, 1), (256, 2), (256, 4), (256, 8), (256, 16)}
-    assert {approx(L, 0)[1:] for _, L, *_ in G.SOFTRANK_CASES} == tilings
+    assert {ring_or_tiling("ptr_softrank_fwd_bwd", L)[1:] for _, L, *_ in G.SOFTRANK_CASES} == tilings
     assert {d for _, _, d, _, _ in G.SOFTRANK_CASES} == {2.0, 0.3} and any(o for *_, o in G.SOFTRANK_CASES)
     assert {("none" if k == 0 else "> n" if k > L else "cut") for _, L, _, k, _ in G.SOFTRANK_CASES} == {"none", "> n", "cut"}
     assert {L for _, L, *_ in G.STLISTNET_CASES} == {64, 63, 128, 1500} and {T for _, _, T, _, _ in G.STLISTNET_CASES} == {1.0, 2.0, 0.5}

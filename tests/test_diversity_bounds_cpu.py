@@ -9,8 +9,6 @@
   * the case lists reach every (G, TP) of the loss kernel and every (G, DPT) of the metric kernel at its smallest and largest length.
 """
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -18,9 +16,9 @@ import pytest
 import diversity_bounds as DB
 import diversity_ref as DR
 import golden_util as GU
+from launch_form import group_form
 
 C = DB.C_DIV
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def ratio(got, ref, E):
@@ -373,31 +371,27 @@ def test_fault_nan_ranking_of_the_parent_commit():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 5. coverage of the case lists
-def _src(name):
-    return open(os.path.join(ROOT, "ptranking_amd", "csrc", name)).read()
+def loss_form(T, L):
+    return group_form("ptr_alphadcg_fwd_bwd", T, L)
 
 
-def test_dispatch_mirrors_follow_the_sources():
-    m = re.search(r"inline int tp_of\(int T\) \{ return T <= 4 \? 4 : T <= 8 \? 8 : T <= 16 \? 16 : 32; \}", _src("ptr_div.h"))
-    assert m and [DB.tp_of(T) for T in (1, 4, 5, 8, 9, 16, 17, 32)] == [4, 4, 8, 8, 16, 16, 32, 32]
-    assert "const int QPB = L <= 128 ? kBlock / kWave : 1;" in _src("diversity.hip")
-    body = re.search(r"inline Tiling pick_tiling\(int L\) \{(.*?)\n\}", _src("ptr_device.h"), re.S).group(1)
-    steps = [(int(a), (int(g), int(d))) for a, g, d in re.findall(r"if \(L <= (\d+)\) return \{(\d+), (\d+)\};", body)]
-    last = tuple(int(v) for v in re.search(r"\n\s*return \{(\d+), (\d+)\};", body).groups())
-    for L in (1, 64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025, 2048, 2049, 4096):
-        want = next((f for top, f in steps if L <= top), last)
-        assert DB.metric_form(L) == want, L
+def metric_form(L):
+    return group_form("ptr_div_metrics_at_ks", L)
+
+
+def test_the_library_serves_the_forms_the_case_lists_name():
+    assert [loss_form(T, 40)[1] for T in (1, 4, 5, 8, 9, 16, 17, 32)] == [4, 4, 8, 8, 16, 16, 32, 32]
     for form, (lo, hi) in DB.METRIC_FORM_L.items():
-        assert DB.metric_form(lo) == DB.metric_form(hi) == form and (lo == 1 or DB.metric_form(lo - 1) != form)
-        assert hi == 4096 or DB.metric_form(hi + 1) != form
+        assert metric_form(lo) == metric_form(hi) == form and (lo == 1 or metric_form(lo - 1) != form)
+        assert hi == 4096 or metric_form(hi + 1) != form
 
 
 def test_coverage_of_the_case_lists():
     loss = DB.loss_cases()
-    forms = {DB.loss_form(c["rele"].shape[1], c["rele"].shape[2]) for c in loss}
+    forms = {loss_form(c["rele"].shape[1], c["rele"].shape[2]) for c in loss}
     assert forms == {(G, TP) for G in (64, 256) for TP in (4, 8, 16, 32)}
     for (T, L), form in {**DB.LOSS_FORMS, **DB.LOSS_LIMIT_FORMS}.items():
-        assert DB.loss_form(T, L) == form and any(c["rele"].shape[1:] == (T, L) for c in loss)
+        assert loss_form(T, L) == form and any(c["rele"].shape[1:] == (T, L) for c in loss)
     small = [c for c in loss if c["rele"].shape[2] <= 128 and c["name"].startswith("form_")]
     assert {c["preds"].shape[0] for c in small} == {1, 4, 5, 9}
     lens = {int(v) - c["preds"].shape[1] if v > 2 else int(v) for c in loss for v in c["lens"]}
@@ -411,7 +405,7 @@ def test_coverage_of_the_case_lists():
     deep = [c for c in loss if c["name"].startswith("deep")]
     assert deep and all(c["alpha"] == 0.9 and ((c["rele"][0] > 0).sum(1) >= 40).all() for c in deep)
     met = DB.metric_cases()
-    seen = {(DB.metric_form(c["preds"].shape[1]), c["preds"].shape[1]) for c in met}
+    seen = {(metric_form(c["preds"].shape[1]), c["preds"].shape[1]) for c in met}
     for form, (lo, hi) in DB.METRIC_FORM_L.items():
         assert (form, lo) in seen and (form, hi) in seen
     assert {c["rele"].shape[1] for c in met} == {1, 5, 32} and {c["max_label"] for c in met} == {1.0, 3.0, None}

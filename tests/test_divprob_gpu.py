@@ -24,12 +24,12 @@ import torch.multiprocessing as mp
 
 import divprob_ref as DR
 import golden_util as GU
+from launch_form import group_form
 
 pytestmark = pytest.mark.gpu
 
 GOLD = GU._load("divprob.npz")
 NAMES = {0: "aNDCG", 1: "nERR-IA", 2: "PairCLS", 3: "LambdaPairCLS"}
-TILES = {0: 2, 1: 1, 2: 1, 3: 3}
 
 
 def rows(fams, objectives):
@@ -116,13 +116,6 @@ def _batch(rng, B, T, L, density=0.15, graded=False, ragged=True, var=(0.05, 1.0
     return mus, vars_, rele, lens, nts
 
 
-def form_of(obj, T, L):
-    """(G, TP) the entry point dispatches to (csrc/divprob.hip)"""
-    TP = 4 if T <= 4 else 8 if T <= 8 else 16 if T <= 16 else 32
-    per_query = 4 * ((L + 3) // 4 * 4) * (3 + TILES[obj] * TP) + 16
-    return (64 if L <= 128 and 4 * per_query <= 160 * 1024 else 256), TP
-
-
 # objective -> (T, L) cases: every (G, TP) of every objective; LambdaPairCLS at T = 32, L = 128 is the list of <= 128 documents whose four
 # tiles do not fit, served by G = 256
 FORMS = [(obj, T, L) for obj in range(4) for T, L in ((3, 40), (7, 100), (12, 128), (30, 64), (4, 200), (8, 300), (16, 260), (32, 140))]
@@ -130,8 +123,9 @@ FORMS += [(3, 32, 128)]
 
 
 def test_forms_cover_every_instantiation():
-    assert {(obj,) + form_of(obj, T, L) for obj, T, L in FORMS} == {(obj, G, TP) for obj in range(4) for G in (64, 256) for TP in (4, 8, 16, 32)}
-    assert form_of(3, 32, 128) == (256, 32) and form_of(3, 30, 64) == (64, 32)
+    form = lambda obj, T, L: group_form("ptr_divprob_fwd_bwd", obj, T, L)           # (G, TP) the entry point launches
+    assert {(obj,) + form(obj, T, L) for obj, T, L in FORMS} == {(obj, G, TP) for obj in range(4) for G in (64, 256) for TP in (4, 8, 16, 32)}
+    assert form(3, 32, 128) == (256, 32) and form(3, 30, 64) == (64, 32)
 
 
 def _check_forms_case(obj, T, L, B, axis, seed, density=0.15):

@@ -1,5 +1,5 @@
 """CPU: the public surface of the wide-head attention forms (heads of 129 .. PTR_MHSA_MAX_HEAD_DIM floats, csrc/listsf_wide.hip): argument
-checks of the C ABI before any launch, the module's limit, the dispatch rules restated against tests/test_listsf_wide_gpu.py's case
+checks of the C ABI before any launch, the module's limit, the forms the library launches for tests/test_listsf_wide_gpu.py's case
 list, and the reference-generated fixture (tests/golden/make_golden_listsf_wide.py) against the oracle's restatement."""
 import ctypes
 import importlib
@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import golden_util as G
+from launch_form import launch_form
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "ptranking_amd.h")
@@ -81,42 +82,22 @@ def test_module_accepts_heads_up_to_the_limit():
         LS.MultiheadAttention(700, 1)                                  # Yahoo! with ONE head stays out of reach
 
 
-def _wide_dispatch():
-    """The dispatch rules of the wide forms, restated: taken for dh > 128 ahead of the narrow dispatch; DT = 2 ceil(dh / 32) column tiles
-    (10 .. 22); backward = dK / dV storing dS + dQ from it when a dS scratch is passed, else recomputing dQ + dK / dV; global accesses of
-    4 floats when dh and the row stride are multiples of 4, of 2 when they are even, else scalar.  Each rule's text must still be in the
-    source."""
-    src = {f: open(os.path.join(CSRC, f)).read() for f in ("listsf.hip", "listsf_wide.hip", "ptr_attn.h")}
-    for f, needle in [("ptr_attn.h", "constexpr int kAttnNarrowMaxHeadDim = 128;"),
-                      ("listsf.hip", "if (a.dh > kAttnNarrowMaxHeadDim) return mhsa_wide_forward(Q, K, V, lens, a, O, lse, st, who);"),
-                      ("listsf.hip", "if (a.dh > kAttnNarrowMaxHeadDim) return mhsa_wide_backward(Q, K, V, dO, lse, dvec, lens, a, dQ, dK, dV, ds_ws, st, who);\n"
-                                     "    const int DT = (a.dh + 15) / 16;"),
-                      ("listsf_wide.hip", "switch ((dh + 31) / 32) {"), ("listsf_wide.hip", "case 5: return f.template operator()<10>();"),
-                      ("listsf_wide.hip", "case 10: return f.template operator()<20>();"),
-                      ("listsf_wide.hip", "default: return f.template operator()<kWideMaxDT>();"), ("listsf_wide.hip", "constexpr int kWideMaxDT = 22;"),
-                      ("listsf_wide.hip", "static_assert(PTR_MHSA_MAX_HEAD_DIM == 16 * kWideMaxDT"),
-                      ("listsf_wide.hip", "if (ds_ws) {"), ("listsf_wide.hip", "dkv(mhsa_wide_bwd_dkv_kernel<D, true>)"),
-                      ("listsf_wide.hip", "wide_launch(mhsa_wide_bwd_dq_ds_kernel<D>"), ("listsf_wide.hip", "wide_launch(mhsa_wide_bwd_dq_kernel<D>"),
-                      ("listsf_wide.hip", "return dkv(mhsa_wide_bwd_dkv_kernel<D, false>);"),
-                      ("listsf_wide.hip", "if (((dh | stride) & 3) == 0 && (a & 15) == 0) return 4;"),
-                      ("listsf_wide.hip", "if (((dh | stride) & 1) == 0 && (a & 7) == 0) return 2;"), ("listsf_wide.hip", "constexpr int kWideChunk = 16;")]:
-        assert needle in src[f], f"csrc/{f} no longer contains {needle!r}: restate the wide dispatch rules here"
-
-    def form(Bn, L, F, H, mode, ds, packed):
-        dh = F // H
-        assert 128 < dh <= _limit()
-        ld = 3 * F if packed else F
-        return dict(DT=2 * -(-dh // 32), ds=ds, access=4 if (dh | ld) % 4 == 0 else 2 if (dh | ld) % 2 == 0 else 1, L=L, dh=dh, mode=mode, packed=packed,
-                    chunks=-(-L // 16), blocks=-(-L // 64))
-    return form
+def _wide_form(Bn, L, F, H, mode, ds, packed):
+    """The wide form ptr_mhsa_forward / ptr_mhsa_backward launch for a case of 16-byte aligned arrays: DT column tiles (10 .. 22), the
+    stored-dS backward or the recomputing one, floats per global access; the chunks of 16 streamed rows and the blocks of 64 rows of L."""
+    dh = F // H
+    assert 128 < dh <= _limit()
+    ld = 3 * F if packed else F
+    wide, DT, _, _, store_ds, access = launch_form("ptr_mhsa_backward", L, dh, ld, ds, 16)[:6]
+    assert wide and launch_form("ptr_mhsa_forward", L, dh, ld, ds, 16)[:2] == (wide, DT)
+    return dict(DT=DT, ds=bool(store_ds), access=access, L=L, dh=dh, mode=mode, packed=packed, chunks=-(-L // 16), blocks=-(-L // 64))
 
 
 def test_wide_bound_cases_hit_every_dispatch_form():
     """tests/test_listsf_wide_gpu.py's case list launches every wide kernel form: each DT with the recomputing backward (dQ, dK / dV) and
     with the stored-dS backward (dK / dV storing dS, dQ from dS), 16-, 8- and 4-byte accesses, packed and separate, every mode."""
     Gm = importlib.import_module("test_listsf_wide_gpu")
-    form = _wide_dispatch()
-    forms = [form(*c) for c in Gm.WIDE_CASES]
+    forms = [_wide_form(*c) for c in Gm.WIDE_CASES]
     assert {(f["DT"], f["ds"]) for f in forms} == {(dt, ds) for dt in range(10, 23, 2) for ds in (False, True)}
     assert all(f["L"] >= 128 for f in forms if f["ds"])               # the product passes the dS scratch from 128 keys on (listsf.py _ds_scratch)
     assert {f["access"] for f in forms} == {4, 2, 1}

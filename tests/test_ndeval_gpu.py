@@ -2,7 +2,7 @@
 (tests/golden/ndeval.npz), every output element against the float64 restatement tests/ndeval_ref.py (expected difference 0: the same IEEE
 operations in the same order), the greedy ideal ranking exactly, bit identity, and the Python surface.
 
-Dispatch forms (pick_tiling): (G, DPT) = (64, 1) L <= 64, (64, 2) L <= 128 — one wavefront per query, four queries per workgroup —
+Dispatch forms: (G, DPT) = (64, 1) L <= 64, (64, 2) L <= 128 — one wavefront per query, four queries per workgroup —
 and (256, 1) (256, 2) (256, 4) (256, 8) (256, 16) — one workgroup per query, up to PTR_MAX_LIST_LEN = 4096, which is also the LDS limit.
 
 The gate against the restatement is 2^-50 max(1, |ref|): a few ulp of headroom for a host log() that may differ between machines (the 20

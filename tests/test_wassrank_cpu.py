@@ -19,6 +19,7 @@ import golden_util as G
 import wassrank_bounds as WB
 import wassrank_ref as W
 from f64_loss_bounds import gate_losses
+from launch_form import group_form
 
 REF = os.environ.get("PTRANKING_REF") or "/root/reference"
 NEEDS_REF = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "ptranking")),
@@ -401,29 +402,26 @@ def test_gate_inputs_screen_the_eg_discontinuities():
 
 
 def test_the_gate_cases_reach_every_form_of_the_kernel():
-    """The dispatch rule of ptr_wassrank_fwd_bwd restated: 64 threads x 1 column up to 64 documents of padded width, 64 x 2 up to 128,
+    """The forms of ptr_wassrank_fwd_bwd, asked of the library: 64 threads x 1 column up to 64 documents of padded width, 64 x 2 up to 128,
     128 x 2 up to 256, 256 x 2 beyond; five costs each.  The ragged batches reach all 20 with scaling off and on, list lengths 0, 1, 2 and
     a ragged width in each; the widest form runs one, two and three column tiles, with one, two and four waves alive in the last."""
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ptranking_amd", "csrc", "wassrank.hip")).read()
-    for rule in ("if (L <= 64) rc = dispatch_cost<64, 1>", "else if (L <= 128) rc = dispatch_cost<64, 2>", "else if (L <= 256) rc = dispatch_cost<128, 2>",
-                 "else rc = dispatch_cost<256, 2>"):
-        assert rule in src, rule
-    assert [WB.tiling(L) for L in (1, 64, 65, 128, 129, 256, 257, 4096)] == [(64, 1)] * 2 + [(64, 2)] * 2 + [(128, 2)] * 2 + [(256, 2)] * 2
+    form = lambda L: group_form("ptr_wassrank_fwd_bwd", L)
+    assert [form(L) for L in (1, 64, 65, 128, 129, 256, 257, 4096)] == [(64, 1)] * 2 + [(64, 2)] * 2 + [(128, 2)] * 2 + [(256, 2)] * 2
     forms = {(64, 1), (64, 2), (128, 2), (256, 2)}
     for scale in (False, True):
-        seen = {(c["kw"]["cost_type"], WB.tiling(c["L"])) for c in WB.RAGGED_CASES if c["kw"]["scale_by_max_label"] is scale}
+        seen = {(c["kw"]["cost_type"], form(c["L"])) for c in WB.RAGGED_CASES if c["kw"]["scale_by_max_label"] is scale}
         assert seen == {(cost, f) for cost in W.COST_TYPES for f in forms}
     for c in WB.RAGGED_CASES:
         assert {0, 1, 2} <= set(c["lens"]) and max(c["lens"]) == c["L"]
     assert any(c["L"] % 4 for c in WB.RAGGED_CASES)
     for cost in W.COST_TYPES:
-        wide = [c for c in WB.RAGGED_CASES if c["kw"]["cost_type"] == cost and WB.tiling(c["L"]) == (256, 2)]
-        tiles = {WB.column_tiles(n, c["L"]) for c in wide for n in c["lens"] if n > 1}
+        wide = [c for c in WB.RAGGED_CASES if c["kw"]["cost_type"] == cost and form(c["L"]) == (256, 2)]
+        tiles = {-(-n // 512) for c in wide for n in c["lens"] if n > 1}      # trips of the column-tile loop: 256 x 2 columns a tile
         assert tiles == {1, 2, 3}, (cost, tiles)
-        last = {(WB.column_tiles(n, c["L"]), -(-min((n - 1) % 512 + 1, 256) // 64)) for c in wide for n in c["lens"] if n > 1}
+        last = {(-(-n // 512), -(-min((n - 1) % 512 + 1, 256) // 64)) for c in wide for n in c["lens"] if n > 1}
         assert {(2, 1), (2, 2), (2, 4), (3, 1), (1, 4)} <= last, (cost, last)
     sweep = WB.SWEEP_CASES
-    assert {WB.tiling(c["L"]) for c in sweep} == {(64, 2), (256, 2)}
+    assert {form(c["L"]) for c in sweep} == {(64, 2), (256, 2)}
     for L in WB.SWEEP_LENS:
         here = [c for c in sweep if c["L"] == L]
         assert {(c["kw"]["lam"], c["kw"]["sh_itr"]) for c in here if c["kw"]["cost_type"] == "eg"} >= \

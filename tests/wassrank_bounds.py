@@ -72,17 +72,6 @@ SCREEN = 1e-3                         # every eg gain and gain difference of a r
 MAX_SCREENED = 0.01
 
 
-def tiling(L):
-    """(G, DPT) of the kernel form that serves the padded width L (the dispatch rule of ptr_wassrank_fwd_bwd)."""
-    return (64, 1) if L <= 64 else (64, 2) if L <= 128 else (128, 2) if L <= 256 else (256, 2)
-
-
-def column_tiles(n, L):
-    """Trips of the column-tile loop of one row pass for a list of n documents in the form of width L."""
-    g, dpt = tiling(L)
-    return -(-n // (g * dpt))
-
-
 def _t(a):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
 
