@@ -729,9 +729,68 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *   ptr_alphadcg_fwd_bwd                         T, L                                     G, TP
  *   ptr_div_metrics_at_ks                        L                                        G, DPT
  *   ptr_divprob_fwd_bwd                          objective, T, L                          G, TP
+ *   ptr_gbdt_histogram                           m, F, max_bin                            kind, features per tile, tiles, row chunks, LDS bytes
+ *                                                                                           kind: 0 nothing, 1 direct, 2 LDS tile
  * G: threads per query, DPT: documents per thread, TP: subtopic tile.  PTR_ERR_INVALID_ARG for an entry without a form, another nargs, or
  * nform below the count. */
 int ptr_launch_form(const char *entry, const int64_t *args, int nargs, int32_t *form, int nform);
+
+/* ---- A histogram gradient-boosted tree trainer (csrc/gbdt.hip).  The symbols below are ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
+ * The reference's tree frame (ptranking/ltr_tree/lambdamart/lightgbm_lambdaMART.py) hands the boosting to LightGBM; ptranking_amd/gbdt.py
+ * grows the trees leaf-wise on these entry points instead.  No parity with LightGBM is claimed: the binning and tie rules are this
+ * project's own, and there is no GOSS, EFB, categorical or missing-value handling.
+ *
+ * Common rules: every argument is validated before any launch (PTR_ERR_INVALID_ARG: a NULL pointer that a launch would touch, a negative
+ * size, max_bin < 2, a stride that is no multiple of 16 or below F; PTR_ERR_UNSUPPORTED: max_bin > PTR_GBDT_MAX_BIN); an empty input
+ * launches nothing; row indices are int32 (n <= 2^31 - 1).  Integer atomics only: every result's bits depend on the data alone.
+ *
+ * Layouts.  bins [n][stride] uint8, row-major, stride = round_up(F, 16), 16-byte aligned, pad bytes 0.  hist [F][max_bin][3] int64: the
+ * sum of qg, the sum of qh and the row count of every (feature, bin).  A split record is 9 int64: the float64 gain's bit pattern (-inf: no
+ * valid split), feature, bin (both -1 without a split), then the LEFT child's sum qg, sum qh and count and the RIGHT child's.
+ *
+ * ptr_gbdt_bin: bins[r][f] = the number of edges[f][0 .. nbins[f] - 1) that are < X[r][f]; X [n][F] fp32 row-major, edges [F][max_bin - 1]
+ *   ascending per feature, nbins [F] in 1 .. max_bin.  So x <= edges[f][b] is bin <= b.  Non-finite features are the caller's error.
+ * ptr_gbdt_quantize: e_g = the largest integer with max|g| 2^e_g < 2^30 (0 when g is all zero), e_h likewise; qg = rint(g 2^e_g),
+ *   qh = rint(h 2^e_h) as int32 (ties to even); expo [2] = {e_g, e_h} in device memory.  A NaN or an infinity in g or h ORs 1 into flag [1]
+ *   (the caller zeroes it once and reads it when it likes) and that row is written as 0, 0; nothing is clamped.  state [2]: scratch.
+ * ptr_gbdt_histogram: ADDS the rows rows[0 .. m) (rows == NULL: the rows 0 .. m - 1) into a caller-zeroed hist.  A row index outside
+ *   [0, n) or a bin >= max_bin is skipped.  Forms, by m alone (ptr_launch_form): m <= 256 adds straight into global memory, one thread per
+ *   (row, feature); beyond, a grid of row chunks x tiles of 16 features sums in LDS (20 bytes per (feature, bin)) and flushes the bins it
+ *   touched with global integer atomic adds.
+ * ptr_gbdt_hist_sub: out = parent - child over one histogram, element-wise (out may alias parent): the larger child from the smaller.
+ * ptr_gbdt_best_split: per leaf histogram hist[l] of a batch [nleaf][F][max_bin][3], the best (feature, bin) -> rec [nleaf][9].  float64
+ *   throughout, NOT contracted into FMAs (the library is built with -ffp-contract=off), in this order:
+ *     G = (double)sum_qg 2^-e_g, H = (double)sum_qh 2^-e_h (exact);  gain = ((GL GL) / (HL + l2) + (GR GR) / (HR + l2)) - (G G) / (H + l2).
+ *   A candidate (f, b), b < nbins[f] - 1, sends bins <= b left; it is valid when both children hold >= min_data_in_leaf rows, both Hessian
+ *   sums are >= max(min_sum_hessian_in_leaf, 2^-40) and gain >= min_gain_to_split.  Ties: the lowest feature, then the lowest bin.
+ *   expo [2] as ptr_gbdt_quantize wrote it; ws: nleaf * F * 9 int64 of scratch.  lambda_l2 < 0 or a NaN threshold: PTR_ERR_INVALID_ARG.
+ * ptr_gbdt_partition: out = the rows of rows[0 .. m) with bins[row][feature] <= bin in their order, then the others in theirs;
+ *   left_count [1] = how many went left.  ws: ptr_gbdt_partition_ws_ints(m) int32 of scratch.  feature outside 0 .. F - 1 or bin outside
+ *   0 .. 255: PTR_ERR_INVALID_ARG.
+ * ptr_gbdt_add_leaf_values: scores[rows[i]] += values[l] for offsets[l] <= i < offsets[l + 1], l < nleaves, i < total; the row lists of a
+ *   finished tree's leaves are disjoint, so one launch serves them all.
+ * ptr_gbdt_predict: out[r] = the fp32 sum, in tree order from 0, of the leaf value each tree gives X[r].  Tree t owns the nodes
+ *   tree_offsets[t] .. tree_offsets[t + 1] of feature / threshold / left / right (child indices within the tree, a negative child is leaf
+ *   ~i) and the leaf values value[tree_offsets[t] + t ..] (a tree of k nodes has k + 1 leaves; k = 0 is a single leaf).  A row goes left
+ *   on x <= threshold.  A malformed tree yields NaN, never a read out of range. */
+#define PTR_GBDT_MAX_BIN 256
+int ptr_gbdt_bin(const float *X, int64_t n, int F, const float *edges, const int32_t *nbins, int max_bin, int stride, uint8_t *bins,
+                 void *stream);
+int ptr_gbdt_quantize(const float *g, const float *h, int64_t n, int32_t *qg, int32_t *qh, int32_t *expo, int32_t *flag, uint32_t *state,
+                      void *stream);
+int ptr_gbdt_histogram(const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows, int64_t m,
+                       int F, int max_bin, int64_t *hist, void *stream);
+int ptr_gbdt_hist_sub(const int64_t *parent, const int64_t *child, int F, int max_bin, int64_t *out, void *stream);
+int ptr_gbdt_best_split(const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *expo, double lambda_l2,
+                        int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double min_gain_to_split, int64_t *ws, int64_t *rec,
+                        void *stream);
+size_t ptr_gbdt_partition_ws_ints(int64_t m);
+int ptr_gbdt_partition(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m, int feature, int bin,
+                       int32_t *out, int32_t *left_count, int32_t *ws, void *stream);
+int ptr_gbdt_add_leaf_values(float *scores, int64_t n, const int32_t *rows, const int32_t *offsets, const float *values, int nleaves,
+                             int64_t total, void *stream);
+int ptr_gbdt_predict(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                     const int32_t *right, const float *value, const int32_t *tree_offsets, int ntrees, float *out, void *stream);
 
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):

@@ -8,7 +8,9 @@
     diversity   the diversification frame: DALETOR (alpha-DCG loss kernel), DivProbRanker (Gaussian pairwise-rank loss kernel),
                 alpha-nDCG / ERR-IA / nERR-IA on the device, DivQueryBatches
     tree        the tree frame's custom LightGBM objectives (RankNet / LambdaRank / ListNet gradient + Hessian over ragged groups):
-                TreeObjective, the six drop-in functions, install_tree(); the boosting itself stays in LightGBM
+                TreeObjective, the six drop-in functions, install_tree(): the hook for a LightGBM booster
+    gbdt        a native LambdaMART: GBDT (a histogram gradient-boosted tree trainer on the device, leaf-wise growth on fixed-point
+                integer histograms) and LambdaMART (the tree objectives above + GBDT, scores and gradients never leave the device)
     dp          data-parallel gradient exchange (one RCCL all-reduce per step)
     install()   rebinds the ranker names of RANKER_NAMES (RankNet, LambdaRank, LambdaLoss, ApproxNDCG, ListNet, ListMLE, STListNet,
                 RankCosine, RankMSE, SoftRank, WassRank) inside an installed ptranking so LTREvaluator uses them unchanged; a WassRank
@@ -20,7 +22,8 @@
 The only compute implementation is the HIP library ptranking_amd/libptranking_amd.so (C ABI: include/ptranking_amd.h);
 there is no CPU fallback.  Build it with `python -m ptranking_amd.build`.
 """
-from . import _lib, batching, diversity, dp, functional, host, rankers, scorer, tree   # noqa: F401
+from . import _lib, batching, diversity, dp, functional, gbdt, host, rankers, scorer, tree   # noqa: F401
+from .gbdt import GBDT, LambdaMART                  # noqa: F401
 from .batching import PaddedQueryBatches            # noqa: F401
 from . import letor                                   # noqa: F401
 from .host import LABEL_TYPE, DeviceEvaluator       # noqa: F401

@@ -6,6 +6,7 @@
 #include "ptr_attn.h"
 #include "ptr_device.h"
 #include "ptr_div.h"
+#include "ptr_gbdt.h"
 
 namespace ptr {
 
@@ -77,6 +78,7 @@ static const FormQuery kFormQueries[] = {
     {"ptr_alphadcg_fwd_bwd", 2, 2, [](const int64_t *a, int32_t *out) { put(out, div_form((int)a[0], (int)a[1])); }},
     {"ptr_div_metrics_at_ks", 1, 2, [](const int64_t *a, int32_t *out) { put(out, pick_tiling((int)a[0])); }},
     {"ptr_divprob_fwd_bwd", 3, 2, [](const int64_t *a, int32_t *out) { put(out, divprob_form((int)a[0], (int)a[1], (int)a[2])); }},
+    {"ptr_gbdt_histogram", 3, 5, [](const int64_t *a, int32_t *out) { put(out, gbdt_hist_form(a[0], (int)a[1], (int)a[2])); }},
 };
 
 }  // namespace ptr

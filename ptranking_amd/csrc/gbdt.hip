@@ -1,0 +1,505 @@
+// A histogram gradient-boosted tree trainer on the device: binning, fixed-point gradients, per-leaf histograms, the split scan, the stable
+// row partition, the leaf-value update and prediction.  ptranking_amd/gbdt.py grows the trees leaf-wise on these entry points; the
+// reference's tree frame (ptranking/ltr_tree/lambdamart/lightgbm_lambdaMART.py) hands this work to LightGBM.
+//
+// Why fixed point.  ptr_gbdt_quantize scales a round's gradients and Hessians by a power of two so that the largest magnitude lies just
+// below 2^30 and rounds them to int32.  Every histogram sum is then an int64 sum of int32 terms, and integer addition is associative: the
+// bits of a histogram do not depend on the row order, the number of workgroups, how a leaf's rows are chunked, or whether the histogram
+// was built from rows or by subtracting a sibling from its parent.  The kernels use integer atomics only (LDS and global); there is no
+// float atomic in this file.  An int64 sum holds 2^33 rows at the extreme; the split scan turns sums into float64 exactly up to 2^53,
+// that is 2^23 rows with every gradient at the extreme.
+//
+// Layouts.  bins [n][stride] uint8, row-major, stride = round_up(F, 16), pad bytes 0: the 16 features of a tile are one 16-byte load of
+// a row.  hist [F][max_bin][3] int64: sum qg, sum qh, count.  Split records: 9 int64 (include/ptranking_amd.h).
+//
+// Histogram forms (gbdt_hist_form, ptr_gbdt.h):
+//   direct   m <= 256 rows: one thread per (row, feature) adds into global memory; a small leaf touches few bins, zeroing and flushing a
+//            tile would cost more than the adds;
+//   LDS      grid = row chunks x feature tiles of 16.  A workgroup keeps [16][max_bin] of (int64, int64, int32) in LDS (20 bytes per
+//            entry, 80 KiB at 256 bins: two workgroups per compute unit), each lane loads one row's 16 bins as a uint4 and its qg, qh once,
+//            and walks the 16 features ROTATED by its lane number: in one step the 64 lanes address 16 different features, so a constant
+//            feature (every row in one bin) meets 4 lanes per address and step, not 64.  The flush adds only the bins the chunk touched.
+#include "ptr_gbdt.h"
+
+namespace ptr {
+
+using u64 = unsigned long long;
+constexpr int kRec = 9;                  // int64 values of a split record
+
+// ---------------------------------------------------------------- binning
+__global__ void __launch_bounds__(kBlock)
+gbdt_bin_kernel(const float *__restrict__ X, int64_t n, int F, const float *__restrict__ edges, const int32_t *__restrict__ nbins, int max_bin,
+                int stride, uint8_t *__restrict__ bins) {
+    const int64_t total = n * stride;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
+        const int64_t row = e / stride;
+        const int f = (int)(e - row * stride);
+        int b = 0;
+        if (f < F) {
+            const float x = X[row * F + f];
+            const float *ed = edges + (size_t)f * (max_bin - 1);
+            int lo = 0, hi = min(max(nbins[f], 1), max_bin) - 1;          // the number of edges < x, by bisection over [0, nbins - 1)
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (ed[mid] < x) lo = mid + 1; else hi = mid;
+            }
+            b = lo;
+        }
+        bins[e] = (uint8_t)b;
+    }
+}
+
+// ---------------------------------------------------------------- quantization
+// state[0], state[1]: the bit patterns of max|g| and max|h| (non-negative floats order as unsigned integers): an integer atomic max.
+__global__ void __launch_bounds__(kBlock)
+gbdt_absmax_kernel(const float *__restrict__ g, const float *__restrict__ h, int64_t n, uint32_t *__restrict__ state, int32_t *__restrict__ flag) {
+    __shared__ uint32_t red[2];
+    if (threadIdx.x < 2) red[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t mg = 0, mh = 0;
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const uint32_t a = __float_as_uint(g[i]) & 0x7fffffffu, b = __float_as_uint(h[i]) & 0x7fffffffu;
+        if (a >= 0x7f800000u || b >= 0x7f800000u) bad = true;           // inf or NaN
+        else { mg = max(mg, a); mh = max(mh, b); }
+    }
+    atomicMax(&red[0], mg);
+    atomicMax(&red[1], mh);
+    if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(flag, 1);
+    if (threadIdx.x == 0) { atomicMax(&state[0], red[0]); atomicMax(&state[1], red[1]); }
+}
+
+// the largest e with m 2^e < 2^30: m = fr 2^ex with fr in [0.5, 1), so e = 30 - ex; 0 for m == 0
+__device__ __forceinline__ int gbdt_exponent(uint32_t bits) {
+    if (bits == 0) return 0;
+    int ex;
+    (void)frexpf(__uint_as_float(bits), &ex);
+    return 30 - ex;
+}
+
+__global__ void __launch_bounds__(kBlock)
+gbdt_quantize_kernel(const float *__restrict__ g, const float *__restrict__ h, int64_t n, const uint32_t *__restrict__ state,
+                     int32_t *__restrict__ qg, int32_t *__restrict__ qh, int32_t *__restrict__ expo) {
+    const int eg = gbdt_exponent(state[0]), eh = gbdt_exponent(state[1]);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { expo[0] = eg; expo[1] = eh; }
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const float a = g[i], b = h[i];
+        const bool fin = (__float_as_uint(a) & 0x7fffffffu) < 0x7f800000u && (__float_as_uint(b) & 0x7fffffffu) < 0x7f800000u;
+        qg[i] = fin ? (int32_t)rintf(ldexpf(a, eg)) : 0;                // a non-finite entry raised the flag; its row carries nothing
+        qh[i] = fin ? (int32_t)rintf(ldexpf(b, eh)) : 0;
+    }
+}
+
+// ---------------------------------------------------------------- histograms
+__device__ __forceinline__ void hist_add_global(int64_t *__restrict__ cell, int64_t g, int64_t h, int64_t c) {
+    atomicAdd(reinterpret_cast<u64 *>(cell), (u64)g);
+    atomicAdd(reinterpret_cast<u64 *>(cell + 1), (u64)h);
+    atomicAdd(reinterpret_cast<u64 *>(cell + 2), (u64)c);
+}
+
+__global__ void __launch_bounds__(kBlock)
+gbdt_hist_direct_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg, const int32_t *__restrict__ qh,
+                        const int32_t *__restrict__ rows, int m, int F, int max_bin, int64_t *__restrict__ hist) {
+    const int e = blockIdx.x * kBlock + threadIdx.x;                    // m <= kGbdtDirectRows: m * stride fits an int
+    if (e >= m * stride) return;
+    const int i = e / stride, f = e - i * stride;
+    const int row = rows ? rows[i] : i;
+    if (f >= F || row < 0 || row >= n) return;
+    const int b = bins[(size_t)row * stride + f];
+    if (b >= max_bin) return;
+    hist_add_global(hist + ((size_t)f * max_bin + b) * 3, qg[row], qh[row], 1);
+}
+
+__global__ void __launch_bounds__(kBlock)
+gbdt_hist_lds_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg, const int32_t *__restrict__ qh,
+                     const int32_t *__restrict__ rows, int m, int F, int max_bin, int64_t *__restrict__ hist) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gbdt_smem[];
+    const int cells = kGbdtTile * max_bin;
+    u64 *lg = reinterpret_cast<u64 *>(gbdt_smem), *lh = lg + cells;
+    uint32_t *lc = reinterpret_cast<uint32_t *>(lh + cells);
+    const int tid = threadIdx.x, f0 = blockIdx.y * kGbdtTile;
+    for (int e = tid; e < cells; e += kBlock) { lg[e] = 0; lh[e] = 0; lc[e] = 0; }
+    __syncthreads();
+
+    // this workgroup's rows: chunk c of gridDim.x, whole multiples of the block except the last
+    const int per = (int)((((int64_t)m + gridDim.x - 1) / gridDim.x + kBlock - 1) / kBlock) * kBlock;
+    const int64_t r0 = (int64_t)blockIdx.x * per;
+    const int64_t r1 = r0 + per < (int64_t)m ? r0 + per : (int64_t)m;
+    const int nf = min(kGbdtTile, F - f0);
+    for (int64_t i = r0 + tid; i < r1; i += kBlock) {
+        const int row = rows ? rows[i] : (int)i;
+        if (row < 0 || row >= n) continue;
+        const uint4 bv = *reinterpret_cast<const uint4 *>(bins + (size_t)row * stride + f0);
+        const u64 g = (u64)(int64_t)qg[row], h = (u64)(int64_t)qh[row];
+#pragma unroll
+        for (int k = 0; k < kGbdtTile; ++k) {
+            const int f = (k + tid) & (kGbdtTile - 1);
+            const uint32_t w = (f >> 2) == 0 ? bv.x : (f >> 2) == 1 ? bv.y : (f >> 2) == 2 ? bv.z : bv.w;
+            const int b = (w >> ((f & 3) * 8)) & 0xff;
+            if (f < nf && b < max_bin) {
+                const int c = f * max_bin + b;
+                atomicAdd(&lg[c], g);
+                atomicAdd(&lh[c], h);
+                atomicAdd(&lc[c], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < nf * max_bin; e += kBlock) {
+        const uint32_t c = lc[e];
+        if (c) hist_add_global(hist + ((size_t)f0 * max_bin + e) * 3, (int64_t)lg[e], (int64_t)lh[e], (int64_t)c);
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+gbdt_hist_sub_kernel(const int64_t *__restrict__ parent, const int64_t *__restrict__ child, int64_t count, int64_t *__restrict__ out) {
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < count; e += (int64_t)gridDim.x * kBlock) out[e] = parent[e] - child[e];
+}
+
+// ---------------------------------------------------------------- the split scan
+template <class T> __device__ __forceinline__ T wave_scan_add(T v, int lane) {       // inclusive, over the 64 lanes
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const T o = __shfl_up(v, d);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+struct SplitCand { double gain; int bin; int64_t gl, hl, cl; };
+
+// One wavefront per (leaf, feature): lane t owns the bins 4 t .. 4 t + 3, one prefix pass.  Writes the feature's best candidate to ws.
+// All arithmetic is float64 and nothing is contracted (the library is built with -ffp-contract=off):
+//   gain = ((GL * GL) / (HL + l2) + (GR * GR) / (HR + l2)) - (G * G) / (H + l2),   G = (double)qsum * 2^-e_g, H likewise (both exact).
+__global__ void __launch_bounds__(kBlock)
+gbdt_split_feature_kernel(const int64_t *__restrict__ hist, int nleaf, int F, int max_bin, const int32_t *__restrict__ nbins,
+                          const int32_t *__restrict__ expo, double l2, int64_t min_data, double min_hess, double min_gain,
+                          int64_t *__restrict__ ws) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t item = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    if (item >= (int64_t)nleaf * F) return;
+    const int f = (int)(item % F);
+    const int64_t *hp = hist + item * max_bin * 3;
+    const int nb = min(max(nbins[f], 1), max_bin);
+    int64_t pg[4], ph[4], pc[4], sg = 0, sh = 0, sc = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int b = lane * 4 + k;
+        if (b < nb) { sg += hp[b * 3]; sh += hp[b * 3 + 1]; sc += hp[b * 3 + 2]; }
+        pg[k] = sg; ph[k] = sh; pc[k] = sc;
+    }
+    const int64_t ig = wave_scan_add(sg, lane) - sg, ih = wave_scan_add(sh, lane) - sh, ic = wave_scan_add(sc, lane) - sc;
+    const int64_t TG = __shfl(ig + sg, kWave - 1), TH = __shfl(ih + sh, kWave - 1), TC = __shfl(ic + sc, kWave - 1);
+    const int eg = expo[0], eh = expo[1];
+    const double G = ldexp((double)TG, -eg), H = ldexp((double)TH, -eh);
+    const double parent = (G * G) / (H + l2);
+    const double floor_h = fmax(min_hess, 0x1p-40);
+    SplitCand best{-INFINITY, -1, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int b = lane * 4 + k;
+        if (b >= nb - 1) continue;                                      // the last bin leaves nothing on the right
+        const int64_t gl = ig + pg[k], hl = ih + ph[k], cl = ic + pc[k];
+        const int64_t cr = TC - cl;
+        if (cl < min_data || cr < min_data) continue;
+        const double GL = ldexp((double)gl, -eg), HL = ldexp((double)hl, -eh);
+        const double GR = ldexp((double)(TG - gl), -eg), HR = ldexp((double)(TH - hl), -eh);
+        if (!(HL >= floor_h) || !(HR >= floor_h)) continue;
+        const double gain = ((GL * GL) / (HL + l2) + (GR * GR) / (HR + l2)) - parent;
+        if (!(gain >= min_gain)) continue;
+        if (gain > best.gain) best = SplitCand{gain, b, gl, hl, cl};     // ascending bins: a tie keeps the lowest
+    }
+    // the wave's best: highest gain, then lowest bin
+#pragma unroll
+    for (int d = kWave / 2; d >= 1; d >>= 1) {
+        const double og = __shfl_xor(best.gain, d);
+        const int ob = __shfl_xor(best.bin, d);
+        const int64_t o1 = __shfl_xor(best.gl, d), o2 = __shfl_xor(best.hl, d), o3 = __shfl_xor(best.cl, d);
+        if (ob >= 0 && (best.bin < 0 || og > best.gain || (og == best.gain && ob < best.bin))) best = SplitCand{og, ob, o1, o2, o3};
+    }
+    if (lane == 0) {
+        int64_t *r = ws + item * kRec;
+        const bool ok = best.bin >= 0;
+        r[0] = __double_as_longlong(ok ? best.gain : -INFINITY);
+        r[1] = ok ? f : -1; r[2] = best.bin;
+        r[3] = best.gl; r[4] = best.hl; r[5] = best.cl;
+        r[6] = ok ? TG - best.gl : 0; r[7] = ok ? TH - best.hl : 0; r[8] = ok ? TC - best.cl : 0;
+    }
+}
+
+// One wavefront per leaf: the best of its F feature records, ties to the lowest feature.
+__global__ void __launch_bounds__(kWave)
+gbdt_split_leaf_kernel(const int64_t *__restrict__ ws, int F, int64_t *__restrict__ rec) {
+    const int lane = threadIdx.x;
+    const int64_t *w = ws + (int64_t)blockIdx.x * F * kRec;
+    double bg = -INFINITY;
+    int bf = -1;
+    for (int f = lane; f < F; f += kWave) {
+        const double g = __longlong_as_double(w[(int64_t)f * kRec]);
+        if (w[(int64_t)f * kRec + 1] >= 0 && (bf < 0 || g > bg)) { bg = g; bf = f; }
+    }
+#pragma unroll
+    for (int d = kWave / 2; d >= 1; d >>= 1) {
+        const double og = __shfl_xor(bg, d);
+        const int of = __shfl_xor(bf, d);
+        if (of >= 0 && (bf < 0 || og > bg || (og == bg && of < bf))) { bg = og; bf = of; }
+    }
+    if (lane < kRec) {
+        int64_t v = lane == 0 ? __double_as_longlong(-INFINITY) : lane <= 2 ? -1 : 0;
+        if (bf >= 0) v = w[(int64_t)bf * kRec + lane];
+        rec[(int64_t)blockIdx.x * kRec + lane] = v;
+    }
+}
+
+// ---------------------------------------------------------------- the stable partition
+constexpr int kPartSteps = 4;                                           // a workgroup owns 4 x 256 consecutive entries of the list
+
+__device__ __forceinline__ bool part_goes_left(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ rows, int64_t i, int m,
+                                               int feature, int bin, int &row) {
+    row = i < m ? rows[i] : -1;
+    return row >= 0 && row < n && (int)bins[(size_t)row * stride + feature] <= bin;
+}
+
+__global__ void __launch_bounds__(kBlock)
+gbdt_part_count_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ rows, int m, int feature, int bin,
+                       int32_t *__restrict__ counts) {
+    __shared__ int32_t tot;
+    if (threadIdx.x == 0) tot = 0;
+    __syncthreads();
+    int c = 0, row;
+    for (int s = 0; s < kPartSteps; ++s)
+        c += part_goes_left(bins, stride, n, rows, ((int64_t)blockIdx.x * kPartSteps + s) * kBlock + threadIdx.x, m, feature, bin, row) ? 1 : 0;
+    atomicAdd(&tot, c);
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = tot;
+}
+
+// counts [nb] -> their exclusive prefix, in place; counts[nb] and left_count[0] = the total.  One workgroup.
+__global__ void __launch_bounds__(kBlock)
+gbdt_part_scan_kernel(int32_t *__restrict__ counts, int nb, int32_t *__restrict__ left_count) {
+    __shared__ int32_t seg[kBlock];
+    const int t = threadIdx.x, per = (nb + kBlock - 1) / kBlock;
+    const int lo = min(t * per, nb), hi = min(lo + per, nb);
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += counts[i];
+    seg[t] = s;
+    __syncthreads();
+    for (int d = 1; d < kBlock; d <<= 1) {
+        const int o = t >= d ? seg[t - d] : 0;
+        __syncthreads();
+        seg[t] += o;
+        __syncthreads();
+    }
+    int run = seg[t] - s;
+    for (int i = lo; i < hi; ++i) { const int c = counts[i]; counts[i] = run; run += c; }
+    if (t == kBlock - 1) { counts[nb] = seg[t]; left_count[0] = seg[t]; }
+}
+
+__global__ void __launch_bounds__(kBlock)
+gbdt_part_scatter_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ rows, int m, int feature, int bin,
+                         const int32_t *__restrict__ counts, int nb, int32_t *__restrict__ out) {
+    __shared__ int32_t wave_left[kBlock / kWave];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    int left_before = counts[blockIdx.x];
+    const int total_left = counts[nb];
+    for (int s = 0; s < kPartSteps; ++s) {
+        const int64_t i = ((int64_t)blockIdx.x * kPartSteps + s) * kBlock + threadIdx.x;
+        int row;
+        const bool left = part_goes_left(bins, stride, n, rows, i, m, feature, bin, row);
+        const unsigned long long mask = __ballot(left);
+        if (lane == 0) wave_left[wave] = __popcll(mask);
+        __syncthreads();
+        int before = left_before + __popcll(mask & ((1ull << lane) - 1));
+        int step_left = 0;
+        for (int w = 0; w < kBlock / kWave; ++w) { if (w < wave) before += wave_left[w]; step_left += wave_left[w]; }
+        if (i < m) out[left ? before : total_left + (int)(i - before)] = row;     // `before` = the lefts ahead of entry i
+        left_before += step_left;
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------- leaf values and prediction
+__global__ void __launch_bounds__(kBlock)
+gbdt_add_leaf_values_kernel(float *__restrict__ scores, int n, const int32_t *__restrict__ rows, const int32_t *__restrict__ offsets,
+                            const float *__restrict__ values, int nleaves, int total) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= total) return;
+    int lo = 0, hi = nleaves;                                           // the leaf whose [offsets[l], offsets[l + 1]) holds i
+    while (lo + 1 < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (offsets[mid] <= i) lo = mid; else hi = mid;
+    }
+    const int row = rows[i];
+    if (i < offsets[nleaves] && i >= offsets[0] && row >= 0 && row < n) scores[row] += values[lo];
+}
+
+__global__ void __launch_bounds__(kBlock)
+gbdt_predict_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t *__restrict__ feature, const float *__restrict__ threshold,
+                    const int32_t *__restrict__ left, const int32_t *__restrict__ right, const float *__restrict__ value,
+                    const int32_t *__restrict__ tree_offsets, int ntrees, float *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float *x = X + i * F;
+    float s = 0.0f;
+    for (int t = 0; t < ntrees; ++t) {
+        const int base = tree_offsets[t], nn = tree_offsets[t + 1] - base, leaves = base + t;      // a tree of nn nodes has nn + 1 leaves
+        int node = nn > 0 ? 0 : ~0;
+        for (int step = 0; step < nn && node >= 0; ++step) {
+            if (node >= nn) break;
+            const int f = feature[base + node];
+            if (f < 0 || f >= F) break;
+            node = x[f] <= threshold[base + node] ? left[base + node] : right[base + node];
+        }
+        s += (node < 0 && ~node <= nn) ? value[leaves + ~node] : NAN;   // a malformed tree (a cycle, an index out of range) gives NaN
+    }
+    out[i] = s;
+}
+
+static int grid_for(int64_t elems, int cap = 1 << 16) {
+    const int64_t b = (elems + kBlock - 1) / kBlock;
+    return (int)(b < 1 ? 1 : b > cap ? cap : b);
+}
+static int check_max_bin(int max_bin, const char *who) {
+    if (max_bin < 2 || max_bin > PTR_GBDT_MAX_BIN) {
+        set_error("%s: max_bin must be in 2 .. %d, got %d", who, PTR_GBDT_MAX_BIN, max_bin);
+        return max_bin > PTR_GBDT_MAX_BIN ? PTR_ERR_UNSUPPORTED : PTR_ERR_INVALID_ARG;
+    }
+    return 0;
+}
+static int check_bins_layout(int64_t n, int F, int stride, const char *who) {
+    if (n < 0 || F < 0 || n > INT32_MAX) { set_error("%s: bad size (n=%lld, F=%d; n must fit an int32 row index)", who, (long long)n, F); return PTR_ERR_INVALID_ARG; }
+    if (stride < F || stride % kGbdtTile != 0) {
+        set_error("%s: stride must be a multiple of %d and at least F (stride=%d, F=%d)", who, kGbdtTile, stride, F);
+        return PTR_ERR_INVALID_ARG;
+    }
+    return 0;
+}
+
+}  // namespace ptr
+
+using namespace ptr;
+
+extern "C" int ptr_gbdt_bin(const float *X, int64_t n, int F, const float *edges, const int32_t *nbins, int max_bin, int stride, uint8_t *bins,
+                            void *stream) {
+    const char *who = "ptr_gbdt_bin";
+    if (int rc = check_bins_layout(n, F, stride, who)) return rc;
+    if (int rc = check_max_bin(max_bin, who)) return rc;
+    if (n == 0 || F == 0) return 0;
+    if (!X || !edges || !nbins || !bins) { set_error("%s: NULL pointer (X, edges, nbins or bins)", who); return PTR_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(gbdt_bin_kernel, dim3(grid_for(n * stride)), dim3(kBlock), 0, as_stream(stream), X, n, F, edges, nbins, max_bin, stride, bins);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_quantize(const float *g, const float *h, int64_t n, int32_t *qg, int32_t *qh, int32_t *expo, int32_t *flag, uint32_t *state,
+                                 void *stream) {
+    const char *who = "ptr_gbdt_quantize";
+    if (n < 0) { set_error("%s: negative size (n=%lld)", who, (long long)n); return PTR_ERR_INVALID_ARG; }
+    if (n == 0) return 0;
+    if (!g || !h || !qg || !qh || !expo || !flag || !state) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_hip(hipMemsetAsync(state, 0, 2 * sizeof(uint32_t), as_stream(stream)), who)) return rc;
+    hipLaunchKernelGGL(gbdt_absmax_kernel, dim3(grid_for(n, 1024)), dim3(kBlock), 0, as_stream(stream), g, h, n, state, flag);
+    hipLaunchKernelGGL(gbdt_quantize_kernel, dim3(grid_for(n, 4096)), dim3(kBlock), 0, as_stream(stream), g, h, n, state, qg, qh, expo);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_histogram(const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows, int64_t m,
+                                  int F, int max_bin, int64_t *hist, void *stream) {
+    const char *who = "ptr_gbdt_histogram";
+    if (int rc = check_bins_layout(n, F, stride, who)) return rc;
+    if (int rc = check_max_bin(max_bin, who)) return rc;
+    if (m < 0 || m > INT32_MAX) { set_error("%s: bad row count m=%lld", who, (long long)m); return PTR_ERR_INVALID_ARG; }
+    if (!rows && m > n) { set_error("%s: rows is NULL (the first m rows), so m must not exceed n (m=%lld, n=%lld)", who, (long long)m, (long long)n); return PTR_ERR_INVALID_ARG; }
+    const GbdtHistForm form = gbdt_hist_form(m, F, max_bin);
+    if (form.kind == 0) return 0;
+    if (!bins || !qg || !qh || !hist) { set_error("%s: NULL pointer (bins, qg, qh or hist)", who); return PTR_ERR_INVALID_ARG; }
+    if (reinterpret_cast<uintptr_t>(bins) & 15) { set_error("%s: bins must be 16-byte aligned", who); return PTR_ERR_INVALID_ARG; }
+    if (form.kind == 1) {
+        hipLaunchKernelGGL(gbdt_hist_direct_kernel, dim3((unsigned)((m * stride + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), bins, stride, (int)n, qg, qh, rows,
+                           (int)m, F, max_bin, hist);
+    } else {
+        if (int rc = allow_lds(gbdt_hist_lds_kernel, (size_t)form.lds_bytes)) return rc;
+        hipLaunchKernelGGL(gbdt_hist_lds_kernel, dim3(form.chunks, form.tiles), dim3(kBlock), (size_t)form.lds_bytes, as_stream(stream), bins, stride,
+                           (int)n, qg, qh, rows, (int)m, F, max_bin, hist);
+    }
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_hist_sub(const int64_t *parent, const int64_t *child, int F, int max_bin, int64_t *out, void *stream) {
+    const char *who = "ptr_gbdt_hist_sub";
+    if (F < 0) { set_error("%s: negative size (F=%d)", who, F); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_max_bin(max_bin, who)) return rc;
+    if (F == 0) return 0;
+    if (!parent || !child || !out) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
+    const int64_t count = (int64_t)F * max_bin * 3;
+    hipLaunchKernelGGL(gbdt_hist_sub_kernel, dim3(grid_for(count)), dim3(kBlock), 0, as_stream(stream), parent, child, count, out);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_best_split(const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *expo, double lambda_l2,
+                                   int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double min_gain_to_split, int64_t *ws, int64_t *rec,
+                                   void *stream) {
+    const char *who = "ptr_gbdt_best_split";
+    if (nleaf < 0 || F < 0) { set_error("%s: negative size (nleaf=%d, F=%d)", who, nleaf, F); return PTR_ERR_INVALID_ARG; }
+    if (int rc = check_max_bin(max_bin, who)) return rc;
+    if (!(lambda_l2 >= 0.0) || !(min_sum_hessian_in_leaf == min_sum_hessian_in_leaf) || !(min_gain_to_split == min_gain_to_split)) {
+        set_error("%s: lambda_l2 must be >= 0 and no threshold may be NaN", who);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (nleaf == 0) return 0;
+    if (!rec || (F > 0 && (!hist || !nbins || !expo || !ws))) { set_error("%s: NULL pointer (hist, nbins, expo, ws or rec)", who); return PTR_ERR_INVALID_ARG; }
+    const int64_t items = (int64_t)nleaf * F;
+    if (items > 0)
+        hipLaunchKernelGGL(gbdt_split_feature_kernel, dim3((unsigned)((items + 3) / 4)), dim3(kBlock), 0, as_stream(stream), hist, nleaf, F, max_bin, nbins,
+                           expo, lambda_l2, min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws);
+    hipLaunchKernelGGL(gbdt_split_leaf_kernel, dim3(nleaf), dim3(kWave), 0, as_stream(stream), ws, F, rec);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" size_t ptr_gbdt_partition_ws_ints(int64_t m) {
+    return m <= 0 ? 1 : (size_t)((m + kPartSteps * kBlock - 1) / (kPartSteps * kBlock)) + 1;
+}
+
+extern "C" int ptr_gbdt_partition(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m, int feature, int bin,
+                                  int32_t *out, int32_t *left_count, int32_t *ws, void *stream) {
+    const char *who = "ptr_gbdt_partition";
+    if (int rc = check_bins_layout(n, F, stride, who)) return rc;
+    if (m < 0 || m > INT32_MAX) { set_error("%s: bad row count m=%lld", who, (long long)m); return PTR_ERR_INVALID_ARG; }
+    if (feature < 0 || feature >= F || bin < 0 || bin > 255) {
+        set_error("%s: feature must be in 0 .. F - 1 and bin in 0 .. 255 (feature=%d, F=%d, bin=%d)", who, feature, F, bin);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (!left_count) { set_error("%s: NULL left_count", who); return PTR_ERR_INVALID_ARG; }
+    if (m == 0) return check_hip(hipMemsetAsync(left_count, 0, sizeof(int32_t), as_stream(stream)), who);
+    if (!bins || !rows || !out || !ws) { set_error("%s: NULL pointer (bins, rows, out or ws)", who); return PTR_ERR_INVALID_ARG; }
+    const int nb = (int)ptr_gbdt_partition_ws_ints(m) - 1;
+    hipLaunchKernelGGL(gbdt_part_count_kernel, dim3(nb), dim3(kBlock), 0, as_stream(stream), bins, stride, (int)n, rows, (int)m, feature, bin, ws);
+    hipLaunchKernelGGL(gbdt_part_scan_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), ws, nb, left_count);
+    hipLaunchKernelGGL(gbdt_part_scatter_kernel, dim3(nb), dim3(kBlock), 0, as_stream(stream), bins, stride, (int)n, rows, (int)m, feature, bin, ws, nb, out);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_add_leaf_values(float *scores, int64_t n, const int32_t *rows, const int32_t *offsets, const float *values, int nleaves,
+                                        int64_t total, void *stream) {
+    const char *who = "ptr_gbdt_add_leaf_values";
+    if (n < 0 || n > INT32_MAX || nleaves < 0 || total < 0 || total > INT32_MAX) {
+        set_error("%s: bad size (n=%lld, nleaves=%d, total=%lld)", who, (long long)n, nleaves, (long long)total);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (nleaves == 0 || total == 0) return 0;
+    if (!scores || !rows || !offsets || !values) { set_error("%s: NULL pointer (scores, rows, offsets or values)", who); return PTR_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(gbdt_add_leaf_values_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), scores, (int)n, rows,
+                       offsets, values, nleaves, (int)total);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_predict(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                const int32_t *right, const float *value, const int32_t *tree_offsets, int ntrees, float *out, void *stream) {
+    const char *who = "ptr_gbdt_predict";
+    if (n < 0 || F < 0 || ntrees < 0) { set_error("%s: negative size (n=%lld, F=%d, ntrees=%d)", who, (long long)n, F, ntrees); return PTR_ERR_INVALID_ARG; }
+    if (n == 0) return 0;
+    if (!out || (F > 0 && !X)) { set_error("%s: NULL pointer (X or out)", who); return PTR_ERR_INVALID_ARG; }
+    if (ntrees > 0 && (!feature || !threshold || !left || !right || !value || !tree_offsets)) { set_error("%s: NULL tree array", who); return PTR_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(gbdt_predict_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), X, n, F, feature, threshold, left,
+                       right, value, tree_offsets, ntrees, out);
+    return check_hip(hipGetLastError(), who);
+}

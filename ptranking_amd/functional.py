@@ -16,7 +16,9 @@ from . import _lib
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
            "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "ndeval_measures", "div_ideal_order", "NDEVAL_MEASURES","divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
-           "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "gaussian_metric_objective", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES"]
+           "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "gaussian_metric_objective", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES",
+           "gbdt_bin", "gbdt_quantize", "gbdt_histogram", "gbdt_hist_sub", "gbdt_best_split", "gbdt_partition", "gbdt_add_leaf_values", "gbdt_predict",
+           "GBDT_MAX_BIN", "GBDT_RECORD"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
 # launch table, and it draws its own)
@@ -30,6 +32,8 @@ TREE_HESSIANS = {"reference": 0, "sum": 1, "constant": 2}                   # PT
 TREE_GAIN_TYPES = {"Power": 0, "Label": 1}                                  # PTR_TREE_GAIN_*; lightgbm_util.py:306
 SMOOTH_METRICS = {"P": 0, "AP": 1, "nERR": 2, "nDCG": 3, 0: 0, 1: 1, 2: 2, 3: 3}   # PTR_SMOOTH_*; metric/smooth_metric/metric_as_opt_objective.py
 PL_DISTRIBUTIONS = {"PL": 0, "STPL": 1, 0: 0, 1: 1}   # PTR_PL_DIST_*; ptranking/ltr_adhoc/listwise/mdprank.py:19
+GBDT_MAX_BIN = 256                                                         # PTR_GBDT_MAX_BIN
+GBDT_RECORD = ("gain", "feature", "bin", "left_g", "left_h", "left_count", "right_g", "right_h", "right_count")   # a split record's 9 int64
 WASS_COST_TYPES = {"p1": 0, "p2": 1, "eg": 2, "dg": 3, "ddg": 4}   # PTR_WASS_COST_*; wassrank/wasserstein_cost_mat.py:113-139
 
 
@@ -621,4 +625,173 @@ def sum_f32(x, scale=1.0):
     out = torch.empty(1, device=x.device, dtype=torch.float32)
     with torch.cuda.device(x.device):
         _lib.call("ptr_sum_f32", _lib.ptr(x), x.numel(), C.c_float(float(scale)), _lib.ptr(out), _lib.current_stream(x.device))
+    return out
+
+
+# ---- the histogram gradient-boosted tree kernels (csrc/gbdt.hip; include/ptranking_amd.h states every contract).  Thin wrappers: gbdt.py
+# holds the trainer.  None of them is differentiable.
+def _gbdt_bins(bins, F):
+    bins = _check("bins", bins, torch.uint8)
+    if bins.dim() != 2 or bins.shape[1] % 16 or bins.shape[1] < F:
+        raise ValueError(f"bins must be [rows, round_up(F, 16)] uint8 for F={F}, got {tuple(bins.shape)}")
+    return bins
+
+
+def _gbdt_max_bin(max_bin):
+    if not 2 <= int(max_bin) <= GBDT_MAX_BIN:
+        raise ValueError(f"max_bin must be in 2 .. {GBDT_MAX_BIN}, got {max_bin}")
+    return int(max_bin)
+
+
+def gbdt_bin(X, edges, nbins):
+    """Bin indices of a feature matrix -> uint8 [n, round_up(F, 16)] (pad columns 0).  X float32 [n, F]; edges float32 [F, max_bin - 1],
+    ascending per feature; nbins int32 [F].  bin = the number of the feature's first nbins - 1 edges below x, so x <= edges[f, b] is
+    bin <= b."""
+    X = _check("X", X)
+    if X.dim() != 2:
+        raise ValueError(f"X must be [rows, features], got {tuple(X.shape)}")
+    n, F = X.shape
+    edges = _check("edges", edges)
+    if edges.dim() != 2 or edges.shape[0] != F:
+        raise ValueError(f"edges must be [features, max_bin - 1], got {tuple(edges.shape)}")
+    max_bin = _gbdt_max_bin(edges.shape[1] + 1)
+    nbins = _check("nbins", nbins, torch.int32, (F,))
+    stride = (F + 15) // 16 * 16
+    bins = torch.empty((n, stride), device=X.device, dtype=torch.uint8)
+    with torch.cuda.device(X.device):
+        _lib.call("ptr_gbdt_bin", _lib.ptr(X), n, F, _lib.ptr(edges), _lib.ptr(nbins), max_bin, stride, _lib.ptr(bins), _lib.current_stream(X.device))
+    return bins
+
+
+def gbdt_quantize(grad, hess, flag=None, out=None):
+    """Fixed-point gradients and Hessians of one boosting round -> (qg, qh, expo, flag): int32 [n] each, expo int32 [2] = (e_g, e_h) with
+    e the largest integer that keeps max|.| 2^e below 2^30, and flag int32 [1], non-zero once a NaN or an infinity was seen (sticky: pass
+    the same tensor every round and read it when convenient).  out = (qg, qh, expo) to write into."""
+    grad = _check("grad", grad)
+    if grad.dim() != 1:
+        raise ValueError(f"grad must be flat [rows], got {tuple(grad.shape)}")
+    hess = _check("hess", hess, shape=grad.shape)
+    dev, n = grad.device, grad.numel()
+    flag = torch.zeros(1, device=dev, dtype=torch.int32) if flag is None else _check("flag", flag, torch.int32, (1,))
+    if out is None:
+        out = (torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.int32), torch.zeros(2, device=dev, dtype=torch.int32))
+    qg, qh = (_check(k, t, torch.int32, (n,)) for k, t in zip(("qg", "qh"), out[:2]))
+    expo = _check("expo", out[2], torch.int32, (2,))
+    state = torch.empty(2, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_quantize", _lib.ptr(grad), _lib.ptr(hess), n, _lib.ptr(qg), _lib.ptr(qh), _lib.ptr(expo), _lib.ptr(flag), _lib.ptr(state),
+                  _lib.current_stream(dev))
+    return qg, qh, expo, flag
+
+
+def gbdt_histogram(bins, qg, qh, rows, F, max_bin, hist=None, m=None):
+    """ADDS the rows of `rows` (int32 [m]; None: the first m rows, all by default) into hist, int64 [F, max_bin, 3] = (sum qg, sum qh,
+    count) per (feature, bin); hist=None starts from zeros.  Integer sums: the bits do not depend on the row order or the launch form."""
+    bins = _gbdt_bins(bins, F)
+    n, dev = bins.shape[0], bins.device
+    max_bin = _gbdt_max_bin(max_bin)
+    qg, qh = _check("qg", qg, torch.int32, (n,)), _check("qh", qh, torch.int32, (n,))
+    if rows is not None:
+        rows = _check("rows", rows, torch.int32)
+        if rows.dim() != 1:
+            raise ValueError(f"rows must be flat, got {tuple(rows.shape)}")
+    m = (n if rows is None else rows.numel()) if m is None else int(m)
+    if m < 0 or m > (n if rows is None else rows.numel()):
+        raise ValueError(f"m={m} exceeds the row list")
+    hist = torch.zeros((F, max_bin, 3), device=dev, dtype=torch.int64) if hist is None else _check("hist", hist, torch.int64, (F, max_bin, 3))
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_histogram", _lib.ptr(bins), bins.shape[1], n, _lib.ptr(qg), _lib.ptr(qh), _lib.ptr(rows), m, F, max_bin, _lib.ptr(hist),
+                  _lib.current_stream(dev))
+    return hist
+
+
+def gbdt_hist_sub(parent, child, out=None):
+    """parent - child over one histogram (the larger child from the smaller, exactly); out may be `parent` itself."""
+    parent = _check("parent", parent, torch.int64)
+    if parent.dim() != 3 or parent.shape[2] != 3:
+        raise ValueError(f"a histogram is [F, max_bin, 3], got {tuple(parent.shape)}")
+    child = _check("child", child, torch.int64, parent.shape)
+    out = torch.empty_like(parent) if out is None else _check("out", out, torch.int64, parent.shape)
+    with torch.cuda.device(parent.device):
+        _lib.call("ptr_gbdt_hist_sub", _lib.ptr(parent), _lib.ptr(child), parent.shape[0], _gbdt_max_bin(parent.shape[1]), _lib.ptr(out),
+                  _lib.current_stream(parent.device))
+    return out
+
+
+def gbdt_best_split(hist, nbins, expo, lambda_l2=0.0, min_data_in_leaf=1, min_sum_hessian_in_leaf=1e-3, min_gain_to_split=0.0, out=None):
+    """The best split of every leaf histogram of a batch -> int64 [leaves, 9] records (GBDT_RECORD; record[0] is the float64 gain's bit
+    pattern: .view(torch.float64), -inf without a valid split).  hist int64 [leaves, F, max_bin, 3] (or one [F, max_bin, 3]); nbins int32
+    [F]; expo as gbdt_quantize returned it.  float64, ties to the lowest feature, then the lowest bin."""
+    hist = _check("hist", hist, torch.int64)
+    if hist.dim() == 3:
+        hist = hist[None]
+    if hist.dim() != 4 or hist.shape[3] != 3:
+        raise ValueError(f"hist must be [leaves, F, max_bin, 3], got {tuple(hist.shape)}")
+    L, F, max_bin = hist.shape[0], hist.shape[1], _gbdt_max_bin(hist.shape[2])
+    nbins = _check("nbins", nbins, torch.int32, (F,))
+    expo = _check("expo", expo, torch.int32, (2,))
+    dev = hist.device
+    rec = torch.empty((L, 9), device=dev, dtype=torch.int64) if out is None else _check("out", out, torch.int64, (L, 9))
+    ws = torch.empty((max(L * F, 1), 9), device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_best_split", _lib.ptr(hist), L, F, max_bin, _lib.ptr(nbins), _lib.ptr(expo), C.c_double(float(lambda_l2)),
+                  C.c_int64(int(min_data_in_leaf)), C.c_double(float(min_sum_hessian_in_leaf)), C.c_double(float(min_gain_to_split)), _lib.ptr(ws),
+                  _lib.ptr(rec), _lib.current_stream(dev))
+    return rec
+
+
+def gbdt_partition(bins, rows, feature, bin, F, out=None, left_count=None):
+    """Stable partition of a row list by bins[row, feature] <= bin -> (out int32 [m]: the left rows in their order, then the right rows in
+    theirs; left_count int32 [1] on the device)."""
+    bins = _gbdt_bins(bins, F)
+    dev = bins.device
+    rows = _check("rows", rows, torch.int32)
+    if rows.dim() != 1:
+        raise ValueError(f"rows must be flat, got {tuple(rows.shape)}")
+    m = rows.numel()
+    out = torch.empty_like(rows) if out is None else _check("out", out, torch.int32, (m,))
+    left_count = torch.empty(1, device=dev, dtype=torch.int32) if left_count is None else _check("left_count", left_count, torch.int32, (1,))
+    ws = torch.empty(int(_lib.query("ptr_gbdt_partition_ws_ints", m)), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_partition", _lib.ptr(bins), bins.shape[1], bins.shape[0], F, _lib.ptr(rows), m, int(feature), int(bin), _lib.ptr(out),
+                  _lib.ptr(left_count), _lib.ptr(ws), _lib.current_stream(dev))
+    return out, left_count
+
+
+def gbdt_add_leaf_values(scores, rows, offsets, values):
+    """scores[rows[i]] += values[l] for offsets[l] <= i < offsets[l + 1], in place: all leaves of a finished tree in one launch.  scores
+    float32 [n], rows int32 (the leaves' row lists, concatenated), offsets int32 [leaves + 1], values float32 [leaves]."""
+    scores = _check("scores", scores)
+    rows = _check("rows", rows, torch.int32)
+    values = _check("values", values)
+    offsets = _check("offsets", offsets, torch.int32, (values.numel() + 1,))
+    if not scores.is_contiguous() or scores.dim() != 1 or rows.dim() != 1:
+        raise ValueError("scores and rows must be flat and contiguous")
+    with torch.cuda.device(scores.device):
+        _lib.call("ptr_gbdt_add_leaf_values", _lib.ptr(scores), scores.numel(), _lib.ptr(rows), _lib.ptr(offsets), _lib.ptr(values), values.numel(),
+                  rows.numel(), _lib.current_stream(scores.device))
+    return scores
+
+
+def gbdt_predict(X, feature, threshold, left, right, value, tree_offsets, ntrees=None):
+    """Scores of raw rows under flat tree arrays -> float32 [n]: per tree the row goes left on x <= threshold; a negative child is leaf ~i;
+    tree t owns the nodes tree_offsets[t] .. tree_offsets[t + 1] and the values value[tree_offsets[t] + t ..].  The leaf values are summed
+    in tree order in fp32.  ntrees: only the first trees."""
+    X = _check("X", X)
+    if X.dim() != 2:
+        raise ValueError(f"X must be [rows, features], got {tuple(X.shape)}")
+    dev = X.device
+    tree_offsets = _check("tree_offsets", tree_offsets, torch.int32)
+    total = tree_offsets.numel() - 1
+    ntrees = total if ntrees is None else int(ntrees)
+    if not 0 <= ntrees <= total:
+        raise ValueError(f"ntrees={ntrees} outside 0 .. {total}")
+    nodes = feature.numel()
+    feature, left, right = (_check(k, t, torch.int32, (nodes,)) for k, t in zip(("feature", "left", "right"), (feature, left, right)))
+    threshold = _check("threshold", threshold, shape=(nodes,))
+    value = _check("value", value, shape=(nodes + total,))
+    out = torch.empty(X.shape[0], device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_predict", _lib.ptr(X), X.shape[0], X.shape[1], _lib.ptr(feature), _lib.ptr(threshold), _lib.ptr(left), _lib.ptr(right),
+                  _lib.ptr(value), _lib.ptr(tree_offsets), ntrees, _lib.ptr(out), _lib.current_stream(dev))
     return out

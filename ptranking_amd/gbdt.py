@@ -1,0 +1,410 @@
+"""A native LambdaMART: a histogram gradient-boosted tree trainer on the GPU (csrc/gbdt.hip) under the tree frame's objectives (csrc/tree.hip).
+
+The reference's tree frame (ptranking/ltr_tree/lambdamart/lightgbm_lambdaMART.py) parses files, hands the boosting to LightGBM and predicts the
+test set.  LightGBM is not installed where this package is developed or tested, so nothing here is compared with it, and no parity is
+claimed: the binning rule, the tie rules and the model file are this project's own.
+
+    GBDT(params)        the booster: fit_bins(X) bins the features once and keeps them resident; update(grad, hess) grows ONE tree leaf-wise
+                        from device gradients and adds its leaf values to the resident training scores; predict / save_model / load_model
+    LambdaMART(params)  the ranker: every round computes the gradient and the Hessian per document with tree_pair_grad_hess /
+                        tree_listnet_grad_hess on the resident scores (no host copy), quantizes them and calls update
+
+Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here: GOSS, EFB,
+categorical features, missing values (a non-finite feature raises), DART, monotone constraints.  There is no CPU path.
+"""
+import json
+
+import numpy as np
+import torch
+
+from . import functional as F
+from . import letor, tree
+
+__all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS"]
+
+# LightGBM's names, so the reference's lightgbm_para_dict passes through.  min_sum_hessian_in_leaf = 1e-3 is LightGBM's default too; the
+# reference's own dict sets 200, which suits LightGBM's built-in lambdarank Hessians, not the sums of tree.hip.
+DEFAULT_PARAMS = {"learning_rate": 0.1, "num_leaves": 31, "num_trees": 100, "min_data_in_leaf": 20, "min_sum_hessian_in_leaf": 1e-3,
+                  "lambda_l2": 0.0, "min_gain_to_split": 0.0, "max_bin": 255, "max_depth": -1}
+IGNORED_PARAMS = ("num_threads", "verbosity", "metric", "boosting_type", "objective", "eval_at")    # accepted, without a meaning here
+MODEL_FORMAT = 1
+
+
+def _params(params):
+    p = dict(DEFAULT_PARAMS)
+    for k, v in (params or {}).items():
+        if k == "boosting_type" and v != "gbdt":
+            raise ValueError(f"boosting_type {v!r} is not implemented: only 'gbdt'")
+        if k in IGNORED_PARAMS:
+            continue
+        if k not in DEFAULT_PARAMS:
+            raise ValueError(f"unknown parameter {k!r} (known: {', '.join(DEFAULT_PARAMS)}; ignored: {', '.join(IGNORED_PARAMS)})")
+        p[k] = v
+    p["max_depth"] = -1 if p["max_depth"] is None else int(p["max_depth"])
+    for k in ("num_leaves", "num_trees", "min_data_in_leaf", "max_bin"):
+        p[k] = int(p[k])
+    for k in ("learning_rate", "min_sum_hessian_in_leaf", "lambda_l2", "min_gain_to_split"):
+        p[k] = float(p[k])
+    if not p["learning_rate"] > 0.0:
+        raise ValueError(f"learning_rate must be > 0, got {p['learning_rate']}")
+    if p["num_leaves"] < 1 or p["num_trees"] < 0 or p["min_data_in_leaf"] < 0:
+        raise ValueError("num_leaves must be >= 1, num_trees and min_data_in_leaf >= 0")
+    if not 2 <= p["max_bin"] <= F.GBDT_MAX_BIN:
+        raise ValueError(f"max_bin must be in 2 .. {F.GBDT_MAX_BIN}, got {p['max_bin']}")
+    if not p["lambda_l2"] >= 0.0 or p["min_sum_hessian_in_leaf"] != p["min_sum_hessian_in_leaf"] or p["min_gain_to_split"] != p["min_gain_to_split"]:
+        raise ValueError("lambda_l2 must be >= 0 and no threshold may be NaN")
+    return p
+
+
+def _midpoints(lo, hi):
+    """An fp32 edge e with lo <= e < hi for adjacent distinct fp32 values: the midpoint, or lo where the midpoint rounds up to hi."""
+    mid = ((lo.astype(np.float64) + hi.astype(np.float64)) * 0.5).astype(np.float32)
+    return np.where(mid >= hi, lo, mid)
+
+
+def bin_edges(X, max_bin):
+    """The binning rule, on the host, once per dataset -> (edges float32 [F, max_bin - 1], padded with +inf; nbins int32 [F]).
+    Per feature: at most max_bin distinct values give one bin per value, the edges at the midpoints (binning is then lossless).  Otherwise
+    the k-th edge (k = 1 .. max_bin - 1) follows the first distinct value whose cumulative row count reaches k n / max_bin, again at the
+    midpoint to the next distinct value; edges that coincide are kept once.  Deterministic: no subsampling."""
+    X = np.asarray(X, dtype=np.float32)
+    if X.ndim != 2:
+        raise ValueError(f"X must be [rows, features], got {X.shape}")
+    if not np.isfinite(X).all():
+        raise ValueError("X holds a NaN or an infinity: missing values are not handled, impute them first")
+    n, nf = X.shape
+    edges = np.full((nf, max_bin - 1), np.inf, np.float32)
+    nbins = np.ones(nf, np.int32)
+    for f in range(nf):
+        vals, counts = np.unique(X[:, f], return_counts=True)
+        if vals.size <= 1:
+            continue
+        if vals.size <= max_bin:
+            cut = np.arange(vals.size - 1)
+        else:
+            cum = np.cumsum(counts)
+            cut = np.unique(np.searchsorted(cum, np.arange(1, max_bin) * (n / max_bin), side="left"))
+            cut = cut[cut < vals.size - 1]
+        e = _midpoints(vals[cut], vals[cut + 1])
+        edges[f, :e.size] = e
+        nbins[f] = e.size + 1
+    return edges, nbins
+
+
+def leaf_value(g_sum, h_sum, expo, lambda_l2, learning_rate):
+    """-G / (H + lambda_l2) * learning_rate in float64 from the integer sums, rounded to fp32; 0 where H + lambda_l2 is not positive (only a
+    tree that never split can get there: the split scan's Hessian floor keeps every child positive)."""
+    G, H = np.ldexp(float(g_sum), -int(expo[0])), np.ldexp(float(h_sum), -int(expo[1]))
+    return np.float32(-G / (H + lambda_l2) * learning_rate) if H + lambda_l2 > 0.0 else np.float32(0.0)
+
+
+class _Leaf:
+    __slots__ = ("start", "count", "depth", "slot", "parent", "side", "g", "h", "rec")
+
+    def __init__(self, start, count, depth, slot, parent, side, g, h, rec):
+        self.start, self.count, self.depth, self.slot, self.parent, self.side, self.g, self.h, self.rec = start, count, depth, slot, parent, side, g, h, rec
+
+
+def _record(r):
+    """A split record as the host reads it: (gain float, feature, bin, left (g, h, count), right (g, h, count))."""
+    r = np.asarray(r, np.int64)
+    return float(r[:1].view(np.float64)[0]), int(r[1]), int(r[2]), tuple(int(v) for v in r[3:6]), tuple(int(v) for v in r[6:9])
+
+
+_NO_SPLIT = (-np.inf, -1, -1, (0, 0, 0), (0, 0, 0))
+
+
+class GBDT:
+    """The booster.  GBDT(params, X=None): params under LightGBM's names (DEFAULT_PARAMS; the keys of IGNORED_PARAMS are accepted and
+    ignored; boosting_type other than 'gbdt' raises).  update() costs one host synchronisation per split: the host reads the two children's
+    records (72 bytes each) to pick the next leaf."""
+
+    def __init__(self, params=None, X=None, device=None):
+        self.params = _params(params)
+        self.trees = []                    # per tree: dict(feature, threshold, left, right, value) of numpy arrays
+        self.edges = self.nbins = None     # host copies (the model file carries them)
+        self.best_iteration = None
+        self._device = device
+        self._flat = None
+        self.n = 0
+        if X is not None:
+            self.fit_bins(X)
+
+    # ---- data
+    def _dev(self):
+        if not torch.cuda.is_available():
+            raise RuntimeError("GBDT needs a GPU: ptranking_amd runs on the MI355X HIP path only (no CPU fallback)")
+        return torch.device("cuda" if self._device is None else self._device)
+
+    def fit_bins(self, X):
+        """Computes the bin edges of X (numpy array or device tensor [n, F]) on the host, bins X on the device and keeps the bins, the
+        training scores (zeros) and the work buffers resident."""
+        dev = self._dev()
+        host = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
+        host = np.ascontiguousarray(host, dtype=np.float32)
+        p = self.params
+        self.edges, self.nbins = bin_edges(host, p["max_bin"])
+        Xd = X.detach().to(dev, torch.float32).contiguous() if isinstance(X, torch.Tensor) else torch.from_numpy(host).to(dev)
+        self.n, self.F = host.shape
+        self._edges_d, self._nbins_d = torch.from_numpy(self.edges).to(dev), torch.from_numpy(self.nbins).to(dev)
+        self.bins = F.gbdt_bin(Xd, self._edges_d, self._nbins_d)
+        n = self.n
+        self.scores = torch.zeros(n, device=dev, dtype=torch.float32)
+        self._arange = torch.arange(n, device=dev, dtype=torch.int32)
+        self._rows, self._tmp = torch.empty_like(self._arange), torch.empty_like(self._arange)
+        self._qg, self._qh = torch.empty_like(self._arange), torch.empty_like(self._arange)
+        self._expo = torch.zeros(2, device=dev, dtype=torch.int32)
+        self._flag = torch.zeros(1, device=dev, dtype=torch.int32)
+        self._lc = torch.zeros(1, device=dev, dtype=torch.int32)
+        self._rec = torch.zeros((2, 9), device=dev, dtype=torch.int64)
+        self._pool = torch.zeros((max(p["num_leaves"], 1), self.F, p["max_bin"], 3), device=dev, dtype=torch.int64)
+        return self
+
+    # ---- one boosting round
+    def _search(self, slot, out_row):
+        p = self.params
+        F.gbdt_best_split(self._pool[slot:slot + 1], self._nbins_d, self._expo, p["lambda_l2"], p["min_data_in_leaf"], p["min_sum_hessian_in_leaf"],
+                          p["min_gain_to_split"], out=self._rec[out_row:out_row + 1])
+
+    def _splittable(self, count, depth):
+        p = self.params
+        return count >= 2 * max(p["min_data_in_leaf"], 1) and (p["max_depth"] <= 0 or depth < p["max_depth"])
+
+    def update(self, grad, hess):
+        """Grows one tree from device fp32 gradients and Hessians [n]: the leaf with the largest gain is split (ties: the older leaf) until
+        num_leaves is reached or no leaf has a valid split; the leaf values -G / (H + lambda_l2) * learning_rate are added to the resident
+        training scores.  Returns the tree (a dict of numpy arrays).  A NaN or an infinity in grad / hess raises."""
+        if self.n == 0 or self.edges is None:
+            raise RuntimeError("call fit_bins(X) first")
+        p, nf, mb = self.params, self.F, self.params["max_bin"]
+        F.gbdt_quantize(grad, hess, flag=self._flag, out=(self._qg, self._qh, self._expo))
+        pool = self._pool
+        pool[0].zero_()
+        F.gbdt_histogram(self.bins, self._qg, self._qh, None, nf, mb, hist=pool[0])
+        self._search(0, 0)
+        head = torch.cat([self._rec[0], pool[0, 0].sum(0), self._expo.to(torch.int64), self._flag.to(torch.int64)]).cpu().numpy()
+        if head[14]:
+            self._flag.zero_()
+            raise FloatingPointError("the gradients or Hessians of this round hold a NaN or an infinity")
+        expo = (int(head[12]), int(head[13]))
+        root_rec = _record(head[:9]) if self._splittable(self.n, 0) else _NO_SPLIT
+        leaves = [_Leaf(0, self.n, 0, 0, -1, 0, int(head[9]), int(head[10]), root_rec)]
+        feature, threshold, left, right = [], [], [], []
+        self._rows.copy_(self._arange)
+        free = 1                                                       # the next unused histogram slot
+        while len(leaves) < p["num_leaves"]:
+            li = max(range(len(leaves)), key=lambda i: (leaves[i].rec[0], -i))
+            leaf = leaves[li]
+            gain, f, b, lsum, rsum = leaf.rec
+            if not gain > -np.inf:
+                break
+            s, m = leaf.start, leaf.count
+            F.gbdt_partition(self.bins, self._rows[s:s + m], f, b, nf, out=self._tmp[s:s + m], left_count=self._lc)
+            self._rows[s:s + m].copy_(self._tmp[s:s + m])
+            node = len(feature)
+            feature.append(f); threshold.append(self.edges[f, b]); left.append(~li); right.append(~len(leaves))
+            if leaf.parent >= 0:
+                (left if leaf.side == 0 else right)[leaf.parent] = node
+            lchild = _Leaf(s, lsum[2], leaf.depth + 1, leaf.slot, node, 0, lsum[0], lsum[1], _NO_SPLIT)
+            rchild = _Leaf(s + lsum[2], rsum[2], leaf.depth + 1, leaf.slot, node, 1, rsum[0], rsum[1], _NO_SPLIT)
+            leaves[li] = lchild
+            leaves.append(rchild)
+            can = [self._splittable(c.count, c.depth) for c in (lchild, rchild)]
+            if len(leaves) < p["num_leaves"] and any(can):
+                small, large = (lchild, rchild) if lchild.count <= rchild.count else (rchild, lchild)
+                small.slot, free = free, free + 1
+                pool[small.slot].zero_()
+                F.gbdt_histogram(self.bins, self._qg, self._qh, self._rows[small.start:small.start + small.count], nf, mb, hist=pool[small.slot])
+                F.gbdt_hist_sub(pool[large.slot], pool[small.slot], out=pool[large.slot])          # the larger child, in the parent's slot
+                for k, c in enumerate((lchild, rchild)):
+                    if can[k]:
+                        self._search(c.slot, k)
+                recs = self._rec.cpu().numpy()                           # the one synchronisation of this split
+                for k, c in enumerate((lchild, rchild)):
+                    if can[k]:
+                        c.rec = _record(recs[k])
+        value = np.array([leaf_value(c.g, c.h, expo, p["lambda_l2"], p["learning_rate"]) for c in leaves], np.float32)
+        order = sorted(range(len(leaves)), key=lambda i: leaves[i].start)
+        offsets = np.array([leaves[i].start for i in order] + [self.n], np.int32)
+        dev = self.scores.device
+        F.gbdt_add_leaf_values(self.scores, self._rows, torch.from_numpy(offsets).to(dev), torch.from_numpy(value[order]).to(dev))
+        t = {"feature": np.array(feature, np.int32), "threshold": np.array(threshold, np.float32), "left": np.array(left, np.int32),
+             "right": np.array(right, np.int32), "value": value}
+        self.trees.append(t)
+        self._flat = None
+        return t
+
+    # ---- the model
+    def flat(self):
+        """The flat tree arrays ptr_gbdt_predict reads (numpy): feature, threshold, left, right, value, tree_offsets."""
+        cat = lambda k, dt: np.concatenate([t[k] for t in self.trees]).astype(dt) if self.trees else np.zeros(0, dt)
+        offs = np.concatenate([[0], np.cumsum([t["feature"].size for t in self.trees])]).astype(np.int32)
+        return {"feature": cat("feature", np.int32), "threshold": cat("threshold", np.float32), "left": cat("left", np.int32),
+                "right": cat("right", np.int32), "value": cat("value", np.float32), "tree_offsets": offs}
+
+    def predict(self, X, num_iteration=None, first_tree=0):
+        """Scores of raw rows X (numpy array or device tensor [n, F]) -> device float32 [n]: the trees first_tree .. num_iteration - 1
+        (default: up to best_iteration when early stopping set it, else all), summed in tree order in fp32 — for a training row the bits of
+        its resident training score."""
+        dev = self._dev()
+        if self._flat is None:
+            self._flat = {k: torch.from_numpy(v).to(dev) for k, v in self.flat().items()}
+        fl = self._flat
+        stop = (self.best_iteration or len(self.trees)) if num_iteration is None else int(num_iteration)
+        if not 0 <= first_tree <= stop <= len(self.trees):
+            raise ValueError(f"trees {first_tree} .. {stop} of {len(self.trees)}")
+        Xd = X.detach().to(dev, torch.float32) if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
+        if first_tree == 0:
+            return F.gbdt_predict(Xd, fl["feature"], fl["threshold"], fl["left"], fl["right"], fl["value"], fl["tree_offsets"], stop)
+        host = self.flat()
+        lo, hi = int(host["tree_offsets"][first_tree]), int(host["tree_offsets"][stop])
+        sub = {k: torch.from_numpy(np.ascontiguousarray(host[k][lo:hi])).to(dev) for k in ("feature", "threshold", "left", "right")}
+        val = torch.from_numpy(np.ascontiguousarray(host["value"][lo + first_tree:hi + stop])).to(dev)
+        offs = torch.from_numpy((host["tree_offsets"][first_tree:stop + 1] - lo).astype(np.int32)).to(dev)
+        return F.gbdt_predict(Xd, sub["feature"], sub["threshold"], sub["left"], sub["right"], val, offs)
+
+    def save_model(self, path):
+        """An .npz of this project's own (not LightGBM's text format): the flat tree arrays, the bin edges, the parameters."""
+        with open(path, "wb") as fh:
+            np.savez(fh, format=np.int64(MODEL_FORMAT), params=np.array(json.dumps(self.params)), edges=self.edges, nbins=self.nbins,
+                     best_iteration=np.int64(self.best_iteration or 0), **self.flat())
+
+    @classmethod
+    def load_model(cls, path, device=None):
+        """The booster save_model wrote; it predicts the same bits.  (The binned training data are not part of a model.)"""
+        with np.load(path, allow_pickle=False) as z:
+            if int(z["format"]) != MODEL_FORMAT:
+                raise ValueError(f"{path}: model format {int(z['format'])}, this version reads {MODEL_FORMAT}")
+            self = cls(json.loads(str(z["params"])), device=device)
+            self.edges, self.nbins = z["edges"], z["nbins"]
+            self.best_iteration = int(z["best_iteration"]) or None
+            offs = z["tree_offsets"]
+            for t in range(offs.size - 1):
+                lo, hi = int(offs[t]), int(offs[t + 1])
+                self.trees.append({"feature": z["feature"][lo:hi], "threshold": z["threshold"][lo:hi], "left": z["left"][lo:hi],
+                                   "right": z["right"][lo:hi], "value": z["value"][lo + t:hi + t + 1]})
+        return self
+
+
+class LambdaMART:
+    """LambdaMART on the native booster.  objective 'lambdarank' (pair_type 'NoTies'), 'ranknet' ('All') or 'listnet', as tree.OBJECTIVES.
+    The defaults are real LambdaMART: weighting='DeltaNDCG' (applied to 'lambdarank'; 'ranknet' is the unweighted pairwise loss) and the
+    never-negative hessian='sum'.  hessian='reference' (the reference's rank-signed Hessian) is accepted, but its sums are negative for
+    low-ranked documents, so leaves can stay unsplittable under the Hessian floor of the split scan."""
+
+    def __init__(self, params=None, objective="lambdarank", weighting="DeltaNDCG", hessian="sum", pair_type=None, epsilon=1.0,
+                 gain_type="Power", device=None):
+        if objective not in tree.OBJECTIVES:
+            raise ValueError(f"objective {objective!r} (supported: {', '.join(map(repr, tree.OBJECTIVES))})")
+        self.params = _params(params)
+        self.objective = objective
+        self.kind, default_pairs = tree.OBJECTIVES[objective]
+        self.pair_type = default_pairs if pair_type is None else pair_type
+        self.weighting = weighting if objective == "lambdarank" else None
+        self.epsilon, self.hessian, self.gain_type = float(epsilon), hessian, gain_type
+        if self.kind == "pair":
+            F._enum("pair_type", self.pair_type, F.TREE_PAIR_TYPES)
+            F._enum("weighting", self.weighting, F.TREE_WEIGHTINGS)
+        else:
+            F._enum("gain_type", gain_type, F.TREE_GAIN_TYPES)
+        F._enum("hessian", hessian, F.TREE_HESSIANS)
+        if not torch.cuda.is_available():
+            raise RuntimeError("LambdaMART needs a GPU: ptranking_amd runs on the MI355X HIP path only (no CPU fallback)")
+        self.device = torch.device("cuda" if device is None else device)
+        self.booster = None
+        self.evals_result = []
+        self.best_iteration = self.best_score = None
+
+    def grad_hess(self, scores, res, out=None):
+        """The round's gradient and Hessian per document, on the device: one launch per length class of tree.bucket_queries, exactly as
+        TreeObjective._run launches them."""
+        out = (torch.empty_like(scores), torch.empty_like(scores)) if out is None else out
+        for max_len, queries in res.buckets:
+            if self.kind == "pair":
+                F.tree_pair_grad_hess(scores, res.labels, res.offsets, self.pair_type, self.weighting, self.epsilon, self.hessian, queries, max_len, out)
+            else:
+                F.tree_listnet_grad_hess(scores, res.labels, res.offsets, self.gain_type, self.hessian, queries, max_len, out)
+        return out
+
+    @staticmethod
+    def padded_index(group, device):
+        """(index int64 [Q, Lmax] into the flat documents, clamped; lens int32 [Q]) for gathering ragged scores into a padded batch."""
+        g = np.asarray(group).reshape(-1).astype(np.int64)
+        start = np.concatenate([[0], np.cumsum(g)])[:-1]
+        lmax = max(int(g.max()) if g.size else 1, 1)
+        idx = start[:, None] + np.minimum(np.arange(lmax)[None, :], np.maximum(g - 1, 0)[:, None])
+        idx = np.minimum(idx, max(int(g.sum()) - 1, 0))
+        return torch.from_numpy(idx).to(device), torch.from_numpy(g.astype(np.int32)).to(device)
+
+    @classmethod
+    def ndcg_at(cls, scores, labels, group, k=5, index=None):
+        """Mean nDCG@k over the queries that hold a relevant document, from flat device scores and labels: functional.metrics_at_ks on the
+        padded gather."""
+        idx, lens = cls.padded_index(group, scores.device) if index is None else index
+        lab = labels[idx]
+        nd = F.metrics_at_ks(scores[idx].contiguous(), lab.contiguous(), [int(k)], lens=lens, which=("ndcg",))["ndcg"][:, 0]
+        pos = torch.arange(idx.shape[1], device=idx.device)[None, :] < lens[:, None]
+        keep = ((lab > 0) & pos).any(dim=1)
+        return float(nd[keep].mean()) if bool(keep.any()) else 0.0
+
+    def fit(self, X, y, group, eval_set=None, eval_group=None, eval_at=5, early_stopping_rounds=None, num_boost_round=None, verbose=0):
+        """X [n, F], y [n] relevance grades, group: documents per query.  eval_set = (X_valid, y_valid) with eval_group: nDCG@eval_at on it
+        after every round (evals_result); early_stopping_rounds: stop after that many rounds without improvement and let predict use the
+        best round (best_iteration), as LightGBM does."""
+        res = tree._Resident(y, group, self.device)
+        X = X if isinstance(X, torch.Tensor) else np.asarray(X)
+        if X.shape[0] != res.n_docs:
+            raise ValueError(f"X holds {X.shape[0]} rows, the groups {res.n_docs}")
+        self.booster = GBDT(self.params, X, device=self.device)
+        self.evals_result, self.best_iteration, self.best_score = [], None, None
+        rounds = self.params["num_trees"] if num_boost_round is None else int(num_boost_round)
+        valid = None
+        if eval_set is not None:
+            Xv, yv = eval_set
+            if eval_group is None:
+                raise ValueError("eval_set needs eval_group")
+            Xv = Xv.detach().to(self.device, torch.float32) if isinstance(Xv, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(Xv, dtype=np.float32)).to(self.device)
+            yv = torch.from_numpy(np.ascontiguousarray(np.asarray(yv).reshape(-1), dtype=np.float32)).to(self.device)
+            valid = (Xv, yv, self.padded_index(eval_group, self.device), torch.zeros(Xv.shape[0], device=self.device, dtype=torch.float32))
+        elif early_stopping_rounds is not None:
+            raise ValueError("early_stopping_rounds needs an eval_set")
+        gh = (torch.empty_like(self.booster.scores), torch.empty_like(self.booster.scores))
+        for it in range(1, rounds + 1):
+            self.grad_hess(self.booster.scores, res, gh)
+            self.booster.update(*gh)
+            if valid is None:
+                continue
+            Xv, yv, index, sv = valid
+            sv += self.booster.predict(Xv, num_iteration=it, first_tree=it - 1)       # the new tree alone: the same fp32 sum, in tree order
+            score = self.ndcg_at(sv, yv, None, eval_at, index=index)
+            self.evals_result.append(score)
+            if self.best_score is None or score > self.best_score:
+                self.best_score, self.best_iteration = score, it
+            if verbose and it % verbose == 0:
+                print(f"[{it}] valid nDCG@{eval_at} {score:.4f}", flush=True)
+            if early_stopping_rounds is not None and it - self.best_iteration >= early_stopping_rounds:
+                break
+        if early_stopping_rounds is None:
+            self.best_iteration = None
+        self.booster.best_iteration = self.best_iteration
+        return self
+
+    def predict(self, X, num_iteration=None):
+        if self.booster is None:
+            raise RuntimeError("fit() first")
+        return self.booster.predict(X, num_iteration)
+
+    def run_letor(self, file_train, file_vali=None, file_test=None, eval_at=5, early_stopping_rounds=None, **loader_kwargs):
+        """The shape of the reference's LightGBMLambdaMART.run() on this project's LETOR parser: trains on file_train (validating on file_vali
+        when given) and predicts file_test (file_train when absent) -> (y_test, group_test, y_pred) as numpy arrays."""
+        def load(path):
+            qs = letor.load_letor_queries(path, **loader_kwargs)
+            return (np.concatenate([x for _, x, _ in qs]), np.concatenate([lab for _, _, lab in qs]), np.array([lab.size for _, _, lab in qs], np.int64))
+        xt, yt, gt = load(file_train)
+        ev = load(file_vali) if file_vali else None
+        self.fit(xt, yt, gt, eval_set=None if ev is None else (ev[0], ev[1]), eval_group=None if ev is None else ev[2], eval_at=eval_at,
+                 early_stopping_rounds=early_stopping_rounds if ev is not None else None)
+        xs, ys, gs = load(file_test) if file_test else (xt, yt, gt)
+        if xs.shape[1] != xt.shape[1]:
+            raise ValueError(f"{file_test} has {xs.shape[1]} features, {file_train} {xt.shape[1]}")
+        return ys, gs, self.predict(xs).cpu().numpy()

@@ -1,0 +1,335 @@
+"""CPU: the gradient-boosted tree entry points are declared, exported and bound; every argument error fires before a launch; the Python
+surface refuses to run without a GPU; the numpy restatement (tests/gbdt_ref.py) that the GPU tests compare against is right, and one
+planted fault per component makes its comparison fail.  No LightGBM comparison exists: the library is not installed where this runs."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import gbdt_ref as R
+from launch_form import launch_form
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRY_POINTS = ("ptr_gbdt_bin", "ptr_gbdt_quantize", "ptr_gbdt_histogram", "ptr_gbdt_hist_sub", "ptr_gbdt_best_split", "ptr_gbdt_partition_ws_ints",
+                "ptr_gbdt_partition", "ptr_gbdt_add_leaf_values", "ptr_gbdt_predict")
+WRAPPERS = ("gbdt_bin", "gbdt_quantize", "gbdt_histogram", "gbdt_hist_sub", "gbdt_best_split", "gbdt_partition", "gbdt_add_leaf_values", "gbdt_predict")
+# the reference's default dict, ptranking/ltr_tree/lambdamart/lightgbm_lambdaMART.py:173-185
+REFERENCE_PARAMS = {"boosting_type": "gbdt", "objective": "lambdarank", "metric": "ndcg", "learning_rate": 0.05, "num_leaves": 400, "num_trees": 1000,
+                    "num_threads": 16, "min_data_in_leaf": 50, "min_sum_hessian_in_leaf": 200, "eval_at": 5, "verbosity": -1}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from ptranking_amd import _lib, build
+    build.build()
+    return _lib.load()
+
+
+def test_symbols_are_declared_exported_and_bound(lib):
+    from ptranking_amd import _lib, build
+    import ptranking_amd as pa
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ptranking_amd.h")).read(), flags=re.S)
+    for name in ENTRY_POINTS:
+        proto = re.search(name + r"\s*\(([^)]*)\)", hdr).group(1)
+        assert proto.count(",") + 1 == len(_lib.SIGNATURES[name]), name
+        assert hasattr(lib, name)
+    assert int(re.search(r"#define PTR_ABI_VERSION (\d+)", hdr).group(1)) == 8 == _lib.ABI_VERSION == lib.ptr_abi_version()
+    assert "gbdt.hip" in build.SOURCES and os.path.isfile(os.path.join(build.CSRC, "gbdt.hip"))
+    for name in WRAPPERS:
+        assert name in pa.functional.__all__ and callable(getattr(pa.functional, name)) and not name.endswith("_loss")
+    assert pa.GBDT is pa.gbdt.GBDT and pa.LambdaMART is pa.gbdt.LambdaMART
+
+
+def test_argument_errors_fire_before_any_launch(lib):
+    one, f64 = C.c_void_p(64), C.c_double
+
+    def err(rc, code, text):
+        assert rc == code and text in lib.ptr_last_error(), (rc, lib.ptr_last_error())
+
+    err(lib.ptr_gbdt_bin(None, 4, 3, one, one, 16, 16, one, None), 1001, b"NULL")
+    err(lib.ptr_gbdt_bin(one, 4, 3, one, one, 1, 16, one, None), 1001, b"max_bin")
+    err(lib.ptr_gbdt_bin(one, 4, 3, one, one, 257, 16, one, None), 1002, b"max_bin")
+    err(lib.ptr_gbdt_bin(one, -1, 3, one, one, 16, 16, one, None), 1001, b"size")
+    err(lib.ptr_gbdt_bin(one, 4, 3, one, one, 16, 12, one, None), 1001, b"stride")
+    err(lib.ptr_gbdt_bin(one, 4, 20, one, one, 16, 16, one, None), 1001, b"stride")
+    assert lib.ptr_gbdt_bin(None, 0, 3, None, None, 16, 16, None, None) == 0                   # empty: nothing to do
+
+    err(lib.ptr_gbdt_quantize(one, None, 4, one, one, one, one, one, None), 1001, b"NULL")
+    err(lib.ptr_gbdt_quantize(one, one, -4, one, one, one, one, one, None), 1001, b"negative")
+    assert lib.ptr_gbdt_quantize(None, None, 0, None, None, None, None, None, None) == 0
+
+    err(lib.ptr_gbdt_histogram(None, 16, 8, one, one, one, 4, 3, 16, one, None), 1001, b"NULL")
+    err(lib.ptr_gbdt_histogram(one, 16, 8, one, one, one, 4, 3, 16, None, None), 1001, b"NULL")
+    err(lib.ptr_gbdt_histogram(one, 16, 8, one, one, one, -1, 3, 16, one, None), 1001, b"row count")
+    err(lib.ptr_gbdt_histogram(one, 16, 8, one, one, None, 9, 3, 16, one, None), 1001, b"rows is NULL")
+    err(lib.ptr_gbdt_histogram(one, 16, 8, one, one, one, 4, 3, 1, one, None), 1001, b"max_bin")
+    err(lib.ptr_gbdt_histogram(one, 16, 8, one, one, one, 4, 3, 257, one, None), 1002, b"max_bin")
+    err(lib.ptr_gbdt_histogram(one, 8, 8, one, one, one, 4, 3, 16, one, None), 1001, b"stride")
+    err(lib.ptr_gbdt_histogram(C.c_void_p(72), 16, 8, one, one, one, 4, 3, 16, one, None), 1001, b"aligned")
+    assert lib.ptr_gbdt_histogram(None, 16, 8, None, None, None, 0, 3, 16, None, None) == 0
+
+    err(lib.ptr_gbdt_hist_sub(one, None, 3, 16, one, None), 1001, b"NULL")
+    err(lib.ptr_gbdt_hist_sub(one, one, -3, 16, one, None), 1001, b"negative")
+    err(lib.ptr_gbdt_hist_sub(one, one, 3, 1, one, None), 1001, b"max_bin")
+    err(lib.ptr_gbdt_hist_sub(one, one, 3, 257, one, None), 1002, b"max_bin")
+
+    args = (f64(0.0), C.c_int64(1), f64(1e-3), f64(0.0))
+    err(lib.ptr_gbdt_best_split(None, 2, 3, 16, one, one, *args, one, one, None), 1001, b"NULL")
+    err(lib.ptr_gbdt_best_split(one, 2, 3, 16, one, one, *args, one, None, None), 1001, b"NULL")
+    err(lib.ptr_gbdt_best_split(one, -2, 3, 16, one, one, *args, one, one, None), 1001, b"negative")
+    err(lib.ptr_gbdt_best_split(one, 2, 3, 1, one, one, *args, one, one, None), 1001, b"max_bin")
+    err(lib.ptr_gbdt_best_split(one, 2, 3, 257, one, one, *args, one, one, None), 1002, b"max_bin")
+    err(lib.ptr_gbdt_best_split(one, 2, 3, 16, one, one, f64(-1.0), C.c_int64(1), f64(1e-3), f64(0.0), one, one, None), 1001, b"lambda_l2")
+    err(lib.ptr_gbdt_best_split(one, 2, 3, 16, one, one, f64(0.0), C.c_int64(1), f64(float("nan")), f64(0.0), one, one, None), 1001, b"NaN")
+    assert lib.ptr_gbdt_best_split(None, 0, 3, 16, None, None, *args, None, None, None) == 0
+
+    err(lib.ptr_gbdt_partition(None, 16, 8, 3, one, 4, 0, 0, one, one, one, None), 1001, b"NULL")
+    err(lib.ptr_gbdt_partition(one, 16, 8, 3, one, 4, 0, 0, one, None, one, None), 1001, b"left_count")
+    err(lib.ptr_gbdt_partition(one, 16, 8, 3, one, -4, 0, 0, one, one, one, None), 1001, b"row count")
+    err(lib.ptr_gbdt_partition(one, 16, 8, 3, one, 4, 3, 0, one, one, one, None), 1001, b"feature")
+    err(lib.ptr_gbdt_partition(one, 16, 8, 3, one, 4, 0, 256, one, one, one, None), 1001, b"bin")
+    err(lib.ptr_gbdt_partition(one, 12, 8, 3, one, 4, 0, 0, one, one, one, None), 1001, b"stride")
+    assert lib.ptr_gbdt_partition_ws_ints(0) == 1 and lib.ptr_gbdt_partition_ws_ints(1024) == 2 and lib.ptr_gbdt_partition_ws_ints(1025) == 3
+
+    err(lib.ptr_gbdt_add_leaf_values(None, 8, one, one, one, 2, 8, None), 1001, b"NULL")
+    err(lib.ptr_gbdt_add_leaf_values(one, 8, one, one, one, -2, 8, None), 1001, b"size")
+    err(lib.ptr_gbdt_add_leaf_values(one, 8, one, one, one, 2, -8, None), 1001, b"size")
+    assert lib.ptr_gbdt_add_leaf_values(None, 8, None, None, None, 0, 8, None) == 0
+
+    err(lib.ptr_gbdt_predict(None, 4, 3, one, one, one, one, one, one, 1, one, None), 1001, b"NULL")
+    err(lib.ptr_gbdt_predict(one, 4, 3, None, one, one, one, one, one, 1, one, None), 1001, b"NULL tree")
+    err(lib.ptr_gbdt_predict(one, -4, 3, one, one, one, one, one, one, 1, one, None), 1001, b"negative")
+    err(lib.ptr_gbdt_predict(one, 4, 3, one, one, one, one, one, one, -1, one, None), 1001, b"negative")
+    assert lib.ptr_gbdt_predict(None, 0, 3, None, None, None, None, None, None, 0, None, None) == 0
+
+    a, out = (C.c_int64 * 3)(1000, 136, 255), (C.c_int32 * 8)()
+    assert lib.ptr_launch_form(b"ptr_gbdt_histogram", a, 2, out, 8) == 1001 and b"takes 3" in lib.ptr_last_error()
+    assert lib.ptr_launch_form(b"ptr_gbdt_histogram", a, 3, out, 4) == 1001
+
+
+def test_histogram_launch_forms_by_shape(lib):
+    assert launch_form("ptr_gbdt_histogram", 0, 136, 255)[0] == 0
+    assert launch_form("ptr_gbdt_histogram", 256, 136, 255)[:3] == (1, 16, 9)
+    kind, tile, tiles, chunks, lds = launch_form("ptr_gbdt_histogram", 257, 136, 255)[:5]
+    assert (kind, tile, tiles, chunks, lds) == (2, 16, 9, 1, 16 * 255 * 20)
+    assert launch_form("ptr_gbdt_histogram", 70000, 17, 256)[:5] == (2, 16, 2, 35, 16 * 256 * 20) and 16 * 256 * 20 <= 160 * 1024
+    assert launch_form("ptr_gbdt_histogram", 2_280_000, 136, 255)[3] == 1024 // 9
+    assert launch_form("ptr_gbdt_histogram", 500_000, 700, 256)[2:4] == (44, 23)
+
+
+def test_python_surface_refuses_to_run_without_a_gpu():
+    import ptranking_amd as pa
+    Fn = pa.functional
+    f32, i32, u8, i64 = (lambda *s: torch.zeros(s, dtype=torch.float32)), (lambda *s: torch.zeros(s, dtype=torch.int32)), \
+        (lambda *s: torch.zeros(s, dtype=torch.uint8)), (lambda *s: torch.zeros(s, dtype=torch.int64))
+    calls = {"gbdt_bin": lambda: Fn.gbdt_bin(f32(4, 3), f32(3, 15), i32(3)),
+             "gbdt_quantize": lambda: Fn.gbdt_quantize(f32(4), f32(4)),
+             "gbdt_histogram": lambda: Fn.gbdt_histogram(u8(4, 16), i32(4), i32(4), i32(2), 3, 16),
+             "gbdt_hist_sub": lambda: Fn.gbdt_hist_sub(i64(3, 16, 3), i64(3, 16, 3)),
+             "gbdt_best_split": lambda: Fn.gbdt_best_split(i64(1, 3, 16, 3), i32(3), i32(2)),
+             "gbdt_partition": lambda: Fn.gbdt_partition(u8(4, 16), i32(2), 0, 0, 3),
+             "gbdt_add_leaf_values": lambda: Fn.gbdt_add_leaf_values(f32(4), i32(4), i32(2), f32(1)),
+             "gbdt_predict": lambda: Fn.gbdt_predict(f32(4, 3), i32(0), f32(0), i32(0), i32(0), f32(1), i32(2))}
+    assert set(calls) == set(WRAPPERS)
+    for name, call in calls.items():
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            call()
+    if not torch.cuda.is_available():
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            pa.GBDT({"num_leaves": 4}).fit_bins(np.zeros((4, 3), np.float32))
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            pa.GBDT({"num_leaves": 4}, X=np.zeros((4, 3), np.float32))
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            pa.LambdaMART({"num_leaves": 4})
+
+
+def test_parameter_handling():
+    from ptranking_amd import gbdt
+    p = gbdt.GBDT(REFERENCE_PARAMS).params
+    assert (p["learning_rate"], p["num_leaves"], p["num_trees"], p["min_data_in_leaf"], p["min_sum_hessian_in_leaf"]) == (0.05, 400, 1000, 50, 200.0)
+    assert p["max_bin"] == 255 and p["max_depth"] == -1 and "num_threads" not in p and "metric" not in p
+    assert gbdt.GBDT().params["min_sum_hessian_in_leaf"] == 1e-3
+    with pytest.raises(ValueError, match="dart"):
+        gbdt.GBDT(dict(REFERENCE_PARAMS, boosting_type="dart"))
+    with pytest.raises(ValueError, match="dart"):
+        gbdt.LambdaMART(dict(REFERENCE_PARAMS, boosting_type="dart"))
+    with pytest.raises(ValueError, match="learning_rate"):
+        gbdt.GBDT({"learning_rate": -0.1})
+    with pytest.raises(ValueError, match="max_bin"):
+        gbdt.GBDT({"max_bin": 257})
+    with pytest.raises(ValueError, match="unknown parameter"):
+        gbdt.GBDT({"feature_fraction": 0.5})
+    with pytest.raises(ValueError, match="objective"):
+        gbdt.LambdaMART(objective="mart")
+
+
+# ---------------------------------------------------------------- the binning rule
+def test_binning_rule_cases():
+    from ptranking_amd import gbdt
+    rng = np.random.default_rng(0)
+    X = np.stack([rng.integers(0, 7, 500).astype(np.float32),                  # 7 distinct values: lossless
+                  rng.standard_normal(500).astype(np.float32),                 # 500 distinct values: quantile bins
+                  np.full(500, 2.5, np.float32),                               # constant: one bin, never split
+                  np.where(rng.random(500) < 0.9, 0.0, rng.standard_normal(500)).astype(np.float32)], axis=1)   # one heavy value
+    for max_bin in (2, 16, 255):
+        edges, nbins = gbdt.bin_edges(X, max_bin)
+        ref_edges, ref_nbins = R.bin_edges(X, max_bin)
+        assert np.array_equal(edges, ref_edges) and np.array_equal(nbins, ref_nbins)
+        assert nbins[2] == 1 and nbins[0] == min(7, max_bin) and nbins[1] == min(max_bin, 500) and 2 <= nbins[3] <= max_bin
+        bins = R.bin_matrix(X, edges, nbins)
+        for f in range(4):
+            e = edges[f, :nbins[f] - 1]
+            assert np.all(np.diff(e) > 0) and np.all(np.isinf(edges[f, nbins[f] - 1:]))
+            assert bins[:, f].max() == nbins[f] - 1                                          # no empty tail: the last bin is used
+            for b, edge in enumerate(e):                                                     # x <= edge  <=>  bin <= b, every row
+                assert np.array_equal(X[:, f] <= edge, bins[:, f] <= b)
+        if max_bin >= 7:                                                                     # lossless: one bin per distinct value
+            assert np.array_equal(np.unique(X[:, 0], return_inverse=True)[1], bins[:, 0])
+        counts = np.bincount(bins[:, 1], minlength=nbins[1])
+        assert counts.max() <= 500 // max_bin + 1 and counts.min() >= 500 // max_bin - 1         # quantile bins of all-distinct values: even
+    # values exactly on an edge go left of it; adjacent floats still get an edge that separates them
+    a = np.float32(1.0)
+    b = np.nextafter(a, np.float32(2.0))
+    edges, nbins = gbdt.bin_edges(np.array([[a], [b], [a]], np.float32), 16)
+    assert nbins[0] == 2 and a <= edges[0, 0] < b
+    bins = R.bin_matrix(np.array([[edges[0, 0]], [b]], np.float32), edges, nbins)
+    assert bins[:, 0].tolist() == [0, 1]
+    with pytest.raises(ValueError, match="NaN"):
+        gbdt.bin_edges(np.array([[np.nan]], np.float32), 16)
+
+
+# ---------------------------------------------------------------- the restatement is right
+def _small(seed=3, n=40, nf=3):
+    rng = np.random.default_rng(seed)
+    X = rng.integers(0, 6, (n, nf)).astype(np.float32)
+    g = rng.standard_normal(n).astype(np.float32)
+    h = (0.05 + rng.random(n)).astype(np.float32)
+    return X, g, h
+
+
+def test_lossless_binning_root_split_equals_exact_greedy():
+    X, g, h = _small()
+    edges, nbins = R.bin_edges(X, 16)
+    bins = R.bin_matrix(X, edges, nbins)
+    qg, qh, expo, flag = R.quantize(g, h)
+    assert flag == 0
+    for l2, min_data in ((0.0, 1), (1.0, 5)):
+        s = R.best_split(R.histogram(bins, qg, qh, None, 16), nbins, expo, l2, min_data, 1e-3, 0.0)
+        gain, f, v, mask = R.exact_greedy_root(X, g, h, l2, min_data, 1e-3, 0.0)
+        assert s["feature"] == f and abs(s["gain"] - gain) <= 1e-6 * abs(gain)       # fp32 gradients are quantized: the 1e-12 case is below
+        assert np.array_equal(bins[:, f] <= s["bin"], mask)                                 # the same partition
+        out, cl = R.partition(bins, np.arange(40), f, s["bin"])
+        assert cl == mask.sum() and np.array_equal(out[:cl], np.nonzero(mask)[0]) and np.array_equal(out[cl:], np.nonzero(~mask)[0])
+        assert edges[f, s["bin"]] >= v and not np.any((X[:, f] > v) & (X[:, f] <= edges[f, s["bin"]]))
+
+
+def test_gain_matches_exact_greedy_to_1e_12_on_exactly_representable_gradients():
+    """With gradients that are multiples of 2^-8 quantization is exact, so the restatement's float64 gain equals the brute-force gain up to
+    float64 rounding: 1e-12 relative."""
+    rng = np.random.default_rng(11)
+    X = rng.integers(0, 6, (40, 3)).astype(np.float32)
+    g = (rng.integers(-256, 257, 40) / 256.0).astype(np.float32)
+    h = (rng.integers(16, 257, 40) / 256.0).astype(np.float32)
+    edges, nbins = R.bin_edges(X, 16)
+    bins = R.bin_matrix(X, edges, nbins)
+    qg, qh, expo, _ = R.quantize(g, h)
+    assert np.array_equal(np.ldexp(qg.astype(np.float64), -expo[0]), g.astype(np.float64))
+    s = R.best_split(R.histogram(bins, qg, qh, None, 16), nbins, expo, 0.5, 2, 1e-3, 0.0)
+    gain, f, v, mask = R.exact_greedy_root(X, g, h, 0.5, 2, 1e-3, 0.0)
+    assert s["feature"] == f and abs(s["gain"] - gain) <= 1e-12 * abs(gain) and np.array_equal(bins[:, f] <= s["bin"], mask)
+
+
+def test_fixed_point_sums_and_subtraction():
+    rng = np.random.default_rng(5)
+    n = 5000
+    g = (rng.standard_normal(n) * np.exp(rng.uniform(-8, 3, n))).astype(np.float32)
+    h = rng.random(n).astype(np.float32)
+    qg, qh, expo, _ = R.quantize(g, h)
+    assert np.abs(qg).max() < 2 ** 30 <= 2 * np.abs(qg.astype(np.int64)).max() + 2 and np.abs(qh).max() < 2 ** 30
+    bins = rng.integers(0, 16, (n, 2)).astype(np.uint8)
+    hist = R.histogram(bins, qg, qh, None, 16)
+    for b in range(16):
+        m = bins[:, 0] == b
+        exact = g[m].astype(np.float64).sum()
+        assert abs(np.ldexp(float(hist[0, b, 0]), -expo[0]) - exact) <= m.sum() * 2.0 ** -31 * float(np.abs(g).max())
+    rows = rng.permutation(n)[:3000].astype(np.int32)
+    parent = R.histogram(bins, qg, qh, rows, 16)
+    out, cl = R.partition(bins, rows, 1, 6)
+    left, right = R.histogram(bins, qg, qh, out[:cl], 16), R.histogram(bins, qg, qh, out[cl:], 16)
+    assert np.array_equal(parent - left, right) and np.array_equal(R.histogram(bins, qg, qh, rows[::-1], 16), parent)
+    assert R.quantize(np.zeros(4, np.float32), np.zeros(4, np.float32))[2] == (0, 0)
+    assert R.quantize(np.array([1.0, np.nan], np.float32), np.ones(2, np.float32))[3] == 1
+
+
+def test_growth_stops_without_a_valid_split():
+    X, g, h = _small(n=40)
+    edges, nbins = R.bin_edges(X, 16)
+    bins = R.bin_matrix(X, edges, nbins)
+    qg, qh, expo, _ = R.quantize(g, h)
+    t, leaf_rows, _ = R.grow_tree(bins, qg, qh, expo, edges, nbins, 16, num_leaves=8, lr=0.1, l2=0.25, min_data=21)
+    assert t["feature"].size == 0 and len(leaf_rows) == 1 and leaf_rows[0].size == 40
+    G, H = np.ldexp(float(qg.astype(np.int64).sum()), -expo[0]), np.ldexp(float(qh.astype(np.int64).sum()), -expo[1])
+    assert t["value"].tolist() == [np.float32(-G / (H + 0.25) * 0.1)]
+    assert np.array_equal(R.predict(X, [t]), np.full(40, t["value"][0], np.float32))
+    t8, rows8, _ = R.grow_tree(bins, qg, qh, expo, edges, nbins, 16, num_leaves=8, min_data=2)
+    assert t8["feature"].size == 7 and sorted(np.concatenate(rows8).tolist()) == list(range(40))
+    scores = R.add_leaf_values(np.zeros(40, np.float32), rows8, t8["value"])
+    assert np.array_equal(R.predict(X, [t8]), scores)                                          # a training row's prediction is its score
+    t3, _, _ = R.grow_tree(bins, qg, qh, expo, edges, nbins, 16, num_leaves=8, min_data=1, max_depth=2)
+    assert t3["feature"].size <= 3
+
+
+def test_model_file_round_trips_without_a_gpu(tmp_path):
+    from ptranking_amd import gbdt
+    m = gbdt.GBDT({"num_leaves": 3, "learning_rate": 0.2, "max_bin": 4})
+    m.edges, m.nbins = np.array([[0.5, 1.5, np.inf], [2.0, np.inf, np.inf]], np.float32), np.array([3, 2], np.int32)
+    m.trees = [{"feature": np.array([0, 1], np.int32), "threshold": np.array([0.5, 2.0], np.float32), "left": np.array([~0, ~1], np.int32),
+                "right": np.array([1, ~2], np.int32), "value": np.array([0.1, -0.2, 0.3], np.float32)},
+               {"feature": np.zeros(0, np.int32), "threshold": np.zeros(0, np.float32), "left": np.zeros(0, np.int32), "right": np.zeros(0, np.int32),
+                "value": np.array([0.05], np.float32)}]
+    m.best_iteration = 1
+    path = tmp_path / "model.npz"
+    m.save_model(path)
+    back = gbdt.GBDT.load_model(path)
+    assert back.params == m.params and back.best_iteration == 1 and len(back.trees) == 2
+    assert np.array_equal(back.edges, m.edges) and np.array_equal(back.nbins, m.nbins)
+    for a, b in zip(m.trees, back.trees):
+        for k in a:
+            assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
+    assert back.flat()["tree_offsets"].tolist() == [0, 2, 2]
+    X = np.array([[0.0, 0.0], [1.0, 1.0], [1.0, 3.0]], np.float32)
+    assert np.array_equal(R.predict(X, back.trees), np.array([np.float32(0.1) + np.float32(0.05), np.float32(-0.2) + np.float32(0.05),
+                                                             np.float32(0.3) + np.float32(0.05)], np.float32))
+
+
+# ---------------------------------------------------------------- planted faults: the comparisons of the GPU tests can fail
+def test_planted_faults_fail_their_comparisons():
+    rng = np.random.default_rng(17)
+    n = 64
+    # min_data_in_leaf taken as < instead of <=: the split that leaves exactly min_data rows on one side is lost
+    bins = np.zeros((n, 1), np.uint8)
+    bins[10:, 0] = 1
+    qg = np.where(np.arange(n) < 10, 1000, -1000).astype(np.int32)
+    qh = np.full(n, 1 << 20, np.int32)
+    hist = R.histogram(bins, qg, qh, None, 4)
+    good = R.best_split(hist, [2], (10, 20), min_data=10)
+    bad = R.best_split(hist, [2], (10, 20), min_data=10, fault="min_data")
+    assert good["feature"] == 0 and good["left"][2] == 10 and bad["feature"] == -1 and not np.array_equal(R.record(good), R.record(bad))
+    # a tie between two identical columns broken to the highest feature
+    bins2 = np.repeat(rng.integers(0, 4, (n, 1)).astype(np.uint8), 2, axis=1)
+    hist2 = R.histogram(bins2, rng.integers(-1000, 1000, n).astype(np.int32), qh, None, 4)
+    good, bad = R.best_split(hist2, [4, 4], (10, 20)), R.best_split(hist2, [4, 4], (10, 20), fault="tie")
+    assert good["gain"] == bad["gain"] and (good["feature"], bad["feature"]) == (0, 1)
+    # an unstable partition
+    rows = rng.permutation(n).astype(np.int32)
+    good, cl = R.partition(bins2, rows, 0, 1)
+    bad, cl_bad = R.partition(bins2, rows, 0, 1, fault="unstable")
+    assert cl == cl_bad and sorted(good.tolist()) == sorted(bad.tolist()) and not np.array_equal(good, bad)
+    # an exponent off by one
+    g, h = rng.standard_normal(n).astype(np.float32), rng.random(n).astype(np.float32)
+    qa, _, ea, _ = R.quantize(g, h)
+    qb, _, eb, _ = R.quantize(g, h, fault="exponent")
+    assert eb[0] == ea[0] + 1 and not np.array_equal(qa, qb)
