@@ -2,15 +2,20 @@
 
 The reference's tree frame (ptranking/ltr_tree/lambdamart/lightgbm_lambdaMART.py) parses files, hands the boosting to LightGBM and predicts the
 test set.  LightGBM is not installed where this package is developed or tested, so nothing here is compared with it, and no parity is
-claimed: the binning rule, the tie rules and the model file are this project's own.
+claimed: the binning rule, the tie rules and the model file are this project's own.  What is pinned from outside is the
+booster's whole fits against scikit-learn's trees (tests/golden/gbdt_sklearn.npz): under squared error, on features of no more distinct
+values than bins, every tree equals HistGradientBoostingRegressor's node for node (growth order, sibling subtraction, leaf values,
+learning rate, the accumulation over rounds), and one tree equals DecisionTreeRegressor's exact greedy best-first tree.  Not pinned:
+LightGBM itself, the quantile binning rule for features of more distinct values than bins, and the ranking objectives inside the booster.
 
-    GBDT(params)        the booster: fit_bins(X) bins the features once and keeps them resident; update(grad, hess) grows ONE tree leaf-wise
+    GBDT(params)       the booster: fit_bins(X) bins the features once and keeps them resident; update(grad, hess) grows ONE tree leaf-wise
                         from device gradients and adds its leaf values to the resident training scores; predict / save_model / load_model
     LambdaMART(params)  the ranker: every round computes the gradient and the Hessian per document with tree_pair_grad_hess /
                         tree_listnet_grad_hess on the resident scores (no host copy), quantizes them and calls update
 
 Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here: GOSS, EFB,
-categorical features, missing values (a non-finite feature raises), DART, monotone constraints.  There is no CPU path.
+categorical features, missing values (a non-finite feature raises: in bin_edges, in predict and for the eval_set of LambdaMART.fit), DART,
+monotone constraints.  There is no CPU path.
 """
 import json
 
@@ -56,6 +61,16 @@ def _params(params):
     return p
 
 
+_NONFINITE = "X holds a NaN or an infinity: missing values are not handled, impute them first"
+
+
+def _require_finite(Xd):
+    """Raises bin_edges' ValueError for a NaN or an infinity in a device matrix: one reduction (the minimum and the maximum, which a NaN
+    poisons) and one host read."""
+    if Xd.numel() and not bool(torch.isfinite(torch.stack(torch.aminmax(Xd)).cpu()).all()):
+        raise ValueError(_NONFINITE)
+
+
 def _midpoints(lo, hi):
     """An fp32 edge e with lo <= e < hi for adjacent distinct fp32 values: the midpoint, or lo where the midpoint rounds up to hi."""
     mid = ((lo.astype(np.float64) + hi.astype(np.float64)) * 0.5).astype(np.float32)
@@ -71,7 +86,7 @@ def bin_edges(X, max_bin):
     if X.ndim != 2:
         raise ValueError(f"X must be [rows, features], got {X.shape}")
     if not np.isfinite(X).all():
-        raise ValueError("X holds a NaN or an infinity: missing values are not handled, impute them first")
+        raise ValueError(_NONFINITE)
     n, nf = X.shape
     edges = np.full((nf, max_bin - 1), np.inf, np.float32)
     nbins = np.ones(nf, np.int32)
@@ -242,10 +257,11 @@ class GBDT:
         return {"feature": cat("feature", np.int32), "threshold": cat("threshold", np.float32), "left": cat("left", np.int32),
                 "right": cat("right", np.int32), "value": cat("value", np.float32), "tree_offsets": offs}
 
-    def predict(self, X, num_iteration=None, first_tree=0):
+    def predict(self, X, num_iteration=None, first_tree=0, check_finite=True):
         """Scores of raw rows X (numpy array or device tensor [n, F]) -> device float32 [n]: the trees first_tree .. num_iteration - 1
         (default: up to best_iteration when early stopping set it, else all), summed in tree order in fp32 — for a training row the bits of
-        its resident training score."""
+        its resident training score.  A NaN or an infinity in X raises, as in bin_edges (a NaN would go right at every node, while binning
+        puts it left); the check costs one synchronisation, and check_finite=False skips it for a matrix the caller has already checked."""
         dev = self._dev()
         if self._flat is None:
             self._flat = {k: torch.from_numpy(v).to(dev) for k, v in self.flat().items()}
@@ -254,6 +270,8 @@ class GBDT:
         if not 0 <= first_tree <= stop <= len(self.trees):
             raise ValueError(f"trees {first_tree} .. {stop} of {len(self.trees)}")
         Xd = X.detach().to(dev, torch.float32) if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
+        if check_finite:
+            _require_finite(Xd)
         if first_tree == 0:
             return F.gbdt_predict(Xd, fl["feature"], fl["threshold"], fl["left"], fl["right"], fl["value"], fl["tree_offsets"], stop)
         host = self.flat()
@@ -364,6 +382,7 @@ class LambdaMART:
             if eval_group is None:
                 raise ValueError("eval_set needs eval_group")
             Xv = Xv.detach().to(self.device, torch.float32) if isinstance(Xv, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(Xv, dtype=np.float32)).to(self.device)
+            _require_finite(Xv)                                                       # once, before the first round: the rounds skip it
             yv = torch.from_numpy(np.ascontiguousarray(np.asarray(yv).reshape(-1), dtype=np.float32)).to(self.device)
             valid = (Xv, yv, self.padded_index(eval_group, self.device), torch.zeros(Xv.shape[0], device=self.device, dtype=torch.float32))
         elif early_stopping_rounds is not None:
@@ -375,7 +394,7 @@ class LambdaMART:
             if valid is None:
                 continue
             Xv, yv, index, sv = valid
-            sv += self.booster.predict(Xv, num_iteration=it, first_tree=it - 1)       # the new tree alone: the same fp32 sum, in tree order
+            sv += self.booster.predict(Xv, num_iteration=it, first_tree=it - 1, check_finite=False)      # the new tree alone: the same fp32 sum
             score = self.ndcg_at(sv, yv, None, eval_at, index=index)
             self.evals_result.append(score)
             if self.best_score is None or score > self.best_score:

@@ -159,43 +159,59 @@ def leaf_value(g_sum, h_sum, expo, l2, lr):
 
 
 # ---- leaf-wise growth
-def grow_tree(bins, qg, qh, expo, edges, nbins, max_bin, num_leaves, lr=0.1, l2=0.0, min_data=1, min_hess=1e-3, min_gain=0.0, max_depth=-1):
+def grow_tree(bins, qg, qh, expo, edges, nbins, max_bin, num_leaves, lr=0.1, l2=0.0, min_data=1, min_hess=1e-3, min_gain=0.0, max_depth=-1,
+              fault=None):
     """One tree: split the leaf with the largest gain (ties: the older leaf) until num_leaves or no valid split.  The left child keeps its
-    parent's leaf number, the right child gets the next one; node k is the k-th split.
+    parent's leaf number, the right child gets the next one; node k is the k-th split.  As in GBDT.update, only the child with fewer rows
+    (ties: the left one) has its histogram summed from its rows; its sibling's is the parent's minus that one.
+    fault: "newest_leaf" splits the newest leaf, not the best one; "no_l2" leaves lambda_l2 out of the leaf values; "larger_hist" takes the
+    larger child's histogram as the smaller's (the two exchanged).
     -> (tree dict of feature / threshold / left / right / value, the leaves' row lists, the smallest margin of any search)."""
     n = bins.shape[0]
+    none = {"gain": -np.inf, "runner_up": -np.inf}
 
-    def search(rows, depth):
-        if rows.size < 2 * max(min_data, 1) or (max_depth > 0 and depth >= max_depth):
-            return {"gain": -np.inf, "runner_up": -np.inf}
-        return best_split(histogram(bins, qg, qh, rows, max_bin), nbins, expo, l2, min_data, min_hess, min_gain)
+    def splittable(count, depth):
+        return count >= 2 * max(min_data, 1) and not (max_depth > 0 and depth >= max_depth)
+
+    def search(hist):
+        return best_split(hist, nbins, expo, l2, min_data, min_hess, min_gain)
 
     all_rows = np.arange(n, dtype=np.int32)
     tot = (int(qg.astype(np.int64).sum()), int(qh.astype(np.int64).sum()))
-    leaves = [{"rows": all_rows, "depth": 0, "parent": -1, "side": 0, "sums": tot, "split": search(all_rows, 0)}]
+    root_hist = histogram(bins, qg, qh, all_rows, max_bin)
+    leaves = [{"rows": all_rows, "depth": 0, "parent": -1, "side": 0, "sums": tot, "hist": root_hist,
+               "split": search(root_hist) if splittable(n, 0) else none}]
     worst = margin(leaves[0]["split"])
     feature, threshold, left, right = [], [], [], []
     while len(leaves) < num_leaves:
-        li = max(range(len(leaves)), key=lambda i: (leaves[i]["split"]["gain"], -i))
+        li = len(leaves) - 1 if fault == "newest_leaf" else max(range(len(leaves)), key=lambda i: (leaves[i]["split"]["gain"], -i))
         leaf = leaves[li]
         s = leaf["split"]
         if not s["gain"] > -np.inf:
             break
         out, cl = partition(bins, leaf["rows"], s["feature"], s["bin"])
-        assert cl == s["left"][2]
+        assert cl == s["left"][2] or fault == "larger_hist"
         node = len(feature)
         feature.append(s["feature"]); threshold.append(edges[s["feature"], s["bin"]]); left.append(~li); right.append(~len(leaves))
         if leaf["parent"] >= 0:
             (left if leaf["side"] == 0 else right)[leaf["parent"]] = node
-        last = len(leaves) + 1 >= num_leaves
-        kids = []
-        for side, rows, sums in ((0, out[:cl], s["left"]), (1, out[cl:], s["right"])):
-            split = {"gain": -np.inf, "runner_up": -np.inf} if last else search(rows, leaf["depth"] + 1)
-            worst = min(worst, margin(split))
-            kids.append({"rows": rows, "depth": leaf["depth"] + 1, "parent": node, "side": side, "sums": sums[:2], "split": split})
+        kids = [{"rows": rows, "depth": leaf["depth"] + 1, "parent": node, "side": side, "sums": sums[:2], "hist": None, "split": none}
+                for side, rows, sums in ((0, out[:cl], s["left"]), (1, out[cl:], s["right"]))]
+        can = [splittable(c["rows"].size, c["depth"]) for c in kids]
+        if len(leaves) + 1 < num_leaves and any(can):
+            small, large = (kids[0], kids[1]) if kids[0]["rows"].size <= kids[1]["rows"].size else (kids[1], kids[0])
+            small["hist"] = histogram(bins, qg, qh, small["rows"], max_bin)
+            large["hist"] = leaf["hist"] - small["hist"]
+            if fault == "larger_hist":
+                small["hist"], large["hist"] = large["hist"], small["hist"]
+            for c, ok in zip(kids, can):
+                if ok:
+                    c["split"] = search(c["hist"])
+                    worst = min(worst, margin(c["split"]))
+        leaf["hist"] = None
         leaves[li] = kids[0]
         leaves.append(kids[1])
-    value = np.array([leaf_value(c["sums"][0], c["sums"][1], expo, l2, lr) for c in leaves], np.float32)
+    value = np.array([leaf_value(c["sums"][0], c["sums"][1], expo, 0.0 if fault == "no_l2" else l2, lr) for c in leaves], np.float32)
     tree = {"feature": np.array(feature, np.int32), "threshold": np.array(threshold, np.float32), "left": np.array(left, np.int32),
             "right": np.array(right, np.int32), "value": value}
     return tree, [c["rows"] for c in leaves], worst

@@ -1,7 +1,9 @@
 """GPU: the gradient-boosted tree kernels (csrc/gbdt.hip), GBDT and LambdaMART against the numpy restatement tests/gbdt_ref.py, fed the same
 fp32 inputs.  Everything a tree decides rests on integer sums, so the comparisons are exact: bins, fixed-point values, histograms, split
 records, partitions, tree structures, fp32 leaf values, scores and predictions are compared bit for bit, and the float64 gain to 1e-12
-relative.  Nothing here is compared with LightGBM: it is not installed where this runs, and the binning and tie rules are this project's own."""
+relative.  The last section pins whole fits to an implementation from outside the project: scikit-learn's trees, read from
+tests/golden/gbdt_sklearn.npz (tests/gbdt_sk.py; scikit-learn itself is not needed here).  Nothing here is compared with LightGBM: it is not
+installed where this runs, and the quantile binning rule and the tie rules are this project's own."""
 import functools
 import os
 import subprocess
@@ -12,6 +14,7 @@ import pytest
 import torch
 
 import gbdt_ref as R
+import gbdt_sk as SK
 from launch_form import launch_form
 
 pytestmark = pytest.mark.gpu
@@ -546,3 +549,157 @@ def test_the_example_runs():
     lines = [l for l in out.stdout.splitlines() if l.startswith("round ")]
     assert len(lines) == 2 and "nDCG@5" in lines[0], out.stdout
     assert float(lines[-1].split("valid nDCG@5 ")[1].split()[0]) > float(out.stdout.split("constant scores: valid nDCG@5 ")[1].split()[0])
+
+
+# ---------------------------------------------------------------- whole fits against scikit-learn (tests/golden/gbdt_sklearn.npz)
+SK_NAMES = ("a", "b", "c", "d", "e", "f")
+
+
+@pytest.fixture(scope="module")
+def sk_fits(tmp_path_factory):
+    """Every fixture case fitted once: GBDT on the case's X, the scores set to sklearn's baseline, per round g = (scores - y) * w and h = w in
+    fp32 on the device, then update.  Records what the tests compare, and the shape of every histogram launch."""
+    import ptranking_amd as pa
+    from ptranking_amd import functional as Fn
+    cases, out = SK.load()[0], {}
+    assert tuple(sorted(cases)) == SK_NAMES
+    real = Fn.gbdt_histogram
+    for name, c in cases.items():
+        launches = []
+
+        def spy(bins, qg, qh, rows, nf, max_bin, **kw):
+            launches.append((bins.shape[0] if rows is None else rows.numel(), nf, max_bin))
+            return real(bins, qg, qh, rows, nf, max_bin, **kw)
+
+        p = c["params"]
+        booster = pa.GBDT(SK.booster_params(p), c["X"])
+        base = np.float32(c["baseline"])
+        booster.scores.fill_(float(base))
+        y, w = dev(c["y"]), dev(np.ones_like(c["y"]) if c["w"] is None else c["w"])
+        rounds = []
+        with pytest.MonkeyPatch.context() as mp:
+            mp.setattr(Fn, "gbdt_histogram", spy)
+            for _ in range(p["rounds"]):
+                tree = booster.update((booster.scores - y) * w, w)
+                rounds.append((tree, booster.scores.cpu().numpy().copy()))
+        fresh = booster.predict(c["fresh"])
+        path = tmp_path_factory.mktemp("sk") / f"{name}.npz"
+        booster.save_model(path)
+        reloaded = pa.GBDT.load_model(path).predict(c["fresh"])
+        out[name] = dict(case=c, booster=booster, rounds=rounds, fresh=(fresh + float(base)).cpu().numpy(), same_bits=torch.equal(fresh, reloaded),
+                         launches=launches)
+    return out
+
+
+@pytest.mark.parametrize("name", SK_NAMES)
+def test_whole_fits_match_sklearn(sk_fits, name):
+    """Cases a - e: HistGradientBoostingRegressor; case f: one DecisionTreeRegressor, the exact greedy best-first tree (g = -y, h = 1 from
+    zero scores).  Trees equal in canonical form; training scores after every round and the fresh predictions within
+    C_GBDT_SK 2^-24 max(1, max |score|), the constant being twice what the numpy restatement needs against sklearn (test_gbdt_cpu.py)."""
+    fit = sk_fits[name]
+    c, p = fit["case"], fit["case"]["params"]
+    edges, nbins = SK.midpoint_edges(c["codes"], p["max_bin"])
+    assert np.array_equal(fit["booster"].edges, edges) and np.array_equal(fit["booster"].nbins, nbins)     # the midpoints the codes imply
+    assert len(fit["rounds"]) == p["rounds"]
+    for r, (tree, scores) in enumerate(fit["rounds"]):
+        nodes, leaves = SK.canonical(tree, c["X"])
+        miss = SK.tree_mismatch(nodes, leaves, c, r)
+        assert miss is None, f"round {r}: {miss}"
+        err = float(np.abs(scores.astype(np.float64) - c["staged"][r]).max())
+        print(f"MEASURED gbdt vs sklearn, case {name} round {r}: training scores need C >= {err / SK.need_unit(c['staged'][r]):.2f}")
+        assert err <= SK.gate(c["staged"][r]), r
+    err = float(np.abs(fit["fresh"].astype(np.float64) - c["fresh_pred"]).max())
+    print(f"MEASURED gbdt vs sklearn, case {name}: {c['fresh'].shape[0]} fresh rows need C >= {err / SK.need_unit(c['fresh_pred']):.2f}")
+    assert err <= SK.gate(c["fresh_pred"])
+    assert fit["same_bits"]                                                          # a saved and reloaded model predicts the same bits
+
+
+@pytest.mark.parametrize("name", SK_NAMES)
+def test_whole_fits_equal_the_restatement_bit_for_bit(sk_fits, name):
+    """The same fits against gbdt_ref.py: should a case miss sklearn, this says whether the kernels or the shared rules are at fault."""
+    fit = sk_fits[name]
+    want, fresh, _ = SK.run_restatement(fit["case"])
+    assert_rounds_equal([(tree, ref_tree, scores, ref_scores) for (tree, scores), (ref_tree, ref_scores) in zip(fit["rounds"], want)])
+    assert np.array_equal(fit["fresh"].view(np.int32), fresh.view(np.int32))
+
+
+def test_sklearn_cases_reach_both_histogram_forms_and_several_feature_tiles(sk_fits):
+    """From the histogram launches the fits really made: the case list cannot silently shrink onto one path."""
+    forms = {name: {form_name(*shape) for shape in fit["launches"]} for name, fit in sk_fits.items()}
+    tiles = {name: (fit["case"]["X"].shape[1] + 15) // 16 for name, fit in sk_fits.items()}
+    assert set().union(*forms.values()) == {"direct", "lds-1-chunk"}
+    assert forms["a"] == {"direct", "lds-1-chunk"} and forms["e"] == {"direct", "lds-1-chunk"}
+    assert (tiles["a"], tiles["b"], tiles["d"], tiles["e"]) == (1, 2, 3, 1)
+    for name, fit in sk_fits.items():
+        n, nf = fit["case"]["X"].shape
+        root = fit["launches"][0]
+        assert root == (n, nf, fit["case"]["params"]["max_bin"]) and form_name(*root) == "lds-1-chunk"
+        assert launch_form("ptr_gbdt_histogram", *root)[2] == tiles[name]
+    assert sk_fits["e"]["launches"][0][0] == 257                                     # one row over the direct form's bound
+
+
+# ---------------------------------------------------------------- non-finite features at prediction time
+def _one_tree_booster():
+    import ptranking_amd as pa
+    X, y, group = ranking_set(2, 10, 5, 20)
+    booster = pa.GBDT({"num_leaves": 4, "min_data_in_leaf": 2}, X)
+    booster.update(dev(y - y.mean()) * -1.0, torch.ones(X.shape[0], device="cuda"))
+    return booster, X
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf"), float("-inf")])
+def test_predict_raises_on_a_non_finite_feature(bad):
+    booster, X = _one_tree_booster()
+    assert torch.isfinite(booster.predict(X)).all()
+    for i, f in ((0, 0), (X.shape[0] - 1, X.shape[1] - 1), (X.shape[0] // 2, 3)):        # first, last and an inner element
+        Xb = X.copy()
+        Xb[i, f] = bad
+        with pytest.raises(ValueError, match="NaN or an infinity"):
+            booster.predict(Xb)
+        with pytest.raises(ValueError, match="NaN or an infinity"):
+            booster.predict(dev(Xb))
+    Xb = X.copy()
+    Xb[0, 0], Xb[1, 0] = np.inf, -np.inf                                                 # both infinities, and a NaN beside them
+    Xb[2, 1] = np.nan
+    with pytest.raises(ValueError, match="NaN or an infinity"):
+        booster.predict(Xb)
+    big = np.full((4, X.shape[1]), np.finfo(np.float32).max, np.float32)                 # finite, however large: no false alarm
+    big[1] = -big[1]
+    assert torch.isfinite(booster.predict(big)).all()
+    assert booster.predict(np.zeros((0, X.shape[1]), np.float32)).numel() == 0
+
+
+def test_fit_raises_on_a_non_finite_validation_feature_before_the_first_round(fit_sets):
+    import ptranking_amd as pa
+    (X, y, group), (Xv, yv, gv) = fit_sets
+    Xb = Xv.copy()
+    Xb[17, 2] = np.nan
+    lm = pa.LambdaMART(dict(FIT_PARAMS, num_trees=2))
+    with pytest.raises(ValueError, match="NaN or an infinity"):
+        lm.fit(X, y, group, eval_set=(Xb, yv), eval_group=gv)
+    assert lm.evals_result == [] and len(lm.booster.trees) == 0
+    with pytest.raises(ValueError, match="NaN or an infinity"):
+        lm.fit(X, y, group, eval_set=(dev(Xb), yv), eval_group=gv)
+    lm.fit(X, y, group, eval_set=(Xv, yv), eval_group=gv)
+    with pytest.raises(ValueError, match="NaN or an infinity"):
+        lm.predict(Xb)
+
+
+def test_fit_checks_the_validation_matrix_once_and_no_round_checks_again(fit_sets, monkeypatch):
+    """The check synchronises, so fit makes it once before the first round; the per-round predict of the checked matrix skips it."""
+    import ptranking_amd as pa
+    from ptranking_amd import gbdt
+    (X, y, group), (Xv, yv, gv) = fit_sets
+    seen, real = [], gbdt._require_finite
+
+    def spy(Xd):
+        seen.append(tuple(Xd.shape))
+        return real(Xd)
+
+    monkeypatch.setattr(gbdt, "_require_finite", spy)
+    lm = pa.LambdaMART(dict(FIT_PARAMS, num_trees=4)).fit(X, y, group, eval_set=(Xv, yv), eval_group=gv)
+    assert len(lm.evals_result) == 4 and seen == [Xv.shape]
+    lm.predict(Xv)
+    assert seen == [Xv.shape, Xv.shape]
+    lm.booster.predict(Xv, check_finite=False)
+    assert len(seen) == 2
