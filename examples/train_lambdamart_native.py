@@ -2,6 +2,7 @@
 
     python examples/train_lambdamart_native.py                                   # synthetic data
     python examples/train_lambdamart_native.py train.txt [vali.txt] [test.txt]   # LETOR text files
+    python examples/train_lambdamart_native.py --grow-policy depthwise           # level by level, in batched passes
 
 The synthetic relevance is planted: a linear part plus a feature interaction a linear scorer cannot express, graded with MSLR-WEB30K's label
 mix.  Prints the validation nDCG@5 every 10 rounds.  No LightGBM comparison: the library is not installed where this project is tested.
@@ -44,6 +45,8 @@ def main():
     ap.add_argument("--num-leaves", type=int, default=31)
     ap.add_argument("--learning-rate", type=float, default=0.1)
     ap.add_argument("--min-data-in-leaf", type=int, default=20)
+    ap.add_argument("--grow-policy", default="leafwise", choices=["leafwise", "depthwise"],
+                    help="depthwise: all leaves of a level are split in one batched pass (one host read per level, not per split)")
     ap.add_argument("--queries", type=int, default=600)
     ap.add_argument("--features", type=int, default=40)
     args = ap.parse_args()
@@ -53,7 +56,8 @@ def main():
         test = from_file(args.files[2]) if len(args.files) > 2 else valid
     else:
         train, valid, test = synthetic(args.queries, args.features, 7), synthetic(args.queries // 4, args.features, 8), synthetic(args.queries // 4, args.features, 9)
-    params = {"num_leaves": args.num_leaves, "learning_rate": args.learning_rate, "min_data_in_leaf": args.min_data_in_leaf, "num_trees": args.rounds}
+    params = {"num_leaves": args.num_leaves, "learning_rate": args.learning_rate, "min_data_in_leaf": args.min_data_in_leaf, "num_trees": args.rounds,
+              "grow_policy": args.grow_policy}
     lm = pa.LambdaMART(params, objective=args.objective)
     yv = torch.from_numpy(valid[1]).cuda()
     constant = pa.LambdaMART.ndcg_at(torch.zeros(valid[0].shape[0], device="cuda"), yv, valid[2], 5)

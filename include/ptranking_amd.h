@@ -731,6 +731,12 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *   ptr_divprob_fwd_bwd                          objective, T, L                          G, TP
  *   ptr_gbdt_histogram                           m, F, max_bin                            kind, features per tile, tiles, row chunks, LDS bytes
  *                                                                                           kind: 0 nothing, 1 direct, 2 LDS tile
+ *   ptr_gbdt_histogram_segments                  m, F, max_bin, total                     kind, features per tile, tiles, row chunks, LDS bytes,
+ *                                                (m: one segment's rows; total: the rows    rows per chunk, the direct form's row bound, the most
+ *                                                of the call's LDS-form segments)           launches of one call
+ *   ptr_gbdt_hist_sub_segments                   K                                        launches of one call (1), workgroup rows per triple
+ *   ptr_gbdt_best_split_slots                    K                                        launches of one call (2), 0
+ *   ptr_gbdt_partition_segments                  m                                        launches of one call (3), workgroups of a segment of m rows
  * G: threads per query, DPT: documents per thread, TP: subtopic tile.  PTR_ERR_INVALID_ARG for an entry without a form, another nargs, or
  * nform below the count. */
 int ptr_launch_form(const char *entry, const int64_t *args, int nargs, int32_t *form, int nform);
@@ -791,6 +797,42 @@ int ptr_gbdt_add_leaf_values(float *scores, int64_t n, const int32_t *rows, cons
                              int64_t total, void *stream);
 int ptr_gbdt_predict(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
                      const int32_t *right, const float *value, const int32_t *tree_offsets, int ntrees, float *out, void *stream);
+
+/* ---- One level of a depth-wise tree in batched passes (csrc/gbdt.hip; grow_policy='depthwise' of ptranking_amd/gbdt.py).  ADDITIVE to ABI
+ * v8 too.  Each pass serves K leaves with a fixed number of launches.  The small int32 tables are DEVICE arrays the caller builds on the host
+ * (it knows every count from the split records it has read) and uploads.  Host checks before any launch, PTR_ERR_INVALID_ARG: a NULL
+ * pointer a launch would touch, K < 0, max_bin < 2 (PTR_ERR_UNSUPPORTED above PTR_GBDT_MAX_BIN, as above), F < 1, the bins layout, a
+ * workspace that is too small.  K == 0 succeeds and launches nothing.  In the kernels a table entry that points outside rows, outside the
+ * pool's slots or at a feature or bin out of range is skipped, never followed.  pool: int64 [nslots][F][max_bin][3].
+ *
+ * ptr_gbdt_histogram_segments: segs [K][3] = (start, count, slot) over the row list rows [nrows]; ADDS the rows rows[start .. start + count)
+ *   into pool[slot] (the caller zeroes the slots) — exactly the integers ptr_gbdt_histogram gives for that row list.  items
+ *   [n_direct + n_lds][3] = (segment, first row within the segment, rows): the work list.  The first n_direct items are whole segments of
+ *   at most 256 rows (one launch: a thread per (row, feature), global integer atomics); the n_lds others are row chunks of longer segments
+ *   (one launch: grid = items x tiles of 16 features, the LDS tile of ptr_gbdt_histogram).  ptr_launch_form gives the form of a segment of
+ *   m rows and the rows per chunk.  Rows listed twice are added twice.
+ * ptr_gbdt_hist_sub_segments: trips [K][3] = (parent slot, child slot, out slot): pool[out] = pool[parent] - pool[child] element-wise; out
+ *   may be the parent.  One launch.
+ * ptr_gbdt_best_split_slots: ptr_gbdt_best_split over the histograms pool[slots[k]], k < K, in place of a contiguous batch -> rec [K][9], each
+ *   bit-identical to ptr_gbdt_best_split on a copy of that slot (one shared scan).  A slot outside the pool gives the record without a
+ *   split.  ws: K * F * 9 int64 of scratch.
+ * ptr_gbdt_partition_segments: segs [K][4] = (start, count, feature, bin), disjoint: out[start .. start + count) = ptr_gbdt_partition of
+ *   rows[start .. start + count) by (feature, bin), left_counts [K] = how many went left; every position of rows [nrows] outside the
+ *   segments is copied to out unchanged, so out is a whole row list (out must not be rows).  blocks [nblocks][2] = (segment, j): one entry
+ *   per 1024 rows of every segment, a segment's entries together in ascending j.  Three launches (count, one scan over all blocks whose
+ *   differences within a segment are the segmented scan, scatter) after one device copy; no atomic decides a position.  ws:
+ *   ptr_gbdt_partition_segments_ws_ints(nblocks) int32, ws_ints of them given. */
+int ptr_gbdt_histogram_segments(const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows,
+                                int64_t nrows, const int32_t *segs, int K, const int32_t *items, int n_direct, int n_lds, int F, int max_bin,
+                                int64_t *pool, int nslots, void *stream);
+int ptr_gbdt_hist_sub_segments(int64_t *pool, int nslots, int F, int max_bin, const int32_t *trips, int K, void *stream);
+int ptr_gbdt_best_split_slots(const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin, const int32_t *nbins,
+                              const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf, double min_sum_hessian_in_leaf,
+                              double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream);
+size_t ptr_gbdt_partition_segments_ws_ints(int64_t nblocks);
+int ptr_gbdt_partition_segments(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t nrows, const int32_t *segs, int K,
+                                const int32_t *blocks, int nblocks, int32_t *out, int32_t *left_counts, int32_t *ws, int64_t ws_ints,
+                                void *stream);
 
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):

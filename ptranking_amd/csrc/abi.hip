@@ -79,6 +79,11 @@ static const FormQuery kFormQueries[] = {
     {"ptr_div_metrics_at_ks", 1, 2, [](const int64_t *a, int32_t *out) { put(out, pick_tiling((int)a[0])); }},
     {"ptr_divprob_fwd_bwd", 3, 2, [](const int64_t *a, int32_t *out) { put(out, divprob_form((int)a[0], (int)a[1], (int)a[2])); }},
     {"ptr_gbdt_histogram", 3, 5, [](const int64_t *a, int32_t *out) { put(out, gbdt_hist_form(a[0], (int)a[1], (int)a[2])); }},
+    {"ptr_gbdt_histogram_segments", 4, 8, [](const int64_t *a, int32_t *out) { put(out, gbdt_hist_segments_form(a[0], (int)a[1], (int)a[2], a[3])); }},
+    // the other batched level passes have one form each: (launches per call, entries of the table one workgroup serves or 0)
+    {"ptr_gbdt_hist_sub_segments", 1, 2, [](const int64_t *, int32_t *out) { out[0] = 1; out[1] = 1; }},
+    {"ptr_gbdt_best_split_slots", 1, 2, [](const int64_t *, int32_t *out) { out[0] = 2; out[1] = 0; }},
+    {"ptr_gbdt_partition_segments", 1, 2, [](const int64_t *a, int32_t *out) { out[0] = 3; out[1] = (int32_t)((a[0] + kGbdtPartRows - 1) / kGbdtPartRows); }},
 };
 
 }  // namespace ptr

@@ -1,5 +1,6 @@
 // A histogram gradient-boosted tree trainer on the device: binning, fixed-point gradients, per-leaf histograms, the split scan, the stable
-// row partition, the leaf-value update and prediction.  ptranking_amd/gbdt.py grows the trees leaf-wise on these entry points; the
+// row partition, the leaf-value update and prediction, and the batched forms of one level of a depth-wise tree (histograms, subtraction,
+// split scan and partition over many leaves per call).  ptranking_amd/gbdt.py grows the trees leaf-wise or depth-wise on these entry points; the
 // reference's tree frame (ptranking/ltr_tree/lambdamart/lightgbm_lambdaMART.py) hands this work to LightGBM.
 //
 // Why fixed point.  ptr_gbdt_quantize scales a round's gradients and Hessians by a power of two so that the largest magnitude lies just
@@ -171,15 +172,10 @@ struct SplitCand { double gain; int bin; int64_t gl, hl, cl; };
 // One wavefront per (leaf, feature): lane t owns the bins 4 t .. 4 t + 3, one prefix pass.  Writes the feature's best candidate to ws.
 // All arithmetic is float64 and nothing is contracted (the library is built with -ffp-contract=off):
 //   gain = ((GL * GL) / (HL + l2) + (GR * GR) / (HR + l2)) - (G * G) / (H + l2),   G = (double)qsum * 2^-e_g, H likewise (both exact).
-__global__ void __launch_bounds__(kBlock)
-gbdt_split_feature_kernel(const int64_t *__restrict__ hist, int nleaf, int F, int max_bin, const int32_t *__restrict__ nbins,
-                          const int32_t *__restrict__ expo, double l2, int64_t min_data, double min_hess, double min_gain,
-                          int64_t *__restrict__ ws) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t item = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
-    if (item >= (int64_t)nleaf * F) return;
-    const int f = (int)(item % F);
-    const int64_t *hp = hist + item * max_bin * 3;
+// (the scan itself is gbdt_split_scan, shared with the slot-list form of the batched level pass)
+__device__ __forceinline__ void gbdt_split_scan(const int64_t *__restrict__ hp, int f, int lane, int max_bin, const int32_t *__restrict__ nbins,
+                                                const int32_t *__restrict__ expo, double l2, int64_t min_data, double min_hess, double min_gain,
+                                                int64_t *__restrict__ r) {
     const int nb = min(max(nbins[f], 1), max_bin);
     int64_t pg[4], ph[4], pc[4], sg = 0, sh = 0, sc = 0;
 #pragma unroll
@@ -218,13 +214,41 @@ gbdt_split_feature_kernel(const int64_t *__restrict__ hist, int nleaf, int F, in
         if (ob >= 0 && (best.bin < 0 || og > best.gain || (og == best.gain && ob < best.bin))) best = SplitCand{og, ob, o1, o2, o3};
     }
     if (lane == 0) {
-        int64_t *r = ws + item * kRec;
         const bool ok = best.bin >= 0;
         r[0] = __double_as_longlong(ok ? best.gain : -INFINITY);
         r[1] = ok ? f : -1; r[2] = best.bin;
         r[3] = best.gl; r[4] = best.hl; r[5] = best.cl;
         r[6] = ok ? TG - best.gl : 0; r[7] = ok ? TH - best.hl : 0; r[8] = ok ? TC - best.cl : 0;
     }
+}
+
+__global__ void __launch_bounds__(kBlock)
+gbdt_split_feature_kernel(const int64_t *__restrict__ hist, int nleaf, int F, int max_bin, const int32_t *__restrict__ nbins,
+                          const int32_t *__restrict__ expo, double l2, int64_t min_data, double min_hess, double min_gain,
+                          int64_t *__restrict__ ws) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t item = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    if (item >= (int64_t)nleaf * F) return;
+    gbdt_split_scan(hist + item * max_bin * 3, (int)(item % F), lane, max_bin, nbins, expo, l2, min_data, min_hess, min_gain, ws + item * kRec);
+}
+
+// The same scan over a list of K slots of a histogram pool [nslots][F][max_bin][3]: item = (k, feature).  A slot outside the pool gives the
+// record of a leaf without a split, and is never read.
+__global__ void __launch_bounds__(kBlock)
+gbdt_split_feature_slots_kernel(const int64_t *__restrict__ pool, int nslots, const int32_t *__restrict__ slots, int K, int F, int max_bin,
+                                const int32_t *__restrict__ nbins, const int32_t *__restrict__ expo, double l2, int64_t min_data, double min_hess,
+                                double min_gain, int64_t *__restrict__ ws) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t item = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    if (item >= (int64_t)K * F) return;
+    const int f = (int)(item % F);
+    const int slot = slots[item / F];
+    int64_t *r = ws + item * kRec;
+    if (slot < 0 || slot >= nslots) {
+        if (lane < kRec) r[lane] = lane == 0 ? __double_as_longlong(-INFINITY) : lane <= 2 ? -1 : 0;
+        return;
+    }
+    gbdt_split_scan(pool + ((int64_t)slot * F + f) * max_bin * 3, f, lane, max_bin, nbins, expo, l2, min_data, min_hess, min_gain, r);
 }
 
 // One wavefront per leaf: the best of its F feature records, ties to the lowest feature.
@@ -313,6 +337,186 @@ gbdt_part_scatter_kernel(const uint8_t *__restrict__ bins, int stride, int n, co
         int step_left = 0;
         for (int w = 0; w < kBlock / kWave; ++w) { if (w < wave) before += wave_left[w]; step_left += wave_left[w]; }
         if (i < m) out[left ? before : total_left + (int)(i - before)] = row;     // `before` = the lefts ahead of entry i
+        left_before += step_left;
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------- one level of a depth-wise tree: the batched forms
+// Every table below comes from the host and is read as untrusted: an entry that points outside rows, outside the pool's slots or at a
+// feature or bin out of range is skipped (the whole item, uniformly for its workgroup, before any barrier), never followed.
+struct GbdtSeg { int start, count, slot; bool ok; };
+
+// segment `seg` of segs [K][3] = (start, count, slot) over rows [nrows], and the rows [r0, r1) of it that the item (seg, begin, len) names
+__device__ __forceinline__ GbdtSeg gbdt_hist_item(const int32_t *__restrict__ segs, int K, const int32_t *__restrict__ item, int64_t nrows, int nslots,
+                                                  int64_t &r0, int64_t &r1) {
+    GbdtSeg s{0, 0, 0, false};
+    const int k = item[0], begin = item[1], len = item[2];
+    if (k < 0 || k >= K) return s;
+    s.start = segs[k * 3]; s.count = segs[k * 3 + 1]; s.slot = segs[k * 3 + 2];
+    if (s.start < 0 || s.count < 0 || (int64_t)s.start + s.count > nrows || s.slot < 0 || s.slot >= nslots) return s;
+    if (begin < 0 || len < 0 || (int64_t)begin + len > s.count) return s;
+    r0 = (int64_t)s.start + begin;
+    r1 = r0 + len;
+    s.ok = true;
+    return s;
+}
+
+// direct form: grid = (items, feature tiles); an item is a whole segment of at most kGbdtDirectRows rows
+__global__ void __launch_bounds__(kBlock)
+gbdt_hist_seg_direct_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg, const int32_t *__restrict__ qh,
+                            const int32_t *__restrict__ rows, int64_t nrows, const int32_t *__restrict__ segs, int K,
+                            const int32_t *__restrict__ items, int F, int max_bin, int64_t *__restrict__ pool, int nslots) {
+    int64_t r0 = 0, r1 = 0;
+    const GbdtSeg s = gbdt_hist_item(segs, K, items + (int64_t)blockIdx.x * 3, nrows, nslots, r0, r1);
+    if (!s.ok || r1 - r0 > kGbdtDirectRows) return;
+    int64_t *hist = pool + (int64_t)s.slot * F * max_bin * 3;
+    const int f0 = blockIdx.y * kGbdtTile, cnt = (int)(r1 - r0) * kGbdtTile;
+    for (int e = threadIdx.x; e < cnt; e += kBlock) {
+        const int f = f0 + (e & (kGbdtTile - 1));
+        const int row = rows[r0 + (e >> 4)];
+        if (f >= F || row < 0 || row >= n) continue;
+        const int b = bins[(size_t)row * stride + f];
+        if (b >= max_bin) continue;
+        hist_add_global(hist + ((size_t)f * max_bin + b) * 3, qg[row], qh[row], 1);
+    }
+}
+
+// LDS form: grid = (items, feature tiles); an item is one row chunk of a segment.  The tile and the rotated walk of gbdt_hist_lds_kernel.
+__global__ void __launch_bounds__(kBlock)
+gbdt_hist_seg_lds_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg, const int32_t *__restrict__ qh,
+                         const int32_t *__restrict__ rows, int64_t nrows, const int32_t *__restrict__ segs, int K,
+                         const int32_t *__restrict__ items, int F, int max_bin, int64_t *__restrict__ pool, int nslots) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gbdt_smem[];
+    int64_t r0 = 0, r1 = 0;
+    const GbdtSeg s = gbdt_hist_item(segs, K, items + (int64_t)blockIdx.x * 3, nrows, nslots, r0, r1);
+    if (!s.ok || r1 == r0) return;
+    int64_t *hist = pool + (int64_t)s.slot * F * max_bin * 3;
+    const int cells = kGbdtTile * max_bin;
+    u64 *lg = reinterpret_cast<u64 *>(gbdt_smem), *lh = lg + cells;
+    uint32_t *lc = reinterpret_cast<uint32_t *>(lh + cells);
+    const int tid = threadIdx.x, f0 = blockIdx.y * kGbdtTile;
+    for (int e = tid; e < cells; e += kBlock) { lg[e] = 0; lh[e] = 0; lc[e] = 0; }
+    __syncthreads();
+    const int nf = min(kGbdtTile, F - f0);
+    for (int64_t i = r0 + tid; i < r1; i += kBlock) {
+        const int row = rows[i];
+        if (row < 0 || row >= n) continue;
+        const uint4 bv = *reinterpret_cast<const uint4 *>(bins + (size_t)row * stride + f0);
+        const u64 g = (u64)(int64_t)qg[row], h = (u64)(int64_t)qh[row];
+#pragma unroll
+        for (int k = 0; k < kGbdtTile; ++k) {
+            const int f = (k + tid) & (kGbdtTile - 1);
+            const uint32_t w = (f >> 2) == 0 ? bv.x : (f >> 2) == 1 ? bv.y : (f >> 2) == 2 ? bv.z : bv.w;
+            const int b = (w >> ((f & 3) * 8)) & 0xff;
+            if (f < nf && b < max_bin) {
+                const int c = f * max_bin + b;
+                atomicAdd(&lg[c], g);
+                atomicAdd(&lh[c], h);
+                atomicAdd(&lc[c], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < nf * max_bin; e += kBlock) {
+        const uint32_t c = lc[e];
+        if (c) hist_add_global(hist + ((size_t)f0 * max_bin + e) * 3, (int64_t)lg[e], (int64_t)lh[e], (int64_t)c);
+    }
+}
+
+// trips [K][3] = (parent slot, child slot, out slot): grid = (K, chunks of one histogram)
+__global__ void __launch_bounds__(kBlock)
+gbdt_hist_sub_seg_kernel(int64_t *__restrict__ pool, int nslots, int64_t slot_elems, const int32_t *__restrict__ trips) {
+    const int p = trips[blockIdx.x * 3], c = trips[blockIdx.x * 3 + 1], o = trips[blockIdx.x * 3 + 2];
+    if (p < 0 || p >= nslots || c < 0 || c >= nslots || o < 0 || o >= nslots) return;
+    const int64_t *pp = pool + p * slot_elems, *cp = pool + c * slot_elems;
+    int64_t *op = pool + o * slot_elems;
+    for (int64_t e = (int64_t)blockIdx.y * kBlock + threadIdx.x; e < slot_elems; e += (int64_t)gridDim.y * kBlock) op[e] = pp[e] - cp[e];
+}
+
+// The batched stable partition.  segs [K][4] = (start, count, feature, bin) over rows [nrows]; blocks [NB][2] = (segment, j): workgroup b owns
+// the entries j * 1024 .. of its segment, and a segment's blocks stand together in ascending j, so block b - j is the segment's first.
+struct GbdtPartSeg { int start, count, feature, bin, nblk; bool ok; };
+__device__ __forceinline__ GbdtPartSeg gbdt_part_block(const int32_t *__restrict__ segs, int K, const int32_t *__restrict__ blocks, int b, int NB,
+                                                       int64_t nrows, int F, int &j) {
+    GbdtPartSeg s{0, 0, 0, 0, 0, false};
+    const int k = blocks[b * 2];
+    j = blocks[b * 2 + 1];
+    if (k < 0 || k >= K) return s;
+    s.start = segs[k * 4]; s.count = segs[k * 4 + 1]; s.feature = segs[k * 4 + 2]; s.bin = segs[k * 4 + 3];
+    if (s.start < 0 || s.count < 0 || (int64_t)s.start + s.count > nrows || s.feature < 0 || s.feature >= F || s.bin < 0 || s.bin > 255) return s;
+    s.nblk = (int)(((int64_t)s.count + kGbdtPartRows - 1) / kGbdtPartRows);
+    if (j < 0 || j >= s.nblk || b - j < 0 || (int64_t)b - j + s.nblk > NB) return s;
+    s.ok = true;
+    return s;
+}
+
+__global__ void __launch_bounds__(kBlock)
+gbdt_part_seg_count_kernel(const uint8_t *__restrict__ bins, int stride, int n, int F, const int32_t *__restrict__ rows, int64_t nrows,
+                           const int32_t *__restrict__ segs, int K, const int32_t *__restrict__ blocks, int NB, int32_t *__restrict__ counts) {
+    __shared__ int32_t tot;
+    int j;
+    const GbdtPartSeg s = gbdt_part_block(segs, K, blocks, blockIdx.x, NB, nrows, F, j);
+    if (!s.ok) { if (threadIdx.x == 0) counts[blockIdx.x] = 0; return; }
+    if (threadIdx.x == 0) tot = 0;
+    __syncthreads();
+    int c = 0, row;
+    for (int st = 0; st < kPartSteps; ++st)
+        c += part_goes_left(bins, stride, n, rows + s.start, ((int64_t)j * kPartSteps + st) * kBlock + threadIdx.x, s.count, s.feature, s.bin, row) ? 1 : 0;
+    atomicAdd(&tot, c);
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = tot;
+}
+
+// counts [NB] -> their exclusive prefix over all blocks, in place, counts[NB] = the total: the scatter takes differences within a segment
+// (the lefts ahead of block b in its segment = prefix[b] - prefix[b - j]), which is the segmented scan.  One workgroup.
+__global__ void __launch_bounds__(kBlock)
+gbdt_part_seg_scan_kernel(int32_t *__restrict__ counts, int nb) {
+    __shared__ int32_t seg[kBlock];
+    const int t = threadIdx.x, per = (nb + kBlock - 1) / kBlock;
+    const int lo = min(t * per, nb), hi = min(lo + per, nb);
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += counts[i];
+    seg[t] = s;
+    __syncthreads();
+    for (int d = 1; d < kBlock; d <<= 1) {
+        const int o = t >= d ? seg[t - d] : 0;
+        __syncthreads();
+        seg[t] += o;
+        __syncthreads();
+    }
+    int run = seg[t] - s;
+    for (int i = lo; i < hi; ++i) { const int c = counts[i]; counts[i] = run; run += c; }
+    if (t == kBlock - 1) counts[nb] = seg[t];
+}
+
+__global__ void __launch_bounds__(kBlock)
+gbdt_part_seg_scatter_kernel(const uint8_t *__restrict__ bins, int stride, int n, int F, const int32_t *__restrict__ rows, int64_t nrows,
+                             const int32_t *__restrict__ segs, int K, const int32_t *__restrict__ blocks, int NB,
+                             const int32_t *__restrict__ counts, int32_t *__restrict__ out, int32_t *__restrict__ left_counts) {
+    __shared__ int32_t wave_left[kBlock / kWave];
+    int j;
+    const GbdtPartSeg s = gbdt_part_block(segs, K, blocks, blockIdx.x, NB, nrows, F, j);
+    if (!s.ok) return;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const int first = blockIdx.x - j;
+    int left_before = counts[blockIdx.x] - counts[first];
+    const int total_left = counts[first + s.nblk] - counts[first];
+    if (j == 0 && threadIdx.x == 0) left_counts[blocks[blockIdx.x * 2]] = total_left;
+    const int32_t *srows = rows + s.start;
+    int32_t *sout = out + s.start;
+    for (int st = 0; st < kPartSteps; ++st) {
+        const int64_t i = ((int64_t)j * kPartSteps + st) * kBlock + threadIdx.x;
+        int row;
+        const bool left = part_goes_left(bins, stride, n, srows, i, s.count, s.feature, s.bin, row);
+        const unsigned long long mask = __ballot(left);
+        if (lane == 0) wave_left[wave] = __popcll(mask);
+        __syncthreads();
+        int before = left_before + __popcll(mask & ((1ull << lane) - 1));
+        int step_left = 0;
+        for (int w = 0; w < kBlock / kWave; ++w) { if (w < wave) before += wave_left[w]; step_left += wave_left[w]; }
+        const int64_t pos = left ? before : total_left + (i - before);            // `before` = the lefts ahead of entry i
+        if (i < s.count && pos >= 0 && pos < s.count) sout[pos] = row;             // a table that lies about its blocks cannot leave the segment
         left_before += step_left;
         __syncthreads();
     }
@@ -501,5 +705,98 @@ extern "C" int ptr_gbdt_predict(const float *X, int64_t n, int F, const int32_t 
     if (ntrees > 0 && (!feature || !threshold || !left || !right || !value || !tree_offsets)) { set_error("%s: NULL tree array", who); return PTR_ERR_INVALID_ARG; }
     hipLaunchKernelGGL(gbdt_predict_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), X, n, F, feature, threshold, left,
                        right, value, tree_offsets, ntrees, out);
+    return check_hip(hipGetLastError(), who);
+}
+
+// ---------------------------------------------------------------- the batched entry points of a depth-wise level
+enum { kCheckMaxBin = 1, kCheckBins = 2 };
+static int check_level_common(const char *who, int64_t n, int F, int stride, int max_bin, int K, int what) {
+    if (K < 0) { set_error("%s: negative table length (K=%d)", who, K); return PTR_ERR_INVALID_ARG; }
+    if (F < 1) { set_error("%s: F must be >= 1, got %d", who, F); return PTR_ERR_INVALID_ARG; }
+    if (what & kCheckMaxBin) if (int rc = check_max_bin(max_bin, who)) return rc;
+    if (what & kCheckBins) if (int rc = check_bins_layout(n, F, stride, who)) return rc;
+    return 0;
+}
+
+extern "C" int ptr_gbdt_histogram_segments(const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows,
+                                           int64_t nrows, const int32_t *segs, int K, const int32_t *items, int n_direct, int n_lds, int F,
+                                           int max_bin, int64_t *pool, int nslots, void *stream) {
+    const char *who = "ptr_gbdt_histogram_segments";
+    if (int rc = check_level_common(who, n, F, stride, max_bin, K, kCheckMaxBin | kCheckBins)) return rc;
+    if (n_direct < 0 || n_lds < 0 || nrows < 0 || nrows > INT32_MAX || nslots < 0) {
+        set_error("%s: bad size (n_direct=%d, n_lds=%d, nrows=%lld, nslots=%d)", who, n_direct, n_lds, (long long)nrows, nslots);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (K == 0 || n_direct + (int64_t)n_lds == 0) return 0;
+    if (!bins || !qg || !qh || !rows || !segs || !items || !pool) { set_error("%s: NULL pointer (bins, qg, qh, rows, segs, items or pool)", who); return PTR_ERR_INVALID_ARG; }
+    if (reinterpret_cast<uintptr_t>(bins) & 15) { set_error("%s: bins must be 16-byte aligned", who); return PTR_ERR_INVALID_ARG; }
+    const GbdtSegForm form = gbdt_hist_segments_form(kGbdtDirectRows + 1, F, max_bin, 0);
+    if (n_direct > 0)
+        hipLaunchKernelGGL(gbdt_hist_seg_direct_kernel, dim3(n_direct, form.tiles), dim3(kBlock), 0, as_stream(stream), bins, stride, (int)n, qg, qh, rows,
+                           nrows, segs, K, items, F, max_bin, pool, nslots);
+    if (n_lds > 0) {
+        if (int rc = allow_lds(gbdt_hist_seg_lds_kernel, (size_t)form.lds_bytes)) return rc;
+        hipLaunchKernelGGL(gbdt_hist_seg_lds_kernel, dim3(n_lds, form.tiles), dim3(kBlock), (size_t)form.lds_bytes, as_stream(stream), bins, stride, (int)n,
+                           qg, qh, rows, nrows, segs, K, items + (int64_t)n_direct * 3, F, max_bin, pool, nslots);
+    }
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_hist_sub_segments(int64_t *pool, int nslots, int F, int max_bin, const int32_t *trips, int K, void *stream) {
+    const char *who = "ptr_gbdt_hist_sub_segments";
+    if (int rc = check_level_common(who, 0, F, 0, max_bin, K, kCheckMaxBin)) return rc;
+    if (nslots < 0) { set_error("%s: negative size (nslots=%d)", who, nslots); return PTR_ERR_INVALID_ARG; }
+    if (K == 0) return 0;
+    if (!pool || !trips) { set_error("%s: NULL pointer (pool or trips)", who); return PTR_ERR_INVALID_ARG; }
+    const int64_t elems = (int64_t)F * max_bin * 3;
+    hipLaunchKernelGGL(gbdt_hist_sub_seg_kernel, dim3(K, grid_for(elems, 64)), dim3(kBlock), 0, as_stream(stream), pool, nslots, elems, trips);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_best_split_slots(const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin, const int32_t *nbins,
+                                         const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf, double min_sum_hessian_in_leaf,
+                                         double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream) {
+    const char *who = "ptr_gbdt_best_split_slots";
+    if (int rc = check_level_common(who, 0, F, 0, max_bin, K, kCheckMaxBin)) return rc;
+    if (nslots < 0) { set_error("%s: negative size (nslots=%d)", who, nslots); return PTR_ERR_INVALID_ARG; }
+    if (!(lambda_l2 >= 0.0) || !(min_sum_hessian_in_leaf == min_sum_hessian_in_leaf) || !(min_gain_to_split == min_gain_to_split)) {
+        set_error("%s: lambda_l2 must be >= 0 and no threshold may be NaN", who);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (K == 0) return 0;
+    if (!pool || !slots || !nbins || !expo || !ws || !rec) { set_error("%s: NULL pointer (pool, slots, nbins, expo, ws or rec)", who); return PTR_ERR_INVALID_ARG; }
+    const int64_t items = (int64_t)K * F;
+    hipLaunchKernelGGL(gbdt_split_feature_slots_kernel, dim3((unsigned)((items + 3) / 4)), dim3(kBlock), 0, as_stream(stream), pool, nslots, slots, K, F,
+                       max_bin, nbins, expo, lambda_l2, min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws);
+    hipLaunchKernelGGL(gbdt_split_leaf_kernel, dim3(K), dim3(kWave), 0, as_stream(stream), ws, F, rec);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" size_t ptr_gbdt_partition_segments_ws_ints(int64_t nblocks) { return nblocks <= 0 ? 1 : (size_t)nblocks + 1; }
+
+extern "C" int ptr_gbdt_partition_segments(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t nrows, const int32_t *segs,
+                                           int K, const int32_t *blocks, int nblocks, int32_t *out, int32_t *left_counts, int32_t *ws,
+                                           int64_t ws_ints, void *stream) {
+    const char *who = "ptr_gbdt_partition_segments";
+    if (int rc = check_level_common(who, n, F, stride, 0, K, kCheckBins)) return rc;
+    if (nblocks < 0 || nrows < 0 || nrows > INT32_MAX) { set_error("%s: bad size (nblocks=%d, nrows=%lld)", who, nblocks, (long long)nrows); return PTR_ERR_INVALID_ARG; }
+    if (nrows > 0 && (!rows || !out)) { set_error("%s: NULL pointer (rows or out)", who); return PTR_ERR_INVALID_ARG; }
+    if (nrows > 0 && rows == out) { set_error("%s: out must not be rows (the partition is not done in place)", who); return PTR_ERR_INVALID_ARG; }
+    if (K > 0 && (!segs || !left_counts)) { set_error("%s: NULL pointer (segs or left_counts)", who); return PTR_ERR_INVALID_ARG; }
+    if (K > 0 && nblocks > 0 && (!bins || !blocks || !ws)) { set_error("%s: NULL pointer (bins, blocks or ws)", who); return PTR_ERR_INVALID_ARG; }
+    if (K > 0 && nblocks > 0 && ws_ints < (int64_t)ptr_gbdt_partition_segments_ws_ints(nblocks)) {
+        set_error("%s: workspace too small (%lld int32, %lld needed)", who, (long long)ws_ints, (long long)ptr_gbdt_partition_segments_ws_ints(nblocks));
+        return PTR_ERR_INVALID_ARG;
+    }
+    hipStream_t s = as_stream(stream);
+    if (nrows > 0)                                                       // the positions outside every segment; the scatter overwrites the rest
+        if (int rc = check_hip(hipMemcpyAsync(out, rows, (size_t)nrows * sizeof(int32_t), hipMemcpyDeviceToDevice, s), who)) return rc;
+    if (K == 0) return 0;
+    if (int rc = check_hip(hipMemsetAsync(left_counts, 0, (size_t)K * sizeof(int32_t), s), who)) return rc;
+    if (nblocks == 0) return 0;
+    hipLaunchKernelGGL(gbdt_part_seg_count_kernel, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, K, blocks, nblocks, ws);
+    hipLaunchKernelGGL(gbdt_part_seg_scan_kernel, dim3(1), dim3(kBlock), 0, s, ws, nblocks);
+    hipLaunchKernelGGL(gbdt_part_seg_scatter_kernel, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, K, blocks, nblocks, ws, out,
+                       left_counts);
     return check_hip(hipGetLastError(), who);
 }

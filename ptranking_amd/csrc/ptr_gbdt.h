@@ -21,4 +21,26 @@ inline GbdtHistForm gbdt_hist_form(int64_t m, int F, int max_bin) {
     return {2, kGbdtTile, tiles, (int)(want < cap ? want : cap), kGbdtTile * max_bin * 20};
 }
 
+// The batched histogram (ptr_gbdt_histogram_segments): a segment of m rows inside a call whose LDS-form segments hold `total` rows together.
+// kind as above, by m alone; an LDS-form segment is cut into row chunks of chunk_rows, which grows with `total` so that a call stays at about
+// kGbdtMaxGroups workgroups.  launches: the most launches one call makes (one per form), however many segments it holds.
+struct GbdtSegForm { int kind; int tile; int tiles; int chunks; int lds_bytes; int chunk_rows; int direct_rows; int launches; };
+inline GbdtSegForm gbdt_hist_segments_form(int64_t m, int F, int max_bin, int64_t total) {
+    const int tiles = (F + kGbdtTile - 1) / kGbdtTile;
+    const int64_t cap = kGbdtMaxGroups / (tiles > 0 ? tiles : 1) > 1 ? kGbdtMaxGroups / (tiles > 0 ? tiles : 1) : 1;
+    int64_t per = ((total > 0 ? total : 0) + cap - 1) / cap;
+    per = (per + kBlock - 1) / kBlock * kBlock;
+    if (per < kGbdtChunkRows) per = kGbdtChunkRows;
+    if (per > (1 << 30)) per = 1 << 30;
+    GbdtSegForm f{0, kGbdtTile, tiles, 0, 0, (int)per, kGbdtDirectRows, 2};
+    if (m <= 0 || F <= 0) return f;
+    if (m <= kGbdtDirectRows) { f.kind = 1; f.chunks = 1; return f; }
+    f.kind = 2;
+    f.chunks = (int)((m + per - 1) / per);
+    f.lds_bytes = kGbdtTile * max_bin * 20;
+    return f;
+}
+
+constexpr int kGbdtPartRows = 1024;      // consecutive entries of a row list that one workgroup of the partition owns
+
 }  // namespace ptr

@@ -9,6 +9,7 @@ Shapes: preds / labels `[B, L]` (padded, row-major), optional `lens` int32 `[B]`
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -18,6 +19,7 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "ndeval_measures", "div_ideal_order", "NDEVAL_MEASURES","divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
            "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "gaussian_metric_objective", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES",
            "gbdt_bin", "gbdt_quantize", "gbdt_histogram", "gbdt_hist_sub", "gbdt_best_split", "gbdt_partition", "gbdt_add_leaf_values", "gbdt_predict",
+           "gbdt_histogram_segments", "gbdt_hist_sub_segments", "gbdt_best_split_slots", "gbdt_partition_segments", "gbdt_segment_items",
            "GBDT_MAX_BIN", "GBDT_RECORD"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
@@ -795,3 +797,128 @@ def gbdt_predict(X, feature, threshold, left, right, value, tree_offsets, ntrees
         _lib.call("ptr_gbdt_predict", _lib.ptr(X), X.shape[0], X.shape[1], _lib.ptr(feature), _lib.ptr(threshold), _lib.ptr(left), _lib.ptr(right),
                   _lib.ptr(value), _lib.ptr(tree_offsets), ntrees, _lib.ptr(out), _lib.current_stream(dev))
     return out
+
+
+# ---- one level of a depth-wise tree in batched passes.  The tables (segs, trips, slots) are small HOST arrays (numpy, or anything
+# np.asarray takes): the host knows every count from the split records it has read, builds the work lists and uploads each in one copy.
+def _gbdt_table(name, table, cols, device):
+    t = np.ascontiguousarray(np.asarray(table, dtype=np.int64).reshape(-1, cols) if cols > 1 else np.asarray(table, dtype=np.int64).reshape(-1))
+    if t.size and (t.min() < -2 ** 31 or t.max() >= 2 ** 31):
+        raise ValueError(f"{name} must hold int32 values")
+    return t, torch.from_numpy(t.astype(np.int32)).to(device)
+
+
+def _gbdt_pool(pool):
+    pool = _check("pool", pool, torch.int64)
+    if pool.dim() != 4 or pool.shape[3] != 3 or pool.shape[1] < 1:
+        raise ValueError(f"pool must be [slots, F >= 1, max_bin, 3], got {tuple(pool.shape)}")
+    _gbdt_max_bin(pool.shape[2])
+    return pool
+
+
+def _gbdt_seg_form(m, F, max_bin, total):
+    a, out = (C.c_int64 * 4)(int(m), int(F), int(max_bin), int(total)), (C.c_int32 * 8)()
+    if _lib.load().ptr_launch_form(b"ptr_gbdt_histogram_segments", a, 4, out, 8) != 0:
+        raise RuntimeError(_lib.load().ptr_last_error().decode())
+    return tuple(out)
+
+
+def gbdt_segment_items(counts, F, max_bin):
+    """The work list of gbdt_histogram_segments for segments of `counts` rows, on the host -> (items int64 [n, 3] = (segment, first row
+    within it, rows), n_direct, n_lds): the segments of at most 256 rows first, whole; then the longer ones in chunks of the row count
+    ptr_launch_form gives for the call's total.  Empty segments get no item."""
+    counts = np.asarray(counts, np.int64).reshape(-1)
+    direct_rows = _gbdt_seg_form(1, F, max_bin, 0)[6]
+    small = np.nonzero((counts > 0) & (counts <= direct_rows))[0]
+    large = np.nonzero(counts > direct_rows)[0]
+    chunk = _gbdt_seg_form(1, F, max_bin, int(counts[large].sum()))[5]
+    nch = (counts[large] + chunk - 1) // chunk
+    seg = np.repeat(large, nch)
+    begin = (np.arange(seg.size) - np.repeat(np.cumsum(nch) - nch, nch)) * chunk
+    items = np.concatenate([np.stack([small, np.zeros_like(small), counts[small]], axis=1),
+                            np.stack([seg, begin, np.minimum(chunk, counts[seg] - begin)], axis=1)]).astype(np.int64)
+    return items, int(small.size), int(seg.size)
+
+
+def gbdt_histogram_segments(bins, qg, qh, rows, segs, F, max_bin, pool):
+    """ADDS, for every segment (start, count, slot) of the host table segs [K, 3], the rows rows[start : start + count] into pool[slot]
+    (int64 [slots, F, max_bin, 3], zeroed by the caller): each slot gets the integers gbdt_histogram gives for that row list.  At most two
+    launches however many segments: the short ones in the direct form, the long ones cut into row chunks in the LDS form.  A segment that
+    leaves the row list or names a slot outside the pool is skipped."""
+    bins = _gbdt_bins(bins, F)
+    n, dev = bins.shape[0], bins.device
+    max_bin = _gbdt_max_bin(max_bin)
+    qg, qh = _check("qg", qg, torch.int32, (n,)), _check("qh", qh, torch.int32, (n,))
+    rows = _check("rows", rows, torch.int32)
+    if rows.dim() != 1:
+        raise ValueError(f"rows must be flat, got {tuple(rows.shape)}")
+    pool = _gbdt_pool(pool)
+    if pool.shape[1] != F or pool.shape[2] != max_bin:
+        raise ValueError(f"pool must be [slots, {F}, {max_bin}, 3], got {tuple(pool.shape)}")
+    host, segs_d = _gbdt_table("segs", segs, 3, dev)
+    K = host.shape[0]
+    if K == 0:
+        return pool
+    items, n_direct, n_lds = gbdt_segment_items(np.where((host[:, 0] >= 0) & (host[:, 0] + host[:, 1] <= rows.numel()), host[:, 1], 0), F, max_bin)
+    _, items_d = _gbdt_table("items", items, 3, dev)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_histogram_segments", _lib.ptr(bins), bins.shape[1], n, _lib.ptr(qg), _lib.ptr(qh), _lib.ptr(rows), rows.numel(),
+                  _lib.ptr(segs_d), K, _lib.ptr(items_d), n_direct, n_lds, F, max_bin, _lib.ptr(pool), pool.shape[0], _lib.current_stream(dev))
+    return pool
+
+
+def gbdt_hist_sub_segments(pool, trips):
+    """pool[out] = pool[parent] - pool[child] for every (parent, child, out) of the host table trips [K, 3], in one launch; out may be the
+    parent.  A triple that names a slot outside the pool is skipped."""
+    pool = _gbdt_pool(pool)
+    host, trips_d = _gbdt_table("trips", trips, 3, pool.device)
+    if host.shape[0]:
+        with torch.cuda.device(pool.device):
+            _lib.call("ptr_gbdt_hist_sub_segments", _lib.ptr(pool), pool.shape[0], pool.shape[1], pool.shape[2], _lib.ptr(trips_d), host.shape[0],
+                      _lib.current_stream(pool.device))
+    return pool
+
+
+def gbdt_best_split_slots(pool, slots, nbins, expo, lambda_l2=0.0, min_data_in_leaf=1, min_sum_hessian_in_leaf=1e-3, min_gain_to_split=0.0, out=None):
+    """gbdt_best_split over the histograms pool[slots[k]] (slots: a host list) -> int64 [K, 9] records, each bit-identical to gbdt_best_split
+    on a copy of that slot.  A slot outside the pool gives the record without a split."""
+    pool = _gbdt_pool(pool)
+    dev, F, max_bin = pool.device, pool.shape[1], pool.shape[2]
+    nbins = _check("nbins", nbins, torch.int32, (F,))
+    expo = _check("expo", expo, torch.int32, (2,))
+    host, slots_d = _gbdt_table("slots", slots, 1, dev)
+    K = host.shape[0]
+    rec = torch.empty((K, 9), device=dev, dtype=torch.int64) if out is None else _check("out", out, torch.int64, (K, 9))
+    ws = torch.empty((max(K * F, 1), 9), device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_best_split_slots", _lib.ptr(pool), pool.shape[0], _lib.ptr(slots_d), K, F, max_bin, _lib.ptr(nbins), _lib.ptr(expo),
+                  C.c_double(float(lambda_l2)), C.c_int64(int(min_data_in_leaf)), C.c_double(float(min_sum_hessian_in_leaf)),
+                  C.c_double(float(min_gain_to_split)), _lib.ptr(ws), _lib.ptr(rec), _lib.current_stream(dev))
+    return rec
+
+
+def gbdt_partition_segments(bins, rows, segs, F, out=None, left_counts=None):
+    """Stable partition of every segment (start, count, feature, bin) of the host table segs [K, 4] (disjoint) inside the row list `rows`, as
+    gbdt_partition would do each -> (out int32 like rows: a whole row list, the positions outside every segment copied; left_counts int32
+    [K] on the device).  A fixed number of launches however many segments; out must not be rows.  A segment that leaves the row list or
+    names a feature or bin out of range is left as it was."""
+    bins = _gbdt_bins(bins, F)
+    dev = bins.device
+    rows = _check("rows", rows, torch.int32)
+    if rows.dim() != 1:
+        raise ValueError(f"rows must be flat, got {tuple(rows.shape)}")
+    host, segs_d = _gbdt_table("segs", segs, 4, dev)
+    K = host.shape[0]
+    out = torch.empty_like(rows) if out is None else _check("out", out, torch.int32, tuple(rows.shape))
+    left_counts = torch.zeros(K, device=dev, dtype=torch.int32) if left_counts is None else _check("left_counts", left_counts, torch.int32, (K,))
+    per = 1024                                                               # kGbdtPartRows: the rows one workgroup owns
+    nblk = np.where((host[:, 0] >= 0) & (host[:, 1] > 0) & (host[:, 0] + host[:, 1] <= rows.numel()), (host[:, 1] + per - 1) // per, 0)
+    seg = np.repeat(np.arange(K), nblk)
+    blocks = np.stack([seg, np.arange(seg.size) - np.repeat(np.cumsum(nblk) - nblk, nblk)], axis=1)
+    _, blocks_d = _gbdt_table("blocks", blocks, 2, dev)
+    ws_ints = int(_lib.query("ptr_gbdt_partition_segments_ws_ints", C.c_int64(int(seg.size))))
+    ws = torch.empty(ws_ints, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_partition_segments", _lib.ptr(bins), bins.shape[1], bins.shape[0], F, _lib.ptr(rows), rows.numel(), _lib.ptr(segs_d), K,
+                  _lib.ptr(blocks_d), int(seg.size), _lib.ptr(out), _lib.ptr(left_counts), _lib.ptr(ws), ws_ints, _lib.current_stream(dev))
+    return out, left_counts

@@ -8,10 +8,16 @@ values than bins, every tree equals HistGradientBoostingRegressor's node for nod
 learning rate, the accumulation over rounds), and one tree equals DecisionTreeRegressor's exact greedy best-first tree.  Not pinned:
 LightGBM itself, the quantile binning rule for features of more distinct values than bins, and the ranking objectives inside the booster.
 
-    GBDT(params)       the booster: fit_bins(X) bins the features once and keeps them resident; update(grad, hess) grows ONE tree leaf-wise
-                        from device gradients and adds its leaf values to the resident training scores; predict / save_model / load_model
+    GBDT(params)       the booster: fit_bins(X) bins the features once and keeps them resident; update(grad, hess) grows ONE tree (leaf-wise, or
+                        depth-wise under grow_policy='depthwise') from device gradients and adds its leaf values to the resident training scores; predict / save_model / load_model
     LambdaMART(params)  the ranker: every round computes the gradient and the Hessian per document with tree_pair_grad_hess /
                         tree_listnet_grad_hess on the resident scores (no host copy), quantizes them and calls update
+
+Growth policies (grow_policy): 'leafwise', the default, splits the leaf of the largest gain and reads the two children's records back after
+every split; 'depthwise' splits ALL leaves of a level in one batched pass (partition, histograms of the smaller children, sibling
+subtraction, split scan over many leaves at once) and reads once per level; under the leaf cap it keeps the level's largest gains.  Where
+the cap cannot bind (num_leaves >= 2^max_depth) the two give the same trees, fp32 leaf values and scores bit for bit; depth-wise whole fits
+are pinned to scikit-learn with max_leaf_nodes=None as well (tests/golden/gbdt_sklearn_depth.npz).  GBDT.host_reads counts the reads.
 
 Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here: GOSS, EFB,
 categorical features, missing values (a non-finite feature raises: in bin_edges, in predict and for the eval_set of LambdaMART.fit), DART,
@@ -30,9 +36,10 @@ __all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS"
 # LightGBM's names, so the reference's lightgbm_para_dict passes through.  min_sum_hessian_in_leaf = 1e-3 is LightGBM's default too; the
 # reference's own dict sets 200, which suits LightGBM's built-in lambdarank Hessians, not the sums of tree.hip.
 DEFAULT_PARAMS = {"learning_rate": 0.1, "num_leaves": 31, "num_trees": 100, "min_data_in_leaf": 20, "min_sum_hessian_in_leaf": 1e-3,
-                  "lambda_l2": 0.0, "min_gain_to_split": 0.0, "max_bin": 255, "max_depth": -1}
+                  "lambda_l2": 0.0, "min_gain_to_split": 0.0, "max_bin": 255, "max_depth": -1, "grow_policy": "leafwise"}
 IGNORED_PARAMS = ("num_threads", "verbosity", "metric", "boosting_type", "objective", "eval_at")    # accepted, without a meaning here
 MODEL_FORMAT = 1
+GROW_POLICIES = ("leafwise", "depthwise")
 
 
 def _params(params):
@@ -50,6 +57,8 @@ def _params(params):
         p[k] = int(p[k])
     for k in ("learning_rate", "min_sum_hessian_in_leaf", "lambda_l2", "min_gain_to_split"):
         p[k] = float(p[k])
+    if p["grow_policy"] not in GROW_POLICIES:
+        raise ValueError(f"grow_policy {p['grow_policy']!r} is not implemented: only 'leafwise' and 'depthwise'")
     if not p["learning_rate"] > 0.0:
         raise ValueError(f"learning_rate must be > 0, got {p['learning_rate']}")
     if p["num_leaves"] < 1 or p["num_trees"] < 0 or p["min_data_in_leaf"] < 0:
@@ -131,8 +140,8 @@ _NO_SPLIT = (-np.inf, -1, -1, (0, 0, 0), (0, 0, 0))
 
 class GBDT:
     """The booster.  GBDT(params, X=None): params under LightGBM's names (DEFAULT_PARAMS; the keys of IGNORED_PARAMS are accepted and
-    ignored; boosting_type other than 'gbdt' raises).  update() costs one host synchronisation per split: the host reads the two children's
-    records (72 bytes each) to pick the next leaf."""
+    ignored; boosting_type other than 'gbdt' raises).  Under grow_policy='leafwise' update() costs one host synchronisation per split: the
+    host reads the two children's records (72 bytes each) to pick the next leaf; under 'depthwise' one per level.  host_reads counts them."""
 
     def __init__(self, params=None, X=None, device=None):
         self.params = _params(params)
@@ -142,6 +151,7 @@ class GBDT:
         self._device = device
         self._flat = None
         self.n = 0
+        self.host_reads = 0                # device-to-host reads inside update(), over the booster's life: what a growth policy costs
         if X is not None:
             self.fit_bins(X)
 
@@ -172,6 +182,7 @@ class GBDT:
         self._flag = torch.zeros(1, device=dev, dtype=torch.int32)
         self._lc = torch.zeros(1, device=dev, dtype=torch.int32)
         self._rec = torch.zeros((2, 9), device=dev, dtype=torch.int64)
+        self._lrec = torch.zeros((max(p["num_leaves"], 2), 9), device=dev, dtype=torch.int64)      # a depth-wise level's records
         self._pool = torch.zeros((max(p["num_leaves"], 1), self.F, p["max_bin"], 3), device=dev, dtype=torch.int64)
         return self
 
@@ -187,7 +198,7 @@ class GBDT:
 
     def update(self, grad, hess):
         """Grows one tree from device fp32 gradients and Hessians [n]: the leaf with the largest gain is split (ties: the older leaf) until
-        num_leaves is reached or no leaf has a valid split; the leaf values -G / (H + lambda_l2) * learning_rate are added to the resident
+        num_leaves is reached or no leaf has a valid split (grow_policy='depthwise': level by level, _grow_depthwise); the leaf values -G / (H + lambda_l2) * learning_rate are added to the resident
         training scores.  Returns the tree (a dict of numpy arrays).  A NaN or an infinity in grad / hess raises."""
         if self.n == 0 or self.edges is None:
             raise RuntimeError("call fit_bins(X) first")
@@ -198,10 +209,15 @@ class GBDT:
         F.gbdt_histogram(self.bins, self._qg, self._qh, None, nf, mb, hist=pool[0])
         self._search(0, 0)
         head = torch.cat([self._rec[0], pool[0, 0].sum(0), self._expo.to(torch.int64), self._flag.to(torch.int64)]).cpu().numpy()
+        self.host_reads += 1
         if head[14]:
             self._flag.zero_()
             raise FloatingPointError("the gradients or Hessians of this round hold a NaN or an infinity")
         expo = (int(head[12]), int(head[13]))
+        if p["grow_policy"] == "depthwise":
+            feature, threshold, left, right, starts, g_sum, h_sum = self._grow_depthwise(head)
+            value = np.array([leaf_value(g, h, expo, p["lambda_l2"], p["learning_rate"]) for g, h in zip(g_sum, h_sum)], np.float32)
+            return self._finish(feature, threshold, left, right, starts, value)
         root_rec = _record(head[:9]) if self._splittable(self.n, 0) else _NO_SPLIT
         leaves = [_Leaf(0, self.n, 0, 0, -1, 0, int(head[9]), int(head[10]), root_rec)]
         feature, threshold, left, right = [], [], [], []
@@ -235,12 +251,17 @@ class GBDT:
                     if can[k]:
                         self._search(c.slot, k)
                 recs = self._rec.cpu().numpy()                           # the one synchronisation of this split
+                self.host_reads += 1
                 for k, c in enumerate((lchild, rchild)):
                     if can[k]:
                         c.rec = _record(recs[k])
         value = np.array([leaf_value(c.g, c.h, expo, p["lambda_l2"], p["learning_rate"]) for c in leaves], np.float32)
-        order = sorted(range(len(leaves)), key=lambda i: leaves[i].start)
-        offsets = np.array([leaves[i].start for i in order] + [self.n], np.int32)
+        return self._finish(feature, threshold, left, right, [c.start for c in leaves], value)
+
+    def _finish(self, feature, threshold, left, right, starts, value):
+        """Adds the leaf values (by leaf index, with the leaves' first positions in the row list) to the training scores; keeps the tree."""
+        order = sorted(range(len(starts)), key=lambda i: starts[i])
+        offsets = np.array([starts[i] for i in order] + [self.n], np.int32)
         dev = self.scores.device
         F.gbdt_add_leaf_values(self.scores, self._rows, torch.from_numpy(offsets).to(dev), torch.from_numpy(value[order]).to(dev))
         t = {"feature": np.array(feature, np.int32), "threshold": np.array(threshold, np.float32), "left": np.array(left, np.int32),
@@ -248,6 +269,73 @@ class GBDT:
         self.trees.append(t)
         self._flat = None
         return t
+
+    def _grow_depthwise(self, head):
+        """Depth-wise growth from the root's record (head, as update read it): every level is one batched pass over all its leaves
+        (partition, histograms of the smaller children, sibling subtraction, split scan) and ONE host read, the records of the level's
+        searched children.  -> (feature, threshold, left, right, the leaves' first positions, their sums qg and qh), by node / leaf index."""
+        p, nf, mb, cap = self.params, self.F, self.params["max_bin"], self.params["num_leaves"]
+        pool = self._pool
+        min_count, max_depth = 2 * max(p["min_data_in_leaf"], 1), p["max_depth"]
+        splittable = lambda count, depth: (count >= min_count) & (max_depth <= 0 or depth < max_depth)      # _splittable over a level
+        feature, threshold = np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.float32)
+        left, right = np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.int32)
+        starts, g_sum, h_sum = np.zeros(cap, np.int64), np.zeros(cap, np.int64), np.zeros(cap, np.int64)
+        g_sum[0], h_sum[0] = head[9], head[10]
+        nodes, leaves, free, depth = 0, 1, 1, 0
+        self._rows.copy_(self._arange)
+        # the frontier, in ascending start: leaf index, start, count, histogram slot, parent node, side, split record (gain -inf: none)
+        leaf, start, count, slot = np.zeros(1, np.int64), np.zeros(1, np.int64), np.full(1, self.n, np.int64), np.zeros(1, np.int64)
+        parent, side = np.full(1, -1, np.int64), np.zeros(1, np.int64)
+        rec = np.asarray(head[:9], np.int64).reshape(1, 9).copy()
+        while True:
+            gain = rec[:, 0].copy().view(np.float64)
+            keep = np.nonzero(splittable(count, depth) & (gain > -np.inf))[0]
+            budget = cap - leaves
+            if keep.size == 0 or budget <= 0:
+                break
+            if keep.size > budget:                                         # the cap: the largest gains, ties to the smaller start
+                keep = np.sort(keep[np.lexsort((start[keep], -gain[keep]))[:budget]])
+            k = keep.size
+            f, b, lsum, rsum = rec[keep, 1], rec[keep, 2], rec[keep, 3:6], rec[keep, 6:9]
+            node = nodes + np.arange(k)
+            feature[node], threshold[node] = f, self.edges[f, b]
+            left[node], right[node] = ~leaf[keep], ~(leaves + np.arange(k))
+            has = parent[keep] >= 0
+            for arr, sd in ((left, 0), (right, 1)):
+                sel = has & (side[keep] == sd)
+                arr[parent[keep][sel]] = node[sel]
+            F.gbdt_partition_segments(self.bins, self._rows, np.stack([start[keep], count[keep], f, b], axis=1), nf, out=self._tmp)
+            self._rows, self._tmp = self._tmp, self._rows
+            # the children, interleaved (left, right): ascending start again
+            c_leaf = np.stack([leaf[keep], leaves + np.arange(k)], axis=1)
+            c_start = np.stack([start[keep], start[keep] + lsum[:, 2]], axis=1)
+            c_count = np.stack([lsum[:, 2], rsum[:, 2]], axis=1)
+            starts[c_leaf], g_sum[c_leaf], h_sum[c_leaf] = c_start, np.stack([lsum[:, 0], rsum[:, 0]], axis=1), np.stack([lsum[:, 1], rsum[:, 1]], axis=1)
+            nodes, leaves, depth = nodes + k, leaves + k, depth + 1
+            can = splittable(c_count, depth)
+            c_slot = np.repeat(slot[keep][:, None], 2, axis=1)
+            c_rec = np.zeros((k, 2, 9), np.int64)
+            c_rec[:, :, 0], c_rec[:, :, 1:3] = np.float64(-np.inf).view(np.int64), -1
+            pairs = np.nonzero(can.any(axis=1))[0] if leaves < cap else np.zeros(0, np.int64)
+            if pairs.size:
+                small = (c_count[pairs, 0] > c_count[pairs, 1]).astype(np.int64)      # the smaller child's side; <= goes left
+                fresh = free + np.arange(pairs.size)
+                free += pairs.size
+                c_slot[pairs, small] = fresh
+                pool[int(fresh[0]):int(fresh[-1]) + 1].zero_()
+                F.gbdt_histogram_segments(self.bins, self._qg, self._qh, self._rows, np.stack([c_start[pairs, small], c_count[pairs, small], fresh], axis=1),
+                                          nf, mb, pool)
+                F.gbdt_hist_sub_segments(pool, np.stack([slot[keep][pairs], fresh, slot[keep][pairs]], axis=1))   # the larger child, in the parent's slot
+                sp, ss = np.nonzero(can[pairs])
+                out = self._lrec[:sp.size]
+                F.gbdt_best_split_slots(pool, c_slot[pairs[sp], ss], self._nbins_d, self._expo, p["lambda_l2"], p["min_data_in_leaf"],
+                                        p["min_sum_hessian_in_leaf"], p["min_gain_to_split"], out=out)
+                c_rec[pairs[sp], ss] = out.cpu().numpy()                   # the one synchronisation of this level
+                self.host_reads += 1
+            leaf, start, count, slot = c_leaf.reshape(-1), c_start.reshape(-1), c_count.reshape(-1), c_slot.reshape(-1)
+            parent, side, rec = np.repeat(node, 2), np.tile(np.array([0, 1], np.int64), k), c_rec.reshape(-1, 9)
+        return feature[:nodes], threshold[:nodes], left[:nodes], right[:nodes], starts[:leaves].tolist(), g_sum[:leaves].tolist(), h_sum[:leaves].tolist()
 
     # ---- the model
     def flat(self):
