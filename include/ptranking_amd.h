@@ -428,6 +428,76 @@ int ptr_mdprank_sample_fwd_bwd(const float *preds, const float *labels, const in
                                float temperature, int distribution, uint64_t seed, int64_t q0, const float *unif, float *loss_out,
                                float *loss_q, float *grad, int64_t *perm_out, void *stream);
 
+/* ---- The adversarial frame's IRGAN point and pair machines (csrc/irgan.hip): sampling documents from the generator's distribution and the
+ * two players' losses.  The three symbols below are ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
+ * Reference: ptranking/ltr_adversarial/pointwise/irgan_point.py, ptranking/ltr_adversarial/pairwise/irgan_pair.py, one query per step there;
+ * here a padded batch [B,L] with lens, and num_pos int32 [B] = the number of relevant documents of a list, which sit at its front (the
+ * reference's train_presort assert); num_pos is clamped to 0 .. lens.  n = lens[q], P = num_pos[q] below.
+ * Uniforms: u(seed, q0 + q, stream, index) of ptr_pl_uniforms; `unif` (nullable) replaces the hash, laid out [B, streams, L] as
+ * ptr_pl_uniforms(B, L, streams) writes it.
+ * Sampling rules.
+ *   with replacement     the inverse CDF on the inclusive prefix sum C of the unnormalised fp32 weights w_i: draw k takes the smallest i with
+ *                        u_k * C_{n-1} < C_i, the last document when there is none, and from there the nearest document at or below with
+ *                        w_i > 0.
+ *   without replacement  V rounds of arg-max over key_i = log-weight_i + gumbel(u_i), order (key descending, index ascending): the law of
+ *                        torch.multinomial(replacement=False), with no weight that can underflow (gumbel as in ptr_pl_sample).
+ *   positives            the V largest of P uniform keys, (key descending, index ascending): V distinct documents of 0 .. P-1, the law of
+ *                        randperm(P)[:V].
+ * ptr_irgan_sample — the documents both players train on.  S = samples per query, 1 .. PTR_IRGAN_MAX_SAMPLES.  Writes pos_idx, neg_idx int64
+ *   [B,S] (0 beyond the valid count) and nsel int32 [B] = V.  unif [B,2,L]: stream 0, index i = the key of positive i; stream 1 = the
+ *   negatives, index k = draw k (with replacement) or index i = document i (without).  z = preds / T.
+ *   PTR_IRGAN_POINT_D   V = min(P, S); neg_idx: V i.i.d. draws with replacement, w_i = exp(z_i - max z) over the n documents
+ *                       (irgan_point.py:130-146)
+ *   PTR_IRGAN_PAIR_D    V = min(P, n - P, S); neg_idx: V draws without replacement, log-weight z_i, documents i >= P only (irgan_pair.py:140-161)
+ *   PTR_IRGAN_PAIR_G    V as PAIR_D; neg_idx: V draws without replacement, log-weight log sigmoid(z_i), all n documents (irgan_pair.py:207-211)
+ *   A list with a NaN score gets nsel = 0.
+ * ptr_irgan_point_gen_fwd_bwd — the generator step of IRGAN_Point (irgan_point.py:184-217), sampling, loss and gradient in one launch.
+ *   p = softmax(g_preds / T), q_i = (1 - lambda) p_i + [i < P] lambda / P; K = draws_per_pos * P documents i.i.d. from q by the inverse CDF on
+ *   w_i = (1 - lambda) e_i + [i < P] lambda Z / P (e_i = exp(z_i - max z), Z = sum e), draw k from stream k / L, index k % L (unif
+ *   [B, draws_per_pos, L]); c_i = the times i was drawn; r_i = 2 (d_preds_i - 0.5) with d_preds [B,L] the discriminator's outputs;
+ *   loss_q = -(1/K) sum_i c_i r_i log p_i p_i / q_i (log p the log-softmax; the importance weight p / q carries gradient, as in the reference);
+ *   with a_i = [i < P] lambda / P and h_i = -(1/K) c_i r_i (p_i / q_i) (1 + log p_i a_i / q_i):  grad_j = (h_j - p_j sum_i h_i) / T.
+ *   Outputs: loss_q [B], valid_q [B] (1.0 where the query trained), grad [B,L] (0 on padding), loss_out [1] = sum of loss_q (nullable),
+ *   counts int32 [B,L] (nullable).  P = 0 or n = 0: loss 0, gradient 0, valid 0 (the reference `continue`s), whatever the scores.  A NaN
+ *   score in g_preds of a list with P > 0: the loss and every real gradient entry of that list are NaN, valid 1, counts 0 (the reference
+ *   stops training there).
+ * ptr_irgan_sel_fwd_bwd — the losses on selected documents, loss and gradient in one launch.  nsel int32 [B] = V (clamped to 0 .. S).
+ *   The discriminator's forms take x = its predictions on the compact batch [B,2S], positives in columns 0 .. V-1, negatives in V .. 2V-1,
+ *   and write grad [B,2S]; d_sel, neg_idx, lens and L are not read (L >= 1):
+ *   PTR_IRGAN_SEL_POINT_D     BCEWithLogits against labels 1 | 0, the mean over 2 V (irgan_point.py:161-169), softplus evaluated stably
+ *   PTR_IRGAN_SEL_PAIR_D_SVM  mean max(0, 1 - (d_pos - d_neg)) (irgan_pair.py:182); at 1 - (d_pos - d_neg) == 0 half the gradient, as torch.max
+ *   PTR_IRGAN_SEL_PAIR_D_LOG  -mean log sigmoid(d_pos - d_neg), through log-sigmoid (:184)
+ *   The generator's forms take x = g_preds [B,L], neg_idx [B,S] and d_sel [B,2S] (the discriminator's predictions, laid out as above), form
+ *   reward_k = sigmoid(max(0, 1 - (d_pos_k - d_neg_k))) (SVM) or log sigmoid(d_neg_k - d_pos_k) (LOG) (irgan_pair.py:39-42) and
+ *   loss_q = -mean_k log sigmoid(g_neg_k / T) reward_k (:216-218); grad [B,L] is non-zero at the named documents only (each named once; an
+ *   index outside 0 .. n-1 names nothing):
+ *   PTR_IRGAN_SEL_PAIR_G_SVM, PTR_IRGAN_SEL_PAIR_G_LOG
+ *   Outputs loss_q [B], valid_q [B], loss_out [1] (nullable).  nsel = 0: loss 0, gradient 0, valid 0.
+ * Forms (ptr_launch_form): lists of up to 256 documents one wavefront per query, four queries per workgroup; longer lists one workgroup of
+ * 256 threads per query; the discriminator's forms of ptr_irgan_sel_fwd_bwd always one wavefront.  LDS per query: 8 (sample), 12 (generator)
+ * or 4 (selected) bytes x round_up(L, 4).  No floating-point atomics; the draw counts are integer LDS atomics.  A query's bits depend on
+ * (its data, L, the parameters, seed, q0 + q) alone.
+ * PTR_ERR_INVALID_ARG (before any HIP call): B < 0, L <= 0, L > PTR_MAX_LIST_LEN, S outside 1 .. PTR_IRGAN_MAX_SAMPLES, temperature <= 0,
+ * infinite or NaN, a mode out of range, lambda outside [0, 1), draws_per_pos outside 1 .. PTR_IRGAN_MAX_DRAWS_PER_POS, and with B > 0 a NULL
+ * required pointer (lens, unif, loss_out, counts are optional; d_sel and neg_idx only for the generator's forms). */
+#define PTR_IRGAN_MAX_SAMPLES 64
+#define PTR_IRGAN_MAX_DRAWS_PER_POS 64
+#define PTR_IRGAN_POINT_D 0
+#define PTR_IRGAN_PAIR_D 1
+#define PTR_IRGAN_PAIR_G 2
+#define PTR_IRGAN_SEL_POINT_D 0
+#define PTR_IRGAN_SEL_PAIR_D_SVM 1
+#define PTR_IRGAN_SEL_PAIR_D_LOG 2
+#define PTR_IRGAN_SEL_PAIR_G_SVM 3
+#define PTR_IRGAN_SEL_PAIR_G_LOG 4
+int ptr_irgan_sample(const float *preds, const int32_t *lens, const int32_t *num_pos, int B, int L, int S, int mode, float temperature,
+                     uint64_t seed, int64_t q0, const float *unif, int64_t *pos_idx, int64_t *neg_idx, int32_t *nsel, void *stream);
+int ptr_irgan_point_gen_fwd_bwd(const float *g_preds, const float *d_preds, const int32_t *lens, const int32_t *num_pos, int B, int L,
+                                float temperature, float lambda, int draws_per_pos, uint64_t seed, int64_t q0, const float *unif,
+                                float *loss_out, float *loss_q, float *valid_q, float *grad, int32_t *counts, void *stream);
+int ptr_irgan_sel_fwd_bwd(const float *x, const float *d_sel, const int64_t *neg_idx, const int32_t *nsel, const int32_t *lens, int B, int L,
+                          int S, int mode, float temperature, float *loss_out, float *loss_q, float *valid_q, float *grad, void *stream);
+
 /* Device tie-shuffled label-descending order (the role of arg_shuffle_ties, sampling_utils.py:13-28) from a
  * counter-based RNG: same distribution, NOT the torch.randperm stream (not parity-checked, statistically tested). */
 int ptr_shuffle_ties_order(const float *labels, const int32_t *lens, int B, int L, uint64_t seed, int64_t *perm,
@@ -737,6 +807,8 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *   ptr_gbdt_hist_sub_segments                   K                                        launches of one call (1), workgroup rows per triple
  *   ptr_gbdt_best_split_slots                    K                                        launches of one call (2), 0
  *   ptr_gbdt_partition_segments                  m                                        launches of one call (3), workgroups of a segment of m rows
+ *   ptr_irgan_sample, ptr_irgan_point_gen_fwd_bwd   L                                     G, queries per workgroup
+ *   ptr_irgan_sel_fwd_bwd                        mode, L                                  G, queries per workgroup
  * G: threads per query, DPT: documents per thread, TP: subtopic tile.  PTR_ERR_INVALID_ARG for an entry without a form, another nargs, or
  * nform below the count. */
 int ptr_launch_form(const char *entry, const int64_t *args, int nargs, int32_t *form, int nform);

@@ -46,6 +46,9 @@ SIGNATURES = {
     "ptr_pl_uniforms": [_i, _i, _i, _u64, C.c_int64, _vp, _vp],
     "ptr_pl_sample": [_vp, _vp, _i, _i, _i, _f, _i, _u64, C.c_int64, _vp, _vp, _vp, _vp],
     "ptr_mdprank_sample_fwd_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ptr_irgan_sample": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp],
+    "ptr_irgan_point_gen_fwd_bwd": [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _i, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ptr_irgan_sel_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
     "ptr_shuffle_ties_order": [_vp, _vp, _i, _i, _u64, _vp, _vp],
     "ptr_sort_desc": [_vp, _vp, _i, _i, _vp, _vp, _vp],
     "ptr_metrics_at_ks": [_vp, _vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -1,0 +1,284 @@
+"""The adversarial frame (the reference's ltr_adversarial) on the fused HIP path: the IRGAN point and pair machines.
+
+  IRGAN_Point   ptranking/ltr_adversarial/pointwise/irgan_point.py:48-232
+  IRGAN_Pair    ptranking/ltr_adversarial/pairwise/irgan_pair.py:50-234
+
+Jun Wang, Lantao Yu, Weinan Zhang, Yu Gong, Yinghui Xu, Benyou Wang, Peng Zhang, Dell Zhang: IRGAN — A Minimax Game for Unifying Generative
+and Discriminative Information Retrieval Models, SIGIR 2017.
+
+A machine holds two players, both point scorers on the fused kernels (AdversarialPlayer: the reference's ad_player.py, weight_decay 1e-3),
+and keeps the reference's method names: fill_global_buffer, mini_max_train, generate_data, train_discriminator, train_generator, reset_* and
+get_*.  They work on batching.PaddedQueryBatches: where the reference walks one query per step through torch.multinomial, torch.randperm,
+fancy indexing and autograd, a padded batch takes one sampling launch (ptr_irgan_sample), one scorer pass and one fused loss launch
+(ptr_irgan_sel_fwd_bwd, ptr_irgan_point_gen_fwd_bwd).
+
+What differs from the reference, on purpose:
+  * ONE optimiser step per BATCH on the sum over its queries of the reference's one-query loss, where the reference steps once per query
+    (as WassRank and the diversification rankers do here: a batch of one query reproduces the reference's step).
+  * The discriminator of IRGAN_Pair scores the positives and the negatives of a query in one compact batch [B, 2 S, F] with lens = 2 nsel;
+    the reference scores them in two calls, which only differs under batch normalisation (its statistics see both halves here).
+  * The draws come from a counter-based stream keyed by (seed, epoch counter, q0 + q), q0 the global index of a batch's first query — not
+    from torch's generator: the same law (tests/test_irgan_gpu.py), another stream, and a shard of a batch draws what the whole batch would.
+  * Sampling without replacement orders Gumbel keys instead of calling torch.multinomial: no weight can underflow.
+  * NaN scores.  IRGAN_Point: a NaN generator score makes that batch's loss NaN and train_generator returns stop_training = True, as the
+    reference's check on the predictions does (irgan_point.py:191-195).  The flag is read once per epoch, not per batch, so no step waits
+    for the host; the price is that the optimiser has already stepped on the NaN batch (and on the batches after it) when the flag is
+    read: the generator's weights are NaN from then on, where the reference returns before the step and keeps them.  Training stops
+    either way; a caller that wants the last finite generator keeps a copy per epoch.  IRGAN_Pair: the reference's pair machine has no
+    NaN stop (irgan_pair.py:94-118 ignores train_generator's result), and there is none here: ptr_irgan_sample gives a list with a NaN
+    score nsel = 0, so such a query adds loss 0 and gradient 0, and a generator whose scores are all NaN trains nothing without a word.
+Out of scope: IRGAN_List, the IRFGAN_* machines with their f-divergences, AdLTREvaluator's file handling and grid search.
+"""
+import copy
+
+import torch
+
+from . import functional as F_
+from .batching import unpack_batch
+from .host import LABEL_TYPE, DeviceEvaluator, PointScorerRanker, scorer_lens
+from .rankers import FusedStepMixin
+from .scorer import FusedScorerMixin
+
+AD_RANKER_NAMES = ("IRGAN_Point", "IRGAN_Pair")
+LAMBDA = 0.5                 # irgan_point.py:16
+DRAWS_PER_POS = 5            # irgan_point.py:203
+DEFAULT_AD_PARAS = {         # irgan_point.py:243-253, irgan_pair.py:244-257
+    "IRGAN_Point": dict(model_id="IRGAN_Point", ad_training_order="DG", d_epoches=1, g_epoches=1, temperature=0.5, samples_per_query=5),
+    "IRGAN_Pair": dict(model_id="IRGAN_Pair", loss_type="svm", ad_training_order="DG", d_epoches=1, g_epoches=1, temperature=0.5,
+                       samples_per_query=5),
+}
+
+
+class AdversarialPlayer(FusedStepMixin, FusedScorerMixin, DeviceEvaluator, PointScorerRanker):
+    """ptranking/ltr_adversarial/base/ad_player.py: a point-scorer ranker with weight_decay 1e-3; ndcg_at_k(s) and the other metric methods run
+    on DeviceEvaluator.  `predict` returns the raw scores: the machines hand the temperature to the kernels."""
+
+    def __init__(self, id=None, sf_para_dict=None, weight_decay=1e-3, gpu=False, device=None):
+        PointScorerRanker.__init__(self, id=id, sf_para_dict=sf_para_dict, weight_decay=weight_decay, gpu=gpu, device=device)
+
+    def score(self, X, lens):
+        """The scores [B, L] of a padded batch; padded rows stay out of the batch-norm statistics."""
+        with scorer_lens(self, lens, X):
+            return self.forward(X)
+
+
+def batch_key(batch):
+    """What the global buffer and the generated data are keyed by: a PaddedQueryBatches batch is a fixed view of its bucket's tensor, so
+    its address and shape name it for as long as the tensor lives.  The global buffer keeps the tensor itself beside its entry
+    (fill_global_buffer), so no address it holds can be handed to another dataset's batch while the buffer is in use."""
+    X = batch[1]
+    return (X.data_ptr(), tuple(X.shape))
+
+
+def buffered(global_buffer, batch):
+    """(num_pos, q0) of a batch from the global buffer; a batch the buffer was not filled from is a KeyError."""
+    num_pos, q0, _ = global_buffer[batch_key(batch)]
+    return num_pos, q0
+
+
+class _IRGANMachine:
+    """What the two machines share: the buffer of positives, the mini-max schedule, the compact batch of selected documents."""
+
+    sample_mode = None
+
+    def __init__(self, eval_dict, data_dict, gpu=False, device=None, seed=137):
+        self.eval_dict, self.data_dict = eval_dict, data_dict
+        self.gpu, self.device = gpu, device
+        self.seed, self._draws = int(seed), 0
+
+    def _set_paras(self, ad_para_dict):
+        self.d_epoches, self.g_epoches = ad_para_dict['d_epoches'], ad_para_dict['g_epoches']
+        self.temperature = ad_para_dict['temperature']
+        self.ad_training_order = ad_para_dict['ad_training_order']
+        self.samples_per_query = ad_para_dict['samples_per_query']
+        if self.ad_training_order not in ('DG', 'GD'):
+            raise ValueError(f"ad_training_order {self.ad_training_order!r} ('DG', 'GD')")
+        if not 1 <= int(self.samples_per_query) <= F_.IRGAN_MAX_SAMPLES:
+            raise ValueError(f"samples_per_query must be in 1 .. {F_.IRGAN_MAX_SAMPLES}, got {self.samples_per_query}")
+
+    def _next_seed(self):
+        """(seed, epoch counter): every pass over the data draws from a stream of its own."""
+        self._draws += 1
+        return (self.seed << 24) + self._draws
+
+    def fill_global_buffer(self, train_data, dict_buffer=None):
+        """Per batch: the number of positive documents per query, counted on the device, and the global index of its first query.  Raises
+        when a list is not presorted (a positive document behind a non-positive one): the samplers take the positives from the front.
+        Nothing is written into dict_buffer before every list has passed that check.  An entry is (num_pos [B] int32, q0, X): the batch's
+        tensor is kept so that its address, which is the key, stays its own."""
+        assert self.data_dict['train_presort'] is True      # this is required for efficient truth exampling
+        q0, unsorted, entries = 0, torch.zeros((), dtype=torch.bool, device=self.device), {}
+        for batch in train_data:
+            ids, X, Y, lens = unpack_batch(batch)
+            key = batch_key(batch)
+            if key not in dict_buffer:
+                pos = Y > 0
+                if lens is not None:
+                    pos = pos & (torch.arange(Y.size(1), device=Y.device)[None, :] < lens[:, None])
+                unsorted |= (pos[:, 1:] & ~pos[:, :-1]).any()
+                entries[key] = (pos.sum(dim=1).to(torch.int32), q0, X)
+            q0 += len(ids)
+        if bool(unsorted):
+            raise ValueError("a list has a relevant document behind a non-relevant one: IRGAN needs presorted training data (train_presort)")
+        dict_buffer.update(entries)
+
+    def mini_max_train(self, train_data=None, generator=None, discriminator=None, global_buffer=None):
+        """irgan_point.py:87-113 / irgan_pair.py:94-118: 'DG' as the released code, 'GD' as Algorithm 1 of the paper; the generated data is
+        refreshed at every 10th discriminator epoch."""
+        def d_part():
+            generated_data = None
+            for d_epoch in range(self.d_epoches):
+                if d_epoch % 10 == 0:
+                    generated_data = self.generate_data(train_data=train_data, generator=generator, global_buffer=global_buffer)
+                self.train_discriminator(train_data=train_data, generated_data=generated_data, discriminator=discriminator)
+            return False
+
+        def g_part():
+            for g_epoch in range(self.g_epoches):
+                if self.train_generator(train_data=train_data, generator=generator, discriminator=discriminator, global_buffer=global_buffer):
+                    return True
+            return False
+
+        for part in ((d_part, g_part) if self.ad_training_order == 'DG' else (g_part, d_part)):
+            if part():
+                return True
+        return False
+
+    def generate_data(self, train_data=None, generator=None, global_buffer=None):
+        """Sampling for training the discriminator: per batch (pos_idx [B, S], neg_idx [B, S], nsel [B]) from the generator's eval-mode scores."""
+        generator.eval_mode()
+        generated_data = dict()
+        seed = self._next_seed()
+        with torch.no_grad():
+            for batch in train_data:
+                ids, X, Y, lens = unpack_batch(batch)
+                num_pos, q0 = buffered(global_buffer, batch)
+                generated_data[batch_key(batch)] = F_.irgan_sample(generator.score(X, lens), num_pos, self.samples_per_query, self.sample_mode,
+                                                                   temperature=self.temperature, seed=seed, q0=q0, lens=lens)
+        return generated_data
+
+    @staticmethod
+    def selected_batch(X, pos_idx, neg_idx, nsel):
+        """The compact padded batch of the selected documents: [B, 2 S, F] with the V positives of a query in rows 0 .. V-1, its V negatives
+        in V .. 2V-1 and zero rows beyond, and lens = 2 nsel."""
+        S = pos_idx.size(1)
+        j = torch.arange(2 * S, device=X.device)[None, :]
+        V = nsel.to(torch.int64)[:, None]
+        src = torch.where(j < V, pos_idx.gather(1, j.clamp(max=S - 1).expand(X.size(0), -1)), neg_idx.gather(1, (j - V).clamp(0, S - 1)))
+        Xs = X.gather(1, src[:, :, None].expand(-1, -1, X.size(2))) * (j < 2 * V)[:, :, None]
+        return Xs, (2 * nsel).to(torch.int32)
+
+    def train_discriminator(self, train_data=None, generated_data=None, discriminator=None, **kwargs):
+        discriminator.train_mode()
+        for batch in train_data:
+            key = batch_key(batch)
+            if key not in generated_data:
+                continue
+            ids, X, Y, lens = unpack_batch(batch)
+            pos_idx, neg_idx, nsel = generated_data[key]
+            Xs, lens_s = self.selected_batch(X, pos_idx, neg_idx, nsel)
+            d_sel = discriminator.score(Xs, lens_s)
+            discriminator._fused_step(F_.irgan_selected(d_sel, nsel, self.d_loss_mode))
+
+    def reset_generator(self):
+        self.generator.init()
+
+    def reset_discriminator(self):
+        self.discriminator.init()
+
+    def reset_generator_discriminator(self):
+        self.reset_generator()
+        self.reset_discriminator()
+
+    def get_generator(self):
+        return self.generator
+
+    def get_discriminator(self):
+        return self.discriminator
+
+
+class IRGAN_Point(_IRGANMachine):
+    """IRGAN's pointwise machine.  The discriminator ends in a sigmoid (TL_AF 'S') and is trained by BCEWithLogits on its outputs, as the
+    reference does; the generator's step draws 5 P documents per query from the importance distribution and weighs log p by the reward
+    2 (D - 0.5) and p / q.  One optimiser step per batch on the sum over the queries of the reference's one-query loss."""
+
+    sample_mode = "POINT_D"
+    d_loss_mode = "POINT_D"
+
+    def __init__(self, eval_dict, data_dict, sf_para_dict=None, ad_para_dict=None, gpu=False, device=None):
+        super().__init__(eval_dict=eval_dict, data_dict=data_dict, gpu=gpu, device=device)
+        assert sf_para_dict[sf_para_dict['sf_id']]['apply_tl_af'] == True   # noqa: E712  irgan_point.py:58
+        g_sf_para_dict = sf_para_dict
+        d_sf_para_dict = copy.deepcopy(g_sf_para_dict)
+        d_sf_para_dict[sf_para_dict['sf_id']]['TL_AF'] = 'S'               # as required by the IRGAN model
+        self.generator = AdversarialPlayer(id='IRGAN_Point_Generator', sf_para_dict=g_sf_para_dict, gpu=gpu, device=device)
+        self.discriminator = AdversarialPlayer(id='IRGAN_Point_Discriminator', sf_para_dict=d_sf_para_dict, gpu=gpu, device=device)
+        self._set_paras(ad_para_dict)
+
+    def train_generator(self, train_data=None, generated_data=None, generator=None, discriminator=None, global_buffer=None):
+        generator.train_mode()
+        discriminator.eval_mode()
+        bad = torch.zeros((), dtype=torch.bool, device=self.device)
+        seed = self._next_seed()
+        for batch in train_data:
+            ids, X, Y, lens = unpack_batch(batch)
+            num_pos, q0 = buffered(global_buffer, batch)
+            with torch.no_grad():
+                d_preds = discriminator.score(X, lens)
+            loss = F_.irgan_point_generator(generator.score(X, lens), d_preds, num_pos, temperature=self.temperature, lam=LAMBDA,
+                                            draws_per_pos=DRAWS_PER_POS, seed=seed, q0=q0, lens=lens)
+            bad |= torch.isnan(loss.detach())
+            generator._fused_step(loss)
+        stop_training = bool(bad)
+        if stop_training:
+            print('Including NaN error.')
+        return stop_training
+
+
+class IRGAN_Pair(_IRGANMachine):
+    """IRGAN's pairwise machine, loss_type 'svm' or 'log'.  The generator (apply_tl_af True) draws the negatives of its own step without
+    replacement with weights sigmoid(scores / T); the reward comes from the discriminator (apply_tl_af False) on the pairs.  One optimiser
+    step per batch on the sum over the queries of the reference's one-query loss."""
+
+    sample_mode = "PAIR_D"
+
+    def __init__(self, eval_dict, data_dict, sf_para_dict=None, ad_para_dict=None, gpu=False, device=None):
+        super().__init__(eval_dict=eval_dict, data_dict=data_dict, gpu=gpu, device=device)
+        self.loss_type = ad_para_dict['loss_type']
+        if self.loss_type not in ('svm', 'log'):
+            raise NotImplementedError(f"loss_type {self.loss_type!r} ('svm', 'log')")
+        sf_para_dict[sf_para_dict['sf_id']]['apply_tl_af'] = True          # irgan_pair.py:62, the caller's dict as in the reference
+        g_sf_para_dict = sf_para_dict
+        d_sf_para_dict = copy.deepcopy(g_sf_para_dict)
+        d_sf_para_dict[sf_para_dict['sf_id']]['apply_tl_af'] = False
+        self.generator = AdversarialPlayer(id='IRGAN_Pair_Generator', sf_para_dict=g_sf_para_dict, gpu=gpu, device=device)
+        self.discriminator = AdversarialPlayer(id='IRGAN_Pair_Discriminator', sf_para_dict=d_sf_para_dict, gpu=gpu, device=device)
+        self._set_paras(ad_para_dict)
+        self.d_loss_mode = "PAIR_D_SVM" if self.loss_type == 'svm' else "PAIR_D_LOG"
+        self.g_loss_mode = "PAIR_G_SVM" if self.loss_type == 'svm' else "PAIR_G_LOG"
+
+    def train_generator(self, train_data=None, generated_data=None, generator=None, discriminator=None, global_buffer=None):
+        generator.train_mode()
+        discriminator.eval_mode()
+        bad = torch.zeros((), dtype=torch.bool, device=self.device)
+        seed = self._next_seed()
+        for batch in train_data:
+            ids, X, Y, lens = unpack_batch(batch)
+            num_pos, q0 = buffered(global_buffer, batch)
+            g_preds = generator.score(X, lens)
+            with torch.no_grad():
+                pos_idx, neg_idx, nsel = F_.irgan_sample(g_preds, num_pos, self.samples_per_query, "PAIR_G", temperature=self.temperature, seed=seed,
+                                                         q0=q0, lens=lens)
+                d_sel = discriminator.score(*self.selected_batch(X, pos_idx, neg_idx, nsel))
+            loss = F_.irgan_selected(g_preds, nsel, self.g_loss_mode, d_sel=d_sel, neg_idx=neg_idx, temperature=self.temperature, lens=lens)
+            bad |= torch.isnan(loss.detach())
+            generator._fused_step(loss)
+        stop_training = bool(bad)
+        if stop_training:
+            print('Including NaN error.')
+        return stop_training
+
+
+def ndcg_at_5(player, data):
+    """nDCG@5 of a player over presorted padded batches, as a float."""
+    return float(player.ndcg_at_k(test_data=data, k=5, label_type=LABEL_TYPE.MultiLabel, presort=True))

@@ -137,6 +137,9 @@ PairwiseForm pairwise_form(bool weighted, int B, int L, bool sigma_positive);   
 struct VecForm { int vec; int G; int V; };               // vec: 1 = the register kernel, G lanes per query and V float4 per lane; 0 = the other kernel
 inline int vec_per_lane(int L) { return L <= 256 ? 1 : L <= 512 ? 2 : 4; }                // float4 per lane: one wavefront holds L <= 1024 documents
 VecForm listnet_form(int L, bool aligned);                                               // listwise.hip
+struct IrganForm { int G; int QPB; };                    // threads per query, queries per workgroup
+IrganForm irgan_form(int L);                             // irgan.hip: the sampler and the generator step
+IrganForm irgan_sel_form(int mode, int L);               // irgan.hip: the losses on selected documents
 VecForm listmle_form(int L, bool aligned);
 VecForm lambdaloss_form(int L, int k, int loss_type, int presort, bool aligned);          // lambdaloss.hip: vec = top-k; else (G, DPT) in (G, V)
 Tiling wassrank_form(int L);                                                              // wassrank.hip

@@ -17,7 +17,8 @@ from . import _lib
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
            "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "ndeval_measures", "div_ideal_order", "NDEVAL_MEASURES","divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
-           "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "gaussian_metric_objective", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES",
+           "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "gaussian_metric_objective", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS",
+           "irgan_uniforms", "irgan_sample", "irgan_point_generator", "irgan_selected", "IRGAN_SAMPLE_MODES", "IRGAN_SELECTED_MODES", "IRGAN_MAX_SAMPLES", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES",
            "gbdt_bin", "gbdt_quantize", "gbdt_histogram", "gbdt_hist_sub", "gbdt_best_split", "gbdt_partition", "gbdt_add_leaf_values", "gbdt_predict",
            "gbdt_histogram_segments", "gbdt_hist_sub_segments", "gbdt_best_split_slots", "gbdt_partition_segments", "gbdt_segment_items",
            "GBDT_MAX_BIN", "GBDT_RECORD"]
@@ -34,6 +35,9 @@ TREE_HESSIANS = {"reference": 0, "sum": 1, "constant": 2}                   # PT
 TREE_GAIN_TYPES = {"Power": 0, "Label": 1}                                  # PTR_TREE_GAIN_*; lightgbm_util.py:306
 SMOOTH_METRICS = {"P": 0, "AP": 1, "nERR": 2, "nDCG": 3, 0: 0, 1: 1, 2: 2, 3: 3}   # PTR_SMOOTH_*; metric/smooth_metric/metric_as_opt_objective.py
 PL_DISTRIBUTIONS = {"PL": 0, "STPL": 1, 0: 0, 1: 1}   # PTR_PL_DIST_*; ptranking/ltr_adhoc/listwise/mdprank.py:19
+IRGAN_SAMPLE_MODES = {"POINT_D": 0, "PAIR_D": 1, "PAIR_G": 2}                # PTR_IRGAN_*; irgan_point.py:130-146, irgan_pair.py:140-161, :207-211
+IRGAN_SELECTED_MODES = {"POINT_D": 0, "PAIR_D_SVM": 1, "PAIR_D_LOG": 2, "PAIR_G_SVM": 3, "PAIR_G_LOG": 4}   # PTR_IRGAN_SEL_*
+IRGAN_MAX_SAMPLES = 64                                                     # PTR_IRGAN_MAX_SAMPLES
 GBDT_MAX_BIN = 256                                                         # PTR_GBDT_MAX_BIN
 GBDT_RECORD = ("gain", "feature", "bin", "left_g", "left_h", "left_count", "right_g", "right_h", "right_count")   # a split record's 9 int64
 WASS_COST_TYPES = {"p1": 0, "p2": 1, "eg": 2, "dg": 3, "ddg": 4}   # PTR_WASS_COST_*; wassrank/wasserstein_cost_mat.py:113-139
@@ -511,6 +515,106 @@ def mdprank_sampled_loss(preds, labels, top_k=10, gamma=1.0, temperature=1.0, di
                   [labels, lens, B, L, S, int(top_k) if top_k else 0, C.c_float(float(gamma)), C.c_float(float(temperature)), dist, _seed64(seed),
                    C.c_int64(int(q0)), unif], own_loss=True, tail=(perm,))[0]
     return (loss, perm) if return_perm else loss
+
+
+def _irgan_samples(samples_per_query):
+    if not 1 <= int(samples_per_query) <= IRGAN_MAX_SAMPLES:
+        raise ValueError(f"samples_per_query must be in 1 .. {IRGAN_MAX_SAMPLES}, got {samples_per_query}")
+    return int(samples_per_query)
+
+
+def _irgan_batch(preds, num_pos, lens, streams, unif):
+    """preds [B, L], num_pos int32 [B], lens, unif [B, streams, L] — checked, contiguous."""
+    preds, B, L = _matrix("preds", preds)
+    _list_len(L)
+    num_pos = _check("num_pos", num_pos, torch.int32, (B,))
+    if num_pos.device != preds.device:
+        raise RuntimeError("preds and num_pos live on different devices")
+    return preds, num_pos, _counts("lens", lens, B), _pl_unif(unif, B, streams, L, preds.device), B, L
+
+
+def irgan_uniforms(B, L, streams, seed=0, q0=0, device=None):
+    """The uniforms irgan_sample (streams = 2: the keys of the positives by document; the negatives by draw under 'POINT_D', by document under
+    the pair modes) and irgan_point_generator (streams = draws_per_pos: draw k sits at flat position k of a query's [streams, L] block) draw
+    for (seed, q0): float32 [B, streams, L], the counter hash of pl_uniforms."""
+    return pl_uniforms(B, L, samples=streams, seed=seed, q0=q0, device=device)
+
+
+def irgan_sample(preds, num_pos, samples_per_query, mode, temperature=1.0, seed=0, q0=0, lens=None, unif=None):
+    """The documents IRGAN's two players train on, drawn on the device -> (pos_idx int64 [B, S], neg_idx int64 [B, S], nsel int32 [B]):
+    per query V = nsel valid columns, 0 beyond.  preds: the generator's raw scores [B, L]; num_pos int32 [B]: the relevant documents of a
+    list sit at its front (train_presort).  pos_idx: V distinct documents of 0 .. P-1, uniform (randperm(P)[:V]).  mode 'POINT_D'
+    (ptranking/ltr_adversarial/pointwise/irgan_point.py:130-146): V = min(P, S), neg_idx V draws WITH replacement from softmax(preds / T);
+    'PAIR_D' (pairwise/irgan_pair.py:140-161): V = min(P, n - P, S), V draws without replacement from softmax(preds / T) over the documents
+    i >= P; 'PAIR_G' (:207-211): V draws without replacement with weights sigmoid(preds / T) over all documents.  Counter-based: the same
+    (seed, q0 + q) draws the same documents in any batch; `unif` float32 [B, 2, L] replaces the generator (irgan_uniforms).  Not
+    differentiable."""
+    S = _irgan_samples(samples_per_query)
+    mode = _enum("mode", mode, IRGAN_SAMPLE_MODES)
+    preds, num_pos, lens, unif, B, L = _irgan_batch(preds.detach(), num_pos, lens, 2, unif)
+    dev = preds.device
+    pos = torch.empty((B, S), device=dev, dtype=torch.int64)
+    neg = torch.empty((B, S), device=dev, dtype=torch.int64)
+    nsel = torch.empty(B, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_irgan_sample", _lib.ptr(preds), _lib.ptr(lens), _lib.ptr(num_pos), B, L, S, mode, C.c_float(float(temperature)), _seed64(seed),
+                  C.c_int64(int(q0)), _lib.ptr(unif), _lib.ptr(pos), _lib.ptr(neg), _lib.ptr(nsel), _lib.current_stream(dev))
+    return pos, neg, nsel
+
+
+def irgan_point_generator(g_preds, d_preds, num_pos, temperature=1.0, lam=0.5, draws_per_pos=5, seed=0, q0=0, lens=None, unif=None, return_parts=False):
+    """The generator step of IRGAN_Point (ptranking/ltr_adversarial/pointwise/irgan_point.py:184-217) for a padded batch, one launch: per
+    query K = draws_per_pos * P documents are drawn from q = (1 - lam) softmax(g_preds / T) + lam / P on the P relevant documents, and the
+    loss is -(1/K) sum over the draws of reward * log p * p / q with reward = 2 (d_preds - 0.5), d_preds [B, L] the discriminator's
+    (detached) outputs; the sum over queries, differentiable in g_preds (the importance weight p / q carries gradient, as in the reference).
+    A query without a relevant document contributes nothing; a NaN score makes its loss NaN.  unif float32 [B, draws_per_pos, L] replaces
+    the generator.  With return_parts also returns dict(loss_q [B], valid_q [B], counts int32 [B, L] (the times each document was drawn))."""
+    g_c, num_pos, lens, unif, B, L = _irgan_batch(g_preds.detach(), num_pos, lens, int(draws_per_pos), unif)
+    d_preds = _check("d_preds", d_preds.detach(), shape=(B, L))
+    if d_preds.device != g_c.device:
+        raise RuntimeError("g_preds and d_preds live on different devices")
+    counts = torch.empty((B, L), device=g_c.device, dtype=torch.int32) if return_parts else None
+    loss, parts = _fused("ptr_irgan_point_gen_fwd_bwd", [g_preds], [g_c],
+                         [d_preds, lens, num_pos, B, L, C.c_float(float(temperature)), C.c_float(float(lam)), int(draws_per_pos), _seed64(seed),
+                          C.c_int64(int(q0)), unif], own_loss=True, slots=(("loss_q", None), ("valid_q", None)), tail=(counts,))
+    if return_parts:
+        parts["counts"] = counts
+        return loss, parts
+    return loss
+
+
+def irgan_selected(x, nsel, mode, d_sel=None, neg_idx=None, temperature=1.0, lens=None, return_parts=False):
+    """IRGAN's losses on the selected documents, loss and gradient in one launch -> the sum over queries, differentiable in x.  nsel int32
+    [B]: the valid pairs per query (irgan_sample).  The discriminator's modes take x = its predictions on the compact batch [B, 2 S],
+    positives in columns 0 .. V-1 and negatives in V .. 2V-1: 'POINT_D' BCEWithLogits against labels 1 | 0, the mean over 2 V
+    (pointwise/irgan_point.py:161-169); 'PAIR_D_SVM' mean max(0, 1 - (d_pos - d_neg)); 'PAIR_D_LOG' -mean log sigmoid(d_pos - d_neg)
+    (pairwise/irgan_pair.py:180-184).  The generator's modes 'PAIR_G_SVM' / 'PAIR_G_LOG' take x = g_preds [B, L], neg_idx int64 [B, S]
+    and d_sel [B, 2 S] (the discriminator's predictions on the pairs), form the reward (irgan_pair.py:39-42) and
+    -mean_k log sigmoid(g_neg_k / T) reward_k (:216-218).  A query with nsel = 0 contributes nothing.  With return_parts also returns
+    dict(loss_q [B], valid_q [B])."""
+    m = _enum("mode", mode, IRGAN_SELECTED_MODES)
+    x_c, B, W = _matrix("x", x.detach())
+    dev = x_c.device
+    nsel = _check("nsel", nsel, torch.int32, (B,))
+    if m >= IRGAN_SELECTED_MODES["PAIR_G_SVM"]:
+        _list_len(W)
+        if d_sel is None or neg_idx is None:
+            raise ValueError(f"mode {mode!r} needs d_sel and neg_idx")
+        neg_idx = _check("neg_idx", neg_idx, torch.int64)
+        if neg_idx.dim() != 2 or neg_idx.shape[0] != B:
+            raise ValueError(f"neg_idx must be [batch, samples_per_query], got {tuple(neg_idx.shape)}")
+        S, L = _irgan_samples(neg_idx.shape[1]), W
+        d_sel = _check("d_sel", d_sel.detach(), shape=(B, 2 * S))
+        lens = _counts("lens", lens, B)
+    else:
+        if W % 2:
+            raise ValueError(f"x must be [batch, 2 * samples_per_query], got {tuple(x_c.shape)}")
+        S, L, d_sel, neg_idx, lens = _irgan_samples(W // 2), 1, None, None, None
+    if any(t is not None and t.device != dev for t in (nsel, d_sel, neg_idx, lens)):
+        raise RuntimeError("x, nsel, d_sel, neg_idx and lens live on different devices")
+    loss, parts = _fused("ptr_irgan_sel_fwd_bwd", [x], [x_c], [d_sel, neg_idx, nsel, lens, B, L, S, m, C.c_float(float(temperature))],
+                         own_loss=True, slots=(("loss_q", None), ("valid_q", None)))
+    return (loss, parts) if return_parts else loss
 
 
 def _ragged(entry, preds, labels, offsets, queries, max_len, out, *params):

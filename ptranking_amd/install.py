@@ -66,6 +66,25 @@ def install_diversification(names=None, ltr_module="ptranking.ltr_diversificatio
     return done
 
 
+def install_adversarial(names=None, ltr_module="ptranking.ltr_adversarial.eval.ltr_adversarial"):
+    """Rebind AD_RANKER_NAMES (IRGAN_Point, IRGAN_Pair) inside the reference's adversarial driver module, which looks its machines up by
+    name (ltr_adversarial.py: globals()[model_id]); returns {name: installed class}.  The installed machines are the stand-alone classes of
+    ptranking_amd.adversarial: the reference's constructor and method names on PaddedQueryBatches (AdLTREvaluator's own file handling and
+    grid search are not replaced).  The default install() binds none of them.  uninstall() restores."""
+    from .adversarial import AD_RANKER_NAMES, IRGAN_Pair, IRGAN_Point
+    classes = {"IRGAN_Point": IRGAN_Point, "IRGAN_Pair": IRGAN_Pair}
+    names = AD_RANKER_NAMES if names is None else tuple(names)
+    mod = importlib.import_module(ltr_module)
+    done = {}
+    for n in names:
+        if n not in classes:
+            raise KeyError(f"{n} is not one of {AD_RANKER_NAMES}")
+        _saved.setdefault((ltr_module, n), getattr(mod, n, None))
+        setattr(mod, n, classes[n])
+        done[n] = classes[n]
+    return done
+
+
 def install_tree(util_module="ptranking.ltr_tree.util.lightgbm_util", user_modules=("ptranking.ltr_tree.lambdamart.lightgbm_lambdaMART",)):
     """Rebind the six custom LightGBM objectives (ptranking_amd.tree.DROP_IN_NAMES: lightgbm_custom_obj_{ranknet,lambdarank,listnet} and
     their *_fobj forms) inside the reference's lightgbm_util module, and inside each of `user_modules` that is ALREADY imported: the
@@ -86,8 +105,8 @@ def install_tree(util_module="ptranking.ltr_tree.util.lightgbm_util", user_modul
 
 
 def uninstall(ltr_module=None):
-    """Restore the reference's own classes and functions: in `ltr_module`, or (default) in every module install(), install_diversification()
-    or install_tree() touched."""
+    """Restore the reference's own classes and functions: in `ltr_module`, or (default) in every module install(), install_diversification(),
+    install_adversarial() or install_tree() touched."""
     for m in sorted({m for m, _ in _saved} if ltr_module is None else {ltr_module}):
         _uninstall_module(m)
 
