@@ -498,6 +498,79 @@ int ptr_irgan_point_gen_fwd_bwd(const float *g_preds, const float *d_preds, cons
 int ptr_irgan_sel_fwd_bwd(const float *x, const float *d_sel, const int64_t *neg_idx, const int32_t *nsel, const int32_t *lens, int B, int L,
                           int S, int mode, float temperature, float *loss_out, float *loss_q, float *valid_q, float *grad, void *stream);
 
+/* ---- The adversarial frame's IRFGAN point and pair machines (csrc/irfgan.hip): the f-divergence generalisation of the block above.  The
+ * three symbols below are ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8, and no entry point or mode above changes.
+ * Reference: ptranking/ltr_adversarial/pointwise/irfgan_point.py, pairwise/irfgan_pair.py, util/pair_sampling.py, util/f_divergence.py, one
+ * query per step there, with an n x n Bradley-Terry matrix, an n x n Bernoulli mask and a P x n weight matrix per query; here a padded
+ * batch [B,L] with lens and num_pos (as above: clamped to 0 .. lens; n = lens[q], P = num_pos[q]) and nothing of size n x n.  Uniforms:
+ * u(seed, q0 + q, stream, index) of ptr_pl_uniforms.  S = samples per query, 1 .. PTR_IRGAN_MAX_SAMPLES.
+ * ptr_irfgan_point_sample (irfgan_point.py:179-192): V = min(P, S); pos_idx the V largest of P uniform keys (stream 0, index i), as
+ *   ptr_irgan_sample; neg_idx V draws WITHOUT replacement from softmax(preds) (no temperature) over all n documents: V rounds of arg-max
+ *   over preds_i + gumbel(u(1, i)).  A list with a NaN score or P = 0 gets nsel = 0.  Writes pos_idx, neg_idx int64 [B,S] (0 beyond V), nsel
+ *   int32 [B].  unif (nullable) [B,2,L] replaces the hash.
+ * ptr_irfgan_pair_sample (pair_sampling.py:26-77, :111-122; irfgan_pair.py:112-130): preds, labels [B,L], every list sorted by label
+ *   descending, labels >= 0 (the caller's duty).
+ *   True pairs: S draws WITH replacement from w_ij = max(0, y_i - y_j) / (log2(2 + i) log2(2 + j)), i < P, j < n, by the inverse CDF in
+ *   row-major order: draw k takes x = u(0, k) W, W the sum of all w; the head is the first row whose running row sum exceeds x (the
+ *   with-replacement rule above on the row sums), the tail the first column of that row with w > 0 whose in-row prefix exceeds the remainder.
+ *   Fake pairs: b_ij = [u(2 + i, j) < sigmoid(s_i - s_j)] for all n x n pairs, the diagonal included; M = the number of set bits; S draws
+ *   WITH replacement, uniform over the set bits: draw k takes r = min(M - 1, floor(floor(u(1, k) 2^24) M / 2^24)), in integers, and names
+ *   the r-th set bit in row-major order.  From the comparisons on, integer arithmetic: the draws depend on the bits alone.
+ *   nsel = S for a usable list; nsel = 0 (and no pair named) for n = 0, a NaN score, equal first and last label (the reference's
+ *   num_unique_labels < 2), W = 0, M = 0.  Writes true_head, true_tail, fake_head, fake_tail int64 [B,S] (0 beyond nsel), nsel int32 [B]
+ *   and bern_count int32 [B] (nullable) = M where the mask was counted, else 0.  The parity route: unif_draw (nullable) [B,2,S] replaces
+ *   streams 0 and 1, unif_bern (nullable) [B,L,L] replaces streams 2 .. L+1 — the one thing of size L x L, for tests only.
+ * ptr_irfgan_fwd_bwd (irfgan_point.py:200-220, irfgan_pair.py:141-170): both players' losses and gradients, one launch.  With
+ *   a(v) = activation_f(v) and c(v) = conjugate_f(activation_f(v)) of util/f_divergence.py, c in CLOSED form:
+ *     f_div           a(v)                    c(v)
+ *     PTR_FDIV_TVAR   0.5 tanh v              0.5 tanh v
+ *     PTR_FDIV_KL     v                       exp(v - 1)
+ *     PTR_FDIV_RKL    -exp(-v)                v - 1
+ *     PTR_FDIV_PC     v                       0.25 v^2 + v
+ *     PTR_FDIV_NC     1 - exp(-v)             2 - 2 exp(-v / 2)
+ *     PTR_FDIV_SH     1 - exp(-v)             expm1(v)
+ *     PTR_FDIV_JS     log 2 - softplus(-v)    softplus(v) - log 2
+ *     PTR_FDIV_GAN    -softplus(-v)           softplus(v)
+ *   (softplus evaluated stably, 1 - exp through expm1).  nsel int32 [B] = V (clamped to 0 .. S).
+ *   PTR_IRFGAN_POINT_D   x = the discriminator's predictions on the compact batch [B,2S], true documents in columns 0 .. V-1, fake in
+ *                        V .. 2V-1; loss_q = mean_k c(x_fake,k) - mean_k a(x_true,k); grad [B,2S].  d_fake, idx_a, idx_b, lens, L unread.
+ *   PTR_IRFGAN_PAIR_D    x [B,4S] = true heads | true tails | fake heads | fake tails, each V wide, v = head - tail; the same loss;
+ *                        grad [B,4S], +g at a head and -g at its tail.
+ *   PTR_IRFGAN_POINT_G   x = g_preds [B,L], idx_a [B,S] the fake documents, d_fake [B,S] the discriminator's eval-mode predictions on them
+ *                        (constants): loss_q = -(1/V) sum_k log softmax(x)[idx_k] c(d_k), the log-softmax over the n real documents;
+ *                        grad_i = -(1/V) (sum_{k: idx_k = i} c_k - p_i sum_k c_k).
+ *   PTR_IRFGAN_PAIR_G    x = g_preds, idx_a / idx_b [B,S] the fake heads / tails, d_fake [B,2S] = heads | tails, each V wide,
+ *                        v_k = d_head - d_tail: loss_q = -(1/V) sum_k log sigmoid(x_h - x_t) c(v_k), through log-sigmoid.  Pairs may repeat
+ *                        and h = t occurs; every document's thread sums its shares in k order (no atomics).
+ *   An index outside 0 .. n-1 names nothing (PAIR_G: the pair).  Outputs loss_q [B], valid_q [B], loss_out [1] (nullable), grad (0 on
+ *   padding).  nsel = 0: loss 0, gradient 0, valid 0.  A non-finite x or d_fake propagates as in IEEE arithmetic.
+ * Forms (ptr_launch_form): as for the IRGAN entry points — the samplers and the generator's modes one wavefront per query up to 256
+ * documents, four queries per workgroup, one workgroup of 256 threads per query beyond; the discriminator's modes always one wavefront.
+ * LDS per query: 4 (point sampler) or 16 (pair sampler) bytes x round_up(L, 4); the losses 768 bytes or 4 bytes per column of x.  No
+ * atomics.  A query's bits depend on (its data, L, S, the parameters, seed, q0 + q) alone, and the samplers' also not on the form.
+ * PTR_ERR_INVALID_ARG (before any HIP call): B < 0, L <= 0, L > PTR_MAX_LIST_LEN, S outside 1 .. PTR_IRGAN_MAX_SAMPLES, a mode or f_div out
+ * of range, and with B > 0 a NULL required pointer (lens, unif*, bern_count, loss_out are optional; d_fake and idx_a only for the
+ * generator's modes, idx_b only for PTR_IRFGAN_PAIR_G). */
+#define PTR_IRFGAN_POINT_D 0
+#define PTR_IRFGAN_PAIR_D 1
+#define PTR_IRFGAN_POINT_G 2
+#define PTR_IRFGAN_PAIR_G 3
+#define PTR_FDIV_TVAR 0
+#define PTR_FDIV_KL 1
+#define PTR_FDIV_RKL 2
+#define PTR_FDIV_PC 3
+#define PTR_FDIV_NC 4
+#define PTR_FDIV_SH 5
+#define PTR_FDIV_JS 6
+#define PTR_FDIV_GAN 7
+int ptr_irfgan_point_sample(const float *preds, const int32_t *lens, const int32_t *num_pos, int B, int L, int S, uint64_t seed, int64_t q0,
+                            const float *unif, int64_t *pos_idx, int64_t *neg_idx, int32_t *nsel, void *stream);
+int ptr_irfgan_pair_sample(const float *preds, const float *labels, const int32_t *lens, const int32_t *num_pos, int B, int L, int S,
+                           uint64_t seed, int64_t q0, const float *unif_draw, const float *unif_bern, int64_t *true_head, int64_t *true_tail,
+                           int64_t *fake_head, int64_t *fake_tail, int32_t *nsel, int32_t *bern_count, void *stream);
+int ptr_irfgan_fwd_bwd(const float *x, const float *d_fake, const int64_t *idx_a, const int64_t *idx_b, const int32_t *nsel, const int32_t *lens,
+                       int B, int L, int S, int mode, int f_div, float *loss_out, float *loss_q, float *valid_q, float *grad, void *stream);
+
 /* Device tie-shuffled label-descending order (the role of arg_shuffle_ties, sampling_utils.py:13-28) from a
  * counter-based RNG: same distribution, NOT the torch.randperm stream (not parity-checked, statistically tested). */
 int ptr_shuffle_ties_order(const float *labels, const int32_t *lens, int B, int L, uint64_t seed, int64_t *perm,
@@ -809,6 +882,8 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *   ptr_gbdt_partition_segments                  m                                        launches of one call (3), workgroups of a segment of m rows
  *   ptr_irgan_sample, ptr_irgan_point_gen_fwd_bwd   L                                     G, queries per workgroup
  *   ptr_irgan_sel_fwd_bwd                        mode, L                                  G, queries per workgroup
+ *   ptr_irfgan_point_sample, ptr_irfgan_pair_sample   L                                   G, queries per workgroup
+ *   ptr_irfgan_fwd_bwd                           mode, L                                  G, queries per workgroup
  * G: threads per query, DPT: documents per thread, TP: subtopic tile.  PTR_ERR_INVALID_ARG for an entry without a form, another nargs, or
  * nform below the count. */
 int ptr_launch_form(const char *entry, const int64_t *args, int nargs, int32_t *form, int nform);

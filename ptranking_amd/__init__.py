@@ -12,7 +12,9 @@
     gbdt        a native LambdaMART: GBDT (a histogram gradient-boosted tree trainer on the device, leaf-wise growth on fixed-point
                 integer histograms) and LambdaMART (the tree objectives above + GBDT, scores and gradients never leave the device)
     adversarial the adversarial frame's IRGAN point and pair machines (IRGAN_Point, IRGAN_Pair): device sampling of the documents both
-                players train on and the two players' fused losses; install_adversarial() rebinds them in the reference's driver module
+                players train on and the two players' fused losses; install_adversarial() rebinds them in the reference's driver module;
+                IRFGAN_Point, IRFGAN_Pair (EXTRA_AD_RANKER_NAMES, install_adversarial(extras=True)): the same players under eight
+                f-divergences, the pair machine's n x n Bernoulli sampler recomputed on the device and never stored
     dp          data-parallel gradient exchange (one RCCL all-reduce per step)
     install()   rebinds the ranker names of RANKER_NAMES (RankNet, LambdaRank, LambdaLoss, ApproxNDCG, ListNet, ListMLE, STListNet,
                 RankCosine, RankMSE, SoftRank, WassRank) inside an installed ptranking so LTREvaluator uses them unchanged; a WassRank
@@ -30,7 +32,7 @@ from .batching import PaddedQueryBatches            # noqa: F401
 from . import letor                                   # noqa: F401
 from .host import LABEL_TYPE, DeviceEvaluator       # noqa: F401
 from .install import install, install_adversarial, install_diversification, install_tree, uninstall   # noqa: F401
-from .adversarial import AD_RANKER_NAMES, IRGAN_Pair, IRGAN_Point   # noqa: F401
+from .adversarial import AD_RANKER_NAMES, EXTRA_AD_RANKER_NAMES, IRFGAN_Pair, IRFGAN_Point, IRGAN_Pair, IRGAN_Point   # noqa: F401
 from .tree import TreeObjective                     # noqa: F401
 from .diversity import DALETOR, DIV_RANKER_NAMES, EXTRA_DIV_RANKER_NAMES, DivProbRanker, DivQueryBatches     # noqa: F401
 from .rankers import (ApproxNDCG, LambdaLoss, LambdaRank, ListMLE, ListNet, RankNet, STListNet, RankCosine, RankMSE, SoftRank, WassRank, DASALC, MDPRank,  # noqa: F401

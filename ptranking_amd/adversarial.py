@@ -27,7 +27,27 @@ What differs from the reference, on purpose:
     either way; a caller that wants the last finite generator keeps a copy per epoch.  IRGAN_Pair: the reference's pair machine has no
     NaN stop (irgan_pair.py:94-118 ignores train_generator's result), and there is none here: ptr_irgan_sample gives a list with a NaN
     score nsel = 0, so such a query adds loss 0 and gradient 0, and a generator whose scores are all NaN trains nothing without a word.
-Out of scope: IRGAN_List, the IRFGAN_* machines with their f-divergences, AdLTREvaluator's file handling and grid search.
+
+  IRFGAN_Point  ptranking/ltr_adversarial/pointwise/irfgan_point.py:17-235
+  IRFGAN_Pair   ptranking/ltr_adversarial/pairwise/irfgan_pair.py:19-185
+
+Sebastian Nowozin, Botond Cseke, Ryota Tomioka: f-GAN — Training Generative Neural Samplers using Variational Divergence Minimization,
+NIPS 2016; the reference's IRFGAN machines put IRGAN's players under its f-divergences.
+
+The IRFGAN machines (EXTRA_AD_RANKER_NAMES) share the players, the buffer, the counter-based draws and the compact batch with the above and
+train by train_discriminator_generator_single_step alone: per batch the generator's scores, one sampling launch (ptr_irfgan_point_sample,
+ptr_irfgan_pair_sample), one compact batch ([B, 2 S, F] | [B, 4 S, F]), the discriminator's step, its eval-mode scores of the fakes, the
+generator's step (ptr_irfgan_fwd_bwd).  What differs from the reference, beyond the list above:
+  * conjugate_f(activation_f(v)) is evaluated in closed form: the reference's literal fp32 composition is inf or NaN from |v| of 9 to 17 on
+    under RKL, NC, SH, JS and GAN, where the closed forms stay finite.
+  * IRFGAN_Pair's fake pairs need no n x n matrix: the Bernoulli mask is recomputed from the counter hash, counted, and never stored.
+  * 'JSW' and IRFGAN_Point.mini_max_train(single_step=False) raise NotImplementedError: neither runs in the reference.
+  * NaN scores.  A list with a NaN generator score gets nsel = 0 from the samplers: it adds loss 0 and gradient 0 to both players.  The
+    flag is accumulated on the device and read once per pass, so the pass trains on the remaining lists and batches before it returns
+    stop_training = True, where the reference returns at the first such query (irfgan_point.py:188-190, irfgan_pair.py:120-123); once the
+    generator's weights are NaN every list is skipped.  Training stops either way.
+Out of scope: IRGAN_List, IRFGAN_List, the semi-supervised (-1 label) route of IRFGAN_Pair, the Gaussian pair sampler, AdLTREvaluator's file
+handling and grid search.
 """
 import copy
 
@@ -40,12 +60,16 @@ from .rankers import FusedStepMixin
 from .scorer import FusedScorerMixin
 
 AD_RANKER_NAMES = ("IRGAN_Point", "IRGAN_Pair")
+EXTRA_AD_RANKER_NAMES = ("IRFGAN_Point", "IRFGAN_Pair")       # install_adversarial(extras=True)
 LAMBDA = 0.5                 # irgan_point.py:16
 DRAWS_PER_POS = 5            # irgan_point.py:203
 DEFAULT_AD_PARAS = {         # irgan_point.py:243-253, irgan_pair.py:244-257
     "IRGAN_Point": dict(model_id="IRGAN_Point", ad_training_order="DG", d_epoches=1, g_epoches=1, temperature=0.5, samples_per_query=5),
     "IRGAN_Pair": dict(model_id="IRGAN_Pair", loss_type="svm", ad_training_order="DG", d_epoches=1, g_epoches=1, temperature=0.5,
                        samples_per_query=5),
+    # irfgan_point.py:246-258, irfgan_pair.py:196-208 (the machines read f_div_id and samples_per_query alone)
+    "IRFGAN_Point": dict(model_id="IRFGAN_Point", samples_per_query=5, d_epoches=1, g_epoches=1, f_div_id="KL", ad_training_order="DG"),
+    "IRFGAN_Pair": dict(model_id="IRFGAN_Pair", d_epoches=1, g_epoches=1, f_div_id="KL", ad_training_order="DG", samples_per_query=5),
 }
 
 
@@ -277,6 +301,154 @@ class IRGAN_Pair(_IRGANMachine):
         if stop_training:
             print('Including NaN error.')
         return stop_training
+
+
+class _IRFGANMachine(_IRGANMachine):
+    """What IRFGAN_Point and IRFGAN_Pair share: the f-divergence, the single step of both players per batch, the compact batch."""
+
+    model_id = None
+    d_mode = g_mode = None
+    parts = 2                                    # the compact batch is [B, parts * S, F]
+
+    def _set_f_paras(self, ad_para_dict):
+        self.f_div_id = ad_para_dict['f_div_id']
+        self.samples_per_query = ad_para_dict['samples_per_query']
+        F_._f_div(self.f_div_id)                 # 'JSW' NotImplementedError, an unknown name ValueError
+        if not 1 <= int(self.samples_per_query) <= F_.IRGAN_MAX_SAMPLES:
+            raise ValueError(f"samples_per_query must be in 1 .. {F_.IRGAN_MAX_SAMPLES}, got {self.samples_per_query}")
+
+    def _players(self, sf_para_dict, d_sf_para_dict, gpu, device):
+        self.generator = AdversarialPlayer(id=self.model_id + '_Generator', sf_para_dict=sf_para_dict, gpu=gpu, device=device)
+        self.discriminator = AdversarialPlayer(id=self.model_id + '_Discriminator', sf_para_dict=d_sf_para_dict, gpu=gpu, device=device)
+
+    @staticmethod
+    def compact_batch(X, idx, nsel):
+        """The compact padded batch of the selected documents: idx a list of K index tensors [B, S]; [B, K S, F] with part p of a query in
+        rows p V .. (p + 1) V - 1 (V = nsel), zero rows beyond K V, and lens = K nsel."""
+        K, S = len(idx), idx[0].size(1)
+        j = torch.arange(K * S, device=X.device)[None, :]
+        V = nsel.to(torch.int64)[:, None]
+        part = torch.div(j, V.clamp(min=1), rounding_mode='floor').clamp(max=K - 1)
+        src = torch.cat(idx, dim=1).gather(1, part * S + (j - part * V).clamp(0, S - 1))
+        Xs = X.gather(1, src[:, :, None].expand(-1, -1, X.size(2))) * (j < K * V)[:, :, None]
+        return Xs, (K * nsel).to(torch.int32)
+
+    def _sample(self, g_preds, batch, seed, global_buffer):
+        """-> (the index tensors of the compact batch, the generator loss's idx_a / idx_b, nsel)."""
+        raise NotImplementedError
+
+    def generate_data(self, **kwargs):
+        """The epoch-wise pieces are reachable only from mini_max_train(single_step=False) of the reference's IRFGAN_Point, which cannot
+        run there (see IRFGAN_Point.mini_max_train); IRFGAN_Pair has none."""
+        raise NotImplementedError(f"{self.model_id} trains by train_discriminator_generator_single_step only")
+
+    train_discriminator = train_generator = generate_data
+
+    def train_discriminator_generator_single_step(self, train_data=None, generator=None, discriminator=None, global_buffer=None):
+        """irfgan_point.py:170-223 / irfgan_pair.py:96-173 per batch: the generator's scores in train mode, one sampling launch, one compact
+        batch, the discriminator's step on the summed per-query loss, its eval-mode scores of the fakes, the generator's step."""
+        generator.train_mode()
+        bad = torch.zeros((), dtype=torch.bool, device=self.device)
+        seed = self._next_seed()
+        K, fakes = self.parts, self.parts // 2
+        for batch in train_data:
+            ids, X, Y, lens = unpack_batch(batch)
+            g_preds = generator.score(X, lens)
+            bad |= torch.isnan(g_preds.detach()).any()
+            with torch.no_grad():
+                idx, idx_a, idx_b, nsel = self._sample(g_preds, batch, seed, global_buffer)
+                Xs, lens_s = self.compact_batch(X, idx, nsel)
+            discriminator.train_mode()
+            discriminator._fused_step(F_.irfgan_loss(discriminator.score(Xs, lens_s), nsel, self.d_mode, self.f_div_id))
+            discriminator.eval_mode()
+            with torch.no_grad():
+                S = idx_a.size(1)
+                V = nsel.to(torch.int64)[:, None]
+                cols = (fakes * V + torch.arange(fakes * S, device=X.device)[None, :]).clamp(max=K * S - 1)
+                d_fake = discriminator.score(Xs, lens_s).gather(1, cols)     # the fake half, each part V wide
+            generator._fused_step(F_.irfgan_loss(g_preds, nsel, self.g_mode, self.f_div_id, d_fake=d_fake, idx_a=idx_a, idx_b=idx_b, lens=lens))
+        stop_training = bool(bad)
+        if stop_training:
+            print('Including NaN error.')
+        return stop_training
+
+
+class IRFGAN_Point(_IRFGANMachine):
+    """IRFGAN's pointwise machine (irfgan_point.py:17-235): the discriminator separates relevant documents from the generator's draws under
+    an f-divergence (ad_para_dict['f_div_id'], functional.F_DIVERGENCES), the generator follows -mean log p(fake) c(D(fake)).  One optimiser
+    step per player per batch on the sum over the queries of the reference's one-query loss."""
+
+    model_id, d_mode, g_mode, parts = "IRFGAN_Point", "POINT_D", "POINT_G", 2
+
+    def __init__(self, eval_dict, data_dict, sf_para_dict=None, ad_para_dict=None, gpu=False, device=None):
+        super().__init__(eval_dict=eval_dict, data_dict=data_dict, gpu=gpu, device=device)
+        self._set_f_paras(ad_para_dict)
+        self._players(sf_para_dict, copy.deepcopy(sf_para_dict), gpu, device)
+
+    def mini_max_train(self, train_data=None, generator=None, discriminator=None, global_buffer=None, single_step=True):
+        if not single_step:
+            raise NotImplementedError("IRFGAN_Point.mini_max_train(single_step=False): the reference's branch reads self.d_epoches, "
+                                      "self.g_epoches and self.ad_training_order, which its constructor never sets (irfgan_point.py:24-26, :57)")
+        return self.train_discriminator_generator_single_step(train_data=train_data, generator=generator, discriminator=discriminator,
+                                                              global_buffer=global_buffer)
+
+    def _sample(self, g_preds, batch, seed, global_buffer):
+        num_pos, q0 = buffered(global_buffer, batch)
+        pos_idx, neg_idx, nsel = F_.irfgan_point_sample(g_preds, num_pos, self.samples_per_query, seed=seed, q0=q0, lens=unpack_batch(batch)[3])
+        return [pos_idx, neg_idx], neg_idx, None, nsel
+
+
+class IRFGAN_Pair(_IRFGANMachine):
+    """IRFGAN's pairwise machine (irfgan_pair.py:19-185), g_key 'BT': true pairs are drawn by label difference with position discounts,
+    fake pairs from a Bernoulli mask of Bradley-Terry probabilities sigmoid(s_i - s_j) of the generator's scores — both on the device,
+    nothing of size n x n held; the discriminator (apply_tl_af False) scores head minus tail.  One optimiser step per player per batch."""
+
+    model_id, d_mode, g_mode, parts = "IRFGAN_Pair", "PAIR_D", "PAIR_G", 4
+
+    def __init__(self, eval_dict, data_dict, sf_para_dict=None, ad_para_dict=None, g_key='BT', sigma=1.0, gpu=False, device=None):
+        super().__init__(eval_dict=eval_dict, data_dict=data_dict, gpu=gpu, device=device)
+        self._set_f_paras(ad_para_dict)
+        assert g_key == 'BT'                                                # irfgan_pair.py:30
+        self.g_key, self.sigma = g_key, sigma                               # sigma: kept as the reference keeps it, unused under 'BT'
+        d_sf_para_dict = copy.deepcopy(sf_para_dict)
+        d_sf_para_dict[sf_para_dict['sf_id']]['apply_tl_af'] = False       # :42
+        self._players(sf_para_dict, d_sf_para_dict, gpu, device)
+
+    def fill_global_buffer(self, train_data, dict_buffer=None):
+        """Per batch (num_pos [B] int32, q0, X, distinct [B] bool): the positives per query, the global index of the batch's first query, the
+        batch's tensor (batch_key) and whether a list holds two distinct labels (irfgan_pair.py:81 num_unique_labels; the sampler makes
+        the same check on the first and last label).  Raises ValueError on a label below 0 (the semi-supervised route is not built) and on a
+        list that is not sorted by label, descending; nothing is written before every list has passed."""
+        assert self.data_dict['train_presort'] is True      # this is required for efficient truth exampling
+        q0, entries = 0, {}
+        negative = torch.zeros((), dtype=torch.bool, device=self.device)
+        unsorted = torch.zeros((), dtype=torch.bool, device=self.device)
+        for batch in train_data:
+            ids, X, Y, lens = unpack_batch(batch)
+            key = batch_key(batch)
+            if key not in dict_buffer:
+                real = torch.ones_like(Y, dtype=torch.bool) if lens is None else torch.arange(Y.size(1), device=Y.device)[None, :] < lens[:, None]
+                negative |= ((Y < 0) & real).any()
+                unsorted |= ((Y[:, 1:] > Y[:, :-1]) & real[:, 1:]).any()
+                n = real.sum(dim=1)
+                first, last = Y[:, 0], Y.gather(1, (n - 1).clamp(min=0)[:, None])[:, 0]
+                entries[key] = (((Y > 0) & real).sum(dim=1).to(torch.int32), q0, X, (n > 0) & (first != last))
+            q0 += len(ids)
+        if bool(negative):
+            raise ValueError("a label below 0: IRFGAN_Pair's semi-supervised route (MSLETOR_SEMI) is not built")
+        if bool(unsorted):
+            raise ValueError("a list is not sorted by label, descending: IRFGAN_Pair needs presorted training data (train_presort)")
+        dict_buffer.update(entries)
+
+    def mini_max_train(self, train_data=None, generator=None, discriminator=None, global_buffer=None):
+        return self.train_discriminator_generator_single_step(train_data=train_data, generator=generator, discriminator=discriminator,
+                                                              global_buffer=global_buffer)
+
+    def _sample(self, g_preds, batch, seed, global_buffer):
+        ids, X, Y, lens = unpack_batch(batch)
+        num_pos, q0 = global_buffer[batch_key(batch)][:2]
+        th, tt, fh, ft, nsel = F_.irfgan_pair_sample(g_preds, Y, num_pos, self.samples_per_query, seed=seed, q0=q0, lens=lens)
+        return [th, tt, fh, ft], fh, ft, nsel
 
 
 def ndcg_at_5(player, data):

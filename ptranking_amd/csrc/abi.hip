@@ -87,6 +87,9 @@ static const FormQuery kFormQueries[] = {
     {"ptr_irgan_sample", 1, 2, [](const int64_t *a, int32_t *out) { put(out, irgan_form((int)a[0])); }},
     {"ptr_irgan_point_gen_fwd_bwd", 1, 2, [](const int64_t *a, int32_t *out) { put(out, irgan_form((int)a[0])); }},
     {"ptr_irgan_sel_fwd_bwd", 2, 2, [](const int64_t *a, int32_t *out) { put(out, irgan_sel_form((int)a[0], (int)a[1])); }},
+    {"ptr_irfgan_point_sample", 1, 2, [](const int64_t *a, int32_t *out) { put(out, irgan_form((int)a[0])); }},
+    {"ptr_irfgan_pair_sample", 1, 2, [](const int64_t *a, int32_t *out) { put(out, irgan_form((int)a[0])); }},
+    {"ptr_irfgan_fwd_bwd", 2, 2, [](const int64_t *a, int32_t *out) { put(out, irfgan_loss_form((int)a[0], (int)a[1])); }},
 };
 
 }  // namespace ptr

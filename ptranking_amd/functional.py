@@ -18,13 +18,14 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
            "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "ndeval_measures", "div_ideal_order", "NDEVAL_MEASURES","divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
            "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "gaussian_metric_objective", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS",
-           "irgan_uniforms", "irgan_sample", "irgan_point_generator", "irgan_selected", "IRGAN_SAMPLE_MODES", "IRGAN_SELECTED_MODES", "IRGAN_MAX_SAMPLES", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES",
+           "irgan_uniforms", "irgan_sample", "irgan_point_generator", "irgan_selected", "IRGAN_SAMPLE_MODES", "IRGAN_SELECTED_MODES", "IRGAN_MAX_SAMPLES",
+           "irfgan_uniforms", "irfgan_point_sample", "irfgan_pair_sample", "IRFGAN_MODES", "F_DIVERGENCES", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES",
            "gbdt_bin", "gbdt_quantize", "gbdt_histogram", "gbdt_hist_sub", "gbdt_best_split", "gbdt_partition", "gbdt_add_leaf_values", "gbdt_predict",
            "gbdt_histogram_segments", "gbdt_hist_sub_segments", "gbdt_best_split_slots", "gbdt_partition_segments", "gbdt_segment_items",
            "GBDT_MAX_BIN", "GBDT_RECORD"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
-# launch table, and it draws its own)
+# launch table, and it draws its own; irfgan_loss is public too: it takes selected documents and a mode, as irgan_selected does)
 LAMBDALOSS_TYPES = {"NDCG_Loss1": 0, "NDCG_Loss2": 1, "NDCG_Loss2++": 2}   # ptranking/ltr_adhoc/listwise/lambdaloss.py:27
 ADCG_TOPK_AXES = {"reference": 0, "subtopics": 0, 0: 0, "documents": 1, 1: 1}   # PTR_ADCG_TOPK_*
 NDEVAL_MEASURES = ("ERR-IA", "nERR-IA", "alpha-DCG", "alpha-nDCG", "NRBP", "nNRBP", "MAP-IA", "P-IA", "strec")   # ndeval.c:1214-1222, its CSV columns
@@ -38,6 +39,8 @@ PL_DISTRIBUTIONS = {"PL": 0, "STPL": 1, 0: 0, 1: 1}   # PTR_PL_DIST_*; ptranking
 IRGAN_SAMPLE_MODES = {"POINT_D": 0, "PAIR_D": 1, "PAIR_G": 2}                # PTR_IRGAN_*; irgan_point.py:130-146, irgan_pair.py:140-161, :207-211
 IRGAN_SELECTED_MODES = {"POINT_D": 0, "PAIR_D_SVM": 1, "PAIR_D_LOG": 2, "PAIR_G_SVM": 3, "PAIR_G_LOG": 4}   # PTR_IRGAN_SEL_*
 IRGAN_MAX_SAMPLES = 64                                                     # PTR_IRGAN_MAX_SAMPLES
+IRFGAN_MODES = {"POINT_D": 0, "PAIR_D": 1, "POINT_G": 2, "PAIR_G": 3}       # PTR_IRFGAN_*; irfgan_point.py:200-220, irfgan_pair.py:141-170
+F_DIVERGENCES = {"TVar": 0, "KL": 1, "RKL": 2, "PC": 3, "NC": 4, "SH": 5, "JS": 6, "GAN": 7}   # PTR_FDIV_*; ltr_adversarial/util/f_divergence.py
 GBDT_MAX_BIN = 256                                                         # PTR_GBDT_MAX_BIN
 GBDT_RECORD = ("gain", "feature", "bin", "left_g", "left_h", "left_count", "right_g", "right_h", "right_count")   # a split record's 9 int64
 WASS_COST_TYPES = {"p1": 0, "p2": 1, "eg": 2, "dg": 3, "ddg": 4}   # PTR_WASS_COST_*; wassrank/wasserstein_cost_mat.py:113-139
@@ -614,6 +617,114 @@ def irgan_selected(x, nsel, mode, d_sel=None, neg_idx=None, temperature=1.0, len
         raise RuntimeError("x, nsel, d_sel, neg_idx and lens live on different devices")
     loss, parts = _fused("ptr_irgan_sel_fwd_bwd", [x], [x_c], [d_sel, neg_idx, nsel, lens, B, L, S, m, C.c_float(float(temperature))],
                          own_loss=True, slots=(("loss_q", None), ("valid_q", None)))
+    return (loss, parts) if return_parts else loss
+
+
+def _f_div(f_div):
+    if f_div == "JSW":
+        raise NotImplementedError("f_div 'JSW': the reference's Jensen-Shannon-weighted pair calls torch.log on the Python float math.pi and "
+                                  "raises TypeError at its first use (util/f_divergence.py:62-67): there is no behaviour to reproduce")
+    return _enum("f_div", f_div, F_DIVERGENCES)
+
+
+def irfgan_uniforms(B, L, samples_per_query=None, seed=0, q0=0, device=None):
+    """The uniforms the IRFGAN samplers draw for (seed, q0), the counter hash of pl_uniforms.  samples_per_query None: float32 [B, 2, L] for
+    irfgan_point_sample (stream 0 the keys of the positives, stream 1 the Gumbel uniforms, both by document).  With samples_per_query = S:
+    (unif_draw [B, 2, S], unif_bern [B, L, L]) for irfgan_pair_sample — streams 0 and 1 by draw, streams 2 + i by partner j.  unif_bern is
+    the one thing of size L x L here: it exists for tests, the product never allocates it."""
+    if samples_per_query is None:
+        return pl_uniforms(B, L, samples=2, seed=seed, q0=q0, device=device)
+    S = _irgan_samples(samples_per_query)
+    _list_len(L)
+    u = pl_uniforms(B, max(int(L), S), samples=int(L) + 2, seed=seed, q0=q0, device=device)
+    return u[:, :2, :S].contiguous(), u[:, 2:, :L].contiguous()
+
+
+def irfgan_point_sample(preds, num_pos, samples_per_query, seed=0, q0=0, lens=None, unif=None):
+    """The documents IRFGAN_Point's players train on (ptranking/ltr_adversarial/pointwise/irfgan_point.py:179-192), drawn on the device ->
+    (pos_idx int64 [B, S], neg_idx int64 [B, S], nsel int32 [B]).  V = nsel = min(P, S): pos_idx V distinct documents of 0 .. P-1, uniform
+    (randperm(P)[:V]); neg_idx V draws WITHOUT replacement from softmax(preds) over all n documents, by Gumbel keys.  A list with a NaN
+    score or without a relevant document gets nsel = 0.  Counter-based: (seed, q0 + q) names the draws in any batch; `unif` float32
+    [B, 2, L] replaces the generator (irfgan_uniforms).  Not differentiable."""
+    S = _irgan_samples(samples_per_query)
+    preds, num_pos, lens, unif, B, L = _irgan_batch(preds.detach(), num_pos, lens, 2, unif)
+    dev = preds.device
+    pos = torch.empty((B, S), device=dev, dtype=torch.int64)
+    neg = torch.empty((B, S), device=dev, dtype=torch.int64)
+    nsel = torch.empty(B, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_irfgan_point_sample", _lib.ptr(preds), _lib.ptr(lens), _lib.ptr(num_pos), B, L, S, _seed64(seed), C.c_int64(int(q0)),
+                  _lib.ptr(unif), _lib.ptr(pos), _lib.ptr(neg), _lib.ptr(nsel), _lib.current_stream(dev))
+    return pos, neg, nsel
+
+
+def irfgan_pair_sample(preds, labels, num_pos, samples_per_query, seed=0, q0=0, lens=None, unif_draw=None, unif_bern=None, return_count=False):
+    """The document pairs IRFGAN_Pair's players train on, drawn on the device without anything of size n x n ->
+    (true_head, true_tail, fake_head, fake_tail int64 [B, S], nsel int32 [B]).  labels [B, L]: every list sorted by label descending, no
+    label below 0 (the caller's duty: IRFGAN_Pair.fill_global_buffer checks both).  True pairs (ptranking/ltr_adversarial/util/
+    pair_sampling.py:26-77): S draws with replacement from w_ij = max(0, y_i - y_j) / (log2(2 + i) log2(2 + j)), i < P, j < n.  Fake pairs
+    (:111-122 on irfgan_pair.py:127-130): a Bernoulli mask with P(b_ij) = sigmoid(s_i - s_j) over all n x n pairs, then S draws with
+    replacement, uniform over its set bits.  nsel = S, or 0 (no pair named) for an empty list, a NaN score, a list whose first and last
+    labels are equal, no true pair of positive weight, or an empty mask.  Counter-based as irfgan_point_sample; unif_draw [B, 2, S] and
+    unif_bern [B, L, L] replace the generator (irfgan_uniforms; tests only).  return_count: also the mask's set bits, int32 [B].  Not
+    differentiable."""
+    S = _irgan_samples(samples_per_query)
+    preds, num_pos, lens, _, B, L = _irgan_batch(preds.detach(), num_pos, lens, 2, None)
+    dev = preds.device
+    labels = _check("labels", labels, shape=(B, L))
+    if unif_draw is not None:
+        unif_draw = _check("unif_draw", unif_draw, shape=(B, 2, S))
+    if unif_bern is not None:
+        unif_bern = _check("unif_bern", unif_bern, shape=(B, L, L))
+    if any(t is not None and t.device != dev for t in (labels, unif_draw, unif_bern)):
+        raise RuntimeError("preds, labels, unif_draw and unif_bern live on different devices")
+    out = [torch.empty((B, S), device=dev, dtype=torch.int64) for _ in range(4)]
+    nsel = torch.empty(B, device=dev, dtype=torch.int32)
+    count = torch.empty(B, device=dev, dtype=torch.int32) if return_count else None
+    with torch.cuda.device(dev):
+        _lib.call("ptr_irfgan_pair_sample", _lib.ptr(preds), _lib.ptr(labels), _lib.ptr(lens), _lib.ptr(num_pos), B, L, S, _seed64(seed),
+                  C.c_int64(int(q0)), _lib.ptr(unif_draw), _lib.ptr(unif_bern), *map(_lib.ptr, out), _lib.ptr(nsel), _lib.ptr(count),
+                  _lib.current_stream(dev))
+    return (*out, nsel, count) if return_count else (*out, nsel)
+
+
+def irfgan_loss(x, nsel, mode, f_div, d_fake=None, idx_a=None, idx_b=None, lens=None, return_parts=False):
+    """IRFGAN's losses under the f-divergence `f_div` (F_DIVERGENCES), loss and gradient in one launch -> the sum over queries,
+    differentiable in x.  With a = activation_f and c = conjugate_f(activation_f(.)) of ptranking/ltr_adversarial/util/f_divergence.py, c
+    evaluated in closed form (include/ptranking_amd.h lists them): the reference's literal composition is inf or NaN in fp32 where these
+    are finite.  nsel int32 [B] = V, the valid samples per query.  'POINT_D' (pointwise/irfgan_point.py:205): x = the discriminator's
+    predictions on the compact batch [B, 2 S], true documents in columns 0 .. V-1, fake in V .. 2V-1; mean c(x_fake) - mean a(x_true).
+    'PAIR_D' (pairwise/irfgan_pair.py:143-150): x [B, 4 S] = true heads | true tails | fake heads | fake tails, v = head - tail.
+    'POINT_G' (irfgan_point.py:213-216): x = g_preds [B, L], idx_a [B, S] the fake documents, d_fake [B, S] the discriminator's
+    predictions on them; -mean_k log softmax(x)[idx_k] c(d_k).  'PAIR_G' (irfgan_pair.py:157-166): idx_a / idx_b the fake heads / tails,
+    d_fake [B, 2 S] = heads | tails; -mean_k log sigmoid(x_h - x_t) c(d_h - d_t).  A query with nsel = 0 contributes nothing.  With
+    return_parts also returns dict(loss_q [B], valid_q [B])."""
+    m = _enum("mode", mode, IRFGAN_MODES)
+    f = _f_div(f_div)
+    x_c, B, W = _matrix("x", x.detach())
+    dev = x_c.device
+    nsel = _check("nsel", nsel, torch.int32, (B,))
+    if m >= IRFGAN_MODES["POINT_G"]:
+        _list_len(W)
+        pair = m == IRFGAN_MODES["PAIR_G"]
+        if d_fake is None or idx_a is None or (pair and idx_b is None):
+            raise ValueError(f"mode {mode!r} needs d_fake, idx_a" + (" and idx_b" if pair else ""))
+        idx_a = _check("idx_a", idx_a, torch.int64)
+        if idx_a.dim() != 2 or idx_a.shape[0] != B:
+            raise ValueError(f"idx_a must be [batch, samples_per_query], got {tuple(idx_a.shape)}")
+        S, L = _irgan_samples(idx_a.shape[1]), W
+        idx_b = _check("idx_b", idx_b, torch.int64, (B, S)) if pair else None
+        d_fake = _check("d_fake", d_fake.detach(), shape=(B, 2 * S if pair else S))
+        lens = _counts("lens", lens, B)
+    else:
+        k = 4 if m == IRFGAN_MODES["PAIR_D"] else 2
+        if W % k:
+            raise ValueError(f"x must be [batch, {k} * samples_per_query], got {tuple(x_c.shape)}")
+        S, L, d_fake, idx_a, idx_b, lens = _irgan_samples(W // k), 1, None, None, None, None
+    if any(t is not None and t.device != dev for t in (nsel, d_fake, idx_a, idx_b, lens)):
+        raise RuntimeError("x, nsel, d_fake, idx_a, idx_b and lens live on different devices")
+    loss, parts = _fused("ptr_irfgan_fwd_bwd", [x], [x_c], [d_fake, idx_a, idx_b, nsel, lens, B, L, S, m, f], own_loss=True,
+                         slots=(("loss_q", None), ("valid_q", None)))
     return (loss, parts) if return_parts else loss
 
 

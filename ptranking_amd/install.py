@@ -66,19 +66,22 @@ def install_diversification(names=None, ltr_module="ptranking.ltr_diversificatio
     return done
 
 
-def install_adversarial(names=None, ltr_module="ptranking.ltr_adversarial.eval.ltr_adversarial"):
+def install_adversarial(names=None, ltr_module="ptranking.ltr_adversarial.eval.ltr_adversarial", extras=False):
     """Rebind AD_RANKER_NAMES (IRGAN_Point, IRGAN_Pair) inside the reference's adversarial driver module, which looks its machines up by
     name (ltr_adversarial.py: globals()[model_id]); returns {name: installed class}.  The installed machines are the stand-alone classes of
     ptranking_amd.adversarial: the reference's constructor and method names on PaddedQueryBatches (AdLTREvaluator's own file handling and
-    grid search are not replaced).  The default install() binds none of them.  uninstall() restores."""
-    from .adversarial import AD_RANKER_NAMES, IRGAN_Pair, IRGAN_Point
-    classes = {"IRGAN_Point": IRGAN_Point, "IRGAN_Pair": IRGAN_Pair}
+    grid search are not replaced).  extras=True adds EXTRA_AD_RANKER_NAMES (IRFGAN_Point, IRFGAN_Pair), which the default leaves alone;
+    an explicit `names` may name them too.  The default install() binds none of them.  uninstall() restores."""
+    from .adversarial import AD_RANKER_NAMES, EXTRA_AD_RANKER_NAMES, IRFGAN_Pair, IRFGAN_Point, IRGAN_Pair, IRGAN_Point
+    classes = {"IRGAN_Point": IRGAN_Point, "IRGAN_Pair": IRGAN_Pair, "IRFGAN_Point": IRFGAN_Point, "IRFGAN_Pair": IRFGAN_Pair}
     names = AD_RANKER_NAMES if names is None else tuple(names)
+    if extras:
+        names = names + tuple(n for n in EXTRA_AD_RANKER_NAMES if n not in names)
     mod = importlib.import_module(ltr_module)
     done = {}
     for n in names:
         if n not in classes:
-            raise KeyError(f"{n} is not one of {AD_RANKER_NAMES}")
+            raise KeyError(f"{n} is not one of {AD_RANKER_NAMES + EXTRA_AD_RANKER_NAMES}")
         _saved.setdefault((ltr_module, n), getattr(mod, n, None))
         setattr(mod, n, classes[n])
         done[n] = classes[n]
