@@ -571,6 +571,77 @@ int ptr_irfgan_pair_sample(const float *preds, const float *labels, const int32_
 int ptr_irfgan_fwd_bwd(const float *x, const float *d_fake, const int64_t *idx_a, const int64_t *idx_b, const int32_t *nsel, const int32_t *lens,
                        int B, int L, int S, int mode, int f_div, float *loss_out, float *loss_q, float *valid_q, float *grad, void *stream);
 
+/* ---- The adversarial frame's list machines, IRGAN_List and IRFGAN_List (csrc/adlist.hip): the rankings the discriminator trains on and both
+ * players' ranking-probability losses.  The two symbols below are ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8, nothing above changes.
+ * Reference: ptranking/ltr_adversarial/listwise/irgan_list.py:24-409, listwise/irfgan_list.py:20-393, util/list_probability.py,
+ * util/list_sampling.py:16-36 (gumbel_softmax), :70-87 (arg_shuffle_ties) — one query per step there, a Python loop of gathers, one
+ * torch.randperm per sample, an [S,K,K] Bradley-Terry matrix and autograd through softmax, sort and LogCumsumExp; here a padded batch
+ * [B,L] with lens, one sampling launch and one fused loss launch per player, nothing of size K x K stored.
+ * Notation: n = lens[q]; S = samples per query, 1 .. PTR_IRGAN_MAX_SAMPLES; K = top_k, K <= 0 the whole list; Kq = min(K, n), or n for the
+ * whole list (the reference's [0:top_k] slice of a shorter list gives n); Kw = K, or L for the whole list.  Uniforms are
+ * u(seed, q0 + q, stream, index) of ptr_pl_uniforms, gumbel(u) as in ptr_pl_sample.
+ * ptr_adlist_sample (irgan_list.py:230-276) — one launch, top-Kq only.  preds, labels [B,L].
+ *   gen_idx[q,s,0..Kq-1] = the first Kq documents in the order (preds_i + gumbel(u(s, i)) descending, index ascending), stream s in
+ *   0 .. S-1: the streams of ptr_pl_sample(..., PTR_PL_DIST_STPL), whose perm it is the prefix of, bit for bit, for equal (seed, q0).  The
+ *   temperature is a positive scale and does not enter the order: no parameter here.
+ *   std_idx[q,s,0..Kq-1] = the first Kq documents in the order (label descending, u(S + s, i) descending, index ascending): uniform
+ *   among label ties, the law of arg_shuffle_ties(label, descending=True); labels of -1 sort last.
+ *   Outputs: std_idx, gen_idx int64 [B,S,Kw], 0 beyond Kq; kq int32 [B] = Kq, and 0 for n = 0 or a list with a NaN score.  unif (nullable)
+ *   [B,2S,L] replaces the hash (the parity route).  Nothing of size [B,S,L] is written when K < L.
+ * ptr_adlist_fwd_bwd — loss and gradient of either player, one launch.  With v = the scores of a ranking in ranking order:
+ *   PTR_ADLIST_PL  lp(v) = sum_{p<Kq} (v_p - L_p), L_p = log sum_{r>=p} e^{v_r} (max-shifted; the two scans run in double, and in the log
+ *                  domain in fp32 where a ranking's scores spread over more than 600);
+ *                  d lp / d v_r = 1 - e^{v_r} sum_{p<=r} e^{-L_p}                                  (list_probability.py:24-30)
+ *   PTR_ADLIST_BT  lp(v) = sum_{p<r} log sigmoid(v_p - v_r), through log-sigmoid: the reference's e_p / (e_p + e_r) with a batch-wide max
+ *                  shift is the same number; d lp / d v_p = sum_{r>p} sigmoid(v_r - v_p) - sum_{r<p} sigmoid(v_p - v_r).  A pair loop,
+ *                  nothing of size K x K stored                                                     (list_probability.py:44-62)
+ *   mode PTR_ADLIST_D: x = the discriminator's scores of the WHOLE list [B,L]; std_idx, gen_idx [B,S,Kw] and kq [B] as the sampler wrote
+ *   them (kq clamped to 0 .. min(n, Kw)); d_preds, temperature, seed, q0, unif, reward unread.
+ *     PTR_ADLIST_IRGAN   loss_q = -sum_s lp(x[std_s]) - sum_s log(1 - lp(x[gen_s]))                (irgan_list.py:336-337)
+ *     PTR_ADLIST_IRFGAN  loss_q = mean_s c(lp(x[gen_s])) - mean_s a(lp(x[std_s])), f_div one of PTR_FDIV_*, a and c in the closed forms of
+ *                        ptr_irfgan_fwd_bwd                                                         (irfgan_list.py:322)
+ *     grad [B,L]: the shares of a document are summed over the samples in a fixed order, no floating-point atomics.  A ranking names
+ *     a document at most once (the sampler's do); an index outside 0 .. n-1 makes its query invalid (loss 0, gradient 0, valid 0).
+ *   mode PTR_ADLIST_G: x = the generator's scores [B,L]; d_preds [B,L] = the discriminator's eval-mode scores, constants; std_idx,
+ *   gen_idx, kq unread.  The kernel draws the S rankings itself from (seed, q0), streams 0 .. S-1, or from unif [B,S,L]:
+ *     y^s = softmax_i((x_i + gumbel_{s,i}) / T) over the n documents, through the log-softmax (normaliser in double); pi_s = the descending order of the key
+ *     x_i + gumbel_{s,i} (the order of the logit); A_s = lp_PL of the Kq largest probabilities — the PL of the PROBABILITIES, as the
+ *     reference takes it (irgan_list.py:379); R_s = the reward from lp(d_preds[pi_s(0..Kq-1)]) under `prob`:
+ *     PTR_ADLIST_IRGAN   loss_q = (1/S) sum_s A_s R_s, R_s by `reward` (get_reward, irgan_list.py:301-310):
+ *                        PTR_ADLIST_REWARD_NEG_EXP -exp(lp) | _NEG_LP -lp | _EXP_1M exp(1 - lp) | _LOG_1M log(1 - lp)
+ *     PTR_ADLIST_IRFGAN  loss_q = -(1/S) sum_s A_s c(lp)                                            (irfgan_list.py:295, :375)
+ *     With h^s_i = d A_s / d y_i (zero outside the top Kq): grad_j = (1/S) sum_s R_s y^s_j (h^s_j - sum_i y^s_i h^s_i) / T, the sign as
+ *     the family's loss.  gen_idx_out (nullable) int64 [B,S,Kw] = ptr_adlist_sample's gen_idx for the same (seed, q0).  Kq = 0 for a list
+ *     with a NaN score in x.
+ *   Outputs: loss_q [B], valid_q [B], loss_out [1] = sum of loss_q (nullable), grad [B,L] (0 on padding).  Kq = 0: loss 0, gradient 0,
+ *   valid 0.  n = 1 is valid: lp = 0 and the gradient is 0; the loss is 0 in every mode except PTR_ADLIST_D under PTR_ADLIST_IRFGAN,
+ *   where it is the constant c(0) - a(0) of the divergence (exp(-1) under KL, 2 log 2 under GAN, 0 otherwise), as in the reference.
+ *   Non-finite values propagate as in IEEE arithmetic: exp(1 - lp) (PTR_ADLIST_REWARD_EXP_1M) overflows fp32 once lp < -87.7, i.e. for
+ *   long rankings, in the reference too.
+ * Forms (ptr_launch_form): as the IRGAN entry points — up to 256 documents one wavefront per query, four queries per workgroup; beyond,
+ * one workgroup of 256 threads per query.  LDS per query: 8 bytes x round_up(L, 4) (sampler), 8 bytes x round_up(L, 4) + 24 bytes x
+ * round_up(min(Kw, L), 4) (losses).  A query's bits depend on (its data, L, S, K, the parameters, seed, q0 + q) alone; the sampler's are
+ * integer counts of exact comparisons and do not depend on the form either.
+ * PTR_ERR_INVALID_ARG (before any HIP call): B < 0, L <= 0, L > PTR_MAX_LIST_LEN, S outside 1 .. PTR_IRGAN_MAX_SAMPLES, top_k >
+ * PTR_MAX_LIST_LEN, temperature <= 0, infinite or NaN, a mode, prob, family, reward or f_div out of range, and with B > 0 a NULL required
+ * pointer (lens, unif, loss_out, gen_idx_out are optional; d_preds only for PTR_ADLIST_G; std_idx, gen_idx, kq only for PTR_ADLIST_D). */
+#define PTR_ADLIST_D 0
+#define PTR_ADLIST_G 1
+#define PTR_ADLIST_PL 0
+#define PTR_ADLIST_BT 1
+#define PTR_ADLIST_IRGAN 0
+#define PTR_ADLIST_IRFGAN 1
+#define PTR_ADLIST_REWARD_NEG_EXP 0
+#define PTR_ADLIST_REWARD_NEG_LP 1
+#define PTR_ADLIST_REWARD_EXP_1M 2
+#define PTR_ADLIST_REWARD_LOG_1M 3
+int ptr_adlist_sample(const float *preds, const float *labels, const int32_t *lens, int B, int L, int S, int top_k, uint64_t seed, int64_t q0,
+                      const float *unif, int64_t *std_idx, int64_t *gen_idx, int32_t *kq, void *stream);
+int ptr_adlist_fwd_bwd(const float *x, const float *d_preds, const int64_t *std_idx, const int64_t *gen_idx, const int32_t *kq,
+                       const int32_t *lens, int B, int L, int S, int top_k, int mode, int prob, int family, int reward, int f_div,
+                       float temperature, uint64_t seed, int64_t q0, const float *unif, float *loss_out, float *loss_q, float *valid_q,
+                       float *grad, int64_t *gen_idx_out, void *stream);
+
 /* Device tie-shuffled label-descending order (the role of arg_shuffle_ties, sampling_utils.py:13-28) from a
  * counter-based RNG: same distribution, NOT the torch.randperm stream (not parity-checked, statistically tested). */
 int ptr_shuffle_ties_order(const float *labels, const int32_t *lens, int B, int L, uint64_t seed, int64_t *perm,
@@ -884,6 +955,7 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *   ptr_irgan_sel_fwd_bwd                        mode, L                                  G, queries per workgroup
  *   ptr_irfgan_point_sample, ptr_irfgan_pair_sample   L                                   G, queries per workgroup
  *   ptr_irfgan_fwd_bwd                           mode, L                                  G, queries per workgroup
+ *   ptr_adlist_sample, ptr_adlist_fwd_bwd        L                                        G, queries per workgroup
  * G: threads per query, DPT: documents per thread, TP: subtopic tile.  PTR_ERR_INVALID_ARG for an entry without a form, another nargs, or
  * nform below the count. */
 int ptr_launch_form(const char *entry, const int64_t *args, int nargs, int32_t *form, int nform);

@@ -14,7 +14,9 @@
     adversarial the adversarial frame's IRGAN point and pair machines (IRGAN_Point, IRGAN_Pair): device sampling of the documents both
                 players train on and the two players' fused losses; install_adversarial() rebinds them in the reference's driver module;
                 IRFGAN_Point, IRFGAN_Pair (EXTRA_AD_RANKER_NAMES, install_adversarial(extras=True)): the same players under eight
-                f-divergences, the pair machine's n x n Bernoulli sampler recomputed on the device and never stored
+                f-divergences, the pair machine's n x n Bernoulli sampler recomputed on the device and never stored;
+                IRGAN_List, IRFGAN_List (LIST_AD_RANKER_NAMES, install_adversarial_list()): the players on whole rankings — one launch
+                samples the standard and the generated rankings, one fused launch per player gives the ranking-probability loss
     dp          data-parallel gradient exchange (one RCCL all-reduce per step)
     install()   rebinds the ranker names of RANKER_NAMES (RankNet, LambdaRank, LambdaLoss, ApproxNDCG, ListNet, ListMLE, STListNet,
                 RankCosine, RankMSE, SoftRank, WassRank) inside an installed ptranking so LTREvaluator uses them unchanged; a WassRank
@@ -31,8 +33,9 @@ from .gbdt import GBDT, LambdaMART                  # noqa: F401
 from .batching import PaddedQueryBatches            # noqa: F401
 from . import letor                                   # noqa: F401
 from .host import LABEL_TYPE, DeviceEvaluator       # noqa: F401
-from .install import install, install_adversarial, install_diversification, install_tree, uninstall   # noqa: F401
-from .adversarial import AD_RANKER_NAMES, EXTRA_AD_RANKER_NAMES, IRFGAN_Pair, IRFGAN_Point, IRGAN_Pair, IRGAN_Point   # noqa: F401
+from .install import install, install_adversarial, install_adversarial_list, install_diversification, install_tree, uninstall   # noqa: F401
+from .adversarial import (AD_RANKER_NAMES, EXTRA_AD_RANKER_NAMES, LIST_AD_RANKER_NAMES, IRFGAN_List, IRFGAN_Pair, IRFGAN_Point, IRGAN_List,   # noqa: F401
+                          IRGAN_Pair, IRGAN_Point)
 from .tree import TreeObjective                     # noqa: F401
 from .diversity import DALETOR, DIV_RANKER_NAMES, EXTRA_DIV_RANKER_NAMES, DivProbRanker, DivQueryBatches     # noqa: F401
 from .rankers import (ApproxNDCG, LambdaLoss, LambdaRank, ListMLE, ListNet, RankNet, STListNet, RankCosine, RankMSE, SoftRank, WassRank, DASALC, MDPRank,  # noqa: F401

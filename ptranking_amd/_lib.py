@@ -52,6 +52,8 @@ SIGNATURES = {
     "ptr_irfgan_point_sample": [_vp, _vp, _vp, _i, _i, _i, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp],
     "ptr_irfgan_pair_sample": [_vp, _vp, _vp, _vp, _i, _i, _i, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ptr_irfgan_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "ptr_adlist_sample": [_vp, _vp, _vp, _i, _i, _i, _i, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp],
+    "ptr_adlist_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ptr_shuffle_ties_order": [_vp, _vp, _i, _i, _u64, _vp, _vp],
     "ptr_sort_desc": [_vp, _vp, _i, _i, _vp, _vp, _vp],
     "ptr_metrics_at_ks": [_vp, _vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],

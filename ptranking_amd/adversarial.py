@@ -46,8 +46,31 @@ generator's step (ptr_irfgan_fwd_bwd).  What differs from the reference, beyond 
     flag is accumulated on the device and read once per pass, so the pass trains on the remaining lists and batches before it returns
     stop_training = True, where the reference returns at the first such query (irfgan_point.py:188-190, irfgan_pair.py:120-123); once the
     generator's weights are NaN every list is skipped.  Training stops either way.
-Out of scope: IRGAN_List, IRFGAN_List, the semi-supervised (-1 label) route of IRFGAN_Pair, the Gaussian pair sampler, AdLTREvaluator's file
-handling and grid search.
+
+  IRGAN_List    ptranking/ltr_adversarial/listwise/irgan_list.py:24-409
+  IRFGAN_List   ptranking/ltr_adversarial/listwise/irfgan_list.py:20-393
+
+The list machines (LIST_AD_RANKER_NAMES, install_adversarial_list) play on whole rankings: the discriminator tells standard rankings (by
+label, ties shuffled) from the generator's Gumbel-softmax rankings through a Plackett-Luce or Bradley-Terry ranking probability of its own
+scores (PL_D), and the generator follows the Plackett-Luce log-probability of its top_k largest stochastic probabilities, weighted by a
+reward from the discriminator (repTrick, dropLog; the conjugate of the f-divergence under IRFGAN_List).  Per batch and epoch: the
+generator's eval-mode scores, one sampling launch (ptr_adlist_sample), the discriminator's train-mode scores of the padded batch, one loss
+launch (ptr_adlist_fwd_bwd, mode D), one step; then the discriminator's eval-mode scores, the generator's train-mode scores, one fused
+launch that draws, sorts and differentiates (mode G), one step.  The 'DG' / 'GD' order and the refresh of the rankings when
+d_epoch % g_mod == 0 (g_mod = 2 if d_epoches > 1 else 1) are the reference's.  What differs from the reference, on purpose:
+  * ONE optimiser step per batch on the sum of the one-query losses; a batch of one query is the reference's step.
+  * The discriminator scores each document of a list ONCE and the kernel gathers by index, where the reference scores the gathered
+    [S, K, F] copies.  The two agree for point scorers without batch normalisation and dropout; with them, the statistics and the masks
+    see each document once here.
+  * Rankings are ordered by the logit x + gumbel, not by the fp32 softmax of it: the same order wherever the probabilities differ, and
+    a defined one where they underflow to equal zeros.
+  * The draws come from the counter stream (seed, epoch counter, q0 + q), not from torch's generator; the label ties are shuffled by
+    uniform keys of that stream, the law of arg_shuffle_ties' torch.randperm.
+  * Refused with an error: optimal_train=True (NotImplementedError; the reference's driver never sets it, so burn_in is the no-op it is
+    there), list-wise scorers (sf_id 'listsf'), mini_max_train(per_query_ad_training=False) (NotImplementedError there too).
+  * IRFGAN_List.pre_check runs once top_k is set: the reference calls it a few lines earlier and would raise AttributeError under
+    mask_label.
+Out of scope: the semi-supervised (-1 label) route of IRFGAN_Pair, the Gaussian pair sampler, AdLTREvaluator's file handling and grid search.
 """
 import copy
 
@@ -61,6 +84,7 @@ from .scorer import FusedScorerMixin
 
 AD_RANKER_NAMES = ("IRGAN_Point", "IRGAN_Pair")
 EXTRA_AD_RANKER_NAMES = ("IRFGAN_Point", "IRFGAN_Pair")       # install_adversarial(extras=True)
+LIST_AD_RANKER_NAMES = ("IRGAN_List", "IRFGAN_List")          # install_adversarial_list()
 LAMBDA = 0.5                 # irgan_point.py:16
 DRAWS_PER_POS = 5            # irgan_point.py:203
 DEFAULT_AD_PARAS = {         # irgan_point.py:243-253, irgan_pair.py:244-257
@@ -70,6 +94,11 @@ DEFAULT_AD_PARAS = {         # irgan_point.py:243-253, irgan_pair.py:244-257
     # irfgan_point.py:246-258, irfgan_pair.py:196-208 (the machines read f_div_id and samples_per_query alone)
     "IRFGAN_Point": dict(model_id="IRFGAN_Point", samples_per_query=5, d_epoches=1, g_epoches=1, f_div_id="KL", ad_training_order="DG"),
     "IRFGAN_Pair": dict(model_id="IRFGAN_Pair", d_epoches=1, g_epoches=1, f_div_id="KL", ad_training_order="DG", samples_per_query=5),
+    # irgan_list.py:420-433, irfgan_list.py:405-420
+    "IRGAN_List": dict(model_id="IRGAN_List", d_epoches=1, g_epoches=1, temperature=0.2, ad_training_order="DG", samples_per_query=10, top_k=2,
+                       PL_D=True, repTrick=False, dropLog=True),
+    "IRFGAN_List": dict(model_id="IRFGAN_List", d_epoches=1, g_epoches=1, f_div_id="KL", temperature=0.2, ad_training_order="GD",
+                        samples_per_query=10, top_k=10, PL_D=True, repTrick=True, dropLog=True),
 }
 
 
@@ -449,6 +478,133 @@ class IRFGAN_Pair(_IRFGANMachine):
         num_pos, q0 = global_buffer[batch_key(batch)][:2]
         th, tt, fh, ft, nsel = F_.irfgan_pair_sample(g_preds, Y, num_pos, self.samples_per_query, seed=seed, q0=q0, lens=lens)
         return [th, tt, fh, ft], fh, ft, nsel
+
+
+class _ListMachine(_IRGANMachine):
+    """What IRGAN_List and IRFGAN_List share: the players, the per-batch mini-max schedule, the sampling and the two fused losses."""
+
+    model_id, family = None, None
+    first_query = 0              # the global index of train_data's first query: a data-parallel shard sets it, so that it draws its rows
+
+    def __init__(self, eval_dict, data_dict, sf_para_dict=None, ad_para_dict=None, optimal_train=False, gpu=False, device=None):
+        super().__init__(eval_dict=eval_dict, data_dict=data_dict, gpu=gpu, device=device)
+        if optimal_train:
+            raise NotImplementedError(f"{self.model_id}(optimal_train=True): the supervised super-players are not built (the reference's driver "
+                                      "never sets it)")
+        if sf_para_dict['sf_id'] != 'pointsf':
+            raise NotImplementedError(f"{self.model_id} plays with point scorers (sf_id 'pointsf'), got {sf_para_dict['sf_id']!r}")
+        g_sf_para_dict = sf_para_dict
+        d_sf_para_dict = copy.deepcopy(g_sf_para_dict)
+        d_sf_para_dict[sf_para_dict['sf_id']]['apply_tl_af'] = True        # irgan_list.py:35-36, irfgan_list.py:31-32
+        d_sf_para_dict[sf_para_dict['sf_id']]['TL_AF'] = 'S'
+        self.generator = AdversarialPlayer(id=self.model_id + '_Generator', sf_para_dict=g_sf_para_dict, gpu=gpu, device=device)
+        self.discriminator = AdversarialPlayer(id=self.model_id + '_Discriminator', sf_para_dict=d_sf_para_dict, gpu=gpu, device=device)
+        self.top_k = ad_para_dict['top_k']
+        self._set_paras(ad_para_dict)
+        self.f_div_id = ad_para_dict.get('f_div_id', 'KL')
+        F_._f_div(self.f_div_id)
+        if self.top_k is not None and int(self.top_k) < 1:
+            raise ValueError(f"top_k must be None (the whole list) or >= 1, got {self.top_k}")
+        self.PL_discriminator = ad_para_dict['PL_D']
+        self.replace_trick_4_generator = ad_para_dict['repTrick']
+        self.drop_discriminator_log_4_reward = ad_para_dict['dropLog']
+        self.optimal_train = optimal_train
+        self.pre_check()
+
+    def pre_check(self):
+        if self.eval_dict is not None and self.eval_dict['mask_label']:
+            # it is impossible to generate a standard ranking due to the existence of '-1'
+            assert self.top_k is not None
+
+    def burn_in(self, train_data=None):
+        """irgan_list.py:64-97 trains the super-players under optimal_train, which is refused here: nothing to do, as in the reference."""
+
+    def fill_global_buffer(self, train_data, dict_buffer=None):
+        """For listwise, no particular global information is required (irgan_list.py:99-101)."""
+        assert self.data_dict['train_presort'] is True
+
+    @property
+    def _loss_kw(self):
+        return dict(prob="PL" if self.PL_discriminator else "BT", family=self.family, f_div=self.f_div_id, top_k=self.top_k,
+                    reward=F_.adlist_reward(self.replace_trick_4_generator, self.drop_discriminator_log_4_reward))
+
+    def per_query_generation(self, X=None, Y=None, lens=None, generator=None, seed=0, q0=0):
+        """irgan_list.py:230-276 for a padded batch: (std_idx, gen_idx [B, S, Kw], kq [B]) from the generator's scores, one launch."""
+        with torch.no_grad():
+            return F_.adlist_sample(generator.score(X, lens), Y, self.samples_per_query, top_k=self.top_k, seed=seed, q0=q0, lens=lens)
+
+    def train_discriminator(self, discriminator=None, X=None, lens=None, samples=None, **kwargs):
+        std_idx, gen_idx, kq = samples
+        loss = F_.adlist_loss(discriminator.score(X, lens), "D", std_idx=std_idx, gen_idx=gen_idx, kq=kq, lens=lens, **self._loss_kw)
+        discriminator._fused_step(loss)
+        return loss
+
+    def train_generator(self, X=None, lens=None, generator=None, discriminator=None, seed=0, q0=0, **kwargs):
+        with torch.no_grad():
+            d_preds = discriminator.score(X, lens)
+        loss = F_.adlist_loss(generator.score(X, lens), "G", d_preds=d_preds, samples_per_query=self.samples_per_query,
+                              temperature=self.temperature, seed=seed, q0=q0, lens=lens, **self._loss_kw)
+        generator._fused_step(loss)
+        return loss
+
+    def mini_max_train(self, train_data=None, generator=None, discriminator=None, global_buffer=None, per_query_ad_training=True):
+        """irgan_list.py:103-227 per batch: 'DG' the discriminator's d_epoches steps (the rankings refreshed when d_epoch % g_mod == 0), then
+        the generator's g_epoches steps; 'GD' the other way round.  Returns False, as the reference does."""
+        if not per_query_ad_training:
+            raise NotImplementedError
+        g_mod = 2 if self.d_epoches > 1 else 1                              # regarding the generation
+        q0 = int(self.first_query)
+        for batch in train_data:
+            ids, X, Y, lens = unpack_batch(batch)
+
+            def d_part():
+                discriminator.train_mode()
+                generator.eval_mode()
+                samples = None
+                for d_epoch in range(self.d_epoches):
+                    if d_epoch % g_mod == 0:                                # update generated data
+                        samples = self.per_query_generation(X=X, Y=Y, lens=lens, generator=generator, seed=self._next_seed(), q0=q0)
+                    self.train_discriminator(discriminator=discriminator, X=X, lens=lens, samples=samples)
+
+            def g_part():
+                generator.train_mode()
+                discriminator.eval_mode()
+                for _ in range(self.g_epoches):
+                    self.train_generator(X=X, lens=lens, generator=generator, discriminator=discriminator, seed=self._next_seed(), q0=q0)
+
+            for part in ((d_part, g_part) if self.ad_training_order == 'DG' else (g_part, d_part)):
+                part()
+            q0 += len(ids)
+        stop_training = False
+        return stop_training
+
+    generate_data = None
+
+    def get_generator(self, super=False):
+        if super:
+            raise NotImplementedError(f"{self.model_id}: the super-players exist under optimal_train only, which is not built")
+        return self.generator
+
+    def get_discriminator(self, super=False):
+        if super:
+            raise NotImplementedError(f"{self.model_id}: the super-players exist under optimal_train only, which is not built")
+        return self.discriminator
+
+
+class IRGAN_List(_ListMachine):
+    """IRGAN's listwise machine (irgan_list.py:24-409).  ad_para_dict: top_k (None: the whole list), PL_D (the discriminator's ranking
+    probability: Plackett-Luce, else Bradley-Terry), repTrick / dropLog (the generator's reward, get_reward), temperature (of the
+    Gumbel-softmax), d_epoches, g_epoches, ad_training_order, samples_per_query."""
+
+    model_id, family = "IRGAN_List", "IRGAN"
+
+
+class IRFGAN_List(_ListMachine):
+    """IRFGAN's listwise machine (irfgan_list.py:20-393): IRGAN_List with the discriminator's loss mean c(lp(gen)) - mean a(lp(std)) and the
+    generator's reward c(lp) under ad_para_dict['f_div_id'] (functional.F_DIVERGENCES); repTrick and dropLog are read and, as in the
+    reference (:295 overrides :283-292), without effect."""
+
+    model_id, family = "IRFGAN_List", "IRFGAN"
 
 
 def ndcg_at_5(player, data):

@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 OBJ_DIR = os.path.join(PKG_DIR, "csrc", "build")
 LIB_PATH = os.path.join(PKG_DIR, "libptranking_amd.so")
 ARCH = "gfx950"
-SOURCES = ["abi.hip", "pairwise.hip", "pairwise_ring.hip", "lambdaloss.hip", "approxndcg.hip", "listwise.hip", "wassrank.hip", "diversity.hip", "divprob.hip", "ndeval.hip","tree.hip", "gbdt.hip","smoothmetric.hip", "gaussmetric.hip", "plsample.hip", "irgan.hip", "irfgan.hip", "metrics.hip", "scorer.hip", "optim.hip", "scorer_bwd.hip", "scorer_x6.hip", "scorer_bwd_x6.hip", "scorer_dw_x6.hip", "linear.hip", "linear_x6.hip", "linear_bw_x6.hip", "bnact.hip", "listsf.hip", "listsf_wide.hip", "train_step.hip", "letor.cpp"]
+SOURCES = ["abi.hip", "pairwise.hip", "pairwise_ring.hip", "lambdaloss.hip", "approxndcg.hip", "listwise.hip", "wassrank.hip", "diversity.hip", "divprob.hip", "ndeval.hip","tree.hip", "gbdt.hip","smoothmetric.hip", "gaussmetric.hip", "plsample.hip", "irgan.hip", "irfgan.hip", "adlist.hip", "metrics.hip", "scorer.hip", "optim.hip", "scorer_bwd.hip", "scorer_x6.hip", "scorer_bwd_x6.hip", "scorer_dw_x6.hip", "linear.hip", "linear_x6.hip", "linear_bw_x6.hip", "bnact.hip", "listsf.hip", "listsf_wide.hip", "train_step.hip", "letor.cpp"]
 # every header of csrc/ (globbed: one that is forgotten in a hand-kept list leaves a stale .so behind an incremental build) + the public header
 HEADERS = sorted(os.path.basename(h) for h in glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join("..", "..", "include", "ptranking_amd.h")]
 CXXFLAGS = ["-O3", "-std=c++20", "-fPIC", "-fno-gpu-rdc", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",

@@ -6,7 +6,7 @@
 //            (the true pairs), :111-122 (the Bernoulli mask and the multinomial over it); util/f_divergence.py (activation_f, conjugate_f).
 // The reference runs one query per step, holds an n x n matrix of Bradley-Terry probabilities, an n x n Bernoulli mask and a P x n weight
 // matrix, and composes conjugate_f(activation_f(v)) literally in fp32.  Here a padded batch [B, L] with lens and num_pos takes one launch
-// per piece, nothing of size n x n is stored, and the composition is evaluated in closed form (fg_conj below).
+// per piece, nothing of size n x n is stored, and the composition is evaluated in closed form (fg_conj, ptr_irgan.h).
 //
 // The pair sampler (irfgan_pair_sample_kernel), n = lens[q], P = num_pos[q], thread t owns rows t, t + G, ...:
 //   true pairs   w_ij = max(0, y_i - y_j) / (log2(2 + i) log2(2 + j)), i < P, j < n.  Pass 1: every thread sums its own rows over all
@@ -216,42 +216,7 @@ template <int G> __global__ void __launch_bounds__(kBlock) irfgan_pair_sample_ke
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the losses
-// a(v) = activation_f(v) and its derivative (util/f_divergence.py)
-__device__ __forceinline__ void fg_act(int f, float v, float &a, float &da) {
-    switch (f) {
-        case PTR_FDIV_TVAR: {
-            const float e = expf(-2.0f * fabsf(v)), d = 1.0f + e;
-            a = 0.5f * tanhf(v);
-            da = 2.0f * e / (d * d);                                         // 0.5 sech^2 v without the cancellation of 1 - tanh^2
-            break;
-        }
-        case PTR_FDIV_KL: case PTR_FDIV_PC: a = v; da = 1.0f; break;
-        case PTR_FDIV_RKL: da = expf(-v); a = -da; break;
-        case PTR_FDIV_NC: case PTR_FDIV_SH: a = -expm1f(-v); da = expf(-v); break;
-        case PTR_FDIV_JS: a = 0.69314718055994531f - ig_softplus(-v); da = ig_sigmoid(-v); break;
-        default: a = -ig_softplus(-v); da = ig_sigmoid(-v); break;           // PTR_FDIV_GAN
-    }
-}
-// c(v) = conjugate_f(activation_f(v)) in closed form and its derivative; the composition cancels or overflows in fp32 long before these do
-// (GAN: -log(1 - exp(-softplus(-v))) is inf from v = 17 on, where softplus(v) is v)
-__device__ __forceinline__ void fg_conj(int f, float v, float &c, float &dc) {
-    switch (f) {
-        case PTR_FDIV_TVAR: {
-            const float e = expf(-2.0f * fabsf(v)), d = 1.0f + e;
-            c = 0.5f * tanhf(v);
-            dc = 2.0f * e / (d * d);
-            break;
-        }
-        case PTR_FDIV_KL: c = expf(v - 1.0f); dc = c; break;
-        case PTR_FDIV_RKL: c = v - 1.0f; dc = 1.0f; break;
-        case PTR_FDIV_PC: c = 0.25f * v * v + v; dc = 0.5f * v + 1.0f; break;
-        case PTR_FDIV_NC: c = -2.0f * expm1f(-0.5f * v); dc = expf(-0.5f * v); break;
-        case PTR_FDIV_SH: c = expm1f(v); dc = expf(v); break;
-        case PTR_FDIV_JS: c = ig_softplus(v) - 0.69314718055994531f; dc = ig_sigmoid(v); break;
-        default: c = ig_softplus(v); dc = ig_sigmoid(v); break;              // PTR_FDIV_GAN
-    }
-}
-
+// fg_act (a(v) = activation_f(v)) and fg_conj (c(v) = conjugate_f(activation_f(v)) in closed form) live in ptr_irgan.h: adlist.hip shares them
 struct FgLossArgs {
     const float *x, *d_fake;
     const int64_t *idx_a, *idx_b;

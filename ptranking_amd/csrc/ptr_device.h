@@ -141,6 +141,7 @@ struct IrganForm { int G; int QPB; };                    // threads per query, q
 IrganForm irgan_form(int L);                             // irgan.hip: the sampler and the generator step
 IrganForm irgan_sel_form(int mode, int L);               // irgan.hip: the losses on selected documents
 IrganForm irfgan_loss_form(int mode, int L);             // irfgan.hip: the f-divergence losses (its samplers take irgan_form)
+IrganForm adlist_form(int L);                            // adlist.hip: the list machines' sampler and losses
 VecForm listmle_form(int L, bool aligned);
 VecForm lambdaloss_form(int L, int k, int loss_type, int presort, bool aligned);          // lambdaloss.hip: vec = top-k; else (G, DPT) in (G, V)
 Tiling wassrank_form(int L);                                                              // wassrank.hip

@@ -1,5 +1,6 @@
-// What the adversarial frame's kernels share (irgan.hip, irfgan.hip): the stable softplus family, the group helpers of the samplers (any,
-// arg-max, the V largest keys, prefix sums into LDS, the inverse-CDF search) and the argument checks.  The header of irgan.hip states the
+// What the adversarial frame's kernels share (irgan.hip, irfgan.hip, adlist.hip): the stable softplus family, the f-divergences' a(v) and
+// c(v) in closed form, the group helpers of the samplers (any, arg-max, the V largest keys, prefix sums into LDS, the inverse-CDF search)
+// and the argument checks.  The header of irgan.hip states the
 // sampling rules these helpers implement.
 #pragma once
 #include <limits.h>
@@ -26,6 +27,42 @@ __device__ __forceinline__ float ig_logsigmoid(float x) { return -ig_softplus(-x
 __device__ __forceinline__ float ig_sigmoid(float x) {
     const float e = expf(-fabsf(x));
     return x >= 0.0f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+}
+
+// a(v) = activation_f(v) and its derivative (util/f_divergence.py)
+__device__ __forceinline__ void fg_act(int f, float v, float &a, float &da) {
+    switch (f) {
+        case PTR_FDIV_TVAR: {
+            const float e = expf(-2.0f * fabsf(v)), d = 1.0f + e;
+            a = 0.5f * tanhf(v);
+            da = 2.0f * e / (d * d);                                         // 0.5 sech^2 v without the cancellation of 1 - tanh^2
+            break;
+        }
+        case PTR_FDIV_KL: case PTR_FDIV_PC: a = v; da = 1.0f; break;
+        case PTR_FDIV_RKL: da = expf(-v); a = -da; break;
+        case PTR_FDIV_NC: case PTR_FDIV_SH: a = -expm1f(-v); da = expf(-v); break;
+        case PTR_FDIV_JS: a = 0.69314718055994531f - ig_softplus(-v); da = ig_sigmoid(-v); break;
+        default: a = -ig_softplus(-v); da = ig_sigmoid(-v); break;           // PTR_FDIV_GAN
+    }
+}
+// c(v) = conjugate_f(activation_f(v)) in closed form and its derivative; the composition cancels or overflows in fp32 long before these do
+// (GAN: -log(1 - exp(-softplus(-v))) is inf from v = 17 on, where softplus(v) is v)
+__device__ __forceinline__ void fg_conj(int f, float v, float &c, float &dc) {
+    switch (f) {
+        case PTR_FDIV_TVAR: {
+            const float e = expf(-2.0f * fabsf(v)), d = 1.0f + e;
+            c = 0.5f * tanhf(v);
+            dc = 2.0f * e / (d * d);
+            break;
+        }
+        case PTR_FDIV_KL: c = expf(v - 1.0f); dc = c; break;
+        case PTR_FDIV_RKL: c = v - 1.0f; dc = 1.0f; break;
+        case PTR_FDIV_PC: c = 0.25f * v * v + v; dc = 0.5f * v + 1.0f; break;
+        case PTR_FDIV_NC: c = -2.0f * expm1f(-0.5f * v); dc = expf(-0.5f * v); break;
+        case PTR_FDIV_SH: c = expm1f(v); dc = expf(v); break;
+        case PTR_FDIV_JS: c = ig_softplus(v) - 0.69314718055994531f; dc = ig_sigmoid(v); break;
+        default: c = ig_softplus(v); dc = ig_sigmoid(v); break;              // PTR_FDIV_GAN
+    }
 }
 
 template <int G> __device__ __forceinline__ bool group_any(bool v, int *red, int t) {

@@ -19,13 +19,14 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "ndeval_measures", "div_ideal_order", "NDEVAL_MEASURES","divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
            "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "gaussian_metric_objective", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS",
            "irgan_uniforms", "irgan_sample", "irgan_point_generator", "irgan_selected", "IRGAN_SAMPLE_MODES", "IRGAN_SELECTED_MODES", "IRGAN_MAX_SAMPLES",
-           "irfgan_uniforms", "irfgan_point_sample", "irfgan_pair_sample", "IRFGAN_MODES", "F_DIVERGENCES", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES",
+           "irfgan_uniforms", "irfgan_point_sample", "irfgan_pair_sample", "IRFGAN_MODES", "F_DIVERGENCES",
+           "adlist_uniforms", "adlist_sample", "ADLIST_MODES", "ADLIST_PROBS", "ADLIST_FAMILIES", "ADLIST_REWARDS", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES",
            "gbdt_bin", "gbdt_quantize", "gbdt_histogram", "gbdt_hist_sub", "gbdt_best_split", "gbdt_partition", "gbdt_add_leaf_values", "gbdt_predict",
            "gbdt_histogram_segments", "gbdt_hist_sub_segments", "gbdt_best_split_slots", "gbdt_partition_segments", "gbdt_segment_items",
            "GBDT_MAX_BIN", "GBDT_RECORD"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
-# launch table, and it draws its own; irfgan_loss is public too: it takes selected documents and a mode, as irgan_selected does)
+# launch table, and it draws its own; irfgan_loss and adlist_loss are public too: they take a mode, as irgan_selected does)
 LAMBDALOSS_TYPES = {"NDCG_Loss1": 0, "NDCG_Loss2": 1, "NDCG_Loss2++": 2}   # ptranking/ltr_adhoc/listwise/lambdaloss.py:27
 ADCG_TOPK_AXES = {"reference": 0, "subtopics": 0, 0: 0, "documents": 1, 1: 1}   # PTR_ADCG_TOPK_*
 NDEVAL_MEASURES = ("ERR-IA", "nERR-IA", "alpha-DCG", "alpha-nDCG", "NRBP", "nNRBP", "MAP-IA", "P-IA", "strec")   # ndeval.c:1214-1222, its CSV columns
@@ -41,6 +42,10 @@ IRGAN_SELECTED_MODES = {"POINT_D": 0, "PAIR_D_SVM": 1, "PAIR_D_LOG": 2, "PAIR_G_
 IRGAN_MAX_SAMPLES = 64                                                     # PTR_IRGAN_MAX_SAMPLES
 IRFGAN_MODES = {"POINT_D": 0, "PAIR_D": 1, "POINT_G": 2, "PAIR_G": 3}       # PTR_IRFGAN_*; irfgan_point.py:200-220, irfgan_pair.py:141-170
 F_DIVERGENCES = {"TVar": 0, "KL": 1, "RKL": 2, "PC": 3, "NC": 4, "SH": 5, "JS": 6, "GAN": 7}   # PTR_FDIV_*; ltr_adversarial/util/f_divergence.py
+ADLIST_MODES = {"D": 0, "G": 1}                                              # PTR_ADLIST_D, _G; listwise/irgan_list.py:315-341, :344-395
+ADLIST_PROBS = {"PL": 0, "BT": 1}                                            # PTR_ADLIST_PL, _BT; util/list_probability.py (PL_D True | False)
+ADLIST_FAMILIES = {"IRGAN": 0, "IRFGAN": 1}                                  # PTR_ADLIST_IRGAN, _IRFGAN
+ADLIST_REWARDS = {"neg_exp": 0, "neg_lp": 1, "exp_1m": 2, "log_1m": 3}       # PTR_ADLIST_REWARD_*; irgan_list.py:301-310
 GBDT_MAX_BIN = 256                                                         # PTR_GBDT_MAX_BIN
 GBDT_RECORD = ("gain", "feature", "bin", "left_g", "left_h", "left_count", "right_g", "right_h", "right_count")   # a split record's 9 int64
 WASS_COST_TYPES = {"p1": 0, "p2": 1, "eg": 2, "dg": 3, "ddg": 4}   # PTR_WASS_COST_*; wassrank/wasserstein_cost_mat.py:113-139
@@ -726,6 +731,104 @@ def irfgan_loss(x, nsel, mode, f_div, d_fake=None, idx_a=None, idx_b=None, lens=
     loss, parts = _fused("ptr_irfgan_fwd_bwd", [x], [x_c], [d_fake, idx_a, idx_b, nsel, lens, B, L, S, m, f], own_loss=True,
                          slots=(("loss_q", None), ("valid_q", None)))
     return (loss, parts) if return_parts else loss
+
+
+def adlist_reward(repTrick, dropLog):
+    """The name in ADLIST_REWARDS of get_reward's branch (listwise/irgan_list.py:301-310) for the reference's two switches."""
+    return ("neg_exp" if dropLog else "neg_lp") if repTrick else ("exp_1m" if dropLog else "log_1m")
+
+
+def _adlist_top_k(top_k, L):
+    """-> (the C argument, Kw): None or <= 0 is the whole list."""
+    k = 0 if top_k is None else int(top_k)
+    if k > _lib.MAX_LIST_LEN:
+        raise ValueError(f"top_k {k} exceeds the supported maximum {_lib.MAX_LIST_LEN}")
+    return (k, k) if k > 0 else (0, L)
+
+
+def adlist_uniforms(B, L, samples_per_query, mode="D", seed=0, q0=0, device=None):
+    """The uniforms adlist_sample (mode 'D': float32 [B, 2 S, L], streams 0 .. S-1 the Gumbel uniforms of the generated rankings, S .. 2S-1
+    the tie keys of the standard ones) and adlist_loss(mode='G') ([B, S, L], the same streams 0 .. S-1) draw for (seed, q0)."""
+    S = _irgan_samples(samples_per_query)
+    return pl_uniforms(B, L, samples=2 * S if _enum("mode", mode, ADLIST_MODES) == 0 else S, seed=seed, q0=q0, device=device)
+
+
+def adlist_sample(preds, labels, samples_per_query, top_k=None, seed=0, q0=0, lens=None, unif=None):
+    """The rankings the list machines' discriminator trains on (ptranking/ltr_adversarial/listwise/irgan_list.py:230-276), one launch ->
+    (std_idx, gen_idx int64 [B, S, Kw], kq int32 [B]); Kw = top_k, or L for the whole list (top_k None); per query Kq = kq = min(top_k, n)
+    valid positions, 0 beyond.  gen_idx: the first Kq documents of the descending order of preds + gumbel — the prefix of
+    sample_rankings_pl(distribution='STPL') for the same (seed, q0), the order of the reference's gumbel_softmax probabilities.  std_idx:
+    the first Kq documents by label, descending, ties in uniformly random order (arg_shuffle_ties); labels of -1 sort last.  A list with a
+    NaN score gets kq = 0.  `unif` float32 [B, 2 S, L] replaces the generator (adlist_uniforms).  Not differentiable."""
+    S = _irgan_samples(samples_per_query)
+    preds, labels, lens, B, L = _batch(preds.detach(), labels, lens)
+    k, Kw = _adlist_top_k(top_k, L)
+    dev = preds.device
+    unif = _pl_unif(unif, B, 2 * S, L, dev)
+    std = torch.empty((B, S, Kw), device=dev, dtype=torch.int64)
+    gen = torch.empty((B, S, Kw), device=dev, dtype=torch.int64)
+    kq = torch.empty(B, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_adlist_sample", _lib.ptr(preds), _lib.ptr(labels), _lib.ptr(lens), B, L, S, k, _seed64(seed), C.c_int64(int(q0)),
+                  _lib.ptr(unif), _lib.ptr(std), _lib.ptr(gen), _lib.ptr(kq), _lib.current_stream(dev))
+    return std, gen, kq
+
+
+def adlist_loss(x, mode, prob="PL", family="IRGAN", reward="exp_1m", f_div="KL", std_idx=None, gen_idx=None, kq=None, d_preds=None,
+                samples_per_query=None, top_k=None, temperature=1.0, seed=0, q0=0, lens=None, unif=None, return_parts=False):
+    """The list machines' losses on ranking probabilities, loss and gradient in one launch -> the sum over queries, differentiable in x.
+    prob 'PL' | 'BT': the Plackett-Luce or Bradley-Terry log-probability lp of a ranking's scores (util/list_probability.py).
+    mode 'D' (irgan_list.py:315-341, irfgan_list.py:322): x = the discriminator's scores of the whole padded batch [B, L]; std_idx, gen_idx
+    [B, S, Kw] and kq [B] from adlist_sample; family 'IRGAN': -sum_s lp(x[std_s]) - sum_s log(1 - lp(x[gen_s])); 'IRFGAN':
+    mean_s c(lp(x[gen_s])) - mean_s a(lp(x[std_s])) under f_div (F_DIVERGENCES; a, c as irfgan_loss).
+    mode 'G' (irgan_list.py:344-395, irfgan_list.py:328-379): x = the generator's scores, d_preds [B, L] the discriminator's (detached)
+    scores; the kernel draws samples_per_query Gumbel-softmax rankings per query from (seed, q0) (or unif [B, S, L]) at `temperature`,
+    keeps the top_k largest probabilities, and weighs their Plackett-Luce log-probability by the reward of the discriminator's lp of the
+    same documents: 'IRGAN' mean_s A_s R_s with `reward` (ADLIST_REWARDS, adlist_reward); 'IRFGAN' -mean_s A_s c(lp).
+    A query with kq = 0 (an empty list, a NaN score) contributes nothing.  With return_parts also returns dict(loss_q [B], valid_q [B],
+    and under 'G' gen_idx int64 [B, S, Kw])."""
+    m = _enum("mode", mode, ADLIST_MODES)
+    pr = _enum("prob", prob, ADLIST_PROBS)
+    fam = _enum("family", family, ADLIST_FAMILIES)
+    rw = _enum("reward", reward, ADLIST_REWARDS)
+    f = _f_div(f_div)
+    if m == ADLIST_MODES["D"] and (std_idx is None or gen_idx is None or kq is None):
+        raise ValueError("mode 'D' needs std_idx, gen_idx and kq (adlist_sample)")
+    if m == ADLIST_MODES["G"] and (d_preds is None or samples_per_query is None):
+        raise ValueError("mode 'G' needs d_preds and samples_per_query")
+    x_c, B, L = _matrix("x", x.detach())
+    _list_len(L)
+    dev = x_c.device
+    lens = _counts("lens", lens, B)
+    gout = None
+    if m == ADLIST_MODES["D"]:
+        std_idx = _check("std_idx", std_idx, torch.int64)
+        if std_idx.dim() != 3 or std_idx.shape[0] != B:
+            raise ValueError(f"std_idx must be [batch, samples_per_query, top_k], got {tuple(std_idx.shape)}")
+        S, Kw = _irgan_samples(std_idx.shape[1]), int(std_idx.shape[2])
+        gen_idx = _check("gen_idx", gen_idx, torch.int64, (B, S, Kw))
+        kq = _check("kq", kq, torch.int32, (B,))
+        k, want = _adlist_top_k(top_k if top_k is not None else (None if Kw == L else Kw), L)
+        if want != Kw:
+            raise ValueError(f"std_idx holds {Kw} positions per ranking, top_k={top_k!r} asks for {want}")
+        d_preds = unif = None
+    else:
+        S = _irgan_samples(samples_per_query)
+        d_preds = _check("d_preds", d_preds.detach(), shape=(B, L))
+        k, Kw = _adlist_top_k(top_k, L)
+        unif = _pl_unif(unif, B, S, L, dev)
+        std_idx = gen_idx = kq = None
+        gout = torch.empty((B, S, Kw), device=dev, dtype=torch.int64) if return_parts else None
+    if any(t is not None and t.device != dev for t in (std_idx, gen_idx, kq, d_preds, lens)):
+        raise RuntimeError("x, std_idx, gen_idx, kq, d_preds and lens live on different devices")
+    loss, parts = _fused("ptr_adlist_fwd_bwd", [x], [x_c],
+                         [d_preds, std_idx, gen_idx, kq, lens, B, L, S, k, m, pr, fam, rw, f, C.c_float(float(temperature)), _seed64(seed),
+                          C.c_int64(int(q0)), unif], own_loss=True, slots=(("loss_q", None), ("valid_q", None)), tail=(gout,))
+    if return_parts:
+        if gout is not None:
+            parts["gen_idx"] = gout
+        return loss, parts
+    return loss
 
 
 def _ragged(entry, preds, labels, offsets, queries, max_len, out, *params):

@@ -88,6 +88,24 @@ def install_adversarial(names=None, ltr_module="ptranking.ltr_adversarial.eval.l
     return done
 
 
+def install_adversarial_list(names=None, ltr_module="ptranking.ltr_adversarial.eval.ltr_adversarial"):
+    """Rebind LIST_AD_RANKER_NAMES (IRGAN_List, IRFGAN_List) inside the reference's adversarial driver module, as install_adversarial does
+    for the point and pair machines (which it leaves alone, as install_adversarial leaves these); returns {name: installed class}.  `names`
+    picks a subset.  The default install() binds neither.  uninstall() restores."""
+    from .adversarial import LIST_AD_RANKER_NAMES, IRFGAN_List, IRGAN_List
+    classes = {"IRGAN_List": IRGAN_List, "IRFGAN_List": IRFGAN_List}
+    names = LIST_AD_RANKER_NAMES if names is None else tuple(names)
+    mod = importlib.import_module(ltr_module)
+    done = {}
+    for n in names:
+        if n not in classes:
+            raise KeyError(f"{n} is not one of {LIST_AD_RANKER_NAMES}")
+        _saved.setdefault((ltr_module, n), getattr(mod, n, None))
+        setattr(mod, n, classes[n])
+        done[n] = classes[n]
+    return done
+
+
 def install_tree(util_module="ptranking.ltr_tree.util.lightgbm_util", user_modules=("ptranking.ltr_tree.lambdamart.lightgbm_lambdaMART",)):
     """Rebind the six custom LightGBM objectives (ptranking_amd.tree.DROP_IN_NAMES: lightgbm_custom_obj_{ranknet,lambdarank,listnet} and
     their *_fobj forms) inside the reference's lightgbm_util module, and inside each of `user_modules` that is ALREADY imported: the
@@ -109,7 +127,7 @@ def install_tree(util_module="ptranking.ltr_tree.util.lightgbm_util", user_modul
 
 def uninstall(ltr_module=None):
     """Restore the reference's own classes and functions: in `ltr_module`, or (default) in every module install(), install_diversification(),
-    install_adversarial() or install_tree() touched."""
+    install_adversarial(), install_adversarial_list() or install_tree() touched."""
     for m in sorted({m for m, _ in _saved} if ltr_module is None else {ltr_module}):
         _uninstall_module(m)
 
