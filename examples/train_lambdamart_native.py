@@ -3,6 +3,8 @@
     python examples/train_lambdamart_native.py                                   # synthetic data
     python examples/train_lambdamart_native.py train.txt [vali.txt] [test.txt]   # LETOR text files
     python examples/train_lambdamart_native.py --grow-policy depthwise           # level by level, in batched passes
+    python examples/train_lambdamart_native.py --bagging-fraction 0.5 --bagging-freq 1 --by-query   # every tree on a fresh half of the queries
+    python examples/train_lambdamart_native.py --goss                            # gradient-based one-side sampling (top 0.2, other 0.1)
 
 The synthetic relevance is planted: a linear part plus a feature interaction a linear scorer cannot express, graded with MSLR-WEB30K's label
 mix.  Prints the validation nDCG@5 every 10 rounds.  No LightGBM comparison: the library is not installed where this project is tested.
@@ -47,6 +49,10 @@ def main():
     ap.add_argument("--min-data-in-leaf", type=int, default=20)
     ap.add_argument("--grow-policy", default="leafwise", choices=["leafwise", "depthwise"],
                     help="depthwise: all leaves of a level are split in one batched pass (one host read per level, not per split)")
+    ap.add_argument("--bagging-fraction", type=float, default=1.0, help="the share of rows (of queries with --by-query) a tree is grown on")
+    ap.add_argument("--bagging-freq", type=int, default=0, help="redraw the bag every k trees; 0: no bagging")
+    ap.add_argument("--by-query", action="store_true", help="bagging samples whole queries")
+    ap.add_argument("--goss", action="store_true", help="data_sample_strategy='goss' in place of bagging")
     ap.add_argument("--queries", type=int, default=600)
     ap.add_argument("--features", type=int, default=40)
     args = ap.parse_args()
@@ -57,8 +63,12 @@ def main():
     else:
         train, valid, test = synthetic(args.queries, args.features, 7), synthetic(args.queries // 4, args.features, 8), synthetic(args.queries // 4, args.features, 9)
     params = {"num_leaves": args.num_leaves, "learning_rate": args.learning_rate, "min_data_in_leaf": args.min_data_in_leaf, "num_trees": args.rounds,
-              "grow_policy": args.grow_policy}
+              "grow_policy": args.grow_policy, "bagging_fraction": args.bagging_fraction, "bagging_freq": args.bagging_freq,
+              "bagging_by_query": args.by_query, "data_sample_strategy": "goss" if args.goss else "bagging"}
     lm = pa.LambdaMART(params, objective=args.objective)
+    how = {None: "none", "goss": f"goss (top_rate {lm.params['top_rate']}, other_rate {lm.params['other_rate']})",
+           "bagging": f"bagging {args.bagging_fraction} {'by query' if args.by_query else 'by row'}, redrawn every {args.bagging_freq} trees"}
+    print(f"sampling: {how[pa.gbdt.sampling(lm.params)]}")
     yv = torch.from_numpy(valid[1]).cuda()
     constant = pa.LambdaMART.ndcg_at(torch.zeros(valid[0].shape[0], device="cuda"), yv, valid[2], 5)
     print(f"{train[0].shape[0]} training documents in {train[2].size} queries, {train[0].shape[1]} features; constant scores: valid nDCG@5 {constant:.4f}")

@@ -951,6 +951,9 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *   ptr_gbdt_hist_sub_segments                   K                                        launches of one call (1), workgroup rows per triple
  *   ptr_gbdt_best_split_slots                    K                                        launches of one call (2), 0
  *   ptr_gbdt_partition_segments                  m                                        launches of one call (3), workgroups of a segment of m rows
+ *   ptr_gbdt_goss                                n                                        counting passes (3), digits per pass (2048), workgroups
+ *                                                                                           of a pass, launches of one call (5; 0 for n == 0)
+ *   ptr_gbdt_partition_mask                      m                                        launches of one call (3), workgroups of a list of m rows
  *   ptr_irgan_sample, ptr_irgan_point_gen_fwd_bwd   L                                     G, queries per workgroup
  *   ptr_irgan_sel_fwd_bwd                        mode, L                                  G, queries per workgroup
  *   ptr_irfgan_point_sample, ptr_irfgan_pair_sample   L                                   G, queries per workgroup
@@ -963,7 +966,7 @@ int ptr_launch_form(const char *entry, const int64_t *args, int nargs, int32_t *
 /* ---- A histogram gradient-boosted tree trainer (csrc/gbdt.hip).  The symbols below are ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
  * The reference's tree frame (ptranking/ltr_tree/lambdamart/lightgbm_lambdaMART.py) hands the boosting to LightGBM; ptranking_amd/gbdt.py
  * grows the trees leaf-wise on these entry points instead.  No parity with LightGBM is claimed: the binning and tie rules are this
- * project's own, and there is no GOSS, EFB, categorical or missing-value handling.
+ * project's own (the row-sampling rules of the section after next among them), and there is no EFB, categorical or missing-value handling.
  *
  * Common rules: every argument is validated before any launch (PTR_ERR_INVALID_ARG: a NULL pointer that a launch would touch, a negative
  * size, max_bin < 2, a stride that is no multiple of 16 or below F; PTR_ERR_UNSUPPORTED: max_bin > PTR_GBDT_MAX_BIN); an empty input
@@ -1052,6 +1055,47 @@ size_t ptr_gbdt_partition_segments_ws_ints(int64_t nblocks);
 int ptr_gbdt_partition_segments(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t nrows, const int32_t *segs, int K,
                                 const int32_t *blocks, int nblocks, int32_t *out, int32_t *left_counts, int32_t *ws, int64_t ws_ints,
                                 void *stream);
+
+/* ---- Row sampling for the tree trainer: bagging by row or by query, and GOSS (csrc/gbdt.hip; bagging_fraction, bagging_freq,
+ * bagging_by_query and data_sample_strategy='goss' of ptranking_amd/gbdt.py).  ADDITIVE to ABI v8 too.  The rules are this project's own; no
+ * parity with LightGBM's random streams is claimed.  tests/gbdt_sample_ref.py restates them in numpy.  Argument rules as above: everything
+ * is validated before any launch (PTR_ERR_INVALID_ARG: a NULL pointer a launch would touch, a negative size or draw, n > 2^31 - 1, a rate
+ * outside its range, a bad bins layout), and an empty input launches nothing.
+ *
+ * Uniforms.  u(draw, unit) = pl_uniform(pl_query_keys(seed, draw), (uint32_t)unit) of the counter stream of the device samplers
+ *   (csrc/ptr_plhash.h): a multiple of 2^-24 in [0, 1) that depends on (seed, draw, unit) alone.
+ * ptr_gbdt_bag_mask: mask[r] = u(draw, unit_r) < fraction, one byte per row, 1 = in the bag; unit_r = r, or qid[r] when qid is given (all
+ *   rows of a query share one draw).  A Bernoulli draw per unit, not a fixed count.  fraction in (0, 1]; 1.0 keeps every row.  The
+ *   trainer's tree t (from 0) uses draw = t / bagging_freq (integer division) and fraction = (float)bagging_fraction.
+ * ptr_gbdt_goss: gradient-based one-side sampling of one round.  key_r = fabsf(g_r * h_r), one fp32 product; K = max(1, floor(n top_rate))
+ *   with the product in float64; tau = the K-th largest key, found exactly by a radix select over the keys' uint32 bit patterns (three
+ *   counting passes, integer counters only; a NaN key counts as the smallest).  A row with key >= tau is in the top set and keeps g, h: ties
+ *   at tau are all in, so the top set may exceed K.  Any other row (a NaN key compares false and is one) is kept iff
+ *   u(draw, r) < (float)(other_rate / (1 - top_rate)), and a KEPT other row has g and h multiplied in fp32 by
+ *   (float)((1 - top_rate) / other_rate); a dropped row's g and h are copied unchanged (a NaN stays a NaN for ptr_gbdt_quantize's flag).
+ *   Writes g_out, h_out [n] (each may be its input), mask [n] (1 = kept) and info [3] = {tau's bit pattern, the size of the top set, the
+ *   number kept}.  top_rate, other_rate > 0 with top_rate + other_rate <= 1.  ws: ptr_gbdt_goss_ws_ints(n) int32 of scratch.  The trainer
+ *   uses draw = t and leaves the first floor(1 / learning_rate) trees unsampled.
+ * ptr_gbdt_partition_mask: ptr_gbdt_partition's stable count / scan / scatter (the same three kernels) under the predicate mask[row] != 0:
+ *   out = the rows of rows[0 .. m) with a set mask byte in their order, then the others in theirs; left_count [1] = how many were kept.
+ *   rows == NULL is the list 0 .. m - 1.  A row index outside [0, n) is not kept and its mask byte is never read.  out must not be rows.
+ *   ws: ptr_gbdt_partition_ws_ints(m) int32.
+ * ptr_gbdt_add_tree_binned: scores[rows[i]] += the leaf value ONE tree gives the binned row, i < m (rows == NULL: the rows 0 .. m - 1; a
+ *   row index outside [0, n) is skipped).  The tree is in ptr_gbdt_predict's node layout with the split BIN in place of the threshold
+ *   (feature, bin, left, right [nnodes], value [nnodes + 1]; nnodes == 0 is a single leaf); a row goes left on bins[row][feature] <= bin,
+ *   which is x <= edges[feature][bin] by the binning rule, so the value is the one ptr_gbdt_predict adds for the raw row.  A malformed
+ *   tree adds NaN, never a read out of range.  The rows of the list must be distinct.
+ * A sampled tree is grown on the front segment [0, left_count) of the partitioned list and its leaf values reach the rows behind it through
+ * ptr_gbdt_add_tree_binned, so the resident training scores stay the bits of ptr_gbdt_predict for every row. */
+int ptr_gbdt_bag_mask(int64_t n, const int32_t *qid, uint64_t seed, int64_t draw, float fraction, uint8_t *mask, void *stream);
+size_t ptr_gbdt_goss_ws_ints(int64_t n);
+int ptr_gbdt_goss(const float *g, const float *h, int64_t n, double top_rate, double other_rate, uint64_t seed, int64_t draw, float *g_out,
+                  float *h_out, uint8_t *mask, int32_t *info, int32_t *ws, void *stream);
+int ptr_gbdt_partition_mask(const uint8_t *mask, int64_t n, const int32_t *rows, int64_t m, int32_t *out, int32_t *left_count, int32_t *ws,
+                            void *stream);
+int ptr_gbdt_add_tree_binned(float *scores, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m,
+                             const int32_t *feature, const int32_t *bin, const int32_t *left, const int32_t *right, const float *value,
+                             int nnodes, void *stream);
 
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):

@@ -109,13 +109,18 @@ SIGNATURES = {
     "ptr_gbdt_best_split_slots": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, C.c_double, C.c_int64, C.c_double, C.c_double, _vp, _vp, _vp],
     "ptr_gbdt_partition_segments_ws_ints": [C.c_int64],
     "ptr_gbdt_partition_segments": [_vp, _i, C.c_int64, _i, _vp, C.c_int64, _vp, _i, _vp, _i, _vp, _vp, _vp, C.c_int64, _vp],
+    "ptr_gbdt_bag_mask": [C.c_int64, _vp, _u64, C.c_int64, _f, _vp, _vp],
+    "ptr_gbdt_goss_ws_ints": [C.c_int64],
+    "ptr_gbdt_goss": [_vp, _vp, C.c_int64, C.c_double, C.c_double, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ptr_gbdt_partition_mask": [_vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _vp],
+    "ptr_gbdt_add_tree_binned": [_vp, _vp, _i, C.c_int64, _i, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "ptr_letor_scan":[C.c_char_p, _i, _vp, _vp, _vp],
     "ptr_letor_load": [C.c_char_p, _i, _f, C.c_int64, C.c_int32, C.c_int64, _vp, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {"ptr_last_error": C.c_char_p, "ptr_mlp_num_params": C.c_size_t, "ptr_mlp_backward_ws_floats": C.c_size_t,
              "ptr_mlp_backward_dz_floats": C.c_size_t, "ptr_mlp_acts_floats": C.c_size_t, "ptr_mlp_x6_ws_bytes": C.c_size_t, "ptr_linear_backward_weight_ws_floats": C.c_size_t, "ptr_bn_ws_floats": C.c_size_t,
              "ptr_bn_slot_floats": C.c_size_t, "ptr_gbdt_partition_ws_ints": C.c_size_t,
-             "ptr_gbdt_partition_segments_ws_ints": C.c_size_t,
+             "ptr_gbdt_partition_segments_ws_ints": C.c_size_t, "ptr_gbdt_goss_ws_ints": C.c_size_t,
              "ptr_layernorm_backward_ws_floats": C.c_size_t}
 OPTIONAL = set()
 

@@ -20,7 +20,16 @@
 //            entry, 80 KiB at 256 bins: two workgroups per compute unit), each lane loads one row's 16 bins as a uint4 and its qg, qh once,
 //            and walks the 16 features ROTATED by its lane number: in one step the 64 lanes address 16 different features, so a constant
 //            feature (every row in one bin) meets 4 lanes per address and step, not 64.  The flush adds only the bins the chunk touched.
+//
+// Row sampling (bagging by row or by query, GOSS): a keep mask of one byte per row, the stable partition under the predicate mask[row], and
+// a walk of the finished tree over the binned rows outside the bag.  GOSS's threshold is the exact K-th largest |g h|: the keys are
+// non-negative floats, their uint32 bit patterns order as integers, and a radix select of three counting passes (digits of 11, 11 and 10
+// bits; LDS counters flushed with one integer atomic per touched digit) finds it without sorting and without a float atomic.  Each pass
+// starts by reading the finished table of the pass before, in every workgroup alike, so no launch exists only to pick a digit.
+#include <math.h>
+
 #include "ptr_gbdt.h"
+#include "ptr_plhash.h"
 
 namespace ptr {
 
@@ -284,15 +293,27 @@ __device__ __forceinline__ bool part_goes_left(const uint8_t *__restrict__ bins,
     return row >= 0 && row < n && (int)bins[(size_t)row * stride + feature] <= bin;
 }
 
-__global__ void __launch_bounds__(kBlock)
-gbdt_part_count_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ rows, int m, int feature, int bin,
-                       int32_t *__restrict__ counts) {
+// The predicates of the stable partition: pred(i, row) gives entry i's row (-1 past the list) and whether it goes to the front.
+struct PartByBin {                                                      // ptr_gbdt_partition: bins[row][feature] <= bin
+    const uint8_t *bins; int stride, n; const int32_t *rows; int m, feature, bin;
+    __device__ __forceinline__ bool operator()(int64_t i, int &row) const { return part_goes_left(bins, stride, n, rows, i, m, feature, bin, row); }
+};
+struct PartByMask {                                                     // ptr_gbdt_partition_mask: mask[row] != 0; rows == NULL: the list 0 .. m - 1
+    const uint8_t *mask; int n; const int32_t *rows; int m;
+    __device__ __forceinline__ bool operator()(int64_t i, int &row) const {
+        row = i < m ? (rows ? rows[i] : (int)i) : -1;
+        return row >= 0 && row < n && mask[row] != 0;
+    }
+};
+
+template <class Pred> __global__ void __launch_bounds__(kBlock)
+gbdt_part_count_kernel(const Pred pred, int32_t *__restrict__ counts) {
     __shared__ int32_t tot;
     if (threadIdx.x == 0) tot = 0;
     __syncthreads();
     int c = 0, row;
     for (int s = 0; s < kPartSteps; ++s)
-        c += part_goes_left(bins, stride, n, rows, ((int64_t)blockIdx.x * kPartSteps + s) * kBlock + threadIdx.x, m, feature, bin, row) ? 1 : 0;
+        c += pred(((int64_t)blockIdx.x * kPartSteps + s) * kBlock + threadIdx.x, row) ? 1 : 0;
     atomicAdd(&tot, c);
     __syncthreads();
     if (threadIdx.x == 0) counts[blockIdx.x] = tot;
@@ -319,9 +340,8 @@ gbdt_part_scan_kernel(int32_t *__restrict__ counts, int nb, int32_t *__restrict_
     if (t == kBlock - 1) { counts[nb] = seg[t]; left_count[0] = seg[t]; }
 }
 
-__global__ void __launch_bounds__(kBlock)
-gbdt_part_scatter_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ rows, int m, int feature, int bin,
-                         const int32_t *__restrict__ counts, int nb, int32_t *__restrict__ out) {
+template <class Pred> __global__ void __launch_bounds__(kBlock)
+gbdt_part_scatter_kernel(const Pred pred, const int32_t *__restrict__ counts, int nb, int32_t *__restrict__ out) {
     __shared__ int32_t wave_left[kBlock / kWave];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     int left_before = counts[blockIdx.x];
@@ -329,14 +349,14 @@ gbdt_part_scatter_kernel(const uint8_t *__restrict__ bins, int stride, int n, co
     for (int s = 0; s < kPartSteps; ++s) {
         const int64_t i = ((int64_t)blockIdx.x * kPartSteps + s) * kBlock + threadIdx.x;
         int row;
-        const bool left = part_goes_left(bins, stride, n, rows, i, m, feature, bin, row);
+        const bool left = pred(i, row);
         const unsigned long long mask = __ballot(left);
         if (lane == 0) wave_left[wave] = __popcll(mask);
         __syncthreads();
         int before = left_before + __popcll(mask & ((1ull << lane) - 1));
         int step_left = 0;
         for (int w = 0; w < kBlock / kWave; ++w) { if (w < wave) before += wave_left[w]; step_left += wave_left[w]; }
-        if (i < m) out[left ? before : total_left + (int)(i - before)] = row;     // `before` = the lefts ahead of entry i
+        if (i < pred.m) out[left ? before : total_left + (int)(i - before)] = row;     // `before` = the lefts ahead of entry i
         left_before += step_left;
         __syncthreads();
     }
@@ -559,6 +579,143 @@ gbdt_predict_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t
     out[i] = s;
 }
 
+// One finished tree over the BINNED rows of a row list: x <= edges[f][b] is bin <= b, so the walk lands in the leaf ptr_gbdt_predict finds on
+// the raw row, and the same fp32 value is added.  The rows a sampled tree was not grown on get their leaf value here.
+__global__ void __launch_bounds__(kBlock)
+gbdt_add_tree_binned_kernel(float *__restrict__ scores, const uint8_t *__restrict__ bins, int stride, int n, int F, const int32_t *__restrict__ rows,
+                            int m, const int32_t *__restrict__ feature, const int32_t *__restrict__ bin, const int32_t *__restrict__ left,
+                            const int32_t *__restrict__ right, const float *__restrict__ value, int nn) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m) return;
+    const int row = rows ? rows[i] : i;
+    if (row < 0 || row >= n) return;
+    const uint8_t *x = bins + (size_t)row * stride;
+    int node = nn > 0 ? 0 : ~0;
+    for (int step = 0; step < nn && node >= 0; ++step) {
+        if (node >= nn) break;
+        const int f = feature[node];
+        if (f < 0 || f >= F) break;
+        node = (int)x[f] <= bin[node] ? left[node] : right[node];
+    }
+    scores[row] += (node < 0 && ~node <= nn) ? value[~node] : NAN;      // a malformed tree (a cycle, an index out of range) gives NaN
+}
+
+// ---------------------------------------------------------------- row sampling: the bag and GOSS
+// u(draw, unit) = pl_uniform(pl_query_keys(seed, draw), unit) of ptr_plhash.h: a multiple of 2^-24 in [0, 1), a function of its three
+// arguments alone.  include/ptranking_amd.h states the rules; tests/gbdt_sample_ref.py restates them.
+__global__ void __launch_bounds__(kBlock)
+gbdt_bag_mask_kernel(int64_t n, const int32_t *__restrict__ qid, uint64_t seed, int64_t draw, float fraction, uint8_t *__restrict__ mask) {
+    const PlKeys keys = pl_query_keys(seed, draw);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+        mask[i] = pl_uniform(keys, qid ? (uint32_t)qid[i] : (uint32_t)i) < fraction ? 1 : 0;
+}
+
+// The digit that holds the K-th largest of the keys a table of kGossDigits counters counted (K >= 1, at most their number), and K less the
+// keys in the digits above it.  Thread t sums the 8 digits below the top - 8 t; one scan over the 256 sums.  Every thread of every workgroup
+// gets the same answer: it depends on the finished table alone.
+__device__ __forceinline__ void goss_pick(const uint32_t *__restrict__ table, uint32_t K, uint32_t &digit, uint32_t &krem) {
+    __shared__ uint32_t scan[kBlock];
+    __shared__ uint32_t res[2];
+    constexpr int per = kGossDigits / kBlock;
+    const int t = threadIdx.x;
+    uint32_t c[per], s = 0;
+#pragma unroll
+    for (int k = 0; k < per; ++k) { c[k] = table[kGossDigits - 1 - (t * per + k)]; s += c[k]; }
+    scan[t] = s;
+    if (t == 0) { res[0] = 0; res[1] = 1; }
+    __syncthreads();
+    for (int d = 1; d < kBlock; d <<= 1) {
+        const uint32_t o = t >= d ? scan[t - d] : 0;
+        __syncthreads();
+        scan[t] += o;
+        __syncthreads();
+    }
+    uint32_t run = scan[t] - s;
+    if (run < K && K <= run + s) {                                      // one thread: the sums ahead of it fall short of K, with its own they reach it
+#pragma unroll
+        for (int k = 0; k < per; ++k) {
+            if (run < K && K <= run + c[k]) { res[0] = (uint32_t)(kGossDigits - 1 - (t * per + k)); res[1] = K - run; }
+            run += c[k];
+        }
+    }
+    __syncthreads();
+    digit = res[0];
+    krem = res[1];
+    __syncthreads();
+}
+
+constexpr uint32_t kGossNan = 0x7f800000u;                              // |g h| bit patterns above this one are NaNs
+__device__ __forceinline__ uint32_t goss_bits(float g, float h) { return __float_as_uint(g * h) & 0x7fffffffu; }      // one fp32 product
+
+// Counting pass P of the select: the keys whose digits above pass P's equal the digits chosen so far, counted by pass P's digit.  LDS
+// counters, flushed with one global integer atomic per digit the workgroup touched.  A NaN key counts as 0, the smallest.
+template <int P> __global__ void __launch_bounds__(kBlock)
+gbdt_goss_count_kernel(const float *__restrict__ g, const float *__restrict__ h, int64_t n, uint32_t K, uint32_t *__restrict__ tables,
+                       int32_t *__restrict__ info) {
+    __shared__ uint32_t cnt[kGossDigits];
+    constexpr int shift = P == 0 ? 21 : P == 1 ? 10 : 0;
+    constexpr uint32_t digits = P == 2 ? 1023u : 2047u, above = P == 0 ? 0u : P == 1 ? 0xffe00000u : 0xfffffc00u;
+    for (int e = threadIdx.x; e < kGossDigits; e += kBlock) cnt[e] = 0;
+    if (P == 0 && blockIdx.x == 0 && threadIdx.x < 3) info[threadIdx.x] = 0;
+    uint32_t prefix = 0, k = K, d;
+    if (P >= 1) { goss_pick(tables, k, d, k); prefix = d << 21; }
+    if (P >= 2) { goss_pick(tables + kGossDigits, k, d, k); prefix |= d << 10; }
+    __syncthreads();
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        uint32_t key = goss_bits(g[i], h[i]);
+        if (key > kGossNan) key = 0;
+        if ((key & above) == prefix) atomicAdd(&cnt[(key >> shift) & digits], 1u);
+    }
+    __syncthreads();
+    uint32_t *out = tables + P * kGossDigits;
+    for (int e = threadIdx.x; e < kGossDigits; e += kBlock) {
+        const uint32_t c = cnt[e];
+        if (c) atomicAdd(&out[e], c);
+    }
+}
+
+// tau from the three tables; then per row: top (key >= tau, a NaN never), kept (top, or u(draw, row) < p_other), g and h of a kept row
+// outside the top times w_other.  g_out / h_out may be g / h: a thread reads its row before it writes it.
+__global__ void __launch_bounds__(kBlock)
+gbdt_goss_apply_kernel(const float *g, const float *h, int64_t n, uint32_t K, const uint32_t *__restrict__ tables, uint64_t seed, int64_t draw,
+                       float p_other, float w_other, float *g_out, float *h_out, uint8_t *__restrict__ mask, int32_t *__restrict__ info) {
+    __shared__ uint32_t tot[2];
+    uint32_t k = K, d0, d1, d2;
+    goss_pick(tables, k, d0, k);
+    goss_pick(tables + kGossDigits, k, d1, k);
+    goss_pick(tables + 2 * kGossDigits, k, d2, k);
+    const uint32_t tau = d0 << 21 | d1 << 10 | d2;
+    if (threadIdx.x < 2) tot[threadIdx.x] = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) info[0] = (int32_t)tau;
+    __syncthreads();
+    const PlKeys keys = pl_query_keys(seed, draw);
+    uint32_t ntop = 0, nkeep = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        float a = g[i], b = h[i];
+        const uint32_t key = goss_bits(a, b);
+        const bool top = key <= kGossNan && key >= tau;
+        const bool keep = top || pl_uniform(keys, (uint32_t)i) < p_other;
+        if (keep && !top) { a *= w_other; b *= w_other; }
+        g_out[i] = a;
+        h_out[i] = b;
+        mask[i] = keep ? 1 : 0;
+        ntop += top ? 1 : 0;
+        nkeep += keep ? 1 : 0;
+    }
+    atomicAdd(&tot[0], ntop);
+    atomicAdd(&tot[1], nkeep);
+    __syncthreads();
+    if (threadIdx.x < 2 && tot[threadIdx.x]) atomicAdd(&info[1 + threadIdx.x], (int32_t)tot[threadIdx.x]);
+}
+
+// count, scan, scatter: the three launches of a stable partition under either predicate
+template <class Pred> static int launch_partition(const Pred &pred, int nb, int32_t *out, int32_t *left_count, int32_t *ws, hipStream_t s, const char *who) {
+    hipLaunchKernelGGL(gbdt_part_count_kernel<Pred>, dim3(nb), dim3(kBlock), 0, s, pred, ws);
+    hipLaunchKernelGGL(gbdt_part_scan_kernel, dim3(1), dim3(kBlock), 0, s, ws, nb, left_count);
+    hipLaunchKernelGGL(gbdt_part_scatter_kernel<Pred>, dim3(nb), dim3(kBlock), 0, s, pred, ws, nb, out);
+    return check_hip(hipGetLastError(), who);
+}
+
 static int grid_for(int64_t elems, int cap = 1 << 16) {
     const int64_t b = (elems + kBlock - 1) / kBlock;
     return (int)(b < 1 ? 1 : b > cap ? cap : b);
@@ -676,10 +833,7 @@ extern "C" int ptr_gbdt_partition(const uint8_t *bins, int stride, int64_t n, in
     if (m == 0) return check_hip(hipMemsetAsync(left_count, 0, sizeof(int32_t), as_stream(stream)), who);
     if (!bins || !rows || !out || !ws) { set_error("%s: NULL pointer (bins, rows, out or ws)", who); return PTR_ERR_INVALID_ARG; }
     const int nb = (int)ptr_gbdt_partition_ws_ints(m) - 1;
-    hipLaunchKernelGGL(gbdt_part_count_kernel, dim3(nb), dim3(kBlock), 0, as_stream(stream), bins, stride, (int)n, rows, (int)m, feature, bin, ws);
-    hipLaunchKernelGGL(gbdt_part_scan_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), ws, nb, left_count);
-    hipLaunchKernelGGL(gbdt_part_scatter_kernel, dim3(nb), dim3(kBlock), 0, as_stream(stream), bins, stride, (int)n, rows, (int)m, feature, bin, ws, nb, out);
-    return check_hip(hipGetLastError(), who);
+    return launch_partition(PartByBin{bins, stride, (int)n, rows, (int)m, feature, bin}, nb, out, left_count, ws, as_stream(stream), who);
 }
 
 extern "C" int ptr_gbdt_add_leaf_values(float *scores, int64_t n, const int32_t *rows, const int32_t *offsets, const float *values, int nleaves,
@@ -705,6 +859,81 @@ extern "C" int ptr_gbdt_predict(const float *X, int64_t n, int F, const int32_t 
     if (ntrees > 0 && (!feature || !threshold || !left || !right || !value || !tree_offsets)) { set_error("%s: NULL tree array", who); return PTR_ERR_INVALID_ARG; }
     hipLaunchKernelGGL(gbdt_predict_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), X, n, F, feature, threshold, left,
                        right, value, tree_offsets, ntrees, out);
+    return check_hip(hipGetLastError(), who);
+}
+
+// ---------------------------------------------------------------- the entry points of row sampling
+static int check_rows(int64_t n, const char *who) {
+    if (n < 0 || n > INT32_MAX) { set_error("%s: bad size (n=%lld; n must fit an int32 row index)", who, (long long)n); return PTR_ERR_INVALID_ARG; }
+    return 0;
+}
+
+extern "C" int ptr_gbdt_bag_mask(int64_t n, const int32_t *qid, uint64_t seed, int64_t draw, float fraction, uint8_t *mask, void *stream) {
+    const char *who = "ptr_gbdt_bag_mask";
+    if (int rc = check_rows(n, who)) return rc;
+    if (!(fraction > 0.0f && fraction <= 1.0f)) { set_error("%s: fraction must be in (0, 1], got %g", who, (double)fraction); return PTR_ERR_INVALID_ARG; }
+    if (draw < 0) { set_error("%s: negative draw (%lld)", who, (long long)draw); return PTR_ERR_INVALID_ARG; }
+    if (n == 0) return 0;
+    if (!mask) { set_error("%s: NULL pointer (mask)", who); return PTR_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(gbdt_bag_mask_kernel, dim3(grid_for(n, 4096)), dim3(kBlock), 0, as_stream(stream), n, qid, seed, draw, fraction, mask);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" size_t ptr_gbdt_goss_ws_ints(int64_t n) { (void)n; return (size_t)kGossPasses * kGossDigits + kGossState; }
+
+extern "C" int ptr_gbdt_goss(const float *g, const float *h, int64_t n, double top_rate, double other_rate, uint64_t seed, int64_t draw,
+                             float *g_out, float *h_out, uint8_t *mask, int32_t *info, int32_t *ws, void *stream) {
+    const char *who = "ptr_gbdt_goss";
+    if (int rc = check_rows(n, who)) return rc;
+    if (!(top_rate > 0.0) || !(other_rate > 0.0) || !(top_rate + other_rate <= 1.0)) {
+        set_error("%s: top_rate and other_rate must be > 0 and sum to at most 1 (got %g, %g)", who, top_rate, other_rate);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (draw < 0) { set_error("%s: negative draw (%lld)", who, (long long)draw); return PTR_ERR_INVALID_ARG; }
+    if (n == 0) return 0;
+    if (!g || !h || !g_out || !h_out || !mask || !info || !ws) { set_error("%s: NULL pointer (g, h, g_out, h_out, mask, info or ws)", who); return PTR_ERR_INVALID_ARG; }
+    int64_t K = (int64_t)floor((double)n * top_rate);
+    K = K < 1 ? 1 : K > n ? n : K;
+    const float p_other = (float)(other_rate / (1.0 - top_rate)), w_other = (float)((1.0 - top_rate) / other_rate);
+    const GbdtGossForm form = gbdt_goss_form(n);
+    hipStream_t s = as_stream(stream);
+    uint32_t *tables = reinterpret_cast<uint32_t *>(ws);
+    if (int rc = check_hip(hipMemsetAsync(ws, 0, ptr_gbdt_goss_ws_ints(n) * sizeof(int32_t), s), who)) return rc;
+    hipLaunchKernelGGL(gbdt_goss_count_kernel<0>, dim3(form.groups), dim3(kBlock), 0, s, g, h, n, (uint32_t)K, tables, info);
+    hipLaunchKernelGGL(gbdt_goss_count_kernel<1>, dim3(form.groups), dim3(kBlock), 0, s, g, h, n, (uint32_t)K, tables, info);
+    hipLaunchKernelGGL(gbdt_goss_count_kernel<2>, dim3(form.groups), dim3(kBlock), 0, s, g, h, n, (uint32_t)K, tables, info);
+    hipLaunchKernelGGL(gbdt_goss_apply_kernel, dim3(form.groups), dim3(kBlock), 0, s, g, h, n, (uint32_t)K, tables, seed, draw, p_other, w_other, g_out,
+                       h_out, mask, info);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_partition_mask(const uint8_t *mask, int64_t n, const int32_t *rows, int64_t m, int32_t *out, int32_t *left_count,
+                                       int32_t *ws, void *stream) {
+    const char *who = "ptr_gbdt_partition_mask";
+    if (int rc = check_rows(n, who)) return rc;
+    if (m < 0 || m > INT32_MAX) { set_error("%s: bad row count m=%lld", who, (long long)m); return PTR_ERR_INVALID_ARG; }
+    if (!left_count) { set_error("%s: NULL left_count", who); return PTR_ERR_INVALID_ARG; }
+    if (m == 0) return check_hip(hipMemsetAsync(left_count, 0, sizeof(int32_t), as_stream(stream)), who);
+    if (!out || !ws || (n > 0 && !mask)) { set_error("%s: NULL pointer (mask, out or ws)", who); return PTR_ERR_INVALID_ARG; }
+    if (rows == out) { set_error("%s: out must not be rows (the partition is not done in place)", who); return PTR_ERR_INVALID_ARG; }
+    const int nb = (int)ptr_gbdt_partition_ws_ints(m) - 1;
+    return launch_partition(PartByMask{mask, (int)n, rows, (int)m}, nb, out, left_count, ws, as_stream(stream), who);
+}
+
+extern "C" int ptr_gbdt_add_tree_binned(float *scores, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m,
+                                        const int32_t *feature, const int32_t *bin, const int32_t *left, const int32_t *right, const float *value,
+                                        int nnodes, void *stream) {
+    const char *who = "ptr_gbdt_add_tree_binned";
+    if (int rc = check_bins_layout(n, F, stride, who)) return rc;
+    if (m < 0 || m > INT32_MAX || nnodes < 0) { set_error("%s: bad size (m=%lld, nnodes=%d)", who, (long long)m, nnodes); return PTR_ERR_INVALID_ARG; }
+    if (!rows && m > n) { set_error("%s: rows is NULL (the first m rows), so m must not exceed n (m=%lld, n=%lld)", who, (long long)m, (long long)n); return PTR_ERR_INVALID_ARG; }
+    if (m == 0 || n == 0) return 0;
+    if (!scores || !value || (nnodes > 0 && (!bins || !feature || !bin || !left || !right))) {
+        set_error("%s: NULL pointer (scores, bins, value or a tree array)", who);
+        return PTR_ERR_INVALID_ARG;
+    }
+    hipLaunchKernelGGL(gbdt_add_tree_binned_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), scores, bins, stride,
+                       (int)n, F, rows, (int)m, feature, bin, left, right, value, nnodes);
     return check_hip(hipGetLastError(), who);
 }
 

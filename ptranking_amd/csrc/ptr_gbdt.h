@@ -43,4 +43,19 @@ inline GbdtSegForm gbdt_hist_segments_form(int64_t m, int F, int max_bin, int64_
 
 constexpr int kGbdtPartRows = 1024;      // consecutive entries of a row list that one workgroup of the partition owns
 
+// The exact k-th largest |g h| of GOSS (ptr_gbdt_goss): a radix select over the keys' uint32 bit patterns, most significant digit first.
+constexpr int kGossPasses = 3;           // digits of 11, 11 and 10 bits (shifts 21, 10, 0)
+constexpr int kGossDigits = 2048;        // counters per pass: 8 KiB of LDS per workgroup, one global table per pass
+constexpr int kGossRowsPerGroup = 4096;  // least rows per workgroup of a counting pass
+constexpr int kGossMaxGroups = 2048;     // workgroups of one counting pass at the most (256 compute units x 8)
+constexpr int kGossState = 4;            // int32 after the three tables: reserved for the select
+
+// passes, digits per pass, workgroups of one counting pass (and of the apply pass), launches of one call (a memset, 3 counts, the apply)
+struct GbdtGossForm { int passes; int digits; int groups; int launches; };
+inline GbdtGossForm gbdt_goss_form(int64_t n) {
+    if (n <= 0) return {kGossPasses, kGossDigits, 0, 0};
+    const int64_t want = (n + kGossRowsPerGroup - 1) / kGossRowsPerGroup;
+    return {kGossPasses, kGossDigits, (int)(want < kGossMaxGroups ? want : kGossMaxGroups), 2 + kGossPasses};
+}
+
 }  // namespace ptr

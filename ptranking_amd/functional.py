@@ -23,6 +23,7 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "adlist_uniforms", "adlist_sample", "ADLIST_MODES", "ADLIST_PROBS", "ADLIST_FAMILIES", "ADLIST_REWARDS", "shuffle_ties_order", "sort_desc", "metrics_at_ks", "sum_f32", "LAMBDALOSS_TYPES",
            "gbdt_bin", "gbdt_quantize", "gbdt_histogram", "gbdt_hist_sub", "gbdt_best_split", "gbdt_partition", "gbdt_add_leaf_values", "gbdt_predict",
            "gbdt_histogram_segments", "gbdt_hist_sub_segments", "gbdt_best_split_slots", "gbdt_partition_segments", "gbdt_segment_items",
+           "gbdt_bag_mask", "gbdt_goss", "gbdt_partition_mask", "gbdt_add_tree_binned",
            "GBDT_MAX_BIN", "GBDT_RECORD"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
@@ -1240,3 +1241,100 @@ def gbdt_partition_segments(bins, rows, segs, F, out=None, left_counts=None):
         _lib.call("ptr_gbdt_partition_segments", _lib.ptr(bins), bins.shape[1], bins.shape[0], F, _lib.ptr(rows), rows.numel(), _lib.ptr(segs_d), K,
                   _lib.ptr(blocks_d), int(seg.size), _lib.ptr(out), _lib.ptr(left_counts), _lib.ptr(ws), ws_ints, _lib.current_stream(dev))
     return out, left_counts
+
+
+# ---- row sampling for the tree trainer (bagging by row or by query, GOSS): include/ptranking_amd.h states the rules.
+def gbdt_bag_mask(n, seed, draw, fraction, qid=None, out=None, device=None):
+    """The bag of one draw -> uint8 [n], 1 = in the bag: unit r (the row, or qid[r] with qid int32 [n]: whole queries) is kept iff the
+    counter stream's u(draw, unit) < float32(fraction).  A Bernoulli draw per unit; fraction in (0, 1]."""
+    n = int(n)
+    if qid is not None:
+        qid = _check("qid", qid, torch.int32, (n,))
+        device = qid.device
+    if out is not None:
+        out = _check("out", out, torch.uint8, (n,))
+        device = out.device
+    if device is None or torch.device(device).type != "cuda":
+        raise RuntimeError(f"gbdt_bag_mask on {device}: ptranking_amd runs on the MI355X HIP path only (no CPU fallback)")
+    if not 0.0 < float(fraction) <= 1.0:
+        raise ValueError(f"fraction must be in (0, 1], got {fraction}")
+    if int(draw) < 0:
+        raise ValueError(f"draw must be >= 0, got {draw}")
+    device = torch.device(device)
+    out = torch.empty(n, device=device, dtype=torch.uint8) if out is None else out
+    with torch.cuda.device(device):
+        _lib.call("ptr_gbdt_bag_mask", n, _lib.ptr(qid), _seed64(seed), int(draw), C.c_float(float(fraction)), _lib.ptr(out), _lib.current_stream(device))
+    return out
+
+
+def gbdt_goss(grad, hess, top_rate, other_rate, seed, draw, out=None, mask=None, info=None):
+    """Gradient-based one-side sampling of one round -> (g', h', mask uint8 [n], info int32 [3] = (the bit pattern of tau, the size of the
+    top set, the number kept)).  tau is the exact K-th largest |g h| (K = max(1, floor(n top_rate))); the rows at or above it are kept as
+    they are, any other row with probability other_rate / (1 - top_rate), its g and h times (1 - top_rate) / other_rate.  out = (g', h')
+    to write into; they may be grad and hess themselves."""
+    grad = _check("grad", grad)
+    if grad.dim() != 1:
+        raise ValueError(f"grad must be flat [rows], got {tuple(grad.shape)}")
+    hess = _check("hess", hess, shape=grad.shape)
+    top_rate, other_rate = float(top_rate), float(other_rate)
+    if not (top_rate > 0.0 and other_rate > 0.0 and top_rate + other_rate <= 1.0):
+        raise ValueError(f"top_rate and other_rate must be > 0 and sum to at most 1, got {top_rate}, {other_rate}")
+    if int(draw) < 0:
+        raise ValueError(f"draw must be >= 0, got {draw}")
+    dev, n = grad.device, grad.numel()
+    out = (torch.empty_like(grad), torch.empty_like(hess)) if out is None else out
+    g_out, h_out = (_check(k, t, torch.float32, (n,)) for k, t in zip(("g_out", "h_out"), out))
+    mask = torch.empty(n, device=dev, dtype=torch.uint8) if mask is None else _check("mask", mask, torch.uint8, (n,))
+    info = torch.zeros(3, device=dev, dtype=torch.int32) if info is None else _check("info", info, torch.int32, (3,))
+    ws = torch.empty(int(_lib.query("ptr_gbdt_goss_ws_ints", n)), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_goss", _lib.ptr(grad), _lib.ptr(hess), n, C.c_double(top_rate), C.c_double(other_rate), _seed64(seed), int(draw),
+                  _lib.ptr(g_out), _lib.ptr(h_out), _lib.ptr(mask), _lib.ptr(info), _lib.ptr(ws), _lib.current_stream(dev))
+    return g_out, h_out, mask, info
+
+
+def gbdt_partition_mask(mask, rows=None, m=None, out=None, left_count=None):
+    """Stable partition of a row list by mask[row] != 0 -> (out int32 [m]: the kept rows in their order, then the others in theirs;
+    left_count int32 [1] on the device).  rows=None is the list 0 .. m - 1 (m: all rows of the mask by default).  A row index outside the
+    mask is not kept."""
+    mask = _check("mask", mask, torch.uint8)
+    if mask.dim() != 1:
+        raise ValueError(f"mask must be flat [rows], got {tuple(mask.shape)}")
+    dev, n = mask.device, mask.numel()
+    if rows is not None:
+        rows = _check("rows", rows, torch.int32)
+        if rows.dim() != 1 or (m is not None and int(m) != rows.numel()):
+            raise ValueError(f"rows must be flat and hold m entries, got {tuple(rows.shape)}")
+        m = rows.numel()
+    m = n if m is None else int(m)
+    if m < 0:
+        raise ValueError(f"m={m} is negative")
+    out = torch.empty(m, device=dev, dtype=torch.int32) if out is None else _check("out", out, torch.int32, (m,))
+    left_count = torch.empty(1, device=dev, dtype=torch.int32) if left_count is None else _check("left_count", left_count, torch.int32, (1,))
+    ws = torch.empty(int(_lib.query("ptr_gbdt_partition_ws_ints", m)), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_partition_mask", _lib.ptr(mask), n, _lib.ptr(rows), m, _lib.ptr(out), _lib.ptr(left_count), _lib.ptr(ws),
+                  _lib.current_stream(dev))
+    return out, left_count
+
+
+def gbdt_add_tree_binned(scores, bins, F, rows, feature, bin, left, right, value):
+    """scores[row] += the leaf value one tree gives the BINNED row, for every row of `rows` (int32, distinct; None: all rows), in place.
+    The tree as gbdt_predict takes one, with the split bins (int32 [nodes]) in place of the thresholds: left on bins[row, feature] <= bin,
+    which is x <= edges[feature, bin], so the value is gbdt_predict's for the raw row.  value float32 [nodes + 1]."""
+    scores = _check("scores", scores)
+    bins = _gbdt_bins(bins, F)
+    n, dev = bins.shape[0], bins.device
+    if scores.dim() != 1 or scores.numel() != n or not scores.is_contiguous():
+        raise ValueError(f"scores must be flat and contiguous [{n}], got {tuple(scores.shape)}")
+    if rows is not None:
+        rows = _check("rows", rows, torch.int32)
+        if rows.dim() != 1:
+            raise ValueError(f"rows must be flat, got {tuple(rows.shape)}")
+    nodes = feature.numel()
+    feature, bin, left, right = (_check(k, t, torch.int32, (nodes,)) for k, t in zip(("feature", "bin", "left", "right"), (feature, bin, left, right)))
+    value = _check("value", value, shape=(nodes + 1,))
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_add_tree_binned", _lib.ptr(scores), _lib.ptr(bins), bins.shape[1], n, F, _lib.ptr(rows), n if rows is None else rows.numel(),
+                  _lib.ptr(feature), _lib.ptr(bin), _lib.ptr(left), _lib.ptr(right), _lib.ptr(value), nodes, _lib.current_stream(dev))
+    return scores

@@ -19,9 +19,20 @@ subtraction, split scan over many leaves at once) and reads once per level; unde
 the cap cannot bind (num_leaves >= 2^max_depth) the two give the same trees, fp32 leaf values and scores bit for bit; depth-wise whole fits
 are pinned to scikit-learn with max_leaf_nodes=None as well (tests/golden/gbdt_sklearn_depth.npz).  GBDT.host_reads counts the reads.
 
-Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here: GOSS, EFB,
-categorical features, missing values (a non-finite feature raises: in bin_edges, in predict and for the eval_set of LambdaMART.fit), DART,
-monotone constraints.  There is no CPU path.
+Row sampling (LightGBM's names; the rules are this project's own, stated in include/ptranking_amd.h and restated in
+tests/gbdt_sample_ref.py; no parity with LightGBM's random streams is claimed).  bagging_fraction < 1 with bagging_freq = k > 0 grows tree
+t on a Bernoulli bag of the rows (of whole queries under bagging_by_query, which needs fit_bins(X, group)), redrawn before the trees
+0, k, 2k, ... from the counter stream seeded by bagging_seed.  data_sample_strategy='goss' keeps, after the first floor(1 / learning_rate)
+trees, the rows at or above the exact K-th largest |g h| (K = floor(n top_rate)) and any other row with probability
+other_rate / (1 - top_rate), its gradient and Hessian times (1 - top_rate) / other_rate; it cannot be combined with bagging.  The mask, the
+select, the stable partition that puts the bag at the front of the row list and the walk that gives the rows outside the bag their leaf
+value all run on the device; the size of the bag reaches the host in the one read update() makes anyway (it is the root's row count), so
+host_reads does not grow, and booster.scores stays predict(X) bit for bit for every row.  Without sampling update() issues exactly the
+calls it issued before these parameters existed.
+
+Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here:
+feature_fraction, EFB, categorical features, missing values (a non-finite feature raises: in bin_edges, in predict and for the eval_set of
+LambdaMART.fit), DART, monotone constraints.  There is no CPU path.
 """
 import json
 
@@ -36,10 +47,13 @@ __all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS"
 # LightGBM's names, so the reference's lightgbm_para_dict passes through.  min_sum_hessian_in_leaf = 1e-3 is LightGBM's default too; the
 # reference's own dict sets 200, which suits LightGBM's built-in lambdarank Hessians, not the sums of tree.hip.
 DEFAULT_PARAMS = {"learning_rate": 0.1, "num_leaves": 31, "num_trees": 100, "min_data_in_leaf": 20, "min_sum_hessian_in_leaf": 1e-3,
-                  "lambda_l2": 0.0, "min_gain_to_split": 0.0, "max_bin": 255, "max_depth": -1, "grow_policy": "leafwise"}
+                  "lambda_l2": 0.0, "min_gain_to_split": 0.0, "max_bin": 255, "max_depth": -1, "grow_policy": "leafwise",
+                  "bagging_fraction": 1.0, "bagging_freq": 0, "bagging_seed": 3, "bagging_by_query": False, "data_sample_strategy": "bagging",
+                  "top_rate": 0.2, "other_rate": 0.1}
 IGNORED_PARAMS = ("num_threads", "verbosity", "metric", "boosting_type", "objective", "eval_at")    # accepted, without a meaning here
 MODEL_FORMAT = 1
 GROW_POLICIES = ("leafwise", "depthwise")
+SAMPLE_STRATEGIES = ("bagging", "goss")
 
 
 def _params(params):
@@ -67,7 +81,35 @@ def _params(params):
         raise ValueError(f"max_bin must be in 2 .. {F.GBDT_MAX_BIN}, got {p['max_bin']}")
     if not p["lambda_l2"] >= 0.0 or p["min_sum_hessian_in_leaf"] != p["min_sum_hessian_in_leaf"] or p["min_gain_to_split"] != p["min_gain_to_split"]:
         raise ValueError("lambda_l2 must be >= 0 and no threshold may be NaN")
+    for k in ("bagging_fraction", "top_rate", "other_rate"):
+        p[k] = float(p[k])
+    if isinstance(p["bagging_by_query"], (bool, np.bool_)):
+        p["bagging_by_query"] = bool(p["bagging_by_query"])
+    else:
+        raise ValueError(f"bagging_by_query must be True or False, got {p['bagging_by_query']!r}")
+    if int(p["bagging_freq"]) != p["bagging_freq"] or int(p["bagging_seed"]) != p["bagging_seed"]:
+        raise ValueError("bagging_freq and bagging_seed must be integers")
+    p["bagging_freq"], p["bagging_seed"] = int(p["bagging_freq"]), int(p["bagging_seed"])
+    if not 0.0 < p["bagging_fraction"] <= 1.0:
+        raise ValueError(f"bagging_fraction must be in (0, 1], got {p['bagging_fraction']}")
+    if p["bagging_freq"] < 0 or p["bagging_seed"] < 0:
+        raise ValueError("bagging_freq and bagging_seed must be >= 0")
+    if p["data_sample_strategy"] not in SAMPLE_STRATEGIES:
+        raise ValueError(f"data_sample_strategy {p['data_sample_strategy']!r} is not implemented: only 'bagging' and 'goss'")
+    if not (p["top_rate"] > 0.0 and p["other_rate"] > 0.0 and p["top_rate"] + p["other_rate"] <= 1.0):
+        raise ValueError(f"top_rate and other_rate must be > 0 and sum to at most 1, got {p['top_rate']}, {p['other_rate']}")
+    if p["data_sample_strategy"] == "goss" and _bagging(p):
+        raise ValueError("data_sample_strategy 'goss' cannot be combined with bagging (bagging_freq > 0 and bagging_fraction < 1)")
     return p
+
+
+def _bagging(p):
+    return p["bagging_freq"] > 0 and p["bagging_fraction"] < 1.0
+
+
+def sampling(p):
+    """None, 'bagging' or 'goss': the row sampling the parameters switch on.  bagging_freq > 0 with bagging_fraction 1.0 switches nothing on."""
+    return "goss" if p["data_sample_strategy"] == "goss" else "bagging" if _bagging(p) else None
 
 
 _NONFINITE = "X holds a NaN or an infinity: missing values are not handled, impute them first"
@@ -152,6 +194,7 @@ class GBDT:
         self._flat = None
         self.n = 0
         self.host_reads = 0                # device-to-host reads inside update(), over the booster's life: what a growth policy costs
+        self._qid = None
         if X is not None:
             self.fit_bins(X)
 
@@ -161,10 +204,16 @@ class GBDT:
             raise RuntimeError("GBDT needs a GPU: ptranking_amd runs on the MI355X HIP path only (no CPU fallback)")
         return torch.device("cuda" if self._device is None else self._device)
 
-    def fit_bins(self, X):
+    def fit_bins(self, X, group=None):
         """Computes the bin edges of X (numpy array or device tensor [n, F]) on the host, bins X on the device and keeps the bins, the
-        training scores (zeros) and the work buffers resident."""
+        training scores (zeros) and the work buffers resident.  group: the documents per query, which bagging_by_query samples by."""
         dev = self._dev()
+        if group is not None:
+            group = np.asarray(group).reshape(-1).astype(np.int64)
+            if (group < 0).any() or int(group.sum()) != len(X):
+                raise ValueError(f"group must hold non-negative counts that sum to the {len(X)} rows of X")
+        elif self._by_query():
+            raise ValueError("bagging_by_query needs the queries: fit_bins(X, group=...)")
         host = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
         host = np.ascontiguousarray(host, dtype=np.float32)
         p = self.params
@@ -184,7 +233,35 @@ class GBDT:
         self._rec = torch.zeros((2, 9), device=dev, dtype=torch.int64)
         self._lrec = torch.zeros((max(p["num_leaves"], 2), 9), device=dev, dtype=torch.int64)      # a depth-wise level's records
         self._pool = torch.zeros((max(p["num_leaves"], 1), self.F, p["max_bin"], 3), device=dev, dtype=torch.int64)
+        self._qid = None if group is None else torch.from_numpy(np.repeat(np.arange(group.size, dtype=np.int32), group)).to(dev)
+        if sampling(p):
+            self._mask = torch.empty(n, device=dev, dtype=torch.uint8)
+            self._none = torch.full((1,), -1, device=dev, dtype=torch.int32)
+            self._bag_draw = None                                      # the draw self._mask holds (bagging_freq > 1 reuses it)
+            if sampling(p) == "goss":
+                self._gg, self._gh = torch.empty_like(self.scores), torch.empty_like(self.scores)
+                self._info = torch.zeros(3, device=dev, dtype=torch.int32)
         return self
+
+    def _by_query(self):
+        return sampling(self.params) == "bagging" and self.params["bagging_by_query"]
+
+    def _sample(self, grad, hess):
+        """The keep mask of the tree about to be grown, in self._mask -> (grad, hess) to quantize, or None for a tree on every row (GOSS's
+        warm-up).  Bagging: tree t uses draw t // bagging_freq and keeps the mask between draws.  GOSS: draw t, its own weighted copies."""
+        p, t = self.params, len(self.trees)
+        if sampling(p) == "goss":
+            if t < int(np.floor(1.0 / p["learning_rate"])):
+                return None
+            F.gbdt_goss(grad, hess, p["top_rate"], p["other_rate"], p["bagging_seed"], t, out=(self._gg, self._gh), mask=self._mask, info=self._info)
+            return self._gg, self._gh
+        if p["bagging_by_query"] and self._qid is None:
+            raise ValueError("bagging_by_query needs the queries: fit_bins(X, group=...)")
+        draw = t // p["bagging_freq"]
+        if draw != self._bag_draw:
+            F.gbdt_bag_mask(self.n, p["bagging_seed"], draw, p["bagging_fraction"], qid=self._qid if p["bagging_by_query"] else None, out=self._mask)
+            self._bag_draw = draw
+        return grad, hess
 
     # ---- one boosting round
     def _search(self, slot, out_row):
@@ -203,10 +280,20 @@ class GBDT:
         if self.n == 0 or self.edges is None:
             raise RuntimeError("call fit_bins(X) first")
         p, nf, mb = self.params, self.F, self.params["max_bin"]
+        sampled = self._sample(grad, hess) if sampling(p) else None
+        if sampled is not None:
+            grad, hess = sampled
         F.gbdt_quantize(grad, hess, flag=self._flag, out=(self._qg, self._qh, self._expo))
         pool = self._pool
         pool[0].zero_()
-        F.gbdt_histogram(self.bins, self._qg, self._qh, None, nf, mb, hist=pool[0])
+        if sampled is None:
+            F.gbdt_histogram(self.bins, self._qg, self._qh, None, nf, mb, hist=pool[0])
+        else:
+            # the bag first, in order, then the rest: the tree grows on [0, m).  m is known on the device alone until the head read below (it
+            # is the root's count), so the root's histogram runs over all n entries of a list whose out-of-bag entries are -1, which it skips
+            F.gbdt_partition_mask(self._mask, out=self._rows, left_count=self._lc)
+            torch.where(self._mask != 0, self._arange, self._none, out=self._tmp)
+            F.gbdt_histogram(self.bins, self._qg, self._qh, self._tmp, nf, mb, hist=pool[0])
         self._search(0, 0)
         head = torch.cat([self._rec[0], pool[0, 0].sum(0), self._expo.to(torch.int64), self._flag.to(torch.int64)]).cpu().numpy()
         self.host_reads += 1
@@ -214,14 +301,16 @@ class GBDT:
             self._flag.zero_()
             raise FloatingPointError("the gradients or Hessians of this round hold a NaN or an infinity")
         expo = (int(head[12]), int(head[13]))
+        bag = self.n if sampled is None else int(head[11])             # the root's row count: the size of the bag
         if p["grow_policy"] == "depthwise":
-            feature, threshold, left, right, starts, g_sum, h_sum = self._grow_depthwise(head)
+            feature, threshold, left, right, starts, g_sum, h_sum, split_bin = self._grow_depthwise(head, bag, sampled is not None)
             value = np.array([leaf_value(g, h, expo, p["lambda_l2"], p["learning_rate"]) for g, h in zip(g_sum, h_sum)], np.float32)
-            return self._finish(feature, threshold, left, right, starts, value)
-        root_rec = _record(head[:9]) if self._splittable(self.n, 0) else _NO_SPLIT
-        leaves = [_Leaf(0, self.n, 0, 0, -1, 0, int(head[9]), int(head[10]), root_rec)]
-        feature, threshold, left, right = [], [], [], []
-        self._rows.copy_(self._arange)
+            return self._finish(feature, threshold, left, right, starts, value, bag, split_bin)
+        root_rec = _record(head[:9]) if self._splittable(bag, 0) else _NO_SPLIT
+        leaves = [_Leaf(0, bag, 0, 0, -1, 0, int(head[9]), int(head[10]), root_rec)]
+        feature, threshold, left, right, split_bin = [], [], [], [], []
+        if sampled is None:
+            self._rows.copy_(self._arange)
         free = 1                                                       # the next unused histogram slot
         while len(leaves) < p["num_leaves"]:
             li = max(range(len(leaves)), key=lambda i: (leaves[i].rec[0], -i))
@@ -233,7 +322,7 @@ class GBDT:
             F.gbdt_partition(self.bins, self._rows[s:s + m], f, b, nf, out=self._tmp[s:s + m], left_count=self._lc)
             self._rows[s:s + m].copy_(self._tmp[s:s + m])
             node = len(feature)
-            feature.append(f); threshold.append(self.edges[f, b]); left.append(~li); right.append(~len(leaves))
+            feature.append(f); threshold.append(self.edges[f, b]); left.append(~li); right.append(~len(leaves)); split_bin.append(b)
             if leaf.parent >= 0:
                 (left if leaf.side == 0 else right)[leaf.parent] = node
             lchild = _Leaf(s, lsum[2], leaf.depth + 1, leaf.slot, node, 0, lsum[0], lsum[1], _NO_SPLIT)
@@ -256,36 +345,45 @@ class GBDT:
                     if can[k]:
                         c.rec = _record(recs[k])
         value = np.array([leaf_value(c.g, c.h, expo, p["lambda_l2"], p["learning_rate"]) for c in leaves], np.float32)
-        return self._finish(feature, threshold, left, right, [c.start for c in leaves], value)
+        return self._finish(feature, threshold, left, right, [c.start for c in leaves], value, bag, split_bin)
 
-    def _finish(self, feature, threshold, left, right, starts, value):
-        """Adds the leaf values (by leaf index, with the leaves' first positions in the row list) to the training scores; keeps the tree."""
+    def _finish(self, feature, threshold, left, right, starts, value, m, split_bin):
+        """Adds the leaf values (by leaf index, with the leaves' first positions in the row list) to the training scores; keeps the tree.
+        The tree grew on the first m entries of the row list: the rows behind them (outside a sampled tree's bag) are walked through the
+        tree on their bins and get the same fp32 leaf value, so the scores stay predict(X) bit for bit.  split_bin, the split bins by node,
+        serves that one call and is not part of the model."""
         order = sorted(range(len(starts)), key=lambda i: starts[i])
-        offsets = np.array([starts[i] for i in order] + [self.n], np.int32)
+        offsets = np.array([starts[i] for i in order] + [m], np.int32)
         dev = self.scores.device
         F.gbdt_add_leaf_values(self.scores, self._rows, torch.from_numpy(offsets).to(dev), torch.from_numpy(value[order]).to(dev))
         t = {"feature": np.array(feature, np.int32), "threshold": np.array(threshold, np.float32), "left": np.array(left, np.int32),
              "right": np.array(right, np.int32), "value": value}
+        if m < self.n:
+            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+            F.gbdt_add_tree_binned(self.scores, self.bins, self.F, self._rows[m:], up(t["feature"], np.int32), up(split_bin, np.int32), up(t["left"], np.int32),
+                                   up(t["right"], np.int32), up(value, np.float32))
         self.trees.append(t)
         self._flat = None
         return t
 
-    def _grow_depthwise(self, head):
+    def _grow_depthwise(self, head, m, sampled):
         """Depth-wise growth from the root's record (head, as update read it): every level is one batched pass over all its leaves
         (partition, histograms of the smaller children, sibling subtraction, split scan) and ONE host read, the records of the level's
-        searched children.  -> (feature, threshold, left, right, the leaves' first positions, their sums qg and qh), by node / leaf index."""
+        searched children.  The root is the first m entries of the row list (a sampled tree's bag, which update has put there: `sampled`).
+        -> (feature, threshold, left, right, the leaves' first positions, their sums qg and qh, the split bins), by node / leaf index."""
         p, nf, mb, cap = self.params, self.F, self.params["max_bin"], self.params["num_leaves"]
         pool = self._pool
         min_count, max_depth = 2 * max(p["min_data_in_leaf"], 1), p["max_depth"]
         splittable = lambda count, depth: (count >= min_count) & (max_depth <= 0 or depth < max_depth)      # _splittable over a level
         feature, threshold = np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.float32)
-        left, right = np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.int32)
+        left, right, split_bin = np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.int32)
         starts, g_sum, h_sum = np.zeros(cap, np.int64), np.zeros(cap, np.int64), np.zeros(cap, np.int64)
         g_sum[0], h_sum[0] = head[9], head[10]
         nodes, leaves, free, depth = 0, 1, 1, 0
-        self._rows.copy_(self._arange)
+        if not sampled:
+            self._rows.copy_(self._arange)
         # the frontier, in ascending start: leaf index, start, count, histogram slot, parent node, side, split record (gain -inf: none)
-        leaf, start, count, slot = np.zeros(1, np.int64), np.zeros(1, np.int64), np.full(1, self.n, np.int64), np.zeros(1, np.int64)
+        leaf, start, count, slot = np.zeros(1, np.int64), np.zeros(1, np.int64), np.full(1, m, np.int64), np.zeros(1, np.int64)
         parent, side = np.full(1, -1, np.int64), np.zeros(1, np.int64)
         rec = np.asarray(head[:9], np.int64).reshape(1, 9).copy()
         while True:
@@ -299,7 +397,7 @@ class GBDT:
             k = keep.size
             f, b, lsum, rsum = rec[keep, 1], rec[keep, 2], rec[keep, 3:6], rec[keep, 6:9]
             node = nodes + np.arange(k)
-            feature[node], threshold[node] = f, self.edges[f, b]
+            feature[node], threshold[node], split_bin[node] = f, self.edges[f, b], b
             left[node], right[node] = ~leaf[keep], ~(leaves + np.arange(k))
             has = parent[keep] >= 0
             for arr, sd in ((left, 0), (right, 1)):
@@ -335,7 +433,7 @@ class GBDT:
                 self.host_reads += 1
             leaf, start, count, slot = c_leaf.reshape(-1), c_start.reshape(-1), c_count.reshape(-1), c_slot.reshape(-1)
             parent, side, rec = np.repeat(node, 2), np.tile(np.array([0, 1], np.int64), k), c_rec.reshape(-1, 9)
-        return feature[:nodes], threshold[:nodes], left[:nodes], right[:nodes], starts[:leaves].tolist(), g_sum[:leaves].tolist(), h_sum[:leaves].tolist()
+        return feature[:nodes], threshold[:nodes], left[:nodes], right[:nodes], starts[:leaves].tolist(), g_sum[:leaves].tolist(), h_sum[:leaves].tolist(), split_bin[:nodes]
 
     # ---- the model
     def flat(self):
@@ -461,7 +559,7 @@ class LambdaMART:
         X = X if isinstance(X, torch.Tensor) else np.asarray(X)
         if X.shape[0] != res.n_docs:
             raise ValueError(f"X holds {X.shape[0]} rows, the groups {res.n_docs}")
-        self.booster = GBDT(self.params, X, device=self.device)
+        self.booster = GBDT(self.params, device=self.device).fit_bins(X, group=np.asarray(group).reshape(-1))
         self.evals_result, self.best_iteration, self.best_score = [], None, None
         rounds = self.params["num_trees"] if num_boost_round is None else int(num_boost_round)
         valid = None
