@@ -966,7 +966,8 @@ int ptr_launch_form(const char *entry, const int64_t *args, int nargs, int32_t *
 /* ---- A histogram gradient-boosted tree trainer (csrc/gbdt.hip).  The symbols below are ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
  * The reference's tree frame (ptranking/ltr_tree/lambdamart/lightgbm_lambdaMART.py) hands the boosting to LightGBM; ptranking_amd/gbdt.py
  * grows the trees leaf-wise on these entry points instead.  No parity with LightGBM is claimed: the binning and tie rules are this
- * project's own (the row-sampling rules of the section after next among them), and there is no EFB, categorical or missing-value handling.
+ * project's own (the row-sampling rules of the section after next among them), and there is no EFB or categorical handling.  Missing
+ * values have entry points of their own, in the last section on the trainer; the ones here take finite features.
  *
  * Common rules: every argument is validated before any launch (PTR_ERR_INVALID_ARG: a NULL pointer that a launch would touch, a negative
  * size, max_bin < 2, a stride that is no multiple of 16 or below F; PTR_ERR_UNSUPPORTED: max_bin > PTR_GBDT_MAX_BIN); an empty input
@@ -1096,6 +1097,55 @@ int ptr_gbdt_partition_mask(const uint8_t *mask, int64_t n, const int32_t *rows,
 int ptr_gbdt_add_tree_binned(float *scores, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m,
                              const int32_t *feature, const int32_t *bin, const int32_t *left, const int32_t *right, const float *value,
                              int nnodes, void *stream);
+
+/* ---- Missing feature values with learned directions (csrc/gbdt.hip; use_missing=True of ptranking_amd/gbdt.py).  ADDITIVE to ABI v8 too;
+ * every symbol above keeps its signature and its results bit for bit (each pair shares one kernel or one template, the older entry point
+ * passing "no missing").  A NaN is a missing value; an infinity stays the caller's error.  The rules are scikit-learn's
+ * (HistGradientBoostingRegressor) wherever its are deterministic; tests/gbdt_missing_ref.py restates them in numpy.  Out of scope:
+ * zero_as_missing, and the LETOR loader's absent features, which stay zeros.  Argument rules as above: everything is validated before any
+ * launch, and the int32 tables in device memory (nan_bin, the segment table, also_left by node) are read as untrusted in the kernels.
+ *
+ * Bins.  nan_bin [F] int32 in device memory: the bin of feature f's NaNs, behind its value bins (nbins[f] <= nan_bin[f] < max_bin; the
+ *   trainer uses nan_bin[f] = nbins[f]), or -1 for a feature whose training rows hold no NaN.  nbins keeps counting value bins only, and
+ *   the histogram layout [F][max_bin][3] is unchanged: the histogram entry points serve both.  An entry outside that range reads as -1 in
+ *   every kernel (a device table cannot be checked before the launch); a scalar also_left outside -1 .. 255 is PTR_ERR_INVALID_ARG.
+ * ptr_gbdt_bin_missing: ptr_gbdt_bin, and a NaN of feature f gets the bin nan_bin[f] (bin 0 where that is -1, as ptr_gbdt_bin gives).
+ * ptr_gbdt_best_split_missing, ptr_gbdt_best_split_slots_missing: the scan of ptr_gbdt_best_split / _slots with (MG, MH, MC) = the
+ *   histogram entry of the NaN bin (zero without one); the node's totals include it.  Candidates per feature: (1) b < nbins - 1, bins <= b
+ *   left and the missing rows right; (2) only when MC > 0, b = nbins - 1: every value left, the NaNs right (its threshold is the +inf
+ *   padding of the edges); (3) only when MC > 0, b < nbins - 1 with the missing rows LEFT, the left sums being the prefix plus (MG, MH,
+ *   MC).  The validity rules and the uncontracted float64 gain are ptr_gbdt_best_split's; one prefix pass serves both directions.  Ties:
+ *   the highest gain, then the lowest feature, then missing-right before missing-left, then the lowest bin among missing-right candidates
+ *   and the HIGHEST bin among missing-left ones (scikit-learn scans those from the top bin down and keeps the first of equal gains; bins
+ *   that are empty in a node make such ties bit-exact and common).  The record stays 9 int64; field 2 is bin + 256 * default_left, and the
+ *   sums are the true left and right sums with the missing rows on their side.  default_left is the winning candidate's direction when
+ *   MC > 0; otherwise the node's rows do not decide it and default_left = (left count > right count).
+ * ptr_gbdt_partition_missing: ptr_gbdt_partition, and the bin also_left goes left as well (-1: none): a row goes left iff
+ *   bins[row][feature] <= bin or bins[row][feature] == also_left.  The trainer passes nan_bin[feature] where default_left is set.
+ * ptr_gbdt_partition_segments_missing: ptr_gbdt_partition_segments over segs [K][5] = (start, count, feature, bin, also_left); a segment
+ *   whose also_left lies outside -1 .. 255 is left as it was.
+ * ptr_gbdt_add_tree_binned_missing: ptr_gbdt_add_tree_binned with also_left [nnodes]: at a node the bin also_left[node] goes left too.
+ * ptr_gbdt_predict_missing: ptr_gbdt_predict with default_left [nodes of all trees] uint8: at a node a NaN feature goes left where the
+ *   byte is set and right otherwise; any other value goes left on x <= threshold.  A malformed tree yields NaN, never a read out of range. */
+int ptr_gbdt_bin_missing(const float *X, int64_t n, int F, const float *edges, const int32_t *nbins, const int32_t *nan_bin, int max_bin,
+                         int stride, uint8_t *bins, void *stream);
+int ptr_gbdt_best_split_missing(const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *nan_bin,
+                                const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf, double min_sum_hessian_in_leaf,
+                                double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream);
+int ptr_gbdt_best_split_slots_missing(const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin, const int32_t *nbins,
+                                      const int32_t *nan_bin, const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf,
+                                      double min_sum_hessian_in_leaf, double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream);
+int ptr_gbdt_partition_missing(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m, int feature, int bin,
+                               int also_left, int32_t *out, int32_t *left_count, int32_t *ws, void *stream);
+int ptr_gbdt_partition_segments_missing(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t nrows,
+                                        const int32_t *segs, int K, const int32_t *blocks, int nblocks, int32_t *out, int32_t *left_counts,
+                                        int32_t *ws, int64_t ws_ints, void *stream);
+int ptr_gbdt_add_tree_binned_missing(float *scores, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m,
+                                     const int32_t *feature, const int32_t *bin, const int32_t *left, const int32_t *right,
+                                     const float *value, const int32_t *also_left, int nnodes, void *stream);
+int ptr_gbdt_predict_missing(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                             const int32_t *right, const float *value, const int32_t *tree_offsets, const uint8_t *default_left, int ntrees,
+                             float *out, void *stream);
 
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):

@@ -26,6 +26,11 @@
 // non-negative floats, their uint32 bit patterns order as integers, and a radix select of three counting passes (digits of 11, 11 and 10
 // bits; LDS counters flushed with one integer atomic per touched digit) finds it without sorting and without a float atomic.  Each pass
 // starts by reading the finished table of the pass before, in every workgroup alike, so no launch exists only to pick a digit.
+//
+// Missing values (the *_missing entry points; use_missing=True of gbdt.py): a feature's NaNs sit in one more bin behind its value bins, so
+// the histogram layout and the histogram kernels are the same.  The split scan is a template on "missing" (one prefix pass, the second
+// direction behind a wave-uniform test), both stable partitions and the binned walk take one more bin that goes left (also_left, -1: none)
+// and the raw predictor a default_left byte per node; each older entry point passes "no missing" and computes what it computed.
 #include <math.h>
 
 #include "ptr_gbdt.h"
@@ -38,8 +43,8 @@ constexpr int kRec = 9;                  // int64 values of a split record
 
 // ---------------------------------------------------------------- binning
 __global__ void __launch_bounds__(kBlock)
-gbdt_bin_kernel(const float *__restrict__ X, int64_t n, int F, const float *__restrict__ edges, const int32_t *__restrict__ nbins, int max_bin,
-                int stride, uint8_t *__restrict__ bins) {
+gbdt_bin_kernel(const float *__restrict__ X, int64_t n, int F, const float *__restrict__ edges, const int32_t *__restrict__ nbins,
+                const int32_t *__restrict__ nan_bin, int max_bin, int stride, uint8_t *__restrict__ bins) {
     const int64_t total = n * stride;
     for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
         const int64_t row = e / stride;
@@ -54,6 +59,10 @@ gbdt_bin_kernel(const float *__restrict__ X, int64_t n, int F, const float *__re
                 if (ed[mid] < x) lo = mid + 1; else hi = mid;
             }
             b = lo;
+            if (nan_bin && x != x) {                                    // a missing value: the feature's NaN bin, where it has one (else 0, as the bisection gives)
+                const int nb = nan_bin[f];
+                if (nb >= 0 && nb < max_bin) b = nb;
+            }
         }
         bins[e] = (uint8_t)b;
     }
@@ -178,14 +187,41 @@ template <class T> __device__ __forceinline__ T wave_scan_add(T v, int lane) {  
 
 struct SplitCand { double gain; int bin; int64_t gl, hl, cl; };
 
+// The gain of one candidate's left sums against the node's totals, or false where a validity rule rejects it.
+__device__ __forceinline__ bool gbdt_split_gain(int64_t gl, int64_t hl, int64_t cl, int64_t TG, int64_t TH, int64_t TC, int eg, int eh, double l2,
+                                                int64_t min_data, double floor_h, double min_gain, double parent, double &gain) {
+    const int64_t cr = TC - cl;
+    if (cl < min_data || cr < min_data) return false;
+    const double GL = ldexp((double)gl, -eg), HL = ldexp((double)hl, -eh);
+    const double GR = ldexp((double)(TG - gl), -eg), HR = ldexp((double)(TH - hl), -eh);
+    if (!(HL >= floor_h) || !(HR >= floor_h)) return false;
+    gain = ((GL * GL) / (HL + l2) + (GR * GR) / (HR + l2)) - parent;
+    return gain >= min_gain;
+}
+
 // One wavefront per (leaf, feature): lane t owns the bins 4 t .. 4 t + 3, one prefix pass.  Writes the feature's best candidate to ws.
 // All arithmetic is float64 and nothing is contracted (the library is built with -ffp-contract=off):
 //   gain = ((GL * GL) / (HL + l2) + (GR * GR) / (HR + l2)) - (G * G) / (H + l2),   G = (double)qsum * 2^-e_g, H likewise (both exact).
 // (the scan itself is gbdt_split_scan, shared with the slot-list form of the batched level pass)
+//
+// kMissing (the *_missing entry points): the feature's NaN bin nan_bin[f] (a bin at or behind the value bins; anything else reads as "none")
+// holds the node's missing rows (MG, MH, MC), which the totals include.  The candidates b < nb - 1 send the missing rows right; where
+// MC > 0 the candidate b = nb - 1 (every value left, the NaNs right) joins them, and every b < nb - 1 is evaluated a second time with the
+// missing rows on the left, behind the wave-uniform test MC > 0.  A candidate's order key is b with the missing rows right and 511 - b
+// with them left, and the lowest key wins a tie: missing-right before missing-left, then the lowest bin among the missing-right candidates
+// and the HIGHEST among the missing-left ones (scikit-learn scans those from the top bin down and keeps the first of equal gains; bins
+// that are empty in a node make such ties bit-exact and common).  Field 2 of the record is bin + 256 * default_left; with MC == 0
+// default_left = (left count > right count).
+template <bool kMissing>
 __device__ __forceinline__ void gbdt_split_scan(const int64_t *__restrict__ hp, int f, int lane, int max_bin, const int32_t *__restrict__ nbins,
-                                                const int32_t *__restrict__ expo, double l2, int64_t min_data, double min_hess, double min_gain,
-                                                int64_t *__restrict__ r) {
+                                                const int32_t *__restrict__ nan_bin, const int32_t *__restrict__ expo, double l2, int64_t min_data,
+                                                double min_hess, double min_gain, int64_t *__restrict__ r) {
     const int nb = min(max(nbins[f], 1), max_bin);
+    int64_t MG = 0, MH = 0, MC = 0;
+    if (kMissing) {
+        const int mbin = nan_bin[f];
+        if (mbin >= nb && mbin < max_bin) { MG = hp[mbin * 3]; MH = hp[mbin * 3 + 1]; MC = hp[mbin * 3 + 2]; }
+    }
     int64_t pg[4], ph[4], pc[4], sg = 0, sh = 0, sc = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -194,7 +230,7 @@ __device__ __forceinline__ void gbdt_split_scan(const int64_t *__restrict__ hp, 
         pg[k] = sg; ph[k] = sh; pc[k] = sc;
     }
     const int64_t ig = wave_scan_add(sg, lane) - sg, ih = wave_scan_add(sh, lane) - sh, ic = wave_scan_add(sc, lane) - sc;
-    const int64_t TG = __shfl(ig + sg, kWave - 1), TH = __shfl(ih + sh, kWave - 1), TC = __shfl(ic + sc, kWave - 1);
+    const int64_t TG = __shfl(ig + sg, kWave - 1) + MG, TH = __shfl(ih + sh, kWave - 1) + MH, TC = __shfl(ic + sc, kWave - 1) + MC;
     const int eg = expo[0], eh = expo[1];
     const double G = ldexp((double)TG, -eg), H = ldexp((double)TH, -eh);
     const double parent = (G * G) / (H + l2);
@@ -203,16 +239,16 @@ __device__ __forceinline__ void gbdt_split_scan(const int64_t *__restrict__ hp, 
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int b = lane * 4 + k;
-        if (b >= nb - 1) continue;                                      // the last bin leaves nothing on the right
+        if (b >= nb - 1 && !(kMissing && MC > 0 && b == nb - 1)) continue;   // the last bin leaves nothing on the right, unless the NaNs are there
         const int64_t gl = ig + pg[k], hl = ih + ph[k], cl = ic + pc[k];
-        const int64_t cr = TC - cl;
-        if (cl < min_data || cr < min_data) continue;
-        const double GL = ldexp((double)gl, -eg), HL = ldexp((double)hl, -eh);
-        const double GR = ldexp((double)(TG - gl), -eg), HR = ldexp((double)(TH - hl), -eh);
-        if (!(HL >= floor_h) || !(HR >= floor_h)) continue;
-        const double gain = ((GL * GL) / (HL + l2) + (GR * GR) / (HR + l2)) - parent;
-        if (!(gain >= min_gain)) continue;
-        if (gain > best.gain) best = SplitCand{gain, b, gl, hl, cl};     // ascending bins: a tie keeps the lowest
+        double gain;
+        if (gbdt_split_gain(gl, hl, cl, TG, TH, TC, eg, eh, l2, min_data, floor_h, min_gain, parent, gain) &&
+            (gain > best.gain || (kMissing && gain == best.gain && b < best.bin)))
+            best = SplitCand{gain, b, gl, hl, cl};                       // ascending bins: a tie keeps the lowest (and beats any missing-left key)
+        if (kMissing && MC > 0 && b < nb - 1 &&
+            gbdt_split_gain(gl + MG, hl + MH, cl + MC, TG, TH, TC, eg, eh, l2, min_data, floor_h, min_gain, parent, gain) &&
+            (gain > best.gain || (gain == best.gain && 511 - b < best.bin)))
+            best = SplitCand{gain, 511 - b, gl + MG, hl + MH, cl + MC};   // a tie among missing-left candidates keeps the highest bin
     }
     // the wave's best: highest gain, then lowest bin
 #pragma unroll
@@ -225,28 +261,36 @@ __device__ __forceinline__ void gbdt_split_scan(const int64_t *__restrict__ hp, 
     if (lane == 0) {
         const bool ok = best.bin >= 0;
         r[0] = __double_as_longlong(ok ? best.gain : -INFINITY);
-        r[1] = ok ? f : -1; r[2] = best.bin;
+        r[1] = ok ? f : -1;
+        if (kMissing && ok) {
+            const bool mleft = best.bin >= 256;
+            const int64_t dl = MC > 0 ? (mleft ? 1 : 0) : (best.cl > TC - best.cl ? 1 : 0);
+            r[2] = (mleft ? 511 - best.bin : best.bin) + 256 * dl;
+        } else {
+            r[2] = best.bin;
+        }
         r[3] = best.gl; r[4] = best.hl; r[5] = best.cl;
         r[6] = ok ? TG - best.gl : 0; r[7] = ok ? TH - best.hl : 0; r[8] = ok ? TC - best.cl : 0;
     }
 }
 
-__global__ void __launch_bounds__(kBlock)
+template <bool kMissing> __global__ void __launch_bounds__(kBlock)
 gbdt_split_feature_kernel(const int64_t *__restrict__ hist, int nleaf, int F, int max_bin, const int32_t *__restrict__ nbins,
-                          const int32_t *__restrict__ expo, double l2, int64_t min_data, double min_hess, double min_gain,
-                          int64_t *__restrict__ ws) {
+                          const int32_t *__restrict__ nan_bin, const int32_t *__restrict__ expo, double l2, int64_t min_data, double min_hess,
+                          double min_gain, int64_t *__restrict__ ws) {
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t item = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
     if (item >= (int64_t)nleaf * F) return;
-    gbdt_split_scan(hist + item * max_bin * 3, (int)(item % F), lane, max_bin, nbins, expo, l2, min_data, min_hess, min_gain, ws + item * kRec);
+    gbdt_split_scan<kMissing>(hist + item * max_bin * 3, (int)(item % F), lane, max_bin, nbins, nan_bin, expo, l2, min_data, min_hess, min_gain,
+                              ws + item * kRec);
 }
 
 // The same scan over a list of K slots of a histogram pool [nslots][F][max_bin][3]: item = (k, feature).  A slot outside the pool gives the
 // record of a leaf without a split, and is never read.
-__global__ void __launch_bounds__(kBlock)
+template <bool kMissing> __global__ void __launch_bounds__(kBlock)
 gbdt_split_feature_slots_kernel(const int64_t *__restrict__ pool, int nslots, const int32_t *__restrict__ slots, int K, int F, int max_bin,
-                                const int32_t *__restrict__ nbins, const int32_t *__restrict__ expo, double l2, int64_t min_data, double min_hess,
-                                double min_gain, int64_t *__restrict__ ws) {
+                                const int32_t *__restrict__ nbins, const int32_t *__restrict__ nan_bin, const int32_t *__restrict__ expo, double l2,
+                                int64_t min_data, double min_hess, double min_gain, int64_t *__restrict__ ws) {
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t item = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
     if (item >= (int64_t)K * F) return;
@@ -257,7 +301,7 @@ gbdt_split_feature_slots_kernel(const int64_t *__restrict__ pool, int nslots, co
         if (lane < kRec) r[lane] = lane == 0 ? __double_as_longlong(-INFINITY) : lane <= 2 ? -1 : 0;
         return;
     }
-    gbdt_split_scan(pool + ((int64_t)slot * F + f) * max_bin * 3, f, lane, max_bin, nbins, expo, l2, min_data, min_hess, min_gain, r);
+    gbdt_split_scan<kMissing>(pool + ((int64_t)slot * F + f) * max_bin * 3, f, lane, max_bin, nbins, nan_bin, expo, l2, min_data, min_hess, min_gain, r);
 }
 
 // One wavefront per leaf: the best of its F feature records, ties to the lowest feature.
@@ -288,15 +332,17 @@ gbdt_split_leaf_kernel(const int64_t *__restrict__ ws, int F, int64_t *__restric
 constexpr int kPartSteps = 4;                                           // a workgroup owns 4 x 256 consecutive entries of the list
 
 __device__ __forceinline__ bool part_goes_left(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ rows, int64_t i, int m,
-                                               int feature, int bin, int &row) {
+                                               int feature, int bin, int also_left, int &row) {
     row = i < m ? rows[i] : -1;
-    return row >= 0 && row < n && (int)bins[(size_t)row * stride + feature] <= bin;
+    if (row < 0 || row >= n) return false;
+    const int b = bins[(size_t)row * stride + feature];
+    return b <= bin || b == also_left;                                  // also_left: the NaN bin of a split whose missing rows go left, or -1
 }
 
 // The predicates of the stable partition: pred(i, row) gives entry i's row (-1 past the list) and whether it goes to the front.
-struct PartByBin {                                                      // ptr_gbdt_partition: bins[row][feature] <= bin
-    const uint8_t *bins; int stride, n; const int32_t *rows; int m, feature, bin;
-    __device__ __forceinline__ bool operator()(int64_t i, int &row) const { return part_goes_left(bins, stride, n, rows, i, m, feature, bin, row); }
+struct PartByBin {                                                      // ptr_gbdt_partition: bins[row][feature] <= bin, or == also_left
+    const uint8_t *bins; int stride, n; const int32_t *rows; int m, feature, bin, also_left;
+    __device__ __forceinline__ bool operator()(int64_t i, int &row) const { return part_goes_left(bins, stride, n, rows, i, m, feature, bin, also_left, row); }
 };
 struct PartByMask {                                                     // ptr_gbdt_partition_mask: mask[row] != 0; rows == NULL: the list 0 .. m - 1
     const uint8_t *mask; int n; const int32_t *rows; int m;
@@ -454,16 +500,19 @@ gbdt_hist_sub_seg_kernel(int64_t *__restrict__ pool, int nslots, int64_t slot_el
     for (int64_t e = (int64_t)blockIdx.y * kBlock + threadIdx.x; e < slot_elems; e += (int64_t)gridDim.y * kBlock) op[e] = pp[e] - cp[e];
 }
 
-// The batched stable partition.  segs [K][4] = (start, count, feature, bin) over rows [nrows]; blocks [NB][2] = (segment, j): workgroup b owns
+// The batched stable partition.  segs [K][cols] = (start, count, feature, bin[, also_left]) over rows [nrows], cols 4 or 5; blocks [NB][2] = (segment, j): workgroup b owns
 // the entries j * 1024 .. of its segment, and a segment's blocks stand together in ascending j, so block b - j is the segment's first.
-struct GbdtPartSeg { int start, count, feature, bin, nblk; bool ok; };
-__device__ __forceinline__ GbdtPartSeg gbdt_part_block(const int32_t *__restrict__ segs, int K, const int32_t *__restrict__ blocks, int b, int NB,
+struct GbdtPartSeg { int start, count, feature, bin, also_left, nblk; bool ok; };
+__device__ __forceinline__ GbdtPartSeg gbdt_part_block(const int32_t *__restrict__ segs, int cols, int K, const int32_t *__restrict__ blocks, int b, int NB,
                                                        int64_t nrows, int F, int &j) {
-    GbdtPartSeg s{0, 0, 0, 0, 0, false};
+    GbdtPartSeg s{0, 0, 0, 0, -1, 0, false};
     const int k = blocks[b * 2];
     j = blocks[b * 2 + 1];
     if (k < 0 || k >= K) return s;
-    s.start = segs[k * 4]; s.count = segs[k * 4 + 1]; s.feature = segs[k * 4 + 2]; s.bin = segs[k * 4 + 3];
+    segs += (int64_t)k * cols;
+    s.start = segs[0]; s.count = segs[1]; s.feature = segs[2]; s.bin = segs[3];
+    if (cols > 4) s.also_left = segs[4];
+    if (s.also_left < -1 || s.also_left > 255) return s;
     if (s.start < 0 || s.count < 0 || (int64_t)s.start + s.count > nrows || s.feature < 0 || s.feature >= F || s.bin < 0 || s.bin > 255) return s;
     s.nblk = (int)(((int64_t)s.count + kGbdtPartRows - 1) / kGbdtPartRows);
     if (j < 0 || j >= s.nblk || b - j < 0 || (int64_t)b - j + s.nblk > NB) return s;
@@ -473,16 +522,16 @@ __device__ __forceinline__ GbdtPartSeg gbdt_part_block(const int32_t *__restrict
 
 __global__ void __launch_bounds__(kBlock)
 gbdt_part_seg_count_kernel(const uint8_t *__restrict__ bins, int stride, int n, int F, const int32_t *__restrict__ rows, int64_t nrows,
-                           const int32_t *__restrict__ segs, int K, const int32_t *__restrict__ blocks, int NB, int32_t *__restrict__ counts) {
+                           const int32_t *__restrict__ segs, int cols, int K, const int32_t *__restrict__ blocks, int NB, int32_t *__restrict__ counts) {
     __shared__ int32_t tot;
     int j;
-    const GbdtPartSeg s = gbdt_part_block(segs, K, blocks, blockIdx.x, NB, nrows, F, j);
+    const GbdtPartSeg s = gbdt_part_block(segs, cols, K, blocks, blockIdx.x, NB, nrows, F, j);
     if (!s.ok) { if (threadIdx.x == 0) counts[blockIdx.x] = 0; return; }
     if (threadIdx.x == 0) tot = 0;
     __syncthreads();
     int c = 0, row;
     for (int st = 0; st < kPartSteps; ++st)
-        c += part_goes_left(bins, stride, n, rows + s.start, ((int64_t)j * kPartSteps + st) * kBlock + threadIdx.x, s.count, s.feature, s.bin, row) ? 1 : 0;
+        c += part_goes_left(bins, stride, n, rows + s.start, ((int64_t)j * kPartSteps + st) * kBlock + threadIdx.x, s.count, s.feature, s.bin, s.also_left, row) ? 1 : 0;
     atomicAdd(&tot, c);
     __syncthreads();
     if (threadIdx.x == 0) counts[blockIdx.x] = tot;
@@ -512,11 +561,11 @@ gbdt_part_seg_scan_kernel(int32_t *__restrict__ counts, int nb) {
 
 __global__ void __launch_bounds__(kBlock)
 gbdt_part_seg_scatter_kernel(const uint8_t *__restrict__ bins, int stride, int n, int F, const int32_t *__restrict__ rows, int64_t nrows,
-                             const int32_t *__restrict__ segs, int K, const int32_t *__restrict__ blocks, int NB,
+                             const int32_t *__restrict__ segs, int cols, int K, const int32_t *__restrict__ blocks, int NB,
                              const int32_t *__restrict__ counts, int32_t *__restrict__ out, int32_t *__restrict__ left_counts) {
     __shared__ int32_t wave_left[kBlock / kWave];
     int j;
-    const GbdtPartSeg s = gbdt_part_block(segs, K, blocks, blockIdx.x, NB, nrows, F, j);
+    const GbdtPartSeg s = gbdt_part_block(segs, cols, K, blocks, blockIdx.x, NB, nrows, F, j);
     if (!s.ok) return;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int first = blockIdx.x - j;
@@ -528,7 +577,7 @@ gbdt_part_seg_scatter_kernel(const uint8_t *__restrict__ bins, int stride, int n
     for (int st = 0; st < kPartSteps; ++st) {
         const int64_t i = ((int64_t)j * kPartSteps + st) * kBlock + threadIdx.x;
         int row;
-        const bool left = part_goes_left(bins, stride, n, srows, i, s.count, s.feature, s.bin, row);
+        const bool left = part_goes_left(bins, stride, n, srows, i, s.count, s.feature, s.bin, s.also_left, row);
         const unsigned long long mask = __ballot(left);
         if (lane == 0) wave_left[wave] = __popcll(mask);
         __syncthreads();
@@ -560,7 +609,7 @@ gbdt_add_leaf_values_kernel(float *__restrict__ scores, int n, const int32_t *__
 __global__ void __launch_bounds__(kBlock)
 gbdt_predict_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t *__restrict__ feature, const float *__restrict__ threshold,
                     const int32_t *__restrict__ left, const int32_t *__restrict__ right, const float *__restrict__ value,
-                    const int32_t *__restrict__ tree_offsets, int ntrees, float *__restrict__ out) {
+                    const int32_t *__restrict__ tree_offsets, const uint8_t *__restrict__ default_left, int ntrees, float *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const float *x = X + i * F;
@@ -572,7 +621,9 @@ gbdt_predict_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t
             if (node >= nn) break;
             const int f = feature[base + node];
             if (f < 0 || f >= F) break;
-            node = x[f] <= threshold[base + node] ? left[base + node] : right[base + node];
+            const float xv = x[f];
+            const bool go_left = (default_left && xv != xv) ? default_left[base + node] != 0 : xv <= threshold[base + node];   // a NaN follows the node's direction
+            node = go_left ? left[base + node] : right[base + node];
         }
         s += (node < 0 && ~node <= nn) ? value[leaves + ~node] : NAN;   // a malformed tree (a cycle, an index out of range) gives NaN
     }
@@ -584,7 +635,7 @@ gbdt_predict_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t
 __global__ void __launch_bounds__(kBlock)
 gbdt_add_tree_binned_kernel(float *__restrict__ scores, const uint8_t *__restrict__ bins, int stride, int n, int F, const int32_t *__restrict__ rows,
                             int m, const int32_t *__restrict__ feature, const int32_t *__restrict__ bin, const int32_t *__restrict__ left,
-                            const int32_t *__restrict__ right, const float *__restrict__ value, int nn) {
+                            const int32_t *__restrict__ right, const float *__restrict__ value, const int32_t *__restrict__ also_left, int nn) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= m) return;
     const int row = rows ? rows[i] : i;
@@ -595,7 +646,8 @@ gbdt_add_tree_binned_kernel(float *__restrict__ scores, const uint8_t *__restric
         if (node >= nn) break;
         const int f = feature[node];
         if (f < 0 || f >= F) break;
-        node = (int)x[f] <= bin[node] ? left[node] : right[node];
+        const int b = x[f];
+        node = (b <= bin[node] || (also_left && b == also_left[node])) ? left[node] : right[node];
     }
     scores[row] += (node < 0 && ~node <= nn) ? value[~node] : NAN;      // a malformed tree (a cycle, an index out of range) gives NaN
 }
@@ -740,15 +792,25 @@ static int check_bins_layout(int64_t n, int F, int stride, const char *who) {
 
 using namespace ptr;
 
-extern "C" int ptr_gbdt_bin(const float *X, int64_t n, int F, const float *edges, const int32_t *nbins, int max_bin, int stride, uint8_t *bins,
-                            void *stream) {
-    const char *who = "ptr_gbdt_bin";
+// nan_bin == NULL: no missing values (ptr_gbdt_bin)
+static int gbdt_bin_impl(const char *who, const float *X, int64_t n, int F, const float *edges, const int32_t *nbins, const int32_t *nan_bin, bool missing,
+                         int max_bin, int stride, uint8_t *bins, void *stream) {
     if (int rc = check_bins_layout(n, F, stride, who)) return rc;
     if (int rc = check_max_bin(max_bin, who)) return rc;
     if (n == 0 || F == 0) return 0;
-    if (!X || !edges || !nbins || !bins) { set_error("%s: NULL pointer (X, edges, nbins or bins)", who); return PTR_ERR_INVALID_ARG; }
-    hipLaunchKernelGGL(gbdt_bin_kernel, dim3(grid_for(n * stride)), dim3(kBlock), 0, as_stream(stream), X, n, F, edges, nbins, max_bin, stride, bins);
+    if (!X || !edges || !nbins || !bins || (missing && !nan_bin)) { set_error("%s: NULL pointer (X, edges, nbins%s or bins)", who, missing ? ", nan_bin" : ""); return PTR_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(gbdt_bin_kernel, dim3(grid_for(n * stride)), dim3(kBlock), 0, as_stream(stream), X, n, F, edges, nbins, nan_bin, max_bin, stride, bins);
     return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_bin(const float *X, int64_t n, int F, const float *edges, const int32_t *nbins, int max_bin, int stride, uint8_t *bins,
+                            void *stream) {
+    return gbdt_bin_impl("ptr_gbdt_bin", X, n, F, edges, nbins, nullptr, false, max_bin, stride, bins, stream);
+}
+
+extern "C" int ptr_gbdt_bin_missing(const float *X, int64_t n, int F, const float *edges, const int32_t *nbins, const int32_t *nan_bin, int max_bin,
+                                    int stride, uint8_t *bins, void *stream) {
+    return gbdt_bin_impl("ptr_gbdt_bin_missing", X, n, F, edges, nbins, nan_bin, true, max_bin, stride, bins, stream);
 }
 
 extern "C" int ptr_gbdt_quantize(const float *g, const float *h, int64_t n, int32_t *qg, int32_t *qh, int32_t *expo, int32_t *flag, uint32_t *state,
@@ -796,10 +858,9 @@ extern "C" int ptr_gbdt_hist_sub(const int64_t *parent, const int64_t *child, in
     return check_hip(hipGetLastError(), who);
 }
 
-extern "C" int ptr_gbdt_best_split(const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *expo, double lambda_l2,
-                                   int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double min_gain_to_split, int64_t *ws, int64_t *rec,
-                                   void *stream) {
-    const char *who = "ptr_gbdt_best_split";
+static int gbdt_best_split_impl(const char *who, const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *nan_bin,
+                                bool missing, const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf, double min_sum_hessian_in_leaf,
+                                double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream) {
     if (nleaf < 0 || F < 0) { set_error("%s: negative size (nleaf=%d, F=%d)", who, nleaf, F); return PTR_ERR_INVALID_ARG; }
     if (int rc = check_max_bin(max_bin, who)) return rc;
     if (!(lambda_l2 >= 0.0) || !(min_sum_hessian_in_leaf == min_sum_hessian_in_leaf) || !(min_gain_to_split == min_gain_to_split)) {
@@ -807,33 +868,64 @@ extern "C" int ptr_gbdt_best_split(const int64_t *hist, int nleaf, int F, int ma
         return PTR_ERR_INVALID_ARG;
     }
     if (nleaf == 0) return 0;
-    if (!rec || (F > 0 && (!hist || !nbins || !expo || !ws))) { set_error("%s: NULL pointer (hist, nbins, expo, ws or rec)", who); return PTR_ERR_INVALID_ARG; }
+    if (!rec || (F > 0 && (!hist || !nbins || !expo || !ws || (missing && !nan_bin)))) {
+        set_error("%s: NULL pointer (hist, nbins%s, expo, ws or rec)", who, missing ? ", nan_bin" : "");
+        return PTR_ERR_INVALID_ARG;
+    }
     const int64_t items = (int64_t)nleaf * F;
-    if (items > 0)
-        hipLaunchKernelGGL(gbdt_split_feature_kernel, dim3((unsigned)((items + 3) / 4)), dim3(kBlock), 0, as_stream(stream), hist, nleaf, F, max_bin, nbins,
-                           expo, lambda_l2, min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws);
+    const dim3 grid((unsigned)((items + 3) / 4));
+    if (items > 0 && missing)
+        hipLaunchKernelGGL(gbdt_split_feature_kernel<true>, grid, dim3(kBlock), 0, as_stream(stream), hist, nleaf, F, max_bin, nbins, nan_bin, expo, lambda_l2,
+                           min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws);
+    else if (items > 0)
+        hipLaunchKernelGGL(gbdt_split_feature_kernel<false>, grid, dim3(kBlock), 0, as_stream(stream), hist, nleaf, F, max_bin, nbins, nan_bin, expo, lambda_l2,
+                           min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws);
     hipLaunchKernelGGL(gbdt_split_leaf_kernel, dim3(nleaf), dim3(kWave), 0, as_stream(stream), ws, F, rec);
     return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_best_split(const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *expo, double lambda_l2,
+                                   int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double min_gain_to_split, int64_t *ws, int64_t *rec,
+                                   void *stream) {
+    return gbdt_best_split_impl("ptr_gbdt_best_split", hist, nleaf, F, max_bin, nbins, nullptr, false, expo, lambda_l2, min_data_in_leaf,
+                                min_sum_hessian_in_leaf, min_gain_to_split, ws, rec, stream);
+}
+
+extern "C" int ptr_gbdt_best_split_missing(const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *nan_bin,
+                                           const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf, double min_sum_hessian_in_leaf,
+                                           double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream) {
+    return gbdt_best_split_impl("ptr_gbdt_best_split_missing", hist, nleaf, F, max_bin, nbins, nan_bin, true, expo, lambda_l2, min_data_in_leaf,
+                                min_sum_hessian_in_leaf, min_gain_to_split, ws, rec, stream);
 }
 
 extern "C" size_t ptr_gbdt_partition_ws_ints(int64_t m) {
     return m <= 0 ? 1 : (size_t)((m + kPartSteps * kBlock - 1) / (kPartSteps * kBlock)) + 1;
 }
 
-extern "C" int ptr_gbdt_partition(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m, int feature, int bin,
-                                  int32_t *out, int32_t *left_count, int32_t *ws, void *stream) {
-    const char *who = "ptr_gbdt_partition";
+static int gbdt_partition_impl(const char *who, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m, int feature, int bin,
+                               int also_left, int32_t *out, int32_t *left_count, int32_t *ws, void *stream) {
     if (int rc = check_bins_layout(n, F, stride, who)) return rc;
     if (m < 0 || m > INT32_MAX) { set_error("%s: bad row count m=%lld", who, (long long)m); return PTR_ERR_INVALID_ARG; }
     if (feature < 0 || feature >= F || bin < 0 || bin > 255) {
         set_error("%s: feature must be in 0 .. F - 1 and bin in 0 .. 255 (feature=%d, F=%d, bin=%d)", who, feature, F, bin);
         return PTR_ERR_INVALID_ARG;
     }
+    if (also_left < -1 || also_left > 255) { set_error("%s: also_left must be -1 (none) or a bin in 0 .. 255, got %d", who, also_left); return PTR_ERR_INVALID_ARG; }
     if (!left_count) { set_error("%s: NULL left_count", who); return PTR_ERR_INVALID_ARG; }
     if (m == 0) return check_hip(hipMemsetAsync(left_count, 0, sizeof(int32_t), as_stream(stream)), who);
     if (!bins || !rows || !out || !ws) { set_error("%s: NULL pointer (bins, rows, out or ws)", who); return PTR_ERR_INVALID_ARG; }
     const int nb = (int)ptr_gbdt_partition_ws_ints(m) - 1;
-    return launch_partition(PartByBin{bins, stride, (int)n, rows, (int)m, feature, bin}, nb, out, left_count, ws, as_stream(stream), who);
+    return launch_partition(PartByBin{bins, stride, (int)n, rows, (int)m, feature, bin, also_left}, nb, out, left_count, ws, as_stream(stream), who);
+}
+
+extern "C" int ptr_gbdt_partition(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m, int feature, int bin,
+                                  int32_t *out, int32_t *left_count, int32_t *ws, void *stream) {
+    return gbdt_partition_impl("ptr_gbdt_partition", bins, stride, n, F, rows, m, feature, bin, -1, out, left_count, ws, stream);
+}
+
+extern "C" int ptr_gbdt_partition_missing(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m, int feature, int bin,
+                                          int also_left, int32_t *out, int32_t *left_count, int32_t *ws, void *stream) {
+    return gbdt_partition_impl("ptr_gbdt_partition_missing", bins, stride, n, F, rows, m, feature, bin, also_left, out, left_count, ws, stream);
 }
 
 extern "C" int ptr_gbdt_add_leaf_values(float *scores, int64_t n, const int32_t *rows, const int32_t *offsets, const float *values, int nleaves,
@@ -850,16 +942,31 @@ extern "C" int ptr_gbdt_add_leaf_values(float *scores, int64_t n, const int32_t 
     return check_hip(hipGetLastError(), who);
 }
 
-extern "C" int ptr_gbdt_predict(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
-                                const int32_t *right, const float *value, const int32_t *tree_offsets, int ntrees, float *out, void *stream) {
-    const char *who = "ptr_gbdt_predict";
+static int gbdt_predict_impl(const char *who, const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                             const int32_t *right, const float *value, const int32_t *tree_offsets, const uint8_t *default_left, bool missing, int ntrees,
+                             float *out, void *stream) {
     if (n < 0 || F < 0 || ntrees < 0) { set_error("%s: negative size (n=%lld, F=%d, ntrees=%d)", who, (long long)n, F, ntrees); return PTR_ERR_INVALID_ARG; }
     if (n == 0) return 0;
     if (!out || (F > 0 && !X)) { set_error("%s: NULL pointer (X or out)", who); return PTR_ERR_INVALID_ARG; }
-    if (ntrees > 0 && (!feature || !threshold || !left || !right || !value || !tree_offsets)) { set_error("%s: NULL tree array", who); return PTR_ERR_INVALID_ARG; }
+    if (ntrees > 0 && (!feature || !threshold || !left || !right || !value || !tree_offsets || (missing && !default_left))) {
+        set_error("%s: NULL tree array", who);
+        return PTR_ERR_INVALID_ARG;
+    }
     hipLaunchKernelGGL(gbdt_predict_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), X, n, F, feature, threshold, left,
-                       right, value, tree_offsets, ntrees, out);
+                       right, value, tree_offsets, default_left, ntrees, out);
     return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_predict(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                const int32_t *right, const float *value, const int32_t *tree_offsets, int ntrees, float *out, void *stream) {
+    return gbdt_predict_impl("ptr_gbdt_predict", X, n, F, feature, threshold, left, right, value, tree_offsets, nullptr, false, ntrees, out, stream);
+}
+
+extern "C" int ptr_gbdt_predict_missing(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                        const int32_t *right, const float *value, const int32_t *tree_offsets, const uint8_t *default_left, int ntrees,
+                                        float *out, void *stream) {
+    return gbdt_predict_impl("ptr_gbdt_predict_missing", X, n, F, feature, threshold, left, right, value, tree_offsets, default_left, true, ntrees, out,
+                             stream);
 }
 
 // ---------------------------------------------------------------- the entry points of row sampling
@@ -920,21 +1027,34 @@ extern "C" int ptr_gbdt_partition_mask(const uint8_t *mask, int64_t n, const int
     return launch_partition(PartByMask{mask, (int)n, rows, (int)m}, nb, out, left_count, ws, as_stream(stream), who);
 }
 
-extern "C" int ptr_gbdt_add_tree_binned(float *scores, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m,
-                                        const int32_t *feature, const int32_t *bin, const int32_t *left, const int32_t *right, const float *value,
-                                        int nnodes, void *stream) {
-    const char *who = "ptr_gbdt_add_tree_binned";
+static int gbdt_add_tree_binned_impl(const char *who, float *scores, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m,
+                                     const int32_t *feature, const int32_t *bin, const int32_t *left, const int32_t *right, const float *value,
+                                     const int32_t *also_left, bool missing, int nnodes, void *stream) {
     if (int rc = check_bins_layout(n, F, stride, who)) return rc;
     if (m < 0 || m > INT32_MAX || nnodes < 0) { set_error("%s: bad size (m=%lld, nnodes=%d)", who, (long long)m, nnodes); return PTR_ERR_INVALID_ARG; }
     if (!rows && m > n) { set_error("%s: rows is NULL (the first m rows), so m must not exceed n (m=%lld, n=%lld)", who, (long long)m, (long long)n); return PTR_ERR_INVALID_ARG; }
     if (m == 0 || n == 0) return 0;
-    if (!scores || !value || (nnodes > 0 && (!bins || !feature || !bin || !left || !right))) {
+    if (!scores || !value || (nnodes > 0 && (!bins || !feature || !bin || !left || !right || (missing && !also_left)))) {
         set_error("%s: NULL pointer (scores, bins, value or a tree array)", who);
         return PTR_ERR_INVALID_ARG;
     }
     hipLaunchKernelGGL(gbdt_add_tree_binned_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), scores, bins, stride,
-                       (int)n, F, rows, (int)m, feature, bin, left, right, value, nnodes);
+                       (int)n, F, rows, (int)m, feature, bin, left, right, value, also_left, nnodes);
     return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_add_tree_binned(float *scores, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m,
+                                        const int32_t *feature, const int32_t *bin, const int32_t *left, const int32_t *right, const float *value,
+                                        int nnodes, void *stream) {
+    return gbdt_add_tree_binned_impl("ptr_gbdt_add_tree_binned", scores, bins, stride, n, F, rows, m, feature, bin, left, right, value, nullptr, false,
+                                     nnodes, stream);
+}
+
+extern "C" int ptr_gbdt_add_tree_binned_missing(float *scores, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m,
+                                                const int32_t *feature, const int32_t *bin, const int32_t *left, const int32_t *right,
+                                                const float *value, const int32_t *also_left, int nnodes, void *stream) {
+    return gbdt_add_tree_binned_impl("ptr_gbdt_add_tree_binned_missing", scores, bins, stride, n, F, rows, m, feature, bin, left, right, value, also_left,
+                                     true, nnodes, stream);
 }
 
 // ---------------------------------------------------------------- the batched entry points of a depth-wise level
@@ -982,10 +1102,10 @@ extern "C" int ptr_gbdt_hist_sub_segments(int64_t *pool, int nslots, int F, int 
     return check_hip(hipGetLastError(), who);
 }
 
-extern "C" int ptr_gbdt_best_split_slots(const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin, const int32_t *nbins,
-                                         const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf, double min_sum_hessian_in_leaf,
-                                         double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream) {
-    const char *who = "ptr_gbdt_best_split_slots";
+static int gbdt_best_split_slots_impl(const char *who, const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin,
+                                      const int32_t *nbins, const int32_t *nan_bin, bool missing, const int32_t *expo, double lambda_l2,
+                                      int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double min_gain_to_split, int64_t *ws, int64_t *rec,
+                                      void *stream) {
     if (int rc = check_level_common(who, 0, F, 0, max_bin, K, kCheckMaxBin)) return rc;
     if (nslots < 0) { set_error("%s: negative size (nslots=%d)", who, nslots); return PTR_ERR_INVALID_ARG; }
     if (!(lambda_l2 >= 0.0) || !(min_sum_hessian_in_leaf == min_sum_hessian_in_leaf) || !(min_gain_to_split == min_gain_to_split)) {
@@ -993,20 +1113,42 @@ extern "C" int ptr_gbdt_best_split_slots(const int64_t *pool, int nslots, const 
         return PTR_ERR_INVALID_ARG;
     }
     if (K == 0) return 0;
-    if (!pool || !slots || !nbins || !expo || !ws || !rec) { set_error("%s: NULL pointer (pool, slots, nbins, expo, ws or rec)", who); return PTR_ERR_INVALID_ARG; }
+    if (!pool || !slots || !nbins || !expo || !ws || !rec || (missing && !nan_bin)) {
+        set_error("%s: NULL pointer (pool, slots, nbins%s, expo, ws or rec)", who, missing ? ", nan_bin" : "");
+        return PTR_ERR_INVALID_ARG;
+    }
     const int64_t items = (int64_t)K * F;
-    hipLaunchKernelGGL(gbdt_split_feature_slots_kernel, dim3((unsigned)((items + 3) / 4)), dim3(kBlock), 0, as_stream(stream), pool, nslots, slots, K, F,
-                       max_bin, nbins, expo, lambda_l2, min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws);
+    const dim3 grid((unsigned)((items + 3) / 4));
+    if (missing)
+        hipLaunchKernelGGL(gbdt_split_feature_slots_kernel<true>, grid, dim3(kBlock), 0, as_stream(stream), pool, nslots, slots, K, F, max_bin, nbins, nan_bin,
+                           expo, lambda_l2, min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws);
+    else
+        hipLaunchKernelGGL(gbdt_split_feature_slots_kernel<false>, grid, dim3(kBlock), 0, as_stream(stream), pool, nslots, slots, K, F, max_bin, nbins, nan_bin,
+                           expo, lambda_l2, min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws);
     hipLaunchKernelGGL(gbdt_split_leaf_kernel, dim3(K), dim3(kWave), 0, as_stream(stream), ws, F, rec);
     return check_hip(hipGetLastError(), who);
 }
 
+extern "C" int ptr_gbdt_best_split_slots(const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin, const int32_t *nbins,
+                                         const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf, double min_sum_hessian_in_leaf,
+                                         double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream) {
+    return gbdt_best_split_slots_impl("ptr_gbdt_best_split_slots", pool, nslots, slots, K, F, max_bin, nbins, nullptr, false, expo, lambda_l2,
+                                      min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws, rec, stream);
+}
+
+extern "C" int ptr_gbdt_best_split_slots_missing(const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin, const int32_t *nbins,
+                                                 const int32_t *nan_bin, const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf,
+                                                 double min_sum_hessian_in_leaf, double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream) {
+    return gbdt_best_split_slots_impl("ptr_gbdt_best_split_slots_missing", pool, nslots, slots, K, F, max_bin, nbins, nan_bin, true, expo, lambda_l2,
+                                      min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws, rec, stream);
+}
+
 extern "C" size_t ptr_gbdt_partition_segments_ws_ints(int64_t nblocks) { return nblocks <= 0 ? 1 : (size_t)nblocks + 1; }
 
-extern "C" int ptr_gbdt_partition_segments(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t nrows, const int32_t *segs,
-                                           int K, const int32_t *blocks, int nblocks, int32_t *out, int32_t *left_counts, int32_t *ws,
-                                           int64_t ws_ints, void *stream) {
-    const char *who = "ptr_gbdt_partition_segments";
+// cols: the width of a segs entry, 4 (start, count, feature, bin) or 5 (with also_left)
+static int gbdt_partition_segments_impl(const char *who, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t nrows,
+                                        const int32_t *segs, int cols, int K, const int32_t *blocks, int nblocks, int32_t *out, int32_t *left_counts,
+                                        int32_t *ws, int64_t ws_ints, void *stream) {
     if (int rc = check_level_common(who, n, F, stride, 0, K, kCheckBins)) return rc;
     if (nblocks < 0 || nrows < 0 || nrows > INT32_MAX) { set_error("%s: bad size (nblocks=%d, nrows=%lld)", who, nblocks, (long long)nrows); return PTR_ERR_INVALID_ARG; }
     if (nrows > 0 && (!rows || !out)) { set_error("%s: NULL pointer (rows or out)", who); return PTR_ERR_INVALID_ARG; }
@@ -1023,9 +1165,23 @@ extern "C" int ptr_gbdt_partition_segments(const uint8_t *bins, int stride, int6
     if (K == 0) return 0;
     if (int rc = check_hip(hipMemsetAsync(left_counts, 0, (size_t)K * sizeof(int32_t), s), who)) return rc;
     if (nblocks == 0) return 0;
-    hipLaunchKernelGGL(gbdt_part_seg_count_kernel, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, K, blocks, nblocks, ws);
+    hipLaunchKernelGGL(gbdt_part_seg_count_kernel, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, cols, K, blocks, nblocks, ws);
     hipLaunchKernelGGL(gbdt_part_seg_scan_kernel, dim3(1), dim3(kBlock), 0, s, ws, nblocks);
-    hipLaunchKernelGGL(gbdt_part_seg_scatter_kernel, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, K, blocks, nblocks, ws, out,
+    hipLaunchKernelGGL(gbdt_part_seg_scatter_kernel, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, cols, K, blocks, nblocks, ws, out,
                        left_counts);
     return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_partition_segments(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t nrows, const int32_t *segs,
+                                           int K, const int32_t *blocks, int nblocks, int32_t *out, int32_t *left_counts, int32_t *ws,
+                                           int64_t ws_ints, void *stream) {
+    return gbdt_partition_segments_impl("ptr_gbdt_partition_segments", bins, stride, n, F, rows, nrows, segs, 4, K, blocks, nblocks, out, left_counts, ws,
+                                        ws_ints, stream);
+}
+
+extern "C" int ptr_gbdt_partition_segments_missing(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t nrows,
+                                                   const int32_t *segs, int K, const int32_t *blocks, int nblocks, int32_t *out, int32_t *left_counts,
+                                                   int32_t *ws, int64_t ws_ints, void *stream) {
+    return gbdt_partition_segments_impl("ptr_gbdt_partition_segments_missing", bins, stride, n, F, rows, nrows, segs, 5, K, blocks, nblocks, out,
+                                        left_counts, ws, ws_ints, stream);
 }

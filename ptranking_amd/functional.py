@@ -964,10 +964,14 @@ def _gbdt_max_bin(max_bin):
     return int(max_bin)
 
 
-def gbdt_bin(X, edges, nbins):
+def _gbdt_nan_bin(nan_bin, F):
+    return _check("nan_bin", nan_bin, torch.int32, (F,))
+
+
+def gbdt_bin(X, edges, nbins, nan_bin=None):
     """Bin indices of a feature matrix -> uint8 [n, round_up(F, 16)] (pad columns 0).  X float32 [n, F]; edges float32 [F, max_bin - 1],
     ascending per feature; nbins int32 [F].  bin = the number of the feature's first nbins - 1 edges below x, so x <= edges[f, b] is
-    bin <= b."""
+    bin <= b.  nan_bin (int32 [F], -1: none): a NaN of feature f gets the bin nan_bin[f] (ptr_gbdt_bin_missing)."""
     X = _check("X", X)
     if X.dim() != 2:
         raise ValueError(f"X must be [rows, features], got {tuple(X.shape)}")
@@ -980,7 +984,11 @@ def gbdt_bin(X, edges, nbins):
     stride = (F + 15) // 16 * 16
     bins = torch.empty((n, stride), device=X.device, dtype=torch.uint8)
     with torch.cuda.device(X.device):
-        _lib.call("ptr_gbdt_bin", _lib.ptr(X), n, F, _lib.ptr(edges), _lib.ptr(nbins), max_bin, stride, _lib.ptr(bins), _lib.current_stream(X.device))
+        if nan_bin is None:
+            _lib.call("ptr_gbdt_bin", _lib.ptr(X), n, F, _lib.ptr(edges), _lib.ptr(nbins), max_bin, stride, _lib.ptr(bins), _lib.current_stream(X.device))
+        else:
+            _lib.call("ptr_gbdt_bin_missing", _lib.ptr(X), n, F, _lib.ptr(edges), _lib.ptr(nbins), _lib.ptr(_gbdt_nan_bin(nan_bin, F)), max_bin, stride,
+                      _lib.ptr(bins), _lib.current_stream(X.device))
     return bins
 
 
@@ -1039,10 +1047,11 @@ def gbdt_hist_sub(parent, child, out=None):
     return out
 
 
-def gbdt_best_split(hist, nbins, expo, lambda_l2=0.0, min_data_in_leaf=1, min_sum_hessian_in_leaf=1e-3, min_gain_to_split=0.0, out=None):
+def gbdt_best_split(hist, nbins, expo, lambda_l2=0.0, min_data_in_leaf=1, min_sum_hessian_in_leaf=1e-3, min_gain_to_split=0.0, out=None, nan_bin=None):
     """The best split of every leaf histogram of a batch -> int64 [leaves, 9] records (GBDT_RECORD; record[0] is the float64 gain's bit
     pattern: .view(torch.float64), -inf without a valid split).  hist int64 [leaves, F, max_bin, 3] (or one [F, max_bin, 3]); nbins int32
-    [F]; expo as gbdt_quantize returned it.  float64, ties to the lowest feature, then the lowest bin."""
+    [F]; expo as gbdt_quantize returned it.  float64, ties to the lowest feature, then the lowest bin.  nan_bin (int32 [F], -1: none):
+    the scan with learned directions for the missing rows (ptr_gbdt_best_split_missing); record[2] is then bin + 256 * default_left."""
     hist = _check("hist", hist, torch.int64)
     if hist.dim() == 3:
         hist = hist[None]
@@ -1054,16 +1063,20 @@ def gbdt_best_split(hist, nbins, expo, lambda_l2=0.0, min_data_in_leaf=1, min_su
     dev = hist.device
     rec = torch.empty((L, 9), device=dev, dtype=torch.int64) if out is None else _check("out", out, torch.int64, (L, 9))
     ws = torch.empty((max(L * F, 1), 9), device=dev, dtype=torch.int64)
+    tail = (C.c_double(float(lambda_l2)), C.c_int64(int(min_data_in_leaf)), C.c_double(float(min_sum_hessian_in_leaf)),
+            C.c_double(float(min_gain_to_split)), _lib.ptr(ws), _lib.ptr(rec), _lib.current_stream(dev))
     with torch.cuda.device(dev):
-        _lib.call("ptr_gbdt_best_split", _lib.ptr(hist), L, F, max_bin, _lib.ptr(nbins), _lib.ptr(expo), C.c_double(float(lambda_l2)),
-                  C.c_int64(int(min_data_in_leaf)), C.c_double(float(min_sum_hessian_in_leaf)), C.c_double(float(min_gain_to_split)), _lib.ptr(ws),
-                  _lib.ptr(rec), _lib.current_stream(dev))
+        if nan_bin is None:
+            _lib.call("ptr_gbdt_best_split", _lib.ptr(hist), L, F, max_bin, _lib.ptr(nbins), _lib.ptr(expo), *tail)
+        else:
+            _lib.call("ptr_gbdt_best_split_missing", _lib.ptr(hist), L, F, max_bin, _lib.ptr(nbins), _lib.ptr(_gbdt_nan_bin(nan_bin, F)), _lib.ptr(expo), *tail)
     return rec
 
 
-def gbdt_partition(bins, rows, feature, bin, F, out=None, left_count=None):
+def gbdt_partition(bins, rows, feature, bin, F, out=None, left_count=None, also_left=None):
     """Stable partition of a row list by bins[row, feature] <= bin -> (out int32 [m]: the left rows in their order, then the right rows in
-    theirs; left_count int32 [1] on the device)."""
+    theirs; left_count int32 [1] on the device).  also_left: one more bin that goes left (the NaN bin of a split whose missing rows go
+    left), or -1 (ptr_gbdt_partition_missing)."""
     bins = _gbdt_bins(bins, F)
     dev = bins.device
     rows = _check("rows", rows, torch.int32)
@@ -1074,8 +1087,12 @@ def gbdt_partition(bins, rows, feature, bin, F, out=None, left_count=None):
     left_count = torch.empty(1, device=dev, dtype=torch.int32) if left_count is None else _check("left_count", left_count, torch.int32, (1,))
     ws = torch.empty(int(_lib.query("ptr_gbdt_partition_ws_ints", m)), device=dev, dtype=torch.int32)
     with torch.cuda.device(dev):
-        _lib.call("ptr_gbdt_partition", _lib.ptr(bins), bins.shape[1], bins.shape[0], F, _lib.ptr(rows), m, int(feature), int(bin), _lib.ptr(out),
-                  _lib.ptr(left_count), _lib.ptr(ws), _lib.current_stream(dev))
+        if also_left is None:
+            _lib.call("ptr_gbdt_partition", _lib.ptr(bins), bins.shape[1], bins.shape[0], F, _lib.ptr(rows), m, int(feature), int(bin), _lib.ptr(out),
+                      _lib.ptr(left_count), _lib.ptr(ws), _lib.current_stream(dev))
+        else:
+            _lib.call("ptr_gbdt_partition_missing", _lib.ptr(bins), bins.shape[1], bins.shape[0], F, _lib.ptr(rows), m, int(feature), int(bin),
+                      int(also_left), _lib.ptr(out), _lib.ptr(left_count), _lib.ptr(ws), _lib.current_stream(dev))
     return out, left_count
 
 
@@ -1094,10 +1111,11 @@ def gbdt_add_leaf_values(scores, rows, offsets, values):
     return scores
 
 
-def gbdt_predict(X, feature, threshold, left, right, value, tree_offsets, ntrees=None):
+def gbdt_predict(X, feature, threshold, left, right, value, tree_offsets, ntrees=None, default_left=None):
     """Scores of raw rows under flat tree arrays -> float32 [n]: per tree the row goes left on x <= threshold; a negative child is leaf ~i;
     tree t owns the nodes tree_offsets[t] .. tree_offsets[t + 1] and the values value[tree_offsets[t] + t ..].  The leaf values are summed
-    in tree order in fp32.  ntrees: only the first trees."""
+    in tree order in fp32.  ntrees: only the first trees.  default_left (uint8 [nodes]): a NaN feature goes left where the node's byte is
+    set, right otherwise (ptr_gbdt_predict_missing)."""
     X = _check("X", X)
     if X.dim() != 2:
         raise ValueError(f"X must be [rows, features], got {tuple(X.shape)}")
@@ -1113,8 +1131,13 @@ def gbdt_predict(X, feature, threshold, left, right, value, tree_offsets, ntrees
     value = _check("value", value, shape=(nodes + total,))
     out = torch.empty(X.shape[0], device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _lib.call("ptr_gbdt_predict", _lib.ptr(X), X.shape[0], X.shape[1], _lib.ptr(feature), _lib.ptr(threshold), _lib.ptr(left), _lib.ptr(right),
-                  _lib.ptr(value), _lib.ptr(tree_offsets), ntrees, _lib.ptr(out), _lib.current_stream(dev))
+        if default_left is None:
+            _lib.call("ptr_gbdt_predict", _lib.ptr(X), X.shape[0], X.shape[1], _lib.ptr(feature), _lib.ptr(threshold), _lib.ptr(left), _lib.ptr(right),
+                      _lib.ptr(value), _lib.ptr(tree_offsets), ntrees, _lib.ptr(out), _lib.current_stream(dev))
+        else:
+            default_left = _check("default_left", default_left, torch.uint8, (nodes,))
+            _lib.call("ptr_gbdt_predict_missing", _lib.ptr(X), X.shape[0], X.shape[1], _lib.ptr(feature), _lib.ptr(threshold), _lib.ptr(left),
+                      _lib.ptr(right), _lib.ptr(value), _lib.ptr(tree_offsets), _lib.ptr(default_left), ntrees, _lib.ptr(out), _lib.current_stream(dev))
     return out
 
 
@@ -1198,9 +1221,10 @@ def gbdt_hist_sub_segments(pool, trips):
     return pool
 
 
-def gbdt_best_split_slots(pool, slots, nbins, expo, lambda_l2=0.0, min_data_in_leaf=1, min_sum_hessian_in_leaf=1e-3, min_gain_to_split=0.0, out=None):
+def gbdt_best_split_slots(pool, slots, nbins, expo, lambda_l2=0.0, min_data_in_leaf=1, min_sum_hessian_in_leaf=1e-3, min_gain_to_split=0.0, out=None,
+                          nan_bin=None):
     """gbdt_best_split over the histograms pool[slots[k]] (slots: a host list) -> int64 [K, 9] records, each bit-identical to gbdt_best_split
-    on a copy of that slot.  A slot outside the pool gives the record without a split."""
+    on a copy of that slot.  A slot outside the pool gives the record without a split.  nan_bin: as gbdt_best_split."""
     pool = _gbdt_pool(pool)
     dev, F, max_bin = pool.device, pool.shape[1], pool.shape[2]
     nbins = _check("nbins", nbins, torch.int32, (F,))
@@ -1209,24 +1233,29 @@ def gbdt_best_split_slots(pool, slots, nbins, expo, lambda_l2=0.0, min_data_in_l
     K = host.shape[0]
     rec = torch.empty((K, 9), device=dev, dtype=torch.int64) if out is None else _check("out", out, torch.int64, (K, 9))
     ws = torch.empty((max(K * F, 1), 9), device=dev, dtype=torch.int64)
+    tail = (C.c_double(float(lambda_l2)), C.c_int64(int(min_data_in_leaf)), C.c_double(float(min_sum_hessian_in_leaf)),
+            C.c_double(float(min_gain_to_split)), _lib.ptr(ws), _lib.ptr(rec), _lib.current_stream(dev))
     with torch.cuda.device(dev):
-        _lib.call("ptr_gbdt_best_split_slots", _lib.ptr(pool), pool.shape[0], _lib.ptr(slots_d), K, F, max_bin, _lib.ptr(nbins), _lib.ptr(expo),
-                  C.c_double(float(lambda_l2)), C.c_int64(int(min_data_in_leaf)), C.c_double(float(min_sum_hessian_in_leaf)),
-                  C.c_double(float(min_gain_to_split)), _lib.ptr(ws), _lib.ptr(rec), _lib.current_stream(dev))
+        if nan_bin is None:
+            _lib.call("ptr_gbdt_best_split_slots", _lib.ptr(pool), pool.shape[0], _lib.ptr(slots_d), K, F, max_bin, _lib.ptr(nbins), _lib.ptr(expo), *tail)
+        else:
+            _lib.call("ptr_gbdt_best_split_slots_missing", _lib.ptr(pool), pool.shape[0], _lib.ptr(slots_d), K, F, max_bin, _lib.ptr(nbins),
+                      _lib.ptr(_gbdt_nan_bin(nan_bin, F)), _lib.ptr(expo), *tail)
     return rec
 
 
-def gbdt_partition_segments(bins, rows, segs, F, out=None, left_counts=None):
+def gbdt_partition_segments(bins, rows, segs, F, out=None, left_counts=None, also_left=False):
     """Stable partition of every segment (start, count, feature, bin) of the host table segs [K, 4] (disjoint) inside the row list `rows`, as
     gbdt_partition would do each -> (out int32 like rows: a whole row list, the positions outside every segment copied; left_counts int32
     [K] on the device).  A fixed number of launches however many segments; out must not be rows.  A segment that leaves the row list or
-    names a feature or bin out of range is left as it was."""
+    names a feature or bin out of range is left as it was.  also_left=True: segs is [K, 5], the fifth column one more bin that goes left
+    or -1, as gbdt_partition's also_left (ptr_gbdt_partition_segments_missing)."""
     bins = _gbdt_bins(bins, F)
     dev = bins.device
     rows = _check("rows", rows, torch.int32)
     if rows.dim() != 1:
         raise ValueError(f"rows must be flat, got {tuple(rows.shape)}")
-    host, segs_d = _gbdt_table("segs", segs, 4, dev)
+    host, segs_d = _gbdt_table("segs", segs, 5 if also_left else 4, dev)
     K = host.shape[0]
     out = torch.empty_like(rows) if out is None else _check("out", out, torch.int32, tuple(rows.shape))
     left_counts = torch.zeros(K, device=dev, dtype=torch.int32) if left_counts is None else _check("left_counts", left_counts, torch.int32, (K,))
@@ -1238,7 +1267,7 @@ def gbdt_partition_segments(bins, rows, segs, F, out=None, left_counts=None):
     ws_ints = int(_lib.query("ptr_gbdt_partition_segments_ws_ints", C.c_int64(int(seg.size))))
     ws = torch.empty(ws_ints, device=dev, dtype=torch.int32)
     with torch.cuda.device(dev):
-        _lib.call("ptr_gbdt_partition_segments", _lib.ptr(bins), bins.shape[1], bins.shape[0], F, _lib.ptr(rows), rows.numel(), _lib.ptr(segs_d), K,
+        _lib.call("ptr_gbdt_partition_segments_missing" if also_left else "ptr_gbdt_partition_segments", _lib.ptr(bins), bins.shape[1], bins.shape[0], F, _lib.ptr(rows), rows.numel(), _lib.ptr(segs_d), K,
                   _lib.ptr(blocks_d), int(seg.size), _lib.ptr(out), _lib.ptr(left_counts), _lib.ptr(ws), ws_ints, _lib.current_stream(dev))
     return out, left_counts
 
@@ -1318,10 +1347,11 @@ def gbdt_partition_mask(mask, rows=None, m=None, out=None, left_count=None):
     return out, left_count
 
 
-def gbdt_add_tree_binned(scores, bins, F, rows, feature, bin, left, right, value):
+def gbdt_add_tree_binned(scores, bins, F, rows, feature, bin, left, right, value, also_left=None):
     """scores[row] += the leaf value one tree gives the BINNED row, for every row of `rows` (int32, distinct; None: all rows), in place.
     The tree as gbdt_predict takes one, with the split bins (int32 [nodes]) in place of the thresholds: left on bins[row, feature] <= bin,
-    which is x <= edges[feature, bin], so the value is gbdt_predict's for the raw row.  value float32 [nodes + 1]."""
+    which is x <= edges[feature, bin], so the value is gbdt_predict's for the raw row.  value float32 [nodes + 1].  also_left (int32
+    [nodes]): per node one more bin that goes left, or -1 (ptr_gbdt_add_tree_binned_missing)."""
     scores = _check("scores", scores)
     bins = _gbdt_bins(bins, F)
     n, dev = bins.shape[0], bins.device
@@ -1335,6 +1365,12 @@ def gbdt_add_tree_binned(scores, bins, F, rows, feature, bin, left, right, value
     feature, bin, left, right = (_check(k, t, torch.int32, (nodes,)) for k, t in zip(("feature", "bin", "left", "right"), (feature, bin, left, right)))
     value = _check("value", value, shape=(nodes + 1,))
     with torch.cuda.device(dev):
-        _lib.call("ptr_gbdt_add_tree_binned", _lib.ptr(scores), _lib.ptr(bins), bins.shape[1], n, F, _lib.ptr(rows), n if rows is None else rows.numel(),
-                  _lib.ptr(feature), _lib.ptr(bin), _lib.ptr(left), _lib.ptr(right), _lib.ptr(value), nodes, _lib.current_stream(dev))
+        if also_left is None:
+            _lib.call("ptr_gbdt_add_tree_binned", _lib.ptr(scores), _lib.ptr(bins), bins.shape[1], n, F, _lib.ptr(rows), n if rows is None else rows.numel(),
+                      _lib.ptr(feature), _lib.ptr(bin), _lib.ptr(left), _lib.ptr(right), _lib.ptr(value), nodes, _lib.current_stream(dev))
+        else:
+            also_left = _check("also_left", also_left, torch.int32, (nodes,))
+            _lib.call("ptr_gbdt_add_tree_binned_missing", _lib.ptr(scores), _lib.ptr(bins), bins.shape[1], n, F, _lib.ptr(rows),
+                      n if rows is None else rows.numel(), _lib.ptr(feature), _lib.ptr(bin), _lib.ptr(left), _lib.ptr(right), _lib.ptr(value),
+                      _lib.ptr(also_left), nodes, _lib.current_stream(dev))
     return scores

@@ -30,9 +30,19 @@ value all run on the device; the size of the bag reaches the host in the one rea
 host_reads does not grow, and booster.scores stays predict(X) bit for bit for every row.  Without sampling update() issues exactly the
 calls it issued before these parameters existed.
 
+Missing values (use_missing, LightGBM's name).  The default here is False: a NaN raises in bin_edges, in predict and for the eval_set of
+LambdaMART.fit, and every call is the one made before the switch existed.  LightGBM's own default is True.  Under use_missing=True a NaN
+is a missing value (an infinity still raises): a feature that holds one in the training matrix keeps a NaN bin behind its value bins
+(bin_edges gives it at most max_bin - 1 of those), the split scan tries every threshold with the missing rows on the right and, where
+the node holds missing rows, also the NaNs against all values and every threshold with them on the left, and each node keeps the
+direction that won (default_left), or the side of the larger child where its rows do not decide.  predict sends a NaN along default_left.
+The rules are scikit-learn's wherever its are deterministic, and whole fits on data with NaNs are pinned to HistGradientBoostingRegressor
+node for node (tests/golden/gbdt_sklearn_missing.npz; include/ptranking_amd.h states the rules, tests/gbdt_missing_ref.py restates
+them).  Such a model is saved as format 2 (format 1 with default_left per node and nan_bin per feature); a model without the switch saves
+the format-1 file it always did.  Not here: zero_as_missing, and the LETOR loader's absent features, which stay zeros.
+
 Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here:
-feature_fraction, EFB, categorical features, missing values (a non-finite feature raises: in bin_edges, in predict and for the eval_set of
-LambdaMART.fit), DART, monotone constraints.  There is no CPU path.
+feature_fraction, EFB, categorical features, DART, monotone constraints.  There is no CPU path.
 """
 import json
 
@@ -49,9 +59,10 @@ __all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS"
 DEFAULT_PARAMS = {"learning_rate": 0.1, "num_leaves": 31, "num_trees": 100, "min_data_in_leaf": 20, "min_sum_hessian_in_leaf": 1e-3,
                   "lambda_l2": 0.0, "min_gain_to_split": 0.0, "max_bin": 255, "max_depth": -1, "grow_policy": "leafwise",
                   "bagging_fraction": 1.0, "bagging_freq": 0, "bagging_seed": 3, "bagging_by_query": False, "data_sample_strategy": "bagging",
-                  "top_rate": 0.2, "other_rate": 0.1}
+                  "top_rate": 0.2, "other_rate": 0.1, "use_missing": False}
 IGNORED_PARAMS = ("num_threads", "verbosity", "metric", "boosting_type", "objective", "eval_at")    # accepted, without a meaning here
-MODEL_FORMAT = 1
+MODEL_FORMAT = 1                       # a model trained without use_missing
+MODEL_FORMAT_MISSING = 2               # one trained under it: format 1 with default_left per node and nan_bin per feature
 GROW_POLICIES = ("leafwise", "depthwise")
 SAMPLE_STRATEGIES = ("bagging", "goss")
 
@@ -83,10 +94,11 @@ def _params(params):
         raise ValueError("lambda_l2 must be >= 0 and no threshold may be NaN")
     for k in ("bagging_fraction", "top_rate", "other_rate"):
         p[k] = float(p[k])
-    if isinstance(p["bagging_by_query"], (bool, np.bool_)):
-        p["bagging_by_query"] = bool(p["bagging_by_query"])
-    else:
-        raise ValueError(f"bagging_by_query must be True or False, got {p['bagging_by_query']!r}")
+    for k in ("bagging_by_query", "use_missing"):
+        if isinstance(p[k], (bool, np.bool_)):
+            p[k] = bool(p[k])
+        else:
+            raise ValueError(f"{k} must be True or False, got {p[k]!r}")
     if int(p["bagging_freq"]) != p["bagging_freq"] or int(p["bagging_seed"]) != p["bagging_seed"]:
         raise ValueError("bagging_freq and bagging_seed must be integers")
     p["bagging_freq"], p["bagging_seed"] = int(p["bagging_freq"]), int(p["bagging_seed"])
@@ -113,6 +125,7 @@ def sampling(p):
 
 
 _NONFINITE = "X holds a NaN or an infinity: missing values are not handled, impute them first"
+_INFINITE = "X holds an infinity: under use_missing a NaN is a missing value, an infinity is not handled"
 
 
 def _require_finite(Xd):
@@ -122,39 +135,59 @@ def _require_finite(Xd):
         raise ValueError(_NONFINITE)
 
 
+def _require_no_infinity(Xd):
+    """The check under use_missing, where a NaN passes: raises for an infinity in a device matrix; one reduction and one host read."""
+    if Xd.numel() and bool(torch.isinf(Xd).any().cpu()):
+        raise ValueError(_INFINITE)
+
+
 def _midpoints(lo, hi):
     """An fp32 edge e with lo <= e < hi for adjacent distinct fp32 values: the midpoint, or lo where the midpoint rounds up to hi."""
     mid = ((lo.astype(np.float64) + hi.astype(np.float64)) * 0.5).astype(np.float32)
     return np.where(mid >= hi, lo, mid)
 
 
-def bin_edges(X, max_bin):
+def bin_edges(X, max_bin, use_missing=False):
     """The binning rule, on the host, once per dataset -> (edges float32 [F, max_bin - 1], padded with +inf; nbins int32 [F]).
     Per feature: at most max_bin distinct values give one bin per value, the edges at the midpoints (binning is then lossless).  Otherwise
     the k-th edge (k = 1 .. max_bin - 1) follows the first distinct value whose cumulative row count reaches k n / max_bin, again at the
-    midpoint to the next distinct value; edges that coincide are kept once.  Deterministic: no subsampling."""
+    midpoint to the next distinct value; edges that coincide are kept once.  Deterministic: no subsampling.
+    use_missing=True -> (edges, nbins, nan_bin int32 [F]): a NaN is a missing value and takes no part in the rule (the distinct values, the
+    counts and n are those of the feature's other rows).  A feature that holds one is binned under max_bin - 1 in place of max_bin, and
+    its NaNs get the bin behind its value bins, nan_bin[f] = nbins[f] (nbins counts value bins only); a feature without a NaN has
+    nan_bin[f] = -1 and the edges it has without the switch.  An infinity raises either way."""
     X = np.asarray(X, dtype=np.float32)
     if X.ndim != 2:
         raise ValueError(f"X must be [rows, features], got {X.shape}")
-    if not np.isfinite(X).all():
+    if use_missing:
+        if np.isinf(X).any():
+            raise ValueError(_INFINITE)
+    elif not np.isfinite(X).all():
         raise ValueError(_NONFINITE)
-    n, nf = X.shape
+    nf = X.shape[1]
     edges = np.full((nf, max_bin - 1), np.inf, np.float32)
     nbins = np.ones(nf, np.int32)
+    nan_bin = np.full(nf, -1, np.int32)
     for f in range(nf):
-        vals, counts = np.unique(X[:, f], return_counts=True)
-        if vals.size <= 1:
-            continue
-        if vals.size <= max_bin:
-            cut = np.arange(vals.size - 1)
-        else:
-            cum = np.cumsum(counts)
-            cut = np.unique(np.searchsorted(cum, np.arange(1, max_bin) * (n / max_bin), side="left"))
-            cut = cut[cut < vals.size - 1]
-        e = _midpoints(vals[cut], vals[cut + 1])
-        edges[f, :e.size] = e
-        nbins[f] = e.size + 1
-    return edges, nbins
+        col = X[:, f]
+        cap = max_bin
+        if use_missing and np.isnan(col).any():
+            col, cap = col[~np.isnan(col)], max_bin - 1
+        n = col.size
+        vals, counts = np.unique(col, return_counts=True)
+        if vals.size > 1:
+            if vals.size <= cap:
+                cut = np.arange(vals.size - 1)
+            else:
+                cum = np.cumsum(counts)
+                cut = np.unique(np.searchsorted(cum, np.arange(1, cap) * (n / cap), side="left"))
+                cut = cut[cut < vals.size - 1]
+            e = _midpoints(vals[cut], vals[cut + 1])
+            edges[f, :e.size] = e
+            nbins[f] = e.size + 1
+        if cap < max_bin:
+            nan_bin[f] = nbins[f]
+    return (edges, nbins, nan_bin) if use_missing else (edges, nbins)
 
 
 def leaf_value(g_sum, h_sum, expo, lambda_l2, learning_rate):
@@ -189,6 +222,8 @@ class GBDT:
         self.params = _params(params)
         self.trees = []                    # per tree: dict(feature, threshold, left, right, value) of numpy arrays
         self.edges = self.nbins = None     # host copies (the model file carries them)
+        self.nan_bin = None                # under use_missing: the NaN bin per feature, -1 where training saw no NaN
+        self._nan_bin_d = None
         self.best_iteration = None
         self._device = device
         self._flat = None
@@ -217,11 +252,15 @@ class GBDT:
         host = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
         host = np.ascontiguousarray(host, dtype=np.float32)
         p = self.params
-        self.edges, self.nbins = bin_edges(host, p["max_bin"])
+        if p["use_missing"]:
+            self.edges, self.nbins, self.nan_bin = bin_edges(host, p["max_bin"], True)
+        else:
+            self.edges, self.nbins = bin_edges(host, p["max_bin"])
         Xd = X.detach().to(dev, torch.float32).contiguous() if isinstance(X, torch.Tensor) else torch.from_numpy(host).to(dev)
         self.n, self.F = host.shape
         self._edges_d, self._nbins_d = torch.from_numpy(self.edges).to(dev), torch.from_numpy(self.nbins).to(dev)
-        self.bins = F.gbdt_bin(Xd, self._edges_d, self._nbins_d)
+        self._nan_bin_d = torch.from_numpy(self.nan_bin).to(dev) if p["use_missing"] else None
+        self.bins = F.gbdt_bin(Xd, self._edges_d, self._nbins_d, nan_bin=self._nan_bin_d)
         n = self.n
         self.scores = torch.zeros(n, device=dev, dtype=torch.float32)
         self._arange = torch.arange(n, device=dev, dtype=torch.int32)
@@ -267,7 +306,7 @@ class GBDT:
     def _search(self, slot, out_row):
         p = self.params
         F.gbdt_best_split(self._pool[slot:slot + 1], self._nbins_d, self._expo, p["lambda_l2"], p["min_data_in_leaf"], p["min_sum_hessian_in_leaf"],
-                          p["min_gain_to_split"], out=self._rec[out_row:out_row + 1])
+                          p["min_gain_to_split"], out=self._rec[out_row:out_row + 1], nan_bin=self._nan_bin_d)
 
     def _splittable(self, count, depth):
         p = self.params
@@ -303,12 +342,13 @@ class GBDT:
         expo = (int(head[12]), int(head[13]))
         bag = self.n if sampled is None else int(head[11])             # the root's row count: the size of the bag
         if p["grow_policy"] == "depthwise":
-            feature, threshold, left, right, starts, g_sum, h_sum, split_bin = self._grow_depthwise(head, bag, sampled is not None)
+            feature, threshold, left, right, starts, g_sum, h_sum, split_bin, go_left = self._grow_depthwise(head, bag, sampled is not None)
             value = np.array([leaf_value(g, h, expo, p["lambda_l2"], p["learning_rate"]) for g, h in zip(g_sum, h_sum)], np.float32)
-            return self._finish(feature, threshold, left, right, starts, value, bag, split_bin)
+            return self._finish(feature, threshold, left, right, starts, value, bag, split_bin, go_left)
         root_rec = _record(head[:9]) if self._splittable(bag, 0) else _NO_SPLIT
         leaves = [_Leaf(0, bag, 0, 0, -1, 0, int(head[9]), int(head[10]), root_rec)]
-        feature, threshold, left, right, split_bin = [], [], [], [], []
+        feature, threshold, left, right, split_bin, go_left = [], [], [], [], [], []
+        missing = p["use_missing"]
         if sampled is None:
             self._rows.copy_(self._arange)
         free = 1                                                       # the next unused histogram slot
@@ -319,7 +359,11 @@ class GBDT:
             if not gain > -np.inf:
                 break
             s, m = leaf.start, leaf.count
-            F.gbdt_partition(self.bins, self._rows[s:s + m], f, b, nf, out=self._tmp[s:s + m], left_count=self._lc)
+            if missing:                                                    # field 2 of a record of the missing scan: bin + 256 * default_left
+                dl, b = b >> 8, b & 255
+                go_left.append(dl)
+            F.gbdt_partition(self.bins, self._rows[s:s + m], f, b, nf, out=self._tmp[s:s + m], left_count=self._lc,
+                             also_left=(int(self.nan_bin[f]) if dl else -1) if missing else None)
             self._rows[s:s + m].copy_(self._tmp[s:s + m])
             node = len(feature)
             feature.append(f); threshold.append(self.edges[f, b]); left.append(~li); right.append(~len(leaves)); split_bin.append(b)
@@ -345,23 +389,28 @@ class GBDT:
                     if can[k]:
                         c.rec = _record(recs[k])
         value = np.array([leaf_value(c.g, c.h, expo, p["lambda_l2"], p["learning_rate"]) for c in leaves], np.float32)
-        return self._finish(feature, threshold, left, right, [c.start for c in leaves], value, bag, split_bin)
+        return self._finish(feature, threshold, left, right, [c.start for c in leaves], value, bag, split_bin, go_left)
 
-    def _finish(self, feature, threshold, left, right, starts, value, m, split_bin):
+    def _finish(self, feature, threshold, left, right, starts, value, m, split_bin, go_left=()):
         """Adds the leaf values (by leaf index, with the leaves' first positions in the row list) to the training scores; keeps the tree.
         The tree grew on the first m entries of the row list: the rows behind them (outside a sampled tree's bag) are walked through the
         tree on their bins and get the same fp32 leaf value, so the scores stay predict(X) bit for bit.  split_bin, the split bins by node,
-        serves that one call and is not part of the model."""
+        serves that one call and is not part of the model.  go_left (use_missing): default_left by node, kept with the tree; in the walk
+        a node's NaN bin goes left with it."""
         order = sorted(range(len(starts)), key=lambda i: starts[i])
         offsets = np.array([starts[i] for i in order] + [m], np.int32)
         dev = self.scores.device
         F.gbdt_add_leaf_values(self.scores, self._rows, torch.from_numpy(offsets).to(dev), torch.from_numpy(value[order]).to(dev))
         t = {"feature": np.array(feature, np.int32), "threshold": np.array(threshold, np.float32), "left": np.array(left, np.int32),
              "right": np.array(right, np.int32), "value": value}
+        also = None
+        if self.params["use_missing"]:
+            t["default_left"] = np.array(go_left, np.uint8).reshape(-1)
+            also = np.where(t["default_left"] != 0, self.nan_bin[t["feature"]], -1)
         if m < self.n:
             up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
             F.gbdt_add_tree_binned(self.scores, self.bins, self.F, self._rows[m:], up(t["feature"], np.int32), up(split_bin, np.int32), up(t["left"], np.int32),
-                                   up(t["right"], np.int32), up(value, np.float32))
+                                   up(t["right"], np.int32), up(value, np.float32), also_left=None if also is None else up(also, np.int32))
         self.trees.append(t)
         self._flat = None
         return t
@@ -370,13 +419,15 @@ class GBDT:
         """Depth-wise growth from the root's record (head, as update read it): every level is one batched pass over all its leaves
         (partition, histograms of the smaller children, sibling subtraction, split scan) and ONE host read, the records of the level's
         searched children.  The root is the first m entries of the row list (a sampled tree's bag, which update has put there: `sampled`).
-        -> (feature, threshold, left, right, the leaves' first positions, their sums qg and qh, the split bins), by node / leaf index."""
+        -> (feature, threshold, left, right, the leaves' first positions, their sums qg and qh, the split bins, default_left (zeros without
+        use_missing)), by node / leaf index."""
         p, nf, mb, cap = self.params, self.F, self.params["max_bin"], self.params["num_leaves"]
         pool = self._pool
         min_count, max_depth = 2 * max(p["min_data_in_leaf"], 1), p["max_depth"]
         splittable = lambda count, depth: (count >= min_count) & (max_depth <= 0 or depth < max_depth)      # _splittable over a level
         feature, threshold = np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.float32)
         left, right, split_bin = np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.int32)
+        go_left, missing = np.zeros(max(cap - 1, 0), np.uint8), p["use_missing"]
         starts, g_sum, h_sum = np.zeros(cap, np.int64), np.zeros(cap, np.int64), np.zeros(cap, np.int64)
         g_sum[0], h_sum[0] = head[9], head[10]
         nodes, leaves, free, depth = 0, 1, 1, 0
@@ -397,13 +448,19 @@ class GBDT:
             k = keep.size
             f, b, lsum, rsum = rec[keep, 1], rec[keep, 2], rec[keep, 3:6], rec[keep, 6:9]
             node = nodes + np.arange(k)
+            if missing:                                                    # field 2 of a record of the missing scan: bin + 256 * default_left
+                go_left[node], b = b >> 8, b & 255
             feature[node], threshold[node], split_bin[node] = f, self.edges[f, b], b
             left[node], right[node] = ~leaf[keep], ~(leaves + np.arange(k))
             has = parent[keep] >= 0
             for arr, sd in ((left, 0), (right, 1)):
                 sel = has & (side[keep] == sd)
                 arr[parent[keep][sel]] = node[sel]
-            F.gbdt_partition_segments(self.bins, self._rows, np.stack([start[keep], count[keep], f, b], axis=1), nf, out=self._tmp)
+            if missing:
+                also = np.where(go_left[node] != 0, self.nan_bin[f], -1)
+                F.gbdt_partition_segments(self.bins, self._rows, np.stack([start[keep], count[keep], f, b, also], axis=1), nf, out=self._tmp, also_left=True)
+            else:
+                F.gbdt_partition_segments(self.bins, self._rows, np.stack([start[keep], count[keep], f, b], axis=1), nf, out=self._tmp)
             self._rows, self._tmp = self._tmp, self._rows
             # the children, interleaved (left, right): ascending start again
             c_leaf = np.stack([leaf[keep], leaves + np.arange(k)], axis=1)
@@ -428,26 +485,30 @@ class GBDT:
                 sp, ss = np.nonzero(can[pairs])
                 out = self._lrec[:sp.size]
                 F.gbdt_best_split_slots(pool, c_slot[pairs[sp], ss], self._nbins_d, self._expo, p["lambda_l2"], p["min_data_in_leaf"],
-                                        p["min_sum_hessian_in_leaf"], p["min_gain_to_split"], out=out)
+                                        p["min_sum_hessian_in_leaf"], p["min_gain_to_split"], out=out, nan_bin=self._nan_bin_d)
                 c_rec[pairs[sp], ss] = out.cpu().numpy()                   # the one synchronisation of this level
                 self.host_reads += 1
             leaf, start, count, slot = c_leaf.reshape(-1), c_start.reshape(-1), c_count.reshape(-1), c_slot.reshape(-1)
             parent, side, rec = np.repeat(node, 2), np.tile(np.array([0, 1], np.int64), k), c_rec.reshape(-1, 9)
-        return feature[:nodes], threshold[:nodes], left[:nodes], right[:nodes], starts[:leaves].tolist(), g_sum[:leaves].tolist(), h_sum[:leaves].tolist(), split_bin[:nodes]
+        return feature[:nodes], threshold[:nodes], left[:nodes], right[:nodes], starts[:leaves].tolist(), g_sum[:leaves].tolist(), h_sum[:leaves].tolist(), split_bin[:nodes], go_left[:nodes]
 
     # ---- the model
     def flat(self):
         """The flat tree arrays ptr_gbdt_predict reads (numpy): feature, threshold, left, right, value, tree_offsets."""
         cat = lambda k, dt: np.concatenate([t[k] for t in self.trees]).astype(dt) if self.trees else np.zeros(0, dt)
         offs = np.concatenate([[0], np.cumsum([t["feature"].size for t in self.trees])]).astype(np.int32)
-        return {"feature": cat("feature", np.int32), "threshold": cat("threshold", np.float32), "left": cat("left", np.int32),
-                "right": cat("right", np.int32), "value": cat("value", np.float32), "tree_offsets": offs}
+        out = {"feature": cat("feature", np.int32), "threshold": cat("threshold", np.float32), "left": cat("left", np.int32),
+               "right": cat("right", np.int32), "value": cat("value", np.float32), "tree_offsets": offs}
+        if self.params["use_missing"]:
+            out["default_left"] = cat("default_left", np.uint8)
+        return out
 
     def predict(self, X, num_iteration=None, first_tree=0, check_finite=True):
         """Scores of raw rows X (numpy array or device tensor [n, F]) -> device float32 [n]: the trees first_tree .. num_iteration - 1
         (default: up to best_iteration when early stopping set it, else all), summed in tree order in fp32 — for a training row the bits of
         its resident training score.  A NaN or an infinity in X raises, as in bin_edges (a NaN would go right at every node, while binning
-        puts it left); the check costs one synchronisation, and check_finite=False skips it for a matrix the caller has already checked."""
+        puts it left); the check costs one synchronisation, and check_finite=False skips it for a matrix the caller has already checked.
+        A model trained under use_missing takes NaNs: at a node a NaN feature follows the node's default_left; an infinity still raises."""
         dev = self._dev()
         if self._flat is None:
             self._flat = {k: torch.from_numpy(v).to(dev) for k, v in self.flat().items()}
@@ -457,36 +518,51 @@ class GBDT:
             raise ValueError(f"trees {first_tree} .. {stop} of {len(self.trees)}")
         Xd = X.detach().to(dev, torch.float32) if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
         if check_finite:
-            _require_finite(Xd)
+            _require_no_infinity(Xd) if self.params["use_missing"] else _require_finite(Xd)
         if first_tree == 0:
-            return F.gbdt_predict(Xd, fl["feature"], fl["threshold"], fl["left"], fl["right"], fl["value"], fl["tree_offsets"], stop)
+            return F.gbdt_predict(Xd, fl["feature"], fl["threshold"], fl["left"], fl["right"], fl["value"], fl["tree_offsets"], stop,
+                                  default_left=fl.get("default_left"))
         host = self.flat()
         lo, hi = int(host["tree_offsets"][first_tree]), int(host["tree_offsets"][stop])
-        sub = {k: torch.from_numpy(np.ascontiguousarray(host[k][lo:hi])).to(dev) for k in ("feature", "threshold", "left", "right")}
+        sub = {k: torch.from_numpy(np.ascontiguousarray(host[k][lo:hi])).to(dev) for k in ("feature", "threshold", "left", "right", "default_left") if k in host}
         val = torch.from_numpy(np.ascontiguousarray(host["value"][lo + first_tree:hi + stop])).to(dev)
         offs = torch.from_numpy((host["tree_offsets"][first_tree:stop + 1] - lo).astype(np.int32)).to(dev)
-        return F.gbdt_predict(Xd, sub["feature"], sub["threshold"], sub["left"], sub["right"], val, offs)
+        return F.gbdt_predict(Xd, sub["feature"], sub["threshold"], sub["left"], sub["right"], val, offs, default_left=sub.get("default_left"))
 
     def save_model(self, path):
-        """An .npz of this project's own (not LightGBM's text format): the flat tree arrays, the bin edges, the parameters."""
+        """An .npz of this project's own (not LightGBM's text format): the flat tree arrays, the bin edges, the parameters.  Format 1
+        without use_missing (the file this method wrote before the switch existed: the switch is not among its parameters); format 2 under
+        it, with default_left per node and nan_bin per feature."""
+        if self.params["use_missing"]:
+            head = dict(format=np.int64(MODEL_FORMAT_MISSING), params=np.array(json.dumps(self.params)), edges=self.edges, nbins=self.nbins,
+                        nan_bin=np.full(0, -1, np.int32) if self.nan_bin is None else self.nan_bin)
+        else:
+            params = {k: v for k, v in self.params.items() if k != "use_missing"}
+            head = dict(format=np.int64(MODEL_FORMAT), params=np.array(json.dumps(params)), edges=self.edges, nbins=self.nbins)
         with open(path, "wb") as fh:
-            np.savez(fh, format=np.int64(MODEL_FORMAT), params=np.array(json.dumps(self.params)), edges=self.edges, nbins=self.nbins,
-                     best_iteration=np.int64(self.best_iteration or 0), **self.flat())
+            np.savez(fh, **head, best_iteration=np.int64(self.best_iteration or 0), **self.flat())
 
     @classmethod
     def load_model(cls, path, device=None):
         """The booster save_model wrote; it predicts the same bits.  (The binned training data are not part of a model.)"""
         with np.load(path, allow_pickle=False) as z:
-            if int(z["format"]) != MODEL_FORMAT:
-                raise ValueError(f"{path}: model format {int(z['format'])}, this version reads {MODEL_FORMAT}")
+            fmt = int(z["format"])
+            if fmt not in (MODEL_FORMAT, MODEL_FORMAT_MISSING):
+                raise ValueError(f"{path}: model format {fmt}, this version reads {MODEL_FORMAT} and {MODEL_FORMAT_MISSING}")
             self = cls(json.loads(str(z["params"])), device=device)
+            if self.params["use_missing"] != (fmt == MODEL_FORMAT_MISSING):
+                raise ValueError(f"{path}: model format {fmt} with use_missing={self.params['use_missing']}")
             self.edges, self.nbins = z["edges"], z["nbins"]
+            if fmt == MODEL_FORMAT_MISSING:
+                self.nan_bin = z["nan_bin"]
             self.best_iteration = int(z["best_iteration"]) or None
             offs = z["tree_offsets"]
             for t in range(offs.size - 1):
                 lo, hi = int(offs[t]), int(offs[t + 1])
                 self.trees.append({"feature": z["feature"][lo:hi], "threshold": z["threshold"][lo:hi], "left": z["left"][lo:hi],
                                    "right": z["right"][lo:hi], "value": z["value"][lo + t:hi + t + 1]})
+                if fmt == MODEL_FORMAT_MISSING:
+                    self.trees[-1]["default_left"] = z["default_left"][lo:hi]
         return self
 
 
@@ -568,7 +644,7 @@ class LambdaMART:
             if eval_group is None:
                 raise ValueError("eval_set needs eval_group")
             Xv = Xv.detach().to(self.device, torch.float32) if isinstance(Xv, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(Xv, dtype=np.float32)).to(self.device)
-            _require_finite(Xv)                                                       # once, before the first round: the rounds skip it
+            _require_no_infinity(Xv) if self.params["use_missing"] else _require_finite(Xv)   # once, before the first round: the rounds skip it
             yv = torch.from_numpy(np.ascontiguousarray(np.asarray(yv).reshape(-1), dtype=np.float32)).to(self.device)
             valid = (Xv, yv, self.padded_index(eval_group, self.device), torch.zeros(Xv.shape[0], device=self.device, dtype=torch.float32))
         elif early_stopping_rounds is not None:
