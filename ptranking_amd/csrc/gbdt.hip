@@ -21,6 +21,12 @@
 //            and walks the 16 features ROTATED by its lane number: in one step the 64 lanes address 16 different features, so a constant
 //            feature (every row in one bin) meets 4 lanes per address and step, not 64.  The flush adds only the bins the chunk touched.
 //
+// One body per step.  The single-list and the batched (segment) kernels of a step differ only in how a workgroup finds its rows and its
+// destination; the work is a device function both call: gbdt_hist_tile (the LDS tile: zero, rotated walk, flush), hist_add_direct,
+// part_count and part_scatter under a predicate (PartByBin, PartByMask; a batched workgroup builds a PartByBin over its segment), one scan
+// kernel for both partitions on block_scan_add (goss_pick scans with it too), and gbdt_walk, to which the raw predictor and the binned walk
+// pass their comparison.
+//
 // Row sampling (bagging by row or by query, GOSS): a keep mask of one byte per row, the stable partition under the predicate mask[row], and
 // a walk of the finished tree over the binned rows outside the bag.  GOSS's threshold is the exact K-th largest |g h|: the keys are
 // non-negative floats, their uint32 bit patterns order as integers, and a radix select of three counting passes (digits of 11, 11 and 10
@@ -116,13 +122,9 @@ __device__ __forceinline__ void hist_add_global(int64_t *__restrict__ cell, int6
     atomicAdd(reinterpret_cast<u64 *>(cell + 2), (u64)c);
 }
 
-__global__ void __launch_bounds__(kBlock)
-gbdt_hist_direct_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg, const int32_t *__restrict__ qh,
-                        const int32_t *__restrict__ rows, int m, int F, int max_bin, int64_t *__restrict__ hist) {
-    const int e = blockIdx.x * kBlock + threadIdx.x;                    // m <= kGbdtDirectRows: m * stride fits an int
-    if (e >= m * stride) return;
-    const int i = e / stride, f = e - i * stride;
-    const int row = rows ? rows[i] : i;
+// The direct form's add of one (row, feature): a feature in the stride's padding, a row outside the matrix or a bin outside the histogram adds nothing.
+__device__ __forceinline__ void hist_add_direct(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg,
+                                                const int32_t *__restrict__ qh, int row, int f, int F, int max_bin, int64_t *__restrict__ hist) {
     if (f >= F || row < 0 || row >= n) return;
     const int b = bins[(size_t)row * stride + f];
     if (b >= max_bin) return;
@@ -130,20 +132,26 @@ gbdt_hist_direct_kernel(const uint8_t *__restrict__ bins, int stride, int n, con
 }
 
 __global__ void __launch_bounds__(kBlock)
-gbdt_hist_lds_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg, const int32_t *__restrict__ qh,
-                     const int32_t *__restrict__ rows, int m, int F, int max_bin, int64_t *__restrict__ hist) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char gbdt_smem[];
+gbdt_hist_direct_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg, const int32_t *__restrict__ qh,
+                        const int32_t *__restrict__ rows, int m, int F, int max_bin, int64_t *__restrict__ hist) {
+    const int e = blockIdx.x * kBlock + threadIdx.x;                    // m <= kGbdtDirectRows: m * stride fits an int
+    if (e >= m * stride) return;
+    const int i = e / stride, f = e - i * stride;
+    hist_add_direct(bins, stride, n, qg, qh, rows ? rows[i] : i, f, F, max_bin, hist);
+}
+
+// The LDS form of one workgroup: zeroes its tile [kGbdtTile][max_bin] of (int64, int64, int32) at `smem`, adds the entries [r0, r1) of the row
+// list (rows == NULL: the rows r0 .. r1 - 1 themselves) for the feature tile blockIdx.y, and flushes the bins it touched into hist
+// [F][max_bin][3].  Every thread of the workgroup calls it.
+__device__ __forceinline__ void gbdt_hist_tile(unsigned char *smem, const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg,
+                                               const int32_t *__restrict__ qh, const int32_t *__restrict__ rows, int64_t r0, int64_t r1, int F,
+                                               int max_bin, int64_t *__restrict__ hist) {
     const int cells = kGbdtTile * max_bin;
-    u64 *lg = reinterpret_cast<u64 *>(gbdt_smem), *lh = lg + cells;
+    u64 *lg = reinterpret_cast<u64 *>(smem), *lh = lg + cells;
     uint32_t *lc = reinterpret_cast<uint32_t *>(lh + cells);
     const int tid = threadIdx.x, f0 = blockIdx.y * kGbdtTile;
     for (int e = tid; e < cells; e += kBlock) { lg[e] = 0; lh[e] = 0; lc[e] = 0; }
     __syncthreads();
-
-    // this workgroup's rows: chunk c of gridDim.x, whole multiples of the block except the last
-    const int per = (int)((((int64_t)m + gridDim.x - 1) / gridDim.x + kBlock - 1) / kBlock) * kBlock;
-    const int64_t r0 = (int64_t)blockIdx.x * per;
-    const int64_t r1 = r0 + per < (int64_t)m ? r0 + per : (int64_t)m;
     const int nf = min(kGbdtTile, F - f0);
     for (int64_t i = r0 + tid; i < r1; i += kBlock) {
         const int row = rows ? rows[i] : (int)i;
@@ -171,6 +179,17 @@ gbdt_hist_lds_kernel(const uint8_t *__restrict__ bins, int stride, int n, const 
 }
 
 __global__ void __launch_bounds__(kBlock)
+gbdt_hist_lds_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg, const int32_t *__restrict__ qh,
+                     const int32_t *__restrict__ rows, int m, int F, int max_bin, int64_t *__restrict__ hist) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gbdt_smem[];
+    // this workgroup's rows: chunk c of gridDim.x, whole multiples of the block except the last
+    const int per = (int)((((int64_t)m + gridDim.x - 1) / gridDim.x + kBlock - 1) / kBlock) * kBlock;
+    const int64_t r0 = (int64_t)blockIdx.x * per;
+    const int64_t r1 = r0 + per < (int64_t)m ? r0 + per : (int64_t)m;
+    gbdt_hist_tile(gbdt_smem, bins, stride, n, qg, qh, rows, r0, r1, F, max_bin, hist);
+}
+
+__global__ void __launch_bounds__(kBlock)
 gbdt_hist_sub_kernel(const int64_t *__restrict__ parent, const int64_t *__restrict__ child, int64_t count, int64_t *__restrict__ out) {
     for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < count; e += (int64_t)gridDim.x * kBlock) out[e] = parent[e] - child[e];
 }
@@ -186,6 +205,9 @@ template <class T> __device__ __forceinline__ T wave_scan_add(T v, int lane) {  
 }
 
 struct SplitCand { double gain; int bin; int64_t gl, hl, cl; };
+
+// field 0 .. kRec - 1 of the record of a leaf without a split: gain -inf, feature and bin -1, no sums
+__device__ __forceinline__ int64_t gbdt_no_split(int field) { return field == 0 ? __double_as_longlong(-INFINITY) : field <= 2 ? -1 : 0; }
 
 // The gain of one candidate's left sums against the node's totals, or false where a validity rule rejects it.
 __device__ __forceinline__ bool gbdt_split_gain(int64_t gl, int64_t hl, int64_t cl, int64_t TG, int64_t TH, int64_t TC, int eg, int eh, double l2,
@@ -298,7 +320,7 @@ gbdt_split_feature_slots_kernel(const int64_t *__restrict__ pool, int nslots, co
     const int slot = slots[item / F];
     int64_t *r = ws + item * kRec;
     if (slot < 0 || slot >= nslots) {
-        if (lane < kRec) r[lane] = lane == 0 ? __double_as_longlong(-INFINITY) : lane <= 2 ? -1 : 0;
+        if (lane < kRec) r[lane] = gbdt_no_split(lane);
         return;
     }
     gbdt_split_scan<kMissing>(pool + ((int64_t)slot * F + f) * max_bin * 3, f, lane, max_bin, nbins, nan_bin, expo, l2, min_data, min_hess, min_gain, r);
@@ -322,27 +344,24 @@ gbdt_split_leaf_kernel(const int64_t *__restrict__ ws, int F, int64_t *__restric
         if (of >= 0 && (bf < 0 || og > bg || (og == bg && of < bf))) { bg = og; bf = of; }
     }
     if (lane < kRec) {
-        int64_t v = lane == 0 ? __double_as_longlong(-INFINITY) : lane <= 2 ? -1 : 0;
-        if (bf >= 0) v = w[(int64_t)bf * kRec + lane];
-        rec[(int64_t)blockIdx.x * kRec + lane] = v;
+        rec[(int64_t)blockIdx.x * kRec + lane] = bf >= 0 ? w[(int64_t)bf * kRec + lane] : gbdt_no_split(lane);
     }
 }
 
 // ---------------------------------------------------------------- the stable partition
-constexpr int kPartSteps = 4;                                           // a workgroup owns 4 x 256 consecutive entries of the list
+// A list is cut into pieces of kGbdtPartRows consecutive entries, one per workgroup, which walks its piece in kPartSteps steps of the block.
+constexpr int kPartSteps = kGbdtPartRows / kBlock;
+static_assert(kPartSteps * kBlock == kGbdtPartRows, "a workgroup of the partition owns whole steps of the block");
 
-__device__ __forceinline__ bool part_goes_left(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ rows, int64_t i, int m,
-                                               int feature, int bin, int also_left, int &row) {
-    row = i < m ? rows[i] : -1;
-    if (row < 0 || row >= n) return false;
-    const int b = bins[(size_t)row * stride + feature];
-    return b <= bin || b == also_left;                                  // also_left: the NaN bin of a split whose missing rows go left, or -1
-}
-
-// The predicates of the stable partition: pred(i, row) gives entry i's row (-1 past the list) and whether it goes to the front.
-struct PartByBin {                                                      // ptr_gbdt_partition: bins[row][feature] <= bin, or == also_left
+// The predicates of the stable partition: pred(i, row) gives entry i's row (-1 past the list of pred.m entries) and whether it goes to the front.
+struct PartByBin {                                                      // bins[row][feature] <= bin, or == also_left
     const uint8_t *bins; int stride, n; const int32_t *rows; int m, feature, bin, also_left;
-    __device__ __forceinline__ bool operator()(int64_t i, int &row) const { return part_goes_left(bins, stride, n, rows, i, m, feature, bin, also_left, row); }
+    __device__ __forceinline__ bool operator()(int64_t i, int &row) const {
+        row = i < m ? rows[i] : -1;
+        if (row < 0 || row >= n) return false;
+        const int b = bins[(size_t)row * stride + feature];
+        return b <= bin || b == also_left;                              // also_left: the NaN bin of a split whose missing rows go left, or -1
+    }
 };
 struct PartByMask {                                                     // ptr_gbdt_partition_mask: mask[row] != 0; rows == NULL: the list 0 .. m - 1
     const uint8_t *mask; int n; const int32_t *rows; int m;
@@ -352,48 +371,42 @@ struct PartByMask {                                                     // ptr_g
     }
 };
 
-template <class Pred> __global__ void __launch_bounds__(kBlock)
-gbdt_part_count_kernel(const Pred pred, int32_t *__restrict__ counts) {
+// Inclusive sums of one value per thread over the workgroup's kBlock threads, through buf [kBlock] in LDS.  A thread's last access to buf
+// is to its own entry, behind a barrier: the next call may use the same buf at once.
+template <class T> __device__ __forceinline__ T block_scan_add(T *buf, T v) {
+    const int t = threadIdx.x;
+    buf[t] = v;
+    __syncthreads();
+    for (int d = 1; d < kBlock; d <<= 1) {
+        const T o = t >= d ? buf[t - d] : 0;
+        __syncthreads();
+        buf[t] += o;
+        __syncthreads();
+    }
+    return buf[t];
+}
+
+// *count = the entries of piece j of pred's list that go to the front.  Every thread of the workgroup calls it.
+template <class Pred> __device__ __forceinline__ void part_count(const Pred &pred, int j, int32_t *__restrict__ count) {
     __shared__ int32_t tot;
     if (threadIdx.x == 0) tot = 0;
     __syncthreads();
     int c = 0, row;
     for (int s = 0; s < kPartSteps; ++s)
-        c += pred(((int64_t)blockIdx.x * kPartSteps + s) * kBlock + threadIdx.x, row) ? 1 : 0;
+        c += pred(((int64_t)j * kPartSteps + s) * kBlock + threadIdx.x, row) ? 1 : 0;
     atomicAdd(&tot, c);
     __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = tot;
+    if (threadIdx.x == 0) *count = tot;
 }
 
-// counts [nb] -> their exclusive prefix, in place; counts[nb] and left_count[0] = the total.  One workgroup.
-__global__ void __launch_bounds__(kBlock)
-gbdt_part_scan_kernel(int32_t *__restrict__ counts, int nb, int32_t *__restrict__ left_count) {
-    __shared__ int32_t seg[kBlock];
-    const int t = threadIdx.x, per = (nb + kBlock - 1) / kBlock;
-    const int lo = min(t * per, nb), hi = min(lo + per, nb);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += counts[i];
-    seg[t] = s;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const int o = t >= d ? seg[t - d] : 0;
-        __syncthreads();
-        seg[t] += o;
-        __syncthreads();
-    }
-    int run = seg[t] - s;
-    for (int i = lo; i < hi; ++i) { const int c = counts[i]; counts[i] = run; run += c; }
-    if (t == kBlock - 1) { counts[nb] = seg[t]; left_count[0] = seg[t]; }
-}
-
-template <class Pred> __global__ void __launch_bounds__(kBlock)
-gbdt_part_scatter_kernel(const Pred pred, const int32_t *__restrict__ counts, int nb, int32_t *__restrict__ out) {
+// Piece j of pred's list into out [pred.m]: left_before entries of the pieces ahead of it and total_left of the whole list go to the front.
+// An entry that goes to the front lands behind the front entries ahead of it, any other behind the front and the other entries ahead of
+// it: both orders are kept.  A position outside the list is not written (counts that do not belong to this list cannot leave it).
+template <class Pred> __device__ __forceinline__ void part_scatter(const Pred &pred, int j, int left_before, int total_left, int32_t *__restrict__ out) {
     __shared__ int32_t wave_left[kBlock / kWave];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    int left_before = counts[blockIdx.x];
-    const int total_left = counts[nb];
     for (int s = 0; s < kPartSteps; ++s) {
-        const int64_t i = ((int64_t)blockIdx.x * kPartSteps + s) * kBlock + threadIdx.x;
+        const int64_t i = ((int64_t)j * kPartSteps + s) * kBlock + threadIdx.x;
         int row;
         const bool left = pred(i, row);
         const unsigned long long mask = __ballot(left);
@@ -402,10 +415,37 @@ gbdt_part_scatter_kernel(const Pred pred, const int32_t *__restrict__ counts, in
         int before = left_before + __popcll(mask & ((1ull << lane) - 1));
         int step_left = 0;
         for (int w = 0; w < kBlock / kWave; ++w) { if (w < wave) before += wave_left[w]; step_left += wave_left[w]; }
-        if (i < pred.m) out[left ? before : total_left + (int)(i - before)] = row;     // `before` = the lefts ahead of entry i
+        const int64_t pos = left ? before : total_left + (i - before);                // `before` = the lefts ahead of entry i
+        if (i < pred.m && pos >= 0 && pos < pred.m) out[pos] = row;
         left_before += step_left;
         __syncthreads();
     }
+}
+
+template <class Pred> __global__ void __launch_bounds__(kBlock)
+gbdt_part_count_kernel(const Pred pred, int32_t *__restrict__ counts) { part_count(pred, blockIdx.x, counts + blockIdx.x); }
+
+// counts [nb] -> their exclusive prefix, in place; counts[nb], and left_count[0] where it is not NULL, = the total.  One workgroup.  The
+// batched partition scans the counts of all its segments at once and takes differences within a segment.
+__global__ void __launch_bounds__(kBlock)
+gbdt_part_scan_kernel(int32_t *__restrict__ counts, int nb, int32_t *__restrict__ left_count) {
+    __shared__ int32_t seg[kBlock];
+    const int t = threadIdx.x, per = (nb + kBlock - 1) / kBlock;
+    const int lo = min(t * per, nb), hi = min(lo + per, nb);
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += counts[i];
+    const int upto = block_scan_add(seg, s);
+    int run = upto - s;
+    for (int i = lo; i < hi; ++i) { const int c = counts[i]; counts[i] = run; run += c; }
+    if (t == kBlock - 1) {
+        counts[nb] = upto;
+        if (left_count) left_count[0] = upto;
+    }
+}
+
+template <class Pred> __global__ void __launch_bounds__(kBlock)
+gbdt_part_scatter_kernel(const Pred pred, const int32_t *__restrict__ counts, int nb, int32_t *__restrict__ out) {
+    part_scatter(pred, blockIdx.x, counts[blockIdx.x], counts[nb], out);
 }
 
 // ---------------------------------------------------------------- one level of a depth-wise tree: the batched forms
@@ -438,17 +478,11 @@ gbdt_hist_seg_direct_kernel(const uint8_t *__restrict__ bins, int stride, int n,
     if (!s.ok || r1 - r0 > kGbdtDirectRows) return;
     int64_t *hist = pool + (int64_t)s.slot * F * max_bin * 3;
     const int f0 = blockIdx.y * kGbdtTile, cnt = (int)(r1 - r0) * kGbdtTile;
-    for (int e = threadIdx.x; e < cnt; e += kBlock) {
-        const int f = f0 + (e & (kGbdtTile - 1));
-        const int row = rows[r0 + (e >> 4)];
-        if (f >= F || row < 0 || row >= n) continue;
-        const int b = bins[(size_t)row * stride + f];
-        if (b >= max_bin) continue;
-        hist_add_global(hist + ((size_t)f * max_bin + b) * 3, qg[row], qh[row], 1);
-    }
+    for (int e = threadIdx.x; e < cnt; e += kBlock)
+        hist_add_direct(bins, stride, n, qg, qh, rows[r0 + (e >> 4)], f0 + (e & (kGbdtTile - 1)), F, max_bin, hist);
 }
 
-// LDS form: grid = (items, feature tiles); an item is one row chunk of a segment.  The tile and the rotated walk of gbdt_hist_lds_kernel.
+// LDS form: grid = (items, feature tiles); an item is one row chunk of a segment
 __global__ void __launch_bounds__(kBlock)
 gbdt_hist_seg_lds_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg, const int32_t *__restrict__ qh,
                          const int32_t *__restrict__ rows, int64_t nrows, const int32_t *__restrict__ segs, int K,
@@ -457,37 +491,7 @@ gbdt_hist_seg_lds_kernel(const uint8_t *__restrict__ bins, int stride, int n, co
     int64_t r0 = 0, r1 = 0;
     const GbdtSeg s = gbdt_hist_item(segs, K, items + (int64_t)blockIdx.x * 3, nrows, nslots, r0, r1);
     if (!s.ok || r1 == r0) return;
-    int64_t *hist = pool + (int64_t)s.slot * F * max_bin * 3;
-    const int cells = kGbdtTile * max_bin;
-    u64 *lg = reinterpret_cast<u64 *>(gbdt_smem), *lh = lg + cells;
-    uint32_t *lc = reinterpret_cast<uint32_t *>(lh + cells);
-    const int tid = threadIdx.x, f0 = blockIdx.y * kGbdtTile;
-    for (int e = tid; e < cells; e += kBlock) { lg[e] = 0; lh[e] = 0; lc[e] = 0; }
-    __syncthreads();
-    const int nf = min(kGbdtTile, F - f0);
-    for (int64_t i = r0 + tid; i < r1; i += kBlock) {
-        const int row = rows[i];
-        if (row < 0 || row >= n) continue;
-        const uint4 bv = *reinterpret_cast<const uint4 *>(bins + (size_t)row * stride + f0);
-        const u64 g = (u64)(int64_t)qg[row], h = (u64)(int64_t)qh[row];
-#pragma unroll
-        for (int k = 0; k < kGbdtTile; ++k) {
-            const int f = (k + tid) & (kGbdtTile - 1);
-            const uint32_t w = (f >> 2) == 0 ? bv.x : (f >> 2) == 1 ? bv.y : (f >> 2) == 2 ? bv.z : bv.w;
-            const int b = (w >> ((f & 3) * 8)) & 0xff;
-            if (f < nf && b < max_bin) {
-                const int c = f * max_bin + b;
-                atomicAdd(&lg[c], g);
-                atomicAdd(&lh[c], h);
-                atomicAdd(&lc[c], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    for (int e = tid; e < nf * max_bin; e += kBlock) {
-        const uint32_t c = lc[e];
-        if (c) hist_add_global(hist + ((size_t)f0 * max_bin + e) * 3, (int64_t)lg[e], (int64_t)lh[e], (int64_t)c);
-    }
+    gbdt_hist_tile(gbdt_smem, bins, stride, n, qg, qh, rows, r0, r1, F, max_bin, pool + (int64_t)s.slot * F * max_bin * 3);
 }
 
 // trips [K][3] = (parent slot, child slot, out slot): grid = (K, chunks of one histogram)
@@ -523,72 +527,26 @@ __device__ __forceinline__ GbdtPartSeg gbdt_part_block(const int32_t *__restrict
 __global__ void __launch_bounds__(kBlock)
 gbdt_part_seg_count_kernel(const uint8_t *__restrict__ bins, int stride, int n, int F, const int32_t *__restrict__ rows, int64_t nrows,
                            const int32_t *__restrict__ segs, int cols, int K, const int32_t *__restrict__ blocks, int NB, int32_t *__restrict__ counts) {
-    __shared__ int32_t tot;
     int j;
     const GbdtPartSeg s = gbdt_part_block(segs, cols, K, blocks, blockIdx.x, NB, nrows, F, j);
     if (!s.ok) { if (threadIdx.x == 0) counts[blockIdx.x] = 0; return; }
-    if (threadIdx.x == 0) tot = 0;
-    __syncthreads();
-    int c = 0, row;
-    for (int st = 0; st < kPartSteps; ++st)
-        c += part_goes_left(bins, stride, n, rows + s.start, ((int64_t)j * kPartSteps + st) * kBlock + threadIdx.x, s.count, s.feature, s.bin, s.also_left, row) ? 1 : 0;
-    atomicAdd(&tot, c);
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = tot;
+    part_count(PartByBin{bins, stride, n, rows + s.start, s.count, s.feature, s.bin, s.also_left}, j, counts + blockIdx.x);
 }
 
-// counts [NB] -> their exclusive prefix over all blocks, in place, counts[NB] = the total: the scatter takes differences within a segment
-// (the lefts ahead of block b in its segment = prefix[b] - prefix[b - j]), which is the segmented scan.  One workgroup.
-__global__ void __launch_bounds__(kBlock)
-gbdt_part_seg_scan_kernel(int32_t *__restrict__ counts, int nb) {
-    __shared__ int32_t seg[kBlock];
-    const int t = threadIdx.x, per = (nb + kBlock - 1) / kBlock;
-    const int lo = min(t * per, nb), hi = min(lo + per, nb);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += counts[i];
-    seg[t] = s;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const int o = t >= d ? seg[t - d] : 0;
-        __syncthreads();
-        seg[t] += o;
-        __syncthreads();
-    }
-    int run = seg[t] - s;
-    for (int i = lo; i < hi; ++i) { const int c = counts[i]; counts[i] = run; run += c; }
-    if (t == kBlock - 1) counts[nb] = seg[t];
-}
-
+// counts: the exclusive prefix over the blocks of all segments (gbdt_part_scan_kernel); the lefts ahead of block b in its segment are
+// prefix[b] - prefix[b - j], which is the segmented scan.  A table that lies about its blocks cannot leave the segment (part_scatter).
 __global__ void __launch_bounds__(kBlock)
 gbdt_part_seg_scatter_kernel(const uint8_t *__restrict__ bins, int stride, int n, int F, const int32_t *__restrict__ rows, int64_t nrows,
                              const int32_t *__restrict__ segs, int cols, int K, const int32_t *__restrict__ blocks, int NB,
                              const int32_t *__restrict__ counts, int32_t *__restrict__ out, int32_t *__restrict__ left_counts) {
-    __shared__ int32_t wave_left[kBlock / kWave];
     int j;
     const GbdtPartSeg s = gbdt_part_block(segs, cols, K, blocks, blockIdx.x, NB, nrows, F, j);
     if (!s.ok) return;
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int first = blockIdx.x - j;
-    int left_before = counts[blockIdx.x] - counts[first];
     const int total_left = counts[first + s.nblk] - counts[first];
     if (j == 0 && threadIdx.x == 0) left_counts[blocks[blockIdx.x * 2]] = total_left;
-    const int32_t *srows = rows + s.start;
-    int32_t *sout = out + s.start;
-    for (int st = 0; st < kPartSteps; ++st) {
-        const int64_t i = ((int64_t)j * kPartSteps + st) * kBlock + threadIdx.x;
-        int row;
-        const bool left = part_goes_left(bins, stride, n, srows, i, s.count, s.feature, s.bin, s.also_left, row);
-        const unsigned long long mask = __ballot(left);
-        if (lane == 0) wave_left[wave] = __popcll(mask);
-        __syncthreads();
-        int before = left_before + __popcll(mask & ((1ull << lane) - 1));
-        int step_left = 0;
-        for (int w = 0; w < kBlock / kWave; ++w) { if (w < wave) before += wave_left[w]; step_left += wave_left[w]; }
-        const int64_t pos = left ? before : total_left + (i - before);            // `before` = the lefts ahead of entry i
-        if (i < s.count && pos >= 0 && pos < s.count) sout[pos] = row;             // a table that lies about its blocks cannot leave the segment
-        left_before += step_left;
-        __syncthreads();
-    }
+    part_scatter(PartByBin{bins, stride, n, rows + s.start, s.count, s.feature, s.bin, s.also_left}, j, counts[blockIdx.x] - counts[first], total_left,
+                 out + s.start);
 }
 
 // ---------------------------------------------------------------- leaf values and prediction
@@ -606,6 +564,22 @@ gbdt_add_leaf_values_kernel(float *__restrict__ scores, int n, const int32_t *__
     if (i < offsets[nleaves] && i >= offsets[0] && row >= 0 && row < n) scores[row] += values[lo];
 }
 
+// One row's walk down a tree of nn nodes (nn + 1 leaves; a child c < 0 is the leaf ~c) -> the node it ends in.  goes_left(node, f) decides at
+// a node that splits on feature f, which the walk has checked against F.  The walk takes nn steps at the most and stops at an index out of
+// range, so a malformed tree (a cycle, a node or feature out of range) ends it on something gbdt_is_leaf rejects.
+template <class GoesLeft> __device__ __forceinline__ int gbdt_walk(int nn, int F, const int32_t *__restrict__ feature, const int32_t *__restrict__ left,
+                                                                   const int32_t *__restrict__ right, const GoesLeft &goes_left) {
+    int node = nn > 0 ? 0 : ~0;
+    for (int step = 0; step < nn && node >= 0; ++step) {
+        if (node >= nn) break;
+        const int f = feature[node];
+        if (f < 0 || f >= F) break;
+        node = goes_left(node, f) ? left[node] : right[node];
+    }
+    return node;
+}
+__device__ __forceinline__ bool gbdt_is_leaf(int node, int nn) { return node < 0 && ~node <= nn; }
+
 __global__ void __launch_bounds__(kBlock)
 gbdt_predict_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t *__restrict__ feature, const float *__restrict__ threshold,
                     const int32_t *__restrict__ left, const int32_t *__restrict__ right, const float *__restrict__ value,
@@ -616,16 +590,11 @@ gbdt_predict_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t
     float s = 0.0f;
     for (int t = 0; t < ntrees; ++t) {
         const int base = tree_offsets[t], nn = tree_offsets[t + 1] - base, leaves = base + t;      // a tree of nn nodes has nn + 1 leaves
-        int node = nn > 0 ? 0 : ~0;
-        for (int step = 0; step < nn && node >= 0; ++step) {
-            if (node >= nn) break;
-            const int f = feature[base + node];
-            if (f < 0 || f >= F) break;
+        const int node = gbdt_walk(nn, F, feature + base, left + base, right + base, [&](int at, int f) {
             const float xv = x[f];
-            const bool go_left = (default_left && xv != xv) ? default_left[base + node] != 0 : xv <= threshold[base + node];   // a NaN follows the node's direction
-            node = go_left ? left[base + node] : right[base + node];
-        }
-        s += (node < 0 && ~node <= nn) ? value[leaves + ~node] : NAN;   // a malformed tree (a cycle, an index out of range) gives NaN
+            return (default_left && xv != xv) ? default_left[base + at] != 0 : xv <= threshold[base + at];   // a NaN follows the node's direction
+        });
+        s += gbdt_is_leaf(node, nn) ? value[leaves + ~node] : NAN;      // a malformed tree gives NaN
     }
     out[i] = s;
 }
@@ -641,15 +610,11 @@ gbdt_add_tree_binned_kernel(float *__restrict__ scores, const uint8_t *__restric
     const int row = rows ? rows[i] : i;
     if (row < 0 || row >= n) return;
     const uint8_t *x = bins + (size_t)row * stride;
-    int node = nn > 0 ? 0 : ~0;
-    for (int step = 0; step < nn && node >= 0; ++step) {
-        if (node >= nn) break;
-        const int f = feature[node];
-        if (f < 0 || f >= F) break;
+    const int node = gbdt_walk(nn, F, feature, left, right, [&](int at, int f) {
         const int b = x[f];
-        node = (b <= bin[node] || (also_left && b == also_left[node])) ? left[node] : right[node];
-    }
-    scores[row] += (node < 0 && ~node <= nn) ? value[~node] : NAN;      // a malformed tree (a cycle, an index out of range) gives NaN
+        return b <= bin[at] || (also_left && b == also_left[at]);
+    });
+    scores[row] += gbdt_is_leaf(node, nn) ? value[~node] : NAN;         // a malformed tree gives NaN
 }
 
 // ---------------------------------------------------------------- row sampling: the bag and GOSS
@@ -673,16 +638,8 @@ __device__ __forceinline__ void goss_pick(const uint32_t *__restrict__ table, ui
     uint32_t c[per], s = 0;
 #pragma unroll
     for (int k = 0; k < per; ++k) { c[k] = table[kGossDigits - 1 - (t * per + k)]; s += c[k]; }
-    scan[t] = s;
     if (t == 0) { res[0] = 0; res[1] = 1; }
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const uint32_t o = t >= d ? scan[t - d] : 0;
-        __syncthreads();
-        scan[t] += o;
-        __syncthreads();
-    }
-    uint32_t run = scan[t] - s;
+    uint32_t run = block_scan_add(scan, s) - s;
     if (run < K && K <= run + s) {                                      // one thread: the sums ahead of it fall short of K, with its own they reach it
 #pragma unroll
         for (int k = 0; k < per; ++k) {
@@ -779,6 +736,13 @@ static int check_max_bin(int max_bin, const char *who) {
     }
     return 0;
 }
+static int check_split_thresholds(double lambda_l2, double min_hess, double min_gain, const char *who) {
+    if (!(lambda_l2 >= 0.0) || !(min_hess == min_hess) || !(min_gain == min_gain)) {
+        set_error("%s: lambda_l2 must be >= 0 and no threshold may be NaN", who);
+        return PTR_ERR_INVALID_ARG;
+    }
+    return 0;
+}
 static int check_bins_layout(int64_t n, int F, int stride, const char *who) {
     if (n < 0 || F < 0 || n > INT32_MAX) { set_error("%s: bad size (n=%lld, F=%d; n must fit an int32 row index)", who, (long long)n, F); return PTR_ERR_INVALID_ARG; }
     if (stride < F || stride % kGbdtTile != 0) {
@@ -863,10 +827,7 @@ static int gbdt_best_split_impl(const char *who, const int64_t *hist, int nleaf,
                                 double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream) {
     if (nleaf < 0 || F < 0) { set_error("%s: negative size (nleaf=%d, F=%d)", who, nleaf, F); return PTR_ERR_INVALID_ARG; }
     if (int rc = check_max_bin(max_bin, who)) return rc;
-    if (!(lambda_l2 >= 0.0) || !(min_sum_hessian_in_leaf == min_sum_hessian_in_leaf) || !(min_gain_to_split == min_gain_to_split)) {
-        set_error("%s: lambda_l2 must be >= 0 and no threshold may be NaN", who);
-        return PTR_ERR_INVALID_ARG;
-    }
+    if (int rc = check_split_thresholds(lambda_l2, min_sum_hessian_in_leaf, min_gain_to_split, who)) return rc;
     if (nleaf == 0) return 0;
     if (!rec || (F > 0 && (!hist || !nbins || !expo || !ws || (missing && !nan_bin)))) {
         set_error("%s: NULL pointer (hist, nbins%s, expo, ws or rec)", who, missing ? ", nan_bin" : "");
@@ -899,7 +860,7 @@ extern "C" int ptr_gbdt_best_split_missing(const int64_t *hist, int nleaf, int F
 }
 
 extern "C" size_t ptr_gbdt_partition_ws_ints(int64_t m) {
-    return m <= 0 ? 1 : (size_t)((m + kPartSteps * kBlock - 1) / (kPartSteps * kBlock)) + 1;
+    return m <= 0 ? 1 : (size_t)((m + kGbdtPartRows - 1) / kGbdtPartRows) + 1;
 }
 
 static int gbdt_partition_impl(const char *who, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m, int feature, int bin,
@@ -1108,10 +1069,7 @@ static int gbdt_best_split_slots_impl(const char *who, const int64_t *pool, int 
                                       void *stream) {
     if (int rc = check_level_common(who, 0, F, 0, max_bin, K, kCheckMaxBin)) return rc;
     if (nslots < 0) { set_error("%s: negative size (nslots=%d)", who, nslots); return PTR_ERR_INVALID_ARG; }
-    if (!(lambda_l2 >= 0.0) || !(min_sum_hessian_in_leaf == min_sum_hessian_in_leaf) || !(min_gain_to_split == min_gain_to_split)) {
-        set_error("%s: lambda_l2 must be >= 0 and no threshold may be NaN", who);
-        return PTR_ERR_INVALID_ARG;
-    }
+    if (int rc = check_split_thresholds(lambda_l2, min_sum_hessian_in_leaf, min_gain_to_split, who)) return rc;
     if (K == 0) return 0;
     if (!pool || !slots || !nbins || !expo || !ws || !rec || (missing && !nan_bin)) {
         set_error("%s: NULL pointer (pool, slots, nbins%s, expo, ws or rec)", who, missing ? ", nan_bin" : "");
@@ -1166,7 +1124,7 @@ static int gbdt_partition_segments_impl(const char *who, const uint8_t *bins, in
     if (int rc = check_hip(hipMemsetAsync(left_counts, 0, (size_t)K * sizeof(int32_t), s), who)) return rc;
     if (nblocks == 0) return 0;
     hipLaunchKernelGGL(gbdt_part_seg_count_kernel, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, cols, K, blocks, nblocks, ws);
-    hipLaunchKernelGGL(gbdt_part_seg_scan_kernel, dim3(1), dim3(kBlock), 0, s, ws, nblocks);
+    hipLaunchKernelGGL(gbdt_part_scan_kernel, dim3(1), dim3(kBlock), 0, s, ws, nblocks, (int32_t *)nullptr);
     hipLaunchKernelGGL(gbdt_part_seg_scatter_kernel, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, cols, K, blocks, nblocks, ws, out,
                        left_counts);
     return check_hip(hipGetLastError(), who);

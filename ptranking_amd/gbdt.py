@@ -141,6 +141,17 @@ def _require_no_infinity(Xd):
         raise ValueError(_INFINITE)
 
 
+def _require_values(Xd, use_missing):
+    """The check a device matrix passes before it is walked: no infinity under use_missing, nothing but finite values without it."""
+    _require_no_infinity(Xd) if use_missing else _require_finite(Xd)
+
+
+def _device_matrix(X, dev):
+    """X (numpy array or tensor) as a contiguous float32 tensor on dev."""
+    X = X.detach() if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32))
+    return X.to(dev, torch.float32).contiguous()
+
+
 def _midpoints(lo, hi):
     """An fp32 edge e with lo <= e < hi for adjacent distinct fp32 values: the midpoint, or lo where the midpoint rounds up to hi."""
     mid = ((lo.astype(np.float64) + hi.astype(np.float64)) * 0.5).astype(np.float32)
@@ -256,7 +267,7 @@ class GBDT:
             self.edges, self.nbins, self.nan_bin = bin_edges(host, p["max_bin"], True)
         else:
             self.edges, self.nbins = bin_edges(host, p["max_bin"])
-        Xd = X.detach().to(dev, torch.float32).contiguous() if isinstance(X, torch.Tensor) else torch.from_numpy(host).to(dev)
+        Xd = _device_matrix(X if isinstance(X, torch.Tensor) else host, dev)
         self.n, self.F = host.shape
         self._edges_d, self._nbins_d = torch.from_numpy(self.edges).to(dev), torch.from_numpy(self.nbins).to(dev)
         self._nan_bin_d = torch.from_numpy(self.nan_bin).to(dev) if p["use_missing"] else None
@@ -309,21 +320,22 @@ class GBDT:
                           p["min_gain_to_split"], out=self._rec[out_row:out_row + 1], nan_bin=self._nan_bin_d)
 
     def _splittable(self, count, depth):
+        """Whether a leaf of `count` rows at `depth` may split: one leaf, or a level's counts as an array."""
         p = self.params
-        return count >= 2 * max(p["min_data_in_leaf"], 1) and (p["max_depth"] <= 0 or depth < p["max_depth"])
+        return (count >= 2 * max(p["min_data_in_leaf"], 1)) & (p["max_depth"] <= 0 or depth < p["max_depth"])
 
     def update(self, grad, hess):
         """Grows one tree from device fp32 gradients and Hessians [n]: the leaf with the largest gain is split (ties: the older leaf) until
-        num_leaves is reached or no leaf has a valid split (grow_policy='depthwise': level by level, _grow_depthwise); the leaf values -G / (H + lambda_l2) * learning_rate are added to the resident
-        training scores.  Returns the tree (a dict of numpy arrays).  A NaN or an infinity in grad / hess raises."""
+        num_leaves is reached or no leaf has a valid split (_grow_leafwise; grow_policy='depthwise': level by level, _grow_depthwise); the
+        leaf values -G / (H + lambda_l2) * learning_rate are added to the resident training scores.  Returns the tree (a dict of numpy
+        arrays).  A NaN or an infinity in grad / hess raises."""
         if self.n == 0 or self.edges is None:
             raise RuntimeError("call fit_bins(X) first")
-        p, nf, mb = self.params, self.F, self.params["max_bin"]
+        p, nf, mb, pool = self.params, self.F, self.params["max_bin"], self._pool
         sampled = self._sample(grad, hess) if sampling(p) else None
         if sampled is not None:
             grad, hess = sampled
         F.gbdt_quantize(grad, hess, flag=self._flag, out=(self._qg, self._qh, self._expo))
-        pool = self._pool
         pool[0].zero_()
         if sampled is None:
             F.gbdt_histogram(self.bins, self._qg, self._qh, None, nf, mb, hist=pool[0])
@@ -341,16 +353,22 @@ class GBDT:
             raise FloatingPointError("the gradients or Hessians of this round hold a NaN or an infinity")
         expo = (int(head[12]), int(head[13]))
         bag = self.n if sampled is None else int(head[11])             # the root's row count: the size of the bag
-        if p["grow_policy"] == "depthwise":
-            feature, threshold, left, right, starts, g_sum, h_sum, split_bin, go_left = self._grow_depthwise(head, bag, sampled is not None)
-            value = np.array([leaf_value(g, h, expo, p["lambda_l2"], p["learning_rate"]) for g, h in zip(g_sum, h_sum)], np.float32)
-            return self._finish(feature, threshold, left, right, starts, value, bag, split_bin, go_left)
-        root_rec = _record(head[:9]) if self._splittable(bag, 0) else _NO_SPLIT
-        leaves = [_Leaf(0, bag, 0, 0, -1, 0, int(head[9]), int(head[10]), root_rec)]
-        feature, threshold, left, right, split_bin, go_left = [], [], [], [], [], []
-        missing = p["use_missing"]
         if sampled is None:
             self._rows.copy_(self._arange)
+        grow = self._grow_depthwise if p["grow_policy"] == "depthwise" else self._grow_leafwise
+        feature, threshold, left, right, starts, g_sum, h_sum, split_bin, go_left = grow(head, bag)
+        value = np.array([leaf_value(g, h, expo, p["lambda_l2"], p["learning_rate"]) for g, h in zip(g_sum, h_sum)], np.float32)
+        return self._finish(feature, threshold, left, right, starts, value, bag, split_bin, go_left)
+
+    def _grow_leafwise(self, head, m):
+        """Leaf-wise growth from the root's record (head, as update read it) over the first m entries of the row list: the leaf with the
+        largest gain is split (ties: the older leaf), the smaller child's histogram is built and the larger one's subtracted, and ONE host
+        read per split brings the two children's records.  -> what _grow_depthwise returns."""
+        p, nf, mb, pool = self.params, self.F, self.params["max_bin"], self._pool
+        root_rec = _record(head[:9]) if self._splittable(m, 0) else _NO_SPLIT
+        leaves = [_Leaf(0, m, 0, 0, -1, 0, int(head[9]), int(head[10]), root_rec)]
+        feature, threshold, left, right, split_bin, go_left = [], [], [], [], [], []
+        missing = p["use_missing"]
         free = 1                                                       # the next unused histogram slot
         while len(leaves) < p["num_leaves"]:
             li = max(range(len(leaves)), key=lambda i: (leaves[i].rec[0], -i))
@@ -388,8 +406,7 @@ class GBDT:
                 for k, c in enumerate((lchild, rchild)):
                     if can[k]:
                         c.rec = _record(recs[k])
-        value = np.array([leaf_value(c.g, c.h, expo, p["lambda_l2"], p["learning_rate"]) for c in leaves], np.float32)
-        return self._finish(feature, threshold, left, right, [c.start for c in leaves], value, bag, split_bin, go_left)
+        return feature, threshold, left, right, [c.start for c in leaves], [c.g for c in leaves], [c.h for c in leaves], split_bin, go_left
 
     def _finish(self, feature, threshold, left, right, starts, value, m, split_bin, go_left=()):
         """Adds the leaf values (by leaf index, with the leaves' first positions in the row list) to the training scores; keeps the tree.
@@ -415,31 +432,27 @@ class GBDT:
         self._flat = None
         return t
 
-    def _grow_depthwise(self, head, m, sampled):
+    def _grow_depthwise(self, head, m):
         """Depth-wise growth from the root's record (head, as update read it): every level is one batched pass over all its leaves
         (partition, histograms of the smaller children, sibling subtraction, split scan) and ONE host read, the records of the level's
-        searched children.  The root is the first m entries of the row list (a sampled tree's bag, which update has put there: `sampled`).
+        searched children.  The root is the first m entries of the row list (all rows, or a sampled tree's bag, which update has put there).
         -> (feature, threshold, left, right, the leaves' first positions, their sums qg and qh, the split bins, default_left (zeros without
         use_missing)), by node / leaf index."""
         p, nf, mb, cap = self.params, self.F, self.params["max_bin"], self.params["num_leaves"]
         pool = self._pool
-        min_count, max_depth = 2 * max(p["min_data_in_leaf"], 1), p["max_depth"]
-        splittable = lambda count, depth: (count >= min_count) & (max_depth <= 0 or depth < max_depth)      # _splittable over a level
         feature, threshold = np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.float32)
         left, right, split_bin = np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.int32)
         go_left, missing = np.zeros(max(cap - 1, 0), np.uint8), p["use_missing"]
         starts, g_sum, h_sum = np.zeros(cap, np.int64), np.zeros(cap, np.int64), np.zeros(cap, np.int64)
         g_sum[0], h_sum[0] = head[9], head[10]
         nodes, leaves, free, depth = 0, 1, 1, 0
-        if not sampled:
-            self._rows.copy_(self._arange)
         # the frontier, in ascending start: leaf index, start, count, histogram slot, parent node, side, split record (gain -inf: none)
         leaf, start, count, slot = np.zeros(1, np.int64), np.zeros(1, np.int64), np.full(1, m, np.int64), np.zeros(1, np.int64)
         parent, side = np.full(1, -1, np.int64), np.zeros(1, np.int64)
         rec = np.asarray(head[:9], np.int64).reshape(1, 9).copy()
         while True:
             gain = rec[:, 0].copy().view(np.float64)
-            keep = np.nonzero(splittable(count, depth) & (gain > -np.inf))[0]
+            keep = np.nonzero(self._splittable(count, depth) & (gain > -np.inf))[0]
             budget = cap - leaves
             if keep.size == 0 or budget <= 0:
                 break
@@ -456,11 +469,8 @@ class GBDT:
             for arr, sd in ((left, 0), (right, 1)):
                 sel = has & (side[keep] == sd)
                 arr[parent[keep][sel]] = node[sel]
-            if missing:
-                also = np.where(go_left[node] != 0, self.nan_bin[f], -1)
-                F.gbdt_partition_segments(self.bins, self._rows, np.stack([start[keep], count[keep], f, b, also], axis=1), nf, out=self._tmp, also_left=True)
-            else:
-                F.gbdt_partition_segments(self.bins, self._rows, np.stack([start[keep], count[keep], f, b], axis=1), nf, out=self._tmp)
+            also = [np.where(go_left[node] != 0, self.nan_bin[f], -1)] if missing else []       # the fifth column of the missing form
+            F.gbdt_partition_segments(self.bins, self._rows, np.stack([start[keep], count[keep], f, b] + also, axis=1), nf, out=self._tmp, also_left=missing)
             self._rows, self._tmp = self._tmp, self._rows
             # the children, interleaved (left, right): ascending start again
             c_leaf = np.stack([leaf[keep], leaves + np.arange(k)], axis=1)
@@ -468,7 +478,7 @@ class GBDT:
             c_count = np.stack([lsum[:, 2], rsum[:, 2]], axis=1)
             starts[c_leaf], g_sum[c_leaf], h_sum[c_leaf] = c_start, np.stack([lsum[:, 0], rsum[:, 0]], axis=1), np.stack([lsum[:, 1], rsum[:, 1]], axis=1)
             nodes, leaves, depth = nodes + k, leaves + k, depth + 1
-            can = splittable(c_count, depth)
+            can = self._splittable(c_count, depth)
             c_slot = np.repeat(slot[keep][:, None], 2, axis=1)
             c_rec = np.zeros((k, 2, 9), np.int64)
             c_rec[:, :, 0], c_rec[:, :, 1:3] = np.float64(-np.inf).view(np.int64), -1
@@ -516,9 +526,9 @@ class GBDT:
         stop = (self.best_iteration or len(self.trees)) if num_iteration is None else int(num_iteration)
         if not 0 <= first_tree <= stop <= len(self.trees):
             raise ValueError(f"trees {first_tree} .. {stop} of {len(self.trees)}")
-        Xd = X.detach().to(dev, torch.float32) if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev)
+        Xd = _device_matrix(X, dev)
         if check_finite:
-            _require_no_infinity(Xd) if self.params["use_missing"] else _require_finite(Xd)
+            _require_values(Xd, self.params["use_missing"])
         if first_tree == 0:
             return F.gbdt_predict(Xd, fl["feature"], fl["threshold"], fl["left"], fl["right"], fl["value"], fl["tree_offsets"], stop,
                                   default_left=fl.get("default_left"))
@@ -643,8 +653,8 @@ class LambdaMART:
             Xv, yv = eval_set
             if eval_group is None:
                 raise ValueError("eval_set needs eval_group")
-            Xv = Xv.detach().to(self.device, torch.float32) if isinstance(Xv, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(Xv, dtype=np.float32)).to(self.device)
-            _require_no_infinity(Xv) if self.params["use_missing"] else _require_finite(Xv)   # once, before the first round: the rounds skip it
+            Xv = _device_matrix(Xv, self.device)
+            _require_values(Xv, self.params["use_missing"])              # once, before the first round: the rounds skip it
             yv = torch.from_numpy(np.ascontiguousarray(np.asarray(yv).reshape(-1), dtype=np.float32)).to(self.device)
             valid = (Xv, yv, self.padded_index(eval_group, self.device), torch.zeros(Xv.shape[0], device=self.device, dtype=torch.float32))
         elif early_stopping_rounds is not None:

@@ -123,7 +123,8 @@ def hist_data(nf, max_bin, n=N_ROWS, extreme=False):
 
 
 def row_list(m, order, n=N_ROWS):
-    rows = np.random.default_rng(m + 1).permutation(n)[:m].astype(np.int32)
+    rng = np.random.default_rng(m + 1)
+    rows = (rng.permutation(n)[:m] if m <= n else rng.integers(0, n, m)).astype(np.int32)      # a list longer than the matrix repeats rows
     return np.sort(rows) if order == "sorted" else rows
 
 
@@ -303,7 +304,8 @@ def test_best_split_exact_ties_go_to_the_lower_feature_then_the_lower_bin():
 
 
 # ---------------------------------------------------------------- ptr_gbdt_partition
-@pytest.mark.parametrize("m", [0, 1, 64, 65, 1000, 1024, 1025, 70000])
+# 256 * 1024 + 1025 entries are 258 workgroups: a thread of the scan over their counts owns two of them, and the last threads own none
+@pytest.mark.parametrize("m", [0, 1, 64, 65, 1000, 1024, 1025, 70000, 256 * 1024 + 1025])
 def test_partition_is_stable_and_exact(m):
     from ptranking_amd import functional as F
     bins, _, _, dbins, _, _ = hist_data(29, 16)

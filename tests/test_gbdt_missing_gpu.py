@@ -144,7 +144,8 @@ def test_binning_with_nan_bins(nf):
 
 
 # ---------------------------------------------------------------- both partitions
-@pytest.mark.parametrize("m", [1, 255, 256, 257, 1024, 1025, 4097])
+# 256 * 1024 + 1025 entries are 258 workgroups: a thread of the scan over their counts owns two of them, and the last threads own none
+@pytest.mark.parametrize("m", [1, 255, 256, 257, 1024, 1025, 4097, 256 * 1024 + 1025])
 def test_partitions_with_a_bin_that_goes_left_as_well(m):
     from ptranking_amd import functional as F
     rng = np.random.default_rng(m)
@@ -153,6 +154,8 @@ def test_partitions_with_a_bin_that_goes_left_as_well(m):
     binsn[:, :3] = rng.integers(0, 12, (n, 3))
     bins = dev(binsn)
     rows = rng.permutation(n).astype(np.int32)
+    if m > 4097:
+        rows[:m] = rng.integers(0, n, m)                                  # the long list repeats rows
     for also in (9, 11, 2, -1):
         out, lc = F.gbdt_partition(bins, dev(rows[:m]), 1, 3, 3, also_left=also)
         want, wl = MR.partition(binsn, rows[:m], 1, 3, also)

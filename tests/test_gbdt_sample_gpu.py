@@ -129,19 +129,23 @@ def test_goss_with_a_nan_gradient():
 
 
 # ---------------------------------------------------------------- ptr_gbdt_partition_mask
-@pytest.mark.parametrize("m", [0, 1, 255, 256, 257, 1024, 1025, 3 * 1024 + 17])
+# 256 * 1024 + 1025 entries are 258 workgroups: a thread of the scan over their counts owns two of them, and the last threads own none.
+# That list is longer than the mask: it repeats rows, and the identity list runs past the mask's end.
+@pytest.mark.parametrize("m", [0, 1, 255, 256, 257, 1024, 1025, 3 * 1024 + 17, 256 * 1024 + 1025])
 def test_partition_mask_is_stable_and_exact(m):
     from ptranking_amd import functional as F
     rng = np.random.default_rng(m)
     n = 4000
     lists = {"identity": None, "subset": rng.permutation(n)[:m].astype(np.int32),
              "out of range": (rng.permutation(n + 600)[:m] - 300).astype(np.int32)}
+    if m > n:
+        lists.update({"subset": rng.integers(0, n, m).astype(np.int32), "out of range": rng.integers(-300, n + 300, m).astype(np.int32)})
     for kind, mask in (("zeros", np.zeros(n, np.uint8)), ("ones", np.ones(n, np.uint8)), ("random", (rng.random(n) < 0.4).astype(np.uint8) * 3)):
         for name, rows in lists.items():
             out, lc = F.gbdt_partition_mask(dev(mask), None if rows is None else dev(rows), m=m if rows is None else None)
             want, kept = S.partition_mask(mask, rows, m)
             assert out.numel() == m and int(lc) == kept and np.array_equal(out.cpu().numpy(), want), (kind, name)
-            if name != "out of range":
+            if name == "subset" or (name == "identity" and m <= n):                      # a list inside the mask
                 assert kept == {"zeros": 0, "ones": m}.get(kind, kept)
     if m > 600:
         r = lists["out of range"]
