@@ -5,6 +5,7 @@
     python examples/train_lambdamart_native.py --grow-policy depthwise           # level by level, in batched passes
     python examples/train_lambdamart_native.py --bagging-fraction 0.5 --bagging-freq 1 --by-query   # every tree on a fresh half of the queries
     python examples/train_lambdamart_native.py --goss                            # gradient-based one-side sampling (top 0.2, other 0.1)
+    python examples/train_lambdamart_native.py --objective lambdarank_ndcg       # the truncated, normalised lambdarank (level 30)
 
 The synthetic relevance is planted: a linear part plus a feature interaction a linear scorer cannot express, graded with MSLR-WEB30K's label
 mix.  Prints the validation nDCG@5 every 10 rounds.  No LightGBM comparison: the library is not installed where this project is tested.
@@ -42,7 +43,11 @@ def from_file(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("files", nargs="*", help="train.txt [vali.txt] [test.txt]")
-    ap.add_argument("--objective", default="lambdarank", choices=["lambdarank", "ranknet", "listnet"])
+    ap.add_argument("--objective", default="lambdarank", choices=["lambdarank", "ranknet", "listnet", "lambdarank_ndcg"],
+                    help="lambdarank_ndcg: the truncated, normalised lambdarank (this project's rule, modelled on LightGBM's built-in objective)")
+    ap.add_argument("--truncation-level", type=int, default=30, help="lambdarank_truncation_level (lambdarank_ndcg only)")
+    ap.add_argument("--no-norm", action="store_true", help="lambdarank_norm=False (lambdarank_ndcg only)")
+    ap.add_argument("--sigmoid", type=float, default=1.0, help="the sigmoid's steepness (lambdarank_ndcg only)")
     ap.add_argument("--rounds", type=int, default=100)
     ap.add_argument("--num-leaves", type=int, default=31)
     ap.add_argument("--learning-rate", type=float, default=0.1)
@@ -64,7 +69,8 @@ def main():
         train, valid, test = synthetic(args.queries, args.features, 7), synthetic(args.queries // 4, args.features, 8), synthetic(args.queries // 4, args.features, 9)
     params = {"num_leaves": args.num_leaves, "learning_rate": args.learning_rate, "min_data_in_leaf": args.min_data_in_leaf, "num_trees": args.rounds,
               "grow_policy": args.grow_policy, "bagging_fraction": args.bagging_fraction, "bagging_freq": args.bagging_freq,
-              "bagging_by_query": args.by_query, "data_sample_strategy": "goss" if args.goss else "bagging"}
+              "bagging_by_query": args.by_query, "data_sample_strategy": "goss" if args.goss else "bagging",
+              "lambdarank_truncation_level": args.truncation_level, "lambdarank_norm": not args.no_norm, "sigmoid": args.sigmoid}
     lm = pa.LambdaMART(params, objective=args.objective)
     how = {None: "none", "goss": f"goss (top_rate {lm.params['top_rate']}, other_rate {lm.params['other_rate']})",
            "bagging": f"bagging {args.bagging_fraction} {'by query' if args.by_query else 'by row'}, redrawn every {args.bagging_freq} trees"}

@@ -70,7 +70,10 @@ def main():
     _, labels, _, qoff = parse_letor_file(args.train)
     group = np.diff(qoff)
     assert len(labels) < 2 ** 24, "the score table is indexed through a float32 feature"
-    obj = pa.TreeObjective(labels, group, args.objective, weighting=None if args.weighting == "none" else args.weighting, hessian="sum")
+    if args.objective == "lambdarank_ndcg":                       # its weight and its Hessian are part of the rule: --weighting does not apply
+        obj = pa.TreeObjective(labels, group, args.objective)
+    else:
+        obj = pa.TreeObjective(labels, group, args.objective, weighting=None if args.weighting == "none" else args.weighting, hessian="sum")
     table = ScoreTable(len(labels), dev)
     data = padded_batch(labels, group, dev)
     ndcg = lambda: float(table.ndcg_at_k(test_data=data, k=10, label_type=pa.LABEL_TYPE.MultiLabel)[0])

@@ -300,7 +300,32 @@ int ptr_ndeval_measures(const float *preds, const float *rele, const int32_t *le
  *
  * PTR_ERR_INVALID_ARG (before any launch): a NULL pointer while nq > 0, a negative size, queries == NULL with nq != B, epsilon < 0 or NaN, an
  * enum value out of range.  PTR_ERR_UNSUPPORTED: max_len > PTR_MAX_LIST_LEN.  LDS per query: 4 round_up(max_len, 4) bytes times 2 (no weights),
- * 3 (_DELTA_GAIN, ListNet) or 4 (_DELTA_NDCG): 64 KiB at 4096 documents. */
+ * 3 (_DELTA_GAIN, ListNet) or 4 (_DELTA_NDCG): 64 KiB at 4096 documents.
+ *
+ * ptr_tree_lambdarank_ndcg_grad_hess (ADDITIVE to ABI v8: PTR_ABI_VERSION stays 8) is the truncated, normalised lambdarank that the
+ * reference's tree frame runs by default through LightGBM's built-in objective='lambdarank' (lightgbm_lambdaMART.py:170-185).  The rule below
+ * is THIS PROJECT'S OWN, modelled on LightGBM's LambdarankNDCG; LightGBM is not available where this library is built and tested, the rule is
+ * compared with nothing of LightGBM's, and no parity with it is claimed.  Same ragged layout, `queries` subset list, max_len contract and
+ * forms as above.  For one query of n documents, scores s, labels y >= 0, gain g = 2^y - 1, r(i) the 0-based rank of document i in
+ * predicted order (a higher score first, equal scores by original index), D(r) = 1 / log2(r + 2), T = truncation_level >= 1,
+ * sigma = sigmoid > 0:
+ *   1. maxDCG = the sum over the min(T, n) largest gains, in descending order, of g D(position); inv = 1 / maxDCG where maxDCG > 0, else 0.
+ *   2. A pair {i, j} counts if and only if y_i != y_j and min(r(i), r(j)) < T.  `hi` is its document of the larger label, `lo` the other,
+ *      ds = s_hi - s_lo.
+ *   3. delta = (g_hi - g_lo) |D(r(hi)) - D(r(lo))| inv; if norm is set and the query's largest and smallest scores differ,
+ *      delta /= (0.01 + |ds|).
+ *   4. p = 1 / (1 + exp(sigma ds)), lam = sigma delta p, h = sigma^2 delta p (1 - p).
+ *   5. grad[hi] -= lam, grad[lo] += lam, hess[hi] += h, hess[lo] += h, S += 2 lam.
+ *   6. If norm is set and S > 0, every grad and hess of the query is multiplied by log2(1 + S) / S.
+ *   (Two labels so close that their fp32 gains coincide give delta = 0: such a pair contributes nothing either way.)
+ *   The gradients of a query sum to 0 and no Hessian is negative.  One document, equal labels, or NO RELEVANT DOCUMENT: exactly 0 in both
+ *   outputs.  The last case DIFFERS from PTR_TREE_W_DELTA_NDCG above, which returns NaN there (its normalised gains are 0 / 0); here inv = 0.
+ *   With T >= n, norm = 0 and sigmoid = 1 the result is that of ptr_tree_pair_grad_hess(PTR_TREE_PAIRS_NOTIES, PTR_TREE_W_DELTA_NDCG,
+ *   epsilon 1, PTR_TREE_HESS_SUM) on every list that holds a relevant document, up to rounding and that kernel's 1e-16 Hessian floor.
+ *   A NaN score or label: NaN on every document of that list and of no other.  A launched query longer than max_len: NaN, as above.
+ *   norm: 0 is off, any other value is on.  PTR_ERR_INVALID_ARG as above, and for truncation_level < 1 or a sigmoid that is not > 0 (NaN
+ *   included).  No atomics, nothing of size n x n; every sum has an order that depends on the query alone (each document's partners in rank
+ *   order; maxDCG and S by a halving tree over n).  LDS per query: 28 round_up(max_len, 4) bytes, 112 KiB at 4096 documents. */
 #define PTR_TREE_PAIRS_ALL 0
 #define PTR_TREE_PAIRS_NOTIES 1
 #define PTR_TREE_PAIRS_NO00 2
@@ -317,6 +342,8 @@ int ptr_tree_pair_grad_hess(const float *preds, const float *labels, const int64
                             int pair_type, int weighting, float epsilon, int hessian, float *grad, float *hess, void *stream);
 int ptr_tree_listnet_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries, int nq, int max_len,
                                int gain_type, int hessian, float *grad, float *hess, void *stream);
+int ptr_tree_lambdarank_ndcg_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries, int nq,
+                                       int max_len, int truncation_level, float sigmoid, int norm, float *grad, float *hess, void *stream);
 
 /* ---- Smooth-rank metric objectives (csrc/smoothmetric.hip).  The symbol below is ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
  * ptr_smoothmetric_fwd_bwd — loss and dLoss/dpreds of precision_ / AP_ / nERR_ / nDCG_as_opt_objective

@@ -221,6 +221,133 @@ tree_listnet_kernel(const float *__restrict__ preds, const float *__restrict__ l
     }
 }
 
+// ---- LightGBM-style truncated, normalised lambdarank (ptr_tree_lambdarank_ndcg_grad_hess; include/ptranking_amd.h states the rule).
+// The rule is this project's own, written after LightGBM's LambdarankNDCG; nothing here is compared with LightGBM.
+// LDS per query: 7 rows of Lp = round_up(max_len, 4) words (28 Lp bytes, 112 KiB at 4096 documents):
+//   S   scores by document (float4 reads of the rank count)     -> after the scatter: sum_j lam per rank, the row of the S tree
+//   Y   labels by document (likewise)                           -> after the scatter: grad per rank
+//   Rs | Rg | Rd   score and gain of the document AT rank r, and the discount table 1 / log2(r + 2): a partner read is a broadcast
+//   H   the terms of maxDCG by document, summed by the tree     -> hess per rank
+//   Ix  the document at rank r
+// Work split: the thread that owns rank r (strided where the list is longer than the group) walks EVERY rank when r < T and only the ranks
+// below min(T, n) otherwise, in rank order (four interleaved chains per sum), and writes its own document's two results; a pair of two
+// top-T documents is evaluated from both ends.  The first T ranks sit in the first lanes of the first pass, so one wavefront carries the
+// n-step walks and the rest T-step ones.
+constexpr int kLrnRows = 7;
+
+// Descending rank of document i among keys[0 .. n) in ONE pass: #{j : k_j > k_i} + #{j < i : k_j == k_i} (count_ranks' rule).  Label rows and
+// the first boosting round's scores are all ties, where count_ranks' second pass costs i steps per document; this costs n / 4 either way.
+__device__ __forceinline__ int rank_indexed(const float *keys, int n, int i, float own) {
+    const float4 *k4 = reinterpret_cast<const float4 *>(keys);
+    const int n4 = (n + 3) >> 2;
+    int rk = 0;
+    for (int j4 = 0; j4 < n4; ++j4) {
+        const float4 v = k4[j4];
+        const int j = 4 * j4;
+        rk += (v.x > own || (v.x == own && j < i)) + (v.y > own || (v.y == own && j + 1 < i)) + (v.z > own || (v.z == own && j + 2 < i)) +
+              (v.w > own || (v.w == own && j + 3 < i));
+    }
+    return rk;
+}
+
+template <int G>
+__global__ void __launch_bounds__(kBlock)
+tree_lambdarank_ndcg_kernel(const float *__restrict__ preds, const float *__restrict__ labels, const int64_t *__restrict__ offsets, int B,
+                            const int32_t *__restrict__ queries, int nq, int Lp, int max_len, int T, float sigma, int norm,
+                            float *__restrict__ grad, float *__restrict__ hess) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, grp = tid / G, t = tid % G;
+    const TreeQuery qu = tree_query<G>(offsets, B, queries, nq, max_len, t, grad, hess);
+    const int64_t base = qu.base;
+    const int n = G >= kWave ? __builtin_amdgcn_readfirstlane(qu.n) : qu.n;
+
+    float *S = smem + (size_t)grp * kLrnRows * Lp, *Y = S + Lp, *Rs = Y + Lp, *Rg = Rs + Lp, *Rd = Rg + Lp, *H = Rd + Lp;
+    int *Ix = reinterpret_cast<int *>(H + Lp);
+
+    // ---- stage the scores and the labels; both rows are padded with -inf up to a multiple of 4 (rank_indexed reads float4)
+    bool bad = false;
+    const int np = (n + 3) & ~3;
+    for (int i = t; i < np; i += G) {
+        const float s = i < n ? preds[base + i] : -INFINITY, y = i < n ? labels[base + i] : -INFINITY;
+        S[i] = s; Y[i] = y;
+        bad |= s != s || y != y;
+    }
+    // a NaN score or label gives the list no ranking (the ranks below would not be a permutation): NaN on every document of this list
+    const bool nanq = group_any<G>(bad, tid);
+    group_sync<G>();
+
+    // ---- ranks by score and by label; scatter into rank order; the terms of maxDCG (the IDCG cut at T)
+    if (!nanq) {
+        for (int i = t; i < n; i += G) {
+            const float s = S[i], y = Y[i];
+            const int r = rank_indexed(S, n, i, s), ry = rank_indexed(Y, n, i, y);
+            const float g = gain_of(y);
+            Rs[r] = s; Rg[r] = g; Ix[r] = i;
+            Rd[i] = inv_log2_pos(i);
+            H[i] = ry < T ? g * inv_log2_pos(ry) : 0.0f;
+        }
+    }
+    group_tree<G>(H, n, t, [](float a, float b) { return a + b; });
+    const float maxdcg = n > 0 ? H[0] : 0.0f;
+    const float inv = maxdcg > 0.0f ? 1.0f / maxdcg : 0.0f;
+    // the score-distance division applies where the list's largest and smallest scores differ
+    const bool spread = norm != 0 && n > 0 && !nanq && Rs[0] != Rs[n - 1];
+    group_sync<G>();
+
+    const int Tn = T < n ? T : n;
+    const float sigma2 = sigma * sigma;
+    if (!nanq) {
+        for (int r = t; r < n; r += G) {
+            const float sr = Rs[r], gr = Rg[r], dr = Rd[r];
+            const int kend = r < T ? n : Tn;
+            // four interleaved chains per sum (partner k adds into chain k mod 4), joined as (0 + 1) + (2 + 3): a fixed order that depends on
+            // the query alone, a quarter of the in-order rounding of one chain, and four independent dependency chains for the adder
+            float g[4] = {0.0f, 0.0f, 0.0f, 0.0f}, h[4] = {0.0f, 0.0f, 0.0f, 0.0f}, l[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            auto partner = [&](int k, float &ga, float &ha, float &la) {
+                const float dg = gr - Rg[k];                       // > 0: this document is the pair's `hi`
+                const float d0 = sr - Rs[k];
+                const float ds = dg > 0.0f ? d0 : -d0;             // s_hi - s_lo: the difference first, sigma after
+                float delta = fabsf(dg) * fabsf(dr - Rd[k]) * inv;
+                if (spread) delta *= rcp_nr(0.01f + fabsf(ds));
+                const float x = sigma * ds;
+                const float e = __expf(-fabsf(x));
+                const float r1 = rcp1p(e);
+                const float p = x >= 0.0f ? e * r1 : r1;           // 1 / (1 + exp(x))
+                const float lam = sigma * delta * p;
+                const float hv = sigma2 * delta * (e * r1 * r1);   // p (1 - p) without the cancellation of 1 - p
+                const bool on = dg != 0.0f;                        // equal gains: equal labels (k == r among them), or delta = 0
+                ga += on ? (dg > 0.0f ? -lam : lam) : 0.0f;
+                ha += on ? hv : 0.0f;
+                la += on ? lam : 0.0f;
+            };
+            int k = 0;
+            for (; k + 4 <= kend; k += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) partner(k + u, g[u], h[u], l[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 3; ++u)
+                if (k + u < kend) partner(k + u, g[u], h[u], l[u]);
+            Y[r] = (g[0] + g[1]) + (g[2] + g[3]);
+            H[r] = (h[0] + h[1]) + (h[2] + h[3]);
+            S[r] = (l[0] + l[1]) + (l[2] + l[3]);
+        }
+    }
+    // S = 2 sum lam: every pair was seen once from each end
+    group_tree<G>(S, n, t, [](float a, float b) { return a + b; });
+    const float total = n > 0 ? S[0] : 0.0f;
+    if (nanq) {
+        for (int i = t; i < n; i += G) { grad[base + i] = NAN; hess[base + i] = NAN; }
+        return;
+    }
+    const float scale = norm != 0 && total > 0.0f ? log1pf(total) * 1.4426950408889634f / total : 1.0f;    // log2(1 + S) / S
+    for (int r = t; r < n; r += G) {
+        const int i = Ix[r];
+        grad[base + i] = Y[r] * scale;
+        hess[base + i] = H[r] * scale;
+    }
+}
+
 // ---- host side
 static int tree_check(const void *preds, const void *labels, const void *offsets, int B, const void *queries, int nq, int max_len, int hessian,
                       const void *grad, const void *hess, const char *who) {
@@ -307,5 +434,23 @@ extern "C" int ptr_tree_listnet_grad_hess(const float *preds, const float *label
         const size_t lds = (size_t)(kBlock / G) * 3 * Lp * sizeof(float);
         return launch_queries(tree_listnet_kernel<G>, nq, kBlock / G, kBlock, lds, stream, who, preds, labels, offsets, B, queries, nq, Lp, max_len,
                               gain_type == PTR_TREE_GAIN_POWER ? 1 : 0, hessian == PTR_TREE_HESS_CONSTANT ? 1 : 0, grad, hess);
+    });
+}
+
+extern "C" int ptr_tree_lambdarank_ndcg_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries,
+                                                  int nq, int max_len, int truncation_level, float sigmoid, int norm, float *grad, float *hess,
+                                                  void *stream) {
+    using namespace ptr;
+    const char *who = "ptr_tree_lambdarank_ndcg_grad_hess";
+    if (int rc = tree_check(preds, labels, offsets, B, queries, nq, max_len, PTR_TREE_HESS_SUM, grad, hess, who)) return rc;
+    if (truncation_level < 1) { set_error("%s: truncation_level must be >= 1 (got %d)", who, truncation_level); return PTR_ERR_INVALID_ARG; }
+    if (!(sigmoid > 0.0f)) { set_error("%s: sigmoid must be > 0 (got %g)", who, (double)sigmoid); return PTR_ERR_INVALID_ARG; }
+    if (int rc = tree_check_len(max_len, who)) return rc;
+    if (nq == 0 || max_len == 0) return 0;
+    const int Lp = round_up(max_len, 4);
+    return dispatch_tree_form(max_len, [&]<int G>() {
+        const size_t lds = (size_t)(kBlock / G) * kLrnRows * Lp * sizeof(float);
+        return launch_queries(tree_lambdarank_ndcg_kernel<G>, nq, kBlock / G, kBlock, lds, stream, who, preds, labels, offsets, B, queries, nq, Lp,
+                              max_len, truncation_level, sigmoid, norm, grad, hess);
     });
 }

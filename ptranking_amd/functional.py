@@ -16,7 +16,7 @@ from . import _lib
 
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
-           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "ndeval_measures", "div_ideal_order", "NDEVAL_MEASURES","divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
+           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "ndeval_measures", "div_ideal_order", "NDEVAL_MEASURES","divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "tree_lambdarank_ndcg_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
            "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "gaussian_metric_objective", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS",
            "irgan_uniforms", "irgan_sample", "irgan_point_generator", "irgan_selected", "IRGAN_SAMPLE_MODES", "IRGAN_SELECTED_MODES", "IRGAN_MAX_SAMPLES",
            "irfgan_uniforms", "irfgan_point_sample", "irfgan_pair_sample", "IRFGAN_MODES", "F_DIVERGENCES",
@@ -887,6 +887,33 @@ def tree_listnet_grad_hess(preds, labels, offsets, gain_type="Power", hessian="r
     hess = p (1 - p) per query of the ragged batch; gain 2^label - 1 ('Power') or the label ('Label').  Arguments as tree_pair_grad_hess."""
     return _ragged("ptr_tree_listnet_grad_hess", preds, labels, offsets, queries, max_len, out, _enum("gain_type", gain_type, TREE_GAIN_TYPES),
                    _enum("hessian", hessian, TREE_HESSIANS))
+
+
+def lambdarank_ndcg_settings(truncation_level=30, sigmoid=1.0, norm=True):
+    """The three settings of the truncated, normalised lambdarank, validated -> (int truncation_level >= 1, float sigmoid > 0, bool norm).
+    A bool is no truncation level, and norm must be a real bool (LightGBM's lambdarank_truncation_level, sigmoid, lambdarank_norm)."""
+    t = truncation_level
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.floating)) or t != t or int(t) != t or t < 1:
+        raise ValueError(f"lambdarank_truncation_level must be an integer >= 1, got {truncation_level!r}")
+    if isinstance(sigmoid, (bool, np.bool_)) or not isinstance(sigmoid, (int, float, np.integer, np.floating)) or not float(np.float32(sigmoid)) > 0.0 \
+            or not np.isfinite(np.float32(sigmoid)):
+        raise ValueError(f"sigmoid must be a finite float > 0 (in float32), got {sigmoid!r}")
+    if not isinstance(norm, (bool, np.bool_)):
+        raise ValueError(f"lambdarank_norm must be True or False, got {norm!r}")
+    return int(t), float(sigmoid), bool(norm)
+
+
+def tree_lambdarank_ndcg_grad_hess(preds, labels, offsets, truncation_level=30, sigmoid=1.0, norm=True, queries=None, max_len=None, out=None):
+    """Gradient and Hessian per document of the truncated, normalised lambdarank over LightGBM's ragged layout, in one launch
+    (ptr_tree_lambdarank_ndcg_grad_hess; include/ptranking_amd.h states the rule in full).  The rule is this project's own, modelled on
+    LightGBM's LambdarankNDCG (the objective the reference's tree frame runs by default); it is compared with nothing of LightGBM's.
+    A pair counts where the labels differ and one of the two documents ranks in the first `truncation_level`; it weighs
+    (g_hi - g_lo) |D_hi - D_lo| / maxDCG@truncation_level, divided by 0.01 + |s_hi - s_lo| under `norm`; lam = sigmoid w p and
+    h = sigmoid^2 w p (1 - p) with p = 1 / (1 + exp(sigmoid (s_hi - s_lo))); under `norm` a query's results are scaled by log2(1 + S) / S,
+    S = 2 sum lam.  No Hessian is negative; a list without a relevant document is exactly 0 (not NaN, as weighting='DeltaNDCG' gives).
+    Arguments and layout as tree_pair_grad_hess."""
+    t, sigma, norm = lambdarank_ndcg_settings(truncation_level, sigmoid, norm)
+    return _ragged("ptr_tree_lambdarank_ndcg_grad_hess", preds, labels, offsets, queries, max_len, out, min(t, 2 ** 31 - 1), C.c_float(sigma), int(norm))
 
 
 def shuffle_ties_order(labels, seed, lens=None):

@@ -11,7 +11,7 @@ LightGBM itself, the quantile binning rule for features of more distinct values 
     GBDT(params)       the booster: fit_bins(X) bins the features once and keeps them resident; update(grad, hess) grows ONE tree (leaf-wise, or
                         depth-wise under grow_policy='depthwise') from device gradients and adds its leaf values to the resident training scores; predict / save_model / load_model
     LambdaMART(params)  the ranker: every round computes the gradient and the Hessian per document with tree_pair_grad_hess /
-                        tree_listnet_grad_hess on the resident scores (no host copy), quantizes them and calls update
+                        tree_listnet_grad_hess / tree_lambdarank_ndcg_grad_hess on the resident scores (no host copy), quantizes them and calls update
 
 Growth policies (grow_policy): 'leafwise', the default, splits the leaf of the largest gain and reads the two children's records back after
 every split; 'depthwise' splits ALL leaves of a level in one batched pass (partition, histograms of the smaller children, sibling
@@ -41,6 +41,17 @@ node for node (tests/golden/gbdt_sklearn_missing.npz; include/ptranking_amd.h st
 them).  Such a model is saved as format 2 (format 1 with default_left per node and nan_bin per feature); a model without the switch saves
 the format-1 file it always did.  Not here: zero_as_missing, and the LETOR loader's absent features, which stay zeros.
 
+The truncated, normalised lambdarank: LambdaMART(objective='lambdarank_ndcg').  The reference's tree frame runs LightGBM's BUILT-IN
+objective='lambdarank' by default (lightgbm_lambdaMART.py:170-185); 'lambdarank_ndcg' is this project's own rule modelled on that objective
+(LightGBM's LambdarankNDCG), stated in include/ptranking_amd.h and restated in tests/lambdarank_ndcg_ref.py.  It is compared with nothing of
+LightGBM's and no parity is claimed.  A pair counts where the labels differ and one of its documents ranks in the first
+lambdarank_truncation_level (30); its weight is the Delta-nDCG against maxDCG at that level, divided by 0.01 + |score difference| under
+lambdarank_norm (True); lam = sigmoid w p, h = sigmoid^2 w p (1 - p) (sigmoid 1.0); under lambdarank_norm a query's results are scaled by
+log2(1 + S) / S, S = 2 sum lam.  The three settings come from the parameter dict under LightGBM's names; the other objectives and the bare
+booster ignore them.  The key 'objective' of the dict stays ignored (the objective is LambdaMART's argument, and its default stays
+'lambdarank', the reference's CUSTOM all-pairs objective), and label_gain stays unknown (the gain is 2^y - 1).  A model file written before
+the three keys existed loads with their defaults.
+
 Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here:
 feature_fraction, EFB, categorical features, DART, monotone constraints.  There is no CPU path.
 """
@@ -59,7 +70,9 @@ __all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS"
 DEFAULT_PARAMS = {"learning_rate": 0.1, "num_leaves": 31, "num_trees": 100, "min_data_in_leaf": 20, "min_sum_hessian_in_leaf": 1e-3,
                   "lambda_l2": 0.0, "min_gain_to_split": 0.0, "max_bin": 255, "max_depth": -1, "grow_policy": "leafwise",
                   "bagging_fraction": 1.0, "bagging_freq": 0, "bagging_seed": 3, "bagging_by_query": False, "data_sample_strategy": "bagging",
-                  "top_rate": 0.2, "other_rate": 0.1, "use_missing": False}
+                  "top_rate": 0.2, "other_rate": 0.1, "use_missing": False,
+                  # LambdaMART(objective='lambdarank_ndcg') alone reads these three; the other objectives and the bare booster ignore them
+                  "lambdarank_truncation_level": 30, "lambdarank_norm": True, "sigmoid": 1.0}
 IGNORED_PARAMS = ("num_threads", "verbosity", "metric", "boosting_type", "objective", "eval_at")    # accepted, without a meaning here
 MODEL_FORMAT = 1                       # a model trained without use_missing
 MODEL_FORMAT_MISSING = 2               # one trained under it: format 1 with default_left per node and nan_bin per feature
@@ -112,6 +125,8 @@ def _params(params):
         raise ValueError(f"top_rate and other_rate must be > 0 and sum to at most 1, got {p['top_rate']}, {p['other_rate']}")
     if p["data_sample_strategy"] == "goss" and _bagging(p):
         raise ValueError("data_sample_strategy 'goss' cannot be combined with bagging (bagging_freq > 0 and bagging_fraction < 1)")
+    p["lambdarank_truncation_level"], p["sigmoid"], p["lambdarank_norm"] = F.lambdarank_ndcg_settings(p["lambdarank_truncation_level"], p["sigmoid"],
+                                                                                                   p["lambdarank_norm"])
     return p
 
 
@@ -580,7 +595,10 @@ class LambdaMART:
     """LambdaMART on the native booster.  objective 'lambdarank' (pair_type 'NoTies'), 'ranknet' ('All') or 'listnet', as tree.OBJECTIVES.
     The defaults are real LambdaMART: weighting='DeltaNDCG' (applied to 'lambdarank'; 'ranknet' is the unweighted pairwise loss) and the
     never-negative hessian='sum'.  hessian='reference' (the reference's rank-signed Hessian) is accepted, but its sums are negative for
-    low-ranked documents, so leaves can stay unsplittable under the Hessian floor of the split scan."""
+    low-ranked documents, so leaves can stay unsplittable under the Hessian floor of the split scan.
+    objective 'lambdarank_ndcg' is the truncated, normalised lambdarank of the module docstring: it reads lambdarank_truncation_level,
+    lambdarank_norm and sigmoid from params, and weighting, hessian, pair_type, epsilon and gain_type do not apply to it (a non-default
+    value raises ValueError)."""
 
     def __init__(self, params=None, objective="lambdarank", weighting="DeltaNDCG", hessian="sum", pair_type=None, epsilon=1.0,
                  gain_type="Power", device=None):
@@ -595,6 +613,9 @@ class LambdaMART:
         if self.kind == "pair":
             F._enum("pair_type", self.pair_type, F.TREE_PAIR_TYPES)
             F._enum("weighting", self.weighting, F.TREE_WEIGHTINGS)
+        elif self.kind == "lambdarank_ndcg":
+            tree.not_applicable(objective, dict(weighting=weighting, hessian=hessian, pair_type=pair_type, epsilon=epsilon, gain_type=gain_type),
+                                dict(weighting="DeltaNDCG", hessian="sum", pair_type=None, epsilon=1.0, gain_type="Power"))
         else:
             F._enum("gain_type", gain_type, F.TREE_GAIN_TYPES)
         F._enum("hessian", hessian, F.TREE_HESSIANS)
@@ -612,6 +633,10 @@ class LambdaMART:
         for max_len, queries in res.buckets:
             if self.kind == "pair":
                 F.tree_pair_grad_hess(scores, res.labels, res.offsets, self.pair_type, self.weighting, self.epsilon, self.hessian, queries, max_len, out)
+            elif self.kind == "lambdarank_ndcg":
+                p = self.params
+                F.tree_lambdarank_ndcg_grad_hess(scores, res.labels, res.offsets, p["lambdarank_truncation_level"], p["sigmoid"], p["lambdarank_norm"],
+                                                 queries, max_len, out)
             else:
                 F.tree_listnet_grad_hess(scores, res.labels, res.offsets, self.gain_type, self.hessian, queries, max_len, out)
         return out

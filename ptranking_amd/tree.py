@@ -16,6 +16,13 @@ What reading the reference turned up, and what each mode does about it (DESIGN.m
   3. its Hessian's sigmoid ignores epsilon: kept, in every mode;
   4. its wrappers call group.astype(np.int), which numpy >= 1.24 refuses: nothing here needs np.int;
   5. its sort is not stable: here equal scores rank by original index (the first boosting round has all scores equal).
+
+objective='lambdarank_ndcg' is none of the reference's custom objectives: it is the truncated, normalised lambdarank that the reference's
+tree frame runs by default through LightGBM's BUILT-IN objective='lambdarank' (lightgbm_lambdaMART.py:170-185).  The rule is this project's
+own, modelled on LightGBM's LambdarankNDCG and compared with nothing of LightGBM's (include/ptranking_amd.h states it): a pair counts where
+the labels differ and one of its documents ranks in the first truncation_level; its weight is the Delta-nDCG against maxDCG@truncation_level,
+divided by 0.01 + |score difference| under norm; under norm a query's results are scaled by log2(1 + S) / S, S = 2 sum lam.  Its Hessian is
+never negative, and a list without a relevant document is exactly 0 where weighting='DeltaNDCG' gives NaN.
 """
 import weakref
 
@@ -33,7 +40,8 @@ __all__ = ["TreeObjective", "bucket_queries", "LENGTH_CLASSES", "OBJECTIVES", "l
 # to 128, one workgroup per query beyond); the one-workgroup form is split further because its LDS rows are sized by the longest list.
 LENGTH_CLASSES = (16, 128, 256, 512, 1024, 2048, _lib.MAX_LIST_LEN)
 # objective -> (kind, default pair_type): what the reference's wrappers pass (lightgbm_util.py:203-204, :262-264, :351-352)
-OBJECTIVES = {"ranknet": ("pair", "All"), "lambdarank": ("pair", "NoTies"), "listnet": ("listnet", None)}
+OBJECTIVES = {"ranknet": ("pair", "All"), "lambdarank": ("pair", "NoTies"), "listnet": ("listnet", None),
+              "lambdarank_ndcg": ("lambdarank_ndcg", None)}           # the truncated, normalised lambdarank: no wrapper of the reference's
 
 FIRST_ORDER = False            # lightgbm_util.py:75: True makes the drop-in functions return the constant Hessian
 CONSTANT_HESSIAN = 1.0         # lightgbm_util.py:76 (the only value the kernel fills)
@@ -57,6 +65,14 @@ def bucket_queries(group, classes=LENGTH_CLASSES):
             out.append((int(g[idx].max()), idx))
         lo = hi
     return out
+
+
+def not_applicable(objective, given, defaults):
+    """Raises for a setting that `objective` has no use for and that was given a value other than its default."""
+    for k, v in given.items():
+        d = defaults[k]
+        if (v is None) != (d is None) or v != d:
+            raise ValueError(f"{k}={v!r} does not apply to objective {objective!r} (leave it at its default {d!r})")
 
 
 class _Resident:
@@ -86,7 +102,9 @@ class TreeObjective:
 
     TreeObjective(labels, group, objective, ...) uploads the labels and the offsets ONCE and buckets the queries by length class once; a
     call moves only `preds` to the device and `grad` / `hess` back.  objective: 'ranknet' (pair_type 'All'), 'lambdarank' ('NoTies') or
-    'listnet'.  The defaults are the reference's wrappers: unweighted, epsilon 1, the rank-signed Hessian, gain 'Power'.  Opt-in, and not
+    'listnet', or 'lambdarank_ndcg' (the truncated, normalised lambdarank of the module docstring, with truncation_level, sigmoid and norm;
+    pair_type, weighting, epsilon, hessian and gain_type do not apply to it, and a non-default value raises; the other objectives ignore
+    its three settings).  The defaults are the reference's wrappers: unweighted, epsilon 1, the rank-signed Hessian, gain 'Power'.  Opt-in, and not
     what the reference computes: weighting='DeltaNDCG' (real LambdaMART) or 'DeltaGain', hessian='sum' (never negative) or 'constant'.
 
     __call__(preds) takes a numpy array of any float dtype and returns (grad, hess) as float64 numpy arrays, like the reference; the
@@ -94,18 +112,22 @@ class TreeObjective:
     objective for .fobj / .sklearn alone, which take both from their arguments.  There is no CPU path: without a GPU it raises."""
 
     def __init__(self, labels=None, group=None, objective="lambdarank", pair_type=None, weighting=None, epsilon=1.0, hessian="reference",
-                 gain_type="Power", device=None):
+                 gain_type="Power", device=None, truncation_level=30, sigmoid=1.0, norm=True):
         if objective not in OBJECTIVES:
             raise ValueError(f"objective {objective!r} (supported: {', '.join(map(repr, OBJECTIVES))})")
         self.objective = objective
         self.kind, default_pairs = OBJECTIVES[objective]
         self.pair_type = default_pairs if pair_type is None else pair_type
         self.weighting, self.epsilon, self.hessian, self.gain_type = weighting, float(epsilon), hessian, gain_type
+        self.truncation_level, self.sigmoid, self.norm = F.lambdarank_ndcg_settings(truncation_level, sigmoid, norm)
         if self.kind == "pair":
             F._enum("pair_type", self.pair_type, F.TREE_PAIR_TYPES)
             F._enum("weighting", weighting, F.TREE_WEIGHTINGS)
             if not self.epsilon >= 0.0:
                 raise ValueError(f"epsilon must be >= 0, got {epsilon!r}")
+        elif self.kind == "lambdarank_ndcg":
+            not_applicable(objective, dict(pair_type=pair_type, weighting=weighting, epsilon=epsilon, hessian=hessian, gain_type=gain_type),
+                           dict(pair_type=None, weighting=None, epsilon=1.0, hessian="reference", gain_type="Power"))
         else:
             F._enum("gain_type", gain_type, F.TREE_GAIN_TYPES)
         F._enum("hessian", hessian, F.TREE_HESSIANS)
@@ -131,6 +153,8 @@ class TreeObjective:
         for max_len, queries in res.buckets:
             if self.kind == "pair":
                 F.tree_pair_grad_hess(p, res.labels, res.offsets, self.pair_type, self.weighting, self.epsilon, self.hessian, queries, max_len, out)
+            elif self.kind == "lambdarank_ndcg":
+                F.tree_lambdarank_ndcg_grad_hess(p, res.labels, res.offsets, self.truncation_level, self.sigmoid, self.norm, queries, max_len, out)
             else:
                 F.tree_listnet_grad_hess(p, res.labels, res.offsets, self.gain_type, self.hessian, queries, max_len, out)
         both = torch.stack(out).cpu().numpy().astype(np.float64)           # one copy back; every document belongs to a launched query
