@@ -6,9 +6,11 @@
     python examples/train_lambdamart_native.py --bagging-fraction 0.5 --bagging-freq 1 --by-query   # every tree on a fresh half of the queries
     python examples/train_lambdamart_native.py --goss                            # gradient-based one-side sampling (top 0.2, other 0.1)
     python examples/train_lambdamart_native.py --objective lambdarank_ndcg       # the truncated, normalised lambdarank (level 30)
+    python examples/train_lambdamart_native.py --categorical 3,7                 # the columns 3 and 7 hold codes: set splits
 
 The synthetic relevance is planted: a linear part plus a feature interaction a linear scorer cannot express, graded with MSLR-WEB30K's label
-mix.  Prints the validation nDCG@5 every 10 rounds.  No LightGBM comparison: the library is not installed where this project is tested.
+mix; a column named by --categorical holds one of 23 codes, and membership in a scattered set of 5 of them lifts the relevance, which a
+node that cuts codes into "low" and "high" needs many splits to isolate.  Prints the validation nDCG@5 every 10 rounds.  No LightGBM comparison: the library is not installed where this project is tested.
 """
 import argparse
 import os
@@ -24,13 +26,20 @@ from ptranking_amd import letor   # noqa: E402
 MSLR_P = (0.5147, 0.3250, 0.1339, 0.0183, 0.0081)      # MSLR-WEB30K's grade frequencies, 0 .. 4
 
 
-def synthetic(queries, features, seed):
+CODES, PLANTED = 23, (1, 4, 7, 13, 20)
+
+
+def synthetic(queries, features, seed, categorical=()):
     rng = np.random.default_rng(seed)
     group = rng.integers(20, 120, queries)
     n = int(group.sum())
     X = rng.standard_normal((n, features)).astype(np.float32)
     w = np.random.default_rng(1).standard_normal(features) / np.sqrt(features)
+    w[list(categorical)] = 0.0
     s = X @ w + 0.8 * X[:, 0] * X[:, 1] + 0.5 * rng.standard_normal(n)
+    for f in categorical:
+        X[:, f] = rng.integers(0, CODES, n)
+        s = s + 0.9 * np.isin(X[:, f], PLANTED)
     y = np.digitize(s, np.quantile(s, np.cumsum(MSLR_P)[:-1])).astype(np.float32)
     return X, y, group
 
@@ -58,19 +67,22 @@ def main():
     ap.add_argument("--bagging-freq", type=int, default=0, help="redraw the bag every k trees; 0: no bagging")
     ap.add_argument("--by-query", action="store_true", help="bagging samples whole queries")
     ap.add_argument("--goss", action="store_true", help="data_sample_strategy='goss' in place of bagging")
+    ap.add_argument("--categorical", default="", help="0-based columns that hold integer codes, as in 3,7 (categorical_feature)")
     ap.add_argument("--queries", type=int, default=600)
     ap.add_argument("--features", type=int, default=40)
     args = ap.parse_args()
+    cats = tuple(int(c) for c in args.categorical.split(",") if c.strip())
     if args.files:
         train = from_file(args.files[0])
         valid = from_file(args.files[1]) if len(args.files) > 1 else train
         test = from_file(args.files[2]) if len(args.files) > 2 else valid
     else:
-        train, valid, test = synthetic(args.queries, args.features, 7), synthetic(args.queries // 4, args.features, 8), synthetic(args.queries // 4, args.features, 9)
+        train, valid, test = (synthetic(q, args.features, seed, cats) for q, seed in ((args.queries, 7), (args.queries // 4, 8), (args.queries // 4, 9)))
     params = {"num_leaves": args.num_leaves, "learning_rate": args.learning_rate, "min_data_in_leaf": args.min_data_in_leaf, "num_trees": args.rounds,
               "grow_policy": args.grow_policy, "bagging_fraction": args.bagging_fraction, "bagging_freq": args.bagging_freq,
               "bagging_by_query": args.by_query, "data_sample_strategy": "goss" if args.goss else "bagging",
-              "lambdarank_truncation_level": args.truncation_level, "lambdarank_norm": not args.no_norm, "sigmoid": args.sigmoid}
+              "lambdarank_truncation_level": args.truncation_level, "lambdarank_norm": not args.no_norm, "sigmoid": args.sigmoid,
+              "categorical_feature": cats}
     lm = pa.LambdaMART(params, objective=args.objective)
     how = {None: "none", "goss": f"goss (top_rate {lm.params['top_rate']}, other_rate {lm.params['other_rate']})",
            "bagging": f"bagging {args.bagging_fraction} {'by query' if args.by_query else 'by row'}, redrawn every {args.bagging_freq} trees"}
@@ -83,6 +95,9 @@ def main():
         if it % 10 == 0:
             print(f"round {it}: valid nDCG@5 {score:.4f}")
     yt = torch.from_numpy(test[1]).cuda()
+    if cats:
+        nodes = sum(int((t["cat_index"] >= 0).sum()) for t in lm.booster.trees)
+        print(f"categorical columns {list(cats)}: {nodes} of {sum(t['feature'].size for t in lm.booster.trees)} nodes split on a set of codes")
     print(f"test nDCG@5 {pa.LambdaMART.ndcg_at(lm.predict(test[0]), yt, test[2], 5):.4f} with {len(lm.booster.trees)} trees")
 
 

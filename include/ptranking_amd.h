@@ -1174,6 +1174,73 @@ int ptr_gbdt_predict_missing(const float *X, int64_t n, int F, const int32_t *fe
                              const int32_t *right, const float *value, const int32_t *tree_offsets, const uint8_t *default_left, int ntrees,
                              float *out, void *stream);
 
+/* ---- Categorical features: set splits (csrc/gbdt.hip; categorical_feature of ptranking_amd/gbdt.py).  ADDITIVE to ABI v8 too; every
+ * symbol above keeps its signature and its results bit for bit (each pair shares one kernel template, the older entry point passing "no
+ * categorical").  The rules are scikit-learn's (HistGradientBoostingRegressor(categorical_features=...), _find_best_bin_to_split_category)
+ * wherever its are deterministic, under LightGBM's parameter names; tests/gbdt_cat_ref.py restates them in numpy.  Out of scope:
+ * max_cat_to_onehot, cat_l2, min_data_per_group, max_cat_threshold.
+ *
+ * A categorical column holds integer codes; its edges are 0.5, 1.5, ..., so ptr_gbdt_bin maps code c to bin c and nbins[f] is the largest
+ * code plus 1.  is_cat [F] uint8 in device memory: non-zero marks a categorical feature.  nan_bin is as in the section above and may be
+ * NULL (no missing values): one _cat family serves both.  A left set is 256 bits in 4 int64, bit b in word b / 64.
+ *
+ * The rule, for a categorical feature at a node with totals (TG, TH, TC), the NaN bin included:
+ *   1. The categories are the value bins 0 .. nbins[f] - 1 and, where nan_bin[f] >= 0, the NaN bin.  G_c, H_c are the exact float64
+ *      values ldexp(qsum, -e), as in the numeric scan.
+ *   2. A category is USED iff it holds a row and H_c * (TC / TH) >= cat_smooth, in float64 in that order, nothing contracted (and its key
+ *      is a number: with cat_smooth = 0 a category of zero Hessian is not used).
+ *   3. Its key is v_c = G_c / (H_c + cat_smooth).
+ *   4. With u used categories, u <= 1 gives no split on this feature; otherwise the used categories are sorted ascending by v, equal keys
+ *      by the lower bin (scikit-learn's qsort leaves that open: the tie rule is this project's own).
+ *   5. Candidates.  Left to right: the first i + 1 sorted categories go left, i = 0 .. (u + 1) / 2 - 1.  Right to left: the last i + 1
+ *      go left, i = 0 .. (u + 1) / 2 - 2.  Unused categories and empty bins always go right.
+ *   6. Validity and gain: those of ptr_gbdt_best_split (min_data_in_leaf, the Hessian floor, min_gain_to_split, the uncontracted float64
+ *      gain over integer sums of the categories that go left).  scikit-learn's continue / break walk accepts the same candidates whenever
+ *      counts and Hessian sums grow along the scan.
+ *   7. Ties: the highest gain, then the lowest feature, then left-to-right before right-to-left, then the candidate with fewer categories
+ *      on the left (scikit-learn's first-found).
+ *   8. The record stays 9 int64 with the true left and right sums.  Field 2 is the number of left categories (at most 128) plus
+ *      256 * default_left; default_left is the NaN bin's bit in the left set, 0 without a NaN bin.  The left set goes to sets [nleaf][4];
+ *      a numeric winner, or a leaf without a split, leaves its set zero, and a numeric winner's record is the one ptr_gbdt_best_split
+ *      (nan_bin NULL) or ptr_gbdt_best_split_missing writes.
+ * ptr_gbdt_best_split_cat, ptr_gbdt_best_split_slots_cat: ws holds nleaf * F * 13 (K * F * 13) int64: the features' records, then their
+ *   sets.  cat_smooth must be finite and >= 0.  One wavefront per (leaf, feature) as before; a categorical feature ranks its keys by
+ *   counting (each lane's four keys broadcast in turn), permutes the sums through 6 KiB of LDS per wavefront and scans once for both
+ *   directions.  Integer sums and vector stores only: the bits depend on the histogram alone.
+ * ptr_gbdt_partition_cat: a row goes left iff, at a categorical feature, bit bins[row][feature] of set (4 int64 in device memory) is
+ *   set; at any other feature iff bins[row][feature] <= bin, or default_left (0 or 1) is set and the bin is nan_bin[feature].
+ * ptr_gbdt_partition_segments_cat: the same over segs [K][5] = (start, count, feature, bin, default_left) with sets [K][4] beside it.
+ * ptr_gbdt_add_tree_binned_cat, ptr_gbdt_predict_cat: cat_index [nodes] is -1 at a numeric node, else the node's set cat_sets[cat_index]
+ *   (ncat sets; over all trees in ptr_gbdt_predict_cat).  default_left [nodes] uint8 may be NULL (nothing goes left by default).  The
+ *   binned walk tests the bin's bit at a categorical node and bin <= bin[node] (or the NaN bin under default_left) at a numeric one.  The
+ *   raw walk turns x into a code at a categorical node: a NaN follows default_left; a value that is no integer in 0 .. 255 is in no
+ *   set and goes right, and so does a code the training data never held; otherwise the code's bit decides.  ptr_gbdt_predict_cat takes
+ *   no nan_bin: raw rows have no bins.  A malformed tree (a cat_index at or past ncat, a node whose kind is not its feature's) yields
+ *   NaN, never a read out of range.  Everything is validated before any launch. */
+int ptr_gbdt_best_split_cat(const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *nan_bin,
+                            const uint8_t *is_cat, const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf,
+                            double min_sum_hessian_in_leaf, double min_gain_to_split, double cat_smooth, int64_t *ws, int64_t *rec,
+                            int64_t *sets, void *stream);
+int ptr_gbdt_best_split_slots_cat(const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin, const int32_t *nbins,
+                                  const int32_t *nan_bin, const uint8_t *is_cat, const int32_t *expo, double lambda_l2,
+                                  int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double min_gain_to_split, double cat_smooth,
+                                  int64_t *ws, int64_t *rec, int64_t *sets, void *stream);
+int ptr_gbdt_partition_cat(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m, int feature, int bin,
+                           int default_left, const uint8_t *is_cat, const int32_t *nan_bin, const int64_t *set, int32_t *out,
+                           int32_t *left_count, int32_t *ws, void *stream);
+int ptr_gbdt_partition_segments_cat(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t nrows,
+                                    const int32_t *segs, const int64_t *sets, int K, const uint8_t *is_cat, const int32_t *nan_bin,
+                                    const int32_t *blocks, int nblocks, int32_t *out, int32_t *left_counts, int32_t *ws, int64_t ws_ints,
+                                    void *stream);
+int ptr_gbdt_add_tree_binned_cat(float *scores, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m,
+                                 const int32_t *feature, const int32_t *bin, const int32_t *left, const int32_t *right, const float *value,
+                                 const uint8_t *default_left, const uint8_t *is_cat, const int32_t *nan_bin, const int32_t *cat_index,
+                                 const int64_t *cat_sets, int ncat, int nnodes, void *stream);
+int ptr_gbdt_predict_cat(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                         const int32_t *right, const float *value, const int32_t *tree_offsets, const uint8_t *default_left,
+                         const uint8_t *is_cat, const int32_t *cat_index, const int64_t *cat_sets, int ncat, int ntrees, float *out,
+                         void *stream);
+
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):
  *   "<label> qid:<id> <fid>:<val> ... [# comment]", feature ids one-indexed unless one_indexed == 0 (Yahoo! sets,

@@ -296,23 +296,164 @@ __device__ __forceinline__ void gbdt_split_scan(const int64_t *__restrict__ hp, 
     }
 }
 
-template <bool kMissing> __global__ void __launch_bounds__(kBlock)
+// ---- categorical features (the *_cat entry points; categorical_feature of gbdt.py): a split sends a SET of bins left.
+constexpr int kSetWords = 4;             // a left set: 256 bits, bit b in word b / 64
+constexpr int kCatSorted = 3 * PTR_GBDT_MAX_BIN;   // int64 of LDS per wavefront: (G, H, C) of up to 256 categories in sorted order (6 KiB)
+
+// lane `src` (wave-uniform) of a double, through two v_readlane
+__device__ __forceinline__ double wave_read(double v, int src) {
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_readlane((int)b, src), hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
+    return __longlong_as_double((long long)(((u64)(uint32_t)hi << 32) | (uint32_t)lo));
+}
+
+struct GbdtCatArgs { const uint8_t *is_cat; double cat_smooth; int64_t *sets; };      // sets [items][kSetWords], beside the records
+
+// The scan of one categorical feature (include/ptranking_amd.h states the rule, tests/gbdt_cat_ref.py restates it).  Lane t owns the bins
+// 4 t .. 4 t + 3 as categories: the value bins below nbins[f] and, where nan_bin names one, the NaN bin.  A category is used iff it holds
+// rows, H_c (TC / TH) >= cat_smooth and its key v_c = G_c / (H_c + cat_smooth) is a number; an unused one carries the key NaN, which no
+// comparison counts.  The rank of a used category is the number of used ones ahead of it under (key, bin): every lane's four keys are
+// broadcast in turn (v_readlane; up to 256 rounds of 4 comparisons) — no sort network, and the order is total, so the ranks are a
+// permutation of 0 .. u - 1 whatever the keys.  The sums go to LDS at their rank and come back by position, lane t owning the sorted
+// positions 4 t .. 4 t + 3; one wave_scan_add pass then serves both directions: the left sums of "the first p + 1" are the prefix P[p], those
+// of "the last i + 1" the used total minus P[u - 2 - i].  A candidate's order key is i left to right and 256 + i right to left (i + 1
+// categories go left): the lowest key wins a tie, as in the numeric scan.  The winner's set is built from the ranks: a nibble per lane,
+// OR-ed over each group of 16 lanes into one 64-bit word, stored by the lanes 0, 16, 32 and 48.
+__device__ __forceinline__ void gbdt_split_scan_cat(const int64_t *__restrict__ hp, int f, int lane, int max_bin, const int32_t *__restrict__ nbins,
+                                                    const int32_t *__restrict__ nan_bin, const int32_t *__restrict__ expo, double l2, int64_t min_data,
+                                                    double min_hess, double min_gain, double cat_smooth, int64_t *sorted, int64_t *__restrict__ r,
+                                                    int64_t *__restrict__ set) {
+    const int nb = min(max(nbins[f], 1), max_bin);
+    int mbin = nan_bin ? nan_bin[f] : -1;
+    if (mbin < nb || mbin >= max_bin) mbin = -1;
+    const int span = mbin >= 0 ? mbin + 1 : nb;                         // no category at or behind this bin
+    int64_t cg[4], ch[4], cc[4], sg = 0, sh = 0, sc = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int b = lane * 4 + k;
+        const bool is = b < nb || b == mbin;
+        cg[k] = is ? hp[b * 3] : 0; ch[k] = is ? hp[b * 3 + 1] : 0; cc[k] = is ? hp[b * 3 + 2] : 0;
+        sg += cg[k]; sh += ch[k]; sc += cc[k];
+    }
+    const int64_t TG = __shfl(wave_scan_add(sg, lane), kWave - 1), TH = __shfl(wave_scan_add(sh, lane), kWave - 1),
+                  TC = __shfl(wave_scan_add(sc, lane), kWave - 1);
+    const int eg = expo[0], eh = expo[1];
+    const double G = ldexp((double)TG, -eg), H = ldexp((double)TH, -eh);
+    const double parent = (G * G) / (H + l2);
+    const double floor_h = fmax(min_hess, 0x1p-40);
+    const double factor = (double)TC / H;
+    double key[4];
+    int u = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double Gc = ldexp((double)cg[k], -eg), Hc = ldexp((double)ch[k], -eh);
+        const double v = Gc / (Hc + cat_smooth);
+        const bool used = cc[k] > 0 && Hc * factor >= cat_smooth && v == v;
+        key[k] = used ? v : (double)NAN;
+        u += __popcll(__ballot(used));
+    }
+    int rank[4] = {0, 0, 0, 0};
+    const int nl = (span + 3) >> 2;                                     // the lanes that own a category: at most 64
+    for (int s = 0; s < nl; ++s) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double ov = wave_read(key[j], s);
+            const int ob = s * 4 + j;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) rank[k] += (ov < key[k] || (ov == key[k] && ob < lane * 4 + k)) ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (key[k] == key[k]) {                                         // rank < the number of used categories <= 256: inside the wave's LDS
+            sorted[rank[k]] = cg[k]; sorted[PTR_GBDT_MAX_BIN + rank[k]] = ch[k]; sorted[2 * PTR_GBDT_MAX_BIN + rank[k]] = cc[k];
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");              // the wave's own stores, read back by other lanes of the same wave
+    __builtin_amdgcn_wave_barrier();
+    int64_t pg[4], ph[4], pc[4];
+    sg = sh = sc = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int p = lane * 4 + k;
+        if (p < u) { sg += sorted[p]; sh += sorted[PTR_GBDT_MAX_BIN + p]; sc += sorted[2 * PTR_GBDT_MAX_BIN + p]; }
+        pg[k] = sg; ph[k] = sh; pc[k] = sc;
+    }
+    const int64_t ig = wave_scan_add(sg, lane) - sg, ih = wave_scan_add(sh, lane) - sh, ic = wave_scan_add(sc, lane) - sc;
+    const int64_t UG = __shfl(ig + sg, kWave - 1), UH = __shfl(ih + sh, kWave - 1), UC = __shfl(ic + sc, kWave - 1);
+    const int mid = (u + 1) >> 1;
+    SplitCand best{-INFINITY, -1, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int p = lane * 4 + k;
+        if (u <= 1 || p >= u) continue;
+        const int64_t gl = ig + pg[k], hl = ih + ph[k], cl = ic + pc[k];
+        double gain;
+        if (p < mid && gbdt_split_gain(gl, hl, cl, TG, TH, TC, eg, eh, l2, min_data, floor_h, min_gain, parent, gain) &&
+            (gain > best.gain || (gain == best.gain && p < best.bin)))
+            best = SplitCand{gain, p, gl, hl, cl};                       // left to right: the first p + 1 sorted categories
+        const int i = u - 2 - p;                                        // right to left: the last i + 1, for i = 0 .. mid - 2
+        if (i >= 0 && i <= mid - 2 && gbdt_split_gain(UG - gl, UH - hl, UC - cl, TG, TH, TC, eg, eh, l2, min_data, floor_h, min_gain, parent, gain) &&
+            (gain > best.gain || (gain == best.gain && 256 + i < best.bin)))
+            best = SplitCand{gain, 256 + i, UG - gl, UH - hl, UC - cl};
+    }
+#pragma unroll
+    for (int d = kWave / 2; d >= 1; d >>= 1) {
+        const double og = __shfl_xor(best.gain, d);
+        const int ob = __shfl_xor(best.bin, d);
+        const int64_t o1 = __shfl_xor(best.gl, d), o2 = __shfl_xor(best.hl, d), o3 = __shfl_xor(best.cl, d);
+        if (ob >= 0 && (best.bin < 0 || og > best.gain || (og == best.gain && ob < best.bin))) best = SplitCand{og, ob, o1, o2, o3};
+    }
+    const bool ok = best.bin >= 0;                                      // the same in every lane: the order of the candidates is total
+    const int rtl = best.bin >> 8, i = best.bin & 255;
+    uint32_t nib = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const bool in = ok && key[k] == key[k] && (rtl ? rank[k] >= u - 1 - i : rank[k] <= i);
+        nib |= (in ? 1u : 0u) << k;
+    }
+    u64 word = (u64)nib << ((lane & 15) * 4);
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) word |= __shfl_xor(word, d);
+    if ((lane & 15) == 0) set[lane >> 4] = (int64_t)word;
+    const int dl = mbin >= 0 ? (int)((__shfl(nib, mbin >> 2) >> (mbin & 3)) & 1u) : 0;      // the NaN bin's bit
+    if (lane == 0) {
+        r[0] = __double_as_longlong(ok ? best.gain : -INFINITY);
+        r[1] = ok ? f : -1;
+        r[2] = ok ? (i + 1) + 256 * dl : -1;
+        r[3] = best.gl; r[4] = best.hl; r[5] = best.cl;
+        r[6] = ok ? TG - best.gl : 0; r[7] = ok ? TH - best.hl : 0; r[8] = ok ? TC - best.cl : 0;
+    }
+}
+
+// kCat (the *_cat entry points): a feature with is_cat[f] != 0 takes the categorical scan, any other the numeric one and a zero set; the
+// branch is uniform for the wavefront.  Without kCat the kernel holds neither the branch nor the LDS.
+template <bool kMissing, bool kCat> __global__ void __launch_bounds__(kBlock)
 gbdt_split_feature_kernel(const int64_t *__restrict__ hist, int nleaf, int F, int max_bin, const int32_t *__restrict__ nbins,
                           const int32_t *__restrict__ nan_bin, const int32_t *__restrict__ expo, double l2, int64_t min_data, double min_hess,
-                          double min_gain, int64_t *__restrict__ ws) {
+                          double min_gain, int64_t *__restrict__ ws, const GbdtCatArgs cat) {
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t item = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
     if (item >= (int64_t)nleaf * F) return;
-    gbdt_split_scan<kMissing>(hist + item * max_bin * 3, (int)(item % F), lane, max_bin, nbins, nan_bin, expo, l2, min_data, min_hess, min_gain,
-                              ws + item * kRec);
+    const int f = (int)(item % F);
+    if constexpr (kCat) {
+        __shared__ int64_t cat_sorted[kBlock / kWave][kCatSorted];
+        if (cat.is_cat[f]) {
+            gbdt_split_scan_cat(hist + item * max_bin * 3, f, lane, max_bin, nbins, kMissing ? nan_bin : nullptr, expo, l2, min_data, min_hess, min_gain,
+                                cat.cat_smooth, cat_sorted[threadIdx.x >> 6], ws + item * kRec, cat.sets + item * kSetWords);
+            return;
+        }
+        if (lane < kSetWords) cat.sets[item * kSetWords + lane] = 0;
+    }
+    gbdt_split_scan<kMissing>(hist + item * max_bin * 3, f, lane, max_bin, nbins, nan_bin, expo, l2, min_data, min_hess, min_gain, ws + item * kRec);
 }
 
 // The same scan over a list of K slots of a histogram pool [nslots][F][max_bin][3]: item = (k, feature).  A slot outside the pool gives the
 // record of a leaf without a split, and is never read.
-template <bool kMissing> __global__ void __launch_bounds__(kBlock)
+template <bool kMissing, bool kCat> __global__ void __launch_bounds__(kBlock)
 gbdt_split_feature_slots_kernel(const int64_t *__restrict__ pool, int nslots, const int32_t *__restrict__ slots, int K, int F, int max_bin,
                                 const int32_t *__restrict__ nbins, const int32_t *__restrict__ nan_bin, const int32_t *__restrict__ expo, double l2,
-                                int64_t min_data, double min_hess, double min_gain, int64_t *__restrict__ ws) {
+                                int64_t min_data, double min_hess, double min_gain, int64_t *__restrict__ ws, const GbdtCatArgs cat) {
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t item = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
     if (item >= (int64_t)K * F) return;
@@ -321,14 +462,26 @@ gbdt_split_feature_slots_kernel(const int64_t *__restrict__ pool, int nslots, co
     int64_t *r = ws + item * kRec;
     if (slot < 0 || slot >= nslots) {
         if (lane < kRec) r[lane] = gbdt_no_split(lane);
+        if (kCat && lane < kSetWords) cat.sets[item * kSetWords + lane] = 0;
         return;
     }
-    gbdt_split_scan<kMissing>(pool + ((int64_t)slot * F + f) * max_bin * 3, f, lane, max_bin, nbins, nan_bin, expo, l2, min_data, min_hess, min_gain, r);
+    const int64_t *hp = pool + ((int64_t)slot * F + f) * max_bin * 3;
+    if constexpr (kCat) {
+        __shared__ int64_t cat_sorted[kBlock / kWave][kCatSorted];
+        if (cat.is_cat[f]) {
+            gbdt_split_scan_cat(hp, f, lane, max_bin, nbins, kMissing ? nan_bin : nullptr, expo, l2, min_data, min_hess, min_gain, cat.cat_smooth,
+                                cat_sorted[threadIdx.x >> 6], r, cat.sets + item * kSetWords);
+            return;
+        }
+        if (lane < kSetWords) cat.sets[item * kSetWords + lane] = 0;
+    }
+    gbdt_split_scan<kMissing>(hp, f, lane, max_bin, nbins, nan_bin, expo, l2, min_data, min_hess, min_gain, r);
 }
 
-// One wavefront per leaf: the best of its F feature records, ties to the lowest feature.
+// One wavefront per leaf: the best of its F feature records, ties to the lowest feature.  sets (NULL: none): the winner's left set, from
+// ws_sets [leaves][F][kSetWords], zero for a leaf without a split.
 __global__ void __launch_bounds__(kWave)
-gbdt_split_leaf_kernel(const int64_t *__restrict__ ws, int F, int64_t *__restrict__ rec) {
+gbdt_split_leaf_kernel(const int64_t *__restrict__ ws, int F, int64_t *__restrict__ rec, const int64_t *__restrict__ ws_sets, int64_t *__restrict__ sets) {
     const int lane = threadIdx.x;
     const int64_t *w = ws + (int64_t)blockIdx.x * F * kRec;
     double bg = -INFINITY;
@@ -346,6 +499,8 @@ gbdt_split_leaf_kernel(const int64_t *__restrict__ ws, int F, int64_t *__restric
     if (lane < kRec) {
         rec[(int64_t)blockIdx.x * kRec + lane] = bf >= 0 ? w[(int64_t)bf * kRec + lane] : gbdt_no_split(lane);
     }
+    if (sets && lane >= 16 && lane < 16 + kSetWords)
+        sets[(int64_t)blockIdx.x * kSetWords + lane - 16] = bf >= 0 ? ws_sets[((int64_t)blockIdx.x * F + bf) * kSetWords + lane - 16] : 0;
 }
 
 // ---------------------------------------------------------------- the stable partition
@@ -361,6 +516,20 @@ struct PartByBin {                                                      // bins[
         if (row < 0 || row >= n) return false;
         const int b = bins[(size_t)row * stride + feature];
         return b <= bin || b == also_left;                              // also_left: the NaN bin of a split whose missing rows go left, or -1
+    }
+};
+// the *_cat partitions: at a categorical feature (is_cat[feature] != 0) bit bins[row][feature] of the node's set (4 int64 in device
+// memory); at any other one PartByBin's rule, the NaN bin nan_bin[feature] going left under default_left.  The three tables are read as
+// they are found: every load is uniform for the workgroup, and a bin indexes the 256 bits of a set whatever it is.
+struct PartBySet {
+    const uint8_t *bins; int stride, n; const int32_t *rows; int m, feature, bin, default_left;
+    const uint8_t *is_cat; const int32_t *nan_bin; const int64_t *set;
+    __device__ __forceinline__ bool operator()(int64_t i, int &row) const {
+        row = i < m ? rows[i] : -1;
+        if (row < 0 || row >= n) return false;
+        const int b = bins[(size_t)row * stride + feature];
+        if (is_cat[feature]) return (((u64)set[b >> 6]) >> (b & 63)) & 1ull;
+        return b <= bin || (default_left && nan_bin && b == nan_bin[feature]);
     }
 };
 struct PartByMask {                                                     // ptr_gbdt_partition_mask: mask[row] != 0; rows == NULL: the list 0 .. m - 1
@@ -524,29 +693,40 @@ __device__ __forceinline__ GbdtPartSeg gbdt_part_block(const int32_t *__restrict
     return s;
 }
 
-__global__ void __launch_bounds__(kBlock)
+// kCat (ptr_gbdt_partition_segments_cat): the fifth column of a segment is default_left, and segment k splits under PartBySet with the set
+// cat.sets[k]; without it the kernels are the ones they were.
+struct GbdtCatSegs { const uint8_t *is_cat; const int32_t *nan_bin; const int64_t *sets; };
+__device__ __forceinline__ PartBySet gbdt_part_by_set(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ rows,
+                                                      const GbdtPartSeg &s, int k, const GbdtCatSegs &cat) {
+    return PartBySet{bins, stride, n, rows + s.start, s.count, s.feature, s.bin, s.also_left > 0 ? 1 : 0, cat.is_cat, cat.nan_bin, cat.sets + (int64_t)k * kSetWords};
+}
+
+template <bool kCat> __global__ void __launch_bounds__(kBlock)
 gbdt_part_seg_count_kernel(const uint8_t *__restrict__ bins, int stride, int n, int F, const int32_t *__restrict__ rows, int64_t nrows,
-                           const int32_t *__restrict__ segs, int cols, int K, const int32_t *__restrict__ blocks, int NB, int32_t *__restrict__ counts) {
+                           const int32_t *__restrict__ segs, int cols, int K, const int32_t *__restrict__ blocks, int NB, int32_t *__restrict__ counts,
+                           const GbdtCatSegs cat) {
     int j;
     const GbdtPartSeg s = gbdt_part_block(segs, cols, K, blocks, blockIdx.x, NB, nrows, F, j);
     if (!s.ok) { if (threadIdx.x == 0) counts[blockIdx.x] = 0; return; }
-    part_count(PartByBin{bins, stride, n, rows + s.start, s.count, s.feature, s.bin, s.also_left}, j, counts + blockIdx.x);
+    if constexpr (kCat) part_count(gbdt_part_by_set(bins, stride, n, rows, s, blocks[blockIdx.x * 2], cat), j, counts + blockIdx.x);
+    else part_count(PartByBin{bins, stride, n, rows + s.start, s.count, s.feature, s.bin, s.also_left}, j, counts + blockIdx.x);
 }
 
 // counts: the exclusive prefix over the blocks of all segments (gbdt_part_scan_kernel); the lefts ahead of block b in its segment are
 // prefix[b] - prefix[b - j], which is the segmented scan.  A table that lies about its blocks cannot leave the segment (part_scatter).
-__global__ void __launch_bounds__(kBlock)
+template <bool kCat> __global__ void __launch_bounds__(kBlock)
 gbdt_part_seg_scatter_kernel(const uint8_t *__restrict__ bins, int stride, int n, int F, const int32_t *__restrict__ rows, int64_t nrows,
                              const int32_t *__restrict__ segs, int cols, int K, const int32_t *__restrict__ blocks, int NB,
-                             const int32_t *__restrict__ counts, int32_t *__restrict__ out, int32_t *__restrict__ left_counts) {
+                             const int32_t *__restrict__ counts, int32_t *__restrict__ out, int32_t *__restrict__ left_counts, const GbdtCatSegs cat) {
     int j;
     const GbdtPartSeg s = gbdt_part_block(segs, cols, K, blocks, blockIdx.x, NB, nrows, F, j);
     if (!s.ok) return;
     const int first = blockIdx.x - j;
     const int total_left = counts[first + s.nblk] - counts[first];
     if (j == 0 && threadIdx.x == 0) left_counts[blocks[blockIdx.x * 2]] = total_left;
-    part_scatter(PartByBin{bins, stride, n, rows + s.start, s.count, s.feature, s.bin, s.also_left}, j, counts[blockIdx.x] - counts[first], total_left,
-                 out + s.start);
+    if constexpr (kCat) part_scatter(gbdt_part_by_set(bins, stride, n, rows, s, blocks[blockIdx.x * 2], cat), j, counts[blockIdx.x] - counts[first], total_left, out + s.start);
+    else part_scatter(PartByBin{bins, stride, n, rows + s.start, s.count, s.feature, s.bin, s.also_left}, j, counts[blockIdx.x] - counts[first], total_left,
+                      out + s.start);
 }
 
 // ---------------------------------------------------------------- leaf values and prediction
@@ -580,41 +760,74 @@ template <class GoesLeft> __device__ __forceinline__ int gbdt_walk(int nn, int F
 }
 __device__ __forceinline__ bool gbdt_is_leaf(int node, int nn) { return node < 0 && ~node <= nn; }
 
-__global__ void __launch_bounds__(kBlock)
+// The categorical nodes of a walk (the *_cat entry points): cat_index [nodes] is -1 at a numeric node, else the node's left set
+// cat_sets[cat_index] (kSetWords int64 each, ncat of them).  The tables are device memory and read as untrusted: an index at or past ncat,
+// or a node whose kind is not its feature's (is_cat [F]), is a malformed tree: -2, which the walks turn into NaN.
+struct GbdtCatWalk { const uint8_t *is_cat; const int32_t *cat_index; const int64_t *cat_sets; int ncat; };
+__device__ __forceinline__ int gbdt_cat_node(const GbdtCatWalk &c, int node, int f) {
+    const int ci = c.cat_index[node];
+    const bool isc = c.is_cat[f] != 0;
+    if (ci < 0) return isc ? -2 : -1;
+    return isc && ci < c.ncat ? ci : -2;
+}
+__device__ __forceinline__ bool gbdt_in_set(const int64_t *__restrict__ set, int b) { return (((u64)set[b >> 6]) >> (b & 63)) & 1ull; }     // b in 0 .. 255
+
+template <bool kCat> __global__ void __launch_bounds__(kBlock)
 gbdt_predict_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t *__restrict__ feature, const float *__restrict__ threshold,
                     const int32_t *__restrict__ left, const int32_t *__restrict__ right, const float *__restrict__ value,
-                    const int32_t *__restrict__ tree_offsets, const uint8_t *__restrict__ default_left, int ntrees, float *__restrict__ out) {
+                    const int32_t *__restrict__ tree_offsets, const uint8_t *__restrict__ default_left, int ntrees, float *__restrict__ out,
+                    const GbdtCatWalk cat) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const float *x = X + i * F;
     float s = 0.0f;
     for (int t = 0; t < ntrees; ++t) {
         const int base = tree_offsets[t], nn = tree_offsets[t + 1] - base, leaves = base + t;      // a tree of nn nodes has nn + 1 leaves
+        bool bad = false;
         const int node = gbdt_walk(nn, F, feature + base, left + base, right + base, [&](int at, int f) {
             const float xv = x[f];
+            if constexpr (kCat) {
+                const int ci = gbdt_cat_node(cat, base + at, f);
+                if (ci == -2) { bad = true; return false; }
+                if (ci >= 0) {                                          // a NaN follows the node's direction; what is no code 0 .. 255 is in no set
+                    if (xv != xv) return default_left && default_left[base + at] != 0;
+                    if (!(xv >= 0.0f && xv <= 255.0f)) return false;
+                    const int c = (int)xv;
+                    return (float)c == xv && gbdt_in_set(cat.cat_sets + (int64_t)ci * kSetWords, c);
+                }
+            }
             return (default_left && xv != xv) ? default_left[base + at] != 0 : xv <= threshold[base + at];   // a NaN follows the node's direction
         });
-        s += gbdt_is_leaf(node, nn) ? value[leaves + ~node] : NAN;      // a malformed tree gives NaN
+        s += gbdt_is_leaf(node, nn) && !bad ? value[leaves + ~node] : NAN;      // a malformed tree gives NaN
     }
     out[i] = s;
 }
 
 // One finished tree over the BINNED rows of a row list: x <= edges[f][b] is bin <= b, so the walk lands in the leaf ptr_gbdt_predict finds on
 // the raw row, and the same fp32 value is added.  The rows a sampled tree was not grown on get their leaf value here.
-__global__ void __launch_bounds__(kBlock)
+// kCat: also_left is NULL, and a numeric node sends the NaN bin nan_bin[f] left where default_left[node] is set (both may be NULL).
+template <bool kCat> __global__ void __launch_bounds__(kBlock)
 gbdt_add_tree_binned_kernel(float *__restrict__ scores, const uint8_t *__restrict__ bins, int stride, int n, int F, const int32_t *__restrict__ rows,
                             int m, const int32_t *__restrict__ feature, const int32_t *__restrict__ bin, const int32_t *__restrict__ left,
-                            const int32_t *__restrict__ right, const float *__restrict__ value, const int32_t *__restrict__ also_left, int nn) {
+                            const int32_t *__restrict__ right, const float *__restrict__ value, const int32_t *__restrict__ also_left, int nn,
+                            const uint8_t *__restrict__ default_left, const int32_t *__restrict__ nan_bin, const GbdtCatWalk cat) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= m) return;
     const int row = rows ? rows[i] : i;
     if (row < 0 || row >= n) return;
     const uint8_t *x = bins + (size_t)row * stride;
+    bool bad = false;
     const int node = gbdt_walk(nn, F, feature, left, right, [&](int at, int f) {
         const int b = x[f];
+        if constexpr (kCat) {
+            const int ci = gbdt_cat_node(cat, at, f);
+            if (ci == -2) { bad = true; return false; }
+            if (ci >= 0) return gbdt_in_set(cat.cat_sets + (int64_t)ci * kSetWords, b);
+            return b <= bin[at] || (default_left && nan_bin && default_left[at] != 0 && b == nan_bin[f]);
+        }
         return b <= bin[at] || (also_left && b == also_left[at]);
     });
-    scores[row] += gbdt_is_leaf(node, nn) ? value[~node] : NAN;         // a malformed tree gives NaN
+    scores[row] += gbdt_is_leaf(node, nn) && !bad ? value[~node] : NAN;         // a malformed tree gives NaN
 }
 
 // ---------------------------------------------------------------- row sampling: the bag and GOSS
@@ -822,12 +1035,23 @@ extern "C" int ptr_gbdt_hist_sub(const int64_t *parent, const int64_t *child, in
     return check_hip(hipGetLastError(), who);
 }
 
+// The categorical form of a split search (the *_cat entry points): is_cat == NULL is "no categorical".  ws then holds the items' records
+// and, behind them, their sets: items * (kRec + kSetWords) int64.
+struct GbdtCatSearch { const uint8_t *is_cat; double cat_smooth; int64_t *sets; };
+static int check_cat_search(const GbdtCatSearch &cat, bool on, int F, const char *who) {
+    if (!on) return 0;
+    if (!(cat.cat_smooth >= 0.0) || cat.cat_smooth > 1.79769313486231570e308) { set_error("%s: cat_smooth must be a finite number >= 0, got %g", who, cat.cat_smooth); return PTR_ERR_INVALID_ARG; }
+    if (!cat.sets || (F > 0 && !cat.is_cat)) { set_error("%s: NULL pointer (is_cat or sets)", who); return PTR_ERR_INVALID_ARG; }
+    return 0;
+}
+
 static int gbdt_best_split_impl(const char *who, const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *nan_bin,
                                 bool missing, const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf, double min_sum_hessian_in_leaf,
-                                double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream) {
+                                double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream, bool cat_on = false, GbdtCatSearch cat = {nullptr, 0.0, nullptr}) {
     if (nleaf < 0 || F < 0) { set_error("%s: negative size (nleaf=%d, F=%d)", who, nleaf, F); return PTR_ERR_INVALID_ARG; }
     if (int rc = check_max_bin(max_bin, who)) return rc;
     if (int rc = check_split_thresholds(lambda_l2, min_sum_hessian_in_leaf, min_gain_to_split, who)) return rc;
+    if (int rc = check_cat_search(cat, cat_on && nleaf > 0, F, who)) return rc;
     if (nleaf == 0) return 0;
     if (!rec || (F > 0 && (!hist || !nbins || !expo || !ws || (missing && !nan_bin)))) {
         set_error("%s: NULL pointer (hist, nbins%s, expo, ws or rec)", who, missing ? ", nan_bin" : "");
@@ -835,13 +1059,16 @@ static int gbdt_best_split_impl(const char *who, const int64_t *hist, int nleaf,
     }
     const int64_t items = (int64_t)nleaf * F;
     const dim3 grid((unsigned)((items + 3) / 4));
-    if (items > 0 && missing)
-        hipLaunchKernelGGL(gbdt_split_feature_kernel<true>, grid, dim3(kBlock), 0, as_stream(stream), hist, nleaf, F, max_bin, nbins, nan_bin, expo, lambda_l2,
-                           min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws);
-    else if (items > 0)
-        hipLaunchKernelGGL(gbdt_split_feature_kernel<false>, grid, dim3(kBlock), 0, as_stream(stream), hist, nleaf, F, max_bin, nbins, nan_bin, expo, lambda_l2,
-                           min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws);
-    hipLaunchKernelGGL(gbdt_split_leaf_kernel, dim3(nleaf), dim3(kWave), 0, as_stream(stream), ws, F, rec);
+    int64_t *ws_sets = cat_on ? ws + items * kRec : nullptr;
+    const GbdtCatArgs ca{cat.is_cat, cat.cat_smooth, ws_sets};
+#define PTR_LAUNCH_SPLIT(M, C)                                                                                                                        \
+    hipLaunchKernelGGL((gbdt_split_feature_kernel<M, C>), grid, dim3(kBlock), 0, as_stream(stream), hist, nleaf, F, max_bin, nbins, nan_bin, expo, lambda_l2, \
+                       min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws, ca)
+    if (items > 0 && cat_on) { if (missing) PTR_LAUNCH_SPLIT(true, true); else PTR_LAUNCH_SPLIT(false, true); }
+    else if (items > 0 && missing) PTR_LAUNCH_SPLIT(true, false);
+    else if (items > 0) PTR_LAUNCH_SPLIT(false, false);
+#undef PTR_LAUNCH_SPLIT
+    hipLaunchKernelGGL(gbdt_split_leaf_kernel, dim3(nleaf), dim3(kWave), 0, as_stream(stream), ws, F, rec, ws_sets, cat_on ? cat.sets : nullptr);
     return check_hip(hipGetLastError(), who);
 }
 
@@ -857,6 +1084,14 @@ extern "C" int ptr_gbdt_best_split_missing(const int64_t *hist, int nleaf, int F
                                            double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream) {
     return gbdt_best_split_impl("ptr_gbdt_best_split_missing", hist, nleaf, F, max_bin, nbins, nan_bin, true, expo, lambda_l2, min_data_in_leaf,
                                 min_sum_hessian_in_leaf, min_gain_to_split, ws, rec, stream);
+}
+
+extern "C" int ptr_gbdt_best_split_cat(const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *nan_bin,
+                                       const uint8_t *is_cat, const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf,
+                                       double min_sum_hessian_in_leaf, double min_gain_to_split, double cat_smooth, int64_t *ws, int64_t *rec,
+                                       int64_t *sets, void *stream) {
+    return gbdt_best_split_impl("ptr_gbdt_best_split_cat", hist, nleaf, F, max_bin, nbins, nan_bin, nan_bin != nullptr, expo, lambda_l2, min_data_in_leaf,
+                                min_sum_hessian_in_leaf, min_gain_to_split, ws, rec, stream, true, GbdtCatSearch{is_cat, cat_smooth, sets});
 }
 
 extern "C" size_t ptr_gbdt_partition_ws_ints(int64_t m) {
@@ -877,6 +1112,25 @@ static int gbdt_partition_impl(const char *who, const uint8_t *bins, int stride,
     if (!bins || !rows || !out || !ws) { set_error("%s: NULL pointer (bins, rows, out or ws)", who); return PTR_ERR_INVALID_ARG; }
     const int nb = (int)ptr_gbdt_partition_ws_ints(m) - 1;
     return launch_partition(PartByBin{bins, stride, (int)n, rows, (int)m, feature, bin, also_left}, nb, out, left_count, ws, as_stream(stream), who);
+}
+
+extern "C" int ptr_gbdt_partition_cat(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m, int feature, int bin,
+                                      int default_left, const uint8_t *is_cat, const int32_t *nan_bin, const int64_t *set, int32_t *out,
+                                      int32_t *left_count, int32_t *ws, void *stream) {
+    const char *who = "ptr_gbdt_partition_cat";
+    if (int rc = check_bins_layout(n, F, stride, who)) return rc;
+    if (m < 0 || m > INT32_MAX) { set_error("%s: bad row count m=%lld", who, (long long)m); return PTR_ERR_INVALID_ARG; }
+    if (feature < 0 || feature >= F || bin < 0 || bin > 255) {
+        set_error("%s: feature must be in 0 .. F - 1 and bin in 0 .. 255 (feature=%d, F=%d, bin=%d)", who, feature, F, bin);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (default_left != 0 && default_left != 1) { set_error("%s: default_left must be 0 or 1, got %d", who, default_left); return PTR_ERR_INVALID_ARG; }
+    if (!left_count || !is_cat || !set) { set_error("%s: NULL pointer (left_count, is_cat or set)", who); return PTR_ERR_INVALID_ARG; }
+    if (m == 0) return check_hip(hipMemsetAsync(left_count, 0, sizeof(int32_t), as_stream(stream)), who);
+    if (!bins || !rows || !out || !ws) { set_error("%s: NULL pointer (bins, rows, out or ws)", who); return PTR_ERR_INVALID_ARG; }
+    const int nb = (int)ptr_gbdt_partition_ws_ints(m) - 1;
+    return launch_partition(PartBySet{bins, stride, (int)n, rows, (int)m, feature, bin, default_left, is_cat, nan_bin, set}, nb, out, left_count, ws,
+                            as_stream(stream), who);
 }
 
 extern "C" int ptr_gbdt_partition(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m, int feature, int bin,
@@ -905,7 +1159,7 @@ extern "C" int ptr_gbdt_add_leaf_values(float *scores, int64_t n, const int32_t 
 
 static int gbdt_predict_impl(const char *who, const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
                              const int32_t *right, const float *value, const int32_t *tree_offsets, const uint8_t *default_left, bool missing, int ntrees,
-                             float *out, void *stream) {
+                             float *out, void *stream, bool cat_on = false, GbdtCatWalk cat = {nullptr, nullptr, nullptr, 0}) {
     if (n < 0 || F < 0 || ntrees < 0) { set_error("%s: negative size (n=%lld, F=%d, ntrees=%d)", who, (long long)n, F, ntrees); return PTR_ERR_INVALID_ARG; }
     if (n == 0) return 0;
     if (!out || (F > 0 && !X)) { set_error("%s: NULL pointer (X or out)", who); return PTR_ERR_INVALID_ARG; }
@@ -913,9 +1167,34 @@ static int gbdt_predict_impl(const char *who, const float *X, int64_t n, int F, 
         set_error("%s: NULL tree array", who);
         return PTR_ERR_INVALID_ARG;
     }
-    hipLaunchKernelGGL(gbdt_predict_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), X, n, F, feature, threshold, left,
-                       right, value, tree_offsets, default_left, ntrees, out);
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+    if (cat_on)
+        hipLaunchKernelGGL(gbdt_predict_kernel<true>, grid, dim3(kBlock), 0, as_stream(stream), X, n, F, feature, threshold, left, right, value, tree_offsets,
+                           default_left, ntrees, out, cat);
+    else
+        hipLaunchKernelGGL(gbdt_predict_kernel<false>, grid, dim3(kBlock), 0, as_stream(stream), X, n, F, feature, threshold, left, right, value, tree_offsets,
+                           default_left, ntrees, out, cat);
     return check_hip(hipGetLastError(), who);
+}
+
+// what the two walks ask of their categorical tables before a launch
+static int check_cat_walk(const GbdtCatWalk &cat, bool any_nodes, int F, const char *who) {
+    if (cat.ncat < 0) { set_error("%s: negative size (ncat=%d)", who, cat.ncat); return PTR_ERR_INVALID_ARG; }
+    if (any_nodes && ((F > 0 && !cat.is_cat) || !cat.cat_index || (cat.ncat > 0 && !cat.cat_sets))) {
+        set_error("%s: NULL pointer (is_cat, cat_index or cat_sets)", who);
+        return PTR_ERR_INVALID_ARG;
+    }
+    return 0;
+}
+
+extern "C" int ptr_gbdt_predict_cat(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                    const int32_t *right, const float *value, const int32_t *tree_offsets, const uint8_t *default_left,
+                                    const uint8_t *is_cat, const int32_t *cat_index, const int64_t *cat_sets, int ncat, int ntrees, float *out,
+                                    void *stream) {
+    const char *who = "ptr_gbdt_predict_cat";
+    const GbdtCatWalk cat{is_cat, cat_index, cat_sets, ncat};
+    if (int rc = check_cat_walk(cat, n > 0 && ntrees > 0, F, who)) return rc;
+    return gbdt_predict_impl(who, X, n, F, feature, threshold, left, right, value, tree_offsets, default_left, false, ntrees, out, stream, true, cat);
 }
 
 extern "C" int ptr_gbdt_predict(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
@@ -990,7 +1269,8 @@ extern "C" int ptr_gbdt_partition_mask(const uint8_t *mask, int64_t n, const int
 
 static int gbdt_add_tree_binned_impl(const char *who, float *scores, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m,
                                      const int32_t *feature, const int32_t *bin, const int32_t *left, const int32_t *right, const float *value,
-                                     const int32_t *also_left, bool missing, int nnodes, void *stream) {
+                                     const int32_t *also_left, bool missing, int nnodes, void *stream, bool cat_on = false,
+                                     const uint8_t *default_left = nullptr, const int32_t *nan_bin = nullptr, GbdtCatWalk cat = {nullptr, nullptr, nullptr, 0}) {
     if (int rc = check_bins_layout(n, F, stride, who)) return rc;
     if (m < 0 || m > INT32_MAX || nnodes < 0) { set_error("%s: bad size (m=%lld, nnodes=%d)", who, (long long)m, nnodes); return PTR_ERR_INVALID_ARG; }
     if (!rows && m > n) { set_error("%s: rows is NULL (the first m rows), so m must not exceed n (m=%lld, n=%lld)", who, (long long)m, (long long)n); return PTR_ERR_INVALID_ARG; }
@@ -999,9 +1279,25 @@ static int gbdt_add_tree_binned_impl(const char *who, float *scores, const uint8
         set_error("%s: NULL pointer (scores, bins, value or a tree array)", who);
         return PTR_ERR_INVALID_ARG;
     }
-    hipLaunchKernelGGL(gbdt_add_tree_binned_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), scores, bins, stride,
-                       (int)n, F, rows, (int)m, feature, bin, left, right, value, also_left, nnodes);
+    const dim3 grid((unsigned)((m + kBlock - 1) / kBlock));
+    if (cat_on)
+        hipLaunchKernelGGL(gbdt_add_tree_binned_kernel<true>, grid, dim3(kBlock), 0, as_stream(stream), scores, bins, stride, (int)n, F, rows, (int)m, feature, bin,
+                           left, right, value, also_left, nnodes, default_left, nan_bin, cat);
+    else
+        hipLaunchKernelGGL(gbdt_add_tree_binned_kernel<false>, grid, dim3(kBlock), 0, as_stream(stream), scores, bins, stride, (int)n, F, rows, (int)m, feature, bin,
+                           left, right, value, also_left, nnodes, default_left, nan_bin, cat);
     return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_add_tree_binned_cat(float *scores, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m,
+                                            const int32_t *feature, const int32_t *bin, const int32_t *left, const int32_t *right, const float *value,
+                                            const uint8_t *default_left, const uint8_t *is_cat, const int32_t *nan_bin, const int32_t *cat_index,
+                                            const int64_t *cat_sets, int ncat, int nnodes, void *stream) {
+    const char *who = "ptr_gbdt_add_tree_binned_cat";
+    const GbdtCatWalk cat{is_cat, cat_index, cat_sets, ncat};
+    if (int rc = check_cat_walk(cat, m > 0 && n > 0 && nnodes > 0, F, who)) return rc;
+    return gbdt_add_tree_binned_impl(who, scores, bins, stride, n, F, rows, m, feature, bin, left, right, value, nullptr, false, nnodes, stream, true,
+                                     default_left, nan_bin, cat);
 }
 
 extern "C" int ptr_gbdt_add_tree_binned(float *scores, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t m,
@@ -1066,10 +1362,11 @@ extern "C" int ptr_gbdt_hist_sub_segments(int64_t *pool, int nslots, int F, int 
 static int gbdt_best_split_slots_impl(const char *who, const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin,
                                       const int32_t *nbins, const int32_t *nan_bin, bool missing, const int32_t *expo, double lambda_l2,
                                       int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double min_gain_to_split, int64_t *ws, int64_t *rec,
-                                      void *stream) {
+                                      void *stream, bool cat_on = false, GbdtCatSearch cat = {nullptr, 0.0, nullptr}) {
     if (int rc = check_level_common(who, 0, F, 0, max_bin, K, kCheckMaxBin)) return rc;
     if (nslots < 0) { set_error("%s: negative size (nslots=%d)", who, nslots); return PTR_ERR_INVALID_ARG; }
     if (int rc = check_split_thresholds(lambda_l2, min_sum_hessian_in_leaf, min_gain_to_split, who)) return rc;
+    if (int rc = check_cat_search(cat, cat_on && K > 0, F, who)) return rc;
     if (K == 0) return 0;
     if (!pool || !slots || !nbins || !expo || !ws || !rec || (missing && !nan_bin)) {
         set_error("%s: NULL pointer (pool, slots, nbins%s, expo, ws or rec)", who, missing ? ", nan_bin" : "");
@@ -1077,14 +1374,26 @@ static int gbdt_best_split_slots_impl(const char *who, const int64_t *pool, int 
     }
     const int64_t items = (int64_t)K * F;
     const dim3 grid((unsigned)((items + 3) / 4));
-    if (missing)
-        hipLaunchKernelGGL(gbdt_split_feature_slots_kernel<true>, grid, dim3(kBlock), 0, as_stream(stream), pool, nslots, slots, K, F, max_bin, nbins, nan_bin,
-                           expo, lambda_l2, min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws);
-    else
-        hipLaunchKernelGGL(gbdt_split_feature_slots_kernel<false>, grid, dim3(kBlock), 0, as_stream(stream), pool, nslots, slots, K, F, max_bin, nbins, nan_bin,
-                           expo, lambda_l2, min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws);
-    hipLaunchKernelGGL(gbdt_split_leaf_kernel, dim3(K), dim3(kWave), 0, as_stream(stream), ws, F, rec);
+    int64_t *ws_sets = cat_on ? ws + items * kRec : nullptr;
+    const GbdtCatArgs ca{cat.is_cat, cat.cat_smooth, ws_sets};
+#define PTR_LAUNCH_SPLIT(M, C)                                                                                                                          \
+    hipLaunchKernelGGL((gbdt_split_feature_slots_kernel<M, C>), grid, dim3(kBlock), 0, as_stream(stream), pool, nslots, slots, K, F, max_bin, nbins, nan_bin, \
+                       expo, lambda_l2, min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws, ca)
+    if (cat_on) { if (missing) PTR_LAUNCH_SPLIT(true, true); else PTR_LAUNCH_SPLIT(false, true); }
+    else if (missing) PTR_LAUNCH_SPLIT(true, false);
+    else PTR_LAUNCH_SPLIT(false, false);
+#undef PTR_LAUNCH_SPLIT
+    hipLaunchKernelGGL(gbdt_split_leaf_kernel, dim3(K), dim3(kWave), 0, as_stream(stream), ws, F, rec, ws_sets, cat_on ? cat.sets : nullptr);
     return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_best_split_slots_cat(const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin, const int32_t *nbins,
+                                             const int32_t *nan_bin, const uint8_t *is_cat, const int32_t *expo, double lambda_l2,
+                                             int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double min_gain_to_split, double cat_smooth,
+                                             int64_t *ws, int64_t *rec, int64_t *sets, void *stream) {
+    return gbdt_best_split_slots_impl("ptr_gbdt_best_split_slots_cat", pool, nslots, slots, K, F, max_bin, nbins, nan_bin, nan_bin != nullptr, expo, lambda_l2,
+                                      min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws, rec, stream, true,
+                                      GbdtCatSearch{is_cat, cat_smooth, sets});
 }
 
 extern "C" int ptr_gbdt_best_split_slots(const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin, const int32_t *nbins,
@@ -1106,8 +1415,9 @@ extern "C" size_t ptr_gbdt_partition_segments_ws_ints(int64_t nblocks) { return 
 // cols: the width of a segs entry, 4 (start, count, feature, bin) or 5 (with also_left)
 static int gbdt_partition_segments_impl(const char *who, const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t nrows,
                                         const int32_t *segs, int cols, int K, const int32_t *blocks, int nblocks, int32_t *out, int32_t *left_counts,
-                                        int32_t *ws, int64_t ws_ints, void *stream) {
+                                        int32_t *ws, int64_t ws_ints, void *stream, bool cat_on = false, GbdtCatSegs cat = {nullptr, nullptr, nullptr}) {
     if (int rc = check_level_common(who, n, F, stride, 0, K, kCheckBins)) return rc;
+    if (cat_on && K > 0 && (!cat.is_cat || !cat.sets)) { set_error("%s: NULL pointer (is_cat or sets)", who); return PTR_ERR_INVALID_ARG; }
     if (nblocks < 0 || nrows < 0 || nrows > INT32_MAX) { set_error("%s: bad size (nblocks=%d, nrows=%lld)", who, nblocks, (long long)nrows); return PTR_ERR_INVALID_ARG; }
     if (nrows > 0 && (!rows || !out)) { set_error("%s: NULL pointer (rows or out)", who); return PTR_ERR_INVALID_ARG; }
     if (nrows > 0 && rows == out) { set_error("%s: out must not be rows (the partition is not done in place)", who); return PTR_ERR_INVALID_ARG; }
@@ -1123,11 +1433,25 @@ static int gbdt_partition_segments_impl(const char *who, const uint8_t *bins, in
     if (K == 0) return 0;
     if (int rc = check_hip(hipMemsetAsync(left_counts, 0, (size_t)K * sizeof(int32_t), s), who)) return rc;
     if (nblocks == 0) return 0;
-    hipLaunchKernelGGL(gbdt_part_seg_count_kernel, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, cols, K, blocks, nblocks, ws);
+    if (cat_on)
+        hipLaunchKernelGGL(gbdt_part_seg_count_kernel<true>, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, cols, K, blocks, nblocks, ws, cat);
+    else
+        hipLaunchKernelGGL(gbdt_part_seg_count_kernel<false>, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, cols, K, blocks, nblocks, ws, cat);
     hipLaunchKernelGGL(gbdt_part_scan_kernel, dim3(1), dim3(kBlock), 0, s, ws, nblocks, (int32_t *)nullptr);
-    hipLaunchKernelGGL(gbdt_part_seg_scatter_kernel, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, cols, K, blocks, nblocks, ws, out,
-                       left_counts);
+    if (cat_on)
+        hipLaunchKernelGGL(gbdt_part_seg_scatter_kernel<true>, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, cols, K, blocks, nblocks, ws,
+                           out, left_counts, cat);
+    else
+        hipLaunchKernelGGL(gbdt_part_seg_scatter_kernel<false>, dim3(nblocks), dim3(kBlock), 0, s, bins, stride, (int)n, F, rows, nrows, segs, cols, K, blocks, nblocks, ws,
+                           out, left_counts, cat);
     return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_partition_segments_cat(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t nrows, const int32_t *segs,
+                                               const int64_t *sets, int K, const uint8_t *is_cat, const int32_t *nan_bin, const int32_t *blocks,
+                                               int nblocks, int32_t *out, int32_t *left_counts, int32_t *ws, int64_t ws_ints, void *stream) {
+    return gbdt_partition_segments_impl("ptr_gbdt_partition_segments_cat", bins, stride, n, F, rows, nrows, segs, 5, K, blocks, nblocks, out, left_counts, ws,
+                                        ws_ints, stream, true, GbdtCatSegs{is_cat, nan_bin, sets});
 }
 
 extern "C" int ptr_gbdt_partition_segments(const uint8_t *bins, int stride, int64_t n, int F, const int32_t *rows, int64_t nrows, const int32_t *segs,

@@ -24,7 +24,8 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "gbdt_bin", "gbdt_quantize", "gbdt_histogram", "gbdt_hist_sub", "gbdt_best_split", "gbdt_partition", "gbdt_add_leaf_values", "gbdt_predict",
            "gbdt_histogram_segments", "gbdt_hist_sub_segments", "gbdt_best_split_slots", "gbdt_partition_segments", "gbdt_segment_items",
            "gbdt_bag_mask", "gbdt_goss", "gbdt_partition_mask", "gbdt_add_tree_binned",
-           "GBDT_MAX_BIN", "GBDT_RECORD"]
+           "gbdt_best_split_cat", "gbdt_best_split_slots_cat", "gbdt_partition_cat", "gbdt_partition_segments_cat", "gbdt_add_tree_binned_cat",
+           "gbdt_predict_cat", "GBDT_MAX_BIN", "GBDT_RECORD"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
 # launch table, and it draws its own; irfgan_loss and adlist_loss are public too: they take a mode, as irgan_selected does)
@@ -1401,3 +1402,190 @@ def gbdt_add_tree_binned(scores, bins, F, rows, feature, bin, left, right, value
                       n if rows is None else rows.numel(), _lib.ptr(feature), _lib.ptr(bin), _lib.ptr(left), _lib.ptr(right), _lib.ptr(value),
                       _lib.ptr(also_left), nodes, _lib.current_stream(dev))
     return scores
+
+
+# ---- categorical features: set splits (the *_cat entry points; include/ptranking_amd.h states the rule).  is_cat: uint8 [F] on the
+# device, non-zero = categorical.  nan_bin stays optional (None: no missing values).  A left set is 256 bits in 4 int64, bit b in word b // 64.
+def _gbdt_is_cat(is_cat, F):
+    return _check("is_cat", is_cat, torch.uint8, (F,))
+
+
+def _gbdt_cat_smooth(cat_smooth):
+    cat_smooth = float(cat_smooth)
+    if not 0.0 <= cat_smooth < float("inf"):
+        raise ValueError(f"cat_smooth must be a finite number >= 0, got {cat_smooth}")
+    return cat_smooth
+
+
+def _gbdt_sets(name, sets, rows, device):
+    """An int64 [rows, 4] table of left sets on the device: a tensor as it is, anything else (a host array) uploaded."""
+    if not isinstance(sets, torch.Tensor):
+        sets = torch.from_numpy(np.ascontiguousarray(np.asarray(sets, dtype=np.int64).reshape(-1, 4))).to(device)
+    return _check(name, sets.reshape(-1, 4) if sets.dim() == 1 else sets, torch.int64, (rows, 4))
+
+
+def gbdt_best_split_cat(hist, nbins, expo, is_cat, cat_smooth=10.0, lambda_l2=0.0, min_data_in_leaf=1, min_sum_hessian_in_leaf=1e-3, min_gain_to_split=0.0,
+                        out=None, sets=None, nan_bin=None):
+    """gbdt_best_split with categorical features -> (records int64 [leaves, 9], sets int64 [leaves, 4]).  A feature with is_cat != 0 is
+    searched over SETS of its bins: the used categories (H_c TC / TH >= cat_smooth) sorted by G_c / (H_c + cat_smooth), the first or the
+    last i + 1 of them going left.  record[2] of a categorical winner is the number of left categories + 256 * default_left and its set the
+    bins that go left; a numeric winner has gbdt_best_split's record and a zero set (ptr_gbdt_best_split_cat)."""
+    hist = _check("hist", hist, torch.int64)
+    if hist.dim() == 3:
+        hist = hist[None]
+    if hist.dim() != 4 or hist.shape[3] != 3:
+        raise ValueError(f"hist must be [leaves, F, max_bin, 3], got {tuple(hist.shape)}")
+    L, F, max_bin = hist.shape[0], hist.shape[1], _gbdt_max_bin(hist.shape[2])
+    nbins = _check("nbins", nbins, torch.int32, (F,))
+    expo = _check("expo", expo, torch.int32, (2,))
+    is_cat, cat_smooth = _gbdt_is_cat(is_cat, F), _gbdt_cat_smooth(cat_smooth)
+    nan_bin = None if nan_bin is None else _gbdt_nan_bin(nan_bin, F)
+    dev = hist.device
+    rec = torch.empty((L, 9), device=dev, dtype=torch.int64) if out is None else _check("out", out, torch.int64, (L, 9))
+    sets = torch.empty((L, 4), device=dev, dtype=torch.int64) if sets is None else _check("sets", sets, torch.int64, (L, 4))
+    ws = torch.empty((max(L * F, 1), 13), device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_best_split_cat", _lib.ptr(hist), L, F, max_bin, _lib.ptr(nbins), _lib.ptr(nan_bin), _lib.ptr(is_cat), _lib.ptr(expo),
+                  C.c_double(float(lambda_l2)), C.c_int64(int(min_data_in_leaf)), C.c_double(float(min_sum_hessian_in_leaf)),
+                  C.c_double(float(min_gain_to_split)), C.c_double(cat_smooth), _lib.ptr(ws), _lib.ptr(rec), _lib.ptr(sets), _lib.current_stream(dev))
+    return rec, sets
+
+
+def gbdt_best_split_slots_cat(pool, slots, nbins, expo, is_cat, cat_smooth=10.0, lambda_l2=0.0, min_data_in_leaf=1, min_sum_hessian_in_leaf=1e-3,
+                              min_gain_to_split=0.0, out=None, sets=None, nan_bin=None):
+    """gbdt_best_split_cat over the histograms pool[slots[k]] (slots: a host list) -> (records int64 [K, 9], sets int64 [K, 4]), each
+    bit-identical to gbdt_best_split_cat on a copy of that slot.  A slot outside the pool gives the record without a split and a zero set."""
+    pool = _gbdt_pool(pool)
+    dev, F, max_bin = pool.device, pool.shape[1], pool.shape[2]
+    nbins = _check("nbins", nbins, torch.int32, (F,))
+    expo = _check("expo", expo, torch.int32, (2,))
+    is_cat, cat_smooth = _gbdt_is_cat(is_cat, F), _gbdt_cat_smooth(cat_smooth)
+    nan_bin = None if nan_bin is None else _gbdt_nan_bin(nan_bin, F)
+    host, slots_d = _gbdt_table("slots", slots, 1, dev)
+    K = host.shape[0]
+    rec = torch.empty((K, 9), device=dev, dtype=torch.int64) if out is None else _check("out", out, torch.int64, (K, 9))
+    sets = torch.empty((K, 4), device=dev, dtype=torch.int64) if sets is None else _check("sets", sets, torch.int64, (K, 4))
+    ws = torch.empty((max(K * F, 1), 13), device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_best_split_slots_cat", _lib.ptr(pool), pool.shape[0], _lib.ptr(slots_d), K, F, max_bin, _lib.ptr(nbins), _lib.ptr(nan_bin),
+                  _lib.ptr(is_cat), _lib.ptr(expo), C.c_double(float(lambda_l2)), C.c_int64(int(min_data_in_leaf)),
+                  C.c_double(float(min_sum_hessian_in_leaf)), C.c_double(float(min_gain_to_split)), C.c_double(cat_smooth), _lib.ptr(ws), _lib.ptr(rec),
+                  _lib.ptr(sets), _lib.current_stream(dev))
+    return rec, sets
+
+
+def gbdt_partition_cat(bins, rows, feature, bin, F, is_cat, set, default_left=0, nan_bin=None, out=None, left_count=None):
+    """gbdt_partition under a node of either kind -> (out, left_count).  At a categorical feature a row goes left iff bit
+    bins[row, feature] of `set` (int64 [4]: a device tensor, or a host array that is uploaded) is set; at any other feature on
+    bins[row, feature] <= bin, the NaN bin nan_bin[feature] going left too where default_left is set (ptr_gbdt_partition_cat)."""
+    bins = _gbdt_bins(bins, F)
+    dev = bins.device
+    rows = _check("rows", rows, torch.int32)
+    if rows.dim() != 1:
+        raise ValueError(f"rows must be flat, got {tuple(rows.shape)}")
+    if int(default_left) not in (0, 1):
+        raise ValueError(f"default_left must be 0 or 1, got {default_left}")
+    m = rows.numel()
+    is_cat = _gbdt_is_cat(is_cat, F)
+    nan_bin = None if nan_bin is None else _gbdt_nan_bin(nan_bin, F)
+    set = _gbdt_sets("set", set, 1, dev)
+    out = torch.empty_like(rows) if out is None else _check("out", out, torch.int32, (m,))
+    left_count = torch.empty(1, device=dev, dtype=torch.int32) if left_count is None else _check("left_count", left_count, torch.int32, (1,))
+    ws = torch.empty(int(_lib.query("ptr_gbdt_partition_ws_ints", m)), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_partition_cat", _lib.ptr(bins), bins.shape[1], bins.shape[0], F, _lib.ptr(rows), m, int(feature), int(bin), int(default_left),
+                  _lib.ptr(is_cat), _lib.ptr(nan_bin), _lib.ptr(set), _lib.ptr(out), _lib.ptr(left_count), _lib.ptr(ws), _lib.current_stream(dev))
+    return out, left_count
+
+
+def gbdt_partition_segments_cat(bins, rows, segs, sets, F, is_cat, nan_bin=None, out=None, left_counts=None):
+    """gbdt_partition_cat over every segment (start, count, feature, bin, default_left) of the host table segs [K, 5], segment k under the
+    set sets[k] (int64 [K, 4], host or device) -> (out, left_counts), as gbdt_partition_segments (ptr_gbdt_partition_segments_cat)."""
+    bins = _gbdt_bins(bins, F)
+    dev = bins.device
+    rows = _check("rows", rows, torch.int32)
+    if rows.dim() != 1:
+        raise ValueError(f"rows must be flat, got {tuple(rows.shape)}")
+    host, segs_d = _gbdt_table("segs", segs, 5, dev)
+    K = host.shape[0]
+    is_cat = _gbdt_is_cat(is_cat, F)
+    nan_bin = None if nan_bin is None else _gbdt_nan_bin(nan_bin, F)
+    sets = _gbdt_sets("sets", sets, K, dev)
+    out = torch.empty_like(rows) if out is None else _check("out", out, torch.int32, tuple(rows.shape))
+    left_counts = torch.zeros(K, device=dev, dtype=torch.int32) if left_counts is None else _check("left_counts", left_counts, torch.int32, (K,))
+    per = 1024                                                               # kGbdtPartRows: the rows one workgroup owns
+    nblk = np.where((host[:, 0] >= 0) & (host[:, 1] > 0) & (host[:, 0] + host[:, 1] <= rows.numel()), (host[:, 1] + per - 1) // per, 0)
+    seg = np.repeat(np.arange(K), nblk)
+    blocks = np.stack([seg, np.arange(seg.size) - np.repeat(np.cumsum(nblk) - nblk, nblk)], axis=1)
+    _, blocks_d = _gbdt_table("blocks", blocks, 2, dev)
+    ws_ints = int(_lib.query("ptr_gbdt_partition_segments_ws_ints", C.c_int64(int(seg.size))))
+    ws = torch.empty(ws_ints, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_partition_segments_cat", _lib.ptr(bins), bins.shape[1], bins.shape[0], F, _lib.ptr(rows), rows.numel(), _lib.ptr(segs_d),
+                  _lib.ptr(sets), K, _lib.ptr(is_cat), _lib.ptr(nan_bin), _lib.ptr(blocks_d), int(seg.size), _lib.ptr(out), _lib.ptr(left_counts),
+                  _lib.ptr(ws), ws_ints, _lib.current_stream(dev))
+    return out, left_counts
+
+
+def _gbdt_cat_nodes(cat_index, cat_sets, nodes, device):
+    cat_index = _check("cat_index", cat_index, torch.int32, (nodes,))
+    cat_sets = _check("cat_sets", cat_sets, torch.int64)
+    if cat_sets.dim() != 2 or cat_sets.shape[1] != 4:
+        raise ValueError(f"cat_sets must be [sets, 4] int64, got {tuple(cat_sets.shape)}")
+    return cat_index, cat_sets
+
+
+def gbdt_add_tree_binned_cat(scores, bins, F, rows, feature, bin, left, right, value, is_cat, cat_index, cat_sets, default_left=None, nan_bin=None):
+    """gbdt_add_tree_binned for a tree with both node kinds: cat_index int32 [nodes] is -1 at a numeric node (left on
+    bins[row, feature] <= bin, the NaN bin nan_bin[feature] too where default_left[node] is set), else the row goes left iff bit
+    bins[row, feature] of cat_sets[cat_index] (int64 [sets, 4]) is set.  A malformed tree gives NaN (ptr_gbdt_add_tree_binned_cat)."""
+    scores = _check("scores", scores)
+    bins = _gbdt_bins(bins, F)
+    n, dev = bins.shape[0], bins.device
+    if scores.dim() != 1 or scores.numel() != n or not scores.is_contiguous():
+        raise ValueError(f"scores must be flat and contiguous [{n}], got {tuple(scores.shape)}")
+    if rows is not None:
+        rows = _check("rows", rows, torch.int32)
+        if rows.dim() != 1:
+            raise ValueError(f"rows must be flat, got {tuple(rows.shape)}")
+    nodes = feature.numel()
+    feature, bin, left, right = (_check(k, t, torch.int32, (nodes,)) for k, t in zip(("feature", "bin", "left", "right"), (feature, bin, left, right)))
+    value = _check("value", value, shape=(nodes + 1,))
+    is_cat = _gbdt_is_cat(is_cat, F)
+    cat_index, cat_sets = _gbdt_cat_nodes(cat_index, cat_sets, nodes, dev)
+    default_left = None if default_left is None else _check("default_left", default_left, torch.uint8, (nodes,))
+    nan_bin = None if nan_bin is None else _gbdt_nan_bin(nan_bin, F)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_add_tree_binned_cat", _lib.ptr(scores), _lib.ptr(bins), bins.shape[1], n, F, _lib.ptr(rows), n if rows is None else rows.numel(),
+                  _lib.ptr(feature), _lib.ptr(bin), _lib.ptr(left), _lib.ptr(right), _lib.ptr(value), _lib.ptr(default_left), _lib.ptr(is_cat),
+                  _lib.ptr(nan_bin), _lib.ptr(cat_index), _lib.ptr(cat_sets), cat_sets.shape[0], nodes, _lib.current_stream(dev))
+    return scores
+
+
+def gbdt_predict_cat(X, feature, threshold, left, right, value, tree_offsets, is_cat, cat_index, cat_sets, ntrees=None, default_left=None):
+    """gbdt_predict for trees with both node kinds (cat_index, cat_sets as gbdt_add_tree_binned_cat takes them, over the nodes of all
+    trees).  At a categorical node a NaN follows default_left (right without one), a value that is no integer in 0 .. 255 goes right, any
+    other code goes left iff its bit is set: a code the training data never held is in no set.  A malformed tree gives NaN
+    (ptr_gbdt_predict_cat)."""
+    X = _check("X", X)
+    if X.dim() != 2:
+        raise ValueError(f"X must be [rows, features], got {tuple(X.shape)}")
+    dev = X.device
+    tree_offsets = _check("tree_offsets", tree_offsets, torch.int32)
+    total = tree_offsets.numel() - 1
+    ntrees = total if ntrees is None else int(ntrees)
+    if not 0 <= ntrees <= total:
+        raise ValueError(f"ntrees={ntrees} outside 0 .. {total}")
+    nodes = feature.numel()
+    feature, left, right = (_check(k, t, torch.int32, (nodes,)) for k, t in zip(("feature", "left", "right"), (feature, left, right)))
+    threshold = _check("threshold", threshold, shape=(nodes,))
+    value = _check("value", value, shape=(nodes + total,))
+    is_cat = _gbdt_is_cat(is_cat, X.shape[1])
+    cat_index, cat_sets = _gbdt_cat_nodes(cat_index, cat_sets, nodes, dev)
+    default_left = None if default_left is None else _check("default_left", default_left, torch.uint8, (nodes,))
+    out = torch.empty(X.shape[0], device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_predict_cat", _lib.ptr(X), X.shape[0], X.shape[1], _lib.ptr(feature), _lib.ptr(threshold), _lib.ptr(left), _lib.ptr(right),
+                  _lib.ptr(value), _lib.ptr(tree_offsets), _lib.ptr(default_left), _lib.ptr(is_cat), _lib.ptr(cat_index), _lib.ptr(cat_sets),
+                  cat_sets.shape[0], ntrees, _lib.ptr(out), _lib.current_stream(dev))
+    return out

@@ -52,8 +52,20 @@ booster ignore them.  The key 'objective' of the dict stays ignored (the objecti
 'lambdarank', the reference's CUSTOM all-pairs objective), and label_gain stays unknown (the gain is 2^y - 1).  A model file written before
 the three keys existed loads with their defaults.
 
+Categorical features (categorical_feature, a list of 0-based column indices; cat_smooth, default 10.0; LightGBM's names).  Such a column
+holds integer codes in 0 .. max_bin - 1 (bin_edges maps code c to bin c), and a node on it sends a SET of codes left.  The rules are
+scikit-learn's (HistGradientBoostingRegressor(categorical_features=...)) wherever its are deterministic, stated in
+include/ptranking_amd.h and restated in tests/gbdt_cat_ref.py: at a node a category is used iff H_c TC / TH >= cat_smooth, the used
+categories are sorted by G_c / (H_c + cat_smooth) (equal keys by the lower code: this project's own tie rule), and the candidates are the
+first or the last i + 1 of them up to the middle; unused categories and empty bins go right.  cat_smooth plays both roles of
+scikit-learn's MIN_CAT_SUPPORT.  Under use_missing a NaN of such a column is one more category.  Whole fits are pinned to scikit-learn
+node for node, left sets included (tests/golden/gbdt_sklearn_cat.npz); LightGBM's own categorical search is not claimed.  A tree then keeps
+cat_index per node (-1: numeric) and cat_set [sets, 4] int64, 256 bits per set; the model is saved as format 3.  predict sends a code
+the training data never held right (it is in no set).  With categorical_feature empty every call and every model file is the one made
+before the keys existed.  Not here: max_cat_to_onehot, cat_l2, min_data_per_group, max_cat_threshold.
+
 Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here:
-feature_fraction, EFB, categorical features, DART, monotone constraints.  There is no CPU path.
+feature_fraction, EFB, DART, monotone constraints.  There is no CPU path.
 """
 import json
 
@@ -70,12 +82,14 @@ __all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS"
 DEFAULT_PARAMS = {"learning_rate": 0.1, "num_leaves": 31, "num_trees": 100, "min_data_in_leaf": 20, "min_sum_hessian_in_leaf": 1e-3,
                   "lambda_l2": 0.0, "min_gain_to_split": 0.0, "max_bin": 255, "max_depth": -1, "grow_policy": "leafwise",
                   "bagging_fraction": 1.0, "bagging_freq": 0, "bagging_seed": 3, "bagging_by_query": False, "data_sample_strategy": "bagging",
-                  "top_rate": 0.2, "other_rate": 0.1, "use_missing": False,
+                  "top_rate": 0.2, "other_rate": 0.1, "use_missing": False, "categorical_feature": (), "cat_smooth": 10.0,
                   # LambdaMART(objective='lambdarank_ndcg') alone reads these three; the other objectives and the bare booster ignore them
                   "lambdarank_truncation_level": 30, "lambdarank_norm": True, "sigmoid": 1.0}
 IGNORED_PARAMS = ("num_threads", "verbosity", "metric", "boosting_type", "objective", "eval_at")    # accepted, without a meaning here
 MODEL_FORMAT = 1                       # a model trained without use_missing
 MODEL_FORMAT_MISSING = 2               # one trained under it: format 1 with default_left per node and nan_bin per feature
+MODEL_FORMAT_CAT = 3                   # one with categorical features: format 1 or 2 plus categorical_feature, cat_index per node and cat_sets
+CAT_KEYS = ("categorical_feature", "cat_smooth")      # not among the parameters of a format 1 or 2 file
 GROW_POLICIES = ("leafwise", "depthwise")
 SAMPLE_STRATEGIES = ("bagging", "goss")
 
@@ -125,9 +139,34 @@ def _params(params):
         raise ValueError(f"top_rate and other_rate must be > 0 and sum to at most 1, got {p['top_rate']}, {p['other_rate']}")
     if p["data_sample_strategy"] == "goss" and _bagging(p):
         raise ValueError("data_sample_strategy 'goss' cannot be combined with bagging (bagging_freq > 0 and bagging_fraction < 1)")
+    p["categorical_feature"] = _categorical(p["categorical_feature"])
+    try:
+        p["cat_smooth"] = float(p["cat_smooth"])
+    except (TypeError, ValueError):
+        raise ValueError(f"cat_smooth must be a number >= 0, got {p['cat_smooth']!r}") from None
+    if not 0.0 <= p["cat_smooth"] < np.inf:
+        raise ValueError(f"cat_smooth must be a finite number >= 0, got {p['cat_smooth']}")
     p["lambdarank_truncation_level"], p["sigmoid"], p["lambdarank_norm"] = F.lambdarank_ndcg_settings(p["lambdarank_truncation_level"], p["sigmoid"],
                                                                                                    p["lambdarank_norm"])
     return p
+
+
+def _categorical(cat):
+    """categorical_feature as a sorted tuple of ints; a duplicate, negative or non-integer entry raises ValueError."""
+    if cat is None:
+        return ()
+    if isinstance(cat, (str, bytes)) or not isinstance(cat, (list, tuple, np.ndarray)):
+        raise ValueError(f"categorical_feature must be a list or tuple of 0-based column indices, got {cat!r}")
+    out = []
+    for c in np.asarray(cat, dtype=object).reshape(-1).tolist() if isinstance(cat, np.ndarray) else cat:
+        if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)):
+            raise ValueError(f"categorical_feature must hold integers, got {c!r}")
+        if c < 0:
+            raise ValueError(f"categorical_feature must hold 0-based column indices, got {c}")
+        out.append(int(c))
+    if len(set(out)) != len(out):
+        raise ValueError(f"categorical_feature holds a column twice: {sorted(out)}")
+    return tuple(sorted(out))
 
 
 def _bagging(p):
@@ -156,9 +195,23 @@ def _require_no_infinity(Xd):
         raise ValueError(_INFINITE)
 
 
-def _require_values(Xd, use_missing):
-    """The check a device matrix passes before it is walked: no infinity under use_missing, nothing but finite values without it."""
+def _not_codes(max_bin):
+    return f"a categorical column must hold integer codes in 0 .. {max_bin - 1} (under use_missing a NaN too, and then codes up to max_bin - 2)"
+
+
+def _require_values(Xd, use_missing, categorical=(), max_bin=F.GBDT_MAX_BIN):
+    """The check a device matrix passes before it is walked: no infinity under use_missing, nothing but finite values without it; in a
+    categorical column nothing but integer codes in 0 .. max_bin - 1 (a NaN passes under use_missing), for one more reduction and read."""
     _require_no_infinity(Xd) if use_missing else _require_finite(Xd)
+    if categorical and Xd.numel():
+        if max(categorical) >= Xd.shape[1]:
+            raise ValueError(f"categorical_feature {max(categorical)} with {Xd.shape[1]} columns")
+        col = Xd[:, list(categorical)]
+        ok = (col == torch.floor(col)) & (col >= 0) & (col <= max_bin - 1)
+        if use_missing:
+            ok |= torch.isnan(col)
+        if not bool(ok.all().cpu()):
+            raise ValueError(_not_codes(max_bin))
 
 
 def _device_matrix(X, dev):
@@ -173,7 +226,7 @@ def _midpoints(lo, hi):
     return np.where(mid >= hi, lo, mid)
 
 
-def bin_edges(X, max_bin, use_missing=False):
+def bin_edges(X, max_bin, use_missing=False, categorical=()):
     """The binning rule, on the host, once per dataset -> (edges float32 [F, max_bin - 1], padded with +inf; nbins int32 [F]).
     Per feature: at most max_bin distinct values give one bin per value, the edges at the midpoints (binning is then lossless).  Otherwise
     the k-th edge (k = 1 .. max_bin - 1) follows the first distinct value whose cumulative row count reaches k n / max_bin, again at the
@@ -181,7 +234,11 @@ def bin_edges(X, max_bin, use_missing=False):
     use_missing=True -> (edges, nbins, nan_bin int32 [F]): a NaN is a missing value and takes no part in the rule (the distinct values, the
     counts and n are those of the feature's other rows).  A feature that holds one is binned under max_bin - 1 in place of max_bin, and
     its NaNs get the bin behind its value bins, nan_bin[f] = nbins[f] (nbins counts value bins only); a feature without a NaN has
-    nan_bin[f] = -1 and the edges it has without the switch.  An infinity raises either way."""
+    nan_bin[f] = -1 and the edges it has without the switch.  An infinity raises either way.
+    categorical: the columns that hold integer codes.  Such a feature gets the edges 0.5, 1.5, ..., so that code c lands in bin c, and
+    nbins[f] = the largest code + 1; a value that is no integer in 0 .. max_bin - 1 raises (0 .. max_bin - 2 where the column holds a NaN,
+    whose bin stays behind the value bins)."""
+    categorical = _categorical(categorical)
     X = np.asarray(X, dtype=np.float32)
     if X.ndim != 2:
         raise ValueError(f"X must be [rows, features], got {X.shape}")
@@ -191,6 +248,8 @@ def bin_edges(X, max_bin, use_missing=False):
     elif not np.isfinite(X).all():
         raise ValueError(_NONFINITE)
     nf = X.shape[1]
+    if categorical and categorical[-1] >= nf:
+        raise ValueError(f"categorical_feature {categorical[-1]} with {nf} columns")
     edges = np.full((nf, max_bin - 1), np.inf, np.float32)
     nbins = np.ones(nf, np.int32)
     nan_bin = np.full(nf, -1, np.int32)
@@ -199,6 +258,15 @@ def bin_edges(X, max_bin, use_missing=False):
         cap = max_bin
         if use_missing and np.isnan(col).any():
             col, cap = col[~np.isnan(col)], max_bin - 1
+        if f in categorical:
+            if col.size and not ((col == np.floor(col)) & (col >= 0) & (col <= cap - 1)).all():
+                raise ValueError(f"feature {f}: " + _not_codes(max_bin))
+            top = int(col.max()) if col.size else 0
+            edges[f, :top] = np.arange(top, dtype=np.float32) + np.float32(0.5)
+            nbins[f] = top + 1
+            if cap < max_bin:
+                nan_bin[f] = nbins[f]
+            continue
         n = col.size
         vals, counts = np.unique(col, return_counts=True)
         if vals.size > 1:
@@ -224,10 +292,11 @@ def leaf_value(g_sum, h_sum, expo, lambda_l2, learning_rate):
 
 
 class _Leaf:
-    __slots__ = ("start", "count", "depth", "slot", "parent", "side", "g", "h", "rec")
+    __slots__ = ("start", "count", "depth", "slot", "parent", "side", "g", "h", "rec", "set")
 
-    def __init__(self, start, count, depth, slot, parent, side, g, h, rec):
+    def __init__(self, start, count, depth, slot, parent, side, g, h, rec, set=None):
         self.start, self.count, self.depth, self.slot, self.parent, self.side, self.g, self.h, self.rec = start, count, depth, slot, parent, side, g, h, rec
+        self.set = set                     # categorical features: the left set of rec, 4 int64 as the host read them
 
 
 def _record(r):
@@ -250,6 +319,7 @@ class GBDT:
         self.edges = self.nbins = None     # host copies (the model file carries them)
         self.nan_bin = None                # under use_missing: the NaN bin per feature, -1 where training saw no NaN
         self._nan_bin_d = None
+        self._is_cat = self._is_cat_d = None   # categorical_feature as a mask over the features: host bool [F], device uint8 [F]
         self.best_iteration = None
         self._device = device
         self._flat = None
@@ -278,10 +348,13 @@ class GBDT:
         host = X.detach().cpu().numpy() if isinstance(X, torch.Tensor) else np.asarray(X)
         host = np.ascontiguousarray(host, dtype=np.float32)
         p = self.params
+        cats = p["categorical_feature"]
+        if cats and cats[-1] >= host.shape[1]:
+            raise ValueError(f"categorical_feature {cats[-1]} with {host.shape[1]} columns")
         if p["use_missing"]:
-            self.edges, self.nbins, self.nan_bin = bin_edges(host, p["max_bin"], True)
+            self.edges, self.nbins, self.nan_bin = bin_edges(host, p["max_bin"], True, **({"categorical": cats} if cats else {}))
         else:
-            self.edges, self.nbins = bin_edges(host, p["max_bin"])
+            self.edges, self.nbins = bin_edges(host, p["max_bin"], **({"categorical": cats} if cats else {}))
         Xd = _device_matrix(X if isinstance(X, torch.Tensor) else host, dev)
         self.n, self.F = host.shape
         self._edges_d, self._nbins_d = torch.from_numpy(self.edges).to(dev), torch.from_numpy(self.nbins).to(dev)
@@ -297,6 +370,10 @@ class GBDT:
         self._lc = torch.zeros(1, device=dev, dtype=torch.int32)
         self._rec = torch.zeros((2, 9), device=dev, dtype=torch.int64)
         self._lrec = torch.zeros((max(p["num_leaves"], 2), 9), device=dev, dtype=torch.int64)      # a depth-wise level's records
+        if cats:
+            self._set_is_cat(dev)
+            self._sets = torch.zeros((2, 4), device=dev, dtype=torch.int64)                            # the left sets beside _rec and _lrec
+            self._lsets = torch.zeros((max(p["num_leaves"], 2), 4), device=dev, dtype=torch.int64)
         self._pool = torch.zeros((max(p["num_leaves"], 1), self.F, p["max_bin"], 3), device=dev, dtype=torch.int64)
         self._qid = None if group is None else torch.from_numpy(np.repeat(np.arange(group.size, dtype=np.int32), group)).to(dev)
         if sampling(p):
@@ -307,6 +384,11 @@ class GBDT:
                 self._gg, self._gh = torch.empty_like(self.scores), torch.empty_like(self.scores)
                 self._info = torch.zeros(3, device=dev, dtype=torch.int32)
         return self
+
+    def _set_is_cat(self, dev):
+        self._is_cat = np.zeros(self.edges.shape[0], bool)
+        self._is_cat[list(self.params["categorical_feature"])] = True
+        self._is_cat_d = torch.from_numpy(self._is_cat.astype(np.uint8)).to(dev)
 
     def _by_query(self):
         return sampling(self.params) == "bagging" and self.params["bagging_by_query"]
@@ -331,6 +413,11 @@ class GBDT:
     # ---- one boosting round
     def _search(self, slot, out_row):
         p = self.params
+        if p["categorical_feature"]:
+            F.gbdt_best_split_cat(self._pool[slot:slot + 1], self._nbins_d, self._expo, self._is_cat_d, p["cat_smooth"], p["lambda_l2"], p["min_data_in_leaf"],
+                                  p["min_sum_hessian_in_leaf"], p["min_gain_to_split"], out=self._rec[out_row:out_row + 1],
+                                  sets=self._sets[out_row:out_row + 1], nan_bin=self._nan_bin_d)
+            return
         F.gbdt_best_split(self._pool[slot:slot + 1], self._nbins_d, self._expo, p["lambda_l2"], p["min_data_in_leaf"], p["min_sum_hessian_in_leaf"],
                           p["min_gain_to_split"], out=self._rec[out_row:out_row + 1], nan_bin=self._nan_bin_d)
 
@@ -361,7 +448,8 @@ class GBDT:
             torch.where(self._mask != 0, self._arange, self._none, out=self._tmp)
             F.gbdt_histogram(self.bins, self._qg, self._qh, self._tmp, nf, mb, hist=pool[0])
         self._search(0, 0)
-        head = torch.cat([self._rec[0], pool[0, 0].sum(0), self._expo.to(torch.int64), self._flag.to(torch.int64)]).cpu().numpy()
+        head = torch.cat([self._rec[0], pool[0, 0].sum(0), self._expo.to(torch.int64), self._flag.to(torch.int64)]
+                         + ([self._sets[0]] if p["categorical_feature"] else [])).cpu().numpy()      # the root's left set rides in the same read
         self.host_reads += 1
         if head[14]:
             self._flag.zero_()
@@ -371,9 +459,9 @@ class GBDT:
         if sampled is None:
             self._rows.copy_(self._arange)
         grow = self._grow_depthwise if p["grow_policy"] == "depthwise" else self._grow_leafwise
-        feature, threshold, left, right, starts, g_sum, h_sum, split_bin, go_left = grow(head, bag)
+        feature, threshold, left, right, starts, g_sum, h_sum, split_bin, go_left, cat_index, cat_sets = grow(head, bag)
         value = np.array([leaf_value(g, h, expo, p["lambda_l2"], p["learning_rate"]) for g, h in zip(g_sum, h_sum)], np.float32)
-        return self._finish(feature, threshold, left, right, starts, value, bag, split_bin, go_left)
+        return self._finish(feature, threshold, left, right, starts, value, bag, split_bin, go_left, cat_index, cat_sets)
 
     def _grow_leafwise(self, head, m):
         """Leaf-wise growth from the root's record (head, as update read it) over the first m entries of the row list: the leaf with the
@@ -381,8 +469,10 @@ class GBDT:
         read per split brings the two children's records.  -> what _grow_depthwise returns."""
         p, nf, mb, pool = self.params, self.F, self.params["max_bin"], self._pool
         root_rec = _record(head[:9]) if self._splittable(m, 0) else _NO_SPLIT
-        leaves = [_Leaf(0, m, 0, 0, -1, 0, int(head[9]), int(head[10]), root_rec)]
+        cats = bool(p["categorical_feature"])
+        leaves = [_Leaf(0, m, 0, 0, -1, 0, int(head[9]), int(head[10]), root_rec, head[15:19].copy() if cats else None)]
         feature, threshold, left, right, split_bin, go_left = [], [], [], [], [], []
+        cat_index, cat_sets = ([], []) if cats else (None, None)
         missing = p["use_missing"]
         free = 1                                                       # the next unused histogram slot
         while len(leaves) < p["num_leaves"]:
@@ -392,14 +482,24 @@ class GBDT:
             if not gain > -np.inf:
                 break
             s, m = leaf.start, leaf.count
+            is_c = cats and bool(self._is_cat[f])
             if missing:                                                    # field 2 of a record of the missing scan: bin + 256 * default_left
                 dl, b = b >> 8, b & 255
                 go_left.append(dl)
-            F.gbdt_partition(self.bins, self._rows[s:s + m], f, b, nf, out=self._tmp[s:s + m], left_count=self._lc,
-                             also_left=(int(self.nan_bin[f]) if dl else -1) if missing else None)
+            if is_c:                                                       # field 2 of a categorical record: left categories + 256 * default_left
+                b = 0
+            if cats:
+                cat_index.append(len(cat_sets) if is_c else -1)
+                if is_c:
+                    cat_sets.append(leaf.set)
+                F.gbdt_partition_cat(self.bins, self._rows[s:s + m], f, b, nf, self._is_cat_d, leaf.set, default_left=dl if missing else 0,
+                                     nan_bin=self._nan_bin_d, out=self._tmp[s:s + m], left_count=self._lc)
+            else:
+                F.gbdt_partition(self.bins, self._rows[s:s + m], f, b, nf, out=self._tmp[s:s + m], left_count=self._lc,
+                                 also_left=(int(self.nan_bin[f]) if dl else -1) if missing else None)
             self._rows[s:s + m].copy_(self._tmp[s:s + m])
             node = len(feature)
-            feature.append(f); threshold.append(self.edges[f, b]); left.append(~li); right.append(~len(leaves)); split_bin.append(b)
+            feature.append(f); threshold.append(np.float32(0.0) if is_c else self.edges[f, b]); left.append(~li); right.append(~len(leaves)); split_bin.append(b)
             if leaf.parent >= 0:
                 (left if leaf.side == 0 else right)[leaf.parent] = node
             lchild = _Leaf(s, lsum[2], leaf.depth + 1, leaf.slot, node, 0, lsum[0], lsum[1], _NO_SPLIT)
@@ -416,19 +516,22 @@ class GBDT:
                 for k, c in enumerate((lchild, rchild)):
                     if can[k]:
                         self._search(c.slot, k)
-                recs = self._rec.cpu().numpy()                           # the one synchronisation of this split
+                recs = (torch.cat([self._rec, self._sets], dim=1) if cats else self._rec).cpu().numpy()      # the one synchronisation of this split
                 self.host_reads += 1
                 for k, c in enumerate((lchild, rchild)):
                     if can[k]:
-                        c.rec = _record(recs[k])
-        return feature, threshold, left, right, [c.start for c in leaves], [c.g for c in leaves], [c.h for c in leaves], split_bin, go_left
+                        c.rec = _record(recs[k, :9])
+                        c.set = recs[k, 9:13].copy() if cats else None
+        return (feature, threshold, left, right, [c.start for c in leaves], [c.g for c in leaves], [c.h for c in leaves], split_bin, go_left, cat_index,
+                cat_sets)
 
-    def _finish(self, feature, threshold, left, right, starts, value, m, split_bin, go_left=()):
+    def _finish(self, feature, threshold, left, right, starts, value, m, split_bin, go_left=(), cat_index=None, cat_sets=None):
         """Adds the leaf values (by leaf index, with the leaves' first positions in the row list) to the training scores; keeps the tree.
         The tree grew on the first m entries of the row list: the rows behind them (outside a sampled tree's bag) are walked through the
         tree on their bins and get the same fp32 leaf value, so the scores stay predict(X) bit for bit.  split_bin, the split bins by node,
         serves that one call and is not part of the model.  go_left (use_missing): default_left by node, kept with the tree; in the walk
-        a node's NaN bin goes left with it."""
+        a node's NaN bin goes left with it.  cat_index, cat_sets (categorical features): per node -1 or the index of its left set, and the
+        sets, kept with the tree as cat_index and cat_set [sets, 4] int64; a tree without them is the dict it always was."""
         order = sorted(range(len(starts)), key=lambda i: starts[i])
         offsets = np.array([starts[i] for i in order] + [m], np.int32)
         dev = self.scores.device
@@ -439,8 +542,15 @@ class GBDT:
         if self.params["use_missing"]:
             t["default_left"] = np.array(go_left, np.uint8).reshape(-1)
             also = np.where(t["default_left"] != 0, self.nan_bin[t["feature"]], -1)
-        if m < self.n:
-            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        if cat_index is not None:
+            t["cat_index"] = np.array(cat_index, np.int32).reshape(-1)
+            t["cat_set"] = np.array(cat_sets, np.int64).reshape(-1, 4)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        if m < self.n and cat_index is not None:
+            F.gbdt_add_tree_binned_cat(self.scores, self.bins, self.F, self._rows[m:], up(t["feature"], np.int32), up(split_bin, np.int32), up(t["left"], np.int32),
+                                       up(t["right"], np.int32), up(value, np.float32), self._is_cat_d, up(t["cat_index"], np.int32), up(t["cat_set"], np.int64),
+                                       default_left=up(t["default_left"], np.uint8) if "default_left" in t else None, nan_bin=self._nan_bin_d)
+        elif m < self.n:
             F.gbdt_add_tree_binned(self.scores, self.bins, self.F, self._rows[m:], up(t["feature"], np.int32), up(split_bin, np.int32), up(t["left"], np.int32),
                                    up(t["right"], np.int32), up(value, np.float32), also_left=None if also is None else up(also, np.int32))
         self.trees.append(t)
@@ -458,13 +568,15 @@ class GBDT:
         feature, threshold = np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.float32)
         left, right, split_bin = np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.int32), np.zeros(max(cap - 1, 0), np.int32)
         go_left, missing = np.zeros(max(cap - 1, 0), np.uint8), p["use_missing"]
+        cats = bool(p["categorical_feature"])                              # a record then carries its left set in the columns 9 .. 12
+        cat_index, cat_sets, ncol = (np.full(max(cap - 1, 0), -1, np.int32), [], 13) if cats else (None, None, 9)
         starts, g_sum, h_sum = np.zeros(cap, np.int64), np.zeros(cap, np.int64), np.zeros(cap, np.int64)
         g_sum[0], h_sum[0] = head[9], head[10]
         nodes, leaves, free, depth = 0, 1, 1, 0
         # the frontier, in ascending start: leaf index, start, count, histogram slot, parent node, side, split record (gain -inf: none)
         leaf, start, count, slot = np.zeros(1, np.int64), np.zeros(1, np.int64), np.full(1, m, np.int64), np.zeros(1, np.int64)
         parent, side = np.full(1, -1, np.int64), np.zeros(1, np.int64)
-        rec = np.asarray(head[:9], np.int64).reshape(1, 9).copy()
+        rec = np.concatenate([head[:9], head[15:19]] if cats else [head[:9]]).astype(np.int64).reshape(1, ncol)
         while True:
             gain = rec[:, 0].copy().view(np.float64)
             keep = np.nonzero(self._splittable(count, depth) & (gain > -np.inf))[0]
@@ -478,14 +590,23 @@ class GBDT:
             node = nodes + np.arange(k)
             if missing:                                                    # field 2 of a record of the missing scan: bin + 256 * default_left
                 go_left[node], b = b >> 8, b & 255
-            feature[node], threshold[node], split_bin[node] = f, self.edges[f, b], b
+            if cats:                                                       # field 2 of a categorical record: left categories + 256 * default_left
+                is_c = self._is_cat[f]
+                b = np.where(is_c, 0, b)
+                cat_index[node[is_c]] = len(cat_sets) + np.arange(int(is_c.sum()))
+                cat_sets.extend(rec[keep[is_c], 9:13])
+            feature[node], threshold[node], split_bin[node] = f, np.where(is_c, np.float32(0.0), self.edges[f, b]) if cats else self.edges[f, b], b
             left[node], right[node] = ~leaf[keep], ~(leaves + np.arange(k))
             has = parent[keep] >= 0
             for arr, sd in ((left, 0), (right, 1)):
                 sel = has & (side[keep] == sd)
                 arr[parent[keep][sel]] = node[sel]
             also = [np.where(go_left[node] != 0, self.nan_bin[f], -1)] if missing else []       # the fifth column of the missing form
-            F.gbdt_partition_segments(self.bins, self._rows, np.stack([start[keep], count[keep], f, b] + also, axis=1), nf, out=self._tmp, also_left=missing)
+            if cats:
+                F.gbdt_partition_segments_cat(self.bins, self._rows, np.stack([start[keep], count[keep], f, b, go_left[node].astype(np.int64)], axis=1),
+                                              rec[keep, 9:13], nf, self._is_cat_d, nan_bin=self._nan_bin_d, out=self._tmp)
+            else:
+                F.gbdt_partition_segments(self.bins, self._rows, np.stack([start[keep], count[keep], f, b] + also, axis=1), nf, out=self._tmp, also_left=missing)
             self._rows, self._tmp = self._tmp, self._rows
             # the children, interleaved (left, right): ascending start again
             c_leaf = np.stack([leaf[keep], leaves + np.arange(k)], axis=1)
@@ -495,7 +616,7 @@ class GBDT:
             nodes, leaves, depth = nodes + k, leaves + k, depth + 1
             can = self._splittable(c_count, depth)
             c_slot = np.repeat(slot[keep][:, None], 2, axis=1)
-            c_rec = np.zeros((k, 2, 9), np.int64)
+            c_rec = np.zeros((k, 2, ncol), np.int64)
             c_rec[:, :, 0], c_rec[:, :, 1:3] = np.float64(-np.inf).view(np.int64), -1
             pairs = np.nonzero(can.any(axis=1))[0] if leaves < cap else np.zeros(0, np.int64)
             if pairs.size:
@@ -509,23 +630,36 @@ class GBDT:
                 F.gbdt_hist_sub_segments(pool, np.stack([slot[keep][pairs], fresh, slot[keep][pairs]], axis=1))   # the larger child, in the parent's slot
                 sp, ss = np.nonzero(can[pairs])
                 out = self._lrec[:sp.size]
-                F.gbdt_best_split_slots(pool, c_slot[pairs[sp], ss], self._nbins_d, self._expo, p["lambda_l2"], p["min_data_in_leaf"],
-                                        p["min_sum_hessian_in_leaf"], p["min_gain_to_split"], out=out, nan_bin=self._nan_bin_d)
+                if cats:
+                    F.gbdt_best_split_slots_cat(pool, c_slot[pairs[sp], ss], self._nbins_d, self._expo, self._is_cat_d, p["cat_smooth"], p["lambda_l2"],
+                                                p["min_data_in_leaf"], p["min_sum_hessian_in_leaf"], p["min_gain_to_split"], out=out,
+                                                sets=self._lsets[:sp.size], nan_bin=self._nan_bin_d)
+                    out = torch.cat([out, self._lsets[:sp.size]], dim=1)
+                else:
+                    F.gbdt_best_split_slots(pool, c_slot[pairs[sp], ss], self._nbins_d, self._expo, p["lambda_l2"], p["min_data_in_leaf"],
+                                            p["min_sum_hessian_in_leaf"], p["min_gain_to_split"], out=out, nan_bin=self._nan_bin_d)
                 c_rec[pairs[sp], ss] = out.cpu().numpy()                   # the one synchronisation of this level
                 self.host_reads += 1
             leaf, start, count, slot = c_leaf.reshape(-1), c_start.reshape(-1), c_count.reshape(-1), c_slot.reshape(-1)
-            parent, side, rec = np.repeat(node, 2), np.tile(np.array([0, 1], np.int64), k), c_rec.reshape(-1, 9)
-        return feature[:nodes], threshold[:nodes], left[:nodes], right[:nodes], starts[:leaves].tolist(), g_sum[:leaves].tolist(), h_sum[:leaves].tolist(), split_bin[:nodes], go_left[:nodes]
+            parent, side, rec = np.repeat(node, 2), np.tile(np.array([0, 1], np.int64), k), c_rec.reshape(-1, ncol)
+        return (feature[:nodes], threshold[:nodes], left[:nodes], right[:nodes], starts[:leaves].tolist(), g_sum[:leaves].tolist(), h_sum[:leaves].tolist(),
+                split_bin[:nodes], go_left[:nodes], cat_index[:nodes] if cats else None, cat_sets)
 
     # ---- the model
     def flat(self):
-        """The flat tree arrays ptr_gbdt_predict reads (numpy): feature, threshold, left, right, value, tree_offsets."""
+        """The flat tree arrays ptr_gbdt_predict reads (numpy): feature, threshold, left, right, value, tree_offsets; under use_missing
+        default_left; with categorical features cat_index (per node -1, or the index of its left set among ALL trees' sets) and cat_sets."""
         cat = lambda k, dt: np.concatenate([t[k] for t in self.trees]).astype(dt) if self.trees else np.zeros(0, dt)
         offs = np.concatenate([[0], np.cumsum([t["feature"].size for t in self.trees])]).astype(np.int32)
         out = {"feature": cat("feature", np.int32), "threshold": cat("threshold", np.float32), "left": cat("left", np.int32),
                "right": cat("right", np.int32), "value": cat("value", np.float32), "tree_offsets": offs}
         if self.params["use_missing"]:
             out["default_left"] = cat("default_left", np.uint8)
+        if self.params["categorical_feature"]:
+            base = np.concatenate([[0], np.cumsum([t["cat_set"].shape[0] for t in self.trees])]).astype(np.int32)
+            out["cat_index"] = (np.concatenate([np.where(t["cat_index"] >= 0, t["cat_index"] + b, -1) for t, b in zip(self.trees, base)]).astype(np.int32)
+                                if self.trees else np.zeros(0, np.int32))
+            out["cat_sets"] = (np.concatenate([t["cat_set"] for t in self.trees]) if self.trees else np.zeros((0, 4))).astype(np.int64).reshape(-1, 4)
         return out
 
     def predict(self, X, num_iteration=None, first_tree=0, check_finite=True):
@@ -533,7 +667,9 @@ class GBDT:
         (default: up to best_iteration when early stopping set it, else all), summed in tree order in fp32 — for a training row the bits of
         its resident training score.  A NaN or an infinity in X raises, as in bin_edges (a NaN would go right at every node, while binning
         puts it left); the check costs one synchronisation, and check_finite=False skips it for a matrix the caller has already checked.
-        A model trained under use_missing takes NaNs: at a node a NaN feature follows the node's default_left; an infinity still raises."""
+        A model trained under use_missing takes NaNs: at a node a NaN feature follows the node's default_left; an infinity still raises.
+        A categorical column must hold integer codes in 0 .. max_bin - 1 (the same check; check_finite=False skips it, and the kernel then
+        sends what is no integer code in 0 .. 255 right).  A code the training data never held is legal: it is in no left set and goes right."""
         dev = self._dev()
         if self._flat is None:
             self._flat = {k: torch.from_numpy(v).to(dev) for k, v in self.flat().items()}
@@ -542,8 +678,11 @@ class GBDT:
         if not 0 <= first_tree <= stop <= len(self.trees):
             raise ValueError(f"trees {first_tree} .. {stop} of {len(self.trees)}")
         Xd = _device_matrix(X, dev)
+        cats = self.params["categorical_feature"]
         if check_finite:
-            _require_values(Xd, self.params["use_missing"])
+            _require_values(Xd, self.params["use_missing"], *((cats, self.params["max_bin"]) if cats else ()))
+        if cats:
+            return self._predict_cat(Xd, first_tree, stop)
         if first_tree == 0:
             return F.gbdt_predict(Xd, fl["feature"], fl["threshold"], fl["left"], fl["right"], fl["value"], fl["tree_offsets"], stop,
                                   default_left=fl.get("default_left"))
@@ -554,15 +693,44 @@ class GBDT:
         offs = torch.from_numpy((host["tree_offsets"][first_tree:stop + 1] - lo).astype(np.int32)).to(dev)
         return F.gbdt_predict(Xd, sub["feature"], sub["threshold"], sub["left"], sub["right"], val, offs, default_left=sub.get("default_left"))
 
+    def _predict_cat(self, Xd, first_tree, stop):
+        """predict for a model with categorical features: the trees first_tree .. stop - 1 through ptr_gbdt_predict_cat."""
+        dev, fl = Xd.device, self._flat
+        if Xd.shape[1] != self.edges.shape[0]:
+            raise ValueError(f"X holds {Xd.shape[1]} columns, the model {self.edges.shape[0]}")
+        if self._is_cat_d is None or self._is_cat_d.device != dev:
+            self._set_is_cat(dev)
+        if first_tree == 0:
+            return F.gbdt_predict_cat(Xd, fl["feature"], fl["threshold"], fl["left"], fl["right"], fl["value"], fl["tree_offsets"], self._is_cat_d,
+                                      fl["cat_index"], fl["cat_sets"], stop, default_left=fl.get("default_left"))
+        host = self.flat()
+        lo, hi = int(host["tree_offsets"][first_tree]), int(host["tree_offsets"][stop])
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        sub = {k: up(host[k][lo:hi]) for k in ("feature", "threshold", "left", "right", "default_left") if k in host}
+        ci = host["cat_index"][lo:hi]
+        first = int((host["cat_index"][:lo] >= 0).sum())                   # the sets of the trees ahead
+        sets = host["cat_sets"][first:first + int((ci >= 0).sum())]
+        val = up(host["value"][lo + first_tree:hi + stop])
+        offs = up((host["tree_offsets"][first_tree:stop + 1] - lo).astype(np.int32))
+        return F.gbdt_predict_cat(Xd, sub["feature"], sub["threshold"], sub["left"], sub["right"], val, offs, self._is_cat_d,
+                                  up(np.where(ci >= 0, ci - first, -1).astype(np.int32)), up(sets), default_left=sub.get("default_left"))
+
     def save_model(self, path):
         """An .npz of this project's own (not LightGBM's text format): the flat tree arrays, the bin edges, the parameters.  Format 1
-        without use_missing (the file this method wrote before the switch existed: the switch is not among its parameters); format 2 under
-        it, with default_left per node and nan_bin per feature."""
-        if self.params["use_missing"]:
-            head = dict(format=np.int64(MODEL_FORMAT_MISSING), params=np.array(json.dumps(self.params)), edges=self.edges, nbins=self.nbins,
+        without use_missing (the file this method wrote before the switch existed: neither the switch nor the categorical keys are among its
+        parameters); format 2 under it, with default_left per node and nan_bin per feature; format 3 with categorical features: format 1
+        or 2 (by use_missing, with every parameter) plus categorical_feature, cat_index per node and cat_sets."""
+        if self.params["categorical_feature"]:
+            head = dict(format=np.int64(MODEL_FORMAT_CAT), params=np.array(json.dumps(self.params)), edges=self.edges, nbins=self.nbins,
+                        categorical_feature=np.array(self.params["categorical_feature"], np.int32))
+            if self.params["use_missing"]:
+                head["nan_bin"] = np.full(0, -1, np.int32) if self.nan_bin is None else self.nan_bin
+        elif self.params["use_missing"]:
+            params = {k: v for k, v in self.params.items() if k not in CAT_KEYS}
+            head = dict(format=np.int64(MODEL_FORMAT_MISSING), params=np.array(json.dumps(params)), edges=self.edges, nbins=self.nbins,
                         nan_bin=np.full(0, -1, np.int32) if self.nan_bin is None else self.nan_bin)
         else:
-            params = {k: v for k, v in self.params.items() if k != "use_missing"}
+            params = {k: v for k, v in self.params.items() if k != "use_missing" and k not in CAT_KEYS}
             head = dict(format=np.int64(MODEL_FORMAT), params=np.array(json.dumps(params)), edges=self.edges, nbins=self.nbins)
         with open(path, "wb") as fh:
             np.savez(fh, **head, best_iteration=np.int64(self.best_iteration or 0), **self.flat())
@@ -572,22 +740,35 @@ class GBDT:
         """The booster save_model wrote; it predicts the same bits.  (The binned training data are not part of a model.)"""
         with np.load(path, allow_pickle=False) as z:
             fmt = int(z["format"])
-            if fmt not in (MODEL_FORMAT, MODEL_FORMAT_MISSING):
-                raise ValueError(f"{path}: model format {fmt}, this version reads {MODEL_FORMAT} and {MODEL_FORMAT_MISSING}")
+            if fmt not in (MODEL_FORMAT, MODEL_FORMAT_MISSING, MODEL_FORMAT_CAT):
+                raise ValueError(f"{path}: model format {fmt}, this version reads {MODEL_FORMAT}, {MODEL_FORMAT_MISSING} and {MODEL_FORMAT_CAT}")
             self = cls(json.loads(str(z["params"])), device=device)
-            if self.params["use_missing"] != (fmt == MODEL_FORMAT_MISSING):
+            cats = fmt == MODEL_FORMAT_CAT
+            if bool(self.params["categorical_feature"]) != cats or (cats and self.params["categorical_feature"] != tuple(z["categorical_feature"].tolist())):
+                raise ValueError(f"{path}: model format {fmt} with categorical_feature={self.params['categorical_feature']}")
+            if not cats and self.params["use_missing"] != (fmt == MODEL_FORMAT_MISSING):
                 raise ValueError(f"{path}: model format {fmt} with use_missing={self.params['use_missing']}")
             self.edges, self.nbins = z["edges"], z["nbins"]
-            if fmt == MODEL_FORMAT_MISSING:
+            if cats and self.params["categorical_feature"][-1] >= self.edges.shape[0]:
+                raise ValueError(f"{path}: categorical_feature {self.params['categorical_feature'][-1]} with {self.edges.shape[0]} features")
+            missing = self.params["use_missing"]
+            if missing:
                 self.nan_bin = z["nan_bin"]
+            first = 0
             self.best_iteration = int(z["best_iteration"]) or None
             offs = z["tree_offsets"]
             for t in range(offs.size - 1):
                 lo, hi = int(offs[t]), int(offs[t + 1])
                 self.trees.append({"feature": z["feature"][lo:hi], "threshold": z["threshold"][lo:hi], "left": z["left"][lo:hi],
                                    "right": z["right"][lo:hi], "value": z["value"][lo + t:hi + t + 1]})
-                if fmt == MODEL_FORMAT_MISSING:
+                if missing:
                     self.trees[-1]["default_left"] = z["default_left"][lo:hi]
+                if cats:
+                    ci = z["cat_index"][lo:hi]
+                    k = int((ci >= 0).sum())
+                    self.trees[-1]["cat_index"] = np.where(ci >= 0, ci - first, -1).astype(np.int32)
+                    self.trees[-1]["cat_set"] = z["cat_sets"][first:first + k].astype(np.int64).reshape(-1, 4)
+                    first += k
         return self
 
 
@@ -679,7 +860,8 @@ class LambdaMART:
             if eval_group is None:
                 raise ValueError("eval_set needs eval_group")
             Xv = _device_matrix(Xv, self.device)
-            _require_values(Xv, self.params["use_missing"])              # once, before the first round: the rounds skip it
+            cats = self.params["categorical_feature"]
+            _require_values(Xv, self.params["use_missing"], *((cats, self.params["max_bin"]) if cats else ()))   # once, before the first round: the rounds skip it
             yv = torch.from_numpy(np.ascontiguousarray(np.asarray(yv).reshape(-1), dtype=np.float32)).to(self.device)
             valid = (Xv, yv, self.padded_index(eval_group, self.device), torch.zeros(Xv.shape[0], device=self.device, dtype=torch.float32))
         elif early_stopping_rounds is not None:
