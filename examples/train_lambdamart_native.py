@@ -7,6 +7,8 @@
     python examples/train_lambdamart_native.py --goss                            # gradient-based one-side sampling (top 0.2, other 0.1)
     python examples/train_lambdamart_native.py --objective lambdarank_ndcg       # the truncated, normalised lambdarank (level 30)
     python examples/train_lambdamart_native.py --categorical 3,7                 # the columns 3 and 7 hold codes: set splits
+    python examples/train_lambdamart_native.py --monotone 0:1,5:-1               # scores non-decreasing in column 0, non-increasing in 5
+    python examples/train_lambdamart_native.py --interaction "0,1;2,3"           # a path uses the columns of one group only (the rest: one more group)
 
 The synthetic relevance is planted: a linear part plus a feature interaction a linear scorer cannot express, graded with MSLR-WEB30K's label
 mix; a column named by --categorical holds one of 23 codes, and membership in a scattered set of 5 of them lifts the relevance, which a
@@ -68,6 +70,8 @@ def main():
     ap.add_argument("--by-query", action="store_true", help="bagging samples whole queries")
     ap.add_argument("--goss", action="store_true", help="data_sample_strategy='goss' in place of bagging")
     ap.add_argument("--categorical", default="", help="0-based columns that hold integer codes, as in 3,7 (categorical_feature)")
+    ap.add_argument("--monotone", default="", help="column:sign pairs, as in 0:1,5:-1 (monotone_constraints; the other columns get 0)")
+    ap.add_argument("--interaction", default="", help="groups of columns, as in 0,1;2,3 (interaction_constraints)")
     ap.add_argument("--queries", type=int, default=600)
     ap.add_argument("--features", type=int, default=40)
     args = ap.parse_args()
@@ -83,7 +87,18 @@ def main():
               "bagging_by_query": args.by_query, "data_sample_strategy": "goss" if args.goss else "bagging",
               "lambdarank_truncation_level": args.truncation_level, "lambdarank_norm": not args.no_norm, "sigmoid": args.sigmoid,
               "categorical_feature": cats}
+    if args.monotone:
+        mono = [0] * train[0].shape[1]
+        for pair in args.monotone.split(","):
+            col, sign = pair.split(":")
+            mono[int(col)] = int(sign)
+        params["monotone_constraints"] = mono
+    if args.interaction:
+        params["interaction_constraints"] = [[int(c) for c in g.split(",") if c.strip()] for g in args.interaction.split(";") if g.strip()]
     lm = pa.LambdaMART(params, objective=args.objective)
+    if pa.gbdt.constraints(lm.params):
+        print(f"constraints: {', '.join(pa.gbdt.constraints(lm.params))} (monotone on the columns "
+              f"{[c for c, m in enumerate(lm.params['monotone_constraints']) if m]}, groups {[list(g) for g in lm.params['interaction_constraints']]})")
     how = {None: "none", "goss": f"goss (top_rate {lm.params['top_rate']}, other_rate {lm.params['other_rate']})",
            "bagging": f"bagging {args.bagging_fraction} {'by query' if args.by_query else 'by row'}, redrawn every {args.bagging_freq} trees"}
     print(f"sampling: {how[pa.gbdt.sampling(lm.params)]}")

@@ -1241,6 +1241,49 @@ int ptr_gbdt_predict_cat(const float *X, int64_t n, int F, const int32_t *featur
                          const uint8_t *is_cat, const int32_t *cat_index, const int64_t *cat_sets, int ncat, int ntrees, float *out,
                          void *stream);
 
+/* ---- Monotone and interaction constraints (csrc/gbdt.hip; monotone_constraints, interaction_constraints of ptranking_amd/gbdt.py).
+ * ADDITIVE to ABI v8 too; every symbol above keeps its signature and its results bit for bit (the constrained scan is one more template
+ * flag of the same kernels, the older entry points passing "no constraints").  Training-time rules: a tree, prediction and the model
+ * formats do not change.  The rules are scikit-learn's (HistGradientBoostingRegressor(monotonic_cst=..., interaction_cst=...)) wherever
+ * its are deterministic, which is LightGBM's monotone_constraints_method 'basic'; tests/gbdt_cst_ref.py restates them in numpy.  Out of
+ * scope: the methods 'intermediate' and 'advanced', monotone_penalty.
+ *
+ * Per node the grower keeps (lo, hi, v) as float64: [lo, hi] bounds the values of the node's children, v is the node's own value.  Root:
+ * lo = -inf, hi = +inf, v = -G / (H + lambda_l2).
+ *
+ * The bounded gain.  Under active monotone constraints EVERY split search of the fit uses it on EVERY candidate: numeric features, the
+ * three missing-value candidates, categorical set candidates, features whose constraint is 0, nodes whose bounds are infinite.
+ *   1. vL = clamp(-GL / (HL + l2), lo, hi) = min(max(., lo), hi), and vR likewise.
+ *   2. The candidate is rejected if the feature's constraint is +1 and vL > vR, or -1 and vL < vR (a categorical feature has none).
+ *   3. gain = ((G * v) - (GL * vL)) - (GR * vR), float64 in that order, every product and difference rounded, nothing contracted.
+ *   4. The validity rules, min_gain_to_split, the tie rules and the record (9 int64) are those of the scans above.
+ * When a node splits on feature f, each child takes its clamped vL or vR as its v; with mid = (vL + vR) / 2 its bounds are
+ *   constraint 0: left [lo, hi], right [lo, hi];   +1: left [lo, mid], right [mid, hi];   -1: left [mid, hi], right [lo, mid]
+ * (scikit-learn's grower.py:574-595).  The host computes vL, vR and mid from the integer sums of the record it has read anyway.  A leaf's
+ * stored value is float32(v * learning_rate) with its clamped v.
+ *
+ * Interaction constraints.  The groups are sets of features; features in no group form one more group (scikit-learn's rule; LightGBM's
+ * treatment of unlisted features is not claimed).  The root's active groups are all groups and every feature is allowed; a child of a
+ * split on f keeps the active groups that contain f, and its allowed features are their union.  The scan skips a feature that is not
+ * allowed; a node with no valid allowed candidate is a leaf.  With interaction constraints alone the gain is that of the scans above,
+ * bit for bit, on the allowed features.
+ *
+ * ptr_gbdt_best_split_cst, ptr_gbdt_best_split_slots_cst: the arguments of the _cat forms plus three tables in device memory, read as
+ *   untrusted:  mono [F] int8 (an entry outside -1 .. 1 reads as 0);  cst [nleaf][3] ([K][3], by place in the slot list) float64
+ *   (lo, hi, v), or NULL: interaction constraints alone;  allowed [nleaf][F] ([K][F]) uint8, non-zero = allowed, or NULL: every feature.
+ *   A NaN among a leaf's (lo, hi, v), or lo > hi, makes that leaf's record "no split".  One of cst and allowed must be given, and cst
+ *   needs mono.  is_cat may be NULL here (no categorical feature; sets is then not written and may be NULL, and ws holds 9 int64 per
+ *   (leaf, feature) in place of 13).  Everything is validated before any launch. */
+int ptr_gbdt_best_split_cst(const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *nan_bin,
+                            const uint8_t *is_cat, const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf,
+                            double min_sum_hessian_in_leaf, double min_gain_to_split, double cat_smooth, int64_t *ws, int64_t *rec,
+                            int64_t *sets, const int8_t *mono, const double *cst, const uint8_t *allowed, void *stream);
+int ptr_gbdt_best_split_slots_cst(const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin, const int32_t *nbins,
+                                  const int32_t *nan_bin, const uint8_t *is_cat, const int32_t *expo, double lambda_l2,
+                                  int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double min_gain_to_split, double cat_smooth,
+                                  int64_t *ws, int64_t *rec, int64_t *sets, const int8_t *mono, const double *cst, const uint8_t *allowed,
+                                  void *stream);
+
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):
  *   "<label> qid:<id> <fid>:<val> ... [# comment]", feature ids one-indexed unless one_indexed == 0 (Yahoo! sets,

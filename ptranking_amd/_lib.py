@@ -125,6 +125,10 @@ SIGNATURES = {
     "ptr_gbdt_best_split_cat": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_int64, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp],
     "ptr_gbdt_best_split_slots_cat": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_int64, C.c_double, C.c_double, C.c_double, _vp, _vp,
                                       _vp, _vp],
+    "ptr_gbdt_best_split_cst": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_int64, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _vp],
+    "ptr_gbdt_best_split_slots_cst": [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_int64, C.c_double, C.c_double, C.c_double, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp],
     "ptr_gbdt_partition_cat": [_vp, _i, C.c_int64, _i, _vp, C.c_int64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ptr_gbdt_partition_segments_cat": [_vp, _i, C.c_int64, _i, _vp, C.c_int64, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, C.c_int64, _vp],
     "ptr_gbdt_add_tree_binned_cat": [_vp, _vp, _i, C.c_int64, _i, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],

@@ -37,6 +37,11 @@
 // the histogram layout and the histogram kernels are the same.  The split scan is a template on "missing" (one prefix pass, the second
 // direction behind a wave-uniform test), both stable partitions and the binned walk take one more bin that goes left (also_left, -1: none)
 // and the raw predictor a default_left byte per node; each older entry point passes "no missing" and computes what it computed.
+//
+// Monotone and interaction constraints (the *_cst entry points; monotone_constraints, interaction_constraints of gbdt.py): training-time
+// rules that live in the split scan alone.  The scan is a template on "constrained" as well: such a wavefront first reads its leaf's
+// (lo, hi, v), its feature's sign and its permission from three small device tables (scalar loads: the item is wave-uniform), and every
+// candidate then takes the bounded gain; the grower computes the children's rows of the tables on the host from the record it reads anyway.
 #include <math.h>
 
 #include "ptr_gbdt.h"
@@ -209,15 +214,32 @@ struct SplitCand { double gain; int bin; int64_t gl, hl, cl; };
 // field 0 .. kRec - 1 of the record of a leaf without a split: gain -inf, feature and bin -1, no sums
 __device__ __forceinline__ int64_t gbdt_no_split(int field) { return field == 0 ? __double_as_longlong(-INFINITY) : field <= 2 ? -1 : 0; }
 
-// The gain of one candidate's left sums against the node's totals, or false where a validity rule rejects it.
+// ---- monotone and interaction constraints (the *_cst entry points; monotone_constraints and interaction_constraints of gbdt.py).
+// Three device tables, read as untrusted: mono [F] int8 (anything outside -1 .. 1 reads as 0), cst [leaves][3] float64 (lo, hi, v) or NULL
+// (interaction constraints alone: today's gain), allowed [leaves][F] uint8 or NULL (every feature allowed).
+struct GbdtCstArgs { const int8_t *mono; const double *cst; const uint8_t *allowed; };
+// What one wavefront keeps of them: on (the bounded gain applies), the feature's sign, the leaf's bounds and its value v.  Under `on` the
+// scan hands gbdt_split_gain the node's loss G * v where the unbounded gain takes the parent's term (one value live, not two).
+struct GbdtBound { bool on; int sign; double lo, hi, v; };
+
+// The gain of one candidate's left sums against the node's totals, or false where a validity rule rejects it.  kCst with bd.on: the
+// bounded gain of include/ptranking_amd.h, vL = clamp(-GL / (HL + l2), lo, hi) and vR likewise, rejected where they break the feature's
+// order, gain = ((G * v) - (GL * vL)) - (GR * vR).
+template <bool kCst>
 __device__ __forceinline__ bool gbdt_split_gain(int64_t gl, int64_t hl, int64_t cl, int64_t TG, int64_t TH, int64_t TC, int eg, int eh, double l2,
-                                                int64_t min_data, double floor_h, double min_gain, double parent, double &gain) {
+                                                int64_t min_data, double floor_h, double min_gain, double parent, double &gain, const GbdtBound &bd) {
     const int64_t cr = TC - cl;
     if (cl < min_data || cr < min_data) return false;
     const double GL = ldexp((double)gl, -eg), HL = ldexp((double)hl, -eh);
     const double GR = ldexp((double)(TG - gl), -eg), HR = ldexp((double)(TH - hl), -eh);
     if (!(HL >= floor_h) || !(HR >= floor_h)) return false;
-    gain = ((GL * GL) / (HL + l2) + (GR * GR) / (HR + l2)) - parent;
+    if (kCst && bd.on) {
+        const double vl = fmin(fmax(-GL / (HL + l2), bd.lo), bd.hi), vr = fmin(fmax(-GR / (HR + l2), bd.lo), bd.hi);
+        if ((bd.sign > 0 && vl > vr) || (bd.sign < 0 && vl < vr)) return false;
+        gain = ((parent - (GL * vl)) - (GR * vr));
+    } else {
+        gain = ((GL * GL) / (HL + l2) + (GR * GR) / (HR + l2)) - parent;
+    }
     return gain >= min_gain;
 }
 
@@ -234,10 +256,10 @@ __device__ __forceinline__ bool gbdt_split_gain(int64_t gl, int64_t hl, int64_t 
 // and the HIGHEST among the missing-left ones (scikit-learn scans those from the top bin down and keeps the first of equal gains; bins
 // that are empty in a node make such ties bit-exact and common).  Field 2 of the record is bin + 256 * default_left; with MC == 0
 // default_left = (left count > right count).
-template <bool kMissing>
+template <bool kMissing, bool kCst>
 __device__ __forceinline__ void gbdt_split_scan(const int64_t *__restrict__ hp, int f, int lane, int max_bin, const int32_t *__restrict__ nbins,
                                                 const int32_t *__restrict__ nan_bin, const int32_t *__restrict__ expo, double l2, int64_t min_data,
-                                                double min_hess, double min_gain, int64_t *__restrict__ r) {
+                                                double min_hess, double min_gain, int64_t *__restrict__ r, GbdtBound bd) {
     const int nb = min(max(nbins[f], 1), max_bin);
     int64_t MG = 0, MH = 0, MC = 0;
     if (kMissing) {
@@ -255,7 +277,7 @@ __device__ __forceinline__ void gbdt_split_scan(const int64_t *__restrict__ hp, 
     const int64_t TG = __shfl(ig + sg, kWave - 1) + MG, TH = __shfl(ih + sh, kWave - 1) + MH, TC = __shfl(ic + sc, kWave - 1) + MC;
     const int eg = expo[0], eh = expo[1];
     const double G = ldexp((double)TG, -eg), H = ldexp((double)TH, -eh);
-    const double parent = (G * G) / (H + l2);
+    const double parent = (kCst && bd.on) ? G * bd.v : (G * G) / (H + l2);
     const double floor_h = fmax(min_hess, 0x1p-40);
     SplitCand best{-INFINITY, -1, 0, 0, 0};
 #pragma unroll
@@ -264,11 +286,11 @@ __device__ __forceinline__ void gbdt_split_scan(const int64_t *__restrict__ hp, 
         if (b >= nb - 1 && !(kMissing && MC > 0 && b == nb - 1)) continue;   // the last bin leaves nothing on the right, unless the NaNs are there
         const int64_t gl = ig + pg[k], hl = ih + ph[k], cl = ic + pc[k];
         double gain;
-        if (gbdt_split_gain(gl, hl, cl, TG, TH, TC, eg, eh, l2, min_data, floor_h, min_gain, parent, gain) &&
+        if (gbdt_split_gain<kCst>(gl, hl, cl, TG, TH, TC, eg, eh, l2, min_data, floor_h, min_gain, parent, gain, bd) &&
             (gain > best.gain || (kMissing && gain == best.gain && b < best.bin)))
             best = SplitCand{gain, b, gl, hl, cl};                       // ascending bins: a tie keeps the lowest (and beats any missing-left key)
         if (kMissing && MC > 0 && b < nb - 1 &&
-            gbdt_split_gain(gl + MG, hl + MH, cl + MC, TG, TH, TC, eg, eh, l2, min_data, floor_h, min_gain, parent, gain) &&
+            gbdt_split_gain<kCst>(gl + MG, hl + MH, cl + MC, TG, TH, TC, eg, eh, l2, min_data, floor_h, min_gain, parent, gain, bd) &&
             (gain > best.gain || (gain == best.gain && 511 - b < best.bin)))
             best = SplitCand{gain, 511 - b, gl + MG, hl + MH, cl + MC};   // a tie among missing-left candidates keeps the highest bin
     }
@@ -319,10 +341,11 @@ struct GbdtCatArgs { const uint8_t *is_cat; double cat_smooth; int64_t *sets; };
 // of "the last i + 1" the used total minus P[u - 2 - i].  A candidate's order key is i left to right and 256 + i right to left (i + 1
 // categories go left): the lowest key wins a tie, as in the numeric scan.  The winner's set is built from the ranks: a nibble per lane,
 // OR-ed over each group of 16 lanes into one 64-bit word, stored by the lanes 0, 16, 32 and 48.
+template <bool kCst>
 __device__ __forceinline__ void gbdt_split_scan_cat(const int64_t *__restrict__ hp, int f, int lane, int max_bin, const int32_t *__restrict__ nbins,
                                                     const int32_t *__restrict__ nan_bin, const int32_t *__restrict__ expo, double l2, int64_t min_data,
                                                     double min_hess, double min_gain, double cat_smooth, int64_t *sorted, int64_t *__restrict__ r,
-                                                    int64_t *__restrict__ set) {
+                                                    int64_t *__restrict__ set, GbdtBound bd) {
     const int nb = min(max(nbins[f], 1), max_bin);
     int mbin = nan_bin ? nan_bin[f] : -1;
     if (mbin < nb || mbin >= max_bin) mbin = -1;
@@ -339,8 +362,9 @@ __device__ __forceinline__ void gbdt_split_scan_cat(const int64_t *__restrict__ 
                   TC = __shfl(wave_scan_add(sc, lane), kWave - 1);
     const int eg = expo[0], eh = expo[1];
     const double G = ldexp((double)TG, -eg), H = ldexp((double)TH, -eh);
-    const double parent = (G * G) / (H + l2);
+    const double parent = (kCst && bd.on) ? G * bd.v : (G * G) / (H + l2);
     const double floor_h = fmax(min_hess, 0x1p-40);
+    if (kCst) bd.sign = 0;                                              // a set split has no order to keep
     const double factor = (double)TC / H;
     double key[4];
     int u = 0;
@@ -389,11 +413,12 @@ __device__ __forceinline__ void gbdt_split_scan_cat(const int64_t *__restrict__ 
         if (u <= 1 || p >= u) continue;
         const int64_t gl = ig + pg[k], hl = ih + ph[k], cl = ic + pc[k];
         double gain;
-        if (p < mid && gbdt_split_gain(gl, hl, cl, TG, TH, TC, eg, eh, l2, min_data, floor_h, min_gain, parent, gain) &&
+        if (p < mid && gbdt_split_gain<kCst>(gl, hl, cl, TG, TH, TC, eg, eh, l2, min_data, floor_h, min_gain, parent, gain, bd) &&
             (gain > best.gain || (gain == best.gain && p < best.bin)))
             best = SplitCand{gain, p, gl, hl, cl};                       // left to right: the first p + 1 sorted categories
         const int i = u - 2 - p;                                        // right to left: the last i + 1, for i = 0 .. mid - 2
-        if (i >= 0 && i <= mid - 2 && gbdt_split_gain(UG - gl, UH - hl, UC - cl, TG, TH, TC, eg, eh, l2, min_data, floor_h, min_gain, parent, gain) &&
+        if (i >= 0 && i <= mid - 2 &&
+            gbdt_split_gain<kCst>(UG - gl, UH - hl, UC - cl, TG, TH, TC, eg, eh, l2, min_data, floor_h, min_gain, parent, gain, bd) &&
             (gain > best.gain || (gain == best.gain && 256 + i < best.bin)))
             best = SplitCand{gain, 256 + i, UG - gl, UH - hl, UC - cl};
     }
@@ -426,41 +451,75 @@ __device__ __forceinline__ void gbdt_split_scan_cat(const int64_t *__restrict__ 
     }
 }
 
+// What the constrained scan reads for the wavefront of (leaf, f), all of it wave-uniform -> false where the wavefront has nothing to
+// search: the feature is not allowed at the leaf, or the leaf's bounds are no interval (a NaN among lo, hi, v, or lo > hi).
+// The wavefront's leaf and feature pass through v_readfirstlane, so the table reads are scalar loads and the bounds stay out of the VGPRs.
+__device__ __forceinline__ bool gbdt_cst_bound(const GbdtCstArgs &cs, int64_t leaf_v, int f_v, int F, GbdtBound &bd) {
+    const int64_t leaf = __builtin_amdgcn_readfirstlane((int)leaf_v);     // below nleaf (K), an int
+    const int f = __builtin_amdgcn_readfirstlane(f_v);
+    bd = GbdtBound{false, 0, 0.0, 0.0, 0.0};
+    if (cs.allowed && !cs.allowed[leaf * F + f]) return false;
+    if (!cs.cst) return true;
+    const double lo = cs.cst[leaf * 3], hi = cs.cst[leaf * 3 + 1], v = cs.cst[leaf * 3 + 2];
+    if (!(lo <= hi) || v != v) return false;
+    const int m = cs.mono[f];
+    bd = GbdtBound{true, m == 1 ? 1 : m == -1 ? -1 : 0, lo, hi, v};
+    return true;
+}
+
 // kCat (the *_cat entry points): a feature with is_cat[f] != 0 takes the categorical scan, any other the numeric one and a zero set; the
-// branch is uniform for the wavefront.  Without kCat the kernel holds neither the branch nor the LDS.
-template <bool kMissing, bool kCat> __global__ void __launch_bounds__(kBlock)
+// branch is uniform for the wavefront.  Without kCat the kernel holds neither the branch nor the LDS.  kCst (the *_cst entry points): the
+// wavefront first reads its leaf's bounds and its feature's sign and permission; without kCst the kernel reads none of the three tables.
+template <bool kMissing, bool kCat, bool kCst> __global__ void __launch_bounds__(kBlock)
 gbdt_split_feature_kernel(const int64_t *__restrict__ hist, int nleaf, int F, int max_bin, const int32_t *__restrict__ nbins,
                           const int32_t *__restrict__ nan_bin, const int32_t *__restrict__ expo, double l2, int64_t min_data, double min_hess,
-                          double min_gain, int64_t *__restrict__ ws, const GbdtCatArgs cat) {
+                          double min_gain, int64_t *__restrict__ ws, const GbdtCatArgs cat, const GbdtCstArgs cs) {
     const int lane = threadIdx.x & (kWave - 1);
-    const int64_t item = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    int wave = threadIdx.x >> 6;
+    if constexpr (kCst) wave = __builtin_amdgcn_readfirstlane(wave);     // the item is wave-uniform: its addresses stay in scalar registers
+    const int64_t item = (int64_t)blockIdx.x * (kBlock / kWave) + wave;
     if (item >= (int64_t)nleaf * F) return;
     const int f = (int)(item % F);
+    GbdtBound bd{false, 0, 0.0, 0.0, 0.0};
+    if constexpr (kCst) {
+        if (!gbdt_cst_bound(cs, item / F, f, F, bd)) {
+            if (lane < kRec) ws[item * kRec + lane] = gbdt_no_split(lane);
+            if (kCat && lane < kSetWords) cat.sets[item * kSetWords + lane] = 0;
+            return;
+        }
+    }
     if constexpr (kCat) {
         __shared__ int64_t cat_sorted[kBlock / kWave][kCatSorted];
         if (cat.is_cat[f]) {
-            gbdt_split_scan_cat(hist + item * max_bin * 3, f, lane, max_bin, nbins, kMissing ? nan_bin : nullptr, expo, l2, min_data, min_hess, min_gain,
-                                cat.cat_smooth, cat_sorted[threadIdx.x >> 6], ws + item * kRec, cat.sets + item * kSetWords);
+            gbdt_split_scan_cat<kCst>(hist + item * max_bin * 3, f, lane, max_bin, nbins, kMissing ? nan_bin : nullptr, expo, l2, min_data, min_hess,
+                                      min_gain, cat.cat_smooth, cat_sorted[threadIdx.x >> 6], ws + item * kRec, cat.sets + item * kSetWords, bd);
             return;
         }
         if (lane < kSetWords) cat.sets[item * kSetWords + lane] = 0;
     }
-    gbdt_split_scan<kMissing>(hist + item * max_bin * 3, f, lane, max_bin, nbins, nan_bin, expo, l2, min_data, min_hess, min_gain, ws + item * kRec);
+    gbdt_split_scan<kMissing, kCst>(hist + item * max_bin * 3, f, lane, max_bin, nbins, nan_bin, expo, l2, min_data, min_hess, min_gain, ws + item * kRec,
+                                    bd);
 }
 
 // The same scan over a list of K slots of a histogram pool [nslots][F][max_bin][3]: item = (k, feature).  A slot outside the pool gives the
-// record of a leaf without a split, and is never read.
-template <bool kMissing, bool kCat> __global__ void __launch_bounds__(kBlock)
+// record of a leaf without a split, and is never read.  The tables of kCst are indexed by k, the place in the list.
+template <bool kMissing, bool kCat, bool kCst> __global__ void __launch_bounds__(kBlock)
 gbdt_split_feature_slots_kernel(const int64_t *__restrict__ pool, int nslots, const int32_t *__restrict__ slots, int K, int F, int max_bin,
                                 const int32_t *__restrict__ nbins, const int32_t *__restrict__ nan_bin, const int32_t *__restrict__ expo, double l2,
-                                int64_t min_data, double min_hess, double min_gain, int64_t *__restrict__ ws, const GbdtCatArgs cat) {
+                                int64_t min_data, double min_hess, double min_gain, int64_t *__restrict__ ws, const GbdtCatArgs cat,
+                                const GbdtCstArgs cs) {
     const int lane = threadIdx.x & (kWave - 1);
-    const int64_t item = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    int wave = threadIdx.x >> 6;
+    if constexpr (kCst) wave = __builtin_amdgcn_readfirstlane(wave);
+    const int64_t item = (int64_t)blockIdx.x * (kBlock / kWave) + wave;
     if (item >= (int64_t)K * F) return;
     const int f = (int)(item % F);
     const int slot = slots[item / F];
     int64_t *r = ws + item * kRec;
-    if (slot < 0 || slot >= nslots) {
+    GbdtBound bd{false, 0, 0.0, 0.0, 0.0};
+    bool live = slot >= 0 && slot < nslots;
+    if constexpr (kCst) live = live && gbdt_cst_bound(cs, item / F, f, F, bd);
+    if (!live) {
         if (lane < kRec) r[lane] = gbdt_no_split(lane);
         if (kCat && lane < kSetWords) cat.sets[item * kSetWords + lane] = 0;
         return;
@@ -469,13 +528,13 @@ gbdt_split_feature_slots_kernel(const int64_t *__restrict__ pool, int nslots, co
     if constexpr (kCat) {
         __shared__ int64_t cat_sorted[kBlock / kWave][kCatSorted];
         if (cat.is_cat[f]) {
-            gbdt_split_scan_cat(hp, f, lane, max_bin, nbins, kMissing ? nan_bin : nullptr, expo, l2, min_data, min_hess, min_gain, cat.cat_smooth,
-                                cat_sorted[threadIdx.x >> 6], r, cat.sets + item * kSetWords);
+            gbdt_split_scan_cat<kCst>(hp, f, lane, max_bin, nbins, kMissing ? nan_bin : nullptr, expo, l2, min_data, min_hess, min_gain, cat.cat_smooth,
+                                      cat_sorted[threadIdx.x >> 6], r, cat.sets + item * kSetWords, bd);
             return;
         }
         if (lane < kSetWords) cat.sets[item * kSetWords + lane] = 0;
     }
-    gbdt_split_scan<kMissing>(hp, f, lane, max_bin, nbins, nan_bin, expo, l2, min_data, min_hess, min_gain, r);
+    gbdt_split_scan<kMissing, kCst>(hp, f, lane, max_bin, nbins, nan_bin, expo, l2, min_data, min_hess, min_gain, r, bd);
 }
 
 // One wavefront per leaf: the best of its F feature records, ties to the lowest feature.  sets (NULL: none): the winner's left set, from
@@ -1045,13 +1104,24 @@ static int check_cat_search(const GbdtCatSearch &cat, bool on, int F, const char
     return 0;
 }
 
+// The constrained form of a split search (the *_cst entry points): cst == NULL is "interaction constraints alone", allowed == NULL "monotone
+// constraints alone"; one of the two must be there, and cst needs mono.
+static int check_cst_search(const GbdtCstArgs &cs, bool on, int F, const char *who) {
+    if (!on) return 0;
+    if (!cs.cst && !cs.allowed) { set_error("%s: neither cst nor allowed: the unconstrained entry point serves that", who); return PTR_ERR_INVALID_ARG; }
+    if (cs.cst && F > 0 && !cs.mono) { set_error("%s: NULL pointer (mono, with cst)", who); return PTR_ERR_INVALID_ARG; }
+    return 0;
+}
+
 static int gbdt_best_split_impl(const char *who, const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *nan_bin,
                                 bool missing, const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf, double min_sum_hessian_in_leaf,
-                                double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream, bool cat_on = false, GbdtCatSearch cat = {nullptr, 0.0, nullptr}) {
+                                double min_gain_to_split, int64_t *ws, int64_t *rec, void *stream, bool cat_on = false, GbdtCatSearch cat = {nullptr, 0.0, nullptr},
+                                bool cst_on = false, GbdtCstArgs cs = {nullptr, nullptr, nullptr}) {
     if (nleaf < 0 || F < 0) { set_error("%s: negative size (nleaf=%d, F=%d)", who, nleaf, F); return PTR_ERR_INVALID_ARG; }
     if (int rc = check_max_bin(max_bin, who)) return rc;
     if (int rc = check_split_thresholds(lambda_l2, min_sum_hessian_in_leaf, min_gain_to_split, who)) return rc;
     if (int rc = check_cat_search(cat, cat_on && nleaf > 0, F, who)) return rc;
+    if (int rc = check_cst_search(cs, cst_on && nleaf > 0, F, who)) return rc;
     if (nleaf == 0) return 0;
     if (!rec || (F > 0 && (!hist || !nbins || !expo || !ws || (missing && !nan_bin)))) {
         set_error("%s: NULL pointer (hist, nbins%s, expo, ws or rec)", who, missing ? ", nan_bin" : "");
@@ -1061,12 +1131,18 @@ static int gbdt_best_split_impl(const char *who, const int64_t *hist, int nleaf,
     const dim3 grid((unsigned)((items + 3) / 4));
     int64_t *ws_sets = cat_on ? ws + items * kRec : nullptr;
     const GbdtCatArgs ca{cat.is_cat, cat.cat_smooth, ws_sets};
-#define PTR_LAUNCH_SPLIT(M, C)                                                                                                                        \
-    hipLaunchKernelGGL((gbdt_split_feature_kernel<M, C>), grid, dim3(kBlock), 0, as_stream(stream), hist, nleaf, F, max_bin, nbins, nan_bin, expo, lambda_l2, \
-                       min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws, ca)
-    if (items > 0 && cat_on) { if (missing) PTR_LAUNCH_SPLIT(true, true); else PTR_LAUNCH_SPLIT(false, true); }
-    else if (items > 0 && missing) PTR_LAUNCH_SPLIT(true, false);
-    else if (items > 0) PTR_LAUNCH_SPLIT(false, false);
+#define PTR_LAUNCH_SPLIT(M, C, S)                                                                                                                     \
+    hipLaunchKernelGGL((gbdt_split_feature_kernel<M, C, S>), grid, dim3(kBlock), 0, as_stream(stream), hist, nleaf, F, max_bin, nbins, nan_bin, expo,     \
+                       lambda_l2, min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws, ca, cs)
+#define PTR_LAUNCH_SPLIT_MC(S)                                                                                                                        \
+    do {                                                                                                                                              \
+        if (cat_on) { if (missing) PTR_LAUNCH_SPLIT(true, true, S); else PTR_LAUNCH_SPLIT(false, true, S); }                                          \
+        else if (missing) PTR_LAUNCH_SPLIT(true, false, S);                                                                                           \
+        else PTR_LAUNCH_SPLIT(false, false, S);                                                                                                       \
+    } while (0)
+    if (items > 0 && cst_on) PTR_LAUNCH_SPLIT_MC(true);
+    else if (items > 0) PTR_LAUNCH_SPLIT_MC(false);
+#undef PTR_LAUNCH_SPLIT_MC
 #undef PTR_LAUNCH_SPLIT
     hipLaunchKernelGGL(gbdt_split_leaf_kernel, dim3(nleaf), dim3(kWave), 0, as_stream(stream), ws, F, rec, ws_sets, cat_on ? cat.sets : nullptr);
     return check_hip(hipGetLastError(), who);
@@ -1092,6 +1168,15 @@ extern "C" int ptr_gbdt_best_split_cat(const int64_t *hist, int nleaf, int F, in
                                        int64_t *sets, void *stream) {
     return gbdt_best_split_impl("ptr_gbdt_best_split_cat", hist, nleaf, F, max_bin, nbins, nan_bin, nan_bin != nullptr, expo, lambda_l2, min_data_in_leaf,
                                 min_sum_hessian_in_leaf, min_gain_to_split, ws, rec, stream, true, GbdtCatSearch{is_cat, cat_smooth, sets});
+}
+
+extern "C" int ptr_gbdt_best_split_cst(const int64_t *hist, int nleaf, int F, int max_bin, const int32_t *nbins, const int32_t *nan_bin,
+                                       const uint8_t *is_cat, const int32_t *expo, double lambda_l2, int64_t min_data_in_leaf,
+                                       double min_sum_hessian_in_leaf, double min_gain_to_split, double cat_smooth, int64_t *ws, int64_t *rec,
+                                       int64_t *sets, const int8_t *mono, const double *cst, const uint8_t *allowed, void *stream) {
+    return gbdt_best_split_impl("ptr_gbdt_best_split_cst", hist, nleaf, F, max_bin, nbins, nan_bin, nan_bin != nullptr, expo, lambda_l2, min_data_in_leaf,
+                                min_sum_hessian_in_leaf, min_gain_to_split, ws, rec, stream, is_cat != nullptr, GbdtCatSearch{is_cat, cat_smooth, sets}, true,
+                                GbdtCstArgs{mono, cst, allowed});
 }
 
 extern "C" size_t ptr_gbdt_partition_ws_ints(int64_t m) {
@@ -1362,11 +1447,13 @@ extern "C" int ptr_gbdt_hist_sub_segments(int64_t *pool, int nslots, int F, int 
 static int gbdt_best_split_slots_impl(const char *who, const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin,
                                       const int32_t *nbins, const int32_t *nan_bin, bool missing, const int32_t *expo, double lambda_l2,
                                       int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double min_gain_to_split, int64_t *ws, int64_t *rec,
-                                      void *stream, bool cat_on = false, GbdtCatSearch cat = {nullptr, 0.0, nullptr}) {
+                                      void *stream, bool cat_on = false, GbdtCatSearch cat = {nullptr, 0.0, nullptr}, bool cst_on = false,
+                                      GbdtCstArgs cs = {nullptr, nullptr, nullptr}) {
     if (int rc = check_level_common(who, 0, F, 0, max_bin, K, kCheckMaxBin)) return rc;
     if (nslots < 0) { set_error("%s: negative size (nslots=%d)", who, nslots); return PTR_ERR_INVALID_ARG; }
     if (int rc = check_split_thresholds(lambda_l2, min_sum_hessian_in_leaf, min_gain_to_split, who)) return rc;
     if (int rc = check_cat_search(cat, cat_on && K > 0, F, who)) return rc;
+    if (int rc = check_cst_search(cs, cst_on && K > 0, F, who)) return rc;
     if (K == 0) return 0;
     if (!pool || !slots || !nbins || !expo || !ws || !rec || (missing && !nan_bin)) {
         set_error("%s: NULL pointer (pool, slots, nbins%s, expo, ws or rec)", who, missing ? ", nan_bin" : "");
@@ -1376,12 +1463,18 @@ static int gbdt_best_split_slots_impl(const char *who, const int64_t *pool, int 
     const dim3 grid((unsigned)((items + 3) / 4));
     int64_t *ws_sets = cat_on ? ws + items * kRec : nullptr;
     const GbdtCatArgs ca{cat.is_cat, cat.cat_smooth, ws_sets};
-#define PTR_LAUNCH_SPLIT(M, C)                                                                                                                          \
-    hipLaunchKernelGGL((gbdt_split_feature_slots_kernel<M, C>), grid, dim3(kBlock), 0, as_stream(stream), pool, nslots, slots, K, F, max_bin, nbins, nan_bin, \
-                       expo, lambda_l2, min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws, ca)
-    if (cat_on) { if (missing) PTR_LAUNCH_SPLIT(true, true); else PTR_LAUNCH_SPLIT(false, true); }
-    else if (missing) PTR_LAUNCH_SPLIT(true, false);
-    else PTR_LAUNCH_SPLIT(false, false);
+#define PTR_LAUNCH_SPLIT(M, C, S)                                                                                                                       \
+    hipLaunchKernelGGL((gbdt_split_feature_slots_kernel<M, C, S>), grid, dim3(kBlock), 0, as_stream(stream), pool, nslots, slots, K, F, max_bin, nbins,     \
+                       nan_bin, expo, lambda_l2, min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws, ca, cs)
+#define PTR_LAUNCH_SPLIT_MC(S)                                                                                                                          \
+    do {                                                                                                                                                \
+        if (cat_on) { if (missing) PTR_LAUNCH_SPLIT(true, true, S); else PTR_LAUNCH_SPLIT(false, true, S); }                                            \
+        else if (missing) PTR_LAUNCH_SPLIT(true, false, S);                                                                                             \
+        else PTR_LAUNCH_SPLIT(false, false, S);                                                                                                         \
+    } while (0)
+    if (items > 0 && cst_on) PTR_LAUNCH_SPLIT_MC(true);
+    else if (items > 0) PTR_LAUNCH_SPLIT_MC(false);
+#undef PTR_LAUNCH_SPLIT_MC
 #undef PTR_LAUNCH_SPLIT
     hipLaunchKernelGGL(gbdt_split_leaf_kernel, dim3(K), dim3(kWave), 0, as_stream(stream), ws, F, rec, ws_sets, cat_on ? cat.sets : nullptr);
     return check_hip(hipGetLastError(), who);
@@ -1394,6 +1487,16 @@ extern "C" int ptr_gbdt_best_split_slots_cat(const int64_t *pool, int nslots, co
     return gbdt_best_split_slots_impl("ptr_gbdt_best_split_slots_cat", pool, nslots, slots, K, F, max_bin, nbins, nan_bin, nan_bin != nullptr, expo, lambda_l2,
                                       min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws, rec, stream, true,
                                       GbdtCatSearch{is_cat, cat_smooth, sets});
+}
+
+extern "C" int ptr_gbdt_best_split_slots_cst(const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin, const int32_t *nbins,
+                                             const int32_t *nan_bin, const uint8_t *is_cat, const int32_t *expo, double lambda_l2,
+                                             int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double min_gain_to_split, double cat_smooth,
+                                             int64_t *ws, int64_t *rec, int64_t *sets, const int8_t *mono, const double *cst, const uint8_t *allowed,
+                                             void *stream) {
+    return gbdt_best_split_slots_impl("ptr_gbdt_best_split_slots_cst", pool, nslots, slots, K, F, max_bin, nbins, nan_bin, nan_bin != nullptr, expo, lambda_l2,
+                                      min_data_in_leaf, min_sum_hessian_in_leaf, min_gain_to_split, ws, rec, stream, is_cat != nullptr,
+                                      GbdtCatSearch{is_cat, cat_smooth, sets}, true, GbdtCstArgs{mono, cst, allowed});
 }
 
 extern "C" int ptr_gbdt_best_split_slots(const int64_t *pool, int nslots, const int32_t *slots, int K, int F, int max_bin, const int32_t *nbins,

@@ -25,7 +25,7 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "gbdt_histogram_segments", "gbdt_hist_sub_segments", "gbdt_best_split_slots", "gbdt_partition_segments", "gbdt_segment_items",
            "gbdt_bag_mask", "gbdt_goss", "gbdt_partition_mask", "gbdt_add_tree_binned",
            "gbdt_best_split_cat", "gbdt_best_split_slots_cat", "gbdt_partition_cat", "gbdt_partition_segments_cat", "gbdt_add_tree_binned_cat",
-           "gbdt_predict_cat", "GBDT_MAX_BIN", "GBDT_RECORD"]
+           "gbdt_predict_cat", "gbdt_best_split_cst", "gbdt_best_split_slots_cst", "GBDT_MAX_BIN", "GBDT_RECORD"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
 # launch table, and it draws its own; irfgan_loss and adlist_loss are public too: they take a mode, as irgan_selected does)
@@ -1471,6 +1471,79 @@ def gbdt_best_split_slots_cat(pool, slots, nbins, expo, is_cat, cat_smooth=10.0,
                   _lib.ptr(is_cat), _lib.ptr(expo), C.c_double(float(lambda_l2)), C.c_int64(int(min_data_in_leaf)),
                   C.c_double(float(min_sum_hessian_in_leaf)), C.c_double(float(min_gain_to_split)), C.c_double(cat_smooth), _lib.ptr(ws), _lib.ptr(rec),
                   _lib.ptr(sets), _lib.current_stream(dev))
+    return rec, sets
+
+
+# ---- monotone and interaction constraints (the *_cst entry points; include/ptranking_amd.h states the rules).  mono: int8 [F] on the
+# device; cst: float64 [leaves, 3] = (lo, hi, v) per leaf or None (interaction constraints alone); allowed: uint8 [leaves, F] or None.
+def _gbdt_cst_tables(mono, cst, allowed, leaves, F):
+    if cst is None and allowed is None:
+        raise ValueError("neither cst nor allowed: the unconstrained search serves that")
+    if cst is not None:
+        if mono is None:
+            raise ValueError("cst needs mono")
+        cst = _check("cst", cst, torch.float64, (leaves, 3))
+    mono = None if mono is None else _check("mono", mono, torch.int8, (F,))
+    allowed = None if allowed is None else _check("allowed", allowed, torch.uint8, (leaves, F))
+    return mono, cst, allowed
+
+
+def gbdt_best_split_cst(hist, nbins, expo, mono=None, cst=None, allowed=None, is_cat=None, cat_smooth=10.0, lambda_l2=0.0, min_data_in_leaf=1,
+                        min_sum_hessian_in_leaf=1e-3, min_gain_to_split=0.0, out=None, sets=None, nan_bin=None):
+    """gbdt_best_split_cat (is_cat None: gbdt_best_split, sets then stay None) under monotone and interaction constraints -> (records int64
+    [leaves, 9], sets int64 [leaves, 4] or None).  With cst every candidate takes the bounded gain: its children's values clamped to the
+    leaf's [lo, hi], rejected where they break the order mono[f] asks for, gain = G v - GL vL - GR vR; a feature with allowed == 0 at a leaf
+    is not searched there (ptr_gbdt_best_split_cst)."""
+    hist = _check("hist", hist, torch.int64)
+    if hist.dim() == 3:
+        hist = hist[None]
+    if hist.dim() != 4 or hist.shape[3] != 3:
+        raise ValueError(f"hist must be [leaves, F, max_bin, 3], got {tuple(hist.shape)}")
+    L, F, max_bin = hist.shape[0], hist.shape[1], _gbdt_max_bin(hist.shape[2])
+    nbins = _check("nbins", nbins, torch.int32, (F,))
+    expo = _check("expo", expo, torch.int32, (2,))
+    mono, cst, allowed = _gbdt_cst_tables(mono, cst, allowed, L, F)
+    is_cat, cat_smooth = None if is_cat is None else _gbdt_is_cat(is_cat, F), _gbdt_cat_smooth(cat_smooth)
+    nan_bin = None if nan_bin is None else _gbdt_nan_bin(nan_bin, F)
+    dev = hist.device
+    rec = torch.empty((L, 9), device=dev, dtype=torch.int64) if out is None else _check("out", out, torch.int64, (L, 9))
+    if is_cat is not None:
+        sets = torch.empty((L, 4), device=dev, dtype=torch.int64) if sets is None else _check("sets", sets, torch.int64, (L, 4))
+    elif sets is not None:
+        raise ValueError("sets without is_cat")
+    ws = torch.empty((max(L * F, 1), 13 if is_cat is not None else 9), device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_best_split_cst", _lib.ptr(hist), L, F, max_bin, _lib.ptr(nbins), _lib.ptr(nan_bin), _lib.ptr(is_cat), _lib.ptr(expo),
+                  C.c_double(float(lambda_l2)), C.c_int64(int(min_data_in_leaf)), C.c_double(float(min_sum_hessian_in_leaf)),
+                  C.c_double(float(min_gain_to_split)), C.c_double(cat_smooth), _lib.ptr(ws), _lib.ptr(rec), _lib.ptr(sets), _lib.ptr(mono), _lib.ptr(cst),
+                  _lib.ptr(allowed), _lib.current_stream(dev))
+    return rec, sets
+
+
+def gbdt_best_split_slots_cst(pool, slots, nbins, expo, mono=None, cst=None, allowed=None, is_cat=None, cat_smooth=10.0, lambda_l2=0.0,
+                              min_data_in_leaf=1, min_sum_hessian_in_leaf=1e-3, min_gain_to_split=0.0, out=None, sets=None, nan_bin=None):
+    """gbdt_best_split_cst over the histograms pool[slots[k]] (slots: a host list) -> (records int64 [K, 9], sets int64 [K, 4] or None), each
+    bit-identical to gbdt_best_split_cst on a copy of that slot; row k of cst and allowed belongs to slots[k]."""
+    pool = _gbdt_pool(pool)
+    dev, F, max_bin = pool.device, pool.shape[1], pool.shape[2]
+    nbins = _check("nbins", nbins, torch.int32, (F,))
+    expo = _check("expo", expo, torch.int32, (2,))
+    is_cat, cat_smooth = None if is_cat is None else _gbdt_is_cat(is_cat, F), _gbdt_cat_smooth(cat_smooth)
+    nan_bin = None if nan_bin is None else _gbdt_nan_bin(nan_bin, F)
+    host, slots_d = _gbdt_table("slots", slots, 1, dev)
+    K = host.shape[0]
+    mono, cst, allowed = _gbdt_cst_tables(mono, cst, allowed, K, F)
+    rec = torch.empty((K, 9), device=dev, dtype=torch.int64) if out is None else _check("out", out, torch.int64, (K, 9))
+    if is_cat is not None:
+        sets = torch.empty((K, 4), device=dev, dtype=torch.int64) if sets is None else _check("sets", sets, torch.int64, (K, 4))
+    elif sets is not None:
+        raise ValueError("sets without is_cat")
+    ws = torch.empty((max(K * F, 1), 13 if is_cat is not None else 9), device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_best_split_slots_cst", _lib.ptr(pool), pool.shape[0], _lib.ptr(slots_d), K, F, max_bin, _lib.ptr(nbins), _lib.ptr(nan_bin),
+                  _lib.ptr(is_cat), _lib.ptr(expo), C.c_double(float(lambda_l2)), C.c_int64(int(min_data_in_leaf)),
+                  C.c_double(float(min_sum_hessian_in_leaf)), C.c_double(float(min_gain_to_split)), C.c_double(cat_smooth), _lib.ptr(ws), _lib.ptr(rec),
+                  _lib.ptr(sets), _lib.ptr(mono), _lib.ptr(cst), _lib.ptr(allowed), _lib.current_stream(dev))
     return rec, sets
 
 

@@ -64,8 +64,24 @@ cat_index per node (-1: numeric) and cat_set [sets, 4] int64, 256 bits per set; 
 the training data never held right (it is in no set).  With categorical_feature empty every call and every model file is the one made
 before the keys existed.  Not here: max_cat_to_onehot, cat_l2, min_data_per_group, max_cat_threshold.
 
+Monotone constraints (monotone_constraints, a sequence of -1 / 0 / +1, one per feature; LightGBM's name) and interaction constraints
+(interaction_constraints, a sequence of groups of 0-based column indices).  Both are training-time rules: a tree, predict and the model
+format numbers do not change.  The rules are scikit-learn's (HistGradientBoostingRegressor(monotonic_cst=..., interaction_cst=...)) wherever
+its are deterministic, which is LightGBM's monotone_constraints_method 'basic' (the only method here); include/ptranking_amd.h states them
+and tests/gbdt_cst_ref.py restates them.  Every node keeps (lo, hi, v) in float64: the bounds of its children's values and its own value.
+Under active monotone constraints every split search of the fit uses the bounded gain on every candidate: vL = clamp(-GL / (HL + l2), lo,
+hi) and vR likewise, the candidate rejected where vL > vR under +1 or vL < vR under -1, gain = G v - GL vL - GR vR; the children of a
+split on a constrained feature share the bound mid = (vL + vR) / 2, and a leaf stores float32(v * learning_rate) with its clamped v.
+predict is then non-decreasing (+1) or non-increasing (-1) in the feature, exactly.  A categorical column takes no monotone constraint.
+Under interaction constraints a child of a split on f keeps the groups that contain f and may split on their union only; features in
+no group form one more group (scikit-learn's rule: LightGBM's own treatment of unlisted features is not claimed).  The host computes the
+children's (lo, hi, v) from the integer sums of the record it has read anyway and uploads small tables before each search, so host_reads
+does not grow.  Whole fits are pinned to scikit-learn node for node (tests/golden/gbdt_sklearn_cst.npz).  With all constraints zero and no
+groups every call and every model file is the one made before the keys existed.  Not here: the methods 'intermediate' and 'advanced',
+monotone_penalty.
+
 Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here:
-feature_fraction, EFB, DART, monotone constraints.  There is no CPU path.
+feature_fraction, EFB, DART.  There is no CPU path.
 """
 import json
 
@@ -75,7 +91,7 @@ import torch
 from . import functional as F
 from . import letor, tree
 
-__all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS"]
+__all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS", "constraints"]
 
 # LightGBM's names, so the reference's lightgbm_para_dict passes through.  min_sum_hessian_in_leaf = 1e-3 is LightGBM's default too; the
 # reference's own dict sets 200, which suits LightGBM's built-in lambdarank Hessians, not the sums of tree.hip.
@@ -83,6 +99,7 @@ DEFAULT_PARAMS = {"learning_rate": 0.1, "num_leaves": 31, "num_trees": 100, "min
                   "lambda_l2": 0.0, "min_gain_to_split": 0.0, "max_bin": 255, "max_depth": -1, "grow_policy": "leafwise",
                   "bagging_fraction": 1.0, "bagging_freq": 0, "bagging_seed": 3, "bagging_by_query": False, "data_sample_strategy": "bagging",
                   "top_rate": 0.2, "other_rate": 0.1, "use_missing": False, "categorical_feature": (), "cat_smooth": 10.0,
+                  "monotone_constraints": (), "monotone_constraints_method": "basic", "interaction_constraints": (),
                   # LambdaMART(objective='lambdarank_ndcg') alone reads these three; the other objectives and the bare booster ignore them
                   "lambdarank_truncation_level": 30, "lambdarank_norm": True, "sigmoid": 1.0}
 IGNORED_PARAMS = ("num_threads", "verbosity", "metric", "boosting_type", "objective", "eval_at")    # accepted, without a meaning here
@@ -90,6 +107,8 @@ MODEL_FORMAT = 1                       # a model trained without use_missing
 MODEL_FORMAT_MISSING = 2               # one trained under it: format 1 with default_left per node and nan_bin per feature
 MODEL_FORMAT_CAT = 3                   # one with categorical features: format 1 or 2 plus categorical_feature, cat_index per node and cat_sets
 CAT_KEYS = ("categorical_feature", "cat_smooth")      # not among the parameters of a format 1 or 2 file
+CST_KEYS = ("monotone_constraints", "monotone_constraints_method", "interaction_constraints")   # in a model file only where one is active
+MONOTONE_METHODS = ("basic",)
 GROW_POLICIES = ("leafwise", "depthwise")
 SAMPLE_STRATEGIES = ("bagging", "goss")
 
@@ -146,6 +165,13 @@ def _params(params):
         raise ValueError(f"cat_smooth must be a number >= 0, got {p['cat_smooth']!r}") from None
     if not 0.0 <= p["cat_smooth"] < np.inf:
         raise ValueError(f"cat_smooth must be a finite number >= 0, got {p['cat_smooth']}")
+    p["monotone_constraints"] = _monotone(p["monotone_constraints"])
+    if p["monotone_constraints_method"] not in MONOTONE_METHODS:
+        raise ValueError(f"monotone_constraints_method {p['monotone_constraints_method']!r} is not implemented: only 'basic'")
+    for c in p["categorical_feature"]:
+        if c < len(p["monotone_constraints"]) and p["monotone_constraints"][c] != 0:
+            raise ValueError(f"monotone_constraints: column {c} is categorical, it takes no monotone constraint")
+    p["interaction_constraints"] = _interaction(p["interaction_constraints"])
     p["lambdarank_truncation_level"], p["sigmoid"], p["lambdarank_norm"] = F.lambdarank_ndcg_settings(p["lambdarank_truncation_level"], p["sigmoid"],
                                                                                                    p["lambdarank_norm"])
     return p
@@ -167,6 +193,58 @@ def _categorical(cat):
     if len(set(out)) != len(out):
         raise ValueError(f"categorical_feature holds a column twice: {sorted(out)}")
     return tuple(sorted(out))
+
+
+def _sequence(name, v, what):
+    if v is None:
+        return []
+    if isinstance(v, (str, bytes)) or not isinstance(v, (list, tuple, np.ndarray)):
+        raise ValueError(f"{name} must be a list or tuple of {what}, got {v!r}")
+    return np.asarray(v, dtype=object).reshape(-1).tolist() if isinstance(v, np.ndarray) and v.dtype != object else list(v)
+
+
+def _monotone(mono):
+    """monotone_constraints as a tuple of -1 / 0 / +1; anything else raises ValueError."""
+    out = []
+    for c in _sequence("monotone_constraints", mono, "-1 / 0 / +1, one per feature"):
+        if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)) or c not in (-1, 0, 1):
+            raise ValueError(f"monotone_constraints must hold -1, 0 or +1, got {c!r}")
+        out.append(int(c))
+    return tuple(out)
+
+
+def _interaction(groups):
+    """interaction_constraints as a tuple of sorted tuples of ints; an empty group or a negative or non-integer entry raises ValueError."""
+    out = []
+    for g in (groups if isinstance(groups, np.ndarray) and groups.ndim == 2 else _sequence("interaction_constraints", groups, "groups of 0-based column indices")):
+        if isinstance(g, (set, frozenset)):
+            g = sorted(g, key=repr)
+        members = _sequence("interaction_constraints", g, "groups of 0-based column indices")
+        if not members:
+            raise ValueError("interaction_constraints holds an empty group")
+        for c in members:
+            if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)):
+                raise ValueError(f"interaction_constraints must hold integers, got {c!r}")
+            if c < 0:
+                raise ValueError(f"interaction_constraints must hold 0-based column indices, got {c}")
+        out.append(tuple(sorted({int(c) for c in members})))
+    return tuple(out)
+
+
+def constraints(p):
+    """The constraints the parameters switch on, a tuple out of 'monotone' and 'interaction': () with every monotone constraint 0 (or none
+    given) and no group."""
+    return (("monotone",) if any(p["monotone_constraints"]) else ()) + (("interaction",) if p["interaction_constraints"] else ())
+
+
+def _interaction_groups(p, nf):
+    """The groups as sets over nf features, the features in no group as one more group (scikit-learn's rule); an index >= nf raises."""
+    groups = [frozenset(g) for g in p["interaction_constraints"]]
+    for g in groups:
+        if max(g) >= nf:
+            raise ValueError(f"interaction_constraints {max(g)} with {nf} columns")
+    rest = frozenset(range(nf)) - frozenset().union(*groups)
+    return groups + ([rest] if rest else [])
 
 
 def _bagging(p):
@@ -292,11 +370,13 @@ def leaf_value(g_sum, h_sum, expo, lambda_l2, learning_rate):
 
 
 class _Leaf:
-    __slots__ = ("start", "count", "depth", "slot", "parent", "side", "g", "h", "rec", "set")
+    __slots__ = ("start", "count", "depth", "slot", "parent", "side", "g", "h", "rec", "set", "cst", "groups")
 
-    def __init__(self, start, count, depth, slot, parent, side, g, h, rec, set=None):
+    def __init__(self, start, count, depth, slot, parent, side, g, h, rec, set=None, cst=None, groups=None):
         self.start, self.count, self.depth, self.slot, self.parent, self.side, self.g, self.h, self.rec = start, count, depth, slot, parent, side, g, h, rec
         self.set = set                     # categorical features: the left set of rec, 4 int64 as the host read them
+        self.cst = cst                     # monotone constraints: (lo, hi, v) float64, the bounds of the children's values and the leaf's own
+        self.groups = groups               # interaction constraints: the indices of the leaf's active groups
 
 
 def _record(r):
@@ -320,6 +400,8 @@ class GBDT:
         self.nan_bin = None                # under use_missing: the NaN bin per feature, -1 where training saw no NaN
         self._nan_bin_d = None
         self._is_cat = self._is_cat_d = None   # categorical_feature as a mask over the features: host bool [F], device uint8 [F]
+        self._mono = self._mono_d = None       # active monotone constraints: host int8 [F] and its device copy
+        self._groups = None                    # active interaction constraints: the groups as sets, the unlisted features' group included
         self.best_iteration = None
         self._device = device
         self._flat = None
@@ -338,6 +420,7 @@ class GBDT:
     def fit_bins(self, X, group=None):
         """Computes the bin edges of X (numpy array or device tensor [n, F]) on the host, bins X on the device and keeps the bins, the
         training scores (zeros) and the work buffers resident.  group: the documents per query, which bagging_by_query samples by."""
+        groups = self._check_constraints(np.shape(X))                      # the refusals of the constraints come before any device work
         dev = self._dev()
         if group is not None:
             group = np.asarray(group).reshape(-1).astype(np.int64)
@@ -374,6 +457,12 @@ class GBDT:
             self._set_is_cat(dev)
             self._sets = torch.zeros((2, 4), device=dev, dtype=torch.int64)                            # the left sets beside _rec and _lrec
             self._lsets = torch.zeros((max(p["num_leaves"], 2), 4), device=dev, dtype=torch.int64)
+        self._mono = self._mono_d = self._groups = None
+        if "monotone" in constraints(p):
+            self._mono = np.array(p["monotone_constraints"], np.int8)
+            self._mono_d = torch.from_numpy(self._mono).to(dev)
+        if groups is not None:
+            self._groups, self._allowed_rows = groups, {}
         self._pool = torch.zeros((max(p["num_leaves"], 1), self.F, p["max_bin"], 3), device=dev, dtype=torch.int64)
         self._qid = None if group is None else torch.from_numpy(np.repeat(np.arange(group.size, dtype=np.int32), group)).to(dev)
         if sampling(p):
@@ -384,6 +473,18 @@ class GBDT:
                 self._gg, self._gh = torch.empty_like(self.scores), torch.empty_like(self.scores)
                 self._info = torch.zeros(3, device=dev, dtype=torch.int32)
         return self
+
+    def _check_constraints(self, shape):
+        """Checks monotone_constraints and interaction_constraints against the columns of X -> the interaction groups as sets (the unlisted
+        features' group included), or None without interaction constraints."""
+        p = self.params
+        if not p["monotone_constraints"] and not p["interaction_constraints"]:
+            return None
+        if len(shape) != 2:
+            raise ValueError(f"X must be [rows, features], got {tuple(shape)}")
+        if p["monotone_constraints"] and len(p["monotone_constraints"]) != shape[1]:
+            raise ValueError(f"monotone_constraints holds {len(p['monotone_constraints'])} entries, X {shape[1]} columns")
+        return _interaction_groups(p, shape[1]) if p["interaction_constraints"] else None
 
     def _set_is_cat(self, dev):
         self._is_cat = np.zeros(self.edges.shape[0], bool)
@@ -411,8 +512,52 @@ class GBDT:
         return grad, hess
 
     # ---- one boosting round
-    def _search(self, slot, out_row):
+    def _allowed(self, groups):
+        """The features a leaf of these active groups may split on, uint8 [F] (cached by the groups)."""
+        row = self._allowed_rows.get(groups)
+        if row is None:
+            row = np.zeros(self.F, np.uint8)
+            for g in groups:
+                row[list(self._groups[g])] = 1
+            self._allowed_rows[groups] = row
+        return row
+
+    def _cst_tables(self, cst, groups):
+        """The device tables of the leaves about to be searched: (cst float64 [k, 3] or None, allowed uint8 [k, F] or None), from the leaves'
+        (lo, hi, v) and active groups; one small host-to-device copy each, on the current stream."""
+        dev = self.scores.device
+        cst_d = None if self._mono is None else torch.from_numpy(np.ascontiguousarray(np.asarray(cst, np.float64).reshape(-1, 3))).to(dev)
+        allowed_d = None if self._groups is None else torch.from_numpy(np.stack([self._allowed(g) for g in groups])).to(dev)
+        return cst_d, allowed_d
+
+    def _child_cst(self, cst, f, lsum, rsum):
+        """(lo, hi, v) of the two children of a split on f (one node, or a level's nodes as arrays) from the parent's and the record's
+        integer sums: vL = clamp(-GL / (HL + l2), lo, hi), vR likewise, mid = (vL + vR) / 2 -> ([.., 3] left, [.., 3] right) float64."""
+        eg, eh = self._expo_host
+        cst, lsum, rsum = np.asarray(cst, np.float64), np.asarray(lsum, np.int64), np.asarray(rsum, np.int64)
+        lo, hi = cst[..., 0], cst[..., 1]
+        l2 = np.float64(self.params["lambda_l2"])
+        value = lambda sums: np.minimum(np.maximum(-np.ldexp(sums[..., 0].astype(np.float64), -eg) / (np.ldexp(sums[..., 1].astype(np.float64), -eh) + l2), lo), hi)
+        vl, vr = value(lsum), value(rsum)
+        mid = (vl + vr) / np.float64(2.0)
+        sign = self._mono[f]
+        left = np.stack([np.where(sign < 0, mid, lo), np.where(sign > 0, mid, hi), vl], axis=-1)
+        right = np.stack([np.where(sign > 0, mid, lo), np.where(sign < 0, mid, hi), vr], axis=-1)
+        return left, right
+
+    def _child_groups(self, groups, f):
+        """The active groups of a child of a split on f: the parent's that contain f."""
+        return tuple(g for g in groups if f in self._groups[g])
+
+    def _search(self, slot, out_row, tables=None):
         p = self.params
+        if tables is not None:                                             # monotone or interaction constraints: row 0 of the tables is this leaf's
+            cats = bool(p["categorical_feature"])
+            F.gbdt_best_split_cst(self._pool[slot:slot + 1], self._nbins_d, self._expo, self._mono_d, tables[0], tables[1],
+                                  self._is_cat_d if cats else None, p["cat_smooth"], p["lambda_l2"], p["min_data_in_leaf"], p["min_sum_hessian_in_leaf"],
+                                  p["min_gain_to_split"], out=self._rec[out_row:out_row + 1], sets=self._sets[out_row:out_row + 1] if cats else None,
+                                  nan_bin=self._nan_bin_d)
+            return
         if p["categorical_feature"]:
             F.gbdt_best_split_cat(self._pool[slot:slot + 1], self._nbins_d, self._expo, self._is_cat_d, p["cat_smooth"], p["lambda_l2"], p["min_data_in_leaf"],
                                   p["min_sum_hessian_in_leaf"], p["min_gain_to_split"], out=self._rec[out_row:out_row + 1],
@@ -447,21 +592,46 @@ class GBDT:
             F.gbdt_partition_mask(self._mask, out=self._rows, left_count=self._lc)
             torch.where(self._mask != 0, self._arange, self._none, out=self._tmp)
             F.gbdt_histogram(self.bins, self._qg, self._qh, self._tmp, nf, mb, hist=pool[0])
-        self._search(0, 0)
+        active = constraints(p)
+        self._search(0, 0, self._root_tables() if active else None)
         head = torch.cat([self._rec[0], pool[0, 0].sum(0), self._expo.to(torch.int64), self._flag.to(torch.int64)]
                          + ([self._sets[0]] if p["categorical_feature"] else [])).cpu().numpy()      # the root's left set rides in the same read
         self.host_reads += 1
         if head[14]:
             self._flag.zero_()
             raise FloatingPointError("the gradients or Hessians of this round hold a NaN or an infinity")
-        expo = (int(head[12]), int(head[13]))
+        expo = self._expo_host = (int(head[12]), int(head[13]))
+        self._leaf_v = None                                                # under monotone constraints: the leaves' clamped v, set by the grower
         bag = self.n if sampled is None else int(head[11])             # the root's row count: the size of the bag
         if sampled is None:
             self._rows.copy_(self._arange)
         grow = self._grow_depthwise if p["grow_policy"] == "depthwise" else self._grow_leafwise
         feature, threshold, left, right, starts, g_sum, h_sum, split_bin, go_left, cat_index, cat_sets = grow(head, bag)
-        value = np.array([leaf_value(g, h, expo, p["lambda_l2"], p["learning_rate"]) for g, h in zip(g_sum, h_sum)], np.float32)
+        if self._leaf_v is not None and len(g_sum) > 1:                   # a leaf stores float32(v * learning_rate) with its clamped v
+            value = np.array([np.float32(v * p["learning_rate"]) for v in self._leaf_v], np.float32)
+        else:
+            value = np.array([leaf_value(g, h, expo, p["lambda_l2"], p["learning_rate"]) for g, h in zip(g_sum, h_sum)], np.float32)
         return self._finish(feature, threshold, left, right, starts, value, bag, split_bin, go_left, cat_index, cat_sets)
+
+    def _root_tables(self):
+        """The root's tables.  Its sums are known on the device alone before the head read, so its v = -G / (H + lambda_l2) is computed
+        there, in float64 from the integer totals: no host read; lo = -inf, hi = +inf, every group active."""
+        cst_d = None
+        if self._mono is not None:
+            tot = self._pool[0, 0].sum(0)
+            scale = ((1023 - self._expo.to(torch.int64)) << 52).view(torch.float64)      # 2^-e, built from its bits: exact
+            G, H = tot[0].to(torch.float64) * scale[0], tot[1].to(torch.float64) * scale[1]
+            den = H + self.params["lambda_l2"]
+            v = torch.where(den > 0.0, -G / den, torch.zeros_like(den))
+            cst_d = torch.stack([torch.full_like(v, -np.inf), torch.full_like(v, np.inf), v]).reshape(1, 3)
+        allowed_d = None if self._groups is None else torch.from_numpy(self._allowed(tuple(range(len(self._groups))))[None]).to(self.scores.device)
+        return cst_d, allowed_d
+
+    def _root_cst(self, head):
+        """(lo, hi, v) of the root on the host, from the totals of the head read: what _root_tables computed on the device."""
+        G, H = np.ldexp(np.float64(int(head[9])), -self._expo_host[0]), np.ldexp(np.float64(int(head[10])), -self._expo_host[1])
+        den = H + np.float64(self.params["lambda_l2"])
+        return np.array([-np.inf, np.inf, -G / den if den > 0.0 else 0.0], np.float64)
 
     def _grow_leafwise(self, head, m):
         """Leaf-wise growth from the root's record (head, as update read it) over the first m entries of the row list: the leaf with the
@@ -470,7 +640,9 @@ class GBDT:
         p, nf, mb, pool = self.params, self.F, self.params["max_bin"], self._pool
         root_rec = _record(head[:9]) if self._splittable(m, 0) else _NO_SPLIT
         cats = bool(p["categorical_feature"])
-        leaves = [_Leaf(0, m, 0, 0, -1, 0, int(head[9]), int(head[10]), root_rec, head[15:19].copy() if cats else None)]
+        mono, inter = self._mono is not None, self._groups is not None
+        leaves = [_Leaf(0, m, 0, 0, -1, 0, int(head[9]), int(head[10]), root_rec, head[15:19].copy() if cats else None,
+                        self._root_cst(head) if mono else None, tuple(range(len(self._groups))) if inter else None)]
         feature, threshold, left, right, split_bin, go_left = [], [], [], [], [], []
         cat_index, cat_sets = ([], []) if cats else (None, None)
         missing = p["use_missing"]
@@ -504,6 +676,10 @@ class GBDT:
                 (left if leaf.side == 0 else right)[leaf.parent] = node
             lchild = _Leaf(s, lsum[2], leaf.depth + 1, leaf.slot, node, 0, lsum[0], lsum[1], _NO_SPLIT)
             rchild = _Leaf(s + lsum[2], rsum[2], leaf.depth + 1, leaf.slot, node, 1, rsum[0], rsum[1], _NO_SPLIT)
+            if mono:
+                lchild.cst, rchild.cst = self._child_cst(leaf.cst, f, lsum, rsum)
+            if inter:
+                lchild.groups = rchild.groups = self._child_groups(leaf.groups, f)
             leaves[li] = lchild
             leaves.append(rchild)
             can = [self._splittable(c.count, c.depth) for c in (lchild, rchild)]
@@ -513,15 +689,18 @@ class GBDT:
                 pool[small.slot].zero_()
                 F.gbdt_histogram(self.bins, self._qg, self._qh, self._rows[small.start:small.start + small.count], nf, mb, hist=pool[small.slot])
                 F.gbdt_hist_sub(pool[large.slot], pool[small.slot], out=pool[large.slot])          # the larger child, in the parent's slot
+                tables = self._cst_tables([lchild.cst, rchild.cst], [lchild.groups, rchild.groups]) if (mono or inter) else None
                 for k, c in enumerate((lchild, rchild)):
                     if can[k]:
-                        self._search(c.slot, k)
+                        self._search(c.slot, k, None if tables is None else tuple(None if t is None else t[k:k + 1] for t in tables))
                 recs = (torch.cat([self._rec, self._sets], dim=1) if cats else self._rec).cpu().numpy()      # the one synchronisation of this split
                 self.host_reads += 1
                 for k, c in enumerate((lchild, rchild)):
                     if can[k]:
                         c.rec = _record(recs[k, :9])
                         c.set = recs[k, 9:13].copy() if cats else None
+        if mono:
+            self._leaf_v = [float(c.cst[2]) for c in leaves]
         return (feature, threshold, left, right, [c.start for c in leaves], [c.g for c in leaves], [c.h for c in leaves], split_bin, go_left, cat_index,
                 cat_sets)
 
@@ -577,6 +756,12 @@ class GBDT:
         leaf, start, count, slot = np.zeros(1, np.int64), np.zeros(1, np.int64), np.full(1, m, np.int64), np.zeros(1, np.int64)
         parent, side = np.full(1, -1, np.int64), np.zeros(1, np.int64)
         rec = np.concatenate([head[:9], head[15:19]] if cats else [head[:9]]).astype(np.int64).reshape(1, ncol)
+        mono, inter = self._mono is not None, self._groups is not None
+        cst = self._root_cst(head).reshape(1, 3) if mono else None        # the frontier's (lo, hi, v) and active groups
+        groups = [tuple(range(len(self._groups)))] if inter else None
+        v_leaf = np.zeros(cap, np.float64)
+        if mono:
+            v_leaf[0] = cst[0, 2]
         while True:
             gain = rec[:, 0].copy().view(np.float64)
             keep = np.nonzero(self._splittable(count, depth) & (gain > -np.inf))[0]
@@ -613,6 +798,11 @@ class GBDT:
             c_start = np.stack([start[keep], start[keep] + lsum[:, 2]], axis=1)
             c_count = np.stack([lsum[:, 2], rsum[:, 2]], axis=1)
             starts[c_leaf], g_sum[c_leaf], h_sum[c_leaf] = c_start, np.stack([lsum[:, 0], rsum[:, 0]], axis=1), np.stack([lsum[:, 1], rsum[:, 1]], axis=1)
+            if mono:
+                c_cst = np.stack(self._child_cst(cst[keep], f, lsum, rsum), axis=1)          # [k, 2, 3]
+                v_leaf[c_leaf] = c_cst[:, :, 2]
+            if inter:
+                c_groups = [self._child_groups(groups[i], int(fi)) for i, fi in zip(keep, f)]
             nodes, leaves, depth = nodes + k, leaves + k, depth + 1
             can = self._splittable(c_count, depth)
             c_slot = np.repeat(slot[keep][:, None], 2, axis=1)
@@ -630,7 +820,15 @@ class GBDT:
                 F.gbdt_hist_sub_segments(pool, np.stack([slot[keep][pairs], fresh, slot[keep][pairs]], axis=1))   # the larger child, in the parent's slot
                 sp, ss = np.nonzero(can[pairs])
                 out = self._lrec[:sp.size]
-                if cats:
+                if mono or inter:
+                    cst_d, allowed_d = self._cst_tables(c_cst[pairs[sp], ss] if mono else None, [c_groups[i] for i in pairs[sp]] if inter else None)
+                    F.gbdt_best_split_slots_cst(pool, c_slot[pairs[sp], ss], self._nbins_d, self._expo, self._mono_d, cst_d, allowed_d,
+                                                self._is_cat_d if cats else None, p["cat_smooth"], p["lambda_l2"], p["min_data_in_leaf"],
+                                                p["min_sum_hessian_in_leaf"], p["min_gain_to_split"], out=out, sets=self._lsets[:sp.size] if cats else None,
+                                                nan_bin=self._nan_bin_d)
+                    if cats:
+                        out = torch.cat([out, self._lsets[:sp.size]], dim=1)
+                elif cats:
                     F.gbdt_best_split_slots_cat(pool, c_slot[pairs[sp], ss], self._nbins_d, self._expo, self._is_cat_d, p["cat_smooth"], p["lambda_l2"],
                                                 p["min_data_in_leaf"], p["min_sum_hessian_in_leaf"], p["min_gain_to_split"], out=out,
                                                 sets=self._lsets[:sp.size], nan_bin=self._nan_bin_d)
@@ -642,6 +840,12 @@ class GBDT:
                 self.host_reads += 1
             leaf, start, count, slot = c_leaf.reshape(-1), c_start.reshape(-1), c_count.reshape(-1), c_slot.reshape(-1)
             parent, side, rec = np.repeat(node, 2), np.tile(np.array([0, 1], np.int64), k), c_rec.reshape(-1, ncol)
+            if mono:
+                cst = c_cst.reshape(-1, 3)
+            if inter:
+                groups = [g for g in c_groups for _ in (0, 1)]
+        if mono:
+            self._leaf_v = v_leaf[:leaves].tolist()
         return (feature[:nodes], threshold[:nodes], left[:nodes], right[:nodes], starts[:leaves].tolist(), g_sum[:leaves].tolist(), h_sum[:leaves].tolist(),
                 split_bin[:nodes], go_left[:nodes], cat_index[:nodes] if cats else None, cat_sets)
 
@@ -720,17 +924,18 @@ class GBDT:
         without use_missing (the file this method wrote before the switch existed: neither the switch nor the categorical keys are among its
         parameters); format 2 under it, with default_left per node and nan_bin per feature; format 3 with categorical features: format 1
         or 2 (by use_missing, with every parameter) plus categorical_feature, cat_index per node and cat_sets."""
+        own = self.params if constraints(self.params) else {k: v for k, v in self.params.items() if k not in CST_KEYS}      # inactive: today's file
         if self.params["categorical_feature"]:
-            head = dict(format=np.int64(MODEL_FORMAT_CAT), params=np.array(json.dumps(self.params)), edges=self.edges, nbins=self.nbins,
+            head = dict(format=np.int64(MODEL_FORMAT_CAT), params=np.array(json.dumps(own)), edges=self.edges, nbins=self.nbins,
                         categorical_feature=np.array(self.params["categorical_feature"], np.int32))
             if self.params["use_missing"]:
                 head["nan_bin"] = np.full(0, -1, np.int32) if self.nan_bin is None else self.nan_bin
         elif self.params["use_missing"]:
-            params = {k: v for k, v in self.params.items() if k not in CAT_KEYS}
+            params = {k: v for k, v in own.items() if k not in CAT_KEYS}
             head = dict(format=np.int64(MODEL_FORMAT_MISSING), params=np.array(json.dumps(params)), edges=self.edges, nbins=self.nbins,
                         nan_bin=np.full(0, -1, np.int32) if self.nan_bin is None else self.nan_bin)
         else:
-            params = {k: v for k, v in self.params.items() if k != "use_missing" and k not in CAT_KEYS}
+            params = {k: v for k, v in own.items() if k != "use_missing" and k not in CAT_KEYS}
             head = dict(format=np.int64(MODEL_FORMAT), params=np.array(json.dumps(params)), edges=self.edges, nbins=self.nbins)
         with open(path, "wb") as fh:
             np.savez(fh, **head, best_iteration=np.int64(self.best_iteration or 0), **self.flat())
