@@ -1284,6 +1284,79 @@ int ptr_gbdt_best_split_slots_cst(const int64_t *pool, int nslots, const int32_t
                                   int64_t *ws, int64_t *rec, int64_t *sets, const int8_t *mono, const double *cst, const uint8_t *allowed,
                                   void *stream);
 
+/* ---- TreeSHAP feature contributions (csrc/gbdt.hip; GBDT.predict(pred_contrib=True), GBDT.set_background of ptranking_amd/gbdt.py).
+ * ADDITIVE to ABI v8 too; every symbol above keeps its signature and its results bit for bit.  tests/gbdt_shap_ref.py restates the rule.
+ *
+ * The rule: path-dependent TreeSHAP (Lundberg, Erion, Lee 2018, Algorithm 2) in its per-leaf closed form.  Take a tree, a leaf l with fp32
+ * value v_l, and the set U of DISTINCT features on its root-to-leaf path, d = |U|.  For each k in U:
+ *   the zero fraction z_k = the product, over the path's nodes that split on k in path order, of cover(child taken) / cover(node);
+ *   the one fraction o_k(x), 0 or 1 = 1 iff row x goes the path's way at every node that splits on k.
+ * "Goes the path's way" is the predicate of ptr_gbdt_predict / _missing / _cat on the raw row (x <= threshold, a NaN along default_left, set
+ * membership), so a row's o's are all 1 at exactly the leaf predict reaches.  Then
+ *   phi_k(x) += v_l (o_k - z_k) sum over S in U \ {k} of |S|! (d - |S| - 1)! / d!  prod_{j in S} o_j  prod_{j not in S, j != k} z_j
+ *   phi_F(x) += v_l prod_{k in U} z_k                      (the expected value: the last column)
+ * summed in float64 over the leaves in table order (tree order, then leaf order).  The covers are the rows of a BACKGROUND matrix: a tree
+ * and the model files keep no counts.  ptr_gbdt_leaf_counts counts the rows per leaf and the host sums them into node covers.
+ *
+ * How the sum over S is formed.  |S|! (d - |S| - 1)! / d! is the integral over t in [0, 1] of t^|S| (1 - t)^(d - 1 - |S|), so the sum is the
+ * integral of prod_{j in U, j != k} (z_j (1 - t) + o_j t), a polynomial of degree d - 1 with positive factors, and the Gauss-Legendre rule of
+ * Q = ceil(d / 2) nodes on [0, 1] integrates it exactly.  Nothing cancels, whatever d.  The rules of Q = 1 .. 32 nodes are a table the
+ * caller hands in: quad_t, quad_w [528] float64, the rule of Q nodes at Q (Q - 1) / 2 (GBDT builds it with numpy's leggauss).
+ *
+ * The order of operations (float64, every operation rounded, nothing contracted).  With the elements e = 0 .. d - 1 in table order and
+ * the nodes (t_q, w_q), q = 0 .. Q - 1:
+ *   P_q = 1, pz = 1;  for j = 0 .. d - 1:  P_q <- P_q * ((z_j * (1 - t_q)) + (o_j ? t_q : 0));  pz <- pz * z_j
+ *   sum_e = 0;  for q = 0 .. Q - 1:  sum_e <- sum_e + w_q * (P_q / ((z_e * (1 - t_q)) + (o_e ? t_q : 0)))
+ *   phi[feature of e] <- phi[feature of e] + ((sum_e * (o_e - z_e)) * v);   phi[F] <- phi[F] + v * pz.
+ *
+ * The path tables, one row per leaf, built on the host once per model and background (nleaves leaves, npath path nodes, nelem elements):
+ *   path_offsets [nleaves + 1] int32: leaf l owns the entries path_offsets[l] .. path_offsets[l + 1] of
+ *     path_node [npath] int32: the node, an index over the nodes of ALL trees (into feature / threshold / default_left / cat_index), root first;
+ *     path_dir  [npath] uint8: 1 where the path goes left there;
+ *     path_elem [npath] uint8: which of the leaf's elements the node's feature is;
+ *   elem_offsets [nleaves + 1] int32: leaf l owns the entries elem_offsets[l] .. elem_offsets[l + 1] (at most 63: one lane each, and the
+ *     rules of up to 32 nodes; depth itself is unbounded, a feature used five times is one element) of
+ *     elem_feature [nelem] int32, in the order of first use on the path, and elem_z [nelem] float64;
+ *   leaf_value [nleaves] float32.
+ * A sub-range of leaves is served by offsetting path_offsets, elem_offsets and leaf_value alone: their entries are absolute.
+ *
+ * ptr_gbdt_leaf_counts (_missing: default_left per node; _cat: the tables of ptr_gbdt_predict_cat): counts [nleaves] int64, nleaves =
+ *   nodes + ntrees in the layout of the leaf values, is zeroed and then holds the rows of X [n, F] per leaf: one launch over all trees,
+ *   one 64-bit integer atomic per (row, tree).  A row a malformed tree loses counts nowhere; the node arrays hold `nodes` entries and may be
+ *   NULL where nodes == 0 (leaf-only trees).
+ * ptr_gbdt_shap (_missing, _cat likewise, one kernel body): phi [n, F + 1] float64, every entry written.  One wavefront owns a row for
+ *   the whole table and keeps its F + 1 sums in LDS: no float atomic, and a row's bits depend on the row and the tables alone, not on n,
+ *   its place or the grid.  F above 8000: PTR_ERR_UNSUPPORTED.  The tables are read as untrusted: an offset, node, feature or element index
+ *   out of range, or a leaf of more than 63 elements, makes the row's phi NaN, never an access out of range.  Everything else is
+ *   validated before any launch (PTR_ERR_INVALID_ARG: a negative size, a NULL pointer a launch would touch). */
+int ptr_gbdt_leaf_counts(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                         const int32_t *right, const int32_t *tree_offsets, int ntrees, int64_t nodes, int64_t nleaves, int64_t *counts,
+                         void *stream);
+int ptr_gbdt_leaf_counts_missing(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                 const int32_t *right, const int32_t *tree_offsets, const uint8_t *default_left, int ntrees,
+                                 int64_t nodes, int64_t nleaves, int64_t *counts, void *stream);
+int ptr_gbdt_leaf_counts_cat(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                             const int32_t *right, const int32_t *tree_offsets, const uint8_t *default_left, const uint8_t *is_cat,
+                             const int32_t *cat_index, const int64_t *cat_sets, int ncat, int ntrees, int64_t nodes, int64_t nleaves,
+                             int64_t *counts, void *stream);
+int ptr_gbdt_shap(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, int64_t nodes,
+                  const int32_t *path_offsets, const int32_t *elem_offsets, const float *leaf_value, int64_t nleaves,
+                  const int32_t *path_node, const uint8_t *path_dir, const uint8_t *path_elem, int64_t npath,
+                  const int32_t *elem_feature, const double *elem_z, int64_t nelem, const double *quad_t, const double *quad_w,
+        double *phi, void *stream);
+int ptr_gbdt_shap_missing(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, int64_t nodes,
+                          const int32_t *path_offsets, const int32_t *elem_offsets, const float *leaf_value, int64_t nleaves,
+                          const int32_t *path_node, const uint8_t *path_dir, const uint8_t *path_elem, int64_t npath,
+                          const int32_t *elem_feature, const double *elem_z, int64_t nelem, const double *quad_t, const double *quad_w,
+        const uint8_t *default_left, double *phi,
+                          void *stream);
+int ptr_gbdt_shap_cat(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, int64_t nodes,
+                      const int32_t *path_offsets, const int32_t *elem_offsets, const float *leaf_value, int64_t nleaves,
+                      const int32_t *path_node, const uint8_t *path_dir, const uint8_t *path_elem, int64_t npath,
+                      const int32_t *elem_feature, const double *elem_z, int64_t nelem, const double *quad_t, const double *quad_w,
+        const uint8_t *default_left,
+                      const uint8_t *is_cat, const int32_t *cat_index, const int64_t *cat_sets, int ncat, double *phi, void *stream);
+
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):
  *   "<label> qid:<id> <fid>:<val> ... [# comment]", feature ids one-indexed unless one_indexed == 0 (Yahoo! sets,

@@ -133,6 +133,15 @@ SIGNATURES = {
     "ptr_gbdt_partition_segments_cat": [_vp, _i, C.c_int64, _i, _vp, C.c_int64, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, C.c_int64, _vp],
     "ptr_gbdt_add_tree_binned_cat": [_vp, _vp, _i, C.c_int64, _i, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "ptr_gbdt_predict_cat": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "ptr_gbdt_leaf_counts": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _vp],
+    "ptr_gbdt_leaf_counts_missing": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, C.c_int64, _vp, _vp],
+    "ptr_gbdt_leaf_counts_cat": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int64, C.c_int64, _vp, _vp],
+    "ptr_gbdt_shap": [_vp, C.c_int64, _i, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, _vp,
+                      _vp],
+    "ptr_gbdt_shap_missing": [_vp, C.c_int64, _i, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp,
+                              _vp, _vp, _vp, _vp],
+    "ptr_gbdt_shap_cat": [_vp, C.c_int64, _i, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp,
+                          _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
     "ptr_letor_scan":[C.c_char_p, _i, _vp, _vp, _vp],
     "ptr_letor_load": [C.c_char_p, _i, _f, C.c_int64, C.c_int32, C.c_int64, _vp, _i, _vp, _vp, _vp],
 }

@@ -831,6 +831,23 @@ __device__ __forceinline__ int gbdt_cat_node(const GbdtCatWalk &c, int node, int
 }
 __device__ __forceinline__ bool gbdt_in_set(const int64_t *__restrict__ set, int b) { return (((u64)set[b >> 6]) >> (b & 63)) & 1ull; }     // b in 0 .. 255
 
+// How a raw value decides at node `at` (an index over the nodes of ALL trees) that splits on feature f: the one predicate of every walk over
+// raw rows (prediction, the leaf counts and the one fractions of TreeSHAP).  bad: a malformed categorical table.
+template <bool kCat> __device__ __forceinline__ bool gbdt_raw_goes_left(float xv, int at, int f, const float *__restrict__ threshold,
+                                                                        const uint8_t *__restrict__ default_left, const GbdtCatWalk &cat, bool &bad) {
+    if constexpr (kCat) {
+        const int ci = gbdt_cat_node(cat, at, f);
+        if (ci == -2) { bad = true; return false; }
+        if (ci >= 0) {                                                  // a NaN follows the node's direction; what is no code 0 .. 255 is in no set
+            if (xv != xv) return default_left && default_left[at] != 0;
+            if (!(xv >= 0.0f && xv <= 255.0f)) return false;
+            const int c = (int)xv;
+            return (float)c == xv && gbdt_in_set(cat.cat_sets + (int64_t)ci * kSetWords, c);
+        }
+    }
+    return (default_left && xv != xv) ? default_left[at] != 0 : xv <= threshold[at];       // a NaN follows the node's direction
+}
+
 template <bool kCat> __global__ void __launch_bounds__(kBlock)
 gbdt_predict_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t *__restrict__ feature, const float *__restrict__ threshold,
                     const int32_t *__restrict__ left, const int32_t *__restrict__ right, const float *__restrict__ value,
@@ -843,23 +860,119 @@ gbdt_predict_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t
     for (int t = 0; t < ntrees; ++t) {
         const int base = tree_offsets[t], nn = tree_offsets[t + 1] - base, leaves = base + t;      // a tree of nn nodes has nn + 1 leaves
         bool bad = false;
-        const int node = gbdt_walk(nn, F, feature + base, left + base, right + base, [&](int at, int f) {
-            const float xv = x[f];
-            if constexpr (kCat) {
-                const int ci = gbdt_cat_node(cat, base + at, f);
-                if (ci == -2) { bad = true; return false; }
-                if (ci >= 0) {                                          // a NaN follows the node's direction; what is no code 0 .. 255 is in no set
-                    if (xv != xv) return default_left && default_left[base + at] != 0;
-                    if (!(xv >= 0.0f && xv <= 255.0f)) return false;
-                    const int c = (int)xv;
-                    return (float)c == xv && gbdt_in_set(cat.cat_sets + (int64_t)ci * kSetWords, c);
-                }
-            }
-            return (default_left && xv != xv) ? default_left[base + at] != 0 : xv <= threshold[base + at];   // a NaN follows the node's direction
-        });
+        const int node = gbdt_walk(nn, F, feature + base, left + base, right + base,
+                                   [&](int at, int f) { return gbdt_raw_goes_left<kCat>(x[f], base + at, f, threshold, default_left, cat, bad); });
         s += gbdt_is_leaf(node, nn) && !bad ? value[leaves + ~node] : NAN;      // a malformed tree gives NaN
     }
     out[i] = s;
+}
+
+// The rows of a background matrix per LEAF of every tree (the covers of TreeSHAP): the walk of gbdt_predict_kernel, one integer atomic per
+// (row, tree).  counts [nodes + ntrees] int64 in the layout of the leaf values.  A row a malformed tree loses counts nowhere.  The node arrays
+// may be NULL where nodes == 0 (leaf-only trees).
+template <bool kCat> __global__ void __launch_bounds__(kBlock)
+gbdt_leaf_counts_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t *__restrict__ feature, const float *__restrict__ threshold,
+                        const int32_t *__restrict__ left, const int32_t *__restrict__ right, const int32_t *__restrict__ tree_offsets,
+                        const uint8_t *__restrict__ default_left, int ntrees, int64_t nodes, int64_t nleaves, int64_t *__restrict__ counts, const GbdtCatWalk cat) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float *x = X + i * F;
+    for (int t = 0; t < ntrees; ++t) {
+        const int base = tree_offsets[t], nn = tree_offsets[t + 1] - base;
+        if (base < 0 || nn < 0 || (int64_t)base + nn > nodes) continue;   // a tree outside the node arrays (a tree of no node reads none of them)
+        bool bad = false;
+        const int node = gbdt_walk(nn, F, feature + base, left + base, right + base,
+                                   [&](int at, int f) { return gbdt_raw_goes_left<kCat>(x[f], base + at, f, threshold, default_left, cat, bad); });
+        const int64_t cell = (int64_t)base + t + ~node;
+        if (gbdt_is_leaf(node, nn) && !bad && cell >= 0 && cell < nleaves) atomicAdd(reinterpret_cast<u64 *>(counts + cell), 1ull);
+    }
+}
+
+// ---------------------------------------------------------------- TreeSHAP
+// Path-dependent TreeSHAP in its per-leaf form (include/ptranking_amd.h states the rule, tests/gbdt_shap_ref.py restates it operation by
+// operation).  A workgroup is ONE wavefront and owns a row: it walks the leaf table in order and keeps the row's [F + 1] float64 sums in
+// LDS, so a row's bits depend on the row and the tables alone.  Per leaf: lane p evaluates the path's node p (the predicate of
+// gbdt_raw_goes_left against the node's direction bit) and a disagreement marks the node's element in LDS; lane e then holds element e's
+// (z, o).  The sum over subsets is a Gauss-Legendre quadrature (below): lane q multiplies the path's factors up at node t_q, one broadcast of
+// z per element, then lane e divides its own factor out of every P(t_q), read by broadcast, and adds v (o - z) sum to its feature's
+// cell; the elements of a path carry distinct features, so the adds need no atomic.  (Lundberg's EXTEND / UNWIND recurrences, one
+// subset-size weight per lane with a neighbour exchange per step, were built first and are bit-equal to their numpy restatement, but
+// UNWIND is a polynomial deflation: on a chain of 63 features it lost local accuracy down to 8e-4.  The quadrature holds 2e-15 there.)
+constexpr int kShapWave = 64;            // lanes: the elements of a path, kShapWave - 1 at the most (the rules of up to 32 nodes are exact for them)
+constexpr int kShapMaxGroups = 8192;     // workgroups of a launch at the most (256 compute units x 32 wavefronts); the rows beyond stride
+constexpr int kShapQuad = 528;           // the Gauss-Legendre rules of 1 .. 32 nodes on [0, 1], one after the other
+constexpr int kShapMaxF = 8000;          // (F + 1) float64 of LDS per wavefront: 64 KiB less the element marks
+
+struct GbdtShapTables {
+    const int32_t *path_offsets, *elem_offsets; const float *leaf_value; int64_t nleaves;
+    const int32_t *path_node; const uint8_t *path_dir, *path_elem; int64_t npath;
+    const int32_t *elem_feature; const double *elem_z; int64_t nelem;
+    const double *quad_t, *quad_w;       // kShapQuad nodes and weights: the rule of Q nodes at Q (Q - 1) / 2
+};
+
+template <bool kCat> __global__ void __launch_bounds__(kShapWave)
+gbdt_shap_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t *__restrict__ feature, const float *__restrict__ threshold,
+                 int64_t nodes, const uint8_t *__restrict__ default_left, const GbdtCatWalk cat, const GbdtShapTables tb, double *__restrict__ phi) {
+    extern __shared__ double shap_acc[];                                 // [F + 1] sums, then kShapWave marks
+    uint32_t *marks = reinterpret_cast<uint32_t *>(shap_acc + F + 1);
+    const int lane = threadIdx.x;
+    marks[lane] = 0;
+    for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
+        const float *x = X + row * F;
+        for (int k = lane; k <= F; k += kShapWave) shap_acc[k] = 0.0;
+        bool bad = false;
+        for (int64_t l = 0; l < tb.nleaves; ++l) {
+            const int p0 = tb.path_offsets[l], p1 = tb.path_offsets[l + 1], e0 = tb.elem_offsets[l], e1 = tb.elem_offsets[l + 1];
+            const int d = e1 - e0;
+            if (p0 < 0 || p1 < p0 || p1 > tb.npath || e0 < 0 || d < 0 || e1 > tb.nelem || d >= kShapWave) { bad = true; continue; }    // wave-uniform
+            __syncthreads();                                            // the marks are clear and the sums of the leaf before are written
+            for (int p = p0 + lane; p < p1; p += kShapWave) {
+                const int at = tb.path_node[p], e = tb.path_elem[p];
+                if (at < 0 || at >= nodes || e >= d) { bad = true; continue; }
+                const int f = feature[at];
+                if (f < 0 || f >= F) { bad = true; continue; }
+                if (gbdt_raw_goes_left<kCat>(x[f], at, f, threshold, default_left, cat, bad) != (tb.path_dir[p] != 0)) marks[e] = 1;
+            }
+            __syncthreads();
+            double z = 1.0;
+            bool o = false;
+            int f = F;
+            if (lane < d) {
+                o = marks[lane] == 0;
+                marks[lane] = 0;
+                z = tb.elem_z[e0 + lane];
+                f = tb.elem_feature[e0 + lane];
+                if (f < 0 || f >= F) { bad = true; f = F; }
+            }
+            const u64 ones = __ballot(o);
+            // The Shapley weight of a subset size is a Beta integral, so element k's sum over subsets is the integral over t in [0, 1] of
+            // prod_{j != k} (z_j (1 - t) + o_j t): a polynomial of degree d - 1, which the Gauss-Legendre rule of Q = ceil(d / 2) nodes
+            // integrates exactly.  Every factor and weight is positive: nothing cancels, at 63 elements as at 3.
+            const int Q = (d + 1) >> 1, rule = Q * (Q - 1) / 2;
+            // lane q: P(t_q) = prod_j (z_j (1 - t_q) + o_j t_q) in element order, one broadcast of z per element (o comes from the ballot)
+            const double t = lane < Q ? tb.quad_t[rule + lane] : 0.5, u = 1.0 - t;
+            double P = 1.0, pz = 1.0;
+            for (int j = 0; j < d; ++j) {
+                const double zj = __shfl(z, j, kShapWave);
+                P = P * (zj * u + (((ones >> j) & 1ull) ? t : 0.0));
+                pz = pz * zj;
+            }
+            // lane e: sum_q w_q P(t_q) / (z_e (1 - t_q) + o_e t_q), its own factor divided out again
+            double sum = 0.0;
+            for (int q = 0; q < Q; ++q) {
+                const double tq = tb.quad_t[rule + q], wq = tb.quad_w[rule + q];
+                const double mine = z * (1.0 - tq) + (o ? tq : 0.0);
+                sum = sum + wq * (__shfl(P, q, kShapWave) / mine);
+            }
+            const double v = (double)tb.leaf_value[l];
+            if (lane < d) shap_acc[f] = shap_acc[f] + sum * ((o ? 1.0 : 0.0) - z) * v;
+            if (lane == 0) shap_acc[F] = shap_acc[F] + v * pz;
+        }
+        __syncthreads();
+        const bool nan = __ballot(bad) != 0;
+        for (int k = lane; k <= F; k += kShapWave) phi[row * (F + 1) + k] = nan ? (double)NAN : shap_acc[k];
+        __syncthreads();
+    }
 }
 
 // One finished tree over the BINNED rows of a row list: x <= edges[f][b] is bin <= b, so the walk lands in the leaf ptr_gbdt_predict finds on
@@ -1292,6 +1405,125 @@ extern "C" int ptr_gbdt_predict_missing(const float *X, int64_t n, int F, const 
                                         float *out, void *stream) {
     return gbdt_predict_impl("ptr_gbdt_predict_missing", X, n, F, feature, threshold, left, right, value, tree_offsets, default_left, true, ntrees, out,
                              stream);
+}
+
+// ---------------------------------------------------------------- the entry points of TreeSHAP
+static int gbdt_leaf_counts_impl(const char *who, const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                 const int32_t *right, const int32_t *tree_offsets, const uint8_t *default_left, bool missing, int ntrees, int64_t nodes,
+                                 int64_t nleaves, int64_t *counts, void *stream, bool cat_on = false, GbdtCatWalk cat = {nullptr, nullptr, nullptr, 0}) {
+    if (n < 0 || F < 0 || ntrees < 0 || nodes < 0 || nleaves < 0) {
+        set_error("%s: negative size (n=%lld, F=%d, ntrees=%d, nodes=%lld, nleaves=%lld)", who, (long long)n, F, ntrees, (long long)nodes,
+                  (long long)nleaves);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (nleaves == 0) return 0;
+    if (!counts) { set_error("%s: NULL pointer (counts)", who); return PTR_ERR_INVALID_ARG; }
+    const bool walk = n > 0 && ntrees > 0;
+    if (walk && F > 0 && !X) { set_error("%s: NULL pointer (X)", who); return PTR_ERR_INVALID_ARG; }
+    if (walk && (!tree_offsets || (nodes > 0 && (!feature || !threshold || !left || !right || (missing && !default_left))))) {
+        set_error("%s: NULL tree array", who);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (int rc = check_hip(hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)nleaves, as_stream(stream)), who)) return rc;
+    if (!walk) return 0;
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+    if (cat_on)
+        hipLaunchKernelGGL(gbdt_leaf_counts_kernel<true>, grid, dim3(kBlock), 0, as_stream(stream), X, n, F, feature, threshold, left, right, tree_offsets,
+                           default_left, ntrees, nodes, nleaves, counts, cat);
+    else
+        hipLaunchKernelGGL(gbdt_leaf_counts_kernel<false>, grid, dim3(kBlock), 0, as_stream(stream), X, n, F, feature, threshold, left, right, tree_offsets,
+                           default_left, ntrees, nodes, nleaves, counts, cat);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_leaf_counts(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                    const int32_t *right, const int32_t *tree_offsets, int ntrees, int64_t nodes, int64_t nleaves, int64_t *counts,
+                                    void *stream) {
+    return gbdt_leaf_counts_impl("ptr_gbdt_leaf_counts", X, n, F, feature, threshold, left, right, tree_offsets, nullptr, false, ntrees, nodes, nleaves, counts,
+                                 stream);
+}
+
+extern "C" int ptr_gbdt_leaf_counts_missing(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                            const int32_t *right, const int32_t *tree_offsets, const uint8_t *default_left, int ntrees,
+                                            int64_t nodes, int64_t nleaves, int64_t *counts, void *stream) {
+    return gbdt_leaf_counts_impl("ptr_gbdt_leaf_counts_missing", X, n, F, feature, threshold, left, right, tree_offsets, default_left, true, ntrees,
+                                 nodes, nleaves, counts, stream);
+}
+
+extern "C" int ptr_gbdt_leaf_counts_cat(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                        const int32_t *right, const int32_t *tree_offsets, const uint8_t *default_left, const uint8_t *is_cat,
+                                        const int32_t *cat_index, const int64_t *cat_sets, int ncat, int ntrees, int64_t nodes, int64_t nleaves,
+                                        int64_t *counts, void *stream) {
+    const char *who = "ptr_gbdt_leaf_counts_cat";
+    const GbdtCatWalk cat{is_cat, cat_index, cat_sets, ncat};
+    if (int rc = check_cat_walk(cat, n > 0 && ntrees > 0 && nleaves > 0 && nodes > 0, F, who)) return rc;
+    return gbdt_leaf_counts_impl(who, X, n, F, feature, threshold, left, right, tree_offsets, default_left, false, ntrees, nodes, nleaves, counts, stream, true,
+                                 cat);
+}
+
+static int gbdt_shap_impl(const char *who, const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, int64_t nodes,
+                          const GbdtShapTables &tb, const uint8_t *default_left, bool missing, double *phi, void *stream, bool cat_on = false,
+                          GbdtCatWalk cat = {nullptr, nullptr, nullptr, 0}) {
+    if (n < 0 || F < 0 || nodes < 0 || tb.nleaves < 0 || tb.npath < 0 || tb.nelem < 0) {
+        set_error("%s: negative size (n=%lld, F=%d, nodes=%lld, nleaves=%lld, npath=%lld, nelem=%lld)", who, (long long)n, F, (long long)nodes,
+                  (long long)tb.nleaves, (long long)tb.npath, (long long)tb.nelem);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (nodes > INT32_MAX || tb.npath > INT32_MAX || tb.nelem > INT32_MAX) {
+        set_error("%s: nodes, npath and nelem must fit an int32 index", who);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (F > kShapMaxF) { set_error("%s: F=%d, at most %d (a row's sums live in LDS)", who, F, kShapMaxF); return PTR_ERR_UNSUPPORTED; }
+    if (n == 0) return 0;
+    if (!phi || (F > 0 && !X)) { set_error("%s: NULL pointer (X or phi)", who); return PTR_ERR_INVALID_ARG; }
+    if (tb.nleaves > 0 && (!tb.path_offsets || !tb.elem_offsets || !tb.leaf_value)) { set_error("%s: NULL leaf table", who); return PTR_ERR_INVALID_ARG; }
+    if (tb.npath > 0 && (!tb.path_node || !tb.path_dir || !tb.path_elem || !feature || !threshold || (missing && !default_left))) {
+        set_error("%s: NULL path table or tree array", who);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (tb.nelem > 0 && (!tb.elem_feature || !tb.elem_z || !tb.quad_t || !tb.quad_w)) {
+        set_error("%s: NULL element table or quadrature table", who);
+        return PTR_ERR_INVALID_ARG;
+    }
+    const dim3 grid((unsigned)(n < kShapMaxGroups ? n : kShapMaxGroups));
+    const size_t lds = sizeof(double) * (size_t)(F + 1) + sizeof(uint32_t) * kShapWave;
+    if (cat_on)
+        hipLaunchKernelGGL(gbdt_shap_kernel<true>, grid, dim3(kShapWave), lds, as_stream(stream), X, n, F, feature, threshold, nodes, default_left, cat, tb, phi);
+    else
+        hipLaunchKernelGGL(gbdt_shap_kernel<false>, grid, dim3(kShapWave), lds, as_stream(stream), X, n, F, feature, threshold, nodes, default_left, cat, tb, phi);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_shap(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, int64_t nodes,
+                             const int32_t *path_offsets, const int32_t *elem_offsets, const float *leaf_value, int64_t nleaves,
+                             const int32_t *path_node, const uint8_t *path_dir, const uint8_t *path_elem, int64_t npath,
+                             const int32_t *elem_feature, const double *elem_z, int64_t nelem, const double *quad_t, const double *quad_w,
+        double *phi, void *stream) {
+    const GbdtShapTables tb{path_offsets, elem_offsets, leaf_value, nleaves, path_node, path_dir, path_elem, npath, elem_feature, elem_z, nelem, quad_t, quad_w};
+    return gbdt_shap_impl("ptr_gbdt_shap", X, n, F, feature, threshold, nodes, tb, nullptr, false, phi, stream);
+}
+
+extern "C" int ptr_gbdt_shap_missing(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, int64_t nodes,
+                                     const int32_t *path_offsets, const int32_t *elem_offsets, const float *leaf_value, int64_t nleaves,
+                                     const int32_t *path_node, const uint8_t *path_dir, const uint8_t *path_elem, int64_t npath,
+                                     const int32_t *elem_feature, const double *elem_z, int64_t nelem, const double *quad_t, const double *quad_w,
+        const uint8_t *default_left, double *phi,
+                                     void *stream) {
+    const GbdtShapTables tb{path_offsets, elem_offsets, leaf_value, nleaves, path_node, path_dir, path_elem, npath, elem_feature, elem_z, nelem, quad_t, quad_w};
+    return gbdt_shap_impl("ptr_gbdt_shap_missing", X, n, F, feature, threshold, nodes, tb, default_left, true, phi, stream);
+}
+
+extern "C" int ptr_gbdt_shap_cat(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, int64_t nodes,
+                                 const int32_t *path_offsets, const int32_t *elem_offsets, const float *leaf_value, int64_t nleaves,
+                                 const int32_t *path_node, const uint8_t *path_dir, const uint8_t *path_elem, int64_t npath,
+                                 const int32_t *elem_feature, const double *elem_z, int64_t nelem, const double *quad_t, const double *quad_w,
+        const uint8_t *default_left,
+                                 const uint8_t *is_cat, const int32_t *cat_index, const int64_t *cat_sets, int ncat, double *phi, void *stream) {
+    const char *who = "ptr_gbdt_shap_cat";
+    const GbdtShapTables tb{path_offsets, elem_offsets, leaf_value, nleaves, path_node, path_dir, path_elem, npath, elem_feature, elem_z, nelem, quad_t, quad_w};
+    const GbdtCatWalk cat{is_cat, cat_index, cat_sets, ncat};
+    if (int rc = check_cat_walk(cat, n > 0 && npath > 0, F, who)) return rc;
+    return gbdt_shap_impl(who, X, n, F, feature, threshold, nodes, tb, default_left, false, phi, stream, true, cat);
 }
 
 // ---------------------------------------------------------------- the entry points of row sampling

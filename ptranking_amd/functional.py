@@ -25,7 +25,8 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "gbdt_histogram_segments", "gbdt_hist_sub_segments", "gbdt_best_split_slots", "gbdt_partition_segments", "gbdt_segment_items",
            "gbdt_bag_mask", "gbdt_goss", "gbdt_partition_mask", "gbdt_add_tree_binned",
            "gbdt_best_split_cat", "gbdt_best_split_slots_cat", "gbdt_partition_cat", "gbdt_partition_segments_cat", "gbdt_add_tree_binned_cat",
-           "gbdt_predict_cat", "gbdt_best_split_cst", "gbdt_best_split_slots_cst", "GBDT_MAX_BIN", "GBDT_RECORD"]
+           "gbdt_predict_cat", "gbdt_best_split_cst", "gbdt_best_split_slots_cst", "gbdt_leaf_counts", "gbdt_shap", "SHAP_TABLE_KEYS", "GBDT_MAX_BIN",
+           "GBDT_RECORD"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
 # launch table, and it draws its own; irfgan_loss and adlist_loss are public too: they take a mode, as irgan_selected does)
@@ -1662,3 +1663,90 @@ def gbdt_predict_cat(X, feature, threshold, left, right, value, tree_offsets, is
                   _lib.ptr(value), _lib.ptr(tree_offsets), _lib.ptr(default_left), _lib.ptr(is_cat), _lib.ptr(cat_index), _lib.ptr(cat_sets),
                   cat_sets.shape[0], ntrees, _lib.ptr(out), _lib.current_stream(dev))
     return out
+
+
+# ---- TreeSHAP feature contributions (include/ptranking_amd.h states the rule and the layout of the path tables)
+SHAP_TABLE_KEYS = ("path_offsets", "elem_offsets", "leaf_value", "path_node", "path_dir", "path_elem", "elem_feature", "elem_z", "quad_t", "quad_w")
+_SHAP_TABLE_TYPES = (torch.int32, torch.int32, torch.float32, torch.int32, torch.uint8, torch.uint8, torch.int32, torch.float64, torch.float64, torch.float64)
+SHAP_QUAD = 528                        # the Gauss-Legendre rules of 1 .. 32 nodes on [0, 1]: the rule of Q nodes at Q (Q - 1) / 2
+
+
+def _gbdt_walk_kind(X, nodes, default_left, is_cat, cat_index, cat_sets):
+    """The form a walk over raw rows takes: '' (plain), '_missing' or '_cat', with the checked optional arrays."""
+    if (is_cat is None) != (cat_index is None) or (is_cat is None) != (cat_sets is None):
+        raise ValueError("is_cat, cat_index and cat_sets go together")
+    default_left = None if default_left is None else _check("default_left", default_left, torch.uint8, (nodes,))
+    if is_cat is None:
+        return ("" if default_left is None else "_missing"), default_left, None, None, None
+    is_cat = _gbdt_is_cat(is_cat, X.shape[1])
+    cat_index, cat_sets = _gbdt_cat_nodes(cat_index, cat_sets, nodes, X.device)
+    return "_cat", default_left, is_cat, cat_index, cat_sets
+
+
+def gbdt_leaf_counts(X, feature, threshold, left, right, tree_offsets, default_left=None, is_cat=None, cat_index=None, cat_sets=None):
+    """The rows of X (float32 [n, F]) per LEAF of every tree -> int64 [nodes + trees], in the layout of gbdt_predict's leaf values: the
+    walk of gbdt_predict (gbdt_predict_cat with is_cat, cat_index, cat_sets), one launch, one integer atomic per (row, tree).  The covers of
+    gbdt_shap are these counts, summed into node counts on the host (ptr_gbdt_leaf_counts, _missing, _cat)."""
+    X = _check("X", X)
+    if X.dim() != 2:
+        raise ValueError(f"X must be [rows, features], got {tuple(X.shape)}")
+    dev = X.device
+    tree_offsets = _check("tree_offsets", tree_offsets, torch.int32)
+    if tree_offsets.dim() != 1 or tree_offsets.numel() < 1:
+        raise ValueError(f"tree_offsets must be [trees + 1], got {tuple(tree_offsets.shape)}")
+    ntrees = tree_offsets.numel() - 1
+    nodes = feature.numel()
+    feature, left, right = (_check(k, t, torch.int32, (nodes,)) for k, t in zip(("feature", "left", "right"), (feature, left, right)))
+    threshold = _check("threshold", threshold, shape=(nodes,))
+    kind, default_left, is_cat, cat_index, cat_sets = _gbdt_walk_kind(X, nodes, default_left, is_cat, cat_index, cat_sets)
+    counts = torch.empty(nodes + ntrees, device=dev, dtype=torch.int64)
+    head = (_lib.ptr(X), X.shape[0], X.shape[1], _lib.ptr(feature), _lib.ptr(threshold), _lib.ptr(left), _lib.ptr(right), _lib.ptr(tree_offsets))
+    tail = (ntrees, nodes, counts.numel(), _lib.ptr(counts), _lib.current_stream(dev))
+    with torch.cuda.device(dev):
+        if kind == "":
+            _lib.call("ptr_gbdt_leaf_counts", *head, *tail)
+        elif kind == "_missing":
+            _lib.call("ptr_gbdt_leaf_counts_missing", *head, _lib.ptr(default_left), *tail)
+        else:
+            _lib.call("ptr_gbdt_leaf_counts_cat", *head, _lib.ptr(default_left), _lib.ptr(is_cat), _lib.ptr(cat_index), _lib.ptr(cat_sets),
+                      cat_sets.shape[0], *tail)
+    return counts
+
+
+def gbdt_shap(X, feature, threshold, tables, default_left=None, is_cat=None, cat_index=None, cat_sets=None):
+    """TreeSHAP contributions of raw rows X (float32 [n, F]) -> float64 [n, F + 1]: a column per feature, then the expected value.
+    feature, threshold (and default_left, cat_index) over the nodes of ALL trees; tables: the path tables (SHAP_TABLE_KEYS, one row per
+    leaf; gbdt.shap_tables builds them).  A sub-range of leaves is served by slicing path_offsets, elem_offsets and leaf_value alone.  A
+    row's bits depend on the row and the tables alone; malformed tables give NaN (ptr_gbdt_shap, _missing, _cat)."""
+    X = _check("X", X)
+    if X.dim() != 2:
+        raise ValueError(f"X must be [rows, features], got {tuple(X.shape)}")
+    dev = X.device
+    missing = [k for k in SHAP_TABLE_KEYS if k not in tables]
+    if missing:
+        raise ValueError(f"tables lacks {', '.join(missing)}")
+    tb = {k: _check(k, tables[k], dt) for k, dt in zip(SHAP_TABLE_KEYS, _SHAP_TABLE_TYPES)}
+    if any(t.dim() != 1 for t in tb.values()):
+        raise ValueError("every path table must be flat")
+    nleaves, npath, nelem = tb["leaf_value"].numel(), tb["path_node"].numel(), tb["elem_feature"].numel()
+    for k, size in (("path_offsets", nleaves + 1), ("elem_offsets", nleaves + 1), ("path_dir", npath), ("path_elem", npath), ("elem_z", nelem),
+                    ("quad_t", SHAP_QUAD), ("quad_w", SHAP_QUAD)):
+        if tb[k].numel() != size:
+            raise ValueError(f"{k} must have shape ({size},), got {tuple(tb[k].shape)}")
+    nodes = feature.numel()
+    feature = _check("feature", feature, torch.int32, (nodes,))
+    threshold = _check("threshold", threshold, shape=(nodes,))
+    kind, default_left, is_cat, cat_index, cat_sets = _gbdt_walk_kind(X, nodes, default_left, is_cat, cat_index, cat_sets)
+    phi = torch.empty((X.shape[0], X.shape[1] + 1), device=dev, dtype=torch.float64)
+    args = (_lib.ptr(X), X.shape[0], X.shape[1], _lib.ptr(feature), _lib.ptr(threshold), nodes, _lib.ptr(tb["path_offsets"]),
+            _lib.ptr(tb["elem_offsets"]), _lib.ptr(tb["leaf_value"]), nleaves, _lib.ptr(tb["path_node"]), _lib.ptr(tb["path_dir"]),
+            _lib.ptr(tb["path_elem"]), npath, _lib.ptr(tb["elem_feature"]), _lib.ptr(tb["elem_z"]), nelem, _lib.ptr(tb["quad_t"]), _lib.ptr(tb["quad_w"]))
+    with torch.cuda.device(dev):
+        if kind == "":
+            _lib.call("ptr_gbdt_shap", *args, _lib.ptr(phi), _lib.current_stream(dev))
+        elif kind == "_missing":
+            _lib.call("ptr_gbdt_shap_missing", *args, _lib.ptr(default_left), _lib.ptr(phi), _lib.current_stream(dev))
+        else:
+            _lib.call("ptr_gbdt_shap_cat", *args, _lib.ptr(default_left), _lib.ptr(is_cat), _lib.ptr(cat_index), _lib.ptr(cat_sets), cat_sets.shape[0],
+                      _lib.ptr(phi), _lib.current_stream(dev))
+    return phi

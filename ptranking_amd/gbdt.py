@@ -80,6 +80,20 @@ does not grow.  Whole fits are pinned to scikit-learn node for node (tests/golde
 groups every call and every model file is the one made before the keys existed.  Not here: the methods 'intermediate' and 'advanced',
 monotone_penalty.
 
+Feature contributions (LightGBM's predict(pred_contrib=True) and feature_importance()).  predict(X, pred_contrib=True) returns device
+float64 [n, F + 1]: path-dependent TreeSHAP (Lundberg et al., Algorithm 2) per feature and the expected value in the last column, so a
+row's entries sum to its score.  The rule is stated in include/ptranking_amd.h and restated twice in tests/gbdt_shap_ref.py (the Shapley
+definition itself, exponential in the features of a tree, and the polynomial recurrences in the kernel's order of operations); nothing is
+compared with LightGBM or the shap package.  TreeSHAP weighs the two children of a node by their covers, and neither a tree nor the
+pinned model files keep row counts: set_background(X) walks a background matrix through every tree in one launch, counts its rows per
+leaf with integer atomics, and the host sums them into covers and builds one path-table row per leaf (the path's nodes with their
+directions, the distinct features as elements with their zero fractions, the leaf value).  The training matrix gives the counts the trees
+were grown on (x <= edge is bin <= b).  The kernel gives a row to one wavefront, one lane per element of a path (at most 63 distinct
+features on a path; depth is free), and sums in float64 in LDS in leaf order: no float atomic, and a row's bits do not depend on the
+batch.  The covers live in memory only: a loaded or a grown booster calls set_background again, and pred_contrib=True without one raises.
+feature_importance('split') counts the splits per feature on the host; 'gain' raises, since the trees keep no gains.  With
+pred_contrib=False every call is the one made before the flag existed.
+
 Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here:
 feature_fraction, EFB, DART.  There is no CPU path.
 """
@@ -91,7 +105,7 @@ import torch
 from . import functional as F
 from . import letor, tree
 
-__all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS", "constraints"]
+__all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS", "constraints", "shap_tables", "SHAP_MAX_ELEMENTS"]
 
 # LightGBM's names, so the reference's lightgbm_para_dict passes through.  min_sum_hessian_in_leaf = 1e-3 is LightGBM's default too; the
 # reference's own dict sets 200, which suits LightGBM's built-in lambdarank Hessians, not the sums of tree.hip.
@@ -110,6 +124,7 @@ CAT_KEYS = ("categorical_feature", "cat_smooth")      # not among the parameters
 CST_KEYS = ("monotone_constraints", "monotone_constraints_method", "interaction_constraints")   # in a model file only where one is active
 MONOTONE_METHODS = ("basic",)
 GROW_POLICIES = ("leafwise", "depthwise")
+SHAP_MAX_ELEMENTS = 63                 # distinct features on one root-to-leaf path: one lane each, within the quadrature rules of up to 32 nodes
 SAMPLE_STRATEGIES = ("bagging", "goss")
 
 
@@ -388,6 +403,86 @@ def _record(r):
 _NO_SPLIT = (-np.inf, -1, -1, (0, 0, 0), (0, 0, 0))
 
 
+def shap_tables(trees, leaf_counts):
+    """The path tables of TreeSHAP (include/ptranking_amd.h documents the layout), numpy, one row per leaf in tree order, then leaf order.
+    trees: tree dicts (feature, left, right, value); leaf_counts: per tree the rows of the background per leaf (int64 [nodes + 1]).  The
+    cover of a node is the sum over the leaves below it.  z of an element = the product, in path order, of cover(child) / cover(node)
+    over the path's nodes on its feature (float64).  Also -> tree_leaf_offsets int64 [trees + 1] and covers (per tree, per node).
+    ValueError: a node or a leaf of cover 0, a path of more than SHAP_MAX_ELEMENTS distinct features, a tree that is no tree."""
+    path_offsets, elem_offsets, leaf_value = [0], [0], []
+    path_node, path_dir, path_elem, elem_feature, elem_z, covers = [], [], [], [], [], []
+    base = 0
+    for ti, (t, counts) in enumerate(zip(trees, leaf_counts)):
+        feature, left, right = (np.asarray(t[k]).astype(np.int64) for k in ("feature", "left", "right"))
+        nn = feature.size
+        counts = np.asarray(counts).astype(np.int64).reshape(-1)
+        if counts.size != nn + 1 or np.asarray(t["value"]).size != nn + 1:
+            raise ValueError(f"tree {ti}: {nn} nodes with {np.asarray(t['value']).size} leaf values and {counts.size} leaf counts")
+        up_node, up_leaf = np.full((nn, 2), -1, np.int64), np.full((nn + 1, 2), -1, np.int64)      # (parent, went left)
+        for i in range(nn):
+            for c, d in ((int(left[i]), 1), (int(right[i]), 0)):
+                into, j = (up_leaf, ~c) if c < 0 else (up_node, c)
+                if not 0 <= j < into.shape[0] or into[j, 0] >= 0 or c == 0:
+                    raise ValueError(f"tree {ti}: node {i} has the child {c}, which is out of range or has a parent already")
+                into[j] = (i, d)
+        cover = np.zeros(nn, np.int64)
+        paths = []
+        for l in range(nn + 1):
+            path, (at, d) = [], up_leaf[l]
+            while at >= 0 and len(path) <= nn:
+                path.append((int(at), int(d)))
+                cover[at] += counts[l]
+                at, d = up_node[at]
+            if nn and (not path or path[-1][0] != 0 or len(path) > nn):
+                raise ValueError(f"tree {ti}: leaf {l} does not hang below the root")
+            paths.append(path[::-1])
+        for i in np.nonzero(cover <= 0)[0][:1]:
+            raise ValueError(f"tree {ti}: node {int(i)} has cover 0: no row of the background reaches it")
+        for l in np.nonzero(counts <= 0)[0][:1]:
+            raise ValueError(f"tree {ti}: node ~{int(l)} (leaf {int(l)}) has cover 0: no row of the background reaches it")
+        covers.append(cover)
+        for l, path in enumerate(paths):
+            feats, z = [], []
+            for k, (at, d) in enumerate(path):
+                f = int(feature[at])
+                child = counts[l] if k + 1 == len(path) else cover[path[k + 1][0]]
+                frac = np.float64(child) / np.float64(cover[at])
+                if f not in feats:
+                    feats.append(f)
+                    z.append(np.float64(1.0))
+                e = feats.index(f)
+                z[e] = z[e] * frac
+                path_node.append(base + at)
+                path_dir.append(d)
+                path_elem.append(e)
+            if len(feats) > SHAP_MAX_ELEMENTS:
+                raise ValueError(f"tree {ti}: the path to leaf {l} holds {len(feats)} distinct features, at most {SHAP_MAX_ELEMENTS}")
+            elem_feature += feats
+            elem_z += z
+            path_offsets.append(len(path_node))
+            elem_offsets.append(len(elem_feature))
+        leaf_value.append(np.asarray(t["value"], np.float32).reshape(-1))
+        base += nn
+    if max(len(path_node), len(elem_feature), base) >= 2 ** 31:
+        raise ValueError("the path tables need int32 indices")
+    leaves = np.concatenate([[0], np.cumsum([np.asarray(t["feature"]).size + 1 for t in trees])]).astype(np.int64)
+    return {"path_offsets": np.array(path_offsets, np.int32), "elem_offsets": np.array(elem_offsets, np.int32),
+            "leaf_value": np.concatenate(leaf_value).astype(np.float32) if leaf_value else np.zeros(0, np.float32),
+            "path_node": np.array(path_node, np.int32), "path_dir": np.array(path_dir, np.uint8), "path_elem": np.array(path_elem, np.uint8),
+            "elem_feature": np.array(elem_feature, np.int32), "elem_z": np.array(elem_z, np.float64), "quad_t": _SHAP_QUAD[0], "quad_w": _SHAP_QUAD[1],
+            "tree_leaf_offsets": leaves, "covers": covers}
+
+
+def shap_quadrature():
+    """The Gauss-Legendre rules of TreeSHAP on [0, 1], float64: the rule of Q nodes (Q = 1 .. 32) at Q (Q - 1) / 2 .. of (t [528], w [528]).
+    The rule of Q nodes integrates a polynomial of degree 2 Q - 1 exactly: a path of d elements takes Q = ceil(d / 2)."""
+    ts, ws = zip(*(np.polynomial.legendre.leggauss(q) for q in range(1, (SHAP_MAX_ELEMENTS + 1) // 2 + 1)))
+    return (np.concatenate(ts) + 1.0) / 2.0, np.concatenate(ws) / 2.0
+
+
+_SHAP_QUAD = shap_quadrature()
+
+
 class GBDT:
     """The booster.  GBDT(params, X=None): params under LightGBM's names (DEFAULT_PARAMS; the keys of IGNORED_PARAMS are accepted and
     ignored; boosting_type other than 'gbdt' raises).  Under grow_policy='leafwise' update() costs one host synchronisation per split: the
@@ -405,6 +500,7 @@ class GBDT:
         self.best_iteration = None
         self._device = device
         self._flat = None
+        self._shap = None                  # set_background: the path tables of TreeSHAP on the device, for the trees held then
         self.n = 0
         self.host_reads = 0                # device-to-host reads inside update(), over the booster's life: what a growth policy costs
         self._qid = None
@@ -733,7 +829,7 @@ class GBDT:
             F.gbdt_add_tree_binned(self.scores, self.bins, self.F, self._rows[m:], up(t["feature"], np.int32), up(split_bin, np.int32), up(t["left"], np.int32),
                                    up(t["right"], np.int32), up(value, np.float32), also_left=None if also is None else up(also, np.int32))
         self.trees.append(t)
-        self._flat = None
+        self._flat = self._shap = None
         return t
 
     def _grow_depthwise(self, head, m):
@@ -866,8 +962,72 @@ class GBDT:
             out["cat_sets"] = (np.concatenate([t["cat_set"] for t in self.trees]) if self.trees else np.zeros((0, 4))).astype(np.int64).reshape(-1, 4)
         return out
 
-    def predict(self, X, num_iteration=None, first_tree=0, check_finite=True):
-        """Scores of raw rows X (numpy array or device tensor [n, F]) -> device float32 [n]: the trees first_tree .. num_iteration - 1
+    def feature_importance(self, importance_type="split"):
+        """How often the trees split on each feature -> int64 [F] (numpy), counted on the host.  'gain' raises: a tree keeps no gains, and
+        the three model file formats are pinned, so there is nowhere to keep them."""
+        if importance_type != "split":
+            raise ValueError(f"importance_type {importance_type!r}: only 'split'.  'gain' is not available: the trees keep no split gains and the "
+                             f"model file formats are pinned, so a loaded model could not report them")
+        if self.edges is None:
+            raise RuntimeError("fit_bins() or load_model() first: the model has no features yet")
+        used = np.concatenate([np.asarray(t["feature"]).reshape(-1) for t in self.trees]).astype(np.int64) if self.trees else np.zeros(0, np.int64)
+        return np.bincount(used, minlength=self.edges.shape[0]).astype(np.int64)
+
+    def _flat_device(self, dev):
+        if self._flat is None:
+            self._flat = {k: torch.from_numpy(v).to(dev) for k, v in self.flat().items()}
+        return self._flat
+
+    def _cat_walk(self, Xd):
+        """The categorical arguments of a walk over raw rows ({} for a model without categorical features)."""
+        if not self.params["categorical_feature"]:
+            return {}
+        if Xd.shape[1] != self.edges.shape[0]:
+            raise ValueError(f"X holds {Xd.shape[1]} columns, the model {self.edges.shape[0]}")
+        if self._is_cat_d is None or self._is_cat_d.device != Xd.device:
+            self._set_is_cat(Xd.device)
+        return {"is_cat": self._is_cat_d, "cat_index": self._flat["cat_index"], "cat_sets": self._flat["cat_sets"]}
+
+    def set_background(self, X, check_finite=True):
+        """The background matrix of predict(pred_contrib=True): X (numpy array or device tensor [n, F], raw rows as predict takes them) is
+        walked through every tree in one launch (ptr_gbdt_leaf_counts), the rows per leaf are summed into node covers on the host, and the
+        path tables of TreeSHAP are built and uploaded.  The trees keep no row counts; under this project's binning x <= edge is bin <= b, so
+        the TRAINING matrix as background gives the counts the trees were grown on.  Every node and leaf must be reached by a row
+        (ValueError names the tree and the node).  The covers live in memory only: save_model writes what it wrote, a loaded model calls
+        set_background again, and so does a booster that has grown since."""
+        dev = self._dev()
+        fl = self._flat_device(dev)
+        Xd = _device_matrix(X, dev)
+        if self.edges is not None and Xd.dim() == 2 and Xd.shape[1] != self.edges.shape[0]:
+            raise ValueError(f"X holds {Xd.shape[1]} columns, the model {self.edges.shape[0]}")
+        cats = self.params["categorical_feature"]
+        if check_finite:
+            _require_values(Xd, self.params["use_missing"], *((cats, self.params["max_bin"]) if cats else ()))
+        counts = F.gbdt_leaf_counts(Xd, fl["feature"], fl["threshold"], fl["left"], fl["right"], fl["tree_offsets"],
+                                    default_left=fl.get("default_left"), **self._cat_walk(Xd)).cpu().numpy()
+        offs = np.concatenate([[0], np.cumsum([t["feature"].size + 1 for t in self.trees])]).astype(np.int64)
+        host = shap_tables(self.trees, [counts[offs[t]:offs[t + 1]] for t in range(len(self.trees))])
+        self._shap = {"ntrees": len(self.trees), "tree_leaf_offsets": host["tree_leaf_offsets"], "leaf_counts": counts,
+                      "tables": {k: torch.from_numpy(host[k]).to(dev) for k in F.SHAP_TABLE_KEYS}}
+        return self
+
+    def _contrib(self, Xd, first_tree, stop):
+        """predict(pred_contrib=True): the leaves of the trees first_tree .. stop - 1 of the resident path tables through ptr_gbdt_shap."""
+        if self._shap is None or self._shap["ntrees"] != len(self.trees):
+            raise RuntimeError("pred_contrib=True needs covers and the trees keep none: call set_background(X) first (after load_model and "
+                               "after every update() too; the training matrix gives the counts the trees were grown on)")
+        if Xd.shape[1] != self.edges.shape[0]:
+            raise ValueError(f"X holds {Xd.shape[1]} columns, the model {self.edges.shape[0]}")
+        fl, tb = self._flat, dict(self._shap["tables"])
+        lo, hi = int(self._shap["tree_leaf_offsets"][first_tree]), int(self._shap["tree_leaf_offsets"][stop])
+        tb["path_offsets"], tb["elem_offsets"], tb["leaf_value"] = tb["path_offsets"][lo:hi + 1], tb["elem_offsets"][lo:hi + 1], tb["leaf_value"][lo:hi]
+        return F.gbdt_shap(Xd, fl["feature"], fl["threshold"], tb, default_left=fl.get("default_left"), **self._cat_walk(Xd))
+
+    def predict(self, X, num_iteration=None, first_tree=0, check_finite=True, pred_contrib=False):
+        """pred_contrib=True -> device float64 [n, F + 1]: the TreeSHAP contribution of every feature to the score of every row over the
+        same trees, and the expected value in the last column (LightGBM's layout); a row's entries sum to its score up to the fp32
+        rounding of predict's own sum.  It needs set_background.  Otherwise:
+        Scores of raw rows X (numpy array or device tensor [n, F]) -> device float32 [n]: the trees first_tree .. num_iteration - 1
         (default: up to best_iteration when early stopping set it, else all), summed in tree order in fp32 — for a training row the bits of
         its resident training score.  A NaN or an infinity in X raises, as in bin_edges (a NaN would go right at every node, while binning
         puts it left); the check costs one synchronisation, and check_finite=False skips it for a matrix the caller has already checked.
@@ -885,6 +1045,8 @@ class GBDT:
         cats = self.params["categorical_feature"]
         if check_finite:
             _require_values(Xd, self.params["use_missing"], *((cats, self.params["max_bin"]) if cats else ()))
+        if pred_contrib:
+            return self._contrib(Xd, first_tree, stop)
         if cats:
             return self._predict_cat(Xd, first_tree, stop)
         if first_tree == 0:
@@ -1092,10 +1254,20 @@ class LambdaMART:
         self.booster.best_iteration = self.best_iteration
         return self
 
-    def predict(self, X, num_iteration=None):
+    def predict(self, X, num_iteration=None, pred_contrib=False):
+        """The booster's scores, or with pred_contrib=True its TreeSHAP contributions float64 [n, F + 1] (set_background first)."""
         if self.booster is None:
             raise RuntimeError("fit() first")
+        if pred_contrib:
+            return self.booster.predict(X, num_iteration, pred_contrib=True)
         return self.booster.predict(X, num_iteration)
+
+    def set_background(self, X):
+        """GBDT.set_background on the fitted booster: the covers of predict(pred_contrib=True), usually from the training matrix."""
+        if self.booster is None:
+            raise RuntimeError("fit() first")
+        self.booster.set_background(X)
+        return self
 
     def run_letor(self, file_train, file_vali=None, file_test=None, eval_at=5, early_stopping_rounds=None, **loader_kwargs):
         """The shape of the reference's LightGBMLambdaMART.run() on this project's LETOR parser: trains on file_train (validating on file_vali
