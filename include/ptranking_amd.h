@@ -981,6 +981,9 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *   ptr_gbdt_goss                                n                                        counting passes (3), digits per pass (2048), workgroups
  *                                                                                           of a pass, launches of one call (5; 0 for n == 0)
  *   ptr_gbdt_partition_mask                      m                                        launches of one call (3), workgroups of a list of m rows
+ *   ptr_gbdt_leaf_sums                           n, nleaves                               kind, threads per workgroup, workgroups, LDS bytes, the
+ *                                                                                           most leaves of the LDS form (1024)
+ *                                                                                           kind: 0 nothing, 1 LDS cells, 2 global atomics
  *   ptr_irgan_sample, ptr_irgan_point_gen_fwd_bwd   L                                     G, queries per workgroup
  *   ptr_irgan_sel_fwd_bwd                        mode, L                                  G, queries per workgroup
  *   ptr_irfgan_point_sample, ptr_irfgan_pair_sample   L                                   G, queries per workgroup
@@ -1356,6 +1359,49 @@ int ptr_gbdt_shap_cat(const float *X, int64_t n, int F, const int32_t *feature, 
                       const int32_t *elem_feature, const double *elem_z, int64_t nelem, const double *quad_t, const double *quad_w,
         const uint8_t *default_left,
                       const uint8_t *is_cat, const int32_t *cat_index, const int64_t *cat_sets, int ncat, double *phi, void *stream);
+
+/* ---- A trained model on new data (csrc/gbdt.hip; GBDT.predict(pred_leaf=True), GBDT.refit and fit_bins(init_model=...) of
+ * ptranking_amd/gbdt.py).  ADDITIVE to ABI v8 too; every symbol above keeps its signature and its results bit for bit.
+ * tests/gbdt_lifecycle_ref.py restates the walk, the sums and the refit rule.
+ *
+ * All three walks take raw fp32 rows X [n][F] and decide at a node exactly as ptr_gbdt_predict / _missing / _cat do (x <= threshold, a NaN
+ * along default_left, set membership, an unseen code right); the _missing forms add default_left per node, the _cat forms the tables of
+ * ptr_gbdt_predict_cat (default_left may be NULL there).  Validated before any launch (PTR_ERR_INVALID_ARG): a negative size, a NULL
+ * pointer a launch would touch.  There is no CPU path.
+ *
+ * ptr_gbdt_predict_leaf: leaf [n][ntrees] int32 row-major (LightGBM's pred_leaf layout): leaf[r][t - first] = the index l of the leaf ~l
+ *   that tree t gives row r, for the trees first .. first + ntrees - 1 of tree_offsets (the node arrays hold `nodes` entries over ALL
+ *   trees, and cat_index stays absolute).  A tree of no node gives 0; a malformed tree, or one outside the node arrays, gives -1.  Nothing
+ *   is summed.  One thread per (row, tree).
+ * ptr_gbdt_leaf_sums: ONE tree of `nodes` nodes (its arrays start at the tree; cat_index still indexes cat_sets of ncat sets).  Writes
+ *   leaf [n] int32 (-1 for a row the tree loses or whose leaf index is >= nleaves) and ADDS (qg[r], qh[r], 1) into sums[leaf][3], int64
+ *   [nleaves][3] that the caller has zeroed; qg, qh int32 [n] as ptr_gbdt_quantize wrote them.  Integer atomics only: the sums do not depend
+ *   on the order of the adds or on the launch shape.  Forms (ptr_launch_form, by n and nleaves): nleaves <= 1024, a workgroup of 256 threads
+ *   takes >= 1024 consecutive rows, sums them in LDS cells of (int64, int64, uint32) = 20 bytes (20 KiB at the most: eight workgroups, all
+ *   the waves a compute unit holds, fit its 160 KiB) and flushes the cells a row reached with one global atomic per non-zero value; beyond
+ *   1024 leaves every row adds into global memory.  At most 1024 workgroups per launch.
+ * ptr_gbdt_add_by_leaf: scores[r] += values[leaf[r]] where 0 <= leaf[r] < nleaves; other rows are skipped. */
+int ptr_gbdt_predict_leaf(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                          const int32_t *right, const int32_t *tree_offsets, int first, int ntrees, int64_t nodes, int32_t *leaf,
+                          void *stream);
+int ptr_gbdt_predict_leaf_missing(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                  const int32_t *right, const int32_t *tree_offsets, const uint8_t *default_left, int first, int ntrees,
+                                  int64_t nodes, int32_t *leaf, void *stream);
+int ptr_gbdt_predict_leaf_cat(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                              const int32_t *right, const int32_t *tree_offsets, const uint8_t *default_left, const uint8_t *is_cat,
+                              const int32_t *cat_index, const int64_t *cat_sets, int ncat, int first, int ntrees, int64_t nodes,
+                              int32_t *leaf, void *stream);
+int ptr_gbdt_leaf_sums(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                       const int32_t *right, int nodes, const int32_t *qg, const int32_t *qh, int nleaves, int32_t *leaf, int64_t *sums,
+                       void *stream);
+int ptr_gbdt_leaf_sums_missing(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                               const int32_t *right, const uint8_t *default_left, int nodes, const int32_t *qg, const int32_t *qh,
+                               int nleaves, int32_t *leaf, int64_t *sums, void *stream);
+int ptr_gbdt_leaf_sums_cat(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                           const int32_t *right, const uint8_t *default_left, const uint8_t *is_cat, const int32_t *cat_index,
+                           const int64_t *cat_sets, int ncat, int nodes, const int32_t *qg, const int32_t *qh, int nleaves, int32_t *leaf,
+                           int64_t *sums, void *stream);
+int ptr_gbdt_add_by_leaf(float *scores, int64_t n, const int32_t *leaf, const float *values, int nleaves, void *stream);
 
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):

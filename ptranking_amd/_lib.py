@@ -142,6 +142,13 @@ SIGNATURES = {
                               _vp, _vp, _vp, _vp],
     "ptr_gbdt_shap_cat": [_vp, C.c_int64, _i, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp,
                           _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
+    "ptr_gbdt_predict_leaf": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int64, _vp, _vp],
+    "ptr_gbdt_predict_leaf_missing": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int64, _vp, _vp],
+    "ptr_gbdt_predict_leaf_cat": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_int64, _vp, _vp],
+    "ptr_gbdt_leaf_sums": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp],
+    "ptr_gbdt_leaf_sums_missing": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp],
+    "ptr_gbdt_leaf_sums_cat": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
+    "ptr_gbdt_add_by_leaf": [_vp, C.c_int64, _vp, _vp, _i, _vp],
     "ptr_letor_scan":[C.c_char_p, _i, _vp, _vp, _vp],
     "ptr_letor_load": [C.c_char_p, _i, _f, C.c_int64, C.c_int32, C.c_int64, _vp, _i, _vp, _vp, _vp],
 }

@@ -86,6 +86,7 @@ static const FormQuery kFormQueries[] = {
     {"ptr_gbdt_partition_segments", 1, 2, [](const int64_t *a, int32_t *out) { out[0] = 3; out[1] = (int32_t)((a[0] + kGbdtPartRows - 1) / kGbdtPartRows); }},
     {"ptr_gbdt_goss", 1, 4, [](const int64_t *a, int32_t *out) { put(out, gbdt_goss_form(a[0])); }},
     {"ptr_gbdt_partition_mask", 1, 2, [](const int64_t *a, int32_t *out) { out[0] = 3; out[1] = (int32_t)((a[0] + kGbdtPartRows - 1) / kGbdtPartRows); }},
+    {"ptr_gbdt_leaf_sums", 2, 5, [](const int64_t *a, int32_t *out) { put(out, gbdt_leaf_sums_form(a[0], a[1])); }},
     {"ptr_irgan_sample", 1, 2, [](const int64_t *a, int32_t *out) { put(out, irgan_form((int)a[0])); }},
     {"ptr_irgan_point_gen_fwd_bwd", 1, 2, [](const int64_t *a, int32_t *out) { put(out, irgan_form((int)a[0])); }},
     {"ptr_irgan_sel_fwd_bwd", 2, 2, [](const int64_t *a, int32_t *out) { put(out, irgan_sel_form((int)a[0], (int)a[1])); }},

@@ -42,6 +42,12 @@
 // rules that live in the split scan alone.  The scan is a template on "constrained" as well: such a wavefront first reads its leaf's
 // (lo, hi, v), its feature's sign and its permission from three small device tables (scalar loads: the item is wave-uniform), and every
 // candidate then takes the bounded gain; the grower computes the children's rows of the tables on the host from the record it reads anyway.
+//
+// A trained model on new data (ptr_gbdt_predict_leaf, ptr_gbdt_leaf_sums, ptr_gbdt_add_by_leaf; predict(pred_leaf=True), refit and
+// fit_bins(init_model=...) of gbdt.py): walks of raw rows through gbdt_walk under the predicate of the raw predictor, so every row lands where
+// prediction puts it.  The leaf index per (row, tree) with nothing summed; for one tree the leaf per row and the integer sums (qg, qh, 1) per
+// leaf, in LDS cells per workgroup up to kLeafSumsLdsLeaves leaves and straight into global memory beyond (gbdt_leaf_sums_form, ptr_gbdt.h,
+// gives the budget and why); and scores[r] += values[leaf[r]].  Integer atomics only, as everywhere in this file.
 #include <math.h>
 
 #include "ptr_gbdt.h"
@@ -888,6 +894,94 @@ gbdt_leaf_counts_kernel(const float *__restrict__ X, int64_t n, int F, const int
     }
 }
 
+// ---------------------------------------------------------------- a trained model on new data: leaf indices, per-leaf sums, add by leaf
+// The leaf index of every (row, tree): the walk of gbdt_predict_kernel with nothing summed.  One thread per cell of leaf [n][stop - first],
+// the tree fastest: a wavefront's stores are consecutive and its rows few.  A tree outside the node arrays or a malformed one gives -1.
+template <bool kCat> __global__ void __launch_bounds__(kBlock)
+gbdt_predict_leaf_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t *__restrict__ feature, const float *__restrict__ threshold,
+                         const int32_t *__restrict__ left, const int32_t *__restrict__ right, const int32_t *__restrict__ tree_offsets,
+                         const uint8_t *__restrict__ default_left, int first, int ntrees, int64_t nodes, int32_t *__restrict__ leaf, const GbdtCatWalk cat) {
+    const int64_t total = n * ntrees;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
+        const int64_t i = e / ntrees;
+        const int t = first + (int)(e - i * ntrees);
+        const int base = tree_offsets[t], nn = tree_offsets[t + 1] - base;
+        int out = -1;
+        if (base >= 0 && nn >= 0 && (int64_t)base + nn <= nodes) {       // a tree of no node reads none of the node arrays
+            const float *x = X + i * F;
+            bool bad = false;
+            const int node = gbdt_walk(nn, F, feature + base, left + base, right + base,
+                                       [&](int at, int f) { return gbdt_raw_goes_left<kCat>(x[f], base + at, f, threshold, default_left, cat, bad); });
+            if (gbdt_is_leaf(node, nn) && !bad) out = ~node;
+        }
+        leaf[e] = out;
+    }
+}
+
+// One row of ONE tree (nn nodes, the arrays start at the tree) -> its leaf index, or -1 where the tree loses the row or the leaf is past nleaves.
+template <bool kCat> __device__ __forceinline__ int gbdt_leaf_of(const float *__restrict__ x, int F, const int32_t *__restrict__ feature,
+                                                                 const float *__restrict__ threshold, const int32_t *__restrict__ left,
+                                                                 const int32_t *__restrict__ right, const uint8_t *__restrict__ default_left, int nn,
+                                                                 int nleaves, const GbdtCatWalk &cat) {
+    bool bad = false;
+    const int node = gbdt_walk(nn, F, feature, left, right,
+                               [&](int at, int f) { return gbdt_raw_goes_left<kCat>(x[f], at, f, threshold, default_left, cat, bad); });
+    return gbdt_is_leaf(node, nn) && !bad && ~node < nleaves ? ~node : -1;
+}
+
+// The per-leaf sums of refit, both forms.  A workgroup owns the rows [r0, r1), whole multiples of the block except the last.  kLds: it zeroes
+// nleaves cells of (int64, int64, uint32) in LDS, adds its rows there and flushes the cells a row reached, one global atomic per value;
+// otherwise every row adds into global memory.  Integer atomics either way: the sums are those of any other launch shape.
+template <bool kCat, bool kLds> __global__ void __launch_bounds__(kBlock)
+gbdt_leaf_sums_kernel(const float *__restrict__ X, int64_t n, int F, const int32_t *__restrict__ feature, const float *__restrict__ threshold,
+                      const int32_t *__restrict__ left, const int32_t *__restrict__ right, const uint8_t *__restrict__ default_left, int nn,
+                      const int32_t *__restrict__ qg, const int32_t *__restrict__ qh, int nleaves, int32_t *__restrict__ leaf,
+                      int64_t *__restrict__ sums, const GbdtCatWalk cat) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gbdt_smem[];
+    const int64_t per = (((n + gridDim.x - 1) / gridDim.x + kBlock - 1) / kBlock) * kBlock;
+    const int64_t r0 = (int64_t)blockIdx.x * per;
+    const int64_t r1 = r0 + per < n ? r0 + per : n;
+    const int tid = threadIdx.x;
+    u64 *lg = reinterpret_cast<u64 *>(gbdt_smem), *lh = lg + (kLds ? nleaves : 0);
+    uint32_t *lc = reinterpret_cast<uint32_t *>(lh + (kLds ? nleaves : 0));
+    if constexpr (kLds) {
+        for (int e = tid; e < nleaves; e += kBlock) { lg[e] = 0; lh[e] = 0; lc[e] = 0; }
+        __syncthreads();
+    }
+    for (int64_t i = r0 + tid; i < r1; i += kBlock) {
+        const int l = gbdt_leaf_of<kCat>(X + i * F, F, feature, threshold, left, right, default_left, nn, nleaves, cat);
+        leaf[i] = l;
+        if (l < 0) continue;
+        if constexpr (kLds) {
+            atomicAdd(&lg[l], (u64)(int64_t)qg[i]);
+            atomicAdd(&lh[l], (u64)(int64_t)qh[i]);
+            atomicAdd(&lc[l], 1u);
+        } else {
+            hist_add_global(sums + (size_t)l * 3, qg[i], qh[i], 1);
+        }
+    }
+    if constexpr (kLds) {
+        __syncthreads();
+        for (int e = tid; e < nleaves; e += kBlock) {
+            const uint32_t c = lc[e];
+            if (!c) continue;
+            int64_t *cell = sums + (size_t)e * 3;
+            if (lg[e]) atomicAdd(reinterpret_cast<u64 *>(cell), lg[e]);
+            if (lh[e]) atomicAdd(reinterpret_cast<u64 *>(cell + 1), lh[e]);
+            atomicAdd(reinterpret_cast<u64 *>(cell + 2), (u64)c);
+        }
+    }
+}
+
+// scores[r] += values[leaf[r]] for the rows whose leaf index is one: what refit adds after it has re-estimated a tree's values.
+__global__ void __launch_bounds__(kBlock)
+gbdt_add_by_leaf_kernel(float *__restrict__ scores, int64_t n, const int32_t *__restrict__ leaf, const float *__restrict__ values, int nleaves) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int l = leaf[i];
+    if (l >= 0 && l < nleaves) scores[i] += values[l];
+}
+
 // ---------------------------------------------------------------- TreeSHAP
 // Path-dependent TreeSHAP in its per-leaf form (include/ptranking_amd.h states the rule, tests/gbdt_shap_ref.py restates it operation by
 // operation).  A workgroup is ONE wavefront and owns a row: it walks the leaf table in order and keeps the row's [F + 1] float64 sums in
@@ -1459,6 +1553,116 @@ extern "C" int ptr_gbdt_leaf_counts_cat(const float *X, int64_t n, int F, const 
     if (int rc = check_cat_walk(cat, n > 0 && ntrees > 0 && nleaves > 0 && nodes > 0, F, who)) return rc;
     return gbdt_leaf_counts_impl(who, X, n, F, feature, threshold, left, right, tree_offsets, default_left, false, ntrees, nodes, nleaves, counts, stream, true,
                                  cat);
+}
+
+// ---------------------------------------------------------------- the entry points of a trained model on new data
+static int gbdt_predict_leaf_impl(const char *who, const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                  const int32_t *right, const int32_t *tree_offsets, const uint8_t *default_left, bool missing, int first, int ntrees,
+                                  int64_t nodes, int32_t *leaf, void *stream, bool cat_on = false, GbdtCatWalk cat = {nullptr, nullptr, nullptr, 0}) {
+    if (n < 0 || F < 0 || first < 0 || ntrees < 0 || nodes < 0) {
+        set_error("%s: negative size (n=%lld, F=%d, first=%d, ntrees=%d, nodes=%lld)", who, (long long)n, F, first, ntrees, (long long)nodes);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (n == 0 || ntrees == 0) return 0;
+    if (!leaf || (F > 0 && !X)) { set_error("%s: NULL pointer (X or leaf)", who); return PTR_ERR_INVALID_ARG; }
+    if (!tree_offsets || (nodes > 0 && (!feature || !threshold || !left || !right || (missing && !default_left)))) {
+        set_error("%s: NULL tree array", who);
+        return PTR_ERR_INVALID_ARG;
+    }
+    const int64_t blocks = (n * ntrees + kBlock - 1) / kBlock;
+    const dim3 grid((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)));  // the kernel strides beyond
+    if (cat_on)
+        hipLaunchKernelGGL(gbdt_predict_leaf_kernel<true>, grid, dim3(kBlock), 0, as_stream(stream), X, n, F, feature, threshold, left, right, tree_offsets,
+                           default_left, first, ntrees, nodes, leaf, cat);
+    else
+        hipLaunchKernelGGL(gbdt_predict_leaf_kernel<false>, grid, dim3(kBlock), 0, as_stream(stream), X, n, F, feature, threshold, left, right, tree_offsets,
+                           default_left, first, ntrees, nodes, leaf, cat);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_predict_leaf(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                     const int32_t *right, const int32_t *tree_offsets, int first, int ntrees, int64_t nodes, int32_t *leaf,
+                                     void *stream) {
+    return gbdt_predict_leaf_impl("ptr_gbdt_predict_leaf", X, n, F, feature, threshold, left, right, tree_offsets, nullptr, false, first, ntrees, nodes, leaf,
+                                  stream);
+}
+
+extern "C" int ptr_gbdt_predict_leaf_missing(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                             const int32_t *right, const int32_t *tree_offsets, const uint8_t *default_left, int first, int ntrees,
+                                             int64_t nodes, int32_t *leaf, void *stream) {
+    return gbdt_predict_leaf_impl("ptr_gbdt_predict_leaf_missing", X, n, F, feature, threshold, left, right, tree_offsets, default_left, true, first, ntrees,
+                                  nodes, leaf, stream);
+}
+
+extern "C" int ptr_gbdt_predict_leaf_cat(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                         const int32_t *right, const int32_t *tree_offsets, const uint8_t *default_left, const uint8_t *is_cat,
+                                         const int32_t *cat_index, const int64_t *cat_sets, int ncat, int first, int ntrees, int64_t nodes,
+                                         int32_t *leaf, void *stream) {
+    const char *who = "ptr_gbdt_predict_leaf_cat";
+    const GbdtCatWalk cat{is_cat, cat_index, cat_sets, ncat};
+    if (int rc = check_cat_walk(cat, n > 0 && ntrees > 0 && nodes > 0, F, who)) return rc;
+    return gbdt_predict_leaf_impl(who, X, n, F, feature, threshold, left, right, tree_offsets, default_left, false, first, ntrees, nodes, leaf, stream, true,
+                                  cat);
+}
+
+static int gbdt_leaf_sums_impl(const char *who, const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                               const int32_t *right, const uint8_t *default_left, bool missing, int nodes, const int32_t *qg, const int32_t *qh,
+                               int nleaves, int32_t *leaf, int64_t *sums, void *stream, bool cat_on = false,
+                               GbdtCatWalk cat = {nullptr, nullptr, nullptr, 0}) {
+    if (n < 0 || F < 0 || nodes < 0 || nleaves < 0) {
+        set_error("%s: negative size (n=%lld, F=%d, nodes=%d, nleaves=%d)", who, (long long)n, F, nodes, nleaves);
+        return PTR_ERR_INVALID_ARG;
+    }
+    const GbdtLeafSumsForm form = gbdt_leaf_sums_form(n, nleaves);
+    if (n == 0) return 0;
+    if (!leaf || !qg || !qh || (F > 0 && !X) || (nleaves > 0 && !sums)) { set_error("%s: NULL pointer (X, qg, qh, leaf or sums)", who); return PTR_ERR_INVALID_ARG; }
+    if (nodes > 0 && (!feature || !threshold || !left || !right || (missing && !default_left))) {
+        set_error("%s: NULL tree array", who);
+        return PTR_ERR_INVALID_ARG;
+    }
+    const bool lds = form.kind == 1;                                    // nleaves == 0: the global form writes leaf = -1 and adds nothing
+    const dim3 grid((unsigned)form.groups);
+    const size_t smem = lds ? (size_t)form.lds_bytes : 0;
+#define PTR_LEAF_SUMS(CAT, LDS)                                                                                                                     \
+    hipLaunchKernelGGL((gbdt_leaf_sums_kernel<CAT, LDS>), grid, dim3(kBlock), smem, as_stream(stream), X, n, F, feature, threshold, left, right,  \
+                       default_left, nodes, qg, qh, nleaves, leaf, sums, cat)
+    if (cat_on) { if (lds) PTR_LEAF_SUMS(true, true); else PTR_LEAF_SUMS(true, false); }
+    else { if (lds) PTR_LEAF_SUMS(false, true); else PTR_LEAF_SUMS(false, false); }
+#undef PTR_LEAF_SUMS
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_leaf_sums(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                  const int32_t *right, int nodes, const int32_t *qg, const int32_t *qh, int nleaves, int32_t *leaf, int64_t *sums,
+                                  void *stream) {
+    return gbdt_leaf_sums_impl("ptr_gbdt_leaf_sums", X, n, F, feature, threshold, left, right, nullptr, false, nodes, qg, qh, nleaves, leaf, sums, stream);
+}
+
+extern "C" int ptr_gbdt_leaf_sums_missing(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                          const int32_t *right, const uint8_t *default_left, int nodes, const int32_t *qg, const int32_t *qh,
+                                          int nleaves, int32_t *leaf, int64_t *sums, void *stream) {
+    return gbdt_leaf_sums_impl("ptr_gbdt_leaf_sums_missing", X, n, F, feature, threshold, left, right, default_left, true, nodes, qg, qh, nleaves, leaf,
+                               sums, stream);
+}
+
+extern "C" int ptr_gbdt_leaf_sums_cat(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                                      const int32_t *right, const uint8_t *default_left, const uint8_t *is_cat, const int32_t *cat_index,
+                                      const int64_t *cat_sets, int ncat, int nodes, const int32_t *qg, const int32_t *qh, int nleaves,
+                                      int32_t *leaf, int64_t *sums, void *stream) {
+    const char *who = "ptr_gbdt_leaf_sums_cat";
+    const GbdtCatWalk cat{is_cat, cat_index, cat_sets, ncat};
+    if (int rc = check_cat_walk(cat, n > 0 && nodes > 0, F, who)) return rc;
+    return gbdt_leaf_sums_impl(who, X, n, F, feature, threshold, left, right, default_left, false, nodes, qg, qh, nleaves, leaf, sums, stream, true, cat);
+}
+
+extern "C" int ptr_gbdt_add_by_leaf(float *scores, int64_t n, const int32_t *leaf, const float *values, int nleaves, void *stream) {
+    const char *who = "ptr_gbdt_add_by_leaf";
+    if (n < 0 || nleaves < 0) { set_error("%s: negative size (n=%lld, nleaves=%d)", who, (long long)n, nleaves); return PTR_ERR_INVALID_ARG; }
+    if (n == 0 || nleaves == 0) return 0;
+    if (!scores || !leaf || !values) { set_error("%s: NULL pointer (scores, leaf or values)", who); return PTR_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(gbdt_add_by_leaf_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), scores, n, leaf, values,
+                       nleaves);
+    return check_hip(hipGetLastError(), who);
 }
 
 static int gbdt_shap_impl(const char *who, const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, int64_t nodes,

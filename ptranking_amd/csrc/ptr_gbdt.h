@@ -58,4 +58,26 @@ inline GbdtGossForm gbdt_goss_form(int64_t n) {
     return {kGossPasses, kGossDigits, (int)(want < kGossMaxGroups ? want : kGossMaxGroups), 2 + kGossPasses};
 }
 
+// The per-leaf sums of refit (ptr_gbdt_leaf_sums): one tree, n rows, nleaves cells of (sum qg, sum qh, count).
+// LDS budget: a cell is (int64, int64, uint32) = 20 bytes, as in the histogram tile, and a workgroup keeps at most kLeafSumsLdsLeaves of them:
+// 20 KiB.  Eight workgroups of 256 threads are the 32 waves a compute unit holds, and 8 x 20 KiB = 160 KiB is its whole LDS, so the budget
+// never costs a wave; it is 4 to 30 times the leaves of a tree people train (31 .. 255).  The walk is a chain of dependent loads, so waves in
+// flight are what hide its latency: 256 threads, one row each per step, and a workgroup takes at least kLeafSumsRows rows so that zeroing
+// and flushing nleaves cells is paid once per 1024 walks.  The grid stops at kLeafSumsMaxGroups = 256 compute units x 4 and strides beyond.
+constexpr int kLeafSumsLdsLeaves = 1024; // most leaves a workgroup sums in LDS; a tree of more adds straight into global memory
+constexpr int kLeafSumsRows = 1024;      // least rows per workgroup
+constexpr int kLeafSumsMaxGroups = 1024; // workgroups of one launch at the most
+
+// kind 0: nothing to launch (n == 0); 1: LDS cells, the non-zero ones flushed with one global atomic per value; 2: global integer atomics
+// per row (nleaves == 0 too: every row is lost and nothing is added).  groups: the workgroups of the launch; lds_bytes: what one of them
+// declares; lds_leaves: the budget.
+struct GbdtLeafSumsForm { int kind; int block; int groups; int lds_bytes; int lds_leaves; };
+inline GbdtLeafSumsForm gbdt_leaf_sums_form(int64_t n, int64_t nleaves) {
+    if (n <= 0) return {0, kBlock, 0, 0, kLeafSumsLdsLeaves};
+    const int64_t want = (n + kLeafSumsRows - 1) / kLeafSumsRows;
+    const int groups = (int)(want < kLeafSumsMaxGroups ? want : kLeafSumsMaxGroups);
+    if (nleaves > 0 && nleaves <= kLeafSumsLdsLeaves) return {1, kBlock, groups, (int)nleaves * 20, kLeafSumsLdsLeaves};
+    return {2, kBlock, groups, 0, kLeafSumsLdsLeaves};
+}
+
 }  // namespace ptr

@@ -26,7 +26,7 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "gbdt_bag_mask", "gbdt_goss", "gbdt_partition_mask", "gbdt_add_tree_binned",
            "gbdt_best_split_cat", "gbdt_best_split_slots_cat", "gbdt_partition_cat", "gbdt_partition_segments_cat", "gbdt_add_tree_binned_cat",
            "gbdt_predict_cat", "gbdt_best_split_cst", "gbdt_best_split_slots_cst", "gbdt_leaf_counts", "gbdt_shap", "SHAP_TABLE_KEYS", "GBDT_MAX_BIN",
-           "GBDT_RECORD"]
+           "GBDT_RECORD", "gbdt_predict_leaf", "gbdt_leaf_sums", "gbdt_add_by_leaf"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
 # launch table, and it draws its own; irfgan_loss and adlist_loss are public too: they take a mode, as irgan_selected does)
@@ -1750,3 +1750,88 @@ def gbdt_shap(X, feature, threshold, tables, default_left=None, is_cat=None, cat
             _lib.call("ptr_gbdt_shap_cat", *args, _lib.ptr(default_left), _lib.ptr(is_cat), _lib.ptr(cat_index), _lib.ptr(cat_sets), cat_sets.shape[0],
                       _lib.ptr(phi), _lib.current_stream(dev))
     return phi
+
+
+# ---- a trained model on new data: leaf indices, the per-leaf sums of refit, add by leaf (include/ptranking_amd.h states the rules)
+def _gbdt_tree_nodes(X, feature, threshold, left, right):
+    X = _check("X", X)
+    if X.dim() != 2:
+        raise ValueError(f"X must be [rows, features], got {tuple(X.shape)}")
+    nodes = feature.numel()
+    feature, left, right = (_check(k, t, torch.int32, (nodes,)) for k, t in zip(("feature", "left", "right"), (feature, left, right)))
+    return X, nodes, feature, _check("threshold", threshold, shape=(nodes,)), left, right
+
+
+def gbdt_predict_leaf(X, feature, threshold, left, right, tree_offsets, first_tree=0, stop=None, default_left=None, is_cat=None, cat_index=None,
+                      cat_sets=None):
+    """The leaf every tree puts every row in -> int32 [n, stop - first_tree] (LightGBM's pred_leaf layout): entry [r, t - first_tree] is the
+    index l of the leaf ~l of tree t, found by the walk of gbdt_predict (gbdt_predict_cat with is_cat, cat_index, cat_sets) over the flat
+    arrays of ALL trees.  A tree of no node gives 0, a malformed tree -1 (ptr_gbdt_predict_leaf, _missing, _cat)."""
+    X, nodes, feature, threshold, left, right = _gbdt_tree_nodes(X, feature, threshold, left, right)
+    dev = X.device
+    tree_offsets = _check("tree_offsets", tree_offsets, torch.int32)
+    if tree_offsets.dim() != 1 or tree_offsets.numel() < 1:
+        raise ValueError(f"tree_offsets must be [trees + 1], got {tuple(tree_offsets.shape)}")
+    total = tree_offsets.numel() - 1
+    stop = total if stop is None else int(stop)
+    first_tree = int(first_tree)
+    if not 0 <= first_tree <= stop <= total:
+        raise ValueError(f"trees {first_tree} .. {stop} of {total}")
+    kind, default_left, is_cat, cat_index, cat_sets = _gbdt_walk_kind(X, nodes, default_left, is_cat, cat_index, cat_sets)
+    out = torch.empty((X.shape[0], stop - first_tree), device=dev, dtype=torch.int32)
+    head = (_lib.ptr(X), X.shape[0], X.shape[1], _lib.ptr(feature), _lib.ptr(threshold), _lib.ptr(left), _lib.ptr(right), _lib.ptr(tree_offsets))
+    tail = (first_tree, stop - first_tree, nodes, _lib.ptr(out), _lib.current_stream(dev))
+    with torch.cuda.device(dev):
+        if kind == "":
+            _lib.call("ptr_gbdt_predict_leaf", *head, *tail)
+        elif kind == "_missing":
+            _lib.call("ptr_gbdt_predict_leaf_missing", *head, _lib.ptr(default_left), *tail)
+        else:
+            _lib.call("ptr_gbdt_predict_leaf_cat", *head, _lib.ptr(default_left), _lib.ptr(is_cat), _lib.ptr(cat_index), _lib.ptr(cat_sets),
+                      cat_sets.shape[0], *tail)
+    return out
+
+
+def gbdt_leaf_sums(X, feature, threshold, left, right, qg, qh, nleaves=None, default_left=None, is_cat=None, cat_index=None, cat_sets=None, leaf=None,
+                   sums=None):
+    """ONE tree over raw rows -> (leaf int32 [n], sums int64 [nleaves, 3]): leaf[r] is the row's leaf index (-1 where the tree loses it) and
+    (qg[r], qh[r], 1) is ADDED into sums[leaf[r]]; sums=None starts from zeros, nleaves defaults to nodes + 1.  feature, threshold, left, right
+    (and default_left, cat_index) are the tree's own nodes; cat_index indexes cat_sets as given.  Integer atomics only: the sums do not depend
+    on the launch form (ptr_launch_form 'ptr_gbdt_leaf_sums': LDS cells up to 1024 leaves, global atomics beyond)."""
+    X, nodes, feature, threshold, left, right = _gbdt_tree_nodes(X, feature, threshold, left, right)
+    dev, n = X.device, X.shape[0]
+    qg, qh = _check("qg", qg, torch.int32, (n,)), _check("qh", qh, torch.int32, (n,))
+    nleaves = nodes + 1 if nleaves is None else int(nleaves)
+    if nleaves < 0:
+        raise ValueError(f"nleaves={nleaves}")
+    kind, default_left, is_cat, cat_index, cat_sets = _gbdt_walk_kind(X, nodes, default_left, is_cat, cat_index, cat_sets)
+    leaf = torch.empty(n, device=dev, dtype=torch.int32) if leaf is None else _check("leaf", leaf, torch.int32, (n,))
+    sums = torch.zeros((nleaves, 3), device=dev, dtype=torch.int64) if sums is None else _check("sums", sums, torch.int64, (nleaves, 3))
+    if not leaf.is_contiguous() or not sums.is_contiguous():
+        raise ValueError("leaf and sums must be contiguous")
+    head = (_lib.ptr(X), n, X.shape[1], _lib.ptr(feature), _lib.ptr(threshold), _lib.ptr(left), _lib.ptr(right))
+    tail = (nodes, _lib.ptr(qg), _lib.ptr(qh), nleaves, _lib.ptr(leaf), _lib.ptr(sums), _lib.current_stream(dev))
+    with torch.cuda.device(dev):
+        if kind == "":
+            _lib.call("ptr_gbdt_leaf_sums", *head, *tail)
+        elif kind == "_missing":
+            _lib.call("ptr_gbdt_leaf_sums_missing", *head, _lib.ptr(default_left), *tail)
+        else:
+            _lib.call("ptr_gbdt_leaf_sums_cat", *head, _lib.ptr(default_left), _lib.ptr(is_cat), _lib.ptr(cat_index), _lib.ptr(cat_sets),
+                      cat_sets.shape[0], *tail)
+    return leaf, sums
+
+
+def gbdt_add_by_leaf(scores, leaf, values):
+    """scores[r] += values[leaf[r]] in place where 0 <= leaf[r] < leaves; other rows are skipped.  scores float32 [n], leaf int32 [n], values
+    float32 [leaves] (ptr_gbdt_add_by_leaf)."""
+    scores = _check("scores", scores)
+    if scores.dim() != 1 or not scores.is_contiguous():
+        raise ValueError("scores must be flat and contiguous")
+    leaf = _check("leaf", leaf, torch.int32, (scores.numel(),))
+    values = _check("values", values)
+    if values.dim() != 1:
+        raise ValueError(f"values must be flat, got {tuple(values.shape)}")
+    with torch.cuda.device(scores.device):
+        _lib.call("ptr_gbdt_add_by_leaf", _lib.ptr(scores), scores.numel(), _lib.ptr(leaf), _lib.ptr(values), values.numel(), _lib.current_stream(scores.device))
+    return scores

@@ -94,9 +94,27 @@ batch.  The covers live in memory only: a loaded or a grown booster calls set_ba
 feature_importance('split') counts the splits per feature on the host; 'gain' raises, since the trees keep no gains.  With
 pred_contrib=False every call is the one made before the flag existed.
 
+A trained model on new data (LightGBM's init_model, Booster.refit and predict(pred_leaf=True); the rules are this project's own, stated
+in include/ptranking_amd.h and restated in tests/gbdt_lifecycle_ref.py; nothing is compared with LightGBM).  predict(X, pred_leaf=True)
+returns device int32 [n, trees]: the index of the leaf each tree puts each row in, by the walk predict itself makes
+(ptr_gbdt_predict_leaf), so value[leaf] summed in tree order in fp32 is the score.  fit_bins(X, init_model=...) and
+LambdaMART.fit(..., init_model=...) continue a GBDT, a LambdaMART or a saved model on X: the bins are the model's (the trainer must share
+max_bin, use_missing and categorical_feature with it; a categorical code above the model's largest, or a NaN in a feature the model keeps
+no NaN bin for, raises), the trees are copies of those predict uses by default, the resident scores start at predict(X), and the tree
+counter goes on (the bagging draws and GOSS's warm-up count all trees; evals_result holds the added rounds and best_iteration counts all
+trees).  Since every decision rests on integer sums, a fit split in two (train, save, load, continue) gives the trees, values and scores
+of the unsplit fit bit for bit.  refit(X, grad_hess, decay_rate=0.9) returns a NEW booster with the same structures whose leaf values are
+re-estimated on X tree by tree: gradients at the running scores, ptr_gbdt_quantize, the per-leaf integer sums of ptr_gbdt_leaf_sums
+(LDS cells per workgroup up to 1024 leaves, global integer atomics beyond), one host read per tree, value = float32(decay_rate * old +
+(1 - decay_rate) * (-G / (H + lambda_l2) * learning_rate)) in float64, a leaf no row reaches keeping its value, then ptr_gbdt_add_by_leaf;
+on the training data with decay_rate=0 an unsampled, unconstrained model gets its own values back bit for bit.  Monotone constraints
+refuse refit.  LambdaMART.refit(X, y, group) supplies the ranker's objective.  With init_model=None and pred_leaf=False every call and
+every model file is the one made before they existed; a continued or refitted model saves in the same three formats.
+
 Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here:
 feature_fraction, EFB, DART.  There is no CPU path.
 """
+import copy
 import json
 
 import numpy as np
@@ -384,6 +402,54 @@ def leaf_value(g_sum, h_sum, expo, lambda_l2, learning_rate):
     return np.float32(-G / (H + lambda_l2) * learning_rate) if H + lambda_l2 > 0.0 else np.float32(0.0)
 
 
+def refit_value(old, g_sum, h_sum, count, expo, lambda_l2, learning_rate, decay_rate):
+    """The value refit gives a leaf: float32(decay_rate * float64(old) + (1 - decay_rate) * new) with new = -G / (H + lambda_l2) *
+    learning_rate in float64 from the integer sums, in leaf_value's order of operations.  A leaf no row reaches (count 0) or one with
+    H + lambda_l2 <= 0 keeps old."""
+    G, H = np.ldexp(float(g_sum), -int(expo[0])), np.ldexp(float(h_sum), -int(expo[1]))
+    if int(count) <= 0 or not H + lambda_l2 > 0.0:
+        return np.float32(old)
+    new = -G / (H + lambda_l2) * learning_rate
+    return np.float32(decay_rate * float(np.float32(old)) + (1.0 - decay_rate) * new)
+
+
+def _decay_rate(decay_rate):
+    try:
+        decay = float(decay_rate)
+    except (TypeError, ValueError):
+        raise ValueError(f"decay_rate must be a number in [0, 1], got {decay_rate!r}") from None
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError(f"decay_rate must be in [0, 1], got {decay_rate!r}")
+    return decay
+
+
+INIT_MODEL_KEYS = ("max_bin", "use_missing", "categorical_feature")    # what a trainer must share with the model it continues: they fix the bins
+
+
+def _initial_model(init_model, params, device=None):
+    """init_model (a GBDT, a LambdaMART or the path of a saved model) as a GBDT whose bins the parameters `params` can continue on; a
+    difference in one of INIT_MODEL_KEYS raises ValueError naming the key.  Runs on the host."""
+    model = init_model
+    if isinstance(model, LambdaMART):
+        model = model.booster
+        if model is None:
+            raise ValueError("init_model is a LambdaMART that has not been fitted")
+    elif not isinstance(model, GBDT):
+        if not isinstance(model, (str, bytes)) and not hasattr(model, "__fspath__"):
+            raise ValueError(f"init_model must be a GBDT, a LambdaMART or the path of a saved model, got {type(init_model).__name__}")
+        model = GBDT.load_model(model, device=device)
+    for k in INIT_MODEL_KEYS:
+        if params[k] != model.params[k]:
+            raise ValueError(f"init_model was trained with {k}={model.params[k]!r}, this trainer has {k}={params[k]!r}: the bins would differ")
+    if model.edges is None:
+        raise ValueError("init_model holds no bin edges: fit_bins() or load_model() first")
+    return model
+
+
+def _copy_tree(t):
+    return {k: np.array(v) for k, v in t.items()}
+
+
 class _Leaf:
     __slots__ = ("start", "count", "depth", "slot", "parent", "side", "g", "h", "rec", "set", "cst", "groups")
 
@@ -513,10 +579,15 @@ class GBDT:
             raise RuntimeError("GBDT needs a GPU: ptranking_amd runs on the MI355X HIP path only (no CPU fallback)")
         return torch.device("cuda" if self._device is None else self._device)
 
-    def fit_bins(self, X, group=None):
+    def fit_bins(self, X, group=None, init_model=None):
         """Computes the bin edges of X (numpy array or device tensor [n, F]) on the host, bins X on the device and keeps the bins, the
-        training scores (zeros) and the work buffers resident.  group: the documents per query, which bagging_by_query samples by."""
+        training scores (zeros) and the work buffers resident.  group: the documents per query, which bagging_by_query samples by.
+        init_model (a GBDT, a LambdaMART or the path of a saved model): continue that model on X.  The edges are the model's (no bin_edges
+        call), the trees are copies of those its predict uses by default (best_iteration is cleared), and the resident scores start at
+        predict(X) over them, so update() goes on from tree len(trees): a fit split in two gives the bits of the unsplit fit.  The trainer
+        must share max_bin, use_missing and categorical_feature with the model, and X must fit its bins (ValueError otherwise)."""
         groups = self._check_constraints(np.shape(X))                      # the refusals of the constraints come before any device work
+        model = None if init_model is None else _initial_model(init_model, self.params, self._device)
         dev = self._dev()
         if group is not None:
             group = np.asarray(group).reshape(-1).astype(np.int64)
@@ -530,7 +601,9 @@ class GBDT:
         cats = p["categorical_feature"]
         if cats and cats[-1] >= host.shape[1]:
             raise ValueError(f"categorical_feature {cats[-1]} with {host.shape[1]} columns")
-        if p["use_missing"]:
+        if model is not None:
+            self._take_bins(model, host)
+        elif p["use_missing"]:
             self.edges, self.nbins, self.nan_bin = bin_edges(host, p["max_bin"], True, **({"categorical": cats} if cats else {}))
         else:
             self.edges, self.nbins = bin_edges(host, p["max_bin"], **({"categorical": cats} if cats else {}))
@@ -568,7 +641,40 @@ class GBDT:
             if sampling(p) == "goss":
                 self._gg, self._gh = torch.empty_like(self.scores), torch.empty_like(self.scores)
                 self._info = torch.zeros(3, device=dev, dtype=torch.int32)
+        if model is not None:
+            stop = model.best_iteration or len(model.trees)
+            self.trees = [_copy_tree(t) for t in model.trees[:stop]]
+            self.best_iteration = None
+            self._flat = self._shap = None
+            self.scores = self.predict(Xd, check_finite=False)             # the bits predict goes on giving: each new tree is added after them
         return self
+
+    def _take_bins(self, model, host):
+        """The edges of an initial model in place of bin_edges(host), with bin_edges' refusals of what the matrix may hold and two more:
+        what the model's bins cannot represent."""
+        p = self.params
+        if host.ndim != 2 or host.shape[1] != model.edges.shape[0]:
+            raise ValueError(f"X must be [rows, {model.edges.shape[0]}] as the initial model's, got {host.shape}")
+        nan = np.isnan(host)
+        if p["use_missing"]:
+            if np.isinf(host).any():
+                raise ValueError(_INFINITE)
+            nan_bin = np.asarray(model.nan_bin).reshape(-1)
+            if nan_bin.size != host.shape[1]:
+                raise ValueError(f"init_model holds nan_bin for {nan_bin.size} features, X {host.shape[1]} columns")
+            for f in np.nonzero(nan.any(axis=0) & (nan_bin < 0))[0][:1]:
+                raise ValueError(f"feature {int(f)} holds a NaN, and the initial model keeps no NaN bin for it (nan_bin is -1): its training data held none")
+        elif not np.isfinite(host).all():
+            raise ValueError(_NONFINITE)
+        for f in p["categorical_feature"]:
+            col = host[:, f][~nan[:, f]]
+            if col.size and not ((col == np.floor(col)) & (col >= 0) & (col <= p["max_bin"] - 1)).all():
+                raise ValueError(f"feature {f}: " + _not_codes(p["max_bin"]))
+            if col.size and col.max() > int(model.nbins[f]) - 1:
+                raise ValueError(f"feature {f} holds the categorical code {int(col.max())}, above the initial model's largest, {int(model.nbins[f]) - 1}: "
+                                 f"its bins cannot represent it")
+        self.edges, self.nbins = np.array(model.edges, np.float32), np.array(model.nbins, np.int32)
+        self.nan_bin = np.array(model.nan_bin, np.int32) if p["use_missing"] else None
 
     def _check_constraints(self, shape):
         """Checks monotone_constraints and interaction_constraints against the columns of X -> the interaction groups as sets (the unlisted
@@ -1023,8 +1129,10 @@ class GBDT:
         tb["path_offsets"], tb["elem_offsets"], tb["leaf_value"] = tb["path_offsets"][lo:hi + 1], tb["elem_offsets"][lo:hi + 1], tb["leaf_value"][lo:hi]
         return F.gbdt_shap(Xd, fl["feature"], fl["threshold"], tb, default_left=fl.get("default_left"), **self._cat_walk(Xd))
 
-    def predict(self, X, num_iteration=None, first_tree=0, check_finite=True, pred_contrib=False):
-        """pred_contrib=True -> device float64 [n, F + 1]: the TreeSHAP contribution of every feature to the score of every row over the
+    def predict(self, X, num_iteration=None, first_tree=0, check_finite=True, pred_contrib=False, pred_leaf=False):
+        """pred_leaf=True -> device int32 [n, trees]: the index of the leaf each of the same trees puts each row in (LightGBM's layout);
+        value[leaf] summed in tree order in fp32 is the score.  It cannot be combined with pred_contrib.
+        pred_contrib=True -> device float64 [n, F + 1]: the TreeSHAP contribution of every feature to the score of every row over the
         same trees, and the expected value in the last column (LightGBM's layout); a row's entries sum to its score up to the fp32
         rounding of predict's own sum.  It needs set_background.  Otherwise:
         Scores of raw rows X (numpy array or device tensor [n, F]) -> device float32 [n]: the trees first_tree .. num_iteration - 1
@@ -1034,6 +1142,8 @@ class GBDT:
         A model trained under use_missing takes NaNs: at a node a NaN feature follows the node's default_left; an infinity still raises.
         A categorical column must hold integer codes in 0 .. max_bin - 1 (the same check; check_finite=False skips it, and the kernel then
         sends what is no integer code in 0 .. 255 right).  A code the training data never held is legal: it is in no left set and goes right."""
+        if pred_leaf and pred_contrib:
+            raise ValueError("pred_leaf and pred_contrib cannot be combined: ask for one of them")
         dev = self._dev()
         if self._flat is None:
             self._flat = {k: torch.from_numpy(v).to(dev) for k, v in self.flat().items()}
@@ -1047,6 +1157,11 @@ class GBDT:
             _require_values(Xd, self.params["use_missing"], *((cats, self.params["max_bin"]) if cats else ()))
         if pred_contrib:
             return self._contrib(Xd, first_tree, stop)
+        if pred_leaf:
+            if self.edges is not None and Xd.shape[1] != self.edges.shape[0]:
+                raise ValueError(f"X holds {Xd.shape[1]} columns, the model {self.edges.shape[0]}")
+            return F.gbdt_predict_leaf(Xd, fl["feature"], fl["threshold"], fl["left"], fl["right"], fl["tree_offsets"], first_tree, stop,
+                                       default_left=fl.get("default_left"), **self._cat_walk(Xd))
         if cats:
             return self._predict_cat(Xd, first_tree, stop)
         if first_tree == 0:
@@ -1080,6 +1195,66 @@ class GBDT:
         offs = up((host["tree_offsets"][first_tree:stop + 1] - lo).astype(np.int32))
         return F.gbdt_predict_cat(Xd, sub["feature"], sub["threshold"], sub["left"], sub["right"], val, offs, self._is_cat_d,
                                   up(np.where(ci >= 0, ci - first, -1).astype(np.int32)), up(sets), default_left=sub.get("default_left"))
+
+    def refit(self, X, grad_hess, decay_rate=0.9):
+        """Keeps the tree structures and re-estimates the leaf values on new data (LightGBM's Booster.refit; the rule is this project's own
+        and no parity is claimed) -> a NEW booster with the same structures, edges and parameters and its own value arrays; self is
+        untouched.  X: raw rows [n, F] as predict takes them; grad_hess(scores) -> device fp32 (grad, hess) [n] at the running scores, which
+        start at zero.  Per tree, in order: grad_hess, gbdt_quantize (a NaN or an infinity raises, as in update), gbdt_leaf_sums over the
+        tree, ONE host read of the sums (host_reads grows by one per tree), refit_value per leaf on the host
+        (float32(decay_rate * old + (1 - decay_rate) * new), new = -G / (H + lambda_l2) * learning_rate; a leaf no row reaches or one with
+        H + lambda_l2 <= 0 keeps old), gbdt_add_by_leaf with the new values.  The trees are those predict uses by default (up to
+        best_iteration when early stopping set it, which the new booster clears), so its .scores are its predict(X) bit for bit.  On the
+        training matrix with the training objective and decay_rate=0 an unsampled, unconstrained model gets its own leaf values back bit
+        for bit.  Active monotone constraints raise: clamped values cannot be re-estimated leaf by leaf without breaking the guarantee."""
+        decay = _decay_rate(decay_rate)
+        p = self.params
+        if "monotone" in constraints(p):
+            raise ValueError("refit is not available under monotone_constraints: the leaf values were clamped between their neighbours', and "
+                             "re-estimating them leaf by leaf would break the guarantee")
+        if self.edges is None:
+            raise RuntimeError("fit_bins() or load_model() first: there is no model to refit")
+        dev = self._dev()
+        Xd = _device_matrix(X, dev)
+        if Xd.dim() != 2 or Xd.shape[1] != self.edges.shape[0]:
+            raise ValueError(f"X must be [rows, {self.edges.shape[0]}], got {tuple(Xd.shape)}")
+        cats = p["categorical_feature"]
+        _require_values(Xd, p["use_missing"], *((cats, p["max_bin"]) if cats else ()))
+        stop = self.best_iteration or len(self.trees)
+        new = GBDT(p, device=self._device)
+        new.edges, new.nbins = np.array(self.edges), np.array(self.nbins)
+        new.nan_bin = None if self.nan_bin is None else np.array(self.nan_bin)
+        new.trees = [_copy_tree(t) for t in self.trees[:stop]]
+        new.host_reads = self.host_reads
+        fl = new._flat_device(dev)                                         # the structures on the device; the values are not read from it
+        walk = new._cat_walk(Xd)
+        n = Xd.shape[0]
+        scores = torch.zeros(n, device=dev, dtype=torch.float32)
+        qg, qh = torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.int32)
+        expo, flag = torch.zeros(2, device=dev, dtype=torch.int32), torch.zeros(1, device=dev, dtype=torch.int32)
+        leaf = torch.empty(n, device=dev, dtype=torch.int32)
+        sums = torch.zeros((max([t["value"].size for t in new.trees], default=1), 3), device=dev, dtype=torch.int64)
+        offs = np.concatenate([[0], np.cumsum([t["feature"].size for t in new.trees])]).astype(np.int64)
+        for ti, t in enumerate(new.trees):
+            grad, hess = grad_hess(scores)
+            F.gbdt_quantize(grad, hess, flag=flag, out=(qg, qh, expo))
+            lo, hi, nl = int(offs[ti]), int(offs[ti + 1]), t["value"].size
+            cells = sums[:nl]
+            cells.zero_()
+            F.gbdt_leaf_sums(Xd, fl["feature"][lo:hi], fl["threshold"][lo:hi], fl["left"][lo:hi], fl["right"][lo:hi], qg, qh, nl,
+                             default_left=fl["default_left"][lo:hi] if "default_left" in fl else None, leaf=leaf, sums=cells,
+                             **({"is_cat": walk["is_cat"], "cat_index": walk["cat_index"][lo:hi], "cat_sets": walk["cat_sets"]} if walk else {}))
+            head = torch.cat([cells.reshape(-1), expo.to(torch.int64), flag.to(torch.int64)]).cpu().numpy()      # the one read of this tree
+            new.host_reads += 1
+            if head[-1]:
+                raise FloatingPointError("the gradients or Hessians of this round hold a NaN or an infinity")
+            ex, s = (int(head[-3]), int(head[-2])), head[:-3].reshape(nl, 3)
+            t["value"] = np.array([refit_value(t["value"][l], s[l, 0], s[l, 1], s[l, 2], ex, p["lambda_l2"], p["learning_rate"], decay) for l in range(nl)],
+                                  np.float32)
+            F.gbdt_add_by_leaf(scores, leaf, torch.from_numpy(t["value"]).to(dev))
+        new._flat = new._shap = None                                       # the device copy holds the old values
+        new.scores = scores                                                # no bins are resident: update() still asks for fit_bins first
+        return new
 
     def save_model(self, path):
         """An .npz of this project's own (not LightGBM's text format): the flat tree arrays, the bin edges, the parameters.  Format 1
@@ -1210,15 +1385,21 @@ class LambdaMART:
         keep = ((lab > 0) & pos).any(dim=1)
         return float(nd[keep].mean()) if bool(keep.any()) else 0.0
 
-    def fit(self, X, y, group, eval_set=None, eval_group=None, eval_at=5, early_stopping_rounds=None, num_boost_round=None, verbose=0):
+    def fit(self, X, y, group, eval_set=None, eval_group=None, eval_at=5, early_stopping_rounds=None, num_boost_round=None, verbose=0,
+            init_model=None):
         """X [n, F], y [n] relevance grades, group: documents per query.  eval_set = (X_valid, y_valid) with eval_group: nDCG@eval_at on it
         after every round (evals_result); early_stopping_rounds: stop after that many rounds without improvement and let predict use the
-        best round (best_iteration), as LightGBM does."""
+        best round (best_iteration), as LightGBM does.
+        init_model (a GBDT, a LambdaMART or the path of a saved model): the rounds are ADDED to that model's trees (GBDT.fit_bins): the
+        training scores and the validation scores start at its predictions, num_boost_round / num_trees count the added rounds,
+        evals_result holds the added rounds, and best_iteration counts all trees."""
         res = tree._Resident(y, group, self.device)
         X = X if isinstance(X, torch.Tensor) else np.asarray(X)
         if X.shape[0] != res.n_docs:
             raise ValueError(f"X holds {X.shape[0]} rows, the groups {res.n_docs}")
-        self.booster = GBDT(self.params, device=self.device).fit_bins(X, group=np.asarray(group).reshape(-1))
+        self.booster = GBDT(self.params, device=self.device).fit_bins(X, group=np.asarray(group).reshape(-1),
+                                                                      **({} if init_model is None else {"init_model": init_model}))
+        base = len(self.booster.trees)                                     # the initial model's trees: the rounds count on from them
         self.evals_result, self.best_iteration, self.best_score = [], None, None
         rounds = self.params["num_trees"] if num_boost_round is None else int(num_boost_round)
         valid = None
@@ -1230,11 +1411,12 @@ class LambdaMART:
             cats = self.params["categorical_feature"]
             _require_values(Xv, self.params["use_missing"], *((cats, self.params["max_bin"]) if cats else ()))   # once, before the first round: the rounds skip it
             yv = torch.from_numpy(np.ascontiguousarray(np.asarray(yv).reshape(-1), dtype=np.float32)).to(self.device)
-            valid = (Xv, yv, self.padded_index(eval_group, self.device), torch.zeros(Xv.shape[0], device=self.device, dtype=torch.float32))
+            sv = self.booster.predict(Xv, check_finite=False) if base else torch.zeros(Xv.shape[0], device=self.device, dtype=torch.float32)
+            valid = (Xv, yv, self.padded_index(eval_group, self.device), sv)
         elif early_stopping_rounds is not None:
             raise ValueError("early_stopping_rounds needs an eval_set")
         gh = (torch.empty_like(self.booster.scores), torch.empty_like(self.booster.scores))
-        for it in range(1, rounds + 1):
+        for it in range(base + 1, base + rounds + 1):
             self.grad_hess(self.booster.scores, res, gh)
             self.booster.update(*gh)
             if valid is None:
@@ -1254,13 +1436,31 @@ class LambdaMART:
         self.booster.best_iteration = self.best_iteration
         return self
 
-    def predict(self, X, num_iteration=None, pred_contrib=False):
-        """The booster's scores, or with pred_contrib=True its TreeSHAP contributions float64 [n, F + 1] (set_background first)."""
+    def predict(self, X, num_iteration=None, pred_contrib=False, pred_leaf=False):
+        """The booster's scores, or with pred_contrib=True its TreeSHAP contributions float64 [n, F + 1] (set_background first), or with
+        pred_leaf=True the leaf index per row and tree, int32 [n, trees]."""
         if self.booster is None:
             raise RuntimeError("fit() first")
+        if pred_leaf:
+            return self.booster.predict(X, num_iteration, pred_contrib=pred_contrib, pred_leaf=True)
         if pred_contrib:
             return self.booster.predict(X, num_iteration, pred_contrib=True)
         return self.booster.predict(X, num_iteration)
+
+    def refit(self, X, y, group, decay_rate=0.9):
+        """GBDT.refit of the fitted booster on new queries under this ranker's objective -> a NEW LambdaMART around the refitted booster (its
+        .booster.scores are its predict(X)); self is untouched."""
+        decay = _decay_rate(decay_rate)
+        if self.booster is None:
+            raise RuntimeError("fit() first")
+        res = tree._Resident(y, group, self.device)
+        if np.shape(X)[0] != res.n_docs:
+            raise ValueError(f"X holds {np.shape(X)[0]} rows, the groups {res.n_docs}")
+        gh = (torch.empty(res.n_docs, device=self.device, dtype=torch.float32), torch.empty(res.n_docs, device=self.device, dtype=torch.float32))
+        new = copy.copy(self)
+        new.booster = self.booster.refit(X, lambda scores: self.grad_hess(scores, res, gh), decay)
+        new.evals_result, new.best_iteration, new.best_score = [], None, None
+        return new
 
     def set_background(self, X):
         """GBDT.set_background on the fitted booster: the covers of predict(pred_contrib=True), usually from the training matrix."""
