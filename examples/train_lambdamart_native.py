@@ -6,6 +6,7 @@
     python examples/train_lambdamart_native.py --bagging-fraction 0.5 --bagging-freq 1 --by-query   # every tree on a fresh half of the queries
     python examples/train_lambdamart_native.py --goss                            # gradient-based one-side sampling (top 0.2, other 0.1)
     python examples/train_lambdamart_native.py --objective lambdarank_ndcg       # the truncated, normalised lambdarank (level 30)
+    python examples/train_lambdamart_native.py --objective rank_xendcg           # cross-entropy nDCG: O(n) per query
     python examples/train_lambdamart_native.py --categorical 3,7                 # the columns 3 and 7 hold codes: set splits
     python examples/train_lambdamart_native.py --monotone 0:1,5:-1               # scores non-decreasing in column 0, non-increasing in 5
     python examples/train_lambdamart_native.py --interaction "0,1;2,3"           # a path uses the columns of one group only (the rest: one more group)
@@ -54,11 +55,13 @@ def from_file(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("files", nargs="*", help="train.txt [vali.txt] [test.txt]")
-    ap.add_argument("--objective", default="lambdarank", choices=["lambdarank", "ranknet", "listnet", "lambdarank_ndcg"],
-                    help="lambdarank_ndcg: the truncated, normalised lambdarank (this project's rule, modelled on LightGBM's built-in objective)")
+    ap.add_argument("--objective", default="lambdarank", choices=list(pa.tree.OBJECTIVES),
+                    help="lambdarank_ndcg: the truncated, normalised lambdarank; rank_xendcg: cross-entropy nDCG (this project's rules, modelled "
+                         "on LightGBM's two built-in ranking objectives)")
     ap.add_argument("--truncation-level", type=int, default=30, help="lambdarank_truncation_level (lambdarank_ndcg only)")
     ap.add_argument("--no-norm", action="store_true", help="lambdarank_norm=False (lambdarank_ndcg only)")
     ap.add_argument("--sigmoid", type=float, default=1.0, help="the sigmoid's steepness (lambdarank_ndcg only)")
+    ap.add_argument("--objective-seed", type=int, default=5, help="the seed of the uniforms rank_xendcg draws every round (rank_xendcg only)")
     ap.add_argument("--rounds", type=int, default=100)
     ap.add_argument("--num-leaves", type=int, default=31)
     ap.add_argument("--learning-rate", type=float, default=0.1)
@@ -86,6 +89,7 @@ def main():
               "grow_policy": args.grow_policy, "bagging_fraction": args.bagging_fraction, "bagging_freq": args.bagging_freq,
               "bagging_by_query": args.by_query, "data_sample_strategy": "goss" if args.goss else "bagging",
               "lambdarank_truncation_level": args.truncation_level, "lambdarank_norm": not args.no_norm, "sigmoid": args.sigmoid,
+              "objective_seed": args.objective_seed,
               "categorical_feature": cats}
     if args.monotone:
         mono = [0] * train[0].shape[1]

@@ -70,7 +70,7 @@ def main():
     _, labels, _, qoff = parse_letor_file(args.train)
     group = np.diff(qoff)
     assert len(labels) < 2 ** 24, "the score table is indexed through a float32 feature"
-    if args.objective == "lambdarank_ndcg":                       # its weight and its Hessian are part of the rule: --weighting does not apply
+    if args.objective in ("lambdarank_ndcg", "rank_xendcg"):      # the weight and the Hessian are part of the rule: --weighting does not apply
         obj = pa.TreeObjective(labels, group, args.objective)
     else:
         obj = pa.TreeObjective(labels, group, args.objective, weighting=None if args.weighting == "none" else args.weighting, hessian="sum")

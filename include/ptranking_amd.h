@@ -325,7 +325,35 @@ int ptr_ndeval_measures(const float *preds, const float *rele, const int32_t *le
  *   A NaN score or label: NaN on every document of that list and of no other.  A launched query longer than max_len: NaN, as above.
  *   norm: 0 is off, any other value is on.  PTR_ERR_INVALID_ARG as above, and for truncation_level < 1 or a sigmoid that is not > 0 (NaN
  *   included).  No atomics, nothing of size n x n; every sum has an order that depends on the query alone (each document's partners in rank
- *   order; maxDCG and S by a halving tree over n).  LDS per query: 28 round_up(max_len, 4) bytes, 112 KiB at 4096 documents. */
+ *   order; maxDCG and S by a halving tree over n).  LDS per query: 28 round_up(max_len, 4) bytes, 112 KiB at 4096 documents.
+ *
+ * ptr_tree_xendcg_grad_hess (ADDITIVE to ABI v8: PTR_ABI_VERSION stays 8) is the cross-entropy nDCG objective (Bruch, "An Alternative Cross
+ * Entropy Loss for Learning-to-Rank"), LightGBM's second built-in ranking objective, objective='rank_xendcg'.  The rule below is THIS
+ * PROJECT'S OWN, modelled on LightGBM's RankXENDCG; LightGBM is not available where this library is built and tested, the rule is compared
+ * with nothing of LightGBM's, and no parity with it is claimed (its random stream in particular is not reproduced).  Same ragged layout,
+ * `queries` subset list, max_len contract and forms as above.  It costs O(n) per query.  For one query of n documents, scores s, labels
+ * y >= 0 and one uniform u_i in [0, 1) per document:
+ *   1. n <= 1: grad = hess = 0 exactly.
+ *   2. rho_i = exp(s_i - max s) / Z, Z the sum of the numerators (the softmax of ptr_tree_listnet_grad_hess, by the same code).
+ *   3. phi_i = 2^{y_i} - u_i (> 0, since u_i < 1); P = sum_j phi_j.
+ *   4. q_i = max(1 - rho_i, 2^-20).  The floor is this project's addition: LightGBM divides by 1 - rho unguarded and returns inf / NaN when
+ *      one document holds all of the softmax mass in fp32.  With the floor every output is finite for finite inputs.
+ *   5. First order:  a_i = rho_i - phi_i / P,  x_i = a_i / q_i,  A = sum_i x_i.
+ *   6. Second order: b_i = rho_i (A - x_i),    z_i = b_i / q_i,  Bs = sum_i z_i.
+ *   7. Third order:  c_i = rho_i (Bs - z_i).
+ *   8. grad_i = (a_i + b_i) + c_i;  hess_i = rho_i (1 - rho_i), UNFLOORED, never negative.
+ *   Edge rules: a NaN score or label, a negative label, or a supplied uniform outside [0, 1) (NaN included) gives NaN grad and hess on every
+ *   document of that list — a list of one document included — and of no other list.  A launched query longer than max_len: NaN, as above.
+ *   The uniforms: unif == NULL draws them from the counter stream of ptr_pl_uniforms' hash (csrc/ptr_plhash.h): for the GLOBAL document
+ *   index d = offsets[q] + i, keys = pl_sample_keys(pl_query_keys(seed, draw), hi32(d)) and u = pl_uniform(keys, lo32(d)), a multiple of
+ *   2^-24 in [0, 1).  A document's uniform depends on (seed, draw, d) alone, not on the length class, subset or form that launched its query;
+ *   a caller passes the boosting round as `draw`.  unif != NULL is a device array of one fp32 uniform per document [documents], read in
+ *   place of the stream (seed and draw are then unused).
+ *   Every sum (max, Z, P, A, Bs) is a halving tree over n whose shape depends on n alone: the bits of a list do not depend on the form, the
+ *   launch or the batch around it.  No atomics, nothing of size n x n.  One thread owns document i (strided where the list is longer than
+ *   the group) and keeps rho_i, q_i and its running terms in registers across the three passes.  PTR_ERR_INVALID_ARG as above (`hessian`
+ *   does not exist here), and for draw < 0.  LDS per query: 2 rows (the scores | the tree's row), 8 round_up(max_len, 4) bytes, 32 KiB at
+ *   4096 documents. */
 #define PTR_TREE_PAIRS_ALL 0
 #define PTR_TREE_PAIRS_NOTIES 1
 #define PTR_TREE_PAIRS_NO00 2
@@ -344,6 +372,8 @@ int ptr_tree_listnet_grad_hess(const float *preds, const float *labels, const in
                                int gain_type, int hessian, float *grad, float *hess, void *stream);
 int ptr_tree_lambdarank_ndcg_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries, int nq,
                                        int max_len, int truncation_level, float sigmoid, int norm, float *grad, float *hess, void *stream);
+int ptr_tree_xendcg_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries, int nq,
+                              int max_len, const float *unif, uint64_t seed, int64_t draw, float *grad, float *hess, void *stream);
 
 /* ---- Smooth-rank metric objectives (csrc/smoothmetric.hip).  The symbol below is ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
  * ptr_smoothmetric_fwd_bwd — loss and dLoss/dpreds of precision_ / AP_ / nERR_ / nDCG_as_opt_objective
@@ -989,6 +1019,7 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *   ptr_irfgan_point_sample, ptr_irfgan_pair_sample   L                                   G, queries per workgroup
  *   ptr_irfgan_fwd_bwd                           mode, L                                  G, queries per workgroup
  *   ptr_adlist_sample, ptr_adlist_fwd_bwd        L                                        G, queries per workgroup
+ *   ptr_tree_xendcg_grad_hess                    max_len                                  G, queries per workgroup, documents per thread
  * G: threads per query, DPT: documents per thread, TP: subtopic tile.  PTR_ERR_INVALID_ARG for an entry without a form, another nargs, or
  * nform below the count. */
 int ptr_launch_form(const char *entry, const int64_t *args, int nargs, int32_t *form, int nform);

@@ -4,6 +4,9 @@ user has on the same GPU without it: the closed form of the reference's per_quer
 PADDED [chunk, L, L] tensors, one length class at a time, in chunks that fit a byte budget.
 
     python profiles/prof_tree.py profiles/mi355x_tree_objectives.json
+    python profiles/prof_tree.py --xendcg profiles/mi355x_xendcg.json [kernel_stats.csv]    # rank_xendcg's and ListNet's calls side by side
+        (CALL time: host enqueue included.  kernel_stats.csv: the *_kernel_stats.csv of a run of the same command under
+        `rocprofv3 --kernel-trace --stats`, made first and on its own; its kernel times are folded into the file)
 
 Scenario: QUERIES queries whose lengths follow the mix bench.py's padded batches use (bench.padded_lens, the lengths behind its
 pair_statistics rows): Gamma(2.2) with mean 120, here clipped to MSLR-WEB30K's [1, 1251] instead of a padded L, with four lists of 1251 documents
@@ -33,7 +36,10 @@ CHUNK_BYTES = 1 << 28            # budget of one [chunk, L, L] fp32 intermediate
 REFERENCE_CPU = dict(seconds_per_query=0.085, documents=128, pair_type="All", measured_on="the build machine's CPU, not on the GPU machine",
                      what="ptranking/ltr_tree/util/lightgbm_util.py per_query_gradient_hessian_lambda, numpy 2.2.6")
 VARIANTS = {"ranknet_reference": dict(objective="ranknet"), "lambdarank_reference": dict(objective="lambdarank"),
-            "lambdamart_sum": dict(objective="lambdarank", weighting="DeltaNDCG", hessian="sum"), "listnet": dict(objective="listnet")}
+            "lambdamart_sum": dict(objective="lambdarank", weighting="DeltaNDCG", hessian="sum"), "listnet": dict(objective="listnet"),
+            "rank_xendcg": dict(objective="rank_xendcg")}
+XENDCG_REPS = int(os.environ.get("PROF_XENDCG_REPS", 2000))      # (fewer under a trace, which records every launch)
+# launch sets per timed window of --xendcg (one set: every length class once): windows of ~0.2 s
 
 
 def pair_issue_cycles(weighted):
@@ -119,6 +125,8 @@ def main(out_path):
             for max_len, queries in res.buckets:
                 if obj.kind == "pair":
                     F.tree_pair_grad_hess(p, res.labels, res.offsets, obj.pair_type, obj.weighting, obj.epsilon, obj.hessian, queries, max_len, out)
+                elif obj.kind == "xendcg":
+                    F.tree_xendcg_grad_hess(p, res.labels, res.offsets, obj.objective_seed, 0, None, queries, max_len, out)
                 else:
                     F.tree_listnet_grad_hess(p, res.labels, res.offsets, obj.gain_type, obj.hessian, queries, max_len, out)
         kern, _ = events(launches)
@@ -208,5 +216,94 @@ def main(out_path):
     print(f"wrote {out_path}")
 
 
+def kernel_stats(path, launches_per_set):
+    """Kernel time per launch set from rocprofv3's kernel statistics of a run of main_xendcg, however many sets it made: the instances of
+    each kernel template summed, over its launches / launches_per_set."""
+    import csv
+    out = {}
+    with open(path, newline="") as f:
+        for row in csv.DictReader(f):
+            name = row.get("Name") or row.get("KernelName") or ""
+            for key, kern in (("listnet", "tree_listnet_kernel"), ("rank_xendcg", "tree_xendcg_kernel")):
+                if kern in name:
+                    o = out.setdefault(key, dict(kernel=kern, launches=0, total_ns=0.0))
+                    o["launches"] += int(float(row["Calls"]))
+                    o["total_ns"] += float(row["TotalDurationNs"])
+    for o in out.values():
+        o["kernel_ms_per_launch_set"] = o["total_ns"] * 1e-6 / (o["launches"] / launches_per_set)
+    return out
+
+
+def main_xendcg(out_path, stats_path=None):
+    """rank_xendcg's calls against ListNet's on the same batch, at the same commit: both are a softmax per query; rank_xendcg reads the
+    same 8 bytes and writes the same 8 bytes per document, hashes a uniform and does three more tree sums.  A timed window is XENDCG_REPS
+    launch sets between two device events; ROUNDS windows per objective, alternating; every window kept.  What the events bracket is CALL
+    time: six short launches per set, each entered through Python and ctypes, so the host's enqueue is in it.  Kernel time comes from a
+    trace (kernel_stats)."""
+    import numpy as np
+    import torch
+    import ptranking_amd as pa
+    import ptranking_amd.functional as F
+
+    assert torch.cuda.is_available(), "prof_tree.py measures on the GPU only"
+    dev = torch.device("cuda:0")
+    preds, labels, group = draw()
+    res = pa.TreeObjective(labels, group, "rank_xendcg")._own
+    p = torch.from_numpy(preds).to(dev)
+    out = (torch.empty_like(p), torch.empty_like(p))
+
+    def listnet():
+        for max_len, queries in res.buckets:
+            F.tree_listnet_grad_hess(p, res.labels, res.offsets, "Power", "reference", queries, max_len, out)
+
+    def xendcg():
+        for max_len, queries in res.buckets:
+            F.tree_xendcg_grad_hess(p, res.labels, res.offsets, 5, 0, None, queries, max_len, out)
+
+    def window(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(XENDCG_REPS):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / XENDCG_REPS
+
+    fns = {"listnet": listnet, "rank_xendcg": xendcg}
+    for fn in fns.values():
+        window(fn)
+    rounds = {k: [] for k in fns}
+    for _ in range(ROUNDS):
+        for k, fn in fns.items():
+            rounds[k].append(window(fn))
+    docs = int(group.sum())
+    rows = {}
+    for k, v in rounds.items():
+        med = statistics.median(v)
+        rows[k] = dict(call_median_ms_per_launch_set=med, call_all_windows_ms=v)
+        print(json.dumps({"variant": k, "call_median_ms_per_launch_set": med}), flush=True)
+    ratio = rows["rank_xendcg"]["call_median_ms_per_launch_set"] / rows["listnet"]["call_median_ms_per_launch_set"]
+    trace = None
+    if stats_path:
+        trace = kernel_stats(stats_path, len(res.buckets))
+        trace["rank_xendcg_over_listnet"] = trace["rank_xendcg"]["kernel_ms_per_launch_set"] / trace["listnet"]["kernel_ms_per_launch_set"]
+        print(json.dumps({"kernel_trace": trace}), flush=True)
+    with open(out_path, "w") as f:
+        json.dump(dict(device=torch.cuda.get_device_name(0), torch=torch.__version__,
+                       scenario=dict(queries=QUERIES, documents=docs, longest=int(group.max()), mean_len=float(group.mean()),
+                                     length_classes=[(m, len(i)) for m, i in res.buckets_host], launches_per_set=len(res.buckets),
+                                     sets_per_window=XENDCG_REPS, windows=ROUNDS,
+                                     bytes_per_document=16,
+                                     what="CALL time: device events around XENDCG_REPS launch sets (one launch per length class), host "
+                                          "enqueue through Python and ctypes included; kernel_trace: kernel time from rocprofv3 "
+                                          "--kernel-trace --stats in a run of its own, summed over each kernel's instances"),
+                       variants=rows, call_rank_xendcg_over_listnet=ratio, kernel_trace=trace), f, indent=1)
+        f.write("\n")
+    print(f"call time: rank_xendcg / listnet = {ratio:.3f}; wrote {out_path}")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--xendcg":
+        main_xendcg(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "mi355x_xendcg.json"), sys.argv[3] if len(sys.argv) > 3 else None)
+        sys.exit(0)
     main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "mi355x_tree_objectives.json"))

@@ -42,6 +42,7 @@ SIGNATURES = {
     "ptr_tree_pair_grad_hess": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp],
     "ptr_tree_listnet_grad_hess": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "ptr_tree_lambdarank_ndcg_grad_hess": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp],
+    "ptr_tree_xendcg_grad_hess": [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _u64, C.c_int64, _vp, _vp, _vp],
     "ptr_smoothmetric_fwd_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ptr_gaussmetric_fwd_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ptr_pl_uniforms": [_i, _i, _i, _u64, C.c_int64, _vp, _vp],

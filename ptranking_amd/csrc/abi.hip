@@ -95,6 +95,7 @@ static const FormQuery kFormQueries[] = {
     {"ptr_irfgan_fwd_bwd", 2, 2, [](const int64_t *a, int32_t *out) { put(out, irfgan_loss_form((int)a[0], (int)a[1])); }},
     {"ptr_adlist_sample", 1, 2, [](const int64_t *a, int32_t *out) { put(out, adlist_form((int)a[0])); }},
     {"ptr_adlist_fwd_bwd", 1, 2, [](const int64_t *a, int32_t *out) { put(out, adlist_form((int)a[0])); }},
+    {"ptr_tree_xendcg_grad_hess", 1, 3, [](const int64_t *a, int32_t *out) { put(out, tree_form((int)a[0])); }},
 };
 
 }  // namespace ptr

@@ -145,6 +145,14 @@ IrganForm adlist_form(int L);                            // adlist.hip: the list
 VecForm listmle_form(int L, bool aligned);
 VecForm lambdaloss_form(int L, int k, int loss_type, int presort, bool aligned);          // lambdaloss.hip: vec = top-k; else (G, DPT) in (G, V)
 Tiling wassrank_form(int L);                                                              // wassrank.hip
+// The tree frame's ragged kernels (tree.hip), by the longest launched list: G threads per query (16 up to 16 documents, pick_tiling's
+// beyond), kBlock / G queries per workgroup, and the documents one thread owns in the kernels that keep them in registers (pick_tiling's
+// DPT: G * DPT covers the launch's longest list)
+struct TreeForm { int G; int QPB; int DPT; };
+inline TreeForm tree_form(int max_len) {
+    const Tiling t = max_len <= 16 ? Tiling{16, 1} : pick_tiling(max_len);
+    return {t.G, kBlock / t.G, t.DPT};
+}
 
 // Grid of a PERSISTENT kernel (its wavefronts walk the work with a grid stride): the blocks the device keeps resident at once — CUs x the
 // occupancy of `kernel` at `block` threads and `lds` bytes of dynamic LDS — capped by the blocks the work needs.  Cached per kernel.

@@ -30,8 +30,9 @@
 //   G = 256  n <= 4096    one workgroup per query (PTR_MAX_LIST_LEN)
 // The host buckets its queries by length class once and launches each class through the `queries` index list (ptranking_amd/tree.py).
 // LDS per query: K rows of round_up(max_len, 4) floats — scores | labels | (normalised) gains | discounts; K = 2 (no weights), 3 (DeltaGain),
-// 4 (DeltaNDCG): at most 16 round_up(n, 4) bytes.  ListNet: scores | gains | the tree's row.
+// 4 (DeltaNDCG): at most 16 round_up(n, 4) bytes.  ListNet: scores | gains | the tree's row.  XE-nDCG: scores | the tree's row.
 #include "ptr_device.h"
+#include "ptr_plhash.h"
 
 namespace ptr {
 
@@ -54,6 +55,19 @@ template <int G, class Op> __device__ __forceinline__ void group_tree(float *x, 
         m = h;
         group_sync<G>();
     }
+}
+
+// Max and normaliser of the softmax of row[0 .. n) (_softmax, lightgbm_util.py:5-11), both by the tree over the scratch row T; every thread of
+// the group gets the same two values.  Starts with a group barrier; the caller passes another before it writes T again.
+template <int G> __device__ __forceinline__ void softmax_parts(const float *row, float *T, int n, int t, float &mx, float &z) {
+    group_sync<G>();
+    for (int i = t; i < n; i += G) T[i] = row[i];
+    group_tree<G>(T, n, t, [](float a, float b) { return fmaxf(a, b); });
+    mx = n > 0 ? T[0] : 0.0f;
+    group_sync<G>();
+    for (int i = t; i < n; i += G) T[i] = expf(row[i] - mx);
+    group_tree<G>(T, n, t, [](float a, float b) { return a + b; });
+    z = n > 0 ? T[0] : 1.0f;
 }
 
 // The query of this group: its first document and its length.  A query longer than the launch's max_len (the caller's error: the LDS rows
@@ -200,24 +214,97 @@ tree_listnet_kernel(const float *__restrict__ preds, const float *__restrict__ l
     }
     const bool nanq = group_any<G>(bad, tid);
 
-    // max and normaliser of one row (_softmax, :5-11), both by the tree; every thread of the group gets the same two values
-    auto softmax_parts = [&](const float *row, float &mx, float &z) {
-        group_sync<G>();
-        for (int i = t; i < n; i += G) T[i] = row[i];
-        group_tree<G>(T, n, t, [](float a, float b) { return fmaxf(a, b); });
-        mx = n > 0 ? T[0] : 0.0f;
-        group_sync<G>();
-        for (int i = t; i < n; i += G) T[i] = expf(row[i] - mx);
-        group_tree<G>(T, n, t, [](float a, float b) { return a + b; });
-        z = n > 0 ? T[0] : 1.0f;
-    };
     float ms, zs, my, zy;
-    softmax_parts(S, ms, zs);
-    softmax_parts(Y, my, zy);
+    softmax_parts<G>(S, T, n, t, ms, zs);
+    softmax_parts<G>(Y, T, n, t, my, zy);
     for (int i = t; i < n; i += G) {
         const float pp = expf(S[i] - ms) / zs, pt = expf(Y[i] - my) / zy;
         grad[base + i] = nanq ? NAN : pp - pt;
         hess[base + i] = const_hess ? 1.0f : (nanq ? NAN : pp * (1.0f - pp));
+    }
+}
+
+// ---- Cross-entropy nDCG, LightGBM's rank_xendcg (ptr_tree_xendcg_grad_hess; include/ptranking_amd.h states the rule).  The rule is this
+// project's own, written after LightGBM's RankXENDCG; nothing here is compared with LightGBM.  O(n) per query: a softmax and three more
+// tree sums (P, A, Bs).  LDS per query: 2 rows of Lp words (scores | the tree's row): 32 KiB at 4096 documents.  A thread owns the documents
+// t, t + G, ... (at most K of them: tree_form gives the launch the smallest K in 1, 2, 4, 8, 16 that covers its longest list, so the
+// length classes of the host each get a kernel without idle slots) and keeps rho, q and the running terms of each in registers across
+// the three passes.  Neither G nor K touches a result: every sum is a tree over n.
+constexpr float kXeFloor = 0x1p-20f;               // the floor of 1 - rho
+
+// sum of v over the documents of the group, by the tree over T; every thread gets the same value
+template <int G, int K> __device__ __forceinline__ float owned_sum(float *T, const float (&v)[K], int n, int t) {
+    group_sync<G>();                                // the readers of the previous T[0] are done
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if (t + k * G < n) T[t + k * G] = v[k];
+    group_tree<G>(T, n, t, [](float a, float b) { return a + b; });
+    return n > 0 ? T[0] : 0.0f;
+}
+
+template <int G, int K>
+__global__ void __launch_bounds__(kBlock)
+tree_xendcg_kernel(const float *__restrict__ preds, const float *__restrict__ labels, const int64_t *__restrict__ offsets, int B,
+                   const int32_t *__restrict__ queries, int nq, int Lp, int max_len, const float *__restrict__ unif, uint64_t seed,
+                   int64_t draw, float *__restrict__ grad, float *__restrict__ hess) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, grp = tid / G, t = tid % G;
+    const TreeQuery qu = tree_query<G>(offsets, B, queries, nq, max_len, t, grad, hess);
+    const int64_t base = qu.base;
+    const int n = G >= kWave ? __builtin_amdgcn_readfirstlane(qu.n) : qu.n;
+    float *S = smem + (size_t)grp * 2 * Lp, *T = S + Lp;
+
+    // ---- stage the scores; phi = 2^y - u from the label and the document's uniform (its global index keys the stream)
+    const PlKeys round_keys = pl_query_keys(seed, draw);
+    float rho[K], q[K], g[K], v[K];
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int i = t + k * G;
+        v[k] = 0.0f;
+        if (i < n) {
+            const uint64_t d = (uint64_t)(base + i);
+            const float s = preds[base + i], y = labels[base + i];
+            const float u = unif ? unif[base + i] : pl_uniform(pl_sample_keys(round_keys, (uint32_t)(d >> 32)), (uint32_t)d);
+            S[i] = s;
+            v[k] = exp2f(y) - u;
+            bad |= s != s || !(y >= 0.0f) || !(u >= 0.0f && u < 1.0f);
+        }
+    }
+    // a NaN score or label, a negative label or a uniform outside [0, 1): NaN on every document of this list, and of no other
+    const bool nanq = group_any<G>(bad, tid);
+
+    float ms, zs;
+    softmax_parts<G>(S, T, n, t, ms, zs);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int i = t + k * G;
+        rho[k] = i < n ? expf(S[i] - ms) / zs : 0.0f;
+        q[k] = fmaxf(1.0f - rho[k], kXeFloor);
+    }
+    const float P = owned_sum<G, K>(T, v, n, t);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {                   // first order
+        g[k] = rho[k] - v[k] / P;
+        v[k] = g[k] / q[k];
+    }
+    const float A = owned_sum<G, K>(T, v, n, t);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {                   // second order
+        const float b = rho[k] * (A - v[k]);
+        g[k] += b;
+        v[k] = b / q[k];
+    }
+    const float Bs = owned_sum<G, K>(T, v, n, t);
+    const bool one = n <= 1;                        // exactly 0
+#pragma unroll
+    for (int k = 0; k < K; ++k) {                   // third order
+        const int i = t + k * G;
+        if (i < n) {
+            const float c = rho[k] * (Bs - v[k]);
+            grad[base + i] = nanq ? NAN : one ? 0.0f : g[k] + c;
+            hess[base + i] = nanq ? NAN : one ? 0.0f : rho[k] * (1.0f - rho[k]);
+        }
     }
 }
 
@@ -453,4 +540,23 @@ extern "C" int ptr_tree_lambdarank_ndcg_grad_hess(const float *preds, const floa
         return launch_queries(tree_lambdarank_ndcg_kernel<G>, nq, kBlock / G, kBlock, lds, stream, who, preds, labels, offsets, B, queries, nq, Lp,
                               max_len, truncation_level, sigmoid, norm, grad, hess);
     });
+}
+
+extern "C" int ptr_tree_xendcg_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries, int nq,
+                                         int max_len, const float *unif, uint64_t seed, int64_t draw, float *grad, float *hess, void *stream) {
+    using namespace ptr;
+    const char *who = "ptr_tree_xendcg_grad_hess";
+    if (int rc = tree_check(preds, labels, offsets, B, queries, nq, max_len, PTR_TREE_HESS_SUM, grad, hess, who)) return rc;
+    if (draw < 0) { set_error("%s: draw must be >= 0 (got %lld)", who, (long long)draw); return PTR_ERR_INVALID_ARG; }
+    if (int rc = tree_check_len(max_len, who)) return rc;
+    if (nq == 0 || max_len == 0) return 0;
+    const int Lp = round_up(max_len, 4);
+    auto go = [&]<int G, int K>() {
+        static_assert(G * K <= PTR_MAX_LIST_LEN);
+        const size_t lds = (size_t)(kBlock / G) * 2 * Lp * sizeof(float);
+        return launch_queries(tree_xendcg_kernel<G, K>, nq, kBlock / G, kBlock, lds, stream, who, preds, labels, offsets, B, queries, nq, Lp, max_len,
+                              unif, seed, draw, grad, hess);
+    };
+    // tree_form: sixteen queries per workgroup up to 16 documents, pick_tiling's (G, documents per thread) beyond
+    return max_len <= 16 ? go.template operator()<16, 1>() : dispatch_tiling(max_len, go);
 }

@@ -16,7 +16,7 @@ from . import _lib
 
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
-           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "ndeval_measures", "div_ideal_order", "NDEVAL_MEASURES","divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "tree_lambdarank_ndcg_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
+           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "ndeval_measures", "div_ideal_order", "NDEVAL_MEASURES","divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "tree_lambdarank_ndcg_grad_hess", "tree_xendcg_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
            "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "gaussian_metric_objective", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS",
            "irgan_uniforms", "irgan_sample", "irgan_point_generator", "irgan_selected", "IRGAN_SAMPLE_MODES", "IRGAN_SELECTED_MODES", "IRGAN_MAX_SAMPLES",
            "irfgan_uniforms", "irfgan_point_sample", "irfgan_pair_sample", "IRFGAN_MODES", "F_DIVERGENCES",
@@ -916,6 +916,35 @@ def tree_lambdarank_ndcg_grad_hess(preds, labels, offsets, truncation_level=30, 
     Arguments and layout as tree_pair_grad_hess."""
     t, sigma, norm = lambdarank_ndcg_settings(truncation_level, sigmoid, norm)
     return _ragged("ptr_tree_lambdarank_ndcg_grad_hess", preds, labels, offsets, queries, max_len, out, min(t, 2 ** 31 - 1), C.c_float(sigma), int(norm))
+
+
+def _count(name, v, top=2 ** 63 - 1):
+    """A non-negative integer setting (no bool, no fraction) -> int."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= v <= top or int(v) != v:
+        raise ValueError(f"{name} must be an integer in 0 .. {top}, got {v!r}")
+    return int(v)
+
+
+def objective_seed(seed=5):
+    """The seed of rank_xendcg's uniforms, validated -> a non-negative int below 2^64 (LightGBM's objective_seed, default 5)."""
+    return _count("objective_seed", seed, 2 ** 64 - 1)
+
+
+def tree_xendcg_grad_hess(preds, labels, offsets, seed=5, draw=0, unif=None, queries=None, max_len=None, out=None):
+    """Gradient and Hessian per document of the cross-entropy nDCG objective (LightGBM's objective='rank_xendcg') over LightGBM's ragged
+    layout, in one launch that costs O(n) per query (ptr_tree_xendcg_grad_hess; include/ptranking_amd.h states the rule in full).  The rule
+    is this project's own, modelled on LightGBM's RankXENDCG; it is compared with nothing of LightGBM's.  With rho = softmax(preds) per
+    query, phi = 2^label - u and q = max(1 - rho, 2^-20):  a = rho - phi / sum phi,  b = rho (A - a / q) with A = sum a / q,
+    c = rho (Bs - b / q) with Bs = sum b / q,  grad = a + b + c,  hess = rho (1 - rho).  One uniform u in [0, 1) per document comes from
+    the counter stream keyed by (seed, draw, the document's global index) — pass the boosting round as `draw` — or from `unif`, a float32
+    [documents] tensor that replaces the stream.  A list of one document is exactly 0; a NaN score or label, a negative label or a uniform
+    outside [0, 1) gives NaN on that list alone.  Arguments and layout as tree_pair_grad_hess."""
+    seed, draw = objective_seed(seed), _count("draw", draw)
+    if unif is not None:
+        unif = _check("unif", unif, shape=_check("preds", preds).shape)
+        if unif.device != preds.device:
+            raise RuntimeError("preds and unif live on different devices")
+    return _ragged("ptr_tree_xendcg_grad_hess", preds, labels, offsets, queries, max_len, out, _lib.ptr(unif), _seed64(seed), C.c_int64(draw))
 
 
 def shuffle_ties_order(labels, seed, lens=None):

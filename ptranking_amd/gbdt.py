@@ -11,7 +11,7 @@ LightGBM itself, the quantile binning rule for features of more distinct values 
     GBDT(params)       the booster: fit_bins(X) bins the features once and keeps them resident; update(grad, hess) grows ONE tree (leaf-wise, or
                         depth-wise under grow_policy='depthwise') from device gradients and adds its leaf values to the resident training scores; predict / save_model / load_model
     LambdaMART(params)  the ranker: every round computes the gradient and the Hessian per document with tree_pair_grad_hess /
-                        tree_listnet_grad_hess / tree_lambdarank_ndcg_grad_hess on the resident scores (no host copy), quantizes them and calls update
+                        tree_listnet_grad_hess / tree_lambdarank_ndcg_grad_hess / tree_xendcg_grad_hess on the resident scores (no host copy), quantizes them and calls update
 
 Growth policies (grow_policy): 'leafwise', the default, splits the leaf of the largest gain and reads the two children's records back after
 every split; 'depthwise' splits ALL leaves of a level in one batched pass (partition, histograms of the smaller children, sibling
@@ -51,6 +51,18 @@ log2(1 + S) / S, S = 2 sum lam.  The three settings come from the parameter dict
 booster ignore them.  The key 'objective' of the dict stays ignored (the objective is LambdaMART's argument, and its default stays
 'lambdarank', the reference's CUSTOM all-pairs objective), and label_gain stays unknown (the gain is 2^y - 1).  A model file written before
 the three keys existed loads with their defaults.
+
+Cross-entropy nDCG: LambdaMART(objective='rank_xendcg'), LightGBM's other built-in ranking objective (Bruch, "An Alternative Cross Entropy
+Loss for Learning-to-Rank"): O(n) per query where lambdarank costs O(n T).  The rule is this project's own, modelled on LightGBM's
+RankXENDCG, stated in include/ptranking_amd.h and restated in tests/xendcg_ref.py; it is compared with nothing of LightGBM's and no parity is
+claimed (its random stream in particular is not LightGBM's).  rho = softmax(scores) per query, phi = 2^y - u with one uniform u in [0, 1)
+per document and round, q = max(1 - rho, 2^-20) (the floor is this project's addition: LightGBM divides by 1 - rho unguarded; here every
+output is finite); a = rho - phi / sum phi, b = rho (A - a / q), c = rho (Bs - b / q) with A = sum a / q, Bs = sum b / q; grad = a + b + c,
+hess = rho (1 - rho).  The uniforms come from the counter stream bagging uses, keyed by (objective_seed, the tree counter, the document's
+row): objective_seed (5, LightGBM's name and default) is read by this objective alone, round t draws with draw = t = the trees grown so
+far, so a fit continued through init_model goes on in the stream where the first fit stopped and equals the unsplit fit bit for bit, and
+refit re-estimates tree t under draw t.  weighting, hessian, pair_type, epsilon and gain_type do not apply.  A model file written before
+the key existed loads with the default.
 
 Categorical features (categorical_feature, a list of 0-based column indices; cat_smooth, default 10.0; LightGBM's names).  Such a column
 holds integer codes in 0 .. max_bin - 1 (bin_edges maps code c to bin c), and a node on it sends a SET of codes left.  The rules are
@@ -133,7 +145,8 @@ DEFAULT_PARAMS = {"learning_rate": 0.1, "num_leaves": 31, "num_trees": 100, "min
                   "top_rate": 0.2, "other_rate": 0.1, "use_missing": False, "categorical_feature": (), "cat_smooth": 10.0,
                   "monotone_constraints": (), "monotone_constraints_method": "basic", "interaction_constraints": (),
                   # LambdaMART(objective='lambdarank_ndcg') alone reads these three; the other objectives and the bare booster ignore them
-                  "lambdarank_truncation_level": 30, "lambdarank_norm": True, "sigmoid": 1.0}
+                  "lambdarank_truncation_level": 30, "lambdarank_norm": True, "sigmoid": 1.0,
+                  "objective_seed": 5}                    # LambdaMART(objective='rank_xendcg') alone reads it
 IGNORED_PARAMS = ("num_threads", "verbosity", "metric", "boosting_type", "objective", "eval_at")    # accepted, without a meaning here
 MODEL_FORMAT = 1                       # a model trained without use_missing
 MODEL_FORMAT_MISSING = 2               # one trained under it: format 1 with default_left per node and nan_bin per feature
@@ -207,6 +220,7 @@ def _params(params):
     p["interaction_constraints"] = _interaction(p["interaction_constraints"])
     p["lambdarank_truncation_level"], p["sigmoid"], p["lambdarank_norm"] = F.lambdarank_ndcg_settings(p["lambdarank_truncation_level"], p["sigmoid"],
                                                                                                    p["lambdarank_norm"])
+    p["objective_seed"] = F.objective_seed(p["objective_seed"])
     return p
 
 
@@ -1196,11 +1210,12 @@ class GBDT:
         return F.gbdt_predict_cat(Xd, sub["feature"], sub["threshold"], sub["left"], sub["right"], val, offs, self._is_cat_d,
                                   up(np.where(ci >= 0, ci - first, -1).astype(np.int32)), up(sets), default_left=sub.get("default_left"))
 
-    def refit(self, X, grad_hess, decay_rate=0.9):
+    def refit(self, X, grad_hess, decay_rate=0.9, with_tree=False):
         """Keeps the tree structures and re-estimates the leaf values on new data (LightGBM's Booster.refit; the rule is this project's own
         and no parity is claimed) -> a NEW booster with the same structures, edges and parameters and its own value arrays; self is
         untouched.  X: raw rows [n, F] as predict takes them; grad_hess(scores) -> device fp32 (grad, hess) [n] at the running scores, which
-        start at zero.  Per tree, in order: grad_hess, gbdt_quantize (a NaN or an infinity raises, as in update), gbdt_leaf_sums over the
+        start at zero (with_tree=True: grad_hess(scores, t) with t the index of the tree whose values are re-estimated next, for an
+        objective that draws per round).  Per tree, in order: grad_hess, gbdt_quantize (a NaN or an infinity raises, as in update), gbdt_leaf_sums over the
         tree, ONE host read of the sums (host_reads grows by one per tree), refit_value per leaf on the host
         (float32(decay_rate * old + (1 - decay_rate) * new), new = -G / (H + lambda_l2) * learning_rate; a leaf no row reaches or one with
         H + lambda_l2 <= 0 keeps old), gbdt_add_by_leaf with the new values.  The trees are those predict uses by default (up to
@@ -1236,7 +1251,7 @@ class GBDT:
         sums = torch.zeros((max([t["value"].size for t in new.trees], default=1), 3), device=dev, dtype=torch.int64)
         offs = np.concatenate([[0], np.cumsum([t["feature"].size for t in new.trees])]).astype(np.int64)
         for ti, t in enumerate(new.trees):
-            grad, hess = grad_hess(scores)
+            grad, hess = grad_hess(scores, ti) if with_tree else grad_hess(scores)
             F.gbdt_quantize(grad, hess, flag=flag, out=(qg, qh, expo))
             lo, hi, nl = int(offs[ti]), int(offs[ti + 1]), t["value"].size
             cells = sums[:nl]
@@ -1321,7 +1336,9 @@ class LambdaMART:
     low-ranked documents, so leaves can stay unsplittable under the Hessian floor of the split scan.
     objective 'lambdarank_ndcg' is the truncated, normalised lambdarank of the module docstring: it reads lambdarank_truncation_level,
     lambdarank_norm and sigmoid from params, and weighting, hessian, pair_type, epsilon and gain_type do not apply to it (a non-default
-    value raises ValueError)."""
+    value raises ValueError).
+    objective 'rank_xendcg' is the cross-entropy nDCG objective of the module docstring: it reads objective_seed from params, draws round
+    t's uniforms under draw = t (the tree counter), and the same five settings do not apply to it."""
 
     def __init__(self, params=None, objective="lambdarank", weighting="DeltaNDCG", hessian="sum", pair_type=None, epsilon=1.0,
                  gain_type="Power", device=None):
@@ -1336,7 +1353,7 @@ class LambdaMART:
         if self.kind == "pair":
             F._enum("pair_type", self.pair_type, F.TREE_PAIR_TYPES)
             F._enum("weighting", self.weighting, F.TREE_WEIGHTINGS)
-        elif self.kind == "lambdarank_ndcg":
+        elif self.kind in ("lambdarank_ndcg", "xendcg"):
             tree.not_applicable(objective, dict(weighting=weighting, hessian=hessian, pair_type=pair_type, epsilon=epsilon, gain_type=gain_type),
                                 dict(weighting="DeltaNDCG", hessian="sum", pair_type=None, epsilon=1.0, gain_type="Power"))
         else:
@@ -1349,9 +1366,9 @@ class LambdaMART:
         self.evals_result = []
         self.best_iteration = self.best_score = None
 
-    def grad_hess(self, scores, res, out=None):
+    def grad_hess(self, scores, res, out=None, draw=0):
         """The round's gradient and Hessian per document, on the device: one launch per length class of tree.bucket_queries, exactly as
-        TreeObjective._run launches them."""
+        TreeObjective._run launches them.  draw: the round whose uniforms 'rank_xendcg' draws (the other objectives ignore it)."""
         out = (torch.empty_like(scores), torch.empty_like(scores)) if out is None else out
         for max_len, queries in res.buckets:
             if self.kind == "pair":
@@ -1360,6 +1377,8 @@ class LambdaMART:
                 p = self.params
                 F.tree_lambdarank_ndcg_grad_hess(scores, res.labels, res.offsets, p["lambdarank_truncation_level"], p["sigmoid"], p["lambdarank_norm"],
                                                  queries, max_len, out)
+            elif self.kind == "xendcg":
+                F.tree_xendcg_grad_hess(scores, res.labels, res.offsets, self.params["objective_seed"], draw, None, queries, max_len, out)
             else:
                 F.tree_listnet_grad_hess(scores, res.labels, res.offsets, self.gain_type, self.hessian, queries, max_len, out)
         return out
@@ -1417,7 +1436,7 @@ class LambdaMART:
             raise ValueError("early_stopping_rounds needs an eval_set")
         gh = (torch.empty_like(self.booster.scores), torch.empty_like(self.booster.scores))
         for it in range(base + 1, base + rounds + 1):
-            self.grad_hess(self.booster.scores, res, gh)
+            self.grad_hess(self.booster.scores, res, gh, draw=len(self.booster.trees))      # the tree counter, as bagging's draws
             self.booster.update(*gh)
             if valid is None:
                 continue
@@ -1458,7 +1477,7 @@ class LambdaMART:
             raise ValueError(f"X holds {np.shape(X)[0]} rows, the groups {res.n_docs}")
         gh = (torch.empty(res.n_docs, device=self.device, dtype=torch.float32), torch.empty(res.n_docs, device=self.device, dtype=torch.float32))
         new = copy.copy(self)
-        new.booster = self.booster.refit(X, lambda scores: self.grad_hess(scores, res, gh), decay)
+        new.booster = self.booster.refit(X, lambda scores, t: self.grad_hess(scores, res, gh, draw=t), decay, with_tree=True)      # tree t under draw t
         new.evals_result, new.best_iteration, new.best_score = [], None, None
         return new
 

@@ -23,6 +23,14 @@ own, modelled on LightGBM's LambdarankNDCG and compared with nothing of LightGBM
 the labels differ and one of its documents ranks in the first truncation_level; its weight is the Delta-nDCG against maxDCG@truncation_level,
 divided by 0.01 + |score difference| under norm; under norm a query's results are scaled by log2(1 + S) / S, S = 2 sum lam.  Its Hessian is
 never negative, and a list without a relevant document is exactly 0 where weighting='DeltaNDCG' gives NaN.
+
+objective='rank_xendcg' is LightGBM's second built-in ranking objective, the cross-entropy nDCG loss of Bruch ("An Alternative Cross Entropy
+Loss for Learning-to-Rank"), which costs O(n) per query where lambdarank costs O(n T).  Again the rule is this project's own, modelled on
+LightGBM's RankXENDCG and compared with nothing of LightGBM's (include/ptranking_amd.h states it): rho = softmax(scores), phi = 2^y - u with
+one uniform u per document and round, q = max(1 - rho, 2^-20) (the floor is this project's addition: every output is finite);
+a = rho - phi / sum phi, b = rho (A - a / q), c = rho (Bs - b / q) with A = sum a / q and Bs = sum b / q; grad = a + b + c and
+hess = rho (1 - rho).  The uniforms come from a counter stream keyed by (objective_seed, draw, the document's index): TreeObjective counts
+its calls in .draw, LightGBM calls the objective once per round, so two objects with one seed replay the same rounds bit for bit.
 """
 import weakref
 
@@ -41,7 +49,8 @@ __all__ = ["TreeObjective", "bucket_queries", "LENGTH_CLASSES", "OBJECTIVES", "l
 LENGTH_CLASSES = (16, 128, 256, 512, 1024, 2048, _lib.MAX_LIST_LEN)
 # objective -> (kind, default pair_type): what the reference's wrappers pass (lightgbm_util.py:203-204, :262-264, :351-352)
 OBJECTIVES = {"ranknet": ("pair", "All"), "lambdarank": ("pair", "NoTies"), "listnet": ("listnet", None),
-              "lambdarank_ndcg": ("lambdarank_ndcg", None)}           # the truncated, normalised lambdarank: no wrapper of the reference's
+              "lambdarank_ndcg": ("lambdarank_ndcg", None),           # the truncated, normalised lambdarank: no wrapper of the reference's
+              "rank_xendcg": ("xendcg", None)}                         # cross-entropy nDCG, LightGBM's other built-in: likewise
 
 FIRST_ORDER = False            # lightgbm_util.py:75: True makes the drop-in functions return the constant Hessian
 CONSTANT_HESSIAN = 1.0         # lightgbm_util.py:76 (the only value the kernel fills)
@@ -104,7 +113,9 @@ class TreeObjective:
     call moves only `preds` to the device and `grad` / `hess` back.  objective: 'ranknet' (pair_type 'All'), 'lambdarank' ('NoTies') or
     'listnet', or 'lambdarank_ndcg' (the truncated, normalised lambdarank of the module docstring, with truncation_level, sigmoid and norm;
     pair_type, weighting, epsilon, hessian and gain_type do not apply to it, and a non-default value raises; the other objectives ignore
-    its three settings).  The defaults are the reference's wrappers: unweighted, epsilon 1, the rank-signed Hessian, gain 'Power'.  Opt-in, and not
+    its three settings), or 'rank_xendcg' (the cross-entropy nDCG objective of the module docstring, with objective_seed; the same five
+    settings do not apply to it; .draw, which starts at 0 and advances by one per __call__ / fobj / sklearn call, numbers the round whose
+    uniforms a call draws).  The defaults are the reference's wrappers: unweighted, epsilon 1, the rank-signed Hessian, gain 'Power'.  Opt-in, and not
     what the reference computes: weighting='DeltaNDCG' (real LambdaMART) or 'DeltaGain', hessian='sum' (never negative) or 'constant'.
 
     __call__(preds) takes a numpy array of any float dtype and returns (grad, hess) as float64 numpy arrays, like the reference; the
@@ -112,7 +123,7 @@ class TreeObjective:
     objective for .fobj / .sklearn alone, which take both from their arguments.  There is no CPU path: without a GPU it raises."""
 
     def __init__(self, labels=None, group=None, objective="lambdarank", pair_type=None, weighting=None, epsilon=1.0, hessian="reference",
-                 gain_type="Power", device=None, truncation_level=30, sigmoid=1.0, norm=True):
+                 gain_type="Power", device=None, truncation_level=30, sigmoid=1.0, norm=True, objective_seed=5):
         if objective not in OBJECTIVES:
             raise ValueError(f"objective {objective!r} (supported: {', '.join(map(repr, OBJECTIVES))})")
         self.objective = objective
@@ -120,12 +131,13 @@ class TreeObjective:
         self.pair_type = default_pairs if pair_type is None else pair_type
         self.weighting, self.epsilon, self.hessian, self.gain_type = weighting, float(epsilon), hessian, gain_type
         self.truncation_level, self.sigmoid, self.norm = F.lambdarank_ndcg_settings(truncation_level, sigmoid, norm)
+        self.objective_seed, self.draw = F.objective_seed(objective_seed), 0
         if self.kind == "pair":
             F._enum("pair_type", self.pair_type, F.TREE_PAIR_TYPES)
             F._enum("weighting", weighting, F.TREE_WEIGHTINGS)
             if not self.epsilon >= 0.0:
                 raise ValueError(f"epsilon must be >= 0, got {epsilon!r}")
-        elif self.kind == "lambdarank_ndcg":
+        elif self.kind in ("lambdarank_ndcg", "xendcg"):
             not_applicable(objective, dict(pair_type=pair_type, weighting=weighting, epsilon=epsilon, hessian=hessian, gain_type=gain_type),
                            dict(pair_type=None, weighting=None, epsilon=1.0, hessian="reference", gain_type="Power"))
         else:
@@ -155,8 +167,11 @@ class TreeObjective:
                 F.tree_pair_grad_hess(p, res.labels, res.offsets, self.pair_type, self.weighting, self.epsilon, self.hessian, queries, max_len, out)
             elif self.kind == "lambdarank_ndcg":
                 F.tree_lambdarank_ndcg_grad_hess(p, res.labels, res.offsets, self.truncation_level, self.sigmoid, self.norm, queries, max_len, out)
+            elif self.kind == "xendcg":
+                F.tree_xendcg_grad_hess(p, res.labels, res.offsets, self.objective_seed, self.draw, None, queries, max_len, out)
             else:
                 F.tree_listnet_grad_hess(p, res.labels, res.offsets, self.gain_type, self.hessian, queries, max_len, out)
+        self.draw += 1                                                     # one call per boosting round (rank_xendcg's stream reads it)
         both = torch.stack(out).cpu().numpy().astype(np.float64)           # one copy back; every document belongs to a launched query
         return both[0], both[1]
 
