@@ -1005,6 +1005,12 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *   ptr_gbdt_histogram_segments                  m, F, max_bin, total                     kind, features per tile, tiles, row chunks, LDS bytes,
  *                                                (m: one segment's rows; total: the rows    rows per chunk, the direct form's row bound, the most
  *                                                of the call's LDS-form segments)           launches of one call
+ *   ptr_gbdt_histogram_packed                    m, F, max_bin, bound_g, bound_h          kind, features per tile, tiles, row chunks, LDS bytes,
+ *                                                                                           rows per flush R
+ *   ptr_gbdt_histogram_segments_packed           m, F, max_bin, total, bound_g, bound_h   kind, features per tile, tiles, row chunks, LDS bytes,
+ *                                                                                           rows per chunk, the direct form's row bound, R
+ *   ptr_gbdt_leaf_sums_rows                      total, nleaves                           threads per workgroup, workgroups per leaf, entries of
+ *                                                                                           a leaf one workgroup takes per step (2048)
  *   ptr_gbdt_hist_sub_segments                   K                                        launches of one call (1), workgroup rows per triple
  *   ptr_gbdt_best_split_slots                    K                                        launches of one call (2), 0
  *   ptr_gbdt_partition_segments                  m                                        launches of one call (3), workgroups of a segment of m rows
@@ -1433,6 +1439,40 @@ int ptr_gbdt_leaf_sums_cat(const float *X, int64_t n, int F, const int32_t *feat
                            const int64_t *cat_sets, int ncat, int nodes, const int32_t *qg, const int32_t *qh, int nleaves, int32_t *leaf,
                            int64_t *sums, void *stream);
 int ptr_gbdt_add_by_leaf(float *scores, int64_t n, const int32_t *leaf, const float *values, int nleaves, void *stream);
+
+/* ---- Quantized-gradient training (csrc/gbdt.hip; use_quantized_grad, num_grad_quant_bins, stochastic_rounding, quant_train_renew_leaf and
+ * quant_seed of ptranking_amd/gbdt.py).  ADDITIVE to ABI v8 too; every symbol above keeps its signature and its results bit for bit.  The
+ * parameter names are LightGBM's (quant_seed is this project's own), the rules are this project's own and no parity with LightGBM is
+ * claimed; tests/gbdt_quant_ref.py restates them.
+ *
+ * ptr_gbdt_quantize_low: ptr_gbdt_quantize with B = `levels` levels, a power of two in 2 .. 256 (PTR_ERR_INVALID_ARG otherwise, and for a
+ *   draw outside 0 .. 2^62 - 1).  With max|g| = fr 2^ex, fr in [0.5, 1): e_g = log2(B / 2) - ex; for max|h|, e_h = log2(B) - ex; a maximum
+ *   of zero gives 0.  x = g 2^e_g is exact in fp32 with |x| < B / 2 (|h 2^e_h| < B).  stochastic != 0: q = floor((double)x + (double)u),
+ *   u = pl_uniform(pl_query_keys(seed, draw'), row) of the counter stream ptr_gbdt_bag_mask draws from, a multiple of 2^-24 in [0, 1),
+ *   draw' = 2 draw for g and 2 draw + 1 for h; the sum is exact in float64, so E[q] = x.  stochastic == 0: q = rint(x), ties to even.
+ *   |qg| <= B / 2 and |qh| <= B.  qg, qh, expo, flag and state are those of ptr_gbdt_quantize (a NaN or an infinity ORs 1 into flag and
+ *   its row is written as 0, 0), so every entry point above serves the result: the true value of a sum is still q 2^-e.
+ * ptr_gbdt_histogram_packed, ptr_gbdt_histogram_segments_packed: ptr_gbdt_histogram and ptr_gbdt_histogram_segments for |qg| <= bound_g
+ *   (1 .. 128) and |qh| <= bound_h (1 .. 256; PTR_ERR_INVALID_ARG outside).  The same hist and pool, the same grid and the same direct form
+ *   up to 256 rows; within the bounds the result is the int64 entry point's, bit for bit.  A value outside the bounds is the caller's
+ *   error: the sums are then unspecified, but no access leaves the buffers.  In the LDS form a cell is ONE 64-bit word: sum qg in bits
+ *   0 - 20, sum qh in bits 21 - 41 (both two's complement), the count in bits 42 - 63; a row adds qg + (qh << 21) + (1 << 42) with one
+ *   64-bit LDS integer atomic, 8 bytes per (feature, bin) (32 KiB at 256 bins).  The fields are exact for R = floor((2^20 - 1) /
+ *   max(2 bound_g, bound_h)) rows, so a workgroup flushes the cells it touched into hist (global integer atomics) and zeroes them every R
+ *   rows of its chunk.  ptr_launch_form reports R.  No float atomic.
+ * ptr_gbdt_leaf_sums_rows: ADDS (qg[r], qh[r], 1) of the rows r = rows[i], offsets[l] <= i < offsets[l + 1], into sums[l][3] (int64
+ *   [nleaves][3], zeroed by the caller) for l < nleaves: rows, offsets and total as ptr_gbdt_add_leaf_values takes them.  A leaf whose range
+ *   leaves [0, total) and a row outside [0, n) are skipped.  grid = (nleaves, parts): a leaf is split over `parts` workgroups in steps of
+ *   2048 entries; register sums, wave and workgroup integer reductions, one global integer atomic per workgroup and value. */
+int ptr_gbdt_quantize_low(const float *g, const float *h, int64_t n, int levels, int stochastic, uint64_t seed, int64_t draw, int32_t *qg,
+                          int32_t *qh, int32_t *expo, int32_t *flag, uint32_t *state, void *stream);
+int ptr_gbdt_histogram_packed(const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows,
+                              int64_t m, int F, int max_bin, int bound_g, int bound_h, int64_t *hist, void *stream);
+int ptr_gbdt_histogram_segments_packed(const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows,
+                                       int64_t nrows, const int32_t *segs, int K, const int32_t *items, int n_direct, int n_lds, int F,
+                                       int max_bin, int bound_g, int bound_h, int64_t *pool, int nslots, void *stream);
+int ptr_gbdt_leaf_sums_rows(const int32_t *rows, const int32_t *offsets, int nleaves, int64_t total, const int32_t *qg, const int32_t *qh,
+                            int64_t n, int64_t *sums, void *stream);
 
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):

@@ -150,6 +150,10 @@ SIGNATURES = {
     "ptr_gbdt_leaf_sums_missing": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp],
     "ptr_gbdt_leaf_sums_cat": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
     "ptr_gbdt_add_by_leaf": [_vp, C.c_int64, _vp, _vp, _i, _vp],
+    "ptr_gbdt_quantize_low": [_vp, _vp, C.c_int64, _i, _i, C.c_uint64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ptr_gbdt_histogram_packed": [_vp, _i, C.c_int64, _vp, _vp, _vp, C.c_int64, _i, _i, _i, _i, _vp, _vp],
+    "ptr_gbdt_histogram_segments_packed": [_vp, _i, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp],
+    "ptr_gbdt_leaf_sums_rows": [_vp, _vp, _i, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp],
     "ptr_letor_scan":[C.c_char_p, _i, _vp, _vp, _vp],
     "ptr_letor_load": [C.c_char_p, _i, _f, C.c_int64, C.c_int32, C.c_int64, _vp, _i, _vp, _vp, _vp],
 }

@@ -80,6 +80,11 @@ static const FormQuery kFormQueries[] = {
     {"ptr_divprob_fwd_bwd", 3, 2, [](const int64_t *a, int32_t *out) { put(out, divprob_form((int)a[0], (int)a[1], (int)a[2])); }},
     {"ptr_gbdt_histogram", 3, 5, [](const int64_t *a, int32_t *out) { put(out, gbdt_hist_form(a[0], (int)a[1], (int)a[2])); }},
     {"ptr_gbdt_histogram_segments", 4, 8, [](const int64_t *a, int32_t *out) { put(out, gbdt_hist_segments_form(a[0], (int)a[1], (int)a[2], a[3])); }},
+    {"ptr_gbdt_histogram_packed", 5, 6,
+     [](const int64_t *a, int32_t *out) { put(out, gbdt_hist_packed_form(a[0], (int)a[1], (int)a[2], (int)a[3], (int)a[4])); }},
+    {"ptr_gbdt_histogram_segments_packed", 6, 8,
+     [](const int64_t *a, int32_t *out) { put(out, gbdt_hist_segments_packed_form(a[0], (int)a[1], (int)a[2], a[3], (int)a[4], (int)a[5])); }},
+    {"ptr_gbdt_leaf_sums_rows", 2, 3, [](const int64_t *a, int32_t *out) { put(out, gbdt_leaf_sums_rows_form(a[0], a[1])); }},
     // the other batched level passes have one form each: (launches per call, entries of the table one workgroup serves or 0)
     {"ptr_gbdt_hist_sub_segments", 1, 2, [](const int64_t *, int32_t *out) { out[0] = 1; out[1] = 1; }},
     {"ptr_gbdt_best_split_slots", 1, 2, [](const int64_t *, int32_t *out) { out[0] = 2; out[1] = 0; }},

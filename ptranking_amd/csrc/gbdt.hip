@@ -21,6 +21,10 @@
 //            and walks the 16 features ROTATED by its lane number: in one step the 64 lanes address 16 different features, so a constant
 //            feature (every row in one bin) meets 4 lanes per address and step, not 64.  The flush adds only the bins the chunk touched.
 //
+//   packed   the LDS form for low-bit gradients (ptr_gbdt_quantize_low: |qg| <= B / 2, |qh| <= B, B <= 256): the three sums of a cell in one
+//            64-bit word, one LDS atomic per (row, feature), 8 bytes per cell, a flush every R rows; the same grid, the same bits.  The
+//            header of gbdt_hist_tile_packed says how the freed LDS is spent and why.
+//
 // One body per step.  The single-list and the batched (segment) kernels of a step differ only in how a workgroup finds its rows and its
 // destination; the work is a device function both call: gbdt_hist_tile (the LDS tile: zero, rotated walk, flush), hist_add_direct,
 // part_count and part_scatter under a predicate (PartByBin, PartByMask; a batched workgroup builds a PartByBin over its segment), one scan
@@ -105,24 +109,53 @@ gbdt_absmax_kernel(const float *__restrict__ g, const float *__restrict__ h, int
     if (threadIdx.x == 0) { atomicMax(&state[0], red[0]); atomicMax(&state[1], red[1]); }
 }
 
-// the largest e with m 2^e < 2^30: m = fr 2^ex with fr in [0.5, 1), so e = 30 - ex; 0 for m == 0
-__device__ __forceinline__ int gbdt_exponent(uint32_t bits) {
+// the largest e with m 2^e < 2^top: m = fr 2^ex with fr in [0.5, 1), so e = top - ex; 0 for m == 0
+__device__ __forceinline__ int gbdt_exponent(uint32_t bits, int top) {
     if (bits == 0) return 0;
     int ex;
     (void)frexpf(__uint_as_float(bits), &ex);
-    return 30 - ex;
+    return top - ex;
 }
 
 __global__ void __launch_bounds__(kBlock)
 gbdt_quantize_kernel(const float *__restrict__ g, const float *__restrict__ h, int64_t n, const uint32_t *__restrict__ state,
                      int32_t *__restrict__ qg, int32_t *__restrict__ qh, int32_t *__restrict__ expo) {
-    const int eg = gbdt_exponent(state[0]), eh = gbdt_exponent(state[1]);
+    const int eg = gbdt_exponent(state[0], 30), eh = gbdt_exponent(state[1], 30);
     if (blockIdx.x == 0 && threadIdx.x == 0) { expo[0] = eg; expo[1] = eh; }
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
         const float a = g[i], b = h[i];
         const bool fin = (__float_as_uint(a) & 0x7fffffffu) < 0x7f800000u && (__float_as_uint(b) & 0x7fffffffu) < 0x7f800000u;
         qg[i] = fin ? (int32_t)rintf(ldexpf(a, eg)) : 0;                // a non-finite entry raised the flag; its row carries nothing
         qh[i] = fin ? (int32_t)rintf(ldexpf(b, eh)) : 0;
+    }
+}
+
+// Low-bit gradients (ptr_gbdt_quantize_low; use_quantized_grad of gbdt.py): B levels, B = 2^lb.  The scales put max|g| just below B / 2
+// and max|h| just below B, so x = ldexpf(g, e_g) is exact with |x| < B / 2.  Stochastic rounding takes q = floor(x + u) with u the multiple
+// of 2^-24 in [0, 1) of the counter stream bagging draws from, keyed by (seed, 2 draw) for g and (seed, 2 draw + 1) for h and indexed by
+// the row: the sum is exact in float64 (x holds 24 bits above 2^-149 at the worst, u 24 bits above 2^-24, and a double 53), so E[q] = x and
+// nothing is rounded twice.  |qg| <= B / 2 and |qh| <= B either way.  The outputs are those of gbdt_quantize_kernel.
+__global__ void __launch_bounds__(kBlock)
+gbdt_quantize_low_kernel(const float *__restrict__ g, const float *__restrict__ h, int64_t n, const uint32_t *__restrict__ state, int lb,
+                         int stochastic, uint64_t seed, int64_t draw, int32_t *__restrict__ qg, int32_t *__restrict__ qh,
+                         int32_t *__restrict__ expo) {
+    const int eg = gbdt_exponent(state[0], lb - 1), eh = gbdt_exponent(state[1], lb);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { expo[0] = eg; expo[1] = eh; }
+    const PlKeys kg = pl_query_keys(seed, 2 * draw), kh = pl_query_keys(seed, 2 * draw + 1);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const float a = g[i], b = h[i];
+        const bool fin = (__float_as_uint(a) & 0x7fffffffu) < 0x7f800000u && (__float_as_uint(b) & 0x7fffffffu) < 0x7f800000u;
+        const float xa = ldexpf(a, eg), xb = ldexpf(b, eh);
+        int32_t ra, rb;
+        if (stochastic) {
+            ra = (int32_t)floor((double)xa + (double)pl_uniform(kg, (uint32_t)i));
+            rb = (int32_t)floor((double)xb + (double)pl_uniform(kh, (uint32_t)i));
+        } else {
+            ra = (int32_t)rintf(xa);
+            rb = (int32_t)rintf(xb);
+        }
+        qg[i] = fin ? ra : 0;
+        qh[i] = fin ? rb : 0;
     }
 }
 
@@ -189,15 +222,97 @@ __device__ __forceinline__ void gbdt_hist_tile(unsigned char *smem, const uint8_
     }
 }
 
-__global__ void __launch_bounds__(kBlock)
+// ---- the packed tile (ptr_gbdt_histogram_packed, ptr_gbdt_histogram_segments_packed; use_quantized_grad of gbdt.py)
+// For |qg| <= bound_g <= 128 and |qh| <= bound_h <= 256 the three sums of a cell share ONE 64-bit LDS word (ptr_gbdt.h gives the layout and
+// R, the rows a tile takes between flushes): a (row, feature) costs one ds_add_u64 where gbdt_hist_tile issues two and a ds_add_u32, and a
+// cell is 8 bytes, not 20.  The result is the int64 kernels', bit for bit: the fields never overflow within R rows, the flush unpacks them
+// into int64 and global memory is summed in int64 as before.
+//
+// What the freed LDS buys.  A [16][256] tile is 32 KiB against 80, and it is spent on RESIDENT WORKGROUPS: five per compute unit (20 waves)
+// where the int64 tile allows two (8 waves).  The loop is a chain of dependent accesses — rows[i], then a random 16-byte gather of that
+// row's bins and its qg, qh, then LDS atomics whose returns nobody waits for — and nothing but other waves hides the gather.  The other
+// candidates were weighed from the code, not measured: a 32-feature tile (64 KiB) halves the reloads of rows / qg / qh, 12 of the 28 bytes a
+// (row, tile) reads, but stays at two workgroups, so it trades the smaller cost for the larger; per-wave replicas (4 x 32 KiB) also stay
+// at one workgroup of four waves per 128 KiB and only help a constant feature, which the rotated walk already spreads over 16 addresses
+// per wave step.  So the tile stays at 16 features (the grid, the row chunks and the host's work lists are those of the int64 form), the
+// rotated walk stays, and each lane keeps the NEXT row's gather in flight while it issues the atomics of the current one.
+//
+// Measured afterwards (profiles/mi355x_gbdt_quant.json, F = 136, max_bin = 255): the packed kernel is NOT faster than the int64 one.  Over
+// 795 428 rows it takes 0.312 ms against 0.309 ms at B = 4 and 0.479 ms against 0.311 ms at B = 256; over 1 / 16 of them 0.076 ms both.  The
+// time follows the number of flushes (B = 256 flushes twice per 7 168-row chunk), so the global atomics of the flush bound both kernels
+// at these shapes, not the LDS atomics this tile saves; fewer, longer chunks are the lever, and they are not tried here.
+//
+// A chunk longer than R rows is walked in runs of R: after each run the workgroup flushes the cells it touched and zeroes them.  A touched
+// cell is a non-zero word: with a count c >= 1 the word is g + h 2^21 + c 2^42 and |g + h 2^21| < 2^42.  The flush peels the fields from
+// the low end, subtracting each sign-extended field before it shifts, so a negative sum's borrow is undone.
+__device__ __forceinline__ int64_t gbdt_packed_low(u64 w) { return (int64_t)(w << (64 - kGbdtPackedBits)) >> (64 - kGbdtPackedBits); }
+
+struct GbdtPackedRow { uint4 bv; u64 add; bool live; };
+__device__ __forceinline__ GbdtPackedRow gbdt_packed_row(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg,
+                                                         const int32_t *__restrict__ qh, const int32_t *__restrict__ rows, int64_t i, int64_t end,
+                                                         int f0) {
+    GbdtPackedRow r{make_uint4(0, 0, 0, 0), 0, false};
+    if (i >= end) return r;
+    const int row = rows ? rows[i] : (int)i;
+    if (row < 0 || row >= n) return r;
+    r.bv = *reinterpret_cast<const uint4 *>(bins + (size_t)row * stride + f0);
+    r.add = (u64)((int64_t)qg[row] + ((int64_t)qh[row] << kGbdtPackedBits) + ((int64_t)1 << (2 * kGbdtPackedBits)));
+    r.live = true;
+    return r;
+}
+
+// The packed LDS form of one workgroup, with gbdt_hist_tile's arguments and flush_rows = R >= 1: its tile is [kGbdtTile][max_bin] u64 at `smem`.
+__device__ __forceinline__ void gbdt_hist_tile_packed(unsigned char *smem, const uint8_t *__restrict__ bins, int stride, int n,
+                                                      const int32_t *__restrict__ qg, const int32_t *__restrict__ qh, const int32_t *__restrict__ rows,
+                                                      int64_t r0, int64_t r1, int F, int max_bin, int64_t *__restrict__ hist, int flush_rows) {
+    u64 *cell = reinterpret_cast<u64 *>(smem);
+    const int tid = threadIdx.x, f0 = blockIdx.y * kGbdtTile;
+    const int nf = min(kGbdtTile, F - f0);
+    for (int e = tid; e < kGbdtTile * max_bin; e += kBlock) cell[e] = 0;
+    __syncthreads();
+    for (int64_t s0 = r0; s0 < r1; s0 += flush_rows) {
+        const int64_t s1 = s0 + flush_rows < r1 ? s0 + flush_rows : r1;
+        GbdtPackedRow cur = gbdt_packed_row(bins, stride, n, qg, qh, rows, s0 + tid, s1, f0);
+        for (int64_t i = s0 + tid; i < s1; i += kBlock) {
+            const GbdtPackedRow next = gbdt_packed_row(bins, stride, n, qg, qh, rows, i + kBlock, s1, f0);
+            if (cur.live) {
+#pragma unroll
+                for (int k = 0; k < kGbdtTile; ++k) {
+                    const int f = (k + tid) & (kGbdtTile - 1);
+                    const uint32_t w = (f >> 2) == 0 ? cur.bv.x : (f >> 2) == 1 ? cur.bv.y : (f >> 2) == 2 ? cur.bv.z : cur.bv.w;
+                    const int b = (w >> ((f & 3) * 8)) & 0xff;
+                    if (f < nf && b < max_bin) atomicAdd(&cell[f * max_bin + b], cur.add);
+                }
+            }
+            cur = next;
+        }
+        __syncthreads();
+        for (int e = tid; e < nf * max_bin; e += kBlock) {
+            u64 w = cell[e];
+            if (w) {
+                const int64_t g = gbdt_packed_low(w);
+                w = (u64)((int64_t)(w - (u64)g) >> kGbdtPackedBits);
+                const int64_t h = gbdt_packed_low(w);
+                const int64_t c = (int64_t)(w - (u64)h) >> kGbdtPackedBits;
+                hist_add_global(hist + ((size_t)f0 * max_bin + e) * 3, g, h, c);
+                cell[e] = 0;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// kPacked: the packed tile and its flush_rows; without it the int64 tile, which ignores the argument
+template <bool kPacked> __global__ void __launch_bounds__(kBlock)
 gbdt_hist_lds_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg, const int32_t *__restrict__ qh,
-                     const int32_t *__restrict__ rows, int m, int F, int max_bin, int64_t *__restrict__ hist) {
+                     const int32_t *__restrict__ rows, int m, int F, int max_bin, int64_t *__restrict__ hist, int flush_rows) {
     extern __shared__ __attribute__((aligned(16))) unsigned char gbdt_smem[];
     // this workgroup's rows: chunk c of gridDim.x, whole multiples of the block except the last
     const int per = (int)((((int64_t)m + gridDim.x - 1) / gridDim.x + kBlock - 1) / kBlock) * kBlock;
     const int64_t r0 = (int64_t)blockIdx.x * per;
     const int64_t r1 = r0 + per < (int64_t)m ? r0 + per : (int64_t)m;
-    gbdt_hist_tile(gbdt_smem, bins, stride, n, qg, qh, rows, r0, r1, F, max_bin, hist);
+    if constexpr (kPacked) gbdt_hist_tile_packed(gbdt_smem, bins, stride, n, qg, qh, rows, r0, r1, F, max_bin, hist, flush_rows);
+    else gbdt_hist_tile(gbdt_smem, bins, stride, n, qg, qh, rows, r0, r1, F, max_bin, hist);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -716,16 +831,18 @@ gbdt_hist_seg_direct_kernel(const uint8_t *__restrict__ bins, int stride, int n,
         hist_add_direct(bins, stride, n, qg, qh, rows[r0 + (e >> 4)], f0 + (e & (kGbdtTile - 1)), F, max_bin, hist);
 }
 
-// LDS form: grid = (items, feature tiles); an item is one row chunk of a segment
-__global__ void __launch_bounds__(kBlock)
+// LDS form: grid = (items, feature tiles); an item is one row chunk of a segment.  kPacked as in gbdt_hist_lds_kernel.
+template <bool kPacked> __global__ void __launch_bounds__(kBlock)
 gbdt_hist_seg_lds_kernel(const uint8_t *__restrict__ bins, int stride, int n, const int32_t *__restrict__ qg, const int32_t *__restrict__ qh,
                          const int32_t *__restrict__ rows, int64_t nrows, const int32_t *__restrict__ segs, int K,
-                         const int32_t *__restrict__ items, int F, int max_bin, int64_t *__restrict__ pool, int nslots) {
+                         const int32_t *__restrict__ items, int F, int max_bin, int64_t *__restrict__ pool, int nslots, int flush_rows) {
     extern __shared__ __attribute__((aligned(16))) unsigned char gbdt_smem[];
     int64_t r0 = 0, r1 = 0;
     const GbdtSeg s = gbdt_hist_item(segs, K, items + (int64_t)blockIdx.x * 3, nrows, nslots, r0, r1);
     if (!s.ok || r1 == r0) return;
-    gbdt_hist_tile(gbdt_smem, bins, stride, n, qg, qh, rows, r0, r1, F, max_bin, pool + (int64_t)s.slot * F * max_bin * 3);
+    int64_t *hist = pool + (int64_t)s.slot * F * max_bin * 3;
+    if constexpr (kPacked) gbdt_hist_tile_packed(gbdt_smem, bins, stride, n, qg, qh, rows, r0, r1, F, max_bin, hist, flush_rows);
+    else gbdt_hist_tile(gbdt_smem, bins, stride, n, qg, qh, rows, r0, r1, F, max_bin, hist);
 }
 
 // trips [K][3] = (parent slot, child slot, out slot): grid = (K, chunks of one histogram)
@@ -807,6 +924,45 @@ gbdt_add_leaf_values_kernel(float *__restrict__ scores, int n, const int32_t *__
     }
     const int row = rows[i];
     if (i < offsets[nleaves] && i >= offsets[0] && row >= 0 && row < n) scores[row] += values[lo];
+}
+
+// The sum over a wavefront of an int64, in every lane
+__device__ __forceinline__ int64_t wave_sum(int64_t v) {
+#pragma unroll
+    for (int d = kWave / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// Per-leaf sums over the grower's row list (ptr_gbdt_leaf_sums_rows; quant_train_renew_leaf of gbdt.py): grid = (nleaves, parts).  The
+// workgroup (l, p) walks the entries offsets[l] + (p + k parts) kLeafRowsChunk .. of leaf l, k = 0, 1, ..., each thread summing (qg, qh, 1)
+// of its rows in int64 registers; the wavefronts reduce with shuffles, the workgroup through 12 LDS words, and thread 0 adds the three
+// totals into sums[l] with one global integer atomic each (none where the workgroup met no row).  offsets is read as untrusted: a leaf
+// whose range is no sub-range of [0, total) is skipped; a row outside [0, n) is skipped.
+__global__ void __launch_bounds__(kBlock)
+gbdt_leaf_sums_rows_kernel(const int32_t *__restrict__ rows, const int32_t *__restrict__ offsets, int total, const int32_t *__restrict__ qg,
+                           const int32_t *__restrict__ qh, int n, int64_t *__restrict__ sums) {
+    __shared__ int64_t red[kBlock / kWave][3];
+    const int leaf = blockIdx.x;
+    const int lo = offsets[leaf], hi = offsets[leaf + 1];
+    if (lo < 0 || hi > total || lo >= hi) return;                       // uniform for the workgroup, before the barrier
+    int64_t g = 0, h = 0, c = 0;
+    for (int64_t base = (int64_t)lo + (int64_t)blockIdx.y * kLeafRowsChunk; base < hi; base += (int64_t)gridDim.y * kLeafRowsChunk) {
+        const int64_t end = base + kLeafRowsChunk < hi ? base + kLeafRowsChunk : hi;
+        for (int64_t i = base + threadIdx.x; i < end; i += kBlock) {
+            const int row = rows[i];
+            if (row >= 0 && row < n) { g += qg[row]; h += qh[row]; c += 1; }
+        }
+    }
+    g = wave_sum(g); h = wave_sum(h); c = wave_sum(c);
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    if (lane == 0) { red[wave][0] = g; red[wave][1] = h; red[wave][2] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        g = h = c = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) { g += red[w][0]; h += red[w][1]; c += red[w][2]; }
+        if (c) hist_add_global(sums + (int64_t)leaf * 3, g, h, c);
+    }
 }
 
 // One row's walk down a tree of nn nodes (nn + 1 leaves; a child c < 0 is the leaf ~c) -> the node it ends in.  goes_left(node, f) decides at
@@ -1256,21 +1412,55 @@ extern "C" int ptr_gbdt_bin_missing(const float *X, int64_t n, int F, const floa
     return gbdt_bin_impl("ptr_gbdt_bin_missing", X, n, F, edges, nbins, nan_bin, true, max_bin, stride, bins, stream);
 }
 
+// The checks and the absmax pass both quantisers share -> 0 to go on to the rounding kernel, 1 for an empty input, or an error.
+static int gbdt_quantize_begin(const char *who, const float *g, const float *h, int64_t n, int32_t *qg, int32_t *qh, int32_t *expo, int32_t *flag,
+                               uint32_t *state, void *stream, int &rc) {
+    rc = 0;
+    if (n < 0) { set_error("%s: negative size (n=%lld)", who, (long long)n); rc = PTR_ERR_INVALID_ARG; return 1; }
+    if (n == 0) return 1;
+    if (!g || !h || !qg || !qh || !expo || !flag || !state) { set_error("%s: NULL pointer", who); rc = PTR_ERR_INVALID_ARG; return 1; }
+    if ((rc = check_hip(hipMemsetAsync(state, 0, 2 * sizeof(uint32_t), as_stream(stream)), who))) return 1;
+    hipLaunchKernelGGL(gbdt_absmax_kernel, dim3(grid_for(n, 1024)), dim3(kBlock), 0, as_stream(stream), g, h, n, state, flag);
+    return 0;
+}
+
 extern "C" int ptr_gbdt_quantize(const float *g, const float *h, int64_t n, int32_t *qg, int32_t *qh, int32_t *expo, int32_t *flag, uint32_t *state,
                                  void *stream) {
     const char *who = "ptr_gbdt_quantize";
-    if (n < 0) { set_error("%s: negative size (n=%lld)", who, (long long)n); return PTR_ERR_INVALID_ARG; }
-    if (n == 0) return 0;
-    if (!g || !h || !qg || !qh || !expo || !flag || !state) { set_error("%s: NULL pointer", who); return PTR_ERR_INVALID_ARG; }
-    if (int rc = check_hip(hipMemsetAsync(state, 0, 2 * sizeof(uint32_t), as_stream(stream)), who)) return rc;
-    hipLaunchKernelGGL(gbdt_absmax_kernel, dim3(grid_for(n, 1024)), dim3(kBlock), 0, as_stream(stream), g, h, n, state, flag);
+    int rc;
+    if (gbdt_quantize_begin(who, g, h, n, qg, qh, expo, flag, state, stream, rc)) return rc;
     hipLaunchKernelGGL(gbdt_quantize_kernel, dim3(grid_for(n, 4096)), dim3(kBlock), 0, as_stream(stream), g, h, n, state, qg, qh, expo);
     return check_hip(hipGetLastError(), who);
 }
 
-extern "C" int ptr_gbdt_histogram(const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows, int64_t m,
-                                  int F, int max_bin, int64_t *hist, void *stream) {
-    const char *who = "ptr_gbdt_histogram";
+extern "C" int ptr_gbdt_quantize_low(const float *g, const float *h, int64_t n, int levels, int stochastic, uint64_t seed, int64_t draw, int32_t *qg,
+                                     int32_t *qh, int32_t *expo, int32_t *flag, uint32_t *state, void *stream) {
+    const char *who = "ptr_gbdt_quantize_low";
+    if (levels < 2 || levels > 256 || (levels & (levels - 1))) {
+        set_error("%s: levels must be a power of two in 2 .. 256, got %d", who, levels);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (draw < 0 || draw > (INT64_MAX - 1) / 2) { set_error("%s: draw must be in 0 .. 2^62 - 1", who); return PTR_ERR_INVALID_ARG; }
+    int rc;
+    if (gbdt_quantize_begin(who, g, h, n, qg, qh, expo, flag, state, stream, rc)) return rc;
+    hipLaunchKernelGGL(gbdt_quantize_low_kernel, dim3(grid_for(n, 4096)), dim3(kBlock), 0, as_stream(stream), g, h, n, state, __builtin_ctz((unsigned)levels),
+                       stochastic != 0 ? 1 : 0, seed, draw, qg, qh, expo);
+    return check_hip(hipGetLastError(), who);
+}
+
+// bound_g, bound_h of the packed forms -> rows per flush in flush_rows, or an error
+static int check_packed_bounds(int bound_g, int bound_h, int &flush_rows, const char *who) {
+    if (bound_g < 1 || bound_g > 128 || bound_h < 1 || bound_h > 256) {
+        set_error("%s: bound_g must be in 1 .. 128 and bound_h in 1 .. 256, got %d and %d", who, bound_g, bound_h);
+        return PTR_ERR_INVALID_ARG;
+    }
+    flush_rows = gbdt_packed_flush_rows(bound_g, bound_h);
+    return 0;
+}
+
+// flush_rows == 0: the int64 tile (ptr_gbdt_histogram); > 0: the packed one
+static int gbdt_histogram_impl(const char *who, const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows,
+                               int64_t m, int F, int max_bin, int64_t *hist, int flush_rows, void *stream) {
     if (int rc = check_bins_layout(n, F, stride, who)) return rc;
     if (int rc = check_max_bin(max_bin, who)) return rc;
     if (m < 0 || m > INT32_MAX) { set_error("%s: bad row count m=%lld", who, (long long)m); return PTR_ERR_INVALID_ARG; }
@@ -1282,12 +1472,29 @@ extern "C" int ptr_gbdt_histogram(const uint8_t *bins, int stride, int64_t n, co
     if (form.kind == 1) {
         hipLaunchKernelGGL(gbdt_hist_direct_kernel, dim3((unsigned)((m * stride + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), bins, stride, (int)n, qg, qh, rows,
                            (int)m, F, max_bin, hist);
+    } else if (flush_rows > 0) {
+        const size_t lds = (size_t)kGbdtTile * max_bin * kGbdtPackedCell;
+        hipLaunchKernelGGL(gbdt_hist_lds_kernel<true>, dim3(form.chunks, form.tiles), dim3(kBlock), lds, as_stream(stream), bins, stride, (int)n, qg, qh, rows,
+                           (int)m, F, max_bin, hist, flush_rows);
     } else {
-        if (int rc = allow_lds(gbdt_hist_lds_kernel, (size_t)form.lds_bytes)) return rc;
-        hipLaunchKernelGGL(gbdt_hist_lds_kernel, dim3(form.chunks, form.tiles), dim3(kBlock), (size_t)form.lds_bytes, as_stream(stream), bins, stride,
-                           (int)n, qg, qh, rows, (int)m, F, max_bin, hist);
+        if (int rc = allow_lds(gbdt_hist_lds_kernel<false>, (size_t)form.lds_bytes)) return rc;
+        hipLaunchKernelGGL(gbdt_hist_lds_kernel<false>, dim3(form.chunks, form.tiles), dim3(kBlock), (size_t)form.lds_bytes, as_stream(stream), bins, stride,
+                           (int)n, qg, qh, rows, (int)m, F, max_bin, hist, 0);
     }
     return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_histogram(const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows, int64_t m,
+                                  int F, int max_bin, int64_t *hist, void *stream) {
+    return gbdt_histogram_impl("ptr_gbdt_histogram", bins, stride, n, qg, qh, rows, m, F, max_bin, hist, 0, stream);
+}
+
+extern "C" int ptr_gbdt_histogram_packed(const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows,
+                                         int64_t m, int F, int max_bin, int bound_g, int bound_h, int64_t *hist, void *stream) {
+    const char *who = "ptr_gbdt_histogram_packed";
+    int flush_rows = 0;
+    if (int rc = check_packed_bounds(bound_g, bound_h, flush_rows, who)) return rc;
+    return gbdt_histogram_impl(who, bins, stride, n, qg, qh, rows, m, F, max_bin, hist, flush_rows, stream);
 }
 
 extern "C" int ptr_gbdt_hist_sub(const int64_t *parent, const int64_t *child, int F, int max_bin, int64_t *out, void *stream) {
@@ -1446,6 +1653,21 @@ extern "C" int ptr_gbdt_add_leaf_values(float *scores, int64_t n, const int32_t 
     if (!scores || !rows || !offsets || !values) { set_error("%s: NULL pointer (scores, rows, offsets or values)", who); return PTR_ERR_INVALID_ARG; }
     hipLaunchKernelGGL(gbdt_add_leaf_values_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream), scores, (int)n, rows,
                        offsets, values, nleaves, (int)total);
+    return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_leaf_sums_rows(const int32_t *rows, const int32_t *offsets, int nleaves, int64_t total, const int32_t *qg, const int32_t *qh,
+                                       int64_t n, int64_t *sums, void *stream) {
+    const char *who = "ptr_gbdt_leaf_sums_rows";
+    if (n < 0 || n > INT32_MAX || nleaves < 0 || total < 0 || total > INT32_MAX) {
+        set_error("%s: bad size (n=%lld, nleaves=%d, total=%lld)", who, (long long)n, nleaves, (long long)total);
+        return PTR_ERR_INVALID_ARG;
+    }
+    const GbdtLeafRowsForm form = gbdt_leaf_sums_rows_form(total, nleaves);
+    if (form.parts == 0 || n == 0) return 0;
+    if (!rows || !offsets || !qg || !qh || !sums) { set_error("%s: NULL pointer (rows, offsets, qg, qh or sums)", who); return PTR_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(gbdt_leaf_sums_rows_kernel, dim3(nleaves, form.parts), dim3(kBlock), 0, as_stream(stream), rows, offsets, (int)total, qg, qh, (int)n,
+                       sums);
     return check_hip(hipGetLastError(), who);
 }
 
@@ -1845,10 +2067,10 @@ static int check_level_common(const char *who, int64_t n, int F, int stride, int
     return 0;
 }
 
-extern "C" int ptr_gbdt_histogram_segments(const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows,
-                                           int64_t nrows, const int32_t *segs, int K, const int32_t *items, int n_direct, int n_lds, int F,
-                                           int max_bin, int64_t *pool, int nslots, void *stream) {
-    const char *who = "ptr_gbdt_histogram_segments";
+// flush_rows == 0: the int64 tile (ptr_gbdt_histogram_segments); > 0: the packed one
+static int gbdt_histogram_segments_impl(const char *who, const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh,
+                                        const int32_t *rows, int64_t nrows, const int32_t *segs, int K, const int32_t *items, int n_direct, int n_lds,
+                                        int F, int max_bin, int64_t *pool, int nslots, int flush_rows, void *stream) {
     if (int rc = check_level_common(who, n, F, stride, max_bin, K, kCheckMaxBin | kCheckBins)) return rc;
     if (n_direct < 0 || n_lds < 0 || nrows < 0 || nrows > INT32_MAX || nslots < 0) {
         set_error("%s: bad size (n_direct=%d, n_lds=%d, nrows=%lld, nslots=%d)", who, n_direct, n_lds, (long long)nrows, nslots);
@@ -1861,12 +2083,33 @@ extern "C" int ptr_gbdt_histogram_segments(const uint8_t *bins, int stride, int6
     if (n_direct > 0)
         hipLaunchKernelGGL(gbdt_hist_seg_direct_kernel, dim3(n_direct, form.tiles), dim3(kBlock), 0, as_stream(stream), bins, stride, (int)n, qg, qh, rows,
                            nrows, segs, K, items, F, max_bin, pool, nslots);
-    if (n_lds > 0) {
-        if (int rc = allow_lds(gbdt_hist_seg_lds_kernel, (size_t)form.lds_bytes)) return rc;
-        hipLaunchKernelGGL(gbdt_hist_seg_lds_kernel, dim3(n_lds, form.tiles), dim3(kBlock), (size_t)form.lds_bytes, as_stream(stream), bins, stride, (int)n,
-                           qg, qh, rows, nrows, segs, K, items + (int64_t)n_direct * 3, F, max_bin, pool, nslots);
+    if (n_lds > 0 && flush_rows > 0) {
+        const size_t lds = (size_t)kGbdtTile * max_bin * kGbdtPackedCell;
+        hipLaunchKernelGGL(gbdt_hist_seg_lds_kernel<true>, dim3(n_lds, form.tiles), dim3(kBlock), lds, as_stream(stream), bins, stride, (int)n, qg, qh, rows,
+                           nrows, segs, K, items + (int64_t)n_direct * 3, F, max_bin, pool, nslots, flush_rows);
+    } else if (n_lds > 0) {
+        if (int rc = allow_lds(gbdt_hist_seg_lds_kernel<false>, (size_t)form.lds_bytes)) return rc;
+        hipLaunchKernelGGL(gbdt_hist_seg_lds_kernel<false>, dim3(n_lds, form.tiles), dim3(kBlock), (size_t)form.lds_bytes, as_stream(stream), bins, stride, (int)n,
+                           qg, qh, rows, nrows, segs, K, items + (int64_t)n_direct * 3, F, max_bin, pool, nslots, 0);
     }
     return check_hip(hipGetLastError(), who);
+}
+
+extern "C" int ptr_gbdt_histogram_segments(const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows,
+                                           int64_t nrows, const int32_t *segs, int K, const int32_t *items, int n_direct, int n_lds, int F,
+                                           int max_bin, int64_t *pool, int nslots, void *stream) {
+    return gbdt_histogram_segments_impl("ptr_gbdt_histogram_segments", bins, stride, n, qg, qh, rows, nrows, segs, K, items, n_direct, n_lds, F, max_bin,
+                                        pool, nslots, 0, stream);
+}
+
+extern "C" int ptr_gbdt_histogram_segments_packed(const uint8_t *bins, int stride, int64_t n, const int32_t *qg, const int32_t *qh, const int32_t *rows,
+                                                  int64_t nrows, const int32_t *segs, int K, const int32_t *items, int n_direct, int n_lds, int F,
+                                                  int max_bin, int bound_g, int bound_h, int64_t *pool, int nslots, void *stream) {
+    const char *who = "ptr_gbdt_histogram_segments_packed";
+    int flush_rows = 0;
+    if (int rc = check_packed_bounds(bound_g, bound_h, flush_rows, who)) return rc;
+    return gbdt_histogram_segments_impl(who, bins, stride, n, qg, qh, rows, nrows, segs, K, items, n_direct, n_lds, F, max_bin, pool, nslots, flush_rows,
+                                        stream);
 }
 
 extern "C" int ptr_gbdt_hist_sub_segments(int64_t *pool, int nslots, int F, int max_bin, const int32_t *trips, int K, void *stream) {

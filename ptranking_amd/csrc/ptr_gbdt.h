@@ -41,6 +41,44 @@ inline GbdtSegForm gbdt_hist_segments_form(int64_t m, int F, int max_bin, int64_
     return f;
 }
 
+// The packed histogram (ptr_gbdt_histogram_packed, ptr_gbdt_histogram_segments_packed): low-bit gradients, |qg| <= bound_g <= 128 and
+// |qh| <= bound_h <= 256.  One LDS cell per (feature, bin) is ONE 64-bit word of three fields, from the low end: sum qg in 21 bits, sum qh
+// in 21 bits (both two's complement), the count in 22 bits.  A row adds qg + (qh << 21) + (1 << 42) with one 64-bit LDS atomic.  The fields
+// are exact while at most R = floor((2^20 - 1) / max(2 bound_g, bound_h)) rows went into a tile since it was last flushed; a workgroup
+// flushes and re-zeroes its tile every R rows.  The grid, the row chunks and the direct form are those of the int64 kernels.
+constexpr int kGbdtPackedBits = 21;      // bits of the two sum fields
+constexpr int kGbdtPackedCell = 8;       // bytes per (feature, bin) in LDS: [16][256] cells are 32 KiB, five workgroups per compute unit
+inline int gbdt_packed_flush_rows(int bound_g, int bound_h) {
+    const int b = 2 * bound_g > bound_h ? 2 * bound_g : bound_h;
+    return ((1 << (kGbdtPackedBits - 1)) - 1) / (b > 0 ? b : 1);
+}
+// the form of ptr_gbdt_histogram with the packed tile's LDS bytes, and rows per flush R
+struct GbdtPackedForm { int kind; int tile; int tiles; int chunks; int lds_bytes; int flush_rows; };
+inline GbdtPackedForm gbdt_hist_packed_form(int64_t m, int F, int max_bin, int bound_g, int bound_h) {
+    const GbdtHistForm f = gbdt_hist_form(m, F, max_bin);
+    return {f.kind, f.tile, f.tiles, f.chunks, f.kind == 2 ? kGbdtTile * max_bin * kGbdtPackedCell : 0, gbdt_packed_flush_rows(bound_g, bound_h)};
+}
+// the form of ptr_gbdt_histogram_segments likewise (at most two launches per call, as there)
+struct GbdtSegPackedForm { int kind; int tile; int tiles; int chunks; int lds_bytes; int chunk_rows; int direct_rows; int flush_rows; };
+inline GbdtSegPackedForm gbdt_hist_segments_packed_form(int64_t m, int F, int max_bin, int64_t total, int bound_g, int bound_h) {
+    const GbdtSegForm f = gbdt_hist_segments_form(m, F, max_bin, total);
+    return {f.kind, f.tile, f.tiles, f.chunks, f.kind == 2 ? kGbdtTile * max_bin * kGbdtPackedCell : 0, f.chunk_rows, f.direct_rows,
+            gbdt_packed_flush_rows(bound_g, bound_h)};
+}
+
+// The per-leaf sums over the grower's row list (ptr_gbdt_leaf_sums_rows): grid = (nleaves, parts).  The workgroup (l, p) sums the entries
+// offsets[l] + p * kLeafRowsChunk .. of leaf l, striding by parts * kLeafRowsChunk, in registers, reduces over its wavefronts and adds the
+// three totals with one global integer atomic each; a workgroup without an entry leaves at once.  parts grows with the list so that a
+// leaf of every row is still spread over kLeafRowsMaxParts workgroups.
+constexpr int kLeafRowsChunk = 2048;     // consecutive entries of a leaf that one workgroup takes per step
+constexpr int kLeafRowsMaxParts = 64;    // workgroups per leaf at the most
+struct GbdtLeafRowsForm { int block; int parts; int chunk_rows; };
+inline GbdtLeafRowsForm gbdt_leaf_sums_rows_form(int64_t total, int64_t nleaves) {
+    if (total <= 0 || nleaves <= 0) return {kBlock, 0, kLeafRowsChunk};
+    const int64_t want = (total + kLeafRowsChunk - 1) / kLeafRowsChunk;
+    return {kBlock, (int)(want < kLeafRowsMaxParts ? want : kLeafRowsMaxParts), kLeafRowsChunk};
+}
+
 constexpr int kGbdtPartRows = 1024;      // consecutive entries of a row list that one workgroup of the partition owns
 
 // The exact k-th largest |g h| of GOSS (ptr_gbdt_goss): a radix select over the keys' uint32 bit patterns, most significant digit first.

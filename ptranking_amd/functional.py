@@ -26,7 +26,7 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "gbdt_bag_mask", "gbdt_goss", "gbdt_partition_mask", "gbdt_add_tree_binned",
            "gbdt_best_split_cat", "gbdt_best_split_slots_cat", "gbdt_partition_cat", "gbdt_partition_segments_cat", "gbdt_add_tree_binned_cat",
            "gbdt_predict_cat", "gbdt_best_split_cst", "gbdt_best_split_slots_cst", "gbdt_leaf_counts", "gbdt_shap", "SHAP_TABLE_KEYS", "GBDT_MAX_BIN",
-           "GBDT_RECORD", "gbdt_predict_leaf", "gbdt_leaf_sums", "gbdt_add_by_leaf"]
+           "GBDT_RECORD", "gbdt_predict_leaf", "gbdt_leaf_sums", "gbdt_add_by_leaf", "gbdt_quantize_low", "gbdt_quant_levels", "gbdt_leaf_sums_rows"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
 # launch table, and it draws its own; irfgan_loss and adlist_loss are public too: they take a mode, as irgan_selected does)
@@ -1071,9 +1071,51 @@ def gbdt_quantize(grad, hess, flag=None, out=None):
     return qg, qh, expo, flag
 
 
-def gbdt_histogram(bins, qg, qh, rows, F, max_bin, hist=None, m=None):
+def gbdt_quant_levels(levels):
+    """num_grad_quant_bins as an int: a power of two in 2 .. 256, anything else raises ValueError."""
+    if isinstance(levels, (bool, np.bool_)) or not isinstance(levels, (int, np.integer)) or not 2 <= levels <= 256 or levels & (levels - 1):
+        raise ValueError(f"num_grad_quant_bins must be a power of two in 2 .. 256, got {levels!r}")
+    return int(levels)
+
+
+def gbdt_quantize_low(grad, hess, levels=4, stochastic=True, seed=0, draw=0, flag=None, out=None):
+    """gbdt_quantize with B = `levels` integer levels (a power of two in 2 .. 256): |qg| <= B / 2, |qh| <= B, expo = (log2(B / 2) - ex_g,
+    log2(B) - ex_h) for max|.| = fr 2^ex.  stochastic: q = floor(x + u) with the uniform u of the counter stream gbdt_bag_mask draws from,
+    keyed by (seed, 2 draw) for grad and (seed, 2 draw + 1) for hess and indexed by the row, so E[q] = x; otherwise q = rint(x).  The
+    outputs are gbdt_quantize's, and every kernel that takes those takes these (ptr_gbdt_quantize_low)."""
+    grad = _check("grad", grad)
+    if grad.dim() != 1:
+        raise ValueError(f"grad must be flat [rows], got {tuple(grad.shape)}")
+    hess = _check("hess", hess, shape=grad.shape)
+    levels = gbdt_quant_levels(levels)
+    if int(seed) != seed or not 0 <= int(seed) < 2 ** 64 or int(draw) != draw or not 0 <= int(draw) < 2 ** 62:
+        raise ValueError(f"seed must be an integer in 0 .. 2^64 - 1 and draw one in 0 .. 2^62 - 1, got {seed!r} and {draw!r}")
+    dev, n = grad.device, grad.numel()
+    flag = torch.zeros(1, device=dev, dtype=torch.int32) if flag is None else _check("flag", flag, torch.int32, (1,))
+    if out is None:
+        out = (torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.int32), torch.zeros(2, device=dev, dtype=torch.int32))
+    qg, qh = (_check(k, t, torch.int32, (n,)) for k, t in zip(("qg", "qh"), out[:2]))
+    expo = _check("expo", out[2], torch.int32, (2,))
+    state = torch.empty(2, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_quantize_low", _lib.ptr(grad), _lib.ptr(hess), n, levels, int(bool(stochastic)), C.c_uint64(int(seed)), C.c_int64(int(draw)),
+                  _lib.ptr(qg), _lib.ptr(qh), _lib.ptr(expo), _lib.ptr(flag), _lib.ptr(state), _lib.current_stream(dev))
+    return qg, qh, expo, flag
+
+
+def _gbdt_bounds(bounds):
+    """bounds = (bound_g, bound_h) of the packed histogram kernels as two ints in 1 .. 128 and 1 .. 256."""
+    bg, bh = (int(b) for b in bounds)
+    if not (1 <= bg <= 128 and 1 <= bh <= 256):
+        raise ValueError(f"bounds must be (1 .. 128, 1 .. 256), got {tuple(bounds)!r}")
+    return bg, bh
+
+
+def gbdt_histogram(bins, qg, qh, rows, F, max_bin, hist=None, m=None, bounds=None):
     """ADDS the rows of `rows` (int32 [m]; None: the first m rows, all by default) into hist, int64 [F, max_bin, 3] = (sum qg, sum qh,
-    count) per (feature, bin); hist=None starts from zeros.  Integer sums: the bits do not depend on the row order or the launch form."""
+    count) per (feature, bin); hist=None starts from zeros.  Integer sums: the bits do not depend on the row order or the launch form.
+    bounds = (bound_g, bound_h): the caller's promise that |qg| <= bound_g <= 128 and |qh| <= bound_h <= 256 (gbdt_quantize_low: B / 2 and
+    B); the packed kernel then sums the three values of a cell in one 64-bit LDS word and gives the same bits (ptr_gbdt_histogram_packed)."""
     bins = _gbdt_bins(bins, F)
     n, dev = bins.shape[0], bins.device
     max_bin = _gbdt_max_bin(max_bin)
@@ -1087,8 +1129,12 @@ def gbdt_histogram(bins, qg, qh, rows, F, max_bin, hist=None, m=None):
         raise ValueError(f"m={m} exceeds the row list")
     hist = torch.zeros((F, max_bin, 3), device=dev, dtype=torch.int64) if hist is None else _check("hist", hist, torch.int64, (F, max_bin, 3))
     with torch.cuda.device(dev):
-        _lib.call("ptr_gbdt_histogram", _lib.ptr(bins), bins.shape[1], n, _lib.ptr(qg), _lib.ptr(qh), _lib.ptr(rows), m, F, max_bin, _lib.ptr(hist),
-                  _lib.current_stream(dev))
+        if bounds is None:
+            _lib.call("ptr_gbdt_histogram", _lib.ptr(bins), bins.shape[1], n, _lib.ptr(qg), _lib.ptr(qh), _lib.ptr(rows), m, F, max_bin, _lib.ptr(hist),
+                      _lib.current_stream(dev))
+        else:
+            _lib.call("ptr_gbdt_histogram_packed", _lib.ptr(bins), bins.shape[1], n, _lib.ptr(qg), _lib.ptr(qh), _lib.ptr(rows), m, F, max_bin,
+                      *_gbdt_bounds(bounds), _lib.ptr(hist), _lib.current_stream(dev))
     return hist
 
 
@@ -1169,6 +1215,26 @@ def gbdt_add_leaf_values(scores, rows, offsets, values):
     return scores
 
 
+def gbdt_leaf_sums_rows(rows, offsets, qg, qh, sums=None):
+    """ADDS (qg[r], qh[r], 1) over the rows r = rows[i], offsets[l] <= i < offsets[l + 1], into sums[l], int64 [leaves, 3] (None: zeros):
+    rows and offsets as gbdt_add_leaf_values takes them.  A long leaf is split over several workgroups; integer reductions and one global
+    integer atomic per workgroup and value, so the bits depend on the data alone (ptr_gbdt_leaf_sums_rows)."""
+    rows = _check("rows", rows, torch.int32)
+    offsets = _check("offsets", offsets, torch.int32)
+    if rows.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("rows must be flat and offsets hold leaves + 1 entries")
+    nleaves, dev = offsets.numel() - 1, rows.device
+    qg = _check("qg", qg, torch.int32)
+    qh = _check("qh", qh, torch.int32, qg.shape)
+    if qg.dim() != 1:
+        raise ValueError(f"qg must be flat, got {tuple(qg.shape)}")
+    sums = torch.zeros((nleaves, 3), device=dev, dtype=torch.int64) if sums is None else _check("sums", sums, torch.int64, (nleaves, 3))
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_leaf_sums_rows", _lib.ptr(rows), _lib.ptr(offsets), nleaves, rows.numel(), _lib.ptr(qg), _lib.ptr(qh), qg.numel(), _lib.ptr(sums),
+                  _lib.current_stream(dev))
+    return sums
+
+
 def gbdt_predict(X, feature, threshold, left, right, value, tree_offsets, ntrees=None, default_left=None):
     """Scores of raw rows under flat tree arrays -> float32 [n]: per tree the row goes left on x <= threshold; a negative child is leaf ~i;
     tree t owns the nodes tree_offsets[t] .. tree_offsets[t + 1] and the values value[tree_offsets[t] + t ..].  The leaf values are summed
@@ -1240,11 +1306,12 @@ def gbdt_segment_items(counts, F, max_bin):
     return items, int(small.size), int(seg.size)
 
 
-def gbdt_histogram_segments(bins, qg, qh, rows, segs, F, max_bin, pool):
+def gbdt_histogram_segments(bins, qg, qh, rows, segs, F, max_bin, pool, bounds=None):
     """ADDS, for every segment (start, count, slot) of the host table segs [K, 3], the rows rows[start : start + count] into pool[slot]
     (int64 [slots, F, max_bin, 3], zeroed by the caller): each slot gets the integers gbdt_histogram gives for that row list.  At most two
     launches however many segments: the short ones in the direct form, the long ones cut into row chunks in the LDS form.  A segment that
-    leaves the row list or names a slot outside the pool is skipped."""
+    leaves the row list or names a slot outside the pool is skipped.  bounds: as in gbdt_histogram (ptr_gbdt_histogram_segments_packed; the work
+    list is the same, since the packed form keeps the grid and the row chunks)."""
     bins = _gbdt_bins(bins, F)
     n, dev = bins.shape[0], bins.device
     max_bin = _gbdt_max_bin(max_bin)
@@ -1261,9 +1328,13 @@ def gbdt_histogram_segments(bins, qg, qh, rows, segs, F, max_bin, pool):
         return pool
     items, n_direct, n_lds = gbdt_segment_items(np.where((host[:, 0] >= 0) & (host[:, 0] + host[:, 1] <= rows.numel()), host[:, 1], 0), F, max_bin)
     _, items_d = _gbdt_table("items", items, 3, dev)
+    head = (_lib.ptr(bins), bins.shape[1], n, _lib.ptr(qg), _lib.ptr(qh), _lib.ptr(rows), rows.numel(), _lib.ptr(segs_d), K, _lib.ptr(items_d), n_direct,
+            n_lds, F, max_bin)
     with torch.cuda.device(dev):
-        _lib.call("ptr_gbdt_histogram_segments", _lib.ptr(bins), bins.shape[1], n, _lib.ptr(qg), _lib.ptr(qh), _lib.ptr(rows), rows.numel(),
-                  _lib.ptr(segs_d), K, _lib.ptr(items_d), n_direct, n_lds, F, max_bin, _lib.ptr(pool), pool.shape[0], _lib.current_stream(dev))
+        if bounds is None:
+            _lib.call("ptr_gbdt_histogram_segments", *head, _lib.ptr(pool), pool.shape[0], _lib.current_stream(dev))
+        else:
+            _lib.call("ptr_gbdt_histogram_segments_packed", *head, *_gbdt_bounds(bounds), _lib.ptr(pool), pool.shape[0], _lib.current_stream(dev))
     return pool
 
 

@@ -123,6 +123,24 @@ on the training data with decay_rate=0 an unsampled, unconstrained model gets it
 refuse refit.  LambdaMART.refit(X, y, group) supplies the ranker's objective.  With init_model=None and pred_leaf=False every call and
 every model file is the one made before they existed; a continued or refitted model saves in the same three formats.
 
+Quantized-gradient training (use_quantized_grad, num_grad_quant_bins, stochastic_rounding, quant_train_renew_leaf: LightGBM 4's names;
+quant_seed is this project's own).  The rules are this project's own, stated in include/ptranking_amd.h and restated in
+tests/gbdt_quant_ref.py; nothing is compared with LightGBM and no parity is claimed.  Under use_quantized_grad=True a round's gradients
+are rounded to B = num_grad_quant_bins integer levels (a power of two in 2 .. 256, default 4): with max|g| = fr 2^ex, fr in [0.5, 1), the
+scale is 2^(log2(B / 2) - ex) for the gradients and 2^(log2(B) - ex) for the Hessians, so |qg| <= B / 2 and |qh| <= B.
+stochastic_rounding (True) takes q = floor(x + u) with one uniform u per row and value from the counter stream bagging draws from, keyed
+by (quant_seed, the tree counter), so E[q] = x, two fits give the same bits and a fit continued through init_model equals the unsplit fit
+bit for bit; False takes q = rint(x).  The integers and their power-of-two scale flow through the split scans, the constraints, sibling
+subtraction and leaf_value unchanged; what is new is the histogram kernel: the three sums of a (feature, bin) share one 64-bit LDS word,
+one LDS atomic per (row, feature) where the 30-bit kernel issues three, 8 bytes per cell where it keeps 20, flushed every
+floor((2^20 - 1) / B) rows, and bit-equal to the 30-bit kernel on the same integers.  quant_train_renew_leaf (False) also quantizes the
+round's gradients to 30 bits, grows the tree on the low-bit pair and takes every leaf's value from the 30-bit sums over the leaf's rows
+(ptr_gbdt_leaf_sums_rows): LightGBM recommends it for ranking objectives.  It costs exactly ONE more host read per tree, which
+host_reads counts, and it refuses active monotone constraints, as refit does.  The five keys are written to a model file only under
+use_quantized_grad=True; an older file loads with the defaults, and the format numbers, the trees, predict, refit, SHAP and init_model do
+not change.  With the switch off every call and every model file is the one made before the keys existed.  Not here: LightGBM's own
+scale (it divides by the maximum, not by a power of two) and its random stream.
+
 Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here:
 feature_fraction, EFB, DART.  There is no CPU path.
 """
@@ -146,13 +164,16 @@ DEFAULT_PARAMS = {"learning_rate": 0.1, "num_leaves": 31, "num_trees": 100, "min
                   "monotone_constraints": (), "monotone_constraints_method": "basic", "interaction_constraints": (),
                   # LambdaMART(objective='lambdarank_ndcg') alone reads these three; the other objectives and the bare booster ignore them
                   "lambdarank_truncation_level": 30, "lambdarank_norm": True, "sigmoid": 1.0,
-                  "objective_seed": 5}                    # LambdaMART(objective='rank_xendcg') alone reads it
+                  "objective_seed": 5,                    # LambdaMART(objective='rank_xendcg') alone reads it
+                  # quantized-gradient training: the first four names are LightGBM's, quant_seed is this project's own
+                  "use_quantized_grad": False, "num_grad_quant_bins": 4, "stochastic_rounding": True, "quant_train_renew_leaf": False, "quant_seed": 0}
 IGNORED_PARAMS = ("num_threads", "verbosity", "metric", "boosting_type", "objective", "eval_at")    # accepted, without a meaning here
 MODEL_FORMAT = 1                       # a model trained without use_missing
 MODEL_FORMAT_MISSING = 2               # one trained under it: format 1 with default_left per node and nan_bin per feature
 MODEL_FORMAT_CAT = 3                   # one with categorical features: format 1 or 2 plus categorical_feature, cat_index per node and cat_sets
 CAT_KEYS = ("categorical_feature", "cat_smooth")      # not among the parameters of a format 1 or 2 file
 CST_KEYS = ("monotone_constraints", "monotone_constraints_method", "interaction_constraints")   # in a model file only where one is active
+QUANT_KEYS = ("use_quantized_grad", "num_grad_quant_bins", "stochastic_rounding", "quant_train_renew_leaf", "quant_seed")   # likewise: only under the switch
 MONOTONE_METHODS = ("basic",)
 GROW_POLICIES = ("leafwise", "depthwise")
 SHAP_MAX_ELEMENTS = 63                 # distinct features on one root-to-leaf path: one lane each, within the quadrature rules of up to 32 nodes
@@ -186,7 +207,7 @@ def _params(params):
         raise ValueError("lambda_l2 must be >= 0 and no threshold may be NaN")
     for k in ("bagging_fraction", "top_rate", "other_rate"):
         p[k] = float(p[k])
-    for k in ("bagging_by_query", "use_missing"):
+    for k in ("bagging_by_query", "use_missing", "use_quantized_grad", "stochastic_rounding", "quant_train_renew_leaf"):
         if isinstance(p[k], (bool, np.bool_)):
             p[k] = bool(p[k])
         else:
@@ -221,6 +242,14 @@ def _params(params):
     p["lambdarank_truncation_level"], p["sigmoid"], p["lambdarank_norm"] = F.lambdarank_ndcg_settings(p["lambdarank_truncation_level"], p["sigmoid"],
                                                                                                    p["lambdarank_norm"])
     p["objective_seed"] = F.objective_seed(p["objective_seed"])
+    p["num_grad_quant_bins"] = F.gbdt_quant_levels(p["num_grad_quant_bins"])
+    seed = p["quant_seed"]
+    if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"quant_seed must be an integer in 0 .. 2^64 - 1, got {seed!r}")
+    p["quant_seed"] = int(seed)
+    if p["quant_train_renew_leaf"] and any(p["monotone_constraints"]):
+        raise ValueError("quant_train_renew_leaf is not available under monotone_constraints: the leaf values are clamped between their "
+                         "neighbours', and re-estimating them leaf by leaf would break the guarantee")
     return p
 
 
@@ -633,6 +662,11 @@ class GBDT:
         self._qg, self._qh = torch.empty_like(self._arange), torch.empty_like(self._arange)
         self._expo = torch.zeros(2, device=dev, dtype=torch.int32)
         self._flag = torch.zeros(1, device=dev, dtype=torch.int32)
+        # the one switch of both growers' histogram calls: under use_quantized_grad the packed kernels, told |qg| <= B / 2 and |qh| <= B
+        self._hist_kw = {"bounds": (p["num_grad_quant_bins"] // 2, p["num_grad_quant_bins"])} if p["use_quantized_grad"] else {}
+        self._q30 = None                                               # quant_train_renew_leaf: the round's 30-bit (qg, qh, expo)
+        if p["use_quantized_grad"] and p["quant_train_renew_leaf"]:
+            self._q30 = (torch.empty_like(self._arange), torch.empty_like(self._arange), torch.zeros(2, device=dev, dtype=torch.int32))
         self._lc = torch.zeros(1, device=dev, dtype=torch.int32)
         self._rec = torch.zeros((2, 9), device=dev, dtype=torch.int64)
         self._lrec = torch.zeros((max(p["num_leaves"], 2), 9), device=dev, dtype=torch.int64)      # a depth-wise level's records
@@ -798,16 +832,22 @@ class GBDT:
         sampled = self._sample(grad, hess) if sampling(p) else None
         if sampled is not None:
             grad, hess = sampled
-        F.gbdt_quantize(grad, hess, flag=self._flag, out=(self._qg, self._qh, self._expo))
+        if p["use_quantized_grad"]:                                        # low-bit gradients under the tree counter's draw; the 30-bit pair beside them for the leaves
+            F.gbdt_quantize_low(grad, hess, p["num_grad_quant_bins"], p["stochastic_rounding"], p["quant_seed"], len(self.trees), flag=self._flag,
+                                out=(self._qg, self._qh, self._expo))
+            if self._q30 is not None:
+                F.gbdt_quantize(grad, hess, flag=self._flag, out=self._q30)
+        else:
+            F.gbdt_quantize(grad, hess, flag=self._flag, out=(self._qg, self._qh, self._expo))
         pool[0].zero_()
         if sampled is None:
-            F.gbdt_histogram(self.bins, self._qg, self._qh, None, nf, mb, hist=pool[0])
+            F.gbdt_histogram(self.bins, self._qg, self._qh, None, nf, mb, hist=pool[0], **self._hist_kw)
         else:
             # the bag first, in order, then the rest: the tree grows on [0, m).  m is known on the device alone until the head read below (it
             # is the root's count), so the root's histogram runs over all n entries of a list whose out-of-bag entries are -1, which it skips
             F.gbdt_partition_mask(self._mask, out=self._rows, left_count=self._lc)
             torch.where(self._mask != 0, self._arange, self._none, out=self._tmp)
-            F.gbdt_histogram(self.bins, self._qg, self._qh, self._tmp, nf, mb, hist=pool[0])
+            F.gbdt_histogram(self.bins, self._qg, self._qh, self._tmp, nf, mb, hist=pool[0], **self._hist_kw)
         active = constraints(p)
         self._search(0, 0, self._root_tables() if active else None)
         head = torch.cat([self._rec[0], pool[0, 0].sum(0), self._expo.to(torch.int64), self._flag.to(torch.int64)]
@@ -823,11 +863,30 @@ class GBDT:
             self._rows.copy_(self._arange)
         grow = self._grow_depthwise if p["grow_policy"] == "depthwise" else self._grow_leafwise
         feature, threshold, left, right, starts, g_sum, h_sum, split_bin, go_left, cat_index, cat_sets = grow(head, bag)
-        if self._leaf_v is not None and len(g_sum) > 1:                   # a leaf stores float32(v * learning_rate) with its clamped v
+        if self._q30 is not None:
+            value = self._renewed_values(starts, bag)
+        elif self._leaf_v is not None and len(g_sum) > 1:                 # a leaf stores float32(v * learning_rate) with its clamped v
             value = np.array([np.float32(v * p["learning_rate"]) for v in self._leaf_v], np.float32)
         else:
             value = np.array([leaf_value(g, h, expo, p["lambda_l2"], p["learning_rate"]) for g, h in zip(g_sum, h_sum)], np.float32)
         return self._finish(feature, threshold, left, right, starts, value, bag, split_bin, go_left, cat_index, cat_sets)
+
+    def _renewed_values(self, starts, m):
+        """quant_train_renew_leaf: the leaves' values from the round's 30-bit gradients, fp32 by leaf index.  The tree grew on low-bit sums;
+        ptr_gbdt_leaf_sums_rows sums the 30-bit pair per leaf over the row list the grower holds (the list and offsets gbdt_add_leaf_values
+        gets), and ONE host read brings the sums and their exponents: host_reads grows by one per tree."""
+        p = self.params
+        order = sorted(range(len(starts)), key=lambda i: starts[i])
+        offsets = torch.from_numpy(np.array([starts[i] for i in order] + [m], np.int32)).to(self.scores.device)
+        qg, qh, expo = self._q30
+        sums = F.gbdt_leaf_sums_rows(self._rows[:m], offsets, qg, qh)
+        head = torch.cat([sums.reshape(-1), expo.to(torch.int64)]).cpu().numpy()
+        self.host_reads += 1
+        ex, s = (int(head[-2]), int(head[-1])), head[:-2].reshape(-1, 3)
+        value = np.zeros(len(starts), np.float32)
+        for j, i in enumerate(order):
+            value[i] = leaf_value(s[j, 0], s[j, 1], ex, p["lambda_l2"], p["learning_rate"])
+        return value
 
     def _root_tables(self):
         """The root's tables.  Its sums are known on the device alone before the head read, so its v = -G / (H + lambda_l2) is computed
@@ -903,7 +962,8 @@ class GBDT:
                 small, large = (lchild, rchild) if lchild.count <= rchild.count else (rchild, lchild)
                 small.slot, free = free, free + 1
                 pool[small.slot].zero_()
-                F.gbdt_histogram(self.bins, self._qg, self._qh, self._rows[small.start:small.start + small.count], nf, mb, hist=pool[small.slot])
+                F.gbdt_histogram(self.bins, self._qg, self._qh, self._rows[small.start:small.start + small.count], nf, mb, hist=pool[small.slot],
+                                 **self._hist_kw)
                 F.gbdt_hist_sub(pool[large.slot], pool[small.slot], out=pool[large.slot])          # the larger child, in the parent's slot
                 tables = self._cst_tables([lchild.cst, rchild.cst], [lchild.groups, rchild.groups]) if (mono or inter) else None
                 for k, c in enumerate((lchild, rchild)):
@@ -1032,7 +1092,7 @@ class GBDT:
                 c_slot[pairs, small] = fresh
                 pool[int(fresh[0]):int(fresh[-1]) + 1].zero_()
                 F.gbdt_histogram_segments(self.bins, self._qg, self._qh, self._rows, np.stack([c_start[pairs, small], c_count[pairs, small], fresh], axis=1),
-                                          nf, mb, pool)
+                                          nf, mb, pool, **self._hist_kw)
                 F.gbdt_hist_sub_segments(pool, np.stack([slot[keep][pairs], fresh, slot[keep][pairs]], axis=1))   # the larger child, in the parent's slot
                 sp, ss = np.nonzero(can[pairs])
                 out = self._lrec[:sp.size]
@@ -1277,6 +1337,8 @@ class GBDT:
         parameters); format 2 under it, with default_left per node and nan_bin per feature; format 3 with categorical features: format 1
         or 2 (by use_missing, with every parameter) plus categorical_feature, cat_index per node and cat_sets."""
         own = self.params if constraints(self.params) else {k: v for k, v in self.params.items() if k not in CST_KEYS}      # inactive: today's file
+        if not own["use_quantized_grad"]:                                  # likewise: without the switch, the file written before the keys existed
+            own = {k: v for k, v in own.items() if k not in QUANT_KEYS}
         if self.params["categorical_feature"]:
             head = dict(format=np.int64(MODEL_FORMAT_CAT), params=np.array(json.dumps(own)), edges=self.edges, nbins=self.nbins,
                         categorical_feature=np.array(self.params["categorical_feature"], np.int32))
