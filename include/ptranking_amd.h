@@ -1020,6 +1020,10 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *   ptr_gbdt_leaf_sums                           n, nleaves                               kind, threads per workgroup, workgroups, LDS bytes, the
  *                                                                                           most leaves of the LDS form (1024)
  *                                                                                           kind: 0 nothing, 1 LDS cells, 2 global atomics
+ *   ptr_gbdt_dart_walk                           n, F, max_nodes                          kind, threads per workgroup, workgroups, LDS bytes, the
+ *                                                (max_nodes: the largest listed tree)       most nodes of a tree walked from LDS (511), 1 where a
+ *                                                                                           tree of max_nodes nodes is, else 0
+ *                                                                                           kind: 0 nothing, 1 row tile in LDS, 2 direct
  *   ptr_irgan_sample, ptr_irgan_point_gen_fwd_bwd   L                                     G, queries per workgroup
  *   ptr_irgan_sel_fwd_bwd                        mode, L                                  G, queries per workgroup
  *   ptr_irfgan_point_sample, ptr_irfgan_pair_sample   L                                   G, queries per workgroup
@@ -1473,6 +1477,48 @@ int ptr_gbdt_histogram_segments_packed(const uint8_t *bins, int stride, int64_t 
                                        int max_bin, int bound_g, int bound_h, int64_t *pool, int nslots, void *stream);
 int ptr_gbdt_leaf_sums_rows(const int32_t *rows, const int32_t *offsets, int nleaves, int64_t total, const int32_t *qg, const int32_t *qh,
                             int64_t n, int64_t *sums, void *stream);
+
+/* ---- DART boosting for the tree trainer (csrc/gbdt_dart.hip; boosting='dart' of GBDT and LambdaMART with drop_rate, max_drop, skip_drop, uniform_drop,
+ * xgboost_dart_mode and drop_seed of ptranking_amd/gbdt.py; Rashmi & Gilad-Bachrach, "DART: Dropouts meet Multiple Additive Regression
+ * Trees").  ADDITIVE to ABI v8 too: PTR_ABI_VERSION stays 8 and every symbol above keeps its signature and its results bit for bit.  The
+ * parameter names are LightGBM's, the rule is this project's own, modelled on LightGBM's DART, and no parity with LightGBM (its random
+ * stream in particular) is claimed; tests/gbdt_dart_ref.py restates it.
+ *
+ * The rule of a round.  T droppable trees (those grown in this fit; the trees of an initial model are never dropped and carry no weight:
+ *   LightGBM's rule) with weights w_t (float64).  rate = min(drop_rate, max_drop / T) when max_drop > 0, else drop_rate.  uniform_drop:
+ *   p_t = rate; otherwise p_t = min(1, rate w_t / mean(w)); in float64, then rounded to fp32.  The whole round drops nothing iff
+ *   u(drop_seed, draw, 0xFFFFFFFF) < (float)skip_drop; otherwise tree t is dropped iff u(drop_seed, draw, t) < p_t, with
+ *   u(seed, draw, unit) = pl_uniform(pl_query_keys(seed, draw), unit) of the counter stream ptr_gbdt_bag_mask draws from and draw = the
+ *   trees of the booster so far.  With k trees dropped the new tree is grown on gradients taken at the scores WITHOUT them, at the
+ *   learning rate lr / (1 + k) (xgboost_dart_mode and k > 0: lr / (lr + k)); the dropped trees' leaf values are scaled by k / (k + 1)
+ *   (xgboost_dart_mode: k / (k + lr)) and added back.  w of the new tree is its learning rate, and a dropped tree's w is scaled with it.
+ *
+ * The forest in bin space.  nodes: two uint32 per node.  Word 0 = feature (bits 0 - 15) | split bin (16 - 23) | also-left bin (24 - 31): a
+ *   row goes left iff b <= split bin || b == also-left bin, b = bins[row][feature]; a node without an also-left bin stores its split bin
+ *   there.  Word 1 = left (bits 0 - 15) | right (16 - 31), each an int16; a child c < 0 is the leaf ~c.  So F <= 65535 and a tree holds at
+ *   most 32 767 nodes.  values: fp32.  tree_offsets int32 [ntrees + 1]: tree t owns the nodes tree_offsets[t] .. tree_offsets[t + 1] - 1
+ *   and the tree_offsets[t + 1] - tree_offsets[t] + 1 leaf values from tree_offsets[t] + t on (the layout of ptr_gbdt_predict's trees).
+ *
+ * ptr_gbdt_dart_walk: out[i] = in[i] + sign acc_i for the rows i < n of bins [n][stride] (16-byte aligned; the layout of ptr_gbdt_bin),
+ *   acc_i = 0.0f, then + values_t[leaf_t(bins_i)] for the listed trees t = list[0], .., list[k - 1] in that order: fp32 adds, rounded to
+ *   nearest, nothing contracted or reassociated, so numpy float32 restates a row bit for bit.  sign is +1 or -1 (PTR_ERR_INVALID_ARG
+ *   otherwise); out may be in.  A malformed tree (a cycle, a node or a feature out of range: the walk takes at most as many steps as the tree
+ *   has nodes) and a list entry outside 0 .. ntrees - 1 give the row NaN.  One launch, a workgroup of 256 threads per 256 consecutive rows.
+ *   Forms (ptr_launch_form): where 256 (stride + 4) <= 40 KiB the workgroup copies its rows' bins, one contiguous block, into LDS at a row
+ *   pitch of stride + 4 bytes (conflict-free for 64 rows reading one feature) and every bin is read from global memory once for all listed
+ *   trees; a wider matrix (the launcher decides by the stride it is given; ptr_launch_form assumes round_up(F, 16)) takes the direct form,
+ *   which reads the bins from global memory.  Either way the listed trees go through two LDS
+ *   buffers, tree j + 1 fetched while tree j is walked; a tree of more than 511 nodes is walked from global memory.  F > 65535:
+ *   PTR_ERR_UNSUPPORTED.
+ * ptr_gbdt_dart_select: sel[0] = the number of dropped trees, sel[1 ..] = their indices, ascending (sel int32 [T + 1]; entries behind the
+ *   count are left alone), under the rule above from p fp32 [T] on the device.  One workgroup.  skip_drop outside [0, 1] or a negative
+ *   draw: PTR_ERR_INVALID_ARG.
+ * ptr_gbdt_dart_scale: values[v] = (float)((double)values[v] * factor) over the leaf values of the listed trees (distinct; an entry
+ *   outside the forest is skipped).  The same two IEEE operations on the host keep its copy of the values bit-equal. */
+int ptr_gbdt_dart_walk(const float *in, float *out, const uint8_t *bins, int stride, int64_t n, int F, const uint32_t *nodes,
+                       const float *values, const int32_t *tree_offsets, int ntrees, const int32_t *list, int k, int sign, void *stream);
+int ptr_gbdt_dart_select(const float *p, int T, uint64_t seed, int64_t draw, float skip_drop, int32_t *sel, void *stream);
+int ptr_gbdt_dart_scale(float *values, const int32_t *tree_offsets, int ntrees, const int32_t *list, int k, double factor, void *stream);
 
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):

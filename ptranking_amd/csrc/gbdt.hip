@@ -720,21 +720,6 @@ struct PartByMask {                                                     // ptr_g
     }
 };
 
-// Inclusive sums of one value per thread over the workgroup's kBlock threads, through buf [kBlock] in LDS.  A thread's last access to buf
-// is to its own entry, behind a barrier: the next call may use the same buf at once.
-template <class T> __device__ __forceinline__ T block_scan_add(T *buf, T v) {
-    const int t = threadIdx.x;
-    buf[t] = v;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const T o = t >= d ? buf[t - d] : 0;
-        __syncthreads();
-        buf[t] += o;
-        __syncthreads();
-    }
-    return buf[t];
-}
-
 // *count = the entries of piece j of pred's list that go to the front.  Every thread of the workgroup calls it.
 template <class Pred> __device__ __forceinline__ void part_count(const Pred &pred, int j, int32_t *__restrict__ count) {
     __shared__ int32_t tot;

@@ -118,4 +118,54 @@ inline GbdtLeafSumsForm gbdt_leaf_sums_form(int64_t n, int64_t nleaves) {
     return {2, kBlock, groups, 0, kLeafSumsLdsLeaves};
 }
 
+// The forest walk of DART (ptr_gbdt_dart_walk, csrc/gbdt_dart.hip): a workgroup of 256 threads takes 256 consecutive rows through every
+// listed tree.  LDS budget, per workgroup:
+//   trees   two buffers (the tree walked and the next one, fetched meanwhile) of kDartLdsNodes packed nodes of 8 bytes and
+//           kDartLdsNodes + 1 leaf values of 4 bytes: 2 x (4088 + 2048) = 12 272 bytes, declared as kDartTreeBytes = 2 x 6144 = 12 KiB.  511
+//           nodes are the 512 leaves above everything people train with (31 .. 255) and above the reference's own grid (400);
+//   rows    the tile form keeps the 256 rows' bins at a pitch of stride + 4 bytes: 256 x 148 = 37 888 bytes at the 136 features of MSLR.
+// A compute unit has 160 KiB: at 136 features a workgroup declares 37 888 + 12 288 = 50 176 bytes, so three fit (150 528 bytes): 12 of the
+// 32 waves a compute unit holds.  The walk is a chain of dependent LDS reads (node, bin, node, ...), which those waves hide among
+// themselves; at 64 features (17 408 + 12 288 bytes) five fit.  kDartTileBytes = 40 KiB caps the tile where a third workgroup still fits
+// (3 x (40 960 + 12 288) = 159 744 <= 163 840): stride <= 144.  Beyond it the direct form reads the bins from global memory, one byte
+// per node at a random offset, and declares the trees' 12 KiB alone.  This arithmetic is a design estimate, not a measurement: what was
+// measured is in profiles/mi355x_gbdt_dart.json.
+constexpr int kDartLdsNodes = 511;       // most nodes of a tree that is walked from LDS; a larger tree is walked from global memory
+constexpr int kDartTreeBytes = 2 * 6144; // the two tree buffers
+constexpr int kDartTileBytes = 40 * 1024;   // most bytes of the row tile; a wider matrix takes the direct form
+constexpr int kDartMaxFeatures = 65535;  // a packed node keeps its feature in 16 bits
+constexpr int kDartMaxNodes = 32767;     // and its children in int16: at most 32 768 leaves
+
+// kind 0: nothing to launch (n == 0); 1: tile (the rows' bins in LDS); 2: direct (bins from global memory).  groups: the workgroups;
+// lds_bytes: what one declares; lds_nodes: kDartLdsNodes; staged: 1 where a tree of max_nodes nodes is walked from LDS, 0 from global memory.
+struct GbdtDartForm { int kind; int block; int groups; int lds_bytes; int lds_nodes; int staged; };
+inline GbdtDartForm gbdt_dart_walk_form_of_stride(int64_t n, int64_t stride, int64_t max_nodes) {      // what the launcher asks, with the matrix's own stride
+    const int staged = max_nodes <= kDartLdsNodes ? 1 : 0;
+    if (n <= 0) return {0, kBlock, 0, 0, kDartLdsNodes, staged};
+    const int groups = (int)((n + kBlock - 1) / kBlock);
+    const int64_t tile = (int64_t)kBlock * (stride + 4);
+    if (tile <= kDartTileBytes) return {1, kBlock, groups, (int)tile + kDartTreeBytes, kDartLdsNodes, staged};
+    return {2, kBlock, groups, kDartTreeBytes, kDartLdsNodes, staged};
+}
+inline GbdtDartForm gbdt_dart_walk_form(int64_t n, int F, int64_t max_nodes) {                      // for the stride ptr_gbdt_bin gives F features
+    return gbdt_dart_walk_form_of_stride(n, (int64_t)(F + kGbdtTile - 1) / kGbdtTile * kGbdtTile, max_nodes);
+}
+
+#if defined(__HIPCC__)
+// Inclusive sums of one value per thread over the workgroup's kBlock threads, through buf [kBlock] in LDS.  A thread's last access to buf
+// is to its own entry, behind a barrier: the next call may use the same buf at once.
+template <class T> __device__ __forceinline__ T block_scan_add(T *buf, T v) {
+    const int t = threadIdx.x;
+    buf[t] = v;
+    __syncthreads();
+    for (int d = 1; d < kBlock; d <<= 1) {
+        const T o = t >= d ? buf[t - d] : 0;
+        __syncthreads();
+        buf[t] += o;
+        __syncthreads();
+    }
+    return buf[t];
+}
+#endif
+
 }  // namespace ptr

@@ -26,7 +26,8 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "gbdt_bag_mask", "gbdt_goss", "gbdt_partition_mask", "gbdt_add_tree_binned",
            "gbdt_best_split_cat", "gbdt_best_split_slots_cat", "gbdt_partition_cat", "gbdt_partition_segments_cat", "gbdt_add_tree_binned_cat",
            "gbdt_predict_cat", "gbdt_best_split_cst", "gbdt_best_split_slots_cst", "gbdt_leaf_counts", "gbdt_shap", "SHAP_TABLE_KEYS", "GBDT_MAX_BIN",
-           "GBDT_RECORD", "gbdt_predict_leaf", "gbdt_leaf_sums", "gbdt_add_by_leaf", "gbdt_quantize_low", "gbdt_quant_levels", "gbdt_leaf_sums_rows"]
+           "GBDT_RECORD", "gbdt_predict_leaf", "gbdt_leaf_sums", "gbdt_add_by_leaf", "gbdt_quantize_low", "gbdt_quant_levels", "gbdt_leaf_sums_rows",
+           "gbdt_dart_pack", "gbdt_dart_walk", "gbdt_dart_select", "gbdt_dart_scale"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
 # launch table, and it draws its own; irfgan_loss and adlist_loss are public too: they take a mode, as irgan_selected does)
@@ -1935,3 +1936,93 @@ def gbdt_add_by_leaf(scores, leaf, values):
     with torch.cuda.device(scores.device):
         _lib.call("ptr_gbdt_add_by_leaf", _lib.ptr(scores), scores.numel(), _lib.ptr(leaf), _lib.ptr(values), values.numel(), _lib.current_stream(scores.device))
     return scores
+
+
+# ---- DART boosting (csrc/gbdt_dart.hip; include/ptranking_amd.h states the rule, the packed node and the contracts).
+GBDT_DART_MAX_FEATURES = 65535                                             # a packed node keeps its feature in 16 bits
+GBDT_DART_MAX_NODES = 32767                                                # and its children in int16: at most 32 768 leaves
+
+
+def gbdt_dart_pack(feature, bin, left, right, also_left=None):
+    """The packed nodes of one tree, numpy int32 [nodes, 2] (the bits of the two uint32 words): word 0 = feature | split bin << 16 |
+    also-left bin << 24, word 1 = left | right << 16 as int16.  also_left (per node a bin, or -1): a node without one stores its split
+    bin.  ValueError for a feature above 65535, a bin outside 0 .. 255 or a child outside int16.  Runs on the host."""
+    feature, bin, left, right = (np.asarray(a).astype(np.int64).reshape(-1) for a in (feature, bin, left, right))
+    also = bin if also_left is None else np.where(np.asarray(also_left).reshape(-1) < 0, bin, np.asarray(also_left).astype(np.int64).reshape(-1))
+    if not (feature.size == bin.size == left.size == right.size == also.size):
+        raise ValueError("feature, bin, left, right and also_left must hold one entry per node")
+    if feature.size > GBDT_DART_MAX_NODES:
+        raise ValueError(f"a packed tree holds at most {GBDT_DART_MAX_NODES} nodes, got {feature.size}")
+    if feature.size and (feature.min() < 0 or feature.max() > GBDT_DART_MAX_FEATURES or min(bin.min(), also.min()) < 0 or max(bin.max(), also.max()) > 255
+                         or min(left.min(), right.min()) < -32768 or max(left.max(), right.max()) > 32767):
+        raise ValueError("a packed node takes a feature in 0 .. 65535, bins in 0 .. 255 and children in int16")
+    out = np.empty((feature.size, 2), np.uint32)
+    out[:, 0] = (feature | (bin << 16) | (also << 24)).astype(np.uint32)
+    out[:, 1] = ((left & 0xFFFF) | ((right & 0xFFFF) << 16)).astype(np.uint32)
+    return out.view(np.int32)
+
+
+def gbdt_dart_walk(scores, bins, F, nodes, values, tree_offsets, trees, sign=1, out=None):
+    """out[i] = scores[i] + sign * (the leaf values the listed trees give binned row i, summed in list order in fp32) -> out (default:
+    scores itself, in place).  bins uint8 [n, round_up(F, 16)]; nodes int32 [N, 2] (gbdt_dart_pack), values float32, tree_offsets int32
+    [ntrees + 1]: the resident forest; trees int32 [k] on the device: the list; sign +1 or -1.  A malformed tree or a list entry outside
+    the forest gives the row NaN (ptr_gbdt_dart_walk)."""
+    scores = _check("scores", scores)
+    bins = _gbdt_bins(bins, F)
+    n, dev = bins.shape[0], bins.device
+    if scores.dim() != 1 or scores.numel() != n or not scores.is_contiguous():
+        raise ValueError(f"scores must be flat and contiguous [{n}], got {tuple(scores.shape)}")
+    if int(F) > GBDT_DART_MAX_FEATURES:
+        raise ValueError(f"a packed node keeps its feature in 16 bits: F must be <= {GBDT_DART_MAX_FEATURES}, got {F}")
+    if sign not in (1, -1):
+        raise ValueError(f"sign must be +1 or -1, got {sign!r}")
+    out = scores if out is None else _check("out", out, torch.float32, (n,))
+    if not out.is_contiguous():
+        raise ValueError("out must be contiguous")
+    nodes = _check("nodes", nodes, torch.int32)
+    if nodes.dim() != 2 or nodes.shape[1] != 2:
+        raise ValueError(f"nodes must be [nodes, 2] int32, got {tuple(nodes.shape)}")
+    values = _check("values", values)
+    tree_offsets = _check("tree_offsets", tree_offsets, torch.int32)
+    trees = _check("trees", trees, torch.int32)
+    if values.dim() != 1 or tree_offsets.dim() != 1 or tree_offsets.numel() < 1 or trees.dim() != 1:
+        raise ValueError("values, tree_offsets (at least one entry) and trees must be flat")
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_dart_walk", _lib.ptr(scores), _lib.ptr(out), _lib.ptr(bins), bins.shape[1], n, int(F), _lib.ptr(nodes), _lib.ptr(values),
+                  _lib.ptr(tree_offsets), tree_offsets.numel() - 1, _lib.ptr(trees), trees.numel(), int(sign), _lib.current_stream(dev))
+    return out
+
+
+def gbdt_dart_select(p, seed, draw, skip_drop, out=None):
+    """The trees one DART round drops -> sel int32 [T + 1] on the device: sel[0] = their number k, sel[1 : 1 + k] = their indices,
+    ascending.  p float32 [T] on the device: the drop probability per tree.  Tree t is dropped iff u(seed, draw, t) < p[t]; the whole round
+    drops nothing iff u(seed, draw, 0xFFFFFFFF) < float32(skip_drop) (ptr_gbdt_dart_select)."""
+    p = _check("p", p)
+    if p.dim() != 1:
+        raise ValueError(f"p must be flat [trees], got {tuple(p.shape)}")
+    if not 0.0 <= float(skip_drop) <= 1.0:
+        raise ValueError(f"skip_drop must be in [0, 1], got {skip_drop}")
+    if int(draw) < 0:
+        raise ValueError(f"draw must be >= 0, got {draw}")
+    T, dev = p.numel(), p.device
+    out = torch.zeros(T + 1, device=dev, dtype=torch.int32) if out is None else _check("out", out, torch.int32, (T + 1,))
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_dart_select", _lib.ptr(p), T, _seed64(seed), int(draw), C.c_float(float(skip_drop)), _lib.ptr(out), _lib.current_stream(dev))
+    return out
+
+
+def gbdt_dart_scale(values, tree_offsets, trees, factor):
+    """values[v] = float32(float64(values[v]) * factor) over the leaf values of the listed trees (int32 [k] on the device, distinct), in
+    place (ptr_gbdt_dart_scale)."""
+    values = _check("values", values)
+    tree_offsets = _check("tree_offsets", tree_offsets, torch.int32)
+    trees = _check("trees", trees, torch.int32)
+    if values.dim() != 1 or not values.is_contiguous() or tree_offsets.dim() != 1 or tree_offsets.numel() < 1 or trees.dim() != 1:
+        raise ValueError("values (contiguous), tree_offsets (at least one entry) and trees must be flat")
+    factor = float(factor)
+    if factor != factor:
+        raise ValueError("factor is NaN")
+    with torch.cuda.device(values.device):
+        _lib.call("ptr_gbdt_dart_scale", _lib.ptr(values), _lib.ptr(tree_offsets), tree_offsets.numel() - 1, _lib.ptr(trees), trees.numel(),
+                  C.c_double(factor), _lib.current_stream(values.device))
+    return values

@@ -141,8 +141,33 @@ use_quantized_grad=True; an older file loads with the defaults, and the format n
 not change.  With the switch off every call and every model file is the one made before the keys existed.  Not here: LightGBM's own
 scale (it divides by the maximum, not by a power of two) and its random stream.
 
+DART boosting (GBDT(params, boosting='dart') and LambdaMART(params, boosting='dart'): like the objective, the boosting type is an
+argument, and boosting_type='dart' in the dict alone stays refused as it always was; a reference dict is passed as
+LambdaMART(d, boosting=d.pop('boosting_type')).  In the dict: drop_rate 0.1, max_drop 50, skip_drop 0.5, uniform_drop False, xgboost_dart_mode False, drop_seed 4:
+LightGBM's names and defaults; Rashmi & Gilad-Bachrach, "DART: Dropouts meet Multiple Additive Regression Trees").  The rule is this
+project's own, modelled on LightGBM's DART, stated in include/ptranking_amd.h and restated in tests/gbdt_dart_ref.py; nothing is compared
+with LightGBM and no parity is claimed.  With T droppable trees of weights w_t: rate = min(drop_rate, max_drop / T) when max_drop > 0
+(max_drop <= 0: no cap); p_t = rate under uniform_drop, otherwise min(1, rate * w_t / mean(w)), in float64, then rounded to fp32.  A round
+drops nothing iff u(drop_seed, t, 0xFFFFFFFF) < skip_drop, else tree j iff u(drop_seed, t, j) < p_j, with the counter stream bagging uses
+and t the trees so far.  GBDT.begin_round() selects the drops on the device (ONE host read of the list, which host_reads counts),
+subtracts the dropped trees from the resident scores in one launch of ptr_gbdt_dart_walk and returns the scores, at which the caller
+takes its gradients; under 'gbdt' it launches nothing and returns scores.  update() then raises unless begin_round() ran since the last
+update; it grows the tree exactly as under 'gbdt' (monotone constraints and quant_train_renew_leaf included) at the learning rate
+lr / (1 + k) with k trees dropped (xgboost_dart_mode and k > 0: lr / (lr + k)), adds it, scales the dropped trees' values by k / (k + 1)
+(xgboost_dart_mode: k / (k + lr)) on the device and on the host with the same two IEEE operations, value = float32(float64(value) *
+factor), and adds them back (a second launch); last_drop holds the dropped trees' indices.  w of a tree is its learning rate at birth and
+is scaled with the tree.  The walk kernel keeps the forest resident in bin space (8 bytes per node, appended by the host tree by tree),
+copies a workgroup's 256 rows of bins into LDS once for all listed trees and stages the trees through two LDS buffers; so DART needs at
+most 65535 features and num_leaves <= 32768 (ValueError otherwise).  The trees of an init_model are never dropped and carry no weight
+(LightGBM's rule), so a fit split in two does NOT equal the unsplit fit under 'dart'.  LambdaMART.fit calls begin_round(); with an
+eval_set the validation rows are binned once under the trainer's edges (a NaN in a feature without a NaN bin raises) and their scores
+follow every round through the same kernel; early_stopping_rounds raises, since later rounds rewrite earlier trees (as in LightGBM), and
+best_iteration stays None.  The model formats are unchanged (the trees carry their final values); the seven keys are written to a model
+file only under 'dart'.  With 'gbdt' every call and every model file is the one made before the keys existed.  Not here: categorical_feature
+under 'dart' (ValueError: the resident forest keeps no left sets), LightGBM's own random stream.
+
 Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here:
-feature_fraction, EFB, DART.  There is no CPU path.
+feature_fraction, EFB, and DART from the dict's boosting_type alone (it is the argument boosting='dart', above).  There is no CPU path.
 """
 import copy
 import json
@@ -153,7 +178,8 @@ import torch
 from . import functional as F
 from . import letor, tree
 
-__all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS", "constraints", "shap_tables", "SHAP_MAX_ELEMENTS"]
+__all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS", "constraints", "shap_tables", "SHAP_MAX_ELEMENTS", "dart_rates",
+           "dart_probabilities"]
 
 # LightGBM's names, so the reference's lightgbm_para_dict passes through.  min_sum_hessian_in_leaf = 1e-3 is LightGBM's default too; the
 # reference's own dict sets 200, which suits LightGBM's built-in lambdarank Hessians, not the sums of tree.hip.
@@ -166,25 +192,31 @@ DEFAULT_PARAMS = {"learning_rate": 0.1, "num_leaves": 31, "num_trees": 100, "min
                   "lambdarank_truncation_level": 30, "lambdarank_norm": True, "sigmoid": 1.0,
                   "objective_seed": 5,                    # LambdaMART(objective='rank_xendcg') alone reads it
                   # quantized-gradient training: the first four names are LightGBM's, quant_seed is this project's own
-                  "use_quantized_grad": False, "num_grad_quant_bins": 4, "stochastic_rounding": True, "quant_train_renew_leaf": False, "quant_seed": 0}
-IGNORED_PARAMS = ("num_threads", "verbosity", "metric", "boosting_type", "objective", "eval_at")    # accepted, without a meaning here
+                  "use_quantized_grad": False, "num_grad_quant_bins": 4, "stochastic_rounding": True, "quant_train_renew_leaf": False, "quant_seed": 0,
+                  # DART (the argument boosting='dart', which sets boosting_type here): the other six are read under it alone (LightGBM's names and defaults)
+                  "boosting_type": "gbdt", "drop_rate": 0.1, "max_drop": 50, "skip_drop": 0.5, "uniform_drop": False, "xgboost_dart_mode": False,
+                  "drop_seed": 4}
+IGNORED_PARAMS = ("num_threads", "verbosity", "metric", "objective", "eval_at")    # accepted, without a meaning here
 MODEL_FORMAT = 1                       # a model trained without use_missing
 MODEL_FORMAT_MISSING = 2               # one trained under it: format 1 with default_left per node and nan_bin per feature
 MODEL_FORMAT_CAT = 3                   # one with categorical features: format 1 or 2 plus categorical_feature, cat_index per node and cat_sets
 CAT_KEYS = ("categorical_feature", "cat_smooth")      # not among the parameters of a format 1 or 2 file
 CST_KEYS = ("monotone_constraints", "monotone_constraints_method", "interaction_constraints")   # in a model file only where one is active
 QUANT_KEYS = ("use_quantized_grad", "num_grad_quant_bins", "stochastic_rounding", "quant_train_renew_leaf", "quant_seed")   # likewise: only under the switch
+DART_KEYS = ("boosting_type", "drop_rate", "max_drop", "skip_drop", "uniform_drop", "xgboost_dart_mode", "drop_seed")   # likewise: only under 'dart'
+BOOSTING_TYPES = ("gbdt", "dart")
 MONOTONE_METHODS = ("basic",)
 GROW_POLICIES = ("leafwise", "depthwise")
 SHAP_MAX_ELEMENTS = 63                 # distinct features on one root-to-leaf path: one lane each, within the quadrature rules of up to 32 nodes
 SAMPLE_STRATEGIES = ("bagging", "goss")
 
 
-def _params(params):
+def _params(params, boosting=None):
+    """The checked parameters.  boosting: the `boosting` argument of GBDT / LambdaMART (None: 'gbdt').  boosting_type='dart' in the dict
+    alone stays refused, as it always was: DART is switched on by the argument, as the objective is (a dict that names the same type
+    beside the argument passes, so a booster's own params rebuild it)."""
     p = dict(DEFAULT_PARAMS)
     for k, v in (params or {}).items():
-        if k == "boosting_type" and v != "gbdt":
-            raise ValueError(f"boosting_type {v!r} is not implemented: only 'gbdt'")
         if k in IGNORED_PARAMS:
             continue
         if k not in DEFAULT_PARAMS:
@@ -207,7 +239,16 @@ def _params(params):
         raise ValueError("lambda_l2 must be >= 0 and no threshold may be NaN")
     for k in ("bagging_fraction", "top_rate", "other_rate"):
         p[k] = float(p[k])
-    for k in ("bagging_by_query", "use_missing", "use_quantized_grad", "stochastic_rounding", "quant_train_renew_leaf"):
+    if boosting is not None and boosting not in BOOSTING_TYPES:
+        raise ValueError(f"boosting {boosting!r} is not implemented: only 'gbdt' and 'dart'")
+    if p["boosting_type"] not in BOOSTING_TYPES:
+        raise ValueError(f"boosting_type {p['boosting_type']!r} is not implemented: only 'gbdt' and 'dart'")
+    if p["boosting_type"] != "gbdt" and p["boosting_type"] != boosting:
+        raise ValueError(f"boosting_type {p['boosting_type']!r} in the parameter dict is not implemented: only 'gbdt'; DART is the argument "
+                         f"boosting='dart' of GBDT and LambdaMART, with its six settings in the dict")
+    if boosting is not None:
+        p["boosting_type"] = boosting
+    for k in ("bagging_by_query", "use_missing", "use_quantized_grad", "stochastic_rounding", "quant_train_renew_leaf", "uniform_drop", "xgboost_dart_mode"):
         if isinstance(p[k], (bool, np.bool_)):
             p[k] = bool(p[k])
         else:
@@ -247,6 +288,24 @@ def _params(params):
     if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
         raise ValueError(f"quant_seed must be an integer in 0 .. 2^64 - 1, got {seed!r}")
     p["quant_seed"] = int(seed)
+    for k in ("drop_rate", "skip_drop"):
+        try:
+            p[k] = float(p[k])
+        except (TypeError, ValueError):
+            raise ValueError(f"{k} must be a number in [0, 1], got {p[k]!r}") from None
+        if not 0.0 <= p[k] <= 1.0:
+            raise ValueError(f"{k} must be in [0, 1], got {p[k]}")
+    for k in ("max_drop", "drop_seed"):
+        if isinstance(p[k], (bool, np.bool_)) or not isinstance(p[k], (int, np.integer)):
+            raise ValueError(f"{k} must be an integer, got {p[k]!r}")
+        p[k] = int(p[k])
+    if not 0 <= p["drop_seed"] < 2 ** 64:
+        raise ValueError(f"drop_seed must be in 0 .. 2^64 - 1, got {p['drop_seed']}")
+    if p["boosting_type"] == "dart":
+        if p["categorical_feature"]:
+            raise ValueError("boosting_type 'dart' with categorical_feature is not implemented: the resident forest keeps no left sets")
+        if p["num_leaves"] > F.GBDT_DART_MAX_NODES + 1:
+            raise ValueError(f"boosting_type 'dart' keeps a node's children in int16: num_leaves must be <= {F.GBDT_DART_MAX_NODES + 1}, got {p['num_leaves']}")
     if p["quant_train_renew_leaf"] and any(p["monotone_constraints"]):
         raise ValueError("quant_train_renew_leaf is not available under monotone_constraints: the leaf values are clamped between their "
                          "neighbours', and re-estimating them leaf by leaf would break the guarantee")
@@ -321,6 +380,29 @@ def _interaction_groups(p, nf):
             raise ValueError(f"interaction_constraints {max(g)} with {nf} columns")
     rest = frozenset(range(nf)) - frozenset().union(*groups)
     return groups + ([rest] if rest else [])
+
+
+def dart_rates(p, k):
+    """(the learning rate of a tree grown with k trees dropped, the factor the dropped trees are scaled by), float64: lr / (1 + k) and
+    k / (k + 1); under xgboost_dart_mode and k > 0, lr / (lr + k) and k / (k + lr).  k = 0: (lr, 1)."""
+    lr = float(p["learning_rate"])
+    if k <= 0:
+        return lr, 1.0
+    if p["xgboost_dart_mode"]:
+        return lr / (lr + k), k / (k + lr)
+    return lr / (1.0 + k), k / (k + 1.0)
+
+
+def dart_probabilities(p, w):
+    """The drop probability of every droppable tree from the weights w -> float32 [T]: rate = min(drop_rate, max_drop / T) when
+    max_drop > 0; uniform_drop: rate; otherwise min(1, rate * w / mean(w)); float64, then rounded."""
+    w = np.asarray(w, np.float64).reshape(-1)
+    rate = float(p["drop_rate"])
+    if p["max_drop"] > 0 and w.size:
+        rate = min(rate, p["max_drop"] / w.size)
+    if p["uniform_drop"] or not w.size:
+        return np.full(w.size, rate, np.float64).astype(np.float32)
+    return np.minimum(1.0, rate * w / w.mean()).astype(np.float32)
 
 
 def _bagging(p):
@@ -594,11 +676,11 @@ _SHAP_QUAD = shap_quadrature()
 
 class GBDT:
     """The booster.  GBDT(params, X=None): params under LightGBM's names (DEFAULT_PARAMS; the keys of IGNORED_PARAMS are accepted and
-    ignored; boosting_type other than 'gbdt' raises).  Under grow_policy='leafwise' update() costs one host synchronisation per split: the
+    ignored; boosting_type other than 'gbdt' raises).  boosting='dart': DART, where every round is begin_round(), then update().  Under grow_policy='leafwise' update() costs one host synchronisation per split: the
     host reads the two children's records (72 bytes each) to pick the next leaf; under 'depthwise' one per level.  host_reads counts them."""
 
-    def __init__(self, params=None, X=None, device=None):
-        self.params = _params(params)
+    def __init__(self, params=None, X=None, device=None, boosting=None):
+        self.params = _params(params, boosting)
         self.trees = []                    # per tree: dict(feature, threshold, left, right, value) of numpy arrays
         self.edges = self.nbins = None     # host copies (the model file carries them)
         self.nan_bin = None                # under use_missing: the NaN bin per feature, -1 where training saw no NaN
@@ -613,6 +695,8 @@ class GBDT:
         self.n = 0
         self.host_reads = 0                # device-to-host reads inside update(), over the booster's life: what a growth policy costs
         self._qid = None
+        self.last_drop = ()                # under 'dart': the indices (into trees) of the trees the last round dropped
+        self._dart = None                  # under 'dart', after fit_bins: the resident forest in bin space and the round's state
         if X is not None:
             self.fit_bins(X)
 
@@ -652,6 +736,8 @@ class GBDT:
             self.edges, self.nbins = bin_edges(host, p["max_bin"], **({"categorical": cats} if cats else {}))
         Xd = _device_matrix(X if isinstance(X, torch.Tensor) else host, dev)
         self.n, self.F = host.shape
+        if p["boosting_type"] == "dart" and self.F > F.GBDT_DART_MAX_FEATURES:
+            raise ValueError(f"boosting_type 'dart' keeps a node's feature in 16 bits: at most {F.GBDT_DART_MAX_FEATURES} features, got {self.F}")
         self._edges_d, self._nbins_d = torch.from_numpy(self.edges).to(dev), torch.from_numpy(self.nbins).to(dev)
         self._nan_bin_d = torch.from_numpy(self.nan_bin).to(dev) if p["use_missing"] else None
         self.bins = F.gbdt_bin(Xd, self._edges_d, self._nbins_d, nan_bin=self._nan_bin_d)
@@ -695,6 +781,11 @@ class GBDT:
             self.best_iteration = None
             self._flat = self._shap = None
             self.scores = self.predict(Xd, check_finite=False)             # the bits predict goes on giving: each new tree is added after them
+        self.last_drop, self._dart = (), None
+        if p["boosting_type"] == "dart":
+            # base: the trees of an initial model, never dropped; w: the droppable trees' weights; nodes / values / offsets: the forest on the
+            # device (None until the first tree), used: its (nodes, values) in use; drop: the round begin_round opened, (indices, device list)
+            self._dart = {"base": len(self.trees), "w": [], "nodes": None, "values": None, "offsets": None, "used": (0, 0), "drop": None}
         return self
 
     def _take_bins(self, model, host):
@@ -829,6 +920,11 @@ class GBDT:
         if self.n == 0 or self.edges is None:
             raise RuntimeError("call fit_bins(X) first")
         p, nf, mb, pool = self.params, self.F, self.params["max_bin"], self._pool
+        dart = self._dart
+        if dart is not None and dart["drop"] is None:
+            raise RuntimeError("boosting_type 'dart': call begin_round() before update() and take the gradients at the scores it returns")
+        k = len(dart["drop"][0]) if dart is not None else 0
+        self._tree_lr = dart_rates(p, k)[0] if dart is not None else p["learning_rate"]      # the learning rate of the tree about to be grown
         sampled = self._sample(grad, hess) if sampling(p) else None
         if sampled is not None:
             grad, hess = sampled
@@ -866,10 +962,13 @@ class GBDT:
         if self._q30 is not None:
             value = self._renewed_values(starts, bag)
         elif self._leaf_v is not None and len(g_sum) > 1:                 # a leaf stores float32(v * learning_rate) with its clamped v
-            value = np.array([np.float32(v * p["learning_rate"]) for v in self._leaf_v], np.float32)
+            value = np.array([np.float32(v * self._tree_lr) for v in self._leaf_v], np.float32)
         else:
-            value = np.array([leaf_value(g, h, expo, p["lambda_l2"], p["learning_rate"]) for g, h in zip(g_sum, h_sum)], np.float32)
-        return self._finish(feature, threshold, left, right, starts, value, bag, split_bin, go_left, cat_index, cat_sets)
+            value = np.array([leaf_value(g, h, expo, p["lambda_l2"], self._tree_lr) for g, h in zip(g_sum, h_sum)], np.float32)
+        t = self._finish(feature, threshold, left, right, starts, value, bag, split_bin, go_left, cat_index, cat_sets)
+        if dart is not None:
+            self._dart_end_round()
+        return t
 
     def _renewed_values(self, starts, m):
         """quant_train_renew_leaf: the leaves' values from the round's 30-bit gradients, fp32 by leaf index.  The tree grew on low-bit sums;
@@ -885,7 +984,7 @@ class GBDT:
         ex, s = (int(head[-2]), int(head[-1])), head[:-2].reshape(-1, 3)
         value = np.zeros(len(starts), np.float32)
         for j, i in enumerate(order):
-            value[i] = leaf_value(s[j, 0], s[j, 1], ex, p["lambda_l2"], p["learning_rate"])
+            value[i] = leaf_value(s[j, 0], s[j, 1], ex, p["lambda_l2"], self._tree_lr)
         return value
 
     def _root_tables(self):
@@ -1010,7 +1109,95 @@ class GBDT:
                                    up(t["right"], np.int32), up(value, np.float32), also_left=None if also is None else up(also, np.int32))
         self.trees.append(t)
         self._flat = self._shap = None
+        if self._dart is not None:
+            self._dart_append(F.gbdt_dart_pack(t["feature"], split_bin, t["left"], t["right"], also), value)
         return t
+
+    # ---- DART: the resident forest in bin space and the two halves of a round
+    def _dart_append(self, nodes, value):
+        """Appends a finished tree (packed on the host) to the preallocated device buffers of the forest; they double when full."""
+        d, dev = self._dart, self.scores.device
+        un, uv = d["used"]
+        T = len(d["w"])
+        need = (un + nodes.shape[0], uv + value.size, T + 2)
+        if d["nodes"] is None or need[0] > d["nodes"].shape[0] or need[1] > d["values"].numel() or need[2] > d["offsets"].numel():
+            per, cap = max(self.params["num_leaves"], 2), max(2 * T, self.params["num_trees"], 16)
+            grown = (torch.zeros((max(cap * (per - 1), need[0]), 2), device=dev, dtype=torch.int32), torch.zeros(max(cap * per, need[1]), device=dev, dtype=torch.float32),
+                     torch.zeros(cap + 1, device=dev, dtype=torch.int32))
+            if d["nodes"] is not None:
+                grown[0][:un].copy_(d["nodes"][:un]); grown[1][:uv].copy_(d["values"][:uv]); grown[2][:T + 1].copy_(d["offsets"][:T + 1])
+            d["nodes"], d["values"], d["offsets"] = grown
+        if nodes.shape[0]:
+            d["nodes"][un:need[0]].copy_(torch.from_numpy(np.ascontiguousarray(nodes)))
+        d["values"][uv:need[1]].copy_(torch.from_numpy(np.ascontiguousarray(value, dtype=np.float32)))
+        d["offsets"][T + 1:T + 2].fill_(need[0])
+        d["used"] = need[:2]
+        d["w"].append(float(self._tree_lr))
+
+    def dart_walk(self, scores, bins, sign):
+        """scores += sign * (the values the trees the open round dropped give the binned rows), in place, through ptr_gbdt_dart_walk: what
+        begin_round and update do to the training scores, for other rows binned under the trainer's edges (bin_rows), such as a validation
+        set's.  Before update() the forest holds the old values, behind it the rescaled ones.  Nothing is launched for a round without drops."""
+        d = self._dart
+        drop = d["drop"] if d["drop"] is not None else d.get("closed")
+        if drop is None or not drop[0]:
+            return scores
+        T = len(d["w"])
+        return F.gbdt_dart_walk(scores, bins, self.F, d["nodes"], d["values"], d["offsets"][:T + 1], drop[1], sign)
+
+    def bin_rows(self, X):
+        """Rows X (numpy array or tensor [m, F]) binned under the trainer's edges -> device uint8 [m, round_up(F, 16)].  A NaN or an infinity
+        raises as in predict; under use_missing a NaN in a feature that keeps no NaN bin raises, as for the rows of an initial model."""
+        Xd = _device_matrix(X, self._dev())
+        if Xd.dim() != 2 or Xd.shape[1] != self.edges.shape[0]:
+            raise ValueError(f"X must be [rows, {self.edges.shape[0]}], got {tuple(Xd.shape)}")
+        _require_values(Xd, self.params["use_missing"])
+        if self.params["use_missing"]:
+            lacking = torch.isnan(Xd).any(dim=0).cpu().numpy() & (self.nan_bin < 0)
+            for f in np.nonzero(lacking)[0][:1]:
+                raise ValueError(f"feature {int(f)} holds a NaN, and the trainer keeps no NaN bin for it (nan_bin is -1): its training data held none")
+        return F.gbdt_bin(Xd, self._edges_d, self._nbins_d, nan_bin=self._nan_bin_d)
+
+    def begin_round(self):
+        """Opens a boosting round -> the scores to take the gradients at.  Under 'gbdt' that is `scores` and nothing is launched.  Under
+        'dart' the round's drops are selected on the device (ptr_gbdt_dart_select; ONE host read of the list, which host_reads counts), the
+        dropped trees are subtracted from the resident scores in place in one launch (ptr_gbdt_dart_walk, sign -1), and update() puts
+        them back rescaled.  last_drop holds the dropped trees' indices."""
+        d = self._dart
+        if d is None:
+            return self.scores
+        if self.n == 0 or self.edges is None:
+            raise RuntimeError("call fit_bins(X) first")
+        if d["drop"] is not None:
+            raise RuntimeError("begin_round() was called already: update() closes the round")
+        p, T, dev = self.params, len(d["w"]), self.scores.device
+        idx, lst = [], None
+        if T:
+            sel = F.gbdt_dart_select(torch.from_numpy(dart_probabilities(p, d["w"])).to(dev), p["drop_seed"], len(self.trees), p["skip_drop"])
+            host = sel.cpu().numpy()                                       # the one read of this round's list
+            self.host_reads += 1
+            idx, lst = [int(t) for t in host[1:1 + int(host[0])]], sel[1:1 + int(host[0])]
+        d["drop"] = (idx, lst)
+        self.last_drop = tuple(d["base"] + t for t in idx)
+        self.dart_walk(self.scores, self.bins, -1)
+        return self.scores
+
+    def _dart_end_round(self):
+        """update() under 'dart', behind the new tree: the dropped trees' values are rescaled on the device and on the host by the same two
+        IEEE operations, then added back to the resident scores (sign +1); their weights are scaled with them."""
+        d = self._dart
+        idx, lst = d["drop"]
+        if idx:
+            factor = dart_rates(self.params, len(idx))[1]
+            T = len(d["w"])
+            F.gbdt_dart_scale(d["values"], d["offsets"][:T + 1], lst, factor)
+            for t in idx:
+                tree = self.trees[d["base"] + t]
+                tree["value"] = (tree["value"].astype(np.float64) * factor).astype(np.float32)
+                d["w"][t] *= factor
+            self._flat = self._shap = None                                 # the device copy predict keeps holds the old values
+        d["closed"], d["drop"] = d["drop"], None
+        self.dart_walk(self.scores, self.bins, +1)
 
     def _grow_depthwise(self, head, m):
         """Depth-wise growth from the root's record (head, as update read it): every level is one batched pass over all its leaves
@@ -1296,7 +1483,7 @@ class GBDT:
         cats = p["categorical_feature"]
         _require_values(Xd, p["use_missing"], *((cats, p["max_bin"]) if cats else ()))
         stop = self.best_iteration or len(self.trees)
-        new = GBDT(p, device=self._device)
+        new = GBDT(p, device=self._device, boosting=p["boosting_type"])
         new.edges, new.nbins = np.array(self.edges), np.array(self.nbins)
         new.nan_bin = None if self.nan_bin is None else np.array(self.nan_bin)
         new.trees = [_copy_tree(t) for t in self.trees[:stop]]
@@ -1339,6 +1526,8 @@ class GBDT:
         own = self.params if constraints(self.params) else {k: v for k, v in self.params.items() if k not in CST_KEYS}      # inactive: today's file
         if not own["use_quantized_grad"]:                                  # likewise: without the switch, the file written before the keys existed
             own = {k: v for k, v in own.items() if k not in QUANT_KEYS}
+        if own["boosting_type"] != "dart":                                 # likewise
+            own = {k: v for k, v in own.items() if k not in DART_KEYS}
         if self.params["categorical_feature"]:
             head = dict(format=np.int64(MODEL_FORMAT_CAT), params=np.array(json.dumps(own)), edges=self.edges, nbins=self.nbins,
                         categorical_feature=np.array(self.params["categorical_feature"], np.int32))
@@ -1361,7 +1550,8 @@ class GBDT:
             fmt = int(z["format"])
             if fmt not in (MODEL_FORMAT, MODEL_FORMAT_MISSING, MODEL_FORMAT_CAT):
                 raise ValueError(f"{path}: model format {fmt}, this version reads {MODEL_FORMAT}, {MODEL_FORMAT_MISSING} and {MODEL_FORMAT_CAT}")
-            self = cls(json.loads(str(z["params"])), device=device)
+            own = json.loads(str(z["params"]))
+            self = cls(own, device=device, boosting=own.get("boosting_type"))
             cats = fmt == MODEL_FORMAT_CAT
             if bool(self.params["categorical_feature"]) != cats or (cats and self.params["categorical_feature"] != tuple(z["categorical_feature"].tolist())):
                 raise ValueError(f"{path}: model format {fmt} with categorical_feature={self.params['categorical_feature']}")
@@ -1403,10 +1593,10 @@ class LambdaMART:
     t's uniforms under draw = t (the tree counter), and the same five settings do not apply to it."""
 
     def __init__(self, params=None, objective="lambdarank", weighting="DeltaNDCG", hessian="sum", pair_type=None, epsilon=1.0,
-                 gain_type="Power", device=None):
+                 gain_type="Power", device=None, boosting=None):
         if objective not in tree.OBJECTIVES:
             raise ValueError(f"objective {objective!r} (supported: {', '.join(map(repr, tree.OBJECTIVES))})")
-        self.params = _params(params)
+        self.params = _params(params, boosting)
         self.objective = objective
         self.kind, default_pairs = tree.OBJECTIVES[objective]
         self.pair_type = default_pairs if pair_type is None else pair_type
@@ -1426,7 +1616,7 @@ class LambdaMART:
         self.device = torch.device("cuda" if device is None else device)
         self.booster = None
         self.evals_result = []
-        self.best_iteration = self.best_score = None
+        self.best_iteration = self.best_score = self.valid_scores = None
 
     def grad_hess(self, scores, res, out=None, draw=0):
         """The round's gradient and Hessian per document, on the device: one launch per length class of tree.bucket_queries, exactly as
@@ -1474,11 +1664,15 @@ class LambdaMART:
         init_model (a GBDT, a LambdaMART or the path of a saved model): the rounds are ADDED to that model's trees (GBDT.fit_bins): the
         training scores and the validation scores start at its predictions, num_boost_round / num_trees count the added rounds,
         evals_result holds the added rounds, and best_iteration counts all trees."""
+        dart = self.params["boosting_type"] == "dart"
+        if dart and early_stopping_rounds is not None:
+            raise ValueError("early_stopping_rounds is not available under boosting_type 'dart': later rounds rewrite earlier trees, so no "
+                             "earlier round's model can be returned")
         res = tree._Resident(y, group, self.device)
         X = X if isinstance(X, torch.Tensor) else np.asarray(X)
         if X.shape[0] != res.n_docs:
             raise ValueError(f"X holds {X.shape[0]} rows, the groups {res.n_docs}")
-        self.booster = GBDT(self.params, device=self.device).fit_bins(X, group=np.asarray(group).reshape(-1),
+        self.booster = GBDT(self.params, device=self.device, boosting=self.params["boosting_type"]).fit_bins(X, group=np.asarray(group).reshape(-1),
                                                                       **({} if init_model is None else {"init_model": init_model}))
         base = len(self.booster.trees)                                     # the initial model's trees: the rounds count on from them
         self.evals_result, self.best_iteration, self.best_score = [], None, None
@@ -1494,16 +1688,21 @@ class LambdaMART:
             yv = torch.from_numpy(np.ascontiguousarray(np.asarray(yv).reshape(-1), dtype=np.float32)).to(self.device)
             sv = self.booster.predict(Xv, check_finite=False) if base else torch.zeros(Xv.shape[0], device=self.device, dtype=torch.float32)
             valid = (Xv, yv, self.padded_index(eval_group, self.device), sv)
+            bins_v = self.booster.bin_rows(Xv) if dart else None        # once: the dropped trees are walked over them every round
         elif early_stopping_rounds is not None:
             raise ValueError("early_stopping_rounds needs an eval_set")
         gh = (torch.empty_like(self.booster.scores), torch.empty_like(self.booster.scores))
         for it in range(base + 1, base + rounds + 1):
-            self.grad_hess(self.booster.scores, res, gh, draw=len(self.booster.trees))      # the tree counter, as bagging's draws
+            self.grad_hess(self.booster.begin_round(), res, gh, draw=len(self.booster.trees))      # the tree counter, as bagging's draws
+            if dart and valid is not None:
+                self.booster.dart_walk(valid[3], bins_v, -1)               # the dropped trees' old values leave the validation scores
             self.booster.update(*gh)
             if valid is None:
                 continue
             Xv, yv, index, sv = valid
             sv += self.booster.predict(Xv, num_iteration=it, first_tree=it - 1, check_finite=False)      # the new tree alone: the same fp32 sum
+            if dart:
+                self.booster.dart_walk(sv, bins_v, +1)                     # and come back rescaled
             score = self.ndcg_at(sv, yv, None, eval_at, index=index)
             self.evals_result.append(score)
             if self.best_score is None or score > self.best_score:
@@ -1515,6 +1714,7 @@ class LambdaMART:
         if early_stopping_rounds is None:
             self.best_iteration = None
         self.booster.best_iteration = self.best_iteration
+        self.valid_scores = None if valid is None else valid[3]           # the validation scores the rounds tracked, on the device
         return self
 
     def predict(self, X, num_iteration=None, pred_contrib=False, pred_leaf=False):
