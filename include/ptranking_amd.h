@@ -1520,6 +1520,55 @@ int ptr_gbdt_dart_walk(const float *in, float *out, const uint8_t *bins, int str
 int ptr_gbdt_dart_select(const float *p, int T, uint64_t seed, int64_t draw, float skip_drop, int32_t *sel, void *stream);
 int ptr_gbdt_dart_scale(float *values, const int32_t *tree_offsets, int ntrees, const int32_t *list, int k, double factor, void *stream);
 
+/* ---- Linear trees for the tree trainer (csrc/gbdt_linear.hip; linear_tree and linear_lambda of ptranking_amd/gbdt.py, LightGBM's names).
+ * ADDITIVE to ABI v8 too: PTR_ABI_VERSION stays 8 and every symbol above keeps its signature and its results bit for bit.  The rule is this
+ * project's own, modelled on LightGBM's LinearTreeLearner; nothing is compared with LightGBM and no parity is claimed;
+ * tests/gbdt_linear_ref.py restates it in float64 numpy.
+ *
+ * The rule.  A tree grows exactly as without the switch.  Then, per leaf:
+ *   1. Regressors: P = the distinct features of the nodes on the root-to-leaf path, in order of first appearance from the root; k = |P|;
+ *      PTR_GBDT_LINEAR_MAX_FEATURES = 30.
+ *   2. Rows: the leaf's entries of the grower's row list (the bag under bagging or GOSS).  A row is usable iff none of its k regressors is
+ *      NaN; m_u counts the usable rows, in integers.
+ *   3. Moments, float64, from the round's fp32 gradients g and Hessians h (the pair quantization is handed, after GOSS's re-weighting):
+ *      z = (x_P1 .. x_Pk, 1), A = sum h z z^T, b = sum g z over the usable rows.
+ *   4. Solve: L = linear_lambda on the k feature diagonals, 0 on the intercept; Cholesky of A + L without pivoting; c = -(A + L)^-1 b.
+ *   5. Fallback, the leaf stays constant: k = 0 (status 1); k > 30 (2); m_u < k + 1 (3); a pivot p_j that is not finite or not
+ *      > 2^-40 (A + L)_jj (4: the relative floor is part of the rule, not a tolerance; a regressor that is constant over the leaf is
+ *      collinear with the intercept and lands here); a solution entry that is not finite (5).  Status 0: fitted.
+ *   6. Stored per tree, beside its arrays: leaf_features int32 [leaves][30] padded with -1 (a constant leaf: all -1), leaf_coeff float64
+ *      [leaves][30] = c_j lr, leaf_const float64 [leaves] = c_(k+1) lr, lr the tree's learning rate; value[leaf] stays the constant value.
+ *   7. A leaf's output for a row: value[leaf] where the leaf is constant or a regressor of the row is NaN, else
+ *      (float)(const + sum_j coeff_j (double)x_Pj), float64, the terms added in path order, each product rounded, then the sum.
+ *   8. A tree's outputs are added in fp32 in tree order, so the resident training scores stay ptr_gbdt_predict_linear's bit for bit.
+ *
+ * ptr_gbdt_linear_moments: X fp32 [n][F] raw rows, rows int32 [m] the row list, items int32 [nitems][3] = (leaf, first entry, entries <=
+ *   1024) listed by the host, feats int32 [leaves][30], nfeat int32 [leaves] = k, g and h fp32 [n].  Item i writes its partial to
+ *   ws[i] float64 [32][32]: entry [r][c], r <= c <= k, is A_rc, entry [r][k + 1] is b_r (the upper triangle alone is defined), and its
+ *   usable rows to usable[i].  A row index outside 0 .. n - 1 is skipped; a malformed item sums nothing.  v_mfma_f64_16x16x4_f64, four
+ *   entries per step; no float atomic: two runs give the same bits.  Per element |ws - exact| <= (m + 2) 2^-53 sum |h z_r z_c| in any order.
+ * ptr_gbdt_linear_solve: item_offsets int32 [leaves + 1]: leaf l owns the partials item_offsets[l] .. item_offsets[l + 1] - 1, added in that
+ *   order.  One wavefront per leaf.  Writes coeff float64 [leaves][30], cst float64 [leaves] (zeros for a leaf that falls back), status
+ *   int32 [leaves] and m_u int32 [leaves].  lambda must be finite and >= 0.
+ * ptr_gbdt_predict_linear: out[i] = the outputs (rule 7) of the trees first_tree .. stop - 1 for raw row i, 0.0f + each in tree order in
+ *   fp32.  The tree arrays are ptr_gbdt_predict's (default_left may be NULL: a NaN then goes right); the three leaf arrays follow the
+ *   layout of value.  A malformed tree or a regressor outside 0 .. F - 1 gives NaN.
+ * ptr_gbdt_add_tree_linear: scores[i] += the output of ONE tree (tree_offsets int32 [2] = 0, nodes) for every row of X, the same walk and
+ *   the same device function. */
+#define PTR_GBDT_LINEAR_MAX_FEATURES 30
+int ptr_gbdt_linear_moments(const float *X, int64_t n, int F, const int32_t *rows, int64_t m, const int32_t *items, int64_t nitems,
+                            const int32_t *feats, const int32_t *nfeat, int leaves, const float *g, const float *h, double *ws, int32_t *usable,
+                            void *stream);
+int ptr_gbdt_linear_solve(const double *ws, const int32_t *usable, int64_t nitems, const int32_t *item_offsets, const int32_t *nfeat, int leaves,
+                          double lambda, double lr, double *coeff, double *cst, int32_t *status, int32_t *usable_out, void *stream);
+int ptr_gbdt_predict_linear(const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                            const int32_t *right, const float *value, const int32_t *tree_offsets, const uint8_t *default_left,
+                            const int32_t *leaf_features, const double *leaf_coeff, const double *leaf_const, int first_tree, int stop, float *out,
+                            void *stream);
+int ptr_gbdt_add_tree_linear(float *scores, const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
+                             const int32_t *right, const float *value, const int32_t *tree_offsets, const uint8_t *default_left,
+                             const int32_t *leaf_features, const double *leaf_coeff, const double *leaf_const, void *stream);
+
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):
  *   "<label> qid:<id> <fid>:<val> ... [# comment]", feature ids one-indexed unless one_indexed == 0 (Yahoo! sets,

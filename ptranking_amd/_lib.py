@@ -157,6 +157,10 @@ SIGNATURES = {
     "ptr_gbdt_dart_walk": [_vp, _vp, _vp, _i, C.c_int64, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
     "ptr_gbdt_dart_select": [_vp, _i, _u64, C.c_int64, _f, _vp, _vp],
     "ptr_gbdt_dart_scale": [_vp, _vp, _i, _vp, _i, C.c_double, _vp],
+    "ptr_gbdt_linear_moments": [_vp, C.c_int64, _i, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
+    "ptr_gbdt_linear_solve": [_vp, _vp, C.c_int64, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp],
+    "ptr_gbdt_predict_linear": [_vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "ptr_gbdt_add_tree_linear": [_vp, _vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ptr_letor_scan":[C.c_char_p, _i, _vp, _vp, _vp],
     "ptr_letor_load": [C.c_char_p, _i, _f, C.c_int64, C.c_int32, C.c_int64, _vp, _i, _vp, _vp, _vp],
 }

@@ -166,6 +166,53 @@ template <class T> __device__ __forceinline__ T block_scan_add(T *buf, T v) {
     }
     return buf[t];
 }
+
+constexpr int kSetWords = 4;             // a left set: 256 bits, bit b in word b / 64
+
+// One row's walk down a tree of nn nodes (nn + 1 leaves; a child c < 0 is the leaf ~c) -> the node it ends in.  goes_left(node, f) decides at
+// a node that splits on feature f, which the walk has checked against F.  The walk takes nn steps at the most and stops at an index out of
+// range, so a malformed tree (a cycle, a node or feature out of range) ends it on something gbdt_is_leaf rejects.
+template <class GoesLeft> __device__ __forceinline__ int gbdt_walk(int nn, int F, const int32_t *__restrict__ feature, const int32_t *__restrict__ left,
+                                                                   const int32_t *__restrict__ right, const GoesLeft &goes_left) {
+    int node = nn > 0 ? 0 : ~0;
+    for (int step = 0; step < nn && node >= 0; ++step) {
+        if (node >= nn) break;
+        const int f = feature[node];
+        if (f < 0 || f >= F) break;
+        node = goes_left(node, f) ? left[node] : right[node];
+    }
+    return node;
+}
+__device__ __forceinline__ bool gbdt_is_leaf(int node, int nn) { return node < 0 && ~node <= nn; }
+
+// The categorical nodes of a walk (the *_cat entry points): cat_index [nodes] is -1 at a numeric node, else the node's left set
+// cat_sets[cat_index] (kSetWords int64 each, ncat of them).  The tables are device memory and read as untrusted: an index at or past ncat,
+// or a node whose kind is not its feature's (is_cat [F]), is a malformed tree: -2, which the walks turn into NaN.
+struct GbdtCatWalk { const uint8_t *is_cat; const int32_t *cat_index; const int64_t *cat_sets; int ncat; };
+__device__ __forceinline__ int gbdt_cat_node(const GbdtCatWalk &c, int node, int f) {
+    const int ci = c.cat_index[node];
+    const bool isc = c.is_cat[f] != 0;
+    if (ci < 0) return isc ? -2 : -1;
+    return isc && ci < c.ncat ? ci : -2;
+}
+__device__ __forceinline__ bool gbdt_in_set(const int64_t *__restrict__ set, int b) { return (((unsigned long long)set[b >> 6]) >> (b & 63)) & 1ull; }     // b in 0 .. 255
+
+// How a raw value decides at node `at` (an index over the nodes of ALL trees) that splits on feature f: the one predicate of every walk over
+// raw rows (prediction, the leaf counts and the one fractions of TreeSHAP).  bad: a malformed categorical table.
+template <bool kCat> __device__ __forceinline__ bool gbdt_raw_goes_left(float xv, int at, int f, const float *__restrict__ threshold,
+                                                                        const uint8_t *__restrict__ default_left, const GbdtCatWalk &cat, bool &bad) {
+    if constexpr (kCat) {
+        const int ci = gbdt_cat_node(cat, at, f);
+        if (ci == -2) { bad = true; return false; }
+        if (ci >= 0) {                                                  // a NaN follows the node's direction; what is no code 0 .. 255 is in no set
+            if (xv != xv) return default_left && default_left[at] != 0;
+            if (!(xv >= 0.0f && xv <= 255.0f)) return false;
+            const int c = (int)xv;
+            return (float)c == xv && gbdt_in_set(cat.cat_sets + (int64_t)ci * kSetWords, c);
+        }
+    }
+    return (default_left && xv != xv) ? default_left[at] != 0 : xv <= threshold[at];       // a NaN follows the node's direction
+}
 #endif
 
 }  // namespace ptr

@@ -27,7 +27,9 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "gbdt_best_split_cat", "gbdt_best_split_slots_cat", "gbdt_partition_cat", "gbdt_partition_segments_cat", "gbdt_add_tree_binned_cat",
            "gbdt_predict_cat", "gbdt_best_split_cst", "gbdt_best_split_slots_cst", "gbdt_leaf_counts", "gbdt_shap", "SHAP_TABLE_KEYS", "GBDT_MAX_BIN",
            "GBDT_RECORD", "gbdt_predict_leaf", "gbdt_leaf_sums", "gbdt_add_by_leaf", "gbdt_quantize_low", "gbdt_quant_levels", "gbdt_leaf_sums_rows",
-           "gbdt_dart_pack", "gbdt_dart_walk", "gbdt_dart_select", "gbdt_dart_scale"]
+           "gbdt_dart_pack", "gbdt_dart_walk", "gbdt_dart_select", "gbdt_dart_scale",
+           "gbdt_linear_items", "gbdt_linear_moments", "gbdt_linear_solve", "gbdt_predict_linear", "gbdt_add_tree_linear", "GBDT_LINEAR_MAX_FEATURES",
+           "GBDT_LINEAR_CHUNK_ROWS", "GBDT_LINEAR_STATUS"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
 # launch table, and it draws its own; irfgan_loss and adlist_loss are public too: they take a mode, as irgan_selected does)
@@ -2026,3 +2028,123 @@ def gbdt_dart_scale(values, tree_offsets, trees, factor):
         _lib.call("ptr_gbdt_dart_scale", _lib.ptr(values), _lib.ptr(tree_offsets), tree_offsets.numel() - 1, _lib.ptr(trees), trees.numel(),
                   C.c_double(factor), _lib.current_stream(values.device))
     return values
+
+
+# ---- linear trees (csrc/gbdt_linear.hip; include/ptranking_amd.h states the rule, the workspace layout and the contracts).
+GBDT_LINEAR_MAX_FEATURES = 30                                              # regressors of a leaf at the most (PTR_GBDT_LINEAR_MAX_FEATURES)
+GBDT_LINEAR_CHUNK_ROWS = 1024                                              # entries of the row list per item (kLinChunkRows)
+GBDT_LINEAR_STATUS = ("fitted", "no feature", "too many features", "too few usable rows", "pivot below the floor", "solution not finite")
+
+
+def gbdt_linear_items(offsets, nfeat):
+    """The work list of gbdt_linear_moments, on the host: offsets [leaves + 1] the leaves' segments of the row list, nfeat [leaves] their
+    regressor counts -> (items int32 [nitems, 3] = (leaf, first entry, entries <= GBDT_LINEAR_CHUNK_ROWS), item_offsets int32
+    [leaves + 1]).  A leaf of no regressor or of more than GBDT_LINEAR_MAX_FEATURES gets no item: it stays constant."""
+    offsets, nfeat = np.asarray(offsets, np.int64).reshape(-1), np.asarray(nfeat, np.int64).reshape(-1)
+    if offsets.size != nfeat.size + 1 or (np.diff(offsets) < 0).any() or (offsets.size and offsets[0] < 0):
+        raise ValueError("offsets must ascend from >= 0 and hold one entry more than nfeat")
+    items, item_offsets = [], [0]
+    for l in range(nfeat.size):
+        if 1 <= nfeat[l] <= GBDT_LINEAR_MAX_FEATURES:
+            first = np.arange(offsets[l], offsets[l + 1], GBDT_LINEAR_CHUNK_ROWS)
+            items += [(l, int(f), int(min(GBDT_LINEAR_CHUNK_ROWS, offsets[l + 1] - f))) for f in first]
+        item_offsets.append(len(items))
+    return np.array(items, np.int32).reshape(-1, 3), np.array(item_offsets, np.int32)
+
+
+def _linear_leaf_tables(feats, nfeat):
+    feats, nfeat = _check("feats", feats, torch.int32), _check("nfeat", nfeat, torch.int32)
+    if feats.dim() != 2 or feats.shape[1] != GBDT_LINEAR_MAX_FEATURES or nfeat.dim() != 1 or nfeat.numel() != feats.shape[0]:
+        raise ValueError(f"feats must be [leaves, {GBDT_LINEAR_MAX_FEATURES}] and nfeat [leaves], got {tuple(feats.shape)} and {tuple(nfeat.shape)}")
+    return feats, nfeat
+
+
+def gbdt_linear_moments(X, rows, items, feats, nfeat, grad, hess):
+    """The per-item partial moments of the leaves' linear fits -> (ws float64 [nitems, 32, 32], usable int32 [nitems]).  X float32 [n, F]
+    raw rows; rows int32 [m] the row list; items int32 [nitems, 3] (gbdt_linear_items, on the device); feats int32 [leaves, 30] padded
+    with -1 and nfeat int32 [leaves]: the regressors; grad, hess float32 [n].  ws[i, r, c] for r <= c <= k is sum h z_r z_c over the
+    item's usable rows, ws[i, r, k + 1] is sum g z_r, z = (x_P1 .. x_Pk, 1); the rest of a slot is undefined (ptr_gbdt_linear_moments)."""
+    X = _check("X", X)
+    if X.dim() != 2:
+        raise ValueError(f"X must be [rows, features], got {tuple(X.shape)}")
+    n, dev = X.shape[0], X.device
+    rows, items = _check("rows", rows, torch.int32), _check("items", items, torch.int32)
+    if rows.dim() != 1 or items.dim() != 2 or items.shape[1] != 3:
+        raise ValueError(f"rows must be flat and items [nitems, 3], got {tuple(rows.shape)} and {tuple(items.shape)}")
+    feats, nfeat = _linear_leaf_tables(feats, nfeat)
+    grad, hess = _check("grad", grad, shape=(n,)), _check("hess", hess, shape=(n,))
+    ws = torch.empty((items.shape[0], 32, 32), device=dev, dtype=torch.float64)
+    usable = torch.zeros(items.shape[0], device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_linear_moments", _lib.ptr(X), n, X.shape[1], _lib.ptr(rows), rows.numel(), _lib.ptr(items), items.shape[0], _lib.ptr(feats),
+                  _lib.ptr(nfeat), nfeat.numel(), _lib.ptr(grad), _lib.ptr(hess), _lib.ptr(ws), _lib.ptr(usable), _lib.current_stream(dev))
+    return ws, usable
+
+
+def gbdt_linear_solve(ws, usable, item_offsets, nfeat, linear_lambda, lr):
+    """The leaves' fits from their partial moments -> (coeff float64 [leaves, 30], const float64 [leaves], status int32 [leaves], m_u int32
+    [leaves]).  item_offsets int32 [leaves + 1]: the partials of a leaf, added in order; the ridge term on the k feature diagonals; Cholesky
+    without pivoting under the relative pivot floor 2^-40; c = -(A + L)^-1 b times lr.  status indexes GBDT_LINEAR_STATUS; a leaf that
+    falls back gets zeros (ptr_gbdt_linear_solve)."""
+    ws, usable = _check("ws", ws, torch.float64), _check("usable", usable, torch.int32)
+    if ws.dim() != 3 or tuple(ws.shape[1:]) != (32, 32) or usable.dim() != 1 or usable.numel() != ws.shape[0]:
+        raise ValueError(f"ws must be [nitems, 32, 32] and usable [nitems], got {tuple(ws.shape)} and {tuple(usable.shape)}")
+    item_offsets, nfeat = _check("item_offsets", item_offsets, torch.int32), _check("nfeat", nfeat, torch.int32)
+    leaves, dev = nfeat.numel(), ws.device
+    if item_offsets.dim() != 1 or item_offsets.numel() != leaves + 1:
+        raise ValueError(f"item_offsets must be [{leaves + 1}], got {tuple(item_offsets.shape)}")
+    lam = float(linear_lambda)
+    if not 0.0 <= lam < float("inf"):
+        raise ValueError(f"linear_lambda must be finite and >= 0, got {linear_lambda!r}")
+    coeff = torch.zeros((leaves, GBDT_LINEAR_MAX_FEATURES), device=dev, dtype=torch.float64)
+    const = torch.zeros(leaves, device=dev, dtype=torch.float64)
+    status, mu = torch.zeros(leaves, device=dev, dtype=torch.int32), torch.zeros(leaves, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.call("ptr_gbdt_linear_solve", _lib.ptr(ws), _lib.ptr(usable), ws.shape[0], _lib.ptr(item_offsets), _lib.ptr(nfeat), leaves, C.c_double(lam),
+                  C.c_double(float(lr)), _lib.ptr(coeff), _lib.ptr(const), _lib.ptr(status), _lib.ptr(mu), _lib.current_stream(dev))
+    return coeff, const, status, mu
+
+
+def _linear_walk_arrays(X, feature, threshold, left, right, value, tree_offsets, default_left, leaf_features, leaf_coeff, leaf_const):
+    X = _check("X", X)
+    if X.dim() != 2:
+        raise ValueError(f"X must be [rows, features], got {tuple(X.shape)}")
+    tree_offsets = _check("tree_offsets", tree_offsets, torch.int32)
+    total, nodes = tree_offsets.numel() - 1, feature.numel()
+    feature, left, right = (_check(k, t, torch.int32, (nodes,)) for k, t in zip(("feature", "left", "right"), (feature, left, right)))
+    threshold = _check("threshold", threshold, shape=(nodes,))
+    value = _check("value", value, shape=(nodes + total,))
+    if default_left is not None:
+        default_left = _check("default_left", default_left, torch.uint8, (nodes,))
+    leaf_features = _check("leaf_features", leaf_features, torch.int32, (nodes + total, GBDT_LINEAR_MAX_FEATURES))
+    leaf_coeff = _check("leaf_coeff", leaf_coeff, torch.float64, (nodes + total, GBDT_LINEAR_MAX_FEATURES))
+    leaf_const = _check("leaf_const", leaf_const, torch.float64, (nodes + total,))
+    return X, total, (feature, threshold, left, right, value, tree_offsets, default_left, leaf_features, leaf_coeff, leaf_const)
+
+
+def gbdt_predict_linear(X, feature, threshold, left, right, value, tree_offsets, leaf_features, leaf_coeff, leaf_const, first_tree=0, stop=None,
+                        default_left=None):
+    """Scores of raw rows under flat arrays of linear trees -> float32 [n]: the walk of gbdt_predict; a leaf's output is value[leaf] where
+    leaf_features[leaf, 0] < 0 or a regressor of the row is NaN, else float32(leaf_const + sum_j leaf_coeff_j * float64(x_j)) in float64 in
+    path order; the outputs of the trees first_tree .. stop - 1 are summed in tree order in fp32 (ptr_gbdt_predict_linear)."""
+    X, total, arrays = _linear_walk_arrays(X, feature, threshold, left, right, value, tree_offsets, default_left, leaf_features, leaf_coeff, leaf_const)
+    stop = total if stop is None else int(stop)
+    if not 0 <= int(first_tree) <= stop <= total:
+        raise ValueError(f"trees {first_tree} .. {stop} of {total}")
+    out = torch.empty(X.shape[0], device=X.device, dtype=torch.float32)
+    with torch.cuda.device(X.device):
+        _lib.call("ptr_gbdt_predict_linear", _lib.ptr(X), X.shape[0], X.shape[1], *map(_lib.ptr, arrays), int(first_tree), stop, _lib.ptr(out), _lib.current_stream(X.device))
+    return out
+
+
+def gbdt_add_tree_linear(scores, X, feature, threshold, left, right, value, leaf_features, leaf_coeff, leaf_const, default_left=None):
+    """scores[i] += the output of ONE linear tree for every raw row of X, in place: the walk and the leaf output of gbdt_predict_linear, so
+    the resident training scores stay its sums bit for bit (ptr_gbdt_add_tree_linear)."""
+    scores = _check("scores", scores, shape=(X.shape[0],))
+    if not scores.is_contiguous():
+        raise ValueError("scores must be contiguous")
+    offsets = torch.tensor([0, feature.numel()], device=X.device, dtype=torch.int32)
+    X, _, arrays = _linear_walk_arrays(X, feature, threshold, left, right, value, offsets, default_left, leaf_features, leaf_coeff, leaf_const)
+    with torch.cuda.device(X.device):
+        _lib.call("ptr_gbdt_add_tree_linear", _lib.ptr(scores), _lib.ptr(X), X.shape[0], X.shape[1], *map(_lib.ptr, arrays), _lib.current_stream(X.device))
+    return scores

@@ -166,6 +166,27 @@ best_iteration stays None.  The model formats are unchanged (the trees carry the
 file only under 'dart'.  With 'gbdt' every call and every model file is the one made before the keys existed.  Not here: categorical_feature
 under 'dart' (ValueError: the resident forest keeps no left sets), LightGBM's own random stream.
 
+Linear trees (linear_tree, linear_lambda: LightGBM's names).  The rule is this project's own, modelled on LightGBM's LinearTreeLearner,
+stated in include/ptranking_amd.h and restated in tests/gbdt_linear_ref.py; nothing is compared with LightGBM and no parity is claimed.
+Under linear_tree=True a tree grows exactly as without it (the same histograms, scans, partitions and constant-leaf gains); then every
+leaf is fitted with a linear model over P, the distinct features of the nodes on its root-to-leaf path in order of first appearance
+(k = |P| <= 30).  Over the leaf's rows of the grower's row list (the bag under sampling) that hold no NaN among the k regressors, in
+float64 from the round's fp32 gradients and Hessians (the pair quantization is handed): z = (x_P1 .. x_Pk, 1), A = sum h z z^T,
+b = sum g z, c = -(A + L)^-1 b by a Cholesky factorisation without pivoting, L = linear_lambda on the k feature diagonals.  The leaf
+stays constant when k = 0, k > 30, fewer than k + 1 usable rows, a pivot p_j that is not finite or not above 2^-40 (A + L)_jj (the
+relative floor is part of the rule: a regressor that is constant over the leaf falls back), or a solution that is not finite.  A tree
+keeps leaf_features int32 [leaves, 30] (-1 padded; all -1: constant), leaf_coeff float64 [leaves, 30] = c_j lr and leaf_const float64
+[leaves] beside value, which stays the constant value; a leaf's output for a row is value[leaf] where the leaf is constant or a
+regressor is NaN, else float32(leaf_const + sum_j leaf_coeff_j float64(x_Pj)) in float64 in path order, by ONE device function for
+training and prediction, so booster.scores stays predict(X) bit for bit.  The moments run on the fp64 matrix instruction
+(v_mfma_f64_16x16x4_f64, csrc/gbdt_linear.hip) with no float atomic: two fits give the same bits.  fit_bins keeps the fp32 matrix resident
+(n F 4 bytes more); the fits cost exactly ONE more host read per tree, which host_reads counts.  Such a model is saved as format 4
+(format 1 or 2 plus the three arrays); the two keys are written to a model file only under the switch.  Refused (ValueError):
+boosting='dart', categorical_feature, active monotone_constraints, quant_train_renew_leaf, refit, set_background and pred_contrib, and an
+init_model whose linear_tree differs.  use_quantized_grad (structure from the low-bit sums, the fits from the fp32 pair), interaction
+constraints, use_missing, both growth policies and both sampling schemes work as before.  With the switch off every call and every
+model file is the one made before the keys existed.
+
 Everything a tree decides rests on integer sums (ptr_gbdt_quantize), so two fits of the same data give the same bits.  Not here:
 feature_fraction, EFB, and DART from the dict's boosting_type alone (it is the argument boosting='dart', above).  There is no CPU path.
 """
@@ -179,7 +200,7 @@ from . import functional as F
 from . import letor, tree
 
 __all__ = ["GBDT", "LambdaMART", "bin_edges", "DEFAULT_PARAMS", "IGNORED_PARAMS", "constraints", "shap_tables", "SHAP_MAX_ELEMENTS", "dart_rates",
-           "dart_probabilities"]
+           "dart_probabilities", "linear_path_features"]
 
 # LightGBM's names, so the reference's lightgbm_para_dict passes through.  min_sum_hessian_in_leaf = 1e-3 is LightGBM's default too; the
 # reference's own dict sets 200, which suits LightGBM's built-in lambdarank Hessians, not the sums of tree.hip.
@@ -195,15 +216,20 @@ DEFAULT_PARAMS = {"learning_rate": 0.1, "num_leaves": 31, "num_trees": 100, "min
                   "use_quantized_grad": False, "num_grad_quant_bins": 4, "stochastic_rounding": True, "quant_train_renew_leaf": False, "quant_seed": 0,
                   # DART (the argument boosting='dart', which sets boosting_type here): the other six are read under it alone (LightGBM's names and defaults)
                   "boosting_type": "gbdt", "drop_rate": 0.1, "max_drop": 50, "skip_drop": 0.5, "uniform_drop": False, "xgboost_dart_mode": False,
-                  "drop_seed": 4}
+                  "drop_seed": 4,
+                  # linear trees: a leaf carries a linear model over the features on its path (LightGBM's names)
+                  "linear_tree": False, "linear_lambda": 0.0}
 IGNORED_PARAMS = ("num_threads", "verbosity", "metric", "objective", "eval_at")    # accepted, without a meaning here
 MODEL_FORMAT = 1                       # a model trained without use_missing
 MODEL_FORMAT_MISSING = 2               # one trained under it: format 1 with default_left per node and nan_bin per feature
 MODEL_FORMAT_CAT = 3                   # one with categorical features: format 1 or 2 plus categorical_feature, cat_index per node and cat_sets
+MODEL_FORMAT_LINEAR = 4                # one of linear trees: format 1 or 2 (by use_missing) plus leaf_features, leaf_coeff and leaf_const per leaf
 CAT_KEYS = ("categorical_feature", "cat_smooth")      # not among the parameters of a format 1 or 2 file
 CST_KEYS = ("monotone_constraints", "monotone_constraints_method", "interaction_constraints")   # in a model file only where one is active
 QUANT_KEYS = ("use_quantized_grad", "num_grad_quant_bins", "stochastic_rounding", "quant_train_renew_leaf", "quant_seed")   # likewise: only under the switch
 DART_KEYS = ("boosting_type", "drop_rate", "max_drop", "skip_drop", "uniform_drop", "xgboost_dart_mode", "drop_seed")   # likewise: only under 'dart'
+LINEAR_KEYS = ("linear_tree", "linear_lambda")      # likewise: only under linear_tree
+LINEAR_ARRAYS = ("leaf_features", "leaf_coeff", "leaf_const")      # what a linear tree keeps beside its arrays, per leaf
 BOOSTING_TYPES = ("gbdt", "dart")
 MONOTONE_METHODS = ("basic",)
 GROW_POLICIES = ("leafwise", "depthwise")
@@ -248,7 +274,8 @@ def _params(params, boosting=None):
                          f"boosting='dart' of GBDT and LambdaMART, with its six settings in the dict")
     if boosting is not None:
         p["boosting_type"] = boosting
-    for k in ("bagging_by_query", "use_missing", "use_quantized_grad", "stochastic_rounding", "quant_train_renew_leaf", "uniform_drop", "xgboost_dart_mode"):
+    for k in ("bagging_by_query", "use_missing", "use_quantized_grad", "stochastic_rounding", "quant_train_renew_leaf", "uniform_drop", "xgboost_dart_mode",
+              "linear_tree"):
         if isinstance(p[k], (bool, np.bool_)):
             p[k] = bool(p[k])
         else:
@@ -306,6 +333,21 @@ def _params(params, boosting=None):
             raise ValueError("boosting_type 'dart' with categorical_feature is not implemented: the resident forest keeps no left sets")
         if p["num_leaves"] > F.GBDT_DART_MAX_NODES + 1:
             raise ValueError(f"boosting_type 'dart' keeps a node's children in int16: num_leaves must be <= {F.GBDT_DART_MAX_NODES + 1}, got {p['num_leaves']}")
+    try:
+        p["linear_lambda"] = float(p["linear_lambda"])
+    except (TypeError, ValueError):
+        raise ValueError(f"linear_lambda must be a finite number >= 0, got {p['linear_lambda']!r}") from None
+    if not 0.0 <= p["linear_lambda"] < np.inf:
+        raise ValueError(f"linear_lambda must be a finite number >= 0, got {p['linear_lambda']}")
+    if p["linear_tree"]:
+        if p["boosting_type"] == "dart":
+            raise ValueError("linear_tree under boosting_type 'dart' is not implemented: the resident forest lives in bin space and keeps no raw values")
+        if p["categorical_feature"]:
+            raise ValueError("linear_tree with categorical_feature is not implemented: a category code is no regressor")
+        if any(p["monotone_constraints"]):
+            raise ValueError("linear_tree is not available under monotone_constraints: a linear leaf breaks the guarantee")
+        if p["quant_train_renew_leaf"]:
+            raise ValueError("linear_tree with quant_train_renew_leaf is not implemented: the leaves are fitted from the fp32 gradients already")
     if p["quant_train_renew_leaf"] and any(p["monotone_constraints"]):
         raise ValueError("quant_train_renew_leaf is not available under monotone_constraints: the leaf values are clamped between their "
                          "neighbours', and re-estimating them leaf by leaf would break the guarantee")
@@ -566,6 +608,9 @@ def _initial_model(init_model, params, device=None):
     for k in INIT_MODEL_KEYS:
         if params[k] != model.params[k]:
             raise ValueError(f"init_model was trained with {k}={model.params[k]!r}, this trainer has {k}={params[k]!r}: the bins would differ")
+    if params["linear_tree"] != model.params["linear_tree"]:
+        raise ValueError(f"init_model was trained with linear_tree={model.params['linear_tree']!r}, this trainer has linear_tree={params['linear_tree']!r}: "
+                         f"constant and linear leaves do not share a forest")
     if model.edges is None:
         raise ValueError("init_model holds no bin edges: fit_bins() or load_model() first")
     return model
@@ -573,6 +618,27 @@ def _initial_model(init_model, params, device=None):
 
 def _copy_tree(t):
     return {k: np.array(v) for k, v in t.items()}
+
+
+def linear_path_features(feature, left, right):
+    """The regressors of every leaf of a tree (node arrays as a tree dict keeps them), on the host -> (feats int32 [leaves, 30] padded
+    with -1, nfeat int32 [leaves]): the distinct features of the nodes on the root-to-leaf path in order of first appearance from the
+    root.  nfeat is the true count; a leaf of more than GBDT_LINEAR_MAX_FEATURES of them keeps its row of -1: it stays constant."""
+    feature, left, right = (np.asarray(a).astype(np.int64).reshape(-1) for a in (feature, left, right))
+    nn = feature.size
+    feats, nfeat = np.full((nn + 1, F.GBDT_LINEAR_MAX_FEATURES), -1, np.int32), np.zeros(nn + 1, np.int32)
+    stack = [(0, ())] if nn else []
+    while stack:
+        at, path = stack.pop()
+        if at < 0:
+            nfeat[~at] = len(path)
+            if len(path) <= F.GBDT_LINEAR_MAX_FEATURES:
+                feats[~at, :len(path)] = path
+            continue
+        f = int(feature[at])
+        here = path if f in path else path + (f,)
+        stack += [(int(right[at]), here), (int(left[at]), here)]
+    return feats, nfeat
 
 
 class _Leaf:
@@ -696,6 +762,8 @@ class GBDT:
         self.host_reads = 0                # device-to-host reads inside update(), over the booster's life: what a growth policy costs
         self._qid = None
         self.last_drop = ()                # under 'dart': the indices (into trees) of the trees the last round dropped
+        self.last_linear_status = None     # under linear_tree: the status per leaf of the last tree's fits (an index into F.GBDT_LINEAR_STATUS)
+        self._X = self._linear = None      # under linear_tree: the resident fp32 matrix; the fits of the tree update() is finishing
         self._dart = None                  # under 'dart', after fit_bins: the resident forest in bin space and the round's state
         if X is not None:
             self.fit_bins(X)
@@ -712,7 +780,9 @@ class GBDT:
         init_model (a GBDT, a LambdaMART or the path of a saved model): continue that model on X.  The edges are the model's (no bin_edges
         call), the trees are copies of those its predict uses by default (best_iteration is cleared), and the resident scores start at
         predict(X) over them, so update() goes on from tree len(trees): a fit split in two gives the bits of the unsplit fit.  The trainer
-        must share max_bin, use_missing and categorical_feature with the model, and X must fit its bins (ValueError otherwise)."""
+        must share max_bin, use_missing, categorical_feature and linear_tree with the model, and X must fit its bins (ValueError otherwise).
+        Under linear_tree the fp32 device matrix stays resident beside the bins, n * F * 4 bytes more (a device tensor passed by the
+        caller is kept by reference, not copied): the leaf fits and the scores read raw values."""
         groups = self._check_constraints(np.shape(X))                      # the refusals of the constraints come before any device work
         model = None if init_model is None else _initial_model(init_model, self.params, self._device)
         dev = self._dev()
@@ -741,6 +811,7 @@ class GBDT:
         self._edges_d, self._nbins_d = torch.from_numpy(self.edges).to(dev), torch.from_numpy(self.nbins).to(dev)
         self._nan_bin_d = torch.from_numpy(self.nan_bin).to(dev) if p["use_missing"] else None
         self.bins = F.gbdt_bin(Xd, self._edges_d, self._nbins_d, nan_bin=self._nan_bin_d)
+        self._X = Xd if p["linear_tree"] else None                        # linear trees read raw values: the fp32 matrix stays resident
         n = self.n
         self.scores = torch.zeros(n, device=dev, dtype=torch.float32)
         self._arange = torch.arange(n, device=dev, dtype=torch.int32)
@@ -959,6 +1030,7 @@ class GBDT:
             self._rows.copy_(self._arange)
         grow = self._grow_depthwise if p["grow_policy"] == "depthwise" else self._grow_leafwise
         feature, threshold, left, right, starts, g_sum, h_sum, split_bin, go_left, cat_index, cat_sets = grow(head, bag)
+        self._linear = self._fit_linear(feature, left, right, starts, bag, grad, hess) if p["linear_tree"] else None
         if self._q30 is not None:
             value = self._renewed_values(starts, bag)
         elif self._leaf_v is not None and len(g_sum) > 1:                 # a leaf stores float32(v * learning_rate) with its clamped v
@@ -969,6 +1041,32 @@ class GBDT:
         if dart is not None:
             self._dart_end_round()
         return t
+
+    def _fit_linear(self, feature, left, right, starts, m, grad, hess):
+        """linear_tree: the leaves' linear models -> (leaf_features, leaf_coeff, leaf_const, status) by leaf index, numpy.  The host takes the
+        path features from the node arrays, lists the work items over the row list the grower holds, and the device sums the moments
+        from the round's fp32 pair (ptr_gbdt_linear_moments) and solves every leaf (ptr_gbdt_linear_solve); ONE host read brings the
+        coefficients and the statuses: host_reads grows by one per tree.  A leaf that falls back keeps its row of -1."""
+        p, dev, K = self.params, self.scores.device, F.GBDT_LINEAR_MAX_FEATURES
+        feats, nfeat = linear_path_features(feature, left, right)
+        order = sorted(range(len(starts)), key=lambda i: starts[i])
+        ends = dict(zip(order, [starts[i] for i in order[1:]] + [m]))        # segments do not ascend with the leaf index: an item carries its own start
+        items, item_offsets = [], [0]
+        for l in range(len(starts)):
+            it, _ = F.gbdt_linear_items([starts[l], ends[l]], [nfeat[l]])
+            it[:, 0] = l
+            items.append(it)
+            item_offsets.append(item_offsets[-1] + it.shape[0])
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        feats_d, nfeat_d = up(feats), up(nfeat)
+        ws, usable = F.gbdt_linear_moments(self._X, self._rows[:m], up(np.concatenate(items).astype(np.int32).reshape(-1, 3)), feats_d, nfeat_d, grad, hess)
+        coeff, const, status, _ = F.gbdt_linear_solve(ws, usable, up(np.array(item_offsets, np.int32)), nfeat_d, p["linear_lambda"], self._tree_lr)
+        head = torch.cat([coeff.reshape(-1), const, status.to(torch.float64)]).cpu().numpy()      # the one read of this tree's fits
+        self.host_reads += 1
+        nl = len(starts)
+        coeff, const, status = head[:nl * K].reshape(nl, K), head[nl * K:nl * K + nl], head[nl * K + nl:].astype(np.int32)
+        feats[status != 0] = -1
+        return feats, np.ascontiguousarray(coeff), np.ascontiguousarray(const), status
 
     def _renewed_values(self, starts, m):
         """quant_train_renew_leaf: the leaves' values from the round's 30-bit gradients, fp32 by leaf index.  The tree grew on low-bit sums;
@@ -1089,7 +1187,9 @@ class GBDT:
         order = sorted(range(len(starts)), key=lambda i: starts[i])
         offsets = np.array([starts[i] for i in order] + [m], np.int32)
         dev = self.scores.device
-        F.gbdt_add_leaf_values(self.scores, self._rows, torch.from_numpy(offsets).to(dev), torch.from_numpy(value[order]).to(dev))
+        linear = self.params["linear_tree"]
+        if not linear:
+            F.gbdt_add_leaf_values(self.scores, self._rows, torch.from_numpy(offsets).to(dev), torch.from_numpy(value[order]).to(dev))
         t = {"feature": np.array(feature, np.int32), "threshold": np.array(threshold, np.float32), "left": np.array(left, np.int32),
              "right": np.array(right, np.int32), "value": value}
         also = None
@@ -1100,7 +1200,14 @@ class GBDT:
             t["cat_index"] = np.array(cat_index, np.int32).reshape(-1)
             t["cat_set"] = np.array(cat_sets, np.int64).reshape(-1, 4)
         up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-        if m < self.n and cat_index is not None:
+        if linear:
+            # one walk over ALL rows of the resident raw matrix, in or out of the bag, through the leaf output predict runs: it replaces both
+            # gbdt_add_leaf_values and the binned walk below
+            t["leaf_features"], t["leaf_coeff"], t["leaf_const"], self.last_linear_status = self._linear
+            F.gbdt_add_tree_linear(self.scores, self._X, up(t["feature"], np.int32), up(t["threshold"], np.float32), up(t["left"], np.int32),
+                                   up(t["right"], np.int32), up(value, np.float32), up(t["leaf_features"], np.int32), up(t["leaf_coeff"], np.float64),
+                                   up(t["leaf_const"], np.float64), default_left=up(t["default_left"], np.uint8) if "default_left" in t else None)
+        elif m < self.n and cat_index is not None:
             F.gbdt_add_tree_binned_cat(self.scores, self.bins, self.F, self._rows[m:], up(t["feature"], np.int32), up(split_bin, np.int32), up(t["left"], np.int32),
                                        up(t["right"], np.int32), up(value, np.float32), self._is_cat_d, up(t["cat_index"], np.int32), up(t["cat_set"], np.int64),
                                        default_left=up(t["default_left"], np.uint8) if "default_left" in t else None, nan_bin=self._nan_bin_d)
@@ -1327,6 +1434,10 @@ class GBDT:
             out["cat_index"] = (np.concatenate([np.where(t["cat_index"] >= 0, t["cat_index"] + b, -1) for t, b in zip(self.trees, base)]).astype(np.int32)
                                 if self.trees else np.zeros(0, np.int32))
             out["cat_sets"] = (np.concatenate([t["cat_set"] for t in self.trees]) if self.trees else np.zeros((0, 4))).astype(np.int64).reshape(-1, 4)
+        if self.params["linear_tree"]:
+            K = F.GBDT_LINEAR_MAX_FEATURES
+            out["leaf_features"], out["leaf_coeff"] = cat("leaf_features", np.int32).reshape(-1, K), cat("leaf_coeff", np.float64).reshape(-1, K)
+            out["leaf_const"] = cat("leaf_const", np.float64)
         return out
 
     def feature_importance(self, importance_type="split"):
@@ -1362,6 +1473,8 @@ class GBDT:
         the TRAINING matrix as background gives the counts the trees were grown on.  Every node and leaf must be reached by a row
         (ValueError names the tree and the node).  The covers live in memory only: save_model writes what it wrote, a loaded model calls
         set_background again, and so does a booster that has grown since."""
+        if self.params["linear_tree"]:
+            raise ValueError("set_background is not available under linear_tree: TreeSHAP attributes constant leaf values, a linear leaf has none")
         dev = self._dev()
         fl = self._flat_device(dev)
         Xd = _device_matrix(X, dev)
@@ -1392,7 +1505,8 @@ class GBDT:
 
     def predict(self, X, num_iteration=None, first_tree=0, check_finite=True, pred_contrib=False, pred_leaf=False):
         """pred_leaf=True -> device int32 [n, trees]: the index of the leaf each of the same trees puts each row in (LightGBM's layout);
-        value[leaf] summed in tree order in fp32 is the score.  It cannot be combined with pred_contrib.
+        value[leaf] summed in tree order in fp32 is the score (not under linear_tree: the indices are the same walk's, but a linear leaf's
+        output depends on the row, so summing value[leaf] no longer gives the score).  It cannot be combined with pred_contrib.
         pred_contrib=True -> device float64 [n, F + 1]: the TreeSHAP contribution of every feature to the score of every row over the
         same trees, and the expected value in the last column (LightGBM's layout); a row's entries sum to its score up to the fp32
         rounding of predict's own sum.  It needs set_background.  Otherwise:
@@ -1405,6 +1519,8 @@ class GBDT:
         sends what is no integer code in 0 .. 255 right).  A code the training data never held is legal: it is in no left set and goes right."""
         if pred_leaf and pred_contrib:
             raise ValueError("pred_leaf and pred_contrib cannot be combined: ask for one of them")
+        if pred_contrib and self.params["linear_tree"]:
+            raise ValueError("pred_contrib=True is not available under linear_tree: TreeSHAP attributes constant leaf values, a linear leaf has none")
         dev = self._dev()
         if self._flat is None:
             self._flat = {k: torch.from_numpy(v).to(dev) for k, v in self.flat().items()}
@@ -1425,6 +1541,11 @@ class GBDT:
                                        default_left=fl.get("default_left"), **self._cat_walk(Xd))
         if cats:
             return self._predict_cat(Xd, first_tree, stop)
+        if self.params["linear_tree"]:                                     # every range of trees in one launch over the resident flat arrays
+            if self.edges is not None and Xd.shape[1] != self.edges.shape[0]:
+                raise ValueError(f"X holds {Xd.shape[1]} columns, the model {self.edges.shape[0]}")
+            return F.gbdt_predict_linear(Xd, fl["feature"], fl["threshold"], fl["left"], fl["right"], fl["value"], fl["tree_offsets"], fl["leaf_features"],
+                                         fl["leaf_coeff"], fl["leaf_const"], first_tree, stop, default_left=fl.get("default_left"))
         if first_tree == 0:
             return F.gbdt_predict(Xd, fl["feature"], fl["threshold"], fl["left"], fl["right"], fl["value"], fl["tree_offsets"], stop,
                                   default_left=fl.get("default_left"))
@@ -1471,6 +1592,8 @@ class GBDT:
         for bit.  Active monotone constraints raise: clamped values cannot be re-estimated leaf by leaf without breaking the guarantee."""
         decay = _decay_rate(decay_rate)
         p = self.params
+        if p["linear_tree"]:
+            raise ValueError("refit is not available under linear_tree: it re-estimates constant leaf values, and a linear leaf's coefficients would go stale")
         if "monotone" in constraints(p):
             raise ValueError("refit is not available under monotone_constraints: the leaf values were clamped between their neighbours', and "
                              "re-estimating them leaf by leaf would break the guarantee")
@@ -1522,12 +1645,16 @@ class GBDT:
         """An .npz of this project's own (not LightGBM's text format): the flat tree arrays, the bin edges, the parameters.  Format 1
         without use_missing (the file this method wrote before the switch existed: neither the switch nor the categorical keys are among its
         parameters); format 2 under it, with default_left per node and nan_bin per feature; format 3 with categorical features: format 1
-        or 2 (by use_missing, with every parameter) plus categorical_feature, cat_index per node and cat_sets."""
+        or 2 (by use_missing, with every parameter) plus categorical_feature, cat_index per node and cat_sets; format 4 under linear_tree:
+        format 1 or 2 (by use_missing) plus leaf_features, leaf_coeff and leaf_const per leaf and the two linear keys."""
         own = self.params if constraints(self.params) else {k: v for k, v in self.params.items() if k not in CST_KEYS}      # inactive: today's file
         if not own["use_quantized_grad"]:                                  # likewise: without the switch, the file written before the keys existed
             own = {k: v for k, v in own.items() if k not in QUANT_KEYS}
         if own["boosting_type"] != "dart":                                 # likewise
             own = {k: v for k, v in own.items() if k not in DART_KEYS}
+        linear = own["linear_tree"]
+        if not linear:                                                     # likewise
+            own = {k: v for k, v in own.items() if k not in LINEAR_KEYS}
         if self.params["categorical_feature"]:
             head = dict(format=np.int64(MODEL_FORMAT_CAT), params=np.array(json.dumps(own)), edges=self.edges, nbins=self.nbins,
                         categorical_feature=np.array(self.params["categorical_feature"], np.int32))
@@ -1540,6 +1667,8 @@ class GBDT:
         else:
             params = {k: v for k, v in own.items() if k != "use_missing" and k not in CAT_KEYS}
             head = dict(format=np.int64(MODEL_FORMAT), params=np.array(json.dumps(params)), edges=self.edges, nbins=self.nbins)
+        if linear:                                                         # format 1 or 2 with its own number; flat() carries the three arrays
+            head["format"] = np.int64(MODEL_FORMAT_LINEAR)
         with open(path, "wb") as fh:
             np.savez(fh, **head, best_iteration=np.int64(self.best_iteration or 0), **self.flat())
 
@@ -1548,10 +1677,16 @@ class GBDT:
         """The booster save_model wrote; it predicts the same bits.  (The binned training data are not part of a model.)"""
         with np.load(path, allow_pickle=False) as z:
             fmt = int(z["format"])
-            if fmt not in (MODEL_FORMAT, MODEL_FORMAT_MISSING, MODEL_FORMAT_CAT):
-                raise ValueError(f"{path}: model format {fmt}, this version reads {MODEL_FORMAT}, {MODEL_FORMAT_MISSING} and {MODEL_FORMAT_CAT}")
+            if fmt not in (MODEL_FORMAT, MODEL_FORMAT_MISSING, MODEL_FORMAT_CAT, MODEL_FORMAT_LINEAR):
+                raise ValueError(f"{path}: model format {fmt}, this version reads {MODEL_FORMAT}, {MODEL_FORMAT_MISSING}, {MODEL_FORMAT_CAT} and "
+                                 f"{MODEL_FORMAT_LINEAR}")
             own = json.loads(str(z["params"]))
             self = cls(own, device=device, boosting=own.get("boosting_type"))
+            linear = fmt == MODEL_FORMAT_LINEAR
+            if self.params["linear_tree"] != linear:
+                raise ValueError(f"{path}: model format {fmt} with linear_tree={self.params['linear_tree']}")
+            if linear:                                                     # the format underneath, by use_missing
+                fmt = MODEL_FORMAT_MISSING if self.params["use_missing"] else MODEL_FORMAT
             cats = fmt == MODEL_FORMAT_CAT
             if bool(self.params["categorical_feature"]) != cats or (cats and self.params["categorical_feature"] != tuple(z["categorical_feature"].tolist())):
                 raise ValueError(f"{path}: model format {fmt} with categorical_feature={self.params['categorical_feature']}")
@@ -1572,6 +1707,9 @@ class GBDT:
                                    "right": z["right"][lo:hi], "value": z["value"][lo + t:hi + t + 1]})
                 if missing:
                     self.trees[-1]["default_left"] = z["default_left"][lo:hi]
+                if linear:
+                    for k in LINEAR_ARRAYS:
+                        self.trees[-1][k] = z[k][lo + t:hi + t + 1]
                 if cats:
                     ci = z["cat_index"][lo:hi]
                     k = int((ci >= 0).sum())
