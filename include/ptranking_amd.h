@@ -416,6 +416,28 @@ int ptr_smoothmetric_fwd_bwd(const float *preds, const float *labels, const int3
                              float alpha, float max_label, float *loss_out, float *loss_q, float *valid_q, float *ranks, float *max_label_ws,
                              float *grad, void *stream);
 
+/* ---- NeuralNDCG (csrc/neuralndcg.hip).  The symbol below is ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
+ * ptr_neuralndcg_fwd_bwd — nDCG on the NeuralSort relaxation of sorting with Sinkhorn scaling, and its exact gradient through every
+ * iteration, in one launch.  The rule is this project's own, modelled on allRank's neuralNDCG (Pobrotyn & Bialobrzeski 2021); nothing is
+ * compared with allRank and no parity is claimed.  Per query with n = lens[q] real documents, scores s, labels y, tau > 0, iters = T >= 0,
+ * cut-off k (k <= 0: n); gains g_j = 2^y_j - 1 (powered != 0) or y_j; discounts d_i = 1 / log2(i + 2):
+ *   1. NeuralSort.  B_j = sum_k |s_j - s_k| over the real documents, c_i = n + 1 - 2 (i + 1), P0_ij = softmax over j of (c_i s_j - B_j) / tau
+ *      (row i a position, column j a document; the row's own maximum is subtracted before the exponential).
+ *   2. Sinkhorn scaling, exactly T times, no data-dependent stop: every column is divided by max(its sum over i, 1e-10), then every row by
+ *      max(its sum over j, 1e-10).
+ *   3. ndcg_q = sum_{i < min(k, n)} d_i sum_j P_ij g_j / idcg_q, idcg_q the ideal DCG of the labels at the same cut-off; a query with
+ *      idcg_q = 0 or n = 0 gives ndcg_q = 0 and a zero gradient.  loss_q = -ndcg_q and loss_out = the SUM over the queries, as every other
+ *      objective here returns it (allRank takes the mean).  The subgradient of |x| at 0 is 0: tied scores are legal.
+ *   4. grad = d loss / d s exactly, through all T iterations (a clamped sum passes no gradient, as torch.clamp does).
+ *   Outputs: loss_q [B], grad [B,L] (padded slots exactly 0), loss_out [1] (nullable: the caller sums loss_q with ptr_sum_f32).
+ *   ws: workspace of B * (workspace bytes per query) bytes where ptr_launch_form says the scaling history does not fit the LDS; else nullable.
+ *   Lists up to the cut-over length (ptr_launch_form) keep K = exp(logit - row maximum) in LDS; longer ones, up to 1024, recompute it.
+ *   No atomics: a query's outputs depend on (its documents, L, the parameters) alone, on every run and in any batch.
+ *   PTR_ERR_INVALID_ARG (before any launch): a NULL required pointer, tau <= 0 or not finite, iters < 0 or > 65535, L <= 0 or L > 1024, a
+ *   missing workspace. */
+int ptr_neuralndcg_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, float tau, int iters, int k, int powered,
+                           float *loss_out, float *loss_q, float *grad, float *ws, void *stream);
+
 /* ---- Gaussian expected-rank metric objectives (csrc/gaussmetric.hip).  The symbol below is ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
  * ptr_gaussmetric_fwd_bwd — loss, dLoss/dmus and dLoss/dvars of precision_ / AP_ / nERR_ / nDCG_as_opt_objective
  * (ptranking/metric/smooth_metric/metric_as_opt_objective.py:12-257) on the expected ranks of documents whose scores are independent normal
@@ -997,6 +1019,9 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *                                                alignment of the arrays in bytes           floats per global access
  *   ptr_layernorm_forward, ptr_layernorm_backward   R, F                                  NI, forward workgroups, backward workgroups
  *   ptr_wassrank_fwd_bwd                         L                                        G, DPT
+ *   ptr_neuralndcg_fwd_bwd                       L, iters                                 resident (1: K in LDS, 0: recomputed), G, history in
+ *                                                                                           LDS, LDS bytes and workspace bytes per query, the
+ *                                                                                           longest list of the resident form (the cut-over)
  *   ptr_alphadcg_fwd_bwd                         T, L                                     G, TP
  *   ptr_div_metrics_at_ks                        L                                        G, DPT
  *   ptr_divprob_fwd_bwd                          objective, T, L                          G, TP

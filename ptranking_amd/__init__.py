@@ -23,7 +23,8 @@
                 configured with mode='EntropicOT' (or smooth_type='NG') now raises NotImplementedError instead of running the reference's
                 torch code; install(names=RANKER_NAMES + METRIC_RANKER_NAMES) adds SmoothMetric (P / AP / nERR / nDCG on smooth ranks as the
                 training objective), which the reference has no class for; install(names=RANKER_NAMES + PROB_RANKER_NAMES) adds
-                ProbSmoothMetric (the same four objectives on Gaussian expected ranks, a mean and a variance per document)
+                ProbSmoothMetric (the same four objectives on Gaussian expected ranks, a mean and a variance per document);
+                install(names=RANKER_NAMES + SORT_RANKER_NAMES) adds NeuralNDCG (nDCG on the NeuralSort relaxation with Sinkhorn scaling)
 
 The only compute implementation is the HIP library ptranking_amd/libptranking_amd.so (C ABI: include/ptranking_amd.h);
 there is no CPU fallback.  Build it with `python -m ptranking_amd.build`.
@@ -39,7 +40,8 @@ from .adversarial import (AD_RANKER_NAMES, EXTRA_AD_RANKER_NAMES, LIST_AD_RANKER
 from .tree import TreeObjective                     # noqa: F401
 from .diversity import DALETOR, DIV_RANKER_NAMES, EXTRA_DIV_RANKER_NAMES, DivProbRanker, DivQueryBatches     # noqa: F401
 from .rankers import (ApproxNDCG, LambdaLoss, LambdaRank, ListMLE, ListNet, RankNet, STListNet, RankCosine, RankMSE, SoftRank, WassRank, DASALC, MDPRank,  # noqa: F401
-                      SmoothMetric, ProbSmoothMetric, DEFAULT_PARAS, EXTRA_RANKER_NAMES, METRIC_RANKER_NAMES, PROB_RANKER_NAMES, RANKER_NAMES,
+                      SmoothMetric, ProbSmoothMetric, NeuralNDCG, DEFAULT_PARAS, EXTRA_RANKER_NAMES, METRIC_RANKER_NAMES, PROB_RANKER_NAMES, RANKER_NAMES,
+                      SORT_RANKER_NAMES,
                       make_ranker_classes)
 
 __version__ = "0.1.0"

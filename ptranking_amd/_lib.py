@@ -45,6 +45,7 @@ SIGNATURES = {
     "ptr_tree_xendcg_grad_hess": [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _u64, C.c_int64, _vp, _vp, _vp],
     "ptr_smoothmetric_fwd_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ptr_gaussmetric_fwd_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ptr_neuralndcg_fwd_bwd": [_vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "ptr_pl_uniforms": [_i, _i, _i, _u64, C.c_int64, _vp, _vp],
     "ptr_pl_sample": [_vp, _vp, _i, _i, _i, _f, _i, _u64, C.c_int64, _vp, _vp, _vp, _vp],
     "ptr_mdprank_sample_fwd_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp],

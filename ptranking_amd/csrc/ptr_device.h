@@ -145,6 +145,12 @@ IrganForm adlist_form(int L);                            // adlist.hip: the list
 VecForm listmle_form(int L, bool aligned);
 VecForm lambdaloss_form(int L, int k, int loss_type, int presort, bool aligned);          // lambdaloss.hip: vec = top-k; else (G, DPT) in (G, V)
 Tiling wassrank_form(int L);                                                              // wassrank.hip
+// NeuralNDCG (neuralndcg.hip): K resident in LDS or recomputed, threads per workgroup, where the scaling history lives, bytes per query
+constexpr int kNeuralMaxLen = 1024;
+constexpr int kNeuralMaxIters = 65535;
+constexpr size_t kNeuralLdsBytes = 160 * 1024;
+struct NeuralForm { int resident; int G; int hist_lds; int lds_bytes; int ws_bytes; int cutover; };
+NeuralForm neuralndcg_form(int L, int iters);
 // The tree frame's ragged kernels (tree.hip), by the longest launched list: G threads per query (16 up to 16 documents, pick_tiling's
 // beyond), kBlock / G queries per workgroup, and the documents one thread owns in the kernels that keep them in registers (pick_tiling's
 // DPT: G * DPT covers the launch's longest list)

@@ -29,10 +29,12 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "GBDT_RECORD", "gbdt_predict_leaf", "gbdt_leaf_sums", "gbdt_add_by_leaf", "gbdt_quantize_low", "gbdt_quant_levels", "gbdt_leaf_sums_rows",
            "gbdt_dart_pack", "gbdt_dart_walk", "gbdt_dart_select", "gbdt_dart_scale",
            "gbdt_linear_items", "gbdt_linear_moments", "gbdt_linear_solve", "gbdt_predict_linear", "gbdt_add_tree_linear", "GBDT_LINEAR_MAX_FEATURES",
-           "GBDT_LINEAR_CHUNK_ROWS", "GBDT_LINEAR_STATUS"]
+           "GBDT_LINEAR_CHUNK_ROWS", "GBDT_LINEAR_STATUS", "neuralndcg_form", "NEURALNDCG_MAX_LEN"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
-# launch table, and it draws its own; irfgan_loss and adlist_loss are public too: they take a mode, as irgan_selected does)
+# launch table, and it draws its own; irfgan_loss and adlist_loss are public too: they take a mode, as irgan_selected does; neuralndcg_loss
+# is public too: the set of *_loss names in __all__ is pinned by tests/test_irgan_cpu.py and the launch table of
+# tests/test_functional_launch_gpu.py, so it stays outside __all__ as those do)
 LAMBDALOSS_TYPES = {"NDCG_Loss1": 0, "NDCG_Loss2": 1, "NDCG_Loss2++": 2}   # ptranking/ltr_adhoc/listwise/lambdaloss.py:27
 ADCG_TOPK_AXES = {"reference": 0, "subtopics": 0, 0: 0, "documents": 1, 1: 1}   # PTR_ADCG_TOPK_*
 NDEVAL_MEASURES = ("ERR-IA", "nERR-IA", "alpha-DCG", "alpha-nDCG", "NRBP", "nNRBP", "MAP-IA", "P-IA", "strec")   # ndeval.c:1214-1222, its CSV columns
@@ -263,6 +265,43 @@ def smooth_metric_objective(preds, labels, metric, alpha=10.0, top_k=None, opt_i
         parts["ranks"] = parts["ranks"][:B * L].view(B, L)
         return loss, parts
     return loss
+
+
+NEURALNDCG_MAX_LEN = 1024                                                  # kNeuralMaxLen, csrc/ptr_device.h
+
+
+def neuralndcg_form(L, iters):
+    """ptr_launch_form of ptr_neuralndcg_fwd_bwd -> dict(resident, G, hist_lds, lds_bytes, ws_bytes, cutover): K in LDS or recomputed, threads per
+    workgroup, whether the scaling history lives in LDS, LDS and workspace bytes per query, the longest list of the resident form.  No GPU."""
+    a, out = (C.c_int64 * 2)(int(L), int(iters)), (C.c_int32 * 8)()
+    if _lib.load().ptr_launch_form(b"ptr_neuralndcg_fwd_bwd", a, 2, out, 8) != 0:
+        raise RuntimeError(_lib.load().ptr_last_error().decode())
+    return dict(zip(("resident", "G", "hist_lds", "lds_bytes", "ws_bytes", "cutover"), out))
+
+
+def neuralndcg_loss(preds, labels, temperature=1.0, iters=50, top_k=None, powered=True, lens=None, return_parts=False):
+    """NeuralNDCG (modelled on allRank's neuralNDCG, Pobrotyn & Bialobrzeski 2021; the rule is stated in include/ptranking_amd.h): minus the nDCG
+    of the NeuralSort relaxation P0 = softmax_j((c_i s_j - B_j) / temperature) after exactly `iters` Sinkhorn scalings (columns, then rows, sums
+    clamped at 1e-10), gains 2^y - 1 (powered) or y, cut-off top_k (None: the whole list), SUMMED over the queries (allRank takes the mean),
+    with the exact gradient through every iteration.  Lists of up to 1024 documents.  With return_parts also returns dict(loss_q [B])."""
+    if not float(temperature) > 0.0 or not math.isfinite(float(temperature)):
+        raise ValueError(f"temperature must be a finite number > 0 (got {temperature!r})")
+    if int(iters) != iters or not 0 <= int(iters) <= 65535:
+        raise ValueError(f"iters must be an integer in [0, 65535] (got {iters!r})")
+    if not isinstance(preds, torch.Tensor) or not isinstance(labels, torch.Tensor):
+        raise TypeError("preds and labels must be torch.Tensors")
+    if preds.dim() != 2 or tuple(labels.shape) != tuple(preds.shape):
+        raise ValueError(f"preds and labels must both be [batch, ranking_size], got {tuple(preds.shape)} and {tuple(labels.shape)}")
+    if preds.shape[1] > NEURALNDCG_MAX_LEN:
+        raise ValueError(f"ranking_size {preds.shape[1]} exceeds the supported maximum {NEURALNDCG_MAX_LEN} of neuralndcg_loss")
+    if lens is not None and tuple(lens.shape) != (preds.shape[0],):
+        raise ValueError(f"lens must have shape {(preds.shape[0],)}, got {tuple(lens.shape)}")
+    preds_c, labels, lens, B, L = _batch(preds.detach(), labels, lens)
+    form = neuralndcg_form(L, int(iters))
+    ws = torch.empty(max(B, 1) * form["ws_bytes"] // 4, device=preds_c.device, dtype=torch.float32) if form["ws_bytes"] else None
+    loss, parts = _fused("ptr_neuralndcg_fwd_bwd", [preds], [preds_c],
+                         [labels, lens, B, L, C.c_float(float(temperature)), int(iters), int(top_k) if top_k else 0, int(bool(powered))], tail=(ws,))
+    return (loss, parts) if return_parts else loss
 
 
 def gaussian_metric_objective(mus, vars, labels, metric, top_k=None, opt_ideal=True, max_label=None, lens=None, const_std=None, return_parts=False):

@@ -35,6 +35,9 @@ METRIC_RANKER_NAMES = ("SmoothMetric",)
 # the same objectives on Gaussian expected ranks (prob_utils.get_expected_rank): the scorer predicts a mean and a variance per document.  No
 # reference class either: bound only by install(names=RANKER_NAMES + PROB_RANKER_NAMES), pa.ProbSmoothMetric
 PROB_RANKER_NAMES = ("ProbSmoothMetric",)
+# NeuralNDCG (NeuralSort + Sinkhorn scaling; the rule is this project's own, modelled on allRank's neuralNDCG): no reference class to rebind by
+# default either: bound only by install(names=RANKER_NAMES + SORT_RANKER_NAMES), pa.NeuralNDCG
+SORT_RANKER_NAMES = ("NeuralNDCG",)
 PROB_SORT_IDS = ('ExpRele', 'RiskAware', 'RERAR')       # ptranking/ltr_diversification/base/div_mdn_ranker.py:43
 
 # default hyper-parameters = the reference's `default_para_dict()`s
@@ -56,6 +59,7 @@ DEFAULT_PARAS = {
     "SmoothMetric": dict(model_id="SmoothMetric", metric='nDCG', alpha=10, top_k=None, opt_ideal=True),   # alpha: listwise/approxNDCG.py:131
     "ProbSmoothMetric": dict(model_id="ProbSmoothMetric", metric='nDCG', top_k=None, opt_ideal=True, limit_delta=0.01, const_std=None,
                              sort_id='ExpRele'),        # limit_delta, sort_id: ltr_diversification/score_and_sort/div_prob_ranker.py:387-389
+    "NeuralNDCG": dict(model_id="NeuralNDCG", temperature=1.0, iters=50, top_k=None, powered=True),
 }
 
 
@@ -398,6 +402,22 @@ class SmoothMetricLoss(FusedStepMixin):
             raise ValueError("SmoothMetric nERR under data parallelism needs model_para_dict['max_label']: the batch maximum is rank-local")
         return self._fused_step(F_.smooth_metric_objective(batch_preds, batch_std_labels, self.metric, alpha=self.alpha, top_k=self.top_k,
                                                            opt_ideal=self.opt_ideal, max_label=self.max_label, lens=kwargs.get('lens')))
+
+
+class NeuralNDCGLoss(FusedStepMixin):
+    temperature, iters, top_k, powered = 1.0, 50, None, True
+
+    def uniform_eval_setting(self, **kwargs):
+        """Validate on the metric that is optimised (the pattern of approxNDCG.py:78-81)."""
+        eval_dict = kwargs['eval_dict']
+        if eval_dict["do_validation"] and not eval_dict['vali_metric'] == 'nDCG':
+            eval_dict['vali_metric'] = 'nDCG'
+
+    def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
+        """functional.neuralndcg_loss: minus the nDCG of the scaled NeuralSort matrix, summed over the batch.  The labels need no order."""
+        assert 'label_type' in kwargs and is_multilabel(kwargs['label_type'])
+        return self._fused_step(F_.neuralndcg_loss(batch_preds, batch_std_labels, temperature=self.temperature, iters=self.iters,
+                                                   top_k=self.top_k, powered=self.powered, lens=kwargs.get('lens')))
 
 
 class ProbSmoothMetricLoss(FusedStepMixin):
@@ -745,9 +765,20 @@ def make_ranker_classes(base=PointScorerRanker):
             self.max_label = model_para_dict.get('max_label')
             self.limit_delta = model_para_dict.get('limit_delta', 0.01)
 
+    class NeuralNDCG(NeuralNDCGLoss, FusedScorerMixin, FusedListScorerMixin, DeviceTrainLoop, DeviceEvaluator, base):
+        """NeuralNDCG as the training objective; model_para_dict: temperature, iters, top_k, powered (each optional: DEFAULT_PARAS)."""
+
+        def __init__(self, sf_para_dict=None, model_para_dict=None, gpu=False, device=None):
+            base.__init__(self, id='NeuralNDCG', sf_para_dict=sf_para_dict, gpu=gpu, device=device)
+            paras = {**DEFAULT_PARAS['NeuralNDCG'], **(model_para_dict or {})}
+            self.temperature, self.iters = float(paras['temperature']), int(paras['iters'])
+            self.top_k, self.powered = paras['top_k'], bool(paras['powered'])
+            if not self.temperature > 0.0 or self.iters < 0:
+                raise ValueError(f"NeuralNDCG needs temperature > 0 and iters >= 0 (got {paras['temperature']!r}, {paras['iters']!r})")
+
     out = dict(RankNet=RankNet, LambdaRank=LambdaRank, LambdaLoss=LambdaLoss, ApproxNDCG=ApproxNDCG, ListNet=ListNet,
                ListMLE=ListMLE, STListNet=STListNet, RankCosine=RankCosine, RankMSE=RankMSE, SoftRank=SoftRank, WassRank=WassRank,
-               DASALC=DASALC, MDPRank=MDPRank, SmoothMetric=SmoothMetric, ProbSmoothMetric=ProbSmoothMetric)
+               DASALC=DASALC, MDPRank=MDPRank, SmoothMetric=SmoothMetric, ProbSmoothMetric=ProbSmoothMetric, NeuralNDCG=NeuralNDCG)
     for name, cls in out.items():
         cls.__name__ = cls.__qualname__ = name
         cls.__module__ = __name__
@@ -762,3 +793,4 @@ SoftRank, DASALC, MDPRank = _standalone["SoftRank"], _standalone["DASALC"], _sta
 WassRank = _standalone["WassRank"]
 SmoothMetric = _standalone["SmoothMetric"]
 ProbSmoothMetric = _standalone["ProbSmoothMetric"]
+NeuralNDCG = _standalone["NeuralNDCG"]
