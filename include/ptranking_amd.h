@@ -353,7 +353,45 @@ int ptr_ndeval_measures(const float *preds, const float *rele, const int32_t *le
  *   launch or the batch around it.  No atomics, nothing of size n x n.  One thread owns document i (strided where the list is longer than
  *   the group) and keeps rho_i, q_i and its running terms in registers across the three passes.  PTR_ERR_INVALID_ARG as above (`hessian`
  *   does not exist here), and for draw < 0.  LDS per query: 2 rows (the scores | the tree's row), 8 round_up(max_len, 4) bytes, 32 KiB at
- *   4096 documents. */
+ *   4096 documents.
+ *
+ * ptr_tree_lambdarank_unbiased_grad_hess and ptr_tree_position_bias_update (ADDITIVE to ABI v8: PTR_ABI_VERSION stays 8) are the
+ * position-debiased lambdarank for click logs (Hu et al., "Unbiased LambdaMART", WWW 2019; LightGBM's lambdarank_unbiased).  The rule below
+ * is THIS PROJECT'S OWN, modelled on the paper and on LightGBM's and XGBoost's statements of it; it is compared with neither and no parity
+ * is claimed.  Same ragged layout, `queries` subset list, max_len contract and forms as above.  Steps 1 to 3, 5 and 6 are those of
+ * ptr_tree_lambdarank_ndcg_grad_hess.  New inputs:
+ *   position  int32 per document (device, nullable), 0-based: the position the document was SHOWN at.  NULL: its index within its query.
+ *   npos      P, the number of position classes, 1 .. PTR_TREE_MAX_BIAS_POSITIONS.  b(d) = min(position[d], P - 1).  A negative position
+ *             is the caller's error: its list gets NaN and adds nothing to the costs.
+ *   biases    fp32 [2, P] (device, nullable): row 0 is t+, the bias of the position of a pair's `hi` document; row 1 is t-, the bias of the
+ *             `lo` document's position.  NULL: all 1.
+ *   cost_acc  int64 [2, P] (device): the fixed-point sums of the pair costs per position, ADDED to by every launch (below).
+ *   4'. p, lam0 = sigma delta p and h0 = sigma^2 delta p (1 - p) as in step 4; w = 1 / (t+[b(hi)] t-[b(lo)]), evaluated as the product of
+ *       the two reciprocals; lam = lam0 w, h = h0 w.  The pair's cost is c = delta log(1 + exp(-sigma ds)), delta AFTER the score-distance
+ *       division of step 3;  cost+[b(hi)] += c / t-[b(lo)],  cost-[b(lo)] += c / t+[b(hi)].
+ *   Steps 5 and 6 run on the debiased lam and h.  The costs are NOT multiplied by step 6's factor.  A NaN list adds nothing to the costs.
+ *   With unit (or NULL) biases grad and hess are the bits of ptr_tree_lambdarank_ndcg_grad_hess: a multiplication by 1 is exact.
+ *   The reduction: the thread that owns a document carries two more four-chain fp32 sums in the fixed order of the others (its costs as
+ *   `hi`, its costs as `lo`; every counted pair is visited from both ends, so each end adds its own side only).  Each sum goes to fixed
+ *   point — int64, scale 2^32, round to nearest, clamped to [0, 2^30] before the scale (a NaN sum counts 0) — and is added to a [2, P]
+ *   accumulator in LDS with 64-bit integer LDS atomics; at its end the workgroup adds the non-zero entries to cost_acc with 64-bit
+ *   integer global atomics: at most 2 P per workgroup, none per document, and NO float atomic.  Integer addition is exact and commutative:
+ *   the totals are the same bits whatever the form, the partition of the queries over launches, or the run.  Each document's conversion
+ *   is off by at most 2^-33.  Overflow: cost_acc holds sums below 2^31; a pair's cost is at most delta (ln 2 + sigma |ds|) / t with
+ *   delta <= 100 under norm (<= 1 without) and t >= 2^-10 after an update, and one document's sum is clamped at 2^30, so a position class
+ *   overflows only where its documents' sums total 2^31 ~ 2.1e9: at 4.3e9 documents of average sum 1/2 per class, far beyond any training set.
+ *   LDS per workgroup: 28 round_up(max_len, 4) bytes per query as above (the position class, 8 bits, shares the word of the document
+ *   index, 12 bits) + 8 P (the two rows of bias reciprocals, taken once per workgroup) + 16 P (the accumulator): 28 x 4096 + 24 x 256 =
+ *   120 832 bytes (118 KiB) at 4096 documents and P = 256.
+ *   PTR_ERR_INVALID_ARG as for ptr_tree_lambdarank_ndcg_grad_hess, and for npos outside 1 .. PTR_TREE_MAX_BIAS_POSITIONS or a NULL cost_acc.
+ *
+ * ptr_tree_position_bias_update — one small launch, once per round after every query's launch; no host read:
+ *   cost[s][p] = cost_acc[s][p] 2^-32 in float64 (written to costs_out, float64 [2, P], nullable); for each sign s: if cost[s][0] > 0,
+ *   every p with cost[s][p] > 0 gets biases[s][p] = max(2^-10, (cost[s][p] / cost[s][0]) ^ (1 / (1 + p_norm))), evaluated in float64 and
+ *   stored in fp32; a position whose cost is 0 keeps its bias; if cost[s][0] == 0 every bias of that sign stays.  cost_acc is zeroed for
+ *   the next round.  Round k's gradients and costs use the biases left by round k - 1; they start at all 1, so round 0 is exactly
+ *   ptr_tree_lambdarank_ndcg_grad_hess.  PTR_ERR_INVALID_ARG: npos out of range, a NULL cost_acc or biases, p_norm < 0 or NaN. */
+#define PTR_TREE_MAX_BIAS_POSITIONS 256
 #define PTR_TREE_PAIRS_ALL 0
 #define PTR_TREE_PAIRS_NOTIES 1
 #define PTR_TREE_PAIRS_NO00 2
@@ -374,6 +412,10 @@ int ptr_tree_lambdarank_ndcg_grad_hess(const float *preds, const float *labels, 
                                        int max_len, int truncation_level, float sigmoid, int norm, float *grad, float *hess, void *stream);
 int ptr_tree_xendcg_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries, int nq,
                               int max_len, const float *unif, uint64_t seed, int64_t draw, float *grad, float *hess, void *stream);
+int ptr_tree_lambdarank_unbiased_grad_hess(const float *preds, const float *labels, const int32_t *position, const int64_t *offsets, int B,
+                                           const int32_t *queries, int nq, int max_len, int truncation_level, float sigmoid, int norm,
+                                           const float *biases, int npos, int64_t *cost_acc, float *grad, float *hess, void *stream);
+int ptr_tree_position_bias_update(int64_t *cost_acc, int npos, double p_norm, float *biases, double *costs_out, void *stream);
 
 /* ---- Smooth-rank metric objectives (csrc/smoothmetric.hip).  The symbol below is ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
  * ptr_smoothmetric_fwd_bwd — loss and dLoss/dpreds of precision_ / AP_ / nERR_ / nDCG_as_opt_objective

@@ -337,11 +337,33 @@ __device__ __forceinline__ int rank_indexed(const float *keys, int n, int i, flo
     return rk;
 }
 
-template <int G>
+// ---- The position-debiased variant (UB; ptr_tree_lambdarank_unbiased_grad_hess, Unbiased LambdaMART; include/ptranking_amd.h states the
+// rule): the same body, so the pair arithmetic exists once.  What UB adds:
+//   Ix   the document at rank r in bits 0..11 and its position class b = min(position, P - 1) in bits 12..19: a partner's class is the same
+//        LDS broadcast as its score and gain
+//   Rt   2 P floats per WORKGROUP behind the queries' rows: 1 / t+ | 1 / t-, taken once per workgroup, so a pair multiplies
+//   Acc  2 P int64 per workgroup behind Rt: the fixed-point cost sums cost+ | cost-
+// A pair's weight is w = Rt+[b(hi)] Rt-[b(lo)], a commutative product of the same two values from either end, so both ends compute the same
+// lam.  The owner of rank r carries two more four-chain sums: its costs as `hi` (c / t-[b(partner)]) and as `lo` (c / t+[b(partner)]); every
+// counted pair is walked from both ends, so each end adds its own side.  Both sums go to fixed point (scale 2^32) and into Acc with 64-bit
+// LDS integer atomics; after a workgroup barrier the non-zero entries of Acc go to the caller's accumulator with 64-bit global integer
+// atomics: at most 2 P per workgroup, no float atomic anywhere.  Integer adds are exact and commute: the totals do not depend on the form, the
+// launch partition or the run.  LDS: 28 Lp per query + 24 P per workgroup: 120 832 bytes at 4096 documents and P = 256.
+constexpr int kLrnIdxBits = 12;                      // PTR_MAX_LIST_LEN = 2^12 documents
+static_assert(PTR_MAX_LIST_LEN <= (1 << kLrnIdxBits) && PTR_TREE_MAX_BIAS_POSITIONS <= 256);
+constexpr float kCostClamp = 0x1p30f;                // one document's cost sum, before the 2^32 scale
+
+// sum -> fixed point: int64 at scale 2^32, round to nearest; a NaN or negative sum counts 0
+__device__ __forceinline__ unsigned long long cost_fixed(float x) {
+    return (unsigned long long)__double2ll_rn((double)fminf(fmaxf(x, 0.0f), kCostClamp) * 4294967296.0);
+}
+
+template <int G, bool UB>
 __global__ void __launch_bounds__(kBlock)
 tree_lambdarank_ndcg_kernel(const float *__restrict__ preds, const float *__restrict__ labels, const int64_t *__restrict__ offsets, int B,
                             const int32_t *__restrict__ queries, int nq, int Lp, int max_len, int T, float sigma, int norm,
-                            float *__restrict__ grad, float *__restrict__ hess) {
+                            float *__restrict__ grad, float *__restrict__ hess, const int32_t *__restrict__ position,
+                            const float *__restrict__ biases, int P, unsigned long long *__restrict__ cost_acc) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, grp = tid / G, t = tid % G;
     const TreeQuery qu = tree_query<G>(offsets, B, queries, nq, max_len, t, grad, hess);
@@ -350,6 +372,15 @@ tree_lambdarank_ndcg_kernel(const float *__restrict__ preds, const float *__rest
 
     float *S = smem + (size_t)grp * kLrnRows * Lp, *Y = S + Lp, *Rs = Y + Lp, *Rg = Rs + Lp, *Rd = Rg + Lp, *H = Rd + Lp;
     int *Ix = reinterpret_cast<int *>(H + Lp);
+    float *Rt = smem + (size_t)(kBlock / G) * kLrnRows * Lp;                     // UB: [2, P] reciprocals, then [2, P] int64 sums
+    unsigned long long *Acc = reinterpret_cast<unsigned long long *>(Rt + 2 * P);
+    if constexpr (UB) {
+        for (int j = tid; j < 2 * P; j += kBlock) {
+            Rt[j] = biases ? 1.0f / biases[j] : 1.0f;
+            Acc[j] = 0ull;
+        }
+        __syncthreads();                                                          // every thread of the block arrives: nothing returned yet
+    }
 
     // ---- stage the scores and the labels; both rows are padded with -inf up to a multiple of 4 (rank_indexed reads float4)
     bool bad = false;
@@ -358,6 +389,7 @@ tree_lambdarank_ndcg_kernel(const float *__restrict__ preds, const float *__rest
         const float s = i < n ? preds[base + i] : -INFINITY, y = i < n ? labels[base + i] : -INFINITY;
         S[i] = s; Y[i] = y;
         bad |= s != s || y != y;
+        if constexpr (UB) bad |= position && i < n && position[base + i] < 0;      // the caller's error: NaN on the list, nothing to the costs
     }
     // a NaN score or label gives the list no ranking (the ranks below would not be a permutation): NaN on every document of this list
     const bool nanq = group_any<G>(bad, tid);
@@ -369,7 +401,13 @@ tree_lambdarank_ndcg_kernel(const float *__restrict__ preds, const float *__rest
             const float s = S[i], y = Y[i];
             const int r = rank_indexed(S, n, i, s), ry = rank_indexed(Y, n, i, y);
             const float g = gain_of(y);
-            Rs[r] = s; Rg[r] = g; Ix[r] = i;
+            Rs[r] = s; Rg[r] = g;
+            if constexpr (UB) {
+                const int b = position ? position[base + i] : i;
+                Ix[r] = i | ((b < P - 1 ? b : P - 1) << kLrnIdxBits);
+            } else {
+                Ix[r] = i;
+            }
             Rd[i] = inv_log2_pos(i);
             H[i] = ry < T ? g * inv_log2_pos(ry) : 0.0f;
         }
@@ -390,7 +428,10 @@ tree_lambdarank_ndcg_kernel(const float *__restrict__ preds, const float *__rest
             // four interleaved chains per sum (partner k adds into chain k mod 4), joined as (0 + 1) + (2 + 3): a fixed order that depends on
             // the query alone, a quarter of the in-order rounding of one chain, and four independent dependency chains for the adder
             float g[4] = {0.0f, 0.0f, 0.0f, 0.0f}, h[4] = {0.0f, 0.0f, 0.0f, 0.0f}, l[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            auto partner = [&](int k, float &ga, float &ha, float &la) {
+            float ch[4] = {0.0f, 0.0f, 0.0f, 0.0f}, cl[4] = {0.0f, 0.0f, 0.0f, 0.0f};      // UB: this document's costs as `hi` and as `lo`
+            const int br = UB ? Ix[r] >> kLrnIdxBits : 0;
+            const float rp_own = UB ? Rt[br] : 1.0f, rm_own = UB ? Rt[P + br] : 1.0f;
+            auto partner = [&](int k, float &ga, float &ha, float &la, float &cha, float &cla) {
                 const float dg = gr - Rg[k];                       // > 0: this document is the pair's `hi`
                 const float d0 = sr - Rs[k];
                 const float ds = dg > 0.0f ? d0 : -d0;             // s_hi - s_lo: the difference first, sigma after
@@ -400,9 +441,21 @@ tree_lambdarank_ndcg_kernel(const float *__restrict__ preds, const float *__rest
                 const float e = __expf(-fabsf(x));
                 const float r1 = rcp1p(e);
                 const float p = x >= 0.0f ? e * r1 : r1;           // 1 / (1 + exp(x))
-                const float lam = sigma * delta * p;
-                const float hv = sigma2 * delta * (e * r1 * r1);   // p (1 - p) without the cancellation of 1 - p
+                float lam = sigma * delta * p;
+                float hv = sigma2 * delta * (e * r1 * r1);         // p (1 - p) without the cancellation of 1 - p
                 const bool on = dg != 0.0f;                        // equal gains: equal labels (k == r among them), or delta = 0
+                if constexpr (UB) {
+                    const bool hi = dg > 0.0f;
+                    // the partner's reciprocal bias on the OTHER side: 1 / t- of a `lo` partner, 1 / t+ of a `hi` one
+                    const float other = Rt[(hi ? P : 0) + (Ix[k] >> kLrnIdxBits)];
+                    const float w = (hi ? rp_own : rm_own) * other;
+                    lam *= w;
+                    hv *= w;
+                    // log(1 + exp(-x)) = max(-x, 0) + log1p(exp(-|x|)); the cost goes to this document's side, divided by the partner's bias
+                    const float c = delta * ((x < 0.0f ? -x : 0.0f) + log1pf(e)) * other;
+                    cha += on && hi ? c : 0.0f;
+                    cla += on && !hi ? c : 0.0f;
+                }
                 ga += on ? (dg > 0.0f ? -lam : lam) : 0.0f;
                 ha += on ? hv : 0.0f;
                 la += on ? lam : 0.0f;
@@ -410,14 +463,19 @@ tree_lambdarank_ndcg_kernel(const float *__restrict__ preds, const float *__rest
             int k = 0;
             for (; k + 4 <= kend; k += 4) {
 #pragma unroll
-                for (int u = 0; u < 4; ++u) partner(k + u, g[u], h[u], l[u]);
+                for (int u = 0; u < 4; ++u) partner(k + u, g[u], h[u], l[u], ch[u], cl[u]);
             }
 #pragma unroll
             for (int u = 0; u < 3; ++u)
-                if (k + u < kend) partner(k + u, g[u], h[u], l[u]);
+                if (k + u < kend) partner(k + u, g[u], h[u], l[u], ch[u], cl[u]);
             Y[r] = (g[0] + g[1]) + (g[2] + g[3]);
             H[r] = (h[0] + h[1]) + (h[2] + h[3]);
             S[r] = (l[0] + l[1]) + (l[2] + l[3]);
+            if constexpr (UB) {
+                const unsigned long long fh = cost_fixed((ch[0] + ch[1]) + (ch[2] + ch[3])), fl = cost_fixed((cl[0] + cl[1]) + (cl[2] + cl[3]));
+                if (fh) atomicAdd(&Acc[br], fh);
+                if (fl) atomicAdd(&Acc[P + br], fl);
+            }
         }
     }
     // S = 2 sum lam: every pair was seen once from each end
@@ -425,13 +483,41 @@ tree_lambdarank_ndcg_kernel(const float *__restrict__ preds, const float *__rest
     const float total = n > 0 ? S[0] : 0.0f;
     if (nanq) {
         for (int i = t; i < n; i += G) { grad[base + i] = NAN; hess[base + i] = NAN; }
-        return;
+        if constexpr (!UB) return;
+    } else {
+        const float scale = norm != 0 && total > 0.0f ? log1pf(total) * 1.4426950408889634f / total : 1.0f;    // log2(1 + S) / S
+        for (int r = t; r < n; r += G) {
+            const int i = UB ? Ix[r] & ((1 << kLrnIdxBits) - 1) : Ix[r];
+            grad[base + i] = Y[r] * scale;
+            hess[base + i] = H[r] * scale;
+        }
     }
-    const float scale = norm != 0 && total > 0.0f ? log1pf(total) * 1.4426950408889634f / total : 1.0f;    // log2(1 + S) / S
-    for (int r = t; r < n; r += G) {
-        const int i = Ix[r];
-        grad[base + i] = Y[r] * scale;
-        hess[base + i] = H[r] * scale;
+    if constexpr (UB) {
+        __syncthreads();                                                          // every group's LDS adds have landed
+        for (int j = tid; j < 2 * P; j += kBlock) {
+            const unsigned long long v = Acc[j];
+            if (v) atomicAdd(&cost_acc[j], v);
+        }
+    }
+}
+
+// ptr_tree_position_bias_update: one workgroup, thread p serves position p of both signs
+__global__ void __launch_bounds__(PTR_TREE_MAX_BIAS_POSITIONS)
+tree_position_bias_update_kernel(long long *__restrict__ cost_acc, int P, double inv_exp, float *__restrict__ biases, double *__restrict__ costs_out) {
+    const int p = threadIdx.x;
+    double c[2] = {0.0, 0.0}, c0[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        c0[s] = (double)cost_acc[s * P] * 0x1p-32;
+        if (p < P) c[s] = (double)cost_acc[s * P + p] * 0x1p-32;
+    }
+    __syncthreads();                                                              // every thread has read position 0 before it is cleared
+    if (p >= P) return;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        if (costs_out) costs_out[s * P + p] = c[s];
+        if (c0[s] > 0.0 && c[s] > 0.0) biases[s * P + p] = (float)fmax(0x1p-10, pow(c[s] / c0[s], inv_exp));
+        cost_acc[s * P + p] = 0;
     }
 }
 
@@ -537,9 +623,51 @@ extern "C" int ptr_tree_lambdarank_ndcg_grad_hess(const float *preds, const floa
     const int Lp = round_up(max_len, 4);
     return dispatch_tree_form(max_len, [&]<int G>() {
         const size_t lds = (size_t)(kBlock / G) * kLrnRows * Lp * sizeof(float);
-        return launch_queries(tree_lambdarank_ndcg_kernel<G>, nq, kBlock / G, kBlock, lds, stream, who, preds, labels, offsets, B, queries, nq, Lp,
-                              max_len, truncation_level, sigmoid, norm, grad, hess);
+        return launch_queries(tree_lambdarank_ndcg_kernel<G, false>, nq, kBlock / G, kBlock, lds, stream, who, preds, labels, offsets, B, queries, nq,
+                              Lp, max_len, truncation_level, sigmoid, norm, grad, hess, (const int32_t *)nullptr, (const float *)nullptr, 0,
+                              (unsigned long long *)nullptr);
     });
+}
+
+static int tree_check_npos(int npos, const void *cost_acc, const char *who) {
+    using namespace ptr;
+    if (npos < 1 || npos > PTR_TREE_MAX_BIAS_POSITIONS) {
+        set_error("%s: npos must be in 1 .. PTR_TREE_MAX_BIAS_POSITIONS=%d (got %d)", who, PTR_TREE_MAX_BIAS_POSITIONS, npos);
+        return PTR_ERR_INVALID_ARG;
+    }
+    if (!cost_acc) { set_error("%s: NULL cost_acc", who); return PTR_ERR_INVALID_ARG; }
+    return 0;
+}
+
+extern "C" int ptr_tree_lambdarank_unbiased_grad_hess(const float *preds, const float *labels, const int32_t *position, const int64_t *offsets, int B,
+                                                      const int32_t *queries, int nq, int max_len, int truncation_level, float sigmoid, int norm,
+                                                      const float *biases, int npos, int64_t *cost_acc, float *grad, float *hess, void *stream) {
+    using namespace ptr;
+    const char *who = "ptr_tree_lambdarank_unbiased_grad_hess";
+    if (int rc = tree_check(preds, labels, offsets, B, queries, nq, max_len, PTR_TREE_HESS_SUM, grad, hess, who)) return rc;
+    if (truncation_level < 1) { set_error("%s: truncation_level must be >= 1 (got %d)", who, truncation_level); return PTR_ERR_INVALID_ARG; }
+    if (!(sigmoid > 0.0f)) { set_error("%s: sigmoid must be > 0 (got %g)", who, (double)sigmoid); return PTR_ERR_INVALID_ARG; }
+    if (int rc = tree_check_npos(npos, cost_acc, who)) return rc;
+    if (int rc = tree_check_len(max_len, who)) return rc;
+    if (nq == 0 || max_len == 0) return 0;
+    const int Lp = round_up(max_len, 4);
+    return dispatch_tree_form(max_len, [&]<int G>() {
+        const size_t lds = (size_t)(kBlock / G) * kLrnRows * Lp * sizeof(float) + (size_t)npos * (2 * sizeof(float) + 2 * sizeof(int64_t));
+        return launch_queries(tree_lambdarank_ndcg_kernel<G, true>, nq, kBlock / G, kBlock, lds, stream, who, preds, labels, offsets, B, queries, nq,
+                              Lp, max_len, truncation_level, sigmoid, norm, grad, hess, position, biases, npos,
+                              reinterpret_cast<unsigned long long *>(cost_acc));
+    });
+}
+
+extern "C" int ptr_tree_position_bias_update(int64_t *cost_acc, int npos, double p_norm, float *biases, double *costs_out, void *stream) {
+    using namespace ptr;
+    const char *who = "ptr_tree_position_bias_update";
+    if (int rc = tree_check_npos(npos, cost_acc, who)) return rc;
+    if (!biases) { set_error("%s: NULL biases", who); return PTR_ERR_INVALID_ARG; }
+    if (!(p_norm >= 0.0)) { set_error("%s: p_norm must be >= 0 (got %g)", who, p_norm); return PTR_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(tree_position_bias_update_kernel, dim3(1), dim3(PTR_TREE_MAX_BIAS_POSITIONS), 0, as_stream(stream),
+                       reinterpret_cast<long long *>(cost_acc), npos, 1.0 / (1.0 + p_norm), biases, costs_out);
+    return check_hip(hipGetLastError(), who);
 }
 
 extern "C" int ptr_tree_xendcg_grad_hess(const float *preds, const float *labels, const int64_t *offsets, int B, const int32_t *queries, int nq,

@@ -16,7 +16,7 @@ from . import _lib
 
 __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_loss", "listnet_loss", "listmle_loss",
            "stlistnet_loss", "rankmse_loss", "rankcosine_loss",
-           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "ndeval_measures", "div_ideal_order", "NDEVAL_MEASURES","divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "tree_lambdarank_ndcg_grad_hess", "tree_xendcg_grad_hess", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
+           "softrank_loss", "mdprank_loss", "wassrank_loss", "WASS_COST_TYPES", "alphadcg_loss", "div_metrics_at_ks", "ADCG_TOPK_AXES", "ndeval_measures", "div_ideal_order", "NDEVAL_MEASURES","divprob_loss", "expected_ranks", "DIVPROB_OBJECTIVES", "tree_pair_grad_hess", "tree_listnet_grad_hess", "tree_lambdarank_ndcg_grad_hess", "tree_xendcg_grad_hess", "tree_lambdarank_unbiased_grad_hess", "tree_position_bias_update", "TREE_PAIR_TYPES", "TREE_WEIGHTINGS", "TREE_HESSIANS",
            "TREE_GAIN_TYPES", "smooth_metric_objective", "SMOOTH_METRICS", "gaussian_metric_objective", "pl_uniforms", "sample_rankings_pl", "PL_DISTRIBUTIONS",
            "irgan_uniforms", "irgan_sample", "irgan_point_generator", "irgan_selected", "IRGAN_SAMPLE_MODES", "IRGAN_SELECTED_MODES", "IRGAN_MAX_SAMPLES",
            "irfgan_uniforms", "irfgan_point_sample", "irfgan_pair_sample", "IRFGAN_MODES", "F_DIVERGENCES",
@@ -876,10 +876,11 @@ def adlist_loss(x, mode, prob="PL", family="IRGAN", reward="exp_1m", f_div="KL",
     return loss
 
 
-def _ragged(entry, preds, labels, offsets, queries, max_len, out, *params):
+def _ragged(entry, preds, labels, offsets, queries, max_len, out, *params, per_document=()):
     """The one launch path of the ragged (LightGBM-layout) entry points: (preds, labels, offsets, B, queries, nq, max_len, <params>, grad,
     hess, stream) -> (grad, hess).  preds / labels: flat float32 [N]; offsets: int64 [B + 1], the running sum of the group sizes; queries:
-    int32 [nq] or None (all); max_len: the longest launched list (None: read back from `offsets`, which costs a host sync)."""
+    int32 [nq] or None (all); max_len: the longest launched list (None: read back from `offsets`, which costs a host sync).
+    per_document: further checked per-document arrays (or None) that the entry point takes between labels and offsets."""
     preds = _check("preds", preds)
     if preds.dim() != 1:
         raise ValueError(f"preds must be flat [documents], got {tuple(preds.shape)}")
@@ -907,8 +908,8 @@ def _ragged(entry, preds, labels, offsets, queries, max_len, out, *params):
         out = (new(preds), new(preds))
     grad, hess = (_check(n, t, shape=preds.shape) for n, t in zip(("grad", "hess"), out))
     with torch.cuda.device(dev):
-        _lib.call(entry, _lib.ptr(preds), _lib.ptr(labels), _lib.ptr(offsets), B, _lib.ptr(queries), nq, int(max_len), *params, _lib.ptr(grad),
-                  _lib.ptr(hess), _lib.current_stream(dev))
+        _lib.call(entry, _lib.ptr(preds), _lib.ptr(labels), *(_lib.ptr(t) for t in per_document), _lib.ptr(offsets), B, _lib.ptr(queries), nq,
+                  int(max_len), *params, _lib.ptr(grad), _lib.ptr(hess), _lib.current_stream(dev))
     return grad, hess
 
 
@@ -958,6 +959,70 @@ def tree_lambdarank_ndcg_grad_hess(preds, labels, offsets, truncation_level=30, 
     Arguments and layout as tree_pair_grad_hess."""
     t, sigma, norm = lambdarank_ndcg_settings(truncation_level, sigmoid, norm)
     return _ragged("ptr_tree_lambdarank_ndcg_grad_hess", preds, labels, offsets, queries, max_len, out, min(t, 2 ** 31 - 1), C.c_float(sigma), int(norm))
+
+
+MAX_BIAS_POSITIONS = 256      # PTR_TREE_MAX_BIAS_POSITIONS
+
+
+def position_bias_settings(bias_p_norm=0.5, bias_positions=None, truncation_level=30):
+    """The settings of the position-debiased lambdarank, validated -> (float p_norm >= 0, int P in 1 .. MAX_BIAS_POSITIONS).
+    bias_positions None: truncation_level, capped at MAX_BIAS_POSITIONS (LightGBM's lambdarank_bias_p_norm; the cap is this project's)."""
+    pn = bias_p_norm
+    if isinstance(pn, (bool, np.bool_)) or not isinstance(pn, (int, float, np.integer, np.floating)) or not (0.0 <= float(pn) < np.inf):
+        raise ValueError(f"lambdarank_bias_p_norm must be a finite number >= 0, got {bias_p_norm!r}")
+    P = min(int(truncation_level), MAX_BIAS_POSITIONS) if bias_positions is None else bias_positions
+    if isinstance(P, (bool, np.bool_)) or not isinstance(P, (int, np.integer)) or not 1 <= P <= MAX_BIAS_POSITIONS:
+        raise ValueError(f"lambdarank_bias_positions must be None or an integer in 1 .. {MAX_BIAS_POSITIONS}, got {bias_positions!r}")
+    return float(pn), int(P)
+
+
+def _bias_state(name, t, dtype, P, dev):
+    """A [2, P] array a kernel updates in place: checked, and refused where _check would have to copy it."""
+    if _check(name, t, dtype, (2, P)).data_ptr() != t.data_ptr() or t.device != dev:
+        raise ValueError(f"{name} must be contiguous and on {dev}: the kernel updates it in place")
+    return t
+
+
+def tree_lambdarank_unbiased_grad_hess(preds, labels, offsets, cost_acc, biases=None, position=None, truncation_level=30, sigmoid=1.0, norm=True,
+                                       queries=None, max_len=None, out=None):
+    """Gradient and Hessian per document of the position-debiased lambdarank (Unbiased LambdaMART, Hu et al. 2019; LightGBM's
+    lambdarank_unbiased) over the ragged layout, in one launch (ptr_tree_lambdarank_unbiased_grad_hess; include/ptranking_amd.h states the
+    rule, which is this project's own).  tree_lambdarank_ndcg_grad_hess with every pair's lam and h divided by t+[b(hi)] t-[b(lo)], where
+    b(d) = min(position[d], P - 1) is the class of the position document d was shown at (position: int32 [documents], 0-based; None: the
+    index within the query) and biases is float32 [2, P] (t+ | t-; None: all 1, which gives tree_lambdarank_ndcg_grad_hess bit for bit).
+    cost_acc, int64 [2, P], is ADDED to: the pair costs delta log(1 + exp(-sigmoid ds)) per position at scale 2^32, cost+[b(hi)] += c /
+    t-[b(lo)] and cost-[b(lo)] += c / t+[b(hi)], by integer atomics (the same bits whatever the launch partition); P is read from its
+    shape.  tree_position_bias_update turns it into the next round's biases.  A negative position gives NaN on its list."""
+    t, sigma, norm = lambdarank_ndcg_settings(truncation_level, sigmoid, norm)
+    preds = _check("preds", preds)
+    if not isinstance(cost_acc, torch.Tensor) or cost_acc.dim() != 2:
+        raise ValueError("cost_acc must be an int64 [2, positions] tensor")
+    P = position_bias_settings(0.0, int(cost_acc.shape[1]))[1]
+    _bias_state("cost_acc", cost_acc, torch.int64, P, preds.device)
+    if biases is not None and _check("biases", biases, shape=(2, P)).device != preds.device:
+        raise RuntimeError("preds and biases live on different devices")
+    if position is not None and _check("position", position, torch.int32, preds.shape).device != preds.device:
+        raise RuntimeError("preds and position live on different devices")
+    return _ragged("ptr_tree_lambdarank_unbiased_grad_hess", preds, labels, offsets, queries, max_len, out, min(t, 2 ** 31 - 1), C.c_float(sigma),
+                   int(norm), _lib.ptr(None if biases is None else biases.contiguous()), P, _lib.ptr(cost_acc),
+                   per_document=(None if position is None else position.contiguous(),))
+
+
+def tree_position_bias_update(cost_acc, biases, p_norm=0.5, return_costs=False):
+    """One launch, no host read (ptr_tree_position_bias_update): cost = cost_acc 2^-32 in float64; per sign, where cost[0] > 0 every
+    position p with cost[p] > 0 gets biases[p] = max(2^-10, (cost[p] / cost[0]) ^ (1 / (1 + p_norm))) (a position without cost keeps its
+    bias); cost_acc is zeroed for the next round.  biases (float32 [2, P]) and cost_acc (int64 [2, P]) are updated in place.  Returns
+    biases, or (biases, costs float64 [2, P]) with return_costs."""
+    if not isinstance(cost_acc, torch.Tensor) or cost_acc.dim() != 2:
+        raise ValueError("cost_acc must be an int64 [2, positions] tensor")
+    pn, P = position_bias_settings(p_norm, int(cost_acc.shape[1]))
+    dev = cost_acc.device
+    _bias_state("cost_acc", cost_acc, torch.int64, P, dev)
+    _bias_state("biases", biases, torch.float32, P, dev)
+    costs = torch.empty((2, P), device=dev, dtype=torch.float64) if return_costs else None
+    with torch.cuda.device(dev):
+        _lib.call("ptr_tree_position_bias_update", _lib.ptr(cost_acc), P, C.c_double(pn), _lib.ptr(biases), _lib.ptr(costs), _lib.current_stream(dev))
+    return (biases, costs) if return_costs else biases
 
 
 def _count(name, v, top=2 ** 63 - 1):

@@ -212,6 +212,9 @@ DEFAULT_PARAMS = {"learning_rate": 0.1, "num_leaves": 31, "num_trees": 100, "min
                   # LambdaMART(objective='lambdarank_ndcg') alone reads these three; the other objectives and the bare booster ignore them
                   "lambdarank_truncation_level": 30, "lambdarank_norm": True, "sigmoid": 1.0,
                   "objective_seed": 5,                    # LambdaMART(objective='rank_xendcg') alone reads it
+                  # position-debiased lambdarank (Unbiased LambdaMART): LambdaMART(objective='lambdarank_ndcg') alone reads these three
+                  # (LightGBM's names; lambdarank_bias_positions, the number of position classes, is this project's own)
+                  "lambdarank_unbiased": False, "lambdarank_bias_p_norm": 0.5, "lambdarank_bias_positions": None,
                   # quantized-gradient training: the first four names are LightGBM's, quant_seed is this project's own
                   "use_quantized_grad": False, "num_grad_quant_bins": 4, "stochastic_rounding": True, "quant_train_renew_leaf": False, "quant_seed": 0,
                   # DART (the argument boosting='dart', which sets boosting_type here): the other six are read under it alone (LightGBM's names and defaults)
@@ -229,6 +232,7 @@ CST_KEYS = ("monotone_constraints", "monotone_constraints_method", "interaction_
 QUANT_KEYS = ("use_quantized_grad", "num_grad_quant_bins", "stochastic_rounding", "quant_train_renew_leaf", "quant_seed")   # likewise: only under the switch
 DART_KEYS = ("boosting_type", "drop_rate", "max_drop", "skip_drop", "uniform_drop", "xgboost_dart_mode", "drop_seed")   # likewise: only under 'dart'
 LINEAR_KEYS = ("linear_tree", "linear_lambda")      # likewise: only under linear_tree
+UNBIASED_KEYS = ("lambdarank_unbiased", "lambdarank_bias_p_norm", "lambdarank_bias_positions")   # likewise: only under lambdarank_unbiased
 LINEAR_ARRAYS = ("leaf_features", "leaf_coeff", "leaf_const")      # what a linear tree keeps beside its arrays, per leaf
 BOOSTING_TYPES = ("gbdt", "dart")
 MONOTONE_METHODS = ("basic",)
@@ -310,6 +314,12 @@ def _params(params, boosting=None):
     p["lambdarank_truncation_level"], p["sigmoid"], p["lambdarank_norm"] = F.lambdarank_ndcg_settings(p["lambdarank_truncation_level"], p["sigmoid"],
                                                                                                    p["lambdarank_norm"])
     p["objective_seed"] = F.objective_seed(p["objective_seed"])
+    if not isinstance(p["lambdarank_unbiased"], (bool, np.bool_)):
+        raise ValueError(f"lambdarank_unbiased must be True or False, got {p['lambdarank_unbiased']!r}")
+    p["lambdarank_unbiased"] = bool(p["lambdarank_unbiased"])
+    p["lambdarank_bias_p_norm"] = F.position_bias_settings(p["lambdarank_bias_p_norm"], p["lambdarank_bias_positions"])[0]
+    if p["lambdarank_bias_positions"] is not None:
+        p["lambdarank_bias_positions"] = int(p["lambdarank_bias_positions"])
     p["num_grad_quant_bins"] = F.gbdt_quant_levels(p["num_grad_quant_bins"])
     seed = p["quant_seed"]
     if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
@@ -1652,6 +1662,8 @@ class GBDT:
             own = {k: v for k, v in own.items() if k not in QUANT_KEYS}
         if own["boosting_type"] != "dart":                                 # likewise
             own = {k: v for k, v in own.items() if k not in DART_KEYS}
+        if not own["lambdarank_unbiased"]:                                 # likewise (the biases themselves are training state: no file holds them)
+            own = {k: v for k, v in own.items() if k not in UNBIASED_KEYS}
         linear = own["linear_tree"]
         if not linear:                                                     # likewise
             own = {k: v for k, v in own.items() if k not in LINEAR_KEYS}
@@ -1726,7 +1738,12 @@ class LambdaMART:
     low-ranked documents, so leaves can stay unsplittable under the Hessian floor of the split scan.
     objective 'lambdarank_ndcg' is the truncated, normalised lambdarank of the module docstring: it reads lambdarank_truncation_level,
     lambdarank_norm and sigmoid from params, and weighting, hessian, pair_type, epsilon and gain_type do not apply to it (a non-default
-    value raises ValueError).
+    value raises ValueError).  With lambdarank_unbiased in params it is the position-debiased lambdarank for click logs (Unbiased LambdaMART;
+    include/ptranking_amd.h states the rule, this project's own): fit(..., position=) takes the 0-based position each document was shown
+    at, every pair's lam and h are divided by the learned biases t+[b(hi)] t-[b(lo)] of lambdarank_bias_positions position classes (None:
+    the truncation level, capped at 256), one launch per round re-estimates them from the pair costs with the exponent
+    1 / (1 + lambdarank_bias_p_norm), and .position_biases reads them after the fit.  The model file does not hold them: init_model and
+    refit raise under the switch.  The other objectives ignore the three settings.
     objective 'rank_xendcg' is the cross-entropy nDCG objective of the module docstring: it reads objective_seed from params, draws round
     t's uniforms under draw = t (the tree counter), and the same five settings do not apply to it."""
 
@@ -1755,11 +1772,32 @@ class LambdaMART:
         self.booster = None
         self.evals_result = []
         self.best_iteration = self.best_score = self.valid_scores = None
+        # the position-debiased lambdarank: 'lambdarank_ndcg' alone reads the switch; the state is made by fit
+        self.unbiased = self.kind == "lambdarank_ndcg" and self.params["lambdarank_unbiased"]
+        self._bias = None
+
+    @property
+    def position_biases(self):
+        """After a fit under lambdarank_unbiased: numpy float32 [2, P], the learned t+ | t- per position class."""
+        if self._bias is None:
+            raise RuntimeError("position_biases exists after a fit under objective 'lambdarank_ndcg' with lambdarank_unbiased alone")
+        return self._bias.biases.cpu().numpy()
 
     def grad_hess(self, scores, res, out=None, draw=0):
         """The round's gradient and Hessian per document, on the device: one launch per length class of tree.bucket_queries, exactly as
-        TreeObjective._run launches them.  draw: the round whose uniforms 'rank_xendcg' draws (the other objectives ignore it)."""
+        TreeObjective._run launches them.  draw: the round whose uniforms 'rank_xendcg' draws (the other objectives ignore it).  Under
+        lambdarank_unbiased the launches read the biases of the previous round and one more launch updates them."""
         out = (torch.empty_like(scores), torch.empty_like(scores)) if out is None else out
+        if self.unbiased:
+            p = self.params
+            if self._bias is None:
+                self._bias = tree.PositionBias(F.position_bias_settings(p["lambdarank_bias_p_norm"], p["lambdarank_bias_positions"],
+                                                                        p["lambdarank_truncation_level"])[1], p["lambdarank_bias_p_norm"], scores.device)
+            for max_len, queries in res.buckets:
+                F.tree_lambdarank_unbiased_grad_hess(scores, res.labels, res.offsets, self._bias.cost_acc, self._bias.biases, res.position,
+                                                     p["lambdarank_truncation_level"], p["sigmoid"], p["lambdarank_norm"], queries, max_len, out)
+            self._bias.update()
+            return out
         for max_len, queries in res.buckets:
             if self.kind == "pair":
                 F.tree_pair_grad_hess(scores, res.labels, res.offsets, self.pair_type, self.weighting, self.epsilon, self.hessian, queries, max_len, out)
@@ -1795,8 +1833,10 @@ class LambdaMART:
         return float(nd[keep].mean()) if bool(keep.any()) else 0.0
 
     def fit(self, X, y, group, eval_set=None, eval_group=None, eval_at=5, early_stopping_rounds=None, num_boost_round=None, verbose=0,
-            init_model=None):
-        """X [n, F], y [n] relevance grades, group: documents per query.  eval_set = (X_valid, y_valid) with eval_group: nDCG@eval_at on it
+            init_model=None, position=None):
+        """X [n, F], y [n] relevance grades, group: documents per query.  position (read under lambdarank_unbiased alone): the 0-based
+        position each document was shown at, None for its index within its query; the biases start at 1 with every fit, and
+        .position_biases reads them afterwards.  eval_set = (X_valid, y_valid) with eval_group: nDCG@eval_at on it
         after every round (evals_result); early_stopping_rounds: stop after that many rounds without improvement and let predict use the
         best round (best_iteration), as LightGBM does.
         init_model (a GBDT, a LambdaMART or the path of a saved model): the rounds are ADDED to that model's trees (GBDT.fit_bins): the
@@ -1806,7 +1846,11 @@ class LambdaMART:
         if dart and early_stopping_rounds is not None:
             raise ValueError("early_stopping_rounds is not available under boosting_type 'dart': later rounds rewrite earlier trees, so no "
                              "earlier round's model can be returned")
-        res = tree._Resident(y, group, self.device)
+        if self.unbiased and init_model is not None:
+            raise ValueError("init_model is not available under lambdarank_unbiased: the position biases are training state that the model "
+                             "file does not hold")
+        self._bias = None                                                  # every fit learns its own biases, from 1
+        res = tree._Resident(y, group, self.device, position if self.unbiased else None)
         X = X if isinstance(X, torch.Tensor) else np.asarray(X)
         if X.shape[0] != res.n_docs:
             raise ValueError(f"X holds {X.shape[0]} rows, the groups {res.n_docs}")
@@ -1872,6 +1916,8 @@ class LambdaMART:
         decay = _decay_rate(decay_rate)
         if self.booster is None:
             raise RuntimeError("fit() first")
+        if self.unbiased:
+            raise ValueError("refit is not available under lambdarank_unbiased: it would go on training the position biases of the fit")
         res = tree._Resident(y, group, self.device)
         if np.shape(X)[0] != res.n_docs:
             raise ValueError(f"X holds {np.shape(X)[0]} rows, the groups {res.n_docs}")

@@ -22,7 +22,10 @@ tree frame runs by default through LightGBM's BUILT-IN objective='lambdarank' (l
 own, modelled on LightGBM's LambdarankNDCG and compared with nothing of LightGBM's (include/ptranking_amd.h states it): a pair counts where
 the labels differ and one of its documents ranks in the first truncation_level; its weight is the Delta-nDCG against maxDCG@truncation_level,
 divided by 0.01 + |score difference| under norm; under norm a query's results are scaled by log2(1 + S) / S, S = 2 sum lam.  Its Hessian is
-never negative, and a list without a relevant document is exactly 0 where weighting='DeltaNDCG' gives NaN.
+never negative, and a list without a relevant document is exactly 0 where weighting='DeltaNDCG' gives NaN.  unbiased=True makes it the
+position-debiased lambdarank for click logs (Unbiased LambdaMART, Hu et al. 2019; again a rule of this project's own): every pair's lam
+and h are divided by t+[position of hi] t-[position of lo], and the per-position sums of the pair costs, accumulated on the device in
+fixed point, re-estimate both bias rows after every call.
 
 objective='rank_xendcg' is LightGBM's second built-in ranking objective, the cross-entropy nDCG loss of Bruch ("An Alternative Cross Entropy
 Loss for Learning-to-Rank"), which costs O(n) per query where lambdarank costs O(n T).  Again the rule is this project's own, modelled on
@@ -40,7 +43,7 @@ import torch
 from . import _lib
 from . import functional as F
 
-__all__ = ["TreeObjective", "bucket_queries", "LENGTH_CLASSES", "OBJECTIVES", "lightgbm_custom_obj_ranknet", "lightgbm_custom_obj_lambdarank",
+__all__ = ["TreeObjective", "PositionBias", "bucket_queries", "LENGTH_CLASSES", "OBJECTIVES", "lightgbm_custom_obj_ranknet", "lightgbm_custom_obj_lambdarank",
            "lightgbm_custom_obj_listnet", "lightgbm_custom_obj_ranknet_fobj", "lightgbm_custom_obj_lambdarank_fobj",
            "lightgbm_custom_obj_listnet_fobj", "DROP_IN_NAMES", "FIRST_ORDER", "CONSTANT_HESSIAN"]
 
@@ -84,10 +87,38 @@ def not_applicable(objective, given, defaults):
             raise ValueError(f"{k}={v!r} does not apply to objective {objective!r} (leave it at its default {d!r})")
 
 
-class _Resident:
-    """Labels, offsets and the per-class query lists of one dataset, uploaded once."""
+class PositionBias:
+    """The training state of the position-debiased lambdarank, on the device across rounds: biases float32 [2, P] (t+ | t-, all 1 at the
+    start) and the fixed-point cost accumulator int64 [2, P] that the round's launches add to and update() consumes."""
 
-    def __init__(self, labels, group, device):
+    def __init__(self, positions, p_norm, device):
+        self.p_norm, self.positions = F.position_bias_settings(p_norm, positions)
+        self.biases = torch.ones((2, self.positions), device=device, dtype=torch.float32)
+        self.cost_acc = torch.zeros((2, self.positions), device=device, dtype=torch.int64)
+
+    def update(self):
+        """One launch after the round's per-class launches: the next round's biases; the accumulator reads zero again."""
+        F.tree_position_bias_update(self.cost_acc, self.biases, self.p_norm)
+
+
+def positions_of(position, n_docs):
+    """The shown positions of a dataset, validated -> int32 [n_docs] (None stays None: a document's index within its query)."""
+    if position is None:
+        return None
+    pos = np.asarray(position).reshape(-1)
+    if pos.size != n_docs:
+        raise ValueError(f"position holds {pos.size} documents, the dataset {n_docs}")
+    if not np.issubdtype(pos.dtype, np.integer) and not (np.isfinite(pos).all() and (pos == np.floor(pos)).all()):
+        raise ValueError("position must hold integers")
+    if pos.size and pos.min() < 0:
+        raise ValueError("position holds a negative value (positions are 0-based)")
+    return np.ascontiguousarray(np.minimum(pos, 2 ** 31 - 1), dtype=np.int32)
+
+
+class _Resident:
+    """Labels, offsets and the per-class query lists of one dataset (and the shown positions, where given), uploaded once."""
+
+    def __init__(self, labels, group, device, position=None):
         labels = np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.float32)
         group = np.asarray(group).reshape(-1)
         self.buckets_host = bucket_queries(group)
@@ -97,6 +128,8 @@ class _Resident:
         self.n_docs, self.n_queries = labels.size, group.size
         self.labels_host, self.group_host = labels, group.copy()
         self.labels = torch.from_numpy(labels).to(device)
+        position = positions_of(position, labels.size)
+        self.position = None if position is None else torch.from_numpy(position).to(device)
         self.offsets = torch.from_numpy(offsets).to(device)
         self.buckets = [(m, torch.from_numpy(idx).to(device)) for m, idx in self.buckets_host]
 
@@ -113,7 +146,11 @@ class TreeObjective:
     call moves only `preds` to the device and `grad` / `hess` back.  objective: 'ranknet' (pair_type 'All'), 'lambdarank' ('NoTies') or
     'listnet', or 'lambdarank_ndcg' (the truncated, normalised lambdarank of the module docstring, with truncation_level, sigmoid and norm;
     pair_type, weighting, epsilon, hessian and gain_type do not apply to it, and a non-default value raises; the other objectives ignore
-    its three settings), or 'rank_xendcg' (the cross-entropy nDCG objective of the module docstring, with objective_seed; the same five
+    its three settings; unbiased=True makes it the position-debiased lambdarank for click logs, Unbiased LambdaMART: `position` holds the
+    0-based position each document was shown at (None: its index within its query) and is uploaded once with the labels, bias_positions
+    is the number of position classes (None: truncation_level capped at 256), bias_p_norm the regulariser of the update; the biases and
+    the cost accumulator stay on the device across rounds, one update launch follows the per-class launches of each call, and
+    .position_biases reads the biases as numpy [2, P], t+ | t-; the other objectives ignore the four), or 'rank_xendcg' (the cross-entropy nDCG objective of the module docstring, with objective_seed; the same five
     settings do not apply to it; .draw, which starts at 0 and advances by one per __call__ / fobj / sklearn call, numbers the round whose
     uniforms a call draws).  The defaults are the reference's wrappers: unweighted, epsilon 1, the rank-signed Hessian, gain 'Power'.  Opt-in, and not
     what the reference computes: weighting='DeltaNDCG' (real LambdaMART) or 'DeltaGain', hessian='sum' (never negative) or 'constant'.
@@ -123,7 +160,8 @@ class TreeObjective:
     objective for .fobj / .sklearn alone, which take both from their arguments.  There is no CPU path: without a GPU it raises."""
 
     def __init__(self, labels=None, group=None, objective="lambdarank", pair_type=None, weighting=None, epsilon=1.0, hessian="reference",
-                 gain_type="Power", device=None, truncation_level=30, sigmoid=1.0, norm=True, objective_seed=5):
+                 gain_type="Power", device=None, truncation_level=30, sigmoid=1.0, norm=True, objective_seed=5, unbiased=False, bias_p_norm=0.5,
+                 bias_positions=None, position=None):
         if objective not in OBJECTIVES:
             raise ValueError(f"objective {objective!r} (supported: {', '.join(map(repr, OBJECTIVES))})")
         self.objective = objective
@@ -132,6 +170,11 @@ class TreeObjective:
         self.weighting, self.epsilon, self.hessian, self.gain_type = weighting, float(epsilon), hessian, gain_type
         self.truncation_level, self.sigmoid, self.norm = F.lambdarank_ndcg_settings(truncation_level, sigmoid, norm)
         self.objective_seed, self.draw = F.objective_seed(objective_seed), 0
+        if not isinstance(unbiased, (bool, np.bool_)):
+            raise ValueError(f"unbiased must be True or False, got {unbiased!r}")
+        self.unbiased = bool(unbiased) and self.kind == "lambdarank_ndcg"
+        self.bias_p_norm, self.bias_positions = F.position_bias_settings(bias_p_norm, bias_positions, self.truncation_level)
+        self._position, self._bias = (position if self.unbiased else None), None
         if self.kind == "pair":
             F._enum("pair_type", self.pair_type, F.TREE_PAIR_TYPES)
             F._enum("weighting", weighting, F.TREE_WEIGHTINGS)
@@ -154,7 +197,14 @@ class TreeObjective:
     def _resident(self, labels, group):
         if not torch.cuda.is_available():
             raise RuntimeError("TreeObjective needs a GPU: ptranking_amd runs on the MI355X HIP path only (no CPU fallback)")
-        return _Resident(labels, group, torch.device("cuda" if self._device is None else self._device))
+        return _Resident(labels, group, torch.device("cuda" if self._device is None else self._device), self._position)
+
+    @property
+    def position_biases(self):
+        """numpy float32 [2, P]: t+ | t- as the last call left them (all 1 before the first)."""
+        if not self.unbiased:
+            raise RuntimeError("position_biases exists under objective 'lambdarank_ndcg' with unbiased=True alone")
+        return np.ones((2, self.bias_positions), np.float32) if self._bias is None else self._bias.biases.cpu().numpy()
 
     def _run(self, res, preds):
         preds = np.asarray(preds)
@@ -162,8 +212,13 @@ class TreeObjective:
             raise ValueError(f"preds holds {preds.size} documents, the dataset {res.n_docs}")
         p = torch.from_numpy(np.ascontiguousarray(preds.reshape(-1), dtype=np.float32)).to(res.labels.device)
         out = (torch.empty_like(p), torch.empty_like(p))
+        if self.unbiased and self._bias is None:
+            self._bias = PositionBias(self.bias_positions, self.bias_p_norm, p.device)
         for max_len, queries in res.buckets:
-            if self.kind == "pair":
+            if self.unbiased:
+                F.tree_lambdarank_unbiased_grad_hess(p, res.labels, res.offsets, self._bias.cost_acc, self._bias.biases, res.position,
+                                                     self.truncation_level, self.sigmoid, self.norm, queries, max_len, out)
+            elif self.kind == "pair":
                 F.tree_pair_grad_hess(p, res.labels, res.offsets, self.pair_type, self.weighting, self.epsilon, self.hessian, queries, max_len, out)
             elif self.kind == "lambdarank_ndcg":
                 F.tree_lambdarank_ndcg_grad_hess(p, res.labels, res.offsets, self.truncation_level, self.sigmoid, self.norm, queries, max_len, out)
@@ -171,6 +226,8 @@ class TreeObjective:
                 F.tree_xendcg_grad_hess(p, res.labels, res.offsets, self.objective_seed, self.draw, None, queries, max_len, out)
             else:
                 F.tree_listnet_grad_hess(p, res.labels, res.offsets, self.gain_type, self.hessian, queries, max_len, out)
+        if self.unbiased:
+            self._bias.update()
         self.draw += 1                                                     # one call per boosting round (rank_xendcg's stream reads it)
         both = torch.stack(out).cpu().numpy().astype(np.float64)           # one copy back; every document belongs to a launched query
         return both[0], both[1]
