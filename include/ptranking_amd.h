@@ -1059,6 +1059,8 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *   ptr_lambdaloss_fwd_bwd                       L, k, loss_type, presort, aligned        vec, G, V              vec: 1 top-k kernel; 0 generic, (G, DPT)
  *   ptr_mhsa_forward, ptr_mhsa_backward          L, head dim, row stride, ds_ws given,    wide, D, forward row tiles, dK/dV waves, stored dS,
  *                                                alignment of the arrays in bytes           floats per global access
+ *   ptr_xattn_forward, ptr_xattn_backward        Lq, Lk, head dim                         short side (0 keys / 1 queries), D, waves, row tiles of
+ *                                                                                           the short side the kernel is compiled for (1, 2, 4)
  *   ptr_layernorm_forward, ptr_layernorm_backward   R, F                                  NI, forward workgroups, backward workgroups
  *   ptr_wassrank_fwd_bwd                         L                                        G, DPT
  *   ptr_neuralndcg_fwd_bwd                       L, iters                                 resident (1: K in LDS, 0: recomputed), G, history in
@@ -1635,6 +1637,34 @@ int ptr_gbdt_predict_linear(const float *X, int64_t n, int F, const int32_t *fea
 int ptr_gbdt_add_tree_linear(float *scores, const float *X, int64_t n, int F, const int32_t *feature, const float *threshold, const int32_t *left,
                              const int32_t *right, const float *value, const int32_t *tree_offsets, const uint8_t *default_left,
                              const int32_t *leaf_features, const double *leaf_coeff, const double *leaf_const, void *stream);
+
+/* ---- Rectangular attention with one short side (csrc/xattn.hip), the core of SetRank's induced self-attention blocks (setrank.py).  The
+ * two symbols below are ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8 and nothing above changes.  The rule is this project's own,
+ * modelled on the Set Transformer's ISAB (Lee et al. 2019) as SetRank uses it (Pang et al., SIGIR 2020); it follows ptr_mhsa_forward's
+ * conventions (heads are column blocks of width d_h = F / n_heads; fp32; no [Lq][Lk] tensor is written):
+ *
+ *     O[b][i][h] = sum_j softmax_j( Q[b][i][h] . K[b][j][h] / sqrt(d_h) ) V[b][j][h],    i < Lq, j < Lk,
+ *     lse[b][h][i] = log sum_j exp( Q[b][i][h] . K[b][j][h] / sqrt(d_h) )                (the only side output, [B][n_heads][Lq])
+ *
+ *   lens_k (nullable, [B]): keys j >= lens_k[b] are excluded from the softmax and their dK / dV rows are exact zeros.
+ *   lens_q (nullable, [B]): query rows i >= lens_q[b] give O = 0 and lse = 0 exactly, contribute nothing to dK / dV, and their dQ rows are
+ *   exact zeros.  A query row with no key (lens_k[b] <= 0) gives O = 0 and lse = 0 as well.  Lengths are clamped to 0 .. Lq / Lk.  There is
+ *   no dropout on the probabilities.
+ *   Q: rows of stride ld_q >= F; query b's rows start at Q + b * q_batch_stride (floats).  q_batch_stride = 0 shares ONE [Lq][ld_q] Q among
+ *   all queries (the projected inducing points).  K, V: [B][Lk] rows of stride ld_kv >= F; ld_kv = 2F with K = base, V = base + F serves one
+ *   packed K|V projection, and dK, dV are written with the same stride (so dK|dV is that projection's gradient).  O, dO, dQ are
+ *   [B][Lq][F]: the backward always writes one dQ per query, and the caller sums over b when Q was shared.  dvec: [B * n_heads * Lq] floats
+ *   of scratch (D = rowsum(O * dO)).  O and lse passed to the backward must be the forward's.  Every element of O, lse, dQ, dK, dV is written.
+ *   Contract: min(Lq, Lk) <= 64 (the short side is held in LDS, the long side streams and is bounded by B * n_heads * L < 2^31 only) and
+ *   d_h <= 128; anything else is PTR_ERR_UNSUPPORTED.  Lk <= 64 runs the short-keys form, otherwise Lq <= 64 runs the short-queries form.
+ *   PTR_ERR_INVALID_ARG (before any launch, no device needed): B < 0, a size <= 0, F % n_heads != 0, a row stride below F, a negative
+ *   q_batch_stride, a NULL pointer other than lens_q / lens_k.  B = 0 is a no-op.
+ *   Determinism: no atomics; the cross-wave sums have a fixed order, so a query's bits depend on its own data and (Lq, Lk, F, n_heads) only. */
+int ptr_xattn_forward(const float *Q, int ld_q, int64_t q_batch_stride, const float *K, const float *V, int ld_kv, const int32_t *lens_q,
+                      const int32_t *lens_k, int B, int Lq, int Lk, int F, int n_heads, float *O, float *lse, void *stream);
+int ptr_xattn_backward(const float *Q, int ld_q, int64_t q_batch_stride, const float *K, const float *V, int ld_kv, const int32_t *lens_q,
+                       const int32_t *lens_k, int B, int Lq, int Lk, int F, int n_heads, const float *O, const float *dO, const float *lse,
+                       float *dvec, float *dQ, float *dK, float *dV, void *stream);
 
 /* ---- LETOR / libsvm text input (HOST buffers; the data format feeding the path) ---------------------------------------
  * Replaces the pure-Python tokenizer ptranking/data/data_utils.py:276-387 (iter_lines / parse_letor):

@@ -43,5 +43,7 @@ from .rankers import (ApproxNDCG, LambdaLoss, LambdaRank, ListMLE, ListNet, Rank
                       SmoothMetric, ProbSmoothMetric, NeuralNDCG, DEFAULT_PARAS, EXTRA_RANKER_NAMES, METRIC_RANKER_NAMES, PROB_RANKER_NAMES, RANKER_NAMES,
                       SORT_RANKER_NAMES,
                       make_ranker_classes)
+from . import setrank                                # noqa: F401
+from .setrank import SetRank                         # noqa: F401
 
 __version__ = "0.1.0"

@@ -72,6 +72,8 @@ static const FormQuery kFormQueries[] = {
      [](const int64_t *a, int32_t *out) { put(out, lambdaloss_form((int)a[0], (int)a[1], (int)a[2], (int)a[3], a[4] != 0)); }},
     {"ptr_mhsa_forward", 5, 6, ask_attention},
     {"ptr_mhsa_backward", 5, 6, ask_attention},
+    {"ptr_xattn_forward", 3, 4, [](const int64_t *a, int32_t *out) { put(out, xattn_form((int)a[0], (int)a[1], (int)a[2])); }},
+    {"ptr_xattn_backward", 3, 4, [](const int64_t *a, int32_t *out) { put(out, xattn_form((int)a[0], (int)a[1], (int)a[2])); }},
     {"ptr_layernorm_forward", 2, 3, ask_layernorm},
     {"ptr_layernorm_backward", 2, 3, ask_layernorm},
     {"ptr_wassrank_fwd_bwd", 1, 2, [](const int64_t *a, int32_t *out) { put(out, wassrank_form((int)a[0])); }},

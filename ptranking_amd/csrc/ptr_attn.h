@@ -40,6 +40,91 @@ __device__ __forceinline__ float xor_sum(float v) {
     return v + __shfl_xor(v, 32);
 }
 
+// One MFMA operand (16 rows x head dimension) held in registers in k-slot order: v[blk][c] <-> d = 16*blk + 4*g + c,
+// t[i] <-> d = 16*nb + 4*i + g (the dh % 16 tail).  Loaded once from an LDS tile row (row = tile row of lane j).
+template <int DT>
+struct OperandRegs {
+    f32x4 v[DT];
+    float t[3];
+    __device__ __forceinline__ void load(const float *row, int nb, int rem, int g) {
+#pragma unroll
+        for (int blk = 0; blk < DT; ++blk) v[blk] = blk < nb ? *reinterpret_cast<const f32x4 *>(row + 16 * blk + 4 * g) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 3; ++i) t[i] = i < rem ? row[16 * nb + 4 * i + g] : 0.0f;
+    }
+    // Same operand straight from global memory (row = this lane's row of the head's column block; rows that do not exist
+    // are passed as a valid clamped pointer with ok = false).  Columns >= dh read as zero.
+    __device__ __forceinline__ void load_global(const float *row, bool ok, int dh, int nb, int rem, int g, bool vec) {
+        const float m = ok ? 1.0f : 0.0f;
+#pragma unroll
+        for (int blk = 0; blk < DT; ++blk) {
+            f32x4 x = {0.f, 0.f, 0.f, 0.f};
+            if (blk < nb) {
+                const int c = 16 * blk + 4 * g;
+                if (vec) x = *reinterpret_cast<const f32x4 *>(row + c);
+                else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) x[e] = row[c + e < dh ? c + e : 0] * (c + e < dh ? 1.0f : 0.0f);
+                }
+            }
+            v[blk] = x * m;
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int d = 16 * nb + 4 * i + g;
+            t[i] = i < rem ? row[d < dh ? d : 0] * ((d < dh) ? m : 0.0f) : 0.0f;
+        }
+    }
+};
+
+// acc[ib][ia][r] = sum_d A[a_row0 + 16*ia + 4*g + r][d] * B_ib[j][d]:  NA A-tiles read from LDS (one ds_read_b128 per tile and
+// 4 k-steps), NB B-operands from registers.  NA*NB independent accumulators keep the MFMA pipe free of dependent chains.
+template <int DT, int NA, int NB>
+__device__ __forceinline__ void multi_dot(const float *As, int a_row0, int ld, int nb, int rem, int j, int g,
+                                          const OperandRegs<DT> (&b)[NB], f32x4 (&acc)[NB][NA]) {
+#pragma unroll
+    for (int ib = 0; ib < NB; ++ib)
+#pragma unroll
+        for (int ia = 0; ia < NA; ++ia) acc[ib][ia] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float *ap = As + (size_t)(a_row0 + j) * ld;
+#pragma unroll
+    for (int blk = 0; blk < DT; ++blk) {
+        if (blk < nb) {
+            f32x4 a[NA];
+#pragma unroll
+            for (int ia = 0; ia < NA; ++ia) a[ia] = *reinterpret_cast<const f32x4 *>(ap + (size_t)16 * ia * ld + 16 * blk + 4 * g);
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int ia = 0; ia < NA; ++ia)
+#pragma unroll
+                    for (int ib = 0; ib < NB; ++ib) acc[ib][ia] = mfma4(a[ia][c], b[ib].v[blk][c], acc[ib][ia]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (i < rem) {
+            const int d = 16 * nb + 4 * i + g;
+#pragma unroll
+            for (int ia = 0; ia < NA; ++ia) {
+                const float av = ap[(size_t)16 * ia * ld + d];
+#pragma unroll
+                for (int ib = 0; ib < NB; ++ib) acc[ib][ia] = mfma4(av, b[ib].t[i], acc[ib][ia]);
+            }
+        }
+    }
+}
+
+// The kernel form of ptr_xattn_forward / ptr_xattn_backward (xattn.hip: attention with Lq != Lk, one side of at most kXattnMaxShort rows
+// resident in LDS).  short_q: 0 the keys are the short side, 1 the queries (both short: the keys).  D column tiles of the head, MT row tiles
+// of the short side the kernel is compiled for (1, 2 or 4), 4 waves per workgroup.
+constexpr int kXattnMaxShort = 64;
+struct XattnForm { int short_q; int D; int waves; int MT; };
+inline XattnForm xattn_form(int Lq, int Lk, int dh) {
+    const int sq = Lk <= kXattnMaxShort ? 0 : 1, m = sq ? Lq : Lk;
+    return {sq, (dh + 15) / 16, 4, m <= 16 ? 1 : m <= 32 ? 2 : 4};
+}
+
 // The kernel form of ptr_mhsa_forward / ptr_mhsa_backward.  Narrow (dh <= 128): D = ceil(dh / 16) column tiles, the whole head in registers;
 // two row tiles per forward wave (every K / V operand read feeds two MFMAs) when the rows exist and the registers allow it; 4 waves per
 // workgroup (two workgroups share a CU, one's barrier / staging phases covered by the other's MFMA work) except the dK / dV kernel of the
