@@ -549,6 +549,33 @@ int ptr_mdprank_sample_fwd_bwd(const float *preds, const float *labels, const in
                                float temperature, int distribution, uint64_t seed, int64_t q0, const float *unif, float *loss_out,
                                float *loss_q, float *grad, int64_t *perm_out, void *stream);
 
+/* ---- PL-Rank (csrc/plrank.hip).  The symbol below is ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
+ * ptr_plrank_fwd_bwd — the sample mean of a top-K reward under a Plackett-Luce ranking policy and the PL-Rank estimate of its gradient
+ * (Oosterhuis, "Computationally Efficient Optimization of Plackett-Luce Ranking Models", SIGIR 2021; the PL-Rank-3 form of "Learning-to-Rank
+ * at the Speed of Sampling", SIGIR 2022), sampling included, in one launch.  The rule is this project's own statement; nothing is compared
+ * with the authors' code.  Per query with n = lens[q] real documents, scores s, gains rho_i = 2^label_i - 1:
+ *   K = top_k (n when top_k <= 0 or top_k > n);  theta_k = 1 / log2(k + 2) for k = 0 .. K-1, divided by the ideal DCG@K of the labels when
+ *   normalize != 0 (a query whose ideal DCG is 0 gives value 0 and gradient 0);  e_i = exp(s_i - max_j s_j).
+ *   A sample y is a full permutation drawn as ptr_pl_sample(..., PTR_PL_DIST_PL, temperature = 1) draws it: the uniforms u(seed, q0 + q,
+ *   sample, i) (or unif [B,S,L] when given), key s_i + g_i, order (key descending, index ascending).  Along y, positions p = 0 .. n-1:
+ *     D_p  = sum_{x >= p} e_{y_x}                      (a suffix sum of positive terms, never "total minus prefix")
+ *     PR_p = sum_{x = p}^{K-1} theta_x rho_{y_x},  PR_K = 0
+ *     RI_p = sum_{x <= p} PR_x / D_x,   DR_p = sum_{x <= p} theta_x / D_x     for p < K;   c(p) = min(p, K-1)
+ *     g_{y_p} = [p < K] PR_{p+1} + e_{y_p} (rho_{y_p} DR_{c(p)} - RI_{c(p)})
+ *   The probability-weighted mean of g over the rankings is the exact gradient of the expected reward.
+ *   Outputs: value_q [B] = (1/S) sum_s sum_{p < K} theta_p rho_{y_p};  grad [B,L] = -(1/S) sum_s g (the gradient of the loss -reward; padded
+ *   slots exactly 0);  loss_out [1] = -sum_q value_q (nullable);  perm_out int64 [B,S,L] (nullable), ptr_pl_sample's perm bit for bit.
+ *   n = 0: value 0, gradient 0.  All labels 0: gradient exactly 0.  A NaN score: NaN value and NaN gradient on the real positions of that
+ *   list, perm the identity.  exp is fp32: scores spread over more than ~87 units inside the top K overflow 1 / D.
+ *   Lists of up to PLRANK_MAX_LEN = 1024 documents.  One workgroup per query, min(S, 4) wavefronts sharing its samples; a ranking lives in
+ *   one wavefront's registers, the scans run there; LDS (3 + 3 waves) x 256 ceil(L / 64 -> 1, 2, 4, 8, 16) bytes + 16 (ptr_launch_form).  No
+ *   atomics: a query's bits depend on (its data, L, S, seed, q0 + q) alone, in any batch and on every run.
+ *   PTR_ERR_INVALID_ARG (before any HIP call): B < 0, L <= 0, L > 1024, S < 1, and with B > 0 a NULL preds / labels / value_q / grad.  B = 0
+ *   launches nothing and returns 0. */
+int ptr_plrank_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, int S, int top_k, int normalize,
+                       uint64_t seed, int64_t q0, const float *unif, float *loss_out, float *value_q, float *grad, int64_t *perm_out,
+                       void *stream);
+
 /* ---- The adversarial frame's IRGAN point and pair machines (csrc/irgan.hip): sampling documents from the generator's distribution and the
  * two players' losses.  The three symbols below are ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
  * Reference: ptranking/ltr_adversarial/pointwise/irgan_point.py, ptranking/ltr_adversarial/pairwise/irgan_pair.py, one query per step there;
@@ -1066,6 +1093,8 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *   ptr_neuralndcg_fwd_bwd                       L, iters                                 resident (1: K in LDS, 0: recomputed), G, history in
  *                                                                                           LDS, LDS bytes and workspace bytes per query, the
  *                                                                                           longest list of the resident form (the cut-over)
+ *   ptr_plrank_fwd_bwd                           L, S                                     DPT (positions per lane), wavefronts per query, LDS
+ *                                                                                           bytes per query
  *   ptr_alphadcg_fwd_bwd                         T, L                                     G, TP
  *   ptr_div_metrics_at_ks                        L                                        G, DPT
  *   ptr_divprob_fwd_bwd                          objective, T, L                          G, TP

@@ -151,6 +151,11 @@ constexpr int kNeuralMaxIters = 65535;
 constexpr size_t kNeuralLdsBytes = 160 * 1024;
 struct NeuralForm { int resident; int G; int hist_lds; int lds_bytes; int ws_bytes; int cutover; };
 NeuralForm neuralndcg_form(int L, int iters);
+// PL-Rank (plrank.hip): positions per lane (pick_wave_tiling's DPT), the wavefronts that share a query's samples, LDS bytes per query
+constexpr int kPlrankMaxLen = 1024;
+constexpr int kPlrankMaxWaves = 4;
+struct PlrankForm { int DPT; int waves; int lds_bytes; };
+PlrankForm plrank_form(int L, int S);
 // The tree frame's ragged kernels (tree.hip), by the longest launched list: G threads per query (16 up to 16 documents, pick_tiling's
 // beyond), kBlock / G queries per workgroup, and the documents one thread owns in the kernels that keep them in registers (pick_tiling's
 // DPT: G * DPT covers the launch's longest list)

@@ -29,7 +29,8 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "GBDT_RECORD", "gbdt_predict_leaf", "gbdt_leaf_sums", "gbdt_add_by_leaf", "gbdt_quantize_low", "gbdt_quant_levels", "gbdt_leaf_sums_rows",
            "gbdt_dart_pack", "gbdt_dart_walk", "gbdt_dart_select", "gbdt_dart_scale",
            "gbdt_linear_items", "gbdt_linear_moments", "gbdt_linear_solve", "gbdt_predict_linear", "gbdt_add_tree_linear", "GBDT_LINEAR_MAX_FEATURES",
-           "GBDT_LINEAR_CHUNK_ROWS", "GBDT_LINEAR_STATUS", "neuralndcg_form", "NEURALNDCG_MAX_LEN"]
+           "GBDT_LINEAR_CHUNK_ROWS", "GBDT_LINEAR_STATUS", "neuralndcg_form", "NEURALNDCG_MAX_LEN",
+           "plrank_objective", "plrank_form", "PLRANK_MAX_LEN"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
 # launch table, and it draws its own; irfgan_loss and adlist_loss are public too: they take a mode, as irgan_selected does; neuralndcg_loss
@@ -568,6 +569,47 @@ def mdprank_sampled_loss(preds, labels, top_k=10, gamma=1.0, temperature=1.0, di
                   [labels, lens, B, L, S, int(top_k) if top_k else 0, C.c_float(float(gamma)), C.c_float(float(temperature)), dist, _seed64(seed),
                    C.c_int64(int(q0)), unif], own_loss=True, tail=(perm,))[0]
     return (loss, perm) if return_perm else loss
+
+
+PLRANK_MAX_LEN = 1024                                                      # kPlrankMaxLen, csrc/ptr_device.h
+
+
+def plrank_form(L, samples):
+    """ptr_launch_form of ptr_plrank_fwd_bwd -> dict(DPT, waves, lds_bytes): positions per lane, the wavefronts that share a query's samples,
+    LDS bytes per query.  No GPU."""
+    a, out = (C.c_int64 * 2)(int(L), int(samples)), (C.c_int32 * 3)()
+    if _lib.load().ptr_launch_form(b"ptr_plrank_fwd_bwd", a, 2, out, 3) != 0:
+        raise RuntimeError(_lib.load().ptr_last_error().decode())
+    return dict(zip(("DPT", "waves", "lds_bytes"), out))
+
+
+def plrank_objective(preds, labels, samples=32, top_k=10, normalize=True, seed=0, q0=0, lens=None, unif=None, return_parts=False):
+    """PL-Rank (Oosterhuis 2021 / 2022; the rule is stated in include/ptranking_amd.h): minus the (n)DCG@top_k of `samples` rankings drawn per
+    query from the Plackett-Luce policy exp(preds), as sample_rankings_pl(preds, samples, seed=seed, q0=q0) draws them, averaged over the
+    samples and summed over the queries.  Its backward hands out the PL-Rank estimate of the gradient of the EXPECTED reward (unbiased; not
+    the derivative of the sampled value, which is piecewise constant).  top_k None or 0: the whole list; normalize: divide by the ideal
+    DCG@top_k; `unif` float32 [B, samples, L] replaces the generator.  Lists of up to 1024 documents.  With return_parts also returns
+    dict(value_q [B], grad [B, L] (of the loss, at upstream gradient 1), perm int64 [B, samples, L])."""
+    if isinstance(preds, torch.Tensor) and preds.dim() == 2 and preds.shape[1] > PLRANK_MAX_LEN:
+        raise ValueError(f"ranking_size {preds.shape[1]} exceeds the supported maximum {PLRANK_MAX_LEN} of plrank_objective")
+    preds_c, labels, lens, B, L = _batch(preds.detach(), labels, lens)
+    S = _pl_samples(samples)
+    unif = _pl_unif(unif, B, S, L, preds_c.device)
+    perm = torch.empty((B, S, L), device=preds_c.device, dtype=torch.int64) if return_parts else None
+    dev, parts = preds_c.device, {}
+
+    def launch(x):                                                           # _fused's launch, keeping the gradient for return_parts
+        value_q, grad = torch.empty(max(B, 1), device=dev), torch.empty((B, L), device=dev)
+        out = torch.zeros(1, device=dev)                                     # an empty batch launches nothing: the loss is 0
+        with torch.cuda.device(dev):
+            _lib.call("ptr_plrank_fwd_bwd", _lib.ptr(x), _lib.ptr(labels), _lib.ptr(lens), B, L, S, int(top_k) if top_k else 0,
+                      int(bool(normalize)), _seed64(seed), C.c_int64(int(q0)), _lib.ptr(unif), _lib.ptr(out), _lib.ptr(value_q), _lib.ptr(grad),
+                      _lib.ptr(perm), _lib.current_stream(dev))
+        parts.update(value_q=value_q[:B], grad=grad, perm=perm)
+        return out.reshape(()), grad
+
+    loss = _FusedLoss.apply(launch, preds.contiguous()) if preds.requires_grad else launch(preds_c)[0]
+    return (loss, parts) if return_parts else loss
 
 
 def _irgan_samples(samples_per_query):

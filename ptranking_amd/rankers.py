@@ -38,6 +38,9 @@ PROB_RANKER_NAMES = ("ProbSmoothMetric",)
 # NeuralNDCG (NeuralSort + Sinkhorn scaling; the rule is this project's own, modelled on allRank's neuralNDCG): no reference class to rebind by
 # default either: bound only by install(names=RANKER_NAMES + SORT_RANKER_NAMES), pa.NeuralNDCG
 SORT_RANKER_NAMES = ("NeuralNDCG",)
+# PL-Rank (the policy-gradient estimator of a Plackett-Luce ranking policy's expected (n)DCG@k; the rule is this project's own statement): no
+# reference class either: bound only by install(names=RANKER_NAMES + POLICY_RANKER_NAMES), pa.PLRank
+POLICY_RANKER_NAMES = ("PLRank",)
 PROB_SORT_IDS = ('ExpRele', 'RiskAware', 'RERAR')       # ptranking/ltr_diversification/base/div_mdn_ranker.py:43
 
 # default hyper-parameters = the reference's `default_para_dict()`s
@@ -60,6 +63,7 @@ DEFAULT_PARAS = {
     "ProbSmoothMetric": dict(model_id="ProbSmoothMetric", metric='nDCG', top_k=None, opt_ideal=True, limit_delta=0.01, const_std=None,
                              sort_id='ExpRele'),        # limit_delta, sort_id: ltr_diversification/score_and_sort/div_prob_ranker.py:387-389
     "NeuralNDCG": dict(model_id="NeuralNDCG", temperature=1.0, iters=50, top_k=None, powered=True),
+    "PLRank": dict(model_id="PLRank", samples=32, top_k=10, normalize=True),
 }
 
 
@@ -541,6 +545,28 @@ class MDPRankLoss(FusedStepMixin):
         return self._fused_step(loss)
 
 
+class PLRankLoss(FusedStepMixin):
+    samples, top_k, normalize = 32, 10, True
+    _pl_seed = 137            # ptranking/ltr_global.py:7
+    _pl_calls = 0
+    _query_offset = MDPRankLoss._query_offset
+
+    def uniform_eval_setting(self, **kwargs):
+        """Validate on the metric that is optimised (the pattern of approxNDCG.py:78-81)."""
+        eval_dict = kwargs['eval_dict']
+        if eval_dict["do_validation"] and not eval_dict['vali_metric'] == 'nDCG':
+            eval_dict['vali_metric'] = 'nDCG'
+
+    def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
+        """functional.plrank_objective: minus the sampled (n)DCG@top_k, its backward the PL-Rank gradient estimate.  Every step draws from a
+        seed of its own (the call count), every query from its global index: no two steps reuse uniforms.  The labels need no order."""
+        assert 'label_type' in kwargs and is_multilabel(kwargs['label_type'])
+        self._pl_calls += 1
+        return self._fused_step(F_.plrank_objective(batch_preds, batch_std_labels, samples=self.samples, top_k=self.top_k,
+                                                    normalize=self.normalize, seed=self._pl_seed * 0x9E3779B1 + self._pl_calls,
+                                                    q0=self._query_offset(batch_preds.size(0), kwargs), lens=kwargs.get('lens')))
+
+
 class ListNetLoss(FusedStepMixin):
     _direct_loss = _lib.LOSSES["listnet"]
 
@@ -776,9 +802,20 @@ def make_ranker_classes(base=PointScorerRanker):
             if not self.temperature > 0.0 or self.iters < 0:
                 raise ValueError(f"NeuralNDCG needs temperature > 0 and iters >= 0 (got {paras['temperature']!r}, {paras['iters']!r})")
 
+    class PLRank(PLRankLoss, FusedScorerMixin, FusedListScorerMixin, DeviceTrainLoop, DeviceEvaluator, base):
+        """PL-Rank as the training objective; model_para_dict: samples, top_k, normalize (each optional: DEFAULT_PARAS)."""
+
+        def __init__(self, sf_para_dict=None, model_para_dict=None, gpu=False, device=None):
+            base.__init__(self, id='PLRank', sf_para_dict=sf_para_dict, gpu=gpu, device=device)
+            paras = {**DEFAULT_PARAS['PLRank'], **(model_para_dict or {})}
+            self.samples, self.top_k, self.normalize = int(paras['samples']), paras['top_k'], bool(paras['normalize'])
+            if self.samples < 1:
+                raise ValueError(f"PLRank needs samples >= 1 (got {paras['samples']!r})")
+
     out = dict(RankNet=RankNet, LambdaRank=LambdaRank, LambdaLoss=LambdaLoss, ApproxNDCG=ApproxNDCG, ListNet=ListNet,
                ListMLE=ListMLE, STListNet=STListNet, RankCosine=RankCosine, RankMSE=RankMSE, SoftRank=SoftRank, WassRank=WassRank,
-               DASALC=DASALC, MDPRank=MDPRank, SmoothMetric=SmoothMetric, ProbSmoothMetric=ProbSmoothMetric, NeuralNDCG=NeuralNDCG)
+               DASALC=DASALC, MDPRank=MDPRank, SmoothMetric=SmoothMetric, ProbSmoothMetric=ProbSmoothMetric, NeuralNDCG=NeuralNDCG,
+               PLRank=PLRank)
     for name, cls in out.items():
         cls.__name__ = cls.__qualname__ = name
         cls.__module__ = __name__
@@ -794,3 +831,4 @@ WassRank = _standalone["WassRank"]
 SmoothMetric = _standalone["SmoothMetric"]
 ProbSmoothMetric = _standalone["ProbSmoothMetric"]
 NeuralNDCG = _standalone["NeuralNDCG"]
+PLRank = _standalone["PLRank"]
