@@ -576,6 +576,37 @@ int ptr_plrank_fwd_bwd(const float *preds, const float *labels, const int32_t *l
                        uint64_t seed, int64_t q0, const float *unif, float *loss_out, float *value_q, float *grad, int64_t *perm_out,
                        void *stream);
 
+/* ---- FastSoftRank (csrc/fastsoftrank.hip).  The symbol below is ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
+ * ptr_fastsoftrank_fwd_bwd — soft ranks as the Euclidean projection onto the permutahedron (Blondel, Teboul, Berthet, Djolonga, "Fast
+ * Differentiable Sorting and Ranking", ICML 2020; the L2 regulariser), a rank-space objective on them and its exact gradient, in one launch
+ * with O(L) state per query.  The rule is this project's own statement; nothing is compared with the authors' package.  Per query with
+ * n = lens[q] real documents (L where lens is NULL), scores theta in fp32, eps > 0:
+ *   1. z_i = fp32(-theta_i / eps), one IEEE division.  Everything after this is exact in z.
+ *   2. sigma sorts z descending, equal keys by the lower index; s = z_sigma, rho = (n, n-1, .., 1), u = s - rho in float64.
+ *   3. v = argmin over v_1 >= .. >= v_n of |v - u|^2: the non-increasing isotonic regression.  Two adjacent pools merge only on a STRICT
+ *      violation (left mean < right mean); pools of equal means stay apart.  The pools are the blocks.  The tie rule is part of the rule: the
+ *      Jacobian is discontinuous there.  Computed in the cumulative-sum form: S_k = sum_{i <= k} u_i, g(j) = max_{k > j} (S_k - S_j) / (k - j),
+ *      v_i = min_{j < i} g(j); a block starts at position j + 1 exactly where g(j) is strictly below the minimum of g(0 .. j-1).
+ *   4. soft rank r_{sigma(i)} = s_i - v_i, stored as fp32 of the float64 difference.  eps -> 0: the hard rank (1 = best); eps large: every
+ *      document gets (n + 1) / 2.  Documents of equal score always share a block and a rank.
+ *   5. objective, summed over the batch:  PTR_FSR_SPEARMAN: 1/2 sum_i (r_i - r*_i)^2, r* the fractional hard ranks of the labels descending
+ *      (ties take the mean of their positions);  PTR_FSR_NDCG: -(sum_i (2^{y_i} - 1) / log2(1 + r_i)) / IDCG, IDCG over the whole list, no
+ *      cut-off (a truncation in soft-rank space is not differentiable); a query without a relevant document gives loss 0 and gradient 0.
+ *   6. backward: with a_i = dloss/dr in sorted positions, dloss/dz in sorted positions is a_i minus the mean of a over i's block;
+ *      dloss/dtheta = -(1/eps) times that, scattered back through sigma.
+ *   7. a query of 0 documents: loss 0, rank and gradient rows of zeros.  Padded positions: rank 0, gradient 0.  A query holding a NaN score (or a key
+ *      z that is not finite in fp32): NaN loss, NaN rank and NaN gradient on every real document (the policy of the LambdaLoss kernels); no other query is touched.
+ *   Outputs: loss_q [B];  ranks [B,L] (nullable);  grad [B,L] (nullable: forward only);  loss_out [1] = sum_q loss_q (nullable).
+ *   Lists of up to PTR_MAX_LIST_LEN = 4096 documents.  One wavefront per query (four queries per workgroup) up to the cut-over, a 256-thread
+ *   workgroup per query beyond (ptr_launch_form); 28 round_up(L, 4) + 160 bytes of LDS per query; S, g and the block means in fp64.  No
+ *   atomics: a query's bits depend on (its data, L) alone, in any batch and on every run.
+ *   PTR_ERR_INVALID_ARG (before any HIP call): B < 0, L <= 0, eps not a finite number > 0, an unknown objective, and with B > 0 a NULL
+ *   preds / labels / loss_q; PTR_ERR_UNSUPPORTED: L > PTR_MAX_LIST_LEN.  B = 0 launches no query kernel. */
+#define PTR_FSR_SPEARMAN 0
+#define PTR_FSR_NDCG 1
+int ptr_fastsoftrank_fwd_bwd(const float *preds, const float *labels, const int32_t *lens, int B, int L, float eps, int objective,
+                             float *loss_out, float *loss_q, float *ranks, float *grad, void *stream);
+
 /* ---- The adversarial frame's IRGAN point and pair machines (csrc/irgan.hip): sampling documents from the generator's distribution and the
  * two players' losses.  The three symbols below are ADDITIVE to ABI v8 as well: PTR_ABI_VERSION stays 8.
  * Reference: ptranking/ltr_adversarial/pointwise/irgan_point.py, ptranking/ltr_adversarial/pairwise/irgan_pair.py, one query per step there;
@@ -1095,6 +1126,9 @@ int ptr_layernorm_backward(const float *X, const float *a2, const float *dY, con
  *                                                                                           longest list of the resident form (the cut-over)
  *   ptr_plrank_fwd_bwd                           L, S                                     DPT (positions per lane), wavefronts per query, LDS
  *                                                                                           bytes per query
+ *   ptr_fastsoftrank_fwd_bwd                     L                                        G (64: one wavefront per query, 256: the workgroup),
+ *                                                                                           DPT, queries per workgroup, LDS bytes per workgroup,
+ *                                                                                           the longest list of the wavefront form (the cut-over)
  *   ptr_alphadcg_fwd_bwd                         T, L                                     G, TP
  *   ptr_div_metrics_at_ks                        L                                        G, DPT
  *   ptr_divprob_fwd_bwd                          objective, T, L                          G, TP

@@ -25,7 +25,9 @@
                 training objective), which the reference has no class for; install(names=RANKER_NAMES + PROB_RANKER_NAMES) adds
                 ProbSmoothMetric (the same four objectives on Gaussian expected ranks, a mean and a variance per document);
                 install(names=RANKER_NAMES + SORT_RANKER_NAMES) adds NeuralNDCG (nDCG on the NeuralSort relaxation with Sinkhorn scaling);
-                install(names=RANKER_NAMES + POLICY_RANKER_NAMES) adds PLRank (the PL-Rank policy gradient of a Plackett-Luce ranking policy)
+                install(names=RANKER_NAMES + POLICY_RANKER_NAMES) adds PLRank (the PL-Rank policy gradient of a Plackett-Luce ranking policy);
+                install(names=RANKER_NAMES + PROJ_RANKER_NAMES) adds FastSoftRank (Spearman / soft nDCG on soft ranks that are the projection
+                onto the permutahedron: O(L) state, lists of up to 4096 documents)
 
 The only compute implementation is the HIP library ptranking_amd/libptranking_amd.so (C ABI: include/ptranking_amd.h);
 there is no CPU fallback.  Build it with `python -m ptranking_amd.build`.
@@ -42,7 +44,7 @@ from .tree import TreeObjective                     # noqa: F401
 from .diversity import DALETOR, DIV_RANKER_NAMES, EXTRA_DIV_RANKER_NAMES, DivProbRanker, DivQueryBatches     # noqa: F401
 from .rankers import (ApproxNDCG, LambdaLoss, LambdaRank, ListMLE, ListNet, RankNet, STListNet, RankCosine, RankMSE, SoftRank, WassRank, DASALC, MDPRank,  # noqa: F401
                       SmoothMetric, ProbSmoothMetric, NeuralNDCG, DEFAULT_PARAS, EXTRA_RANKER_NAMES, METRIC_RANKER_NAMES, PROB_RANKER_NAMES, RANKER_NAMES,
-                      SORT_RANKER_NAMES, POLICY_RANKER_NAMES, PLRank,
+                      SORT_RANKER_NAMES, POLICY_RANKER_NAMES, PLRank, PROJ_RANKER_NAMES, FastSoftRank,
                       make_ranker_classes)
 from . import setrank                                # noqa: F401
 from .setrank import SetRank                         # noqa: F401

@@ -52,6 +52,7 @@ SIGNATURES = {
     "ptr_pl_sample": [_vp, _vp, _i, _i, _i, _f, _i, _u64, C.c_int64, _vp, _vp, _vp, _vp],
     "ptr_mdprank_sample_fwd_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp],
     "ptr_plrank_fwd_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ptr_fastsoftrank_fwd_bwd": [_vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp],
     "ptr_irgan_sample": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp],
     "ptr_irgan_point_gen_fwd_bwd": [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _i, _u64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ptr_irgan_sel_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],

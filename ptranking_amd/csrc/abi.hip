@@ -79,6 +79,7 @@ static const FormQuery kFormQueries[] = {
     {"ptr_wassrank_fwd_bwd", 1, 2, [](const int64_t *a, int32_t *out) { put(out, wassrank_form((int)a[0])); }},
     {"ptr_neuralndcg_fwd_bwd", 2, 6, [](const int64_t *a, int32_t *out) { put(out, neuralndcg_form((int)a[0], (int)a[1])); }},
     {"ptr_plrank_fwd_bwd", 2, 3, [](const int64_t *a, int32_t *out) { put(out, plrank_form((int)a[0], (int)a[1])); }},
+    {"ptr_fastsoftrank_fwd_bwd", 1, 5, [](const int64_t *a, int32_t *out) { put(out, fastsoftrank_form((int)a[0])); }},
     {"ptr_alphadcg_fwd_bwd", 2, 2, [](const int64_t *a, int32_t *out) { put(out, div_form((int)a[0], (int)a[1])); }},
     {"ptr_div_metrics_at_ks", 1, 2, [](const int64_t *a, int32_t *out) { put(out, pick_tiling((int)a[0])); }},
     {"ptr_divprob_fwd_bwd", 3, 2, [](const int64_t *a, int32_t *out) { put(out, divprob_form((int)a[0], (int)a[1], (int)a[2])); }},

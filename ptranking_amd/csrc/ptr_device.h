@@ -156,6 +156,11 @@ constexpr int kPlrankMaxLen = 1024;
 constexpr int kPlrankMaxWaves = 4;
 struct PlrankForm { int DPT; int waves; int lds_bytes; };
 PlrankForm plrank_form(int L, int S);
+// FastSoftRank (fastsoftrank.hip): G threads per query (64: one wavefront, up to kFsrWaveMaxLen documents; 256 beyond), documents per thread,
+// queries per workgroup, LDS bytes per workgroup, the cut-over (the longest list of the wavefront form)
+constexpr int kFsrWaveMaxLen = 128;
+struct FsrForm { int G; int DPT; int QPB; int lds_bytes; int cutover; };
+FsrForm fastsoftrank_form(int L);
 // The tree frame's ragged kernels (tree.hip), by the longest launched list: G threads per query (16 up to 16 documents, pick_tiling's
 // beyond), kBlock / G queries per workgroup, and the documents one thread owns in the kernels that keep them in registers (pick_tiling's
 // DPT: G * DPT covers the launch's longest list)

@@ -30,7 +30,8 @@ __all__ = ["ranknet_loss", "lambdarank_loss", "lambdaloss_loss", "approxndcg_los
            "gbdt_dart_pack", "gbdt_dart_walk", "gbdt_dart_select", "gbdt_dart_scale",
            "gbdt_linear_items", "gbdt_linear_moments", "gbdt_linear_solve", "gbdt_predict_linear", "gbdt_add_tree_linear", "GBDT_LINEAR_MAX_FEATURES",
            "GBDT_LINEAR_CHUNK_ROWS", "GBDT_LINEAR_STATUS", "neuralndcg_form", "NEURALNDCG_MAX_LEN",
-           "plrank_objective", "plrank_form", "PLRANK_MAX_LEN"]
+           "plrank_objective", "plrank_form", "PLRANK_MAX_LEN",
+           "fastsoftrank_objective", "soft_ranks", "fastsoftrank_form", "FASTSOFTRANK_MAX_LEN", "FASTSOFTRANK_OBJECTIVES"]
 
 # (mdprank_sampled_loss is public too; the *_loss names of __all__ are the losses that take their inputs as given, one row per loss of the
 # launch table, and it draws its own; irfgan_loss and adlist_loss are public too: they take a mode, as irgan_selected does; neuralndcg_loss
@@ -610,6 +611,59 @@ def plrank_objective(preds, labels, samples=32, top_k=10, normalize=True, seed=0
 
     loss = _FusedLoss.apply(launch, preds.contiguous()) if preds.requires_grad else launch(preds_c)[0]
     return (loss, parts) if return_parts else loss
+
+
+FASTSOFTRANK_MAX_LEN = _lib.MAX_LIST_LEN                                   # PTR_MAX_LIST_LEN: the kernel's state is O(L)
+FASTSOFTRANK_OBJECTIVES = {"spearman": 0, "nDCG": 1}                       # PTR_FSR_SPEARMAN, PTR_FSR_NDCG
+
+
+def fastsoftrank_form(L):
+    """ptr_launch_form of ptr_fastsoftrank_fwd_bwd -> dict(G, DPT, QPB, lds_bytes, cutover): threads per query (64: one wavefront, 256: the
+    workgroup), documents per thread, queries per workgroup, LDS bytes per workgroup, the longest list of the wavefront form.  No GPU."""
+    a, out = (C.c_int64 * 1)(int(L)), (C.c_int32 * 5)()
+    if _lib.load().ptr_launch_form(b"ptr_fastsoftrank_fwd_bwd", a, 1, out, 5) != 0:
+        raise RuntimeError(_lib.load().ptr_last_error().decode())
+    return dict(zip(("G", "DPT", "QPB", "lds_bytes", "cutover"), out))
+
+
+def _fastsoftrank_args(preds, eps, objective):
+    if objective not in FASTSOFTRANK_OBJECTIVES:
+        raise ValueError(f"objective must be one of {tuple(FASTSOFTRANK_OBJECTIVES)}, got {objective!r}")
+    if not float(eps) > 0.0 or not math.isfinite(float(eps)):
+        raise ValueError(f"eps must be a finite number > 0 (got {eps!r})")
+    if isinstance(preds, torch.Tensor) and preds.dim() == 2 and preds.shape[1] > FASTSOFTRANK_MAX_LEN:
+        raise ValueError(f"ranking_size {preds.shape[1]} exceeds the supported maximum {FASTSOFTRANK_MAX_LEN}")
+    return C.c_float(float(eps)), FASTSOFTRANK_OBJECTIVES[objective]
+
+
+def fastsoftrank_objective(preds, labels, eps=1.0, objective='nDCG', lens=None, return_parts=False):
+    """FastSoftRank (Blondel et al., ICML 2020, the L2 projection; the rule is stated in include/ptranking_amd.h): a rank-space objective on the
+    soft ranks r = the projection of -preds / eps onto the permutahedron (1 = best; eps -> 0 the hard ranks, eps large the mean rank), SUMMED
+    over the queries, with its exact gradient.  objective 'spearman': 1/2 sum (r - r*)^2 against the fractional hard ranks of the labels;
+    'nDCG': -(sum (2^y - 1) / log2(1 + r)) / IDCG over the whole list.  One launch, O(L) state: lists of up to 4096 documents.  A useful eps
+    is of the order of (score range) / L: far above it every document gets the mean rank and the gradient vanishes.  With return_parts also
+    returns dict(loss_q [B], ranks [B, L])."""
+    eps_c, obj = _fastsoftrank_args(preds, eps, objective)
+    preds_c, labels, lens, B, L = _batch(preds.detach(), labels, lens)
+    loss, parts = _fused("ptr_fastsoftrank_fwd_bwd", [preds], [preds_c], [labels, lens, B, L, eps_c, obj],
+                         slots=(("loss_q", None), ("ranks", max(B * L, 1))))
+    if return_parts:
+        parts["ranks"] = parts["ranks"][:B * L].view(B, L)
+        return loss, parts
+    return loss
+
+
+def soft_ranks(preds, eps=1.0, lens=None):
+    """The soft ranks of fastsoftrank_objective alone [B, L] (padded positions 0): forward only, through the same entry point."""
+    eps_c, _ = _fastsoftrank_args(preds, eps, "spearman")
+    preds_c, B, L = _matrix("preds", preds.detach() if isinstance(preds, torch.Tensor) else preds)
+    lens = _counts("lens", lens, B)
+    dev = preds_c.device
+    ranks, loss_q = torch.empty((B, L), device=dev), torch.empty(max(B, 1), device=dev)
+    with torch.cuda.device(dev):                                             # the labels enter the loss slot only: the scores stand in
+        _lib.call("ptr_fastsoftrank_fwd_bwd", _lib.ptr(preds_c), _lib.ptr(preds_c), _lib.ptr(lens), B, L, eps_c, 0, None, _lib.ptr(loss_q),
+                  _lib.ptr(ranks), None, _lib.current_stream(dev))
+    return ranks
 
 
 def _irgan_samples(samples_per_query):

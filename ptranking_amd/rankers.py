@@ -41,6 +41,9 @@ SORT_RANKER_NAMES = ("NeuralNDCG",)
 # PL-Rank (the policy-gradient estimator of a Plackett-Luce ranking policy's expected (n)DCG@k; the rule is this project's own statement): no
 # reference class either: bound only by install(names=RANKER_NAMES + POLICY_RANKER_NAMES), pa.PLRank
 POLICY_RANKER_NAMES = ("PLRank",)
+# FastSoftRank (soft ranks as the projection onto the permutahedron; the rule is this project's own statement): no reference class either:
+# bound only by install(names=RANKER_NAMES + PROJ_RANKER_NAMES), pa.FastSoftRank
+PROJ_RANKER_NAMES = ("FastSoftRank",)
 PROB_SORT_IDS = ('ExpRele', 'RiskAware', 'RERAR')       # ptranking/ltr_diversification/base/div_mdn_ranker.py:43
 
 # default hyper-parameters = the reference's `default_para_dict()`s
@@ -64,6 +67,7 @@ DEFAULT_PARAS = {
                              sort_id='ExpRele'),        # limit_delta, sort_id: ltr_diversification/score_and_sort/div_prob_ranker.py:387-389
     "NeuralNDCG": dict(model_id="NeuralNDCG", temperature=1.0, iters=50, top_k=None, powered=True),
     "PLRank": dict(model_id="PLRank", samples=32, top_k=10, normalize=True),
+    "FastSoftRank": dict(model_id="FastSoftRank", eps=1.0, objective='nDCG'),
 }
 
 
@@ -422,6 +426,17 @@ class NeuralNDCGLoss(FusedStepMixin):
         assert 'label_type' in kwargs and is_multilabel(kwargs['label_type'])
         return self._fused_step(F_.neuralndcg_loss(batch_preds, batch_std_labels, temperature=self.temperature, iters=self.iters,
                                                    top_k=self.top_k, powered=self.powered, lens=kwargs.get('lens')))
+
+
+class FastSoftRankLoss(FusedStepMixin):
+    eps, objective = 1.0, 'nDCG'
+    uniform_eval_setting = NeuralNDCGLoss.uniform_eval_setting
+
+    def custom_loss_function(self, batch_preds, batch_std_labels, **kwargs):
+        """functional.fastsoftrank_objective: Spearman or soft nDCG on the projection soft ranks, summed over the batch.  The labels need no order."""
+        assert 'label_type' in kwargs and is_multilabel(kwargs['label_type'])
+        return self._fused_step(F_.fastsoftrank_objective(batch_preds, batch_std_labels, eps=self.eps, objective=self.objective,
+                                                          lens=kwargs.get('lens')))
 
 
 class ProbSmoothMetricLoss(FusedStepMixin):
@@ -812,10 +827,20 @@ def make_ranker_classes(base=PointScorerRanker):
             if self.samples < 1:
                 raise ValueError(f"PLRank needs samples >= 1 (got {paras['samples']!r})")
 
+    class FastSoftRank(FastSoftRankLoss, FusedScorerMixin, FusedListScorerMixin, DeviceTrainLoop, DeviceEvaluator, base):
+        """FastSoftRank as the training objective; model_para_dict: eps, objective ('nDCG' | 'spearman') (each optional: DEFAULT_PARAS)."""
+
+        def __init__(self, sf_para_dict=None, model_para_dict=None, gpu=False, device=None):
+            base.__init__(self, id='FastSoftRank', sf_para_dict=sf_para_dict, gpu=gpu, device=device)
+            paras = {**DEFAULT_PARAS['FastSoftRank'], **(model_para_dict or {})}
+            self.eps, self.objective = float(paras['eps']), paras['objective']
+            if not self.eps > 0.0 or self.objective not in F_.FASTSOFTRANK_OBJECTIVES:
+                raise ValueError(f"FastSoftRank needs eps > 0 and objective in {tuple(F_.FASTSOFTRANK_OBJECTIVES)} (got {paras['eps']!r}, {paras['objective']!r})")
+
     out = dict(RankNet=RankNet, LambdaRank=LambdaRank, LambdaLoss=LambdaLoss, ApproxNDCG=ApproxNDCG, ListNet=ListNet,
                ListMLE=ListMLE, STListNet=STListNet, RankCosine=RankCosine, RankMSE=RankMSE, SoftRank=SoftRank, WassRank=WassRank,
                DASALC=DASALC, MDPRank=MDPRank, SmoothMetric=SmoothMetric, ProbSmoothMetric=ProbSmoothMetric, NeuralNDCG=NeuralNDCG,
-               PLRank=PLRank)
+               PLRank=PLRank, FastSoftRank=FastSoftRank)
     for name, cls in out.items():
         cls.__name__ = cls.__qualname__ = name
         cls.__module__ = __name__
@@ -832,3 +857,4 @@ SmoothMetric = _standalone["SmoothMetric"]
 ProbSmoothMetric = _standalone["ProbSmoothMetric"]
 NeuralNDCG = _standalone["NeuralNDCG"]
 PLRank = _standalone["PLRank"]
+FastSoftRank = _standalone["FastSoftRank"]
