@@ -70,8 +70,12 @@ def set_bits(words):
     return sum(int(w[k]) << (64 * k) for k in range(4))
 
 
-def cat_candidates(hf, nb, mbin, tot, expo, l2, min_data, min_hess, min_gain, cat_smooth, fault=None):
-    """The candidates of one categorical feature from its histogram hf [max_bin, 3] -> (list of (gain, key, left sums (3 ints), left set
+def cat_candidates(hf, nb, mbin, tot, expo, l2, min_data, min_hess, min_gain, cat_smooth, fault=None, exact_ties=False):
+    """exact_ties: two categories whose keys are EQUAL are not screened against each other.  A key is one exact addition or one rounding
+    (H_c + cat_smooth) and one correctly rounded division of exact inputs, with no product that a compiler could contract: equal integer
+    sums, a zero G_c, or proportional (G_c, H_c + cat_smooth) give the same bits here and on the device, and the lower code decides
+    (gbdt_ref.best_split treats twin gains so; low-bit quantized gradients make such twins an everyday event).  The screen stays for keys
+    that differ, however little.  The candidates of one categorical feature from its histogram hf [max_bin, 3] -> (list of (gain, key, left sums (3 ints), left set
     as a python int), the smallest relative gap of the screen: adjacent sort keys from each other, support values from cat_smooth)."""
     mb = hf.shape[0]
     cats = list(range(nb)) + ([mbin] if (nb <= mbin < mb and fault != "nan_ignored") else [])
@@ -94,7 +98,9 @@ def cat_candidates(hf, nb, mbin, tot, expo, l2, min_data, min_hess, min_gain, ca
     if u <= 1:
         return [], gap
     used.sort()                                                          # by the key, then the lower bin
-    for (a, _), (b, _) in zip(used[:-1], used[1:]):
+    for (a, ca), (b, cb) in zip(used[:-1], used[1:]):
+        if exact_ties and (a == b or tuple(hf[ca][:2]) == tuple(hf[cb][:2])):
+            continue
         gap = min(gap, abs(b - a) / max(abs(a), abs(b), 1e-300))
     mid = u // 2 if fault == "wrong_middle" else (u + 1) // 2
     G, Hn = np.ldexp(np.float64(TG), -expo[0]), H

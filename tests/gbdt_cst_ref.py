@@ -16,7 +16,10 @@ split on f keeps the active groups that contain f and may split on their union o
 unconstrained one, bit for bit.
 
 `fault` arguments plant one wrong rule each: "no_clamp" (values are never clamped), "mid_unclamped" (mid from the unclamped values),
-"swapped_neg" (under -1 the children get the bounds of +1), "inherit_all_groups" (a child keeps every group of its parent)."""
+"swapped_neg" (under -1 the children get the bounds of +1), "inherit_all_groups" (a child keeps every group of its parent).  Two more serve
+tests/gbdt_compose_ref.py, where the options meet (they are not in FAULTS: this file's fixture has no case they could change): "cat_row0_set"
+(a searched right child whose split is categorical takes the left set found for its left sibling, the empty set where that one found none)
+and "groups_after_cat" (a categorical split does not narrow the active groups)."""
 import os
 
 import numpy as np
@@ -107,7 +110,7 @@ def allowed_mask(groups, active, nf):
 
 # ---- the split scan
 def best_split(hist, nbins, nan_bin, is_cat, expo, l2=0.0, min_data=1, min_hess=1e-3, min_gain=0.0, cat_smooth=CAT_SMOOTH, mono=None, cst=None,
-               allowed=None, fault=None):
+               allowed=None, fault=None, exact_ties=False):
     """gbdt_cat_ref.best_split under the constraints.  mono int [F] with cst = (lo, hi, v): the bounded gain on every candidate (cst None: the
     unconstrained gain); allowed bool [F] or None.  -> its dict plus vl, vr (the winner's clamped child values under cst), changed (the
     winner differs from the one the same search finds without the order test: a rejection decided), gap (also the smallest relative
@@ -128,7 +131,8 @@ def best_split(hist, nbins, nan_bin, is_cat, expo, l2=0.0, min_data=1, min_hess=
         cands.append((float(gain[f, b, d]), f, b if d == 0 else 511 - b, tuple(int(v) for v in left[f, b, d]), False, 0))
     gap = np.inf
     for f in np.nonzero(is_cat)[0].tolist():
-        cc, g = CR.cat_candidates(hist[f], int(min(max(nbins[f], 1), mb)), int(nb_arr[f]), tot, expo, l2, min_data, min_hess, mg, cat_smooth)
+        cc, g = CR.cat_candidates(hist[f], int(min(max(nbins[f], 1), mb)), int(nb_arr[f]), tot, expo, l2, min_data, min_hess, mg, cat_smooth,
+                                  exact_ties=exact_ties)
         if allowed is None or allowed[f]:
             gap = min(gap, g)
         cands.extend((gn, f, key, lsum, True, bits) for gn, key, lsum, bits in cc)
@@ -176,8 +180,8 @@ margin = CR.margin
 
 # ---- leaf-wise growth (gbdt_cat_ref.grow_tree with the rules above)
 def grow_tree(bins, qg, qh, expo, edges, nbins, nan_bin, is_cat, max_bin, num_leaves, lr=0.1, l2=0.0, min_data=1, min_hess=1e-3, min_gain=0.0,
-              max_depth=-1, cat_smooth=CAT_SMOOTH, mono=None, groups=None, fault=None):
-    """mono: int [F] or None (all zeros counts as None); groups: a list of feature groups or None.  -> (tree dict as gbdt_cat_ref.grow_tree's,
+              max_depth=-1, cat_smooth=CAT_SMOOTH, mono=None, groups=None, fault=None, exact_ties=False):
+    """exact_ties: gbdt_cat_ref.cat_candidates' switch of the screen.  mono: int [F] or None (all zeros counts as None); groups: a list of feature groups or None.  -> (tree dict as gbdt_cat_ref.grow_tree's,
     the leaves' row lists, the smallest margin of any search, stats dict(changed: searches a rejection decided, clamped: leaves whose v is
     not -G / (H + l2), paths: the set of features on each leaf's path))."""
     n, nf = bins.shape[0], np.asarray(nbins).size
@@ -190,7 +194,7 @@ def grow_tree(bins, qg, qh, expo, edges, nbins, nan_bin, is_cat, max_bin, num_le
 
     def search(hist, cst, active):
         return best_split(hist, nbins, nan_bin, is_cat, expo, l2, min_data, min_hess, min_gain, cat_smooth, mono, cst if mono is not None else None,
-                          allowed_mask(groups, active, nf) if groups is not None else None, fault)
+                          allowed_mask(groups, active, nf) if groups is not None else None, fault, exact_ties)
 
     all_rows = np.arange(n, dtype=np.int32)
     tot = (int(qg.astype(np.int64).sum()), int(qh.astype(np.int64).sum()))
@@ -209,7 +213,7 @@ def grow_tree(bins, qg, qh, expo, edges, nbins, nan_bin, is_cat, max_bin, num_le
         if not s["gain"] > -np.inf:
             break
         out, cl = CR.partition(bins, leaf["rows"], s, nan_bin)
-        assert cl == s["left"][2]
+        assert cl == s["left"][2] or fault == "cat_row0_set"
         node = len(feature)
         f = s["feature"]
         feature.append(f); left.append(~li); right.append(~len(leaves)); go_left.append(s["default_left"])
@@ -226,7 +230,7 @@ def grow_tree(bins, qg, qh, expo, edges, nbins, nan_bin, is_cat, max_bin, num_le
         else:
             kid_cst = (None, None)
         active = leaf["active"]
-        if groups is not None and fault != "inherit_all_groups":
+        if groups is not None and fault != "inherit_all_groups" and not (fault == "groups_after_cat" and s["cat"]):
             active = tuple(g for g in active if f in groups[g])
         kids = [{"rows": rows, "depth": leaf["depth"] + 1, "parent": node, "side": side, "sums": sums[:2], "hist": None, "split": none,
                  "cst": kid_cst[side], "active": active, "path": leaf["path"] | {f}}
@@ -241,6 +245,8 @@ def grow_tree(bins, qg, qh, expo, edges, nbins, nan_bin, is_cat, max_bin, num_le
                     c["split"] = search(c["hist"], c["cst"], c["active"])
                     worst = min(worst, margin(c["split"]))
                     changed += int(c["split"]["changed"])
+            if fault == "cat_row0_set" and can[1] and kids[1]["split"]["cat"]:
+                kids[1]["split"] = dict(kids[1]["split"], set=kids[0]["split"]["set"] if can[0] and kids[0]["split"]["cat"] else 0)
         leaf["hist"] = None
         leaves[li] = kids[0]
         leaves.append(kids[1])
